@@ -374,6 +374,7 @@ def native_multi_measure(args) -> dict:
         md.infer_batch(ids, sid, ls)
     lat, samples, gms = [], 0, 0.0
     per_dev = [0] * N
+    pcm = []
     t0 = time.perf_counter()
     for _ in range(args.steps):
         ts = time.perf_counter()
@@ -384,6 +385,8 @@ def native_multi_measure(args) -> dict:
             samples += int(a_.size)
             per_dev[slot[u]] += int(a_.size)
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, [int(a_.size) for a_ in pcm], np.concatenate([np.asarray(a_).ravel() for a_ in pcm]) if pcm else [])
     steps = max(1, args.steps)
     out = {
         "metric": "audio samples/sec (acoustic model + vocoder, phoneme ids -> int16 PCM on host), single_speaker_fast-shaped synthetic blob",
@@ -405,6 +408,31 @@ def native_multi_measure(args) -> dict:
     }
     md.close()
     return out
+
+
+DUMP_MAX_BYTES = 64 << 20       # --dump-outputs: the files of one dump stay below this
+DUMP_SAMPLE_SEED = 1234
+
+
+def dump_outputs(out_dir: str, counts, pcm) -> None:
+    """--dump-outputs DIR: what a caller of the timed path received from its LAST timed step, as .npy files that two builds can be compared
+    with: sample_counts.npy (float64, per utterance, global utterance order) and pcm.npy (float32, the int16 PCM of all utterances
+    concatenated in that order; exact in float32).  A PCM larger than the budget is replaced by a fixed seeded sample of it: pcm.npy then
+    holds the sampled values and pcm_index.npy (float64) their positions."""
+    os.makedirs(out_dir, exist_ok=True)
+    counts = np.asarray(counts, np.float64).ravel()
+    pcm = np.asarray(pcm).ravel().astype(np.float32)
+    np.save(os.path.join(out_dir, "sample_counts.npy"), counts)
+    index_path = os.path.join(out_dir, "pcm_index.npy")
+    if os.path.exists(index_path):
+        os.remove(index_path)
+    budget = DUMP_MAX_BYTES - counts.nbytes - 4096
+    if pcm.nbytes > budget:
+        k = budget // (4 + 8)
+        idx = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(pcm.size, size=k, replace=False))
+        np.save(index_path, idx.astype(np.float64))
+        pcm = pcm[idx]
+    np.save(os.path.join(out_dir, "pcm.npy"), pcm)
 
 
 def _env_conv_math() -> str:
@@ -466,7 +494,12 @@ def main():
                     help="torch.distributed backend of the PCM gather: nccl (= RCCL, the product path) | gloo (tests: the "
                          "PCM goes through the host)")
     ap.add_argument("--share-gpu", action="store_true", help="tests only: every rank uses device 0 (needs --backend gloo)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned to its caller (per-utterance sample counts and the PCM, "
+                         "all utterances of the global batch) as DIR/*.npy; the inputs are the same from run to run for the same arguments")
     args = ap.parse_args()
+    if args.dump_outputs and args.steps < 1:
+        ap.error("--dump-outputs needs --steps >= 1")
     if args.config:
         pz = CONFIG_PRESETS[args.config]
         args.workload, args.batch, args.phonemes, args.ragged = pz["workload"], pz["batch"], pz["phonemes"], pz["ragged"]
@@ -538,6 +571,7 @@ def main():
     gq = None
     gather_busy = [0.0]
     gathered = [0]
+    last_gathered = [None]      # rank 0: the gathered PCM of the latest step (--dump-outputs)
     if dist is not None:
         import queue
         import threading
@@ -557,6 +591,7 @@ def main():
                 gather_busy[0] += time.perf_counter() - tg
                 if res is not None:
                     gathered[0] += sum(int(a_.size) for per_rank in res for a_ in per_rank)
+                    last_gathered[0] = res
                 gq.task_done()
         gth = threading.Thread(target=gather_worker, daemon=True)
         gth.start()
@@ -574,9 +609,12 @@ def main():
         return syn.prepare(fid, sid, ls) if (fid and hasattr(syn, "prepare")) else None
     fresh = [fresh_batch(j + 1) for j in range(max(args.steps, 32))] if prepared is not None else []
 
+    last_counts = [None]        # per-utterance sample counts of the latest step (--dump-outputs)
+
     def step(batch=None):
         batch = batch if batch is not None else prepared
         n_out = sharding.run_shard(syn, batch, None, None) if batch is not None else sharding.run_shard(syn, ids, sid, ls)
+        last_counts[0] = n_out
         total = int(n_out.sum()) if len(n_out) else 0
         if dist is None:
             pcm = syn.pcm_host(copy=False) if batch is not None else syn.pcm_host()
@@ -631,6 +669,17 @@ def main():
     drain_wait = time.perf_counter() - t_drain0
     sync()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs:
+        if dist is None:         # _pcm views the engine's download buffer: written out before any further step rewrites it
+            dump_outputs(args.dump_outputs, last_counts[0], _pcm)
+        elif rank == 0:          # the gathered PCM of the last timed step, per rank -> global utterance order
+            by_utt = {}
+            for r_, per_rank in enumerate(last_gathered[0]):
+                for u, a_ in zip(shards[r_], per_rank):
+                    by_utt[u] = np.asarray(a_).ravel()
+            order = sorted(by_utt)
+            dump_outputs(args.dump_outputs, [by_utt[u].size for u in order],
+                         np.concatenate([by_utt[u] for u in order]) if order else [])
     # ---- the same K steps on the canonical batch, which the warm-up has put into the memo: every step runs ahead of its frame count
     memo_hit_leg = None
     if fresh and dist is None and not stub:

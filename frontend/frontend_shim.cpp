@@ -1,7 +1,7 @@
 // frontend/frontend_shim.cpp -- C ABI over the REFERENCE's host text frontend.
 //
 // north_star keeps the text frontend (text normalisation -> word segmentation -> pinyin / IPA -> phoneme ids) on host C++:
-// this file is linked against the reference's own frontend classes compiled in place from /root/reference (frontend/Makefile;
+// this file is linked against the reference's own frontend classes compiled in place from /root/reference (oracle/frontend.mk;
 // nothing is copied) and exposes the two things libsummertts_hip.so needs from them:
 //   * stsfe_create      walks the frontend sections that follow the acoustic sections of a model blob and constructs the
 //                       frontend objects from them -- the section walk of /root/reference/src/models/SynthesizerTrn.cpp:165-297,

@@ -59,8 +59,8 @@ int ttsLoadModel(char* ttsModelName, float** ttsModel) {
 void tts_free_data(void* data) { free(data); }
 
 // ---- optional host text frontend -------------------------------------------------------------------
-// frontend/_ref/libsummertts_frontend.so = the reference's own TN / jieba / hanzi2phoneid / EnglishText2Id classes compiled
-// in place (frontend/Makefile) behind frontend/frontend_shim.cpp.  It is looked up at run time, never linked: a model blob
+// oracle/_ref/libsummertts_frontend.so = the reference's own TN / jieba / hanzi2phoneid / EnglishText2Id classes compiled
+// in place (oracle/frontend.mk) behind frontend/frontend_shim.cpp.  It is looked up at run time, never linked: a model blob
 // that carries frontend sections behind its acoustic sections gets a frontend (text in, as SynthesizerTrn.cpp:327-355);
 // a weights-only blob -- or a machine without the library -- keeps the phoneme-ids-as-text input.
 struct FrontendApi {
@@ -84,7 +84,7 @@ static FrontendApi& frontend_api() {
         const size_t sl = dir.find_last_of('/');
         dir = sl == std::string::npos ? std::string(".") : dir.substr(0, sl);
         cand.push_back(dir + "/libsummertts_frontend.so");
-        cand.push_back(dir + "/../../frontend/_ref/libsummertts_frontend.so");
+        cand.push_back(dir + "/../../oracle/_ref/libsummertts_frontend.so");
     }
     for (const std::string& path : cand) {
         void* h = dlopen(path.c_str(), RTLD_NOW | RTLD_LOCAL);
@@ -120,7 +120,7 @@ SynthesizerTrn::SynthesizerTrn(float* modelData, int32_t modelSize) {
         if (api.ok) p->fe = api.create(modelData, modelSize, info.blob_floats_consumed, info.lang_type);
         if (!p->fe)
             tts_log(TTS_LOG_ERROR, "SynthesizerTrn: the model carries text-frontend sections but libsummertts_frontend.so is not "
-                                   "available (frontend/Makefile); infer() takes phoneme ids as text\n");
+                                   "available (oracle/frontend.mk); infer() takes phoneme ids as text\n");
     }
 }
 

@@ -79,3 +79,39 @@ def test_multi_native_runs_in_one_process_and_reports_the_communicator():
     assert mg["rccl_ranks"] == 3 and mg["gather_mode"] == "rccl" and sum(mg["utterances_per_device"]) == 6
     assert sum(mg["samples_per_device"]) == 2 * 6 * 1000 and abs(mg["gather_ms_per_step_rank0"] - 0.25) < 1e-9
     assert abs(out["value"] * out["ms_per_step"] * 1e-3 * 2 - 2 * 6 * 1000) < 1.0
+
+
+def _expected_dump(lens):
+    """The stub's PCM for the canonical batch: a ramp of 100 samples per phoneme starting at the utterance's first id."""
+    from summertts_amd import synth_blob as sb
+    vocab = sb.tiny_cfg("hifigan_fix").vocab
+    ids = [sb.synthetic_ids(int(t), vocab, salt=u) for u, t in enumerate(lens)]
+    pcm = np.concatenate([(np.arange(len(a) * 100, dtype=np.int64) + int(a[0])).astype(np.int16) for a in ids])
+    return np.asarray([len(a) * 100 for a in ids], np.float64), pcm.astype(np.float32)
+
+
+def test_dump_outputs_writes_the_last_timed_step_in_global_utterance_order(tmp_path):
+    """`--dump-outputs DIR`: the per-utterance sample counts and the PCM of the last timed step as float .npy files, the utterances of
+    all ranks in their global order, the same for one rank and for two."""
+    lens = np.random.default_rng(1234).integers(64, 257, size=4).tolist()      # bench.py's --ragged lengths of a 4-utterance batch
+    want_counts, want_pcm = _expected_dump(lens)
+    for gpus, batch in ((1, 4), (2, 2)):
+        d = tmp_path / f"g{gpus}"
+        out = _run(["--gpus", str(gpus), "--steps", "2", "--warmup", "0", "--batch", str(batch), "--ragged", "--dump-outputs", str(d)])
+        assert out["steps"] == 2
+        counts, pcm = np.load(d / "sample_counts.npy"), np.load(d / "pcm.npy")
+        assert counts.dtype == np.float64 and pcm.dtype == np.float32 and not (d / "pcm_index.npy").exists()
+        assert np.array_equal(counts, want_counts) and np.array_equal(pcm, want_pcm)
+
+
+def test_dump_outputs_samples_a_large_pcm_within_the_budget(tmp_path):
+    import bench
+    pcm = (np.arange(bench.DUMP_MAX_BYTES // 4 + 1000) % 65536 - 32768).astype(np.int16)
+    for run in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / run), [pcm.size], pcm)
+    total = sum(os.path.getsize(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a"))
+    assert total <= bench.DUMP_MAX_BYTES
+    idx, got = np.load(tmp_path / "a" / "pcm_index.npy"), np.load(tmp_path / "a" / "pcm.npy")
+    assert idx.dtype == np.float64 and got.dtype == np.float32 and idx.size == got.size > 0
+    assert np.array_equal(got, pcm[idx.astype(np.int64)].astype(np.float32))
+    assert np.array_equal(idx, np.load(tmp_path / "b" / "pcm_index.npy"))      # the same sample every run

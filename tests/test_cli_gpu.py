@@ -30,15 +30,15 @@ def read_wav(path):
 
 def test_cli_text_input_through_the_reference_frontend(tmp_path):
     """SURVEY.md 8 f1: SynthesizerTrn::infer(TEXT) on a blob that carries frontend sections -- here an English model: the
-    reference's EnglishText2Id (frontend/_ref/libsummertts_frontend.so, compiled in place from the reference) turns the
+    reference's EnglishText2Id (oracle/_ref/libsummertts_frontend.so, compiled in place from the reference) turns the
     text into IPA ids on the host, lengthScale *= 0.83 (SynthesizerTrn.cpp:354), the HIP engine does the rest.  Checked
     against the oracle fed with the ids the same frontend emits.  (The Chinese frontend needs the FSTs / dictionaries of a
     real model blob, which are absent: not testable end to end.)"""
     import ctypes as C
     import dataclasses
-    fe_path = os.path.join(ROOT, "frontend", "_ref", "libsummertts_frontend.so")
+    fe_path = os.path.join(ROOT, "oracle", "_ref", "libsummertts_frontend.so")
     if not os.path.exists(fe_path):
-        pytest.skip("frontend/_ref/libsummertts_frontend.so did not travel (it is built from /root/reference)")
+        pytest.skip("oracle/_ref/libsummertts_frontend.so did not travel (build() makes it from the reference)")
     exe = build_cli(tmp_path)
     cfg = dataclasses.replace(sb.tiny_cfg("mbb_fix"), lang=1, vocab=sb.ENG_IPA_SYMBOLS)
     ac = sb.make_blob(cfg, 31)

@@ -1,5 +1,5 @@
 """CPU suite: the optional host text frontend.  frontend/_ref/libsummertts_frontend.so is the reference's
-own frontend compiled in place (frontend/Makefile) behind frontend/frontend_shim.cpp; the real model blobs -- the only
+own frontend compiled in place (oracle/frontend.mk, by build()) behind frontend/frontend_shim.cpp; the real model blobs -- the only
 carriers of the WeTextProcessing FSTs and jieba dictionaries -- are absent, so what is checked here is what a synthetic blob
 can carry: the English frontend end to end (its GRU matrices are synthesizable, its 125 k-word table is compiled in), the
 section walk of the Chinese blob layout incl. the `off += off % 4` rule, and that the reference's UNMODIFIED demo
@@ -15,16 +15,14 @@ import pytest
 from conftest import ROOT
 from summertts_amd import engine, synth_blob as sb
 
-FE = os.path.join(ROOT, "frontend", "_ref", "libsummertts_frontend.so")
-REF = "/root/reference"
+FE = os.path.join(ROOT, "oracle", "_ref", "libsummertts_frontend.so")
+DEMO_OBJ = os.path.join(ROOT, "oracle", "_ref", "fe_obj", "test", "main.o")   # the reference's test/main.cpp, compiled by oracle/frontend.mk
 
 
 @pytest.fixture(scope="module")
 def fe():
     if not os.path.exists(FE):
-        if not os.path.isdir(REF):
-            pytest.skip("libsummertts_frontend.so is built from /root/reference, which is absent here, and no prebuilt copy travelled")
-        subprocess.run(["make", "-C", os.path.join(ROOT, "frontend"), "-j8"], check=True, stdout=subprocess.DEVNULL)
+        pytest.skip("oracle/_ref/libsummertts_frontend.so is built from the reference by build(), and it was not built here")
     lib = C.CDLL(FE)
     lib.stsfe_create.restype = C.c_void_p
     lib.stsfe_create.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_int32]
@@ -103,15 +101,15 @@ def test_chinese_section_walk_follows_the_reference_alignment_rule(fe, sizes):
     assert fe.stsfe_scan_sections(blob.ctypes.data, blob.nbytes - 8, ac.size, 0, out) != 0 or pw + pp <= 8
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="needs the reference's test/main.cpp")
 def test_reference_demo_links_unmodified(fe, tmp_path):
     """The reference's own caller (test/main.cpp:75-148: Hanz2Piny helpers + ttsLoadModel + SynthesizerTrn + tts_free_data)
-    compiles against the reference's headers and LINKS against libsummertts_hip.so (+ the frontend library for the
-    Hanz2Piny symbols it uses to read the text file) without a single change."""
+    compiles against the reference's headers (oracle/frontend.mk, next to the frontend library) and LINKS against
+    libsummertts_hip.so (+ the frontend library for the Hanz2Piny symbols it uses to read the text file) without a single change."""
+    assert os.path.exists(DEMO_OBJ), "oracle/frontend.mk builds the demo object together with the frontend library"
     if not os.path.exists(engine.LIB_PATH):
         engine.build_library()
     exe = tmp_path / "tts_test"
-    r = subprocess.run(["g++", "-O1", "-std=c++11", "-w", f"-I{REF}/include", f"-I{REF}/src/header", f"{REF}/test/main.cpp",
+    r = subprocess.run(["g++", DEMO_OBJ,
                         "-L", os.path.dirname(engine.LIB_PATH), "-lsummertts_hip", "-L", os.path.dirname(FE), "-lsummertts_frontend",
                         "-Wl,-rpath," + os.path.dirname(engine.LIB_PATH), "-Wl,-rpath," + os.path.dirname(FE),
                         "-Wl,--allow-shlib-undefined", "-o", str(exe)], capture_output=True, text=True)

@@ -2,7 +2,8 @@
 ``sts_destroy`` with eight processes sharing the GPU (profiles/r05_ab_log.md).  Model construction and teardown touch the driver's
 virtual-memory calls (model.hip Store), host-mapped pinned buffers and stream / event objects; these tests hammer exactly that:
 many short-lived engines, from several processes at once and from several threads of one process, every result checked against the
-oracle's PCM so that a torn-down engine's memory being reused under a live one would show.
+oracle's PCM so that a torn-down engine's memory being reused under a live one would show.  The GPU is shared: at most six processes may
+have it open at once, and the pytest process itself is one of them once a GPU test has run, hence five workers.
 Mirrors the lifetime contract of /root/reference/src/models/SynthesizerTrn.cpp:403-415 (the destructor frees everything the constructor made)."""
 import os
 import subprocess
@@ -34,13 +35,16 @@ print("ok", n, int(want.size))
 """
 
 
+N_WORKERS = 5
+
+
 @pytest.mark.gpu
-def test_create_infer_destroy_from_eight_processes_at_once(tmp_path):
+def test_create_infer_destroy_from_five_processes_at_once(tmp_path):
     script = tmp_path / "stress_worker.py"
     script.write_text(WORKER % {"root": ROOT})
     kinds = ["hifigan_sdp", "mbb_fix", "ms_sdp", "istft_fix"]
     procs = [subprocess.Popen([sys.executable, str(script), "50", str(p), kinds[p % len(kinds)]], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True)
-             for p in range(8)]
+             for p in range(N_WORKERS)]
     fails = []
     for p, pr in enumerate(procs):
         try:
@@ -52,7 +56,7 @@ def test_create_infer_destroy_from_eight_processes_at_once(tmp_path):
             continue
         if pr.returncode != 0 or not out.strip().startswith("ok 50"):
             fails.append((p, pr.returncode, (out + err)[-2000:]))
-    assert not fails, f"{len(fails)} of 8 stress processes failed: {fails}"
+    assert not fails, f"{len(fails)} of {N_WORKERS} stress processes failed: {fails}"
 
 
 @pytest.mark.gpu
