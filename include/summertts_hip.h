@@ -101,7 +101,18 @@ int sts_pcm_host_view(sts_engine* e, const int16_t** pcm, int64_t* count);
  *   run only (the ceil is discontinuous, so waveform parity is checked with the
  *   oracle's durations).  Packed for the whole batch (sum of n entries). */
 int sts_set_forced_durations(sts_engine* e, const int32_t* dur, int64_t count);
-/*   record intermediate tensors of the next run: "x_enc","m","logw","z_p","z","wave" */
+/* ---- sampling noise (VITS inference noise; the reference's SynthesizerTrn::infer fixes both scales at 0, which stays the default).
+ *   noise_scale      scales the prior sample  z_p = m + eps * logs * noise_scale          (SynthesizerTrn.cpp:383: logs, NOT exp(logs))
+ *   noise_scale_w    scales the stochastic duration predictor's latent  z = eps * noise_scale_w  (StochasticDurationPredictor.cpp:129;
+ *                    accepted and ignored by models with the Fix duration predictor, as in the reference)
+ *   seed             utterance b of a call samples with seed + b; the engine never advances it (same call + same seed = same PCM)
+ * eps is a counter-based Philox4x64-10 stream per (seed, utterance element): results do not depend on batching, devices or chunking.
+ * The setting persists and applies to sts_infer_ids, sts_infer_ids_stream, sts_infer_ids_batch and sts_run_batch.  A negative or
+ * non-finite scale answers STS_EINVAL and changes nothing. */
+int sts_set_noise(sts_engine* e, float noise_scale, float noise_scale_w, uint64_t seed);
+int sts_get_noise(const sts_engine* e, float* noise_scale, float* noise_scale_w, uint64_t* seed);
+/*   record intermediate tensors of the next run: "x_enc","m","logs","logw","z_p","z","wave" ("logs": the second half of the
+ *   encoder projection, computed only by runs that record taps or sample the prior) */
 int sts_set_record_taps(sts_engine* e, int enable);
 /*   fetch a tap: malloc()'d copy, channel-major [channels][total_len] (== the reference's column-major
  *   MatrixXf [time, channels]); for batches the utterances are packed along time. */
@@ -177,7 +188,7 @@ int sts_set_profiling(sts_engine* e, int enable);
  * sizeof(sts_profile)) bytes, so a client compiled against an older header passes ITS sizeof and is never overrun;
  * sts_get_profile(e, p) == sts_get_profile_ex(e, p, sizeof(sts_profile)) of the header this library was built from -- use it only
  * when client and library are built together. */
-#define STS_ABI_VERSION 7
+#define STS_ABI_VERSION 8
 int sts_abi_version(void);
 /* bit 0: lab build (-DSTS_EXPERIMENTS: environment knobs of knobs.hpp, every conv tile code);
  * 0 for the shipped library */
@@ -233,6 +244,10 @@ int64_t sts_pool_submit(sts_pool* p, const int32_t* ids, int32_t n, int32_t sid,
 int sts_pool_wait(sts_pool* p, int64_t ticket, int16_t** pcm_out, int32_t* n_out);
 int sts_pool_stats(sts_pool* p, int64_t* batches, int64_t* requests);
 const char* sts_pool_last_error(void);
+/*   sts_pool_submit_ex: sts_pool_submit with this request's own sampling noise (sts_set_noise; the request's seed is used as given).
+ *   Requests with different noise settings share one packed batch. */
+int64_t sts_pool_submit_ex(sts_pool* p, const int32_t* ids, int32_t n, int32_t sid, float length_scale, float noise_scale,
+                           float noise_scale_w, uint64_t seed);
 
 /* ---- multi-device batch (no reference counterpart).  One host process drives n_devices GPUs:
  * one engine (weights replicated) and one worker thread per entry of `devices` (HIP device indices; an index may repeat,
@@ -260,6 +275,9 @@ int sts_multi_gather_mode(const sts_multi* m);
 int sts_multi_rccl_ranks(sts_multi* m);
 double sts_multi_last_gather_ms(const sts_multi* m);
 int sts_multi_set_conv_math(sts_multi* m, int mode);
+/*   sts_multi_set_noise: sts_set_noise for the handle; utterance b of a batch samples with seed + b (b = its index in the caller's
+ *   batch, not within a device's shard: the PCM does not depend on the number of devices). */
+int sts_multi_set_noise(sts_multi* m, float noise_scale, float noise_scale_w, uint64_t seed);
 /*   test hook: the shared library that provides the nccl* entry points (NULL / "" = librccl.so.1) and whether STS_MULTI_RCCL may list
  *   one device several times (tests/fake_rccl: N emulated ranks on one GPU; real RCCL refuses duplicates).  Only before the first
  *   STS_MULTI_RCCL handle of the process is created.  TEST-ONLY: refused with STS_ESTATE unless the process environment carries

@@ -146,6 +146,19 @@ int sts_set_forced_durations(sts_engine* e, const int32_t* dur, int64_t count) {
     return STS_OK;
 }
 
+int sts_set_noise(sts_engine* e, float noise_scale, float noise_scale_w, uint64_t seed) {
+    if (!e) return set_err(STS_EINVAL, "null engine");
+    if (!noise_scale_valid(noise_scale) || !noise_scale_valid(noise_scale_w)) return set_err(STS_EINVAL, "noise scales must be finite and >= 0");
+    e->eng.noise = Engine::Noise{noise_scale, noise_scale_w, seed};
+    return STS_OK;
+}
+int sts_get_noise(const sts_engine* e, float* noise_scale, float* noise_scale_w, uint64_t* seed) {
+    if (!e) return set_err(STS_EINVAL, "null engine");
+    if (noise_scale) *noise_scale = e->eng.noise.ns;
+    if (noise_scale_w) *noise_scale_w = e->eng.noise.nsw;
+    if (seed) *seed = e->eng.noise.seed;
+    return STS_OK;
+}
 int sts_set_record_taps(sts_engine* e, int enable) { if (!e) return set_err(STS_EINVAL, "null engine"); e->eng.record_taps = enable != 0; return STS_OK; }
 int sts_set_conv_math(sts_engine* e, int mode) {
     if (!e) return set_err(STS_EINVAL, "null engine");

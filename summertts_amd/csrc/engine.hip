@@ -345,8 +345,8 @@ int decoder_halo_frames(const Model& M) {
 }
 
 struct BufT {
-    int *meta_i; float* ls; int* ids; int* forced;
-    float *x, *qkv, *att, *y, *x1, *ffh, *m;
+    int *meta_i; float* ls; float *ns, *nsw; uint64_t* seed; int* ids; int* forced;
+    float *x, *qkv, *att, *y, *x1, *ffh, *m, *logs;
     float *dh, *dt1, *dt2, *dc, *dhh, *dp29, *dr[4], *dlogw;
     int *dur, *cum, *frames;
     float *g, *cond_dp, *cond_dec, *cond_wn;
@@ -376,6 +376,7 @@ struct Engine::RunCtx {
     // (ahead: the count is predicted, the kernels read the real one from device memory) makes exactly the dispatch decisions of a call
     // that waited for it -- and returns bit-identical samples.  Batches: Fld == Ftot, nothing changes.
     long Fld = 0; int maxFld = 0; bool ahead = false, ahead_b = false, mapped = false, forced = false;
+    std::vector<Engine::Noise> nz; bool any_ns = false, any_nsw = false;   // per-utterance sampling noise (engine.hpp Noise), which of the two is used
     std::vector<unsigned long long> req_keys; std::vector<long> predF;      // launch-ahead memo: per-utterance request hashes, remembered frame counts (empty: not all known)
     int halo = 0; long Wcap = 0; int upS = 1; long Lsb = 0; int sbC = 0;
     bool use_ff = false; int ffG = 0;
@@ -417,6 +418,14 @@ int Engine::run_setup(RunCtx& c) {
     if ((size_t)(M.hidden / 2 + 8 + 5 * (size_t)maxT) * 4 > 150 * 1024) return fail(STS_EINVAL, "utterance too long for the attention kernel");
     if (have_forced && (long)forced_dur.size() != Ttot) { have_forced = false; return fail(STS_EINVAL, "forced durations do not match the batch"); }
 
+    // sampling noise of every utterance: the caller's per-utterance table (sts_pool, sts_multi) or the engine's setting with seed + b
+    c.nz.resize(B);
+    for (int b = 0; b < B; b++) {
+        c.nz[b] = (int)noise_utt.size() == B ? noise_utt[b] : Noise{noise.ns, noise.nsw, noise.seed + (uint64_t)b};
+        if (M.dur_type != 0) c.nz[b].nsw = 0.f;        // the Fix duration predictor has no latent (FixDurationPredictor.cpp:75)
+        c.any_ns |= c.nz[b].ns != 0.f; c.any_nsw |= c.nz[b].nsw != 0.f;
+    }
+
     const int H = c.H = M.hidden, C = c.C = M.inter;
     const int FF = c.FF = M.n_layers ? M.ffn[0].c1.Cout : 0;
     const int fdp = c.fdp = M.dur_type == 0 ? M.sdp_pre.Cout : M.fix_c1.Cout;
@@ -428,16 +437,19 @@ int Engine::run_setup(RunCtx& c) {
     BufT& bt = c.bt;
     auto layoutT = [&](Arena& A) {
         A.used = 0;
-        // one device block mirroring the pinned staging block [geometry ints | length scales | ids | forced durations]:
-        // a single host-to-device copy per run
-        bt.meta_i = A.get<int>((size_t)9 * B + 8 + B + 2 * (size_t)Ttot);
+        // one device block mirroring the pinned staging block [geometry ints | length scales | noise scales, seeds | ids | forced
+        // durations]: a single host-to-device copy per run
+        bt.meta_i = A.get<int>((size_t)9 * B + 8 + 5 * (size_t)B + 2 * (size_t)Ttot);
         bt.ls = (float*)(bt.meta_i + ((size_t)9 * B + 8));
-        bt.ids = (int*)(bt.ls + B);
+        bt.ns = bt.ls + B; bt.nsw = bt.ns + B;
+        bt.seed = (uint64_t*)(bt.nsw + B);      // (9B + 8 + 3B ints from a 256-byte boundary: 8-byte aligned)
+        bt.ids = (int*)(bt.seed + B);
         bt.forced = bt.ids + Ttot;
         bt.x = A.get<float>((size_t)H * Ttot); bt.qkv = A.get<float>((size_t)3 * H * Ttot);
         bt.att = A.get<float>((size_t)H * Ttot); bt.y = A.get<float>((size_t)H * Ttot * ffn2_slices);
         bt.x1 = A.get<float>((size_t)H * Ttot); bt.ffh = A.get<float>((size_t)FF * Ttot);
         bt.m = A.get<float>((size_t)C * Ttot);
+        bt.logs = (c.any_ns || record_taps) ? A.get<float>((size_t)C * Ttot) : nullptr;
         bt.dh = A.get<float>((size_t)(fdp > H ? fdp : H) * Ttot); bt.dt1 = A.get<float>((size_t)fdp * Ttot);
         bt.dt2 = A.get<float>((size_t)fdp * Ttot); bt.dc = A.get<float>((size_t)fdp * Ttot);
         bt.dhh = A.get<float>((size_t)fdp * Ttot); bt.dp29 = A.get<float>((size_t)29 * Ttot);
@@ -456,7 +468,7 @@ int Engine::run_setup(RunCtx& c) {
 
     // ---------------- one H2D: geometry + ids (+ forced durations)
     const size_t meta_ints = c.meta_ints = (size_t)9 * B + 8;
-    const size_t up_bytes = c.up_bytes = (meta_ints + B + 2 * (size_t)Ttot) * 4 + 1024;
+    const size_t up_bytes = c.up_bytes = (meta_ints + 5 * (size_t)B + 2 * (size_t)Ttot) * 4 + 1024;
     if (!ensure_pinned(up_bytes + ((size_t)Ttot + B) * 4)) return fail(STS_EDEVICE, "pinned host allocation failed");
     int* pm = c.pm = (int*)pinned_;
     int* p_offT = c.p_offT = pm, *p_lenT = c.p_lenT = pm + B, *p_sid = c.p_sid = pm + 2 * B, *p_one = c.p_one = pm + 5 * B;
@@ -468,11 +480,13 @@ int Engine::run_setup(RunCtx& c) {
     c.d_sid = bt.meta_i + 2 * B; c.d_offF = bt.meta_i + 3 * B; c.d_lenF = bt.meta_i + 4 * B; c.d_win = bt.meta_i + 5 * B + 2;
     float* p_ls = (float*)(pm + meta_ints);
     for (int b = 0; b < B; b++) p_ls[b] = ls ? ls[b] : 1.0f;
-    int* p_ids = (int*)(p_ls + B);
+    float* p_ns = p_ls + B; float* p_nsw = p_ns + B; uint64_t* p_seed = (uint64_t*)(p_nsw + B);
+    for (int b = 0; b < B; b++) { p_ns[b] = c.nz[b].ns; p_nsw[b] = c.nz[b].nsw; p_seed[b] = c.nz[b].seed; }
+    int* p_ids = (int*)(p_seed + B);
     for (int b = 0; b < B; b++) memcpy(p_ids + offT[b], ids[b], sizeof(int) * n[b]);
     int* p_forced = p_ids + Ttot;
     if (have_forced) memcpy(p_forced, forced_dur.data(), sizeof(int) * Ttot);
-    HIPCK(hipMemcpyAsync(bt.meta_i, pm, (meta_ints + B + (size_t)Ttot * (have_forced ? 2 : 1)) * 4, hipMemcpyHostToDevice, stream));
+    HIPCK(hipMemcpyAsync(bt.meta_i, pm, (meta_ints + 5 * (size_t)B + (size_t)Ttot * (have_forced ? 2 : 1)) * 4, hipMemcpyHostToDevice, stream));
     if (B > 1) HIPCK(hipEventRecord(ev_setup_, stream));     // (run_durations, batches launched from the memo: the host rewrites part of this block)
 
     // single-segment views travel by value (kernels.hpp SegView): no segment-table load in the kernels of a one-utterance call
@@ -560,8 +574,10 @@ int Engine::run_text_encoder(RunCtx& c) {
         // (the layer's second LayerNorm runs with the next consumer of x: the next layer's q/k/v conv or the output proj)
     }
     produce_x_and_conv(M.n_layers, M.proj, bt.m);
+    if (bt.logs) conv(M.proj_logs, bt.x, lvT, bt.logs, lvT, ConvOpt());   // (the prior's scale: only calls that sample it or record taps)
     tap("x_enc", bt.x, H, Ttot, Ttot);
     tap("m", bt.m, C, Ttot, Ttot);
+    if (bt.logs) tap("logs", bt.logs, C, Ttot, Ttot);
     mark(1);
     return STS_OK;
 }
@@ -588,11 +604,13 @@ int Engine::run_durations(RunCtx& c) {
         conv(M.sdp_pre, bt.x, lvT, bt.dh, lvT, op);
         const float* dh = dds(M.sdp_dds, bt.dh, bt.dt1, bt.dt2, lvT);
         conv(M.sdp_proj, dh, lvT, bt.dc, lvT, ConvOpt());
-        // the latent z starts as zeros (noise scale 0, StochasticDurationPredictor.cpp:129-131): null inputs stand for it
+        // the latent z (StochasticDurationPredictor.cpp:129-131): rand_gen(2, T) * noise_scale_w, flipped.  Without noise it is all
+        // zeros and null inputs stand for it; with noise (some utterance has nsw != 0) it is written into the rows flow n-1 reads
         const float *r0 = nullptr, *r1 = nullptr;
         float *n0 = bt.dr[2], *n1 = bt.dr[3], *s0 = bt.dr[0], *s1 = bt.dr[1];
-        if (M.sdp_flows <= 1) { HIPCK(hipMemsetAsync(bt.dr[0], 0, (size_t)Ttot * 4, stream)); r0 = bt.dr[0]; }
-        for (int i = M.sdp_flows - 1; i > 0; i--) {   // flow 0 is skipped; z == 0 because noise_scale == 0
+        if (c.any_nsw) { sdp_noise(lvT.seg, B, maxT, bt.nsw, bt.seed, bt.dr[0], bt.dr[1], stream); r0 = bt.dr[0]; r1 = bt.dr[1]; }
+        else if (M.sdp_flows <= 1) { HIPCK(hipMemsetAsync(bt.dr[0], 0, (size_t)Ttot * 4, stream)); r0 = bt.dr[0]; }
+        for (int i = M.sdp_flows - 1; i > 0; i--) {   // flow 0 is skipped, as in the reference
             const DConvFlow& cf = M.cf[i];
             // DDSConv(pre(x0) + g): the 1 -> C input conv and the "+ g" ride inside the first DDSConv layer
             const SplineTail tl{&cf.proj, sqrtf((float)cf.filter), r0, r1, n0, n1};
@@ -663,6 +681,10 @@ int Engine::run_durations(RunCtx& c) {
         if (launch_ahead != 2) {          // (2: test mode -- the key is the phoneme count alone, i.e. every request of a length collides)
             mix((unsigned)(c.sid ? c.sid[b] : 0)); { const float lsb = c.ls ? c.ls[b] : 1.0f; unsigned u; memcpy(&u, &lsb, 4); mix(u); }
             for (int t = 0; t < c.n[b]; t++) mix((unsigned)c.ids[b][t]);
+        }
+        if (c.nz[b].nsw != 0.f) {         // sampled durations depend on (nsw, seed) too; a noise-free key never carries these words
+            unsigned u; memcpy(&u, &c.nz[b].nsw, 4); mix(u); mix((unsigned)c.nz[b].seed); mix((unsigned)(c.nz[b].seed >> 32));
+            h ^= 0x5bd1e995ull; h *= 1099511628211ull;
         }
         c.req_keys[b] = h | 1ull;
     }
@@ -901,11 +923,12 @@ int Engine::run_flow(RunCtx& c) {
     const long Fcount = c.Ftot;         // frames of the batch (taps); below, Ftot / maxF are the CAPACITY the buffers and launches are sized for
 #define Ftot Fld
 #define maxF maxFld
-    // ---------------- length regulator (SynthesizerTrn.cpp:304-321, 380-383: z_p == m_expand, noise 0)
+    // ---------------- length regulator (SynthesizerTrn.cpp:304-321, 380-383): z_p == m_expand, + eps * logs_expand * ns when sampling
     stage_begin(2);
+    const PriorNoise pnz{c.any_ns ? bt.logs : nullptr, bt.ns, bt.seed};
     const int half = C / 2;
     if (use_ff) {
-        expand_frames(bt.m, Ttot, bt.cum, lvT.seg, lv1.seg, C, bf.z, Ftot, B, maxF, stream);
+        expand_frames(bt.m, Ttot, bt.cum, lvT.seg, lv1.seg, C, bf.z, Ftot, B, maxF, stream, &pnz);
         tap("z_p", bf.z, C, Ftot, Fcount);
         const int G = ffG;
         const size_t hF = (size_t)half * Ftot;
@@ -974,7 +997,7 @@ int Engine::run_flow(RunCtx& c) {
         for (int hh = 0; hh < 2; hh++) if (cur[hh] != home[hh]) finish_half(hh, -1);
     } else
     {
-    expand_frames(bt.m, Ttot, bt.cum, lvT.seg, lv1.seg, C, bf.z, Ftot, B, maxF, stream);
+    expand_frames(bt.m, Ttot, bt.cum, lvT.seg, lv1.seg, C, bf.z, Ftot, B, maxF, stream, &pnz);
     tap("z_p", bf.z, C, Ftot, Fcount);
 
     // ---------------- reverse flow (ResidualCouplingBlock.cpp:59-70, ResidualCouplingLayer.cpp:47-66, WN.cpp:100-149)

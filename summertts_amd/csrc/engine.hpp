@@ -49,6 +49,7 @@ struct ConvOpt {
 // streaming decode: PCM is handed to `cb` chunk by chunk (cb returns non-zero to stop)
 struct StreamSpec { int chunk_frames; int (*cb)(void* user, const int16_t* pcm, int32_t n_samples, int32_t sample_offset); void* user; };
 int decoder_halo_frames(const Model& M);
+inline bool noise_scale_valid(float s) { return s >= 0.f && s <= 3.0e38f; }   // (false for NaN and +inf)
 
 struct Tap { std::vector<float> data; int channels = 0; long length = 0; };
 
@@ -78,6 +79,10 @@ public:
     std::map<std::string, Tap> taps;
     sts_profile prof{};
     // controls
+    // sampling noise (sts_set_noise): prior scale ns, SDP latent scale nsw, seed of utterance 0 (utterance b of a call: seed + b)
+    struct Noise { float ns = 0.f, nsw = 0.f; uint64_t seed = 0; };
+    Noise noise;
+    std::vector<Noise> noise_utt;      // when it holds B entries: the per-utterance settings of a B-utterance run instead (sts_pool, sts_multi)
     std::vector<int32_t> forced_dur; bool have_forced = false;
     bool record_taps = false; int profiling = 0;       // profiling: 0 off, 1 all stage events, 2 the matrix-core region's two events only (sts_set_profiling)
     int conv_mode = 0;
@@ -91,8 +96,8 @@ public:
     int attn_block_min_wgs = 96;       // attention_mfma_kernel from this many workgroups on (sts_debug_set)
     int launch_ahead = 1;              // 1: a one-utterance call the engine has served before enqueues flow + decoder before the frame count is on the host; 2 (tests): the memo is keyed by the phoneme count alone (sts_debug_set STS_DBG_LAUNCH_AHEAD)
     long ahead_misses = 0;             // launch-ahead calls whose count fell outside the predicted 64-frame bucket (a hash collision; repeated the waiting way)
-    // the launch-ahead memo: hash of an utterance's (ids, speaker, length scale) -> its frame count (a pure function of them: the reference's
-    // noise scale is 0); the last kMemoEntries distinct utterances, FIFO
+    // the launch-ahead memo: hash of an utterance's (ids, speaker, length scale [, nsw, seed when nsw != 0]) -> its frame count (a pure
+    // function of them); the last kMemoEntries distinct utterances, FIFO
     static constexpr size_t kMemoEntries = 1024;
     std::unordered_map<unsigned long long, long> seen_tf_; std::deque<unsigned long long> seen_order_;
     // Host waits of a run (the frame counts of a request the engine has not served before; the run's final stream synchronisation).  A direct

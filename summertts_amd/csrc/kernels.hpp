@@ -311,8 +311,13 @@ void durations(const float* r0, int sdp, float ea_m, float ea_logs, const float*
                int* host_out = nullptr, long total = 0, int seq = 0, unsigned* arrive = nullptr,
                int* len_out = nullptr, int* win_len_out = nullptr, int cap = 0);     // optional: frames[b] clamped to cap, into two device tables
 // z[c][offF[b] + f] = m[c][offT[b] + phoneme(f)]
+// nz (optional; null or nz->logs null = the noise-free regulator): z_p = m_expand + eps * logs_expand * ns[b] (SynthesizerTrn.cpp:383),
+// logs with m's geometry, per-utterance ns / seed tables on the device (noise.hpp)
+struct PriorNoise { const float* logs; const float* ns; const uint64_t* seed; };
 void expand_frames(const float* m, long m_ld, const int* cum, SegView segT, SegView segF, int C,
-                   float* z, long z_ld, int B, int max_frames, hipStream_t st);
+                   float* z, long z_ld, int B, int max_frames, hipStream_t st, const PriorNoise* nz = nullptr);
+// the SDP latent of every utterance (flipped, scaled by nsw[b]) into the two rows the first reverse ConvFlow reads
+void sdp_noise(SegView seg, int B, int max_len, const float* nsw, const uint64_t* seed, float* r0, float* r1, hipStream_t st);
 
 // MB-iSTFT tail.  sb: subband conv output [nb*18 or 18][ld] with per-utterance frames = 16*len+1.
 // spec: [bands*18][ld] (re, im per bin) ; tm: [bands][ld4] with per-utterance n = 4*(frames-1).

@@ -5,6 +5,7 @@
 #include "kernels.hpp"
 #include "devmath.hpp"
 #include "knobs.hpp"
+#include "noise.hpp"
 #include <stdlib.h>
 
 namespace sts {
@@ -757,9 +758,12 @@ void durations(const float* r0, int sdp, float ea_m, float ea_logs, const float*
                        host_out, total, seq, arrive, B, len_out, win_len_out, cap);
 }
 
-// length regulator: frame f of utterance b copies phoneme i with cum[i-1] <= f < cum[i]
+// length regulator: frame f of utterance b copies phoneme i with cum[i-1] <= f < cum[i].  NOISE: the prior sample of
+// SynthesizerTrn.cpp:383, z_p = m_expand + eps * logs_expand * ns (the reference multiplies by logs, not exp(logs)), eps = element
+// c * F + f of the utterance's prior noise stream (noise.hpp); an utterance with ns == 0 stores m_expand as the noise-free kernel does
+template <bool NOISE>
 __global__ __launch_bounds__(256) void expand_frames_kernel(const float* m, long m_ld, const int* cum, SegView segT,
-                                                            SegView segF, int C, float* z, long z_ld) {
+                                                            SegView segF, int C, float* z, long z_ld, PriorNoise nz) {
     const int b = blockIdx.z;
     const int F = seg_len(segF, b), T = seg_len(segT, b);
     const int f = blockIdx.x * 256 + threadIdx.x;
@@ -778,14 +782,50 @@ __global__ __launch_bounds__(256) void expand_frames_kernel(const float* m, long
     else { while (lo < hi) { int mid = (lo + hi) >> 1; if (cum[tb + mid] > f) hi = mid; else lo = mid + 1; } }
     const int c0 = blockIdx.y * 16, c1 = c0 + 16 < C ? c0 + 16 : C;
     if (lo >= T) { for (int c = c0; c < c1; c++) z[(size_t)c * z_ld + fb + f] = 0.f; return; }
+    if constexpr (NOISE) {
+        const float ns = nz.ns[b];
+        if (ns != 0.f) {
+            const uint64_t seed = nz.seed[b];
+            for (int c = c0; c < c1; c++) {
+                const float eps = noise_normal(seed, kNoiseStreamPrior, (uint64_t)c * (uint64_t)F + (uint64_t)f);
+                // (m + (eps * logs) * ns) rounded step by step as the reference's expression: no contraction into an FMA
+                const float v = __fmul_rn(__fmul_rn(eps, nz.logs[(size_t)c * m_ld + tb + lo]), ns);
+                z[(size_t)c * z_ld + fb + f] = __fadd_rn(m[(size_t)c * m_ld + tb + lo], v);
+            }
+            return;
+        }
+    }
 #pragma unroll 4
     for (int c = c0; c < c1; c++) z[(size_t)c * z_ld + fb + f] = m[(size_t)c * m_ld + tb + lo];
 }
 void expand_frames(const float* m, long m_ld, const int* cum, SegView segT, SegView segF, int C, float* z, long z_ld,
-                   int B, int max_frames, hipStream_t st) {
+                   int B, int max_frames, hipStream_t st, const PriorNoise* nz) {
     if (B <= 0 || max_frames <= 0) return;
-    hipLaunchKernelGGL(expand_frames_kernel, dim3((max_frames + 255) / 256, (C + 15) / 16, B), dim3(256), 0, st, m, m_ld, cum,
-                       segT, segF, C, z, z_ld);
+    const dim3 grid((max_frames + 255) / 256, (C + 15) / 16, B);
+    if (nz && nz->logs) hipLaunchKernelGGL(expand_frames_kernel<true>, grid, dim3(256), 0, st, m, m_ld, cum, segT, segF, C, z, z_ld, *nz);
+    else hipLaunchKernelGGL(expand_frames_kernel<false>, grid, dim3(256), 0, st, m, m_ld, cum, segT, segF, C, z, z_ld, PriorNoise{});
+}
+
+// the SDP latent of SynthesizerTrn.cpp:374 / StochasticDurationPredictor.cpp:129-131 for the first reverse ConvFlow, already through
+// nn_flip(z, 0): r0[t] = z[1][t], r1[t] = z[0][t] with z[ch][t] = eps(t * 2 + ch) * nsw (noise.hpp, SDP stream); packed positions
+__global__ __launch_bounds__(256) void sdp_noise_kernel(SegView seg, const float* nsw, const uint64_t* seed, float* r0, float* r1) {
+    const int b = blockIdx.y;
+    const int T = seg_len(seg, b);
+    const int t = blockIdx.x * 256 + threadIdx.x;
+    if (t >= T) return;
+    const size_t p = (size_t)seg_start(seg, b) + t;
+    const float s = nsw[b];
+    if (s == 0.f) { r0[p] = 0.f; r1[p] = 0.f; return; }
+    // one Philox block holds the words of t = 2q, 2q + 1 (both channels): j = 2t + ch
+    const Philox4 w = philox4x64_10((uint64_t)t >> 1, (uint64_t)kNoiseStreamSdp, seed[b]);
+    const int o = (t & 1) * 2;
+    const float z0 = philox_normal(o ? w.w[2] : w.w[0]), z1 = philox_normal(o ? w.w[3] : w.w[1]);
+    r0[p] = z1 * s;
+    r1[p] = z0 * s;
+}
+void sdp_noise(SegView seg, int B, int max_len, const float* nsw, const uint64_t* seed, float* r0, float* r1, hipStream_t st) {
+    if (B <= 0 || max_len <= 0) return;
+    hipLaunchKernelGGL(sdp_noise_kernel, dim3((max_len + 255) / 256, B), dim3(256), 0, st, seg, nsw, seed, r0, r1);
 }
 
 // ---------------------------------------------------------------------------------------------

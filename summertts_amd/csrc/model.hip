@@ -516,9 +516,13 @@ bool load_model(const float* blob, int64_t nfloats, Model& m) {
         HConv p = parse_conv(r);
         if (!r.ok || (p.out_ch & 1) || p.k != 1) FAIL("encoder proj");
         m.inter = p.out_ch / 2;
-        // `logs` (second half) is dead at noiseScale == 0 (/root/reference/src/models/SynthesizerTrn.cpp:357,383): keep m only
+        // `logs` (second half) is dead at noiseScale == 0 (/root/reference/src/models/SynthesizerTrn.cpp:357,383): m is the projection
+        // every call runs; logs is a conv of its own, run only by calls that sample the prior (sts_set_noise) or record taps
         PackOpts o; o.out_rows = m.inter;
         if (!pack_conv(st, p, o, m.proj) || !pack_col(st, p, m.proj, m.inter)) FAIL("proj pack");
+        HConv pl = p;
+        pl.out_ch = m.inter; pl.w = p.w + (size_t)m.inter * p.k * p.in_ch; pl.b = p.b ? p.b + m.inter : nullptr;
+        if (!pack_conv(st, pl, PackOpts(), m.proj_logs)) FAIL("proj logs pack");
     }
 
     // ---- decoder: Generator_hifigan.cpp:44-101, Generator_MS.cpp:51-127, Generator_Istft.cpp:49-113, Generator_MBB.cpp:51-106

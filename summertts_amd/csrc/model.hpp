@@ -76,7 +76,7 @@ struct Model {
     // text encoder
     int hidden = 0, vocab = 0, emb_size = 0, n_layers = 0, inter = 0;
     const float* emb = nullptr;
-    std::vector<DMha> mha; std::vector<DLn> ln1, ln2; std::vector<DFfn> ffn; DConv proj;
+    std::vector<DMha> mha; std::vector<DLn> ln1, ln2; std::vector<DFfn> ffn; DConv proj, proj_logs;
     // decoder
     int subbands = 4, nfft = 16, hop = 4, n_up = 0, n_resk = 0, up_init = 0;
     std::vector<int> up_rate, up_k;

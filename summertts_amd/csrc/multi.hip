@@ -96,6 +96,7 @@ struct sts_multi {
     // one job at a time (the entry points are not re-entrant, like an engine)
     int64_t epoch = 0; int pending = 0; bool stop = false;
     int32_t B = 0; const int32_t* const* ids = nullptr; const int32_t* n = nullptr; const int32_t* sid = nullptr; const float* ls = nullptr;
+    Engine::Noise noise;                    // sts_multi_set_noise: utterance b of a batch samples with noise.seed + b (its index in the caller's batch)
     std::vector<Shard> shards;
     // RCCL gather state (gather_mode == 1)
     int gather_mode = 0;
@@ -280,8 +281,13 @@ struct sts_multi {
             const int nb = (int)sh.utt.size();
             if (nb > 0) {
                 std::vector<const int32_t*> idp(nb); std::vector<int32_t> nn(nb), sd(nb); std::vector<float> l(nb);
-                for (int i = 0; i < nb; i++) { const int u = sh.utt[i]; idp[i] = ids[u]; nn[i] = n[u]; sd[i] = sid ? sid[u] : 0; l[i] = ls ? ls[u] : 1.0f; }
+                eng.noise_utt.resize(nb);
+                for (int i = 0; i < nb; i++) {
+                    const int u = sh.utt[i]; idp[i] = ids[u]; nn[i] = n[u]; sd[i] = sid ? sid[u] : 0; l[i] = ls ? ls[u] : 1.0f;
+                    eng.noise_utt[i] = Engine::Noise{noise.ns, noise.nsw, noise.seed + (uint64_t)u};
+                }
                 sh.rc = eng.run(nb, idp.data(), nn.data(), sd.data(), l.data());
+                eng.noise_utt.clear();
                 if (sh.rc == STS_OK && gather_mode == 1) {
                     sh.n_samples = eng.n_samples;           // the PCM stays on the device: rccl_gather() below
                 } else if (sh.rc == STS_OK) {
@@ -364,6 +370,12 @@ int sts_multi_rccl_ranks(sts_multi* m) {
     return r == ncclSuccess ? n : 0;
 }
 double sts_multi_last_gather_ms(const sts_multi* m) { return m ? m->last_gather_ms : 0.0; }
+int sts_multi_set_noise(sts_multi* m, float noise_scale, float noise_scale_w, uint64_t seed) {
+    if (!m) return multi_err(STS_EINVAL, "null handle");
+    if (!noise_scale_valid(noise_scale) || !noise_scale_valid(noise_scale_w)) return multi_err(STS_EINVAL, "noise scales must be finite and >= 0");
+    m->noise = Engine::Noise{noise_scale, noise_scale_w, seed};
+    return STS_OK;
+}
 int sts_multi_set_conv_math(sts_multi* m, int mode) {
     if (!m) return multi_err(STS_EINVAL, "null handle");
     if (mode < 0 || mode > 3) return multi_err(STS_EINVAL, "conv math must be 0..3");

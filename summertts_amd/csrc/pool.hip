@@ -26,6 +26,7 @@ namespace {
 struct Request {
     int64_t ticket = 0;
     std::vector<int32_t> ids; int32_t sid = 0; float ls = 1.f;
+    Engine::Noise noise;               // sts_pool_submit_ex: this request's sampling noise
     // result
     bool done = false, waited = false; int rc = STS_OK; std::string err;
     int16_t* pcm = nullptr; int32_t n = 0;
@@ -60,8 +61,13 @@ struct sts_pool {
             auto run_group = [&](const std::vector<std::shared_ptr<Request>>& grp, auto&& self) -> void {
                 const int B = (int)grp.size();
                 std::vector<const int32_t*> idp(B); std::vector<int32_t> n(B), sid(B); std::vector<float> ls(B);
-                for (int b = 0; b < B; b++) { idp[b] = grp[b]->ids.data(); n[b] = (int32_t)grp[b]->ids.size(); sid[b] = grp[b]->sid; ls[b] = grp[b]->ls; }
+                eng.noise_utt.resize(B);
+                for (int b = 0; b < B; b++) {
+                    idp[b] = grp[b]->ids.data(); n[b] = (int32_t)grp[b]->ids.size(); sid[b] = grp[b]->sid; ls[b] = grp[b]->ls;
+                    eng.noise_utt[b] = grp[b]->noise;
+                }
                 int rc = eng.run(B, idp.data(), n.data(), sid.data(), ls.data());
+                eng.noise_utt.clear();
                 std::vector<int16_t> all;
                 if (rc == STS_OK) {
                     all.resize((size_t)(eng.total_samples > 0 ? eng.total_samples : 1));
@@ -133,9 +139,15 @@ void sts_pool_destroy(sts_pool* p) {
 }
 
 int64_t sts_pool_submit(sts_pool* p, const int32_t* ids, int32_t n, int32_t sid, float length_scale) {
+    return sts_pool_submit_ex(p, ids, n, sid, length_scale, 0.f, 0.f, 0);
+}
+
+int64_t sts_pool_submit_ex(sts_pool* p, const int32_t* ids, int32_t n, int32_t sid, float length_scale, float noise_scale,
+                           float noise_scale_w, uint64_t seed) {
     if (!p || !ids || n <= 0) return pool_err(STS_EINVAL, "bad request");
+    if (!noise_scale_valid(noise_scale) || !noise_scale_valid(noise_scale_w)) return pool_err(STS_EINVAL, "noise scales must be finite and >= 0");
     auto r = std::make_shared<Request>();
-    r->ids.assign(ids, ids + n); r->sid = sid; r->ls = length_scale;
+    r->ids.assign(ids, ids + n); r->sid = sid; r->ls = length_scale; r->noise = Engine::Noise{noise_scale, noise_scale_w, seed};
     {
         std::lock_guard<std::mutex> lk(p->mu);
         if (p->stop) return pool_err(STS_ESTATE, "pool is shutting down");

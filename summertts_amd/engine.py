@@ -101,6 +101,8 @@ def load_library() -> C.CDLL:
     lib.sts_get_tap.argtypes = [C.c_void_p, C.c_char_p, C.POINTER(C.POINTER(C.c_float)), C.POINTER(C.c_int32),
                                 C.POINTER(C.c_int64)]
     lib.sts_get_durations.argtypes = [C.c_void_p, C.c_void_p, C.c_int64]
+    lib.sts_set_noise.argtypes = [C.c_void_p, C.c_float, C.c_float, C.c_uint64]
+    lib.sts_get_noise.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_uint64)]
     lib.sts_free.argtypes = [C.c_void_p]
     lib.sts_debug_conv1d.argtypes = [C.c_int, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32,
                                      C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_int32,
@@ -119,6 +121,7 @@ EXPORTED_SYMBOLS = [
     "sts_pool_create", "sts_pool_destroy", "sts_pool_submit", "sts_pool_wait", "sts_pool_stats", "sts_pool_last_error",
     "sts_multi_create", "sts_multi_destroy", "sts_multi_device_count", "sts_multi_speaker_num", "sts_multi_infer_ids_batch",
     "sts_multi_shard_of", "sts_multi_last_error", "sts_multi_set_rccl_library", "sts_multi_rccl_ranks", "sts_multi_last_gather_ms", "sts_multi_set_conv_math", "sts_get_profile_ex", "sts_abi_version", "sts_build_flags",
+    "sts_set_noise", "sts_get_noise", "sts_pool_submit_ex", "sts_multi_set_noise",
 ]
 
 
@@ -244,6 +247,18 @@ class Synthesizer:
 
     def set_record_taps(self, on: bool):
         _check(self.lib, self.lib.sts_set_record_taps(self.h, 1 if on else 0))
+
+    def set_noise(self, noise_scale: float = 0.0, noise_scale_w: float = 0.0, seed: int = 0):
+        """Sampling noise of every later call (include/summertts_hip.h sts_set_noise): ``noise_scale`` scales the prior sample
+        (z_p = m + eps * logs * noise_scale, the reference's expression), ``noise_scale_w`` the stochastic duration predictor's
+        latent; utterance b of a batch samples with ``seed + b``.  All zero (the default) = the reference's noise-free ``infer``."""
+        _check(self.lib, self.lib.sts_set_noise(self.h, float(noise_scale), float(noise_scale_w), int(seed) & 0xFFFFFFFFFFFFFFFF))
+
+    def noise(self):
+        """(noise_scale, noise_scale_w, seed) as set by ``set_noise``."""
+        ns, nsw, seed = C.c_float(), C.c_float(), C.c_uint64()
+        _check(self.lib, self.lib.sts_get_noise(self.h, C.byref(ns), C.byref(nsw), C.byref(seed)))
+        return ns.value, nsw.value, seed.value
 
     def set_conv_math(self, mode):
         """Arithmetic of the decoder trunk convs: 0 / 'bf16x3' = fp32 operands as three bf16 terms on the bf16 matrix cores,
@@ -381,6 +396,8 @@ class Pool:
         self.lib.sts_pool_last_error.restype = C.c_char_p
         self.lib.sts_pool_submit.restype = C.c_int64
         self.lib.sts_pool_submit.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_float]
+        self.lib.sts_pool_submit_ex.restype = C.c_int64
+        self.lib.sts_pool_submit_ex.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_float, C.c_uint64]
         self.lib.sts_pool_wait.argtypes = [C.c_void_p, C.c_int64, C.POINTER(C.POINTER(C.c_int16)), C.POINTER(C.c_int32)]
         self.lib.sts_pool_create.argtypes = [C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]
         self.lib.sts_pool_destroy.argtypes = [C.c_void_p]
@@ -389,9 +406,15 @@ class Pool:
         if rc != 0:
             raise StsError(f"sts_pool_create: {rc}: {self.lib.sts_pool_last_error().decode()}")
 
-    def submit(self, ids: Sequence[int], sid: int = 0, length_scale: float = 1.0) -> int:
+    def submit(self, ids: Sequence[int], sid: int = 0, length_scale: float = 1.0, noise_scale: float = 0.0,
+               noise_scale_w: float = 0.0, seed: int = 0) -> int:
+        """Queue one request; the noise arguments are this request's own (``Synthesizer.set_noise``; ``seed`` is used as given)."""
         a = np.ascontiguousarray(ids, dtype=np.int32)
-        t = int(self.lib.sts_pool_submit(self.h, a.ctypes.data, a.size, sid, length_scale))
+        if noise_scale == 0.0 and noise_scale_w == 0.0 and seed == 0:
+            t = int(self.lib.sts_pool_submit(self.h, a.ctypes.data, a.size, sid, length_scale))
+        else:
+            t = int(self.lib.sts_pool_submit_ex(self.h, a.ctypes.data, a.size, sid, length_scale, float(noise_scale),
+                                                float(noise_scale_w), int(seed) & 0xFFFFFFFFFFFFFFFF))
         if t <= 0:
             raise StsError(f"sts_pool_submit: {t}: {self.lib.sts_pool_last_error().decode()}")
         return t
@@ -472,6 +495,12 @@ class MultiDevice:
         self.lib.sts_multi_last_gather_ms.argtypes = [C.c_void_p]
         self.lib.sts_multi_last_gather_ms.restype = C.c_double
         return float(self.lib.sts_multi_last_gather_ms(self.h))
+
+    def set_noise(self, noise_scale: float = 0.0, noise_scale_w: float = 0.0, seed: int = 0):
+        """``Synthesizer.set_noise`` for every device; utterance b of a batch samples with ``seed + b`` whatever its device."""
+        self.lib.sts_multi_set_noise.argtypes = [C.c_void_p, C.c_float, C.c_float, C.c_uint64]
+        if self.lib.sts_multi_set_noise(self.h, float(noise_scale), float(noise_scale_w), int(seed) & 0xFFFFFFFFFFFFFFFF) != 0:
+            raise StsError(f"sts_multi_set_noise: {self.lib.sts_multi_last_error().decode()}")
 
     def set_conv_math(self, mode):
         m = {"bf16x3": 0, "f32": 1, "bf16x3_all": 2, "f16x2": 3}.get(mode, mode)
