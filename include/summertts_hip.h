@@ -48,7 +48,7 @@ typedef struct sts_model_info {
     int32_t is_multi_speaker, lang_type, dur_pred_type, dec_type;
     int32_t vocab, hidden, inter_channels, speaker_num, gin_channels;
     int32_t samples_per_frame;      /* total upsampling factor */
-    int32_t sample_rate;            /* 16000 (/root/reference/test/main.cpp:13,16) */
+    int32_t sample_rate;            /* the model's NATIVE rate, 16000 (/root/reference/test/main.cpp:13,16) -- unchanged by sts_set_output_rate */
     int64_t blob_floats_consumed;   /* floats consumed by the acoustic sections (frontend sections follow) */
 } sts_model_info;
 int sts_get_info(const sts_engine* e, sts_model_info* info);
@@ -71,7 +71,8 @@ int sts_infer_ids(sts_engine* e, const int32_t* ids, int32_t n, int32_t sid, flo
 typedef int (*sts_chunk_cb)(void* user, const int16_t* pcm, int32_t n_samples, int32_t sample_offset);
 int sts_infer_ids_stream(sts_engine* e, const int32_t* ids, int32_t n, int32_t sid, float length_scale,
                          int32_t chunk_frames, sts_chunk_cb cb, void* user, int32_t* n_total);
-/* frames of context the streaming decoder adds on each side of a chunk (a property of the loaded model) */
+/* frames of context the streaming decoder adds on each side of a chunk (a property of the loaded model and, at a non-native output rate,
+ * of the resampler: see sts_set_output_rate) */
 int sts_stream_halo_frames(const sts_engine* e);
 
 /* Batched form (new capability; the reference processes exactly one utterance per call).  The B
@@ -111,8 +112,31 @@ int sts_set_forced_durations(sts_engine* e, const int32_t* dur, int64_t count);
  * non-finite scale answers STS_EINVAL and changes nothing. */
 int sts_set_noise(sts_engine* e, float noise_scale, float noise_scale_w, uint64_t seed);
 int sts_get_noise(const sts_engine* e, float* noise_scale, float* noise_scale_w, uint64_t* seed);
-/*   record intermediate tensors of the next run: "x_enc","m","logs","logw","z_p","z","wave" ("logs": the second half of the
- *   encoder projection, computed only by runs that record taps or sample the prior) */
+/* ---- output sample rate (no reference counterpart: every model produces 16 kHz).  sts_set_output_rate(e, rate): 0 or 16000 = native
+ * (the default; no extra work, bit-identical to an engine that never set a rate), otherwise an integer rate in [8000, 48000]: the decoder's
+ * float wave is resampled on the device and every call form -- sts_infer_ids, sts_infer_ids_batch, sts_run_batch (counts, offsets,
+ * sts_copy_pcm_device / _host, sts_pcm_host_view), sts_infer_ids_stream -- returns int16 PCM at that rate.  The setting persists, like
+ * sts_set_noise.  An invalid rate answers STS_EINVAL and changes nothing.  sts_get_output_rate returns the effective rate (16000 = native).
+ *   The filter (in = 16000, out = the rate; exactly what sts_resample_table returns):
+ *     g = gcd(in, out), P = out / g, Q = in / g; P > 1024 is rejected (e.g. 47999).  L_out = ceil(L_in P / Q) per utterance.
+ *     Output j sits at input position j Q / P: phase phi = (j Q) mod P, base n0 = (j Q) div P.
+ *     c = 0.9 min(1, out / in) (cutoff in units of the input Nyquist), W = 32 / c, K = ceil(W): 2K taps per phase.
+ *     Tap m (0 <= m < 2K) of phase phi reads input n0 - K + 1 + m at offset d = phi / P + K - 1 - m, coefficient
+ *     h = c sinc(c d) I0(beta sqrt(1 - (d / W)^2)) / I0(beta) for |d| < W, else 0; beta = 10, sinc(x) = sin(pi x) / (pi x).
+ *     Designed in float64, every phase normalised to sum 1, rounded to float32: table [P][2K].  Input outside the utterance is 0.
+ *     y_j = the fp32 FMA chain over m = 0 .. 2K-1; PCM = the reference's cast (int16)(int32)(y_j * 32737).
+ *   Streaming: a chunk covering native samples [a, b) emits the outputs ceil(a P / Q) <= j < ceil(b P / Q) (the last one through L_out);
+ *   sample_offset counts output samples.  The decode halo grows by ceil(K / samples_per_frame) frames (sts_stream_halo_frames reports the
+ *   halo at the current rate).  Taps: "wave" stays the native float wave; "wave_out" (non-native rate only) is y before the cast. */
+int sts_set_output_rate(sts_engine* e, int32_t rate);
+int sts_get_output_rate(const sts_engine* e);
+/* Host only (no device): the design above for in_rate -> out_rate (both integers in [8000, 48000]).  *P, *Q, *taps (= 2K) are set when
+ * non-null; table == NULL asks for the sizes only, otherwise it receives the float32 [P][taps] table the kernel uses (capacity_floats
+ * below P * taps: STS_EINVAL). */
+int sts_resample_table(int32_t in_rate, int32_t out_rate, int32_t* P, int32_t* Q, int32_t* taps, float* table, int64_t capacity_floats);
+/*   record intermediate tensors of the next run: "x_enc","m","logs","logw","z_p","z","wave","wave_out" ("logs": the second half of the
+ *   encoder projection, computed only by runs that record taps or sample the prior; "wave_out": the resampled float wave, only at a
+ *   non-native output rate, one-pass calls) */
 int sts_set_record_taps(sts_engine* e, int enable);
 /*   fetch a tap: malloc()'d copy, channel-major [channels][total_len] (== the reference's column-major
  *   MatrixXf [time, channels]); for batches the utterances are packed along time. */
@@ -188,7 +212,7 @@ int sts_set_profiling(sts_engine* e, int enable);
  * sizeof(sts_profile)) bytes, so a client compiled against an older header passes ITS sizeof and is never overrun;
  * sts_get_profile(e, p) == sts_get_profile_ex(e, p, sizeof(sts_profile)) of the header this library was built from -- use it only
  * when client and library are built together. */
-#define STS_ABI_VERSION 8
+#define STS_ABI_VERSION 9
 int sts_abi_version(void);
 /* bit 0: lab build (-DSTS_EXPERIMENTS: environment knobs of knobs.hpp, every conv tile code);
  * 0 for the shipped library */
@@ -248,6 +272,9 @@ const char* sts_pool_last_error(void);
  *   Requests with different noise settings share one packed batch. */
 int64_t sts_pool_submit_ex(sts_pool* p, const int32_t* ids, int32_t n, int32_t sid, float length_scale, float noise_scale,
                            float noise_scale_w, uint64_t seed);
+/*   sts_pool_set_output_rate: sts_set_output_rate on every engine of the pool.  STS_ESTATE while any request is outstanding (submitted and
+ *   not yet collected by sts_pool_wait), so that one batch never mixes rates. */
+int sts_pool_set_output_rate(sts_pool* p, int32_t rate);
 
 /* ---- multi-device batch (no reference counterpart).  One host process drives n_devices GPUs:
  * one engine (weights replicated) and one worker thread per entry of `devices` (HIP device indices; an index may repeat,
@@ -278,6 +305,8 @@ int sts_multi_set_conv_math(sts_multi* m, int mode);
 /*   sts_multi_set_noise: sts_set_noise for the handle; utterance b of a batch samples with seed + b (b = its index in the caller's
  *   batch, not within a device's shard: the PCM does not depend on the number of devices). */
 int sts_multi_set_noise(sts_multi* m, float noise_scale, float noise_scale_w, uint64_t seed);
+/*   sts_multi_set_output_rate: sts_set_output_rate on every engine of the handle; both gathers then exchange counts in output samples. */
+int sts_multi_set_output_rate(sts_multi* m, int32_t rate);
 /*   test hook: the shared library that provides the nccl* entry points (NULL / "" = librccl.so.1) and whether STS_MULTI_RCCL may list
  *   one device several times (tests/fake_rccl: N emulated ranks on one GPU; real RCCL refuses duplicates).  Only before the first
  *   STS_MULTI_RCCL handle of the process is created.  TEST-ONLY: refused with STS_ESTATE unless the process environment carries

@@ -43,7 +43,7 @@ int sts_get_info(const sts_engine* e, sts_model_info* info) {
     info->is_multi_speaker = m.is_ms; info->lang_type = m.lang; info->dur_pred_type = m.dur_type; info->dec_type = m.dec_type;
     info->vocab = m.vocab; info->hidden = m.hidden; info->inter_channels = m.inter;
     info->speaker_num = m.spk_num == 0 ? 1 : m.spk_num; info->gin_channels = m.gin;
-    info->samples_per_frame = m.hop_total; info->sample_rate = 16000;
+    info->samples_per_frame = m.hop_total; info->sample_rate = kNativeRate;   // (the model's native rate, whatever sts_set_output_rate selects)
     info->blob_floats_consumed = m.consumed;
     return STS_OK;
 }
@@ -135,7 +135,7 @@ int sts_infer_ids_stream(sts_engine* e, const int32_t* ids, int32_t n, int32_t s
 
 int sts_stream_halo_frames(const sts_engine* e) {
     if (!e) return set_err(STS_EINVAL, "null engine");
-    return decoder_halo_frames(e->eng.model);
+    return e->eng.stream_halo();
 }
 
 int sts_set_forced_durations(sts_engine* e, const int32_t* dur, int64_t count) {
@@ -190,6 +190,27 @@ int sts_set_host_pcm(sts_engine* e, int enable) { if (!e) return set_err(STS_EIN
 int sts_set_profiling(sts_engine* e, int enable) { if (!e) return set_err(STS_EINVAL, "null engine"); e->eng.profiling = enable == 2 ? 2 : (enable != 0 ? 1 : 0); return STS_OK; }
 
 int sts_abi_version(void) { return STS_ABI_VERSION; }
+
+int sts_set_output_rate(sts_engine* e, int32_t rate) {
+    if (!e) return set_err(STS_EINVAL, "null engine");
+    const int rc = e->eng.set_output_rate(rate);
+    return rc == STS_OK ? STS_OK : set_err(rc, e->eng.error());
+}
+int sts_get_output_rate(const sts_engine* e) {
+    if (!e) return set_err(STS_EINVAL, "null engine");
+    return e->eng.out_rate;
+}
+int sts_resample_table(int32_t in_rate, int32_t out_rate, int32_t* P, int32_t* Q, int32_t* taps, float* table, int64_t capacity_floats) {
+    ResampleDesign d;
+    if (!resample_design(in_rate, out_rate, &d)) return set_err(STS_EINVAL, "rates must be integers in [8000, 48000] with P = out / gcd(in, out) <= 1024");
+    const int64_t need = (int64_t)d.P * 2 * d.K;
+    if (table && capacity_floats < need) return set_err(STS_EINVAL, "table capacity below P * taps floats");
+    if (P) *P = d.P;
+    if (Q) *Q = d.Q;
+    if (taps) *taps = 2 * d.K;
+    if (table) resample_table(d, in_rate, out_rate, table);
+    return STS_OK;
+}
 int sts_build_flags(void) {
 #ifdef STS_EXPERIMENTS
     return 1;

@@ -31,6 +31,7 @@ Engine::~Engine() {
     if (arenaF_.base) (void)hipFree(arenaF_.base);
     if (pinned_) (void)hipHostFree(pinned_);
     if (pinned_pcm_) (void)hipHostFree(pinned_pcm_);
+    if (d_rs_table) (void)hipFree(d_rs_table);
     if (ovf_host_) (void)hipHostFree(ovf_host_);
     if (hmap_) (void)hipHostFree(hmap_);
     if (arrive_) (void)hipFree(arrive_);
@@ -325,6 +326,29 @@ void Engine::tap(const char* name, const float* d, int channels, long ld, long l
 
 // Frames of z (per side) that influence one output sample through the decoder: conv_pre, every upsampler,
 // the widest ResBlock chain of every stage, and the tail.  Conservative (rounded up at every level).
+// sts_set_output_rate: the filter's table is built on the host and uploaded once here, not per call.  An invalid rate changes nothing.
+int Engine::set_output_rate(int rate) {
+    if (rate == 0) rate = kNativeRate;
+    ResampleDesign d;
+    if (rate != kNativeRate && !resample_design(kNativeRate, rate, &d)) return fail(STS_EINVAL, "output rate must be 0 or an integer in [8000, 48000] with P = rate / gcd(16000, rate) <= 1024");
+    if (rate == out_rate) return STS_OK;
+    if (rate == kNativeRate) { out_rate = rate; rs = ResampleDesign(); return STS_OK; }   // (the table stays allocated for a later rate)
+    std::vector<float> h((size_t)d.P * 2 * d.K);
+    resample_table(d, kNativeRate, rate, h.data());
+    HIPCK(hipSetDevice(device));
+    if (stream) HIPCK(hipStreamSynchronize(stream));
+    float* t = nullptr;        // (the old table stays in place until the new one is on the device)
+    HIPCK(hipMalloc((void**)&t, h.size() * sizeof(float)));
+    if (hipMemcpy(t, h.data(), h.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) { (void)hipFree(t); return fail(STS_EDEVICE, "resampler table upload failed"); }
+    if (d_rs_table) (void)hipFree(d_rs_table);
+    d_rs_table = t; out_rate = rate; rs = d;
+    return STS_OK;
+}
+int Engine::stream_halo() const {
+    const int h = decoder_halo_frames(model);
+    return resampling() ? h + (rs.K + model.hop_total - 1) / model.hop_total : h;
+}
+
 int decoder_halo_frames(const Model& M) {
     double R = M.dec_type == 0 ? (M.conv_post.k - 1) / 2 : (M.conv_post.k - 1) / 2 + 12;   // tail: reflect pad, iSTFT overlap, synthesis FIR
     const int nk = M.n_resk;
@@ -355,6 +379,7 @@ struct BufF {
     float *z, *h, *acts, *out, *x0, *regA, *regB, *tailA, *tailB, *tailC, *wave, *fliptmp;
     float *ff_h[2], *ff_part[2], *ff_macc[2], *ff_alt;        // one-launch-per-layer flow (wn_flow.hip): channel-minor h / partial sums / -m slices, alternate home of a z half
     int16_t* pcm;
+    int16_t* pcm_nat; float* wave_out;   // at a non-native output rate: the decoder tail's own int16 samples (not returned), the resampled float wave (taps)
 };
 
 // Everything a run's stages share: batch geometry, workspace pointers, host / device tables.  Engine::run() fills it stage by
@@ -379,6 +404,7 @@ struct Engine::RunCtx {
     std::vector<Engine::Noise> nz; bool any_ns = false, any_nsw = false;   // per-utterance sampling noise (engine.hpp Noise), which of the two is used
     std::vector<unsigned long long> req_keys; std::vector<long> predF;      // launch-ahead memo: per-utterance request hashes, remembered frame counts (empty: not all known)
     int halo = 0; long Wcap = 0; int upS = 1; long Lsb = 0; int sbC = 0;
+    long long Ocap = 0;             // PCM capacity in output samples (== Wcap * hop at the native rate)
     bool use_ff = false; int ffG = 0;
 };
 #define RUN_ALIASES(c)                                                                                                              \
@@ -833,7 +859,7 @@ int Engine::frame_geometry(RunCtx& c) {
     }
     h_pcm = nullptr; pcm_in_host_ = false;
     if (host_pcm && !ss) {   // room for the PCM download that rides at the end of this run
-        const size_t need = (size_t)c.Fld * hop * 2 + 256;
+        const size_t need = (size_t)(resampling() ? out_count((long long)c.Fld * hop) + B : (long long)c.Fld * hop) * 2 + 256;
         if (need > pinned_pcm_cap_) {
             if (pinned_pcm_) (void)hipHostFree(pinned_pcm_);
             pinned_pcm_ = nullptr; pinned_pcm_cap_ = 0;
@@ -855,7 +881,7 @@ int Engine::run_frame_workspace(RunCtx& c) {
     int* const p_lenF = c.p_lenF; int* const d_offF = c.d_offF; int* const d_lenF = c.d_lenF;
     // ---------------- frame-level workspace.  The flow works on all Ftot frames; the decoder works on
     // "windows" of z: whole utterances normally (Wcap == Ftot), one chunk plus its two halos when streaming.
-    const int halo = c.halo = decoder_halo_frames(M);
+    const int halo = c.halo = stream_halo();
     const long Wcap = c.Wcap = ss ? std::min<long>(Ftot, (long)ss->chunk_frames + 2 * halo) : Ftot;
     int upS = 1;
     for (int u : M.up_rate) upS *= u;
@@ -897,17 +923,21 @@ int Engine::run_frame_workspace(RunCtx& c) {
             bf.tailA = A.get<float>((size_t)sbC * Lsb); bf.tailB = A.get<float>((size_t)sbC * Lsb);
             bf.tailC = A.get<float>((size_t)4 * Wcap * upS * 4);
         } else { bf.tailA = bf.tailB = bf.tailC = nullptr; }
-        bf.wave = A.get<float>(record_taps ? (size_t)Wcap * hop : 1);
-        bf.pcm = A.get<int16_t>((size_t)Wcap * hop);
+        bf.wave = A.get<float>(record_taps || resampling() ? (size_t)Wcap * hop : 1);
+        bf.pcm = A.get<int16_t>((size_t)c.Ocap);
+        bf.pcm_nat = resampling() ? A.get<int16_t>((size_t)Wcap * hop) : bf.pcm;
+        bf.wave_out = record_taps && resampling() ? A.get<float>((size_t)c.Ocap) : nullptr;
     };
+    c.Ocap = resampling() ? out_count((long long)Wcap * hop) + B : (long long)Wcap * hop;
     arenaF_.measuring = true; layoutF(arenaF_);
     if (!ensure(arenaF_, arenaF_.used + 4096)) return fail(STS_EDEVICE, "out of device memory (frame-level workspace)");
     arenaF_.measuring = false; layoutF(arenaF_);
     // one short utterance with the PCM wanted on the host: the decoder's last kernel stores its int16 samples into the mapped pinned
     // buffer itself (posted writes over the host link, under the kernel's own run time) instead of a download queued behind it
-    if (pcm_direct && host_pcm && !ss && B == 1 && !record_taps && pinned_pcm_dev_ && (size_t)Wcap * hop * 2 + 256 <= pinned_pcm_cap_ &&
-        (size_t)Wcap * hop * 2 <= ((size_t)4 << 20)) {
+    if (pcm_direct && host_pcm && !ss && B == 1 && !record_taps && pinned_pcm_dev_ && (size_t)c.Ocap * 2 + 256 <= pinned_pcm_cap_ &&
+        (size_t)c.Ocap * 2 <= ((size_t)4 << 20)) {
         bf.pcm = pinned_pcm_dev_;
+        if (!resampling()) bf.pcm_nat = bf.pcm;     // (native rate: the tail's own samples are the PCM; otherwise the resampler writes there)
         pcm_in_host_ = true;
     }
 
@@ -1340,10 +1370,13 @@ int Engine::run_decode(RunCtx& c, int nw, long Wtot, int maxW, int zoff0, int wl
     mark(6);
 
     // ---------------- decoder tail
-    float* wave = record_taps ? bf.wave : nullptr;
+    // (at a non-native output rate the tail always writes the float wave, and its int16 samples go to a scratch buffer: the resampler below
+    // produces the PCM from the wave)
+    float* wave = record_taps || resampling() ? bf.wave : nullptr;
+    int16_t* const pcm = bf.pcm_nat;
     const long Ntot = Wtot * hop;
     if (M.dec_type == 0) {          // Generator_hifigan.cpp:177-179 + SynthesizerTrn.cpp:389-396
-        ConvOpt o; o.in_act = 1; o.slope = 1e-2f; o.epi = EPI_TANH_PCM; o.pcm = bf.pcm; o.aux = wave;
+        ConvOpt o; o.in_act = 1; o.slope = 1e-2f; o.epi = EPI_TANH_PCM; o.pcm = pcm; o.aux = wave;
         with_mean(o);
         conv(M.conv_post, x, lx, nullptr, lx, o);
     } else {                        // Generator_MBB.cpp:174-202, Generator_MS.cpp:198-228, Generator_Istft.cpp:180-197
@@ -1356,27 +1389,49 @@ int Engine::run_decode(RunCtx& c, int nw, long Wtot, int maxW, int zoff0, int wl
         if (tail_fused && M.dec_type != 2 && sbC == 72 && istft_tail_fused_ok(bands, M.fir_taps, M.fir_pad)) {
             // spectrum + inverse DFT / overlap-add + synthesis filter + int16 cast in one launch (misc_kernels.hip istft_tail_fused_kernel)
             const Lvl lo = lvF(S * 16, 0);
-            istft_tail_fused(bf.tailA, lsb.ld, lsb.seg, M.synth_fir, M.fir_taps, M.fir_pad, (float)M.subbands, M.fir_bias, wave, bf.pcm, lo.seg, nw, ltm.max_len, stream);
+            istft_tail_fused(bf.tailA, lsb.ld, lsb.seg, M.synth_fir, M.fir_taps, M.fir_pad, (float)M.subbands, M.fir_bias, wave, pcm, lo.seg, nw, ltm.max_len, stream);
             flops_[3] += 2.0 * (double)Ntot * (16.0 * 4 + 4 * 18 * 4 / 4.0);
-            mark(4);
-            if (wave) tap("wave", wave, 1, Ntot, (wlen0 >= 0 ? (long)wlen0 : Wtot) * hop);
-            return STS_OK;
+            return decode_end(c, wave, nw, Wtot, maxW, wlen0);
         }
         istft_spectrum(bf.tailA, lsb.ld, sbC, bf.tailB, lsb.total, stream);
         float* tm = bf.tailC;
         istft_ola(bf.tailB, lsb.ld, bands, 18, lsb.seg, tm, ltm.ld, ltm.seg, nw, ltm.max_len, stream);
         if (M.dec_type == 2) {
-            quantize_pcm(tm, bf.pcm, Ntot, stream);
+            quantize_pcm(tm, pcm, Ntot, stream);
             if (wave) HIPCK(hipMemcpyAsync(wave, tm, (size_t)Ntot * 4, hipMemcpyDeviceToDevice, stream));
         } else {
             const Lvl lo = lvF(S * 16, 0);
-            synth_fir(tm, ltm.ld, ltm.seg, M.synth_fir, M.fir_taps, M.fir_pad, (float)M.subbands, M.fir_bias /* 0 unless the blob's learned filter carries one (MS); the PQMF bank has none */, wave, bf.pcm, lo.seg, nw,
+            synth_fir(tm, ltm.ld, ltm.seg, M.synth_fir, M.fir_taps, M.fir_pad, (float)M.subbands, M.fir_bias /* 0 unless the blob's learned filter carries one (MS); the PQMF bank has none */, wave, pcm, lo.seg, nw,
                       ltm.max_len, stream);
         }
         flops_[3] += 2.0 * (double)Ntot * (16.0 * 4 + 4 * 18 * 4 / 4.0);
     }
+    return decode_end(c, wave, nw, Wtot, maxW, wlen0);
+}
+
+// the end of a decode: the "wave" tap; at a non-native output rate (and not streaming: run_output resamples each chunk) the resampler, which
+// writes the PCM of every window at the output rate, packed window after window
+int Engine::decode_end(RunCtx& c, const float* wave, int nw, long Wtot, int maxW, int wlen0) {
+    const int hop = c.hop;
+    if (resampling() && !c.ss) {
+        const bool winl = nw == 1 && !c.no_inline_seg && wlen0 >= 0;
+        ResampleArgs a{};
+        a.x = wave;
+        a.seg = winl ? SegView{nullptr, nullptr, hop, 0, 0, wlen0} : SegView{c.d_win + nw, c.d_win + 2 * nw, hop, 0, 0, 0};
+        a.table = d_rs_table; a.P = rs.P; a.Q = rs.Q; a.K = rs.K;
+        a.pcm = c.bf.pcm; a.wave_out = c.bf.wave_out;
+        resample_pcm(a, nw, out_count((long long)maxW * hop), stream);
+    }
     mark(4);
-    if (wave) tap("wave", wave, 1, Ntot, (wlen0 >= 0 ? (long)wlen0 : Wtot) * hop);
+    if (wave && record_taps) {
+        tap("wave", wave, 1, Wtot * hop, (wlen0 >= 0 ? (long)wlen0 : Wtot) * hop);
+        if (c.bf.wave_out && !c.ss) {
+            long long n = 0;
+            if (wlen0 >= 0) n = out_count((long long)wlen0 * hop);
+            else for (int b = 0; b < c.B; b++) n += out_count((long long)c.p_lenF[b] * hop);
+            tap("wave_out", c.bf.wave_out, 1, (long)c.Ocap, (long)n);
+        }
+    }
     return STS_OK;
 }
 
@@ -1464,7 +1519,7 @@ int Engine::run_output(RunCtx& c) {
         if (ahead) {
             // everything is enqueued.  The PCM download is queued for the CAPACITY (<= 63 frames more than needed) and the run's one
             // stream synchronisation happens before the count is looked at: the host never waits for the count by itself
-            if (host_pcm && !pcm_in_host_) HIPCK(hipMemcpyAsync(pinned_pcm_, bf.pcm, (size_t)Fld * hop * 2, hipMemcpyDeviceToHost, stream));
+            if (host_pcm && !pcm_in_host_) HIPCK(hipMemcpyAsync(pinned_pcm_, bf.pcm, (size_t)out_count((long long)Fld * hop) * 2, hipMemcpyDeviceToHost, stream));
             host_us_enq_ = (float)(now_us() - host_t0_);
             if ((rc = final_sync(c.Ttot)) != STS_OK) return rc;
             host_t_sync_ = now_us();
@@ -1485,10 +1540,11 @@ int Engine::run_output(RunCtx& c) {
         }
     }
     const long Fcount = c.Ftot;                // (from here on: the real count)
-    for (int b = 0; b < B; b++) n_samples[b] = p_lenF[b] * hop;
+    for (int b = 0; b < B; b++) n_samples[b] = (int32_t)out_count((long long)p_lenF[b] * hop);     // (at the output rate)
     if (!ss) {
         d_pcm = bf.pcm;
-        total_samples = Fcount * hop;
+        total_samples = 0;
+        for (int b = 0; b < B; b++) total_samples += n_samples[b];
         if (host_pcm) {
             if (!ahead && !pcm_in_host_) HIPCK(hipMemcpyAsync(pinned_pcm_, bf.pcm, (size_t)total_samples * 2, hipMemcpyDeviceToHost, stream));
             h_pcm = (const int16_t*)pinned_pcm_;
@@ -1526,7 +1582,7 @@ int Engine::run_output(RunCtx& c) {
         const long F = Fcount;
         int16_t* hp = nullptr;
         const size_t hp_off = (up_bytes + ((size_t)Ttot + B) * 4 + 255) & ~(size_t)255;
-        if (!ensure_pinned(hp_off + (size_t)ss->chunk_frames * hop * 2 + 256)) return fail(STS_EDEVICE, "pinned host allocation failed");
+        if (!ensure_pinned(hp_off + (size_t)(out_count((long long)ss->chunk_frames * hop) + 1) * 2 + 256)) return fail(STS_EDEVICE, "pinned host allocation failed");
         int* pm = c.pm = (int*)pinned_;
         hp = (int16_t*)(pinned_ + hp_off);
         int* pw = pm + 5 * B + 2;
@@ -1538,8 +1594,19 @@ int Engine::run_output(RunCtx& c) {
             HIPCK(hipMemcpyAsync(d_win, pw, 3 * 4, hipMemcpyHostToDevice, stream));
             const int rc = run_decode(c, 1, w1 - w0, (int)(w1 - w0), (int)w0, (int)(w1 - w0));
             if (rc != STS_OK) return rc;
-            const long ns = (f1 - f0) * hop;
-            HIPCK(hipMemcpyAsync(hp, bf.pcm + (f0 - w0) * hop, (size_t)ns * 2, hipMemcpyDeviceToHost, stream));
+            // native samples [f0 hop, f1 hop) of the utterance; at another output rate the outputs j with ceil(f0 hop P / Q) <= j < ceil(f1 hop P / Q),
+            // resampled from the window (the halo covers the filter's K samples beyond the chunk's edges too: stream_halo)
+            const long long j0 = out_count((long long)f0 * hop), j1 = out_count((long long)f1 * hop);
+            const long ns = (long)(j1 - j0);
+            if (resampling()) {
+                ResampleArgs a{};
+                a.x = bf.wave; a.seg = SegView{nullptr, nullptr, hop, 0, 0, (int)(w1 - w0)};
+                a.table = d_rs_table; a.P = rs.P; a.Q = rs.Q; a.K = rs.K;
+                a.pcm = bf.pcm; a.wave_out = nullptr;
+                a.stream = 1; a.u0 = (long long)w0 * hop; a.L_utt = (long long)F * hop; a.j0 = j0; a.j1 = j1;
+                resample_pcm(a, 1, j1 - j0, stream);
+            }
+            HIPCK(hipMemcpyAsync(hp, resampling() ? bf.pcm : bf.pcm + (f0 - w0) * hop, (size_t)ns * 2, hipMemcpyDeviceToHost, stream));
             HIPCK(hipStreamSynchronize(stream));
             if (conv_math == 3 && ovf_host_ && *(volatile unsigned*)ovf_host_ != 0u) {
                 if (f0 == 0) return kRetrySplitBf16;          // nothing has left yet (run() repeats the call)
@@ -1549,7 +1616,7 @@ int Engine::run_output(RunCtx& c) {
                 continue;
             }
             total_samples += ns;
-            if (ss->cb(ss->user, hp, (int32_t)ns, (int32_t)(f0 * hop)) != 0) break;
+            if (ss->cb(ss->user, hp, (int32_t)ns, (int32_t)j0) != 0) break;
         }
         HIPCK(hipGetLastError());
     }

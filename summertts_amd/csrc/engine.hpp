@@ -52,6 +52,7 @@ int decoder_halo_frames(const Model& M);
 inline bool noise_scale_valid(float s) { return s >= 0.f && s <= 3.0e38f; }   // (false for NaN and +inf)
 
 struct Tap { std::vector<float> data; int channels = 0; long length = 0; };
+constexpr int kNativeRate = 16000;   // every model of the reference produces 16 kHz (test/main.cpp:13,16)
 
 class Engine {
 public:
@@ -83,6 +84,15 @@ public:
     struct Noise { float ns = 0.f, nsw = 0.f; uint64_t seed = 0; };
     Noise noise;
     std::vector<Noise> noise_utt;      // when it holds B entries: the per-utterance settings of a B-utterance run instead (sts_pool, sts_multi)
+    // output sample rate (sts_set_output_rate): kNativeRate = the decoder's own samples, nothing extra runs; otherwise every call's PCM is
+    // the decoder's float wave resampled on the device (resample.hip).  rs: the filter; d_rs_table: its [P][2K] table, uploaded by set
+    int out_rate = kNativeRate;
+    ResampleDesign rs;
+    float* d_rs_table = nullptr;
+    bool resampling() const { return out_rate != kNativeRate; }
+    long long out_count(long long native) const { return resampling() ? (native * rs.P + rs.Q - 1) / rs.Q : native; }   // L_out = ceil(L_in P / Q)
+    int set_output_rate(int rate);
+    int stream_halo() const;           // decoder halo frames of a streaming chunk at the current rate (+ the resampler's K samples)
     std::vector<int32_t> forced_dur; bool have_forced = false;
     bool record_taps = false; int profiling = 0;       // profiling: 0 off, 1 all stage events, 2 the matrix-core region's two events only (sts_set_profiling)
     int conv_mode = 0;
@@ -138,6 +148,7 @@ private:
     int run_frame_workspace(RunCtx& c);
     int run_flow(RunCtx& c);
     int run_decode(RunCtx& c, int nw, long Wtot, int maxW, int zoff0, int wlen0);
+    int decode_end(RunCtx& c, const float* wave, int nw, long Wtot, int maxW, int wlen0);
     int wait_frame_counts(RunCtx& c);
     int frame_geometry(RunCtx& c);
     int run_output(RunCtx& c);

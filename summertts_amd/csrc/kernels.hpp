@@ -334,4 +334,21 @@ void istft_tail_fused(const float* sb, long ld, SegView seg_frames, const float*
 // pcm = (int16)(int32)(wave * 32737)   (SynthesizerTrn.cpp:389-396: truncation, wrap-around)
 void quantize_pcm(const float* wave, int16_t* pcm, long n, hipStream_t st);
 
+// Output sample-rate conversion (resample.hip; the filter is defined there and in include/summertts_hip.h sts_resample_table)
+constexpr int kResampleMinRate = 8000, kResampleMaxRate = 48000, kResampleMaxP = 1024, kResampleMaxK = 72;
+struct ResampleDesign { int P = 1, Q = 1, K = 0; };
+// false: a rate outside [8000, 48000] or P > 1024
+bool resample_design(int in_rate, int out_rate, ResampleDesign* d);
+// the float32 table [P][2K] (host, float64 design)
+void resample_table(const ResampleDesign& d, int in_rate, int out_rate, float* table);
+struct ResampleArgs {
+    const float* x; SegView seg;         // native float wave, windows in frames (scale = samples per frame)
+    const float* table; int P, Q, K;
+    int16_t* pcm; float* wave_out;       // outputs, packed utterance after utterance; wave_out optional (taps)
+    // streaming (one window): the window holds utterance samples [u0, u0 + len) of L_utt; outputs [j0, j1) go to pcm[0 ..)
+    int stream; long long u0, L_utt, j0, j1;
+};
+// grid: nwin windows x ceil(max_out / 1024) tiles; max_out = the most outputs one window emits
+void resample_pcm(const ResampleArgs& a, int nwin, long long max_out, hipStream_t st);
+
 }  // namespace sts

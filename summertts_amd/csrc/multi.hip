@@ -376,6 +376,16 @@ int sts_multi_set_noise(sts_multi* m, float noise_scale, float noise_scale_w, ui
     m->noise = Engine::Noise{noise_scale, noise_scale_w, seed};
     return STS_OK;
 }
+int sts_multi_set_output_rate(sts_multi* m, int32_t rate) {
+    if (!m) return multi_err(STS_EINVAL, "null handle");
+    ResampleDesign d;
+    if (rate != 0 && rate != kNativeRate && !resample_design(kNativeRate, rate, &d)) return multi_err(STS_EINVAL, "output rate must be 0 or an integer in [8000, 48000] with P <= 1024");
+    for (auto& e : m->engines) {      // (every engine's sample counts -- and so the gathers' counts -- are then in output samples)
+        const int rc = e->set_output_rate(rate);
+        if (rc != STS_OK) return multi_err(rc, e->error());
+    }
+    return STS_OK;
+}
 int sts_multi_set_conv_math(sts_multi* m, int mode) {
     if (!m) return multi_err(STS_EINVAL, "null handle");
     if (mode < 0 || mode > 3) return multi_err(STS_EINVAL, "conv math must be 0..3");

@@ -177,6 +177,20 @@ int sts_pool_wait(sts_pool* p, int64_t ticket, int16_t** pcm_out, int32_t* n_out
     return STS_OK;
 }
 
+int sts_pool_set_output_rate(sts_pool* p, int32_t rate) {
+    if (!p) return pool_err(STS_EINVAL, "null pool");
+    std::lock_guard<std::mutex> lk(p->mu);
+    // a request stays pending from submit to wait: with none pending no worker runs, and one batch never mixes rates
+    if (!p->pending.empty()) return pool_err(STS_ESTATE, "requests are outstanding: wait for them before changing the output rate");
+    ResampleDesign d;
+    if (rate != 0 && rate != kNativeRate && !resample_design(kNativeRate, rate, &d)) return pool_err(STS_EINVAL, "output rate must be 0 or an integer in [8000, 48000] with P <= 1024");
+    for (auto& e : p->engines) {
+        const int rc = e->set_output_rate(rate);
+        if (rc != STS_OK) return pool_err(rc, e->error());
+    }
+    return STS_OK;
+}
+
 int sts_pool_stats(sts_pool* p, int64_t* batches, int64_t* requests) {
     if (!p) return pool_err(STS_EINVAL, "null pool");
     std::lock_guard<std::mutex> lk(p->mu);

@@ -103,6 +103,12 @@ def load_library() -> C.CDLL:
     lib.sts_get_durations.argtypes = [C.c_void_p, C.c_void_p, C.c_int64]
     lib.sts_set_noise.argtypes = [C.c_void_p, C.c_float, C.c_float, C.c_uint64]
     lib.sts_get_noise.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_uint64)]
+    lib.sts_set_output_rate.argtypes = [C.c_void_p, C.c_int32]
+    lib.sts_get_output_rate.argtypes = [C.c_void_p]
+    lib.sts_resample_table.argtypes = [C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                                       C.c_void_p, C.c_int64]
+    lib.sts_pool_set_output_rate.argtypes = [C.c_void_p, C.c_int32]
+    lib.sts_multi_set_output_rate.argtypes = [C.c_void_p, C.c_int32]
     lib.sts_free.argtypes = [C.c_void_p]
     lib.sts_debug_conv1d.argtypes = [C.c_int, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32,
                                      C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_int32,
@@ -122,7 +128,19 @@ EXPORTED_SYMBOLS = [
     "sts_multi_create", "sts_multi_destroy", "sts_multi_device_count", "sts_multi_speaker_num", "sts_multi_infer_ids_batch",
     "sts_multi_shard_of", "sts_multi_last_error", "sts_multi_set_rccl_library", "sts_multi_rccl_ranks", "sts_multi_last_gather_ms", "sts_multi_set_conv_math", "sts_get_profile_ex", "sts_abi_version", "sts_build_flags",
     "sts_set_noise", "sts_get_noise", "sts_pool_submit_ex", "sts_multi_set_noise",
+    "sts_set_output_rate", "sts_get_output_rate", "sts_resample_table", "sts_pool_set_output_rate", "sts_multi_set_output_rate",
 ]
+
+
+def resample_table(in_rate: int, out_rate: int):
+    """The output-rate filter of the library (include/summertts_hip.h sts_resample_table; host only, no GPU): -> (P, Q, table), table the
+    float32 [P][taps] coefficients the resampling kernel uses."""
+    lib = load_library()
+    P, Q, taps = C.c_int32(), C.c_int32(), C.c_int32()
+    _check(lib, lib.sts_resample_table(int(in_rate), int(out_rate), C.byref(P), C.byref(Q), C.byref(taps), None, 0))
+    t = np.zeros((P.value, taps.value), np.float32)
+    _check(lib, lib.sts_resample_table(int(in_rate), int(out_rate), None, None, None, t.ctypes.data, t.size))
+    return P.value, Q.value, t
 
 
 def lab_build() -> bool:
@@ -259,6 +277,14 @@ class Synthesizer:
         ns, nsw, seed = C.c_float(), C.c_float(), C.c_uint64()
         _check(self.lib, self.lib.sts_get_noise(self.h, C.byref(ns), C.byref(nsw), C.byref(seed)))
         return ns.value, nsw.value, seed.value
+
+    def set_output_rate(self, rate: int):
+        """PCM sample rate of every later call (include/summertts_hip.h sts_set_output_rate): 0 or 16000 = the model's native rate, else an
+        integer in [8000, 48000], resampled on the device.  An invalid rate raises and leaves the setting unchanged."""
+        _check(self.lib, self.lib.sts_set_output_rate(self.h, int(rate)))
+
+    def output_rate(self) -> int:
+        return int(self.lib.sts_get_output_rate(self.h))
 
     def set_conv_math(self, mode):
         """Arithmetic of the decoder trunk convs: 0 / 'bf16x3' = fp32 operands as three bf16 terms on the bf16 matrix cores,
@@ -429,6 +455,12 @@ class Pool:
         self.lib.sts_free(p)
         return out
 
+    def set_output_rate(self, rate: int):
+        """``Synthesizer.set_output_rate`` for every engine of the pool; raises while any request is outstanding (STS_ESTATE)."""
+        rc = self.lib.sts_pool_set_output_rate(self.h, int(rate))
+        if rc != 0:
+            raise StsError(f"sts_pool_set_output_rate: {rc}: {self.lib.sts_pool_last_error().decode()}")
+
     def stats(self):
         b, r = C.c_int64(), C.c_int64()
         self.lib.sts_pool_stats(self.h, C.byref(b), C.byref(r))
@@ -501,6 +533,12 @@ class MultiDevice:
         self.lib.sts_multi_set_noise.argtypes = [C.c_void_p, C.c_float, C.c_float, C.c_uint64]
         if self.lib.sts_multi_set_noise(self.h, float(noise_scale), float(noise_scale_w), int(seed) & 0xFFFFFFFFFFFFFFFF) != 0:
             raise StsError(f"sts_multi_set_noise: {self.lib.sts_multi_last_error().decode()}")
+
+    def set_output_rate(self, rate: int):
+        """``Synthesizer.set_output_rate`` for every device; the gathers then count output samples."""
+        rc = self.lib.sts_multi_set_output_rate(self.h, int(rate))
+        if rc != 0:
+            raise StsError(f"sts_multi_set_output_rate: {rc}: {self.lib.sts_multi_last_error().decode()}")
 
     def set_conv_math(self, mode):
         m = {"bf16x3": 0, "f32": 1, "bf16x3_all": 2, "f16x2": 3}.get(mode, mode)
