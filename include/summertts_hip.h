@@ -75,6 +75,28 @@ int sts_infer_ids_stream(sts_engine* e, const int32_t* ids, int32_t n, int32_t s
  * of the resampler: see sts_set_output_rate) */
 int sts_stream_halo_frames(const sts_engine* e);
 
+/* Batched streaming (ABI 10): B utterances streamed together, chunk by chunk.  Text encoder, duration predictor and flow run once as
+ * a packed batch of B (as sts_infer_ids_batch; forced durations likewise; sampling noise: utterance b uses seed + b).  Then step k decodes
+ * chunk k of every utterance still live -- frames [k C, min((k + 1) C, F_b)) of utterance b, C = chunk_frames, F_b its frame count -- each
+ * from the window [max(0, f0 - halo), min(F_b, f1 + halo)) (halo = sts_stream_halo_frames), all windows of the step in one decode pass.
+ * The decoder's workspace holds sum_b min(F_b, C + 2 halo) frames, not the whole batch.
+ *   Delivery: step by step; within a step in ascending `utt`; all chunks of a step reach the caller before the next step starts.  An
+ *   utterance leaves the steps once its last chunk is delivered.  sample_offset counts output samples of that utterance at the current
+ *   output rate: chunk k starts at ceil(k C hop P / Q) (k C hop at the native rate), as in sts_infer_ids_stream.  `pcm` is only valid
+ *   during the callback.  A non-zero return stops THAT utterance only: it receives nothing more, the others go on unchanged.
+ *   n_total (may be NULL): [B] samples delivered per utterance.  sid and length_scale may be NULL (0 and 1.0).
+ *   Equality: each utterance's concatenated chunks equal its sts_infer_ids_stream output and member b of sts_infer_ids_batch bit for bit
+ *   when the kernel variant is pinned (sts_set_conv_mode), and to within 1 LSB under the automatic choice.  B == 1 is
+ *   sts_infer_ids_stream itself, bit for bit in every mode.
+ *   conv math 3: an activation beyond fp16's range before anything was delivered repeats the whole call in form 0; at a later step that
+ *   step is decoded again in form 0 for all of its windows, and so are the steps after it.  No chunk is delivered twice, and
+ *   sts_profile.conv_math_fallbacks counts the call once.
+ *   B < 1, chunk_frames <= 0, a NULL callback or NULL ids / n: STS_EINVAL, nothing runs. */
+typedef int (*sts_batch_chunk_cb)(void* user, int32_t utt, const int16_t* pcm, int32_t n_samples, int32_t sample_offset);
+int sts_infer_ids_batch_stream(sts_engine* e, int32_t B, const int32_t* const* ids, const int32_t* n, const int32_t* sid,
+                               const float* length_scale, int32_t chunk_frames, sts_batch_chunk_cb cb, void* user,
+                               int32_t* n_total);
+
 /* Batched form (new capability; the reference processes exactly one utterance per call).  The B
  * utterances are packed along time on the device and run through every kernel together.
  * pcm_out[b] is malloc()'d per utterance. */
@@ -179,6 +201,10 @@ enum { STS_DBG_ATTN_BLOCK_MIN_WGS = 1,
        STS_DBG_ATTN_REG = 7 /* one-query attention: 1 (default) operands in registers (attention_reg_kernel), 0 the round-1 kernel */,
        STS_DBG_LAUNCH_AHEAD = 6 /* one-utterance calls and packed batches: 1 (default) a request the engine has served before (same ids, speaker, length scale: the frame count is a pure function of them) enqueues flow + decoder before the count reaches the host, 0 the host always waits for it, 2 (tests) the memo is keyed by the phoneme count alone -- provokes the repeat that answers a hash collision */,
        STS_DBG_FLOW_FUSED = 5 /* reverse flow: 1 (default) one launch per WaveNet layer (wn_flow.hip, under the two-term fp16 arithmetic), 0 one launch per conv */ };
+/* ABI 10, sts_infer_ids_batch_stream: STS_DBG_STREAM_RETRY_STEP (tests) -- under conv math 3 the overflow word counts as raised after step k
+ * (value k; -1 = off), which takes the split-bf16 repeat of that step (k > 0) or of the whole call (k = 0); STS_DBG_STREAM_DIRECT -- 1 the
+ * last kernel of a step writes the step's chunks into mapped pinned host memory itself, 0 (default) one download per step */
+enum { STS_DBG_STREAM_RETRY_STEP = 16, STS_DBG_STREAM_DIRECT = 17 };
 int sts_debug_set(sts_engine* e, int key, int value);
 
 /* Per-stage device timing of the last run, measured with HIP events on the engine's own stream. */
@@ -212,7 +238,7 @@ int sts_set_profiling(sts_engine* e, int enable);
  * sizeof(sts_profile)) bytes, so a client compiled against an older header passes ITS sizeof and is never overrun;
  * sts_get_profile(e, p) == sts_get_profile_ex(e, p, sizeof(sts_profile)) of the header this library was built from -- use it only
  * when client and library are built together. */
-#define STS_ABI_VERSION 9
+#define STS_ABI_VERSION 10
 int sts_abi_version(void);
 /* bit 0: lab build (-DSTS_EXPERIMENTS: environment knobs of knobs.hpp, every conv tile code);
  * 0 for the shipped library */
@@ -275,6 +301,15 @@ int64_t sts_pool_submit_ex(sts_pool* p, const int32_t* ids, int32_t n, int32_t s
 /*   sts_pool_set_output_rate: sts_set_output_rate on every engine of the pool.  STS_ESTATE while any request is outstanding (submitted and
  *   not yet collected by sts_pool_wait), so that one batch never mixes rates. */
 int sts_pool_set_output_rate(sts_pool* p, int32_t rate);
+/*   sts_pool_submit_stream (ABI 10): a streaming request.  A worker that takes one from the head of the FIFO folds in further queued
+ *   streaming requests with the same chunk_frames (up to max_batch) and runs them as one batched stream (sts_infer_ids_batch_stream);
+ *   streaming and whole-utterance requests never share a batch.  `cb` receives this request's chunks ON THE WORKER THREAD (it must not
+ *   wait on its own ticket, nor on any other of the pool's tickets); a non-zero return stops this request only.  sts_pool_wait returns
+ *   after its last chunk (or its stop) with *pcm_out = NULL and *n_out = samples delivered.  A failure before any chunk of the batch has
+ *   left re-runs its members one by one; a failure after that completes every unfinished member's ticket with the error.  Returns a
+ *   ticket or a negative STS_E* code (STS_EINVAL: bad ids, chunk_frames <= 0, a NULL callback). */
+int64_t sts_pool_submit_stream(sts_pool* p, const int32_t* ids, int32_t n, int32_t sid, float length_scale, float noise_scale,
+                               float noise_scale_w, uint64_t seed, int32_t chunk_frames, sts_chunk_cb cb, void* user);
 
 /* ---- multi-device batch (no reference counterpart).  One host process drives n_devices GPUs:
  * one engine (weights replicated) and one worker thread per entry of `devices` (HIP device indices; an index may repeat,

@@ -133,6 +133,15 @@ int sts_infer_ids_stream(sts_engine* e, const int32_t* ids, int32_t n, int32_t s
     return STS_OK;
 }
 
+int sts_infer_ids_batch_stream(sts_engine* e, int32_t B, const int32_t* const* ids, const int32_t* n, const int32_t* sid,
+                               const float* length_scale, int32_t chunk_frames, sts_batch_chunk_cb cb, void* user, int32_t* n_total) {
+    if (!e) return set_err(STS_EINVAL, "null engine");
+    if (B < 1 || !ids || !n || chunk_frames <= 0 || !cb) return set_err(STS_EINVAL, "B >= 1, ids, n, a positive chunk size and a callback are required");
+    const int rc = e->eng.run_batch_stream(B, ids, n, sid, length_scale, chunk_frames, cb, user, n_total);
+    if (rc != STS_OK) return set_err(rc, e->eng.error());
+    return STS_OK;
+}
+
 int sts_stream_halo_frames(const sts_engine* e) {
     if (!e) return set_err(STS_EINVAL, "null engine");
     return e->eng.stream_halo();
@@ -183,6 +192,8 @@ int sts_debug_set(sts_engine* e, int key, int value) {
         case STS_DBG_ATTN_REG: e->eng.attn_reg = value != 0; return STS_OK;
         case STS_DBG_DDS_TAIL: e->eng.dds_tail = value != 0; return STS_OK;
         case STS_DBG_PCM_DIRECT: e->eng.pcm_direct = value != 0; return STS_OK;
+        case STS_DBG_STREAM_RETRY_STEP: e->eng.stream_retry_step = value < 0 ? -1 : value; return STS_OK;
+        case STS_DBG_STREAM_DIRECT: e->eng.stream_direct = value != 0; return STS_OK;
         default: return set_err(STS_EINVAL, "unknown debug key");
     }
 }

@@ -380,7 +380,14 @@ struct BufF {
     float *ff_h[2], *ff_part[2], *ff_macc[2], *ff_alt;        // one-launch-per-layer flow (wn_flow.hip): channel-minor h / partial sums / -m slices, alternate home of a z half
     int16_t* pcm;
     int16_t* pcm_nat; float* wave_out;   // at a non-native output rate: the decoder tail's own int16 samples (not returned), the resampled float wave (taps)
+    // batched streaming only (null otherwise): the step tables (stream_tab_bytes), the packed chunk buffer of a native-rate step, the
+    // per-window speaker vectors and decoder conditioning of a multi-speaker HiFi-GAN decoder
+    char* stab; int16_t* spack; float *gwin, *cond_win;
 };
+// Batched streaming, the tables of one step with nw windows (one upload, c.d_win points at them): ints [zoff nw | coff nw | wlen nw | sid nw |
+// pack source nw | packed destination nw + 1], then from an 8-byte boundary the resampler's long long [nw][5] = {u0, L_utt, j0, j1, obase}
+static inline size_t stream_tab_ll_off(int nw) { return ((size_t)(6 * nw + 1) * 4 + 7) & ~(size_t)7; }
+static inline size_t stream_tab_bytes(int nw) { return stream_tab_ll_off(nw) + (size_t)nw * 5 * 8; }
 
 // Everything a run's stages share: batch geometry, workspace pointers, host / device tables.  Engine::run() fills it stage by
 // stage; the stage functions below see its fields under the names the pipeline has always used (RUN_ALIASES).
@@ -405,6 +412,7 @@ struct Engine::RunCtx {
     std::vector<unsigned long long> req_keys; std::vector<long> predF;      // launch-ahead memo: per-utterance request hashes, remembered frame counts (empty: not all known)
     int halo = 0; long Wcap = 0; int upS = 1; long Lsb = 0; int sbC = 0;
     long long Ocap = 0;             // PCM capacity in output samples (== Wcap * hop at the native rate)
+    bool bstream = false;           // batched streaming (ss with B > 1): decode windows are chunks of several utterances (run_stream_steps)
     bool use_ff = false; int ffG = 0;
 };
 #define RUN_ALIASES(c)                                                                                                              \
@@ -882,7 +890,12 @@ int Engine::run_frame_workspace(RunCtx& c) {
     // ---------------- frame-level workspace.  The flow works on all Ftot frames; the decoder works on
     // "windows" of z: whole utterances normally (Wcap == Ftot), one chunk plus its two halos when streaming.
     const int halo = c.halo = stream_halo();
-    const long Wcap = c.Wcap = ss ? std::min<long>(Ftot, (long)ss->chunk_frames + 2 * halo) : Ftot;
+    long Wcap = ss ? std::min<long>(Ftot, (long)ss->chunk_frames + 2 * halo) : Ftot;
+    if (c.bstream) {    // a step decodes at most one window per utterance, each at most a chunk plus two halos: sum_b min(F_b, C + 2 halo)
+        Wcap = 0;
+        for (int b = 0; b < B; b++) Wcap += std::min<long>(p_lenF[b], (long)ss->chunk_frames + 2 * halo);
+    }
+    c.Wcap = Wcap;
     int upS = 1;
     for (int u : M.up_rate) upS *= u;
     c.upS = upS;
@@ -927,6 +940,12 @@ int Engine::run_frame_workspace(RunCtx& c) {
         bf.pcm = A.get<int16_t>((size_t)c.Ocap);
         bf.pcm_nat = resampling() ? A.get<int16_t>((size_t)Wcap * hop) : bf.pcm;
         bf.wave_out = record_taps && resampling() ? A.get<float>((size_t)c.Ocap) : nullptr;
+        bf.stab = nullptr; bf.spack = nullptr; bf.gwin = bf.cond_win = nullptr;
+        if (c.bstream) {
+            bf.stab = A.get<char>(stream_tab_bytes(B));
+            if (!resampling()) bf.spack = A.get<int16_t>((size_t)c.Ocap);     // (at another rate the resampler packs into bf.pcm)
+            if (M.dec_type == 0 && c.ms) { bf.gwin = A.get<float>((size_t)M.gin * B); bf.cond_win = A.get<float>((size_t)M.up_init * B); }
+        }
     };
     c.Ocap = resampling() ? out_count((long long)Wcap * hop) + B : (long long)Wcap * hop;
     arenaF_.measuring = true; layoutF(arenaF_);
@@ -1081,7 +1100,13 @@ int Engine::run_decode(RunCtx& c, int nw, long Wtot, int maxW, int zoff0, int wl
     const Lvl lw1 = lvF(1, 0);
     {
         ConvOpt op;
-        if (M.dec_type == 0 && ms) { conv(M.dec_cond, bt.g, lvB, bt.cond_dec, lvB, ConvOpt()); op.ubias = bt.cond_dec; }
+        if (M.dec_type == 0 && ms && c.bstream) {
+            // batched streaming: the conditioning is indexed by window, not by utterance -- gather each window's speaker (the sid table of
+            // the step) and run dec_cond over the nw windows
+            Lvl lw; lw.seg = SegView{nullptr, nullptr, 1, 0, 0, nw}; lw.nb = 1; lw.max_len = nw; lw.total = nw; lw.ld = nw;
+            gather_speaker(M.emb_g, M.spk_num, M.gin, d_win + 3 * nw, nw, bf.gwin, stream);
+            conv(M.dec_cond, bf.gwin, lw, bf.cond_win, lw, ConvOpt()); op.ubias = bf.cond_win;
+        } else if (M.dec_type == 0 && ms) { conv(M.dec_cond, bt.g, lvB, bt.cond_dec, lvB, ConvOpt()); op.ubias = bt.cond_dec; }
         conv(M.conv_pre, bf.z, lz, bf.x0, lw1, op);
     }
     const float* x = bf.x0;
@@ -1485,7 +1510,8 @@ int Engine::run(int B, const int32_t* const* ids, const int32_t* n, const int32_
 int Engine::run_once(int B, const int32_t* const* ids, const int32_t* n, const int32_t* sid, const float* ls, const StreamSpec* ss) {
     Model& M = model;
     if (B <= 0 || !ids || !n) return fail(STS_EINVAL, "empty batch");
-    if (ss && (B != 1 || ss->chunk_frames <= 0 || !ss->cb)) return fail(STS_EINVAL, "streaming takes one utterance, a positive chunk size and a callback");
+    if (ss && (B == 1 ? ss->chunk_frames <= 0 || !ss->cb : ss->chunk_frames <= 0 || !ss->bcb))
+        return fail(STS_EINVAL, "streaming takes a positive chunk size and a callback (a per-utterance one for several utterances)");
     HIPCK(hipSetDevice(device));
     taps.clear();
     memset(&prof, 0, sizeof(prof));
@@ -1496,7 +1522,7 @@ int Engine::run_once(int B, const int32_t* const* ids, const int32_t* n, const i
 
     host_t0_ = now_us(); host_t_sync_ = 0;
     RunCtx c;
-    c.B = B; c.ids = ids; c.n = n; c.sid = sid; c.ls = ls; c.ss = ss;
+    c.B = B; c.ids = ids; c.n = n; c.sid = sid; c.ls = ls; c.ss = ss; c.bstream = ss && B > 1;
     int rc;
     if ((rc = run_setup(c)) != STS_OK) return rc;
     mark(0);
@@ -1574,6 +1600,10 @@ int Engine::run_output(RunCtx& c) {
             prof.launch_ahead = 1;
         }
         HIPCK(hipGetLastError());
+    } else if (c.bstream) {
+        const int rc = run_stream_steps(c);
+        if (rc != STS_OK) return rc;
+        HIPCK(hipGetLastError());
     } else {
         // Streaming: chunk c = frames [f0, f1) is decoded from the window [f0 - halo, f1 + halo)
         // clipped to the utterance; the halo covers the decoder's receptive field, so the kept samples are
@@ -1650,6 +1680,118 @@ int Engine::run_output(RunCtx& c) {
     prof.us_host_setup = host_us_setup_; prof.us_host_enqueue = host_us_enq_;
     prof.us_host_tail = host_t_sync_ > 0 ? (float)(now_us() - host_t_sync_) : 0.f;
     return STS_OK;
+}
+
+// ---- batched streaming (sts_infer_ids_batch_stream): step k decodes chunk k = frames [k C, min((k + 1) C, F_b)) of every live utterance b as
+// one window of a single decode pass -- the window [max(0, f0 - halo), min(F_b, f1 + halo)) at offF[b] + w0 of the packed z, the windows
+// packed in utterance order.  One kernel then gathers the windows' kept samples into one packed chunk buffer (stream_pack at the native
+// rate, the multi-window mode of resample_pcm otherwise), one download (or posted writes into mapped pinned memory: stream_direct), one
+// host synchronisation, and the step's chunks go to the caller in ascending utterance order before the next step is enqueued.  A window
+// is the single stream's window of the same chunk, so its kept samples are the single stream's (bit-identical for a pinned kernel variant).
+int Engine::run_stream_steps(RunCtx& c) {
+    RUN_ALIASES(c)
+    const long Cf = ss->chunk_frames;
+    // (ensure_pinned below may move the pinned block the geometry tables live in)
+    const std::vector<int> offF(p_offF, p_offF + B), lenF(p_lenF, p_lenF + B), sidv(c.p_sid, c.p_sid + B);
+    const size_t hp_off = (up_bytes + ((size_t)Ttot + B) * 4 + 255) & ~(size_t)255;
+    const size_t tab_room = (stream_tab_bytes(B) + 255) & ~(size_t)255;
+    const size_t pcm_bytes = (size_t)c.Ocap * 2 + 256;
+    if (!ensure_pinned(hp_off + tab_room + pcm_bytes)) return fail(STS_EDEVICE, "pinned host allocation failed");
+    c.pm = (int*)pinned_;
+    char* const ht = pinned_ + hp_off;
+    int16_t* hp = (int16_t*)(pinned_ + hp_off + tab_room);
+    int16_t* dst = resampling() ? bf.pcm : bf.spack;             // the step's packed chunks on the device
+    if (stream_direct) {       // posted writes: the last kernel of a step stores the chunks into the mapped pinned buffer itself
+        if (pcm_bytes > pinned_pcm_cap_ || !pinned_pcm_dev_) {
+            (void)hipStreamSynchronize(stream);
+            if (pinned_pcm_) (void)hipHostFree(pinned_pcm_);
+            pinned_pcm_ = nullptr; pinned_pcm_cap_ = 0; pinned_pcm_dev_ = nullptr;
+            if (hipHostMalloc((void**)&pinned_pcm_, pcm_bytes, hipHostMallocMapped) != hipSuccess) return fail(STS_EDEVICE, "pinned host allocation failed");
+            pinned_pcm_cap_ = pcm_bytes;
+            if (hipHostGetDevicePointer((void**)&pinned_pcm_dev_, pinned_pcm_, 0) != hipSuccess) { pinned_pcm_dev_ = nullptr; return fail(STS_EDEVICE, "mapped pinned buffer has no device address"); }
+        }
+        dst = pinned_pcm_dev_; hp = (int16_t*)pinned_pcm_;
+    }
+    c.d_win = (int*)bf.stab;
+    std::vector<char> live(B, 1);
+    if (ss->delivered) for (int b = 0; b < B; b++) ss->delivered[b] = 0;
+    d_pcm = nullptr; total_samples = 0;
+    std::vector<int> wb; std::vector<long long> wj0, wn, wdst;
+    for (long k = 0;; k++) {
+        const long f0 = k * Cf;
+        wb.clear();
+        for (int b = 0; b < B; b++) if (live[b] && f0 < lenF[b]) wb.push_back(b);
+        const int nw = (int)wb.size();
+        if (nw == 0) break;
+        int* ti = (int*)ht;
+        long long* tl = (long long*)(ht + stream_tab_ll_off(nw));
+        wj0.assign(nw, 0); wn.assign(nw, 0); wdst.assign(nw, 0);
+        long Wtot = 0; int maxW = 0; long long dsum = 0, max_out = 0;
+        for (int i = 0; i < nw; i++) {
+            const int b = wb[i];
+            const long F = lenF[b], f1 = std::min<long>(F, f0 + Cf);
+            const long w0 = std::max<long>(0, f0 - halo), w1 = std::min<long>(F, f1 + halo);
+            const long long j0 = out_count((long long)f0 * hop), j1 = out_count((long long)f1 * hop);
+            ti[i] = offF[b] + (int)w0; ti[nw + i] = (int)Wtot; ti[2 * nw + i] = (int)(w1 - w0); ti[3 * nw + i] = sidv[b];
+            ti[4 * nw + i] = (int)((Wtot + (f0 - w0)) * hop); ti[5 * nw + i] = (int)dsum;
+            tl[5 * i] = (long long)w0 * hop; tl[5 * i + 1] = (long long)F * hop; tl[5 * i + 2] = j0; tl[5 * i + 3] = j1; tl[5 * i + 4] = dsum;
+            wj0[i] = j0; wn[i] = j1 - j0; wdst[i] = dsum;
+            dsum += j1 - j0; max_out = std::max(max_out, j1 - j0);
+            Wtot += w1 - w0; maxW = std::max<int>(maxW, (int)(w1 - w0));
+        }
+        ti[6 * nw] = (int)dsum;
+        HIPCK(hipMemcpyAsync(c.d_win, ht, stream_tab_bytes(nw), hipMemcpyHostToDevice, stream));
+        int rc = run_decode(c, nw, Wtot, maxW, 0, -1);
+        if (rc != STS_OK) return rc;
+        if (resampling()) {
+            ResampleArgs a{};
+            a.x = bf.wave; a.seg = SegView{c.d_win + nw, c.d_win + 2 * nw, hop, 0, 0, 0};
+            a.table = d_rs_table; a.P = rs.P; a.Q = rs.Q; a.K = rs.K;
+            a.pcm = dst; a.wave_out = nullptr;
+            a.stream = 2; a.wtab = (const long long*)(bf.stab + stream_tab_ll_off(nw));
+            resample_pcm(a, nw, max_out, stream);
+        } else {
+            stream_pack(bf.pcm, dst, c.d_win + 4 * nw, c.d_win + 5 * nw, nw, max_out, stream);
+        }
+        if (!stream_direct) HIPCK(hipMemcpyAsync(hp, dst, (size_t)dsum * 2, hipMemcpyDeviceToHost, stream));
+        HIPCK(hipStreamSynchronize(stream));
+        if (conv_math == 3 && ((ovf_host_ && *(volatile unsigned*)ovf_host_ != 0u) || (stream_retry_step >= 0 && k == stream_retry_step))) {
+            if (k == 0) return kRetrySplitBf16;           // nothing has left yet (run() repeats the call)
+            h2_fallbacks++;
+            conv_math = 0;                                 // (run() restores the setting)
+            k--;                                           // this step again, every window of it
+            continue;
+        }
+        for (int i = 0; i < nw; i++) {                     // ascending utterance order
+            const int b = wb[i];
+            total_samples += wn[i];
+            if (ss->delivered) ss->delivered[b] += (int32_t)wn[i];
+            if (ss->bcb(ss->user, b, hp + wdst[i], (int32_t)wn[i], (int32_t)wj0[i]) != 0) live[b] = 0;
+        }
+    }
+    return STS_OK;
+}
+
+namespace {
+struct OneUttAdapter { int (*cb)(void*, int32_t, const int16_t*, int32_t, int32_t); void* user; };
+int one_utt_cb(void* u, const int16_t* pcm, int32_t n, int32_t off) { const OneUttAdapter* a = (const OneUttAdapter*)u; return a->cb(a->user, 0, pcm, n, off); }
+}  // namespace
+
+int Engine::run_batch_stream(int B, const int32_t* const* ids, const int32_t* n, const int32_t* sid, const float* ls, int chunk_frames,
+                             int (*cb)(void*, int32_t, const int16_t*, int32_t, int32_t), void* user, int32_t* n_total) {
+    if (B < 1 || !ids || !n || chunk_frames <= 0 || !cb) return fail(STS_EINVAL, "batched streaming takes B >= 1 utterances, a positive chunk size and a callback");
+    if (B == 1) {              // the single stream itself
+        OneUttAdapter a{cb, user};
+        StreamSpec ss{chunk_frames, one_utt_cb, &a};
+        const int rc = run(1, ids, n, sid, ls, &ss);
+        if (rc == STS_OK && n_total) n_total[0] = (int32_t)total_samples;
+        return rc;
+    }
+    std::vector<int32_t> got(B, 0);
+    StreamSpec ss{chunk_frames, nullptr, user, cb, got.data()};
+    const int rc = run(B, ids, n, sid, ls, &ss);
+    if (rc == STS_OK && n_total) for (int b = 0; b < B; b++) n_total[b] = got[b];
+    return rc;
 }
 
 }  // namespace sts

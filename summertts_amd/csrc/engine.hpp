@@ -47,7 +47,13 @@ struct ConvOpt {
 };
 
 // streaming decode: PCM is handed to `cb` chunk by chunk (cb returns non-zero to stop)
-struct StreamSpec { int chunk_frames; int (*cb)(void* user, const int16_t* pcm, int32_t n_samples, int32_t sample_offset); void* user; };
+struct StreamSpec {
+    int chunk_frames; int (*cb)(void* user, const int16_t* pcm, int32_t n_samples, int32_t sample_offset); void* user;
+    // batched streaming (B > 1, Engine::run_stream_steps): chunks of every utterance, per utterance; bcb returns non-zero to stop that
+    // utterance only.  delivered (optional, [B]): samples handed to bcb per utterance
+    int (*bcb)(void* user, int32_t utt, const int16_t* pcm, int32_t n_samples, int32_t sample_offset) = nullptr;
+    int32_t* delivered = nullptr;
+};
 int decoder_halo_frames(const Model& M);
 inline bool noise_scale_valid(float s) { return s >= 0.f && s <= 3.0e38f; }   // (false for NaN and +inf)
 
@@ -60,6 +66,10 @@ public:
     int init(const float* blob, int64_t bytes, int device);
     int run(int B, const int32_t* const* ids, const int32_t* n, const int32_t* sid, const float* ls, const StreamSpec* ss = nullptr);
     int run_once(int B, const int32_t* const* ids, const int32_t* n, const int32_t* sid, const float* ls, const StreamSpec* ss);
+    // batched streaming (sts_infer_ids_batch_stream): B utterances, chunk k of every live one decoded as the windows of one pass per step;
+    // B == 1 is the single stream (run with a one-utterance StreamSpec).  n_total (optional, [B]): samples delivered per utterance
+    int run_batch_stream(int B, const int32_t* const* ids, const int32_t* n, const int32_t* sid, const float* ls, int chunk_frames,
+                         int (*cb)(void*, int32_t, const int16_t*, int32_t, int32_t), void* user, int32_t* n_total);
     const std::string& error() const { return err_; }
 
     Model model;
@@ -127,6 +137,8 @@ public:
     int h2p_tile = -1;                 // lab: tile code of conv_h2p_group (-1: automatic)
     int flow_fused = 1;                // 1: the reverse flow as one launch per WaveNet layer where eligible (wn_flow.hip; two-term fp16 arithmetic only);
                                        // 0: one launch per conv (sts_debug_set STS_DBG_FLOW_FUSED)
+    int stream_retry_step = -1;        // tests (STS_DBG_STREAM_RETRY_STEP): a batched stream under conv_math 3 treats the overflow word as raised after step k
+    int stream_direct = 0;             // batched streaming: 1 the pack / resample kernel writes each step's chunks into mapped pinned host memory, 0 one download (STS_DBG_STREAM_DIRECT)
     hipStream_t stream = nullptr;
 
 private:
@@ -152,6 +164,7 @@ private:
     int wait_frame_counts(RunCtx& c);
     int frame_geometry(RunCtx& c);
     int run_output(RunCtx& c);
+    int run_stream_steps(RunCtx& c);
     void tap(const char* name, const float* d, int channels, long ld, long length);
     void stage_begin(int s);
     void mark(int i);

@@ -347,8 +347,14 @@ struct ResampleArgs {
     int16_t* pcm; float* wave_out;       // outputs, packed utterance after utterance; wave_out optional (taps)
     // streaming (one window): the window holds utterance samples [u0, u0 + len) of L_utt; outputs [j0, j1) go to pcm[0 ..)
     int stream; long long u0, L_utt, j0, j1;
+    // stream == 2 (batched streaming, several windows): window w reads {u0, L_utt, j0, j1, obase} from wtab[5 w ..] instead of the
+    // scalars above, and its outputs [j0, j1) go to pcm[obase ..) -- the windows' chunks packed back to back
+    const long long* wtab;
 };
 // grid: nwin windows x ceil(max_out / 1024) tiles; max_out = the most outputs one window emits
 void resample_pcm(const ResampleArgs& a, int nwin, long long max_out, hipStream_t st);
+// batched streaming at the native rate: window w's kept samples src[src_off[w] ..) -> dst[dst_off[w] .. dst_off[w + 1]) (one packed chunk
+// buffer per step); max_n = the most samples one window keeps
+void stream_pack(const int16_t* src, int16_t* dst, const int* src_off, const int* dst_off, int nwin, long long max_n, hipStream_t st);
 
 }  // namespace sts

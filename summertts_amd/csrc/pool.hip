@@ -27,6 +27,8 @@ struct Request {
     int64_t ticket = 0;
     std::vector<int32_t> ids; int32_t sid = 0; float ls = 1.f;
     Engine::Noise noise;               // sts_pool_submit_ex: this request's sampling noise
+    // sts_pool_submit_stream: chunks go to cb (on the worker thread); the ticket completes with pcm = null, n = samples delivered
+    bool stream = false; int32_t chunk = 0; sts_chunk_cb cb = nullptr; void* user = nullptr;
     // result
     bool done = false, waited = false; int rc = STS_OK; std::string err;
     int16_t* pcm = nullptr; int32_t n = 0;
@@ -54,8 +56,13 @@ struct sts_pool {
                 std::unique_lock<std::mutex> lk(mu);
                 cv_work.wait(lk, [&] { return stop || !queue.empty(); });
                 if (stop && queue.empty()) return;
-                while (!queue.empty() && (int)take.size() < max_batch) { take.push_back(queue.front()); queue.pop_front(); }
+                // a batch is a run of the FIFO's head: whole-utterance requests, or streaming requests of one chunk size -- never both
+                const bool st = queue.front()->stream; const int32_t ch = queue.front()->chunk;
+                while (!queue.empty() && (int)take.size() < max_batch && queue.front()->stream == st && (!st || queue.front()->chunk == ch)) {
+                    take.push_back(queue.front()); queue.pop_front();
+                }
             }
+            if (take.front()->stream) { run_stream_group(eng, take); cv_done.notify_all(); continue; }
             // run `grp` as one packed batch; on failure of a multi-request batch, re-run its members one by one so
             // that a bad request (e.g. an id outside the vocabulary) only fails itself
             auto run_group = [&](const std::vector<std::shared_ptr<Request>>& grp, auto&& self) -> void {
@@ -100,6 +107,47 @@ struct sts_pool {
             run_group(take, run_group);
             cv_done.notify_all();
         }
+    }
+
+    // streaming requests as one batched stream (Engine::run_batch_stream).  A member's ticket completes at its last chunk or its stop; a
+    // failure before any chunk of the batch has left re-runs the members one by one, a later one completes the unfinished tickets with it
+    void run_stream_group(Engine& eng, const std::vector<std::shared_ptr<Request>>& grp) {
+        const int B = (int)grp.size();
+        std::vector<const int32_t*> idp(B); std::vector<int32_t> n(B), sid(B); std::vector<float> ls(B);
+        eng.noise_utt.resize(B);
+        for (int b = 0; b < B; b++) {
+            idp[b] = grp[b]->ids.data(); n[b] = (int32_t)grp[b]->ids.size(); sid[b] = grp[b]->sid; ls[b] = grp[b]->ls;
+            eng.noise_utt[b] = grp[b]->noise;
+        }
+        struct Ctx { sts_pool* p; Engine* eng; const std::vector<std::shared_ptr<Request>>* grp; bool any_left; };
+        Ctx cx{this, &eng, &grp, false};
+        auto cb = [](void* u, int32_t utt, const int16_t* pcm, int32_t ns, int32_t off) -> int {
+            Ctx& c = *(Ctx*)u;
+            Request& r = *(*c.grp)[utt];
+            c.any_left = true;
+            r.n += ns;
+            const int stop = r.cb(r.user, pcm, ns, off);
+            if (stop != 0 || (utt < (int)c.eng->n_samples.size() && r.n >= c.eng->n_samples[utt])) {
+                { std::lock_guard<std::mutex> lk(c.p->mu); r.rc = STS_OK; r.done = true; }
+                c.p->cv_done.notify_all();
+            }
+            return stop;
+        };
+        for (auto& r : grp) r->n = 0;
+        const int rc = eng.run_batch_stream(B, idp.data(), n.data(), sid.data(), ls.data(), grp.front()->chunk, cb, &cx, nullptr);
+        eng.noise_utt.clear();
+        if (rc != STS_OK && B > 1 && !cx.any_left) {
+            for (auto& r : grp) run_stream_group(eng, std::vector<std::shared_ptr<Request>>{r});
+            return;
+        }
+        std::lock_guard<std::mutex> lk(mu);
+        for (auto& r : grp) {
+            if (r->done) continue;
+            r->rc = rc;
+            if (rc != STS_OK) r->err = eng.error();
+            r->done = true;
+        }
+        batches++; requests += B;
     }
 };
 
@@ -148,6 +196,24 @@ int64_t sts_pool_submit_ex(sts_pool* p, const int32_t* ids, int32_t n, int32_t s
     if (!noise_scale_valid(noise_scale) || !noise_scale_valid(noise_scale_w)) return pool_err(STS_EINVAL, "noise scales must be finite and >= 0");
     auto r = std::make_shared<Request>();
     r->ids.assign(ids, ids + n); r->sid = sid; r->ls = length_scale; r->noise = Engine::Noise{noise_scale, noise_scale_w, seed};
+    {
+        std::lock_guard<std::mutex> lk(p->mu);
+        if (p->stop) return pool_err(STS_ESTATE, "pool is shutting down");
+        r->ticket = p->next_ticket++;
+        p->queue.push_back(r);
+        p->pending[r->ticket] = r;
+    }
+    p->cv_work.notify_one();
+    return r->ticket;
+}
+
+int64_t sts_pool_submit_stream(sts_pool* p, const int32_t* ids, int32_t n, int32_t sid, float length_scale, float noise_scale,
+                               float noise_scale_w, uint64_t seed, int32_t chunk_frames, sts_chunk_cb cb, void* user) {
+    if (!p || !ids || n <= 0 || chunk_frames <= 0 || !cb) return pool_err(STS_EINVAL, "bad request");
+    if (!noise_scale_valid(noise_scale) || !noise_scale_valid(noise_scale_w)) return pool_err(STS_EINVAL, "noise scales must be finite and >= 0");
+    auto r = std::make_shared<Request>();
+    r->ids.assign(ids, ids + n); r->sid = sid; r->ls = length_scale; r->noise = Engine::Noise{noise_scale, noise_scale_w, seed};
+    r->stream = true; r->chunk = chunk_frames; r->cb = cb; r->user = user;
     {
         std::lock_guard<std::mutex> lk(p->mu);
         if (p->stop) return pool_err(STS_ESTATE, "pool is shutting down");

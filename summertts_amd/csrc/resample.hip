@@ -110,7 +110,9 @@ __global__ __launch_bounds__(RS_THREADS) void resample_pcm_kernel(ResampleArgs a
     const long long P = a.P, Q = a.Q, K = a.K, T = 2 * a.K;
     const long long win = seg_len(a.seg, b), ib = seg_start(a.seg, b);     // window b: native samples [ib, ib + win) of x
     long long u0 = 0, L = win, j0 = 0, j1 = ceil_div_ll(win * P, Q);
-    if (a.stream) { u0 = a.u0; L = a.L_utt; j0 = a.j0; j1 = a.j1; }      // (one window: utterance samples [u0, u0 + win) of L)
+    long long obw = 0;                                                  // (stream 2: where window b's outputs start in pcm)
+    if (a.stream == 1) { u0 = a.u0; L = a.L_utt; j0 = a.j0; j1 = a.j1; }      // (one window: utterance samples [u0, u0 + win) of L)
+    else if (a.stream == 2) { const long long* t = a.wtab + 5 * b; u0 = t[0]; L = t[1]; j0 = t[2]; j1 = t[3]; obw = t[4]; }
     const long long t0 = j0 + (long long)blockIdx.x * RS_TILE;
     if (t0 >= j1) return;
     const long long t1 = t0 + RS_TILE < j1 ? t0 + RS_TILE : j1;
@@ -134,7 +136,7 @@ __global__ __launch_bounds__(RS_THREADS) void resample_pcm_kernel(ResampleArgs a
         for (int i = tid; i < (int)(P * T); i += RS_THREADS) hs[i] = a.table[i];
     __syncthreads();
     if (span > RS_LDS) return;                                                 // (never: the host admits only Q <= 2P, K <= kResampleMaxK)
-    const long long ob = (long long)s_obase - j0;
+    const long long ob = (long long)s_obase + obw - j0;
     if (tab_lds) resample_chains(hs, xs, s0, t0, t1, P, Q, K, (int)T, ob, tid, a);
     else resample_chains(a.table, xs, s0, t0, t1, P, Q, K, (int)T, ob, tid, a);
 }
@@ -142,6 +144,26 @@ __global__ __launch_bounds__(RS_THREADS) void resample_pcm_kernel(ResampleArgs a
 void resample_pcm(const ResampleArgs& a, int nwin, long long max_out, hipStream_t st) {
     if (nwin <= 0 || max_out <= 0) return;
     hipLaunchKernelGGL(resample_pcm_kernel, dim3((unsigned)((max_out + RS_TILE - 1) / RS_TILE), nwin), dim3(RS_THREADS), 0, st, a);
+}
+
+// One workgroup per (tile of SP_TILE samples, window): a plain int16 copy, SP_PER samples per lane 256 apart (coalesced)
+constexpr int SP_THREADS = 256, SP_PER = 8, SP_TILE = SP_THREADS * SP_PER;
+__global__ __launch_bounds__(SP_THREADS) void stream_pack_kernel(const int16_t* __restrict__ src, int16_t* __restrict__ dst,
+                                                                 const int* __restrict__ src_off, const int* __restrict__ dst_off) {
+    const int w = blockIdx.y;
+    const long long d0 = dst_off[w], n = (long long)dst_off[w + 1] - d0, s0 = src_off[w];
+    const long long t0 = (long long)blockIdx.x * SP_TILE;
+    if (t0 >= n) return;
+#pragma unroll
+    for (int r = 0; r < SP_PER; r++) {
+        const long long i = t0 + r * SP_THREADS + threadIdx.x;
+        if (i < n) dst[d0 + i] = src[s0 + i];
+    }
+}
+
+void stream_pack(const int16_t* src, int16_t* dst, const int* src_off, const int* dst_off, int nwin, long long max_n, hipStream_t st) {
+    if (nwin <= 0 || max_n <= 0) return;
+    hipLaunchKernelGGL(stream_pack_kernel, dim3((unsigned)((max_n + SP_TILE - 1) / SP_TILE), nwin), dim3(SP_THREADS), 0, st, src, dst, src_off, dst_off);
 }
 
 }  // namespace sts

@@ -68,6 +68,11 @@ class PreparedBatch:
 _lib = None
 
 
+# the streaming callbacks of the C ABI (include/summertts_hip.h sts_chunk_cb, sts_batch_chunk_cb)
+CHUNK_CB = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(C.c_int16), C.c_int32, C.c_int32)
+BATCH_CHUNK_CB = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int32, C.POINTER(C.c_int16), C.c_int32, C.c_int32)
+
+
 def load_library() -> C.CDLL:
     global _lib
     if _lib is not None:
@@ -109,6 +114,11 @@ def load_library() -> C.CDLL:
                                        C.c_void_p, C.c_int64]
     lib.sts_pool_set_output_rate.argtypes = [C.c_void_p, C.c_int32]
     lib.sts_multi_set_output_rate.argtypes = [C.c_void_p, C.c_int32]
+    lib.sts_infer_ids_batch_stream.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
+                                               BATCH_CHUNK_CB, C.c_void_p, C.c_void_p]
+    lib.sts_pool_submit_stream.restype = C.c_int64
+    lib.sts_pool_submit_stream.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_float, C.c_uint64,
+                                           C.c_int32, CHUNK_CB, C.c_void_p]
     lib.sts_free.argtypes = [C.c_void_p]
     lib.sts_debug_conv1d.argtypes = [C.c_int, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32,
                                      C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_int32,
@@ -129,6 +139,7 @@ EXPORTED_SYMBOLS = [
     "sts_multi_shard_of", "sts_multi_last_error", "sts_multi_set_rccl_library", "sts_multi_rccl_ranks", "sts_multi_last_gather_ms", "sts_multi_set_conv_math", "sts_get_profile_ex", "sts_abi_version", "sts_build_flags",
     "sts_set_noise", "sts_get_noise", "sts_pool_submit_ex", "sts_multi_set_noise",
     "sts_set_output_rate", "sts_get_output_rate", "sts_resample_table", "sts_pool_set_output_rate", "sts_multi_set_output_rate",
+    "sts_infer_ids_batch_stream", "sts_pool_submit_stream",
 ]
 
 
@@ -203,6 +214,39 @@ class Synthesizer:
                                                   C.c_void_p, C.POINTER(C.c_int32)]
         _check(self.lib, self.lib.sts_infer_ids_stream(self.h, a.ctypes.data, a.size, sid, length_scale, chunk_frames, cb, None,
                                                        C.byref(total)))
+        return chunks, times
+
+    # -- batched streaming (sts_infer_ids_batch_stream) ---------------------------------------
+    def infer_batch_stream(self, ids, chunk_frames: int, sid: Optional[Sequence[int]] = None,
+                           length_scale: Optional[Sequence[float]] = None, on_chunk=None, n_total: Optional[list] = None):
+        """Streams B utterances together: step k decodes chunk k of every live utterance in one pass.  ``on_chunk(utt, pcm: np.int16[],
+        sample_offset, t_seconds)`` is called per chunk, step by step and within a step in ascending ``utt`` (return True to stop that
+        utterance only).  Returns (per-utterance lists of chunks, per-utterance lists of arrival times since the call started); with
+        ``n_total`` a list, it receives the library's per-utterance sample counts."""
+        import time
+        B = len(ids)
+        arrs = [np.ascontiguousarray(x, dtype=np.int32) for x in ids]
+        ptrs = (C.c_void_p * max(B, 1))(*[a.ctypes.data for a in arrs])
+        n = np.array([a.size for a in arrs], dtype=np.int32)
+        sid_a = None if sid is None else np.ascontiguousarray(sid, dtype=np.int32)
+        ls_a = None if length_scale is None else np.ascontiguousarray(length_scale, dtype=np.float32)
+        tot = np.zeros(max(B, 1), dtype=np.int32)
+        chunks = [[] for _ in range(B)]
+        times = [[] for _ in range(B)]
+        t0 = time.perf_counter()
+
+        def _cb(user, utt, pcm, ns, off):
+            arr = np.ctypeslib.as_array(pcm, shape=(ns,)).copy() if ns else np.zeros(0, np.int16)
+            t = time.perf_counter() - t0
+            chunks[utt].append(arr); times[utt].append(t)
+            return 1 if (on_chunk and on_chunk(utt, arr, off, t)) else 0
+        cb = BATCH_CHUNK_CB(_cb)
+        _check(self.lib, self.lib.sts_infer_ids_batch_stream(self.h, B, ptrs, n.ctypes.data,
+                                                             None if sid_a is None else sid_a.ctypes.data,
+                                                             None if ls_a is None else ls_a.ctypes.data, chunk_frames, cb, None,
+                                                             tot.ctypes.data))
+        if n_total is not None:
+            n_total[:] = [int(v) for v in tot[:B]]
         return chunks, times
 
     def stream_halo_frames(self) -> int:
@@ -298,7 +342,7 @@ class Synthesizer:
 
     def debug_set(self, key: str, value: int):
         """Test hooks (include/summertts_hip.h sts_debug_set): 'attn_block_min_wgs' | 'flow_fused' | 'launch_ahead' | ..."""
-        _check(self.lib, self.lib.sts_debug_set(self.h, {"attn_block_min_wgs": 1, "flow_fused": 5, "launch_ahead": 6, "attn_reg": 7, "dds_tail": 8, "pcm_direct": 9, "memo_clear": 10, "h2p": 11, "h2p_tile": 12, "chain_streams": 13, "tail_fused": 14, "ups_rowph": 15}[key], int(value)))
+        _check(self.lib, self.lib.sts_debug_set(self.h, {"attn_block_min_wgs": 1, "flow_fused": 5, "launch_ahead": 6, "attn_reg": 7, "dds_tail": 8, "pcm_direct": 9, "memo_clear": 10, "h2p": 11, "h2p_tile": 12, "chain_streams": 13, "tail_fused": 14, "ups_rowph": 15, "stream_retry_step": 16, "stream_direct": 17}[key], int(value)))
 
     def set_profiling(self, on):
         """False / True: no / all eight stage events per run; 2: only the two events around the decoder's matrix-core region (the
@@ -428,9 +472,28 @@ class Pool:
         self.lib.sts_pool_create.argtypes = [C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]
         self.lib.sts_pool_destroy.argtypes = [C.c_void_p]
         self.lib.sts_pool_stats.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+        self._streams: Dict[int, object] = {}      # ticket -> the ctypes callback of a streaming request (kept alive until it is waited)
         rc = self.lib.sts_pool_create(blob.ctypes.data, blob.nbytes, device, n_engines, max_batch, C.byref(self.h))
         if rc != 0:
             raise StsError(f"sts_pool_create: {rc}: {self.lib.sts_pool_last_error().decode()}")
+
+    def submit_stream(self, ids: Sequence[int], chunk_frames: int, on_chunk, sid: int = 0, length_scale: float = 1.0,
+                      noise_scale: float = 0.0, noise_scale_w: float = 0.0, seed: int = 0) -> int:
+        """Queue one streaming request (sts_pool_submit_stream).  ``on_chunk(pcm: np.int16[], sample_offset)`` runs on the pool's worker
+        thread (return True to stop this request); it must not wait on a ticket of this pool.  ``wait(ticket)`` then returns the number of
+        samples delivered."""
+        a = np.ascontiguousarray(ids, dtype=np.int32)
+
+        def _cb(user, pcm, ns, off):
+            arr = np.ctypeslib.as_array(pcm, shape=(ns,)).copy() if ns else np.zeros(0, np.int16)
+            return 1 if on_chunk(arr, off) else 0
+        cb = CHUNK_CB(_cb)
+        t = int(self.lib.sts_pool_submit_stream(self.h, a.ctypes.data, a.size, sid, length_scale, float(noise_scale), float(noise_scale_w),
+                                                int(seed) & 0xFFFFFFFFFFFFFFFF, int(chunk_frames), cb, None))
+        if t <= 0:
+            raise StsError(f"sts_pool_submit_stream: {t}: {self.lib.sts_pool_last_error().decode()}")
+        self._streams[t] = cb
+        return t
 
     def submit(self, ids: Sequence[int], sid: int = 0, length_scale: float = 1.0, noise_scale: float = 0.0,
                noise_scale_w: float = 0.0, seed: int = 0) -> int:
@@ -446,9 +509,15 @@ class Pool:
         return t
 
     def wait(self, ticket: int) -> np.ndarray:
+        """The PCM of a whole-utterance request; for a streaming request (submit_stream) the number of samples delivered."""
         p = C.POINTER(C.c_int16)()
         n = C.c_int32()
         rc = self.lib.sts_pool_wait(self.h, ticket, C.byref(p), C.byref(n))
+        if ticket in self._streams:
+            self._streams.pop(ticket)
+            if rc != 0:
+                raise StsError(f"sts_pool_wait: {rc}: {self.lib.sts_pool_last_error().decode()}")
+            return int(n.value)
         if rc != 0:
             raise StsError(f"sts_pool_wait: {rc}: {self.lib.sts_pool_last_error().decode()}")
         out = np.ctypeslib.as_array(p, shape=(n.value,)).copy() if n.value else np.zeros(0, np.int16)

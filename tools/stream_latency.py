@@ -1,0 +1,96 @@
+#!/usr/bin/env python3
+"""Time to first audio of N clients that each want their utterance streamed, three ways in one process:
+
+  (a) batched   one sts_infer_ids_batch_stream over the B utterances (chunk k of every utterance per step)
+  (b) serial    B sts_infer_ids_stream calls one after another on the same engine
+  (c) batch     one sts_infer_ids_batch of the B utterances (everyone hears the whole utterance at the end)
+
+Full-size synthetic HiFi-GAN (hifigan_sdp) and MB-iSTFT (mbb_fix) models, 128-phoneme utterances (the configs[1] shape, one
+distinct utterance per client), B in {1, 8, 32}, chunks of 32 and 64 frames.  Per (model, B, chunk, form): time to first chunk over
+the utterances (min / p50 / max), time to the last chunk, and seconds of audio delivered per wall second; the median of --reps
+timed repeats after one warm-up of every shape.  The launch-ahead memo is off, so (c) waits for its frame counts as (a) and (b) do.
+--rate R: PCM at R Hz (sts_set_output_rate).  --direct 1: the batched stream's step output goes to mapped pinned memory (sts_debug_set STS_DBG_STREAM_DIRECT) instead of one
+download.  Prints one JSON line per row.
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+from summertts_amd import engine, synth_blob as sb  # noqa: E402
+
+
+def _batched(syn, ids, chunk):
+    t0 = time.perf_counter()
+    chunks, times = syn.infer_batch_stream(ids, chunk)
+    wall = time.perf_counter() - t0
+    first = [t[0] for t in times]
+    return first, max(t[-1] for t in times), sum(sum(c.size for c in cs) for cs in chunks), wall
+
+
+def _serial(syn, ids, chunk):
+    first, last, n = [], 0.0, 0
+    t0 = time.perf_counter()
+    for x in ids:
+        got = []
+        chunks, _ = syn.infer_ids_stream(x, chunk, on_chunk=lambda pcm, off, t: got.append(time.perf_counter() - t0) and False)
+        first.append(got[0]); last = got[-1]
+        n += sum(c.size for c in chunks)
+    return first, last, n, time.perf_counter() - t0
+
+
+def _batch(syn, ids, chunk):
+    t0 = time.perf_counter()
+    pcm = syn.infer_batch(ids)
+    t = time.perf_counter() - t0
+    return [t] * len(ids), t, sum(p.size for p in pcm), t
+
+
+def main() -> None:
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--models", default="hifigan_sdp,mbb_fix")
+    ap.add_argument("--batches", default="1,8,32")
+    ap.add_argument("--chunks", default="32,64")
+    ap.add_argument("--phonemes", type=int, default=128)
+    ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--direct", type=int, default=0)
+    ap.add_argument("--rate", type=int, default=0, help="output sample rate (0: the native 16 kHz)")
+    a = ap.parse_args()
+    forms = {"batched_stream": _batched, "serial_streams": _serial, "one_batch": _batch}
+    for kind in a.models.split(","):
+        cfg = sb.full_cfg(kind)
+        syn = engine.Synthesizer(sb.make_blob(cfg, 1234))
+        syn.debug_set("launch_ahead", 0)
+        syn.debug_set("stream_direct", a.direct)
+        syn.set_output_rate(a.rate)
+        rate = syn.output_rate()
+        for B in [int(v) for v in a.batches.split(",")]:
+            ids = [sb.synthetic_ids(a.phonemes, cfg.vocab, salt=u) for u in range(B)]
+            for chunk in [int(v) for v in a.chunks.split(",")]:
+                for name, fn in forms.items():
+                    if name == "one_batch" and chunk != int(a.chunks.split(",")[0]):
+                        continue                                  # (does not depend on the chunk size)
+                    fn(syn, ids, chunk)                           # warm-up of this shape
+                    runs = [fn(syn, ids, chunk) for _ in range(a.reps)]
+                    med = lambda v: float(np.median(v))            # noqa: E731
+                    row = {"model": kind, "B": B, "chunk_frames": chunk if name != "one_batch" else None, "form": name,
+                           "first_ms_min": med([min(r[0]) * 1e3 for r in runs]),
+                           "first_ms_p50": med([np.median(r[0]) * 1e3 for r in runs]),
+                           "first_ms_max": med([max(r[0]) * 1e3 for r in runs]),
+                           "last_ms": med([r[1] * 1e3 for r in runs]),
+                           "audio_s_per_wall_s": med([r[2] / rate / r[3] for r in runs]),
+                           "rate": rate, "direct": a.direct, "reps": a.reps}
+                    print(json.dumps(row), flush=True)
+        syn.close()
+
+
+if __name__ == "__main__":
+    main()
