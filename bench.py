@@ -16,6 +16,11 @@ launches the N ranks itself -- one process per GPU, RANK / LOCAL_RANK / WORLD_SI
 127.0.0.1 -- and relays rank 0's JSON line.  Started under ``python -m torch.distributed.run`` it uses the
 environment it is given.
 
+A plain run does only what the headline needs: set-up, warm-up, the K timed steps, ``--dump-outputs`` and the JSON line (value,
+ms_per_step, p50 latency, the trunk roofline of the timed steps).  ``--full`` adds everything that takes runs of its own: the
+memo-hit, sustained, stage-breakdown, sts_infer_ids and other-arithmetic legs with their parity against the compiled reference,
+the measured MFMA ceiling, the request pool, the ``configs`` block, the CPU baseline and, at N > 1, the native-gather leg.
+
 Prints ONE JSON line on rank 0.
 """
 from __future__ import annotations
@@ -478,13 +483,13 @@ def main():
     ap.add_argument("--configs-block", default="auto", choices=["auto", "on", "off"],
                     help="append `configs`: BASELINE configs[2] (32 HiFi-GAN utterances) and configs[4] (64 MB-iSTFT utterances: the iSTFT / PQMF path) "
                          "measured in the same process at 5 steps each, with the parity of their shortest utterance against the compiled reference.  "
-                         "auto = on for the default configs[1] run on one GPU")
+                         "auto = on for the default configs[1] run on one GPU; both need --full")
     ap.add_argument("--multi", default="torch", choices=["torch", "native"],
                     help="--gpus N > 1: torch = one process per GPU, torch.distributed gather (the default, what a launcher starts); native = ONE process, "
                          "sts_multi_create_ex(devices 0..N-1, STS_MULTI_RCCL): the library's own RCCL gather, the code a C++ caller gets")
     ap.add_argument("--multi-leg", default="on", choices=["on", "off"],
                     help="--gpus N > 1 under --multi torch: after the distributed run, rank 0 also measures the library's native RCCL gather in-process and "
-                         "appends it as `multi_native` (on by default: one SCALE invocation measures both gathers)")
+                         "appends it as `multi_native` (on by default under --full: one SCALE invocation measures both gathers)")
     ap.add_argument("--debug-set", action="append", default=[], metavar="KEY=VALUE",
                     help="lab use: sts_debug_set on the timed engine, e.g. tile_claim=0 (A/B of a dispatch choice in one process / on one box)")
     ap.add_argument("--pipeline-engines", type=int, default=2,
@@ -497,9 +502,16 @@ def main():
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the last timed step returned to its caller (per-utterance sample counts and the PCM, "
                          "all utterances of the global batch) as DIR/*.npy; the inputs are the same from run to run for the same arguments")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run every leg that is not the headline: memo-hit, sustained, stage breakdown, sts_infer_ids, "
+                         "the other trunk arithmetics, the measured MFMA ceiling, the request pool, the configs block, the CPU baseline with parity "
+                         "against the compiled reference and, at --gpus N > 1, the native-gather leg (the options above that shape these legs "
+                         "act only with --full).  Off: set-up, warm-up, the timed steps, --dump-outputs and the JSON line")
     args = ap.parse_args()
     if args.dump_outputs and args.steps < 1:
         ap.error("--dump-outputs needs --steps >= 1")
+    if args.configs_block == "on" and not args.full:
+        ap.error("--configs-block on needs --full")
     if args.config:
         pz = CONFIG_PRESETS[args.config]
         args.workload, args.batch, args.phonemes, args.ragged = pz["workload"], pz["batch"], pz["phonemes"], pz["ragged"]
@@ -682,7 +694,7 @@ def main():
                          np.concatenate([by_utt[u] for u in order]) if order else [])
     # ---- the same K steps on the canonical batch, which the warm-up has put into the memo: every step runs ahead of its frame count
     memo_hit_leg = None
-    if fresh and dist is None and not stub:
+    if args.full and fresh and dist is None and not stub:
         tm0 = time.perf_counter()
         msamp = 0
         for _ in range(args.steps):
@@ -700,7 +712,7 @@ def main():
     last = syn.profile()
     # ---- the same step for at least --min-seconds more: what the box sustains once clocks and temperatures have settled
     sustained = None
-    if args.min_seconds > 0 and dist is None and not stub:
+    if args.full and args.min_seconds > 0 and dist is None and not stub:
         ts0 = time.perf_counter()
         ns, ssamp = 0, 0
         while time.perf_counter() - ts0 < args.min_seconds:
@@ -717,9 +729,11 @@ def main():
                      "note": "back-to-back steps right after the K timed ones, same process, same engine, batches the engine has not served before (a rotation of "
                              f"{len(fresh)} with the launch-ahead memo cleared at every wrap); `value` of the line stays the K-step figure the contract defines"}
 
-    # ---- stage breakdown: the same step with all eight stage events on (untimed for the headline)
+    # ---- stage breakdown: the same step with all eight stage events on (untimed for the headline); --timed-profiling 0 takes the
+    # roofline's kernel time from it, so that lab mode runs it without --full too
     stage_acc, stage_steps, stage_wall = dict(acc), max(1, args.steps), elapsed
-    if not stub:
+    stage_leg = not stub and (args.full or args.timed_profiling == 0)
+    if stage_leg:
         syn.set_profiling(True)
         step()
         drain()
@@ -738,7 +752,7 @@ def main():
     # DIFFERENT utterances of the step's length in rotation, launch-ahead off (its memo would hit on a repeated request): what a caller of
     # the drop-in API gets per call when nothing repeats
     api_leg = None
-    if dist is None and not stub and len(ids) == 1 and hasattr(syn, "infer_ids"):
+    if args.full and dist is None and not stub and len(ids) == 1 and hasattr(syn, "infer_ids"):
         syn.set_profiling(False)
         syn.debug_set("launch_ahead", 0)
         rot = [sb.synthetic_ids(len(ids[0]), cfg.vocab, salt=100 + q) for q in range(4)]
@@ -784,7 +798,7 @@ def main():
         finally:
             syn.set_record_taps(False)
 
-    gpu_out = {args.conv_math: capture_output()}
+    gpu_out = {args.conv_math: capture_output()} if args.full else {}
 
     # ---- extra timed legs (rank 0, one GPU): the same step with the trunk convs in the other arithmetics -- the exact-fp32 MFMA
     # instruction and, under the two-term fp16 default, the split-bf16 form -- so that the line carries every arithmetic path
@@ -823,17 +837,17 @@ def main():
         return leg
 
     f32_leg = bf3_leg = None
-    if dist is None and not stub and args.conv_math in ("bf16x3", "f16x2") and not args.no_f32_leg and hasattr(syn, "set_conv_math"):
+    if args.full and dist is None and not stub and args.conv_math in ("bf16x3", "f16x2") and not args.no_f32_leg and hasattr(syn, "set_conv_math"):
         f32_leg = extra_leg("f32")
         if args.conv_math == "f16x2":
             bf3_leg = extra_leg("bf16x3")
-    ceiling = measured_mfma_ceiling(3 if args.conv_math == "f16x2" else BF16_PRODUCTS_PER_F32) if (dist is None and not stub and rank == 0) else None
+    ceiling = measured_mfma_ceiling(3 if args.conv_math == "f16x2" else BF16_PRODUCTS_PER_F32) if (args.full and dist is None and not stub and rank == 0) else None
 
     # ---- extra figure (not the headline): the native request pool (sts_pool: N engines, one worker thread each,
     # one FIFO).  "pipelined" = batch-1 requests only overlapped across engines (max_batch 1); "burst" = the same
     # requests submitted at once with dynamic packed batching (max_batch 8).
     pipelined = None
-    if dist is None and args.pipeline_engines >= 2 and not stub:
+    if args.full and dist is None and args.pipeline_engines >= 2 and not stub:
         nreq = max(8, args.steps)
         pipelined = {"engines": args.pipeline_engines, "requests": nreq}
         for label, mb in (("pipelined_batch1", 1), ("burst_max_batch8", 8)):
@@ -987,7 +1001,7 @@ def main():
                                            {"tflops_fp32_equivalent": (SUSTAINED_F16_TWO_TERM_TFLOPS if products == 3 else SUSTAINED_BF16_SPLIT_TFLOPS) / products,
                                             "frac": achieved_tf / ((SUSTAINED_F16_TWO_TERM_TFLOPS if products == 3 else SUSTAINED_BF16_SPLIT_TFLOPS) / products),
                                             "measured": False,
-                                            "source": "not measured in this run (a multi-rank / forced-distributed run, or tools/ubench/libsts_ubench.so not built): the constant of the arithmetic that ran ("
+                                            "source": "not measured in this run (a run without --full, a multi-rank / forced-distributed run, or tools/ubench/libsts_ubench.so not built): the constant of the arithmetic that ran ("
                                                       + ("1490 fp16 TF/s on two-term planes, round 3" if products == 3 else "1712 bf16 TF/s on three-term planes, round 2")
                                                       + " of the nominal 2500)"}) if split else None,
                 "bf16_issued_tflops": bf16_tf,
@@ -1007,6 +1021,10 @@ def main():
             },
             "roofline_stages": stages,
         }
+        if not stage_leg:       # the timed steps record no stage events: without the stage leg there are no stage figures to report
+            for k in ("stage_ms_per_step", "stage_breakdown_leg", "roofline_stages"):
+                del out[k]
+            del out["host_us_per_step"]["step_wall_minus_device_stages"]
         out["roofline"].update(pmc_extra)
         if dist is not None:
             out["multi_gpu"] = {"backend": args.backend + (" (RCCL)" if args.backend == "nccl" else ""),
@@ -1032,8 +1050,8 @@ def main():
             out["sustained"] = sustained
         if api_leg is not None:
             out["api_call_leg"] = api_leg
-        want_cfgs = args.configs_block == "on" or (args.configs_block == "auto" and world == 1 and dist is None and not stub
-                                                   and config_label(args) == CONFIG_PRESETS[1]["label"])
+        want_cfgs = args.full and (args.configs_block == "on" or (args.configs_block == "auto" and world == 1 and dist is None and not stub
+                                                                   and config_label(args) == CONFIG_PRESETS[1]["label"]))
         if want_cfgs and not stub:
             # configs[2] and configs[4] in the driver's own line: the 32-utterance HiFi-GAN batch and the 64-utterance
             # MB-iSTFT batch (iSTFT + PQMF path), 5 timed steps each, parity of the shortest utterance against the compiled reference
@@ -1041,7 +1059,7 @@ def main():
             # call shape on the MB-iSTFT family ("configs[1]-mbb")
             out["configs"] = {("configs[1]-mbb" if n_ == 5 else f"configs[{n_}]"): measure_config(eng, torch, n_, args.conv_math, steps=(10 if n_ == 5 else 5), with_cpu=not args.no_cpu_baseline)
                               for n_ in (2, 4, 3, 5)}
-        if world == 1 and not args.no_cpu_baseline and not stub:
+        if args.full and world == 1 and not args.no_cpu_baseline and not stub:
             try:
                 cpu_T = args.cpu_sample_phonemes or (len(ids[cpu_u]) if ids else args.phonemes)
                 cpu_ids = ids[cpu_u] if (ids and cpu_T == len(ids[cpu_u])) else sb.synthetic_ids(cpu_T, cfg.vocab)
@@ -1071,7 +1089,7 @@ def main():
     # all N devices through the library's own sharding + RCCL gather (sts_multi_create_ex(0..N-1, STS_MULTI_RCCL): what a C++ caller of the drop-in
     # gets) in this process and appends the figures to the same line.  The other ranks have left their GPUs by then or are about to; a failure of
     # this leg never costs the line its headline.
-    if result_line is not None and world > 1 and args.multi_leg != "off":
+    if args.full and result_line is not None and world > 1 and args.multi_leg != "off":
         try:
             syn.close()
             nat = native_multi_measure(args)

@@ -27,7 +27,7 @@ def _run(extra, env_extra=None):
 
 
 def test_gpus_2_spawns_two_ranks_and_gathers():
-    out = _run(["--gpus", "2", "--steps", "3", "--warmup", "1", "--batch", "2", "--ragged"])
+    out = _run(["--gpus", "2", "--steps", "3", "--warmup", "1", "--batch", "2", "--ragged", "--full"])
     assert out["n_gpus"] == 2 and out["steps"] == 3 and out["scaling"] == "weak"
     assert out["config"]["launched_by"].startswith("bench.py")
     mg = out["multi_gpu"]
@@ -41,6 +41,20 @@ def test_gpus_2_spawns_two_ranks_and_gathers():
     assert "error" not in nat, nat
     assert nat["n_gpus"] == 2 and nat["rccl_ranks"] == 2 and nat["gather_mode"] == "rccl" and nat["value"] > 0 and nat["gather_ms_per_step"] > 0
     assert sum(nat["samples_per_device"]) == 3 * 100 * sum(lens)
+
+
+def test_plain_run_leaves_the_extra_legs_to_full():
+    """Without --full the line carries the headline of the timed steps and nothing that needs a run of its own: here the native-gather leg
+    of N > 1 stays out, and the headline fields are the same as under --full."""
+    args = ["--gpus", "2", "--steps", "3", "--warmup", "1", "--batch", "2", "--ragged"]
+    plain, full = _run(args), _run(args + ["--full"])
+    assert "multi_native" not in plain and "multi_native" in full
+    for k in ("metric", "unit", "higher_is_better", "dtype", "n_gpus", "steps", "warmup", "scaling"):
+        assert plain[k] == full[k], k
+    assert plain["multi_gpu"]["samples_per_rank"] == full["multi_gpu"]["samples_per_rank"]
+    assert abs(plain["value"] * plain["ms_per_step"] * 1e-3 * 3 - sum(plain["multi_gpu"]["samples_per_rank"])) < 1.0
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--configs-block", "on"], capture_output=True, text=True, timeout=120)
+    assert p.returncode != 0 and "--configs-block on needs --full" in p.stderr
 
 
 def test_torchrun_style_environment_is_respected():

@@ -1,6 +1,6 @@
 # same-box A/B of library variants (tools/var_build.sh): bench lines of configs 1-4 per variant, twice
 cd $GRAFT_REPO_ROOT
-B="python bench.py --no-cpu-baseline --no-f32-leg --configs-block off --pipeline-engines 0 --min-seconds 0"
+B="python bench.py --full --no-cpu-baseline --no-f32-leg --configs-block off --pipeline-engines 0 --min-seconds 0"
 line() { local label=$1; shift; "$@" 2>/dev/null | tail -1 | python -c "
 import sys, json
 d = json.loads(sys.stdin.read()); r = d['roofline']; st = d['stage_ms_per_step']

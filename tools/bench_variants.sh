@@ -5,7 +5,7 @@ out=$1; shift
 mkdir -p "$out"
 for spec in "$@"; do
   label=${spec%%|*}; rest=${spec#*|}; envs=${rest%%|*}; args=${rest#*|}
-  env $envs python bench.py --no-cpu-baseline --no-f32-leg --pipeline-engines 0 --steps 30 --warmup 5 $args > "$out/$label.json" 2> "$out/$label.err"
+  env $envs python bench.py --full --no-cpu-baseline --no-f32-leg --pipeline-engines 0 --steps 30 --warmup 5 $args > "$out/$label.json" 2> "$out/$label.err"
   python - "$out/$label.json" "$label" <<'PY'
 import json, sys
 try:

@@ -4,7 +4,7 @@ out=gpurun_out/knob_sweep; mkdir -p $out
 export SUMMERTTS_HIP_LIB=summertts_amd/lib/exp_knobs/libsummertts_hip.so
 for spec in "$@"; do
   label=${spec%%|*}; rest=${spec#*|}; envs=${rest%%|*}; args=${rest#*|}
-  env $envs timeout 150 python bench.py --no-cpu-baseline --no-f32-leg --pipeline-engines 0 --steps 20 --warmup 5 $args > $out/$label.json 2> $out/$label.err
+  env $envs timeout 150 python bench.py --full --no-cpu-baseline --no-f32-leg --pipeline-engines 0 --steps 20 --warmup 5 $args > $out/$label.json 2> $out/$label.err
   python - $out/$label.json "$label" <<'PY'
 import json, sys
 try:

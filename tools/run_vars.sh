@@ -1,8 +1,8 @@
-mkdir -p gpurun_out/r03h
+out=${RUN_VARS_OUT:-lab_out/run_vars}; mkdir -p $out
 for v in ${VARS:-base 6 22 30 base 22}; do
   if [ "$v" = base ]; then lib=summertts_amd/lib/libsummertts_hip.so; else lib=summertts_amd/lib/var/libvar$v.so; fi
-  SUMMERTTS_HIP_LIB=$lib timeout 100 python bench.py --no-cpu-baseline --no-f32-leg --pipeline-engines 0 --steps 30 --warmup 5 > gpurun_out/r03h/v$v.json 2> gpurun_out/r03h/v$v.err
-  python - gpurun_out/r03h/v$v.json $v <<'PY'
+  SUMMERTTS_HIP_LIB=$lib timeout 100 python bench.py --full --no-cpu-baseline --no-f32-leg --pipeline-engines 0 --steps 30 --warmup 5 > $out/v$v.json 2> $out/v$v.err
+  python - $out/v$v.json $v <<'PY'
 import json, sys
 try:
     d = json.loads([l for l in open(sys.argv[1]) if l.startswith("{")][-1]); s = d["stage_ms_per_step"]; r = d["roofline"]

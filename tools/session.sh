@@ -10,7 +10,7 @@ cd "$(dirname "$0")/.."
 WHAT=${1:-final}; TAG=${2:-r06}
 O=gpurun_out/$TAG; mkdir -p $O
 export TMPDIR=/tmp
-B="python bench.py --no-cpu-baseline --no-f32-leg --configs-block off --pipeline-engines 0 --min-seconds 0"
+B="python bench.py --full --no-cpu-baseline --no-f32-leg --configs-block off --pipeline-engines 0 --min-seconds 0"
 line() {   # label, bench args... -> one line of the step's figures
   local label=$1; shift
   $B "$@" 2>/dev/null | tail -1 | python -c "
@@ -36,9 +36,9 @@ tests)
 final)
   bash tools/profile_session.sh $O/c1 > $O/c1.log 2>&1
   bash tools/profile_session.sh $O/c4 --config 4 --steps 3 > $O/c4.log 2>&1
-  timeout 600 python bench.py --steps 20 --warmup 5 > $O/bench_c1.json 2> $O/bench_c1.err
-  for c in 2 3 4 5; do timeout 400 python bench.py --config $c --steps 5 --warmup 2 --cpu-reps 1 --cpu-threads 16 --pipeline-engines 0 > $O/bench_c$c.json 2> $O/bench_c$c.err; done
-  STS_BENCH_FORCE_DIST=1 timeout 200 python bench.py --steps 10 --warmup 3 --no-cpu-baseline --min-seconds 0 > $O/bench_c1_rccl1rank.json 2> $O/bench_c1_rccl1rank.err
+  timeout 600 python bench.py --full --steps 20 --warmup 5 > $O/bench_c1.json 2> $O/bench_c1.err
+  for c in 2 3 4 5; do timeout 400 python bench.py --full --config $c --steps 5 --warmup 2 --cpu-reps 1 --cpu-threads 16 --pipeline-engines 0 > $O/bench_c$c.json 2> $O/bench_c$c.err; done
+  STS_BENCH_FORCE_DIST=1 timeout 200 python bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --min-seconds 0 > $O/bench_c1_rccl1rank.json 2> $O/bench_c1_rccl1rank.err
   timeout 200 python tools/power_trace.py 5 > $O/power_trace.log 2>&1
   [ -f summertts_amd/lib/var/libvar6tt.so ] && SUMMERTTS_HIP_LIB=summertts_amd/lib/var/libvar6tt.so timeout 200 python tools/tile_trace_dump.py $O/tt_b1.npz 1 > $O/tt.log 2>&1
   for f in c1 c2 c3 c4 c5 c1_rccl1rank; do python - $O/bench_$f.json $f <<'PY'

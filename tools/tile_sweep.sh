@@ -5,7 +5,7 @@
 out=gpurun_out/tile_sweep; mkdir -p $out
 export SUMMERTTS_HIP_LIB=summertts_amd/lib/exp_knobs/libsummertts_hip.so
 for t in "$@"; do
-  STS_BF3_GROUP_TILE=$t timeout 100 python bench.py --no-cpu-baseline --no-f32-leg --pipeline-engines 0 --steps 30 --warmup 5 > $out/t$t.json 2> $out/t$t.err
+  STS_BF3_GROUP_TILE=$t timeout 100 python bench.py --full --no-cpu-baseline --no-f32-leg --pipeline-engines 0 --steps 30 --warmup 5 > $out/t$t.json 2> $out/t$t.err
   python - $out/t$t.json "$t" <<'PY'
 import json, sys
 try:
