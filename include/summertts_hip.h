@@ -156,6 +156,49 @@ int sts_get_output_rate(const sts_engine* e);
  * non-null; table == NULL asks for the sizes only, otherwise it receives the float32 [P][taps] table the kernel uses (capacity_floats
  * below P * taps: STS_EINVAL). */
 int sts_resample_table(int32_t in_rate, int32_t out_rate, int32_t* P, int32_t* Q, int32_t* taps, float* table, int64_t capacity_floats);
+/* ---- loudness (ABI 11; no reference counterpart: SynthesizerTrn.cpp:389-396 casts whatever level the model produces, and wraps
+ * around past |o| > 1.0009).  sts_set_loudness(e, mode, target_lufs, peak_dbfs) selects, per engine (the setting persists):
+ *   STS_LOUD_OFF (0, default): no extra work; PCM bit-identical to an engine that never set it.
+ *   STS_LOUD_MEASURE (1): every utterance of a whole-utterance call (sts_infer_ids, sts_infer_ids_batch, sts_run_batch) is measured;
+ *     the PCM is bit-identical to mode 0.  sts_get_loudness reads the results afterwards.
+ *   STS_LOUD_NORMALIZE (2): measures, then casts each utterance with its own gain.
+ * The measurement applies to the float wave at the output rate (sts_set_output_rate): the native wave at 16 kHz, otherwise the
+ * resampled wave (y before the cast; the "wave_out" tap).  For one utterance x[0 .. N) at rate fs:
+ *   1 K-weighting, two biquads in cascade from zero state (y = the filtered x), coefficients as sts_kweight_coeffs returns them:
+ *     high shelf  f0 = 1681.974450955533, G = 3.999843853973347 dB, Q = 0.7071752369554196; K = tan(pi f0 / fs), Vh = 10^(G / 20),
+ *                 Vb = Vh^0.4996667741545416, a0 = 1 + K / Q + K^2:  b = [Vh + Vb K / Q + K^2, 2 (K^2 - Vh), Vh - Vb K / Q + K^2] / a0,
+ *                 a = [1, 2 (K^2 - 1) / a0, (1 - K / Q + K^2) / a0];
+ *     high-pass   f0 = 38.13547087602444, Q = 0.5003270373238773, same K and a0:  b = [1, -2, 1], a = [1, 2 (K^2 - 1) / a0, (1 - K / Q + K^2) / a0].
+ *   2 Blocks: S = floor(fs / 10 + 0.5); block j = y[jS, jS + 4S) for j = 0 .. floor((N - 4S) / S) (none if N < 4S);
+ *     z_j = sum y^2 / (4S), l_j = -0.691 + 10 log10 z_j.
+ *   3 Gating (BS.1770-4, one channel, weight 1): keep l_j > -70; Gr = -0.691 + 10 log10(mean z of those) - 10; the final set has
+ *     l_j > -70 and l_j > Gr; L = -0.691 + 10 log10(mean z of the final set).  An empty final set (shorter than 400 ms, silent, or all
+ *     gated out): L = -inf, the utterance is unmeasured.
+ *   4 Peak p = max |x| (sample peak of the float signal).
+ *   5 Gain, with target T in [-70, 0] LUFS and ceiling C in [-30, 0] dBFS: g_L = 10^((T - L) / 20) if L is finite, else 1;
+ *     g = p > 0 ? min(g_L, 10^(C / 20) / p) : g_L, computed in float64 and rounded to float32 (|x g 32737| <= 32737: mode 2 never wraps).
+ *   6 Mode 2: pcm[i] = the reference's cast (int16)(int32)(x[i] g * 32737), one fp32 multiply in front of it.
+ *   7 Results per utterance of the last whole-utterance call, in call order: lufs (L, -INFINITY when unmeasured), peak (p), gain (g; mode 1
+ *     reports it too), blocks (size of the final set).
+ * An utterance's results are a function of its own x only, bit for bit (not of its batch companions, its position, or repetition).
+ * Streaming needs the whole utterance before normalizing: while the mode is not 0, sts_infer_ids_stream and sts_infer_ids_batch_stream
+ * answer STS_EINVAL (the engine stays usable).  Bad arguments (unknown mode, NaN or out-of-range target / ceiling): STS_EINVAL, nothing
+ * changes.  sts_get_loudness returns the count of the last call's results (0 after a call in mode 0, a streaming call or a failure) and
+ * copies them to out; out == NULL asks for the count alone, a capacity below it answers STS_EINVAL. */
+#define STS_LOUD_OFF 0
+#define STS_LOUD_MEASURE 1
+#define STS_LOUD_NORMALIZE 2
+typedef struct sts_loudness { float lufs; float peak; float gain; int32_t blocks; } sts_loudness;
+int sts_set_loudness(sts_engine* e, int mode, float target_lufs, float peak_dbfs);
+int sts_get_loudness_mode(const sts_engine* e, int* mode, float* target_lufs, float* peak_dbfs);
+int sts_get_loudness(sts_engine* e, sts_loudness* out, int64_t capacity);
+/* Host only (no device), like sts_resample_table: the K-weighting above for rate in [8000, 48000] as float64 {b0, b1, b2, a1, a2} of the
+ * shelf, then of the high-pass. */
+int sts_kweight_coeffs(int32_t rate, double coeffs[10]);
+/* The same kernels on caller signals: B float signals at `rate` packed back to back in x (host memory), lengths[b] samples each (0
+ * allowed); out[b] receives the results defined above for the given target / ceiling. */
+int sts_loudness_measure(int device, const float* x, const int64_t* lengths, int32_t B, int32_t rate,
+                         float target_lufs, float peak_dbfs, sts_loudness* out);
 /*   record intermediate tensors of the next run: "x_enc","m","logs","logw","z_p","z","wave","wave_out" ("logs": the second half of the
  *   encoder projection, computed only by runs that record taps or sample the prior; "wave_out": the resampled float wave, only at a
  *   non-native output rate, one-pass calls) */
@@ -238,7 +281,7 @@ int sts_set_profiling(sts_engine* e, int enable);
  * sizeof(sts_profile)) bytes, so a client compiled against an older header passes ITS sizeof and is never overrun;
  * sts_get_profile(e, p) == sts_get_profile_ex(e, p, sizeof(sts_profile)) of the header this library was built from -- use it only
  * when client and library are built together. */
-#define STS_ABI_VERSION 10
+#define STS_ABI_VERSION 11
 int sts_abi_version(void);
 /* bit 0: lab build (-DSTS_EXPERIMENTS: environment knobs of knobs.hpp, every conv tile code);
  * 0 for the shipped library */
@@ -310,6 +353,9 @@ int sts_pool_set_output_rate(sts_pool* p, int32_t rate);
  *   ticket or a negative STS_E* code (STS_EINVAL: bad ids, chunk_frames <= 0, a NULL callback). */
 int64_t sts_pool_submit_stream(sts_pool* p, const int32_t* ids, int32_t n, int32_t sid, float length_scale, float noise_scale,
                                float noise_scale_w, uint64_t seed, int32_t chunk_frames, sts_chunk_cb cb, void* user);
+/*   sts_pool_set_loudness (ABI 11): sts_set_loudness on every engine of the pool, modes 0 and 2 only (STS_EINVAL for 1).  STS_ESTATE while any
+ *   request is outstanding, as sts_pool_set_output_rate.  While the mode is 2, sts_pool_submit_stream answers STS_EINVAL. */
+int sts_pool_set_loudness(sts_pool* p, int mode, float target_lufs, float peak_dbfs);
 
 /* ---- multi-device batch (no reference counterpart).  One host process drives n_devices GPUs:
  * one engine (weights replicated) and one worker thread per entry of `devices` (HIP device indices; an index may repeat,
@@ -342,6 +388,8 @@ int sts_multi_set_conv_math(sts_multi* m, int mode);
 int sts_multi_set_noise(sts_multi* m, float noise_scale, float noise_scale_w, uint64_t seed);
 /*   sts_multi_set_output_rate: sts_set_output_rate on every engine of the handle; both gathers then exchange counts in output samples. */
 int sts_multi_set_output_rate(sts_multi* m, int32_t rate);
+/*   sts_multi_set_loudness (ABI 11): sts_set_loudness on every engine of the handle, modes 0 and 2 only (STS_EINVAL for 1). */
+int sts_multi_set_loudness(sts_multi* m, int mode, float target_lufs, float peak_dbfs);
 /*   test hook: the shared library that provides the nccl* entry points (NULL / "" = librccl.so.1) and whether STS_MULTI_RCCL may list
  *   one device several times (tests/fake_rccl: N emulated ranks on one GPU; real RCCL refuses duplicates).  Only before the first
  *   STS_MULTI_RCCL handle of the process is created.  TEST-ONLY: refused with STS_ESTATE unless the process environment carries

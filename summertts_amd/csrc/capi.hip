@@ -2,8 +2,10 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <algorithm>
 #include <new>
 #include <string>
+#include <vector>
 
 #include "engine.hpp"
 
@@ -221,6 +223,66 @@ int sts_resample_table(int32_t in_rate, int32_t out_rate, int32_t* P, int32_t* Q
     if (taps) *taps = 2 * d.K;
     if (table) resample_table(d, in_rate, out_rate, table);
     return STS_OK;
+}
+int sts_set_loudness(sts_engine* e, int mode, float target_lufs, float peak_dbfs) {
+    if (!e) return set_err(STS_EINVAL, "null engine");
+    const int rc = e->eng.set_loudness(mode, target_lufs, peak_dbfs);
+    return rc == STS_OK ? STS_OK : set_err(rc, e->eng.error());
+}
+int sts_get_loudness_mode(const sts_engine* e, int* mode, float* target_lufs, float* peak_dbfs) {
+    if (!e) return set_err(STS_EINVAL, "null engine");
+    if (mode) *mode = e->eng.loud_mode;
+    if (target_lufs) *target_lufs = e->eng.loud_target;
+    if (peak_dbfs) *peak_dbfs = e->eng.loud_peak;
+    return STS_OK;
+}
+int sts_get_loudness(sts_engine* e, sts_loudness* out, int64_t capacity) {
+    if (!e) return set_err(STS_EINVAL, "null engine");
+    const int64_t n = (int64_t)e->eng.loud_res.size();
+    if (!out) return (int)n;              // (the count alone)
+    if (capacity < n) return set_err(STS_EINVAL, "capacity below the last call's utterance count");
+    if (n > 0) memcpy(out, e->eng.loud_res.data(), (size_t)n * sizeof(sts_loudness));
+    return (int)n;
+}
+int sts_kweight_coeffs(int32_t rate, double coeffs[10]) {
+    if (!coeffs) return set_err(STS_EINVAL, "null argument");
+    if (!kweight_coeffs(rate, coeffs)) return set_err(STS_EINVAL, "rate must be an integer in [8000, 48000]");
+    return STS_OK;
+}
+int sts_loudness_measure(int device, const float* x, const int64_t* lengths, int32_t B, int32_t rate, float target_lufs, float peak_dbfs,
+                         sts_loudness* out) {
+    if (B < 1 || !lengths || !out) return set_err(STS_EINVAL, "B >= 1, lengths and out are required");
+    if (!loudness_args_valid(2, target_lufs, peak_dbfs)) return set_err(STS_EINVAL, "target in [-70, 0] LUFS, ceiling in [-30, 0] dBFS");
+    LoudArgs a{};
+    if (!loud_coef(rate, &a.k)) return set_err(STS_EINVAL, "rate must be an integer in [8000, 48000]");
+    std::vector<int> len(B);
+    int64_t total = 0, maxl = 0;
+    for (int b = 0; b < B; b++) {
+        if (lengths[b] < 0 || lengths[b] > (int64_t)1 << 30) return set_err(STS_EINVAL, "lengths must be in [0, 2^30]");
+        len[b] = (int)lengths[b]; total += lengths[b]; maxl = std::max<int64_t>(maxl, lengths[b]);
+    }
+    if (total > 0 && !x) return set_err(STS_EINVAL, "null signal");
+    if (hipSetDevice(device) != hipSuccess) return set_err(STS_EDEVICE, "no such device");
+    const size_t ws = loud_ws_bytes(B, total), xb = (((size_t)total * 4 + 255) & ~(size_t)255), lb = (((size_t)B * 4 + 255) & ~(size_t)255);
+    const size_t ob = (size_t)B * sizeof(sts_loudness);
+    char* d = nullptr;
+    if (hipMalloc((void**)&d, xb + lb + ob + ws) != hipSuccess) return set_err(STS_EDEVICE, "out of device memory");
+    hipStream_t st = nullptr;
+    bool ok = hipStreamCreate(&st) == hipSuccess;
+    a.x = (const float*)d; a.len = (const int*)(d + xb); a.ilen = 0; a.scale = 1; a.P = 1; a.Q = 1;
+    a.target = target_lufs; a.ceiling = peak_dbfs;
+    a.out = (float*)(d + xb + lb);
+    loud_ws_carve(a, d + xb + lb + ob, B, total);
+    ok = ok && (total == 0 || hipMemcpyAsync(d, x, (size_t)total * 4, hipMemcpyHostToDevice, st) == hipSuccess) &&
+         hipMemcpyAsync(d + xb, len.data(), (size_t)B * 4, hipMemcpyHostToDevice, st) == hipSuccess;
+    if (ok) {
+        loudness_run(a, B, maxl, nullptr, st);
+        ok = hipGetLastError() == hipSuccess && hipMemcpyAsync(out, a.out, ob, hipMemcpyDeviceToHost, st) == hipSuccess &&
+             hipStreamSynchronize(st) == hipSuccess;
+    }
+    if (st) (void)hipStreamDestroy(st);
+    (void)hipFree(d);
+    return ok ? STS_OK : set_err(STS_EDEVICE, "loudness measurement failed on the device");
 }
 int sts_build_flags(void) {
 #ifdef STS_EXPERIMENTS

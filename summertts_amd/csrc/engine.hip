@@ -32,6 +32,7 @@ Engine::~Engine() {
     if (pinned_) (void)hipHostFree(pinned_);
     if (pinned_pcm_) (void)hipHostFree(pinned_pcm_);
     if (d_rs_table) (void)hipFree(d_rs_table);
+    if (loud_host_) (void)hipHostFree(loud_host_);
     if (ovf_host_) (void)hipHostFree(ovf_host_);
     if (hmap_) (void)hipHostFree(hmap_);
     if (arrive_) (void)hipFree(arrive_);
@@ -344,6 +345,13 @@ int Engine::set_output_rate(int rate) {
     d_rs_table = t; out_rate = rate; rs = d;
     return STS_OK;
 }
+// sts_set_loudness: persists; an invalid argument changes nothing
+int Engine::set_loudness(int mode, float target, float peak) {
+    if (!loudness_args_valid(mode, target, peak))
+        return fail(STS_EINVAL, "loudness: mode 0 (off), 1 (measure) or 2 (normalize), target in [-70, 0] LUFS, ceiling in [-30, 0] dBFS");
+    loud_mode = mode; loud_target = target; loud_peak = peak;
+    return STS_OK;
+}
 int Engine::stream_halo() const {
     const int h = decoder_halo_frames(model);
     return resampling() ? h + (rs.K + model.hop_total - 1) / model.hop_total : h;
@@ -380,6 +388,8 @@ struct BufF {
     float *ff_h[2], *ff_part[2], *ff_macc[2], *ff_alt;        // one-launch-per-layer flow (wn_flow.hip): channel-minor h / partial sums / -m slices, alternate home of a z half
     int16_t* pcm;
     int16_t* pcm_nat; float* wave_out;   // at a non-native output rate: the decoder tail's own int16 samples (not returned), the resampled float wave (taps)
+    // loudness: where the resampler's int16 samples go (scratch when normalising, else pcm), the loudness kernels' workspace (or null)
+    int16_t* pcm_rs; char* lws;
     // batched streaming only (null otherwise): the step tables (stream_tab_bytes), the packed chunk buffer of a native-rate step, the
     // per-window speaker vectors and decoder conditioning of a multi-speaker HiFi-GAN decoder
     char* stab; int16_t* spack; float *gwin, *cond_win;
@@ -919,6 +929,7 @@ int Engine::run_frame_workspace(RunCtx& c) {
     }
     c.use_ff = use_ff; c.ffG = use_ff ? M.cp[0].ff.G : 0;
     BufF& bf = c.bf;
+    const bool loud = loud_mode != 0 && !ss, norm = loud && loud_mode == 2;
     auto layoutF = [&](Arena& A) {
         A.used = 0;
         for (int q = 0; q < 2; q++) {
@@ -936,10 +947,14 @@ int Engine::run_frame_workspace(RunCtx& c) {
             bf.tailA = A.get<float>((size_t)sbC * Lsb); bf.tailB = A.get<float>((size_t)sbC * Lsb);
             bf.tailC = A.get<float>((size_t)4 * Wcap * upS * 4);
         } else { bf.tailA = bf.tailB = bf.tailC = nullptr; }
-        bf.wave = A.get<float>(record_taps || resampling() ? (size_t)Wcap * hop : 1);
+        // (loudness: the tail always writes the float wave, the resampler its float output; normalising, their int16 samples go to
+        // scratch and the gain cast writes bf.pcm)
+        bf.wave = A.get<float>(record_taps || resampling() || loud ? (size_t)Wcap * hop : 1);
         bf.pcm = A.get<int16_t>((size_t)c.Ocap);
-        bf.pcm_nat = resampling() ? A.get<int16_t>((size_t)Wcap * hop) : bf.pcm;
-        bf.wave_out = record_taps && resampling() ? A.get<float>((size_t)c.Ocap) : nullptr;
+        bf.pcm_nat = resampling() || norm ? A.get<int16_t>((size_t)Wcap * hop) : bf.pcm;
+        bf.wave_out = (record_taps || loud) && resampling() ? A.get<float>((size_t)c.Ocap) : nullptr;
+        bf.pcm_rs = norm && resampling() ? A.get<int16_t>((size_t)c.Ocap) : bf.pcm;
+        bf.lws = loud ? A.get<char>(loud_ws_bytes(B, c.Ocap)) : nullptr;
         bf.stab = nullptr; bf.spack = nullptr; bf.gwin = bf.cond_win = nullptr;
         if (c.bstream) {
             bf.stab = A.get<char>(stream_tab_bytes(B));
@@ -956,8 +971,16 @@ int Engine::run_frame_workspace(RunCtx& c) {
     if (pcm_direct && host_pcm && !ss && B == 1 && !record_taps && pinned_pcm_dev_ && (size_t)c.Ocap * 2 + 256 <= pinned_pcm_cap_ &&
         (size_t)c.Ocap * 2 <= ((size_t)4 << 20)) {
         bf.pcm = pinned_pcm_dev_;
-        if (!resampling()) bf.pcm_nat = bf.pcm;     // (native rate: the tail's own samples are the PCM; otherwise the resampler writes there)
+        if (!resampling() && !norm) bf.pcm_nat = bf.pcm;     // (native rate: the tail's own samples are the PCM; otherwise the resampler or the gain cast writes there)
+        if (!norm) bf.pcm_rs = bf.pcm;
         pcm_in_host_ = true;
+    }
+    if (loud && loud_cap_ < B) {      // host-mapped room for the results: the gating kernel writes them there, the run's last synchronisation covers them
+        if (loud_host_) (void)hipHostFree(loud_host_);
+        loud_host_ = nullptr; loud_dev_ = nullptr; loud_cap_ = 0;
+        if (hipHostMalloc((void**)&loud_host_, (size_t)B * sizeof(sts_loudness), hipHostMallocMapped) != hipSuccess) { loud_host_ = nullptr; return fail(STS_EDEVICE, "pinned host allocation failed"); }
+        if (hipHostGetDevicePointer((void**)&loud_dev_, loud_host_, 0) != hipSuccess) { (void)hipHostFree(loud_host_); loud_host_ = nullptr; return fail(STS_EDEVICE, "mapped pinned buffer has no device address"); }
+        loud_cap_ = B;
     }
 
     Lvl& lv1 = c.lv1; lv1 = Lvl(); lv1.seg = (inl && !c.ahead) ? SegView{nullptr, nullptr, 1, 0, 0, p_lenF[0]} : SegView{d_offF, d_lenF, 1, 0, 0, 0};
@@ -1397,7 +1420,7 @@ int Engine::run_decode(RunCtx& c, int nw, long Wtot, int maxW, int zoff0, int wl
     // ---------------- decoder tail
     // (at a non-native output rate the tail always writes the float wave, and its int16 samples go to a scratch buffer: the resampler below
     // produces the PCM from the wave)
-    float* wave = record_taps || resampling() ? bf.wave : nullptr;
+    float* wave = record_taps || resampling() || (loud_mode != 0 && !ss) ? bf.wave : nullptr;
     int16_t* const pcm = bf.pcm_nat;
     const long Ntot = Wtot * hop;
     if (M.dec_type == 0) {          // Generator_hifigan.cpp:177-179 + SynthesizerTrn.cpp:389-396
@@ -1444,8 +1467,24 @@ int Engine::decode_end(RunCtx& c, const float* wave, int nw, long Wtot, int maxW
         a.x = wave;
         a.seg = winl ? SegView{nullptr, nullptr, hop, 0, 0, wlen0} : SegView{c.d_win + nw, c.d_win + 2 * nw, hop, 0, 0, 0};
         a.table = d_rs_table; a.P = rs.P; a.Q = rs.Q; a.K = rs.K;
-        a.pcm = c.bf.pcm; a.wave_out = c.bf.wave_out;
+        a.pcm = c.bf.pcm_rs; a.wave_out = c.bf.wave_out;
         resample_pcm(a, nw, out_count((long long)maxW * hop), stream);
+    }
+    if (loud_mode != 0 && !c.ss) {
+        // loudness of every window (= utterance) of the float signal at the output rate; normalising, the gain cast writes the PCM
+        if (loud_k_rate_ != out_rate) {
+            if (!loud_coef(out_rate, &loud_k_)) return fail(STS_EINVAL, "loudness: output rate outside [8000, 48000]");
+            loud_k_rate_ = out_rate;
+        }
+        LoudArgs a{};
+        a.x = resampling() ? c.bf.wave_out : wave;
+        const bool winl = nw == 1 && !c.no_inline_seg && wlen0 >= 0;
+        a.len = winl ? nullptr : c.d_win + 2 * nw; a.ilen = winl ? wlen0 : 0; a.scale = hop;
+        a.P = resampling() ? rs.P : 1; a.Q = resampling() ? rs.Q : 1;
+        a.target = loud_target; a.ceiling = loud_peak; a.k = loud_k_;
+        loud_ws_carve(a, c.bf.lws, nw, c.Ocap);
+        a.out = loud_dev_;
+        loudness_run(a, nw, out_count((long long)maxW * hop), loud_mode == 2 ? c.bf.pcm : nullptr, stream);
     }
     mark(4);
     if (wave && record_taps) {
@@ -1520,6 +1559,10 @@ int Engine::run_once(int B, const int32_t* const* ids, const int32_t* n, const i
     for (double& f : bytes_w_) f = 0;
     mfma_flops_ = 0; mfma_exec_ = 0; bf16_exec_ = 0; mfma_launches_ = 0; in_mfma_region_ = false;
 
+    loud_res.clear();
+    if (ss && loud_mode != 0)
+        return fail(STS_EINVAL, "streaming is not available while loudness measurement or normalization is on (sts_set_loudness mode 0 first): "
+                                "normalizing needs the whole utterance before its first sample leaves");
     host_t0_ = now_us(); host_t_sync_ = 0;
     RunCtx c;
     c.B = B; c.ids = ids; c.n = n; c.sid = sid; c.ls = ls; c.ss = ss; c.bstream = ss && B > 1;
@@ -1600,6 +1643,7 @@ int Engine::run_output(RunCtx& c) {
             prof.launch_ahead = 1;
         }
         HIPCK(hipGetLastError());
+        if (loud_mode != 0) loud_res.assign((const sts_loudness*)loud_host_, (const sts_loudness*)loud_host_ + B);   // (behind the run's last synchronisation)
     } else if (c.bstream) {
         const int rc = run_stream_steps(c);
         if (rc != STS_OK) return rc;

@@ -56,6 +56,10 @@ struct StreamSpec {
 };
 int decoder_halo_frames(const Model& M);
 inline bool noise_scale_valid(float s) { return s >= 0.f && s <= 3.0e38f; }   // (false for NaN and +inf)
+// sts_set_loudness: mode 0, 1 or 2, target in [-70, 0] LUFS, ceiling in [-30, 0] dBFS (false for NaN)
+inline bool loudness_args_valid(int mode, float target, float peak) {
+    return mode >= 0 && mode <= 2 && target >= -70.f && target <= 0.f && peak >= -30.f && peak <= 0.f;
+}
 
 struct Tap { std::vector<float> data; int channels = 0; long length = 0; };
 constexpr int kNativeRate = 16000;   // every model of the reference produces 16 kHz (test/main.cpp:13,16)
@@ -103,6 +107,12 @@ public:
     long long out_count(long long native) const { return resampling() ? (native * rs.P + rs.Q - 1) / rs.Q : native; }   // L_out = ceil(L_in P / Q)
     int set_output_rate(int rate);
     int stream_halo() const;           // decoder halo frames of a streaming chunk at the current rate (+ the resampler's K samples)
+    // loudness (sts_set_loudness, loudness.hip): 0 off (nothing extra runs), 1 measure every utterance of a whole-utterance call, 2 measure
+    // and cast each utterance with its own gain.  Measured on the float wave at the output rate; loud_res: the last call's results, one per
+    // utterance (empty after a call in mode 0, a streaming call or a failure)
+    int loud_mode = 0; float loud_target = -16.f, loud_peak = -1.f;
+    std::vector<sts_loudness> loud_res;
+    int set_loudness(int mode, float target, float peak);
     std::vector<int32_t> forced_dur; bool have_forced = false;
     bool record_taps = false; int profiling = 0;       // profiling: 0 off, 1 all stage events, 2 the matrix-core region's two events only (sts_set_profiling)
     int conv_mode = 0;
@@ -177,6 +187,8 @@ private:
     unsigned* ovf_host_ = nullptr; unsigned* ovf_ = nullptr;              // conv_math 3: overflow word (host-mapped) and its device address
     int* hmap_ = nullptr; int* hmap_dev_ = nullptr; size_t hmap_cap_ = 0;   // host-mapped result block of the durations kernel
     unsigned* arrive_ = nullptr; int seq_ = 0;
+    float* loud_host_ = nullptr; float* loud_dev_ = nullptr; int loud_cap_ = 0;   // host-mapped sts_loudness[loud_cap_]: the gating kernel's results
+    LoudCoef loud_k_{}; int loud_k_rate_ = 0;                                     // the kernels' filter tables for loud_k_rate_
     hipEvent_t ev_[8] = {};
     static constexpr int kAux = 3;            // ResBlock chains of one decoder stage run concurrently
     hipStream_t aux_[kAux] = {};

@@ -357,4 +357,25 @@ void resample_pcm(const ResampleArgs& a, int nwin, long long max_out, hipStream_
 // buffer per step); max_n = the most samples one window keeps
 void stream_pack(const int16_t* src, int16_t* dst, const int* src_off, const int* dst_off, int nwin, long long max_n, hipStream_t st);
 
+// Loudness measurement and normalisation (loudness.hip; the definition is there and in include/summertts_hip.h sts_set_loudness)
+constexpr int kLoudMinRate = 8000, kLoudMaxRate = 48000, kLoudPow = 9;
+// K-weighting {b0, b1, b2, a1, a2} of the shelf, then of the high-pass, float64 (false: rate outside [8000, 48000])
+bool kweight_coeffs(int rate, double c[10]);
+// what the kernels need of a rate: the filter, S = samples per 100 ms sub-block, Mp[d] = M^(2^d) for the chunk map M = A^32 (row-major 4 x 4)
+struct LoudCoef { double c[10]; double Mp[kLoudPow][16]; int S; };
+bool loud_coef(int rate, LoudCoef* k);
+struct LoudArgs {
+    const float* x;                      // the float signal, utterances packed back to back
+    const int* len; int ilen, scale, P, Q;   // utterance b has ceil(len[b] scale P / Q) samples (len == null: one utterance, ilen)
+    float target, ceiling;               // T (LUFS) and C (dBFS)
+    LoudCoef k;
+    long long* utab; double* E; double* tsum; float* tpeak; float* gain;   // workspace (loud_ws_carve)
+    float* out;                          // [B] sts_loudness {lufs, peak, gain, blocks} or null
+};
+// workspace of B utterances of total_samples samples in all (the frame-level arena's dry run sizes it)
+size_t loud_ws_bytes(int B, long long total_samples);
+void loud_ws_carve(LoudArgs& a, void* ws, int B, long long total_samples);
+// 3 launches (4 with pcm: the gain cast pcm = pcm_cast(x g) into pcm, packed like x); max_len = the longest utterance's sample count or more
+void loudness_run(const LoudArgs& a, int B, long long max_len, int16_t* pcm, hipStream_t st);
+
 }  // namespace sts

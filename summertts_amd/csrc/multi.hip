@@ -386,6 +386,16 @@ int sts_multi_set_output_rate(sts_multi* m, int32_t rate) {
     }
     return STS_OK;
 }
+int sts_multi_set_loudness(sts_multi* m, int mode, float target_lufs, float peak_dbfs) {
+    if (!m) return multi_err(STS_EINVAL, "null handle");
+    if (!loudness_args_valid(mode, target_lufs, peak_dbfs) || mode == 1)
+        return multi_err(STS_EINVAL, "loudness: mode 0 (off) or 2 (normalize), target in [-70, 0] LUFS, ceiling in [-30, 0] dBFS");
+    for (auto& e : m->engines) {
+        const int rc = e->set_loudness(mode, target_lufs, peak_dbfs);
+        if (rc != STS_OK) return multi_err(rc, e->error());
+    }
+    return STS_OK;
+}
 int sts_multi_set_conv_math(sts_multi* m, int mode) {
     if (!m) return multi_err(STS_EINVAL, "null handle");
     if (mode < 0 || mode > 3) return multi_err(STS_EINVAL, "conv math must be 0..3");

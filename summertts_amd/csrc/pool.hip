@@ -44,6 +44,7 @@ struct sts_pool {
     std::map<int64_t, std::shared_ptr<Request>> pending;   // submitted, not yet collected
     int64_t next_ticket = 1;
     int max_batch = 8;
+    int loud_mode = 0;                 // sts_pool_set_loudness (streaming requests are refused while it is 2)
     bool stop = false;
     int64_t batches = 0, requests = 0;
 
@@ -217,6 +218,7 @@ int64_t sts_pool_submit_stream(sts_pool* p, const int32_t* ids, int32_t n, int32
     {
         std::lock_guard<std::mutex> lk(p->mu);
         if (p->stop) return pool_err(STS_ESTATE, "pool is shutting down");
+        if (p->loud_mode != 0) return pool_err(STS_EINVAL, "streaming requests are refused while the pool normalizes loudness (sts_pool_set_loudness mode 0 first)");
         r->ticket = p->next_ticket++;
         p->queue.push_back(r);
         p->pending[r->ticket] = r;
@@ -254,6 +256,20 @@ int sts_pool_set_output_rate(sts_pool* p, int32_t rate) {
         const int rc = e->set_output_rate(rate);
         if (rc != STS_OK) return pool_err(rc, e->error());
     }
+    return STS_OK;
+}
+
+int sts_pool_set_loudness(sts_pool* p, int mode, float target_lufs, float peak_dbfs) {
+    if (!p) return pool_err(STS_EINVAL, "null pool");
+    if (!loudness_args_valid(mode, target_lufs, peak_dbfs) || mode == 1)
+        return pool_err(STS_EINVAL, "pool loudness: mode 0 (off) or 2 (normalize), target in [-70, 0] LUFS, ceiling in [-30, 0] dBFS");
+    std::lock_guard<std::mutex> lk(p->mu);
+    if (!p->pending.empty()) return pool_err(STS_ESTATE, "requests are outstanding: wait for them before changing the loudness setting");
+    for (auto& e : p->engines) {
+        const int rc = e->set_loudness(mode, target_lufs, peak_dbfs);
+        if (rc != STS_OK) return pool_err(rc, e->error());
+    }
+    p->loud_mode = mode;
     return STS_OK;
 }
 

@@ -113,6 +113,13 @@ def load_library() -> C.CDLL:
     lib.sts_resample_table.argtypes = [C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32),
                                        C.c_void_p, C.c_int64]
     lib.sts_pool_set_output_rate.argtypes = [C.c_void_p, C.c_int32]
+    lib.sts_set_loudness.argtypes = [C.c_void_p, C.c_int, C.c_float, C.c_float]
+    lib.sts_get_loudness_mode.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_float), C.POINTER(C.c_float)]
+    lib.sts_get_loudness.argtypes = [C.c_void_p, C.c_void_p, C.c_int64]
+    lib.sts_pool_set_loudness.argtypes = [C.c_void_p, C.c_int, C.c_float, C.c_float]
+    lib.sts_multi_set_loudness.argtypes = [C.c_void_p, C.c_int, C.c_float, C.c_float]
+    lib.sts_kweight_coeffs.argtypes = [C.c_int32, C.c_void_p]
+    lib.sts_loudness_measure.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_void_p]
     lib.sts_multi_set_output_rate.argtypes = [C.c_void_p, C.c_int32]
     lib.sts_infer_ids_batch_stream.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
                                                BATCH_CHUNK_CB, C.c_void_p, C.c_void_p]
@@ -140,7 +147,35 @@ EXPORTED_SYMBOLS = [
     "sts_set_noise", "sts_get_noise", "sts_pool_submit_ex", "sts_multi_set_noise",
     "sts_set_output_rate", "sts_get_output_rate", "sts_resample_table", "sts_pool_set_output_rate", "sts_multi_set_output_rate",
     "sts_infer_ids_batch_stream", "sts_pool_submit_stream",
+    "sts_set_loudness", "sts_get_loudness_mode", "sts_get_loudness", "sts_pool_set_loudness", "sts_multi_set_loudness",
+    "sts_kweight_coeffs", "sts_loudness_measure",
 ]
+
+LOUD_OFF, LOUD_MEASURE, LOUD_NORMALIZE = 0, 1, 2
+# sts_loudness: lufs (-inf when unmeasured), peak, gain, blocks
+LOUDNESS_DTYPE = np.dtype([("lufs", np.float32), ("peak", np.float32), ("gain", np.float32), ("blocks", np.int32)])
+
+
+def kweight_coeffs(rate: int) -> np.ndarray:
+    """The library's K-weighting for ``rate`` (include/summertts_hip.h sts_kweight_coeffs; host only, no GPU): float64 [2][5], each row
+    {b0, b1, b2, a1, a2} -- the shelf, then the high-pass."""
+    lib = load_library()
+    c = np.zeros(10, np.float64)
+    _check(lib, lib.sts_kweight_coeffs(int(rate), c.ctypes.data))
+    return c.reshape(2, 5)
+
+
+def loudness_measure(signals, rate: int, target_lufs: float = -16.0, peak_dbfs: float = -1.0, device: int = 0) -> np.ndarray:
+    """Integrated loudness, sample peak and normalising gain of each float signal in ``signals`` at ``rate`` on the GPU (the engine's
+    kernels, sts_loudness_measure) -> structured array of LOUDNESS_DTYPE, one entry per signal."""
+    lib = load_library()
+    sig = [np.ascontiguousarray(s, dtype=np.float32).ravel() for s in signals]
+    lens = np.asarray([s.size for s in sig], np.int64)
+    x = np.concatenate(sig) if sig and lens.sum() > 0 else np.zeros(1, np.float32)
+    out = np.zeros(len(sig), LOUDNESS_DTYPE)
+    _check(lib, lib.sts_loudness_measure(int(device), x.ctypes.data, lens.ctypes.data, len(sig), int(rate), float(target_lufs),
+                                         float(peak_dbfs), out.ctypes.data))
+    return out
 
 
 def resample_table(in_rate: int, out_rate: int):
@@ -329,6 +364,30 @@ class Synthesizer:
 
     def output_rate(self) -> int:
         return int(self.lib.sts_get_output_rate(self.h))
+
+    def set_loudness(self, mode: int, target_lufs: float = -16.0, peak_dbfs: float = -1.0):
+        """Loudness of every later whole-utterance call (include/summertts_hip.h sts_set_loudness): LOUD_OFF, LOUD_MEASURE (PCM unchanged,
+        results in ``loudness()``) or LOUD_NORMALIZE (each utterance cast with its own gain towards ``target_lufs``, peak at most
+        ``peak_dbfs``).  Invalid arguments raise and leave the setting unchanged."""
+        _check(self.lib, self.lib.sts_set_loudness(self.h, int(mode), float(target_lufs), float(peak_dbfs)))
+
+    def loudness_mode(self):
+        """(mode, target_lufs, peak_dbfs) as set by ``set_loudness``."""
+        m, t, p = C.c_int(), C.c_float(), C.c_float()
+        _check(self.lib, self.lib.sts_get_loudness_mode(self.h, C.byref(m), C.byref(t), C.byref(p)))
+        return m.value, t.value, p.value
+
+    def loudness(self) -> np.ndarray:
+        """Results of the last whole-utterance call, one per utterance in call order (LOUDNESS_DTYPE; empty in mode LOUD_OFF)."""
+        n = self.lib.sts_get_loudness(self.h, None, 0)
+        if n < 0:
+            _check(self.lib, n)
+        out = np.zeros(n, LOUDNESS_DTYPE)
+        if n:
+            rc = self.lib.sts_get_loudness(self.h, out.ctypes.data, n)
+            if rc < 0:
+                _check(self.lib, rc)
+        return out
 
     def set_conv_math(self, mode):
         """Arithmetic of the decoder trunk convs: 0 / 'bf16x3' = fp32 operands as three bf16 terms on the bf16 matrix cores,
@@ -530,6 +589,13 @@ class Pool:
         if rc != 0:
             raise StsError(f"sts_pool_set_output_rate: {rc}: {self.lib.sts_pool_last_error().decode()}")
 
+    def set_loudness(self, mode: int, target_lufs: float = -16.0, peak_dbfs: float = -1.0):
+        """``Synthesizer.set_loudness`` for every engine of the pool (LOUD_OFF or LOUD_NORMALIZE); raises while any request is outstanding
+        (STS_ESTATE)."""
+        rc = self.lib.sts_pool_set_loudness(self.h, int(mode), float(target_lufs), float(peak_dbfs))
+        if rc != 0:
+            raise StsError(f"sts_pool_set_loudness: {rc}: {self.lib.sts_pool_last_error().decode()}")
+
     def stats(self):
         b, r = C.c_int64(), C.c_int64()
         self.lib.sts_pool_stats(self.h, C.byref(b), C.byref(r))
@@ -608,6 +674,12 @@ class MultiDevice:
         rc = self.lib.sts_multi_set_output_rate(self.h, int(rate))
         if rc != 0:
             raise StsError(f"sts_multi_set_output_rate: {rc}: {self.lib.sts_multi_last_error().decode()}")
+
+    def set_loudness(self, mode: int, target_lufs: float = -16.0, peak_dbfs: float = -1.0):
+        """``Synthesizer.set_loudness`` for every device (LOUD_OFF or LOUD_NORMALIZE)."""
+        rc = self.lib.sts_multi_set_loudness(self.h, int(mode), float(target_lufs), float(peak_dbfs))
+        if rc != 0:
+            raise StsError(f"sts_multi_set_loudness: {rc}: {self.lib.sts_multi_last_error().decode()}")
 
     def set_conv_math(self, mode):
         m = {"bf16x3": 0, "f32": 1, "bf16x3_all": 2, "f16x2": 3}.get(mode, mode)
