@@ -248,6 +248,13 @@ enum { STS_DBG_ATTN_BLOCK_MIN_WGS = 1,
  * (value k; -1 = off), which takes the split-bf16 repeat of that step (k > 0) or of the whole call (k = 0); STS_DBG_STREAM_DIRECT -- 1 the
  * last kernel of a step writes the step's chunks into mapped pinned host memory itself, 0 (default) one download per step */
 enum { STS_DBG_STREAM_RETRY_STEP = 16, STS_DBG_STREAM_DIRECT = 17 };
+/* ABI 12, STS_DBG_POISON (tests): value = a 32-bit fill pattern, 0 = off (default).  While it is on, every call fills each workspace arena
+ * with the pattern on the engine's stream right after laying it out (before any upload or kernel writes into it; once per layout, never
+ * between the stages or stream steps of one call), and the host fills the output regions the call will write (the pinned PCM or chunk
+ * buffer up to the call's capacity with the pattern's low 16 bits, the loudness results of its utterances) before the first kernel that
+ * writes them is enqueued.  No result may depend on what the arenas held before: a poisoned call returns what an unpoisoned engine returns, bit for bit.
+ * sts_profile.poison_bytes reports the bytes the last call filled. */
+enum { STS_DBG_POISON = 18 };
 int sts_debug_set(sts_engine* e, int key, int value);
 
 /* Per-stage device timing of the last run, measured with HIP events on the engine's own stream. */
@@ -272,6 +279,7 @@ typedef struct sts_profile {
     float us_host_setup;                  /* host time from the entry of the run to the first launch being enqueued (input checks, tables, the one upload) */
     float us_host_enqueue;                /* host time from the entry of the run to the last launch being enqueued (the GPU runs behind it) */
     float us_host_tail;                   /* host time from the return of the run's last stream synchronisation to the return of the call */
+    int64_t poison_bytes;                 /* ABI 12: bytes of workspace and host outputs the last call filled under STS_DBG_POISON (0 when it is off) */
 } sts_profile;
 /* enable: 0 off; 1 HIP events at all eight stage boundaries of a run (ms_text_encoder ... ms_decoder_mfma); 2 only the two events around the
  * decoder's matrix-core region (ms_decoder_mfma; the per-stage times read 0) -- every event is a barrier packet between two kernels
@@ -281,7 +289,7 @@ int sts_set_profiling(sts_engine* e, int enable);
  * sizeof(sts_profile)) bytes, so a client compiled against an older header passes ITS sizeof and is never overrun;
  * sts_get_profile(e, p) == sts_get_profile_ex(e, p, sizeof(sts_profile)) of the header this library was built from -- use it only
  * when client and library are built together. */
-#define STS_ABI_VERSION 11
+#define STS_ABI_VERSION 12
 int sts_abi_version(void);
 /* bit 0: lab build (-DSTS_EXPERIMENTS: environment knobs of knobs.hpp, every conv tile code);
  * 0 for the shipped library */

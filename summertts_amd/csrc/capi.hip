@@ -196,6 +196,7 @@ int sts_debug_set(sts_engine* e, int key, int value) {
         case STS_DBG_PCM_DIRECT: e->eng.pcm_direct = value != 0; return STS_OK;
         case STS_DBG_STREAM_RETRY_STEP: e->eng.stream_retry_step = value < 0 ? -1 : value; return STS_OK;
         case STS_DBG_STREAM_DIRECT: e->eng.stream_direct = value != 0; return STS_OK;
+        case STS_DBG_POISON: e->eng.poison = (unsigned)value; return STS_OK;
         default: return set_err(STS_EINVAL, "unknown debug key");
     }
 }
@@ -499,10 +500,11 @@ int sts_debug_conv_h2p(int device, const float* x, int32_t Cin, int32_t L, const
         (void)hipMemset(db, 0, (size_t)Cout * 4);
         if (bias) (void)hipMemcpy(db, bias, (size_t)Cout * 4, hipMemcpyHostToDevice);
         (void)hipMemset(dovf, 0, 64);
-        split_planes(dx, L, Cin, L, in_slope, dxp, nullptr, L, dovf, nullptr);
+        const SegView whole{nullptr, nullptr, 1, 0, 0, L};
+        split_planes(dx, L, Cin, whole, 1, L, in_slope, dxp, nullptr, L, dovf, nullptr);
         if (res) {
             (void)hipMemcpy(dres, res, out_b, hipMemcpyHostToDevice);
-            split_planes(dres, L, Cout, L, 1.0f, dtmp, dres16, L, nullptr, nullptr);
+            split_planes(dres, L, Cout, whole, 1, L, 1.0f, dtmp, dres16, L, nullptr, nullptr);
         }
         H2PGroup G;
         memset(&G, 0, sizeof(G));

@@ -331,14 +331,19 @@ void conv_h2p_group(const H2PGroup& Gin, hipStream_t st, int tile) {
 // ------------------------------------------------------------------------------------------------
 // fp32 [C][ld] -> planes of lrelu(x, slope) + x16 copy: the entry of a stage (the upsampler still writes the channel-major tensor).
 // A wave converts 32 positions x 16 channels per step: lane (position, half) reads its 8 channels (two full 128-byte lines per load
-// instruction), writes one 16-byte unit per plane and one 32-byte unit of the x16 copy.
+// instruction), writes one 16-byte unit per plane and one 32-byte unit of the x16 copy.  Only the positions of the stage's segments
+// (grid z = segment) are converted and range-checked: a one-utterance call's buffers are sized for its 64-frame bucket, and the bucket tail
+// -- never written by the upsampler, never read by conv_h2p (its descriptors end at the segment) -- holds whatever an earlier call left there,
+// which must not raise the overflow word.
 // ------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void split_planes_kernel(const float* x, long x_ld, int C, long n, float slope, unsigned char* planes, float* x16, long out_ld, unsigned* ovf) {
+__global__ __launch_bounds__(256) void split_planes_kernel(const float* x, long x_ld, int C, SegView seg, float slope, unsigned char* planes, float* x16, long out_ld, unsigned* ovf) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int l31 = lane & 31, half = lane >> 5;
-    const long pos = ((long)blockIdx.x * 4 + wave) * 32 + l31;
+    const int b = blockIdx.z;
+    const long p = ((long)blockIdx.x * 4 + wave) * 32 + l31;
+    if (p >= (long)seg_len(seg, b)) return;
+    const long pos = (long)seg_start(seg, b) + p;
     const int c = blockIdx.y;
-    if (pos >= n) return;
     const size_t ps = (size_t)C * (size_t)out_ld * 2u;
     float v[8], t[8];
 #pragma unroll
@@ -359,9 +364,11 @@ __global__ __launch_bounds__(256) void split_planes_kernel(const float* x, long 
     if (amax > kH2Limit && ovf) *ovf = 1u;
 }
 
-void split_planes(const float* x, long x_ld, int C, long n, float slope, void* planes, float* x16, long out_ld, unsigned* ovf, hipStream_t st) {
-    if (n <= 0 || C <= 0) return;
-    hipLaunchKernelGGL(split_planes_kernel, dim3((unsigned)((n + 127) / 128), (unsigned)(C / 16)), dim3(256), 0, st, x, x_ld, C, n, slope, (unsigned char*)planes, x16, out_ld, ovf);
+void split_planes(const float* x, long x_ld, int C, const SegView& seg, int nb, long max_n, float slope, void* planes, float* x16, long out_ld,
+                  unsigned* ovf, hipStream_t st) {
+    if (max_n <= 0 || nb <= 0 || C <= 0) return;
+    hipLaunchKernelGGL(split_planes_kernel, dim3((unsigned)((max_n + 127) / 128), (unsigned)(C / 16), (unsigned)nb), dim3(256), 0, st, x, x_ld, C, seg, slope,
+                       (unsigned char*)planes, x16, out_ld, ovf);
 }
 
 }  // namespace sts

@@ -110,6 +110,28 @@ bool Engine::ensure_pinned(size_t bytes) {
     return true;
 }
 
+// STS_DBG_POISON (tests): no result may depend on what a buffer held before the call.  The arenas are filled right after each layout, before
+// the call's first upload or kernel writes into them -- never between its stages or stream steps, which legitimately read what earlier
+// ones wrote.  (The arena's capacity exceeds `used` by at least 4 KB: rounding up to whole words stays inside it.)
+void Engine::poison_arena(const Arena& a) {
+    if (!poison || !a.base || a.used == 0) return;
+    const size_t words = (a.used + 3) / 4;
+    if (hipMemsetD32Async((hipDeviceptr_t)a.base, (int)poison, words, stream) == hipSuccess) poison_bytes_ += (int64_t)words * 4;
+}
+void Engine::poison_host16(void* p, size_t samples) {
+    if (!poison || !p) return;
+    const uint16_t v = (uint16_t)(poison & 0xffffu);
+    uint16_t* q = (uint16_t*)p;
+    for (size_t i = 0; i < samples; i++) q[i] = v;
+    poison_bytes_ += (int64_t)samples * 2;
+}
+void Engine::poison_host32(void* p, size_t words) {
+    if (!poison || !p) return;
+    uint32_t* q = (uint32_t*)p;
+    for (size_t i = 0; i < words; i++) q[i] = poison;
+    poison_bytes_ += (int64_t)words * 4;
+}
+
 void Engine::stage_begin(int s) { cur_stage_ = s; }
 static double now_us() { return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 // profiling 1: all eight stage events; 2: only the two that bracket the decoder's matrix-core region (events 5 / 6) -- every event is a barrier
@@ -509,6 +531,7 @@ int Engine::run_setup(RunCtx& c) {
     arenaT_.measuring = true; layoutT(arenaT_);
     if (!ensure(arenaT_, arenaT_.used + 4096)) return fail(STS_EDEVICE, "out of device memory (phoneme-level workspace)");
     arenaT_.measuring = false; layoutT(arenaT_);
+    poison_arena(arenaT_);
 
     // ---------------- one H2D: geometry + ids (+ forced durations)
     const size_t meta_ints = c.meta_ints = (size_t)9 * B + 8;
@@ -966,6 +989,7 @@ int Engine::run_frame_workspace(RunCtx& c) {
     arenaF_.measuring = true; layoutF(arenaF_);
     if (!ensure(arenaF_, arenaF_.used + 4096)) return fail(STS_EDEVICE, "out of device memory (frame-level workspace)");
     arenaF_.measuring = false; layoutF(arenaF_);
+    poison_arena(arenaF_);
     // one short utterance with the PCM wanted on the host: the decoder's last kernel stores its int16 samples into the mapped pinned
     // buffer itself (posted writes over the host link, under the kernel's own run time) instead of a download queued behind it
     if (pcm_direct && host_pcm && !ss && B == 1 && !record_taps && pinned_pcm_dev_ && (size_t)c.Ocap * 2 + 256 <= pinned_pcm_cap_ &&
@@ -981,6 +1005,10 @@ int Engine::run_frame_workspace(RunCtx& c) {
         if (hipHostMalloc((void**)&loud_host_, (size_t)B * sizeof(sts_loudness), hipHostMallocMapped) != hipSuccess) { loud_host_ = nullptr; return fail(STS_EDEVICE, "pinned host allocation failed"); }
         if (hipHostGetDevicePointer((void**)&loud_dev_, loud_host_, 0) != hipSuccess) { (void)hipHostFree(loud_host_); loud_host_ = nullptr; return fail(STS_EDEVICE, "mapped pinned buffer has no device address"); }
         loud_cap_ = B;
+    }
+    if (poison) {           // the host-visible outputs of this call, before the first kernel that writes them is enqueued
+        if (host_pcm && !ss && pinned_pcm_) poison_host16(pinned_pcm_, std::min<size_t>((size_t)c.Ocap, pinned_pcm_cap_ / 2));
+        if (loud && loud_host_) poison_host32(loud_host_, (size_t)B * sizeof(sts_loudness) / 4);
     }
 
     Lvl& lv1 = c.lv1; lv1 = Lvl(); lv1.seg = (inl && !c.ahead) ? SegView{nullptr, nullptr, 1, 0, 0, p_lenF[0]} : SegView{d_offF, d_lenF, 1, 0, 0, 0};
@@ -1319,7 +1347,7 @@ int Engine::run_decode(RunCtx& c, int nw, long Wtot, int maxW, int zoff0, int wl
                         a2.Cin = c2.Cin; a2.Cout = c2.Cout; a2.ntap = c2.k; a2.tap_step = c2.dil; a2.tap_off = -c2.pad;
                         cur[j] = nxt;
                     }
-                    if (d == 0) split_planes(bup, l2.ld, up.Cout, l2.total, 0.1f, P0, X0, l2.ld, ovf_, stream);
+                    if (d == 0) split_planes(bup, l2.ld, up.Cout, l2.seg, l2.nb, l2.max_len, 0.1f, P0, X0, l2.ld, ovf_, stream);
                     const int ht = h2p_tile < 0 ? -1 : (up.Cout == 128 ? (h2p_tile & 0xff) : ((h2p_tile >> 8) & 0xff));   // lab: low byte = the 128-channel stage, next = wider ones; 0xff = automatic
                     conv_h2p_group(H1, stream, ht == 0xff ? -1 : ht);
                     conv_h2p_group(H2, stream, ht == 0xff ? -1 : ht);
@@ -1507,6 +1535,7 @@ static constexpr int kRetrySplitBf16 = 1;     // run_once: nothing was handed ou
 // An engine that had to repeat two calls in a row stays in the split-bf16 form (a model whose activations do not fit fp16 would
 // otherwise pay for both forms on every call) until sts_set_conv_math is called again.
 int Engine::run(int B, const int32_t* const* ids, const int32_t* n, const int32_t* sid, const float* ls, const StreamSpec* ss) {
+    poison_bytes_ = 0;          // (a split-bf16 repeat lays the arenas out again and fills them again: both fills count)
     if (conv_math != 3) return run_once(B, ids, n, sid, ls, ss);
     if (h2_disabled) {
         conv_math = 0;
@@ -1659,6 +1688,7 @@ int Engine::run_output(RunCtx& c) {
         if (!ensure_pinned(hp_off + (size_t)(out_count((long long)ss->chunk_frames * hop) + 1) * 2 + 256)) return fail(STS_EDEVICE, "pinned host allocation failed");
         int* pm = c.pm = (int*)pinned_;
         hp = (int16_t*)(pinned_ + hp_off);
+        poison_host16(hp, (size_t)out_count((long long)ss->chunk_frames * hop) + 1);
         int* pw = pm + 5 * B + 2;
         d_pcm = nullptr; total_samples = 0;
         for (long f0 = 0; f0 < F; f0 += ss->chunk_frames) {
@@ -1723,6 +1753,7 @@ int Engine::run_output(RunCtx& c) {
     }
     prof.us_host_setup = host_us_setup_; prof.us_host_enqueue = host_us_enq_;
     prof.us_host_tail = host_t_sync_ > 0 ? (float)(now_us() - host_t_sync_) : 0.f;
+    prof.poison_bytes = poison_bytes_;
     return STS_OK;
 }
 
@@ -1756,6 +1787,7 @@ int Engine::run_stream_steps(RunCtx& c) {
         }
         dst = pinned_pcm_dev_; hp = (int16_t*)pinned_pcm_;
     }
+    poison_host16(hp, (size_t)c.Ocap);
     c.d_win = (int*)bf.stab;
     std::vector<char> live(B, 1);
     if (ss->delivered) for (int b = 0; b < B; b++) ss->delivered[b] = 0;

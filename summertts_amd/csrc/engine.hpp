@@ -149,12 +149,17 @@ public:
                                        // 0: one launch per conv (sts_debug_set STS_DBG_FLOW_FUSED)
     int stream_retry_step = -1;        // tests (STS_DBG_STREAM_RETRY_STEP): a batched stream under conv_math 3 treats the overflow word as raised after step k
     int stream_direct = 0;             // batched streaming: 1 the pack / resample kernel writes each step's chunks into mapped pinned host memory, 0 one download (STS_DBG_STREAM_DIRECT)
+    unsigned poison = 0;               // tests (STS_DBG_POISON): 32-bit pattern every call fills its workspace arenas and host outputs with; 0 = off
+    int64_t poison_bytes_ = 0;         // bytes the current call has filled so far (sts_profile.poison_bytes)
     hipStream_t stream = nullptr;
 
 private:
     int fail(int code, const std::string& msg) { err_ = msg; return code; }
     bool ensure(Arena& a, size_t bytes);
     bool ensure_pinned(size_t bytes);
+    void poison_arena(const Arena& a);                 // STS_DBG_POISON: the arena's laid-out extent, on the engine's stream
+    void poison_host16(void* p, size_t samples);       // STS_DBG_POISON: host-visible int16 output, the pattern's low 16 bits
+    void poison_host32(void* p, size_t words);         // STS_DBG_POISON: host-visible 32-bit output words
     ConvArgs conv_args(const DConv& c, const float* x, const Lvl& lin, float* y, const Lvl& lout, const ConvOpt& o, double* flops);
     void conv(const DConv& c, const float* x, const Lvl& lin, float* y, const Lvl& lout, const ConvOpt& o);
     void ln(const DLn& l, const float* a, const float* b, const float* res, float* y, const Lvl& lv, int pre_relu, int post_gelu, int nb = 1, long b_stride = 0);

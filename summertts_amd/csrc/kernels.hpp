@@ -283,8 +283,10 @@ bool conv_h2w_group_eligible(const H2WGroup& G);
 void conv_h2w_group(const H2WGroup& G, hipStream_t st);
 int h2w_transform_weights(const float* wp, int k, int Cin, int Cout, float* dst);        // wp [k][Cin][Cout] -> dst [4 n3 + 3 n2][Cin][Cout]
 void to_x16(const float* x, long x_ld, int C, long n, float* x16, long out_ld, hipStream_t st);
-// fp32 [C][ld] -> planes of lrelu(x, slope) (+ the x16 copy when x16 != null); n = positions to convert (the packed total)
-void split_planes(const float* x, long x_ld, int C, long n, float slope, void* planes, float* x16, long out_ld, unsigned* ovf, hipStream_t st);
+// fp32 [C][ld] -> planes of lrelu(x, slope) (+ the x16 copy when x16 != null) at the positions of the nb segments of `seg` only (max_n >=
+// every segment's length); positions outside them are neither converted nor range-checked
+void split_planes(const float* x, long x_ld, int C, const SegView& seg, int nb, long max_n, float slope, void* planes, float* x16, long out_ld,
+                  unsigned* ovf, hipStream_t st);
 void conv_generic(const ConvArgs& a, hipStream_t st);
 
 void embed(const int* ids, const float* emb, int vocab, int H, float scale, float* x, long ld, int total, hipStream_t st);

@@ -40,7 +40,8 @@ class Profile(C.Structure):
                 ("bytes_text_encoder", C.c_double), ("bytes_duration", C.c_double), ("bytes_flow", C.c_double),
                 ("ms_sync_wait_host", C.c_float), ("flops_decoder_bf16_issued", C.c_double),
                 ("conv_math_fallbacks", C.c_int64), ("conv_math_pinned", C.c_int32), ("launch_ahead", C.c_int32), ("launch_ahead_misses", C.c_int64),
-                ("us_host_setup", C.c_float), ("us_host_enqueue", C.c_float), ("us_host_tail", C.c_float)]
+                ("us_host_setup", C.c_float), ("us_host_enqueue", C.c_float), ("us_host_tail", C.c_float),
+                ("poison_bytes", C.c_int64)]
 
     def as_dict(self) -> dict:
         return {k: getattr(self, k) for k, _ in self._fields_}
@@ -401,7 +402,7 @@ class Synthesizer:
 
     def debug_set(self, key: str, value: int):
         """Test hooks (include/summertts_hip.h sts_debug_set): 'attn_block_min_wgs' | 'flow_fused' | 'launch_ahead' | ..."""
-        _check(self.lib, self.lib.sts_debug_set(self.h, {"attn_block_min_wgs": 1, "flow_fused": 5, "launch_ahead": 6, "attn_reg": 7, "dds_tail": 8, "pcm_direct": 9, "memo_clear": 10, "h2p": 11, "h2p_tile": 12, "chain_streams": 13, "tail_fused": 14, "ups_rowph": 15, "stream_retry_step": 16, "stream_direct": 17}[key], int(value)))
+        _check(self.lib, self.lib.sts_debug_set(self.h, {"attn_block_min_wgs": 1, "flow_fused": 5, "launch_ahead": 6, "attn_reg": 7, "dds_tail": 8, "pcm_direct": 9, "memo_clear": 10, "h2p": 11, "h2p_tile": 12, "chain_streams": 13, "tail_fused": 14, "ups_rowph": 15, "stream_retry_step": 16, "stream_direct": 17, "poison": 18}[key], int(value)))
 
     def set_profiling(self, on):
         """False / True: no / all eight stage events per run; 2: only the two events around the decoder's matrix-core region (the

@@ -421,7 +421,10 @@ def test_full_size_properties(kind):
     a = syn.infer_ids(ids128, 0, 1.0)
     dur = syn.durations(128)
     assert a.size == int(dur.sum()) * cfg.hop_total and a.size > 128 * cfg.hop_total
+    syn.debug_set("poison", 0x7BFF7BFF)       # (workspaces and the PCM buffer filled before the second call: an unwritten sample cannot pass)
     assert np.array_equal(a, syn.infer_ids(ids128, 0, 1.0)), "not deterministic"
+    assert syn.profile()["poison_bytes"] > 0
+    syn.debug_set("poison", 0)
     slow = syn.infer_ids(ids128, 0, 1.5)
     assert (syn.durations(128) >= dur).all() and slow.size > a.size   # lengthScale only stretches
     # batch invariance at full size
@@ -1161,11 +1164,14 @@ def test_launch_ahead_for_packed_batches(kind, size):
             o = port.infer_ids(ids[i], sid[i], ls[i])
             assert_pcm_close(first[off:off + int(n1[i])], o["pcm"], f"{kind} member {i} (waiting path) vs the oracle")
             off += int(n1[i])
-    for _ in range(2):
+    for pattern in (0, 0x7FC00000):          # (the second memo launch on poisoned workspaces and PCM buffer: an unwritten sample cannot pass)
+        syn.debug_set("poison", pattern)
         n2 = syn.run_batch(ids, sid, ls)
         p = syn.profile()
         assert p["launch_ahead"] == 1 and p["launch_ahead_misses"] == 0 and p["ms_sync_wait_host"] < 0.05, p
+        assert (p["poison_bytes"] > 0) == (pattern != 0)
         assert np.array_equal(n2, n1) and np.array_equal(syn.pcm_host(), first), "launch-ahead changed a sample of the batch"
+    syn.debug_set("poison", 0)
     # a member the engine has not served: the whole batch waits; a sub-batch of known members runs ahead
     ids_new = ids[:-1] + [sb.synthetic_ids(lens[-1], cfg.vocab, salt=77)]
     fresh = engine.Synthesizer(blob)
@@ -1285,15 +1291,18 @@ def test_launch_ahead_returns_the_samples_of_the_waiting_path():
     p1 = syn.profile()
     assert p1["launch_ahead"] == 0 and (syn.durations(len(ids)) == dur_u).all()
     assert_pcm_close(first, pcm_ref, "waiting path vs the reference")
-    for _ in range(3):
+    for pattern in (0x7FC00000, -1, 0x7BFF7BFF):       # (workspaces and the PCM buffer poisoned before each memo hit: an unwritten sample cannot pass)
+        syn.debug_set("poison", pattern)
         again = syn.infer_ids(ids, sid_u, ls_u)
         p2 = syn.profile()
+        assert p2["poison_bytes"] > 0
         assert p2["launch_ahead"] == 1 and p2["launch_ahead_misses"] == 0
         assert p2["ms_sync_wait_host"] < 0.02, p2["ms_sync_wait_host"]        # (the count is read after the run's one stream synchronisation)
         assert np.array_equal(again, first), "launch-ahead changed a sample"
         assert (syn.durations(len(ids)) == dur_u).all()
         assert abs(p2["flops_decoder_mfma"] - p1["flops_decoder_mfma"]) <= 1e-6 * p1["flops_decoder_mfma"]      # booked for the real count
         assert p2["frames"] == p1["frames"] and p2["samples"] == first.size
+    syn.debug_set("poison", 0)
     syn.debug_set("launch_ahead", 0)
     assert np.array_equal(syn.infer_ids(ids, sid_u, ls_u), first) and syn.profile()["launch_ahead"] == 0
     syn.debug_set("launch_ahead", 1)
@@ -1310,10 +1319,13 @@ def test_launch_ahead_returns_the_samples_of_the_waiting_path():
     got_other = syn.infer_ids(ids2, sid_u, ls_u)
     assert syn.profile()["launch_ahead"] == 0 and np.array_equal(got_other, want_other)
     # ... and each of the three, once served, runs ahead with its own count: bit-identical whatever came before
+    syn.debug_set("poison", 0x7BFF7BFF)
     for a_ids, a_ls, want in ((ids, ls_u, first), (ids, 1.3, want_long), (ids2, ls_u, want_other), (ids, ls_u, first)):
         got = syn.infer_ids(a_ids, sid_u, a_ls)
         assert syn.profile()["launch_ahead"] == 1 and syn.profile()["launch_ahead_misses"] == 0
+        assert syn.profile()["poison_bytes"] > 0 and syn.profile()["conv_math_fallbacks"] == 0
         assert np.array_equal(got, want), "a remembered request changed a sample"
+    syn.debug_set("poison", 0)
     # a collision (test mode: the memo keyed by the phoneme count alone): the count falls outside the predicted bucket in either direction
     syn.debug_set("launch_ahead", 2)
     assert np.array_equal(syn.infer_ids(ids, sid_u, ls_u), first) and syn.profile()["launch_ahead"] == 0
@@ -1321,8 +1333,11 @@ def test_launch_ahead_returns_the_samples_of_the_waiting_path():
     assert syn.profile()["launch_ahead_misses"] == 1 and np.array_equal(got_long, want_long), "the repeated run differs from a waiting run"
     back = syn.infer_ids(ids, sid_u, ls_u)                        # predicted the longer count, needs fewer
     assert syn.profile()["launch_ahead_misses"] == 2 and np.array_equal(back, first), "an over-provisioned run was not repeated"
+    syn.debug_set("poison", -1)
     again = syn.infer_ids(ids, sid_u, ls_u)
     assert syn.profile()["launch_ahead"] == 1 and syn.profile()["launch_ahead_misses"] == 2 and np.array_equal(again, first)
+    assert syn.profile()["poison_bytes"] > 0
+    syn.debug_set("poison", 0)
     syn.close()
     # every decoder family / duration predictor, small models, against the oracle
     for kind in ("mbb_fix", "ms_sdp", "istft_fix", "ms_hifigan_sdp", "odd"):
