@@ -199,6 +199,48 @@ int sts_kweight_coeffs(int32_t rate, double coeffs[10]);
  * allowed); out[b] receives the results defined above for the given target / ceiling. */
 int sts_loudness_measure(int device, const float* x, const int64_t* lengths, int32_t B, int32_t rate,
                          float target_lufs, float peak_dbfs, sts_loudness* out);
+/* ---- look-ahead peak limiter (ABI 13; no reference counterpart).  sts_set_limiter(e, mode, gain_db, ceiling_dbfs, lookahead_ms): mode
+ * STS_LIMITER_OFF (0, default: nothing extra runs, PCM bit-identical to an engine that never set it) or STS_LIMITER_ON (1).  Valid:
+ * gain_db in [-40, 40], ceiling_dbfs in [-30, 0], lookahead_ms in [0.25, 10]; NaN, anything outside, or an unknown mode: STS_EINVAL,
+ * nothing changes.  The setting persists like sts_set_noise; sts_get_limiter_mode returns the four values.
+ * The limiter works on the float wave at the output rate fs (the native wave at 16 kHz, else the resampler's output: the signal
+ * loudness measures).  For one utterance x[0 .. N):
+ *   1 Design (host, float64; exactly what sts_limiter_design returns): H = floor(lookahead_ms fs / 1000 + 0.5) (1 <= H <= 480),
+ *     c = 10^(ceiling_dbfs / 20), G = 10^(gain_db / 20).
+ *   2 Static gain g0 = float32(G g_loud) (one float64 product, rounded once); g_loud = 1, or under loudness mode 2 the utterance's
+ *     loudness gain as float32.  While the limiter is on, step 5 of the loudness definition drops its peak clamp: g = g_L (the limiter
+ *     holds the ceiling instead; sts_loudness.gain reports g_L, peak_dbfs is accepted and unused).  Loudness mode 1 is unchanged.
+ *   3 v[n] = float32(x[n] g0); a[n] = |v[n]| as float64.
+ *   4 Required gain in fixed point: q[n] = floor(min(1, c / a[n]) 2^30), division and product in float64 (a[n] <= c: q = 2^30; a[n]
+ *     infinite or NaN: q = 0).  Outside the utterance (n < 0 or n >= N): q = 2^30.
+ *   5 Sliding minimum: m[k] = min q[k - H .. k + H] for -H <= k < N + H.
+ *   6 Sliding mean of the minimum, exact: S[n] = sum m[n - H .. n + H] in 64-bit integers; s[n] = float32(float64(S[n]) /
+ *     float64((2H + 1) 2^30)).
+ *   7 y[n] = float32(v[n] s[n]); pcm[n] = the reference's cast (int16)(int32)(y[n] * 32737).
+ * Every window of step 6 contains a window of step 5 that contains n, so s[n] <= c / a[n] and |pcm| <= floor(32737 c) + 1: the cast never
+ * wraps.  Where no sample within 2H exceeds the ceiling, s[n] = 1.0f exactly and y[n] = v[n].  y[n] depends on x[n - 2H .. n + 2H] only,
+ * and steps 4-6 are integer arithmetic: an utterance's result is a function of its own samples, bit for bit.
+ * Whole-utterance calls (sts_infer_ids, sts_infer_ids_batch, sts_run_batch) limit after the resampler and the loudness kernels; the tap
+ * "wave_lim" is y ("wave" / "wave_out" stay the unlimited signals).  sts_get_limiter (conventions of sts_get_loudness; count 0 after a
+ * call with the limiter off, a streaming call or a failure) returns per utterance: gain = g0, min_gain = min s[n] (1.0 when untouched),
+ * peak_out = max |y[n]| over the samples whose y is not NaN, limited = the number of samples with S[n] < (2H + 1) 2^30.
+ * Streaming (sts_infer_ids_stream, sts_infer_ids_batch_stream, sts_pool_submit_stream) is allowed with the limiter on while the loudness
+ * mode is 0: a chunk that emits outputs [j0, j1) is limited from the float signal over [j0 - 2H, j1 + 2H) clipped to the utterance, so
+ * the decode window grows and sts_stream_halo_frames reports the halo at the current rate and limiter setting.  Concatenated chunks
+ * equal the whole-utterance PCM (bit for bit under a pinned conv mode: the streaming contract).  Streaming calls report no stats. */
+#define STS_LIMITER_OFF 0
+#define STS_LIMITER_ON 1
+typedef struct sts_limiter_stats { float gain; float min_gain; float peak_out; int32_t limited; } sts_limiter_stats;
+int sts_set_limiter(sts_engine* e, int mode, float gain_db, float ceiling_dbfs, float lookahead_ms);
+int sts_get_limiter_mode(const sts_engine* e, int* mode, float* gain_db, float* ceiling_dbfs, float* lookahead_ms);
+int sts_get_limiter(sts_engine* e, sts_limiter_stats* out, int64_t capacity);
+/* Host only (no device), like sts_resample_table: step 1 above for rate in [8000, 48000]; each of H, c, G is set when non-null. */
+int sts_limiter_design(int32_t rate, float gain_db, float ceiling_dbfs, float lookahead_ms, int32_t* H, double* c, double* G);
+/* The same kernel on caller signals: B float signals at `rate` packed back to back in x (host memory), lengths[b] samples each (0
+ * allowed), g_loud = 1.  y (float) and pcm (int16) receive the limited signals packed like x, stats[b] the results above; each of the
+ * three may be NULL. */
+int sts_limiter_apply(int device, const float* x, const int64_t* lengths, int32_t B, int32_t rate, float gain_db, float ceiling_dbfs,
+                      float lookahead_ms, float* y, int16_t* pcm, sts_limiter_stats* stats);
 /*   record intermediate tensors of the next run: "x_enc","m","logs","logw","z_p","z","wave","wave_out" ("logs": the second half of the
  *   encoder projection, computed only by runs that record taps or sample the prior; "wave_out": the resampled float wave, only at a
  *   non-native output rate, one-pass calls) */
@@ -289,7 +331,7 @@ int sts_set_profiling(sts_engine* e, int enable);
  * sizeof(sts_profile)) bytes, so a client compiled against an older header passes ITS sizeof and is never overrun;
  * sts_get_profile(e, p) == sts_get_profile_ex(e, p, sizeof(sts_profile)) of the header this library was built from -- use it only
  * when client and library are built together. */
-#define STS_ABI_VERSION 12
+#define STS_ABI_VERSION 13
 int sts_abi_version(void);
 /* bit 0: lab build (-DSTS_EXPERIMENTS: environment knobs of knobs.hpp, every conv tile code);
  * 0 for the shipped library */
@@ -364,6 +406,9 @@ int64_t sts_pool_submit_stream(sts_pool* p, const int32_t* ids, int32_t n, int32
 /*   sts_pool_set_loudness (ABI 11): sts_set_loudness on every engine of the pool, modes 0 and 2 only (STS_EINVAL for 1).  STS_ESTATE while any
  *   request is outstanding, as sts_pool_set_output_rate.  While the mode is 2, sts_pool_submit_stream answers STS_EINVAL. */
 int sts_pool_set_loudness(sts_pool* p, int mode, float target_lufs, float peak_dbfs);
+/*   sts_pool_set_limiter (ABI 13): sts_set_limiter on every engine of the pool.  STS_ESTATE while any request is outstanding, as
+ *   sts_pool_set_output_rate.  Streaming requests are limited chunk by chunk. */
+int sts_pool_set_limiter(sts_pool* p, int mode, float gain_db, float ceiling_dbfs, float lookahead_ms);
 
 /* ---- multi-device batch (no reference counterpart).  One host process drives n_devices GPUs:
  * one engine (weights replicated) and one worker thread per entry of `devices` (HIP device indices; an index may repeat,
@@ -398,6 +443,8 @@ int sts_multi_set_noise(sts_multi* m, float noise_scale, float noise_scale_w, ui
 int sts_multi_set_output_rate(sts_multi* m, int32_t rate);
 /*   sts_multi_set_loudness (ABI 11): sts_set_loudness on every engine of the handle, modes 0 and 2 only (STS_EINVAL for 1). */
 int sts_multi_set_loudness(sts_multi* m, int mode, float target_lufs, float peak_dbfs);
+/*   sts_multi_set_limiter (ABI 13): sts_set_limiter on every engine of the handle. */
+int sts_multi_set_limiter(sts_multi* m, int mode, float gain_db, float ceiling_dbfs, float lookahead_ms);
 /*   test hook: the shared library that provides the nccl* entry points (NULL / "" = librccl.so.1) and whether STS_MULTI_RCCL may list
  *   one device several times (tests/fake_rccl: N emulated ranks on one GPU; real RCCL refuses duplicates).  Only before the first
  *   STS_MULTI_RCCL handle of the process is created.  TEST-ONLY: refused with STS_ESTATE unless the process environment carries

@@ -285,6 +285,80 @@ int sts_loudness_measure(int device, const float* x, const int64_t* lengths, int
     (void)hipFree(d);
     return ok ? STS_OK : set_err(STS_EDEVICE, "loudness measurement failed on the device");
 }
+int sts_set_limiter(sts_engine* e, int mode, float gain_db, float ceiling_dbfs, float lookahead_ms) {
+    if (!e) return set_err(STS_EINVAL, "null engine");
+    const int rc = e->eng.set_limiter(mode, gain_db, ceiling_dbfs, lookahead_ms);
+    return rc == STS_OK ? STS_OK : set_err(rc, e->eng.error());
+}
+int sts_get_limiter_mode(const sts_engine* e, int* mode, float* gain_db, float* ceiling_dbfs, float* lookahead_ms) {
+    if (!e) return set_err(STS_EINVAL, "null engine");
+    if (mode) *mode = e->eng.lim_mode;
+    if (gain_db) *gain_db = e->eng.lim_gain_db;
+    if (ceiling_dbfs) *ceiling_dbfs = e->eng.lim_ceiling;
+    if (lookahead_ms) *lookahead_ms = e->eng.lim_ms;
+    return STS_OK;
+}
+int sts_get_limiter(sts_engine* e, sts_limiter_stats* out, int64_t capacity) {
+    if (!e) return set_err(STS_EINVAL, "null engine");
+    const int64_t n = (int64_t)e->eng.lim_res.size();
+    if (!out) return (int)n;              // (the count alone)
+    if (capacity < n) return set_err(STS_EINVAL, "capacity below the last call's utterance count");
+    if (n > 0) memcpy(out, e->eng.lim_res.data(), (size_t)n * sizeof(sts_limiter_stats));
+    return (int)n;
+}
+int sts_limiter_design(int32_t rate, float gain_db, float ceiling_dbfs, float lookahead_ms, int32_t* H, double* c, double* G) {
+    LimiterDesign d;
+    if (!limiter_design(rate, gain_db, ceiling_dbfs, lookahead_ms, &d))
+        return set_err(STS_EINVAL, "rate in [8000, 48000], gain in [-40, 40] dB, ceiling in [-30, 0] dBFS, look-ahead in [0.25, 10] ms");
+    if (H) *H = d.H;
+    if (c) *c = d.c;
+    if (G) *G = d.G;
+    return STS_OK;
+}
+int sts_limiter_apply(int device, const float* x, const int64_t* lengths, int32_t B, int32_t rate, float gain_db, float ceiling_dbfs,
+                      float lookahead_ms, float* y, int16_t* pcm, sts_limiter_stats* stats) {
+    if (B < 1 || !lengths) return set_err(STS_EINVAL, "B >= 1 and lengths are required");
+    LimiterDesign dsg;
+    if (!limiter_design(rate, gain_db, ceiling_dbfs, lookahead_ms, &dsg))
+        return set_err(STS_EINVAL, "rate in [8000, 48000], gain in [-40, 40] dB, ceiling in [-30, 0] dBFS, look-ahead in [0.25, 10] ms");
+    std::vector<int> len(B);
+    int64_t total = 0, maxl = 0;
+    for (int b = 0; b < B; b++) {
+        if (lengths[b] < 0 || lengths[b] > (int64_t)1 << 30) return set_err(STS_EINVAL, "lengths must be in [0, 2^30]");
+        len[b] = (int)lengths[b]; total += lengths[b]; maxl = std::max<int64_t>(maxl, lengths[b]);
+    }
+    if (total > (int64_t)1 << 30) return set_err(STS_EINVAL, "the signals must hold at most 2^30 samples in all");
+    if (total > 0 && !x) return set_err(STS_EINVAL, "null signal");
+    if (hipSetDevice(device) != hipSuccess) return set_err(STS_EDEVICE, "no such device");
+    const size_t xb = (((size_t)total * 4 + 255) & ~(size_t)255), lb = (((size_t)B * 4 + 255) & ~(size_t)255);
+    const size_t pb = (((size_t)total * 2 + 255) & ~(size_t)255), sb = (((size_t)B * 16 + 255) & ~(size_t)255);
+    char* d = nullptr;
+    if (hipMalloc((void**)&d, 2 * xb + lb + pb + sb + 256) != hipSuccess) return set_err(STS_EDEVICE, "out of device memory");
+    hipStream_t st = nullptr;
+    bool ok = hipStreamCreate(&st) == hipSuccess;
+    LimArgs a{};
+    a.x = (const float*)d; a.len = (const int*)(d + xb); a.ilen = 0; a.scale = 1; a.P = 1; a.Q = 1;
+    a.H = dsg.H; a.c = dsg.c; a.G = dsg.G; a.gloud = nullptr;
+    a.y = y ? (float*)(d + xb + lb) : nullptr;
+    a.pcm = pcm ? (int16_t*)(d + 2 * xb + lb) : nullptr;
+    a.stat = (unsigned*)(d + 2 * xb + lb + pb);
+    std::vector<unsigned> raw((size_t)B * 4);
+    ok = ok && (total == 0 || hipMemcpyAsync(d, x, (size_t)total * 4, hipMemcpyHostToDevice, st) == hipSuccess) &&
+         hipMemcpyAsync(d + xb, len.data(), (size_t)B * 4, hipMemcpyHostToDevice, st) == hipSuccess;
+    if (ok) {
+        limiter_run(a, B, maxl, st);
+        ok = hipGetLastError() == hipSuccess &&
+             (!y || total == 0 || hipMemcpyAsync(y, a.y, (size_t)total * 4, hipMemcpyDeviceToHost, st) == hipSuccess) &&
+             (!pcm || total == 0 || hipMemcpyAsync(pcm, a.pcm, (size_t)total * 2, hipMemcpyDeviceToHost, st) == hipSuccess) &&
+             hipMemcpyAsync(raw.data(), a.stat, (size_t)B * 16, hipMemcpyDeviceToHost, st) == hipSuccess &&
+             hipStreamSynchronize(st) == hipSuccess;
+    }
+    if (st) (void)hipStreamDestroy(st);
+    (void)hipFree(d);
+    if (!ok) return set_err(STS_EDEVICE, "the limiter failed on the device");
+    if (stats) limiter_stats_decode(raw.data(), B, stats);
+    return STS_OK;
+}
 int sts_build_flags(void) {
 #ifdef STS_EXPERIMENTS
     return 1;

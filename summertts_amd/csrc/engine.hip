@@ -33,6 +33,7 @@ Engine::~Engine() {
     if (pinned_pcm_) (void)hipHostFree(pinned_pcm_);
     if (d_rs_table) (void)hipFree(d_rs_table);
     if (loud_host_) (void)hipHostFree(loud_host_);
+    if (lim_host_) (void)hipHostFree(lim_host_);
     if (ovf_host_) (void)hipHostFree(ovf_host_);
     if (hmap_) (void)hipHostFree(hmap_);
     if (arrive_) (void)hipFree(arrive_);
@@ -374,9 +375,26 @@ int Engine::set_loudness(int mode, float target, float peak) {
     loud_mode = mode; loud_target = target; loud_peak = peak;
     return STS_OK;
 }
+// sts_set_limiter: persists; an invalid argument changes nothing
+int Engine::set_limiter(int mode, float gain_db, float ceiling_dbfs, float lookahead_ms) {
+    if (!limiter_args_valid(mode, gain_db, ceiling_dbfs, lookahead_ms))
+        return fail(STS_EINVAL, "limiter: mode 0 (off) or 1 (on), gain in [-40, 40] dB, ceiling in [-30, 0] dBFS, look-ahead in [0.25, 10] ms");
+    lim_mode = mode; lim_gain_db = gain_db; lim_ceiling = ceiling_dbfs; lim_ms = lookahead_ms;
+    return STS_OK;
+}
 int Engine::stream_halo() const {
     const int h = decoder_halo_frames(model);
-    return resampling() ? h + (rs.K + model.hop_total - 1) / model.hop_total : h;
+    // the limiter reads the float signal 2H output samples beyond a chunk's edges: 2H Q / P native samples (+ 1 for the rounding of the
+    // chunk's first output position), on top of the resampler's K
+    long long extra = resampling() ? rs.K : 0;
+    if (lim_mode != 0) {
+        LimiterDesign d;
+        if (limiter_design(out_rate, lim_gain_db, lim_ceiling, lim_ms, &d)) {
+            const long long P = resampling() ? rs.P : 1, Q = resampling() ? rs.Q : 1;
+            extra += (2LL * d.H * Q + P - 1) / P + 1;
+        }
+    }
+    return h + (int)((extra + model.hop_total - 1) / model.hop_total);
 }
 
 int decoder_halo_frames(const Model& M) {
@@ -412,6 +430,8 @@ struct BufF {
     int16_t* pcm_nat; float* wave_out;   // at a non-native output rate: the decoder tail's own int16 samples (not returned), the resampled float wave (taps)
     // loudness: where the resampler's int16 samples go (scratch when normalising, else pcm), the loudness kernels' workspace (or null)
     int16_t* pcm_rs; char* lws;
+    // limiter: its raw result words [B][4], its float output (taps only)
+    char* limws; float* wave_lim;
     // batched streaming only (null otherwise): the step tables (stream_tab_bytes), the packed chunk buffer of a native-rate step, the
     // per-window speaker vectors and decoder conditioning of a multi-speaker HiFi-GAN decoder
     char* stab; int16_t* spack; float *gwin, *cond_win;
@@ -419,7 +439,9 @@ struct BufF {
 // Batched streaming, the tables of one step with nw windows (one upload, c.d_win points at them): ints [zoff nw | coff nw | wlen nw | sid nw |
 // pack source nw | packed destination nw + 1], then from an 8-byte boundary the resampler's long long [nw][5] = {u0, L_utt, j0, j1, obase}
 static inline size_t stream_tab_ll_off(int nw) { return ((size_t)(6 * nw + 1) * 4 + 7) & ~(size_t)7; }
-static inline size_t stream_tab_bytes(int nw) { return stream_tab_ll_off(nw) + (size_t)nw * 5 * 8; }
+// and behind them the limiter's segments, long long [nw][7] = {xbase, u0, xlen, N, j0, j1, dst} (LimArgs::wtab)
+static inline size_t stream_tab_lim_off(int nw) { return stream_tab_ll_off(nw) + (size_t)nw * 5 * 8; }
+static inline size_t stream_tab_bytes(int nw) { return stream_tab_lim_off(nw) + (size_t)nw * 7 * 8; }
 
 // Everything a run's stages share: batch geometry, workspace pointers, host / device tables.  Engine::run() fills it stage by
 // stage; the stage functions below see its fields under the names the pipeline has always used (RUN_ALIASES).
@@ -952,7 +974,8 @@ int Engine::run_frame_workspace(RunCtx& c) {
     }
     c.use_ff = use_ff; c.ffG = use_ff ? M.cp[0].ff.G : 0;
     BufF& bf = c.bf;
-    const bool loud = loud_mode != 0 && !ss, norm = loud && loud_mode == 2;
+    const bool loud = loud_mode != 0 && !ss, lim = lim_mode != 0;      // (a streaming call limits chunk by chunk: the same buffers per window)
+    const bool norm = (loud && loud_mode == 2) || lim;        // the gain cast or the limiter writes the PCM
     auto layoutF = [&](Arena& A) {
         A.used = 0;
         for (int q = 0; q < 2; q++) {
@@ -971,13 +994,15 @@ int Engine::run_frame_workspace(RunCtx& c) {
             bf.tailC = A.get<float>((size_t)4 * Wcap * upS * 4);
         } else { bf.tailA = bf.tailB = bf.tailC = nullptr; }
         // (loudness: the tail always writes the float wave, the resampler its float output; normalising, their int16 samples go to
-        // scratch and the gain cast writes bf.pcm)
-        bf.wave = A.get<float>(record_taps || resampling() || loud ? (size_t)Wcap * hop : 1);
+        // scratch and the gain cast writes bf.pcm; the limiter likewise)
+        bf.wave = A.get<float>(record_taps || resampling() || loud || lim ? (size_t)Wcap * hop : 1);
         bf.pcm = A.get<int16_t>((size_t)c.Ocap);
         bf.pcm_nat = resampling() || norm ? A.get<int16_t>((size_t)Wcap * hop) : bf.pcm;
-        bf.wave_out = (record_taps || loud) && resampling() ? A.get<float>((size_t)c.Ocap) : nullptr;
+        bf.wave_out = (record_taps || loud || lim) && resampling() ? A.get<float>((size_t)c.Ocap) : nullptr;
         bf.pcm_rs = norm && resampling() ? A.get<int16_t>((size_t)c.Ocap) : bf.pcm;
         bf.lws = loud ? A.get<char>(loud_ws_bytes(B, c.Ocap)) : nullptr;
+        bf.limws = lim && !ss ? A.get<char>((size_t)B * 16) : nullptr;
+        bf.wave_lim = lim && !ss && record_taps ? A.get<float>((size_t)c.Ocap) : nullptr;
         bf.stab = nullptr; bf.spack = nullptr; bf.gwin = bf.cond_win = nullptr;
         if (c.bstream) {
             bf.stab = A.get<char>(stream_tab_bytes(B));
@@ -986,6 +1011,7 @@ int Engine::run_frame_workspace(RunCtx& c) {
         }
     };
     c.Ocap = resampling() ? out_count((long long)Wcap * hop) + B : (long long)Wcap * hop;
+    if (ss && lim && resampling()) c.Ocap += B;       // (a window's widened output range is rounded per window)
     arenaF_.measuring = true; layoutF(arenaF_);
     if (!ensure(arenaF_, arenaF_.used + 4096)) return fail(STS_EDEVICE, "out of device memory (frame-level workspace)");
     arenaF_.measuring = false; layoutF(arenaF_);
@@ -1006,9 +1032,16 @@ int Engine::run_frame_workspace(RunCtx& c) {
         if (hipHostGetDevicePointer((void**)&loud_dev_, loud_host_, 0) != hipSuccess) { (void)hipHostFree(loud_host_); loud_host_ = nullptr; return fail(STS_EDEVICE, "mapped pinned buffer has no device address"); }
         loud_cap_ = B;
     }
+    if (lim && !ss && lim_cap_ < B) {        // pinned room for the limiter's result words: downloaded behind its launch, the run's last synchronisation covers them
+        if (lim_host_) { (void)hipStreamSynchronize(stream); (void)hipHostFree(lim_host_); }
+        lim_host_ = nullptr; lim_cap_ = 0;
+        if (hipHostMalloc((void**)&lim_host_, (size_t)B * 16, hipHostMallocDefault) != hipSuccess) { lim_host_ = nullptr; return fail(STS_EDEVICE, "pinned host allocation failed"); }
+        lim_cap_ = B;
+    }
     if (poison) {           // the host-visible outputs of this call, before the first kernel that writes them is enqueued
         if (host_pcm && !ss && pinned_pcm_) poison_host16(pinned_pcm_, std::min<size_t>((size_t)c.Ocap, pinned_pcm_cap_ / 2));
         if (loud && loud_host_) poison_host32(loud_host_, (size_t)B * sizeof(sts_loudness) / 4);
+        if (lim && !ss && lim_host_) poison_host32(lim_host_, (size_t)B * 4);
     }
 
     Lvl& lv1 = c.lv1; lv1 = Lvl(); lv1.seg = (inl && !c.ahead) ? SegView{nullptr, nullptr, 1, 0, 0, p_lenF[0]} : SegView{d_offF, d_lenF, 1, 0, 0, 0};
@@ -1448,7 +1481,7 @@ int Engine::run_decode(RunCtx& c, int nw, long Wtot, int maxW, int zoff0, int wl
     // ---------------- decoder tail
     // (at a non-native output rate the tail always writes the float wave, and its int16 samples go to a scratch buffer: the resampler below
     // produces the PCM from the wave)
-    float* wave = record_taps || resampling() || (loud_mode != 0 && !ss) ? bf.wave : nullptr;
+    float* wave = record_taps || resampling() || lim_mode != 0 || (loud_mode != 0 && !ss) ? bf.wave : nullptr;
     int16_t* const pcm = bf.pcm_nat;
     const long Ntot = Wtot * hop;
     if (M.dec_type == 0) {          // Generator_hifigan.cpp:177-179 + SynthesizerTrn.cpp:389-396
@@ -1498,6 +1531,7 @@ int Engine::decode_end(RunCtx& c, const float* wave, int nw, long Wtot, int maxW
         a.pcm = c.bf.pcm_rs; a.wave_out = c.bf.wave_out;
         resample_pcm(a, nw, out_count((long long)maxW * hop), stream);
     }
+    const float* gloud = nullptr;
     if (loud_mode != 0 && !c.ss) {
         // loudness of every window (= utterance) of the float signal at the output rate; normalising, the gain cast writes the PCM
         if (loud_k_rate_ != out_rate) {
@@ -1512,7 +1546,23 @@ int Engine::decode_end(RunCtx& c, const float* wave, int nw, long Wtot, int maxW
         a.target = loud_target; a.ceiling = loud_peak; a.k = loud_k_;
         loud_ws_carve(a, c.bf.lws, nw, c.Ocap);
         a.out = loud_dev_;
-        loudness_run(a, nw, out_count((long long)maxW * hop), loud_mode == 2 ? c.bf.pcm : nullptr, stream);
+        a.no_clamp = lim_mode != 0;
+        loudness_run(a, nw, out_count((long long)maxW * hop), loud_mode == 2 && lim_mode == 0 ? c.bf.pcm : nullptr, stream);
+        if (loud_mode == 2) gloud = a.gain;
+    }
+    if (lim_mode != 0 && !c.ss) {
+        // the limiter on the same signal (times the loudness gain when normalising); it writes the PCM in place of the gain cast
+        LimiterDesign d;
+        if (!limiter_design(out_rate, lim_gain_db, lim_ceiling, lim_ms, &d)) return fail(STS_EINVAL, "limiter: output rate outside [8000, 48000]");
+        LimArgs a{};
+        a.x = resampling() ? c.bf.wave_out : wave;
+        const bool winl = nw == 1 && !c.no_inline_seg && wlen0 >= 0;
+        a.len = winl ? nullptr : c.d_win + 2 * nw; a.ilen = winl ? wlen0 : 0; a.scale = hop;
+        a.P = resampling() ? rs.P : 1; a.Q = resampling() ? rs.Q : 1;
+        a.H = d.H; a.c = d.c; a.G = d.G; a.gloud = gloud;
+        a.y = c.bf.wave_lim; a.pcm = c.bf.pcm; a.stat = (unsigned*)c.bf.limws;
+        limiter_run(a, nw, out_count((long long)maxW * hop), stream);
+        HIPCK(hipMemcpyAsync(lim_host_, c.bf.limws, (size_t)nw * 16, hipMemcpyDeviceToHost, stream));
     }
     mark(4);
     if (wave && record_taps) {
@@ -1522,6 +1572,12 @@ int Engine::decode_end(RunCtx& c, const float* wave, int nw, long Wtot, int maxW
             if (wlen0 >= 0) n = out_count((long long)wlen0 * hop);
             else for (int b = 0; b < c.B; b++) n += out_count((long long)c.p_lenF[b] * hop);
             tap("wave_out", c.bf.wave_out, 1, (long)c.Ocap, (long)n);
+        }
+        if (c.bf.wave_lim && !c.ss) {
+            long long n = 0;
+            if (wlen0 >= 0) n = out_count((long long)wlen0 * hop);
+            else for (int b = 0; b < c.B; b++) n += out_count((long long)c.p_lenF[b] * hop);
+            tap("wave_lim", c.bf.wave_lim, 1, (long)c.Ocap, (long)n);
         }
     }
     return STS_OK;
@@ -1588,7 +1644,7 @@ int Engine::run_once(int B, const int32_t* const* ids, const int32_t* n, const i
     for (double& f : bytes_w_) f = 0;
     mfma_flops_ = 0; mfma_exec_ = 0; bf16_exec_ = 0; mfma_launches_ = 0; in_mfma_region_ = false;
 
-    loud_res.clear();
+    loud_res.clear(); lim_res.clear();
     if (ss && loud_mode != 0)
         return fail(STS_EINVAL, "streaming is not available while loudness measurement or normalization is on (sts_set_loudness mode 0 first): "
                                 "normalizing needs the whole utterance before its first sample leaves");
@@ -1673,6 +1729,7 @@ int Engine::run_output(RunCtx& c) {
         }
         HIPCK(hipGetLastError());
         if (loud_mode != 0) loud_res.assign((const sts_loudness*)loud_host_, (const sts_loudness*)loud_host_ + B);   // (behind the run's last synchronisation)
+        if (lim_mode != 0) { lim_res.resize(B); limiter_stats_decode(lim_host_, B, lim_res.data()); }
     } else if (c.bstream) {
         const int rc = run_stream_steps(c);
         if (rc != STS_OK) return rc;
@@ -1691,6 +1748,11 @@ int Engine::run_output(RunCtx& c) {
         poison_host16(hp, (size_t)out_count((long long)ss->chunk_frames * hop) + 1);
         int* pw = pm + 5 * B + 2;
         d_pcm = nullptr; total_samples = 0;
+        // limiter: chunk [j0, j1) is limited from the float signal over [j0 - 2H, j1 + 2H) clipped to the utterance (stream_halo covers it)
+        const bool slim = lim_mode != 0;
+        LimiterDesign ld;
+        if (slim && !limiter_design(out_rate, lim_gain_db, lim_ceiling, lim_ms, &ld)) return fail(STS_EINVAL, "limiter: output rate outside [8000, 48000]");
+        const long long Nout = out_count((long long)F * hop);
         for (long f0 = 0; f0 < F; f0 += ss->chunk_frames) {
             const long f1 = std::min<long>(F, f0 + ss->chunk_frames);
             const long w0 = std::max<long>(0, f0 - halo), w1 = std::min<long>(F, f1 + halo);
@@ -1702,15 +1764,26 @@ int Engine::run_output(RunCtx& c) {
             // resampled from the window (the halo covers the filter's K samples beyond the chunk's edges too: stream_halo)
             const long long j0 = out_count((long long)f0 * hop), j1 = out_count((long long)f1 * hop);
             const long ns = (long)(j1 - j0);
+            const long long jl0 = slim ? std::max<long long>(0, j0 - 2 * ld.H) : j0, jl1 = slim ? std::min<long long>(Nout, j1 + 2 * ld.H) : j1;
             if (resampling()) {
                 ResampleArgs a{};
                 a.x = bf.wave; a.seg = SegView{nullptr, nullptr, hop, 0, 0, (int)(w1 - w0)};
                 a.table = d_rs_table; a.P = rs.P; a.Q = rs.Q; a.K = rs.K;
-                a.pcm = bf.pcm; a.wave_out = nullptr;
-                a.stream = 1; a.u0 = (long long)w0 * hop; a.L_utt = (long long)F * hop; a.j0 = j0; a.j1 = j1;
-                resample_pcm(a, 1, j1 - j0, stream);
+                a.pcm = slim ? bf.pcm_rs : bf.pcm; a.wave_out = slim ? bf.wave_out : nullptr;
+                a.stream = 1; a.u0 = (long long)w0 * hop; a.L_utt = (long long)F * hop; a.j0 = jl0; a.j1 = jl1;
+                resample_pcm(a, 1, jl1 - jl0, stream);
             }
-            HIPCK(hipMemcpyAsync(hp, resampling() ? bf.pcm : bf.pcm + (f0 - w0) * hop, (size_t)ns * 2, hipMemcpyDeviceToHost, stream));
+            if (slim) {
+                LimArgs a{};
+                a.x = resampling() ? bf.wave_out : bf.wave;
+                a.H = ld.H; a.c = ld.c; a.G = ld.G;
+                a.pcm = bf.pcm;
+                a.use_seg1 = 1;
+                const long long sg[7] = {0, resampling() ? jl0 : (long long)w0 * hop, resampling() ? jl1 - jl0 : (long long)(w1 - w0) * hop, Nout, j0, j1, 0};
+                for (int i = 0; i < 7; i++) a.seg1[i] = sg[i];
+                limiter_run(a, 1, j1 - j0, stream);
+            }
+            HIPCK(hipMemcpyAsync(hp, resampling() || slim ? bf.pcm : bf.pcm + (f0 - w0) * hop, (size_t)ns * 2, hipMemcpyDeviceToHost, stream));
             HIPCK(hipStreamSynchronize(stream));
             if (conv_math == 3 && ovf_host_ && *(volatile unsigned*)ovf_host_ != 0u) {
                 if (f0 == 0) return kRetrySplitBf16;          // nothing has left yet (run() repeats the call)
@@ -1793,6 +1866,9 @@ int Engine::run_stream_steps(RunCtx& c) {
     if (ss->delivered) for (int b = 0; b < B; b++) ss->delivered[b] = 0;
     d_pcm = nullptr; total_samples = 0;
     std::vector<int> wb; std::vector<long long> wj0, wn, wdst;
+    const bool slim = lim_mode != 0;
+    LimiterDesign ld;
+    if (slim && !limiter_design(out_rate, lim_gain_db, lim_ceiling, lim_ms, &ld)) return fail(STS_EINVAL, "limiter: output rate outside [8000, 48000]");
     for (long k = 0;; k++) {
         const long f0 = k * Cf;
         wb.clear();
@@ -1801,8 +1877,10 @@ int Engine::run_stream_steps(RunCtx& c) {
         if (nw == 0) break;
         int* ti = (int*)ht;
         long long* tl = (long long*)(ht + stream_tab_ll_off(nw));
+        long long* tm = (long long*)(ht + stream_tab_lim_off(nw));
+        long long rsum = 0;                                 // limiter: the resampler's float outputs of the widened ranges, packed
         wj0.assign(nw, 0); wn.assign(nw, 0); wdst.assign(nw, 0);
-        long Wtot = 0; int maxW = 0; long long dsum = 0, max_out = 0;
+        long Wtot = 0; int maxW = 0; long long dsum = 0, max_out = 0, max_rs = 0;
         for (int i = 0; i < nw; i++) {
             const int b = wb[i];
             const long F = lenF[b], f1 = std::min<long>(F, f0 + Cf);
@@ -1810,7 +1888,13 @@ int Engine::run_stream_steps(RunCtx& c) {
             const long long j0 = out_count((long long)f0 * hop), j1 = out_count((long long)f1 * hop);
             ti[i] = offF[b] + (int)w0; ti[nw + i] = (int)Wtot; ti[2 * nw + i] = (int)(w1 - w0); ti[3 * nw + i] = sidv[b];
             ti[4 * nw + i] = (int)((Wtot + (f0 - w0)) * hop); ti[5 * nw + i] = (int)dsum;
-            tl[5 * i] = (long long)w0 * hop; tl[5 * i + 1] = (long long)F * hop; tl[5 * i + 2] = j0; tl[5 * i + 3] = j1; tl[5 * i + 4] = dsum;
+            const long long Nout = out_count((long long)F * hop);
+            const long long jl0 = slim ? std::max<long long>(0, j0 - 2 * ld.H) : j0, jl1 = slim ? std::min<long long>(Nout, j1 + 2 * ld.H) : j1;
+            tl[5 * i] = (long long)w0 * hop; tl[5 * i + 1] = (long long)F * hop; tl[5 * i + 2] = jl0; tl[5 * i + 3] = jl1; tl[5 * i + 4] = slim ? rsum : dsum;
+            tm[7 * i] = resampling() ? rsum : (long long)Wtot * hop; tm[7 * i + 1] = resampling() ? jl0 : (long long)w0 * hop;
+            tm[7 * i + 2] = resampling() ? jl1 - jl0 : (long long)(w1 - w0) * hop; tm[7 * i + 3] = Nout;
+            tm[7 * i + 4] = j0; tm[7 * i + 5] = j1; tm[7 * i + 6] = dsum;
+            rsum += jl1 - jl0; max_rs = std::max(max_rs, jl1 - jl0);
             wj0[i] = j0; wn[i] = j1 - j0; wdst[i] = dsum;
             dsum += j1 - j0; max_out = std::max(max_out, j1 - j0);
             Wtot += w1 - w0; maxW = std::max<int>(maxW, (int)(w1 - w0));
@@ -1823,11 +1907,19 @@ int Engine::run_stream_steps(RunCtx& c) {
             ResampleArgs a{};
             a.x = bf.wave; a.seg = SegView{c.d_win + nw, c.d_win + 2 * nw, hop, 0, 0, 0};
             a.table = d_rs_table; a.P = rs.P; a.Q = rs.Q; a.K = rs.K;
-            a.pcm = dst; a.wave_out = nullptr;
+            a.pcm = slim ? bf.pcm_rs : dst; a.wave_out = slim ? bf.wave_out : nullptr;
             a.stream = 2; a.wtab = (const long long*)(bf.stab + stream_tab_ll_off(nw));
-            resample_pcm(a, nw, max_out, stream);
-        } else {
+            resample_pcm(a, nw, max_rs, stream);
+        } else if (!slim) {
             stream_pack(bf.pcm, dst, c.d_win + 4 * nw, c.d_win + 5 * nw, nw, max_out, stream);
+        }
+        if (slim) {          // every window of the step in one launch; it writes the packed chunks in place of the resampler / the pack
+            LimArgs a{};
+            a.x = resampling() ? bf.wave_out : bf.wave;
+            a.H = ld.H; a.c = ld.c; a.G = ld.G;
+            a.pcm = dst;
+            a.wtab = (const long long*)(bf.stab + stream_tab_lim_off(nw));
+            limiter_run(a, nw, max_out, stream);
         }
         if (!stream_direct) HIPCK(hipMemcpyAsync(hp, dst, (size_t)dsum * 2, hipMemcpyDeviceToHost, stream));
         HIPCK(hipStreamSynchronize(stream));

@@ -60,6 +60,8 @@ inline bool noise_scale_valid(float s) { return s >= 0.f && s <= 3.0e38f; }   //
 inline bool loudness_args_valid(int mode, float target, float peak) {
     return mode >= 0 && mode <= 2 && target >= -70.f && target <= 0.f && peak >= -30.f && peak <= 0.f;
 }
+// sts_limiter_stats of B utterances from the limiter kernel's raw words [B][4] (limiter.hip)
+void limiter_stats_decode(const unsigned* raw, int B, sts_limiter_stats* out);
 
 struct Tap { std::vector<float> data; int channels = 0; long length = 0; };
 constexpr int kNativeRate = 16000;   // every model of the reference produces 16 kHz (test/main.cpp:13,16)
@@ -113,6 +115,12 @@ public:
     int loud_mode = 0; float loud_target = -16.f, loud_peak = -1.f;
     std::vector<sts_loudness> loud_res;
     int set_loudness(int mode, float target, float peak);
+    // look-ahead peak limiter (sts_set_limiter, limiter.hip): 0 off (nothing extra runs), 1 every utterance of a whole-utterance call is
+    // scaled by G (times its loudness gain under loudness mode 2, which then drops its peak clamp) and held under the ceiling; the limiter
+    // writes the PCM.  lim_res: the last call's results, one per utterance (empty after a call with it off, a streaming call or a failure)
+    int lim_mode = 0; float lim_gain_db = 0.f, lim_ceiling = -1.f, lim_ms = 5.f;
+    std::vector<sts_limiter_stats> lim_res;
+    int set_limiter(int mode, float gain_db, float ceiling_dbfs, float lookahead_ms);
     std::vector<int32_t> forced_dur; bool have_forced = false;
     bool record_taps = false; int profiling = 0;       // profiling: 0 off, 1 all stage events, 2 the matrix-core region's two events only (sts_set_profiling)
     int conv_mode = 0;
@@ -194,6 +202,7 @@ private:
     unsigned* arrive_ = nullptr; int seq_ = 0;
     float* loud_host_ = nullptr; float* loud_dev_ = nullptr; int loud_cap_ = 0;   // host-mapped sts_loudness[loud_cap_]: the gating kernel's results
     LoudCoef loud_k_{}; int loud_k_rate_ = 0;                                     // the kernels' filter tables for loud_k_rate_
+    unsigned* lim_host_ = nullptr; int lim_cap_ = 0;                              // pinned: the limiter's raw result words [lim_cap_][4], downloaded behind its launch
     hipEvent_t ev_[8] = {};
     static constexpr int kAux = 3;            // ResBlock chains of one decoder stage run concurrently
     hipStream_t aux_[kAux] = {};

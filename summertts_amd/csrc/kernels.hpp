@@ -373,11 +373,35 @@ struct LoudArgs {
     LoudCoef k;
     long long* utab; double* E; double* tsum; float* tpeak; float* gain;   // workspace (loud_ws_carve)
     float* out;                          // [B] sts_loudness {lufs, peak, gain, blocks} or null
+    int no_clamp;                        // the limiter holds the ceiling: g = g_L (step 5 without its peak clamp)
 };
 // workspace of B utterances of total_samples samples in all (the frame-level arena's dry run sizes it)
 size_t loud_ws_bytes(int B, long long total_samples);
 void loud_ws_carve(LoudArgs& a, void* ws, int B, long long total_samples);
 // 3 launches (4 with pcm: the gain cast pcm = pcm_cast(x g) into pcm, packed like x); max_len = the longest utterance's sample count or more
 void loudness_run(const LoudArgs& a, int B, long long max_len, int16_t* pcm, hipStream_t st);
+
+// Look-ahead peak limiter (limiter.hip; the definition is there and in include/summertts_hip.h sts_set_limiter)
+constexpr int kLimMinRate = 8000, kLimMaxRate = 48000, kLimMaxH = 480;
+// mode 0 or 1, gain in [-40, 40] dB, ceiling in [-30, 0] dBFS, look-ahead in [0.25, 10] ms (false for NaN)
+bool limiter_args_valid(int mode, float gain_db, float ceiling_dbfs, float lookahead_ms);
+// H = floor(ms rate / 1000 + 0.5), c = 10^(ceiling / 20), G = 10^(gain / 20), float64 (false: rate outside [8000, 48000] or a bad argument)
+struct LimiterDesign { int H = 0; double c = 1.0, G = 1.0; };
+bool limiter_design(int rate, float gain_db, float ceiling_dbfs, float lookahead_ms, LimiterDesign* d);
+struct LimArgs {
+    const float* x;                      // the float signal, utterances packed back to back (wtab: the windows of a streaming step)
+    const int* len; int ilen, scale, P, Q;   // utterance b has ceil(len[b] scale P / Q) samples (len == null: one utterance, ilen)
+    int H; double c, G;
+    const float* gloud;                  // [B] loudness gain of each utterance (loud_gate_kernel's word), or null: 1
+    float* y; int16_t* pcm;              // outputs packed like x, each optional (16-byte aligned)
+    unsigned* stat;                      // [B][4] raw words {bits of g0, bits of 1.0f - bits of min s, bits of max |y|, limited} or null
+    // streaming: segment w reads {xbase, u0, xlen, N, j0, j1, dst} from wtab[7 w ..]: x[xbase .. xbase + xlen) holds samples [u0, u0 + xlen)
+    // of an utterance of N, and outputs [j0, j1) go to y / pcm[dst ..)
+    const long long* wtab;
+    // one streaming window without a table: the same seven values by value (use_seg1 != 0, wtab null)
+    int use_seg1; long long seg1[7];
+};
+// one memset (stat) + one launch; max_out = the most outputs one utterance (segment) emits, or more
+void limiter_run(const LimArgs& a, int B, long long max_out, hipStream_t st);
 
 }  // namespace sts

@@ -309,7 +309,7 @@ __global__ __launch_bounds__(LD_THREADS) void loud_gate_kernel(LoudArgs a) {
     const long long nt = (N + LD_TILE - 1) / LD_TILE;
     for (long long t = 0; t < nt; t++) p = fmaxf(p, a.tpeak[tbase + t]);
     double g = isfinite(L) ? pow(10.0, ((double)a.target - L) / 20.0) : 1.0;
-    if (p > 0.f) g = fmin(g, pow(10.0, (double)a.ceiling / 20.0) / (double)p);
+    if (p > 0.f && !a.no_clamp) g = fmin(g, pow(10.0, (double)a.ceiling / 20.0) / (double)p);
     const float gf = (float)g;
     a.gain[b] = gf;
     if (a.out) {

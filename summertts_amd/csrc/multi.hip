@@ -396,6 +396,16 @@ int sts_multi_set_loudness(sts_multi* m, int mode, float target_lufs, float peak
     }
     return STS_OK;
 }
+int sts_multi_set_limiter(sts_multi* m, int mode, float gain_db, float ceiling_dbfs, float lookahead_ms) {
+    if (!m) return multi_err(STS_EINVAL, "null handle");
+    if (!limiter_args_valid(mode, gain_db, ceiling_dbfs, lookahead_ms))
+        return multi_err(STS_EINVAL, "limiter: mode 0 (off) or 1 (on), gain in [-40, 40] dB, ceiling in [-30, 0] dBFS, look-ahead in [0.25, 10] ms");
+    for (auto& e : m->engines) {
+        const int rc = e->set_limiter(mode, gain_db, ceiling_dbfs, lookahead_ms);
+        if (rc != STS_OK) return multi_err(rc, e->error());
+    }
+    return STS_OK;
+}
 int sts_multi_set_conv_math(sts_multi* m, int mode) {
     if (!m) return multi_err(STS_EINVAL, "null handle");
     if (mode < 0 || mode > 3) return multi_err(STS_EINVAL, "conv math must be 0..3");

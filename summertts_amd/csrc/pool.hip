@@ -273,6 +273,19 @@ int sts_pool_set_loudness(sts_pool* p, int mode, float target_lufs, float peak_d
     return STS_OK;
 }
 
+int sts_pool_set_limiter(sts_pool* p, int mode, float gain_db, float ceiling_dbfs, float lookahead_ms) {
+    if (!p) return pool_err(STS_EINVAL, "null pool");
+    if (!limiter_args_valid(mode, gain_db, ceiling_dbfs, lookahead_ms))
+        return pool_err(STS_EINVAL, "pool limiter: mode 0 (off) or 1 (on), gain in [-40, 40] dB, ceiling in [-30, 0] dBFS, look-ahead in [0.25, 10] ms");
+    std::lock_guard<std::mutex> lk(p->mu);
+    if (!p->pending.empty()) return pool_err(STS_ESTATE, "requests are outstanding: wait for them before changing the limiter setting");
+    for (auto& e : p->engines) {
+        const int rc = e->set_limiter(mode, gain_db, ceiling_dbfs, lookahead_ms);
+        if (rc != STS_OK) return pool_err(rc, e->error());
+    }
+    return STS_OK;
+}
+
 int sts_pool_stats(sts_pool* p, int64_t* batches, int64_t* requests) {
     if (!p) return pool_err(STS_EINVAL, "null pool");
     std::lock_guard<std::mutex> lk(p->mu);

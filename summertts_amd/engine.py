@@ -121,6 +121,15 @@ def load_library() -> C.CDLL:
     lib.sts_multi_set_loudness.argtypes = [C.c_void_p, C.c_int, C.c_float, C.c_float]
     lib.sts_kweight_coeffs.argtypes = [C.c_int32, C.c_void_p]
     lib.sts_loudness_measure.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_void_p]
+    lib.sts_set_limiter.argtypes = [C.c_void_p, C.c_int, C.c_float, C.c_float, C.c_float]
+    lib.sts_get_limiter_mode.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float)]
+    lib.sts_get_limiter.argtypes = [C.c_void_p, C.c_void_p, C.c_int64]
+    lib.sts_pool_set_limiter.argtypes = [C.c_void_p, C.c_int, C.c_float, C.c_float, C.c_float]
+    lib.sts_multi_set_limiter.argtypes = [C.c_void_p, C.c_int, C.c_float, C.c_float, C.c_float]
+    lib.sts_limiter_design.argtypes = [C.c_int32, C.c_float, C.c_float, C.c_float, C.POINTER(C.c_int32), C.POINTER(C.c_double),
+                                       C.POINTER(C.c_double)]
+    lib.sts_limiter_apply.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_float,
+                                      C.c_void_p, C.c_void_p, C.c_void_p]
     lib.sts_multi_set_output_rate.argtypes = [C.c_void_p, C.c_int32]
     lib.sts_infer_ids_batch_stream.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
                                                BATCH_CHUNK_CB, C.c_void_p, C.c_void_p]
@@ -150,6 +159,8 @@ EXPORTED_SYMBOLS = [
     "sts_infer_ids_batch_stream", "sts_pool_submit_stream",
     "sts_set_loudness", "sts_get_loudness_mode", "sts_get_loudness", "sts_pool_set_loudness", "sts_multi_set_loudness",
     "sts_kweight_coeffs", "sts_loudness_measure",
+    "sts_set_limiter", "sts_get_limiter_mode", "sts_get_limiter", "sts_pool_set_limiter", "sts_multi_set_limiter",
+    "sts_limiter_design", "sts_limiter_apply",
 ]
 
 LOUD_OFF, LOUD_MEASURE, LOUD_NORMALIZE = 0, 1, 2
@@ -177,6 +188,38 @@ def loudness_measure(signals, rate: int, target_lufs: float = -16.0, peak_dbfs: 
     _check(lib, lib.sts_loudness_measure(int(device), x.ctypes.data, lens.ctypes.data, len(sig), int(rate), float(target_lufs),
                                          float(peak_dbfs), out.ctypes.data))
     return out
+
+
+LIMITER_OFF, LIMITER_ON = 0, 1
+# sts_limiter_stats: gain (g0), min_gain (min s, 1.0 when untouched), peak_out (max |y|), limited (samples with s < 1 before rounding)
+LIMITER_DTYPE = np.dtype([("gain", np.float32), ("min_gain", np.float32), ("peak_out", np.float32), ("limited", np.int32)])
+
+
+def limiter_design(rate: int, gain_db: float = 0.0, ceiling_dbfs: float = -1.0, lookahead_ms: float = 5.0):
+    """The library's limiter design for ``rate`` (include/summertts_hip.h sts_limiter_design; host only, no GPU) -> (H, c, G): the half
+    window in samples, the ceiling and the make-up gain as float64."""
+    lib = load_library()
+    H, c, G = C.c_int32(), C.c_double(), C.c_double()
+    _check(lib, lib.sts_limiter_design(int(rate), float(gain_db), float(ceiling_dbfs), float(lookahead_ms), C.byref(H), C.byref(c),
+                                       C.byref(G)))
+    return H.value, c.value, G.value
+
+
+def limiter_apply(signals, rate: int, gain_db: float = 0.0, ceiling_dbfs: float = -1.0, lookahead_ms: float = 5.0, device: int = 0):
+    """The look-ahead limiter on each float signal in ``signals`` at ``rate`` on the GPU (the engine's kernel, sts_limiter_apply) ->
+    (y, pcm, stats): lists of the limited float32 signals and their int16 casts, and a structured array of LIMITER_DTYPE."""
+    lib = load_library()
+    sig = [np.ascontiguousarray(s, dtype=np.float32).ravel() for s in signals]
+    lens = np.asarray([s.size for s in sig], np.int64)
+    total = int(lens.sum())
+    x = np.concatenate(sig) if sig and total > 0 else np.zeros(1, np.float32)
+    y = np.zeros(max(total, 1), np.float32)
+    pcm = np.zeros(max(total, 1), np.int16)
+    stats = np.zeros(len(sig), LIMITER_DTYPE)
+    _check(lib, lib.sts_limiter_apply(int(device), x.ctypes.data, lens.ctypes.data, len(sig), int(rate), float(gain_db), float(ceiling_dbfs),
+                                      float(lookahead_ms), y.ctypes.data, pcm.ctypes.data, stats.ctypes.data))
+    off = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
+    return ([y[off[b]:off[b + 1]].copy() for b in range(len(sig))], [pcm[off[b]:off[b + 1]].copy() for b in range(len(sig))], stats)
 
 
 def resample_table(in_rate: int, out_rate: int):
@@ -390,6 +433,30 @@ class Synthesizer:
                 _check(self.lib, rc)
         return out
 
+    def set_limiter(self, mode: int, gain_db: float = 0.0, ceiling_dbfs: float = -1.0, lookahead_ms: float = 5.0):
+        """Look-ahead peak limiter of every later whole-utterance call (include/summertts_hip.h sts_set_limiter): LIMITER_OFF or
+        LIMITER_ON (make-up gain ``gain_db``, then no sample above ``ceiling_dbfs``; results in ``limiter()``).  Invalid arguments raise
+        and leave the setting unchanged."""
+        _check(self.lib, self.lib.sts_set_limiter(self.h, int(mode), float(gain_db), float(ceiling_dbfs), float(lookahead_ms)))
+
+    def limiter_mode(self):
+        """(mode, gain_db, ceiling_dbfs, lookahead_ms) as set by ``set_limiter``."""
+        m, g, c, l = C.c_int(), C.c_float(), C.c_float(), C.c_float()
+        _check(self.lib, self.lib.sts_get_limiter_mode(self.h, C.byref(m), C.byref(g), C.byref(c), C.byref(l)))
+        return m.value, g.value, c.value, l.value
+
+    def limiter(self) -> np.ndarray:
+        """Results of the last whole-utterance call, one per utterance in call order (LIMITER_DTYPE; empty with the limiter off)."""
+        n = self.lib.sts_get_limiter(self.h, None, 0)
+        if n < 0:
+            _check(self.lib, n)
+        out = np.zeros(n, LIMITER_DTYPE)
+        if n:
+            rc = self.lib.sts_get_limiter(self.h, out.ctypes.data, n)
+            if rc < 0:
+                _check(self.lib, rc)
+        return out
+
     def set_conv_math(self, mode):
         """Arithmetic of the decoder trunk convs: 0 / 'bf16x3' = fp32 operands as three bf16 terms on the bf16 matrix cores,
         1 / 'f32' = the exact-fp32 MFMA instruction, 3 / 'f16x2' = two fp16 terms, three products (default; a call whose
@@ -597,6 +664,12 @@ class Pool:
         if rc != 0:
             raise StsError(f"sts_pool_set_loudness: {rc}: {self.lib.sts_pool_last_error().decode()}")
 
+    def set_limiter(self, mode: int, gain_db: float = 0.0, ceiling_dbfs: float = -1.0, lookahead_ms: float = 5.0):
+        """``Synthesizer.set_limiter`` for every engine of the pool; raises while any request is outstanding (STS_ESTATE)."""
+        rc = self.lib.sts_pool_set_limiter(self.h, int(mode), float(gain_db), float(ceiling_dbfs), float(lookahead_ms))
+        if rc != 0:
+            raise StsError(f"sts_pool_set_limiter: {rc}: {self.lib.sts_pool_last_error().decode()}")
+
     def stats(self):
         b, r = C.c_int64(), C.c_int64()
         self.lib.sts_pool_stats(self.h, C.byref(b), C.byref(r))
@@ -681,6 +754,12 @@ class MultiDevice:
         rc = self.lib.sts_multi_set_loudness(self.h, int(mode), float(target_lufs), float(peak_dbfs))
         if rc != 0:
             raise StsError(f"sts_multi_set_loudness: {rc}: {self.lib.sts_multi_last_error().decode()}")
+
+    def set_limiter(self, mode: int, gain_db: float = 0.0, ceiling_dbfs: float = -1.0, lookahead_ms: float = 5.0):
+        """``Synthesizer.set_limiter`` for every device."""
+        rc = self.lib.sts_multi_set_limiter(self.h, int(mode), float(gain_db), float(ceiling_dbfs), float(lookahead_ms))
+        if rc != 0:
+            raise StsError(f"sts_multi_set_limiter: {rc}: {self.lib.sts_multi_last_error().decode()}")
 
     def set_conv_math(self, mode):
         m = {"bf16x3": 0, "f32": 1, "bf16x3_all": 2, "f16x2": 3}.get(mode, mode)
