@@ -3,8 +3,8 @@
 //   TextEncoder -> duration predictor -> [one D2H of the frame counts] -> length regulator ->
 //   reverse flow -> decoder -> int16.
 // Everything runs on the engine's own HIP stream; the only host synchronisation inside a run is the
-// data-dependent frame count F (SynthesizerTrn.cpp:376-381).
-#include "engine.hpp"
+// data-dependent frame count F (SynthesizerTrn.cpp:376-381).  The decoder stage (run_decode) lives in decoder.hip.
+#include "run_ctx.hpp"
 #include <time.h>
 #include "knobs.hpp"
 #include "../../include/tts_logger.h"
@@ -17,12 +17,6 @@
 #include <thread>
 
 namespace sts {
-
-#define HIPCK(call)                                                                           \
-    do {                                                                                      \
-        hipError_t e__ = (call);                                                              \
-        if (e__ != hipSuccess) return fail(STS_EDEVICE, std::string(#call) + ": " + hipGetErrorString(e__)); \
-    } while (0)
 
 Engine::~Engine() {
     if (stream) (void)hipStreamSynchronize(stream);
@@ -48,7 +42,6 @@ Engine::~Engine() {
 }
 
 static int default_conv_math();
-static constexpr int MAX_HALO_H2P = 64;      // conv_common.hpp MAX_HALO: the staged window of conv_h2p.hip
 // one polite spin-wait step on whatever host this is built for (the x86 builtin alone broke aarch64 / ppc64 builds)
 static inline void cpu_relax() {
 #if defined(__x86_64__) || defined(__i386__)
@@ -336,7 +329,6 @@ float* Engine::dds(const DDds& d, float* h, float* t1, float* t2, const Lvl& lv,
     return cur;
 }
 
-
 void Engine::tap(const char* name, const float* d, int channels, long ld, long length) {
     if (!record_taps) return;
     Tap& t = taps[name];
@@ -347,9 +339,6 @@ void Engine::tap(const char* name, const float* d, int channels, long ld, long l
                       (size_t)length * sizeof(float), (size_t)channels, hipMemcpyDeviceToHost);
 }
 
-
-// Frames of z (per side) that influence one output sample through the decoder: conv_pre, every upsampler,
-// the widest ResBlock chain of every stage, and the tail.  Conservative (rounded up at every level).
 // sts_set_output_rate: the filter's table is built on the host and uploaded once here, not per call.  An invalid rate changes nothing.
 int Engine::set_output_rate(int rate) {
     if (rate == 0) rate = kNativeRate;
@@ -396,96 +385,6 @@ int Engine::stream_halo() const {
     }
     return h + (int)((extra + model.hop_total - 1) / model.hop_total);
 }
-
-int decoder_halo_frames(const Model& M) {
-    double R = M.dec_type == 0 ? (M.conv_post.k - 1) / 2 : (M.conv_post.k - 1) / 2 + 12;   // tail: reflect pad, iSTFT overlap, synthesis FIR
-    const int nk = M.n_resk;
-    for (int i = M.n_up - 1; i >= 0; i--) {
-        double rb = 0;
-        for (int j = 0; j < nk; j++) {
-            const DResBlock& b = M.rb[(size_t)i * nk + j];
-            double r = 0;
-            for (size_t d = 0; d < b.c1.size(); d++) r += b.c1[d].dil * (b.c1[d].k - 1) / 2 + b.c2[d].dil * (b.c2[d].k - 1) / 2;
-            if (r > rb) rb = r;
-        }
-        R += rb;
-        const DConv& up = M.ups[i];
-        R = ceil((R + up.k) / (double)up.stride) + 1;     // through the transposed conv (kernel k, stride s)
-    }
-    R += (M.conv_pre.k - 1) / 2;
-    return (int)ceil(R) + 1;
-}
-
-struct BufT {
-    int *meta_i; float* ls; float *ns, *nsw; uint64_t* seed; int* ids; int* forced;
-    float *x, *qkv, *att, *y, *x1, *ffh, *m, *logs;
-    float *dh, *dt1, *dt2, *dc, *dhh, *dp29, *dr[4], *dlogw;
-    int *dur, *cum, *frames;
-    float *g, *cond_dp, *cond_dec, *cond_wn;
-};
-struct BufF {
-    float *z, *h, *acts, *out, *x0, *regA, *regB, *tailA, *tailB, *tailC, *wave, *fliptmp;
-    float *ff_h[2], *ff_part[2], *ff_macc[2], *ff_alt;        // one-launch-per-layer flow (wn_flow.hip): channel-minor h / partial sums / -m slices, alternate home of a z half
-    int16_t* pcm;
-    int16_t* pcm_nat; float* wave_out;   // at a non-native output rate: the decoder tail's own int16 samples (not returned), the resampled float wave (taps)
-    // loudness: where the resampler's int16 samples go (scratch when normalising, else pcm), the loudness kernels' workspace (or null)
-    int16_t* pcm_rs; char* lws;
-    // limiter: its raw result words [B][4], its float output (taps only)
-    char* limws; float* wave_lim;
-    // batched streaming only (null otherwise): the step tables (stream_tab_bytes), the packed chunk buffer of a native-rate step, the
-    // per-window speaker vectors and decoder conditioning of a multi-speaker HiFi-GAN decoder
-    char* stab; int16_t* spack; float *gwin, *cond_win;
-};
-// Batched streaming, the tables of one step with nw windows (one upload, c.d_win points at them): ints [zoff nw | coff nw | wlen nw | sid nw |
-// pack source nw | packed destination nw + 1], then from an 8-byte boundary the resampler's long long [nw][5] = {u0, L_utt, j0, j1, obase}
-static inline size_t stream_tab_ll_off(int nw) { return ((size_t)(6 * nw + 1) * 4 + 7) & ~(size_t)7; }
-// and behind them the limiter's segments, long long [nw][7] = {xbase, u0, xlen, N, j0, j1, dst} (LimArgs::wtab)
-static inline size_t stream_tab_lim_off(int nw) { return stream_tab_ll_off(nw) + (size_t)nw * 5 * 8; }
-static inline size_t stream_tab_bytes(int nw) { return stream_tab_lim_off(nw) + (size_t)nw * 7 * 8; }
-
-// Everything a run's stages share: batch geometry, workspace pointers, host / device tables.  Engine::run() fills it stage by
-// stage; the stage functions below see its fields under the names the pipeline has always used (RUN_ALIASES).
-struct Engine::RunCtx {
-    int B = 0; const int32_t* const* ids = nullptr; const int32_t* n = nullptr; const int32_t* sid = nullptr; const float* ls = nullptr;
-    const StreamSpec* ss = nullptr;
-    std::vector<int> offT, lenT; long Ttot = 0; int maxT = 0;
-    int H = 0, C = 0, FF = 0, fdp = 0, wnH = 0, wnL = 0, ffn2_slices = 1;
-    Lvl lvT, lvB, lv1;
-    BufT bt; BufF bf;
-    size_t meta_ints = 0, up_bytes = 0;
-    int *pm = nullptr, *p_offT = nullptr, *p_lenT = nullptr, *p_sid = nullptr, *p_offF = nullptr, *p_lenF = nullptr, *p_one = nullptr;
-    int *d_offT = nullptr, *d_lenT = nullptr, *d_sid = nullptr, *d_offF = nullptr, *d_lenF = nullptr, *d_one = nullptr, *d_win = nullptr;
-    bool inl = false, no_inline_seg = false, ms = false;
-    long Ftot = 0; int maxF = 0, hop = 0;
-    // One utterance (the reference's own call shape): buffers, leading dimensions and every dispatch decision use the frame CAPACITY
-    // Fld = the count rounded up to a bucket of 64 frames, so that a call which launches the flow and the decoder AHEAD of the frame count
-    // (ahead: the count is predicted, the kernels read the real one from device memory) makes exactly the dispatch decisions of a call
-    // that waited for it -- and returns bit-identical samples.  Batches: Fld == Ftot, nothing changes.
-    long Fld = 0; int maxFld = 0; bool ahead = false, ahead_b = false, mapped = false, forced = false;
-    std::vector<Engine::Noise> nz; bool any_ns = false, any_nsw = false;   // per-utterance sampling noise (engine.hpp Noise), which of the two is used
-    std::vector<unsigned long long> req_keys; std::vector<long> predF;      // launch-ahead memo: per-utterance request hashes, remembered frame counts (empty: not all known)
-    int halo = 0; long Wcap = 0; int upS = 1; long Lsb = 0; int sbC = 0;
-    long long Ocap = 0;             // PCM capacity in output samples (== Wcap * hop at the native rate)
-    bool bstream = false;           // batched streaming (ss with B > 1): decode windows are chunks of several utterances (run_stream_steps)
-    bool use_ff = false; int ffG = 0;
-};
-#define RUN_ALIASES(c)                                                                                                              \
-    [[maybe_unused]] Model& M = model;                                                                                              \
-    [[maybe_unused]] const int B = (c).B; [[maybe_unused]] const StreamSpec* const ss = (c).ss;                                     \
-    [[maybe_unused]] const long Ttot = (c).Ttot; [[maybe_unused]] const int maxT = (c).maxT;                                        \
-    [[maybe_unused]] const int H = (c).H, C = (c).C, FF = (c).FF, fdp = (c).fdp, wnH = (c).wnH, wnL = (c).wnL, ffn2_slices = (c).ffn2_slices; \
-    [[maybe_unused]] Lvl &lvT = (c).lvT, &lvB = (c).lvB, &lv1 = (c).lv1;                                                            \
-    [[maybe_unused]] BufT& bt = (c).bt; [[maybe_unused]] BufF& bf = (c).bf;                                                         \
-    [[maybe_unused]] const size_t up_bytes = (c).up_bytes;                                                                          \
-    [[maybe_unused]] int* const pm = (c).pm; [[maybe_unused]] int* const p_offF = (c).p_offF; [[maybe_unused]] int* const p_lenF = (c).p_lenF; \
-    [[maybe_unused]] int* const d_sid = (c).d_sid; [[maybe_unused]] int* const d_offF = (c).d_offF; [[maybe_unused]] int* const d_lenF = (c).d_lenF; \
-    [[maybe_unused]] int* const d_win = (c).d_win;                                                                                  \
-    [[maybe_unused]] const bool inl = (c).inl, no_inline_seg = (c).no_inline_seg, ms = (c).ms;                                      \
-    [[maybe_unused]] const long Ftot = (c).Ftot; [[maybe_unused]] const int maxF = (c).maxF, hop = (c).hop;                         \
-    [[maybe_unused]] const long Fld = (c).Fld; [[maybe_unused]] const int maxFld = (c).maxFld; [[maybe_unused]] const bool ahead = (c).ahead; \
-    [[maybe_unused]] const int halo = (c).halo; [[maybe_unused]] const long Wcap = (c).Wcap, Lsb = (c).Lsb;                         \
-    [[maybe_unused]] const int upS = (c).upS, sbC = (c).sbC;                                                                        \
-    [[maybe_unused]] const bool use_ff = (c).use_ff; [[maybe_unused]] const int ffG = (c).ffG;
 
 // ---- stage 0: batch geometry at the phoneme level, phoneme-level workspace, the one host-to-device copy of a run
 int Engine::run_setup(RunCtx& c) {
@@ -1159,428 +1058,6 @@ int Engine::run_flow(RunCtx& c) {
     return STS_OK;
 #undef Ftot
 #undef maxF
-}
-
-
-// ---- stage 5: one decode pass over `nw` windows of z
-// ---------------- decoder trunk (Generator_hifigan.cpp:139-175 and the identical loops of MS/Istft/MBB)
-// One decode pass over `nw` windows of z.  Window w covers frames [zoff[w], zoff[w] + wlen[w]) of the packed z
-// and owns the compact range starting at coff[w] in every decoder buffer.  (Normal call: the windows ARE the
-// utterances and zoff == coff == offF.)  d_win = device ints {zoff[nw], coff[nw], wlen[nw]}.
-// (zoff0 = frame offset of window 0 inside z: the by-value form of a single window)
-int Engine::run_decode(RunCtx& c, int nw, long Wtot, int maxW, int zoff0, int wlen0) {
-    RUN_ALIASES(c)
-    stage_begin(3);
-    // (wlen0: real length of a single window, by value; < 0: the windows' geometry is read from the device tables)
-    const bool winl = nw == 1 && !no_inline_seg && wlen0 >= 0;
-    auto lvF = [&](int scale, int extra) {
-        Lvl l; l.seg = winl ? SegView{nullptr, nullptr, scale, extra, 0, wlen0} : SegView{d_win + nw, d_win + 2 * nw, scale, extra, 0, 0};
-        l.nb = nw; l.max_len = maxW * scale + extra;
-        l.total = Wtot * scale + (long)nw * extra; l.ld = l.total;
-        return l;
-    };
-    Lvl lz; lz.seg = winl ? SegView{nullptr, nullptr, 1, 0, zoff0, wlen0} : SegView{d_win, d_win + 2 * nw, 1, 0, 0, 0};
-    lz.nb = nw; lz.max_len = maxW; lz.total = Fld; lz.ld = Fld;
-    const Lvl lw1 = lvF(1, 0);
-    {
-        ConvOpt op;
-        if (M.dec_type == 0 && ms && c.bstream) {
-            // batched streaming: the conditioning is indexed by window, not by utterance -- gather each window's speaker (the sid table of
-            // the step) and run dec_cond over the nw windows
-            Lvl lw; lw.seg = SegView{nullptr, nullptr, 1, 0, 0, nw}; lw.nb = 1; lw.max_len = nw; lw.total = nw; lw.ld = nw;
-            gather_speaker(M.emb_g, M.spk_num, M.gin, d_win + 3 * nw, nw, bf.gwin, stream);
-            conv(M.dec_cond, bf.gwin, lw, bf.cond_win, lw, ConvOpt()); op.ubias = bf.cond_win;
-        } else if (M.dec_type == 0 && ms) { conv(M.dec_cond, bt.g, lvB, bt.cond_dec, lvB, ConvOpt()); op.ubias = bt.cond_dec; }
-        conv(M.conv_pre, bf.z, lz, bf.x0, lw1, op);
-    }
-    const float* x = bf.x0;
-    int S = 1;
-    Lvl lx = lw1;
-    // the mean over a stage's ResBlock chains is not formed by a launch of its own: the conv that consumes it (the next upsampler, the
-    // output conv) adds the chains' outputs up while it stages its input window (ConvArgs::nsum), -4 launches / ~40 us per step
-    struct { const float* p[3] = {nullptr, nullptr, nullptr}; int n = 0; float* dst = nullptr; long count = 0; } mean;
-    auto with_mean = [&](ConvOpt& o) { if (mean.n >= 2) { o.sum1 = mean.p[1]; o.sum2 = mean.p[2]; o.nsum = mean.n; o.sum_dst = mean.dst; o.sum_n = mean.count; } };
-    static const bool no_sum_fold = exp_flag("STS_NO_SUM_FOLD");   // experiment knob
-    mark(5);
-    in_mfma_region_ = true;
-    for (int i = 0; i < M.n_up; i++) {
-        const DConv& up = M.ups[i];
-        const int S2 = S * M.up_rate[i];
-        const Lvl l2 = lvF(S2, 0);
-        const size_t ce = (size_t)up.Cout * l2.total;
-        float* reg = (i & 1) ? bf.regB : bf.regA;
-        float* bup = reg;
-        ConvOpt ou; ou.in_act = 1; ou.slope = 0.1f;
-        {   // experiment knob: per-stage kernel variant of the upsamplers, e.g. STS_UP_TILE=6--- (digit = conv mode - 2, '-' = automatic)
-            static const char* ut = exp_env("STS_UP_TILE");
-            if (ut && (int)strlen(ut) > i && ut[i] >= '0' && ut[i] <= '7') ou.tile = ut[i] - '0';
-        }
-        with_mean(ou);
-        conv(up, x, lx, bup, l2, ou);
-        mean.n = 0;
-        // The nResK ResBlock chains only meet in the final sum (Generator_hifigan.cpp:159-173;
-        // /root/reference/src/modules/ResBlock1.cpp:55-69 per chain).
-        const int nk = M.n_resk;
-        const float* outs[8];
-        const int nd0 = nk > 0 ? (int)M.rb[(size_t)i * nk].c1.size() : 0;
-        bool grouped = conv_mode == 0 && nk >= 2 && nk <= kMaxGroup;
-        for (int j = 0; j < nk && grouped; j++) grouped = (int)M.rb[(size_t)i * nk + j].c1.size() == nd0;
-        if (grouped) {   // probe with layer 0 (geometry is the same for every layer of a chain)
-            ConvGroup G; G.n = nk;
-            const double f0 = flops_[3], b0 = bytes_[3];
-            for (int j = 0; j < nk; j++) G.g[j] = conv_args(M.rb[(size_t)i * nk + j].c1[0], bup, l2, bup, l2, ConvOpt(), nullptr);
-            flops_[3] = f0; bytes_[3] = b0;
-            grouped = conv_group_eligible(G);
-        }
-        if (grouped) {
-            // Layer d of ALL chains goes out as one grouped launch: 2 * nd launches per stage instead of
-            // 2 * nd * nResK, nResK times the workgroups per launch (a batch-1 stage otherwise yields only a
-            // few hundred), and chains of different kernel size backfill each other inside the grid.
-            const float* cur[kMaxGroup];
-            for (int j = 0; j < nk; j++) cur[j] = bup;
-            // experiment knob STS_CHAIN_STREAMS=<stage mask>: the chains of the masked stages go out as per-chain launches on
-            // the prioritised auxiliary streams (heaviest chain first) instead of one grouped launch per layer
-            static const int chain_streams_env = exp_int("STS_CHAIN_STREAMS", 0);
-            const int chain_streams = chain_streams_dbg >= 0 ? chain_streams_dbg : chain_streams_env;     // (lab: sts_debug_set STS_DBG_CHAIN_STREAMS)
-            const bool per_chain = ((chain_streams >> i) & 1) && nk <= kAux;
-            int crank[kMaxGroup];
-            for (int j = 0; j < nk; j++) {
-                crank[j] = 0;
-                for (int q = 0; q < nk; q++) {
-                    const int kj = M.rb[(size_t)i * nk + j].c1[0].k, kq = M.rb[(size_t)i * nk + q].c1[0].k;
-                    if (kq < kj || (kq == kj && q < j)) crank[j]++;
-                }
-            }
-            if (per_chain) {
-                (void)hipEventRecord(ev_fork_, stream);
-                for (int k = 0; k < kAux; k++) (void)hipStreamWaitEvent(aux_[k], ev_fork_, 0);
-            }
-            static const bool no_fuse = exp_flag("STS_NO_FUSE");   // experiment knob
-            // the pre-split path (conv_h2p.hip) takes a stage only whole: between its layers the chains' tensors live in the x16 layout
-            // Measured (profiles/r06_h2p_thresholds_and_two_products.log, r06_h2p_vs_fused128_ab.log).  128 channels: the pre-split pair beats BOTH the
-            // staged grouped pair (one HiFi-GAN utterance, 1 002 tiles of 128 x 128: -1.4 % of the trunk) and the fused 128-channel layer kernel
-            // (2 ... 64 utterances: -4.6 ... -11 % of the trunk although the fused kernel keeps the intermediate on chip -- its whole-window staging and
-            // one-workgroup-per-CU residency cost more than the 8 bytes per value it saves); below ~3 tiles per CU (one MB-iSTFT utterance: 294) the
-            // entry split and the second conv's two output tensors cost more than the faster K loop returns.  256+ channels: from ~2 tiles per CU on
-            // (one HiFi-GAN utterance = 252 tiles needs the K split over two wave groups the staged kernel has).  h2p (lab): 2 = always, 3 / 4 = always for
-            // the 128-channel / the wider stages only.  (The 64-channel stage was tried on this path too: it LOSES 1 % to the fused layer kernel at 32 utterances
-            // and 4 % at one -- 4 chunks x k steps are too few to pay for an unfused pair's two epilogues; profiles/r06_h2p_c64_ab.log.)
-            const long h2p_tiles = (long)((l2.max_len + 127) / 128) * (up.Cout / 128) * l2.nb * nk;
-            const long h2p_min = up.Cout == 128 ? 768 : 512;
-            bool h2p_stage = conv_math == 3 && h2p && !per_chain && up.Cout % 128 == 0 && (double)l2.ld * 32.0 < 2.0e9 &&
-                             (h2p == 2 || (h2p == 3 && up.Cout == 128) || (h2p == 4 && up.Cout != 128) || h2p_tiles >= h2p_min);
-            for (int j = 0; j < nk && h2p_stage; j++) {
-                const DResBlock& rb = M.rb[(size_t)i * nk + j];
-                for (int d = 0; d < nd0 && h2p_stage; d++) {
-                    const DConv &c1 = rb.c1[d], &c2 = rb.c2[d];
-                    h2p_stage = c1.wh2p && c2.wh2p && c1.Cin == up.Cout && c1.Cout == up.Cout && c2.Cin == up.Cout && c2.Cout == up.Cout &&
-                                (c1.k & 1) && (c2.k & 1) && c1.dil >= 1 && c2.dil >= 1 && c1.pad == c1.dil * (c1.k - 1) / 2 && c2.pad == c2.dil * (c2.k - 1) / 2 &&
-                                c1.dil * (c1.k - 1) <= MAX_HALO_H2P && c2.dil * (c2.k - 1) <= MAX_HALO_H2P && !c1.depthwise && !c2.depthwise && !c1.transposed && !c2.transposed;
-                }
-            }
-            for (int d = 0; d < nd0; d++) {
-                // narrow stages: the whole layer (conv1 -> lrelu -> conv2 -> + x) of all chains in one launch
-                ResLayerGroup R;
-                memset(&R, 0, sizeof(R));
-                R.n = nk; R.C = up.Cout; R.ld = l2.ld; R.slope = 0.1f; R.seg = l2.seg; R.B = l2.nb; R.max_n = l2.max_len;
-                static const int fuse_maxc = exp_int("STS_FUSE_MAXC", 128);   // experiment knob
-                bool fuse = !no_fuse && R.C <= fuse_maxc;
-                static const bool bf3_nofuse = exp_flag("STS_BF3_NOFUSE");   // experiment knob
-                const bool bf3_layer = (conv_math != 1) && !bf3_nofuse;
-                // split-bf16 arithmetic: the 64/32-channel stages always run fused; the 128-channel stage (whole window = 147 KB of
-                // LDS, one 8-wave workgroup per CU) from ~8 tiles per CU on -- the trunk is power-bound at batch (docs/HISTORY.md 5d), so
-                // dropping the intermediate's HBM round trip pays (batch 8: -3 %), while a single utterance's 1 089 tiles on 256
-                // workgroup slots only tie the unfused pair
-                static const int bf3_fuse128_tiles = exp_int("STS_BF3_FUSE128_TILES", 2048);   // experiment knob
-                if (conv_math != 1) {
-                    if (bf3_nofuse || R.C > 128) fuse = false;
-                    else if (R.C > 64) fuse = fuse && (long)((l2.max_len + 117) / 118) * l2.nb * nk >= bf3_fuse128_tiles;
-                }
-                for (int j = 0; j < nk && fuse; j++) {
-                    const DResBlock& rb = M.rb[(size_t)i * nk + j];
-                    const DConv &c1 = rb.c1[d], &c2 = rb.c2[d];
-                    fuse = c1.Cin == R.C && c1.Cout == R.C && c2.Cin == R.C && c2.Cout == R.C && c1.Cin_pad == R.C &&
-                           c1.Cout_pad == R.C && c2.Cin_pad == R.C && c2.Cout_pad == R.C && !c1.depthwise && !c2.depthwise &&
-                           !c1.transposed && !c2.transposed && c2.dil == 1 && c1.pad == c1.dil * (c1.k - 1) / 2 &&
-                           c2.pad == (c2.k - 1) / 2;
-                    float *t1 = reg + (size_t)(1 + 3 * j) * ce, *pa = t1 + ce, *pb = pa + ce;
-                    float* nxt = (cur[j] == pa) ? pb : pa;
-                    R.g[j].x = cur[j]; R.g[j].y = nxt; R.g[j].w1 = c1.w; R.g[j].b1 = c1.bias; R.g[j].w2 = c2.w; R.g[j].b2 = c2.bias;
-                    R.g[j].k1 = c1.k; R.g[j].dil1 = c1.dil; R.g[j].k2 = c2.k; R.g[j].wu1 = c1.wu; R.g[j].wu2 = c2.wu;
-                    R.g[j].wb1 = c1.wb3; R.g[j].wb2 = c2.wb3p;
-                    if (conv_math == 3 && c1.wh2 && c2.wh2p) { R.g[j].wb1 = c1.wh2; R.g[j].wb2 = c2.wh2p; R.g[j].ws1 = c1.h2_scale; R.g[j].ws2 = c2.h2_scale; R.math = 1; R.ovf = ovf_; }
-                }
-                // the 128-channel variant runs 8-wave workgroups, two per CU: only worth it when the grid fills the chip twice
-                if (fuse && R.C > 64) fuse = (long)((l2.max_len + 117) / 118) * l2.nb * nk >= 512;
-                if (fuse && R.C > 64 && h2p_stage) fuse = false;       // (round 6: the pre-split pair instead of the fused 128-channel layer kernel)
-                if (fuse && resblock_layer_eligible(R)) {
-                    double fl = 0, flw = 0, f = 0;
-                    auto wino_ratio = [](int k) { int n3, n2; wino_split(k, &n3, &n2); return (4.0 * n3 + 3.0 * n2) / (2.0 * k); };
-                    for (int j = 0; j < nk; j++) {   // book FLOPs / algorithmic bytes exactly as for the two separate convs
-                        const DResBlock& rb = M.rb[(size_t)i * nk + j];
-                        ConvOpt o1; o1.in_act = 1; o1.slope = 0.1f;
-                        (void)conv_args(rb.c1[d], cur[j], l2, R.g[j].y, l2, o1, &f); fl += f; flw += f * wino_ratio(rb.c1[d].k);
-                        ConvOpt o2; o2.in_act = 1; o2.slope = 0.1f; o2.res = cur[j]; o2.epi = EPI_RESADD;
-                        (void)conv_args(rb.c2[d], cur[j], l2, R.g[j].y, l2, o2, &f); fl += f; flw += f * wino_ratio(rb.c2[d].k);
-                        cur[j] = R.g[j].y;
-                    }
-                    // both convs in the Winograd domain when the model carries the transformed weights (-31 % MFMAs);
-                    // the direct-form fused kernel otherwise
-                    static const bool no_wino = exp_flag("STS_NO_WINO");   // experiment knob
-                    const bool wino = !no_wino && resblock_wino_eligible(R);
-                    if (bf3_layer && resblock_bf3_eligible(R)) {
-                        static const int bv = exp_int("STS_BF3_LAYER_VARIANT", -1);   // experiment knob
-                        if (per_chain) {
-                            for (int j = 0; j < nk; j++) { ResLayerGroup R1 = R; R1.n = 1; R1.g[0] = R.g[j]; resblock_bf3(R1, aux_[crank[j] % kAux], bv); }
-                        } else resblock_bf3(R, stream, bv);
-                        mfma_flops_ += fl; bf16_exec_ += products() * fl; mfma_launches_ += 1;
-                        continue;
-                    }
-                    if (per_chain) {
-                        for (int j = 0; j < nk; j++) {
-                            ResLayerGroup R1 = R; R1.n = 1; R1.g[0] = R.g[j];
-                            if (wino) resblock_wino(R1, aux_[crank[j] % kAux]); else resblock_layer(R1, aux_[crank[j] % kAux]);
-                        }
-                    } else if (wino) resblock_wino(R, stream);
-                    else resblock_layer(R, stream);
-                    mfma_flops_ += fl; mfma_exec_ += wino ? flw : fl; mfma_launches_ += 1;
-                    continue;
-                }
-                // ---- round 6: the wide stages on pre-split, channel-minor activations (conv_h2p.hip).  The stage input is split once
-                // (planes P0 of lrelu(x) + the x16 copy X0 for the residual); conv1 reads planes and writes planes of lrelu(out); conv2 reads those
-                // and the x16 residual and writes the next layer's x16 + planes -- or, in the last layer, the fp32 [C][ld] tensor the next stage reads.
-                // Buffers: t1 (planes of conv1's output), pa / pb (x16 ping-pong, last layer: fp32), pn (planes of the layer output), per chain.
-                if (h2p_stage) {
-                    H2PGroup H1, H2;
-                    memset(&H1, 0, sizeof(H1)); memset(&H2, 0, sizeof(H2));
-                    H1.n = H2.n = nk; H1.seg = H2.seg = l2.seg; H1.B = H2.B = l2.nb; H1.max_n = H2.max_n = l2.max_len; H1.ovf = H2.ovf = ovf_;
-                    float* const P0 = reg + (size_t)(1 + 4 * nk) * ce; float* const X0 = P0 + ce;
-                    double fl = 0, f = 0;
-                    for (int j = 0; j < nk; j++) {
-                        const DResBlock& rb = M.rb[(size_t)i * nk + j];
-                        const DConv &c1 = rb.c1[d], &c2 = rb.c2[d];
-                        float *t1 = reg + (size_t)(1 + 3 * j) * ce, *pa = t1 + ce, *pb = pa + ce, *pn = reg + (size_t)(1 + 3 * nk + j) * ce;
-                        float* nxt = (cur[j] == pa) ? pb : pa;
-                        const bool last = d + 1 == nd0;
-                        {   // book FLOPs / algorithmic bytes exactly as for the two staged convs
-                            ConvOpt o1; o1.in_act = 1; o1.slope = 0.1f;
-                            (void)conv_args(c1, cur[j], l2, t1, l2, o1, &f); fl += f;
-                            ConvOpt o2; o2.in_act = 1; o2.slope = 0.1f; o2.res = cur[j]; o2.epi = EPI_RESADD;
-                            (void)conv_args(c2, t1, l2, nxt, l2, o2, &f); fl += f;
-                        }
-                        H2PArgs& a1 = H1.g[j];
-                        a1.xp = d == 0 ? (const void*)P0 : (const void*)pn; a1.xp_ld = l2.ld; a1.wb = c1.wh2p; a1.wscale = c1.h2_scale; a1.bias = c1.bias;
-                        a1.yp = t1; a1.yp_ld = l2.ld; a1.yp_slope = 0.1f;
-                        a1.Cin = c1.Cin; a1.Cout = c1.Cout; a1.ntap = c1.k; a1.tap_step = c1.dil; a1.tap_off = -c1.pad;
-                        H2PArgs& a2 = H2.g[j];
-                        a2.xp = t1; a2.xp_ld = l2.ld; a2.wb = c2.wh2p; a2.wscale = c2.h2_scale; a2.bias = c2.bias;
-                        a2.res16 = d == 0 ? X0 : cur[j]; a2.res_ld = l2.ld;
-                        if (last) { a2.y = nxt; a2.y_ld = l2.ld; }
-                        else { a2.y16 = nxt; a2.y16_ld = l2.ld; a2.yp = pn; a2.yp_ld = l2.ld; a2.yp_slope = 0.1f; }
-                        a2.Cin = c2.Cin; a2.Cout = c2.Cout; a2.ntap = c2.k; a2.tap_step = c2.dil; a2.tap_off = -c2.pad;
-                        cur[j] = nxt;
-                    }
-                    if (d == 0) split_planes(bup, l2.ld, up.Cout, l2.seg, l2.nb, l2.max_len, 0.1f, P0, X0, l2.ld, ovf_, stream);
-                    const int ht = h2p_tile < 0 ? -1 : (up.Cout == 128 ? (h2p_tile & 0xff) : ((h2p_tile >> 8) & 0xff));   // lab: low byte = the 128-channel stage, next = wider ones; 0xff = automatic
-                    conv_h2p_group(H1, stream, ht == 0xff ? -1 : ht);
-                    conv_h2p_group(H2, stream, ht == 0xff ? -1 : ht);
-                    mfma_flops_ += fl; bf16_exec_ += products() * fl; mfma_launches_ += 2;
-                    continue;
-                }
-                ConvGroup G1, G2; G1.n = G2.n = nk;
-                double fl1 = 0, fl2 = 0, f = 0;
-                for (int j = 0; j < nk; j++) {
-                    const DResBlock& rb = M.rb[(size_t)i * nk + j];
-                    float *t1 = reg + (size_t)(1 + 3 * j) * ce, *pa = t1 + ce, *pb = pa + ce;
-                    ConvOpt o1; o1.in_act = 1; o1.slope = 0.1f;
-                    G1.g[j] = conv_args(rb.c1[d], cur[j], l2, t1, l2, o1, &f); fl1 += f;
-                    ConvOpt o2; o2.in_act = 1; o2.slope = 0.1f; o2.res = cur[j]; o2.epi = EPI_RESADD;
-                    float* nxt = (cur[j] == pa) ? pb : pa;
-                    G2.g[j] = conv_args(rb.c2[d], t1, l2, nxt, l2, o2, &f); fl2 += f;
-                    cur[j] = nxt;
-                }
-                static const char* gt = exp_env("STS_GROUP_TILE");   // experiment knob: per-stage tile digits, e.g. "4335"
-                const int gtile = gt && (int)strlen(gt) > i ? gt[i] - '0' : -1;
-                // every layer is checked on its own: later layers have larger dilations, and a halo beyond the staged
-                // LDS window (e.g. k = 11 with dilation 7) must take the per-conv path, which falls back to conv_generic
-                if (per_chain) {
-                    for (int j = 0; j < nk; j++) {
-                        hipStream_t cs = aux_[crank[j] % kAux];
-                        for (const ConvArgs* ca : {&G1.g[j], &G2.g[j]}) {
-                            if (conv_math != 1 && conv_bf3_eligible(*ca)) conv_bf3(*ca, cs, -1);
-                            else if (conv_mfma_eligible(*ca)) conv_mfma(*ca, cs, gtile);
-                            else conv_generic(*ca, cs);
-                        }
-                    }
-                    mfma_flops_ += fl1 + fl2; if (conv_math != 1) bf16_exec_ += products() * (fl1 + fl2); else mfma_exec_ += fl1 + fl2; mfma_launches_ += 2;
-                    continue;
-                }
-                if ((conv_math != 1) && conv_bf3_group_eligible(G1) && conv_bf3_group_eligible(G2)) {
-                    static const char* bgt = exp_env("STS_BF3_GROUP_TILE");   // experiment knob: per-stage tile digits
-                    const int bt = bgt && (int)strlen(bgt) > i ? (bgt[i] >= '0' && bgt[i] <= '9' ? bgt[i] - '0' : (bgt[i] >= 'a' && bgt[i] <= 'z' ? bgt[i] - 'a' + 10 : -1)) : -1;
-                    conv_bf3_group(G1, stream, bt);
-                    conv_bf3_group(G2, stream, bt);
-                    mfma_flops_ += fl1 + fl2; bf16_exec_ += products() * (fl1 + fl2); mfma_launches_ += 2;
-                    continue;
-                }
-                if (conv_group_eligible(G1)) conv_mfma_group(G1, stream, gtile);
-                else for (int j = 0; j < nk; j++) { if (conv_mfma_eligible(G1.g[j])) conv_mfma(G1.g[j], stream, -1); else conv_generic(G1.g[j], stream); }
-                if (conv_group_eligible(G2)) conv_mfma_group(G2, stream, gtile);
-                else for (int j = 0; j < nk; j++) { if (conv_mfma_eligible(G2.g[j])) conv_mfma(G2.g[j], stream, -1); else conv_generic(G2.g[j], stream); }
-                mfma_flops_ += fl1 + fl2; mfma_exec_ += fl1 + fl2; mfma_launches_ += 2;
-            }
-            if (per_chain)
-                for (int k = 0; k < kAux; k++) { (void)hipEventRecord(ev_join_[k], aux_[k]); (void)hipStreamWaitEvent(stream, ev_join_[k], 0); }
-            for (int j = 0; j < nk; j++) outs[j] = cur[j];
-        } else {
-            // fallback: the chains run concurrently on separate HIP streams
-            const bool fork = nk > 1 && nk <= 8;
-            if (fork) {
-                (void)hipEventRecord(ev_fork_, stream);
-                for (int k = 0; k < kAux; k++) (void)hipStreamWaitEvent(aux_[k], ev_fork_, 0);
-            }
-            int rank[8];                      // rank[j] = number of chains cheaper than chain j
-            for (int j = 0; j < nk && j < 8; j++) {
-                rank[j] = 0;
-                for (int q = 0; q < nk && q < 8; q++) {
-                    const int kj = M.rb[(size_t)i * nk + j].c1[0].k, kq = M.rb[(size_t)i * nk + q].c1[0].k;
-                    if (kq < kj || (kq == kj && q < j)) rank[j]++;
-                }
-            }
-            for (int j = 0; j < nk; j++) {
-                const DResBlock& rb = M.rb[(size_t)i * nk + j];
-                float *t1 = reg + (size_t)(1 + 3 * j) * ce, *pa = t1 + ce, *pb = pa + ce;
-                if (fork) cur_ = aux_[rank[j] % kAux];
-                const float* cur = bup;
-                const int nd = (int)rb.c1.size();
-                for (int d = 0; d < nd; d++) {
-                    ConvOpt o1; o1.in_act = 1; o1.slope = 0.1f;
-                    conv(rb.c1[d], cur, l2, t1, l2, o1);
-                    ConvOpt o2; o2.in_act = 1; o2.slope = 0.1f; o2.res = cur; o2.epi = EPI_RESADD;
-                    float* nxt = (cur == pa) ? pb : pa;
-                    conv(rb.c2[d], t1, l2, nxt, l2, o2);
-                    cur = nxt;
-                }
-                outs[j] = cur;
-            }
-            if (fork) {
-                for (int j = 0; j < nk && j < kAux; j++) { (void)hipEventRecord(ev_join_[j], aux_[j]); (void)hipStreamWaitEvent(stream, ev_join_[j], 0); }
-                cur_ = stream;
-            }
-        }
-        // xs = ((rb_0 + rb_1) + ...) / nResK (Generator_hifigan.cpp:159-173): formed by the consumer while it stages its input (2 or 3
-        // chains), or -- the fallback -- by a launch that writes it over the (now dead) upsampler output
-        if (nk == 1) x = outs[0];                       // (x / 1 == x)
-        else if (nk <= 3 && !no_sum_fold) { mean.p[0] = outs[0]; mean.p[1] = outs[1]; mean.p[2] = nk > 2 ? outs[2] : nullptr; mean.n = nk; mean.dst = bup; mean.count = (long)ce; x = outs[0]; }
-        else { sum_scale(bup, outs, nk, (long)ce, stream); x = bup; }
-        S = S2; lx = l2;
-    }
-    in_mfma_region_ = false;
-    mark(6);
-
-    // ---------------- decoder tail
-    // (at a non-native output rate the tail always writes the float wave, and its int16 samples go to a scratch buffer: the resampler below
-    // produces the PCM from the wave)
-    float* wave = record_taps || resampling() || lim_mode != 0 || (loud_mode != 0 && !ss) ? bf.wave : nullptr;
-    int16_t* const pcm = bf.pcm_nat;
-    const long Ntot = Wtot * hop;
-    if (M.dec_type == 0) {          // Generator_hifigan.cpp:177-179 + SynthesizerTrn.cpp:389-396
-        ConvOpt o; o.in_act = 1; o.slope = 1e-2f; o.epi = EPI_TANH_PCM; o.pcm = pcm; o.aux = wave;
-        with_mean(o);
-        conv(M.conv_post, x, lx, nullptr, lx, o);
-    } else {                        // Generator_MBB.cpp:174-202, Generator_MS.cpp:198-228, Generator_Istft.cpp:180-197
-        const Lvl lsb = lvF(S, 1);
-        ConvOpt o; o.in_act = 1; o.slope = 1e-2f; o.reflect = 1;
-        with_mean(o);
-        conv(M.conv_post, x, lx, bf.tailA, lsb, o);
-        const int bands = M.dec_type == 2 ? 1 : 4;
-        const Lvl ltm = lvF(S * 4, 0);
-        if (tail_fused && M.dec_type != 2 && sbC == 72 && istft_tail_fused_ok(bands, M.fir_taps, M.fir_pad)) {
-            // spectrum + inverse DFT / overlap-add + synthesis filter + int16 cast in one launch (misc_kernels.hip istft_tail_fused_kernel)
-            const Lvl lo = lvF(S * 16, 0);
-            istft_tail_fused(bf.tailA, lsb.ld, lsb.seg, M.synth_fir, M.fir_taps, M.fir_pad, (float)M.subbands, M.fir_bias, wave, pcm, lo.seg, nw, ltm.max_len, stream);
-            flops_[3] += 2.0 * (double)Ntot * (16.0 * 4 + 4 * 18 * 4 / 4.0);
-            return decode_end(c, wave, nw, Wtot, maxW, wlen0);
-        }
-        istft_spectrum(bf.tailA, lsb.ld, sbC, bf.tailB, lsb.total, stream);
-        float* tm = bf.tailC;
-        istft_ola(bf.tailB, lsb.ld, bands, 18, lsb.seg, tm, ltm.ld, ltm.seg, nw, ltm.max_len, stream);
-        if (M.dec_type == 2) {
-            quantize_pcm(tm, pcm, Ntot, stream);
-            if (wave) HIPCK(hipMemcpyAsync(wave, tm, (size_t)Ntot * 4, hipMemcpyDeviceToDevice, stream));
-        } else {
-            const Lvl lo = lvF(S * 16, 0);
-            synth_fir(tm, ltm.ld, ltm.seg, M.synth_fir, M.fir_taps, M.fir_pad, (float)M.subbands, M.fir_bias /* 0 unless the blob's learned filter carries one (MS); the PQMF bank has none */, wave, pcm, lo.seg, nw,
-                      ltm.max_len, stream);
-        }
-        flops_[3] += 2.0 * (double)Ntot * (16.0 * 4 + 4 * 18 * 4 / 4.0);
-    }
-    return decode_end(c, wave, nw, Wtot, maxW, wlen0);
-}
-
-// the end of a decode: the "wave" tap; at a non-native output rate (and not streaming: run_output resamples each chunk) the resampler, which
-// writes the PCM of every window at the output rate, packed window after window
-int Engine::decode_end(RunCtx& c, const float* wave, int nw, long Wtot, int maxW, int wlen0) {
-    const int hop = c.hop;
-    if (resampling() && !c.ss) {
-        const bool winl = nw == 1 && !c.no_inline_seg && wlen0 >= 0;
-        ResampleArgs a{};
-        a.x = wave;
-        a.seg = winl ? SegView{nullptr, nullptr, hop, 0, 0, wlen0} : SegView{c.d_win + nw, c.d_win + 2 * nw, hop, 0, 0, 0};
-        a.table = d_rs_table; a.P = rs.P; a.Q = rs.Q; a.K = rs.K;
-        a.pcm = c.bf.pcm_rs; a.wave_out = c.bf.wave_out;
-        resample_pcm(a, nw, out_count((long long)maxW * hop), stream);
-    }
-    const float* gloud = nullptr;
-    if (loud_mode != 0 && !c.ss) {
-        // loudness of every window (= utterance) of the float signal at the output rate; normalising, the gain cast writes the PCM
-        if (loud_k_rate_ != out_rate) {
-            if (!loud_coef(out_rate, &loud_k_)) return fail(STS_EINVAL, "loudness: output rate outside [8000, 48000]");
-            loud_k_rate_ = out_rate;
-        }
-        LoudArgs a{};
-        a.x = resampling() ? c.bf.wave_out : wave;
-        const bool winl = nw == 1 && !c.no_inline_seg && wlen0 >= 0;
-        a.len = winl ? nullptr : c.d_win + 2 * nw; a.ilen = winl ? wlen0 : 0; a.scale = hop;
-        a.P = resampling() ? rs.P : 1; a.Q = resampling() ? rs.Q : 1;
-        a.target = loud_target; a.ceiling = loud_peak; a.k = loud_k_;
-        loud_ws_carve(a, c.bf.lws, nw, c.Ocap);
-        a.out = loud_dev_;
-        a.no_clamp = lim_mode != 0;
-        loudness_run(a, nw, out_count((long long)maxW * hop), loud_mode == 2 && lim_mode == 0 ? c.bf.pcm : nullptr, stream);
-        if (loud_mode == 2) gloud = a.gain;
-    }
-    if (lim_mode != 0 && !c.ss) {
-        // the limiter on the same signal (times the loudness gain when normalising); it writes the PCM in place of the gain cast
-        LimiterDesign d;
-        if (!limiter_design(out_rate, lim_gain_db, lim_ceiling, lim_ms, &d)) return fail(STS_EINVAL, "limiter: output rate outside [8000, 48000]");
-        LimArgs a{};
-        a.x = resampling() ? c.bf.wave_out : wave;
-        const bool winl = nw == 1 && !c.no_inline_seg && wlen0 >= 0;
-        a.len = winl ? nullptr : c.d_win + 2 * nw; a.ilen = winl ? wlen0 : 0; a.scale = hop;
-        a.P = resampling() ? rs.P : 1; a.Q = resampling() ? rs.Q : 1;
-        a.H = d.H; a.c = d.c; a.G = d.G; a.gloud = gloud;
-        a.y = c.bf.wave_lim; a.pcm = c.bf.pcm; a.stat = (unsigned*)c.bf.limws;
-        limiter_run(a, nw, out_count((long long)maxW * hop), stream);
-        HIPCK(hipMemcpyAsync(lim_host_, c.bf.limws, (size_t)nw * 16, hipMemcpyDeviceToHost, stream));
-    }
-    mark(4);
-    if (wave && record_taps) {
-        tap("wave", wave, 1, Wtot * hop, (wlen0 >= 0 ? (long)wlen0 : Wtot) * hop);
-        if (c.bf.wave_out && !c.ss) {
-            long long n = 0;
-            if (wlen0 >= 0) n = out_count((long long)wlen0 * hop);
-            else for (int b = 0; b < c.B; b++) n += out_count((long long)c.p_lenF[b] * hop);
-            tap("wave_out", c.bf.wave_out, 1, (long)c.Ocap, (long)n);
-        }
-        if (c.bf.wave_lim && !c.ss) {
-            long long n = 0;
-            if (wlen0 >= 0) n = out_count((long long)wlen0 * hop);
-            else for (int b = 0; b < c.B; b++) n += out_count((long long)c.p_lenF[b] * hop);
-            tap("wave_lim", c.bf.wave_lim, 1, (long)c.Ocap, (long)n);
-        }
-    }
-    return STS_OK;
 }
 
 // The two-term fp16 arithmetic (conv_math 3) cannot hold an activation beyond fp16's range; its kernels raise a word in

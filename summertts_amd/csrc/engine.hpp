@@ -54,7 +54,8 @@ struct StreamSpec {
     int (*bcb)(void* user, int32_t utt, const int16_t* pcm, int32_t n_samples, int32_t sample_offset) = nullptr;
     int32_t* delivered = nullptr;
 };
-int decoder_halo_frames(const Model& M);
+int decoder_halo_frames(const Model& M);   // decoder.hip
+struct WinGeom;                             // the windows of one decode pass (decoder.hip)
 inline bool noise_scale_valid(float s) { return s >= 0.f && s <= 3.0e38f; }   // (false for NaN and +inf)
 // sts_set_loudness: mode 0, 1 or 2, target in [-70, 0] LUFS, ceiling in [-30, 0] dBFS (false for NaN)
 inline bool loudness_args_valid(int mode, float target, float peak) {
@@ -176,14 +177,15 @@ private:
     struct SplineTail { const DConv* proj; float filter_sqrt; const float* r0; const float* r1; float* o0; float* o1; };
     float* dds(const DDds& d, float* h, float* t1, float* t2, const Lvl& lv, const DConv* pre = nullptr, const float* pre_in = nullptr,
                const float* pre_res = nullptr, const SplineTail* tail = nullptr, bool* tail_done = nullptr);
-    struct RunCtx;                  // what the stages of one run share (engine.hip)
+    struct RunCtx;                  // what the stages of one run share (run_ctx.hpp)
+    struct ResStage;                // the ResBlock chains of one decoder stage (decoder.hip)
     int run_setup(RunCtx& c);
     int run_text_encoder(RunCtx& c);
     int run_durations(RunCtx& c);
     int run_frame_workspace(RunCtx& c);
     int run_flow(RunCtx& c);
     int run_decode(RunCtx& c, int nw, long Wtot, int maxW, int zoff0, int wlen0);
-    int decode_end(RunCtx& c, const float* wave, int nw, long Wtot, int maxW, int wlen0);
+    int decode_end(RunCtx& c, const float* wave, const WinGeom& win, long Wtot, int maxW);
     int wait_frame_counts(RunCtx& c);
     int frame_geometry(RunCtx& c);
     int run_output(RunCtx& c);

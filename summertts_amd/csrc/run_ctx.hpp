@@ -1,0 +1,85 @@
+// run_ctx.hpp -- internal to the engine's translation units (engine.hip, decoder.hip): the workspace pointers and the context the stages
+// of one run share.
+#pragma once
+#include "engine.hpp"
+
+namespace sts {
+
+#define HIPCK(call)                                                                           \
+    do {                                                                                      \
+        hipError_t e__ = (call);                                                              \
+        if (e__ != hipSuccess) return fail(STS_EDEVICE, std::string(#call) + ": " + hipGetErrorString(e__)); \
+    } while (0)
+
+struct BufT {
+    int *meta_i; float* ls; float *ns, *nsw; uint64_t* seed; int* ids; int* forced;
+    float *x, *qkv, *att, *y, *x1, *ffh, *m, *logs;
+    float *dh, *dt1, *dt2, *dc, *dhh, *dp29, *dr[4], *dlogw;
+    int *dur, *cum, *frames;
+    float *g, *cond_dp, *cond_dec, *cond_wn;
+};
+struct BufF {
+    float *z, *h, *acts, *out, *x0, *regA, *regB, *tailA, *tailB, *tailC, *wave, *fliptmp;
+    float *ff_h[2], *ff_part[2], *ff_macc[2], *ff_alt;        // one-launch-per-layer flow (wn_flow.hip): channel-minor h / partial sums / -m slices, alternate home of a z half
+    int16_t* pcm;
+    int16_t* pcm_nat; float* wave_out;   // at a non-native output rate: the decoder tail's own int16 samples (not returned), the resampled float wave (taps)
+    // loudness: where the resampler's int16 samples go (scratch when normalising, else pcm), the loudness kernels' workspace (or null)
+    int16_t* pcm_rs; char* lws;
+    // limiter: its raw result words [B][4], its float output (taps only)
+    char* limws; float* wave_lim;
+    // batched streaming only (null otherwise): the step tables (stream_tab_bytes), the packed chunk buffer of a native-rate step, the
+    // per-window speaker vectors and decoder conditioning of a multi-speaker HiFi-GAN decoder
+    char* stab; int16_t* spack; float *gwin, *cond_win;
+};
+// Batched streaming, the tables of one step with nw windows (one upload, c.d_win points at them): ints [zoff nw | coff nw | wlen nw | sid nw |
+// pack source nw | packed destination nw + 1], then from an 8-byte boundary the resampler's long long [nw][5] = {u0, L_utt, j0, j1, obase}
+static inline size_t stream_tab_ll_off(int nw) { return ((size_t)(6 * nw + 1) * 4 + 7) & ~(size_t)7; }
+// and behind them the limiter's segments, long long [nw][7] = {xbase, u0, xlen, N, j0, j1, dst} (LimArgs::wtab)
+static inline size_t stream_tab_lim_off(int nw) { return stream_tab_ll_off(nw) + (size_t)nw * 5 * 8; }
+static inline size_t stream_tab_bytes(int nw) { return stream_tab_lim_off(nw) + (size_t)nw * 7 * 8; }
+
+// Everything a run's stages share: batch geometry, workspace pointers, host / device tables.  Engine::run() fills it stage by
+// stage; the stage functions below see its fields under the names the pipeline has always used (RUN_ALIASES).
+struct Engine::RunCtx {
+    int B = 0; const int32_t* const* ids = nullptr; const int32_t* n = nullptr; const int32_t* sid = nullptr; const float* ls = nullptr;
+    const StreamSpec* ss = nullptr;
+    std::vector<int> offT, lenT; long Ttot = 0; int maxT = 0;
+    int H = 0, C = 0, FF = 0, fdp = 0, wnH = 0, wnL = 0, ffn2_slices = 1;
+    Lvl lvT, lvB, lv1;
+    BufT bt; BufF bf;
+    size_t meta_ints = 0, up_bytes = 0;
+    int *pm = nullptr, *p_offT = nullptr, *p_lenT = nullptr, *p_sid = nullptr, *p_offF = nullptr, *p_lenF = nullptr, *p_one = nullptr;
+    int *d_offT = nullptr, *d_lenT = nullptr, *d_sid = nullptr, *d_offF = nullptr, *d_lenF = nullptr, *d_one = nullptr, *d_win = nullptr;
+    bool inl = false, no_inline_seg = false, ms = false;
+    long Ftot = 0; int maxF = 0, hop = 0;
+    // One utterance (the reference's own call shape): buffers, leading dimensions and every dispatch decision use the frame CAPACITY
+    // Fld = the count rounded up to a bucket of 64 frames, so that a call which launches the flow and the decoder AHEAD of the frame count
+    // (ahead: the count is predicted, the kernels read the real one from device memory) makes exactly the dispatch decisions of a call
+    // that waited for it -- and returns bit-identical samples.  Batches: Fld == Ftot, nothing changes.
+    long Fld = 0; int maxFld = 0; bool ahead = false, ahead_b = false, mapped = false, forced = false;
+    std::vector<Engine::Noise> nz; bool any_ns = false, any_nsw = false;   // per-utterance sampling noise (engine.hpp Noise), which of the two is used
+    std::vector<unsigned long long> req_keys; std::vector<long> predF;      // launch-ahead memo: per-utterance request hashes, remembered frame counts (empty: not all known)
+    int halo = 0; long Wcap = 0; int upS = 1; long Lsb = 0; int sbC = 0;
+    long long Ocap = 0;             // PCM capacity in output samples (== Wcap * hop at the native rate)
+    bool bstream = false;           // batched streaming (ss with B > 1): decode windows are chunks of several utterances (run_stream_steps)
+    bool use_ff = false; int ffG = 0;
+};
+#define RUN_ALIASES(c)                                                                                                              \
+    [[maybe_unused]] Model& M = model;                                                                                              \
+    [[maybe_unused]] const int B = (c).B; [[maybe_unused]] const StreamSpec* const ss = (c).ss;                                     \
+    [[maybe_unused]] const long Ttot = (c).Ttot; [[maybe_unused]] const int maxT = (c).maxT;                                        \
+    [[maybe_unused]] const int H = (c).H, C = (c).C, FF = (c).FF, fdp = (c).fdp, wnH = (c).wnH, wnL = (c).wnL, ffn2_slices = (c).ffn2_slices; \
+    [[maybe_unused]] Lvl &lvT = (c).lvT, &lvB = (c).lvB, &lv1 = (c).lv1;                                                            \
+    [[maybe_unused]] BufT& bt = (c).bt; [[maybe_unused]] BufF& bf = (c).bf;                                                         \
+    [[maybe_unused]] const size_t up_bytes = (c).up_bytes;                                                                          \
+    [[maybe_unused]] int* const pm = (c).pm; [[maybe_unused]] int* const p_offF = (c).p_offF; [[maybe_unused]] int* const p_lenF = (c).p_lenF; \
+    [[maybe_unused]] int* const d_sid = (c).d_sid; [[maybe_unused]] int* const d_offF = (c).d_offF; [[maybe_unused]] int* const d_lenF = (c).d_lenF; \
+    [[maybe_unused]] int* const d_win = (c).d_win;                                                                                  \
+    [[maybe_unused]] const bool inl = (c).inl, no_inline_seg = (c).no_inline_seg, ms = (c).ms;                                      \
+    [[maybe_unused]] const long Ftot = (c).Ftot; [[maybe_unused]] const int maxF = (c).maxF, hop = (c).hop;                         \
+    [[maybe_unused]] const long Fld = (c).Fld; [[maybe_unused]] const int maxFld = (c).maxFld; [[maybe_unused]] const bool ahead = (c).ahead; \
+    [[maybe_unused]] const int halo = (c).halo; [[maybe_unused]] const long Wcap = (c).Wcap, Lsb = (c).Lsb;                         \
+    [[maybe_unused]] const int upS = (c).upS, sbC = (c).sbC;                                                                        \
+    [[maybe_unused]] const bool use_ff = (c).use_ff; [[maybe_unused]] const int ffG = (c).ffG;
+
+}  // namespace sts
