@@ -241,9 +241,54 @@ int sts_limiter_design(int32_t rate, float gain_db, float ceiling_dbfs, float lo
  * three may be NULL. */
 int sts_limiter_apply(int device, const float* x, const int64_t* lengths, int32_t B, int32_t rate, float gain_db, float ceiling_dbfs,
                       float lookahead_ms, float* y, int16_t* pcm, sts_limiter_stats* stats);
+/* ---- duration plans (ABI 14; no reference counterpart: SynthesizerTrn::infer has one lengthScale per call).  sts_set_duration_plan(e, B, n,
+ * plans) gives utterance b of the NEXT call (n[b] phonemes) the plan plans[b]; each field may be absent:
+ *   rate [n[b]] or NULL      per-phoneme multiplier on the utterance's length_scale (SSML <prosody rate> over a span: rate = 1 / speed)
+ *   fixed [n[b]] or NULL     >= 0: exactly this many frames (a <break time> on a pause phoneme); -1: predicted
+ *   target_frames            0: none; > 0: the utterance is exactly this many frames (target_frames * samples_per_frame native samples) long
+ * The plan is copied and applies to the next run only, whatever that run's outcome (the lifetime of forced durations), in every call form:
+ * sts_infer_ids, sts_infer_ids_batch, sts_run_batch, sts_infer_ids_stream, sts_infer_ids_batch_stream.  That run must have the same B and
+ * n[b]: otherwise it answers STS_EINVAL and nothing runs.  B == 0 or plans == NULL drops a pending plan.  A plan and forced durations both
+ * pending at a run: STS_EINVAL, and both are dropped.  An utterance whose plan has all fields NULL / 0 is synthesised as without a plan, bit
+ * for bit; a call with no plan pending launches and uploads nothing new.
+ * Valid (checked at the set call; otherwise STS_EINVAL and nothing changes): rate finite and in [1/64, 64]; fixed in [-1, 100000];
+ * target_frames 0 or in [1, 2^20]; with a target, target_frames - sum fixed >= #free (free: fixed < 0 or fixed == NULL), and with no free
+ * phoneme sum fixed == target_frames.
+ * For one utterance, lw_i the "logw" tap:
+ *   1 u_i = expf(lw_i) * length_scale (fp32: the expression of a call without a plan).
+ *   2 w_i = u_i * rate_i, one fp32 multiply (rate == NULL: w_i = u_i bit for bit).  The tap "dur_w" ([1][total phonemes]; recorded when taps
+ *     are on and the run had a plan) is w.
+ *   3 No target: d_i = fixed_i if fixed_i >= 0, else the clamp of a call without a plan: min(ceilf(w_i), 100000), 0 for NaN or w_i <= 0.
+ *   4 Target F: fixed phonemes keep fixed_i.  R' = F - sum fixed - #free.  Each free phoneme gets d_i = 1 + a_i + e_i, in 64-bit integers:
+ *       k_i = (int64) floorf(fminf(w_i, 4096.f) * 1048576.f); 0 when w_i is NaN or not above 0.
+ *       K = sum k_i over the free phonemes; K == 0: every k_i = 1 and K = #free.
+ *       a_i = (R' k_i) div K, r_i = (R' k_i) mod K (products below 2^54).  L = R' - sum a_i, so 0 <= L < #free.
+ *       e_i = 1 for the L free phonemes that come first in the order (r_i descending, then i ascending), else 0.
+ *     So sum d_i == F exactly, every free phoneme is heard (d_i >= 1), |d_i - 1 - R' k_i / K| < 1, and the result is a function of the
+ *     utterance's own w only (not of its batch companions, its position, or the device).
+ * A run with a plan neither reads nor feeds the launch-ahead memo (STS_DBG_LAUNCH_AHEAD).  From milliseconds: frames = round(ms * 16 /
+ * samples_per_frame) at the model's 16 kHz. */
+typedef struct sts_dur_plan {
+    const float*   rate;          /* [n] or NULL: per-phoneme multiplier on the utterance's length_scale */
+    const int32_t* fixed;         /* [n] or NULL: >= 0 exactly this many frames, -1 = predicted */
+    int32_t        target_frames; /* 0 = none; > 0: the utterance is exactly this many frames long */
+} sts_dur_plan;
+int sts_set_duration_plan(sts_engine* e, int32_t B, const int32_t* n, const sts_dur_plan* plans);
+/* Host only (no device), like sts_resample_table: steps 3-4 above on caller weights w[n] (fixed may be NULL; target_frames 0 = step 3).
+ * STS_EINVAL for an invalid or infeasible plan (the rules above). */
+int sts_duration_fit(const float* w, const int32_t* fixed, int32_t n, int32_t target_frames, int32_t* dur_out);
+/* The same kernel on caller weights, like sts_limiter_apply: B utterances packed back to back in w (host memory), lengths[b] >= 1 weights
+ * each; fixed (packed like w) and target_frames ([B]) may be NULL.  dur_out receives the durations packed like w. */
+int sts_duration_plan_apply(int device, const float* w, const int32_t* fixed, const int32_t* lengths, int32_t B,
+                            const int32_t* target_frames, int32_t* dur_out);
+/* Phoneme start offsets of the last run in output samples, packed like sts_get_durations (same count, same capacity convention): phoneme i
+ * with f frames before it in its utterance starts at ceil(f * samples_per_frame * P / Q) at the current output rate (sts_set_output_rate; f *
+ * samples_per_frame at the native rate) -- the convention of a streaming chunk's sample_offset.  Host arithmetic; after any call form, with
+ * or without a plan. */
+int sts_get_phoneme_offsets(sts_engine* e, int64_t* start, int64_t capacity);
 /*   record intermediate tensors of the next run: "x_enc","m","logs","logw","z_p","z","wave","wave_out" ("logs": the second half of the
  *   encoder projection, computed only by runs that record taps or sample the prior; "wave_out": the resampled float wave, only at a
- *   non-native output rate, one-pass calls) */
+ *   non-native output rate, one-pass calls; "dur_w": the planned duration weights, only a run with a duration plan) */
 int sts_set_record_taps(sts_engine* e, int enable);
 /*   fetch a tap: malloc()'d copy, channel-major [channels][total_len] (== the reference's column-major
  *   MatrixXf [time, channels]); for batches the utterances are packed along time. */
@@ -331,7 +376,7 @@ int sts_set_profiling(sts_engine* e, int enable);
  * sizeof(sts_profile)) bytes, so a client compiled against an older header passes ITS sizeof and is never overrun;
  * sts_get_profile(e, p) == sts_get_profile_ex(e, p, sizeof(sts_profile)) of the header this library was built from -- use it only
  * when client and library are built together. */
-#define STS_ABI_VERSION 13
+#define STS_ABI_VERSION 14
 int sts_abi_version(void);
 /* bit 0: lab build (-DSTS_EXPERIMENTS: environment knobs of knobs.hpp, every conv tile code);
  * 0 for the shipped library */
@@ -409,6 +454,11 @@ int sts_pool_set_loudness(sts_pool* p, int mode, float target_lufs, float peak_d
 /*   sts_pool_set_limiter (ABI 13): sts_set_limiter on every engine of the pool.  STS_ESTATE while any request is outstanding, as
  *   sts_pool_set_output_rate.  Streaming requests are limited chunk by chunk. */
 int sts_pool_set_limiter(sts_pool* p, int mode, float gain_db, float ceiling_dbfs, float lookahead_ms);
+/*   sts_pool_submit_plan (ABI 14): sts_pool_submit_ex with this request's own duration plan (sts_set_duration_plan: rate and fixed hold n
+ *   entries each or are NULL, target_frames 0 = none; an invalid plan answers STS_EINVAL).  Whole-utterance requests only.  Requests with and
+ *   without a plan share one packed batch: the plan is per utterance. */
+int64_t sts_pool_submit_plan(sts_pool* p, const int32_t* ids, int32_t n, int32_t sid, float length_scale, float noise_scale,
+                             float noise_scale_w, uint64_t seed, const float* rate, const int32_t* fixed, int32_t target_frames);
 
 /* ---- multi-device batch (no reference counterpart).  One host process drives n_devices GPUs:
  * one engine (weights replicated) and one worker thread per entry of `devices` (HIP device indices; an index may repeat,
@@ -445,6 +495,10 @@ int sts_multi_set_output_rate(sts_multi* m, int32_t rate);
 int sts_multi_set_loudness(sts_multi* m, int mode, float target_lufs, float peak_dbfs);
 /*   sts_multi_set_limiter (ABI 13): sts_set_limiter on every engine of the handle. */
 int sts_multi_set_limiter(sts_multi* m, int mode, float gain_db, float ceiling_dbfs, float lookahead_ms);
+/*   sts_multi_set_duration_plan (ABI 14): sts_set_duration_plan for the NEXT sts_multi_infer_ids_batch of the handle, which must have the
+ *   same B and n[b] (otherwise STS_EINVAL and nothing runs).  plans[b] belongs to utterance b of the caller's batch and follows it into its
+ *   device's shard: the PCM does not depend on the number of devices. */
+int sts_multi_set_duration_plan(sts_multi* m, int32_t B, const int32_t* n, const sts_dur_plan* plans);
 /*   test hook: the shared library that provides the nccl* entry points (NULL / "" = librccl.so.1) and whether STS_MULTI_RCCL may list
  *   one device several times (tests/fake_rccl: N emulated ranks on one GPU; real RCCL refuses duplicates).  Only before the first
  *   STS_MULTI_RCCL handle of the process is created.  TEST-ONLY: refused with STS_ESTATE unless the process environment carries

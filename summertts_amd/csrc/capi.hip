@@ -157,6 +157,62 @@ int sts_set_forced_durations(sts_engine* e, const int32_t* dur, int64_t count) {
     return STS_OK;
 }
 
+int sts_set_duration_plan(sts_engine* e, int32_t B, const int32_t* n, const sts_dur_plan* plans) {
+    if (!e) return set_err(STS_EINVAL, "null engine");
+    const int rc = e->eng.set_duration_plan(B, n, plans);
+    return rc == STS_OK ? STS_OK : set_err(rc, e->eng.error());
+}
+int sts_get_phoneme_offsets(sts_engine* e, int64_t* start, int64_t capacity) {
+    if (!e) return set_err(STS_EINVAL, "null engine");
+    const int rc = e->eng.phoneme_offsets(start, capacity);
+    return rc == STS_OK ? STS_OK : set_err(rc, e->eng.error());
+}
+int sts_duration_fit(const float* w, const int32_t* fixed, int32_t n, int32_t target_frames, int32_t* dur_out) {
+    if (!dur_out || n < 1) return set_err(STS_EINVAL, "n >= 1 and dur_out are required");
+    const char* why = nullptr;
+    if (!dur_plan_valid(n, nullptr, fixed, target_frames, &why)) return set_err(STS_EINVAL, why);
+    if (!w) {            // (weights are read for the free phonemes only)
+        for (int i = 0; i < n; i++) if (!fixed || fixed[i] < 0) return set_err(STS_EINVAL, "null weights with a free phoneme");
+    }
+    duration_fit(w, fixed, n, target_frames, dur_out);
+    return STS_OK;
+}
+int sts_duration_plan_apply(int device, const float* w, const int32_t* fixed, const int32_t* lengths, int32_t B,
+                            const int32_t* target_frames, int32_t* dur_out) {
+    if (B < 1 || !w || !lengths || !dur_out) return set_err(STS_EINVAL, "B >= 1, w, lengths and dur_out are required");
+    std::vector<int> tab(3 * (size_t)B);     // [offsets | lengths | targets]
+    int64_t total = 0;
+    for (int b = 0; b < B; b++) {
+        if (lengths[b] < 1 || total + lengths[b] > (1 << 24)) return set_err(STS_EINVAL, "lengths must be >= 1 and hold at most 2^24 weights in all");
+        const char* why = nullptr;
+        if (!dur_plan_valid(lengths[b], nullptr, fixed ? fixed + total : nullptr, target_frames ? target_frames[b] : 0, &why)) return set_err(STS_EINVAL, why);
+        tab[b] = (int)total; tab[B + b] = lengths[b]; tab[2 * B + b] = target_frames ? target_frames[b] : 0;
+        total += lengths[b];
+    }
+    if (hipSetDevice(device) != hipSuccess) return set_err(STS_EDEVICE, "no such device");
+    const size_t wb = (((size_t)total * 4 + 255) & ~(size_t)255), tb = ((tab.size() * 4 + 255) & ~(size_t)255), rb = (((size_t)total * 8 + 255) & ~(size_t)255);
+    char* d = nullptr;          // [w | fixed | out | tables | remainders]
+    if (hipMalloc((void**)&d, 3 * wb + tb + rb) != hipSuccess) return set_err(STS_EDEVICE, "out of device memory");
+    hipStream_t st = nullptr;
+    bool ok = hipStreamCreate(&st) == hipSuccess;
+    DurPlanArgs a{};
+    a.w_in = (const float*)d; a.fixed = fixed ? (const int*)(d + wb) : nullptr; a.forced = (int*)(d + 2 * wb);
+    const int* dt = (const int*)(d + 3 * wb);
+    a.target = dt + 2 * B; a.rem = (long long*)(d + 3 * wb + tb);
+    a.seg = SegView{dt, dt + B, 1, 0, 0, 0};
+    ok = ok && hipMemcpyAsync(d, w, (size_t)total * 4, hipMemcpyHostToDevice, st) == hipSuccess &&
+         (!fixed || hipMemcpyAsync(d + wb, fixed, (size_t)total * 4, hipMemcpyHostToDevice, st) == hipSuccess) &&
+         hipMemcpyAsync(d + 3 * wb, tab.data(), tab.size() * 4, hipMemcpyHostToDevice, st) == hipSuccess;
+    if (ok) {
+        duration_plan(a, B, st);
+        ok = hipGetLastError() == hipSuccess && hipMemcpyAsync(dur_out, a.forced, (size_t)total * 4, hipMemcpyDeviceToHost, st) == hipSuccess &&
+             hipStreamSynchronize(st) == hipSuccess;
+    }
+    if (st) (void)hipStreamDestroy(st);
+    (void)hipFree(d);
+    return ok ? STS_OK : set_err(STS_EDEVICE, "the duration plan failed on the device");
+}
+
 int sts_set_noise(sts_engine* e, float noise_scale, float noise_scale_w, uint64_t seed) {
     if (!e) return set_err(STS_EINVAL, "null engine");
     if (!noise_scale_valid(noise_scale) || !noise_scale_valid(noise_scale_w)) return set_err(STS_EINVAL, "noise scales must be finite and >= 0");

@@ -371,6 +371,41 @@ int Engine::set_limiter(int mode, float gain_db, float ceiling_dbfs, float looka
     lim_mode = mode; lim_gain_db = gain_db; lim_ceiling = ceiling_dbfs; lim_ms = lookahead_ms;
     return STS_OK;
 }
+// sts_set_duration_plan: copied and validated here; an invalid plan changes nothing.  B == 0 or plans == null drops a pending plan.
+int Engine::set_duration_plan(int B, const int32_t* n, const sts_dur_plan* plans) {
+    if (B == 0 || !plans) { have_plan = false; return STS_OK; }
+    if (B < 0 || !n) return fail(STS_EINVAL, "duration plan: B >= 0 and n are required");
+    long total = 0;
+    for (int b = 0; b < B; b++) {
+        const char* why = nullptr;
+        if (!dur_plan_valid(n[b], plans[b].rate, plans[b].fixed, plans[b].target_frames, &why)) return fail(STS_EINVAL, why);
+        total += n[b];
+        if (total > (1 << 24)) return fail(STS_EINVAL, "batch too large");
+    }
+    plan_n.assign(n, n + B);
+    plan_rate.assign((size_t)total, 1.0f); plan_fixed.assign((size_t)total, -1); plan_target.assign((size_t)B, 0);
+    size_t off = 0;
+    for (int b = 0; b < B; b++) {
+        if (plans[b].rate) std::copy(plans[b].rate, plans[b].rate + n[b], plan_rate.begin() + (long)off);
+        if (plans[b].fixed) std::copy(plans[b].fixed, plans[b].fixed + n[b], plan_fixed.begin() + (long)off);
+        plan_target[b] = plans[b].target_frames;
+        off += (size_t)n[b];
+    }
+    have_plan = true;
+    return STS_OK;
+}
+// sts_get_phoneme_offsets: host arithmetic on the durations the last run downloaded -- phoneme i with f frames before it in its utterance
+// starts at output sample ceil(f hop P / Q) (f hop at the native rate), the convention of a streaming chunk's sample_offset
+int Engine::phoneme_offsets(int64_t* start, int64_t capacity) {
+    if (!start) return fail(STS_EINVAL, "null argument");
+    if ((int64_t)durations_h.size() > capacity) return fail(STS_ESTATE, "destination too small");
+    size_t i = 0;
+    for (size_t b = 0; b < last_n.size(); b++) {
+        long long f = 0;
+        for (int t = 0; t < last_n[b] && i < durations_h.size(); t++, i++) { start[i] = out_count(f * model.hop_total); f += durations_h[i]; }
+    }
+    return STS_OK;
+}
 int Engine::stream_halo() const {
     const int h = decoder_halo_frames(model);
     // the limiter reads the float signal 2H output samples beyond a chunk's edges: 2H Q / P native samples (+ 1 for the rounding of the
@@ -403,8 +438,15 @@ int Engine::run_setup(RunCtx& c) {
     }
     if (Ttot > (1 << 24)) return fail(STS_EINVAL, "batch too large");
     if ((size_t)(M.hidden / 2 + 8 + 5 * (size_t)maxT) * 4 > 150 * 1024) return fail(STS_EINVAL, "utterance too long for the attention kernel");
+    if (have_plan && have_forced) { have_forced = false; have_plan = false; return fail(STS_EINVAL, "a duration plan and forced durations are both pending: both are dropped"); }
     if (have_forced && (long)forced_dur.size() != Ttot) { have_forced = false; return fail(STS_EINVAL, "forced durations do not match the batch"); }
-
+    if (have_plan) {
+        bool same = (int)plan_n.size() == B;
+        for (int b = 0; b < B && same; b++) same = plan_n[b] == n[b];
+        if (!same) return fail(STS_EINVAL, "the duration plan was set for another batch (B and every n[b] must match)");
+    }
+    const bool plan = c.plan = have_plan;
+    const size_t plan_ints = plan ? 2 * (size_t)Ttot + (size_t)B : 0;      // [rate Ttot | fixed Ttot | target B] behind the ids
     // sampling noise of every utterance: the caller's per-utterance table (sts_pool, sts_multi) or the engine's setting with seed + b
     c.nz.resize(B);
     for (int b = 0; b < B; b++) {
@@ -426,12 +468,16 @@ int Engine::run_setup(RunCtx& c) {
         A.used = 0;
         // one device block mirroring the pinned staging block [geometry ints | length scales | noise scales, seeds | ids | forced
         // durations]: a single host-to-device copy per run
-        bt.meta_i = A.get<int>((size_t)9 * B + 8 + 5 * (size_t)B + 2 * (size_t)Ttot);
+        // (a run with a duration plan: the plan's arrays ride in the same copy, between the ids and `forced`, which the plan kernel then writes)
+        bt.meta_i = A.get<int>((size_t)9 * B + 8 + 5 * (size_t)B + 2 * (size_t)Ttot + plan_ints);
         bt.ls = (float*)(bt.meta_i + ((size_t)9 * B + 8));
         bt.ns = bt.ls + B; bt.nsw = bt.ns + B;
         bt.seed = (uint64_t*)(bt.nsw + B);      // (9B + 8 + 3B ints from a 256-byte boundary: 8-byte aligned)
         bt.ids = (int*)(bt.seed + B);
-        bt.forced = bt.ids + Ttot;
+        bt.plan_rate = plan ? (float*)(bt.ids + Ttot) : nullptr;
+        bt.plan_fixed = plan ? bt.ids + 2 * Ttot : nullptr;
+        bt.plan_target = plan ? bt.ids + 3 * Ttot : nullptr;
+        bt.forced = bt.ids + Ttot + plan_ints;
         bt.x = A.get<float>((size_t)H * Ttot); bt.qkv = A.get<float>((size_t)3 * H * Ttot);
         bt.att = A.get<float>((size_t)H * Ttot); bt.y = A.get<float>((size_t)H * Ttot * ffn2_slices);
         bt.x1 = A.get<float>((size_t)H * Ttot); bt.ffh = A.get<float>((size_t)FF * Ttot);
@@ -448,6 +494,8 @@ int Engine::run_setup(RunCtx& c) {
         bt.cond_dp = A.get<float>((size_t)(fdp > H ? fdp : H) * B);
         bt.cond_dec = A.get<float>((size_t)(M.up_init > 0 ? M.up_init : 1) * B);
         bt.cond_wn = A.get<float>((size_t)(2 * wnH * wnL + 4) * B * (M.n_flows > 0 ? M.n_flows : 1));   // one block per coupling
+        bt.plan_rem = plan ? A.get<long long>(Ttot) : nullptr;
+        bt.dur_w = plan && record_taps ? A.get<float>(Ttot) : nullptr;
     };
     arenaT_.measuring = true; layoutT(arenaT_);
     if (!ensure(arenaT_, arenaT_.used + 4096)) return fail(STS_EDEVICE, "out of device memory (phoneme-level workspace)");
@@ -456,7 +504,7 @@ int Engine::run_setup(RunCtx& c) {
 
     // ---------------- one H2D: geometry + ids (+ forced durations)
     const size_t meta_ints = c.meta_ints = (size_t)9 * B + 8;
-    const size_t up_bytes = c.up_bytes = (meta_ints + 5 * (size_t)B + 2 * (size_t)Ttot) * 4 + 1024;
+    const size_t up_bytes = c.up_bytes = (meta_ints + 5 * (size_t)B + 2 * (size_t)Ttot + plan_ints) * 4 + 1024;
     if (!ensure_pinned(up_bytes + ((size_t)Ttot + B) * 4)) return fail(STS_EDEVICE, "pinned host allocation failed");
     int* pm = c.pm = (int*)pinned_;
     int* p_offT = c.p_offT = pm, *p_lenT = c.p_lenT = pm + B, *p_sid = c.p_sid = pm + 2 * B, *p_one = c.p_one = pm + 5 * B;
@@ -474,7 +522,12 @@ int Engine::run_setup(RunCtx& c) {
     for (int b = 0; b < B; b++) memcpy(p_ids + offT[b], ids[b], sizeof(int) * n[b]);
     int* p_forced = p_ids + Ttot;
     if (have_forced) memcpy(p_forced, forced_dur.data(), sizeof(int) * Ttot);
-    HIPCK(hipMemcpyAsync(bt.meta_i, pm, (meta_ints + 5 * (size_t)B + (size_t)Ttot * (have_forced ? 2 : 1)) * 4, hipMemcpyHostToDevice, stream));
+    if (plan) {          // (never together with forced durations: the plan's arrays take their place in the copy)
+        memcpy(p_ids + Ttot, plan_rate.data(), sizeof(float) * Ttot);
+        memcpy(p_ids + 2 * Ttot, plan_fixed.data(), sizeof(int) * Ttot);
+        memcpy(p_ids + 3 * Ttot, plan_target.data(), sizeof(int) * B);
+    }
+    HIPCK(hipMemcpyAsync(bt.meta_i, pm, (meta_ints + 5 * (size_t)B + (size_t)Ttot * (have_forced ? 2 : 1) + plan_ints) * 4, hipMemcpyHostToDevice, stream));
     if (B > 1) HIPCK(hipEventRecord(ev_setup_, stream));     // (run_durations, batches launched from the memo: the host rewrites part of this block)
 
     // single-segment views travel by value (kernels.hpp SegView): no segment-table load in the kernels of a one-utterance call
@@ -677,7 +730,7 @@ int Engine::run_durations(RunCtx& c) {
         c.req_keys[b] = h | 1ull;
     }
     c.predF.clear();
-    if (launch_ahead && !ss && !have_forced && !record_taps && mapped) {
+    if (launch_ahead && !ss && !have_forced && !c.plan && !record_taps && mapped) {     // (a planned run's frame count is not a function of the memo's key)
         c.predF.resize(B);
         for (int b = 0; b < B; b++) {
             const auto it = seen_tf_.find(c.req_keys[b]);
@@ -690,10 +743,17 @@ int Engine::run_durations(RunCtx& c) {
     c.ahead_b = B > 1 && !c.predF.empty();
     c.hop = M.hop_total;
     const long cap = c.ahead ? (pred + 63) / 64 * 64 : 0;
-    durations(r_final, M.dur_type == 0 ? 1 : 0, M.ea_m, M.ea_logs, bt.ls, have_forced ? bt.forced : nullptr, bt.dlogw,
+    if (c.plan) {        // the plan kernel turns logw and the plan into the forced durations the durations kernel then takes
+        DurPlanArgs pa{};
+        pa.r0 = r_final; pa.sdp = M.dur_type == 0 ? 1 : 0; pa.ea_m = M.ea_m; pa.ea_logs = M.ea_logs; pa.ls = bt.ls;
+        pa.rate = bt.plan_rate; pa.fixed = bt.plan_fixed; pa.target = bt.plan_target;
+        pa.forced = bt.forced; pa.dur_w = bt.dur_w; pa.rem = bt.plan_rem; pa.seg = lvT.seg;
+        duration_plan(pa, B, stream);
+    }
+    durations(r_final, M.dur_type == 0 ? 1 : 0, M.ea_m, M.ea_logs, bt.ls, (have_forced || c.plan) ? bt.forced : nullptr, bt.dlogw,
               bt.dur, bt.cum, bt.frames, lvT.seg, B, stream, mapped ? hmap_dev_ : nullptr, Ttot, seq_, arrive_,
               c.ahead ? c.d_lenF : nullptr, c.ahead ? c.d_win + 2 : nullptr, (int)cap);
-    c.forced = have_forced;
+    c.forced = have_forced || c.plan;      // (neither kind of run feeds the memo)
     have_forced = false;
     mark(2);
     sync_wait_ms_ = 0;
@@ -787,7 +847,9 @@ int Engine::wait_frame_counts(RunCtx& c) {
         if (c.mapped) note_wait(0, Ttot, waited_ms * 1e3, !polled_unready);
     }
     durations_h.assign(p_down, p_down + Ttot);
+    last_n.assign(c.lenT.begin(), c.lenT.end());
     tap("logw", bt.dlogw, 1, Ttot, Ttot);
+    if (bt.dur_w) tap("dur_w", bt.dur_w, 1, Ttot, Ttot);
     c.Ftot = 0; c.maxF = 0;
     for (int b = 0; b < B; b++) {
         int f = p_down[Ttot + b];
@@ -1068,7 +1130,12 @@ static constexpr int kRetrySplitBf16 = 1;     // run_once: nothing was handed ou
 // An engine that had to repeat two calls in a row stays in the split-bf16 form (a model whose activations do not fit fp16 would
 // otherwise pay for both forms on every call) until sts_set_conv_math is called again.
 int Engine::run(int B, const int32_t* const* ids, const int32_t* n, const int32_t* sid, const float* ls, const StreamSpec* ss) {
-    poison_bytes_ = 0;          // (a split-bf16 repeat lays the arenas out again and fills them again: both fills count)
+    const int rc = run_any_math(B, ids, n, sid, ls, ss);
+    have_plan = false;          // a duration plan is for one call, whatever its outcome; the repeat inside the call above applied it again
+    return rc;
+}
+int Engine::run_any_math(int B, const int32_t* const* ids, const int32_t* n, const int32_t* sid, const float* ls, const StreamSpec* ss) {
+    poison_bytes_ = 0;         // (a split-bf16 repeat lays the arenas out again and fills them again: both fills count)
     if (conv_math != 3) return run_once(B, ids, n, sid, ls, ss);
     if (h2_disabled) {
         conv_math = 0;

@@ -123,6 +123,14 @@ public:
     std::vector<sts_limiter_stats> lim_res;
     int set_limiter(int mode, float gain_db, float ceiling_dbfs, float lookahead_ms);
     std::vector<int32_t> forced_dur; bool have_forced = false;
+    // duration plan (sts_set_duration_plan, duration_plan.hip): for the NEXT call only, whatever its outcome -- run() drops it when the call
+    // returns, so the conv-math-3 repeat of a call applies it again.  Materialised for the whole batch: an utterance without a plan has
+    // rate 1 (w * 1.0f == w bit for bit), fixed -1, target 0.  plan_n: the phoneme counts the next call must have.
+    std::vector<int32_t> plan_n, plan_fixed, plan_target; std::vector<float> plan_rate; bool have_plan = false;
+    int set_duration_plan(int B, const int32_t* n, const sts_dur_plan* plans);
+    // phoneme start offsets of the last run in output samples, packed like durations_h (sts_get_phoneme_offsets); last_n: its phoneme counts
+    std::vector<int32_t> last_n;
+    int phoneme_offsets(int64_t* start, int64_t capacity);
     bool record_taps = false; int profiling = 0;       // profiling: 0 off, 1 all stage events, 2 the matrix-core region's two events only (sts_set_profiling)
     int conv_mode = 0;
     int conv_math = 3;                 // 0 = split-bf16 trunk convs (conv_bf3.hip), 1 = exact-fp32 MFMA, 3 = two-term fp16 (sts_set_conv_math)
@@ -177,6 +185,7 @@ private:
     struct SplineTail { const DConv* proj; float filter_sqrt; const float* r0; const float* r1; float* o0; float* o1; };
     float* dds(const DDds& d, float* h, float* t1, float* t2, const Lvl& lv, const DConv* pre = nullptr, const float* pre_in = nullptr,
                const float* pre_res = nullptr, const SplineTail* tail = nullptr, bool* tail_done = nullptr);
+    int run_any_math(int B, const int32_t* const* ids, const int32_t* n, const int32_t* sid, const float* ls, const StreamSpec* ss);
     struct RunCtx;                  // what the stages of one run share (run_ctx.hpp)
     struct ResStage;                // the ResBlock chains of one decoder stage (decoder.hip)
     int run_setup(RunCtx& c);

@@ -312,6 +312,25 @@ void durations(const float* r0, int sdp, float ea_m, float ea_logs, const float*
                float* logw_out, int* dur, int* cum, int* frames, SegView seg, int B, hipStream_t st,
                int* host_out = nullptr, long total = 0, int seq = 0, unsigned* arrive = nullptr,
                int* len_out = nullptr, int* win_len_out = nullptr, int cap = 0);     // optional: frames[b] clamped to cap, into two device tables
+// Duration plans (duration_plan.hip; the definition is there and in include/summertts_hip.h sts_set_duration_plan)
+constexpr int kDurMax = 100000;             // == the durations kernel's clamp per phoneme
+constexpr int kDurMaxTarget = 1 << 20;      // frames of a fitted utterance
+// one utterance's plan: rate (or null) finite in [1/64, 64], fixed (or null) in [-1, kDurMax], target 0 or in [1, kDurMaxTarget] and feasible
+bool dur_plan_valid(int n, const float* rate, const int32_t* fixed, int32_t target, const char** why);
+// steps 3-4 of the definition on the host, for a plan dur_plan_valid accepted
+void duration_fit(const float* w, const int32_t* fixed, int n, int32_t target, int32_t* out);
+struct DurPlanArgs {
+    const float* r0; int sdp; float ea_m, ea_logs; const float* ls;    // the duration predictor's output, as durations() takes it
+    const float* w_in;                   // or the weights themselves (sts_duration_plan_apply): r0, ls and rate are then unused
+    const float* rate; const int* fixed; // [total] each, or null
+    const int* target;                   // [B]: 0 = no target
+    int* forced;                         // out [total]: what durations() then takes as its forced durations
+    float* dur_w;                        // out [total] or null: w (the "dur_w" tap)
+    long long* rem;                      // scratch [total]
+    SegView seg;
+};
+// one workgroup of 256 threads per utterance
+void duration_plan(const DurPlanArgs& a, int B, hipStream_t st);
 // z[c][offF[b] + f] = m[c][offT[b] + phoneme(f)]
 // nz (optional; null or nz->logs null = the noise-free regulator): z_p = m_expand + eps * logs_expand * ns[b] (SynthesizerTrn.cpp:383),
 // logs with m's geometry, per-utterance ns / seed tables on the device (noise.hpp)

@@ -684,6 +684,7 @@ void spline_step(const float* h, long ld, float filter_sqrt, const float* r0, co
 // durations: w = exp(logw) * lengthScale ; ceil ; (int) ; inclusive scan ; frames = max(sum, 1)
 // (/root/reference/src/models/SynthesizerTrn.cpp:376-378, 304-321; ElementwiseAffine.cpp:44-58)
 constexpr int kMaxDur = 100000;   // sanity clamp per phoneme (the reference has none)
+static_assert(kMaxDur == kDurMax, "duration_plan.hip restates this clamp");
 __global__ __launch_bounds__(256) void durations_kernel(const float* r0, int sdp, float ea_m, float ea_logs,
                                                         const float* ls, const int* forced, float* logw_out,
                                                         int* dur, int* cum, int* frames, SegView seg,

@@ -97,6 +97,9 @@ struct sts_multi {
     int64_t epoch = 0; int pending = 0; bool stop = false;
     int32_t B = 0; const int32_t* const* ids = nullptr; const int32_t* n = nullptr; const int32_t* sid = nullptr; const float* ls = nullptr;
     Engine::Noise noise;                    // sts_multi_set_noise: utterance b of a batch samples with noise.seed + b (its index in the caller's batch)
+    // sts_multi_set_duration_plan: the next batch's plans, per utterance of the caller's batch (rate / fixed: n entries or empty = absent)
+    struct UttPlan { std::vector<float> rate; std::vector<int32_t> fixed; int32_t target = 0; };
+    std::vector<UttPlan> plan; std::vector<int32_t> plan_n; bool have_plan = false;
     std::vector<Shard> shards;
     // RCCL gather state (gather_mode == 1)
     int gather_mode = 0;
@@ -286,7 +289,16 @@ struct sts_multi {
                     const int u = sh.utt[i]; idp[i] = ids[u]; nn[i] = n[u]; sd[i] = sid ? sid[u] : 0; l[i] = ls ? ls[u] : 1.0f;
                     eng.noise_utt[i] = Engine::Noise{noise.ns, noise.nsw, noise.seed + (uint64_t)u};
                 }
-                sh.rc = eng.run(nb, idp.data(), nn.data(), sd.data(), l.data());
+                sh.rc = STS_OK;
+                if (have_plan) {      // the plans follow their utterances into the shard
+                    std::vector<sts_dur_plan> pl(nb);
+                    for (int i = 0; i < nb; i++) {
+                        const UttPlan& up = plan[sh.utt[i]];
+                        pl[i] = sts_dur_plan{up.rate.empty() ? nullptr : up.rate.data(), up.fixed.empty() ? nullptr : up.fixed.data(), up.target};
+                    }
+                    sh.rc = eng.set_duration_plan(nb, nn.data(), pl.data());
+                }
+                if (sh.rc == STS_OK) sh.rc = eng.run(nb, idp.data(), nn.data(), sd.data(), l.data());
                 eng.noise_utt.clear();
                 if (sh.rc == STS_OK && gather_mode == 1) {
                     sh.n_samples = eng.n_samples;           // the PCM stays on the device: rccl_gather() below
@@ -406,6 +418,24 @@ int sts_multi_set_limiter(sts_multi* m, int mode, float gain_db, float ceiling_d
     }
     return STS_OK;
 }
+int sts_multi_set_duration_plan(sts_multi* m, int32_t B, const int32_t* n, const sts_dur_plan* plans) {
+    if (!m) return multi_err(STS_EINVAL, "null handle");
+    if (B == 0 || !plans) { m->have_plan = false; return STS_OK; }
+    if (B < 0 || !n) return multi_err(STS_EINVAL, "duration plan: B >= 0 and n are required");
+    for (int b = 0; b < B; b++) {
+        const char* why = nullptr;
+        if (!dur_plan_valid(n[b], plans[b].rate, plans[b].fixed, plans[b].target_frames, &why)) return multi_err(STS_EINVAL, why);
+    }
+    m->plan.assign((size_t)B, sts_multi::UttPlan());
+    m->plan_n.assign(n, n + B);
+    for (int b = 0; b < B; b++) {
+        if (plans[b].rate) m->plan[b].rate.assign(plans[b].rate, plans[b].rate + n[b]);
+        if (plans[b].fixed) m->plan[b].fixed.assign(plans[b].fixed, plans[b].fixed + n[b]);
+        m->plan[b].target = plans[b].target_frames;
+    }
+    m->have_plan = true;
+    return STS_OK;
+}
 int sts_multi_set_conv_math(sts_multi* m, int mode) {
     if (!m) return multi_err(STS_EINVAL, "null handle");
     if (mode < 0 || mode > 3) return multi_err(STS_EINVAL, "conv math must be 0..3");
@@ -513,9 +543,16 @@ int sts_multi_shard_of(const sts_multi* m, int32_t B, const int32_t* n, int32_t*
 
 int sts_multi_infer_ids_batch(sts_multi* m, int32_t B, const int32_t* const* ids, const int32_t* n, const int32_t* sid,
                               const float* length_scale, int16_t** pcm_out, int32_t* n_out) {
-    if (!m || !ids || !n || !pcm_out || !n_out || B <= 0) return multi_err(STS_EINVAL, "bad arguments");
+    if (!m) return multi_err(STS_EINVAL, "bad arguments");
+    struct DropPlan { sts_multi* m; ~DropPlan() { m->have_plan = false; } } drop_plan{m};      // a duration plan is for this call only, whatever its outcome
+    if (!ids || !n || !pcm_out || !n_out || B <= 0) return multi_err(STS_EINVAL, "bad arguments");
     for (int b = 0; b < B; b++) { pcm_out[b] = nullptr; n_out[b] = 0; }      // every output is defined before the first early return
     for (int b = 0; b < B; b++) if (n[b] <= 0 || !ids[b]) return multi_err(STS_EINVAL, "utterance with no phonemes");
+    if (m->have_plan) {
+        bool same = (int)m->plan_n.size() == B;
+        for (int b = 0; b < B && same; b++) same = m->plan_n[b] == n[b];
+        if (!same) return multi_err(STS_EINVAL, "the duration plan was set for another batch (B and every n[b] must match)");
+    }
     const int ndev = (int)m->engines.size();
     const bool was_gather = m->gather_mode == 1;
     {

@@ -27,6 +27,8 @@ struct Request {
     int64_t ticket = 0;
     std::vector<int32_t> ids; int32_t sid = 0; float ls = 1.f;
     Engine::Noise noise;               // sts_pool_submit_ex: this request's sampling noise
+    // sts_pool_submit_plan: this request's duration plan (rate / fixed: n entries or empty = absent; target 0 = none)
+    bool planned = false; std::vector<float> rate; std::vector<int32_t> fixed; int32_t target = 0;
     // sts_pool_submit_stream: chunks go to cb (on the worker thread); the ticket completes with pcm = null, n = samples delivered
     bool stream = false; int32_t chunk = 0; sts_chunk_cb cb = nullptr; void* user = nullptr;
     // result
@@ -74,7 +76,17 @@ struct sts_pool {
                     idp[b] = grp[b]->ids.data(); n[b] = (int32_t)grp[b]->ids.size(); sid[b] = grp[b]->sid; ls[b] = grp[b]->ls;
                     eng.noise_utt[b] = grp[b]->noise;
                 }
-                int rc = eng.run(B, idp.data(), n.data(), sid.data(), ls.data());
+                bool any_plan = false;
+                for (int b = 0; b < B; b++) any_plan = any_plan || grp[b]->planned;
+                int rc = STS_OK;
+                if (any_plan) {      // per utterance: the members without a plan get an empty one (synthesised as without, bit for bit)
+                    std::vector<sts_dur_plan> pl(B, sts_dur_plan{nullptr, nullptr, 0});
+                    for (int b = 0; b < B; b++)
+                        if (grp[b]->planned) pl[b] = sts_dur_plan{grp[b]->rate.empty() ? nullptr : grp[b]->rate.data(),
+                                                                  grp[b]->fixed.empty() ? nullptr : grp[b]->fixed.data(), grp[b]->target};
+                    rc = eng.set_duration_plan(B, n.data(), pl.data());
+                }
+                if (rc == STS_OK) rc = eng.run(B, idp.data(), n.data(), sid.data(), ls.data());
                 eng.noise_utt.clear();
                 std::vector<int16_t> all;
                 if (rc == STS_OK) {
@@ -197,6 +209,29 @@ int64_t sts_pool_submit_ex(sts_pool* p, const int32_t* ids, int32_t n, int32_t s
     if (!noise_scale_valid(noise_scale) || !noise_scale_valid(noise_scale_w)) return pool_err(STS_EINVAL, "noise scales must be finite and >= 0");
     auto r = std::make_shared<Request>();
     r->ids.assign(ids, ids + n); r->sid = sid; r->ls = length_scale; r->noise = Engine::Noise{noise_scale, noise_scale_w, seed};
+    {
+        std::lock_guard<std::mutex> lk(p->mu);
+        if (p->stop) return pool_err(STS_ESTATE, "pool is shutting down");
+        r->ticket = p->next_ticket++;
+        p->queue.push_back(r);
+        p->pending[r->ticket] = r;
+    }
+    p->cv_work.notify_one();
+    return r->ticket;
+}
+
+int64_t sts_pool_submit_plan(sts_pool* p, const int32_t* ids, int32_t n, int32_t sid, float length_scale, float noise_scale,
+                             float noise_scale_w, uint64_t seed, const float* rate, const int32_t* fixed, int32_t target_frames) {
+    if (!p || !ids || n <= 0) return pool_err(STS_EINVAL, "bad request");
+    if (!noise_scale_valid(noise_scale) || !noise_scale_valid(noise_scale_w)) return pool_err(STS_EINVAL, "noise scales must be finite and >= 0");
+    const char* why = nullptr;
+    if (!dur_plan_valid(n, rate, fixed, target_frames, &why)) return pool_err(STS_EINVAL, why);
+    auto r = std::make_shared<Request>();
+    r->ids.assign(ids, ids + n); r->sid = sid; r->ls = length_scale; r->noise = Engine::Noise{noise_scale, noise_scale_w, seed};
+    r->planned = rate || fixed || target_frames != 0;
+    if (rate) r->rate.assign(rate, rate + n);
+    if (fixed) r->fixed.assign(fixed, fixed + n);
+    r->target = target_frames;
     {
         std::lock_guard<std::mutex> lk(p->mu);
         if (p->stop) return pool_err(STS_ESTATE, "pool is shutting down");

@@ -17,6 +17,9 @@ struct BufT {
     float *dh, *dt1, *dt2, *dc, *dhh, *dp29, *dr[4], *dlogw;
     int *dur, *cum, *frames;
     float *g, *cond_dp, *cond_dec, *cond_wn;
+    // a run with a duration plan only (null otherwise): the uploaded plan [rate Ttot | fixed Ttot | target B] between ids and forced, the
+    // plan kernel's remainder scratch, w for the "dur_w" tap
+    float* plan_rate; int *plan_fixed, *plan_target; long long* plan_rem; float* dur_w;
 };
 struct BufF {
     float *z, *h, *acts, *out, *x0, *regA, *regB, *tailA, *tailB, *tailC, *wave, *fliptmp;
@@ -57,6 +60,7 @@ struct Engine::RunCtx {
     // (ahead: the count is predicted, the kernels read the real one from device memory) makes exactly the dispatch decisions of a call
     // that waited for it -- and returns bit-identical samples.  Batches: Fld == Ftot, nothing changes.
     long Fld = 0; int maxFld = 0; bool ahead = false, ahead_b = false, mapped = false, forced = false;
+    bool plan = false;              // this run applies a duration plan (sts_set_duration_plan): never launched ahead, never in the memo
     std::vector<Engine::Noise> nz; bool any_ns = false, any_nsw = false;   // per-utterance sampling noise (engine.hpp Noise), which of the two is used
     std::vector<unsigned long long> req_keys; std::vector<long> predF;      // launch-ahead memo: per-utterance request hashes, remembered frame counts (empty: not all known)
     int halo = 0; long Wcap = 0; int upS = 1; long Lsb = 0; int sbC = 0;

@@ -47,6 +47,32 @@ class Profile(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class DurPlan(C.Structure):
+    """``sts_dur_plan``: one utterance's duration plan (include/summertts_hip.h sts_set_duration_plan)."""
+    _fields_ = [("rate", C.c_void_p), ("fixed", C.c_void_p), ("target_frames", C.c_int32)]
+
+
+def _dur_plans(n: Sequence[int], plans):
+    """-> (n as int32 array, ctypes array of DurPlan, the numpy arrays it points into).  ``plans[b]``: None or a mapping with any of
+    ``rate`` (float per phoneme), ``fixed`` (int per phoneme, -1 = predicted), ``target_frames``."""
+    n = np.ascontiguousarray(n, dtype=np.int32)
+    if len(plans) != n.size:
+        raise ValueError("one plan (or None) per utterance")
+    arr, keep = (DurPlan * max(n.size, 1))(), []
+    for b, p in enumerate(plans):
+        p = p or {}
+        for key, dt in (("rate", np.float32), ("fixed", np.int32)):
+            v = p.get(key)
+            if v is not None:
+                v = np.ascontiguousarray(v, dtype=dt)
+                if v.size != n[b]:
+                    raise ValueError(f"plan {b}: {key} needs one entry per phoneme")
+                keep.append(v)
+                setattr(arr[b], key, v.ctypes.data)
+        arr[b].target_frames = int(p.get("target_frames") or 0)
+    return n, arr, keep
+
+
 class PreparedBatch:
     """run_batch's argument arrays, built once (Synthesizer.prepare)."""
 
@@ -131,6 +157,14 @@ def load_library() -> C.CDLL:
     lib.sts_limiter_apply.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_float,
                                       C.c_void_p, C.c_void_p, C.c_void_p]
     lib.sts_multi_set_output_rate.argtypes = [C.c_void_p, C.c_int32]
+    lib.sts_set_duration_plan.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
+    lib.sts_multi_set_duration_plan.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
+    lib.sts_get_phoneme_offsets.argtypes = [C.c_void_p, C.c_void_p, C.c_int64]
+    lib.sts_duration_fit.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]
+    lib.sts_duration_plan_apply.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
+    lib.sts_pool_submit_plan.restype = C.c_int64
+    lib.sts_pool_submit_plan.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_float, C.c_uint64,
+                                         C.c_void_p, C.c_void_p, C.c_int32]
     lib.sts_infer_ids_batch_stream.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
                                                BATCH_CHUNK_CB, C.c_void_p, C.c_void_p]
     lib.sts_pool_submit_stream.restype = C.c_int64
@@ -161,7 +195,45 @@ EXPORTED_SYMBOLS = [
     "sts_kweight_coeffs", "sts_loudness_measure",
     "sts_set_limiter", "sts_get_limiter_mode", "sts_get_limiter", "sts_pool_set_limiter", "sts_multi_set_limiter",
     "sts_limiter_design", "sts_limiter_apply",
+    "sts_set_duration_plan", "sts_get_phoneme_offsets", "sts_duration_fit", "sts_duration_plan_apply", "sts_pool_submit_plan",
+    "sts_multi_set_duration_plan",
 ]
+
+
+def duration_fit(w, fixed=None, target_frames: int = 0) -> np.ndarray:
+    """Steps 3-4 of the duration-plan definition on caller weights (include/summertts_hip.h sts_duration_fit; host only, no GPU): -> int32
+    durations.  An invalid or infeasible plan raises."""
+    lib = load_library()
+    w = np.ascontiguousarray(w, dtype=np.float32).ravel()
+    f = None if fixed is None else np.ascontiguousarray(fixed, dtype=np.int32).ravel()
+    if f is not None and f.size != w.size:
+        raise ValueError("fixed needs one entry per weight")
+    out = np.zeros(max(w.size, 1), np.int32)
+    _check(lib, lib.sts_duration_fit(w.ctypes.data if w.size else None, None if f is None else f.ctypes.data, w.size, int(target_frames),
+                                     out.ctypes.data))
+    return out[:w.size]
+
+
+def duration_plan_apply(weights, fixed=None, target_frames=None, device: int = 0) -> List[np.ndarray]:
+    """The duration-plan kernel on caller weights (sts_duration_plan_apply): ``weights`` a list of float arrays, one per utterance;
+    ``fixed`` None or a list of int arrays (an entry may be None = all predicted); ``target_frames`` None or one int per utterance ->
+    list of int32 duration arrays."""
+    lib = load_library()
+    ws = [np.ascontiguousarray(x, dtype=np.float32).ravel() for x in weights]
+    lens = np.asarray([x.size for x in ws], np.int32)
+    w = np.concatenate(ws) if ws and lens.sum() > 0 else np.zeros(1, np.float32)
+    f = None
+    if fixed is not None:
+        f = np.concatenate([np.full(ws[b].size, -1, np.int32) if fx is None else np.ascontiguousarray(fx, dtype=np.int32).ravel()
+                            for b, fx in enumerate(fixed)])
+        if f.size != int(lens.sum()):
+            raise ValueError("fixed needs one entry per weight")
+    t = None if target_frames is None else np.ascontiguousarray(target_frames, dtype=np.int32)
+    out = np.zeros(max(int(lens.sum()), 1), np.int32)
+    _check(lib, lib.sts_duration_plan_apply(int(device), w.ctypes.data, None if f is None else f.ctypes.data, lens.ctypes.data, len(ws),
+                                            None if t is None else t.ctypes.data, out.ctypes.data))
+    off = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
+    return [out[off[b]:off[b + 1]].copy() for b in range(len(ws))]
 
 LOUD_OFF, LOUD_MEASURE, LOUD_NORMALIZE = 0, 1, 2
 # sts_loudness: lufs (-inf when unmeasured), peak, gain, blocks
@@ -385,6 +457,23 @@ class Synthesizer:
             return
         d = np.ascontiguousarray(dur, dtype=np.int32)
         _check(self.lib, self.lib.sts_set_forced_durations(self.h, d.ctypes.data, d.size))
+
+    def set_duration_plan(self, n: Optional[Sequence[int]], plans=None):
+        """Duration plan of the NEXT call only (include/summertts_hip.h sts_set_duration_plan).  ``n``: phoneme count of every utterance
+        of that call; ``plans``: per utterance None or a mapping with any of ``rate`` (float per phoneme, multiplies the length scale),
+        ``fixed`` (frames per phoneme, -1 = predicted), ``target_frames`` (the utterance's exact length; 0 = none).  ``n`` or ``plans``
+        None drops a pending plan.  An invalid plan raises and changes nothing."""
+        if n is None or plans is None:
+            _check(self.lib, self.lib.sts_set_duration_plan(self.h, 0, None, None))
+            return
+        nn, arr, keep = _dur_plans(n, plans)
+        _check(self.lib, self.lib.sts_set_duration_plan(self.h, nn.size, nn.ctypes.data, C.cast(arr, C.c_void_p)))
+
+    def phoneme_offsets(self, total_phonemes: int) -> np.ndarray:
+        """Start of every phoneme of the last run in output samples at the current output rate, packed like ``durations``."""
+        s = np.zeros(total_phonemes, np.int64)
+        _check(self.lib, self.lib.sts_get_phoneme_offsets(self.h, s.ctypes.data, s.size))
+        return s
 
     def set_record_taps(self, on: bool):
         _check(self.lib, self.lib.sts_set_record_taps(self.h, 1 if on else 0))
@@ -623,10 +712,15 @@ class Pool:
         return t
 
     def submit(self, ids: Sequence[int], sid: int = 0, length_scale: float = 1.0, noise_scale: float = 0.0,
-               noise_scale_w: float = 0.0, seed: int = 0) -> int:
-        """Queue one request; the noise arguments are this request's own (``Synthesizer.set_noise``; ``seed`` is used as given)."""
+               noise_scale_w: float = 0.0, seed: int = 0, plan=None) -> int:
+        """Queue one request; the noise arguments are this request's own (``Synthesizer.set_noise``; ``seed`` is used as given), and so
+        is ``plan``: None or a mapping as ``Synthesizer.set_duration_plan`` takes per utterance (sts_pool_submit_plan)."""
         a = np.ascontiguousarray(ids, dtype=np.int32)
-        if noise_scale == 0.0 and noise_scale_w == 0.0 and seed == 0:
+        if plan is not None:
+            _, arr, keep = _dur_plans([a.size], [plan])
+            t = int(self.lib.sts_pool_submit_plan(self.h, a.ctypes.data, a.size, sid, length_scale, float(noise_scale), float(noise_scale_w),
+                                                  int(seed) & 0xFFFFFFFFFFFFFFFF, arr[0].rate, arr[0].fixed, arr[0].target_frames))
+        elif noise_scale == 0.0 and noise_scale_w == 0.0 and seed == 0:
             t = int(self.lib.sts_pool_submit(self.h, a.ctypes.data, a.size, sid, length_scale))
         else:
             t = int(self.lib.sts_pool_submit_ex(self.h, a.ctypes.data, a.size, sid, length_scale, float(noise_scale),
@@ -760,6 +854,17 @@ class MultiDevice:
         rc = self.lib.sts_multi_set_limiter(self.h, int(mode), float(gain_db), float(ceiling_dbfs), float(lookahead_ms))
         if rc != 0:
             raise StsError(f"sts_multi_set_limiter: {rc}: {self.lib.sts_multi_last_error().decode()}")
+
+    def set_duration_plan(self, n: Optional[Sequence[int]], plans=None):
+        """``Synthesizer.set_duration_plan`` for the next ``infer_batch``: ``plans[b]`` belongs to utterance b of that batch, whatever its
+        device."""
+        if n is None or plans is None:
+            rc = self.lib.sts_multi_set_duration_plan(self.h, 0, None, None)
+        else:
+            nn, arr, keep = _dur_plans(n, plans)
+            rc = self.lib.sts_multi_set_duration_plan(self.h, nn.size, nn.ctypes.data, C.cast(arr, C.c_void_p))
+        if rc != 0:
+            raise StsError(f"sts_multi_set_duration_plan: {rc}: {self.lib.sts_multi_last_error().decode()}")
 
     def set_conv_math(self, mode):
         m = {"bf16x3": 0, "f32": 1, "bf16x3_all": 2, "f16x2": 3}.get(mode, mode)
