@@ -376,7 +376,7 @@ int sts_set_profiling(sts_engine* e, int enable);
  * sizeof(sts_profile)) bytes, so a client compiled against an older header passes ITS sizeof and is never overrun;
  * sts_get_profile(e, p) == sts_get_profile_ex(e, p, sizeof(sts_profile)) of the header this library was built from -- use it only
  * when client and library are built together. */
-#define STS_ABI_VERSION 14
+#define STS_ABI_VERSION 15
 int sts_abi_version(void);
 /* bit 0: lab build (-DSTS_EXPERIMENTS: environment knobs of knobs.hpp, every conv tile code);
  * 0 for the shipped library */
@@ -398,6 +398,17 @@ int sts_debug_conv1d_bench(int device, const float* x, int32_t Cin, int32_t L, c
                            int32_t depthwise, float in_slope, int32_t in_act, int mode, float** y, int32_t* Lout,
                            int32_t iters, float* ms_out);
 
+/* sts_debug_conv1d_packed (ABI 15): the same conv on B utterances packed back to back along the time axis, as the engine packs a batch:
+ * x [Cin][L] with L = sum(lengths), every lengths[b] >= 1.  The kernels get device offset / length tables of B entries (B = 1 included)
+ * and a grid sized by the longest segment; halos are zero at every segment's edges.  Geometries: "same" padding (odd k, pad =
+ * dil (k - 1) / 2; output segment = input segment) or a transposed conv with pad = (k - stride) / 2 (output segment = input segment x
+ * stride); anything else is STS_EINVAL.  mode as above.  The output buffer starts out as a NaN pattern, so a position no workgroup
+ * writes reads as NaN.  *ovf (optional): the overflow word of the two-term fp16 kernels after the launch (0 for every other mode). */
+int sts_debug_conv1d_packed(int device, const float* x, int32_t Cin, int32_t L, const float* w, const float* bias,
+                            int32_t Cout, int32_t k, int32_t pad, int32_t dil, int32_t stride_transposed,
+                            int32_t depthwise, float in_slope, int32_t in_act, int mode, float** y, int32_t* Lout,
+                            const int32_t* lengths, int32_t B, uint32_t* ovf);
+
 /* One "same"-padded conv (odd k, pad = dil (k - 1) / 2) through the pre-split path of the wide decoder stages (conv_h2p.hip): x fp32
  * [Cin][L] -> split_planes(in_slope) -> conv_h2p_group with `members` identical members -> member 0's three output forms, each decoded to
  * fp32 [Cout][L] (null: not wanted): y = the channel-major fp32 output, y16 = the channel-minor fp32 copy, yp = the two fp16 planes of
@@ -405,6 +416,13 @@ int sts_debug_conv1d_bench(int device, const float* x, int32_t Cin, int32_t L, c
 int sts_debug_conv_h2p(int device, const float* x, int32_t Cin, int32_t L, const float* w, const float* bias, int32_t Cout, int32_t k,
                        int32_t dil, const float* res, float in_slope, float out_slope, int tile, int members, float* y, float* y16,
                        float* yp, int32_t iters, float* ms_out);
+
+/* sts_debug_conv_h2p_packed (ABI 15): sts_debug_conv_h2p on B packed utterances (x, res and the outputs [C][L], L = sum(lengths), every
+ * lengths[b] >= 1): split_planes and conv_h2p_group both get the B-entry segment table and max_n = the longest segment.  The plane and
+ * output buffers start out as a NaN pattern.  *ovf (optional): the overflow word after the launch. */
+int sts_debug_conv_h2p_packed(int device, const float* x, int32_t Cin, int32_t L, const float* w, const float* bias, int32_t Cout, int32_t k,
+                              int32_t dil, const float* res, float in_slope, float out_slope, int tile, int members, float* y, float* y16,
+                              float* yp, const int32_t* lengths, int32_t B, uint32_t* ovf);
 
 /* The same conv through the Winograd-domain lab kernel (conv_h2w.hip: segmented F(2,3) / F(2,2) on two-term fp16 operands): y = fp32 [C][L],
  * y16 = its channel-minor output of lrelu(out, out_slope) decoded to [C][L].  C % 128 == 0, odd k >= 3, (k - 1) dil <= 64. */

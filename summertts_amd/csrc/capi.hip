@@ -461,6 +461,11 @@ int sts_debug_wino_pack(const float* w, int32_t Cout, int32_t k, int32_t Cin, fl
     return n3 + n2;
 }
 
+static int debug_conv1d_impl(int device, const float* x, int32_t Cin, int32_t L, const float* w, const float* bias, int32_t Cout,
+                             int32_t k, int32_t pad, int32_t dil, int32_t stride_t, int32_t depthwise, float in_slope,
+                             int32_t in_act, int mode, float** y_out, int32_t* Lout_out, int32_t iters, float* ms_out,
+                             const int32_t* lengths, int32_t B, uint32_t* ovf_out);
+
 int sts_debug_conv1d(int device, const float* x, int32_t Cin, int32_t L, const float* w, const float* bias, int32_t Cout,
                      int32_t k, int32_t pad, int32_t dil, int32_t stride_t, int32_t depthwise, float in_slope, int32_t in_act,
                      int mode, float** y_out, int32_t* Lout_out) {
@@ -471,11 +476,47 @@ int sts_debug_conv1d(int device, const float* x, int32_t Cin, int32_t L, const f
 int sts_debug_conv1d_bench(int device, const float* x, int32_t Cin, int32_t L, const float* w, const float* bias, int32_t Cout,
                            int32_t k, int32_t pad, int32_t dil, int32_t stride_t, int32_t depthwise, float in_slope,
                            int32_t in_act, int mode, float** y_out, int32_t* Lout_out, int32_t iters, float* ms_out) {
+    return debug_conv1d_impl(device, x, Cin, L, w, bias, Cout, k, pad, dil, stride_t, depthwise, in_slope, in_act, mode, y_out, Lout_out,
+                             iters, ms_out, nullptr, 1, nullptr);
+}
+
+int sts_debug_conv1d_packed(int device, const float* x, int32_t Cin, int32_t L, const float* w, const float* bias, int32_t Cout,
+                            int32_t k, int32_t pad, int32_t dil, int32_t stride_t, int32_t depthwise, float in_slope,
+                            int32_t in_act, int mode, float** y_out, int32_t* Lout_out, const int32_t* lengths, int32_t B, uint32_t* ovf_out) {
+    if (!lengths) return set_err(STS_EINVAL, "packed conv: null segment lengths");
+    return debug_conv1d_impl(device, x, Cin, L, w, bias, Cout, k, pad, dil, stride_t, depthwise, in_slope, in_act, mode, y_out, Lout_out,
+                             0, nullptr, lengths, B, ovf_out);
+}
+
+// lengths == null: one segment of L positions (the stand-alone entries); else B segments packed back to back, as the engine packs a batch
+static int debug_conv1d_impl(int device, const float* x, int32_t Cin, int32_t L, const float* w, const float* bias, int32_t Cout,
+                             int32_t k, int32_t pad, int32_t dil, int32_t stride_t, int32_t depthwise, float in_slope,
+                             int32_t in_act, int mode, float** y_out, int32_t* Lout_out, int32_t iters, float* ms_out,
+                             const int32_t* lengths, int32_t B, uint32_t* ovf_out) {
     if (!x || !w || !y_out || !Lout_out || Cin <= 0 || Cout <= 0 || L <= 0 || k <= 0) return set_err(STS_EINVAL, "bad conv arguments");
+    const bool tr = stride_t > 0;
+    const bool packed = lengths != nullptr;
+    int maxlen = L;
+    std::vector<int> tab;
+    if (packed) {
+        if (B <= 0 || dil < 1) return set_err(STS_EINVAL, "packed conv: B >= 1 segments and dil >= 1");
+        int64_t total = 0;
+        maxlen = 0;
+        tab.assign((size_t)2 * B, 0);
+        for (int b = 0; b < B; b++) {
+            if (lengths[b] <= 0) return set_err(STS_EINVAL, "packed conv: every segment length must be positive");
+            tab[b] = (int)total; tab[B + b] = lengths[b];
+            total += lengths[b]; maxlen = std::max(maxlen, (int)lengths[b]);
+        }
+        if (total != L) return set_err(STS_EINVAL, "packed conv: L must equal the sum of the segment lengths");
+        if (total * (tr ? stride_t : 1) > (int64_t)1 << 26) return set_err(STS_EINVAL, "packed conv: at most 2^26 output positions");
+        // the geometries the engine launches on packed buffers: output segment = input segment (x stride)
+        if (tr ? (k < stride_t || ((k - stride_t) & 1) || pad != (k - stride_t) / 2 || dil != 1) : (!(k & 1) || pad != dil * (k - 1) / 2))
+            return set_err(STS_EINVAL, "packed conv: 'same' padding (odd k, pad = dil (k - 1) / 2) or a transposed conv with pad = (k - stride) / 2");
+    }
     int count = 0;
     if (hipGetDeviceCount(&count) != hipSuccess || count <= 0) return set_err(STS_EDEVICE, "no HIP device visible (no CPU fallback)");
     if (hipSetDevice(device) != hipSuccess) return set_err(STS_EDEVICE, "hipSetDevice failed");
-    const bool tr = stride_t > 0;
     const int Lout = tr ? (L - 1) * stride_t - 2 * pad + (k - 1) + 1 : L + 2 * pad - dil * (k - 1);
     if (Lout <= 0) return set_err(STS_EINVAL, "empty output");
     auto r_up = [](int v, int m) { return (v + m - 1) / m * m; };
@@ -537,7 +578,7 @@ int sts_debug_conv1d_bench(int device, const float* x, int32_t Cin, int32_t L, c
     int seg[2] = {0, 1};
     bool ok = hipMalloc((void**)&dx, (size_t)Cin * L * 4) == hipSuccess && hipMalloc((void**)&dw, (wn + 1024) * 4) == hipSuccess &&
               hipMalloc((void**)&db, bp.size() * 4) == hipSuccess && hipMalloc((void**)&dy, (size_t)Cout * Lout * 4) == hipSuccess &&
-              hipMalloc((void**)&dseg, 32) == hipSuccess;
+              hipMalloc((void**)&dseg, 32 + tab.size() * 4) == hipSuccess;
     int rc = STS_OK;
     if (ok && !wu.empty()) ok = hipMalloc((void**)&dwu, (wu.size() + 1024) * 4) == hipSuccess;
     if (ok && bf3) ok = hipMalloc(&dwb3, wb3.size() + 4096) == hipSuccess;
@@ -546,9 +587,11 @@ int sts_debug_conv1d_bench(int device, const float* x, int32_t Cin, int32_t L, c
         (void)hipMemcpy(dx, x, (size_t)Cin * L * 4, hipMemcpyHostToDevice);
         (void)hipMemcpy(dw, wp.data(), wn * 4, hipMemcpyHostToDevice);
         (void)hipMemcpy(db, bp.data(), bp.size() * 4, hipMemcpyHostToDevice);
-        (void)hipMemset(dseg, 0, 32);
+        (void)hipMemset(dseg, 0, 32 + tab.size() * 4);
         (void)hipMemcpy(dseg, seg, 8, hipMemcpyHostToDevice);
-        (void)hipMemset(dy, 0, (size_t)Cout * Lout * 4);
+        if (packed) (void)hipMemcpy(dseg + 8, tab.data(), tab.size() * 4, hipMemcpyHostToDevice);
+        // packed: a NaN pattern instead of zeros, so that a position no workgroup writes cannot pass
+        (void)hipMemset(dy, packed ? 0xFF : 0, (size_t)Cout * Lout * 4);
         ConvArgs a;
         memset(&a, 0, sizeof(a));
         a.x = dx; a.x_ld = L; a.y = dy; a.y_ld = Lout; a.w = dw; a.bias = bias ? db : nullptr;
@@ -559,6 +602,10 @@ int sts_debug_conv1d_bench(int device, const float* x, int32_t Cin, int32_t L, c
         a.in_act = in_act; a.in_slope = in_slope; a.epi = EPI_STORE;
         // segment lengths in base units: in = L, out = Lout -> two views over the same {off=0,len=1} table
         a.in_seg = SegView{dseg, dseg + 1, L, 0}; a.out_seg = SegView{dseg, dseg + 1, Lout, 0}; a.B = 1;
+        if (packed) {     // real offset / length tables of B entries (behind the overflow word), output scale = stride
+            a.in_seg = SegView{dseg + 8, dseg + 8 + B, 1, 0}; a.out_seg = SegView{dseg + 8, dseg + 8 + B, tr ? stride_t : 1, 0}; a.B = B;
+            a.max_n = tr ? maxlen + J - 1 : maxlen;
+        }
         if (dwu) { (void)hipMemcpy(dwu, wu.data(), wu.size() * 4, hipMemcpyHostToDevice); a.wu = dwu; a.wino_n3 = wn3; a.wino_n2 = wn2; }
         if (dwb3) { (void)hipMemcpy(dwb3, wb3.data(), wb3.size(), hipMemcpyHostToDevice); a.wb3 = dwb3; }
         if (h2) { a.math = 1; a.wscale = h2_scale; a.ovf = (unsigned*)dseg + 4; }     // (overflow word: behind the segment table)
@@ -591,6 +638,7 @@ int sts_debug_conv1d_bench(int device, const float* x, int32_t Cin, int32_t L, c
             float* y = (float*)malloc((size_t)Cout * Lout * 4);
             (void)hipMemcpy(y, dy, (size_t)Cout * Lout * 4, hipMemcpyDeviceToHost);
             *y_out = y; *Lout_out = Lout;
+            if (ovf_out) { *ovf_out = 0; if (h2) (void)hipMemcpy(ovf_out, dseg + 4, 4, hipMemcpyDeviceToHost); }
         }
     }
     (void)hipFree(dx); (void)hipFree(dw); (void)hipFree(db); (void)hipFree(dy); (void)hipFree(dseg); if (dwu) (void)hipFree(dwu); if (dwb3) (void)hipFree(dwb3);
@@ -599,11 +647,47 @@ int sts_debug_conv1d_bench(int device, const float* x, int32_t Cin, int32_t L, c
 
 // One "same"-padded conv through the pre-split path (conv_h2p.hip): x fp32 [Cin][L] -> split_planes -> conv_h2p_group (`members` identical
 // members in one grid; member 0 is returned) -> all three output forms decoded to fp32 [Cout][L] on the host.
+static int debug_conv_h2p_impl(int device, const float* x, int32_t Cin, int32_t L, const float* w, const float* bias, int32_t Cout, int32_t k, int32_t dil,
+                              const float* res, float in_slope, float out_slope, int tile, int members, float* y_out, float* y16_out, float* yp_out,
+                              int32_t iters, float* ms_out, const int32_t* lengths, int32_t B, uint32_t* ovf_out);
+
 int sts_debug_conv_h2p(int device, const float* x, int32_t Cin, int32_t L, const float* w, const float* bias, int32_t Cout, int32_t k, int32_t dil,
                        const float* res, float in_slope, float out_slope, int tile, int members, float* y_out, float* y16_out, float* yp_out,
                        int32_t iters, float* ms_out) {
+    return debug_conv_h2p_impl(device, x, Cin, L, w, bias, Cout, k, dil, res, in_slope, out_slope, tile, members, y_out, y16_out, yp_out, iters, ms_out,
+                               nullptr, 1, nullptr);
+}
+
+// The same conv on B segments packed back to back (L = their sum): split_planes and conv_h2p_group both get the B-entry segment table and
+// max_n = the longest segment; the plane and output buffers start out as a NaN pattern.
+int sts_debug_conv_h2p_packed(int device, const float* x, int32_t Cin, int32_t L, const float* w, const float* bias, int32_t Cout, int32_t k, int32_t dil,
+                              const float* res, float in_slope, float out_slope, int tile, int members, float* y_out, float* y16_out, float* yp_out,
+                              const int32_t* lengths, int32_t B, uint32_t* ovf_out) {
+    if (!lengths) return set_err(STS_EINVAL, "packed conv: null segment lengths");
+    return debug_conv_h2p_impl(device, x, Cin, L, w, bias, Cout, k, dil, res, in_slope, out_slope, tile, members, y_out, y16_out, yp_out, 0, nullptr,
+                               lengths, B, ovf_out);
+}
+
+static int debug_conv_h2p_impl(int device, const float* x, int32_t Cin, int32_t L, const float* w, const float* bias, int32_t Cout, int32_t k, int32_t dil,
+                              const float* res, float in_slope, float out_slope, int tile, int members, float* y_out, float* y16_out, float* yp_out,
+                              int32_t iters, float* ms_out, const int32_t* lengths, int32_t B, uint32_t* ovf_out) {
     if (!x || !w || Cin <= 0 || Cout <= 0 || L <= 0 || k <= 0 || !(k & 1) || dil < 1 || members < 1 || members > kMaxGroup) return set_err(STS_EINVAL, "bad conv arguments");
     if (Cin % 16 || Cout % 32) return set_err(STS_EINVAL, "pre-split conv: Cin % 16 == 0 and Cout % 32 == 0");
+    const bool packed = lengths != nullptr;
+    int maxlen = L;
+    std::vector<int> tab;
+    if (packed) {
+        if (B <= 0) return set_err(STS_EINVAL, "packed conv: B >= 1 segments");
+        int64_t total = 0;
+        maxlen = 0;
+        tab.assign((size_t)2 * B, 0);
+        for (int b = 0; b < B; b++) {
+            if (lengths[b] <= 0) return set_err(STS_EINVAL, "packed conv: every segment length must be positive");
+            tab[b] = (int)total; tab[B + b] = lengths[b];
+            total += lengths[b]; maxlen = std::max(maxlen, (int)lengths[b]);
+        }
+        if (total != L) return set_err(STS_EINVAL, "packed conv: L must equal the sum of the segment lengths");
+    }
     int count = 0;
     if (hipGetDeviceCount(&count) != hipSuccess || count <= 0) return set_err(STS_EDEVICE, "no HIP device visible (no CPU fallback)");
     if (hipSetDevice(device) != hipSuccess) return set_err(STS_EDEVICE, "hipSetDevice failed");
@@ -616,9 +700,10 @@ int sts_debug_conv_h2p(int device, const float* x, int32_t Cin, int32_t L, const
     bf3_pack(wp.data(), 1, k, Cin, Cout, wb.data(), true, 1, &wscale);
     const size_t in_b = (size_t)Cin * L * 4, out_b = (size_t)Cout * L * 4;
     float *dx = nullptr, *db = nullptr, *dres = nullptr, *dres16 = nullptr; void *dxp = nullptr, *dwb = nullptr, *dtmp = nullptr; unsigned* dovf = nullptr;
-    float* dy[kMaxGroup] = {}; float* dy16[kMaxGroup] = {}; void* dyp[kMaxGroup] = {};
+    float* dy[kMaxGroup] = {}; float* dy16[kMaxGroup] = {}; void* dyp[kMaxGroup] = {}; int* dtab = nullptr;
     bool ok = hipMalloc((void**)&dx, in_b) == hipSuccess && hipMalloc(&dxp, in_b) == hipSuccess && hipMalloc(&dwb, wb.size() + 8192) == hipSuccess &&
               hipMalloc((void**)&db, (size_t)Cout * 4) == hipSuccess && hipMalloc((void**)&dovf, 64) == hipSuccess;
+    if (ok && packed) ok = hipMalloc((void**)&dtab, tab.size() * 4) == hipSuccess;
     if (ok && res) ok = hipMalloc((void**)&dres, out_b) == hipSuccess && hipMalloc((void**)&dres16, out_b) == hipSuccess && hipMalloc(&dtmp, out_b) == hipSuccess;
     for (int m = 0; m < members && ok; m++)
         ok = hipMalloc((void**)&dy[m], out_b) == hipSuccess && hipMalloc((void**)&dy16[m], out_b) == hipSuccess && hipMalloc(&dyp[m], out_b) == hipSuccess;
@@ -630,15 +715,24 @@ int sts_debug_conv_h2p(int device, const float* x, int32_t Cin, int32_t L, const
         (void)hipMemset(db, 0, (size_t)Cout * 4);
         if (bias) (void)hipMemcpy(db, bias, (size_t)Cout * 4, hipMemcpyHostToDevice);
         (void)hipMemset(dovf, 0, 64);
-        const SegView whole{nullptr, nullptr, 1, 0, 0, L};
-        split_planes(dx, L, Cin, whole, 1, L, in_slope, dxp, nullptr, L, dovf, nullptr);
+        SegView whole{nullptr, nullptr, 1, 0, 0, L};
+        int nb = 1;
+        if (packed) {     // a real table of B entries; every buffer the kernels write starts out as NaNs (fp32 and fp16 alike)
+            (void)hipMemcpy(dtab, tab.data(), tab.size() * 4, hipMemcpyHostToDevice);
+            whole = SegView{dtab, dtab + B, 1, 0, 0, 0};
+            nb = B;
+            (void)hipMemset(dxp, 0xFF, in_b);
+            if (res) { (void)hipMemset(dres16, 0xFF, out_b); (void)hipMemset(dtmp, 0xFF, out_b); }
+            for (int m = 0; m < members; m++) { (void)hipMemset(dy[m], 0xFF, out_b); (void)hipMemset(dy16[m], 0xFF, out_b); (void)hipMemset(dyp[m], 0xFF, out_b); }
+        }
+        split_planes(dx, L, Cin, whole, nb, maxlen, in_slope, dxp, nullptr, L, dovf, nullptr);
         if (res) {
             (void)hipMemcpy(dres, res, out_b, hipMemcpyHostToDevice);
-            split_planes(dres, L, Cout, whole, 1, L, 1.0f, dtmp, dres16, L, nullptr, nullptr);
+            split_planes(dres, L, Cout, whole, nb, maxlen, 1.0f, dtmp, dres16, L, nullptr, nullptr);
         }
         H2PGroup G;
         memset(&G, 0, sizeof(G));
-        G.n = members; G.seg = SegView{nullptr, nullptr, 1, 0, 0, L}; G.B = 1; G.max_n = L; G.ovf = dovf;
+        G.n = members; G.seg = whole; G.B = nb; G.max_n = maxlen; G.ovf = dovf;
         for (int m = 0; m < members; m++) {
             H2PArgs& a = G.g[m];
             a.xp = dxp; a.xp_ld = L; a.wb = dwb; a.wscale = wscale; a.bias = bias ? db : nullptr; a.res16 = dres16; a.res_ld = L;
@@ -666,6 +760,7 @@ int sts_debug_conv_h2p(int device, const float* x, int32_t Cin, int32_t L, const
         }
         if (rc == STS_OK) {
             if (y_out) (void)hipMemcpy(y_out, dy[0], out_b, hipMemcpyDeviceToHost);
+            if (ovf_out) (void)hipMemcpy(ovf_out, dovf, 4, hipMemcpyDeviceToHost);
             std::vector<float> t16((size_t)Cout * L);
             std::vector<uint16_t> tp((size_t)Cout * L * 2);
             (void)hipMemcpy(t16.data(), dy16[0], out_b, hipMemcpyDeviceToHost);
@@ -683,7 +778,7 @@ int sts_debug_conv_h2p(int device, const float* x, int32_t Cin, int32_t L, const
             }
         }
     }
-    (void)hipFree(dx); (void)hipFree(dxp); (void)hipFree(dwb); (void)hipFree(db); (void)hipFree(dovf);
+    (void)hipFree(dx); (void)hipFree(dxp); (void)hipFree(dwb); (void)hipFree(db); (void)hipFree(dovf); if (dtab) (void)hipFree(dtab);
     if (dres) (void)hipFree(dres); if (dres16) (void)hipFree(dres16); if (dtmp) (void)hipFree(dtmp);
     for (int m = 0; m < kMaxGroup; m++) { if (dy[m]) (void)hipFree(dy[m]); if (dy16[m]) (void)hipFree(dy16[m]); if (dyp[m]) (void)hipFree(dyp[m]); }
     return rc;

@@ -1152,8 +1152,11 @@ static void launch_mfma(const ConvArgs& a, int nphase, hipStream_t st) {
     hipLaunchKernelGGL((conv_mfma_kernel<MW, NW, WM, WN>), dim3(mapped_grid(nx, ny, a.B)), dim3(WM * WN * 64), lds, st, a, mt, nx, ny);
 }
 
+// pinned: the caller named this kernel (tile code 6 / 7) instead of leaving the choice to conv_mfma.  The number of waves K is split over
+// fixes the order a value's products are summed in, so a pinned launch takes it from the conv's own K alone, never from the size of the
+// grid: an utterance's values then do not depend on what it is batched with (the automatic path keeps weighing K against the grid).
 template <int MW, int NW>
-static void launch_splitk(const ConvArgs& a, int nphase, hipStream_t st) {
+static void launch_splitk(const ConvArgs& a, int nphase, hipStream_t st, bool pinned = false) {
     const int mt = (a.Cout_pad + 32 * MW - 1) / (32 * MW);
     const int nt = (a.max_n + 32 * NW - 1) / (32 * NW);
     const int nsl = a.kslices > 1 ? a.kslices : 1;
@@ -1161,11 +1164,11 @@ static void launch_splitk(const ConvArgs& a, int nphase, hipStream_t st) {
     constexpr int E = MW * NW * 16;
     // LDS for the partial tiles: <= 64 KiB normally; a grid that cannot even give every CU one workgroup may take
     // 128 KiB (16 waves on a two-tile workgroup: half the dependent L2/HBM round trips per wave)
-    const bool sparse = (long)mt * nt * nphase * a.B * nsl <= 256;
+    const bool sparse = !pinned && (long)mt * nt * nphase * a.B * nsl <= 256;
     const int ks_cap = E <= 16 ? 16 : (E <= 32 ? (sparse ? 16 : 8) : 4);
     // enough waves that each one issues >= ~6 groups (24 MFMA rounds), but do not drown the chip
     int ks = 1;
-    while (ks < ks_cap && steps / (ks * 2) >= 6 && (long)mt * nt * nphase * a.B * nsl * ks * 2 <= 4096) ks *= 2;
+    while (ks < ks_cap && steps / (ks * 2) >= 6 && (pinned || (long)mt * nt * nphase * a.B * nsl * ks * 2 <= 4096)) ks *= 2;
     dim3 grid(nt, mt * nphase, a.B * nsl);
     size_t lds = (size_t)ks * E * 64 * sizeof(float);
     hipLaunchKernelGGL((conv_mfma_splitk_kernel<MW, NW>), grid, dim3(ks * 64), lds, st, a, mt);
@@ -1318,7 +1321,8 @@ void conv_mfma_group(const ConvGroup& Gin, hipStream_t st, int tile) {
 void conv_mfma(const ConvArgs& a, hipStream_t st, int tile) {
     int nphase = a.transposed ? a.out_stride : 1;
     if (a.max_n <= 0 || a.B <= 0) return;
-    bool splitk = tile == 6 || tile == 7 || a.kslices > 1;
+    const bool pinned = tile == 6 || tile == 7;
+    bool splitk = pinned || a.kslices > 1;
     int nw = tile == 7 ? 2 : 1;
     if (a.kslices > 1 && tile != 7) tile = 6;
     if (tile < 0 || tile > 7) {
@@ -1336,7 +1340,7 @@ void conv_mfma(const ConvArgs& a, hipStream_t st, int tile) {
         else if (a.ntap == 1 && !a.transposed && a.Cin_pad <= 256 && fits32) { splitk = true; nw = 1; }
     }
     if (splitk) {
-        if (nw == 2) launch_splitk<1, 2>(a, nphase, st); else launch_splitk<1, 1>(a, nphase, st);
+        if (nw == 2) launch_splitk<1, 2>(a, nphase, st, pinned); else launch_splitk<1, 1>(a, nphase, st, pinned);
         return;
     }
     switch (tile) {

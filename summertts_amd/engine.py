@@ -183,7 +183,7 @@ EXPORTED_SYMBOLS = [
     "sts_create", "sts_destroy", "sts_speaker_num", "sts_get_info", "sts_infer_ids", "sts_infer_ids_batch",
     "sts_run_batch", "sts_copy_pcm_device", "sts_copy_pcm_host", "sts_pcm_host_view", "sts_set_forced_durations",
     "sts_set_record_taps", "sts_get_tap", "sts_get_durations", "sts_set_conv_mode", "sts_set_conv_math", "sts_set_profiling",
-    "sts_get_profile", "sts_set_host_pcm", "sts_debug_conv1d", "sts_debug_conv1d_bench", "sts_debug_conv_h2p", "sts_debug_conv_h2w", "sts_free", "sts_last_error",
+    "sts_get_profile", "sts_set_host_pcm", "sts_debug_conv1d", "sts_debug_conv1d_bench", "sts_debug_conv1d_packed", "sts_debug_conv_h2p", "sts_debug_conv_h2p_packed", "sts_debug_conv_h2w", "sts_free", "sts_last_error",
     "sts_infer_ids_stream", "sts_stream_halo_frames", "sts_debug_wino_pack", "sts_debug_set", "sts_multi_create_ex", "sts_multi_gather_mode", "sts_multi_gather_layout",
     "sts_pool_create", "sts_pool_destroy", "sts_pool_submit", "sts_pool_wait", "sts_pool_stats", "sts_pool_last_error",
     "sts_multi_create", "sts_multi_destroy", "sts_multi_device_count", "sts_multi_speaker_num", "sts_multi_infer_ids_batch",
@@ -637,6 +637,52 @@ def debug_conv_h2p(x: np.ndarray, w: np.ndarray, bias: Optional[np.ndarray], dil
                                        None if r is None else r.ctypes.data, in_slope, out_slope, tile, members, y.ctypes.data,
                                        y16.ctypes.data, yp.ctypes.data, iters, C.byref(ms)))
     return y, y16, yp, float(ms.value)     # (iters < 0: |iters| timed launches WITHOUT the fp32 [C][L] output: a layer's second conv as the engine runs it)
+
+
+def debug_conv1d_packed(x: np.ndarray, lengths, w: np.ndarray, bias: Optional[np.ndarray], dil: int = 1, stride_transposed: int = 0,
+                        depthwise: bool = False, in_slope: float = 0.0, in_act: int = 0, mode: int = 0, device: int = 0, return_ovf: bool = False):
+    """One conv on utterances packed back to back along the time axis (sts_debug_conv1d_packed).  x: [Cin, sum(lengths)]; w: [Cout, k, Cin].
+    'Same' padding (odd k), or a transposed conv with pad = (k - stride) / 2: the output holds the segments in the same order, each
+    stride times as long.  return_ovf: also the overflow word of the two-term fp16 kernels."""
+    lib = load_library()
+    x = np.ascontiguousarray(x, np.float32)
+    w = np.ascontiguousarray(w, np.float32)
+    ln = np.ascontiguousarray(lengths, np.int32)
+    cout, k = w.shape[0], w.shape[1]
+    pad = (k - stride_transposed) // 2 if stride_transposed else dil * (k - 1) // 2
+    b = None if bias is None else np.ascontiguousarray(bias, np.float32)
+    y = C.POINTER(C.c_float)()
+    lout = C.c_int32()
+    ovf = C.c_uint32(0)
+    lib.sts_debug_conv1d_packed.argtypes = lib.sts_debug_conv1d.argtypes + [C.c_void_p, C.c_int32, C.POINTER(C.c_uint32)]
+    _check(lib, lib.sts_debug_conv1d_packed(device, x.ctypes.data, x.shape[0], x.shape[1], w.ctypes.data, None if b is None else b.ctypes.data,
+                                            cout, k, pad, dil, stride_transposed, 1 if depthwise else 0, in_slope, in_act, mode,
+                                            C.byref(y), C.byref(lout), ln.ctypes.data, ln.size, C.byref(ovf)))
+    out = np.ctypeslib.as_array(y, shape=(cout, lout.value)).copy()
+    lib.sts_free(y)
+    return (out, int(ovf.value)) if return_ovf else out
+
+
+def debug_conv_h2p_packed(x: np.ndarray, lengths, w: np.ndarray, bias: Optional[np.ndarray], dil: int = 1, res: Optional[np.ndarray] = None,
+                          in_slope: float = 0.1, out_slope: float = 0.1, tile: int = -1, members: int = 1, device: int = 0):
+    """debug_conv_h2p on utterances packed back to back (sts_debug_conv_h2p_packed).  x, res: [C, sum(lengths)].  Returns (y, y16, yp, ovf)."""
+    lib = load_library()
+    x = np.ascontiguousarray(x, np.float32)
+    w = np.ascontiguousarray(w, np.float32)
+    ln = np.ascontiguousarray(lengths, np.int32)
+    cout, k = w.shape[0], w.shape[1]
+    b = None if bias is None else np.ascontiguousarray(bias, np.float32)
+    r = None if res is None else np.ascontiguousarray(res, np.float32)
+    L = x.shape[1]
+    y = np.zeros((cout, L), np.float32); y16 = np.zeros((cout, L), np.float32); yp = np.zeros((cout, L), np.float32)
+    ovf = C.c_uint32(0)
+    lib.sts_debug_conv_h2p_packed.argtypes = [C.c_int, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
+                                              C.c_void_p, C.c_float, C.c_float, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                              C.c_void_p, C.c_int32, C.POINTER(C.c_uint32)]
+    _check(lib, lib.sts_debug_conv_h2p_packed(device, x.ctypes.data, x.shape[0], L, w.ctypes.data, None if b is None else b.ctypes.data, cout, k, dil,
+                                              None if r is None else r.ctypes.data, in_slope, out_slope, tile, members, y.ctypes.data,
+                                              y16.ctypes.data, yp.ctypes.data, ln.ctypes.data, ln.size, C.byref(ovf)))
+    return y, y16, yp, int(ovf.value)
 
 
 def debug_conv_h2w(x: np.ndarray, w: np.ndarray, bias: Optional[np.ndarray], dil: int = 1, res: Optional[np.ndarray] = None,

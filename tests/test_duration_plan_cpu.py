@@ -109,12 +109,13 @@ def _arg_count(name, src):
     return len([a for a in m.group(1).split(",") if a.strip()])
 
 
-def test_header_says_14_and_the_library_agrees(lib, tmp_path):
+def test_header_says_15_and_the_library_agrees(lib, tmp_path):
     src = open(HEADER).read()
-    assert re.search(r"#define STS_ABI_VERSION (\d+)", src).group(1) == "14" and lib.sts_abi_version() == 14
+    assert re.search(r"#define STS_ABI_VERSION (\d+)", src).group(1) == "15" and lib.sts_abi_version() == 15
     code = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
     for name, nargs in (("sts_set_duration_plan", 4), ("sts_duration_fit", 5), ("sts_duration_plan_apply", 7), ("sts_get_phoneme_offsets", 3),
-                        ("sts_pool_submit_plan", 11), ("sts_multi_set_duration_plan", 4)):
+                        ("sts_pool_submit_plan", 11), ("sts_multi_set_duration_plan", 4),
+                        ("sts_debug_conv1d_packed", 20), ("sts_debug_conv_h2p_packed", 20)):       # ABI 15: the packed stand-alone conv entries
         assert hasattr(lib, name) and name in engine.EXPORTED_SYMBOLS, name
         assert _arg_count(name, code) == nargs, name
     # the plan struct as the C compiler lays it out, its ctypes mirror, and sts_profile's pinned size

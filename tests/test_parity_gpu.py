@@ -470,7 +470,9 @@ def test_full_size_properties(kind):
 
 def test_long_utterance_and_big_ragged_batch():
     """test/main.cpp joins a whole file into ONE utterance: T in the thousands must work (attention keeps a
-    T-long probability row in LDS), and so must a large ragged batch in one call."""
+    T-long probability row in LDS), and so must a large ragged batch in one call.  Of the 200 members every 4th (and the last, and 57) is
+    compared with the oracle: the oracle for all 200 takes 5.4 s of CPU time, more than the rest of this test (T = 1500 oracle 2.1 s + the GPU
+    runs); for 52 members it takes 1.4 s."""
     cfg = sb.tiny_cfg("hifigan_fix")
     blob = sb.make_blob(cfg, 5)
     syn = engine.Synthesizer(blob)
@@ -485,7 +487,7 @@ def test_long_utterance_and_big_ragged_batch():
     batch_ids = [sb.synthetic_ids(int(t), cfg.vocab, salt=i) for i, t in enumerate(lens)]
     out = syn.infer_batch(batch_ids)
     assert len(out) == 200
-    for i in (0, 57, 199):
+    for i in sorted(set(range(0, 200, 4)) | {57, 199}):
         assert_pcm_close(out[i], port.infer_ids(batch_ids[i], 0, 1.0)["pcm"], f"utt {i} of 200")
     with pytest.raises(engine.StsError):
         syn.infer_ids(sb.synthetic_ids(60000, cfg.vocab), 0, 1.0)   # beyond the attention kernel's LDS row
