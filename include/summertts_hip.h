@@ -286,6 +286,44 @@ int sts_duration_plan_apply(int device, const float* w, const int32_t* fixed, co
  * samples_per_frame at the native rate) -- the convention of a streaming chunk's sample_offset.  Host arithmetic; after any call form, with
  * or without a plan. */
 int sts_get_phoneme_offsets(sts_engine* e, int64_t* start, int64_t capacity);
+/* ---- speaker blending (no reference counterpart: SynthesizerTrn::infer takes one sid, a row of emb_g).  sts_set_speaker_mix(e, B, mixes)
+ * gives utterance b of the NEXT call the conditioning vector g of mixes[b] instead of row sid[b] of the model's table.  With
+ * E[s][c] = emb_g[c * speaker_num + s] (the blob's layout, [gin_channels][speaker_num]) and gin = gin_channels, for every channel c:
+ *     acc_c = 0.0 (float64)
+ *     for k = 0 .. K-1 in order:  acc_c += (double)weight[k] * (double)E[sid[k]][c]
+ *     if vector != NULL:          acc_c += (double)vector_weight * (double)vector[c]
+ *     g_c = (float)acc_c          (one rounding, to nearest even)
+ * Each product of two fp32 values is exact in float64, so the result does not depend on whether the compiler contracts to an FMA.
+ * K = 1, weight = 1, vector = NULL gives g = E[sid[0]] exactly: the plain-sid result, bit for bit.  K = 0, vector_weight = 1 gives g = vector
+ * exactly.  Weights are used as given: not normalised, negative weights (an extrapolation) allowed.  Denormal results are not part of the
+ * contract.
+ * The mix is copied and applies to the next run only, whatever that run's outcome (the lifetime of a duration plan), in every call form:
+ * sts_infer_ids, sts_infer_ids_batch, sts_run_batch, sts_infer_ids_stream, sts_infer_ids_batch_stream.  That run must have the same B:
+ * otherwise it answers STS_EINVAL, nothing runs and the mix is dropped.  B == 0 or mixes == NULL drops a pending mix.  An invalid mix (the
+ * rules in the struct below; sts_speaker_mix_check) answers STS_EINVAL at the set call and changes nothing; a single-speaker model answers
+ * STS_EINVAL for any non-empty mix.  An utterance whose entry is empty (k == 0, vector == NULL) is synthesised with its sid[b] as without a
+ * mix, bit for bit; a call with no mix pending launches and uploads nothing new.  A mixed call launches the blend kernel in place of the
+ * speaker gather and its term table rides in the run's one upload.  A mix is independent of forced durations, duration plans, noise,
+ * output rate, loudness and limiter; a run with a mix neither reads nor feeds the launch-ahead memo (STS_DBG_LAUNCH_AHEAD). */
+typedef struct sts_speaker_mix {
+    int32_t        k;              /* 0..16 table terms; k == 0 and vector == NULL: no mix, the call's sid[b] applies */
+    const int32_t* sid;            /* [k] rows, each in [0, speaker_num) -- out of range is STS_EINVAL here, not "-> 0" */
+    const float*   weight;         /* [k] finite, |w| <= 16 */
+    const float*   vector;         /* NULL or [gin_channels] finite: a caller's own embedding */
+    float          vector_weight;  /* finite, |w| <= 16; read only when vector != NULL */
+} sts_speaker_mix;
+int sts_set_speaker_mix(sts_engine* e, int32_t B, const sts_speaker_mix* mixes);
+/* Host only (no device): the validity rules above for B entries against a table of speaker_num rows of gin floats (speaker_num 0 = a
+ * single-speaker model: only empty entries pass). */
+int sts_speaker_mix_check(int32_t speaker_num, int32_t gin, int32_t B, const sts_speaker_mix* mixes);
+/* Row sid of the model's table as gin_channels floats (what a mix with k = 1, weight 1 produces).  STS_EINVAL: a single-speaker model, sid
+ * outside [0, speaker_num), capacity below gin_channels. */
+int sts_get_speaker_embedding(const sts_engine* e, int32_t sid, float* out, int64_t capacity);
+/* The same kernel on a caller's table (host memory, the blob's layout [gin][speaker_num]), like sts_limiter_apply: g_out [B][gin] receives
+ * utterance b's vector.  sid ([B] or NULL = all 0): the row an EMPTY entry takes (outside [0, speaker_num) -> 0, as a plain call);
+ * mixes == NULL: every entry is empty. */
+int sts_speaker_blend(int device, const float* table, int32_t speaker_num, int32_t gin, int32_t B, const int32_t* sid,
+                      const sts_speaker_mix* mixes, float* g_out);
 /*   record intermediate tensors of the next run: "x_enc","m","logs","logw","z_p","z","wave","wave_out" ("logs": the second half of the
  *   encoder projection, computed only by runs that record taps or sample the prior; "wave_out": the resampled float wave, only at a
  *   non-native output rate, one-pass calls; "dur_w": the planned duration weights, only a run with a duration plan) */
@@ -477,6 +515,10 @@ int sts_pool_set_limiter(sts_pool* p, int mode, float gain_db, float ceiling_dbf
  *   without a plan share one packed batch: the plan is per utterance. */
 int64_t sts_pool_submit_plan(sts_pool* p, const int32_t* ids, int32_t n, int32_t sid, float length_scale, float noise_scale,
                              float noise_scale_w, uint64_t seed, const float* rate, const int32_t* fixed, int32_t target_frames);
+/*   sts_pool_submit_mix: sts_pool_submit_ex with this request's own speaker mix (sts_set_speaker_mix; copied; NULL or an empty entry = the
+ *   plain sid; an invalid mix answers STS_EINVAL).  Whole-utterance requests only.  Mixed and plain requests share one packed batch. */
+int64_t sts_pool_submit_mix(sts_pool* p, const int32_t* ids, int32_t n, int32_t sid, float length_scale, float noise_scale,
+                            float noise_scale_w, uint64_t seed, const sts_speaker_mix* mix);
 
 /* ---- multi-device batch (no reference counterpart).  One host process drives n_devices GPUs:
  * one engine (weights replicated) and one worker thread per entry of `devices` (HIP device indices; an index may repeat,
@@ -517,6 +559,10 @@ int sts_multi_set_limiter(sts_multi* m, int mode, float gain_db, float ceiling_d
  *   same B and n[b] (otherwise STS_EINVAL and nothing runs).  plans[b] belongs to utterance b of the caller's batch and follows it into its
  *   device's shard: the PCM does not depend on the number of devices. */
 int sts_multi_set_duration_plan(sts_multi* m, int32_t B, const int32_t* n, const sts_dur_plan* plans);
+/*   sts_multi_set_speaker_mix: sts_set_speaker_mix for the NEXT sts_multi_infer_ids_batch of the handle, which must have the same B
+ *   (otherwise STS_EINVAL, nothing runs and the mix is dropped).  mixes[b] belongs to utterance b of the caller's batch and follows it into
+ *   its device's shard: the PCM does not depend on the number of devices. */
+int sts_multi_set_speaker_mix(sts_multi* m, int32_t B, const sts_speaker_mix* mixes);
 /*   test hook: the shared library that provides the nccl* entry points (NULL / "" = librccl.so.1) and whether STS_MULTI_RCCL may list
  *   one device several times (tests/fake_rccl: N emulated ranks on one GPU; real RCCL refuses duplicates).  Only before the first
  *   STS_MULTI_RCCL handle of the process is created.  TEST-ONLY: refused with STS_ESTATE unless the process environment carries

@@ -213,6 +213,62 @@ int sts_duration_plan_apply(int device, const float* w, const int32_t* fixed, co
     return ok ? STS_OK : set_err(STS_EDEVICE, "the duration plan failed on the device");
 }
 
+int sts_set_speaker_mix(sts_engine* e, int32_t B, const sts_speaker_mix* mixes) {
+    if (!e) return set_err(STS_EINVAL, "null engine");
+    const int rc = e->eng.set_speaker_mix(B, mixes);
+    return rc == STS_OK ? STS_OK : set_err(rc, e->eng.error());
+}
+int sts_speaker_mix_check(int32_t speaker_num, int32_t gin, int32_t B, const sts_speaker_mix* mixes) {
+    if (B < 0 || (B > 0 && !mixes) || speaker_num < 0 || gin < 0) return set_err(STS_EINVAL, "speaker mix: B >= 0 entries, speaker_num >= 0 and gin >= 0 are required");
+    for (int b = 0; b < B; b++) {
+        const char* why = nullptr;
+        if (!speaker_mix_valid(speaker_num, gin, mixes[b], &why)) return set_err(STS_EINVAL, why);
+    }
+    return STS_OK;
+}
+int sts_get_speaker_embedding(const sts_engine* e, int32_t sid, float* out, int64_t capacity) {
+    if (!e || !out) return set_err(STS_EINVAL, "null argument");
+    const int rc = e->eng.speaker_embedding(sid, out, capacity);
+    if (rc == STS_EINVAL) return set_err(rc, "speaker embedding: a multi-speaker model, sid in [0, speaker_num) and capacity >= gin_channels are required");
+    return rc == STS_OK ? STS_OK : set_err(rc, "speaker embedding: the device copy failed");
+}
+int sts_speaker_blend(int device, const float* table, int32_t speaker_num, int32_t gin, int32_t B, const int32_t* sid,
+                      const sts_speaker_mix* mixes, float* g_out) {
+    if (B < 1 || B > (1 << 20) || !table || !g_out || speaker_num < 1 || gin < 1 || (int64_t)speaker_num * gin > (1 << 28) || (int64_t)B * gin > (1 << 28))
+        return set_err(STS_EINVAL, "B >= 1, a table of speaker_num >= 1 rows of gin >= 1 floats and g_out are required");
+    std::vector<sts_speaker_mix> none;
+    if (!mixes) { none.assign((size_t)B, sts_speaker_mix{0, nullptr, nullptr, nullptr, 0.f}); mixes = none.data(); }
+    for (int b = 0; b < B; b++) {
+        const char* why = nullptr;
+        if (!speaker_mix_valid(speaker_num, gin, mixes[b], &why)) return set_err(STS_EINVAL, why);
+    }
+    std::vector<int32_t> words; int K = 0;
+    speaker_mix_flatten(mixes, B, gin, words, &K);
+    std::vector<int32_t> sidv((size_t)B, 0);
+    if (sid) sidv.assign(sid, sid + B);
+    if (hipSetDevice(device) != hipSuccess) return set_err(STS_EDEVICE, "no such device");
+    auto pad = [](size_t bytes) { return (bytes + 255) & ~(size_t)255; };
+    const size_t tb = pad((size_t)speaker_num * gin * 4), sb = pad((size_t)B * 4), wb = pad(words.size() * 4), gb = pad((size_t)B * gin * 4);
+    char* d = nullptr;          // [table | sid | term table | g]
+    if (hipMalloc((void**)&d, tb + sb + wb + gb) != hipSuccess) return set_err(STS_EDEVICE, "out of device memory");
+    hipStream_t st = nullptr;
+    bool ok = hipStreamCreate(&st) == hipSuccess;
+    std::vector<float> g((size_t)B * gin);       // [gin][B], the engine's layout
+    ok = ok && hipMemcpyAsync(d, table, (size_t)speaker_num * gin * 4, hipMemcpyHostToDevice, st) == hipSuccess &&
+         hipMemcpyAsync(d + tb, sidv.data(), (size_t)B * 4, hipMemcpyHostToDevice, st) == hipSuccess &&
+         hipMemcpyAsync(d + tb + sb, words.data(), words.size() * 4, hipMemcpyHostToDevice, st) == hipSuccess;
+    if (ok) {
+        speaker_blend((const float*)d, speaker_num, gin, (const int*)(d + tb), B, speaker_mix_tab((const int*)(d + tb + sb), B, K), (float*)(d + tb + sb + wb), st);
+        ok = hipGetLastError() == hipSuccess && hipMemcpyAsync(g.data(), d + tb + sb + wb, g.size() * 4, hipMemcpyDeviceToHost, st) == hipSuccess &&
+             hipStreamSynchronize(st) == hipSuccess;
+    }
+    if (st) (void)hipStreamDestroy(st);
+    (void)hipFree(d);
+    if (!ok) return set_err(STS_EDEVICE, "the speaker blend failed on the device");
+    for (int b = 0; b < B; b++) for (int c = 0; c < gin; c++) g_out[(size_t)b * gin + c] = g[(size_t)c * B + b];
+    return STS_OK;
+}
+
 int sts_set_noise(sts_engine* e, float noise_scale, float noise_scale_w, uint64_t seed) {
     if (!e) return set_err(STS_EINVAL, "null engine");
     if (!noise_scale_valid(noise_scale) || !noise_scale_valid(noise_scale_w)) return set_err(STS_EINVAL, "noise scales must be finite and >= 0");

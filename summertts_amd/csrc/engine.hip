@@ -394,6 +394,28 @@ int Engine::set_duration_plan(int B, const int32_t* n, const sts_dur_plan* plans
     have_plan = true;
     return STS_OK;
 }
+// sts_set_speaker_mix: validated and flattened here; an invalid mix changes nothing.  B == 0 or mixes == null drops a pending mix.
+int Engine::set_speaker_mix(int B, const sts_speaker_mix* mixes) {
+    if (B == 0 || !mixes) { have_mix = false; return STS_OK; }
+    if (B < 0 || B > (1 << 20)) return fail(STS_EINVAL, "speaker mix: B >= 0 is required");
+    for (int b = 0; b < B; b++) {
+        const char* why = nullptr;
+        if (!speaker_mix_valid(model.is_ms == 1 ? model.spk_num : 0, model.gin, mixes[b], &why)) return fail(STS_EINVAL, why);
+    }
+    speaker_mix_flatten(mixes, B, model.gin, mix_words, &mix_K);
+    mix_B = B;
+    have_mix = true;
+    return STS_OK;
+}
+// sts_get_speaker_embedding: row sid of the device-resident table (one strided copy of gin floats)
+int Engine::speaker_embedding(int sid, float* out, int64_t capacity) const {
+    if (!out) return STS_EINVAL;
+    if (model.is_ms != 1 || !model.emb_g || sid < 0 || sid >= model.spk_num || capacity < model.gin) return STS_EINVAL;
+    if (hipSetDevice(device) != hipSuccess) return STS_EDEVICE;
+    if (hipMemcpy2D(out, sizeof(float), model.emb_g + sid, (size_t)model.spk_num * sizeof(float), sizeof(float), (size_t)model.gin,
+                    hipMemcpyDeviceToHost) != hipSuccess) return STS_EDEVICE;
+    return STS_OK;
+}
 // sts_get_phoneme_offsets: host arithmetic on the durations the last run downloaded -- phoneme i with f frames before it in its utterance
 // starts at output sample ceil(f hop P / Q) (f hop at the native rate), the convention of a streaming chunk's sample_offset
 int Engine::phoneme_offsets(int64_t* start, int64_t capacity) {
@@ -445,7 +467,10 @@ int Engine::run_setup(RunCtx& c) {
         for (int b = 0; b < B && same; b++) same = plan_n[b] == n[b];
         if (!same) return fail(STS_EINVAL, "the duration plan was set for another batch (B and every n[b] must match)");
     }
+    if (have_mix && mix_B != B) return fail(STS_EINVAL, "the speaker mix was set for another batch (B must match)");      // (run() drops it)
     const bool plan = c.plan = have_plan;
+    const bool mix = c.mix = have_mix && M.is_ms == 1;       // (a single-speaker model accepts empty entries only: nothing to blend)
+    const size_t mix_ints = mix ? mix_words.size() : 0;                    // the term table, between the ids and the plan
     const size_t plan_ints = plan ? 2 * (size_t)Ttot + (size_t)B : 0;      // [rate Ttot | fixed Ttot | target B] behind the ids
     // sampling noise of every utterance: the caller's per-utterance table (sts_pool, sts_multi) or the engine's setting with seed + b
     c.nz.resize(B);
@@ -468,16 +493,18 @@ int Engine::run_setup(RunCtx& c) {
         A.used = 0;
         // one device block mirroring the pinned staging block [geometry ints | length scales | noise scales, seeds | ids | forced
         // durations]: a single host-to-device copy per run
-        // (a run with a duration plan: the plan's arrays ride in the same copy, between the ids and `forced`, which the plan kernel then writes)
-        bt.meta_i = A.get<int>((size_t)9 * B + 8 + 5 * (size_t)B + 2 * (size_t)Ttot + plan_ints);
+        // (a run with a duration plan: the plan's arrays ride in the same copy, between the ids and `forced`, which the plan kernel then writes;
+        // a run with a speaker mix: its term table too, right behind the ids)
+        bt.meta_i = A.get<int>((size_t)9 * B + 8 + 5 * (size_t)B + 2 * (size_t)Ttot + mix_ints + plan_ints);
         bt.ls = (float*)(bt.meta_i + ((size_t)9 * B + 8));
         bt.ns = bt.ls + B; bt.nsw = bt.ns + B;
         bt.seed = (uint64_t*)(bt.nsw + B);      // (9B + 8 + 3B ints from a 256-byte boundary: 8-byte aligned)
         bt.ids = (int*)(bt.seed + B);
-        bt.plan_rate = plan ? (float*)(bt.ids + Ttot) : nullptr;
-        bt.plan_fixed = plan ? bt.ids + 2 * Ttot : nullptr;
-        bt.plan_target = plan ? bt.ids + 3 * Ttot : nullptr;
-        bt.forced = bt.ids + Ttot + plan_ints;
+        bt.mix = mix ? bt.ids + Ttot : nullptr;
+        bt.plan_rate = plan ? (float*)(bt.ids + Ttot + mix_ints) : nullptr;
+        bt.plan_fixed = plan ? bt.ids + 2 * Ttot + mix_ints : nullptr;
+        bt.plan_target = plan ? bt.ids + 3 * Ttot + mix_ints : nullptr;
+        bt.forced = bt.ids + Ttot + mix_ints + plan_ints;
         bt.x = A.get<float>((size_t)H * Ttot); bt.qkv = A.get<float>((size_t)3 * H * Ttot);
         bt.att = A.get<float>((size_t)H * Ttot); bt.y = A.get<float>((size_t)H * Ttot * ffn2_slices);
         bt.x1 = A.get<float>((size_t)H * Ttot); bt.ffh = A.get<float>((size_t)FF * Ttot);
@@ -504,7 +531,7 @@ int Engine::run_setup(RunCtx& c) {
 
     // ---------------- one H2D: geometry + ids (+ forced durations)
     const size_t meta_ints = c.meta_ints = (size_t)9 * B + 8;
-    const size_t up_bytes = c.up_bytes = (meta_ints + 5 * (size_t)B + 2 * (size_t)Ttot + plan_ints) * 4 + 1024;
+    const size_t up_bytes = c.up_bytes = (meta_ints + 5 * (size_t)B + 2 * (size_t)Ttot + mix_ints + plan_ints) * 4 + 1024;
     if (!ensure_pinned(up_bytes + ((size_t)Ttot + B) * 4)) return fail(STS_EDEVICE, "pinned host allocation failed");
     int* pm = c.pm = (int*)pinned_;
     int* p_offT = c.p_offT = pm, *p_lenT = c.p_lenT = pm + B, *p_sid = c.p_sid = pm + 2 * B, *p_one = c.p_one = pm + 5 * B;
@@ -520,14 +547,15 @@ int Engine::run_setup(RunCtx& c) {
     for (int b = 0; b < B; b++) { p_ns[b] = c.nz[b].ns; p_nsw[b] = c.nz[b].nsw; p_seed[b] = c.nz[b].seed; }
     int* p_ids = (int*)(p_seed + B);
     for (int b = 0; b < B; b++) memcpy(p_ids + offT[b], ids[b], sizeof(int) * n[b]);
-    int* p_forced = p_ids + Ttot;
+    if (mix) memcpy(p_ids + Ttot, mix_words.data(), sizeof(int) * mix_ints);
+    int* p_forced = p_ids + Ttot + mix_ints;
     if (have_forced) memcpy(p_forced, forced_dur.data(), sizeof(int) * Ttot);
     if (plan) {          // (never together with forced durations: the plan's arrays take their place in the copy)
-        memcpy(p_ids + Ttot, plan_rate.data(), sizeof(float) * Ttot);
-        memcpy(p_ids + 2 * Ttot, plan_fixed.data(), sizeof(int) * Ttot);
-        memcpy(p_ids + 3 * Ttot, plan_target.data(), sizeof(int) * B);
+        memcpy(p_ids + Ttot + mix_ints, plan_rate.data(), sizeof(float) * Ttot);
+        memcpy(p_ids + 2 * Ttot + mix_ints, plan_fixed.data(), sizeof(int) * Ttot);
+        memcpy(p_ids + 3 * Ttot + mix_ints, plan_target.data(), sizeof(int) * B);
     }
-    HIPCK(hipMemcpyAsync(bt.meta_i, pm, (meta_ints + 5 * (size_t)B + (size_t)Ttot * (have_forced ? 2 : 1) + plan_ints) * 4, hipMemcpyHostToDevice, stream));
+    HIPCK(hipMemcpyAsync(bt.meta_i, pm, (meta_ints + 5 * (size_t)B + (size_t)Ttot * (have_forced ? 2 : 1) + mix_ints + plan_ints) * 4, hipMemcpyHostToDevice, stream));
     if (B > 1) HIPCK(hipEventRecord(ev_setup_, stream));     // (run_durations, batches launched from the memo: the host rewrites part of this block)
 
     // single-segment views travel by value (kernels.hpp SegView): no segment-table load in the kernels of a one-utterance call
@@ -635,7 +663,8 @@ int Engine::run_durations(RunCtx& c) {
 
     // ---------------- speaker conditioning vectors (all 1x1 convs on g; SynthesizerTrn.cpp:363-372)
     stage_begin(1);
-    if (ms) gather_speaker(M.emb_g, M.spk_num, M.gin, d_sid, B, bt.g, stream);
+    if (ms && c.mix) speaker_blend(M.emb_g, M.spk_num, M.gin, d_sid, B, speaker_mix_tab(bt.mix, B, mix_K), bt.g, stream);     // (in place of the gather)
+    else if (ms) gather_speaker(M.emb_g, M.spk_num, M.gin, d_sid, B, bt.g, stream);
 
     // ---------------- duration predictor
     const float* r_final = nullptr;
@@ -730,7 +759,7 @@ int Engine::run_durations(RunCtx& c) {
         c.req_keys[b] = h | 1ull;
     }
     c.predF.clear();
-    if (launch_ahead && !ss && !have_forced && !c.plan && !record_taps && mapped) {     // (a planned run's frame count is not a function of the memo's key)
+    if (launch_ahead && !ss && !have_forced && !c.plan && !c.mix && !record_taps && mapped) {     // (a planned or mixed run's frame count is not a function of the memo's key)
         c.predF.resize(B);
         for (int b = 0; b < B; b++) {
             const auto it = seen_tf_.find(c.req_keys[b]);
@@ -753,7 +782,7 @@ int Engine::run_durations(RunCtx& c) {
     durations(r_final, M.dur_type == 0 ? 1 : 0, M.ea_m, M.ea_logs, bt.ls, (have_forced || c.plan) ? bt.forced : nullptr, bt.dlogw,
               bt.dur, bt.cum, bt.frames, lvT.seg, B, stream, mapped ? hmap_dev_ : nullptr, Ttot, seq_, arrive_,
               c.ahead ? c.d_lenF : nullptr, c.ahead ? c.d_win + 2 : nullptr, (int)cap);
-    c.forced = have_forced || c.plan;      // (neither kind of run feeds the memo)
+    c.forced = have_forced || c.plan || c.mix;      // (none of these runs feeds the memo: its key hashes sid, not the mix)
     have_forced = false;
     mark(2);
     sync_wait_ms_ = 0;
@@ -1132,6 +1161,7 @@ static constexpr int kRetrySplitBf16 = 1;     // run_once: nothing was handed ou
 int Engine::run(int B, const int32_t* const* ids, const int32_t* n, const int32_t* sid, const float* ls, const StreamSpec* ss) {
     const int rc = run_any_math(B, ids, n, sid, ls, ss);
     have_plan = false;          // a duration plan is for one call, whatever its outcome; the repeat inside the call above applied it again
+    have_mix = false;           // and so is a speaker mix
     return rc;
 }
 int Engine::run_any_math(int B, const int32_t* const* ids, const int32_t* n, const int32_t* sid, const float* ls, const StreamSpec* ss) {
@@ -1430,7 +1460,7 @@ int Engine::run_stream_steps(RunCtx& c) {
             const long F = lenF[b], f1 = std::min<long>(F, f0 + Cf);
             const long w0 = std::max<long>(0, f0 - halo), w1 = std::min<long>(F, f1 + halo);
             const long long j0 = out_count((long long)f0 * hop), j1 = out_count((long long)f1 * hop);
-            ti[i] = offF[b] + (int)w0; ti[nw + i] = (int)Wtot; ti[2 * nw + i] = (int)(w1 - w0); ti[3 * nw + i] = sidv[b];
+            ti[i] = offF[b] + (int)w0; ti[nw + i] = (int)Wtot; ti[2 * nw + i] = (int)(w1 - w0); ti[3 * nw + i] = c.mix ? b : sidv[b];      // (a mixed run: the window's utterance, a column of bt.g)
             ti[4 * nw + i] = (int)((Wtot + (f0 - w0)) * hop); ti[5 * nw + i] = (int)dsum;
             const long long Nout = out_count((long long)F * hop);
             const long long jl0 = slim ? std::max<long long>(0, j0 - 2 * ld.H) : j0, jl1 = slim ? std::min<long long>(Nout, j1 + 2 * ld.H) : j1;

@@ -128,6 +128,11 @@ public:
     // rate 1 (w * 1.0f == w bit for bit), fixed -1, target 0.  plan_n: the phoneme counts the next call must have.
     std::vector<int32_t> plan_n, plan_fixed, plan_target; std::vector<float> plan_rate; bool have_plan = false;
     int set_duration_plan(int B, const int32_t* n, const sts_dur_plan* plans);
+    // speaker mix (sts_set_speaker_mix, misc_kernels.hip speaker_blend): for the NEXT call only, whatever its outcome, like the plan.  Kept as
+    // the flattened term table the run uploads (kernels.hpp SpeakerMixTab) for mix_B utterances with mix_K terms in all
+    std::vector<int32_t> mix_words; int mix_B = 0, mix_K = 0; bool have_mix = false;
+    int set_speaker_mix(int B, const sts_speaker_mix* mixes);
+    int speaker_embedding(int sid, float* out, int64_t capacity) const;
     // phoneme start offsets of the last run in output samples, packed like durations_h (sts_get_phoneme_offsets); last_n: its phoneme counts
     std::vector<int32_t> last_n;
     int phoneme_offsets(int64_t* start, int64_t capacity);

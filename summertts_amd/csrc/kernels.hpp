@@ -8,6 +8,10 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <vector>
+
+#include "../../include/summertts_hip.h"
+
 namespace sts {
 
 // Utterance b occupies positions [off[b]*scale + b*extra, ... + len[b]*scale + extra) of a packed row.
@@ -295,7 +299,38 @@ void attention(const AttnArgs& a, hipStream_t st);
 // y[c][seg b] += u[c*B + b]
 void add_ubias(float* y, long ld, const float* u, int C, SegView seg, int B, int max_len, hipStream_t st);
 void gather_speaker(const float* emb_g, int spk_num, int gin, const int* sid, int B, float* g, hipStream_t st);
-// y = (((r0 + r1) + r2) + ...) / count  (ResBlock sum, /root/reference/src/models/Generator_hifigan.cpp:159-173)
+// Speaker blending (the definition is in include/summertts_hip.h, sts_set_speaker_mix)
+constexpr int kMixMaxTerms = 16;
+constexpr float kMixMaxWeight = 16.f;
+inline bool speaker_mix_empty(const sts_speaker_mix& m) { return m.k == 0 && !m.vector; }
+// one entry against a table of spk_num rows of gin floats (spk_num 0: a single-speaker model, which takes empty entries only)
+bool speaker_mix_valid(int spk_num, int gin, const sts_speaker_mix& m, const char** why);
+// host copy of one entry (requests of a pool, utterances of a multi-device batch)
+struct SpeakerMixCopy {
+    std::vector<int32_t> sid; std::vector<float> weight, vector; float vector_weight = 0.f; bool has_vector = false;
+    void assign(const sts_speaker_mix& m, int gin) {
+        sid.assign(m.sid, m.sid + (m.k > 0 ? m.k : 0)); weight.assign(m.weight, m.weight + (m.k > 0 ? m.k : 0));
+        has_vector = m.vector != nullptr; vector_weight = has_vector ? m.vector_weight : 0.f;
+        if (has_vector) vector.assign(m.vector, m.vector + gin); else vector.clear();
+    }
+    sts_speaker_mix view() const {
+        return sts_speaker_mix{(int32_t)sid.size(), sid.empty() ? nullptr : sid.data(), weight.empty() ? nullptr : weight.data(),
+                               has_vector ? vector.data() : nullptr, vector_weight};
+    }
+};
+// The flattened term table of B entries, 32-bit words: [off B + 1 | vidx B | vw B | tsid K | tw K | vec V * gin]: entry b owns the terms
+// off[b] .. off[b + 1) and, when vidx[b] >= 0, row vidx[b] of vec with the weight vw[b] (K terms and V vectors in all)
+struct SpeakerMixTab { const int* off; const int* vidx; const float* vw; const int* tsid; const float* tw; const float* vec; };
+void speaker_mix_flatten(const sts_speaker_mix* mixes, int B, int gin, std::vector<int32_t>& words, int* K);      // entries speaker_mix_valid accepted
+inline SpeakerMixTab speaker_mix_tab(const int* words, int B, int K) {
+    const int* tsid = words + 3 * (size_t)B + 1;
+    return SpeakerMixTab{words, words + B + 1, (const float*)(words + 2 * (size_t)B + 1), tsid, (const float*)(tsid + K), (const float*)(tsid + 2 * (size_t)K)};
+}
+// g[c][b] = (float)(sum_k (double)tw[k] (double)emb_g(tsid[k], c) [+ (double)vw[b] (double)vec[vidx[b]][c]]), float64 accumulation in term
+// order; an entry with no term and no vector takes row sid[b] as gather_speaker does.  One thread per (utterance, channel), g in
+// gather_speaker's layout: one launch serves a batch that has both kinds
+void speaker_blend(const float* emb_g, int spk_num, int gin, const int* sid, int B, const SpeakerMixTab& t, float* g, hipStream_t st);
+// y =(((r0 + r1) + r2) + ...) / count  (ResBlock sum, /root/reference/src/models/Generator_hifigan.cpp:159-173)
 void sum_scale(float* y, const float* const* r, int count, long n, hipStream_t st);
 void flip_channels(float* x, long ld, int C, long n, float* tmp, hipStream_t st);
 

@@ -7,6 +7,7 @@
 #include "knobs.hpp"
 #include "noise.hpp"
 #include <stdlib.h>
+#include <string.h>
 
 namespace sts {
 
@@ -606,6 +607,70 @@ void gather_speaker(const float* emb_g, int spk_num, int gin, const int* sid, in
     int n = gin * B;
     if (n <= 0) return;
     hipLaunchKernelGGL(gather_speaker_kernel, dim3((n + 255) / 256), dim3(256), 0, st, emb_g, spk_num, gin, sid, B, g);
+}
+
+// Speaker blending (include/summertts_hip.h sts_set_speaker_mix): g[c][b] = (float)(sum_k w_k E[s_k][c] [+ vw v[c]]), every product exact
+// in float64 (two fp32 factors), the sum in float64 in term order, one rounding -- so an FMA contraction changes nothing.  An entry with no
+// term and no vector is gather_speaker's row.  (The host validates every term's row; the clamp keeps a read inside the table regardless.)
+__global__ void speaker_blend_kernel(const float* emb_g, int spk_num, int gin, const int* sid, int B, SpeakerMixTab t, float* g) {
+    int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= gin * B) return;
+    int c = i / B, b = i - c * B;
+    const int k0 = t.off[b], k1 = t.off[b + 1], v = t.vidx[b];
+    const float* row = emb_g + (size_t)c * spk_num;
+    if (k0 == k1 && v < 0) {
+        int s = sid[b];
+        if (s < 0 || s >= spk_num) s = 0;
+        g[i] = row[s];
+        return;
+    }
+    double acc = 0.0;
+    for (int k = k0; k < k1; k++) {
+        int s = t.tsid[k];
+        if (s < 0 || s >= spk_num) s = 0;
+        acc += (double)t.tw[k] * (double)row[s];
+    }
+    if (v >= 0) acc += (double)t.vw[b] * (double)t.vec[(size_t)v * gin + c];
+    g[i] = (float)acc;
+}
+void speaker_blend(const float* emb_g, int spk_num, int gin, const int* sid, int B, const SpeakerMixTab& t, float* g, hipStream_t st) {
+    int n = gin * B;
+    if (n <= 0) return;
+    hipLaunchKernelGGL(speaker_blend_kernel, dim3((n + 255) / 256), dim3(256), 0, st, emb_g, spk_num, gin, sid, B, t, g);
+}
+bool speaker_mix_valid(int spk_num, int gin, const sts_speaker_mix& m, const char** why) {
+    auto bad = [&](const char* s) { if (why) *why = s; return false; };
+    auto weight_ok = [](float w) { return w >= -kMixMaxWeight && w <= kMixMaxWeight; };      // (false for NaN and the infinities)
+    if (m.k < 0 || m.k > kMixMaxTerms) return bad("speaker mix: k must be in 0..16");
+    if (speaker_mix_empty(m)) return true;
+    if (spk_num <= 0 || gin <= 0) return bad("speaker mix: a single-speaker model takes no mix");
+    if (m.k > 0 && (!m.sid || !m.weight)) return bad("speaker mix: sid and weight are required when k > 0");
+    for (int k = 0; k < m.k; k++) {
+        if (m.sid[k] < 0 || m.sid[k] >= spk_num) return bad("speaker mix: sid outside [0, speaker_num)");
+        if (!weight_ok(m.weight[k])) return bad("speaker mix: weights must be finite with |w| <= 16");
+    }
+    if (m.vector) {
+        if (!weight_ok(m.vector_weight)) return bad("speaker mix: vector_weight must be finite with |w| <= 16");
+        for (int c = 0; c < gin; c++)
+            if (!(m.vector[c] >= -3.4028234e38f && m.vector[c] <= 3.4028234e38f)) return bad("speaker mix: vector entries must be finite");
+    }
+    return true;
+}
+void speaker_mix_flatten(const sts_speaker_mix* mixes, int B, int gin, std::vector<int32_t>& words, int* K_out) {
+    int K = 0, V = 0;
+    for (int b = 0; b < B; b++) { K += mixes[b].k; V += mixes[b].vector ? 1 : 0; }
+    words.assign(3 * (size_t)B + 1 + 2 * (size_t)K + (size_t)V * gin, 0);
+    int32_t* off = words.data(); int32_t* vidx = off + B + 1; float* vw = (float*)(vidx + B);
+    int32_t* tsid = vidx + 2 * B; float* tw = (float*)(tsid + K); float* vec = tw + K;
+    int k = 0, v = 0;
+    for (int b = 0; b < B; b++) {
+        off[b] = k;
+        for (int j = 0; j < mixes[b].k; j++, k++) { tsid[k] = mixes[b].sid[j]; tw[k] = mixes[b].weight[j]; }
+        vidx[b] = -1; vw[b] = 0.f;
+        if (mixes[b].vector) { vidx[b] = v; vw[b] = mixes[b].vector_weight; memcpy(vec + (size_t)v * gin, mixes[b].vector, sizeof(float) * gin); v++; }
+    }
+    off[B] = k;
+    if (K_out) *K_out = K;
 }
 
 struct SumPtrs { const float* r[8]; };

@@ -100,6 +100,8 @@ struct sts_multi {
     // sts_multi_set_duration_plan: the next batch's plans, per utterance of the caller's batch (rate / fixed: n entries or empty = absent)
     struct UttPlan { std::vector<float> rate; std::vector<int32_t> fixed; int32_t target = 0; };
     std::vector<UttPlan> plan; std::vector<int32_t> plan_n; bool have_plan = false;
+    // sts_multi_set_speaker_mix: the next batch's mixes, per utterance of the caller's batch
+    std::vector<SpeakerMixCopy> mix; bool have_mix = false;
     std::vector<Shard> shards;
     // RCCL gather state (gather_mode == 1)
     int gather_mode = 0;
@@ -298,7 +300,13 @@ struct sts_multi {
                     }
                     sh.rc = eng.set_duration_plan(nb, nn.data(), pl.data());
                 }
+                if (sh.rc == STS_OK && have_mix) {      // and so do the mixes
+                    std::vector<sts_speaker_mix> mx(nb);
+                    for (int i = 0; i < nb; i++) mx[i] = mix[sh.utt[i]].view();
+                    sh.rc = eng.set_speaker_mix(nb, mx.data());
+                }
                 if (sh.rc == STS_OK) sh.rc = eng.run(nb, idp.data(), nn.data(), sd.data(), l.data());
+                else { sh.err = eng.error(); eng.set_duration_plan(0, nullptr, nullptr); eng.set_speaker_mix(0, nullptr); }     // (nothing ran: nothing stays pending)
                 eng.noise_utt.clear();
                 if (sh.rc == STS_OK && gather_mode == 1) {
                     sh.n_samples = eng.n_samples;           // the PCM stays on the device: rccl_gather() below
@@ -436,6 +444,20 @@ int sts_multi_set_duration_plan(sts_multi* m, int32_t B, const int32_t* n, const
     m->have_plan = true;
     return STS_OK;
 }
+int sts_multi_set_speaker_mix(sts_multi* m, int32_t B, const sts_speaker_mix* mixes) {
+    if (!m) return multi_err(STS_EINVAL, "null handle");
+    if (B == 0 || !mixes) { m->have_mix = false; return STS_OK; }
+    if (B < 0) return multi_err(STS_EINVAL, "speaker mix: B >= 0 is required");
+    const Model& M = m->engines[0]->model;
+    for (int b = 0; b < B; b++) {
+        const char* why = nullptr;
+        if (!speaker_mix_valid(M.is_ms == 1 ? M.spk_num : 0, M.gin, mixes[b], &why)) return multi_err(STS_EINVAL, why);
+    }
+    m->mix.assign((size_t)B, SpeakerMixCopy());
+    for (int b = 0; b < B; b++) m->mix[b].assign(mixes[b], M.gin);
+    m->have_mix = true;
+    return STS_OK;
+}
 int sts_multi_set_conv_math(sts_multi* m, int mode) {
     if (!m) return multi_err(STS_EINVAL, "null handle");
     if (mode < 0 || mode > 3) return multi_err(STS_EINVAL, "conv math must be 0..3");
@@ -544,7 +566,7 @@ int sts_multi_shard_of(const sts_multi* m, int32_t B, const int32_t* n, int32_t*
 int sts_multi_infer_ids_batch(sts_multi* m, int32_t B, const int32_t* const* ids, const int32_t* n, const int32_t* sid,
                               const float* length_scale, int16_t** pcm_out, int32_t* n_out) {
     if (!m) return multi_err(STS_EINVAL, "bad arguments");
-    struct DropPlan { sts_multi* m; ~DropPlan() { m->have_plan = false; } } drop_plan{m};      // a duration plan is for this call only, whatever its outcome
+    struct DropPlan { sts_multi* m; ~DropPlan() { m->have_plan = false; m->have_mix = false; } } drop_plan{m};      // a duration plan and a speaker mix are for this call only, whatever its outcome
     if (!ids || !n || !pcm_out || !n_out || B <= 0) return multi_err(STS_EINVAL, "bad arguments");
     for (int b = 0; b < B; b++) { pcm_out[b] = nullptr; n_out[b] = 0; }      // every output is defined before the first early return
     for (int b = 0; b < B; b++) if (n[b] <= 0 || !ids[b]) return multi_err(STS_EINVAL, "utterance with no phonemes");
@@ -553,6 +575,7 @@ int sts_multi_infer_ids_batch(sts_multi* m, int32_t B, const int32_t* const* ids
         for (int b = 0; b < B && same; b++) same = m->plan_n[b] == n[b];
         if (!same) return multi_err(STS_EINVAL, "the duration plan was set for another batch (B and every n[b] must match)");
     }
+    if (m->have_mix && (int)m->mix.size() != B) return multi_err(STS_EINVAL, "the speaker mix was set for another batch (B must match)");
     const int ndev = (int)m->engines.size();
     const bool was_gather = m->gather_mode == 1;
     {

@@ -29,6 +29,8 @@ struct Request {
     Engine::Noise noise;               // sts_pool_submit_ex: this request's sampling noise
     // sts_pool_submit_plan: this request's duration plan (rate / fixed: n entries or empty = absent; target 0 = none)
     bool planned = false; std::vector<float> rate; std::vector<int32_t> fixed; int32_t target = 0;
+    // sts_pool_submit_mix: this request's speaker mix (mixed: a non-empty entry)
+    bool mixed = false; SpeakerMixCopy mix;
     // sts_pool_submit_stream: chunks go to cb (on the worker thread); the ticket completes with pcm = null, n = samples delivered
     bool stream = false; int32_t chunk = 0; sts_chunk_cb cb = nullptr; void* user = nullptr;
     // result
@@ -86,7 +88,15 @@ struct sts_pool {
                                                                   grp[b]->fixed.empty() ? nullptr : grp[b]->fixed.data(), grp[b]->target};
                     rc = eng.set_duration_plan(B, n.data(), pl.data());
                 }
+                bool any_mix = false;
+                for (int b = 0; b < B; b++) any_mix = any_mix || grp[b]->mixed;
+                if (rc == STS_OK && any_mix) {      // per utterance likewise: the plain members get an empty entry (their sid, bit for bit)
+                    std::vector<sts_speaker_mix> mx(B, sts_speaker_mix{0, nullptr, nullptr, nullptr, 0.f});
+                    for (int b = 0; b < B; b++) if (grp[b]->mixed) mx[b] = grp[b]->mix.view();
+                    rc = eng.set_speaker_mix(B, mx.data());
+                }
                 if (rc == STS_OK) rc = eng.run(B, idp.data(), n.data(), sid.data(), ls.data());
+                else { eng.set_duration_plan(0, nullptr, nullptr); eng.set_speaker_mix(0, nullptr); }     // (nothing ran: nothing stays pending for another group)
                 eng.noise_utt.clear();
                 std::vector<int16_t> all;
                 if (rc == STS_OK) {
@@ -232,6 +242,28 @@ int64_t sts_pool_submit_plan(sts_pool* p, const int32_t* ids, int32_t n, int32_t
     if (rate) r->rate.assign(rate, rate + n);
     if (fixed) r->fixed.assign(fixed, fixed + n);
     r->target = target_frames;
+    {
+        std::lock_guard<std::mutex> lk(p->mu);
+        if (p->stop) return pool_err(STS_ESTATE, "pool is shutting down");
+        r->ticket = p->next_ticket++;
+        p->queue.push_back(r);
+        p->pending[r->ticket] = r;
+    }
+    p->cv_work.notify_one();
+    return r->ticket;
+}
+
+int64_t sts_pool_submit_mix(sts_pool* p, const int32_t* ids, int32_t n, int32_t sid, float length_scale, float noise_scale,
+                            float noise_scale_w, uint64_t seed, const sts_speaker_mix* mix) {
+    if (!p || !ids || n <= 0) return pool_err(STS_EINVAL, "bad request");
+    if (!noise_scale_valid(noise_scale) || !noise_scale_valid(noise_scale_w)) return pool_err(STS_EINVAL, "noise scales must be finite and >= 0");
+    const Model& M = p->engines[0]->model;
+    const char* why = nullptr;
+    if (mix && !speaker_mix_valid(M.is_ms == 1 ? M.spk_num : 0, M.gin, *mix, &why)) return pool_err(STS_EINVAL, why);
+    auto r = std::make_shared<Request>();
+    r->ids.assign(ids, ids + n); r->sid = sid; r->ls = length_scale; r->noise = Engine::Noise{noise_scale, noise_scale_w, seed};
+    r->mixed = mix && !speaker_mix_empty(*mix);
+    if (r->mixed) r->mix.assign(*mix, M.gin);
     {
         std::lock_guard<std::mutex> lk(p->mu);
         if (p->stop) return pool_err(STS_ESTATE, "pool is shutting down");

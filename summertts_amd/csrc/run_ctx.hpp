@@ -20,6 +20,8 @@ struct BufT {
     // a run with a duration plan only (null otherwise): the uploaded plan [rate Ttot | fixed Ttot | target B] between ids and forced, the
     // plan kernel's remainder scratch, w for the "dur_w" tap
     float* plan_rate; int *plan_fixed, *plan_target; long long* plan_rem; float* dur_w;
+    // a run with a speaker mix only (null otherwise): the uploaded term table (kernels.hpp SpeakerMixTab) right behind the ids
+    int* mix;
 };
 struct BufF {
     float *z, *h, *acts, *out, *x0, *regA, *regB, *tailA, *tailB, *tailC, *wave, *fliptmp;
@@ -61,6 +63,7 @@ struct Engine::RunCtx {
     // that waited for it -- and returns bit-identical samples.  Batches: Fld == Ftot, nothing changes.
     long Fld = 0; int maxFld = 0; bool ahead = false, ahead_b = false, mapped = false, forced = false;
     bool plan = false;              // this run applies a duration plan (sts_set_duration_plan): never launched ahead, never in the memo
+    bool mix = false;               // this run blends speakers (sts_set_speaker_mix): bt.g comes from speaker_blend; never launched ahead, never in the memo
     std::vector<Engine::Noise> nz; bool any_ns = false, any_nsw = false;   // per-utterance sampling noise (engine.hpp Noise), which of the two is used
     std::vector<unsigned long long> req_keys; std::vector<long> predF;      // launch-ahead memo: per-utterance request hashes, remembered frame counts (empty: not all known)
     int halo = 0; long Wcap = 0; int upS = 1; long Lsb = 0; int sbC = 0;

@@ -73,6 +73,41 @@ def _dur_plans(n: Sequence[int], plans):
     return n, arr, keep
 
 
+class SpeakerMix(C.Structure):
+    """``sts_speaker_mix``: one utterance's speaker mix (include/summertts_hip.h sts_set_speaker_mix)."""
+    _fields_ = [("k", C.c_int32), ("sid", C.c_void_p), ("weight", C.c_void_p), ("vector", C.c_void_p), ("vector_weight", C.c_float)]
+
+
+def _speaker_mixes(mixes, gin: Optional[int] = None):
+    """-> (ctypes array of SpeakerMix, the numpy arrays it points into).  ``mixes[b]``: None (the plain sid) or a mapping with any of
+    ``sid`` + ``weight`` (table rows and their weights, equally many), ``vector`` (a caller's embedding, ``gin`` floats) and
+    ``vector_weight`` (default 1)."""
+    arr, keep = (SpeakerMix * max(len(mixes), 1))(), []
+    for b, m in enumerate(mixes):
+        m = m or {}
+        sid, w = m.get("sid"), m.get("weight")
+        if (sid is None) != (w is None):
+            raise ValueError(f"mix {b}: sid and weight come together")
+        if sid is not None:
+            sid = np.ascontiguousarray(sid, dtype=np.int32).ravel()
+            w = np.ascontiguousarray(w, dtype=np.float32).ravel()
+            if sid.size != w.size:
+                raise ValueError(f"mix {b}: one weight per sid")
+            keep += [sid, w]
+            arr[b].k = sid.size
+            if sid.size:
+                arr[b].sid, arr[b].weight = sid.ctypes.data, w.ctypes.data
+        v = m.get("vector")
+        if v is not None:
+            v = np.ascontiguousarray(v, dtype=np.float32).ravel()
+            if gin and v.size != gin:
+                raise ValueError(f"mix {b}: vector needs gin_channels = {gin} entries")
+            keep.append(v)
+            arr[b].vector = v.ctypes.data
+            arr[b].vector_weight = float(m.get("vector_weight", 1.0))
+    return arr, keep
+
+
 class PreparedBatch:
     """run_batch's argument arrays, built once (Synthesizer.prepare)."""
 
@@ -165,6 +200,13 @@ def load_library() -> C.CDLL:
     lib.sts_pool_submit_plan.restype = C.c_int64
     lib.sts_pool_submit_plan.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_float, C.c_uint64,
                                          C.c_void_p, C.c_void_p, C.c_int32]
+    lib.sts_set_speaker_mix.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
+    lib.sts_multi_set_speaker_mix.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
+    lib.sts_speaker_mix_check.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_void_p]
+    lib.sts_get_speaker_embedding.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64]
+    lib.sts_speaker_blend.argtypes = [C.c_int, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.sts_pool_submit_mix.restype = C.c_int64
+    lib.sts_pool_submit_mix.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_float, C.c_uint64, C.c_void_p]
     lib.sts_infer_ids_batch_stream.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
                                                BATCH_CHUNK_CB, C.c_void_p, C.c_void_p]
     lib.sts_pool_submit_stream.restype = C.c_int64
@@ -197,7 +239,41 @@ EXPORTED_SYMBOLS = [
     "sts_limiter_design", "sts_limiter_apply",
     "sts_set_duration_plan", "sts_get_phoneme_offsets", "sts_duration_fit", "sts_duration_plan_apply", "sts_pool_submit_plan",
     "sts_multi_set_duration_plan",
+    "sts_set_speaker_mix", "sts_speaker_mix_check", "sts_get_speaker_embedding", "sts_speaker_blend", "sts_pool_submit_mix",
+    "sts_multi_set_speaker_mix",
 ]
+
+
+def speaker_mix_check(speaker_num: int, gin: int, mixes) -> None:
+    """The validity rules of a speaker mix (include/summertts_hip.h sts_speaker_mix_check; host only, no GPU) for ``mixes`` (as
+    ``Synthesizer.set_speaker_mix`` takes them) against a table of ``speaker_num`` rows of ``gin`` floats; ``speaker_num`` 0 = a
+    single-speaker model.  Raises StsError for an invalid mix.  (A vector is read as ``gin`` floats: it must hold at least that many.)"""
+    lib = load_library()
+    arr, keep = _speaker_mixes(mixes)
+    for b, m in enumerate(mixes):
+        if m and m.get("vector") is not None and np.size(m["vector"]) < gin:
+            raise ValueError(f"mix {b}: vector needs gin = {gin} entries")
+    _check(lib, lib.sts_speaker_mix_check(int(speaker_num), int(gin), len(mixes), C.cast(arr, C.c_void_p)))
+
+
+def speaker_blend(table, mixes, sid=None, device: int = 0) -> np.ndarray:
+    """The speaker-blend kernel on a caller's table (sts_speaker_blend): ``table`` float32 [gin][speaker_num] (the blob's layout),
+    ``mixes`` as ``Synthesizer.set_speaker_mix`` takes them, ``sid`` None or one row per utterance (what an empty entry takes) ->
+    float32 [B][gin]."""
+    lib = load_library()
+    t = np.ascontiguousarray(table, dtype=np.float32)
+    if t.ndim != 2:
+        raise ValueError("table is [gin][speaker_num]")
+    gin, spk = t.shape
+    arr, keep = _speaker_mixes(mixes, gin)
+    B = len(mixes)
+    s = None if sid is None else np.ascontiguousarray(sid, dtype=np.int32)
+    if s is not None and s.size != B:
+        raise ValueError("one sid per utterance")
+    out = np.zeros((max(B, 1), gin), np.float32)
+    _check(lib, lib.sts_speaker_blend(int(device), t.ctypes.data, spk, gin, B, None if s is None else s.ctypes.data,
+                                      C.cast(arr, C.c_void_p), out.ctypes.data))
+    return out[:B]
 
 
 def duration_fit(w, fixed=None, target_frames: int = 0) -> np.ndarray:
@@ -468,6 +544,23 @@ class Synthesizer:
             return
         nn, arr, keep = _dur_plans(n, plans)
         _check(self.lib, self.lib.sts_set_duration_plan(self.h, nn.size, nn.ctypes.data, C.cast(arr, C.c_void_p)))
+
+    def set_speaker_mix(self, mixes=None):
+        """Speaker mix of the NEXT call only (include/summertts_hip.h sts_set_speaker_mix).  ``mixes``: per utterance of that call None
+        (its plain sid) or a mapping with any of ``sid`` + ``weight`` (rows of the model's table and their weights), ``vector`` (a caller's
+        embedding, gin_channels floats) and ``vector_weight`` (default 1).  None drops a pending mix.  An invalid mix raises and changes
+        nothing."""
+        if mixes is None:
+            _check(self.lib, self.lib.sts_set_speaker_mix(self.h, 0, None))
+            return
+        arr, keep = _speaker_mixes(mixes, int(self.info.gin_channels))
+        _check(self.lib, self.lib.sts_set_speaker_mix(self.h, len(mixes), C.cast(arr, C.c_void_p)))
+
+    def speaker_embedding(self, sid: int) -> np.ndarray:
+        """Row ``sid`` of the model's speaker table: float32 [gin_channels] (sts_get_speaker_embedding)."""
+        out = np.zeros(max(int(self.info.gin_channels), 1), np.float32)
+        _check(self.lib, self.lib.sts_get_speaker_embedding(self.h, int(sid), out.ctypes.data, int(self.info.gin_channels)))
+        return out[:int(self.info.gin_channels)]
 
     def phoneme_offsets(self, total_phonemes: int) -> np.ndarray:
         """Start of every phoneme of the last run in output samples at the current output rate, packed like ``durations``."""
@@ -758,11 +851,19 @@ class Pool:
         return t
 
     def submit(self, ids: Sequence[int], sid: int = 0, length_scale: float = 1.0, noise_scale: float = 0.0,
-               noise_scale_w: float = 0.0, seed: int = 0, plan=None) -> int:
+               noise_scale_w: float = 0.0, seed: int = 0, plan=None, mix=None) -> int:
         """Queue one request; the noise arguments are this request's own (``Synthesizer.set_noise``; ``seed`` is used as given), and so
-        is ``plan``: None or a mapping as ``Synthesizer.set_duration_plan`` takes per utterance (sts_pool_submit_plan)."""
+        is ``plan``: None or a mapping as ``Synthesizer.set_duration_plan`` takes per utterance (sts_pool_submit_plan), or ``mix``: None
+        or a mapping as ``Synthesizer.set_speaker_mix`` takes per utterance (sts_pool_submit_mix).  One request carries a plan or a mix,
+        not both."""
         a = np.ascontiguousarray(ids, dtype=np.int32)
-        if plan is not None:
+        if plan is not None and mix is not None:
+            raise ValueError("a request carries a plan or a mix, not both")
+        if mix is not None:
+            arr, keep = _speaker_mixes([mix])
+            t = int(self.lib.sts_pool_submit_mix(self.h, a.ctypes.data, a.size, sid, length_scale, float(noise_scale), float(noise_scale_w),
+                                                 int(seed) & 0xFFFFFFFFFFFFFFFF, C.cast(arr, C.c_void_p)))
+        elif plan is not None:
             _, arr, keep = _dur_plans([a.size], [plan])
             t = int(self.lib.sts_pool_submit_plan(self.h, a.ctypes.data, a.size, sid, length_scale, float(noise_scale), float(noise_scale_w),
                                                   int(seed) & 0xFFFFFFFFFFFFFFFF, arr[0].rate, arr[0].fixed, arr[0].target_frames))
@@ -911,6 +1012,17 @@ class MultiDevice:
             rc = self.lib.sts_multi_set_duration_plan(self.h, nn.size, nn.ctypes.data, C.cast(arr, C.c_void_p))
         if rc != 0:
             raise StsError(f"sts_multi_set_duration_plan: {rc}: {self.lib.sts_multi_last_error().decode()}")
+
+    def set_speaker_mix(self, mixes=None):
+        """``Synthesizer.set_speaker_mix`` for the next ``infer_batch``: ``mixes[b]`` belongs to utterance b of that batch, whatever its
+        device."""
+        if mixes is None:
+            rc = self.lib.sts_multi_set_speaker_mix(self.h, 0, None)
+        else:
+            arr, keep = _speaker_mixes(mixes)
+            rc = self.lib.sts_multi_set_speaker_mix(self.h, len(mixes), C.cast(arr, C.c_void_p))
+        if rc != 0:
+            raise StsError(f"sts_multi_set_speaker_mix: {rc}: {self.lib.sts_multi_last_error().decode()}")
 
     def set_conv_math(self, mode):
         m = {"bf16x3": 0, "f32": 1, "bf16x3_all": 2, "f16x2": 3}.get(mode, mode)

@@ -5,14 +5,19 @@
 //
 //   g++ -O2 -I include tools/cli/tts_ids.cpp -L summertts_amd/lib -lsummertts_hip -Wl,-rpath,$PWD/summertts_amd/lib -o tts_ids
 //   ./tts_ids ids.txt model.bin out.wav
+//   ./tts_ids --mix 3:0.6,7:0.4 ids.txt model.bin out.wav      a weighted blend of speakers (multi-speaker models, phoneme-id input; the
+//                                                               reference's class has no such call: this path uses summertts_hip.h directly)
 #include <stdint.h>
 #include <stdio.h>
+#include <stdlib.h>
 #include <string.h>
 
 #include <fstream>
 #include <string>
+#include <vector>
 
 #include "SynthesizerTrn.h"
+#include "summertts_hip.h"
 #include "utils.h"
 
 static void put32(char* p, uint32_t v) { memcpy(p, &v, 4); }
@@ -36,8 +41,67 @@ static int write_wav(const char* path, const int16_t* pcm, int32_t n) {
     return 0;
 }
 
+// "sid:weight[,sid:weight...]" -> the terms of one sts_speaker_mix
+static bool parse_mix(const char* s, std::vector<int32_t>& sid, std::vector<float>& weight) {
+    while (*s) {
+        char* end = NULL;
+        const long v = strtol(s, &end, 10);
+        if (end == s || *end != ':') return false;
+        s = end + 1;
+        const float w = strtof(s, &end);
+        if (end == s) return false;
+        sid.push_back((int32_t)v); weight.push_back(w);
+        s = end;
+        if (*s == ',') s++;
+        else if (*s) return false;
+    }
+    return !sid.empty();
+}
+
+// the --mix path: phoneme ids -> sts_set_speaker_mix -> sts_infer_ids
+static int run_mix(const std::string& line, const char* model, const char* out, const std::vector<int32_t>& sid, const std::vector<float>& weight) {
+    std::vector<int32_t> ids;
+    const char* s = line.c_str();
+    for (;;) {
+        char* end = NULL;
+        const long v = strtol(s, &end, 10);
+        if (end == s) break;
+        ids.push_back((int32_t)v);
+        s = end;
+    }
+    while (*s == ' ' || *s == '\t' || *s == '\r') s++;
+    if (*s || ids.empty()) { printf("--mix takes a file of phoneme ids\n"); return 2; }
+    float* dataW = NULL;
+    const int32_t modelSize = ttsLoadModel((char*)model, &dataW);
+    if (modelSize < 0) { printf("Failed to load %s\n", model); return 1; }
+    int dev = 0;
+    if (const char* d = getenv("SUMMERTTS_HIP_DEVICE")) dev = atoi(d);
+    sts_engine* e = NULL;
+    int rc = 0;
+    int16_t* pcm = NULL; int32_t n = 0;
+    const sts_speaker_mix mix = {(int32_t)sid.size(), sid.data(), weight.data(), NULL, 0.f};
+    if (sts_create(dataW, modelSize, dev, &e) != STS_OK || sts_set_speaker_mix(e, 1, &mix) != STS_OK ||
+        sts_infer_ids(e, ids.data(), (int32_t)ids.size(), 0, 1.0f, &pcm, &n) != STS_OK) {
+        printf("%s\n", sts_last_error());
+        rc = 2;
+    } else {
+        write_wav(out, pcm, n);
+        printf("%s: %d samples (%.2f s)\n", out, n, n / 16000.0);
+        sts_free(pcm);
+    }
+    if (e) sts_destroy(e);
+    tts_free_data(dataW);
+    return rc;
+}
+
 int main(int argc, char** argv) {
-    if (argc < 4) { printf("usage: %s <text-or-ids file> <model.bin> <out.wav>\n", argv[0]); return 1; }
+    std::vector<int32_t> mix_sid; std::vector<float> mix_weight;
+    const char* prog = argv[0];
+    if (argc >= 3 && strcmp(argv[1], "--mix") == 0) {
+        if (!parse_mix(argv[2], mix_sid, mix_weight)) { printf("--mix takes sid:weight[,sid:weight...]\n"); return 1; }
+        argv += 2; argc -= 2;
+    }
+    if (argc < 4) { printf("usage: %s [--mix sid:weight[,sid:weight...]] <text-or-ids file> <model.bin> <out.wav>\n", prog); return 1; }
     std::ifstream in(argv[1]);
     if (!in) { printf("Failed to open %s\n", argv[1]); return 0; }
     std::string line, sub;
@@ -45,6 +109,7 @@ int main(int argc, char** argv) {
         if (sub.size() >= 3 && (unsigned char)sub[0] == 0xEF && (unsigned char)sub[1] == 0xBB && (unsigned char)sub[2] == 0xBF) sub = sub.substr(3);
         line = line + sub + "  ";      // whole file = one utterance, as the reference demo does
     }
+    if (!mix_sid.empty()) return run_mix(line, argv[2], argv[3], mix_sid, mix_weight);
     float* dataW = NULL;
     int32_t modelSize = ttsLoadModel(argv[2], &dataW);
     if (modelSize < 0) { printf("Failed to load %s\n", argv[2]); return 1; }
