@@ -128,7 +128,9 @@ int sts_infer_ids_stream(sts_engine* e, const int32_t* ids, int32_t n, int32_t s
                          sts_chunk_cb cb, void* user, int32_t* n_total) {
     if (!e || !ids || !cb) return set_err(STS_EINVAL, "null argument");
     const int32_t* idp[1] = {ids};
-    StreamSpec ss{chunk_frames, cb, user};
+    struct { sts_chunk_cb cb; void* user; } one{cb, user};      // the engine's callback names the utterance; this one has a single one
+    using One = decltype(one);
+    StreamSpec ss{chunk_frames, [](void* u, int32_t, const int16_t* pcm, int32_t ns, int32_t off) { return ((One*)u)->cb(((One*)u)->user, pcm, ns, off); }, &one};
     const int rc = e->eng.run(1, idp, &n, &sid, &length_scale, &ss);
     if (rc != STS_OK) return set_err(rc, e->eng.error());
     if (n_total) *n_total = (int32_t)e->eng.total_samples;

@@ -375,8 +375,8 @@ int Engine::run_decode(RunCtx& c, int nw, long Wtot, int maxW, int zoff0, int wl
     {
         ConvOpt op;
         if (M.dec_type == 0 && ms && c.bstream) {
-            // batched streaming: the conditioning is indexed by window, not by utterance -- gather each window's speaker (the sid table of
-            // the step) and run dec_cond over the nw windows
+            // a stream of several utterances: the conditioning is indexed by window, not by utterance -- gather each window's speaker (the
+            // sid table of the step) and run dec_cond over the nw windows
             Lvl lw; lw.seg = SegView{nullptr, nullptr, 1, 0, 0, nw}; lw.nb = 1; lw.max_len = nw; lw.total = nw; lw.ld = nw;
             // (a run with a speaker mix: the step's table holds each window's UTTERANCE there, and the windows take that column of the blended
             // bt.g [gin][B] -- the same gather with bt.g as the table; a window's index is not its utterance's once a short one has finished)
@@ -459,8 +459,8 @@ int Engine::run_decode(RunCtx& c, int nw, long Wtot, int maxW, int zoff0, int wl
     return decode_end(c, wave, win, Wtot, maxW);
 }
 
-// the end of a decode: the "wave" tap; at a non-native output rate (and not streaming: run_output resamples each chunk) the resampler, which
-// writes the PCM of every window at the output rate, packed window after window
+// the end of a decode: the "wave" tap; at a non-native output rate (and not streaming: run_stream_steps resamples each step's windows) the
+// resampler, which writes the PCM of every window at the output rate, packed window after window
 int Engine::decode_end(RunCtx& c, const float* wave, const WinGeom& win, long Wtot, int maxW) {
     const int hop = c.hop, nw = win.nw, wlen0 = win.wlen0;
     const long long max_out = out_count((long long)maxW * hop);

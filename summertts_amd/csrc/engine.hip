@@ -935,8 +935,8 @@ int Engine::run_frame_workspace(RunCtx& c) {
     // ---------------- frame-level workspace.  The flow works on all Ftot frames; the decoder works on
     // "windows" of z: whole utterances normally (Wcap == Ftot), one chunk plus its two halos when streaming.
     const int halo = c.halo = stream_halo();
-    long Wcap = ss ? std::min<long>(Ftot, (long)ss->chunk_frames + 2 * halo) : Ftot;
-    if (c.bstream) {    // a step decodes at most one window per utterance, each at most a chunk plus two halos: sum_b min(F_b, C + 2 halo)
+    long Wcap = Ftot;
+    if (ss) {    // a step decodes at most one window per utterance, each at most a chunk plus two halos: sum_b min(F_b, C + 2 halo)
         Wcap = 0;
         for (int b = 0; b < B; b++) Wcap += std::min<long>(p_lenF[b], (long)ss->chunk_frames + 2 * halo);
     }
@@ -994,10 +994,12 @@ int Engine::run_frame_workspace(RunCtx& c) {
         bf.limws = lim && !ss ? A.get<char>((size_t)B * 16) : nullptr;
         bf.wave_lim = lim && !ss && record_taps ? A.get<float>((size_t)c.Ocap) : nullptr;
         bf.stab = nullptr; bf.spack = nullptr; bf.gwin = bf.cond_win = nullptr;
-        if (c.bstream) {
+        if (ss) {
             bf.stab = A.get<char>(stream_tab_bytes(B));
-            if (!resampling()) bf.spack = A.get<int16_t>((size_t)c.Ocap);     // (at another rate the resampler packs into bf.pcm)
-            if (M.dec_type == 0 && c.ms) { bf.gwin = A.get<float>((size_t)M.gin * B); bf.cond_win = A.get<float>((size_t)M.up_init * B); }
+            // (only stream_pack writes there: at another rate the resampler packs into bf.pcm, the limiter likewise, and one utterance's
+            // chunk is downloaded from where the decoder wrote it)
+            if (!resampling() && !lim && B > 1) bf.spack = A.get<int16_t>((size_t)c.Ocap);
+            if (M.dec_type == 0 && c.ms && c.bstream) { bf.gwin = A.get<float>((size_t)M.gin * B); bf.cond_win = A.get<float>((size_t)M.up_init * B); }
         }
     };
     c.Ocap = resampling() ? out_count((long long)Wcap * hop) + B : (long long)Wcap * hop;
@@ -1208,8 +1210,7 @@ int Engine::run_any_math(int B, const int32_t* const* ids, const int32_t* n, con
 int Engine::run_once(int B, const int32_t* const* ids, const int32_t* n, const int32_t* sid, const float* ls, const StreamSpec* ss) {
     Model& M = model;
     if (B <= 0 || !ids || !n) return fail(STS_EINVAL, "empty batch");
-    if (ss && (B == 1 ? ss->chunk_frames <= 0 || !ss->cb : ss->chunk_frames <= 0 || !ss->bcb))
-        return fail(STS_EINVAL, "streaming takes a positive chunk size and a callback (a per-utterance one for several utterances)");
+    if (ss && (ss->chunk_frames <= 0 || !ss->cb)) return fail(STS_EINVAL, "streaming takes a positive chunk size and a callback");
     HIPCK(hipSetDevice(device));
     taps.clear();
     memset(&prof, 0, sizeof(prof));
@@ -1304,71 +1305,9 @@ int Engine::run_output(RunCtx& c) {
         HIPCK(hipGetLastError());
         if (loud_mode != 0) loud_res.assign((const sts_loudness*)loud_host_, (const sts_loudness*)loud_host_ + B);   // (behind the run's last synchronisation)
         if (lim_mode != 0) { lim_res.resize(B); limiter_stats_decode(lim_host_, B, lim_res.data()); }
-    } else if (c.bstream) {
+    } else {
         const int rc = run_stream_steps(c);
         if (rc != STS_OK) return rc;
-        HIPCK(hipGetLastError());
-    } else {
-        // Streaming: chunk c = frames [f0, f1) is decoded from the window [f0 - halo, f1 + halo)
-        // clipped to the utterance; the halo covers the decoder's receptive field, so the kept samples are
-        // computed from exactly the inputs the one-pass decode sees (bit-identical for a pinned kernel variant).  PCM of a chunk goes to the caller before the next chunk starts.
-        if (ms && M.dec_type == 0 && B != 1) return fail(STS_EINVAL, "streaming is single-utterance");
-        const long F = Fcount;
-        int16_t* hp = nullptr;
-        const size_t hp_off = (up_bytes + ((size_t)Ttot + B) * 4 + 255) & ~(size_t)255;
-        if (!ensure_pinned(hp_off + (size_t)(out_count((long long)ss->chunk_frames * hop) + 1) * 2 + 256)) return fail(STS_EDEVICE, "pinned host allocation failed");
-        int* pm = c.pm = (int*)pinned_;
-        hp = (int16_t*)(pinned_ + hp_off);
-        poison_host16(hp, (size_t)out_count((long long)ss->chunk_frames * hop) + 1);
-        int* pw = pm + 5 * B + 2;
-        d_pcm = nullptr; total_samples = 0;
-        // limiter: chunk [j0, j1) is limited from the float signal over [j0 - 2H, j1 + 2H) clipped to the utterance (stream_halo covers it)
-        const bool slim = lim_mode != 0;
-        LimiterDesign ld;
-        if (slim && !limiter_design(out_rate, lim_gain_db, lim_ceiling, lim_ms, &ld)) return fail(STS_EINVAL, "limiter: output rate outside [8000, 48000]");
-        const long long Nout = out_count((long long)F * hop);
-        for (long f0 = 0; f0 < F; f0 += ss->chunk_frames) {
-            const long f1 = std::min<long>(F, f0 + ss->chunk_frames);
-            const long w0 = std::max<long>(0, f0 - halo), w1 = std::min<long>(F, f1 + halo);
-            pw[0] = (int)w0; pw[1] = 0; pw[2] = (int)(w1 - w0);
-            HIPCK(hipMemcpyAsync(d_win, pw, 3 * 4, hipMemcpyHostToDevice, stream));
-            const int rc = run_decode(c, 1, w1 - w0, (int)(w1 - w0), (int)w0, (int)(w1 - w0));
-            if (rc != STS_OK) return rc;
-            // native samples [f0 hop, f1 hop) of the utterance; at another output rate the outputs j with ceil(f0 hop P / Q) <= j < ceil(f1 hop P / Q),
-            // resampled from the window (the halo covers the filter's K samples beyond the chunk's edges too: stream_halo)
-            const long long j0 = out_count((long long)f0 * hop), j1 = out_count((long long)f1 * hop);
-            const long ns = (long)(j1 - j0);
-            const long long jl0 = slim ? std::max<long long>(0, j0 - 2 * ld.H) : j0, jl1 = slim ? std::min<long long>(Nout, j1 + 2 * ld.H) : j1;
-            if (resampling()) {
-                ResampleArgs a{};
-                a.x = bf.wave; a.seg = SegView{nullptr, nullptr, hop, 0, 0, (int)(w1 - w0)};
-                a.table = d_rs_table; a.P = rs.P; a.Q = rs.Q; a.K = rs.K;
-                a.pcm = slim ? bf.pcm_rs : bf.pcm; a.wave_out = slim ? bf.wave_out : nullptr;
-                a.stream = 1; a.u0 = (long long)w0 * hop; a.L_utt = (long long)F * hop; a.j0 = jl0; a.j1 = jl1;
-                resample_pcm(a, 1, jl1 - jl0, stream);
-            }
-            if (slim) {
-                LimArgs a{};
-                a.x = resampling() ? bf.wave_out : bf.wave;
-                a.H = ld.H; a.c = ld.c; a.G = ld.G;
-                a.pcm = bf.pcm;
-                a.use_seg1 = 1;
-                const long long sg[7] = {0, resampling() ? jl0 : (long long)w0 * hop, resampling() ? jl1 - jl0 : (long long)(w1 - w0) * hop, Nout, j0, j1, 0};
-                for (int i = 0; i < 7; i++) a.seg1[i] = sg[i];
-                limiter_run(a, 1, j1 - j0, stream);
-            }
-            HIPCK(hipMemcpyAsync(hp, resampling() || slim ? bf.pcm : bf.pcm + (f0 - w0) * hop, (size_t)ns * 2, hipMemcpyDeviceToHost, stream));
-            HIPCK(hipStreamSynchronize(stream));
-            if (conv_math == 3 && ovf_host_ && *(volatile unsigned*)ovf_host_ != 0u) {
-                if (f0 == 0) return kRetrySplitBf16;          // nothing has left yet (run() repeats the call)
-                h2_fallbacks++;
-                conv_math = 0;                                 // (run() restores the setting)
-                f0 -= ss->chunk_frames;                        // this chunk again
-                continue;
-            }
-            total_samples += ns;
-            if (ss->cb(ss->user, hp, (int32_t)ns, (int32_t)j0) != 0) break;
-        }
         HIPCK(hipGetLastError());
     }
     const long Ntot = Fcount * hop;
@@ -1404,12 +1343,14 @@ int Engine::run_output(RunCtx& c) {
     return STS_OK;
 }
 
-// ---- batched streaming (sts_infer_ids_batch_stream): step k decodes chunk k = frames [k C, min((k + 1) C, F_b)) of every live utterance b as
-// one window of a single decode pass -- the window [max(0, f0 - halo), min(F_b, f1 + halo)) at offF[b] + w0 of the packed z, the windows
-// packed in utterance order.  One kernel then gathers the windows' kept samples into one packed chunk buffer (stream_pack at the native
-// rate, the multi-window mode of resample_pcm otherwise), one download (or posted writes into mapped pinned memory: stream_direct), one
-// host synchronisation, and the step's chunks go to the caller in ascending utterance order before the next step is enqueued.  A window
-// is the single stream's window of the same chunk, so its kept samples are the single stream's (bit-identical for a pinned kernel variant).
+// ---- streaming (sts_infer_ids_stream, sts_infer_ids_batch_stream): step k decodes chunk k = frames [k C, min((k + 1) C, F_b))
+// of every live utterance b as one window of a single decode pass -- the window [max(0, f0 - halo), min(F_b, f1 + halo)) at offF[b] + w0 of
+// the packed z, the windows packed in utterance order.  The halo covers the decoder's receptive field, so the kept samples are computed from
+// exactly the inputs the one-pass decode sees (bit-identical for a pinned kernel variant).  One kernel then gathers the windows' kept samples
+// into one packed chunk buffer (stream_pack at the native rate, resample_pcm otherwise, the limiter behind either), one download (or posted
+// writes into mapped pinned memory: stream_direct), one host synchronisation, and the step's chunks go to the caller in ascending utterance
+// order before the next step is enqueued.  One utterance is the B == 1 case: its one window goes to run_decode by value, and at the native
+// rate without a limiter nothing is packed -- the chunk is downloaded from where the decoder wrote it.
 int Engine::run_stream_steps(RunCtx& c) {
     RUN_ALIASES(c)
     const long Cf = ss->chunk_frames;
@@ -1422,7 +1363,13 @@ int Engine::run_stream_steps(RunCtx& c) {
     c.pm = (int*)pinned_;
     char* const ht = pinned_ + hp_off;
     int16_t* hp = (int16_t*)(pinned_ + hp_off + tab_room);
-    int16_t* dst = resampling() ? bf.pcm : bf.spack;             // the step's packed chunks on the device
+    const bool slim = lim_mode != 0;
+    LimiterDesign ld;
+    if (slim && !limiter_design(out_rate, lim_gain_db, lim_ceiling, lim_ms, &ld)) return fail(STS_EINVAL, "limiter: output rate outside [8000, 48000]");
+    // the step's packed chunks on the device: written by the resampler, the limiter, or (native rate, no limiter) stream_pack -- which one
+    // utterance does without unless the chunks are to be stored into host memory
+    const bool pack = !resampling() && !slim && (B > 1 || stream_direct);
+    int16_t* dst = pack ? bf.spack : bf.pcm;
     if (stream_direct) {       // posted writes: the last kernel of a step stores the chunks into the mapped pinned buffer itself
         if (pcm_bytes > pinned_pcm_cap_ || !pinned_pcm_dev_) {
             (void)hipStreamSynchronize(stream);
@@ -1440,9 +1387,18 @@ int Engine::run_stream_steps(RunCtx& c) {
     if (ss->delivered) for (int b = 0; b < B; b++) ss->delivered[b] = 0;
     d_pcm = nullptr; total_samples = 0;
     std::vector<int> wb; std::vector<long long> wj0, wn, wdst;
-    const bool slim = lim_mode != 0;
-    LimiterDesign ld;
-    if (slim && !limiter_design(out_rate, lim_gain_db, lim_ceiling, lim_ms, &ld)) return fail(STS_EINVAL, "limiter: output rate outside [8000, 48000]");
+    // The window of chunk frames [f0, f1) of an utterance of F frames: frames [w0, w1).  Its native samples [f0 hop, f1 hop) are, at the output
+    // rate, the outputs j with ceil(f0 hop P / Q) <= j < ceil(f1 hop P / Q) = [j0, j1) of Nout (the halo covers the filter's K samples beyond the
+    // chunk's edges too: stream_halo).  The limiter produces them from the float signal over [jl0, jl1) = [j0 - 2H, j1 + 2H) clipped to the
+    // utterance (stream_halo covers that as well); without it [jl0, jl1) = [j0, j1).
+    struct Win { long w0, w1; long long j0, j1, jl0, jl1, Nout; };
+    auto window = [&](long F, long f0) {
+        const long f1 = std::min<long>(F, f0 + Cf);
+        Win w{std::max<long>(0, f0 - halo), std::min<long>(F, f1 + halo), out_count((long long)f0 * hop), out_count((long long)f1 * hop), 0, 0,
+              out_count((long long)F * hop)};
+        w.jl0 = slim ? std::max<long long>(0, w.j0 - 2 * ld.H) : w.j0; w.jl1 = slim ? std::min<long long>(w.Nout, w.j1 + 2 * ld.H) : w.j1;
+        return w;
+    };
     for (long k = 0;; k++) {
         const long f0 = k * Cf;
         wb.clear();
@@ -1457,34 +1413,34 @@ int Engine::run_stream_steps(RunCtx& c) {
         long Wtot = 0; int maxW = 0; long long dsum = 0, max_out = 0, max_rs = 0;
         for (int i = 0; i < nw; i++) {
             const int b = wb[i];
-            const long F = lenF[b], f1 = std::min<long>(F, f0 + Cf);
-            const long w0 = std::max<long>(0, f0 - halo), w1 = std::min<long>(F, f1 + halo);
-            const long long j0 = out_count((long long)f0 * hop), j1 = out_count((long long)f1 * hop);
-            ti[i] = offF[b] + (int)w0; ti[nw + i] = (int)Wtot; ti[2 * nw + i] = (int)(w1 - w0); ti[3 * nw + i] = c.mix ? b : sidv[b];      // (a mixed run: the window's utterance, a column of bt.g)
-            ti[4 * nw + i] = (int)((Wtot + (f0 - w0)) * hop); ti[5 * nw + i] = (int)dsum;
-            const long long Nout = out_count((long long)F * hop);
-            const long long jl0 = slim ? std::max<long long>(0, j0 - 2 * ld.H) : j0, jl1 = slim ? std::min<long long>(Nout, j1 + 2 * ld.H) : j1;
-            tl[5 * i] = (long long)w0 * hop; tl[5 * i + 1] = (long long)F * hop; tl[5 * i + 2] = jl0; tl[5 * i + 3] = jl1; tl[5 * i + 4] = slim ? rsum : dsum;
-            tm[7 * i] = resampling() ? rsum : (long long)Wtot * hop; tm[7 * i + 1] = resampling() ? jl0 : (long long)w0 * hop;
-            tm[7 * i + 2] = resampling() ? jl1 - jl0 : (long long)(w1 - w0) * hop; tm[7 * i + 3] = Nout;
-            tm[7 * i + 4] = j0; tm[7 * i + 5] = j1; tm[7 * i + 6] = dsum;
-            rsum += jl1 - jl0; max_rs = std::max(max_rs, jl1 - jl0);
-            wj0[i] = j0; wn[i] = j1 - j0; wdst[i] = dsum;
-            dsum += j1 - j0; max_out = std::max(max_out, j1 - j0);
-            Wtot += w1 - w0; maxW = std::max<int>(maxW, (int)(w1 - w0));
+            const long F = lenF[b];
+            const Win w = window(F, f0);
+            const long wlen = w.w1 - w.w0;
+            const long long nrs = w.jl1 - w.jl0, nout = w.j1 - w.j0;
+            ti[i] = offF[b] + (int)w.w0; ti[nw + i] = (int)Wtot; ti[2 * nw + i] = (int)wlen; ti[3 * nw + i] = c.mix ? b : sidv[b];      // (a mixed run: the window's utterance, a column of bt.g)
+            ti[4 * nw + i] = (int)((Wtot + (f0 - w.w0)) * hop); ti[5 * nw + i] = (int)dsum;
+            tl[5 * i] = (long long)w.w0 * hop; tl[5 * i + 1] = (long long)F * hop; tl[5 * i + 2] = w.jl0; tl[5 * i + 3] = w.jl1; tl[5 * i + 4] = slim ? rsum : dsum;
+            tm[7 * i] = resampling() ? rsum : (long long)Wtot * hop; tm[7 * i + 1] = resampling() ? w.jl0 : (long long)w.w0 * hop;
+            tm[7 * i + 2] = resampling() ? nrs : (long long)wlen * hop; tm[7 * i + 3] = w.Nout;
+            tm[7 * i + 4] = w.j0; tm[7 * i + 5] = w.j1; tm[7 * i + 6] = dsum;
+            rsum += nrs; max_rs = std::max(max_rs, nrs);
+            wj0[i] = w.j0; wn[i] = nout; wdst[i] = dsum;
+            dsum += nout; max_out = std::max(max_out, nout);
+            Wtot += wlen; maxW = std::max<int>(maxW, (int)wlen);
         }
         ti[6 * nw] = (int)dsum;
         HIPCK(hipMemcpyAsync(c.d_win, ht, stream_tab_bytes(nw), hipMemcpyHostToDevice, stream));
-        int rc = run_decode(c, nw, Wtot, maxW, 0, -1);
+        // one utterance: its window by value (no table load in the decoder's kernels); several: the tables, also while one window is live
+        int rc = B == 1 ? run_decode(c, 1, Wtot, maxW, ti[0], ti[2]) : run_decode(c, nw, Wtot, maxW, 0, -1);
         if (rc != STS_OK) return rc;
         if (resampling()) {
             ResampleArgs a{};
             a.x = bf.wave; a.seg = SegView{c.d_win + nw, c.d_win + 2 * nw, hop, 0, 0, 0};
             a.table = d_rs_table; a.P = rs.P; a.Q = rs.Q; a.K = rs.K;
             a.pcm = slim ? bf.pcm_rs : dst; a.wave_out = slim ? bf.wave_out : nullptr;
-            a.stream = 2; a.wtab = (const long long*)(bf.stab + stream_tab_ll_off(nw));
+            a.wtab = (const long long*)(bf.stab + stream_tab_ll_off(nw));
             resample_pcm(a, nw, max_rs, stream);
-        } else if (!slim) {
+        } else if (pack) {
             stream_pack(bf.pcm, dst, c.d_win + 4 * nw, c.d_win + 5 * nw, nw, max_out, stream);
         }
         if (slim) {          // every window of the step in one launch; it writes the packed chunks in place of the resampler / the pack
@@ -1495,7 +1451,9 @@ int Engine::run_stream_steps(RunCtx& c) {
             a.wtab = (const long long*)(bf.stab + stream_tab_lim_off(nw));
             limiter_run(a, nw, max_out, stream);
         }
-        if (!stream_direct) HIPCK(hipMemcpyAsync(hp, dst, (size_t)dsum * 2, hipMemcpyDeviceToHost, stream));
+        // (nothing packed: the one window's kept samples, at its pack source in the decoder's own PCM)
+        const int16_t* const src = resampling() || slim || pack ? dst : bf.pcm + ti[4 * nw];
+        if (!stream_direct) HIPCK(hipMemcpyAsync(hp, src, (size_t)dsum * 2, hipMemcpyDeviceToHost, stream));
         HIPCK(hipStreamSynchronize(stream));
         if (conv_math == 3 && ((ovf_host_ && *(volatile unsigned*)ovf_host_ != 0u) || (stream_retry_step >= 0 && k == stream_retry_step))) {
             if (k == 0) return kRetrySplitBf16;           // nothing has left yet (run() repeats the call)
@@ -1508,29 +1466,17 @@ int Engine::run_stream_steps(RunCtx& c) {
             const int b = wb[i];
             total_samples += wn[i];
             if (ss->delivered) ss->delivered[b] += (int32_t)wn[i];
-            if (ss->bcb(ss->user, b, hp + wdst[i], (int32_t)wn[i], (int32_t)wj0[i]) != 0) live[b] = 0;
+            if (ss->cb(ss->user, b, hp + wdst[i], (int32_t)wn[i], (int32_t)wj0[i]) != 0) live[b] = 0;
         }
     }
     return STS_OK;
 }
 
-namespace {
-struct OneUttAdapter { int (*cb)(void*, int32_t, const int16_t*, int32_t, int32_t); void* user; };
-int one_utt_cb(void* u, const int16_t* pcm, int32_t n, int32_t off) { const OneUttAdapter* a = (const OneUttAdapter*)u; return a->cb(a->user, 0, pcm, n, off); }
-}  // namespace
-
 int Engine::run_batch_stream(int B, const int32_t* const* ids, const int32_t* n, const int32_t* sid, const float* ls, int chunk_frames,
                              int (*cb)(void*, int32_t, const int16_t*, int32_t, int32_t), void* user, int32_t* n_total) {
     if (B < 1 || !ids || !n || chunk_frames <= 0 || !cb) return fail(STS_EINVAL, "batched streaming takes B >= 1 utterances, a positive chunk size and a callback");
-    if (B == 1) {              // the single stream itself
-        OneUttAdapter a{cb, user};
-        StreamSpec ss{chunk_frames, one_utt_cb, &a};
-        const int rc = run(1, ids, n, sid, ls, &ss);
-        if (rc == STS_OK && n_total) n_total[0] = (int32_t)total_samples;
-        return rc;
-    }
     std::vector<int32_t> got(B, 0);
-    StreamSpec ss{chunk_frames, nullptr, user, cb, got.data()};
+    StreamSpec ss{chunk_frames, cb, user, got.data()};
     const int rc = run(B, ids, n, sid, ls, &ss);
     if (rc == STS_OK && n_total) for (int b = 0; b < B; b++) n_total[b] = got[b];
     return rc;

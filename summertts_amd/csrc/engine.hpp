@@ -46,12 +46,10 @@ struct ConvOpt {
     const float* sum1 = nullptr; const float* sum2 = nullptr; int nsum = 0; float* sum_dst = nullptr; long sum_n = 0;
 };
 
-// streaming decode: PCM is handed to `cb` chunk by chunk (cb returns non-zero to stop)
+// streaming decode (Engine::run_stream_steps): the PCM of every utterance is handed to `cb` chunk by chunk; cb returns non-zero to stop
+// that utterance only.  delivered (optional, [B]): samples handed to cb per utterance
 struct StreamSpec {
-    int chunk_frames; int (*cb)(void* user, const int16_t* pcm, int32_t n_samples, int32_t sample_offset); void* user;
-    // batched streaming (B > 1, Engine::run_stream_steps): chunks of every utterance, per utterance; bcb returns non-zero to stop that
-    // utterance only.  delivered (optional, [B]): samples handed to bcb per utterance
-    int (*bcb)(void* user, int32_t utt, const int16_t* pcm, int32_t n_samples, int32_t sample_offset) = nullptr;
+    int chunk_frames; int (*cb)(void* user, int32_t utt, const int16_t* pcm, int32_t n_samples, int32_t sample_offset); void* user;
     int32_t* delivered = nullptr;
 };
 int decoder_halo_frames(const Model& M);   // decoder.hip
@@ -73,8 +71,8 @@ public:
     int init(const float* blob, int64_t bytes, int device);
     int run(int B, const int32_t* const* ids, const int32_t* n, const int32_t* sid, const float* ls, const StreamSpec* ss = nullptr);
     int run_once(int B, const int32_t* const* ids, const int32_t* n, const int32_t* sid, const float* ls, const StreamSpec* ss);
-    // batched streaming (sts_infer_ids_batch_stream): B utterances, chunk k of every live one decoded as the windows of one pass per step;
-    // B == 1 is the single stream (run with a one-utterance StreamSpec).  n_total (optional, [B]): samples delivered per utterance
+    // streaming (sts_infer_ids_batch_stream; sts_infer_ids_stream is its B == 1): B utterances, chunk k of every live one decoded as the
+    // windows of one pass per step.  n_total (optional, [B]): samples delivered per utterance
     int run_batch_stream(int B, const int32_t* const* ids, const int32_t* n, const int32_t* sid, const float* ls, int chunk_frames,
                          int (*cb)(void*, int32_t, const int16_t*, int32_t, int32_t), void* user, int32_t* n_total);
     const std::string& error() const { return err_; }
@@ -169,8 +167,8 @@ public:
     int h2p_tile = -1;                 // lab: tile code of conv_h2p_group (-1: automatic)
     int flow_fused = 1;                // 1: the reverse flow as one launch per WaveNet layer where eligible (wn_flow.hip; two-term fp16 arithmetic only);
                                        // 0: one launch per conv (sts_debug_set STS_DBG_FLOW_FUSED)
-    int stream_retry_step = -1;        // tests (STS_DBG_STREAM_RETRY_STEP): a batched stream under conv_math 3 treats the overflow word as raised after step k
-    int stream_direct = 0;             // batched streaming: 1 the pack / resample kernel writes each step's chunks into mapped pinned host memory, 0 one download (STS_DBG_STREAM_DIRECT)
+    int stream_retry_step = -1;        // tests (STS_DBG_STREAM_RETRY_STEP): a stream (of one utterance or several) under conv_math 3 treats the overflow word as raised after step k
+    int stream_direct = 0;             // streaming, any B: 1 the pack / resample / limiter kernel writes each step's chunks into mapped pinned host memory, 0 one download (STS_DBG_STREAM_DIRECT)
     unsigned poison = 0;               // tests (STS_DBG_POISON): 32-bit pattern every call fills its workspace arenas and host outputs with; 0 = off
     int64_t poison_bytes_ = 0;         // bytes the current call has filled so far (sts_profile.poison_bytes)
     hipStream_t stream = nullptr;

@@ -401,15 +401,13 @@ struct ResampleArgs {
     const float* x; SegView seg;         // native float wave, windows in frames (scale = samples per frame)
     const float* table; int P, Q, K;
     int16_t* pcm; float* wave_out;       // outputs, packed utterance after utterance; wave_out optional (taps)
-    // streaming (one window): the window holds utterance samples [u0, u0 + len) of L_utt; outputs [j0, j1) go to pcm[0 ..)
-    int stream; long long u0, L_utt, j0, j1;
-    // stream == 2 (batched streaming, several windows): window w reads {u0, L_utt, j0, j1, obase} from wtab[5 w ..] instead of the
-    // scalars above, and its outputs [j0, j1) go to pcm[obase ..) -- the windows' chunks packed back to back
+    // streaming (wtab != null): window w reads {u0, L_utt, j0, j1, obase} from wtab[5 w ..]: it holds utterance samples [u0, u0 + len) of
+    // L_utt, and its outputs [j0, j1) go to pcm[obase ..) -- the windows' chunks packed back to back
     const long long* wtab;
 };
 // grid: nwin windows x ceil(max_out / 1024) tiles; max_out = the most outputs one window emits
 void resample_pcm(const ResampleArgs& a, int nwin, long long max_out, hipStream_t st);
-// batched streaming at the native rate: window w's kept samples src[src_off[w] ..) -> dst[dst_off[w] .. dst_off[w + 1]) (one packed chunk
+// streaming at the native rate: window w's kept samples src[src_off[w] ..) -> dst[dst_off[w] .. dst_off[w + 1]) (one packed chunk
 // buffer per step); max_n = the most samples one window keeps
 void stream_pack(const int16_t* src, int16_t* dst, const int* src_off, const int* dst_off, int nwin, long long max_n, hipStream_t st);
 
@@ -452,8 +450,6 @@ struct LimArgs {
     // streaming: segment w reads {xbase, u0, xlen, N, j0, j1, dst} from wtab[7 w ..]: x[xbase .. xbase + xlen) holds samples [u0, u0 + xlen)
     // of an utterance of N, and outputs [j0, j1) go to y / pcm[dst ..)
     const long long* wtab;
-    // one streaming window without a table: the same seven values by value (use_seg1 != 0, wtab null)
-    int use_seg1; long long seg1[7];
 };
 // one memset (stat) + one launch; max_out = the most outputs one utterance (segment) emits, or more
 void limiter_run(const LimArgs& a, int B, long long max_out, hipStream_t st);

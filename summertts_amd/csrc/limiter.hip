@@ -53,8 +53,8 @@ __global__ __launch_bounds__(LM_THREADS) void limiter_kernel(LimArgs a) {
     __shared__ unsigned s_st[3];
     const int b = blockIdx.y, tid = threadIdx.x, lane = tid & 63;
     LmSeg g;
-    if (a.wtab || a.use_seg1) {
-        const long long* w = a.wtab ? a.wtab + 7 * (long long)b : a.seg1;
+    if (a.wtab) {
+        const long long* w = a.wtab + 7 * (long long)b;
         g = LmSeg{w[0], w[1], w[2], w[3], w[4], w[5], w[6]};
         if (tid < 3) s_st[tid] = 0u;
         __syncthreads();

@@ -110,9 +110,8 @@ __global__ __launch_bounds__(RS_THREADS) void resample_pcm_kernel(ResampleArgs a
     const long long P = a.P, Q = a.Q, K = a.K, T = 2 * a.K;
     const long long win = seg_len(a.seg, b), ib = seg_start(a.seg, b);     // window b: native samples [ib, ib + win) of x
     long long u0 = 0, L = win, j0 = 0, j1 = ceil_div_ll(win * P, Q);
-    long long obw = 0;                                                  // (stream 2: where window b's outputs start in pcm)
-    if (a.stream == 1) { u0 = a.u0; L = a.L_utt; j0 = a.j0; j1 = a.j1; }      // (one window: utterance samples [u0, u0 + win) of L)
-    else if (a.stream == 2) { const long long* t = a.wtab + 5 * b; u0 = t[0]; L = t[1]; j0 = t[2]; j1 = t[3]; obw = t[4]; }
+    long long obw = 0;                                                  // (streaming: where window b's outputs start in pcm)
+    if (a.wtab) { const long long* t = a.wtab + 5 * b; u0 = t[0]; L = t[1]; j0 = t[2]; j1 = t[3]; obw = t[4]; }   // (utterance samples [u0, u0 + win) of L)
     const long long t0 = j0 + (long long)blockIdx.x * RS_TILE;
     if (t0 >= j1) return;
     const long long t1 = t0 + RS_TILE < j1 ? t0 + RS_TILE : j1;
@@ -120,7 +119,7 @@ __global__ __launch_bounds__(RS_THREADS) void resample_pcm_kernel(ResampleArgs a
     // the frame counts yet)
     if (tid == 0) s_obase = 0;
     __syncthreads();
-    if (a.seg.off && !a.stream) {
+    if (a.seg.off && !a.wtab) {
         unsigned long long part = 0;
         for (int q = tid; q < b; q += RS_THREADS) part += (unsigned long long)ceil_div_ll((long long)a.seg.len[q] * a.seg.scale * P, Q);
         if (part) atomicAdd(&s_obase, part);

@@ -32,11 +32,11 @@ struct BufF {
     int16_t* pcm_rs; char* lws;
     // limiter: its raw result words [B][4], its float output (taps only)
     char* limws; float* wave_lim;
-    // batched streaming only (null otherwise): the step tables (stream_tab_bytes), the packed chunk buffer of a native-rate step, the
-    // per-window speaker vectors and decoder conditioning of a multi-speaker HiFi-GAN decoder
+    // streaming only (null otherwise): the step tables (stream_tab_bytes); several utterances: the packed chunk buffer stream_pack writes
+    // (native rate, no limiter), the per-window speaker vectors and decoder conditioning of a multi-speaker HiFi-GAN decoder
     char* stab; int16_t* spack; float *gwin, *cond_win;
 };
-// Batched streaming, the tables of one step with nw windows (one upload, c.d_win points at them): ints [zoff nw | coff nw | wlen nw | sid nw |
+// Streaming, the tables of one step with nw windows (one upload, c.d_win points at them): ints [zoff nw | coff nw | wlen nw | sid nw |
 // pack source nw | packed destination nw + 1], then from an 8-byte boundary the resampler's long long [nw][5] = {u0, L_utt, j0, j1, obase}
 static inline size_t stream_tab_ll_off(int nw) { return ((size_t)(6 * nw + 1) * 4 + 7) & ~(size_t)7; }
 // and behind them the limiter's segments, long long [nw][7] = {xbase, u0, xlen, N, j0, j1, dst} (LimArgs::wtab)
@@ -68,7 +68,7 @@ struct Engine::RunCtx {
     std::vector<unsigned long long> req_keys; std::vector<long> predF;      // launch-ahead memo: per-utterance request hashes, remembered frame counts (empty: not all known)
     int halo = 0; long Wcap = 0; int upS = 1; long Lsb = 0; int sbC = 0;
     long long Ocap = 0;             // PCM capacity in output samples (== Wcap * hop at the native rate)
-    bool bstream = false;           // batched streaming (ss with B > 1): decode windows are chunks of several utterances (run_stream_steps)
+    bool bstream = false;           // a stream of several utterances: window i of a step is not utterance i (run_decode gathers the conditioning per window)
     bool use_ff = false; int ffG = 0;
 };
 #define RUN_ALIASES(c)                                                                                                              \

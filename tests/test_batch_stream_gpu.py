@@ -135,6 +135,70 @@ def test_single_utterance_is_the_single_stream_under_auto():
         syn.close()
 
 
+def _offsets_run(offs):
+    pos = 0
+    for off, n in offs:
+        assert off == pos, (off, pos)
+        pos += n
+
+
+_ONE_UTT = [(k, r, lim, None) for k in ("ms_hifigan_sdp", "mbb_fix") for r, lim in ((44100, False), (16000, True), (44100, True))] + \
+           [("ms_hifigan_sdp", 16000, False, "direct"), ("ms_hifigan_sdp", 16000, False, "retry")]
+
+
+@pytest.mark.parametrize("kind,rate,lim,extra", _ONE_UTT, ids=lambda v: str(v))
+def test_one_utterance_is_the_one_window_step(kind, rate, lim, extra):
+    """sts_infer_ids_stream is the B = 1 case of the step loop: with the conv mode pinned its chunks are the one-pass PCM bit for bit and
+    every sample_offset is the running sum, for chunks below / at / above the halo, at another rate, with the limiter (1 ms look-ahead),
+    and with both.  (The native rate without a limiter is tests/test_parity_gpu.py::test_streaming_equals_one_pass for these kinds; here
+    only its two remaining forms: the chunks stored into host memory by the pack kernel, and the later-step split-bf16 repeat.)"""
+    cfg = sb.tiny_cfg(kind)
+    blob = sb.make_blob(cfg, 99)
+    ids = sb.synthetic_ids(13, cfg.vocab, salt=5)
+    sid = 1 if cfg.is_ms else 0
+    syn = engine.Synthesizer(blob)
+    syn.set_conv_mode(6)
+    syn.set_output_rate(rate)
+    if lim:
+        syn.set_limiter(engine.LIMITER_ON, 20.0, -1.0, 1.0)
+
+    def stream(chunk):
+        offs = []
+        chunks, _ = syn.infer_ids_stream(ids, chunk, sid, on_chunk=lambda pcm, off, t: offs.append((off, pcm.size)) and False)
+        _offsets_run(offs)
+        return chunks
+
+    if extra == "retry":
+        # the overflow word counts as raised after step 1: step 0 left in the two-term fp16 form, step 1 and the later ones are decoded in
+        # split-bf16 (tolerance and forced durations as in test_split_bf16_repeat_whole_call_and_later_step)
+        syn.set_conv_math("f16x2")
+        plain = stream(1)
+        dur = syn.durations(len(ids))
+        assert len(plain) > 2
+        syn.set_conv_math("bf16x3")
+        syn.set_forced_durations(dur)
+        bf3 = stream(1)
+        syn.set_conv_math("f16x2")
+        before = syn.profile()["conv_math_fallbacks"]
+        syn.debug_set("stream_retry_step", 1)
+        syn.set_forced_durations(dur)
+        got = stream(1)
+        syn.debug_set("stream_retry_step", -1)
+        assert syn.profile()["conv_math_fallbacks"] == before + 1
+        assert len(got) == len(plain) == len(bf3)
+        assert np.array_equal(got[0], plain[0])
+        for i in range(1, len(got)):
+            assert _lsb(got[i], bf3[i]) <= 1, i
+    else:
+        whole = syn.infer_ids(ids, sid)
+        assert whole.size > 0
+        if extra == "direct":
+            syn.debug_set("stream_direct", 1)
+        for chunk in (1, 7, syn.stream_halo_frames(), 100000):
+            assert np.array_equal(_cat(stream(chunk)), whole), chunk
+    syn.close()
+
+
 def test_stop_one_utterance():
     cfg = sb.tiny_cfg("ms_hifigan_sdp")
     blob = sb.make_blob(cfg, 21)
