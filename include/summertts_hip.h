@@ -324,9 +324,58 @@ int sts_get_speaker_embedding(const sts_engine* e, int32_t sid, float* out, int6
  * mixes == NULL: every entry is empty. */
 int sts_speaker_blend(int device, const float* table, int32_t speaker_num, int32_t gin, int32_t B, const int32_t* sid,
                       const sts_speaker_mix* mixes, float* g_out);
+/* ---- gain plans (no reference counterpart: SynthesizerTrn::infer has no volume control).  sts_set_gain_plan(e, B, n, plans) gives utterance b
+ * of the NEXT call (n[b] phonemes) the plan plans[b]: a gain per phoneme and the width of the transition across a phoneme boundary -- SSML
+ * <prosody volume> and <emphasis> over a span, ducking, muting one word.
+ * Valid (checked at the set call; otherwise STS_EINVAL and nothing changes): gain_db[i] is -INFINITY or finite in [-96, 24]; ramp_ms is
+ * finite and in [0, 50]; NaN anywhere is invalid.
+ * For one utterance, with the run's final durations d_i (after forced durations or a duration plan, if any) and hop = samples_per_frame:
+ * F = max(1, sum d_i) frames, N = F hop native samples, x[0 .. N) the decoder's float wave at the native 16 kHz (the tap "wave").
+ *   1 Design (host, float64; exactly what sts_gain_design returns): q_i = floor(10^(gain_db_i / 20) 2^20 + 0.5) as int32, q_i = 0 for
+ *     -INFINITY, q_i = 2^20 when gain_db == NULL; h = floor(ramp_ms 8 + 0.5), so 0 <= h <= 400: the transition is 2h + 1 native samples wide.
+ *   2 Step function: Q[t] = q_i for the phoneme i whose span [s_i hop, (s_i + d_i) hop) contains t, s_i = sum_{j < i} d_j.  A phoneme with
+ *     d_i = 0 owns nothing.  A sample no phoneme owns (the single frame of an utterance whose durations are all 0) has Q = 2^20.  Outside
+ *     the utterance Q[t] = Q[0] for t < 0 and Q[N - 1] for t >= N: no fade at the edges.
+ *   3 Sliding sum, exact: S[t] = sum Q[t - h .. t + h] in 64-bit integers (S < 2^34; the same in any evaluation order).
+ *   4 Envelope: env[t] = float32(float64(S[t]) / float64((2h + 1) 2^20)).
+ *   5 y[t] = x[t] * env[t], one fp32 multiply.  Where every Q of the window is 2^20, env = 1.0f exactly and y[t] = x[t] bit for bit.
+ * y replaces x as the input of everything downstream: decoder wave -> gain envelope -> resampler -> loudness -> limiter -> cast.  With
+ * nothing downstream (native rate, loudness mode 0 or 1, limiter off) the gain kernel writes the PCM itself with the reference's cast
+ * (int16)(int32)(y * 32737).  A positive gain can take |y| past 1.0009, where that cast wraps around as the reference's does: the limiter
+ * (sts_set_limiter) is the remedy.
+ * Taps: "wave" stays the un-gained signal; "wave_gain" is y (recorded only by a one-pass run that had a plan); "wave_out" and "wave_lim"
+ * are computed from y.
+ * The plan is copied and applies to the next run only, whatever that run's outcome (the lifetime of a duration plan), in every call form:
+ * sts_infer_ids, sts_infer_ids_batch, sts_run_batch, sts_infer_ids_stream, sts_infer_ids_batch_stream.  That run must have the same B and
+ * n[b]: otherwise it answers STS_EINVAL, nothing runs and the plan is dropped.  B == 0 or plans == NULL drops a pending plan.  An utterance
+ * whose entry has gain_db == NULL is synthesised as without a plan, bit for bit; a call with no plan pending launches, allocates and uploads
+ * nothing new.  A planned call launches one kernel behind the decoder's last one; its q table rides in the run's one upload, and nothing
+ * waits on the host: the durations stay on the device.  The plan is independent of forced durations, duration plans, speaker mixes, noise,
+ * output rate, loudness, limiter and conv math (the split-bf16 repeat of a call applies the same plan again); a run with a gain plan
+ * neither reads nor feeds the launch-ahead memo (STS_DBG_LAUNCH_AHEAD).
+ * Streaming: a window's decoded native samples are gained at their absolute positions t before the resampler or the limiter reads them,
+ * the halo samples those two read beyond a chunk included.  The envelope is pointwise in t: sts_stream_halo_frames does not change, and
+ * concatenated chunks equal the whole-utterance PCM (bit for bit under a pinned conv mode, within 1 LSB otherwise). */
+typedef struct sts_gain_plan {
+    const float* gain_db;   /* [n] or NULL: per-phoneme gain in dB; -INFINITY = mute */
+    float        ramp_ms;   /* width of the transition across a phoneme boundary */
+} sts_gain_plan;
+int sts_set_gain_plan(sts_engine* e, int32_t B, const int32_t* n, const sts_gain_plan* plans);
+/* Host only (no device): the validity rules above for B plans of n[b] >= 1 phonemes each. */
+int sts_gain_plan_check(int32_t B, const int32_t* n, const sts_gain_plan* plans);
+/* Host only (no device), like sts_limiter_design: step 1 above for one utterance of n >= 1 phonemes (gain_db may be NULL); each of q ([n])
+ * and h is set when non-null.  STS_EINVAL for an invalid plan. */
+int sts_gain_design(const float* gain_db, int32_t n, float ramp_ms, int32_t* q, int32_t* h);
+/* The same kernel on caller signals, like sts_limiter_apply: B float signals packed back to back in x (host memory); utterance b has
+ * lengths[b] >= 1 phonemes with the durations dur_frames (>= 0, packed for the whole batch) and its signal is max(1, sum d)
+ * samples_per_frame samples long (samples_per_frame >= 1; B <= 65535).  y (float) and pcm (int16) receive the gained signals packed like x; each may
+ * be NULL. */
+int sts_gain_plan_apply(int device, const float* x, const int32_t* dur_frames, const int32_t* lengths, int32_t B, int32_t samples_per_frame,
+                        const sts_gain_plan* plans, float* y, int16_t* pcm);
 /*   record intermediate tensors of the next run: "x_enc","m","logs","logw","z_p","z","wave","wave_out" ("logs": the second half of the
  *   encoder projection, computed only by runs that record taps or sample the prior; "wave_out": the resampled float wave, only at a
- *   non-native output rate, one-pass calls; "dur_w": the planned duration weights, only a run with a duration plan) */
+ *   non-native output rate, one-pass calls; "dur_w": the planned duration weights, only a run with a duration plan; "wave_gain": the
+ *   gained native float wave, only a one-pass run with a gain plan) */
 int sts_set_record_taps(sts_engine* e, int enable);
 /*   fetch a tap: malloc()'d copy, channel-major [channels][total_len] (== the reference's column-major
  *   MatrixXf [time, channels]); for batches the utterances are packed along time. */
@@ -519,6 +568,11 @@ int64_t sts_pool_submit_plan(sts_pool* p, const int32_t* ids, int32_t n, int32_t
  *   plain sid; an invalid mix answers STS_EINVAL).  Whole-utterance requests only.  Mixed and plain requests share one packed batch. */
 int64_t sts_pool_submit_mix(sts_pool* p, const int32_t* ids, int32_t n, int32_t sid, float length_scale, float noise_scale,
                             float noise_scale_w, uint64_t seed, const sts_speaker_mix* mix);
+/*   sts_pool_submit_gain: sts_pool_submit_ex with this request's own gain plan (sts_set_gain_plan: gain_db holds n entries or is NULL;
+ *   copied; NULL or an entry with gain_db == NULL = no plan; an invalid plan answers STS_EINVAL).  Whole-utterance requests only.  Requests
+ *   with and without a plan share one packed batch: the plan is per utterance, and a member without one keeps its samples bit for bit. */
+int64_t sts_pool_submit_gain(sts_pool* p, const int32_t* ids, int32_t n, int32_t sid, float length_scale, float noise_scale,
+                             float noise_scale_w, uint64_t seed, const sts_gain_plan* plan);
 
 /* ---- multi-device batch (no reference counterpart).  One host process drives n_devices GPUs:
  * one engine (weights replicated) and one worker thread per entry of `devices` (HIP device indices; an index may repeat,
@@ -563,6 +617,10 @@ int sts_multi_set_duration_plan(sts_multi* m, int32_t B, const int32_t* n, const
  *   (otherwise STS_EINVAL, nothing runs and the mix is dropped).  mixes[b] belongs to utterance b of the caller's batch and follows it into
  *   its device's shard: the PCM does not depend on the number of devices. */
 int sts_multi_set_speaker_mix(sts_multi* m, int32_t B, const sts_speaker_mix* mixes);
+/*   sts_multi_set_gain_plan: sts_set_gain_plan for the NEXT sts_multi_infer_ids_batch of the handle, which must have the same B and n[b]
+ *   (otherwise STS_EINVAL, nothing runs and the plan is dropped).  plans[b] belongs to utterance b of the caller's batch and follows it into
+ *   its device's shard: the PCM does not depend on the number of devices. */
+int sts_multi_set_gain_plan(sts_multi* m, int32_t B, const int32_t* n, const sts_gain_plan* plans);
 /*   test hook: the shared library that provides the nccl* entry points (NULL / "" = librccl.so.1) and whether STS_MULTI_RCCL may list
  *   one device several times (tests/fake_rccl: N emulated ranks on one GPU; real RCCL refuses duplicates).  Only before the first
  *   STS_MULTI_RCCL handle of the process is created.  TEST-ONLY: refused with STS_ESTATE unless the process environment carries

@@ -271,6 +271,84 @@ int sts_speaker_blend(int device, const float* table, int32_t speaker_num, int32
     return STS_OK;
 }
 
+int sts_set_gain_plan(sts_engine* e, int32_t B, const int32_t* n, const sts_gain_plan* plans) {
+    if (!e) return set_err(STS_EINVAL, "null engine");
+    const int rc = e->eng.set_gain_plan(B, n, plans);
+    return rc == STS_OK ? STS_OK : set_err(rc, e->eng.error());
+}
+int sts_gain_plan_check(int32_t B, const int32_t* n, const sts_gain_plan* plans) {
+    if (B < 0 || (B > 0 && (!n || !plans))) return set_err(STS_EINVAL, "gain plan: B >= 0 plans and their phoneme counts are required");
+    for (int b = 0; b < B; b++) {
+        const char* why = nullptr;
+        if (!gain_plan_valid(n[b], plans[b].gain_db, plans[b].ramp_ms, &why)) return set_err(STS_EINVAL, why);
+    }
+    return STS_OK;
+}
+int sts_gain_design(const float* gain_db, int32_t n, float ramp_ms, int32_t* q, int32_t* h) {
+    const char* why = nullptr;
+    if (!gain_plan_valid(n, gain_db, ramp_ms, &why)) return set_err(STS_EINVAL, why);
+    gain_design(gain_db, n, ramp_ms, q, h);
+    return STS_OK;
+}
+int sts_gain_plan_apply(int device, const float* x, const int32_t* dur_frames, const int32_t* lengths, int32_t B, int32_t samples_per_frame,
+                        const sts_gain_plan* plans, float* y, int16_t* pcm) {
+    if (B < 1 || B > 65535 || !x || !dur_frames || !lengths || !plans || samples_per_frame < 1 || samples_per_frame > (1 << 20))      // (one grid row per signal)
+        return set_err(STS_EINVAL, "1 <= B <= 65535 signals, their durations, phoneme counts and plans, and samples_per_frame >= 1 are required");
+    const int hop = samples_per_frame;
+    // host tables [offT B | lenT B | offF B | lenF B | h B | cum T | q T]: the geometry the engine keeps on the device
+    int64_t T = 0;
+    for (int b = 0; b < B; b++) {
+        const char* why = nullptr;
+        if (lengths[b] < 1 || !gain_plan_valid(lengths[b], plans[b].gain_db, plans[b].ramp_ms, &why)) return set_err(STS_EINVAL, why ? why : "every utterance needs lengths[b] >= 1 phonemes");
+        T += lengths[b];
+        if (T > (1 << 24)) return set_err(STS_EINVAL, "batch too large");
+    }
+    std::vector<int32_t> tab((size_t)5 * B + 2 * (size_t)T);
+    int32_t *offT = tab.data(), *lenT = offT + B, *offF = lenT + B, *lenF = offF + B, *hh = lenF + B, *cum = hh + B, *q = cum + T;
+    int64_t t = 0, F = 0, maxF = 0;
+    for (int b = 0; b < B; b++) {
+        int64_t f = 0;
+        for (int i = 0; i < lengths[b]; i++) {
+            const int32_t d = dur_frames[t + i];
+            if (d < 0 || d > kDurMax) return set_err(STS_EINVAL, "durations must be in [0, 100000]");
+            f += d;
+            if (f > ((int64_t)1 << 30)) return set_err(STS_EINVAL, "the signals must hold at most 2^30 samples in all");
+            cum[t + i] = (int32_t)f;
+        }
+        if (f < 1) f = 1;
+        gain_design(plans[b].gain_db, lengths[b], plans[b].ramp_ms, q + t, hh + b);
+        offT[b] = (int32_t)t; lenT[b] = lengths[b]; offF[b] = (int32_t)F; lenF[b] = (int32_t)f;
+        t += lengths[b]; F += f; maxF = std::max(maxF, f);
+        if (F * hop > ((int64_t)1 << 30)) return set_err(STS_EINVAL, "the signals must hold at most 2^30 samples in all");
+    }
+    const int64_t total = F * hop;
+    if (hipSetDevice(device) != hipSuccess) return set_err(STS_EDEVICE, "no such device");
+    auto pad = [](size_t bytes) { return (bytes + 255) & ~(size_t)255; };
+    const size_t xb = pad((size_t)total * 4), tb = pad(tab.size() * 4), pb = pad((size_t)total * 2);
+    char* d = nullptr;          // [x | tables | y | pcm]
+    if (hipMalloc((void**)&d, 2 * xb + tb + pb) != hipSuccess) return set_err(STS_EDEVICE, "out of device memory");
+    hipStream_t st = nullptr;
+    bool ok = hipStreamCreate(&st) == hipSuccess;
+    const int* dt = (const int*)(d + xb);
+    GainArgs a{};
+    a.x = (const float*)d; a.y = y ? (float*)(d + xb + tb) : nullptr; a.pcm = pcm ? (int16_t*)(d + 2 * xb + tb) : nullptr;
+    a.wseg = SegView{dt + 2 * B, dt + 3 * B, hop, 0, 0, 0}; a.hop = hop;
+    a.tseg = SegView{dt, dt + B, 1, 0, 0, 0};
+    a.h = dt + 4 * B; a.cum = dt + 5 * B; a.q = dt + 5 * B + T;
+    ok = ok && hipMemcpyAsync(d, x, (size_t)total * 4, hipMemcpyHostToDevice, st) == hipSuccess &&
+         hipMemcpyAsync(d + xb, tab.data(), tab.size() * 4, hipMemcpyHostToDevice, st) == hipSuccess;
+    if (ok) {
+        gain_plan_run(a, B, maxF * hop, st);
+        ok = hipGetLastError() == hipSuccess &&
+             (!y || hipMemcpyAsync(y, a.y, (size_t)total * 4, hipMemcpyDeviceToHost, st) == hipSuccess) &&
+             (!pcm || hipMemcpyAsync(pcm, a.pcm, (size_t)total * 2, hipMemcpyDeviceToHost, st) == hipSuccess) &&
+             hipStreamSynchronize(st) == hipSuccess;
+    }
+    if (st) (void)hipStreamDestroy(st);
+    (void)hipFree(d);
+    return ok ? STS_OK : set_err(STS_EDEVICE, "the gain plan failed on the device");
+}
+
 int sts_set_noise(sts_engine* e, float noise_scale, float noise_scale_w, uint64_t seed) {
     if (!e) return set_err(STS_EINVAL, "null engine");
     if (!noise_scale_valid(noise_scale) || !noise_scale_valid(noise_scale_w)) return set_err(STS_EINVAL, "noise scales must be finite and >= 0");

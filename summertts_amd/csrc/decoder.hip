@@ -428,7 +428,7 @@ int Engine::run_decode(RunCtx& c, int nw, long Wtot, int maxW, int zoff0, int wl
     // ---------------- decoder tail
     // (at a non-native output rate the tail always writes the float wave, and its int16 samples go to a scratch buffer: the resampler below
     // produces the PCM from the wave)
-    float* wave = record_taps || resampling() || lim_mode != 0 || (loud_mode != 0 && !ss) ? bf.wave : nullptr;
+    float* wave = record_taps || resampling() || lim_mode != 0 || (loud_mode != 0 && !ss) || c.gain ? bf.wave : nullptr;
     int16_t* const pcm = bf.pcm_nat;
     const long Ntot = Wtot * hop;
     if (M.dec_type == 0) {          // Generator_hifigan.cpp:177-179 + SynthesizerTrn.cpp:389-396
@@ -464,6 +464,19 @@ int Engine::run_decode(RunCtx& c, int nw, long Wtot, int maxW, int zoff0, int wl
 int Engine::decode_end(RunCtx& c, const float* wave, const WinGeom& win, long Wtot, int maxW) {
     const int hop = c.hop, nw = win.nw, wlen0 = win.wlen0;
     const long long max_out = out_count((long long)maxW * hop);
+    const float* const raw = wave;          // (the "wave" tap stays the un-gained signal)
+    if (c.gain) {
+        // the gain plan on every window's native samples at their absolute positions (a streaming window: halo included), one launch; it
+        // writes the PCM too when nothing downstream does (native rate, no gain cast, no limiter).  Everything below reads its output
+        GainArgs g{};
+        g.x = wave; g.y = c.bf.wave_gain;
+        g.pcm = !resampling() && lim_mode == 0 && !(loud_mode == 2 && !c.ss) ? c.bf.pcm : nullptr;
+        g.wseg = win.seg(hop, 0); g.hop = hop;
+        if (c.ss) { g.utt = (const int*)(c.bf.stab + stream_tab_utt_off(nw)); g.wtab = (const long long*)(c.bf.stab + stream_tab_ll_off(nw)); }
+        g.tseg = c.lvT.seg; g.cum = c.bt.cum; g.q = c.bt.gain_q; g.h = c.bt.gain_h;
+        gain_plan_run(g, nw, (long long)maxW * hop, stream);
+        wave = c.bf.wave_gain;
+    }
     // LoudArgs / LimArgs: the float signal at the output rate and its utterances' lengths
     auto signal = [&](auto& a) {
         a.x = resampling() ? c.bf.wave_out : wave;
@@ -506,8 +519,9 @@ int Engine::decode_end(RunCtx& c, const float* wave, const WinGeom& win, long Wt
         HIPCK(hipMemcpyAsync(lim_host_, c.bf.limws, (size_t)nw * 16, hipMemcpyDeviceToHost, stream));
     }
     mark(4);
-    if (wave && record_taps) {
-        tap("wave", wave, 1, Wtot * hop, (wlen0 >= 0 ? (long)wlen0 : Wtot) * hop);
+    if (raw && record_taps) {
+        tap("wave", raw, 1, Wtot * hop, (wlen0 >= 0 ? (long)wlen0 : Wtot) * hop);
+        if (c.gain && !c.ss) tap("wave_gain", c.bf.wave_gain, 1, Wtot * hop, (wlen0 >= 0 ? (long)wlen0 : Wtot) * hop);
         if ((c.bf.wave_out || c.bf.wave_lim) && !c.ss) {    // (a stream has moved the pinned block p_lenF points into: not read then)
             long long n = 0;        // samples at the output rate: what both taps hold
             if (wlen0 >= 0) n = out_count((long long)wlen0 * hop);

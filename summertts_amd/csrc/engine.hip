@@ -407,6 +407,28 @@ int Engine::set_speaker_mix(int B, const sts_speaker_mix* mixes) {
     have_mix = true;
     return STS_OK;
 }
+// sts_set_gain_plan: validated and designed here (q per phoneme, h per utterance); an invalid plan changes nothing.  B == 0 or plans == null
+// drops a pending plan.
+int Engine::set_gain_plan(int B, const int32_t* n, const sts_gain_plan* plans) {
+    if (B == 0 || !plans) { have_gain = false; return STS_OK; }
+    if (B < 0 || !n) return fail(STS_EINVAL, "gain plan: B >= 0 and n are required");
+    long total = 0;
+    for (int b = 0; b < B; b++) {
+        const char* why = nullptr;
+        if (!gain_plan_valid(n[b], plans[b].gain_db, plans[b].ramp_ms, &why)) return fail(STS_EINVAL, why);
+        total += n[b];
+        if (total > (1 << 24)) return fail(STS_EINVAL, "batch too large");
+    }
+    gain_n.assign(n, n + B);
+    gain_words.assign((size_t)total + (size_t)B, 0);
+    size_t off = 0;
+    for (int b = 0; b < B; b++) {
+        gain_design(plans[b].gain_db, n[b], plans[b].ramp_ms, gain_words.data() + off, gain_words.data() + total + b);
+        off += (size_t)n[b];
+    }
+    have_gain = true;
+    return STS_OK;
+}
 // sts_get_speaker_embedding: row sid of the device-resident table (one strided copy of gin floats)
 int Engine::speaker_embedding(int sid, float* out, int64_t capacity) const {
     if (!out) return STS_EINVAL;
@@ -468,7 +490,14 @@ int Engine::run_setup(RunCtx& c) {
         if (!same) return fail(STS_EINVAL, "the duration plan was set for another batch (B and every n[b] must match)");
     }
     if (have_mix && mix_B != B) return fail(STS_EINVAL, "the speaker mix was set for another batch (B must match)");      // (run() drops it)
+    if (have_gain) {
+        bool same = (int)gain_n.size() == B;
+        for (int b = 0; b < B && same; b++) same = gain_n[b] == n[b];
+        if (!same) return fail(STS_EINVAL, "the gain plan was set for another batch (B and every n[b] must match)");      // (run() drops it)
+    }
     const bool plan = c.plan = have_plan;
+    const bool gain = c.gain = have_gain;
+    const size_t gain_ints = gain ? gain_words.size() : 0;                 // [q Ttot | h B], between the mix and the plan
     const bool mix = c.mix = have_mix && M.is_ms == 1;       // (a single-speaker model accepts empty entries only: nothing to blend)
     const size_t mix_ints = mix ? mix_words.size() : 0;                    // the term table, between the ids and the plan
     const size_t plan_ints = plan ? 2 * (size_t)Ttot + (size_t)B : 0;      // [rate Ttot | fixed Ttot | target B] behind the ids
@@ -494,17 +523,19 @@ int Engine::run_setup(RunCtx& c) {
         // one device block mirroring the pinned staging block [geometry ints | length scales | noise scales, seeds | ids | forced
         // durations]: a single host-to-device copy per run
         // (a run with a duration plan: the plan's arrays ride in the same copy, between the ids and `forced`, which the plan kernel then writes;
-        // a run with a speaker mix: its term table too, right behind the ids)
-        bt.meta_i = A.get<int>((size_t)9 * B + 8 + 5 * (size_t)B + 2 * (size_t)Ttot + mix_ints + plan_ints);
+        // a run with a speaker mix: its term table too, right behind the ids; a run with a gain plan: its q / h table behind that)
+        bt.meta_i = A.get<int>((size_t)9 * B + 8 + 5 * (size_t)B + 2 * (size_t)Ttot + mix_ints + gain_ints + plan_ints);
         bt.ls = (float*)(bt.meta_i + ((size_t)9 * B + 8));
         bt.ns = bt.ls + B; bt.nsw = bt.ns + B;
         bt.seed = (uint64_t*)(bt.nsw + B);      // (9B + 8 + 3B ints from a 256-byte boundary: 8-byte aligned)
         bt.ids = (int*)(bt.seed + B);
         bt.mix = mix ? bt.ids + Ttot : nullptr;
-        bt.plan_rate = plan ? (float*)(bt.ids + Ttot + mix_ints) : nullptr;
-        bt.plan_fixed = plan ? bt.ids + 2 * Ttot + mix_ints : nullptr;
-        bt.plan_target = plan ? bt.ids + 3 * Ttot + mix_ints : nullptr;
-        bt.forced = bt.ids + Ttot + mix_ints + plan_ints;
+        bt.gain_q = gain ? bt.ids + Ttot + mix_ints : nullptr;
+        bt.gain_h = gain ? bt.ids + 2 * Ttot + mix_ints : nullptr;
+        bt.plan_rate = plan ? (float*)(bt.ids + Ttot + mix_ints + gain_ints) : nullptr;
+        bt.plan_fixed = plan ? bt.ids + 2 * Ttot + mix_ints + gain_ints : nullptr;
+        bt.plan_target = plan ? bt.ids + 3 * Ttot + mix_ints + gain_ints : nullptr;
+        bt.forced = bt.ids + Ttot + mix_ints + gain_ints + plan_ints;
         bt.x = A.get<float>((size_t)H * Ttot); bt.qkv = A.get<float>((size_t)3 * H * Ttot);
         bt.att = A.get<float>((size_t)H * Ttot); bt.y = A.get<float>((size_t)H * Ttot * ffn2_slices);
         bt.x1 = A.get<float>((size_t)H * Ttot); bt.ffh = A.get<float>((size_t)FF * Ttot);
@@ -531,7 +562,7 @@ int Engine::run_setup(RunCtx& c) {
 
     // ---------------- one H2D: geometry + ids (+ forced durations)
     const size_t meta_ints = c.meta_ints = (size_t)9 * B + 8;
-    const size_t up_bytes = c.up_bytes = (meta_ints + 5 * (size_t)B + 2 * (size_t)Ttot + mix_ints + plan_ints) * 4 + 1024;
+    const size_t up_bytes = c.up_bytes = (meta_ints + 5 * (size_t)B + 2 * (size_t)Ttot + mix_ints + gain_ints + plan_ints) * 4 + 1024;
     if (!ensure_pinned(up_bytes + ((size_t)Ttot + B) * 4)) return fail(STS_EDEVICE, "pinned host allocation failed");
     int* pm = c.pm = (int*)pinned_;
     int* p_offT = c.p_offT = pm, *p_lenT = c.p_lenT = pm + B, *p_sid = c.p_sid = pm + 2 * B, *p_one = c.p_one = pm + 5 * B;
@@ -548,14 +579,15 @@ int Engine::run_setup(RunCtx& c) {
     int* p_ids = (int*)(p_seed + B);
     for (int b = 0; b < B; b++) memcpy(p_ids + offT[b], ids[b], sizeof(int) * n[b]);
     if (mix) memcpy(p_ids + Ttot, mix_words.data(), sizeof(int) * mix_ints);
-    int* p_forced = p_ids + Ttot + mix_ints;
+    if (gain) memcpy(p_ids + Ttot + mix_ints, gain_words.data(), sizeof(int) * gain_ints);
+    int* p_forced = p_ids + Ttot + mix_ints + gain_ints;
     if (have_forced) memcpy(p_forced, forced_dur.data(), sizeof(int) * Ttot);
     if (plan) {          // (never together with forced durations: the plan's arrays take their place in the copy)
-        memcpy(p_ids + Ttot + mix_ints, plan_rate.data(), sizeof(float) * Ttot);
-        memcpy(p_ids + 2 * Ttot + mix_ints, plan_fixed.data(), sizeof(int) * Ttot);
-        memcpy(p_ids + 3 * Ttot + mix_ints, plan_target.data(), sizeof(int) * B);
+        memcpy(p_ids + Ttot + mix_ints + gain_ints, plan_rate.data(), sizeof(float) * Ttot);
+        memcpy(p_ids + 2 * Ttot + mix_ints + gain_ints, plan_fixed.data(), sizeof(int) * Ttot);
+        memcpy(p_ids + 3 * Ttot + mix_ints + gain_ints, plan_target.data(), sizeof(int) * B);
     }
-    HIPCK(hipMemcpyAsync(bt.meta_i, pm, (meta_ints + 5 * (size_t)B + (size_t)Ttot * (have_forced ? 2 : 1) + mix_ints + plan_ints) * 4, hipMemcpyHostToDevice, stream));
+    HIPCK(hipMemcpyAsync(bt.meta_i, pm, (meta_ints + 5 * (size_t)B + (size_t)Ttot * (have_forced ? 2 : 1) + mix_ints + gain_ints + plan_ints) * 4, hipMemcpyHostToDevice, stream));
     if (B > 1) HIPCK(hipEventRecord(ev_setup_, stream));     // (run_durations, batches launched from the memo: the host rewrites part of this block)
 
     // single-segment views travel by value (kernels.hpp SegView): no segment-table load in the kernels of a one-utterance call
@@ -759,7 +791,7 @@ int Engine::run_durations(RunCtx& c) {
         c.req_keys[b] = h | 1ull;
     }
     c.predF.clear();
-    if (launch_ahead && !ss && !have_forced && !c.plan && !c.mix && !record_taps && mapped) {     // (a planned or mixed run's frame count is not a function of the memo's key)
+    if (launch_ahead && !ss && !have_forced && !c.plan && !c.mix && !c.gain && !record_taps && mapped) {     // (a planned or mixed run's frame count is not a function of the memo's key; a run with a gain plan stays off the memo by contract)
         c.predF.resize(B);
         for (int b = 0; b < B; b++) {
             const auto it = seen_tf_.find(c.req_keys[b]);
@@ -782,7 +814,7 @@ int Engine::run_durations(RunCtx& c) {
     durations(r_final, M.dur_type == 0 ? 1 : 0, M.ea_m, M.ea_logs, bt.ls, (have_forced || c.plan) ? bt.forced : nullptr, bt.dlogw,
               bt.dur, bt.cum, bt.frames, lvT.seg, B, stream, mapped ? hmap_dev_ : nullptr, Ttot, seq_, arrive_,
               c.ahead ? c.d_lenF : nullptr, c.ahead ? c.d_win + 2 : nullptr, (int)cap);
-    c.forced = have_forced || c.plan || c.mix;      // (none of these runs feeds the memo: its key hashes sid, not the mix)
+    c.forced = have_forced || c.plan || c.mix || c.gain;      // (none of these runs feeds the memo: its key hashes sid, not the mix)
     have_forced = false;
     mark(2);
     sync_wait_ms_ = 0;
@@ -985,9 +1017,12 @@ int Engine::run_frame_workspace(RunCtx& c) {
         } else { bf.tailA = bf.tailB = bf.tailC = nullptr; }
         // (loudness: the tail always writes the float wave, the resampler its float output; normalising, their int16 samples go to
         // scratch and the gain cast writes bf.pcm; the limiter likewise)
-        bf.wave = A.get<float>(record_taps || resampling() || loud || lim ? (size_t)Wcap * hop : 1);
+        // (a gain plan: the tail likewise writes the float wave and its int16 samples go to scratch; the gain kernel writes the gained wave
+        // and, with nothing downstream, bf.pcm)
+        bf.wave = A.get<float>(record_taps || resampling() || loud || lim || c.gain ? (size_t)Wcap * hop : 1);
+        bf.wave_gain = c.gain ? A.get<float>((size_t)Wcap * hop) : nullptr;
         bf.pcm = A.get<int16_t>((size_t)c.Ocap);
-        bf.pcm_nat = resampling() || norm ? A.get<int16_t>((size_t)Wcap * hop) : bf.pcm;
+        bf.pcm_nat = resampling() || norm || c.gain ? A.get<int16_t>((size_t)Wcap * hop) : bf.pcm;
         bf.wave_out = (record_taps || loud || lim) && resampling() ? A.get<float>((size_t)c.Ocap) : nullptr;
         bf.pcm_rs = norm && resampling() ? A.get<int16_t>((size_t)c.Ocap) : bf.pcm;
         bf.lws = loud ? A.get<char>(loud_ws_bytes(B, c.Ocap)) : nullptr;
@@ -995,7 +1030,7 @@ int Engine::run_frame_workspace(RunCtx& c) {
         bf.wave_lim = lim && !ss && record_taps ? A.get<float>((size_t)c.Ocap) : nullptr;
         bf.stab = nullptr; bf.spack = nullptr; bf.gwin = bf.cond_win = nullptr;
         if (ss) {
-            bf.stab = A.get<char>(stream_tab_bytes(B));
+            bf.stab = A.get<char>(stream_tab_bytes(B, c.gain));
             // (only stream_pack writes there: at another rate the resampler packs into bf.pcm, the limiter likewise, and one utterance's
             // chunk is downloaded from where the decoder wrote it)
             if (!resampling() && !lim && B > 1) bf.spack = A.get<int16_t>((size_t)c.Ocap);
@@ -1013,7 +1048,7 @@ int Engine::run_frame_workspace(RunCtx& c) {
     if (pcm_direct && host_pcm && !ss && B == 1 && !record_taps && pinned_pcm_dev_ && (size_t)c.Ocap * 2 + 256 <= pinned_pcm_cap_ &&
         (size_t)c.Ocap * 2 <= ((size_t)4 << 20)) {
         bf.pcm = pinned_pcm_dev_;
-        if (!resampling() && !norm) bf.pcm_nat = bf.pcm;     // (native rate: the tail's own samples are the PCM; otherwise the resampler or the gain cast writes there)
+        if (!resampling() && !norm && !c.gain) bf.pcm_nat = bf.pcm;     // (native rate: the tail's own samples are the PCM; otherwise the resampler, the gain cast or the gain-plan kernel writes there)
         if (!norm) bf.pcm_rs = bf.pcm;
         pcm_in_host_ = true;
     }
@@ -1164,6 +1199,7 @@ int Engine::run(int B, const int32_t* const* ids, const int32_t* n, const int32_
     const int rc = run_any_math(B, ids, n, sid, ls, ss);
     have_plan = false;          // a duration plan is for one call, whatever its outcome; the repeat inside the call above applied it again
     have_mix = false;           // and so is a speaker mix
+    have_gain = false;          // and a gain plan
     return rc;
 }
 int Engine::run_any_math(int B, const int32_t* const* ids, const int32_t* n, const int32_t* sid, const float* ls, const StreamSpec* ss) {
@@ -1357,7 +1393,7 @@ int Engine::run_stream_steps(RunCtx& c) {
     // (ensure_pinned below may move the pinned block the geometry tables live in)
     const std::vector<int> offF(p_offF, p_offF + B), lenF(p_lenF, p_lenF + B), sidv(c.p_sid, c.p_sid + B);
     const size_t hp_off = (up_bytes + ((size_t)Ttot + B) * 4 + 255) & ~(size_t)255;
-    const size_t tab_room = (stream_tab_bytes(B) + 255) & ~(size_t)255;
+    const size_t tab_room = (stream_tab_bytes(B, c.gain) + 255) & ~(size_t)255;
     const size_t pcm_bytes = (size_t)c.Ocap * 2 + 256;
     if (!ensure_pinned(hp_off + tab_room + pcm_bytes)) return fail(STS_EDEVICE, "pinned host allocation failed");
     c.pm = (int*)pinned_;
@@ -1429,13 +1465,17 @@ int Engine::run_stream_steps(RunCtx& c) {
             Wtot += wlen; maxW = std::max<int>(maxW, (int)wlen);
         }
         ti[6 * nw] = (int)dsum;
-        HIPCK(hipMemcpyAsync(c.d_win, ht, stream_tab_bytes(nw), hipMemcpyHostToDevice, stream));
+        if (c.gain) { int* tu = (int*)(ht + stream_tab_utt_off(nw)); for (int i = 0; i < nw; i++) tu[i] = wb[i]; }     // (the gain kernel: each window's utterance)
+        HIPCK(hipMemcpyAsync(c.d_win, ht, stream_tab_bytes(nw, c.gain), hipMemcpyHostToDevice, stream));
         // one utterance: its window by value (no table load in the decoder's kernels); several: the tables, also while one window is live
         int rc = B == 1 ? run_decode(c, 1, Wtot, maxW, ti[0], ti[2]) : run_decode(c, nw, Wtot, maxW, 0, -1);
         if (rc != STS_OK) return rc;
+        // (a gain plan: run_decode's last launch gained the windows at their absolute positions into bf.wave_gain -- and, with nothing else
+        // downstream, cast them into bf.pcm -- and the resampler and the limiter read that)
+        const float* const sig = c.gain ? bf.wave_gain : bf.wave;
         if (resampling()) {
             ResampleArgs a{};
-            a.x = bf.wave; a.seg = SegView{c.d_win + nw, c.d_win + 2 * nw, hop, 0, 0, 0};
+            a.x = sig; a.seg = SegView{c.d_win + nw, c.d_win + 2 * nw, hop, 0, 0, 0};
             a.table = d_rs_table; a.P = rs.P; a.Q = rs.Q; a.K = rs.K;
             a.pcm = slim ? bf.pcm_rs : dst; a.wave_out = slim ? bf.wave_out : nullptr;
             a.wtab = (const long long*)(bf.stab + stream_tab_ll_off(nw));
@@ -1445,7 +1485,7 @@ int Engine::run_stream_steps(RunCtx& c) {
         }
         if (slim) {          // every window of the step in one launch; it writes the packed chunks in place of the resampler / the pack
             LimArgs a{};
-            a.x = resampling() ? bf.wave_out : bf.wave;
+            a.x = resampling() ? bf.wave_out : sig;
             a.H = ld.H; a.c = ld.c; a.G = ld.G;
             a.pcm = dst;
             a.wtab = (const long long*)(bf.stab + stream_tab_lim_off(nw));

@@ -131,6 +131,11 @@ public:
     std::vector<int32_t> mix_words; int mix_B = 0, mix_K = 0; bool have_mix = false;
     int set_speaker_mix(int B, const sts_speaker_mix* mixes);
     int speaker_embedding(int sid, float* out, int64_t capacity) const;
+    // gain plan (sts_set_gain_plan, gain_plan.hip): for the NEXT call only, whatever its outcome, like the duration plan.  Kept as the table
+    // the run uploads: q per phoneme of the whole batch (an utterance without a plan: 2^20 throughout, env == 1.0f), then h per utterance.
+    // gain_n: the phoneme counts the next call must have
+    std::vector<int32_t> gain_n, gain_words; bool have_gain = false;
+    int set_gain_plan(int B, const int32_t* n, const sts_gain_plan* plans);
     // phoneme start offsets of the last run in output samples, packed like durations_h (sts_get_phoneme_offsets); last_n: its phoneme counts
     std::vector<int32_t> last_n;
     int phoneme_offsets(int64_t* start, int64_t capacity);

@@ -454,4 +454,26 @@ struct LimArgs {
 // one memset (stat) + one launch; max_out = the most outputs one utterance (segment) emits, or more
 void limiter_run(const LimArgs& a, int B, long long max_out, hipStream_t st);
 
+// Gain plans (gain_plan.hip; the definition is there and in include/summertts_hip.h sts_set_gain_plan)
+constexpr int kGainOne = 1 << 20, kGainMaxH = 400;
+// one utterance's plan: gain_db (or null) -INFINITY or finite in [-96, 24], ramp_ms finite in [0, 50] (false for NaN)
+bool gain_plan_valid(int n, const float* gain_db, float ramp_ms, const char** why);
+// step 1 of the definition on the host, for a plan gain_plan_valid accepted: q [n] and h, each optional
+void gain_design(const float* gain_db, int n, float ramp_ms, int32_t* q, int32_t* h);
+struct GainArgs {
+    const float* x;                      // the native float wave: the members' samples as the decoder packs its windows
+    float* y; int16_t* pcm;              // outputs packed like x, each optional (y 16-byte, pcm 8-byte aligned)
+    SegView wseg;                        // member i's place in x, in frames (off == null: one member {ioff, ilen}); its scale is not read: hop is
+    int hop;                             // samples per frame
+    // streaming (null otherwise: member i is the whole utterance i): member i belongs to utterance utt[i] and its first sample is sample
+    // wtab[5 i] of that utterance (the resampler's table of the step)
+    const int* utt; const long long* wtab;
+    SegView tseg;                        // utterance b's phonemes in cum / q
+    const int* cum;                      // inclusive cumulative frame counts inside each utterance (the durations kernel's)
+    const int* q;                        // fixed-point gain per phoneme, packed like cum
+    const int* h;                        // [utterances] half ramp width in samples, 0 .. kGainMaxH
+};
+// one launch: nmem members x ceil(max_len / 4096) tiles; max_len = the longest member's sample count or more
+void gain_plan_run(const GainArgs& a, int nmem, long long max_len, hipStream_t st);
+
 }  // namespace sts

@@ -102,6 +102,9 @@ struct sts_multi {
     std::vector<UttPlan> plan; std::vector<int32_t> plan_n; bool have_plan = false;
     // sts_multi_set_speaker_mix: the next batch's mixes, per utterance of the caller's batch
     std::vector<SpeakerMixCopy> mix; bool have_mix = false;
+    // sts_multi_set_gain_plan: the next batch's gain plans, per utterance of the caller's batch (gain_db: n entries or empty = absent)
+    struct UttGain { std::vector<float> gain_db; float ramp_ms = 0.f; };
+    std::vector<UttGain> gain; std::vector<int32_t> gain_n; bool have_gain = false;
     std::vector<Shard> shards;
     // RCCL gather state (gather_mode == 1)
     int gather_mode = 0;
@@ -305,8 +308,16 @@ struct sts_multi {
                     for (int i = 0; i < nb; i++) mx[i] = mix[sh.utt[i]].view();
                     sh.rc = eng.set_speaker_mix(nb, mx.data());
                 }
+                if (sh.rc == STS_OK && have_gain) {     // and the gain plans
+                    std::vector<sts_gain_plan> gp(nb);
+                    for (int i = 0; i < nb; i++) {
+                        const UttGain& ug = gain[sh.utt[i]];
+                        gp[i] = sts_gain_plan{ug.gain_db.empty() ? nullptr : ug.gain_db.data(), ug.ramp_ms};
+                    }
+                    sh.rc = eng.set_gain_plan(nb, nn.data(), gp.data());
+                }
                 if (sh.rc == STS_OK) sh.rc = eng.run(nb, idp.data(), nn.data(), sd.data(), l.data());
-                else { sh.err = eng.error(); eng.set_duration_plan(0, nullptr, nullptr); eng.set_speaker_mix(0, nullptr); }     // (nothing ran: nothing stays pending)
+                else { sh.err = eng.error(); eng.set_duration_plan(0, nullptr, nullptr); eng.set_speaker_mix(0, nullptr); eng.set_gain_plan(0, nullptr, nullptr); }     // (nothing ran: nothing stays pending)
                 eng.noise_utt.clear();
                 if (sh.rc == STS_OK && gather_mode == 1) {
                     sh.n_samples = eng.n_samples;           // the PCM stays on the device: rccl_gather() below
@@ -444,6 +455,23 @@ int sts_multi_set_duration_plan(sts_multi* m, int32_t B, const int32_t* n, const
     m->have_plan = true;
     return STS_OK;
 }
+int sts_multi_set_gain_plan(sts_multi* m, int32_t B, const int32_t* n, const sts_gain_plan* plans) {
+    if (!m) return multi_err(STS_EINVAL, "null handle");
+    if (B == 0 || !plans) { m->have_gain = false; return STS_OK; }
+    if (B < 0 || !n) return multi_err(STS_EINVAL, "gain plan: B >= 0 and n are required");
+    for (int b = 0; b < B; b++) {
+        const char* why = nullptr;
+        if (!gain_plan_valid(n[b], plans[b].gain_db, plans[b].ramp_ms, &why)) return multi_err(STS_EINVAL, why);
+    }
+    m->gain.assign((size_t)B, sts_multi::UttGain());
+    m->gain_n.assign(n, n + B);
+    for (int b = 0; b < B; b++) {
+        if (plans[b].gain_db) m->gain[b].gain_db.assign(plans[b].gain_db, plans[b].gain_db + n[b]);
+        m->gain[b].ramp_ms = plans[b].ramp_ms;
+    }
+    m->have_gain = true;
+    return STS_OK;
+}
 int sts_multi_set_speaker_mix(sts_multi* m, int32_t B, const sts_speaker_mix* mixes) {
     if (!m) return multi_err(STS_EINVAL, "null handle");
     if (B == 0 || !mixes) { m->have_mix = false; return STS_OK; }
@@ -566,7 +594,7 @@ int sts_multi_shard_of(const sts_multi* m, int32_t B, const int32_t* n, int32_t*
 int sts_multi_infer_ids_batch(sts_multi* m, int32_t B, const int32_t* const* ids, const int32_t* n, const int32_t* sid,
                               const float* length_scale, int16_t** pcm_out, int32_t* n_out) {
     if (!m) return multi_err(STS_EINVAL, "bad arguments");
-    struct DropPlan { sts_multi* m; ~DropPlan() { m->have_plan = false; m->have_mix = false; } } drop_plan{m};      // a duration plan and a speaker mix are for this call only, whatever its outcome
+    struct DropPlan { sts_multi* m; ~DropPlan() { m->have_plan = false; m->have_mix = false; m->have_gain = false; } } drop_plan{m};      // a duration plan, a speaker mix and a gain plan are for this call only, whatever its outcome
     if (!ids || !n || !pcm_out || !n_out || B <= 0) return multi_err(STS_EINVAL, "bad arguments");
     for (int b = 0; b < B; b++) { pcm_out[b] = nullptr; n_out[b] = 0; }      // every output is defined before the first early return
     for (int b = 0; b < B; b++) if (n[b] <= 0 || !ids[b]) return multi_err(STS_EINVAL, "utterance with no phonemes");
@@ -576,6 +604,11 @@ int sts_multi_infer_ids_batch(sts_multi* m, int32_t B, const int32_t* const* ids
         if (!same) return multi_err(STS_EINVAL, "the duration plan was set for another batch (B and every n[b] must match)");
     }
     if (m->have_mix && (int)m->mix.size() != B) return multi_err(STS_EINVAL, "the speaker mix was set for another batch (B must match)");
+    if (m->have_gain) {
+        bool same = (int)m->gain_n.size() == B;
+        for (int b = 0; b < B && same; b++) same = m->gain_n[b] == n[b];
+        if (!same) return multi_err(STS_EINVAL, "the gain plan was set for another batch (B and every n[b] must match)");
+    }
     const int ndev = (int)m->engines.size();
     const bool was_gather = m->gather_mode == 1;
     {

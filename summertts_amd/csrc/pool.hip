@@ -31,6 +31,8 @@ struct Request {
     bool planned = false; std::vector<float> rate; std::vector<int32_t> fixed; int32_t target = 0;
     // sts_pool_submit_mix: this request's speaker mix (mixed: a non-empty entry)
     bool mixed = false; SpeakerMixCopy mix;
+    // sts_pool_submit_gain: this request's gain plan (gained: an entry with gains; gain_db: n entries)
+    bool gained = false; std::vector<float> gain_db; float ramp_ms = 0.f;
     // sts_pool_submit_stream: chunks go to cb (on the worker thread); the ticket completes with pcm = null, n = samples delivered
     bool stream = false; int32_t chunk = 0; sts_chunk_cb cb = nullptr; void* user = nullptr;
     // result
@@ -95,8 +97,15 @@ struct sts_pool {
                     for (int b = 0; b < B; b++) if (grp[b]->mixed) mx[b] = grp[b]->mix.view();
                     rc = eng.set_speaker_mix(B, mx.data());
                 }
+                bool any_gain = false;
+                for (int b = 0; b < B; b++) any_gain = any_gain || grp[b]->gained;
+                if (rc == STS_OK && any_gain) {     // and the gain plans: the members without one get an entry without gains (their samples, bit for bit)
+                    std::vector<sts_gain_plan> gp(B, sts_gain_plan{nullptr, 0.f});
+                    for (int b = 0; b < B; b++) if (grp[b]->gained) gp[b] = sts_gain_plan{grp[b]->gain_db.data(), grp[b]->ramp_ms};
+                    rc = eng.set_gain_plan(B, n.data(), gp.data());
+                }
                 if (rc == STS_OK) rc = eng.run(B, idp.data(), n.data(), sid.data(), ls.data());
-                else { eng.set_duration_plan(0, nullptr, nullptr); eng.set_speaker_mix(0, nullptr); }     // (nothing ran: nothing stays pending for another group)
+                else { eng.set_duration_plan(0, nullptr, nullptr); eng.set_speaker_mix(0, nullptr); eng.set_gain_plan(0, nullptr, nullptr); }     // (nothing ran: nothing stays pending for another group)
                 eng.noise_utt.clear();
                 std::vector<int16_t> all;
                 if (rc == STS_OK) {
@@ -264,6 +273,27 @@ int64_t sts_pool_submit_mix(sts_pool* p, const int32_t* ids, int32_t n, int32_t 
     r->ids.assign(ids, ids + n); r->sid = sid; r->ls = length_scale; r->noise = Engine::Noise{noise_scale, noise_scale_w, seed};
     r->mixed = mix && !speaker_mix_empty(*mix);
     if (r->mixed) r->mix.assign(*mix, M.gin);
+    {
+        std::lock_guard<std::mutex> lk(p->mu);
+        if (p->stop) return pool_err(STS_ESTATE, "pool is shutting down");
+        r->ticket = p->next_ticket++;
+        p->queue.push_back(r);
+        p->pending[r->ticket] = r;
+    }
+    p->cv_work.notify_one();
+    return r->ticket;
+}
+
+int64_t sts_pool_submit_gain(sts_pool* p, const int32_t* ids, int32_t n, int32_t sid, float length_scale, float noise_scale,
+                             float noise_scale_w, uint64_t seed, const sts_gain_plan* plan) {
+    if (!p || !ids || n <= 0) return pool_err(STS_EINVAL, "bad request");
+    if (!noise_scale_valid(noise_scale) || !noise_scale_valid(noise_scale_w)) return pool_err(STS_EINVAL, "noise scales must be finite and >= 0");
+    const char* why = nullptr;
+    if (plan && !gain_plan_valid(n, plan->gain_db, plan->ramp_ms, &why)) return pool_err(STS_EINVAL, why);
+    auto r = std::make_shared<Request>();
+    r->ids.assign(ids, ids + n); r->sid = sid; r->ls = length_scale; r->noise = Engine::Noise{noise_scale, noise_scale_w, seed};
+    r->gained = plan && plan->gain_db;
+    if (r->gained) { r->gain_db.assign(plan->gain_db, plan->gain_db + n); r->ramp_ms = plan->ramp_ms; }
     {
         std::lock_guard<std::mutex> lk(p->mu);
         if (p->stop) return pool_err(STS_ESTATE, "pool is shutting down");

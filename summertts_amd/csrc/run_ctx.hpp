@@ -22,6 +22,8 @@ struct BufT {
     float* plan_rate; int *plan_fixed, *plan_target; long long* plan_rem; float* dur_w;
     // a run with a speaker mix only (null otherwise): the uploaded term table (kernels.hpp SpeakerMixTab) right behind the ids
     int* mix;
+    // a run with a gain plan only (null otherwise): the uploaded table [q Ttot | h B] behind the mix
+    int *gain_q, *gain_h;
 };
 struct BufF {
     float *z, *h, *acts, *out, *x0, *regA, *regB, *tailA, *tailB, *tailC, *wave, *fliptmp;
@@ -32,6 +34,9 @@ struct BufF {
     int16_t* pcm_rs; char* lws;
     // limiter: its raw result words [B][4], its float output (taps only)
     char* limws; float* wave_lim;
+    // a run with a gain plan only (null otherwise): the gained native float wave, laid out like wave (what the resampler, loudness and the
+    // limiter then read in its place)
+    float* wave_gain;
     // streaming only (null otherwise): the step tables (stream_tab_bytes); several utterances: the packed chunk buffer stream_pack writes
     // (native rate, no limiter), the per-window speaker vectors and decoder conditioning of a multi-speaker HiFi-GAN decoder
     char* stab; int16_t* spack; float *gwin, *cond_win;
@@ -41,7 +46,9 @@ struct BufF {
 static inline size_t stream_tab_ll_off(int nw) { return ((size_t)(6 * nw + 1) * 4 + 7) & ~(size_t)7; }
 // and behind them the limiter's segments, long long [nw][7] = {xbase, u0, xlen, N, j0, j1, dst} (LimArgs::wtab)
 static inline size_t stream_tab_lim_off(int nw) { return stream_tab_ll_off(nw) + (size_t)nw * 5 * 8; }
-static inline size_t stream_tab_bytes(int nw) { return stream_tab_lim_off(nw) + (size_t)nw * 7 * 8; }
+// a run with a gain plan: behind those, each window's utterance as ints [nw] (GainArgs::utt)
+static inline size_t stream_tab_utt_off(int nw) { return stream_tab_lim_off(nw) + (size_t)nw * 7 * 8; }
+static inline size_t stream_tab_bytes(int nw, bool gain = false) { return stream_tab_utt_off(nw) + (gain ? (size_t)nw * 4 : 0); }
 
 // Everything a run's stages share: batch geometry, workspace pointers, host / device tables.  Engine::run() fills it stage by
 // stage; the stage functions below see its fields under the names the pipeline has always used (RUN_ALIASES).
@@ -63,6 +70,7 @@ struct Engine::RunCtx {
     // that waited for it -- and returns bit-identical samples.  Batches: Fld == Ftot, nothing changes.
     long Fld = 0; int maxFld = 0; bool ahead = false, ahead_b = false, mapped = false, forced = false;
     bool plan = false;              // this run applies a duration plan (sts_set_duration_plan): never launched ahead, never in the memo
+    bool gain = false;              // this run applies a gain plan (sts_set_gain_plan): the gain kernel runs behind the decoder's tail; never launched ahead, never in the memo
     bool mix = false;               // this run blends speakers (sts_set_speaker_mix): bt.g comes from speaker_blend; never launched ahead, never in the memo
     std::vector<Engine::Noise> nz; bool any_ns = false, any_nsw = false;   // per-utterance sampling noise (engine.hpp Noise), which of the two is used
     std::vector<unsigned long long> req_keys; std::vector<long> predF;      // launch-ahead memo: per-utterance request hashes, remembered frame counts (empty: not all known)

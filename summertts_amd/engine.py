@@ -108,6 +108,31 @@ def _speaker_mixes(mixes, gin: Optional[int] = None):
     return arr, keep
 
 
+class GainPlan(C.Structure):
+    """``sts_gain_plan``: one utterance's gain plan (include/summertts_hip.h sts_set_gain_plan)."""
+    _fields_ = [("gain_db", C.c_void_p), ("ramp_ms", C.c_float)]
+
+
+def _gain_plans(n: Sequence[int], plans):
+    """-> (n as int32 array, ctypes array of GainPlan, the numpy arrays it points into).  ``plans[b]``: None (no plan) or a mapping with
+    ``gain_db`` (float per phoneme, ``-inf`` = mute; None = no gains) and ``ramp_ms`` (default 0)."""
+    n = np.ascontiguousarray(n, dtype=np.int32)
+    if len(plans) != n.size:
+        raise ValueError("one plan (or None) per utterance")
+    arr, keep = (GainPlan * max(n.size, 1))(), []
+    for b, p in enumerate(plans):
+        p = p or {}
+        v = p.get("gain_db")
+        if v is not None:
+            v = np.ascontiguousarray(v, dtype=np.float32).ravel()
+            if v.size != n[b]:
+                raise ValueError(f"plan {b}: gain_db needs one entry per phoneme")
+            keep.append(v)
+            arr[b].gain_db = v.ctypes.data
+        arr[b].ramp_ms = float(p.get("ramp_ms", 0.0))
+    return n, arr, keep
+
+
 class PreparedBatch:
     """run_batch's argument arrays, built once (Synthesizer.prepare)."""
 
@@ -207,6 +232,13 @@ def load_library() -> C.CDLL:
     lib.sts_speaker_blend.argtypes = [C.c_int, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.sts_pool_submit_mix.restype = C.c_int64
     lib.sts_pool_submit_mix.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_float, C.c_uint64, C.c_void_p]
+    lib.sts_set_gain_plan.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
+    lib.sts_multi_set_gain_plan.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
+    lib.sts_gain_plan_check.argtypes = [C.c_int32, C.c_void_p, C.c_void_p]
+    lib.sts_gain_design.argtypes = [C.c_void_p, C.c_int32, C.c_float, C.c_void_p, C.POINTER(C.c_int32)]
+    lib.sts_gain_plan_apply.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.sts_pool_submit_gain.restype = C.c_int64
+    lib.sts_pool_submit_gain.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_float, C.c_uint64, C.c_void_p]
     lib.sts_infer_ids_batch_stream.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
                                                BATCH_CHUNK_CB, C.c_void_p, C.c_void_p]
     lib.sts_pool_submit_stream.restype = C.c_int64
@@ -241,6 +273,8 @@ EXPORTED_SYMBOLS = [
     "sts_multi_set_duration_plan",
     "sts_set_speaker_mix", "sts_speaker_mix_check", "sts_get_speaker_embedding", "sts_speaker_blend", "sts_pool_submit_mix",
     "sts_multi_set_speaker_mix",
+    "sts_set_gain_plan", "sts_gain_plan_check", "sts_gain_design", "sts_gain_plan_apply", "sts_pool_submit_gain",
+    "sts_multi_set_gain_plan",
 ]
 
 
@@ -274,6 +308,52 @@ def speaker_blend(table, mixes, sid=None, device: int = 0) -> np.ndarray:
     _check(lib, lib.sts_speaker_blend(int(device), t.ctypes.data, spk, gin, B, None if s is None else s.ctypes.data,
                                       C.cast(arr, C.c_void_p), out.ctypes.data))
     return out[:B]
+
+
+def gain_plan_check(n: Sequence[int], plans) -> None:
+    """The validity rules of a gain plan (include/summertts_hip.h sts_gain_plan_check; host only, no GPU) for ``plans`` (as
+    ``Synthesizer.set_gain_plan`` takes them) of ``n[b]`` phonemes each.  Raises StsError for an invalid plan."""
+    lib = load_library()
+    nn, arr, keep = _gain_plans(n, plans)
+    _check(lib, lib.sts_gain_plan_check(nn.size, nn.ctypes.data, C.cast(arr, C.c_void_p)))
+
+
+def gain_design(gain_db, n: int, ramp_ms: float = 0.0):
+    """Step 1 of the gain-plan definition (include/summertts_hip.h sts_gain_design; host only, no GPU): ``gain_db`` None or ``n`` floats
+    -> (q, h): the int32 fixed-point gains and the half ramp width in native samples."""
+    lib = load_library()
+    g = None if gain_db is None else np.ascontiguousarray(gain_db, dtype=np.float32).ravel()
+    if g is not None and g.size != n:
+        raise ValueError("gain_db needs one entry per phoneme")
+    q = np.zeros(max(int(n), 1), np.int32)
+    h = C.c_int32()
+    _check(lib, lib.sts_gain_design(None if g is None else g.ctypes.data, int(n), float(ramp_ms), q.ctypes.data, C.byref(h)))
+    return q[:int(n)], h.value
+
+
+def gain_plan_apply(signals, durations, plans, samples_per_frame: int, device: int = 0):
+    """The gain-plan kernel on caller signals (sts_gain_plan_apply): ``durations`` a list of int arrays (frames per phoneme), one per
+    utterance; ``signals[b]`` its float signal of ``max(1, sum d) * samples_per_frame`` samples; ``plans`` as
+    ``Synthesizer.set_gain_plan`` takes them -> (y, pcm): lists of the gained float32 signals and their int16 casts."""
+    lib = load_library()
+    ds = [np.ascontiguousarray(d, dtype=np.int32).ravel() for d in durations]
+    sig = [np.ascontiguousarray(x, dtype=np.float32).ravel() for x in signals]
+    if len(sig) != len(ds):
+        raise ValueError("one signal per utterance")
+    lens = np.asarray([max(1, int(d.sum())) * int(samples_per_frame) for d in ds], np.int64)
+    for b, x in enumerate(sig):
+        if x.size != lens[b]:
+            raise ValueError(f"signal {b} needs max(1, sum d) * samples_per_frame = {lens[b]} samples")
+    nn, arr, keep = _gain_plans([d.size for d in ds], plans)
+    total = int(lens.sum())
+    x = np.concatenate(sig) if sig else np.zeros(1, np.float32)
+    d = np.concatenate(ds) if ds and sum(v.size for v in ds) else np.zeros(1, np.int32)
+    y = np.zeros(max(total, 1), np.float32)
+    pcm = np.zeros(max(total, 1), np.int16)
+    _check(lib, lib.sts_gain_plan_apply(int(device), x.ctypes.data, d.ctypes.data, nn.ctypes.data, len(ds), int(samples_per_frame),
+                                        C.cast(arr, C.c_void_p), y.ctypes.data, pcm.ctypes.data))
+    off = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
+    return [y[off[b]:off[b + 1]].copy() for b in range(len(ds))], [pcm[off[b]:off[b + 1]].copy() for b in range(len(ds))]
 
 
 def duration_fit(w, fixed=None, target_frames: int = 0) -> np.ndarray:
@@ -555,6 +635,17 @@ class Synthesizer:
             return
         arr, keep = _speaker_mixes(mixes, int(self.info.gin_channels))
         _check(self.lib, self.lib.sts_set_speaker_mix(self.h, len(mixes), C.cast(arr, C.c_void_p)))
+
+    def set_gain_plan(self, n: Optional[Sequence[int]], plans=None):
+        """Gain plan of the NEXT call only (include/summertts_hip.h sts_set_gain_plan).  ``n``: phoneme count of every utterance of that
+        call; ``plans``: per utterance None or a mapping with ``gain_db`` (dB per phoneme, ``-inf`` = mute) and ``ramp_ms`` (width of the
+        transition across a phoneme boundary, default 0).  ``n`` or ``plans`` None drops a pending plan.  An invalid plan raises and
+        changes nothing."""
+        if n is None or plans is None:
+            _check(self.lib, self.lib.sts_set_gain_plan(self.h, 0, None, None))
+            return
+        nn, arr, keep = _gain_plans(n, plans)
+        _check(self.lib, self.lib.sts_set_gain_plan(self.h, nn.size, nn.ctypes.data, C.cast(arr, C.c_void_p)))
 
     def speaker_embedding(self, sid: int) -> np.ndarray:
         """Row ``sid`` of the model's speaker table: float32 [gin_channels] (sts_get_speaker_embedding)."""
@@ -851,15 +942,22 @@ class Pool:
         return t
 
     def submit(self, ids: Sequence[int], sid: int = 0, length_scale: float = 1.0, noise_scale: float = 0.0,
-               noise_scale_w: float = 0.0, seed: int = 0, plan=None, mix=None) -> int:
+               noise_scale_w: float = 0.0, seed: int = 0, plan=None, mix=None, gain=None) -> int:
         """Queue one request; the noise arguments are this request's own (``Synthesizer.set_noise``; ``seed`` is used as given), and so
         is ``plan``: None or a mapping as ``Synthesizer.set_duration_plan`` takes per utterance (sts_pool_submit_plan), or ``mix``: None
         or a mapping as ``Synthesizer.set_speaker_mix`` takes per utterance (sts_pool_submit_mix).  One request carries a plan or a mix,
-        not both."""
+        not both.  ``gain``: None or a mapping as ``Synthesizer.set_gain_plan`` takes per utterance (sts_pool_submit_gain); a request with
+        a gain plan carries neither of the other two."""
         a = np.ascontiguousarray(ids, dtype=np.int32)
         if plan is not None and mix is not None:
             raise ValueError("a request carries a plan or a mix, not both")
-        if mix is not None:
+        if gain is not None and (plan is not None or mix is not None):
+            raise ValueError("a request with a gain plan carries no duration plan and no mix")
+        if gain is not None:
+            _, arr, keep = _gain_plans([a.size], [gain])
+            t = int(self.lib.sts_pool_submit_gain(self.h, a.ctypes.data, a.size, sid, length_scale, float(noise_scale), float(noise_scale_w),
+                                                  int(seed) & 0xFFFFFFFFFFFFFFFF, C.cast(arr, C.c_void_p)))
+        elif mix is not None:
             arr, keep = _speaker_mixes([mix])
             t = int(self.lib.sts_pool_submit_mix(self.h, a.ctypes.data, a.size, sid, length_scale, float(noise_scale), float(noise_scale_w),
                                                  int(seed) & 0xFFFFFFFFFFFFFFFF, C.cast(arr, C.c_void_p)))
@@ -1023,6 +1121,17 @@ class MultiDevice:
             rc = self.lib.sts_multi_set_speaker_mix(self.h, len(mixes), C.cast(arr, C.c_void_p))
         if rc != 0:
             raise StsError(f"sts_multi_set_speaker_mix: {rc}: {self.lib.sts_multi_last_error().decode()}")
+
+    def set_gain_plan(self, n: Optional[Sequence[int]], plans=None):
+        """``Synthesizer.set_gain_plan`` for the next ``infer_batch``: ``plans[b]`` belongs to utterance b of that batch, whatever its
+        device."""
+        if n is None or plans is None:
+            rc = self.lib.sts_multi_set_gain_plan(self.h, 0, None, None)
+        else:
+            nn, arr, keep = _gain_plans(n, plans)
+            rc = self.lib.sts_multi_set_gain_plan(self.h, nn.size, nn.ctypes.data, C.cast(arr, C.c_void_p))
+        if rc != 0:
+            raise StsError(f"sts_multi_set_gain_plan: {rc}: {self.lib.sts_multi_last_error().decode()}")
 
     def set_conv_math(self, mode):
         m = {"bf16x3": 0, "f32": 1, "bf16x3_all": 2, "f16x2": 3}.get(mode, mode)
