@@ -516,6 +516,14 @@ int sts_debug_conv_h2p_packed(int device, const float* x, int32_t Cin, int32_t L
 int sts_debug_conv_h2w(int device, const float* x, int32_t C, int32_t L, const float* w, const float* bias, int32_t k, int32_t dil, const float* res,
                        float in_slope, float out_slope, int members, float* y, float* y16, int32_t iters, float* ms_out);
 
+/* One reverse ConvFlow step of the stochastic duration predictor on caller data, launched exactly as the engine launches it where the
+ * projection runs as its own conv (misc_kernels.hip spline_step: one thread per position, 128 per workgroup): (r0, r1) -> (o0, o1) =
+ * (inverse rational-quadratic spline of r1 under the 29 parameters h[.][i], r0).  h is [29][n] with row stride n (10 widths, 10 heights,
+ * 9 inner derivatives, all unnormalised); filter_sqrt divides the first 20 rows.  r0 / r1: n floats each, either may be NULL = all zeros,
+ * as the kernel allows.  o0 / o1 receive n floats each.  On the device every output row is followed by a guard that covers the rest of the
+ * launch's last workgroup and 128 positions more; a guard word the kernel changed is STS_EDEVICE.  1 <= n <= 2^24. */
+int sts_debug_spline_step(int device, const float* h, int64_t n, float filter_sqrt, const float* r0, const float* r1, float* o0, float* o1);
+
 void sts_free(void* p);
 const char* sts_last_error(void);
 

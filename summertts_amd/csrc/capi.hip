@@ -349,6 +349,38 @@ int sts_gain_plan_apply(int device, const float* x, const int32_t* dur_frames, c
     return ok ? STS_OK : set_err(STS_EDEVICE, "the gain plan failed on the device");
 }
 
+int sts_debug_spline_step(int device, const float* h, int64_t n, float filter_sqrt, const float* r0, const float* r1, float* o0, float* o1) {
+    if (!h || !o0 || !o1 || n < 1 || n > (1 << 24) || !(filter_sqrt > 0.f)) return set_err(STS_EINVAL, "h [29][n], 1 <= n <= 2^24, filter_sqrt > 0 and both outputs are required");
+    if (hipSetDevice(device) != hipSuccess) return set_err(STS_EDEVICE, "no such device");
+    auto pad = [](size_t bytes) { return (bytes + 255) & ~(size_t)255; };
+    // each output row is followed by a guard that reaches past the last 128-thread block of the launch; it must come back untouched
+    const size_t guard = (size_t)((n + 127) / 128 * 128 - n) + 128;
+    const size_t hb = pad((size_t)29 * n * 4), rb = pad((size_t)n * 4), ob = pad(((size_t)n + guard) * 4);
+    char* d = nullptr;          // [h | r0 | r1 | o0 + guard | o1 + guard]
+    if (hipMalloc((void**)&d, hb + 2 * rb + 2 * ob) != hipSuccess) return set_err(STS_EDEVICE, "out of device memory");
+    hipStream_t st = nullptr;
+    bool ok = hipStreamCreate(&st) == hipSuccess;
+    float *d0 = (float*)(d + hb + 2 * rb), *d1 = (float*)(d + hb + 2 * rb + ob);
+    std::vector<uint32_t> back0((size_t)n + guard), back1((size_t)n + guard);
+    ok = ok && hipMemcpyAsync(d, h, (size_t)29 * n * 4, hipMemcpyHostToDevice, st) == hipSuccess &&
+         (!r0 || hipMemcpyAsync(d + hb, r0, (size_t)n * 4, hipMemcpyHostToDevice, st) == hipSuccess) &&
+         (!r1 || hipMemcpyAsync(d + hb + rb, r1, (size_t)n * 4, hipMemcpyHostToDevice, st) == hipSuccess) &&
+         hipMemsetAsync(d0, 0xFF, 2 * ob, st) == hipSuccess;
+    if (ok) {
+        spline_step((const float*)d, (long)n, filter_sqrt, r0 ? (const float*)(d + hb) : nullptr, r1 ? (const float*)(d + hb + rb) : nullptr, d0, d1, (long)n, st);
+        ok = hipGetLastError() == hipSuccess && hipMemcpyAsync(back0.data(), d0, back0.size() * 4, hipMemcpyDeviceToHost, st) == hipSuccess &&
+             hipMemcpyAsync(back1.data(), d1, back1.size() * 4, hipMemcpyDeviceToHost, st) == hipSuccess && hipStreamSynchronize(st) == hipSuccess;
+    }
+    if (st) (void)hipStreamDestroy(st);
+    (void)hipFree(d);
+    if (!ok) return set_err(STS_EDEVICE, "the spline step failed on the device");
+    for (size_t i = (size_t)n; i < back0.size(); i++)
+        if (back0[i] != 0xFFFFFFFFu || back1[i] != 0xFFFFFFFFu) return set_err(STS_EDEVICE, "the spline step wrote past n");
+    memcpy(o0, back0.data(), (size_t)n * 4);
+    memcpy(o1, back1.data(), (size_t)n * 4);
+    return STS_OK;
+}
+
 int sts_set_noise(sts_engine* e, float noise_scale, float noise_scale_w, uint64_t seed) {
     if (!e) return set_err(STS_EINVAL, "null engine");
     if (!noise_scale_valid(noise_scale) || !noise_scale_valid(noise_scale_w)) return set_err(STS_EINVAL, "noise scales must be finite and >= 0");

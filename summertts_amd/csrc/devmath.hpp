@@ -34,8 +34,12 @@ __device__ __forceinline__ float softplus_ref(float x) { return logf(expf(x) + 1
 //   rq_spline_param(j, h_j)   the per-parameter transform: exp(h / sqrt(filter)) for the 10 widths and 10 heights, softplus(h) + 1e-3
 //                             for the 9 inner derivatives
 //   rq_spline_inverse_t(x, t) the rest, on the 29 transformed values
+// A derivative logit above ~88.7 overflows the reference's softplus (e^h = inf, then inf - inf = NaN in the quadratic); softplus(h) is h
+// to the last bit long before that, so the overflow case returns h -- the same bits as the reference wherever the reference is finite.
 __device__ __forceinline__ float rq_spline_param(int j, float h, float filter_sqrt) {
-    return j < 20 ? expf(h / filter_sqrt) : softplus_ref(h) + (float)1e-3;
+    if (j < 20) return expf(h / filter_sqrt);
+    const float e = expf(h);
+    return (isinf(e) ? h : logf(e + 1.0f)) + (float)1e-3;
 }
 __device__ __forceinline__ float rq_spline_inverse_t(float x, const float* t) {
     constexpr int NB = 10;
@@ -78,7 +82,10 @@ __device__ __forceinline__ float rq_spline_inverse_t(float x, const float* t) {
     const float aa = xm * (d0 + d1 - delta * 2.0f) + in_h * (delta - d0);
     const float bq = in_h * d0 - xm * (d0 + d1 - 2.0f * delta);
     const float cc = -(delta * xm);
-    const float disc = bq * bq - aa * cc * 4.0f;
+    // Just below a knot with a small derivative d1 in a steep bin (d1 << delta) the exact discriminant, (in_h d1)^2 at the knot, is
+    // below the rounding error of bq * bq, and the fp32 difference can come out negative: the reference's sqrt is NaN there.  The
+    // root of max(disc, 0) is within sqrt(8 eps) of the exact one, and the same bits wherever disc >= 0.
+    const float disc = fmaxf(bq * bq - aa * cc * 4.0f, 0.f);
     const float root = (cc * 2.0f) / (-bq - sqrtf(disc));
     return root * in_w + in_cw;
 }

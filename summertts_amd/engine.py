@@ -237,6 +237,7 @@ def load_library() -> C.CDLL:
     lib.sts_gain_plan_check.argtypes = [C.c_int32, C.c_void_p, C.c_void_p]
     lib.sts_gain_design.argtypes = [C.c_void_p, C.c_int32, C.c_float, C.c_void_p, C.POINTER(C.c_int32)]
     lib.sts_gain_plan_apply.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.sts_debug_spline_step.argtypes = [C.c_int, C.c_void_p, C.c_int64, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.sts_pool_submit_gain.restype = C.c_int64
     lib.sts_pool_submit_gain.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_float, C.c_uint64, C.c_void_p]
     lib.sts_infer_ids_batch_stream.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
@@ -275,6 +276,7 @@ EXPORTED_SYMBOLS = [
     "sts_multi_set_speaker_mix",
     "sts_set_gain_plan", "sts_gain_plan_check", "sts_gain_design", "sts_gain_plan_apply", "sts_pool_submit_gain",
     "sts_multi_set_gain_plan",
+    "sts_debug_spline_step",
 ]
 
 
@@ -354,6 +356,26 @@ def gain_plan_apply(signals, durations, plans, samples_per_frame: int, device: i
                                         C.cast(arr, C.c_void_p), y.ctypes.data, pcm.ctypes.data))
     off = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
     return [y[off[b]:off[b + 1]].copy() for b in range(len(ds))], [pcm[off[b]:off[b + 1]].copy() for b in range(len(ds))]
+
+
+def debug_spline_step(h, filter_sqrt: float, r0=None, r1=None, device: int = 0, o0=None, o1=None):
+    """One reverse ConvFlow step on caller data (sts_debug_spline_step, the engine's spline_step launch): ``h`` float32 [29][n], ``r0`` /
+    ``r1`` None (= zeros) or n floats -> (o0, o1) = (inverse spline of r1, r0).  ``o0`` / ``o1``: optional contiguous float32 arrays of at
+    least n entries to write into (the first n are written, the rest must stay as they were)."""
+    lib = load_library()
+    h = np.ascontiguousarray(h, dtype=np.float32)
+    if h.ndim != 2 or h.shape[0] != 29:
+        raise ValueError("h is [29][n]")
+    n = h.shape[1]
+    r = [None if v is None else np.ascontiguousarray(v, dtype=np.float32).ravel() for v in (r0, r1)]
+    if any(v is not None and v.size != n for v in r):
+        raise ValueError("r0 and r1 hold n entries")
+    o = [np.zeros(max(n, 1), np.float32) if v is None else v for v in (o0, o1)]
+    if any(v.dtype != np.float32 or not v.flags.c_contiguous or v.size < n for v in o):
+        raise ValueError("o0 and o1 are contiguous float32 arrays of at least n entries")
+    _check(lib, lib.sts_debug_spline_step(int(device), h.ctypes.data, n, float(filter_sqrt), None if r[0] is None else r[0].ctypes.data,
+                                          None if r[1] is None else r[1].ctypes.data, o[0].ctypes.data, o[1].ctypes.data))
+    return o[0][:n], o[1][:n]
 
 
 def duration_fit(w, fixed=None, target_frames: int = 0) -> np.ndarray:

@@ -14,6 +14,7 @@ import math
 
 import numpy as np
 
+from spline_ref import rq_inverse
 from summertts_amd import synth_blob as sb
 
 STREAM_SDP, STREAM_PRIOR = 0, 1
@@ -173,37 +174,10 @@ def _dds(d, x):
     return x
 
 
-def _softplus(x):
-    return np.log1p(np.exp(x))
-
-
-def _rq_inverse(x, h, fs, nb=10, tail=5.0):
-    """Inverse rational-quadratic spline with linear tails outside (-tail, tail): x [T], h [29, T]."""
-    out = x.copy()
-    for t in np.nonzero((x < tail) & (x > -tail))[0]:
-        uw, uh, ud = h[:nb, t] / fs, h[nb:2 * nb, t] / fs, h[2 * nb:, t]
-        wdt = np.exp(uw - uw.max()); wdt = wdt / wdt.sum() * (1 - 1e-3 * nb) + 1e-3
-        hgt = np.exp(uh - uh.max()); hgt = hgt / hgt.sum() * (1 - 1e-3 * nb) + 1e-3
-        cw = np.concatenate([[0.0], np.cumsum(wdt)]) * 2 * tail - tail
-        ch = np.concatenate([[0.0], np.cumsum(hgt)]) * 2 * tail - tail
-        cw[-1] = ch[-1] = tail
-        dend = _softplus(0.5397424172369522) + 1e-3          # the boundary derivatives (constant padding, log(e - 1))
-        der = np.concatenate([[dend], _softplus(ud) + 1e-3, [dend]])
-        edges = ch.copy(); edges[-1] += 1e-6
-        b = min(max(int((x[t] >= edges).sum()) - 1, 0), nb - 1)
-        w_, h_ = cw[b + 1] - cw[b], ch[b + 1] - ch[b]
-        d0, d1, delta = der[b], der[b + 1], h_ / w_
-        xm = x[t] - ch[b]
-        a = xm * (d0 + d1 - 2 * delta) + h_ * (delta - d0)
-        bq = h_ * d0 - xm * (d0 + d1 - 2 * delta)
-        c = -delta * xm
-        root = 2 * c / (-bq - math.sqrt(bq * bq - 4 * a * c))
-        out[t] = root * w_ + cw[b]
-    return out
-
-
-def sdp_logw(sec: SdpSection, x: np.ndarray, r0: np.ndarray, r1: np.ndarray, sid: int = 0) -> np.ndarray:
-    """logw [T] of one utterance: x = the encoder output [H, T], (r0, r1) = the flipped latent (sdp_latent)."""
+def sdp_logw(sec: SdpSection, x: np.ndarray, r0: np.ndarray, r1: np.ndarray, sid: int = 0, spline=rq_inverse, trace=None) -> np.ndarray:
+    """logw [T] of one utterance: x = the encoder output [H, T], (r0, r1) = the flipped latent (sdp_latent).  ``spline``: the inverse
+    spline to use (spline_ref.rq_inverse, or rq_inverse_f32 to measure what fp32 costs in it); ``trace``: a list that receives
+    (input, parameters, fs, selected bins) of every spline step."""
     x = np.asarray(x, dtype=np.float64)
     h = _conv(sec.pre, x)
     if sec.cond is not None:
@@ -215,7 +189,13 @@ def sdp_logw(sec: SdpSection, x: np.ndarray, r0: np.ndarray, r1: np.ndarray, sid
         hh = _conv(f["pre"], z0[None]) + g
         p = _conv(f["proj"], _dds(f["dds"], hh))
         fs = math.sqrt(f["pre"]["w"].shape[0])
-        z0, z1 = _rq_inverse(z1, p, fs), z0           # the spline step, then the channel flip
+        if spline is rq_inverse:
+            out, bins, _ = spline(z1, p, fs)
+        else:                                         # a float32 spline: its inputs rounded once, everything else stays float64
+            out, bins, _ = spline(z1.astype(np.float32), p.astype(np.float32), np.float32(fs))
+        if trace is not None:
+            trace.append((z1.copy(), p, fs, bins))
+        z0, z1 = out.astype(np.float64), z0           # the spline step, then the channel flip
     return (z0 - sec.ea_m[0]) * np.exp(-sec.ea_logs[0])
 
 
