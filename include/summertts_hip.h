@@ -284,7 +284,7 @@ int sts_duration_plan_apply(int device, const float* w, const int32_t* fixed, co
 /* Phoneme start offsets of the last run in output samples, packed like sts_get_durations (same count, same capacity convention): phoneme i
  * with f frames before it in its utterance starts at ceil(f * samples_per_frame * P / Q) at the current output rate (sts_set_output_rate; f *
  * samples_per_frame at the native rate) -- the convention of a streaming chunk's sample_offset.  Host arithmetic; after any call form, with
- * or without a plan. */
+ * or without a plan.  After sts_infer_ids_joined the positions are those in the joined output (see there). */
 int sts_get_phoneme_offsets(sts_engine* e, int64_t* start, int64_t capacity);
 /* ---- speaker blending (no reference counterpart: SynthesizerTrn::infer takes one sid, a row of emb_g).  sts_set_speaker_mix(e, B, mixes)
  * gives utterance b of the NEXT call the conditioning vector g of mixes[b] instead of row sid[b] of the model's table.  With
@@ -372,10 +372,67 @@ int sts_gain_design(const float* gain_db, int32_t n, float ramp_ms, int32_t* q, 
  * be NULL. */
 int sts_gain_plan_apply(int device, const float* x, const int32_t* dur_frames, const int32_t* lengths, int32_t B, int32_t samples_per_frame,
                         const sts_gain_plan* plans, float* y, int16_t* pcm);
+/* ---- paragraph synthesis (no reference counterpart: SynthesizerTrn::infer runs a whole line as ONE utterance, at quadratic attention cost and
+ * without batching).  sts_infer_ids_joined runs B sentences as exactly the packed batch sts_infer_ids_batch would run and joins their float
+ * waves on the device into ONE signal -- in front of the resampler, loudness, the limiter and the cast, which then see the paragraph as the
+ * single utterance it is: one loudness gain, a limiter look-ahead and resampler taps that reach across the joins, faded sentence edges.
+ * Native 16 kHz float domain, exact; hop = samples_per_frame.  Sentence b has F_b = max(1, sum d) frames and the native float wave
+ * x_b[0 .. N_b), N_b = F_b hop: the tap "wave_gain" if a gain plan applies, else "wave".
+ * Valid (checked before anything runs; otherwise STS_EINVAL and nothing changes): B >= 1; every gap, lead_frames and trail_frames in
+ * [0, 100000]; fade_ms finite and in [0, 50] (NaN is invalid).  From milliseconds: frames = round(ms * 16 / samples_per_frame), the
+ * convention of the duration plans.
+ *   1 Design (host): h = floor(fade_ms * 16 + 0.5), so 0 <= h <= 800.
+ *   2 Layout (host, 64-bit): start_0 = lead_frames hop; start_{b+1} = start_b + N_b + gap_b hop; N_J = start_{B-1} + N_{B-1} + trail_frames hop.
+ *     Every start_b and N_J is a multiple of hop; F_J = N_J / hop.  (sts_join_layout returns exactly this.)
+ *   3 Envelope of sentence b at local t in [0, N_b): e_b[t] = float32(float64(min(t + 1, N_b - t, h + 1)) / float64(h + 1)): a linear
+ *     fade-in over the first h samples and fade-out over the last h.  h = 0 gives 1.0f everywhere; a sentence shorter than 2h simply
+ *     never reaches 1.
+ *   4 Joined signal: J[start_b + t] = x_b[t] * e_b[t], one fp32 multiply; where e = 1.0f the sample is x_b[t] bit for bit.  Every other
+ *     J[t] is +0.0f.
+ *   5 Downstream J is ONE utterance of F_J frames: the resampler gives L_out = ceil(N_J P / Q) samples, loudness one measurement and one
+ *     gain, the limiter one set of stats, and the cast comes last.  With nothing downstream (native rate, loudness mode 0 or 1, limiter
+ *     off) the join kernel writes the PCM itself with the reference's cast (int16)(int32)(J * 32737).  N_J > 2 10^9 or L_out > 2^31 - 1
+ *     answers STS_EINVAL before the decoder runs.
+ * The join is one kernel launch behind the decoder's last one (behind the gain kernel when a gain plan applies); it writes the silence
+ * too (no memset), and its B-entry table rides in the run's one upload.  A call without a join launches, allocates and uploads nothing
+ * new. */
+typedef struct sts_join {
+    const int32_t* gap_frames;   /* [B-1] or NULL (= all 0): silence between sentence b and b+1, in frames */
+    int32_t lead_frames, trail_frames;   /* silence in front of the first / behind the last sentence, in frames */
+    float   fade_ms;             /* edge fade of every sentence */
+} sts_join;
+/* Host only (no device): the validity rules above (join == NULL = all zeros: only B is checked). */
+int sts_join_check(int32_t B, const sts_join* join);
+/* Host only (no device): steps 1-2 above for B sentences of frames[b] >= 1 frames of samples_per_frame >= 1 samples each.  start ([B], native
+ * samples), total (N_J) and h are each set when non-null.  STS_EINVAL for an invalid join or frame count. */
+int sts_join_layout(int32_t B, const int32_t* frames, int32_t samples_per_frame, const sts_join* join, int64_t* start, int64_t* total,
+                    int32_t* h);
+/* The same kernel on caller signals, like sts_gain_plan_apply: B float signals of frames[b] samples_per_frame samples packed back to back
+ * in x (host memory; at most 2^30 samples in x and in J).  y (float) and pcm (int16) receive J and its cast, N_J samples each; each may be
+ * NULL.  On the device both start out as a NaN / 0x7FFF pattern, so a sample the kernel did not write shows. */
+int sts_join_apply(int device, const float* x, const int32_t* frames, int32_t B, int32_t samples_per_frame, const sts_join* join, float* y,
+                   int16_t* pcm);
+/* The B sentences as the packed batch of sts_infer_ids_batch -- the same sid rule, noise seed + b, forced durations, and a pending
+ * duration plan, speaker mix or gain plan applied per sentence (their B and n[b] must match, as for any call) -- joined as defined above.
+ * *pcm_out is ONE malloc()'d buffer of *n_out = L_out samples.  join == NULL means all zeros: the sentences back to back, no fade.  The
+ * call neither reads nor feeds the launch-ahead memo (STS_DBG_LAUNCH_AHEAD).  B == 1 with an all-zero join returns sts_infer_ids' PCM bit
+ * for bit.
+ * Afterwards: sts_get_durations is unchanged (packed per phoneme); sts_get_phoneme_offsets reports positions in the joined output, phoneme
+ * i of sentence b with f frames before it in its sentence at ceil((start_b + f hop) P / Q); sts_get_join_offsets the sentence starts
+ * ceil(start_b P / Q); sts_get_loudness and sts_get_limiter report count 1.  Taps: "wave" and "wave_gain" stay per sentence (packed);
+ * "wave_join" is J; "wave_out" and "wave_lim" are computed from J.
+ * Out of scope: a streaming form (the step loop decodes chunk k of EVERY member, the wrong order for a paragraph), sts_multi_*, and
+ * per-request plans through the pool. */
+int sts_infer_ids_joined(sts_engine* e, int32_t B, const int32_t* const* ids, const int32_t* n, const int32_t* sid,
+                         const float* length_scale, const sts_join* join, int16_t** pcm_out, int32_t* n_out);
+/* Sentence starts of the last call in output samples, ceil(start_b P / Q): [B] entries (capacity below B: STS_EINVAL).  STS_ESTATE when the
+ * last call was not a joined one. */
+int sts_get_join_offsets(sts_engine* e, int64_t* start, int64_t capacity);
 /*   record intermediate tensors of the next run: "x_enc","m","logs","logw","z_p","z","wave","wave_out" ("logs": the second half of the
  *   encoder projection, computed only by runs that record taps or sample the prior; "wave_out": the resampled float wave, only at a
  *   non-native output rate, one-pass calls; "dur_w": the planned duration weights, only a run with a duration plan; "wave_gain": the
- *   gained native float wave, only a one-pass run with a gain plan) */
+ *   gained native float wave, only a one-pass run with a gain plan; "wave_join": the joined native float wave J, only
+ *   sts_infer_ids_joined) */
 int sts_set_record_taps(sts_engine* e, int enable);
 /*   fetch a tap: malloc()'d copy, channel-major [channels][total_len] (== the reference's column-major
  *   MatrixXf [time, channels]); for batches the utterances are packed along time. */
@@ -581,6 +638,13 @@ int64_t sts_pool_submit_mix(sts_pool* p, const int32_t* ids, int32_t n, int32_t 
  *   with and without a plan share one packed batch: the plan is per utterance, and a member without one keeps its samples bit for bit. */
 int64_t sts_pool_submit_gain(sts_pool* p, const int32_t* ids, int32_t n, int32_t sid, float length_scale, float noise_scale,
                              float noise_scale_w, uint64_t seed, const sts_gain_plan* plan);
+
+/*   sts_pool_submit_joined: a paragraph (sts_infer_ids_joined) as ONE request: one ticket, one PCM.  Sentence b samples with seed + b.  It
+ *   runs as its own packed batch of B, whatever max_batch is, and is never folded with other requests; the pool's output rate, loudness
+ *   and limiter apply to the joined signal.  The ids and the join are copied.  An invalid join or request answers STS_EINVAL.  A joined
+ *   request carries no duration plan, speaker mix or gain plan. */
+int64_t sts_pool_submit_joined(sts_pool* p, int32_t B, const int32_t* const* ids, const int32_t* n, const int32_t* sid,
+                               const float* length_scale, float noise_scale, float noise_scale_w, uint64_t seed, const sts_join* join);
 
 /* ---- multi-device batch (no reference counterpart).  One host process drives n_devices GPUs:
  * one engine (weights replicated) and one worker thread per entry of `devices` (HIP device indices; an index may repeat,

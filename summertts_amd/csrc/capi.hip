@@ -349,6 +349,99 @@ int sts_gain_plan_apply(int device, const float* x, const int32_t* dur_frames, c
     return ok ? STS_OK : set_err(STS_EDEVICE, "the gain plan failed on the device");
 }
 
+int sts_join_check(int32_t B, const sts_join* join) {
+    const char* why = nullptr;
+    if (!join_valid(B, join, &why)) return set_err(STS_EINVAL, why);
+    return STS_OK;
+}
+int sts_join_layout(int32_t B, const int32_t* frames, int32_t samples_per_frame, const sts_join* join, int64_t* start, int64_t* total, int32_t* h) {
+    const char* why = nullptr;
+    if (!join_valid(B, join, &why)) return set_err(STS_EINVAL, why);
+    if (!frames || samples_per_frame < 1) return set_err(STS_EINVAL, "join: frames and samples_per_frame >= 1 are required");
+    std::vector<long long> sil((size_t)B);
+    const long long all = join_silence(B, join, sil.data());
+    long long F = 0;
+    for (int b = 0; b < B; b++) {
+        if (frames[b] < 1) return set_err(STS_EINVAL, "join: every sentence has frames[b] >= 1");
+        if (start) start[b] = (F + sil[b]) * samples_per_frame;
+        F += frames[b];
+    }
+    if (total) *total = (F + all) * samples_per_frame;
+    if (h) *h = join ? join_design(join->fade_ms) : 0;
+    return STS_OK;
+}
+int sts_join_apply(int device, const float* x, const int32_t* frames, int32_t B, int32_t samples_per_frame, const sts_join* join, float* y,
+                   int16_t* pcm) {
+    const char* why = nullptr;
+    if (!join_valid(B, join, &why)) return set_err(STS_EINVAL, why);
+    if (!x || !frames || samples_per_frame < 1 || samples_per_frame > (1 << 20) || B > (1 << 24))
+        return set_err(STS_EINVAL, "1 <= B <= 2^24 signals, their frame counts and samples_per_frame >= 1 are required");
+    const int hop = samples_per_frame;
+    // host table [off B | len B | sil B]: the geometry the engine keeps on the device
+    std::vector<long long> sil((size_t)B);
+    const long long all = join_silence(B, join, sil.data());
+    std::vector<int32_t> tab((size_t)3 * B);
+    int64_t F = 0;
+    for (int b = 0; b < B; b++) {
+        if (frames[b] < 1) return set_err(STS_EINVAL, "join: every sentence has frames[b] >= 1");
+        tab[b] = (int32_t)F; tab[B + b] = frames[b];
+        F += frames[b];
+        if ((F + sil[b]) * hop > ((int64_t)1 << 30)) return set_err(STS_EINVAL, "the signals and the joined signal must hold at most 2^30 samples each");
+        tab[2 * (size_t)B + b] = (int32_t)sil[b];
+    }
+    const int64_t NX = F * hop, NJ = (F + all) * hop;
+    if (NJ > ((int64_t)1 << 30)) return set_err(STS_EINVAL, "the signals and the joined signal must hold at most 2^30 samples each");
+    if (hipSetDevice(device) != hipSuccess) return set_err(STS_EDEVICE, "no such device");
+    auto pad = [](size_t bytes) { return (bytes + 255) & ~(size_t)255; };
+    const size_t xb = pad((size_t)NX * 4), tb = pad(tab.size() * 4), yb = pad((size_t)NJ * 4), pb = pad((size_t)NJ * 2);
+    char* d = nullptr;          // [x | table | y | pcm]
+    if (hipMalloc((void**)&d, xb + tb + yb + pb) != hipSuccess) return set_err(STS_EDEVICE, "out of device memory");
+    hipStream_t st = nullptr;
+    bool ok = hipStreamCreate(&st) == hipSuccess;
+    const int* dt = (const int*)(d + xb);
+    JoinArgs a{};
+    a.x = (const float*)d; a.y = y ? (float*)(d + xb + tb) : nullptr; a.pcm = pcm ? (int16_t*)(d + xb + tb + yb) : nullptr;
+    a.wseg = SegView{dt, dt + B, hop, 0, 0, 0}; a.sil = dt + 2 * B;
+    a.B = B; a.hop = hop; a.h = join ? join_design(join->fade_ms) : 0; a.NJ = NJ;
+    // (the outputs start out as NaN / 0x7FFF: a sample the kernel leaves out shows)
+    ok = ok && hipMemcpyAsync(d, x, (size_t)NX * 4, hipMemcpyHostToDevice, st) == hipSuccess &&
+         hipMemcpyAsync(d + xb, tab.data(), tab.size() * 4, hipMemcpyHostToDevice, st) == hipSuccess &&
+         hipMemsetAsync(d + xb + tb, 0xFF, yb, st) == hipSuccess &&
+         hipMemsetD16Async((hipDeviceptr_t)(d + xb + tb + yb), 0x7FFF, pb / 2, st) == hipSuccess;
+    if (ok) {
+        join_run(a, st);
+        ok = hipGetLastError() == hipSuccess &&
+             (!y || hipMemcpyAsync(y, d + xb + tb, (size_t)NJ * 4, hipMemcpyDeviceToHost, st) == hipSuccess) &&
+             (!pcm || hipMemcpyAsync(pcm, d + xb + tb + yb, (size_t)NJ * 2, hipMemcpyDeviceToHost, st) == hipSuccess) &&
+             hipStreamSynchronize(st) == hipSuccess;
+    }
+    if (st) (void)hipStreamDestroy(st);
+    (void)hipFree(d);
+    return ok ? STS_OK : set_err(STS_EDEVICE, "the join failed on the device");
+}
+int sts_infer_ids_joined(sts_engine* e, int32_t B, const int32_t* const* ids, const int32_t* n, const int32_t* sid,
+                         const float* length_scale, const sts_join* join, int16_t** pcm_out, int32_t* n_out) {
+    if (!pcm_out || !n_out) return set_err(STS_EINVAL, "null output");
+    if (!e) return set_err(STS_EINVAL, "null engine");
+    const bool was = e->eng.host_pcm;
+    e->eng.host_pcm = true;               // the PCM download rides at the end of the run: one stream sync for the whole call
+    int rc = e->eng.run_joined(B, ids, n, sid, length_scale, join);
+    e->eng.host_pcm = was;
+    if (rc != STS_OK) return set_err(rc, e->eng.error());
+    const int64_t total = e->eng.total_samples;
+    int16_t* all = (int16_t*)malloc((size_t)(total > 0 ? total : 1) * 2);
+    if (!all) return set_err(STS_EDEVICE, "out of host memory");
+    rc = sts_copy_pcm_host(e, all, total);
+    if (rc != STS_OK) { free(all); return rc; }
+    *pcm_out = all; *n_out = (int32_t)total;
+    return STS_OK;
+}
+int sts_get_join_offsets(sts_engine* e, int64_t* start, int64_t capacity) {
+    if (!e) return set_err(STS_EINVAL, "null engine");
+    const int rc = e->eng.join_offsets(start, capacity);
+    return rc == STS_OK ? STS_OK : set_err(rc, e->eng.error());
+}
+
 int sts_debug_spline_step(int device, const float* h, int64_t n, float filter_sqrt, const float* r0, const float* r1, float* o0, float* o1) {
     if (!h || !o0 || !o1 || n < 1 || n > (1 << 24) || !(filter_sqrt > 0.f)) return set_err(STS_EINVAL, "h [29][n], 1 <= n <= 2^24, filter_sqrt > 0 and both outputs are required");
     if (hipSetDevice(device) != hipSuccess) return set_err(STS_EDEVICE, "no such device");

@@ -428,7 +428,7 @@ int Engine::run_decode(RunCtx& c, int nw, long Wtot, int maxW, int zoff0, int wl
     // ---------------- decoder tail
     // (at a non-native output rate the tail always writes the float wave, and its int16 samples go to a scratch buffer: the resampler below
     // produces the PCM from the wave)
-    float* wave = record_taps || resampling() || lim_mode != 0 || (loud_mode != 0 && !ss) || c.gain ? bf.wave : nullptr;
+    float* wave = record_taps || resampling() || lim_mode != 0 || (loud_mode != 0 && !ss) || c.gain || c.join ? bf.wave : nullptr;
     int16_t* const pcm = bf.pcm_nat;
     const long Ntot = Wtot * hop;
     if (M.dec_type == 0) {          // Generator_hifigan.cpp:177-179 + SynthesizerTrn.cpp:389-396
@@ -462,31 +462,47 @@ int Engine::run_decode(RunCtx& c, int nw, long Wtot, int maxW, int zoff0, int wl
 // the end of a decode: the "wave" tap; at a non-native output rate (and not streaming: run_stream_steps resamples each step's windows) the
 // resampler, which writes the PCM of every window at the output rate, packed window after window
 int Engine::decode_end(RunCtx& c, const float* wave, const WinGeom& win, long Wtot, int maxW) {
-    const int hop = c.hop, nw = win.nw, wlen0 = win.wlen0;
-    const long long max_out = out_count((long long)maxW * hop);
+    const int hop = c.hop, wlen0 = win.wlen0;
+    int nw = win.nw;
+    long long max_out = out_count((long long)maxW * hop);
+    WinGeom dw = win;                       // the utterances everything behind the gain plan and the join sees
     const float* const raw = wave;          // (the "wave" tap stays the un-gained signal)
     if (c.gain) {
         // the gain plan on every window's native samples at their absolute positions (a streaming window: halo included), one launch; it
-        // writes the PCM too when nothing downstream does (native rate, no gain cast, no limiter).  Everything below reads its output
+        // writes the PCM too when nothing downstream does (native rate, no gain cast, no limiter, no join).  Everything below reads its output
         GainArgs g{};
         g.x = wave; g.y = c.bf.wave_gain;
-        g.pcm = !resampling() && lim_mode == 0 && !(loud_mode == 2 && !c.ss) ? c.bf.pcm : nullptr;
+        g.pcm = !c.join && !resampling() && lim_mode == 0 && !(loud_mode == 2 && !c.ss) ? c.bf.pcm : nullptr;
         g.wseg = win.seg(hop, 0); g.hop = hop;
         if (c.ss) { g.utt = (const int*)(c.bf.stab + stream_tab_utt_off(nw)); g.wtab = (const long long*)(c.bf.stab + stream_tab_ll_off(nw)); }
         g.tseg = c.lvT.seg; g.cum = c.bt.cum; g.q = c.bt.gain_q; g.h = c.bt.gain_h;
         gain_plan_run(g, nw, (long long)maxW * hop, stream);
         wave = c.bf.wave_gain;
     }
+    if (c.join) {
+        // the B sentences (gained or not) into the one joined signal, silence included, one launch; it writes the PCM too when nothing
+        // downstream does.  From here on there is ONE utterance of F_J frames: one resampled signal, one loudness, one set of limiter stats
+        JoinArgs j{};
+        j.x = wave; j.y = c.bf.wave_join;
+        j.pcm = !resampling() && lim_mode == 0 && loud_mode != 2 ? c.bf.pcm : nullptr;
+        j.wseg = win.seg(hop, 0);
+        if (win.inl) j.isil = join_sil[0]; else j.sil = c.bt.join_sil;
+        j.B = nw; j.hop = hop; j.h = join_h; j.NJ = c.FJ * hop;
+        join_run(j, stream);
+        wave = c.bf.wave_join;
+        dw = WinGeom{true, 1, 0, (int)c.FJ, nullptr};
+        nw = 1; max_out = out_count(c.FJ * hop);
+    }
     // LoudArgs / LimArgs: the float signal at the output rate and its utterances' lengths
     auto signal = [&](auto& a) {
         a.x = resampling() ? c.bf.wave_out : wave;
-        a.len = win.len(); a.ilen = win.ilen(); a.scale = hop;
+        a.len = dw.len(); a.ilen = dw.ilen(); a.scale = hop;
         a.P = resampling() ? rs.P : 1; a.Q = resampling() ? rs.Q : 1;
     };
     if (resampling() && !c.ss) {
         ResampleArgs a{};
         a.x = wave;
-        a.seg = win.seg(hop, 0);
+        a.seg = dw.seg(hop, 0);
         a.table = d_rs_table; a.P = rs.P; a.Q = rs.Q; a.K = rs.K;
         a.pcm = c.bf.pcm_rs; a.wave_out = c.bf.wave_out;
         resample_pcm(a, nw, max_out, stream);
@@ -522,9 +538,11 @@ int Engine::decode_end(RunCtx& c, const float* wave, const WinGeom& win, long Wt
     if (raw && record_taps) {
         tap("wave", raw, 1, Wtot * hop, (wlen0 >= 0 ? (long)wlen0 : Wtot) * hop);
         if (c.gain && !c.ss) tap("wave_gain", c.bf.wave_gain, 1, Wtot * hop, (wlen0 >= 0 ? (long)wlen0 : Wtot) * hop);
+        if (c.join) tap("wave_join", c.bf.wave_join, 1, (long)(c.FJ * hop), (long)(c.FJ * hop));
         if ((c.bf.wave_out || c.bf.wave_lim) && !c.ss) {    // (a stream has moved the pinned block p_lenF points into: not read then)
             long long n = 0;        // samples at the output rate: what both taps hold
-            if (wlen0 >= 0) n = out_count((long long)wlen0 * hop);
+            if (c.join) n = out_count(c.FJ * hop);
+            else if (wlen0 >= 0) n = out_count((long long)wlen0 * hop);
             else for (int b = 0; b < c.B; b++) n += out_count((long long)c.p_lenF[b] * hop);
             if (c.bf.wave_out) tap("wave_out", c.bf.wave_out, 1, (long)c.Ocap, (long)n);
             if (c.bf.wave_lim) tap("wave_lim", c.bf.wave_lim, 1, (long)c.Ocap, (long)n);

@@ -444,11 +444,38 @@ int Engine::phoneme_offsets(int64_t* start, int64_t capacity) {
     if (!start) return fail(STS_EINVAL, "null argument");
     if ((int64_t)durations_h.size() > capacity) return fail(STS_ESTATE, "destination too small");
     size_t i = 0;
+    const bool joined = last_join_start.size() == last_n.size() && !last_n.empty();      // (a joined run: positions in the joined output)
     for (size_t b = 0; b < last_n.size(); b++) {
         long long f = 0;
-        for (int t = 0; t < last_n[b] && i < durations_h.size(); t++, i++) { start[i] = out_count(f * model.hop_total); f += durations_h[i]; }
+        const long long base = joined ? last_join_start[b] : 0;
+        for (int t = 0; t < last_n[b] && i < durations_h.size(); t++, i++) { start[i] = out_count(base + f * model.hop_total); f += durations_h[i]; }
     }
     return STS_OK;
+}
+// sts_get_join_offsets: the sentence starts of the last (joined) run in output samples, ceil(start_b P / Q)
+int Engine::join_offsets(int64_t* start, int64_t capacity) {
+    if (!start) return fail(STS_EINVAL, "null argument");
+    if (last_join_start.empty()) return fail(STS_ESTATE, "the last call was not a joined one");
+    if ((int64_t)last_join_start.size() > capacity) return fail(STS_EINVAL, "capacity below the last call's sentence count");
+    for (size_t b = 0; b < last_join_start.size(); b++) start[b] = out_count(last_join_start[b]);
+    return STS_OK;
+}
+// sts_infer_ids_joined: the join is validated and laid out here (silence frames in front of each sentence, h); an invalid join changes
+// nothing.  The run itself is run()'s, with join_on set: run_setup uploads the table, decode_end launches the join kernel
+int Engine::run_joined(int B, const int32_t* const* ids, const int32_t* n, const int32_t* sid, const float* ls, const sts_join* join) {
+    const char* why = nullptr;
+    if (!join_valid(B, join, &why)) return fail(STS_EINVAL, why);
+    if (!ids || !n) return fail(STS_EINVAL, "empty batch");
+    std::vector<long long> sil((size_t)B);
+    join_total_sil = join_silence(B, join, sil.data());
+    if (join_total_sil * model.hop_total > 2000000000LL) return fail(STS_EINVAL, "the joined signal is too long for one call (N_J <= 2 10^9 native samples)");
+    join_sil.resize((size_t)B);
+    for (int b = 0; b < B; b++) join_sil[b] = (int32_t)sil[b];
+    join_h = join ? join_design(join->fade_ms) : 0;
+    join_on = true;
+    const int rc = run(B, ids, n, sid, ls);
+    join_on = false;
+    return rc;
 }
 int Engine::stream_halo() const {
     const int h = decoder_halo_frames(model);
@@ -498,6 +525,8 @@ int Engine::run_setup(RunCtx& c) {
     const bool plan = c.plan = have_plan;
     const bool gain = c.gain = have_gain;
     const size_t gain_ints = gain ? gain_words.size() : 0;                 // [q Ttot | h B], between the mix and the plan
+    const bool join = c.join = join_on;
+    const size_t join_ints = join ? (size_t)B : 0;                         // silence frames in front of each sentence, between the gain plan and the duration plan
     const bool mix = c.mix = have_mix && M.is_ms == 1;       // (a single-speaker model accepts empty entries only: nothing to blend)
     const size_t mix_ints = mix ? mix_words.size() : 0;                    // the term table, between the ids and the plan
     const size_t plan_ints = plan ? 2 * (size_t)Ttot + (size_t)B : 0;      // [rate Ttot | fixed Ttot | target B] behind the ids
@@ -523,8 +552,8 @@ int Engine::run_setup(RunCtx& c) {
         // one device block mirroring the pinned staging block [geometry ints | length scales | noise scales, seeds | ids | forced
         // durations]: a single host-to-device copy per run
         // (a run with a duration plan: the plan's arrays ride in the same copy, between the ids and `forced`, which the plan kernel then writes;
-        // a run with a speaker mix: its term table too, right behind the ids; a run with a gain plan: its q / h table behind that)
-        bt.meta_i = A.get<int>((size_t)9 * B + 8 + 5 * (size_t)B + 2 * (size_t)Ttot + mix_ints + gain_ints + plan_ints);
+        // a run with a speaker mix: its term table too, right behind the ids; a run with a gain plan: its q / h table behind that; a joined run: its silence table behind that)
+        bt.meta_i = A.get<int>((size_t)9 * B + 8 + 5 * (size_t)B + 2 * (size_t)Ttot + mix_ints + gain_ints + join_ints + plan_ints);
         bt.ls = (float*)(bt.meta_i + ((size_t)9 * B + 8));
         bt.ns = bt.ls + B; bt.nsw = bt.ns + B;
         bt.seed = (uint64_t*)(bt.nsw + B);      // (9B + 8 + 3B ints from a 256-byte boundary: 8-byte aligned)
@@ -532,10 +561,11 @@ int Engine::run_setup(RunCtx& c) {
         bt.mix = mix ? bt.ids + Ttot : nullptr;
         bt.gain_q = gain ? bt.ids + Ttot + mix_ints : nullptr;
         bt.gain_h = gain ? bt.ids + 2 * Ttot + mix_ints : nullptr;
-        bt.plan_rate = plan ? (float*)(bt.ids + Ttot + mix_ints + gain_ints) : nullptr;
-        bt.plan_fixed = plan ? bt.ids + 2 * Ttot + mix_ints + gain_ints : nullptr;
-        bt.plan_target = plan ? bt.ids + 3 * Ttot + mix_ints + gain_ints : nullptr;
-        bt.forced = bt.ids + Ttot + mix_ints + gain_ints + plan_ints;
+        bt.join_sil = join ? bt.ids + Ttot + mix_ints + gain_ints : nullptr;
+        bt.plan_rate = plan ? (float*)(bt.ids + Ttot + mix_ints + gain_ints + join_ints) : nullptr;
+        bt.plan_fixed = plan ? bt.ids + 2 * Ttot + mix_ints + gain_ints + join_ints : nullptr;
+        bt.plan_target = plan ? bt.ids + 3 * Ttot + mix_ints + gain_ints + join_ints : nullptr;
+        bt.forced = bt.ids + Ttot + mix_ints + gain_ints + join_ints + plan_ints;
         bt.x = A.get<float>((size_t)H * Ttot); bt.qkv = A.get<float>((size_t)3 * H * Ttot);
         bt.att = A.get<float>((size_t)H * Ttot); bt.y = A.get<float>((size_t)H * Ttot * ffn2_slices);
         bt.x1 = A.get<float>((size_t)H * Ttot); bt.ffh = A.get<float>((size_t)FF * Ttot);
@@ -562,7 +592,7 @@ int Engine::run_setup(RunCtx& c) {
 
     // ---------------- one H2D: geometry + ids (+ forced durations)
     const size_t meta_ints = c.meta_ints = (size_t)9 * B + 8;
-    const size_t up_bytes = c.up_bytes = (meta_ints + 5 * (size_t)B + 2 * (size_t)Ttot + mix_ints + gain_ints + plan_ints) * 4 + 1024;
+    const size_t up_bytes = c.up_bytes = (meta_ints + 5 * (size_t)B + 2 * (size_t)Ttot + mix_ints + gain_ints + join_ints + plan_ints) * 4 + 1024;
     if (!ensure_pinned(up_bytes + ((size_t)Ttot + B) * 4)) return fail(STS_EDEVICE, "pinned host allocation failed");
     int* pm = c.pm = (int*)pinned_;
     int* p_offT = c.p_offT = pm, *p_lenT = c.p_lenT = pm + B, *p_sid = c.p_sid = pm + 2 * B, *p_one = c.p_one = pm + 5 * B;
@@ -580,14 +610,15 @@ int Engine::run_setup(RunCtx& c) {
     for (int b = 0; b < B; b++) memcpy(p_ids + offT[b], ids[b], sizeof(int) * n[b]);
     if (mix) memcpy(p_ids + Ttot, mix_words.data(), sizeof(int) * mix_ints);
     if (gain) memcpy(p_ids + Ttot + mix_ints, gain_words.data(), sizeof(int) * gain_ints);
-    int* p_forced = p_ids + Ttot + mix_ints + gain_ints;
+    if (join) memcpy(p_ids + Ttot + mix_ints + gain_ints, join_sil.data(), sizeof(int) * join_ints);
+    int* p_forced = p_ids + Ttot + mix_ints + gain_ints + join_ints;
     if (have_forced) memcpy(p_forced, forced_dur.data(), sizeof(int) * Ttot);
     if (plan) {          // (never together with forced durations: the plan's arrays take their place in the copy)
-        memcpy(p_ids + Ttot + mix_ints + gain_ints, plan_rate.data(), sizeof(float) * Ttot);
-        memcpy(p_ids + 2 * Ttot + mix_ints + gain_ints, plan_fixed.data(), sizeof(int) * Ttot);
-        memcpy(p_ids + 3 * Ttot + mix_ints + gain_ints, plan_target.data(), sizeof(int) * B);
+        memcpy(p_ids + Ttot + mix_ints + gain_ints + join_ints, plan_rate.data(), sizeof(float) * Ttot);
+        memcpy(p_ids + 2 * Ttot + mix_ints + gain_ints + join_ints, plan_fixed.data(), sizeof(int) * Ttot);
+        memcpy(p_ids + 3 * Ttot + mix_ints + gain_ints + join_ints, plan_target.data(), sizeof(int) * B);
     }
-    HIPCK(hipMemcpyAsync(bt.meta_i, pm, (meta_ints + 5 * (size_t)B + (size_t)Ttot * (have_forced ? 2 : 1) + mix_ints + gain_ints + plan_ints) * 4, hipMemcpyHostToDevice, stream));
+    HIPCK(hipMemcpyAsync(bt.meta_i, pm, (meta_ints + 5 * (size_t)B + (size_t)Ttot * (have_forced ? 2 : 1) + mix_ints + gain_ints + join_ints + plan_ints) * 4, hipMemcpyHostToDevice, stream));
     if (B > 1) HIPCK(hipEventRecord(ev_setup_, stream));     // (run_durations, batches launched from the memo: the host rewrites part of this block)
 
     // single-segment views travel by value (kernels.hpp SegView): no segment-table load in the kernels of a one-utterance call
@@ -791,7 +822,7 @@ int Engine::run_durations(RunCtx& c) {
         c.req_keys[b] = h | 1ull;
     }
     c.predF.clear();
-    if (launch_ahead && !ss && !have_forced && !c.plan && !c.mix && !c.gain && !record_taps && mapped) {     // (a planned or mixed run's frame count is not a function of the memo's key; a run with a gain plan stays off the memo by contract)
+    if (launch_ahead && !ss && !have_forced && !c.plan && !c.mix && !c.gain && !c.join && !record_taps && mapped) {     // (a planned or mixed run's frame count is not a function of the memo's key; a run with a gain plan and a joined run stay off the memo by contract)
         c.predF.resize(B);
         for (int b = 0; b < B; b++) {
             const auto it = seen_tf_.find(c.req_keys[b]);
@@ -814,7 +845,7 @@ int Engine::run_durations(RunCtx& c) {
     durations(r_final, M.dur_type == 0 ? 1 : 0, M.ea_m, M.ea_logs, bt.ls, (have_forced || c.plan) ? bt.forced : nullptr, bt.dlogw,
               bt.dur, bt.cum, bt.frames, lvT.seg, B, stream, mapped ? hmap_dev_ : nullptr, Ttot, seq_, arrive_,
               c.ahead ? c.d_lenF : nullptr, c.ahead ? c.d_win + 2 : nullptr, (int)cap);
-    c.forced = have_forced || c.plan || c.mix || c.gain;      // (none of these runs feeds the memo: its key hashes sid, not the mix)
+    c.forced = have_forced || c.plan || c.mix || c.gain || c.join;      // (none of these runs feeds the memo: its key hashes sid, not the mix)
     have_forced = false;
     mark(2);
     sync_wait_ms_ = 0;
@@ -936,6 +967,13 @@ int Engine::frame_geometry(RunCtx& c) {
     c.Fld = (B == 1 && !ss) ? (c.Ftot + 63) / 64 * 64 : c.Ftot;
     c.maxFld = (B == 1 && !ss) ? (int)c.Fld : c.maxF;
     if ((double)c.Fld * hop > 2.0e9 || (double)c.Fld * hop * 8 > 6.0e10) return fail(STS_EINVAL, "batch produces too many samples for one call");
+    if (c.join) {     // the joined signal's layout (64-bit host arithmetic): F_J frames, sentence b at last_join_start[b]
+        c.FJ = (long long)c.Ftot + join_total_sil;
+        const long long NJ = c.FJ * hop;
+        if (NJ > 2000000000LL || out_count(NJ) > 2147483647LL) return fail(STS_EINVAL, "the joined signal is too long for one call (N_J <= 2 10^9 native and L_out <= 2^31 - 1 output samples)");
+        last_join_start.resize(B);
+        for (int b = 0; b < B; b++) last_join_start[b] = ((long long)p_offF[b] + join_sil[b]) * hop;
+    }
     if (!c.ahead) {   // frame geometry + (normal call) the decode windows = the utterances, in the same copy
         int* pw = pm + 5 * B + 2;
         for (int b = 0; b < B; b++) { pw[b] = p_offF[b]; pw[B + b] = p_offF[b]; pw[2 * B + b] = p_lenF[b]; }
@@ -944,7 +982,8 @@ int Engine::frame_geometry(RunCtx& c) {
     }
     h_pcm = nullptr; pcm_in_host_ = false;
     if (host_pcm && !ss) {   // room for the PCM download that rides at the end of this run
-        const size_t need = (size_t)(resampling() ? out_count((long long)c.Fld * hop) + B : (long long)c.Fld * hop) * 2 + 256;
+        const long long native = c.join ? c.FJ * hop : (long long)c.Fld * hop;       // (a joined run returns the joined signal)
+        const size_t need = (size_t)(resampling() ? out_count(native) + B : native) * 2 + 256;
         if (need > pinned_pcm_cap_) {
             if (pinned_pcm_) (void)hipHostFree(pinned_pcm_);
             pinned_pcm_ = nullptr; pinned_pcm_cap_ = 0;
@@ -1019,10 +1058,13 @@ int Engine::run_frame_workspace(RunCtx& c) {
         // scratch and the gain cast writes bf.pcm; the limiter likewise)
         // (a gain plan: the tail likewise writes the float wave and its int16 samples go to scratch; the gain kernel writes the gained wave
         // and, with nothing downstream, bf.pcm)
-        bf.wave = A.get<float>(record_taps || resampling() || loud || lim || c.gain ? (size_t)Wcap * hop : 1);
+        // (a joined run: again the tail writes the float wave and its int16 samples go to scratch; the join kernel writes the joined wave
+        // and, with nothing downstream, bf.pcm; everything behind it is sized for the one joined utterance: c.Ocap)
+        bf.wave = A.get<float>(record_taps || resampling() || loud || lim || c.gain || c.join ? (size_t)Wcap * hop : 1);
         bf.wave_gain = c.gain ? A.get<float>((size_t)Wcap * hop) : nullptr;
+        bf.wave_join = c.join ? A.get<float>((size_t)(c.FJ * hop)) : nullptr;
         bf.pcm = A.get<int16_t>((size_t)c.Ocap);
-        bf.pcm_nat = resampling() || norm || c.gain ? A.get<int16_t>((size_t)Wcap * hop) : bf.pcm;
+        bf.pcm_nat = resampling() || norm || c.gain || c.join ? A.get<int16_t>((size_t)Wcap * hop) : bf.pcm;
         bf.wave_out = (record_taps || loud || lim) && resampling() ? A.get<float>((size_t)c.Ocap) : nullptr;
         bf.pcm_rs = norm && resampling() ? A.get<int16_t>((size_t)c.Ocap) : bf.pcm;
         bf.lws = loud ? A.get<char>(loud_ws_bytes(B, c.Ocap)) : nullptr;
@@ -1038,6 +1080,7 @@ int Engine::run_frame_workspace(RunCtx& c) {
         }
     };
     c.Ocap = resampling() ? out_count((long long)Wcap * hop) + B : (long long)Wcap * hop;
+    if (c.join) c.Ocap = resampling() ? out_count(c.FJ * hop) + 1 : c.FJ * hop;
     if (ss && lim && resampling()) c.Ocap += B;       // (a window's widened output range is rounded per window)
     arenaF_.measuring = true; layoutF(arenaF_);
     if (!ensure(arenaF_, arenaF_.used + 4096)) return fail(STS_EDEVICE, "out of device memory (frame-level workspace)");
@@ -1048,7 +1091,7 @@ int Engine::run_frame_workspace(RunCtx& c) {
     if (pcm_direct && host_pcm && !ss && B == 1 && !record_taps && pinned_pcm_dev_ && (size_t)c.Ocap * 2 + 256 <= pinned_pcm_cap_ &&
         (size_t)c.Ocap * 2 <= ((size_t)4 << 20)) {
         bf.pcm = pinned_pcm_dev_;
-        if (!resampling() && !norm && !c.gain) bf.pcm_nat = bf.pcm;     // (native rate: the tail's own samples are the PCM; otherwise the resampler, the gain cast or the gain-plan kernel writes there)
+        if (!resampling() && !norm && !c.gain && !c.join) bf.pcm_nat = bf.pcm;     // (native rate: the tail's own samples are the PCM; otherwise the resampler, the gain cast, the gain-plan kernel or the join kernel writes there)
         if (!norm) bf.pcm_rs = bf.pcm;
         pcm_in_host_ = true;
     }
@@ -1255,7 +1298,8 @@ int Engine::run_once(int B, const int32_t* const* ids, const int32_t* n, const i
     for (double& f : bytes_w_) f = 0;
     mfma_flops_ = 0; mfma_exec_ = 0; bf16_exec_ = 0; mfma_launches_ = 0; in_mfma_region_ = false;
 
-    loud_res.clear(); lim_res.clear();
+    loud_res.clear(); lim_res.clear(); last_join_start.clear();
+    if (ss && join_on) return fail(STS_EINVAL, "a joined call has no streaming form");
     if (ss && loud_mode != 0)
         return fail(STS_EINVAL, "streaming is not available while loudness measurement or normalization is on (sts_set_loudness mode 0 first): "
                                 "normalizing needs the whole utterance before its first sample leaves");
@@ -1306,10 +1350,12 @@ int Engine::run_output(RunCtx& c) {
     }
     const long Fcount = c.Ftot;                // (from here on: the real count)
     for (int b = 0; b < B; b++) n_samples[b] = (int32_t)out_count((long long)p_lenF[b] * hop);     // (at the output rate)
+    const int nres = c.join ? 1 : B;           // utterances the output side saw: a joined run's one signal
+    if (c.join) n_samples.assign(1, (int32_t)out_count(c.FJ * hop));
     if (!ss) {
         d_pcm = bf.pcm;
         total_samples = 0;
-        for (int b = 0; b < B; b++) total_samples += n_samples[b];
+        for (int b = 0; b < nres; b++) total_samples += n_samples[b];
         if (host_pcm) {
             if (!ahead && !pcm_in_host_) HIPCK(hipMemcpyAsync(pinned_pcm_, bf.pcm, (size_t)total_samples * 2, hipMemcpyDeviceToHost, stream));
             h_pcm = (const int16_t*)pinned_pcm_;
@@ -1339,8 +1385,8 @@ int Engine::run_output(RunCtx& c) {
             prof.launch_ahead = 1;
         }
         HIPCK(hipGetLastError());
-        if (loud_mode != 0) loud_res.assign((const sts_loudness*)loud_host_, (const sts_loudness*)loud_host_ + B);   // (behind the run's last synchronisation)
-        if (lim_mode != 0) { lim_res.resize(B); limiter_stats_decode(lim_host_, B, lim_res.data()); }
+        if (loud_mode != 0) loud_res.assign((const sts_loudness*)loud_host_, (const sts_loudness*)loud_host_ + nres);   // (behind the run's last synchronisation)
+        if (lim_mode != 0) { lim_res.resize(nres); limiter_stats_decode(lim_host_, nres, lim_res.data()); }
     } else {
         const int rc = run_stream_steps(c);
         if (rc != STS_OK) return rc;

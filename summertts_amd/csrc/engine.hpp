@@ -136,6 +136,14 @@ public:
     // gain_n: the phoneme counts the next call must have
     std::vector<int32_t> gain_n, gain_words; bool have_gain = false;
     int set_gain_plan(int B, const int32_t* n, const sts_gain_plan* plans);
+    // paragraph join (sts_infer_ids_joined, join.hip): run_joined() runs the B sentences as run() would and joins their native float waves
+    // into one signal in front of the resampler, loudness, the limiter and the cast.  join_on: the run in progress joins; join_sil: silence
+    // frames in front of each sentence (kernels.hpp join_silence), join_total_sil: lead + every gap + trail; join_h: the fade in samples.
+    // last_join_start: sentence starts of the last run in native samples (empty: it was not a joined run)
+    bool join_on = false; std::vector<int32_t> join_sil; long long join_total_sil = 0; int join_h = 0;
+    std::vector<int64_t> last_join_start;
+    int run_joined(int B, const int32_t* const* ids, const int32_t* n, const int32_t* sid, const float* ls, const sts_join* join);
+    int join_offsets(int64_t* start, int64_t capacity);
     // phoneme start offsets of the last run in output samples, packed like durations_h (sts_get_phoneme_offsets); last_n: its phoneme counts
     std::vector<int32_t> last_n;
     int phoneme_offsets(int64_t* start, int64_t capacity);

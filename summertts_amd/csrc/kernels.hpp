@@ -476,4 +476,25 @@ struct GainArgs {
 // one launch: nmem members x ceil(max_len / 4096) tiles; max_len = the longest member's sample count or more
 void gain_plan_run(const GainArgs& a, int nmem, long long max_len, hipStream_t st);
 
+// Paragraph join (join.hip; the definition is there and in include/summertts_hip.h sts_infer_ids_joined)
+constexpr int kJoinMaxFrames = 100000, kJoinMaxH = 800;
+// every gap (null: all 0), lead and trail in [0, 100000] frames, fade_ms finite in [0, 50] (false for NaN), B >= 1
+bool join_valid(int B, const sts_join* j, const char** why);
+// step 1 of the definition: h = floor(fade_ms 16 + 0.5)
+int join_design(float fade_ms);
+// silence in front of sentence b, in frames: sil[b] = lead + gap_0 + .. + gap_{b-1}; returns lead + every gap + trail (64-bit: the
+// caller bounds it).  j == null: all zeros
+long long join_silence(int B, const sts_join* j, long long* sil);
+struct JoinArgs {
+    const float* x;                      // the native float waves of the B sentences, packed back to back in call order
+    float* y; int16_t* pcm;              // the joined signal J [NJ] and its cast, each optional (y 16-byte, pcm 8-byte aligned)
+    SegView wseg;                        // sentence b's place in x, in frames (off == null: one sentence {ioff, ilen}); off[b] = len[0] + .. + len[b - 1]
+    const int* sil;                      // [B] silence frames in front of sentence b in J (join_silence); null: one sentence behind isil frames
+    int isil;
+    int B, hop, h;                       // sentences, samples per frame, fade length in samples (0 .. kJoinMaxH)
+    long long NJ;                        // samples of J: (sum len + lead + every gap + trail) hop
+};
+// one launch: ceil(NJ / span) workgroups, each owning a contiguous span of J (silence included: no memset)
+void join_run(const JoinArgs& a, hipStream_t st);
+
 }  // namespace sts

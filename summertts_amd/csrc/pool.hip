@@ -33,6 +33,10 @@ struct Request {
     bool mixed = false; SpeakerMixCopy mix;
     // sts_pool_submit_gain: this request's gain plan (gained: an entry with gains; gain_db: n entries)
     bool gained = false; std::vector<float> gain_db; float ramp_ms = 0.f;
+    // sts_pool_submit_joined: a paragraph -- its sentences (ids / sid / ls above stay empty), the join (gaps copied: join.gap_frames points
+    // into them, or is null) -- run as its own packed batch; sentence b samples with noise.seed + b
+    bool joined = false; std::vector<std::vector<int32_t>> sent_ids; std::vector<int32_t> sent_sid; std::vector<float> sent_ls;
+    std::vector<int32_t> gaps; sts_join join{nullptr, 0, 0, 0.f};
     // sts_pool_submit_stream: chunks go to cb (on the worker thread); the ticket completes with pcm = null, n = samples delivered
     bool stream = false; int32_t chunk = 0; sts_chunk_cb cb = nullptr; void* user = nullptr;
     // result
@@ -63,12 +67,15 @@ struct sts_pool {
                 std::unique_lock<std::mutex> lk(mu);
                 cv_work.wait(lk, [&] { return stop || !queue.empty(); });
                 if (stop && queue.empty()) return;
-                // a batch is a run of the FIFO's head: whole-utterance requests, or streaming requests of one chunk size -- never both
+                // a batch is a run of the FIFO's head: whole-utterance requests, or streaming requests of one chunk size -- never both; a
+                // joined request is a batch by itself
                 const bool st = queue.front()->stream; const int32_t ch = queue.front()->chunk;
-                while (!queue.empty() && (int)take.size() < max_batch && queue.front()->stream == st && (!st || queue.front()->chunk == ch)) {
+                if (queue.front()->joined) { take.push_back(queue.front()); queue.pop_front(); }
+                else while (!queue.empty() && (int)take.size() < max_batch && !queue.front()->joined && queue.front()->stream == st && (!st || queue.front()->chunk == ch)) {
                     take.push_back(queue.front()); queue.pop_front();
                 }
             }
+            if (take.front()->joined) { run_joined_request(eng, *take.front()); cv_done.notify_all(); continue; }
             if (take.front()->stream) { run_stream_group(eng, take); cv_done.notify_all(); continue; }
             // run `grp` as one packed batch; on failure of a multi-request batch, re-run its members one by one so
             // that a bad request (e.g. an id outside the vocabulary) only fails itself
@@ -139,6 +146,35 @@ struct sts_pool {
             run_group(take, run_group);
             cv_done.notify_all();
         }
+    }
+
+    // a paragraph (Engine::run_joined): its sentences as one packed batch of their own, one PCM
+    void run_joined_request(Engine& eng, Request& r) {
+        const int B = (int)r.sent_ids.size();
+        std::vector<const int32_t*> idp(B); std::vector<int32_t> n(B);
+        eng.noise_utt.resize(B);
+        for (int b = 0; b < B; b++) {
+            idp[b] = r.sent_ids[b].data(); n[b] = (int32_t)r.sent_ids[b].size();
+            eng.noise_utt[b] = Engine::Noise{r.noise.ns, r.noise.nsw, r.noise.seed + (uint64_t)b};
+        }
+        int rc = eng.run_joined(B, idp.data(), n.data(), r.sent_sid.data(), r.sent_ls.data(), &r.join);
+        eng.noise_utt.clear();
+        int16_t* pcm = nullptr;
+        const int64_t total = rc == STS_OK ? eng.total_samples : 0;
+        if (rc == STS_OK) {
+            pcm = (int16_t*)malloc((size_t)(total > 0 ? total : 1) * 2);
+            if (!pcm) rc = STS_EDEVICE;
+            else if (eng.h_pcm) memcpy(pcm, eng.h_pcm, (size_t)total * 2);   // downloaded inside the run
+            else if (!eng.pcm_hbm() || hipMemcpyAsync(pcm, eng.pcm_hbm(), (size_t)total * 2, hipMemcpyDeviceToHost, eng.stream) != hipSuccess ||
+                     hipStreamSynchronize(eng.stream) != hipSuccess)
+                rc = STS_EDEVICE;
+        }
+        std::lock_guard<std::mutex> lk(mu);
+        r.rc = rc;
+        if (rc == STS_OK) { r.pcm = pcm; r.n = (int32_t)total; }
+        else { free(pcm); r.err = eng.error().empty() ? "the joined request failed" : eng.error(); }
+        r.done = true;
+        batches++; requests++;
     }
 
     // streaming requests as one batched stream (Engine::run_batch_stream).  A member's ticket completes at its last chunk or its stop; a
@@ -294,6 +330,38 @@ int64_t sts_pool_submit_gain(sts_pool* p, const int32_t* ids, int32_t n, int32_t
     r->ids.assign(ids, ids + n); r->sid = sid; r->ls = length_scale; r->noise = Engine::Noise{noise_scale, noise_scale_w, seed};
     r->gained = plan && plan->gain_db;
     if (r->gained) { r->gain_db.assign(plan->gain_db, plan->gain_db + n); r->ramp_ms = plan->ramp_ms; }
+    {
+        std::lock_guard<std::mutex> lk(p->mu);
+        if (p->stop) return pool_err(STS_ESTATE, "pool is shutting down");
+        r->ticket = p->next_ticket++;
+        p->queue.push_back(r);
+        p->pending[r->ticket] = r;
+    }
+    p->cv_work.notify_one();
+    return r->ticket;
+}
+
+int64_t sts_pool_submit_joined(sts_pool* p, int32_t B, const int32_t* const* ids, const int32_t* n, const int32_t* sid,
+                               const float* length_scale, float noise_scale, float noise_scale_w, uint64_t seed, const sts_join* join) {
+    if (!p || !ids || !n || B < 1 || B > (1 << 20)) return pool_err(STS_EINVAL, "bad request");
+    if (!noise_scale_valid(noise_scale) || !noise_scale_valid(noise_scale_w)) return pool_err(STS_EINVAL, "noise scales must be finite and >= 0");
+    const char* why = nullptr;
+    if (!join_valid(B, join, &why)) return pool_err(STS_EINVAL, why);
+    for (int b = 0; b < B; b++) if (!ids[b] || n[b] <= 0) return pool_err(STS_EINVAL, "bad request");
+    auto r = std::make_shared<Request>();
+    r->joined = true;
+    r->noise = Engine::Noise{noise_scale, noise_scale_w, seed};
+    r->sent_ids.resize((size_t)B); r->sent_sid.assign((size_t)B, 0); r->sent_ls.assign((size_t)B, 1.f);
+    for (int b = 0; b < B; b++) {
+        r->sent_ids[b].assign(ids[b], ids[b] + n[b]);
+        if (sid) r->sent_sid[b] = sid[b];
+        if (length_scale) r->sent_ls[b] = length_scale[b];
+    }
+    if (join) {
+        r->join = *join;
+        if (join->gap_frames && B > 1) { r->gaps.assign(join->gap_frames, join->gap_frames + (B - 1)); r->join.gap_frames = r->gaps.data(); }
+        else r->join.gap_frames = nullptr;
+    }
     {
         std::lock_guard<std::mutex> lk(p->mu);
         if (p->stop) return pool_err(STS_ESTATE, "pool is shutting down");

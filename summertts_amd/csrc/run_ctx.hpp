@@ -24,6 +24,8 @@ struct BufT {
     int* mix;
     // a run with a gain plan only (null otherwise): the uploaded table [q Ttot | h B] behind the mix
     int *gain_q, *gain_h;
+    // a joined run only (null otherwise): the uploaded silence table [B] behind the gain plan's (JoinArgs::sil)
+    int* join_sil;
 };
 struct BufF {
     float *z, *h, *acts, *out, *x0, *regA, *regB, *tailA, *tailB, *tailC, *wave, *fliptmp;
@@ -37,6 +39,8 @@ struct BufF {
     // a run with a gain plan only (null otherwise): the gained native float wave, laid out like wave (what the resampler, loudness and the
     // limiter then read in its place)
     float* wave_gain;
+    // a joined run only (null otherwise): the joined native float wave J [NJ] -- one utterance for everything behind it
+    float* wave_join;
     // streaming only (null otherwise): the step tables (stream_tab_bytes); several utterances: the packed chunk buffer stream_pack writes
     // (native rate, no limiter), the per-window speaker vectors and decoder conditioning of a multi-speaker HiFi-GAN decoder
     char* stab; int16_t* spack; float *gwin, *cond_win;
@@ -71,6 +75,8 @@ struct Engine::RunCtx {
     long Fld = 0; int maxFld = 0; bool ahead = false, ahead_b = false, mapped = false, forced = false;
     bool plan = false;              // this run applies a duration plan (sts_set_duration_plan): never launched ahead, never in the memo
     bool gain = false;              // this run applies a gain plan (sts_set_gain_plan): the gain kernel runs behind the decoder's tail; never launched ahead, never in the memo
+    bool join = false;              // this run joins its sentences into one signal (sts_infer_ids_joined): the join kernel runs behind the decoder's tail (and the gain kernel); never launched ahead, never in the memo
+    long long FJ = 0;               // a joined run: frames of the joined signal (sum of the sentences' + lead + gaps + trail)
     bool mix = false;               // this run blends speakers (sts_set_speaker_mix): bt.g comes from speaker_blend; never launched ahead, never in the memo
     std::vector<Engine::Noise> nz; bool any_ns = false, any_nsw = false;   // per-utterance sampling noise (engine.hpp Noise), which of the two is used
     std::vector<unsigned long long> req_keys; std::vector<long> predF;      // launch-ahead memo: per-utterance request hashes, remembered frame counts (empty: not all known)

@@ -133,6 +133,30 @@ def _gain_plans(n: Sequence[int], plans):
     return n, arr, keep
 
 
+class Join(C.Structure):
+    """``sts_join``: how the sentences of a paragraph are joined (include/summertts_hip.h sts_infer_ids_joined)."""
+    _fields_ = [("gap_frames", C.c_void_p), ("lead_frames", C.c_int32), ("trail_frames", C.c_int32), ("fade_ms", C.c_float)]
+
+
+def _join(B: int, join):
+    """-> (ctypes pointer to a Join or None, what it points into).  ``join``: None (all zeros) or a mapping with any of ``gap_frames``
+    (B - 1 ints, silence between sentence b and b + 1, in frames; None = all 0), ``lead_frames``, ``trail_frames`` (default 0) and
+    ``fade_ms`` (edge fade of every sentence, default 0)."""
+    if join is None:
+        return None, None
+    j = Join()
+    g = join.get("gap_frames")
+    if g is not None:
+        g = np.ascontiguousarray(g, dtype=np.int32).ravel()
+        if g.size != max(int(B) - 1, 0):
+            raise ValueError("gap_frames needs B - 1 entries")
+        j.gap_frames = g.ctypes.data if g.size else None
+    j.lead_frames = int(join.get("lead_frames", 0))
+    j.trail_frames = int(join.get("trail_frames", 0))
+    j.fade_ms = float(join.get("fade_ms", 0.0))
+    return C.pointer(j), (j, g)
+
+
 class PreparedBatch:
     """run_batch's argument arrays, built once (Synthesizer.prepare)."""
 
@@ -240,6 +264,15 @@ def load_library() -> C.CDLL:
     lib.sts_debug_spline_step.argtypes = [C.c_int, C.c_void_p, C.c_int64, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.sts_pool_submit_gain.restype = C.c_int64
     lib.sts_pool_submit_gain.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_float, C.c_uint64, C.c_void_p]
+    lib.sts_join_check.argtypes = [C.c_int32, C.c_void_p]
+    lib.sts_join_layout.argtypes = [C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int32)]
+    lib.sts_join_apply.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.sts_infer_ids_joined.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                         C.POINTER(C.POINTER(C.c_int16)), C.POINTER(C.c_int32)]
+    lib.sts_get_join_offsets.argtypes = [C.c_void_p, C.c_void_p, C.c_int64]
+    lib.sts_pool_submit_joined.restype = C.c_int64
+    lib.sts_pool_submit_joined.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_float,
+                                           C.c_uint64, C.c_void_p]
     lib.sts_infer_ids_batch_stream.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
                                                BATCH_CHUNK_CB, C.c_void_p, C.c_void_p]
     lib.sts_pool_submit_stream.restype = C.c_int64
@@ -277,6 +310,7 @@ EXPORTED_SYMBOLS = [
     "sts_set_gain_plan", "sts_gain_plan_check", "sts_gain_design", "sts_gain_plan_apply", "sts_pool_submit_gain",
     "sts_multi_set_gain_plan",
     "sts_debug_spline_step",
+    "sts_join_check", "sts_join_layout", "sts_join_apply", "sts_infer_ids_joined", "sts_get_join_offsets", "sts_pool_submit_joined",
 ]
 
 
@@ -356,6 +390,48 @@ def gain_plan_apply(signals, durations, plans, samples_per_frame: int, device: i
                                         C.cast(arr, C.c_void_p), y.ctypes.data, pcm.ctypes.data))
     off = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
     return [y[off[b]:off[b + 1]].copy() for b in range(len(ds))], [pcm[off[b]:off[b + 1]].copy() for b in range(len(ds))]
+
+
+def join_check(B: int, join) -> None:
+    """The validity rules of a join (include/summertts_hip.h sts_join_check; host only, no GPU) for ``B`` sentences; ``join`` as
+    ``Synthesizer.infer_joined`` takes it.  Raises StsError for an invalid join."""
+    lib = load_library()
+    jp, keep = _join(B, join)
+    _check(lib, lib.sts_join_check(int(B), jp))
+
+
+def join_layout(frames: Sequence[int], samples_per_frame: int, join=None):
+    """Steps 1-2 of the join definition (include/summertts_hip.h sts_join_layout; host only, no GPU): sentences of ``frames[b]`` frames ->
+    (start, total, h): each sentence's first sample in the joined signal (int64, native samples), the joined length N_J and the fade
+    length in samples."""
+    lib = load_library()
+    f = np.ascontiguousarray(frames, dtype=np.int32).ravel()
+    jp, keep = _join(f.size, join)
+    start = np.zeros(max(f.size, 1), np.int64)
+    total, h = C.c_int64(), C.c_int32()
+    _check(lib, lib.sts_join_layout(f.size, f.ctypes.data, int(samples_per_frame), jp, start.ctypes.data, C.byref(total), C.byref(h)))
+    return start[:f.size], int(total.value), int(h.value)
+
+
+def join_apply(signals, frames: Sequence[int], samples_per_frame: int, join=None, device: int = 0):
+    """The join kernel on caller signals (sts_join_apply): ``signals[b]`` a float signal of ``frames[b] * samples_per_frame`` samples ->
+    (J, pcm): the joined float32 signal and its int16 cast."""
+    lib = load_library()
+    f = np.ascontiguousarray(frames, dtype=np.int32).ravel()
+    sig = [np.ascontiguousarray(x, dtype=np.float32).ravel() for x in signals]
+    if len(sig) != f.size:
+        raise ValueError("one signal per sentence")
+    for b, x in enumerate(sig):
+        if x.size != int(f[b]) * int(samples_per_frame):
+            raise ValueError(f"signal {b} needs frames * samples_per_frame = {int(f[b]) * int(samples_per_frame)} samples")
+    _, total, _ = join_layout(f, samples_per_frame, join)
+    jp, keep = _join(f.size, join)
+    x = np.concatenate(sig) if sig else np.zeros(1, np.float32)
+    y = np.zeros(max(total, 1), np.float32)
+    pcm = np.zeros(max(total, 1), np.int16)
+    _check(lib, lib.sts_join_apply(int(device), x.ctypes.data, f.ctypes.data, f.size, int(samples_per_frame), jp, y.ctypes.data,
+                                   pcm.ctypes.data))
+    return y[:total], pcm[:total]
 
 
 def debug_spline_step(h, filter_sqrt: float, r0=None, r1=None, device: int = 0, o0=None, o1=None):
@@ -627,6 +703,25 @@ class Synthesizer:
         flat = self.pcm_host()
         offs = np.concatenate([[0], np.cumsum(n_out)])
         return [flat[offs[b]:offs[b + 1]].copy() for b in range(len(n_out))]
+
+    def infer_joined(self, ids, sid=None, length_scale=None, join=None) -> np.ndarray:
+        """A paragraph (include/summertts_hip.h sts_infer_ids_joined): the sentences ``ids`` run as one packed batch and are joined on the
+        device into ONE int16 signal, which the resampler, loudness and the limiter see as a single utterance.  ``join``: None (back to
+        back, no fade) or a mapping with any of ``gap_frames`` (B - 1 ints), ``lead_frames``, ``trail_frames`` and ``fade_ms``.  Pending
+        forced durations, duration plans, speaker mixes and gain plans apply per sentence.  An invalid join raises and changes nothing."""
+        p = ids if isinstance(ids, PreparedBatch) else PreparedBatch(ids, sid, length_scale)
+        jp, keep = _join(p.B, join)
+        out, n = C.POINTER(C.c_int16)(), C.c_int32()
+        _check(self.lib, self.lib.sts_infer_ids_joined(self.h, p.B, p.ptrs, p.n_p, p.sid_p, p.ls_p, jp, C.byref(out), C.byref(n)))
+        pcm = np.ctypeslib.as_array(out, shape=(n.value,)).copy() if n.value else np.zeros(0, np.int16)
+        self.lib.sts_free(out)
+        return pcm
+
+    def join_offsets(self, B: int) -> np.ndarray:
+        """Start of every sentence of the last ``infer_joined`` in output samples at the current output rate (sts_get_join_offsets)."""
+        s = np.zeros(max(int(B), 1), np.int64)
+        _check(self.lib, self.lib.sts_get_join_offsets(self.h, s.ctypes.data, int(B)))
+        return s[:int(B)]
 
     # -- parity / diagnostics ---------------------------------------------------------------
     def set_forced_durations(self, dur: Optional[Sequence[int]]):
@@ -996,8 +1091,20 @@ class Pool:
             raise StsError(f"sts_pool_submit: {t}: {self.lib.sts_pool_last_error().decode()}")
         return t
 
+    def submit_joined(self, ids, sid=None, length_scale=None, noise_scale: float = 0.0, noise_scale_w: float = 0.0, seed: int = 0,
+                      join=None) -> int:
+        """Queue one paragraph (sts_pool_submit_joined): the sentences ``ids`` with ``join`` as ``Synthesizer.infer_joined`` takes it.  One
+        ticket, one PCM; it runs as its own packed batch, whatever ``max_batch`` is.  Sentence b samples with ``seed + b``."""
+        p = PreparedBatch(ids, sid, length_scale)
+        jp, keep = _join(p.B, join)
+        t = int(self.lib.sts_pool_submit_joined(self.h, p.B, p.ptrs, p.n_p, p.sid_p, p.ls_p, float(noise_scale), float(noise_scale_w),
+                                                int(seed) & 0xFFFFFFFFFFFFFFFF, jp))
+        if t <= 0:
+            raise StsError(f"sts_pool_submit_joined: {t}: {self.lib.sts_pool_last_error().decode()}")
+        return t
+
     def wait(self, ticket: int) -> np.ndarray:
-        """The PCM of a whole-utterance request; for a streaming request (submit_stream) the number of samples delivered."""
+        """The PCM of a whole-utterance or joined request; for a streaming request (submit_stream) the number of samples delivered."""
         p = C.POINTER(C.c_int16)()
         n = C.c_int32()
         rc = self.lib.sts_pool_wait(self.h, ticket, C.byref(p), C.byref(n))
