@@ -428,11 +428,62 @@ int sts_infer_ids_joined(sts_engine* e, int32_t B, const int32_t* const* ids, co
 /* Sentence starts of the last call in output samples, ceil(start_b P / Q): [B] entries (capacity below B: STS_EINVAL).  STS_ESTATE when the
  * last call was not a joined one. */
 int sts_get_join_offsets(sts_engine* e, int64_t* start, int64_t capacity);
+/* ---- parametric equaliser (no reference counterpart; ABI number unchanged).  sts_set_eq(e, n_bands, bands) puts a tone stage of 0 to
+ * STS_EQ_MAX_BANDS biquad sections in front of loudness and the limiter: an "audio profile" (telephone band, rumble and DC removal, a
+ * presence lift) that loudness mode 2 and the limiter then measure and limit as played.  n_bands = 0 (default) switches the stage off:
+ * nothing extra is allocated, uploaded or launched and the PCM is bit-identical to an engine that never set it.  The setting persists
+ * like sts_set_limiter; sts_get_eq returns it (n_bands always; the first min(n_bands, capacity) bands when bands is non-null).
+ *   Band {type, freq_hz, gain_db, q}: type STS_EQ_PEAK, _LOWSHELF, _HIGHSHELF, _HIGHPASS or _LOWPASS; gain_db is ignored by the two
+ *   passes but must be finite.  Valid at output rate fs: type in 1..5, freq_hz in [20, 0.45 fs], q in [0.1, 8], gain_db in [-24, 24],
+ *   q fs / freq_hz <= 6400 (alpha below is then at least 4.9e-4 and every pole lies at least 1.2e-4 inside the unit circle: the bound
+ *   on which the numerical tolerance below rests), everything finite.  Anything else: STS_EINVAL, nothing changes.  sts_set_eq checks against the engine's current
+ *   output rate; a run checks again (sts_set_output_rate may have been called since) and answers STS_EINVAL before anything is enqueued
+ *   when a band no longer fits.
+ *   1 Coefficients (host, float64; exactly what sts_eq_design returns, 5 per band): the Audio-EQ-Cookbook biquad with
+ *     w0 = 2 pi f0 / fs, alpha = sin w0 / (2 q), A = 10^(gain_db / 40), the shelves in the Q form 2 sqrt(A) alpha:
+ *       peak       b = {1 + alpha A, -2 cos w0, 1 - alpha A}                          a = {1 + alpha / A, -2 cos w0, 1 - alpha / A}
+ *       high-pass  b = {(1 + cos w0) / 2, -(1 + cos w0), (1 + cos w0) / 2}            a = {1 + alpha, -2 cos w0, 1 - alpha}
+ *       low-pass   b = {(1 - cos w0) / 2, 1 - cos w0, (1 - cos w0) / 2}               a = {1 + alpha, -2 cos w0, 1 - alpha}
+ *       low shelf  b = {A (A+1 - (A-1) cos w0 + s), 2 A (A-1 - (A+1) cos w0), A (A+1 - (A-1) cos w0 - s)}
+ *                  a = {A+1 + (A-1) cos w0 + s, -2 (A-1 + (A+1) cos w0), A+1 + (A-1) cos w0 - s},   s = 2 sqrt(A) alpha
+ *       high shelf b = {A (A+1 + (A-1) cos w0 + s), -2 A (A-1 + (A+1) cos w0), A (A+1 + (A-1) cos w0 - s)}
+ *                  a = {A+1 - (A-1) cos w0 + s, 2 (A-1 - (A+1) cos w0), A+1 - (A-1) cos w0 - s}
+ *     normalised by a0 to (b0, b1, b2, a1, a2).
+ *   2 Signal, for one utterance x[0 .. N) (float32) at the output rate, N unchanged, no tail: u_0 = float64(x); section s in band order,
+ *     direct form I from zero state at the utterance's first sample,
+ *       u_s[n] = b0 u_{s-1}[n] + b1 u_{s-1}[n-1] + b2 u_{s-1}[n-2] - a1 u_s[n-1] - a2 u_s[n-2]      (float64);
+ *     y = float32(u_S), pcm = the reference's cast (int16)(int32)(y * 32737).  An utterance's output depends on its own samples only.
+ *   The kernels (eq.hip) evaluate the recurrence as a scan over chunks, which associates it differently: y equals the definition within
+ *   2^-24 |u_S[n]| + 2^-26 max |u_S| per sample (tests/eq_ref.py holds the definition and the scan's order, both in float64).
+ * Place in the chain: decoder tail -> gain plan -> join -> resampler -> EQ -> loudness -> limiter -> cast.  The EQ runs at the output
+ * rate; after sts_infer_ids_joined it sees the ONE joined signal.  With nothing downstream (loudness mode 0 or 1, limiter off) the EQ
+ * kernel writes the PCM itself; loudness and the limiter read the EQ's float output.  Tap "wave_eq": that output ("wave", "wave_gain",
+ * "wave_join", "wave_out" stay the signals in front of it).
+ * Streaming (sts_infer_ids_stream, sts_infer_ids_batch_stream, sts_pool_submit_stream) answers STS_EINVAL while an EQ is set: an IIR has
+ * no finite halo, and a state carried from chunk to chunk would make the PCM depend on the chunking. */
+#define STS_EQ_MAX_BANDS 4
+#define STS_EQ_PEAK 1
+#define STS_EQ_LOWSHELF 2
+#define STS_EQ_HIGHSHELF 3
+#define STS_EQ_HIGHPASS 4
+#define STS_EQ_LOWPASS 5
+typedef struct sts_eq_band { int32_t type; float freq_hz; float gain_db; float q; } sts_eq_band;
+int sts_set_eq(sts_engine* e, int32_t n_bands, const sts_eq_band* bands);
+int sts_get_eq(const sts_engine* e, int32_t* n_bands, sts_eq_band* bands, int32_t capacity);
+/* Host only (no device): the validity rules above at output rate `rate` (STS_OK or STS_EINVAL with the reason in sts_last_error). */
+int sts_eq_check(int32_t rate, int32_t n_bands, const sts_eq_band* bands);
+/* Host only (no device): step 1 for valid bands; coeffs receives 5 float64 per band, {b0, b1, b2, a1, a2}. */
+int sts_eq_design(int32_t rate, int32_t n_bands, const sts_eq_band* bands, double* coeffs);
+/* The same kernels on caller signals, like sts_limiter_apply: B float signals at `rate` packed back to back in x (host memory),
+ * lengths[b] samples each (0 allowed), n_bands >= 1.  y (float) and pcm (int16) receive the equalised signals packed like x; each may be
+ * NULL.  (On the device both start out as NaN / 0x7FFF, so a sample the kernels left out shows.) */
+int sts_eq_apply(int device, const float* x, const int64_t* lengths, int32_t B, int32_t rate, int32_t n_bands,
+                 const sts_eq_band* bands, float* y, int16_t* pcm);
 /*   record intermediate tensors of the next run: "x_enc","m","logs","logw","z_p","z","wave","wave_out" ("logs": the second half of the
  *   encoder projection, computed only by runs that record taps or sample the prior; "wave_out": the resampled float wave, only at a
  *   non-native output rate, one-pass calls; "dur_w": the planned duration weights, only a run with a duration plan; "wave_gain": the
  *   gained native float wave, only a one-pass run with a gain plan; "wave_join": the joined native float wave J, only
- *   sts_infer_ids_joined) */
+ *   sts_infer_ids_joined; "wave_eq": the equaliser's float output at the output rate, only a one-pass run with sts_set_eq) */
 int sts_set_record_taps(sts_engine* e, int enable);
 /*   fetch a tap: malloc()'d copy, channel-major [channels][total_len] (== the reference's column-major
  *   MatrixXf [time, channels]); for batches the utterances are packed along time. */
@@ -624,6 +675,9 @@ int sts_pool_set_loudness(sts_pool* p, int mode, float target_lufs, float peak_d
 /*   sts_pool_set_limiter (ABI 13): sts_set_limiter on every engine of the pool.  STS_ESTATE while any request is outstanding, as
  *   sts_pool_set_output_rate.  Streaming requests are limited chunk by chunk. */
 int sts_pool_set_limiter(sts_pool* p, int mode, float gain_db, float ceiling_dbfs, float lookahead_ms);
+/*   sts_pool_set_eq: sts_set_eq on every engine of the pool (one setting for every request; no per-request EQ).  STS_ESTATE while any
+ *   request is outstanding.  While bands are set, sts_pool_submit_stream answers STS_EINVAL. */
+int sts_pool_set_eq(sts_pool* p, int32_t n_bands, const sts_eq_band* bands);
 /*   sts_pool_submit_plan (ABI 14): sts_pool_submit_ex with this request's own duration plan (sts_set_duration_plan: rate and fixed hold n
  *   entries each or are NULL, target_frames 0 = none; an invalid plan answers STS_EINVAL).  Whole-utterance requests only.  Requests with and
  *   without a plan share one packed batch: the plan is per utterance. */
@@ -681,6 +735,8 @@ int sts_multi_set_output_rate(sts_multi* m, int32_t rate);
 int sts_multi_set_loudness(sts_multi* m, int mode, float target_lufs, float peak_dbfs);
 /*   sts_multi_set_limiter (ABI 13): sts_set_limiter on every engine of the handle. */
 int sts_multi_set_limiter(sts_multi* m, int mode, float gain_db, float ceiling_dbfs, float lookahead_ms);
+/*   sts_multi_set_eq: sts_set_eq on every engine of the handle. */
+int sts_multi_set_eq(sts_multi* m, int32_t n_bands, const sts_eq_band* bands);
 /*   sts_multi_set_duration_plan (ABI 14): sts_set_duration_plan for the NEXT sts_multi_infer_ids_batch of the handle, which must have the
  *   same B and n[b] (otherwise STS_EINVAL and nothing runs).  plans[b] belongs to utterance b of the caller's batch and follows it into its
  *   device's shard: the PCM does not depend on the number of devices. */

@@ -676,6 +676,77 @@ int sts_limiter_apply(int device, const float* x, const int64_t* lengths, int32_
     if (stats) limiter_stats_decode(raw.data(), B, stats);
     return STS_OK;
 }
+int sts_set_eq(sts_engine* e, int32_t n_bands, const sts_eq_band* bands) {
+    if (!e) return set_err(STS_EINVAL, "null engine");
+    const int rc = e->eng.set_eq(n_bands, bands);
+    return rc == STS_OK ? STS_OK : set_err(rc, e->eng.error());
+}
+int sts_get_eq(const sts_engine* e, int32_t* n_bands, sts_eq_band* bands, int32_t capacity) {
+    if (!e) return set_err(STS_EINVAL, "null engine");
+    if (n_bands) *n_bands = e->eng.eq_n;
+    for (int i = 0; bands && i < e->eng.eq_n && i < capacity; i++) bands[i] = e->eng.eq_bands[i];
+    return STS_OK;
+}
+int sts_eq_check(int32_t rate, int32_t n_bands, const sts_eq_band* bands) {
+    const char* why = nullptr;
+    return eq_valid(rate, n_bands, bands, &why) ? STS_OK : set_err(STS_EINVAL, why);
+}
+int sts_eq_design(int32_t rate, int32_t n_bands, const sts_eq_band* bands, double* coeffs) {
+    const char* why = nullptr;
+    if (!eq_valid(rate, n_bands, bands, &why)) return set_err(STS_EINVAL, why);
+    if (n_bands > 0 && !coeffs) return set_err(STS_EINVAL, "null argument");
+    eq_design(rate, n_bands, bands, coeffs);
+    return STS_OK;
+}
+int sts_eq_apply(int device, const float* x, const int64_t* lengths, int32_t B, int32_t rate, int32_t n_bands, const sts_eq_band* bands,
+                 float* y, int16_t* pcm) {
+    if (B < 1 || !lengths) return set_err(STS_EINVAL, "B >= 1 and lengths are required");
+    const char* why = nullptr;
+    if (!eq_valid(rate, n_bands, bands, &why)) return set_err(STS_EINVAL, why);
+    if (n_bands < 1) return set_err(STS_EINVAL, "eq: at least one band to apply");
+    std::vector<int> len(B);
+    int64_t total = 0, maxl = 0;
+    for (int b = 0; b < B; b++) {
+        if (lengths[b] < 0 || lengths[b] > (int64_t)1 << 30) return set_err(STS_EINVAL, "lengths must be in [0, 2^30]");
+        len[b] = (int)lengths[b]; total += lengths[b]; maxl = std::max<int64_t>(maxl, lengths[b]);
+    }
+    if (total > (int64_t)1 << 30) return set_err(STS_EINVAL, "the signals must hold at most 2^30 samples in all");
+    if (total > 0 && !x) return set_err(STS_EINVAL, "null signal");
+    double coef[5 * STS_EQ_MAX_BANDS];
+    eq_design(rate, n_bands, bands, coef);
+    EqTable tab;
+    eq_table(n_bands, coef, &tab);
+    if (hipSetDevice(device) != hipSuccess) return set_err(STS_EDEVICE, "no such device");
+    auto pad = [](size_t bytes) { return (bytes + 255) & ~(size_t)255; };
+    const size_t xb = pad((size_t)total * 4), lb = pad((size_t)B * 4), pb = pad((size_t)total * 2), tb = pad(sizeof(EqTable));
+    const size_t wb = pad(eq_ws_bytes(B, total));
+    char* d = nullptr;          // [x | lengths | tables | y | pcm | workspace]
+    if (hipMalloc((void**)&d, 2 * xb + lb + tb + pb + wb + 256) != hipSuccess) return set_err(STS_EDEVICE, "out of device memory");
+    hipStream_t st = nullptr;
+    bool ok = hipStreamCreate(&st) == hipSuccess;
+    EqArgs a{};
+    a.x = (const float*)d; a.len = (const int*)(d + xb); a.ilen = 0; a.scale = 1; a.P = 1; a.Q = 1;
+    a.S = n_bands; a.tab = (const EqTable*)(d + xb + lb);
+    char* dy = d + xb + lb + tb; char* dp = dy + xb;
+    a.y = y ? (float*)dy : nullptr; a.pcm = pcm ? (int16_t*)dp : nullptr;
+    eq_ws_carve(a, dp + pb, B, total);
+    // (the outputs start out as NaN / 0x7FFF: a sample the kernels leave out shows)
+    ok = ok && (total == 0 || hipMemcpyAsync(d, x, (size_t)total * 4, hipMemcpyHostToDevice, st) == hipSuccess) &&
+         hipMemcpyAsync(d + xb, len.data(), (size_t)B * 4, hipMemcpyHostToDevice, st) == hipSuccess &&
+         hipMemcpyAsync(d + xb + lb, &tab, sizeof(EqTable), hipMemcpyHostToDevice, st) == hipSuccess &&
+         (xb == 0 || hipMemsetAsync(dy, 0xFF, xb, st) == hipSuccess) &&
+         (pb == 0 || hipMemsetD16Async((hipDeviceptr_t)dp, 0x7FFF, pb / 2, st) == hipSuccess);
+    if (ok) {
+        eq_run(a, B, maxl, st);
+        ok = hipGetLastError() == hipSuccess &&
+             (!y || total == 0 || hipMemcpyAsync(y, dy, (size_t)total * 4, hipMemcpyDeviceToHost, st) == hipSuccess) &&
+             (!pcm || total == 0 || hipMemcpyAsync(pcm, dp, (size_t)total * 2, hipMemcpyDeviceToHost, st) == hipSuccess) &&
+             hipStreamSynchronize(st) == hipSuccess;
+    }
+    if (st) (void)hipStreamDestroy(st);
+    (void)hipFree(d);
+    return ok ? STS_OK : set_err(STS_EDEVICE, "the equaliser failed on the device");
+}
 int sts_build_flags(void) {
 #ifdef STS_EXPERIMENTS
     return 1;

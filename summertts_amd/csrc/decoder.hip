@@ -428,7 +428,7 @@ int Engine::run_decode(RunCtx& c, int nw, long Wtot, int maxW, int zoff0, int wl
     // ---------------- decoder tail
     // (at a non-native output rate the tail always writes the float wave, and its int16 samples go to a scratch buffer: the resampler below
     // produces the PCM from the wave)
-    float* wave = record_taps || resampling() || lim_mode != 0 || (loud_mode != 0 && !ss) || c.gain || c.join ? bf.wave : nullptr;
+    float* wave = record_taps || resampling() || lim_mode != 0 || (loud_mode != 0 && !ss) || (eq_n > 0 && !ss) || c.gain || c.join ? bf.wave : nullptr;
     int16_t* const pcm = bf.pcm_nat;
     const long Ntot = Wtot * hop;
     if (M.dec_type == 0) {          // Generator_hifigan.cpp:177-179 + SynthesizerTrn.cpp:389-396
@@ -472,7 +472,7 @@ int Engine::decode_end(RunCtx& c, const float* wave, const WinGeom& win, long Wt
         // writes the PCM too when nothing downstream does (native rate, no gain cast, no limiter, no join).  Everything below reads its output
         GainArgs g{};
         g.x = wave; g.y = c.bf.wave_gain;
-        g.pcm = !c.join && !resampling() && lim_mode == 0 && !(loud_mode == 2 && !c.ss) ? c.bf.pcm : nullptr;
+        g.pcm = !c.join && !resampling() && lim_mode == 0 && !(loud_mode == 2 && !c.ss) && !c.bf.wave_eq ? c.bf.pcm : nullptr;
         g.wseg = win.seg(hop, 0); g.hop = hop;
         if (c.ss) { g.utt = (const int*)(c.bf.stab + stream_tab_utt_off(nw)); g.wtab = (const long long*)(c.bf.stab + stream_tab_ll_off(nw)); }
         g.tseg = c.lvT.seg; g.cum = c.bt.cum; g.q = c.bt.gain_q; g.h = c.bt.gain_h;
@@ -484,7 +484,7 @@ int Engine::decode_end(RunCtx& c, const float* wave, const WinGeom& win, long Wt
         // downstream does.  From here on there is ONE utterance of F_J frames: one resampled signal, one loudness, one set of limiter stats
         JoinArgs j{};
         j.x = wave; j.y = c.bf.wave_join;
-        j.pcm = !resampling() && lim_mode == 0 && loud_mode != 2 ? c.bf.pcm : nullptr;
+        j.pcm = !resampling() && lim_mode == 0 && loud_mode != 2 && !c.bf.wave_eq ? c.bf.pcm : nullptr;
         j.wseg = win.seg(hop, 0);
         if (win.inl) j.isil = join_sil[0]; else j.sil = c.bt.join_sil;
         j.B = nw; j.hop = hop; j.h = join_h; j.NJ = c.FJ * hop;
@@ -494,8 +494,9 @@ int Engine::decode_end(RunCtx& c, const float* wave, const WinGeom& win, long Wt
         nw = 1; max_out = out_count(c.FJ * hop);
     }
     // LoudArgs / LimArgs: the float signal at the output rate and its utterances' lengths
+    const float* sig = nullptr;             // (the EQ's output once it has run)
     auto signal = [&](auto& a) {
-        a.x = resampling() ? c.bf.wave_out : wave;
+        a.x = sig ? sig : resampling() ? c.bf.wave_out : wave;
         a.len = dw.len(); a.ilen = dw.ilen(); a.scale = hop;
         a.P = resampling() ? rs.P : 1; a.Q = resampling() ? rs.Q : 1;
     };
@@ -506,6 +507,17 @@ int Engine::decode_end(RunCtx& c, const float* wave, const WinGeom& win, long Wt
         a.table = d_rs_table; a.P = rs.P; a.Q = rs.Q; a.K = rs.K;
         a.pcm = c.bf.pcm_rs; a.wave_out = c.bf.wave_out;
         resample_pcm(a, nw, max_out, stream);
+    }
+    if (c.bf.wave_eq) {
+        // the equaliser on every utterance of the float signal at the output rate (two launches); loudness and the limiter read its output,
+        // and with neither downstream it writes the PCM
+        EqArgs a{};
+        signal(a);
+        a.S = eq_n; a.tab = d_eq_;
+        a.y = c.bf.wave_eq; a.pcm = lim_mode == 0 && loud_mode != 2 ? c.bf.pcm : nullptr;
+        eq_ws_carve(a, c.bf.eqws, nw, c.Ocap);
+        eq_run(a, nw, max_out, stream);
+        sig = c.bf.wave_eq;
     }
     const float* gloud = nullptr;
     if (loud_mode != 0 && !c.ss) {
@@ -539,12 +551,13 @@ int Engine::decode_end(RunCtx& c, const float* wave, const WinGeom& win, long Wt
         tap("wave", raw, 1, Wtot * hop, (wlen0 >= 0 ? (long)wlen0 : Wtot) * hop);
         if (c.gain && !c.ss) tap("wave_gain", c.bf.wave_gain, 1, Wtot * hop, (wlen0 >= 0 ? (long)wlen0 : Wtot) * hop);
         if (c.join) tap("wave_join", c.bf.wave_join, 1, (long)(c.FJ * hop), (long)(c.FJ * hop));
-        if ((c.bf.wave_out || c.bf.wave_lim) && !c.ss) {    // (a stream has moved the pinned block p_lenF points into: not read then)
+        if ((c.bf.wave_out || c.bf.wave_lim || c.bf.wave_eq) && !c.ss) {    // (a stream has moved the pinned block p_lenF points into: not read then)
             long long n = 0;        // samples at the output rate: what both taps hold
             if (c.join) n = out_count(c.FJ * hop);
             else if (wlen0 >= 0) n = out_count((long long)wlen0 * hop);
             else for (int b = 0; b < c.B; b++) n += out_count((long long)c.p_lenF[b] * hop);
             if (c.bf.wave_out) tap("wave_out", c.bf.wave_out, 1, (long)c.Ocap, (long)n);
+            if (c.bf.wave_eq) tap("wave_eq", c.bf.wave_eq, 1, (long)c.Ocap, (long)n);
             if (c.bf.wave_lim) tap("wave_lim", c.bf.wave_lim, 1, (long)c.Ocap, (long)n);
         }
     }

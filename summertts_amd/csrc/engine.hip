@@ -28,6 +28,7 @@ Engine::~Engine() {
     if (d_rs_table) (void)hipFree(d_rs_table);
     if (loud_host_) (void)hipHostFree(loud_host_);
     if (lim_host_) (void)hipHostFree(lim_host_);
+    if (d_eq_) (void)hipFree(d_eq_);
     if (ovf_host_) (void)hipHostFree(ovf_host_);
     if (hmap_) (void)hipHostFree(hmap_);
     if (arrive_) (void)hipFree(arrive_);
@@ -369,6 +370,30 @@ int Engine::set_limiter(int mode, float gain_db, float ceiling_dbfs, float looka
     if (!limiter_args_valid(mode, gain_db, ceiling_dbfs, lookahead_ms))
         return fail(STS_EINVAL, "limiter: mode 0 (off) or 1 (on), gain in [-40, 40] dB, ceiling in [-30, 0] dBFS, look-ahead in [0.25, 10] ms");
     lim_mode = mode; lim_gain_db = gain_db; lim_ceiling = ceiling_dbfs; lim_ms = lookahead_ms;
+    return STS_OK;
+}
+// sts_set_eq: persists; checked against the current output rate; an invalid argument changes nothing
+int Engine::set_eq(int n_bands, const sts_eq_band* bands) {
+    const char* why = nullptr;
+    if (!eq_valid(out_rate, n_bands, bands, &why)) return fail(STS_EINVAL, why);
+    eq_n = n_bands;
+    for (int i = 0; i < n_bands; i++) eq_bands[i] = bands[i];
+    eq_dirty_ = true;
+    return STS_OK;
+}
+// a run with an EQ, before anything is enqueued: the bands must fit the rate of THIS run; new bands or a new rate: tables to the device
+int Engine::eq_prepare() {
+    const char* why = nullptr;
+    if (!eq_valid(out_rate, eq_n, eq_bands, &why)) return fail(STS_EINVAL, std::string(why) + " -- the equaliser no longer fits the output rate (sts_set_eq again)");
+    if (!eq_dirty_ && eq_tab_rate_ == out_rate && d_eq_) return STS_OK;
+    double coef[5 * STS_EQ_MAX_BANDS];
+    eq_design(out_rate, eq_n, eq_bands, coef);
+    EqTable t;
+    eq_table(eq_n, coef, &t);
+    if (stream) HIPCK(hipStreamSynchronize(stream));      // (no earlier run still reads the old tables)
+    if (!d_eq_) HIPCK(hipMalloc((void**)&d_eq_, sizeof(EqTable)));
+    HIPCK(hipMemcpy(d_eq_, &t, sizeof(EqTable), hipMemcpyHostToDevice));
+    eq_dirty_ = false; eq_tab_rate_ = out_rate;
     return STS_OK;
 }
 // sts_set_duration_plan: copied and validated here; an invalid plan changes nothing.  B == 0 or plans == null drops a pending plan.
@@ -1036,7 +1061,8 @@ int Engine::run_frame_workspace(RunCtx& c) {
     c.use_ff = use_ff; c.ffG = use_ff ? M.cp[0].ff.G : 0;
     BufF& bf = c.bf;
     const bool loud = loud_mode != 0 && !ss, lim = lim_mode != 0;      // (a streaming call limits chunk by chunk: the same buffers per window)
-    const bool norm = (loud && loud_mode == 2) || lim;        // the gain cast or the limiter writes the PCM
+    const bool eq = eq_n > 0 && !ss;                          // (streaming calls are refused while an EQ is set)
+    const bool norm = (loud && loud_mode == 2) || lim || eq;  // the gain cast, the limiter or the EQ kernel writes the PCM
     auto layoutF = [&](Arena& A) {
         A.used = 0;
         for (int q = 0; q < 2; q++) {
@@ -1060,16 +1086,19 @@ int Engine::run_frame_workspace(RunCtx& c) {
         // and, with nothing downstream, bf.pcm)
         // (a joined run: again the tail writes the float wave and its int16 samples go to scratch; the join kernel writes the joined wave
         // and, with nothing downstream, bf.pcm; everything behind it is sized for the one joined utterance: c.Ocap)
-        bf.wave = A.get<float>(record_taps || resampling() || loud || lim || c.gain || c.join ? (size_t)Wcap * hop : 1);
+        // (an equaliser: the same once more; the EQ kernels write its float output and, with nothing downstream, bf.pcm)
+        bf.wave = A.get<float>(record_taps || resampling() || loud || lim || eq || c.gain || c.join ? (size_t)Wcap * hop : 1);
         bf.wave_gain = c.gain ? A.get<float>((size_t)Wcap * hop) : nullptr;
         bf.wave_join = c.join ? A.get<float>((size_t)(c.FJ * hop)) : nullptr;
         bf.pcm = A.get<int16_t>((size_t)c.Ocap);
         bf.pcm_nat = resampling() || norm || c.gain || c.join ? A.get<int16_t>((size_t)Wcap * hop) : bf.pcm;
-        bf.wave_out = (record_taps || loud || lim) && resampling() ? A.get<float>((size_t)c.Ocap) : nullptr;
+        bf.wave_out = (record_taps || loud || lim || eq) && resampling() ? A.get<float>((size_t)c.Ocap) : nullptr;
         bf.pcm_rs = norm && resampling() ? A.get<int16_t>((size_t)c.Ocap) : bf.pcm;
         bf.lws = loud ? A.get<char>(loud_ws_bytes(B, c.Ocap)) : nullptr;
         bf.limws = lim && !ss ? A.get<char>((size_t)B * 16) : nullptr;
         bf.wave_lim = lim && !ss && record_taps ? A.get<float>((size_t)c.Ocap) : nullptr;
+        bf.wave_eq = eq ? A.get<float>((size_t)c.Ocap) : nullptr;
+        bf.eqws = eq ? A.get<char>(eq_ws_bytes(B, c.Ocap)) : nullptr;
         bf.stab = nullptr; bf.spack = nullptr; bf.gwin = bf.cond_win = nullptr;
         if (ss) {
             bf.stab = A.get<char>(stream_tab_bytes(B, c.gain));
@@ -1303,6 +1332,10 @@ int Engine::run_once(int B, const int32_t* const* ids, const int32_t* n, const i
     if (ss && loud_mode != 0)
         return fail(STS_EINVAL, "streaming is not available while loudness measurement or normalization is on (sts_set_loudness mode 0 first): "
                                 "normalizing needs the whole utterance before its first sample leaves");
+    if (ss && eq_n > 0)
+        return fail(STS_EINVAL, "streaming is not available while an equaliser is set (sts_set_eq with 0 bands first): an IIR has no finite "
+                                "halo, and a state carried from chunk to chunk would make the PCM depend on the chunking");
+    if (eq_n > 0) { const int rce = eq_prepare(); if (rce != STS_OK) return rce; }
     host_t0_ = now_us(); host_t_sync_ = 0;
     RunCtx c;
     c.B = B; c.ids = ids; c.n = n; c.sid = sid; c.ls = ls; c.ss = ss; c.bstream = ss && B > 1;

@@ -242,6 +242,15 @@ private:
     double bytes_[4] = {0, 0, 0, 0};
     double bytes_w_[4] = {0, 0, 0, 0};       // the weight share of bytes_ (does not scale with the positions)
     double mfma_flops_ = 0, mfma_exec_ = 0, bf16_exec_ = 0, sync_wait_ms_ = 0; int mfma_launches_ = 0; bool in_mfma_region_ = false;
+    // (the members of the equaliser sit behind everything else: the layout of the members above stays what it was)
+    EqTable* d_eq_ = nullptr; int eq_tab_rate_ = 0; bool eq_dirty_ = true;        // the EQ's tables on the device, the rate they were built for
+    int eq_prepare();                                                             // a run with an EQ: the bands against the current rate, the tables
+public:
+    // parametric equaliser (sts_set_eq, eq.hip): eq_n bands, 0 = off (nothing extra runs).  Every whole-utterance call filters the float
+    // wave at the output rate in front of loudness and the limiter; with neither downstream the EQ kernel writes the PCM.  The device
+    // tables are built and uploaded by the first run after a change of the bands or the output rate (eq_prepare), not per call
+    int eq_n = 0; sts_eq_band eq_bands[STS_EQ_MAX_BANDS] = {};
+    int set_eq(int n_bands, const sts_eq_band* bands);
 };
 
 }  // namespace sts

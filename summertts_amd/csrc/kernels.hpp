@@ -497,4 +497,27 @@ struct JoinArgs {
 // one launch: ceil(NJ / span) workgroups, each owning a contiguous span of J (silence included: no memset)
 void join_run(const JoinArgs& a, hipStream_t st);
 
+// Parametric equaliser (eq.hip; the definition is there and in include/summertts_hip.h sts_set_eq)
+constexpr int kEqMinRate = 8000, kEqMaxRate = 48000, kEqMaxBands = STS_EQ_MAX_BANDS, kEqDim = 2 * kEqMaxBands, kEqPow = 9;
+// the validity rules at an output rate (n_bands 0 is valid: the stage is off); why: the refusal's text, or null
+bool eq_valid(int rate, int n_bands, const sts_eq_band* bands, const char** why);
+// {b0, b1, b2, a1, a2} of every band, normalised by a0, float64 (bands eq_valid accepted)
+void eq_design(int rate, int n_bands, const sts_eq_band* bands, double* coeffs);
+// what the kernels read from device memory: the coefficients, and Mp[d] = M^(2^d) for the chunk map M = A^32 of the cascade's state
+// (per section: last output, last output - the one before), row-major with stride kEqDim
+struct EqTable { double c[kEqMaxBands][5]; double Mp[kEqPow][kEqDim * kEqDim]; };
+void eq_table(int S, const double* coeffs, EqTable* t);
+struct EqArgs {
+    const float* x;                      // the float signal, utterances packed back to back
+    const int* len; int ilen, scale, P, Q;   // utterance b has ceil(len[b] scale P / Q) samples (len == null: one utterance, ilen)
+    int S; const EqTable* tab;           // sections (1 .. 4) and their tables (device memory)
+    float* y; int16_t* pcm;              // outputs packed like x, each optional (not x)
+    long long* utab; double* E;          // workspace (eq_ws_carve)
+};
+// workspace of B utterances of total_samples samples in all (the frame-level arena's dry run sizes it)
+size_t eq_ws_bytes(int B, long long total_samples);
+void eq_ws_carve(EqArgs& a, void* ws, int B, long long total_samples);
+// 2 launches; max_len = the longest utterance's sample count or more
+void eq_run(const EqArgs& a, int B, long long max_len, hipStream_t st);
+
 }  // namespace sts

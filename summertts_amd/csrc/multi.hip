@@ -437,6 +437,17 @@ int sts_multi_set_limiter(sts_multi* m, int mode, float gain_db, float ceiling_d
     }
     return STS_OK;
 }
+int sts_multi_set_eq(sts_multi* m, int32_t n_bands, const sts_eq_band* bands) {
+    if (!m) return multi_err(STS_EINVAL, "null handle");
+    const char* why = nullptr;
+    for (auto& e : m->engines)          // (all or none)
+        if (!eq_valid(e->out_rate, n_bands, bands, &why)) return multi_err(STS_EINVAL, why);
+    for (auto& e : m->engines) {
+        const int rc = e->set_eq(n_bands, bands);
+        if (rc != STS_OK) return multi_err(rc, e->error());
+    }
+    return STS_OK;
+}
 int sts_multi_set_duration_plan(sts_multi* m, int32_t B, const int32_t* n, const sts_dur_plan* plans) {
     if (!m) return multi_err(STS_EINVAL, "null handle");
     if (B == 0 || !plans) { m->have_plan = false; return STS_OK; }

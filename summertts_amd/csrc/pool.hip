@@ -55,6 +55,7 @@ struct sts_pool {
     int64_t next_ticket = 1;
     int max_batch = 8;
     int loud_mode = 0;                 // sts_pool_set_loudness (streaming requests are refused while it is 2)
+    int eq_bands = 0;                  // sts_pool_set_eq (streaming requests are refused while it is not 0)
     bool stop = false;
     int64_t batches = 0, requests = 0;
 
@@ -384,6 +385,7 @@ int64_t sts_pool_submit_stream(sts_pool* p, const int32_t* ids, int32_t n, int32
         std::lock_guard<std::mutex> lk(p->mu);
         if (p->stop) return pool_err(STS_ESTATE, "pool is shutting down");
         if (p->loud_mode != 0) return pool_err(STS_EINVAL, "streaming requests are refused while the pool normalizes loudness (sts_pool_set_loudness mode 0 first)");
+        if (p->eq_bands != 0) return pool_err(STS_EINVAL, "streaming requests are refused while the pool has an equaliser set (sts_pool_set_eq with 0 bands first): an IIR has no finite halo");
         r->ticket = p->next_ticket++;
         p->queue.push_back(r);
         p->pending[r->ticket] = r;
@@ -448,6 +450,21 @@ int sts_pool_set_limiter(sts_pool* p, int mode, float gain_db, float ceiling_dbf
         const int rc = e->set_limiter(mode, gain_db, ceiling_dbfs, lookahead_ms);
         if (rc != STS_OK) return pool_err(rc, e->error());
     }
+    return STS_OK;
+}
+
+int sts_pool_set_eq(sts_pool* p, int32_t n_bands, const sts_eq_band* bands) {
+    if (!p) return pool_err(STS_EINVAL, "null pool");
+    std::lock_guard<std::mutex> lk(p->mu);
+    if (!p->pending.empty()) return pool_err(STS_ESTATE, "requests are outstanding: wait for them before changing the equaliser");
+    const char* why = nullptr;
+    for (auto& e : p->engines)          // (all or none: every engine runs at the same rate)
+        if (!eq_valid(e->out_rate, n_bands, bands, &why)) return pool_err(STS_EINVAL, why);
+    for (auto& e : p->engines) {
+        const int rc = e->set_eq(n_bands, bands);
+        if (rc != STS_OK) return pool_err(rc, e->error());
+    }
+    p->eq_bands = n_bands;
     return STS_OK;
 }
 

@@ -44,6 +44,9 @@ struct BufF {
     // streaming only (null otherwise): the step tables (stream_tab_bytes); several utterances: the packed chunk buffer stream_pack writes
     // (native rate, no limiter), the per-window speaker vectors and decoder conditioning of a multi-speaker HiFi-GAN decoder
     char* stab; int16_t* spack; float *gwin, *cond_win;
+    // a run with an equaliser only (null otherwise): its float output at the output rate, laid out like wave_out (what loudness and the
+    // limiter then read), and the scan's workspace
+    float* wave_eq; char* eqws;
 };
 // Streaming, the tables of one step with nw windows (one upload, c.d_win points at them): ints [zoff nw | coff nw | wlen nw | sid nw |
 // pack source nw | packed destination nw + 1], then from an 8-byte boundary the resampler's long long [nw][5] = {u0, L_utt, j0, j1, obase}

@@ -157,6 +157,29 @@ def _join(B: int, join):
     return C.pointer(j), (j, g)
 
 
+class EqBand(C.Structure):
+    """``sts_eq_band``: one section of the parametric equaliser (include/summertts_hip.h sts_set_eq)."""
+    _fields_ = [("type", C.c_int32), ("freq_hz", C.c_float), ("gain_db", C.c_float), ("q", C.c_float)]
+
+
+EQ_MAX_BANDS = 4
+EQ_PEAK, EQ_LOWSHELF, EQ_HIGHSHELF, EQ_HIGHPASS, EQ_LOWPASS = 1, 2, 3, 4, 5
+
+
+def _eq_bands(bands):
+    """-> (n, ctypes array of EqBand or None).  ``bands``: None / empty (the stage off) or a sequence of ``(type, freq_hz, gain_db, q)``
+    tuples or mappings with those keys (``gain_db`` defaults to 0, ``q`` to 1 / sqrt(2))."""
+    bands = list(bands) if bands is not None else []
+    if not bands:
+        return 0, None
+    arr = (EqBand * len(bands))()
+    for i, b in enumerate(bands):
+        if isinstance(b, dict):
+            b = (b["type"], b["freq_hz"], b.get("gain_db", 0.0), b.get("q", 0.7071067811865476))
+        arr[i].type, arr[i].freq_hz, arr[i].gain_db, arr[i].q = int(b[0]), float(b[1]), float(b[2]), float(b[3])
+    return len(bands), arr
+
+
 class PreparedBatch:
     """run_batch's argument arrays, built once (Synthesizer.prepare)."""
 
@@ -273,6 +296,13 @@ def load_library() -> C.CDLL:
     lib.sts_pool_submit_joined.restype = C.c_int64
     lib.sts_pool_submit_joined.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_float,
                                            C.c_uint64, C.c_void_p]
+    lib.sts_set_eq.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
+    lib.sts_get_eq.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.c_void_p, C.c_int32]
+    lib.sts_eq_check.argtypes = [C.c_int32, C.c_int32, C.c_void_p]
+    lib.sts_eq_design.argtypes = [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
+    lib.sts_eq_apply.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.sts_pool_set_eq.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
+    lib.sts_multi_set_eq.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
     lib.sts_infer_ids_batch_stream.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
                                                BATCH_CHUNK_CB, C.c_void_p, C.c_void_p]
     lib.sts_pool_submit_stream.restype = C.c_int64
@@ -311,6 +341,7 @@ EXPORTED_SYMBOLS = [
     "sts_multi_set_gain_plan",
     "sts_debug_spline_step",
     "sts_join_check", "sts_join_layout", "sts_join_apply", "sts_infer_ids_joined", "sts_get_join_offsets", "sts_pool_submit_joined",
+    "sts_set_eq", "sts_get_eq", "sts_eq_check", "sts_eq_design", "sts_eq_apply", "sts_pool_set_eq", "sts_multi_set_eq",
 ]
 
 
@@ -546,6 +577,42 @@ def limiter_apply(signals, rate: int, gain_db: float = 0.0, ceiling_dbfs: float 
                                       float(lookahead_ms), y.ctypes.data, pcm.ctypes.data, stats.ctypes.data))
     off = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
     return ([y[off[b]:off[b + 1]].copy() for b in range(len(sig))], [pcm[off[b]:off[b + 1]].copy() for b in range(len(sig))], stats)
+
+
+def eq_check(rate: int, bands) -> None:
+    """The validity rules of the equaliser at output rate ``rate`` (include/summertts_hip.h sts_eq_check; host only, no GPU); raises
+    StsError with the reason."""
+    lib = load_library()
+    n, arr = _eq_bands(bands)
+    _check(lib, lib.sts_eq_check(int(rate), n, arr))
+
+
+def eq_design(rate: int, bands) -> np.ndarray:
+    """The library's biquad coefficients of ``bands`` at ``rate`` (sts_eq_design; host only, no GPU) -> float64 [n][5],
+    {b0, b1, b2, a1, a2} per band."""
+    lib = load_library()
+    n, arr = _eq_bands(bands)
+    c = np.zeros((n, 5), np.float64)
+    _check(lib, lib.sts_eq_design(int(rate), n, arr, c.ctypes.data))
+    return c
+
+
+def eq_apply(signals, rate: int, bands, device: int = 0, want_y: bool = True, want_pcm: bool = True):
+    """The equaliser on each float signal in ``signals`` at ``rate`` on the GPU (the engine's kernels, sts_eq_apply) -> (y, pcm): lists of
+    the float32 outputs and their int16 casts.  An output that is not wanted is not computed; its list then holds the sentinel the
+    caller's buffer started with (NaN / 0x7FFF)."""
+    lib = load_library()
+    n, arr = _eq_bands(bands)
+    sig = [np.ascontiguousarray(s, dtype=np.float32).ravel() for s in signals]
+    lens = np.asarray([s.size for s in sig], np.int64)
+    total = int(lens.sum())
+    x = np.concatenate(sig) if sig and total > 0 else np.zeros(1, np.float32)
+    y = np.full(max(total, 1), np.nan, np.float32)
+    pcm = np.full(max(total, 1), 0x7FFF, np.int16)
+    _check(lib, lib.sts_eq_apply(int(device), x.ctypes.data, lens.ctypes.data, len(sig), int(rate), n, arr,
+                                 y.ctypes.data if want_y else None, pcm.ctypes.data if want_pcm else None))
+    off = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
+    return [y[off[b]:off[b + 1]].copy() for b in range(len(sig))], [pcm[off[b]:off[b + 1]].copy() for b in range(len(sig))]
 
 
 def resample_table(in_rate: int, out_rate: int):
@@ -828,6 +895,21 @@ class Synthesizer:
         LIMITER_ON (make-up gain ``gain_db``, then no sample above ``ceiling_dbfs``; results in ``limiter()``).  Invalid arguments raise
         and leave the setting unchanged."""
         _check(self.lib, self.lib.sts_set_limiter(self.h, int(mode), float(gain_db), float(ceiling_dbfs), float(lookahead_ms)))
+
+    def set_eq(self, bands=None):
+        """Parametric equaliser of every later whole-utterance call (include/summertts_hip.h sts_set_eq): up to 4 bands
+        ``(type, freq_hz, gain_db, q)`` (EQ_PEAK, EQ_LOWSHELF, EQ_HIGHSHELF, EQ_HIGHPASS, EQ_LOWPASS) in front of loudness and the
+        limiter; None or an empty list switches it off.  Invalid bands raise and change nothing; streaming calls are refused while
+        bands are set."""
+        n, arr = _eq_bands(bands)
+        _check(self.lib, self.lib.sts_set_eq(self.h, n, arr))
+
+    def get_eq(self):
+        """The bands set by ``set_eq``: a list of ``(type, freq_hz, gain_db, q)``."""
+        n = C.c_int32()
+        arr = (EqBand * EQ_MAX_BANDS)()
+        _check(self.lib, self.lib.sts_get_eq(self.h, C.byref(n), arr, EQ_MAX_BANDS))
+        return [(int(arr[i].type), float(arr[i].freq_hz), float(arr[i].gain_db), float(arr[i].q)) for i in range(n.value)]
 
     def limiter_mode(self):
         """(mode, gain_db, ceiling_dbfs, lookahead_ms) as set by ``set_limiter``."""
@@ -1138,6 +1220,14 @@ class Pool:
         if rc != 0:
             raise StsError(f"sts_pool_set_limiter: {rc}: {self.lib.sts_pool_last_error().decode()}")
 
+    def set_eq(self, bands=None):
+        """``Synthesizer.set_eq`` for every engine of the pool (one setting for every request); raises while any request is outstanding
+        (STS_ESTATE).  Streamed requests are refused while bands are set."""
+        n, arr = _eq_bands(bands)
+        rc = self.lib.sts_pool_set_eq(self.h, n, arr)
+        if rc != 0:
+            raise StsError(f"sts_pool_set_eq: {rc}: {self.lib.sts_pool_last_error().decode()}")
+
     def stats(self):
         b, r = C.c_int64(), C.c_int64()
         self.lib.sts_pool_stats(self.h, C.byref(b), C.byref(r))
@@ -1228,6 +1318,13 @@ class MultiDevice:
         rc = self.lib.sts_multi_set_limiter(self.h, int(mode), float(gain_db), float(ceiling_dbfs), float(lookahead_ms))
         if rc != 0:
             raise StsError(f"sts_multi_set_limiter: {rc}: {self.lib.sts_multi_last_error().decode()}")
+
+    def set_eq(self, bands=None):
+        """``Synthesizer.set_eq`` for every device."""
+        n, arr = _eq_bands(bands)
+        rc = self.lib.sts_multi_set_eq(self.h, n, arr)
+        if rc != 0:
+            raise StsError(f"sts_multi_set_eq: {rc}: {self.lib.sts_multi_last_error().decode()}")
 
     def set_duration_plan(self, n: Optional[Sequence[int]], plans=None):
         """``Synthesizer.set_duration_plan`` for the next ``infer_batch``: ``plans[b]`` belongs to utterance b of that batch, whatever its
