@@ -571,7 +571,7 @@ int sts_set_profiling(sts_engine* e, int enable);
  * sizeof(sts_profile)) bytes, so a client compiled against an older header passes ITS sizeof and is never overrun;
  * sts_get_profile(e, p) == sts_get_profile_ex(e, p, sizeof(sts_profile)) of the header this library was built from -- use it only
  * when client and library are built together. */
-#define STS_ABI_VERSION 15
+#define STS_ABI_VERSION 16
 int sts_abi_version(void);
 /* bit 0: lab build (-DSTS_EXPERIMENTS: environment knobs of knobs.hpp, every conv tile code);
  * 0 for the shipped library */
@@ -631,6 +631,29 @@ int sts_debug_conv_h2w(int device, const float* x, int32_t C, int32_t L, const f
  * as the kernel allows.  o0 / o1 receive n floats each.  On the device every output row is followed by a guard that covers the rest of the
  * launch's last workgroup and 128 positions more; a guard word the kernel changed is STS_EDEVICE.  1 <= n <= 2^24. */
 int sts_debug_spline_step(int device, const float* h, int64_t n, float filter_sqrt, const float* r0, const float* r1, float* o0, float* o1);
+
+/* sts_debug_attention (ABI 16): the text encoder's windowed relative-position attention on caller data, between the q / k / v convs and the
+ * output conv.  q, k, v: [nheads * kc][L], L = sum(lengths), B utterances packed back to back as the engine packs them (every lengths[b]
+ * >= 1).  relk / relv: [kc][2 win + 1], null exactly when win = 0.  nheads is free here (the engine pins 2).
+ * variant: 0 = the kernel the engine's dispatcher picks for this shape with the engine's defaults; 1 = attention_kernel (generic, any shape
+ * whose LDS row fits the device); 2 = attention_reg_kernel (kc <= 96, 2 win + 1 <= 16, longest utterance <= 256); 3 = attention_mfma_kernel
+ * (kc % 16 == 0, kc <= 128, 2 win + 1 <= 32, LDS <= 150 KiB).  A forced variant whose limits the shape does not meet, or a shape no kernel
+ * admits, is STS_EINVAL and nothing is launched.
+ * o: [o_rows][L] floats, o_rows >= nheads * kc.  The device buffers have exactly these sizes; the output starts out as the word 0xFFFFFFFF
+ * everywhere and all of it is copied back, so an element no workgroup wrote -- and a row past nheads * kc that one did -- shows.
+ * *variant_out (optional): the kernel launched (1 | 2 | 3); *jpl_out (optional): keys per lane of the register kernel (2 | 4), else 0. */
+int sts_debug_attention(int device, const float* q, const float* k, const float* v, const float* relk, const float* relv, int32_t nheads,
+                        int32_t kc, int32_t win, const int32_t* lengths, int32_t B, int variant, float* o, int32_t o_rows,
+                        int32_t* variant_out, int32_t* jpl_out);
+
+/* sts_debug_layer_norm (ABI 16): the text encoder's / duration predictors' LayerNorm launch on caller data, all of its fused forms:
+ *   v = [depthwise conv of] a (+ b_0 + ... + b_{nb-1}) ; relu(v) if pre_relu ; y = LN_C(v) * gamma + beta ; gelu(y) if post_gelu ; res + y.
+ * a, res (optional), y: [C][L] (y: [y_rows][L], y_rows >= C), L = sum(lengths) as above.  b: nb in 0..8 partials [C][L], b_stride floats
+ * apart (>= C L; read only when nb > 1), null exactly when nb = 0.  dw_w (optional) [k][C] with dw_b (optional) [C]: tap j reads position
+ * pos + j dil - pad of the SAME utterance, zero outside it.  The output starts out as the word 0xFFFFFFFF and is copied back whole. */
+int sts_debug_layer_norm(int device, const float* a, const float* b, int32_t nb, int64_t b_stride, const float* res, const float* gamma,
+                         const float* beta, int32_t C, int32_t pre_relu, int32_t post_gelu, const float* dw_w, const float* dw_b, int32_t dw_k,
+                         int32_t dw_dil, int32_t dw_pad, const int32_t* lengths, int32_t B, float* y, int32_t y_rows);
 
 void sts_free(void* p);
 const char* sts_last_error(void);

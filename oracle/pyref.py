@@ -147,6 +147,61 @@ class _Model:
             pass
 
 
+_port_lib = None
+
+
+def _port():
+    global _port_lib
+    if _port_lib is None:
+        if not have_port():
+            build(port=True, ref=False)
+        lib = C.CDLL(PORT_SO)
+        lib.port_attention.restype = None
+        lib.port_attention.argtypes = [C.c_void_p] * 5 + [C.c_int32] * 4 + [C.c_void_p]
+        lib.port_layer_norm.restype = None
+        lib.port_layer_norm.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32]
+        _port_lib = lib
+    return _port_lib
+
+
+def port_attention(q, k, v, relk, relv, nheads: int, win: int, lengths) -> np.ndarray:
+    """The oracle's attention loop (vits_oracle.c attention_core, what mha_forward runs between its convs) on a packed batch: q, k, v
+    float32 [nheads * kc][sum(lengths)], relk / relv [kc][2 win + 1] or None with win = 0 -> float32, every utterance on its own."""
+    lib = _port()
+    q = np.ascontiguousarray(q, dtype=np.float32)
+    k = np.ascontiguousarray(k, dtype=np.float32)
+    v = np.ascontiguousarray(v, dtype=np.float32)
+    rows = q.shape[0]
+    kc = rows // nheads
+    assert rows == nheads * kc and k.shape == q.shape and v.shape == q.shape and int(np.sum(lengths)) == q.shape[1]
+    if win > 0:
+        relk = np.ascontiguousarray(relk, dtype=np.float32)
+        relv = np.ascontiguousarray(relv, dtype=np.float32)
+        assert relk.shape == (kc, 2 * win + 1) and relv.shape == relk.shape
+    out = np.zeros(q.shape, np.float32)
+    off = 0
+    for n in lengths:
+        n = int(n)
+        part = [np.ascontiguousarray(x[:, off:off + n]) for x in (q, k, v)]
+        o = np.zeros((rows, n), np.float32)
+        lib.port_attention(part[0].ctypes.data, part[1].ctypes.data, part[2].ctypes.data, relk.ctypes.data if win > 0 else None,
+                           relv.ctypes.data if win > 0 else None, nheads, kc, win, n, o.ctypes.data)
+        out[:, off:off + n] = o
+        off += n
+    return out
+
+
+def port_layer_norm(x, gamma, beta, post_gelu: bool = False) -> np.ndarray:
+    """The oracle's LayerNorm over channels (vits_oracle.c layer_norm, then act_gelu when asked) of x float32 [C][T] -> float32 [C][T]."""
+    lib = _port()
+    y = np.array(x, dtype=np.float32, order="C", copy=True)
+    g = np.ascontiguousarray(gamma, dtype=np.float32)
+    b = np.ascontiguousarray(beta, dtype=np.float32)
+    assert y.ndim == 2 and g.shape == (y.shape[0],) and b.shape == g.shape
+    lib.port_layer_norm(y.ctypes.data, y.shape[0], y.shape[1], g.ctypes.data, b.ctypes.data, 1 if post_gelu else 0)
+    return y
+
+
 class RefModel(_Model):
     """The real reference (Eigen CPU) acoustic path."""
 

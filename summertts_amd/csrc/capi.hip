@@ -474,6 +474,120 @@ int sts_debug_spline_step(int device, const float* h, int64_t n, float filter_sq
     return STS_OK;
 }
 
+namespace {
+// Exact-size device buffers of the kernel-level text-encoder entries: one allocation per tensor, freed on every return path.
+struct DebugBufs {
+    std::vector<void*> ptrs; hipStream_t st = nullptr; bool ok = true;
+    DebugBufs() { ok = hipStreamCreate(&st) == hipSuccess; }
+    ~DebugBufs() { if (st) (void)hipStreamDestroy(st); for (void* p : ptrs) (void)hipFree(p); }
+    void* raw(size_t bytes) {
+        void* d = nullptr;
+        if (ok && hipMalloc(&d, bytes ? bytes : 4) == hipSuccess) { ptrs.push_back(d); return d; }
+        ok = false; return nullptr;
+    }
+    const void* up4(const void* host, size_t words) {                   // null stays null
+        if (!host) return nullptr;
+        void* d = raw(words * 4);
+        ok = ok && hipMemcpyAsync(d, host, words * 4, hipMemcpyHostToDevice, st) == hipSuccess;
+        return d;
+    }
+    const float* up(const float* host, size_t count) { return (const float*)up4(host, count); }
+    const int* up(const int* host, size_t count) { return (const int*)up4(host, count); }
+    float* out(size_t count) {                                          // starts out as the sentinel 0xFFFFFFFF (a NaN)
+        float* d = (float*)raw(count * 4);
+        ok = ok && hipMemsetAsync(d, 0xFF, count * 4, st) == hipSuccess;
+        return d;
+    }
+};
+// lengths[B] -> device table [offsets | lengths]; returns L = sum(lengths) or -1
+long debug_segments(const int32_t* lengths, int32_t B, std::vector<int>& tab, int* max_len) {
+    if (!lengths || B < 1 || B > 65535) return -1;
+    tab.assign(2 * (size_t)B, 0);
+    long L = 0; *max_len = 0;
+    for (int b = 0; b < B; b++) {
+        if (lengths[b] < 1 || L + lengths[b] > (1 << 24)) return -1;
+        tab[b] = (int)L; tab[B + b] = lengths[b]; L += lengths[b];
+        if (lengths[b] > *max_len) *max_len = lengths[b];
+    }
+    return L;
+}
+}  // namespace
+
+int sts_debug_attention(int device, const float* q, const float* k, const float* v, const float* relk, const float* relv, int32_t nheads,
+                        int32_t kc, int32_t win, const int32_t* lengths, int32_t B, int variant, float* o, int32_t o_rows,
+                        int32_t* variant_out, int32_t* jpl_out) {
+    if (variant_out) *variant_out = 0;
+    if (jpl_out) *jpl_out = 0;
+    if (!q || !k || !v || !o) return set_err(STS_EINVAL, "q, k, v and o are required");
+    if (nheads < 1 || nheads > 65535 || kc < 1 || kc > 4096 || win < 0 || win > 4096) return set_err(STS_EINVAL, "1 <= nheads <= 65535, 1 <= kc <= 4096, 0 <= win <= 4096");
+    if ((win > 0) != (relk != nullptr) || (win > 0) != (relv != nullptr)) return set_err(STS_EINVAL, "relk and relv [kc][2 win + 1] go with win > 0, null with win = 0");
+    if (variant < 0 || variant > 3) return set_err(STS_EINVAL, "variant: 0 = the engine's choice, 1 = generic, 2 = register, 3 = matrix-core");
+    const long rows = (long)nheads * kc;
+    if (o_rows < rows) return set_err(STS_EINVAL, "o holds at least nheads * kc rows");
+    std::vector<int> tab; int max_len = 0;
+    const long L = debug_segments(lengths, B, tab, &max_len);
+    if (L < 0 || (double)o_rows * (double)L > (double)(1u << 30)) return set_err(STS_EINVAL, "lengths: B >= 1 entries, each >= 1, sum <= 2^24, o_rows * sum <= 2^30");
+    AttnArgs a;
+    memset(&a, 0, sizeof(a));
+    a.kc = kc; a.win = win; a.px = win > 0 ? 2 * win + 1 : 0; a.nheads = nheads; a.B = B; a.max_len = max_len; a.ld = L;
+    a.block_min_wgs = 0; a.attn_reg = 1;            // the engine's defaults (engine.hpp)
+    AttnPlan plan;
+    if (variant == 0) plan = attention_choose(a);
+    else attention_admits(a, variant, &plan);
+    if (plan.kernel == ATTN_NONE) return set_err(STS_EINVAL, variant == 0 ? "no attention kernel admits this shape (utterance too long for the attention kernel)" : "the shape is outside the forced kernel's limits");
+    if (hipSetDevice(device) != hipSuccess) return set_err(STS_EDEVICE, "no such device");
+    DebugBufs d;
+    a.q = d.up(q, (size_t)rows * L); a.k = d.up(k, (size_t)rows * L); a.v = d.up(v, (size_t)rows * L);
+    a.relk = d.up(relk, (size_t)kc * a.px); a.relv = d.up(relv, (size_t)kc * a.px);
+    const int* dt = d.up(tab.data(), tab.size());
+    a.o = d.out((size_t)o_rows * L);
+    a.seg = SegView{dt, dt + B, 1, 0, 0, 0};
+    if (d.ok) {
+        attention_launch(a, plan, d.st);
+        d.ok = hipGetLastError() == hipSuccess && hipMemcpyAsync(o, a.o, (size_t)o_rows * L * 4, hipMemcpyDeviceToHost, d.st) == hipSuccess &&
+               hipStreamSynchronize(d.st) == hipSuccess;
+    }
+    if (!d.ok) return set_err(STS_EDEVICE, "the attention launch failed on the device");
+    if (variant_out) *variant_out = plan.kernel;
+    if (jpl_out) *jpl_out = plan.jpl;
+    return STS_OK;
+}
+
+int sts_debug_layer_norm(int device, const float* a, const float* b, int32_t nb, int64_t b_stride, const float* res, const float* gamma,
+                         const float* beta, int32_t C, int32_t pre_relu, int32_t post_gelu, const float* dw_w, const float* dw_b, int32_t dw_k,
+                         int32_t dw_dil, int32_t dw_pad, const int32_t* lengths, int32_t B, float* y, int32_t y_rows) {
+    if (!a || !gamma || !beta || !y) return set_err(STS_EINVAL, "a, gamma, beta and y are required");
+    if (C < 1 || C > 65536 || y_rows < C) return set_err(STS_EINVAL, "1 <= C <= 65536 and y holds at least C rows");
+    std::vector<int> tab; int max_len = 0;
+    const long L = debug_segments(lengths, B, tab, &max_len);
+    if (L < 0 || (double)y_rows * (double)L > (double)(1u << 30)) return set_err(STS_EINVAL, "lengths: B >= 1 entries, each >= 1, sum <= 2^24, y_rows * sum <= 2^30");
+    if (nb < 0 || nb > 8 || (nb > 0) != (b != nullptr)) return set_err(STS_EINVAL, "0 <= nb <= 8 partials in b (null with nb = 0)");
+    if (nb > 1 && b_stride < (int64_t)C * L) return set_err(STS_EINVAL, "b_stride >= C * L floats between partials");
+    if (dw_w && (dw_k < 1 || dw_k > 64 || dw_dil < 1 || dw_dil > 4096 || dw_pad < 0 || dw_pad > (1 << 20))) return set_err(STS_EINVAL, "depthwise conv: 1 <= k <= 64, 1 <= dil <= 4096, 0 <= pad <= 2^20");
+    if (!dw_w && dw_b) return set_err(STS_EINVAL, "dw_b goes with dw_w");
+    if (hipSetDevice(device) != hipSuccess) return set_err(STS_EDEVICE, "no such device");
+    DebugBufs d;
+    LnArgs g;
+    memset(&g, 0, sizeof(g));
+    const size_t n = (size_t)C * L;
+    g.a = d.up(a, n); g.a_ld = L;
+    g.nb = nb; g.b_stride = nb > 1 ? (long)b_stride : 0; g.b_ld = L;
+    g.b = d.up(b, nb > 1 ? (size_t)(nb - 1) * (size_t)b_stride + n : n);
+    g.res = d.up(res, n); g.res_ld = L;
+    g.gamma = d.up(gamma, (size_t)C); g.beta = d.up(beta, (size_t)C);
+    g.C = C; g.pre_relu = pre_relu != 0; g.post_gelu = post_gelu != 0;
+    if (dw_w) { g.dw_w = d.up(dw_w, (size_t)dw_k * C); g.dw_b = d.up(dw_b, (size_t)C); g.dw_k = dw_k; g.dw_dil = dw_dil; g.dw_pad = dw_pad; g.dw_ld = C; }
+    const int* dt = d.up(tab.data(), tab.size());
+    g.y = d.out((size_t)y_rows * L); g.y_ld = L;
+    g.seg = SegView{dt, dt + B, 1, 0, 0, 0}; g.B = B; g.max_len = max_len;
+    if (d.ok) {
+        layer_norm(g, d.st);
+        d.ok = hipGetLastError() == hipSuccess && hipMemcpyAsync(y, g.y, (size_t)y_rows * L * 4, hipMemcpyDeviceToHost, d.st) == hipSuccess &&
+               hipStreamSynchronize(d.st) == hipSuccess;
+    }
+    return d.ok ? STS_OK : set_err(STS_EDEVICE, "the LayerNorm launch failed on the device");
+}
+
 int sts_set_noise(sts_engine* e, float noise_scale, float noise_scale_w, uint64_t seed) {
     if (!e) return set_err(STS_EINVAL, "null engine");
     if (!noise_scale_valid(noise_scale) || !noise_scale_valid(noise_scale_w)) return set_err(STS_EINVAL, "noise scales must be finite and >= 0");

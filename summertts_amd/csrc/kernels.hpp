@@ -295,7 +295,13 @@ void conv_generic(const ConvArgs& a, hipStream_t st);
 
 void embed(const int* ids, const float* emb, int vocab, int H, float scale, float* x, long ld, int total, hipStream_t st);
 void layer_norm(const LnArgs& a, hipStream_t st);
-void attention(const AttnArgs& a, hipStream_t st);
+// attention = "which kernel for these AttnArgs" (pure host predicates, the LDS-size tests included) + the launch
+enum AttnKernel : int { ATTN_NONE = 0, ATTN_GENERIC = 1, ATTN_REG = 2, ATTN_MFMA = 3 };
+struct AttnPlan { int kernel; int jpl; int Tpad; size_t lds; };      // jpl: keys per lane of attention_reg_kernel (2 | 4), 0 otherwise
+bool attention_admits(const AttnArgs& a, int kernel, AttnPlan* plan);      // do the kernel's shape limits (fixed-size arrays, LDS) hold?
+AttnPlan attention_choose(const AttnArgs& a);                       // the engine's choice (ATTN_NONE: no kernel admits the shape)
+void attention_launch(const AttnArgs& a, const AttnPlan& p, hipStream_t st);
+int attention(const AttnArgs& a, hipStream_t st);                   // launch(choose); returns the AttnKernel launched
 // y[c][seg b] += u[c*B + b]
 void add_ubias(float* y, long ld, const float* u, int C, SegView seg, int B, int max_len, hipStream_t st);
 void gather_speaker(const float* emb_g, int spk_num, int gin, const int* sid, int B, float* g, hipStream_t st);

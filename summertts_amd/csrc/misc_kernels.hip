@@ -553,33 +553,69 @@ static size_t attention_mfma_lds(const AttnArgs& a, int Tpad) {
     return ((size_t)a.kc * 16 + 16 * 32 + 64 + (size_t)Tpad * 16 + (vb > red ? vb : red)) * sizeof(float);
 }
 
-void attention(const AttnArgs& a, hipStream_t st) {
-    if (a.max_len <= 0 || a.B <= 0) return;
+// The shape limits of one kernel: its fixed-size arrays and its LDS footprint.  (Whether the engine PREFERS the kernel is
+// attention_choose's business.)
+constexpr size_t ATT_MFMA_MAX_LDS = 150 * 1024;     // the block kernel's budget
+constexpr size_t ATT_MAX_LDS = 160 * 1024;          // LDS of one gfx950 workgroup: the generic kernel's row must fit
+bool attention_admits(const AttnArgs& a, int kernel, AttnPlan* plan) {
+    AttnPlan p{ATTN_NONE, 0, 0, 0};
+    bool ok = a.max_len > 0 && a.B > 0 && a.kc > 0 && a.nheads > 0;
+    if (ok && kernel == ATTN_MFMA) {                // qv[8] / oacc[8]: kc <= 128 in tiles of 16; qrel[16][32]: px <= 32
+        p.Tpad = (a.max_len + 63) / 64 * 64;
+        p.lds = attention_mfma_lds(a, p.Tpad);
+        ok = a.kc % 16 == 0 && a.kc <= 128 && a.px <= 32 && p.lds <= ATT_MFMA_MAX_LDS;
+    } else if (ok && kernel == ATTN_REG) {          // 4 waves x ATR_CW channels; rv[16]: px <= 16; 64 JPL keys
+        p.jpl = a.max_len <= 128 ? 2 : 4;
+        p.lds = attention_reg_lds(p.jpl);
+        ok = a.kc <= 4 * ATR_CW && a.px <= 16 && a.max_len <= 256;
+    } else if (ok && kernel == ATTN_GENERIC) {
+        p.lds = (size_t)(a.kc + 8 + (a.px > 16 ? a.px : 16) + 5 * (size_t)a.max_len) * sizeof(float);
+        ok = p.lds <= ATT_MAX_LDS;
+    } else {
+        ok = false;
+    }
+    p.kernel = ok ? kernel : ATTN_NONE;
+    if (!ok) p.jpl = 0;
+    if (plan) *plan = p;
+    return ok;
+}
+
+AttnPlan attention_choose(const AttnArgs& a) {
+    AttnPlan p{ATTN_NONE, 0, 0, 0};
+    if (a.max_len <= 0 || a.B <= 0) return p;
     {   // matrix-core form: 16 queries per workgroup, whenever its LDS footprint fits and the model shape is covered
         static const bool no_mfma = exp_flag("STS_NO_ATTN_MFMA");   // experiment knob
-        const int Tpad = (a.max_len + 63) / 64 * 64;
-        const size_t lds = attention_mfma_lds(a, Tpad);
         // Measured (docs/HISTORY.md 5b): the block kernel is one long dependent chain per workgroup -- with 16 workgroups (one
         // 128-phoneme utterance) it takes 26 us against 11.5 us for the one-query-per-workgroup kernel; from about a
         // hundred workgroups on it wins (batch 8: 98 -> 45 us per launch, text encoder 1.21 -> 0.88 ms)
         const long wgs = (long)((a.max_len + 15) / 16) * a.nheads * a.B;
         const long min_wgs = a.block_min_wgs > 0 ? a.block_min_wgs : 96;
-        if (!no_mfma && wgs >= min_wgs && a.kc % 16 == 0 && a.kc <= 128 && a.px <= 32 && lds <= 150 * 1024) {
-            if (lds > 48 * 1024)
-                hipFuncSetAttribute((const void*)attention_mfma_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            hipLaunchKernelGGL(attention_mfma_kernel, dim3((a.max_len + 15) / 16, a.nheads, a.B), dim3(256), lds, st, a, Tpad);
-            return;
-        }
+        if (!no_mfma && wgs >= min_wgs && attention_admits(a, ATTN_MFMA, &p)) return p;
     }
-    if (a.attn_reg && a.kc <= 4 * ATR_CW && a.px <= 16 && a.max_len <= 256) {   // operands in registers (round 4)
-        if (a.max_len <= 128) hipLaunchKernelGGL(attention_reg_kernel<2>, dim3(a.max_len, a.nheads, a.B), dim3(256), attention_reg_lds(2), st, a);
-        else hipLaunchKernelGGL(attention_reg_kernel<4>, dim3(a.max_len, a.nheads, a.B), dim3(256), attention_reg_lds(4), st, a);
-        return;
+    if (a.attn_reg && attention_admits(a, ATTN_REG, &p)) return p;   // operands in registers (round 4)
+    attention_admits(a, ATTN_GENERIC, &p);
+    return p;
+}
+
+void attention_launch(const AttnArgs& a, const AttnPlan& p, hipStream_t st) {
+    if (p.kernel == ATTN_MFMA) {
+        if (p.lds > 48 * 1024)
+            hipFuncSetAttribute((const void*)attention_mfma_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds);
+        hipLaunchKernelGGL(attention_mfma_kernel, dim3((a.max_len + 15) / 16, a.nheads, a.B), dim3(256), p.lds, st, a, p.Tpad);
+    } else if (p.kernel == ATTN_REG) {
+        if (p.jpl == 2) hipLaunchKernelGGL(attention_reg_kernel<2>, dim3(a.max_len, a.nheads, a.B), dim3(256), p.lds, st, a);
+        else hipLaunchKernelGGL(attention_reg_kernel<4>, dim3(a.max_len, a.nheads, a.B), dim3(256), p.lds, st, a);
+    } else if (p.kernel == ATTN_GENERIC) {
+        if (p.lds > 48 * 1024)
+            hipFuncSetAttribute((const void*)attention_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds);
+        hipLaunchKernelGGL(attention_kernel, dim3(a.max_len, a.nheads, a.B), dim3(256), p.lds, st, a);
     }
-    size_t lds = (size_t)(a.kc + 8 + (a.px > 16 ? a.px : 16) + 5 * (size_t)a.max_len) * sizeof(float);
-    if (lds > 48 * 1024)
-        hipFuncSetAttribute((const void*)attention_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL(attention_kernel, dim3(a.max_len, a.nheads, a.B), dim3(256), lds, st, a);
+}
+
+int attention(const AttnArgs& a, hipStream_t st) {
+    const AttnPlan p = attention_choose(a);
+    attention_launch(a, p, st);
+    return p.kernel;
 }
 
 // ---------------------------------------------------------------------------------------------

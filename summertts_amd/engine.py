@@ -285,6 +285,11 @@ def load_library() -> C.CDLL:
     lib.sts_gain_design.argtypes = [C.c_void_p, C.c_int32, C.c_float, C.c_void_p, C.POINTER(C.c_int32)]
     lib.sts_gain_plan_apply.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.sts_debug_spline_step.argtypes = [C.c_int, C.c_void_p, C.c_int64, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.sts_debug_attention.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
+                                        C.c_void_p, C.c_int32, C.c_int, C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+    lib.sts_debug_layer_norm.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
+                                         C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32,
+                                         C.c_void_p, C.c_int32]
     lib.sts_pool_submit_gain.restype = C.c_int64
     lib.sts_pool_submit_gain.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_float, C.c_uint64, C.c_void_p]
     lib.sts_join_check.argtypes = [C.c_int32, C.c_void_p]
@@ -339,7 +344,7 @@ EXPORTED_SYMBOLS = [
     "sts_multi_set_speaker_mix",
     "sts_set_gain_plan", "sts_gain_plan_check", "sts_gain_design", "sts_gain_plan_apply", "sts_pool_submit_gain",
     "sts_multi_set_gain_plan",
-    "sts_debug_spline_step",
+    "sts_debug_spline_step", "sts_debug_attention", "sts_debug_layer_norm",
     "sts_join_check", "sts_join_layout", "sts_join_apply", "sts_infer_ids_joined", "sts_get_join_offsets", "sts_pool_submit_joined",
     "sts_set_eq", "sts_get_eq", "sts_eq_check", "sts_eq_design", "sts_eq_apply", "sts_pool_set_eq", "sts_multi_set_eq",
 ]
@@ -483,6 +488,80 @@ def debug_spline_step(h, filter_sqrt: float, r0=None, r1=None, device: int = 0, 
     _check(lib, lib.sts_debug_spline_step(int(device), h.ctypes.data, n, float(filter_sqrt), None if r[0] is None else r[0].ctypes.data,
                                           None if r[1] is None else r[1].ctypes.data, o[0].ctypes.data, o[1].ctypes.data))
     return o[0][:n], o[1][:n]
+
+
+ATTN_VARIANTS = {0: "engine's choice", 1: "generic", 2: "register", 3: "mfma"}
+
+
+def _f32(x, shape, what):
+    x = np.ascontiguousarray(x, dtype=np.float32)
+    if x.shape != tuple(shape):
+        raise ValueError(f"{what} is {list(shape)}, got {list(x.shape)}")
+    return x
+
+
+def debug_attention(q, k, v, relk, relv, nheads: int, win: int, lengths, variant: int = 0, device: int = 0, extra_rows: int = 0):
+    """The text encoder's attention on caller data (sts_debug_attention): ``q``, ``k``, ``v`` float32 [nheads * kc][L] with L =
+    sum(lengths), utterances packed back to back; ``relk`` / ``relv`` [kc][2 win + 1], None when ``win`` is 0.  ``variant``: 0 = the
+    engine's choice, 1 = generic, 2 = register, 3 = matrix-core kernel; a forced variant outside its limits raises StsError (STS_EINVAL).
+    -> (o [nheads * kc + extra_rows][L], variant launched, keys per lane of the register kernel or 0).  The output starts out as the word
+    0xFFFFFFFF on the device and comes back whole: ``extra_rows`` > 0 adds rows no kernel may write."""
+    lib = load_library()
+    q = np.ascontiguousarray(q, dtype=np.float32)
+    lens = np.ascontiguousarray(lengths, dtype=np.int32).ravel()
+    if q.ndim != 2 or nheads < 1 or q.shape[0] % nheads or lens.size < 1 or int(lens.sum()) != q.shape[1]:
+        raise ValueError("q is [nheads * kc][sum(lengths)]")
+    rows, L = q.shape
+    kc = rows // nheads
+    k, v = _f32(k, q.shape, "k"), _f32(v, q.shape, "v")
+    if win > 0:
+        relk, relv = _f32(relk, (kc, 2 * win + 1), "relk"), _f32(relv, (kc, 2 * win + 1), "relv")
+    elif relk is not None or relv is not None:
+        raise ValueError("relk and relv are None when win is 0")
+    o = np.zeros((rows + int(extra_rows), L), np.float32)
+    var, jpl = C.c_int32(), C.c_int32()
+    _check(lib, lib.sts_debug_attention(int(device), q.ctypes.data, k.ctypes.data, v.ctypes.data, None if win <= 0 else relk.ctypes.data,
+                                        None if win <= 0 else relv.ctypes.data, int(nheads), kc, int(win), lens.ctypes.data, lens.size,
+                                        int(variant), o.ctypes.data, o.shape[0], C.byref(var), C.byref(jpl)))
+    return o, var.value, jpl.value
+
+
+def debug_layer_norm(a, gamma, beta, lengths, b=None, res=None, pre_relu: bool = False, post_gelu: bool = False, dw_w=None, dw_b=None,
+                     dw_dil: int = 1, dw_pad: int = 0, device: int = 0, extra_rows: int = 0):
+    """The LayerNorm launch on caller data (sts_debug_layer_norm): ``a`` float32 [C][L], L = sum(lengths); ``b`` None or [nb][C][L]
+    split-K partials (nb <= 8); ``res`` None or [C][L]; ``dw_w`` None or [k][C] (fused depthwise conv, ``dw_b`` None or [C]).
+    -> y [C + extra_rows][L], whole, from a device buffer that started out as the word 0xFFFFFFFF."""
+    lib = load_library()
+    a = np.ascontiguousarray(a, dtype=np.float32)
+    lens = np.ascontiguousarray(lengths, dtype=np.int32).ravel()
+    if a.ndim != 2 or lens.size < 1 or int(lens.sum()) != a.shape[1]:
+        raise ValueError("a is [C][sum(lengths)]")
+    Cc, L = a.shape
+    gamma, beta = _f32(gamma, (Cc,), "gamma"), _f32(beta, (Cc,), "beta")
+    nb = 0
+    if b is not None:
+        b = np.ascontiguousarray(b, dtype=np.float32)
+        if b.ndim != 3 or b.shape[1:] != a.shape or not 1 <= b.shape[0] <= 8:
+            raise ValueError("b is [nb][C][L] with 1 <= nb <= 8")
+        nb = b.shape[0]
+    if res is not None:
+        res = _f32(res, a.shape, "res")
+    kk = 0
+    if dw_w is not None:
+        dw_w = np.ascontiguousarray(dw_w, dtype=np.float32)
+        if dw_w.ndim != 2 or dw_w.shape[1] != Cc:
+            raise ValueError("dw_w is [k][C]")
+        kk = dw_w.shape[0]
+        if dw_b is not None:
+            dw_b = _f32(dw_b, (Cc,), "dw_b")
+    elif dw_b is not None:
+        raise ValueError("dw_b goes with dw_w")
+    y = np.zeros((Cc + int(extra_rows), L), np.float32)
+    ptr = lambda x: None if x is None else x.ctypes.data
+    _check(lib, lib.sts_debug_layer_norm(int(device), a.ctypes.data, ptr(b), nb, Cc * L, ptr(res), gamma.ctypes.data, beta.ctypes.data, Cc,
+                                         int(bool(pre_relu)), int(bool(post_gelu)), ptr(dw_w), ptr(dw_b), kk, int(dw_dil), int(dw_pad),
+                                         lens.ctypes.data, lens.size, y.ctypes.data, y.shape[0]))
+    return y
 
 
 def duration_fit(w, fixed=None, target_frames: int = 0) -> np.ndarray:
