@@ -426,9 +426,8 @@ int Engine::run_decode(RunCtx& c, int nw, long Wtot, int maxW, int zoff0, int wl
     mark(6);
 
     // ---------------- decoder tail
-    // (at a non-native output rate the tail always writes the float wave, and its int16 samples go to a scratch buffer: the resampler below
-    // produces the PCM from the wave)
-    float* wave = record_taps || resampling() || lim_mode != 0 || (loud_mode != 0 && !ss) || (eq_n > 0 && !ss) || c.gain || c.join ? bf.wave : nullptr;
+    // (the output chain decides whether the tail writes its float wave, and whether its int16 samples are the PCM or scratch)
+    float* wave = c.oc.wave[OS_TAIL] ? bf.wave : nullptr;
     int16_t* const pcm = bf.pcm_nat;
     const long Ntot = Wtot * hop;
     if (M.dec_type == 0) {          // Generator_hifigan.cpp:177-179 + SynthesizerTrn.cpp:389-396
@@ -459,69 +458,70 @@ int Engine::run_decode(RunCtx& c, int nw, long Wtot, int maxW, int zoff0, int wl
     return decode_end(c, wave, win, Wtot, maxW);
 }
 
-// the end of a decode: the "wave" tap; at a non-native output rate (and not streaming: run_stream_steps resamples each step's windows) the
-// resampler, which writes the PCM of every window at the output rate, packed window after window
+// the end of a decode: a walk down the output chain (out_chain.hpp) behind the tail with one current float signal -- each running stage
+// reads it, writes its own buffer, which becomes the current one, and casts into the PCM when the plan names it the writer -- then the
+// taps.  (A stream: run_stream_steps runs the chain from the resampler on, on each step's windows.)
 int Engine::decode_end(RunCtx& c, const float* wave, const WinGeom& win, long Wtot, int maxW) {
+    const OutChain& oc = c.oc;
     const int hop = c.hop, wlen0 = win.wlen0;
+    const bool whole = !c.ss;
     int nw = win.nw;
     long long max_out = out_count((long long)maxW * hop);
     WinGeom dw = win;                       // the utterances everything behind the gain plan and the join sees
     const float* const raw = wave;          // (the "wave" tap stays the un-gained signal)
-    if (c.gain) {
-        // the gain plan on every window's native samples at their absolute positions (a streaming window: halo included), one launch; it
-        // writes the PCM too when nothing downstream does (native rate, no gain cast, no limiter, no join).  Everything below reads its output
+    const float* cur = wave;
+    auto pcm_of = [&](int stage) { return oc.writer == stage ? c.bf.pcm : nullptr; };
+    if (oc.run[OS_GAIN]) {
+        // the gain plan on every window's native samples at their absolute positions (a streaming window: halo included), one launch
         GainArgs g{};
-        g.x = wave; g.y = c.bf.wave_gain;
-        g.pcm = !c.join && !resampling() && lim_mode == 0 && !(loud_mode == 2 && !c.ss) && !c.bf.wave_eq ? c.bf.pcm : nullptr;
+        g.x = cur; g.y = c.bf.wave_gain; g.pcm = pcm_of(OS_GAIN);
         g.wseg = win.seg(hop, 0); g.hop = hop;
         if (c.ss) { g.utt = (const int*)(c.bf.stab + stream_tab_utt_off(nw)); g.wtab = (const long long*)(c.bf.stab + stream_tab_ll_off(nw)); }
         g.tseg = c.lvT.seg; g.cum = c.bt.cum; g.q = c.bt.gain_q; g.h = c.bt.gain_h;
         gain_plan_run(g, nw, (long long)maxW * hop, stream);
-        wave = c.bf.wave_gain;
+        cur = g.y;
     }
-    if (c.join) {
-        // the B sentences (gained or not) into the one joined signal, silence included, one launch; it writes the PCM too when nothing
-        // downstream does.  From here on there is ONE utterance of F_J frames: one resampled signal, one loudness, one set of limiter stats
+    if (oc.run[OS_JOIN]) {
+        // the B sentences (gained or not) into the one joined signal, silence included, one launch.  From here on there is ONE utterance of
+        // F_J frames: one resampled signal, one loudness, one set of limiter stats
         JoinArgs j{};
-        j.x = wave; j.y = c.bf.wave_join;
-        j.pcm = !resampling() && lim_mode == 0 && loud_mode != 2 && !c.bf.wave_eq ? c.bf.pcm : nullptr;
+        j.x = cur; j.y = c.bf.wave_join; j.pcm = pcm_of(OS_JOIN);
         j.wseg = win.seg(hop, 0);
         if (win.inl) j.isil = join_sil[0]; else j.sil = c.bt.join_sil;
         j.B = nw; j.hop = hop; j.h = join_h; j.NJ = c.FJ * hop;
         join_run(j, stream);
-        wave = c.bf.wave_join;
+        cur = j.y;
         dw = WinGeom{true, 1, 0, (int)c.FJ, nullptr};
         nw = 1; max_out = out_count(c.FJ * hop);
     }
-    // LoudArgs / LimArgs: the float signal at the output rate and its utterances' lengths
-    const float* sig = nullptr;             // (the EQ's output once it has run)
+    // EqArgs / LoudArgs / LimArgs: the float signal at the output rate and its utterances' lengths
     auto signal = [&](auto& a) {
-        a.x = sig ? sig : resampling() ? c.bf.wave_out : wave;
+        a.x = cur;
         a.len = dw.len(); a.ilen = dw.ilen(); a.scale = hop;
-        a.P = resampling() ? rs.P : 1; a.Q = resampling() ? rs.Q : 1;
+        a.P = c.rsP; a.Q = c.rsQ;
     };
-    if (resampling() && !c.ss) {
+    if (oc.run[OS_RESAMPLE] && whole) {
         ResampleArgs a{};
-        a.x = wave;
+        a.x = cur;
         a.seg = dw.seg(hop, 0);
         a.table = d_rs_table; a.P = rs.P; a.Q = rs.Q; a.K = rs.K;
         a.pcm = c.bf.pcm_rs; a.wave_out = c.bf.wave_out;
         resample_pcm(a, nw, max_out, stream);
+        cur = a.wave_out;
     }
-    if (c.bf.wave_eq) {
-        // the equaliser on every utterance of the float signal at the output rate (two launches); loudness and the limiter read its output,
-        // and with neither downstream it writes the PCM
+    if (oc.run[OS_EQ]) {
+        // the equaliser on every utterance of the float signal at the output rate (two launches)
         EqArgs a{};
         signal(a);
-        a.S = eq_n; a.tab = d_eq_;
-        a.y = c.bf.wave_eq; a.pcm = lim_mode == 0 && loud_mode != 2 ? c.bf.pcm : nullptr;
+        a.S = c.eqS; a.tab = d_eq_;
+        a.y = c.bf.wave_eq; a.pcm = pcm_of(OS_EQ);
         eq_ws_carve(a, c.bf.eqws, nw, c.Ocap);
         eq_run(a, nw, max_out, stream);
-        sig = c.bf.wave_eq;
+        cur = a.y;
     }
     const float* gloud = nullptr;
-    if (loud_mode != 0 && !c.ss) {
-        // loudness of every window (= utterance) of the float signal at the output rate; normalising, the gain cast writes the PCM
+    if (oc.run[OS_LOUD]) {
+        // loudness of every window (= utterance) of the current signal; normalising, the gain cast writes the PCM unless the limiter does
         if (loud_k_rate_ != out_rate) {
             if (!loud_coef(out_rate, &loud_k_)) return fail(STS_EINVAL, "loudness: output rate outside [8000, 48000]");
             loud_k_rate_ = out_rate;
@@ -531,18 +531,16 @@ int Engine::decode_end(RunCtx& c, const float* wave, const WinGeom& win, long Wt
         a.target = loud_target; a.ceiling = loud_peak; a.k = loud_k_;
         loud_ws_carve(a, c.bf.lws, nw, c.Ocap);
         a.out = loud_dev_;
-        a.no_clamp = lim_mode != 0;
-        loudness_run(a, nw, max_out, loud_mode == 2 && lim_mode == 0 ? c.bf.pcm : nullptr, stream);
-        if (loud_mode == 2) gloud = a.gain;
+        a.no_clamp = oc.loud_no_clamp;
+        loudness_run(a, nw, max_out, pcm_of(OS_LOUD), stream);
+        if (oc.lim_gloud) gloud = a.gain;
     }
-    if (lim_mode != 0 && !c.ss) {
-        // the limiter on the same signal (times the loudness gain when normalising); it writes the PCM in place of the gain cast
-        LimiterDesign d;
-        if (!limiter_design(out_rate, lim_gain_db, lim_ceiling, lim_ms, &d)) return fail(STS_EINVAL, "limiter: output rate outside [8000, 48000]");
+    if (oc.run[OS_LIMIT] && whole) {
+        // the limiter on the same signal (times the loudness gain when normalising)
         LimArgs a{};
         signal(a);
-        a.H = d.H; a.c = d.c; a.G = d.G; a.gloud = gloud;
-        a.y = c.bf.wave_lim; a.pcm = c.bf.pcm; a.stat = (unsigned*)c.bf.limws;
+        a.H = c.limd.H; a.c = c.limd.c; a.G = c.limd.G; a.gloud = gloud;
+        a.y = c.bf.wave_lim; a.pcm = pcm_of(OS_LIMIT); a.stat = (unsigned*)c.bf.limws;
         limiter_run(a, nw, max_out, stream);
         HIPCK(hipMemcpyAsync(lim_host_, c.bf.limws, (size_t)nw * 16, hipMemcpyDeviceToHost, stream));
     }

@@ -983,9 +983,19 @@ int Engine::wait_frame_counts(RunCtx& c) {
     return STS_OK;
 }
 
-// frame capacity (one utterance: buckets of 64 frames), geometry tables on the device, room for the PCM download
+// the one place that decides the output chain of a run (out_chain.hpp), with the limiter's design and the resampler's ratio for it
+int Engine::plan_output(RunCtx& c) {
+    c.oc = plan_out_chain(OutFacts{c.ss != nullptr, c.B, resampling(), c.gain, c.join, eq_n > 0, loud_mode, lim_mode != 0, record_taps, stream_direct != 0});
+    if (c.oc.run[OS_RESAMPLE]) { c.rsP = rs.P; c.rsQ = rs.Q; }
+    c.eqS = eq_n;
+    if (c.oc.run[OS_LIMIT] && !limiter_design(out_rate, lim_gain_db, lim_ceiling, lim_ms, &c.limd)) return fail(STS_EINVAL, "limiter: output rate outside [8000, 48000]");
+    return STS_OK;
+}
+
+// the output chain, frame capacity (one utterance: buckets of 64 frames), geometry tables on the device, room for the PCM download
 int Engine::frame_geometry(RunCtx& c) {
     Model& M = model;
+    { const int rc = plan_output(c); if (rc != STS_OK) return rc; }
     const int B = c.B; const StreamSpec* const ss = c.ss;
     int* const pm = c.pm; int* const p_offF = c.p_offF; int* const p_lenF = c.p_lenF;
     const int hop = c.hop = M.hop_total;
@@ -1008,7 +1018,7 @@ int Engine::frame_geometry(RunCtx& c) {
     h_pcm = nullptr; pcm_in_host_ = false;
     if (host_pcm && !ss) {   // room for the PCM download that rides at the end of this run
         const long long native = c.join ? c.FJ * hop : (long long)c.Fld * hop;       // (a joined run returns the joined signal)
-        const size_t need = (size_t)(resampling() ? out_count(native) + B : native) * 2 + 256;
+        const size_t need = (size_t)(out_count(native) + (c.oc.run[OS_RESAMPLE] ? B : 0)) * 2 + 256;
         if (need > pinned_pcm_cap_) {
             if (pinned_pcm_) (void)hipHostFree(pinned_pcm_);
             pinned_pcm_ = nullptr; pinned_pcm_cap_ = 0;
@@ -1060,9 +1070,14 @@ int Engine::run_frame_workspace(RunCtx& c) {
     }
     c.use_ff = use_ff; c.ffG = use_ff ? M.cp[0].ff.G : 0;
     BufF& bf = c.bf;
-    const bool loud = loud_mode != 0 && !ss, lim = lim_mode != 0;      // (a streaming call limits chunk by chunk: the same buffers per window)
-    const bool eq = eq_n > 0 && !ss;                          // (streaming calls are refused while an EQ is set)
-    const bool norm = (loud && loud_mode == 2) || lim || eq;  // the gain cast, the limiter or the EQ kernel writes the PCM
+    const OutChain& oc = c.oc;
+    c.Ocap = oc.run[OS_RESAMPLE] ? out_count((long long)Wcap * hop) + B : (long long)Wcap * hop;
+    if (c.join) c.Ocap = oc.run[OS_RESAMPLE] ? out_count(c.FJ * hop) + 1 : c.FJ * hop;
+    if (ss && oc.run[OS_LIMIT] && oc.run[OS_RESAMPLE]) c.Ocap += B;       // (a window's widened output range is rounded per window)
+    // one short utterance with the PCM wanted on the host: the chain's writer stores its int16 samples into the mapped pinned buffer itself
+    // (posted writes over the host link, under the kernel's own run time) instead of a download queued behind it
+    pcm_in_host_ = pcm_direct && host_pcm && !ss && B == 1 && !record_taps && pinned_pcm_dev_ && (size_t)c.Ocap * 2 + 256 <= pinned_pcm_cap_ &&
+                   (size_t)c.Ocap * 2 <= ((size_t)4 << 20);
     auto layoutF = [&](Arena& A) {
         A.used = 0;
         for (int q = 0; q < 2; q++) {
@@ -1080,58 +1095,40 @@ int Engine::run_frame_workspace(RunCtx& c) {
             bf.tailA = A.get<float>((size_t)sbC * Lsb); bf.tailB = A.get<float>((size_t)sbC * Lsb);
             bf.tailC = A.get<float>((size_t)4 * Wcap * upS * 4);
         } else { bf.tailA = bf.tailB = bf.tailC = nullptr; }
-        // (loudness: the tail always writes the float wave, the resampler its float output; normalising, their int16 samples go to
-        // scratch and the gain cast writes bf.pcm; the limiter likewise)
-        // (a gain plan: the tail likewise writes the float wave and its int16 samples go to scratch; the gain kernel writes the gained wave
-        // and, with nothing downstream, bf.pcm)
-        // (a joined run: again the tail writes the float wave and its int16 samples go to scratch; the join kernel writes the joined wave
-        // and, with nothing downstream, bf.pcm; everything behind it is sized for the one joined utterance: c.Ocap)
-        // (an equaliser: the same once more; the EQ kernels write its float output and, with nothing downstream, bf.pcm)
-        bf.wave = A.get<float>(record_taps || resampling() || loud || lim || eq || c.gain || c.join ? (size_t)Wcap * hop : 1);
-        bf.wave_gain = c.gain ? A.get<float>((size_t)Wcap * hop) : nullptr;
-        bf.wave_join = c.join ? A.get<float>((size_t)(c.FJ * hop)) : nullptr;
+        // the output chain: a buffer exists iff a stage of this run reads or writes it (everything behind a join is sized for the one
+        // joined utterance: c.Ocap)
+        bf.wave = A.get<float>(oc.wave[OS_TAIL] ? (size_t)Wcap * hop : 1);
+        bf.wave_gain = oc.wave[OS_GAIN] ? A.get<float>((size_t)Wcap * hop) : nullptr;
+        bf.wave_join = oc.wave[OS_JOIN] ? A.get<float>((size_t)(c.FJ * hop)) : nullptr;
         bf.pcm = A.get<int16_t>((size_t)c.Ocap);
-        bf.pcm_nat = resampling() || norm || c.gain || c.join ? A.get<int16_t>((size_t)Wcap * hop) : bf.pcm;
-        bf.wave_out = (record_taps || loud || lim || eq) && resampling() ? A.get<float>((size_t)c.Ocap) : nullptr;
-        bf.pcm_rs = norm && resampling() ? A.get<int16_t>((size_t)c.Ocap) : bf.pcm;
-        bf.lws = loud ? A.get<char>(loud_ws_bytes(B, c.Ocap)) : nullptr;
-        bf.limws = lim && !ss ? A.get<char>((size_t)B * 16) : nullptr;
-        bf.wave_lim = lim && !ss && record_taps ? A.get<float>((size_t)c.Ocap) : nullptr;
-        bf.wave_eq = eq ? A.get<float>((size_t)c.Ocap) : nullptr;
-        bf.eqws = eq ? A.get<char>(eq_ws_bytes(B, c.Ocap)) : nullptr;
+        if (pcm_in_host_) bf.pcm = pinned_pcm_dev_;
+        bf.pcm_nat = oc.pcm_nat ? A.get<int16_t>((size_t)Wcap * hop) : bf.pcm;
+        bf.wave_out = oc.wave[OS_RESAMPLE] ? A.get<float>((size_t)c.Ocap) : nullptr;
+        bf.pcm_rs = oc.pcm_rs ? A.get<int16_t>((size_t)c.Ocap) : bf.pcm;
+        bf.lws = oc.lws ? A.get<char>(loud_ws_bytes(B, c.Ocap)) : nullptr;
+        bf.limws = oc.limws ? A.get<char>((size_t)B * 16) : nullptr;
+        bf.wave_lim = oc.wave[OS_LIMIT] ? A.get<float>((size_t)c.Ocap) : nullptr;
+        bf.wave_eq = oc.wave[OS_EQ] ? A.get<float>((size_t)c.Ocap) : nullptr;
+        bf.eqws = oc.wave[OS_EQ] ? A.get<char>(eq_ws_bytes(B, c.Ocap)) : nullptr;
         bf.stab = nullptr; bf.spack = nullptr; bf.gwin = bf.cond_win = nullptr;
         if (ss) {
             bf.stab = A.get<char>(stream_tab_bytes(B, c.gain));
-            // (only stream_pack writes there: at another rate the resampler packs into bf.pcm, the limiter likewise, and one utterance's
-            // chunk is downloaded from where the decoder wrote it)
-            if (!resampling() && !lim && B > 1) bf.spack = A.get<int16_t>((size_t)c.Ocap);
+            if (oc.spack) bf.spack = A.get<int16_t>((size_t)c.Ocap);
             if (M.dec_type == 0 && c.ms && c.bstream) { bf.gwin = A.get<float>((size_t)M.gin * B); bf.cond_win = A.get<float>((size_t)M.up_init * B); }
         }
     };
-    c.Ocap = resampling() ? out_count((long long)Wcap * hop) + B : (long long)Wcap * hop;
-    if (c.join) c.Ocap = resampling() ? out_count(c.FJ * hop) + 1 : c.FJ * hop;
-    if (ss && lim && resampling()) c.Ocap += B;       // (a window's widened output range is rounded per window)
     arenaF_.measuring = true; layoutF(arenaF_);
     if (!ensure(arenaF_, arenaF_.used + 4096)) return fail(STS_EDEVICE, "out of device memory (frame-level workspace)");
     arenaF_.measuring = false; layoutF(arenaF_);
     poison_arena(arenaF_);
-    // one short utterance with the PCM wanted on the host: the decoder's last kernel stores its int16 samples into the mapped pinned
-    // buffer itself (posted writes over the host link, under the kernel's own run time) instead of a download queued behind it
-    if (pcm_direct && host_pcm && !ss && B == 1 && !record_taps && pinned_pcm_dev_ && (size_t)c.Ocap * 2 + 256 <= pinned_pcm_cap_ &&
-        (size_t)c.Ocap * 2 <= ((size_t)4 << 20)) {
-        bf.pcm = pinned_pcm_dev_;
-        if (!resampling() && !norm && !c.gain && !c.join) bf.pcm_nat = bf.pcm;     // (native rate: the tail's own samples are the PCM; otherwise the resampler, the gain cast, the gain-plan kernel or the join kernel writes there)
-        if (!norm) bf.pcm_rs = bf.pcm;
-        pcm_in_host_ = true;
-    }
-    if (loud && loud_cap_ < B) {      // host-mapped room for the results: the gating kernel writes them there, the run's last synchronisation covers them
+    if (oc.lws && loud_cap_ < B) {      // host-mapped room for the results: the gating kernel writes them there, the run's last synchronisation covers them
         if (loud_host_) (void)hipHostFree(loud_host_);
         loud_host_ = nullptr; loud_dev_ = nullptr; loud_cap_ = 0;
         if (hipHostMalloc((void**)&loud_host_, (size_t)B * sizeof(sts_loudness), hipHostMallocMapped) != hipSuccess) { loud_host_ = nullptr; return fail(STS_EDEVICE, "pinned host allocation failed"); }
         if (hipHostGetDevicePointer((void**)&loud_dev_, loud_host_, 0) != hipSuccess) { (void)hipHostFree(loud_host_); loud_host_ = nullptr; return fail(STS_EDEVICE, "mapped pinned buffer has no device address"); }
         loud_cap_ = B;
     }
-    if (lim && !ss && lim_cap_ < B) {        // pinned room for the limiter's result words: downloaded behind its launch, the run's last synchronisation covers them
+    if (oc.limws && lim_cap_ < B) {        // pinned room for the limiter's result words: downloaded behind its launch, the run's last synchronisation covers them
         if (lim_host_) { (void)hipStreamSynchronize(stream); (void)hipHostFree(lim_host_); }
         lim_host_ = nullptr; lim_cap_ = 0;
         if (hipHostMalloc((void**)&lim_host_, (size_t)B * 16, hipHostMallocDefault) != hipSuccess) { lim_host_ = nullptr; return fail(STS_EDEVICE, "pinned host allocation failed"); }
@@ -1139,8 +1136,8 @@ int Engine::run_frame_workspace(RunCtx& c) {
     }
     if (poison) {           // the host-visible outputs of this call, before the first kernel that writes them is enqueued
         if (host_pcm && !ss && pinned_pcm_) poison_host16(pinned_pcm_, std::min<size_t>((size_t)c.Ocap, pinned_pcm_cap_ / 2));
-        if (loud && loud_host_) poison_host32(loud_host_, (size_t)B * sizeof(sts_loudness) / 4);
-        if (lim && !ss && lim_host_) poison_host32(lim_host_, (size_t)B * 4);
+        if (oc.lws && loud_host_) poison_host32(loud_host_, (size_t)B * sizeof(sts_loudness) / 4);
+        if (oc.limws && lim_host_) poison_host32(lim_host_, (size_t)B * 4);
     }
 
     Lvl& lv1 = c.lv1; lv1 = Lvl(); lv1.seg = (inl && !c.ahead) ? SegView{nullptr, nullptr, 1, 0, 0, p_lenF[0]} : SegView{d_offF, d_lenF, 1, 0, 0, 0};
@@ -1478,12 +1475,11 @@ int Engine::run_stream_steps(RunCtx& c) {
     c.pm = (int*)pinned_;
     char* const ht = pinned_ + hp_off;
     int16_t* hp = (int16_t*)(pinned_ + hp_off + tab_room);
-    const bool slim = lim_mode != 0;
-    LimiterDesign ld;
-    if (slim && !limiter_design(out_rate, lim_gain_db, lim_ceiling, lim_ms, &ld)) return fail(STS_EINVAL, "limiter: output rate outside [8000, 48000]");
-    // the step's packed chunks on the device: written by the resampler, the limiter, or (native rate, no limiter) stream_pack -- which one
-    // utterance does without unless the chunks are to be stored into host memory
-    const bool pack = !resampling() && !slim && (B > 1 || stream_direct);
+    const OutChain& oc = c.oc;
+    const bool srs = oc.run[OS_RESAMPLE], slim = oc.run[OS_LIMIT], pack = oc.run[OS_PACK];
+    const LimiterDesign& ld = c.limd;
+    // the step's packed chunks on the device: written by the chain's writer when that is the resampler or the limiter, else by stream_pack
+    // -- which one utterance does without unless the chunks are to be stored into host memory
     int16_t* dst = pack ? bf.spack : bf.pcm;
     if (stream_direct) {       // posted writes: the last kernel of a step stores the chunks into the mapped pinned buffer itself
         if (pcm_bytes > pinned_pcm_cap_ || !pinned_pcm_dev_) {
@@ -1535,8 +1531,8 @@ int Engine::run_stream_steps(RunCtx& c) {
             ti[i] = offF[b] + (int)w.w0; ti[nw + i] = (int)Wtot; ti[2 * nw + i] = (int)wlen; ti[3 * nw + i] = c.mix ? b : sidv[b];      // (a mixed run: the window's utterance, a column of bt.g)
             ti[4 * nw + i] = (int)((Wtot + (f0 - w.w0)) * hop); ti[5 * nw + i] = (int)dsum;
             tl[5 * i] = (long long)w.w0 * hop; tl[5 * i + 1] = (long long)F * hop; tl[5 * i + 2] = w.jl0; tl[5 * i + 3] = w.jl1; tl[5 * i + 4] = slim ? rsum : dsum;
-            tm[7 * i] = resampling() ? rsum : (long long)Wtot * hop; tm[7 * i + 1] = resampling() ? w.jl0 : (long long)w.w0 * hop;
-            tm[7 * i + 2] = resampling() ? nrs : (long long)wlen * hop; tm[7 * i + 3] = w.Nout;
+            tm[7 * i] = srs ? rsum : (long long)Wtot * hop; tm[7 * i + 1] = srs ? w.jl0 : (long long)w.w0 * hop;
+            tm[7 * i + 2] = srs ? nrs : (long long)wlen * hop; tm[7 * i + 3] = w.Nout;
             tm[7 * i + 4] = w.j0; tm[7 * i + 5] = w.j1; tm[7 * i + 6] = dsum;
             rsum += nrs; max_rs = std::max(max_rs, nrs);
             wj0[i] = w.j0; wn[i] = nout; wdst[i] = dsum;
@@ -1549,14 +1545,12 @@ int Engine::run_stream_steps(RunCtx& c) {
         // one utterance: its window by value (no table load in the decoder's kernels); several: the tables, also while one window is live
         int rc = B == 1 ? run_decode(c, 1, Wtot, maxW, ti[0], ti[2]) : run_decode(c, nw, Wtot, maxW, 0, -1);
         if (rc != STS_OK) return rc;
-        // (a gain plan: run_decode's last launch gained the windows at their absolute positions into bf.wave_gain -- and, with nothing else
-        // downstream, cast them into bf.pcm -- and the resampler and the limiter read that)
-        const float* const sig = c.gain ? bf.wave_gain : bf.wave;
-        if (resampling()) {
+        // (run_decode ran the chain up to the gain plan on the windows at their absolute positions)
+        if (srs) {
             ResampleArgs a{};
-            a.x = sig; a.seg = SegView{c.d_win + nw, c.d_win + 2 * nw, hop, 0, 0, 0};
+            a.x = c.stage_out(oc.src[OS_RESAMPLE]); a.seg = SegView{c.d_win + nw, c.d_win + 2 * nw, hop, 0, 0, 0};
             a.table = d_rs_table; a.P = rs.P; a.Q = rs.Q; a.K = rs.K;
-            a.pcm = slim ? bf.pcm_rs : dst; a.wave_out = slim ? bf.wave_out : nullptr;
+            a.pcm = oc.writer == OS_RESAMPLE ? dst : bf.pcm_rs; a.wave_out = bf.wave_out;
             a.wtab = (const long long*)(bf.stab + stream_tab_ll_off(nw));
             resample_pcm(a, nw, max_rs, stream);
         } else if (pack) {
@@ -1564,14 +1558,14 @@ int Engine::run_stream_steps(RunCtx& c) {
         }
         if (slim) {          // every window of the step in one launch; it writes the packed chunks in place of the resampler / the pack
             LimArgs a{};
-            a.x = resampling() ? bf.wave_out : sig;
+            a.x = c.stage_out(oc.src[OS_LIMIT]);
             a.H = ld.H; a.c = ld.c; a.G = ld.G;
             a.pcm = dst;
             a.wtab = (const long long*)(bf.stab + stream_tab_lim_off(nw));
             limiter_run(a, nw, max_out, stream);
         }
         // (nothing packed: the one window's kept samples, at its pack source in the decoder's own PCM)
-        const int16_t* const src = resampling() || slim || pack ? dst : bf.pcm + ti[4 * nw];
+        const int16_t* const src = oc.chunk_in_place ? bf.pcm + ti[4 * nw] : dst;
         if (!stream_direct) HIPCK(hipMemcpyAsync(hp, src, (size_t)dsum * 2, hipMemcpyDeviceToHost, stream));
         HIPCK(hipStreamSynchronize(stream));
         if (conv_math == 3 && ((ovf_host_ && *(volatile unsigned*)ovf_host_ != 0u) || (stream_retry_step >= 0 && k == stream_retry_step))) {

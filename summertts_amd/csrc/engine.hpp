@@ -212,6 +212,7 @@ private:
     int run_decode(RunCtx& c, int nw, long Wtot, int maxW, int zoff0, int wlen0);
     int decode_end(RunCtx& c, const float* wave, const WinGeom& win, long Wtot, int maxW);
     int wait_frame_counts(RunCtx& c);
+    int plan_output(RunCtx& c);
     int frame_geometry(RunCtx& c);
     int run_output(RunCtx& c);
     int run_stream_steps(RunCtx& c);

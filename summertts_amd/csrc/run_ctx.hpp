@@ -2,6 +2,7 @@
 // of one run share.
 #pragma once
 #include "engine.hpp"
+#include "out_chain.hpp"
 
 namespace sts {
 
@@ -30,22 +31,18 @@ struct BufT {
 struct BufF {
     float *z, *h, *acts, *out, *x0, *regA, *regB, *tailA, *tailB, *tailC, *wave, *fliptmp;
     float *ff_h[2], *ff_part[2], *ff_macc[2], *ff_alt;        // one-launch-per-layer flow (wn_flow.hip): channel-minor h / partial sums / -m slices, alternate home of a z half
+    // the output chain (out_chain.hpp): a buffer exists iff a stage of this run reads or writes it, and is null otherwise.  pcm: the returned
+    // PCM; pcm_nat / pcm_rs: the tail's / the resampler's int16 samples (pcm when that stage is the writer, else scratch); wave_*: the
+    // stages' float outputs (wave above: the tail's); lws / limws / eqws: stage workspaces; streaming: the step tables (stream_tab_bytes),
+    // stream_pack's packed chunk buffer, the per-window speaker vectors and conditioning of a multi-speaker HiFi-GAN decoder
+    // (members in the order they were added: the layout every earlier build measured with)
     int16_t* pcm;
-    int16_t* pcm_nat; float* wave_out;   // at a non-native output rate: the decoder tail's own int16 samples (not returned), the resampled float wave (taps)
-    // loudness: where the resampler's int16 samples go (scratch when normalising, else pcm), the loudness kernels' workspace (or null)
+    int16_t* pcm_nat; float* wave_out;
     int16_t* pcm_rs; char* lws;
-    // limiter: its raw result words [B][4], its float output (taps only)
     char* limws; float* wave_lim;
-    // a run with a gain plan only (null otherwise): the gained native float wave, laid out like wave (what the resampler, loudness and the
-    // limiter then read in its place)
     float* wave_gain;
-    // a joined run only (null otherwise): the joined native float wave J [NJ] -- one utterance for everything behind it
     float* wave_join;
-    // streaming only (null otherwise): the step tables (stream_tab_bytes); several utterances: the packed chunk buffer stream_pack writes
-    // (native rate, no limiter), the per-window speaker vectors and decoder conditioning of a multi-speaker HiFi-GAN decoder
     char* stab; int16_t* spack; float *gwin, *cond_win;
-    // a run with an equaliser only (null otherwise): its float output at the output rate, laid out like wave_out (what loudness and the
-    // limiter then read), and the scan's workspace
     float* wave_eq; char* eqws;
 };
 // Streaming, the tables of one step with nw windows (one upload, c.d_win points at them): ints [zoff nw | coff nw | wlen nw | sid nw |
@@ -87,6 +84,13 @@ struct Engine::RunCtx {
     long long Ocap = 0;             // PCM capacity in output samples (== Wcap * hop at the native rate)
     bool bstream = false;           // a stream of several utterances: window i of a step is not utterance i (run_decode gathers the conditioning per window)
     bool use_ff = false; int ffG = 0;
+    // the output chain of this run (Engine::plan_output), and next to it the limiter's design, the resampler's ratio (1 / 1: native rate)
+    // and the EQ's band count
+    OutChain oc{}; LimiterDesign limd; int rsP = 1, rsQ = 1, eqS = 0;
+    const float* stage_out(int s) const {      // the float output of stage s (null: it has none in this run)
+        const float* const o[OS_COUNT] = {bf.wave, bf.wave_gain, bf.wave_join, bf.wave_out, nullptr, bf.wave_eq, nullptr, bf.wave_lim};
+        return s < 0 ? nullptr : o[s];
+    }
 };
 #define RUN_ALIASES(c)                                                                                                              \
     [[maybe_unused]] Model& M = model;                                                                                              \
