@@ -421,13 +421,43 @@ int sts_join_apply(int device, const float* x, const int32_t* frames, int32_t B,
  * i of sentence b with f frames before it in its sentence at ceil((start_b + f hop) P / Q); sts_get_join_offsets the sentence starts
  * ceil(start_b P / Q); sts_get_loudness and sts_get_limiter report count 1.  Taps: "wave" and "wave_gain" stay per sentence (packed);
  * "wave_join" is J; "wave_out" and "wave_lim" are computed from J.
- * Out of scope: a streaming form (the step loop decodes chunk k of EVERY member, the wrong order for a paragraph), sts_multi_*, and
- * per-request plans through the pool. */
+ * The streaming form is sts_infer_ids_joined_stream below.  Out of scope: sts_multi_*, and per-request plans through the pool. */
 int sts_infer_ids_joined(sts_engine* e, int32_t B, const int32_t* const* ids, const int32_t* n, const int32_t* sid,
                          const float* length_scale, const sts_join* join, int16_t** pcm_out, int32_t* n_out);
 /* Sentence starts of the last call in output samples, ceil(start_b P / Q): [B] entries (capacity below B: STS_EINVAL).  STS_ESTATE when the
  * last call was not a joined one. */
 int sts_get_join_offsets(sts_engine* e, int64_t* start, int64_t capacity);
+/* The joined signal of sts_infer_ids_joined, streamed: chunked PCM of the ONE signal, in order.
+ *   Front, duration predictor and flow run once as the packed batch of B, exactly as in sts_infer_ids_joined: the same sid rule, noise
+ *   seed + b and forced durations; a pending duration plan, speaker mix or gain plan applies per sentence.
+ *   Layout: sts_join_layout's start_b, N_J, F_J = N_J / hop and h.  N_J > 2 10^9 or L_out > 2^31 - 1 answers STS_EINVAL before the decoder
+ *   runs, as there.
+ *   Chunks: with C = chunk_frames, step k delivers the frames [k C, min((k + 1) C, F_J)) of the JOINED signal -- at the output rate the
+ *   samples [ceil(k C hop P / Q), ceil(min((k + 1) C, F_J) hop P / Q)); sample_offset is the first of them.  There are exactly
+ *   ceil(F_J / C) callbacks, in order, one per step; a step that lies wholly in silence is one of them (and launches no decoder kernel).
+ *   A non-zero return ends the call with STS_OK; *n_total (optional) is the samples delivered.  `pcm` is only valid inside the callback.
+ *   Each step decodes, of every sentence within reach of the chunk, one window (the chunk, the resampler's and limiter's reach, the
+ *   decoder's halo), joins the windows into a window of J and runs resampler and limiter on J as one utterance: the decoder workspace is
+ *   bounded by the chunk, not by the paragraph.
+ *   Equality: the concatenated chunks equal sts_infer_ids_joined's PCM of the same call bit for bit when the kernel variant is pinned
+ *   (sts_set_conv_mode), and agree within 1 LSB under the automatic choice -- the streaming contract of sts_infer_ids_stream.  With
+ *   B == 1 and an all-zero join the chunks equal sts_infer_ids_stream's.
+ *   The limiter may be on: the chunks concatenate to the whole joined PCM, and its look-ahead reaches across the joins.  Loudness mode
+ *   != 0 or EQ bands set answers STS_EINVAL, as for every stream.
+ *   B < 1, chunk_frames <= 0, a NULL callback, NULL ids / n or an invalid join answers STS_EINVAL: nothing runs and nothing changes.
+ *   Afterwards sts_get_join_offsets, sts_get_phoneme_offsets and sts_get_durations answer as after sts_infer_ids_joined.
+ *   Conv math 3: the overflow word follows sts_infer_ids_batch_stream's rule -- raised at step 0 the whole call is repeated in the
+ *   split-bf16 form, raised later that step and the steps after it are decoded in that form, and no chunk leaves twice
+ *   (STS_DBG_STREAM_RETRY_STEP applies).  The call neither reads nor feeds the launch-ahead memo. */
+int sts_infer_ids_joined_stream(sts_engine* e, int32_t B, const int32_t* const* ids, const int32_t* n, const int32_t* sid,
+                                const float* length_scale, const sts_join* join, int32_t chunk_frames, sts_chunk_cb cb, void* user,
+                                int32_t* n_total);
+/* The windowed join kernel of a joined stream on caller signals, like sts_join_apply: y (float) and pcm (int16) receive
+ * J[first_frame hop, (first_frame + n_frames) hop) and its cast, n_frames samples_per_frame samples each; each may be NULL.  The range must lie
+ * inside [0, F_J) with n_frames >= 1.  Only the parts of each sentence inside the range are uploaded, packed compactly, with the window
+ * table the engine's step builds.  On the device both outputs start out as a NaN / 0x7FFF pattern, as in sts_join_apply. */
+int sts_join_apply_range(int device, const float* x, const int32_t* frames, int32_t B, int32_t samples_per_frame, const sts_join* join,
+                         int64_t first_frame, int64_t n_frames, float* y, int16_t* pcm);
 /* ---- parametric equaliser (no reference counterpart; ABI number unchanged).  sts_set_eq(e, n_bands, bands) puts a tone stage of 0 to
  * STS_EQ_MAX_BANDS biquad sections in front of loudness and the limiter: an "audio profile" (telephone band, rumble and DC removal, a
  * presence lift) that loudness mode 2 and the limiter then measure and limit as played.  n_bands = 0 (default) switches the stage off:

@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "engine.hpp"
+#include "join_stream.hpp"
 
 using namespace sts;
 
@@ -434,6 +435,79 @@ int sts_infer_ids_joined(sts_engine* e, int32_t B, const int32_t* const* ids, co
     rc = sts_copy_pcm_host(e, all, total);
     if (rc != STS_OK) { free(all); return rc; }
     *pcm_out = all; *n_out = (int32_t)total;
+    return STS_OK;
+}
+int sts_join_apply_range(int device, const float* x, const int32_t* frames, int32_t B, int32_t samples_per_frame, const sts_join* join,
+                         int64_t first_frame, int64_t n_frames, float* y, int16_t* pcm) {
+    const char* why = nullptr;
+    if (!join_valid(B, join, &why)) return set_err(STS_EINVAL, why);
+    if (!x || !frames || samples_per_frame < 1 || samples_per_frame > (1 << 20) || B > (1 << 24))
+        return set_err(STS_EINVAL, "1 <= B <= 2^24 signals, their frame counts and samples_per_frame >= 1 are required");
+    const int hop = samples_per_frame;
+    std::vector<long long> sil((size_t)B);
+    const long long all = join_silence(B, join, sil.data());
+    int64_t F = 0;
+    for (int b = 0; b < B; b++) {
+        if (frames[b] < 1) return set_err(STS_EINVAL, "join: every sentence has frames[b] >= 1");
+        F += frames[b];
+        if ((F + all) * hop > ((int64_t)1 << 30)) return set_err(STS_EINVAL, "the signals and the joined signal must hold at most 2^30 samples each");
+    }
+    JsPlan js;                  // the layout and the window table the engine's step loop builds, with no decoder halo
+    js.layout(B, frames, sil.data(), all);
+    js.hop = hop;
+    if (first_frame < 0 || n_frames < 1 || first_frame > js.FJ - n_frames) return set_err(STS_EINVAL, "join: the range must be n_frames >= 1 frames inside [0, F_J)");
+    const long long g0 = first_frame, g1 = first_frame + n_frames;
+    std::vector<JsWin> win; std::vector<JsRow> rows;
+    long long Wtot = 0;
+    js.windows(g0, g1, 0, win, &Wtot, nullptr);
+    js.rows(g0, g1, win, rows);
+    const int nw = (int)win.size();
+    const int64_t NX = Wtot * hop, NY = n_frames * hop;
+    if (hipSetDevice(device) != hipSuccess) return set_err(STS_EDEVICE, "no such device");
+    auto pad = [](size_t bytes) { return (bytes + 255) & ~(size_t)255; };
+    const size_t xb = pad((size_t)NX * 4 + 16), tb = pad((size_t)nw * 5 * 8 + 8), yb = pad((size_t)NY * 4), pb = pad((size_t)NY * 2);
+    char* d = nullptr;          // [x: only the parts inside the range, packed | table | y | pcm]
+    if (hipMalloc((void**)&d, xb + tb + yb + pb) != hipSuccess) return set_err(STS_EDEVICE, "out of device memory");
+    hipStream_t st = nullptr;
+    bool ok = hipStreamCreate(&st) == hipSuccess;
+    std::vector<long long> tab((size_t)nw * 5 + 1);
+    std::vector<int64_t> xoffF((size_t)B + 1, 0);       // sentence b's first frame in the caller's x
+    for (int b = 0; b < B; b++) xoffF[b + 1] = xoffF[b] + frames[b];
+    for (int i = 0; i < nw && ok; i++) {
+        const JsWin& w = win[i]; const JsRow& r = rows[i];
+        tab[5 * i] = r.st; tab[5 * i + 1] = r.en; tab[5 * i + 2] = r.S; tab[5 * i + 3] = r.N; tab[5 * i + 4] = r.xoff;
+        ok = hipMemcpyAsync(d + (size_t)w.coff * hop * 4, x + (xoffF[w.b] + w.w0) * hop, (size_t)(w.w1 - w.w0) * hop * 4, hipMemcpyHostToDevice, st) == hipSuccess;
+    }
+    JoinWinArgs a{};
+    a.x = (const float*)d; a.y = y ? (float*)(d + xb + tb) : nullptr; a.pcm = pcm ? (int16_t*)(d + xb + tb + yb) : nullptr;
+    a.rows = (const long long*)(d + xb); a.nw = nw; a.hop = hop; a.h = join ? join_design(join->fade_ms) : 0;
+    a.g0 = g0 * hop; a.g1 = g1 * hop; a.k0 = a.g0; a.k1 = a.g1;
+    // (the outputs start out as NaN / 0x7FFF: a sample the kernel leaves out shows)
+    ok = ok && hipMemcpyAsync(d + xb, tab.data(), tab.size() * 8, hipMemcpyHostToDevice, st) == hipSuccess &&
+         hipMemsetAsync(d + xb + tb, 0xFF, yb, st) == hipSuccess &&
+         hipMemsetD16Async((hipDeviceptr_t)(d + xb + tb + yb), 0x7FFF, pb / 2, st) == hipSuccess;
+    if (ok) {
+        join_window_run(a, st);
+        ok = hipGetLastError() == hipSuccess &&
+             (!y || hipMemcpyAsync(y, d + xb + tb, (size_t)NY * 4, hipMemcpyDeviceToHost, st) == hipSuccess) &&
+             (!pcm || hipMemcpyAsync(pcm, d + xb + tb + yb, (size_t)NY * 2, hipMemcpyDeviceToHost, st) == hipSuccess) &&
+             hipStreamSynchronize(st) == hipSuccess;
+    } else if (st) (void)hipStreamSynchronize(st);
+    if (st) (void)hipStreamDestroy(st);
+    (void)hipFree(d);
+    return ok ? STS_OK : set_err(STS_EDEVICE, "the join failed on the device");
+}
+int sts_infer_ids_joined_stream(sts_engine* e, int32_t B, const int32_t* const* ids, const int32_t* n, const int32_t* sid,
+                                const float* length_scale, const sts_join* join, int32_t chunk_frames, sts_chunk_cb cb, void* user,
+                                int32_t* n_total) {
+    if (!e) return set_err(STS_EINVAL, "null engine");
+    if (B < 1 || !ids || !n || chunk_frames <= 0 || !cb) return set_err(STS_EINVAL, "B >= 1, ids, n, a positive chunk size and a callback are required");
+    struct { sts_chunk_cb cb; void* user; } one{cb, user};      // the engine's callback names the utterance; J is the only one
+    using One = decltype(one);
+    const int rc = e->eng.run_joined_stream(B, ids, n, sid, length_scale, join, chunk_frames,
+                                            [](void* u, int32_t, const int16_t* pcm, int32_t ns, int32_t off) { return ((One*)u)->cb(((One*)u)->user, pcm, ns, off); },
+                                            &one, n_total);
+    if (rc != STS_OK) return set_err(rc, e->eng.error());
     return STS_OK;
 }
 int sts_get_join_offsets(sts_engine* e, int64_t* start, int64_t capacity) {

@@ -481,7 +481,7 @@ int Engine::decode_end(RunCtx& c, const float* wave, const WinGeom& win, long Wt
         gain_plan_run(g, nw, (long long)maxW * hop, stream);
         cur = g.y;
     }
-    if (oc.run[OS_JOIN]) {
+    if (oc.run[OS_JOIN] && whole) {     // (a joined stream: run_stream_steps joins each step's windows into a window of J)
         // the B sentences (gained or not) into the one joined signal, silence included, one launch.  From here on there is ONE utterance of
         // F_J frames: one resampled signal, one loudness, one set of limiter stats
         JoinArgs j{};
@@ -548,7 +548,7 @@ int Engine::decode_end(RunCtx& c, const float* wave, const WinGeom& win, long Wt
     if (raw && record_taps) {
         tap("wave", raw, 1, Wtot * hop, (wlen0 >= 0 ? (long)wlen0 : Wtot) * hop);
         if (c.gain && !c.ss) tap("wave_gain", c.bf.wave_gain, 1, Wtot * hop, (wlen0 >= 0 ? (long)wlen0 : Wtot) * hop);
-        if (c.join) tap("wave_join", c.bf.wave_join, 1, (long)(c.FJ * hop), (long)(c.FJ * hop));
+        if (c.join && !c.ss) tap("wave_join", c.bf.wave_join, 1, (long)(c.FJ * hop), (long)(c.FJ * hop));
         if ((c.bf.wave_out || c.bf.wave_lim || c.bf.wave_eq) && !c.ss) {    // (a stream has moved the pinned block p_lenF points into: not read then)
             long long n = 0;        // samples at the output rate: what both taps hold
             if (c.join) n = out_count(c.FJ * hop);

@@ -486,8 +486,9 @@ int Engine::join_offsets(int64_t* start, int64_t capacity) {
     return STS_OK;
 }
 // sts_infer_ids_joined: the join is validated and laid out here (silence frames in front of each sentence, h); an invalid join changes
-// nothing.  The run itself is run()'s, with join_on set: run_setup uploads the table, decode_end launches the join kernel
-int Engine::run_joined(int B, const int32_t* const* ids, const int32_t* n, const int32_t* sid, const float* ls, const sts_join* join) {
+// nothing.  The run itself is run()'s, with join_on set: run_setup uploads the table, decode_end launches the join kernel (a stream:
+// run_stream_steps launches the windowed one per step)
+int Engine::run_joined(int B, const int32_t* const* ids, const int32_t* n, const int32_t* sid, const float* ls, const sts_join* join, const StreamSpec* ss) {
     const char* why = nullptr;
     if (!join_valid(B, join, &why)) return fail(STS_EINVAL, why);
     if (!ids || !n) return fail(STS_EINVAL, "empty batch");
@@ -498,7 +499,7 @@ int Engine::run_joined(int B, const int32_t* const* ids, const int32_t* n, const
     for (int b = 0; b < B; b++) join_sil[b] = (int32_t)sil[b];
     join_h = join ? join_design(join->fade_ms) : 0;
     join_on = true;
-    const int rc = run(B, ids, n, sid, ls);
+    const int rc = run(B, ids, n, sid, ls, ss);
     join_on = false;
     return rc;
 }
@@ -1046,6 +1047,18 @@ int Engine::run_frame_workspace(RunCtx& c) {
         Wcap = 0;
         for (int b = 0; b < B; b++) Wcap += std::min<long>(p_lenF[b], (long)ss->chunk_frames + 2 * halo);
     }
+    if (ss && c.join) {
+        // a joined stream: the steps walk J (join_stream.hpp).  The workspace is the most frames one step decodes -- the maximum over the
+        // steps of the summed window lengths, never the sum of the sentences
+        JsPlan& js = c.js;
+        std::vector<long long> sil(join_sil.begin(), join_sil.end());
+        js.layout(B, p_lenF, sil.data(), join_total_sil);
+        js.hop = hop; js.C = ss->chunk_frames;
+        js.Hd = decoder_halo_frames(M); js.Ho = halo - js.Hd;
+        js.P = resampling() ? rs.P : 1; js.Q = resampling() ? rs.Q : 1;
+        js.H = c.oc.run[OS_LIMIT] ? c.limd.H : 0;
+        Wcap = std::max<long>(1, (long)js.workspace());
+    }
     c.Wcap = Wcap;
     int upS = 1;
     for (int u : M.up_rate) upS *= u;
@@ -1073,6 +1086,8 @@ int Engine::run_frame_workspace(RunCtx& c) {
     const OutChain& oc = c.oc;
     c.Ocap = oc.run[OS_RESAMPLE] ? out_count((long long)Wcap * hop) + B : (long long)Wcap * hop;
     if (c.join) c.Ocap = oc.run[OS_RESAMPLE] ? out_count(c.FJ * hop) + 1 : c.FJ * hop;
+    const long long jwin = ss && c.join ? c.js.window_frames() * hop : c.FJ * hop;      // floats of the join's output: a step's window of J, or J
+    if (ss && c.join) c.Ocap = oc.run[OS_RESAMPLE] ? out_count(jwin) + 4 : jwin;         // (the widened range of a step lies inside its window's outputs)
     if (ss && oc.run[OS_LIMIT] && oc.run[OS_RESAMPLE]) c.Ocap += B;       // (a window's widened output range is rounded per window)
     // one short utterance with the PCM wanted on the host: the chain's writer stores its int16 samples into the mapped pinned buffer itself
     // (posted writes over the host link, under the kernel's own run time) instead of a download queued behind it
@@ -1099,7 +1114,7 @@ int Engine::run_frame_workspace(RunCtx& c) {
         // joined utterance: c.Ocap)
         bf.wave = A.get<float>(oc.wave[OS_TAIL] ? (size_t)Wcap * hop : 1);
         bf.wave_gain = oc.wave[OS_GAIN] ? A.get<float>((size_t)Wcap * hop) : nullptr;
-        bf.wave_join = oc.wave[OS_JOIN] ? A.get<float>((size_t)(c.FJ * hop)) : nullptr;
+        bf.wave_join = oc.wave[OS_JOIN] ? A.get<float>((size_t)jwin) : nullptr;
         bf.pcm = A.get<int16_t>((size_t)c.Ocap);
         if (pcm_in_host_) bf.pcm = pinned_pcm_dev_;
         bf.pcm_nat = oc.pcm_nat ? A.get<int16_t>((size_t)Wcap * hop) : bf.pcm;
@@ -1112,7 +1127,7 @@ int Engine::run_frame_workspace(RunCtx& c) {
         bf.eqws = oc.wave[OS_EQ] ? A.get<char>(eq_ws_bytes(B, c.Ocap)) : nullptr;
         bf.stab = nullptr; bf.spack = nullptr; bf.gwin = bf.cond_win = nullptr;
         if (ss) {
-            bf.stab = A.get<char>(stream_tab_bytes(B, c.gain));
+            bf.stab = A.get<char>(c.join ? join_stream_tab_bytes(B, c.gain) : stream_tab_bytes(B, c.gain));
             if (oc.spack) bf.spack = A.get<int16_t>((size_t)c.Ocap);
             if (M.dec_type == 0 && c.ms && c.bstream) { bf.gwin = A.get<float>((size_t)M.gin * B); bf.cond_win = A.get<float>((size_t)M.up_init * B); }
         }
@@ -1325,7 +1340,6 @@ int Engine::run_once(int B, const int32_t* const* ids, const int32_t* n, const i
     mfma_flops_ = 0; mfma_exec_ = 0; bf16_exec_ = 0; mfma_launches_ = 0; in_mfma_region_ = false;
 
     loud_res.clear(); lim_res.clear(); last_join_start.clear();
-    if (ss && join_on) return fail(STS_EINVAL, "a joined call has no streaming form");
     if (ss && loud_mode != 0)
         return fail(STS_EINVAL, "streaming is not available while loudness measurement or normalization is on (sts_set_loudness mode 0 first): "
                                 "normalizing needs the whole utterance before its first sample leaves");
@@ -1469,7 +1483,8 @@ int Engine::run_stream_steps(RunCtx& c) {
     // (ensure_pinned below may move the pinned block the geometry tables live in)
     const std::vector<int> offF(p_offF, p_offF + B), lenF(p_lenF, p_lenF + B), sidv(c.p_sid, c.p_sid + B);
     const size_t hp_off = (up_bytes + ((size_t)Ttot + B) * 4 + 255) & ~(size_t)255;
-    const size_t tab_room = (stream_tab_bytes(B, c.gain) + 255) & ~(size_t)255;
+    const bool joined = c.join;       // a joined stream: the steps walk J, one chunk of the ONE signal per step (join_stream.hpp)
+    const size_t tab_room = ((joined ? join_stream_tab_bytes(B, c.gain) : stream_tab_bytes(B, c.gain)) + 255) & ~(size_t)255;
     const size_t pcm_bytes = (size_t)c.Ocap * 2 + 256;
     if (!ensure_pinned(hp_off + tab_room + pcm_bytes)) return fail(STS_EDEVICE, "pinned host allocation failed");
     c.pm = (int*)pinned_;
@@ -1495,7 +1510,7 @@ int Engine::run_stream_steps(RunCtx& c) {
     poison_host16(hp, (size_t)c.Ocap);
     c.d_win = (int*)bf.stab;
     std::vector<char> live(B, 1);
-    if (ss->delivered) for (int b = 0; b < B; b++) ss->delivered[b] = 0;
+    if (ss->delivered) for (int b = 0; b < (joined ? 1 : B); b++) ss->delivered[b] = 0;
     d_pcm = nullptr; total_samples = 0;
     std::vector<int> wb; std::vector<long long> wj0, wn, wdst;
     // The window of chunk frames [f0, f1) of an utterance of F frames: frames [w0, w1).  Its native samples [f0 hop, f1 hop) are, at the output
@@ -1510,62 +1525,132 @@ int Engine::run_stream_steps(RunCtx& c) {
         w.jl0 = slim ? std::max<long long>(0, w.j0 - 2 * ld.H) : w.j0; w.jl1 = slim ? std::min<long long>(w.Nout, w.j1 + 2 * ld.H) : w.j1;
         return w;
     };
-    for (long k = 0;; k++) {
-        const long f0 = k * Cf;
-        wb.clear();
-        for (int b = 0; b < B; b++) if (live[b] && f0 < lenF[b]) wb.push_back(b);
-        const int nw = (int)wb.size();
-        if (nw == 0) break;
+    // a joined stream's step: the tables of its decode windows (the layout every stream uses: run_decode and the gain kernel read them), the
+    // one window of J for the resampler and the limiter, the join's rows; one upload, one decode over the windows (none: no decoder kernel),
+    // the windowed join, then resampler and limiter on the one utterance J.  Everything around it -- download, synchronisation, the
+    // conv-math-3 repeat, the callback -- is the loop's below
+    JsStep jt; std::vector<JsRow> jrows;
+    const long long NJ = c.FJ * hop;
+    auto joined_step = [&](long k, long long* dsum_out) -> int {
+        const JsPlan& js = c.js;
+        js.step(k, jt);
+        const int nw = (int)jt.win.size();
+        js.rows(jt.g0, jt.g1, jt.win, jrows);
         int* ti = (int*)ht;
         long long* tl = (long long*)(ht + stream_tab_ll_off(nw));
         long long* tm = (long long*)(ht + stream_tab_lim_off(nw));
-        long long rsum = 0;                                 // limiter: the resampler's float outputs of the widened ranges, packed
-        wj0.assign(nw, 0); wn.assign(nw, 0); wdst.assign(nw, 0);
-        long Wtot = 0; int maxW = 0; long long dsum = 0, max_out = 0, max_rs = 0;
         for (int i = 0; i < nw; i++) {
-            const int b = wb[i];
-            const long F = lenF[b];
-            const Win w = window(F, f0);
-            const long wlen = w.w1 - w.w0;
-            const long long nrs = w.jl1 - w.jl0, nout = w.j1 - w.j0;
-            ti[i] = offF[b] + (int)w.w0; ti[nw + i] = (int)Wtot; ti[2 * nw + i] = (int)wlen; ti[3 * nw + i] = c.mix ? b : sidv[b];      // (a mixed run: the window's utterance, a column of bt.g)
-            ti[4 * nw + i] = (int)((Wtot + (f0 - w.w0)) * hop); ti[5 * nw + i] = (int)dsum;
-            tl[5 * i] = (long long)w.w0 * hop; tl[5 * i + 1] = (long long)F * hop; tl[5 * i + 2] = w.jl0; tl[5 * i + 3] = w.jl1; tl[5 * i + 4] = slim ? rsum : dsum;
-            tm[7 * i] = srs ? rsum : (long long)Wtot * hop; tm[7 * i + 1] = srs ? w.jl0 : (long long)w.w0 * hop;
-            tm[7 * i + 2] = srs ? nrs : (long long)wlen * hop; tm[7 * i + 3] = w.Nout;
-            tm[7 * i + 4] = w.j0; tm[7 * i + 5] = w.j1; tm[7 * i + 6] = dsum;
-            rsum += nrs; max_rs = std::max(max_rs, nrs);
-            wj0[i] = w.j0; wn[i] = nout; wdst[i] = dsum;
-            dsum += nout; max_out = std::max(max_out, nout);
-            Wtot += wlen; maxW = std::max<int>(maxW, (int)wlen);
+            const JsWin& w = jt.win[i];
+            ti[i] = offF[w.b] + (int)w.w0; ti[nw + i] = (int)w.coff; ti[2 * nw + i] = (int)(w.w1 - w.w0); ti[3 * nw + i] = c.mix ? w.b : sidv[w.b];
+            ti[4 * nw + i] = 0; ti[5 * nw + i] = 0;
+            for (int q = 0; q < 5; q++) tl[5 * i + q] = 0;
+            tl[5 * i] = w.w0 * hop; tl[5 * i + 1] = (long long)lenF[w.b] * hop;        // (the gain kernel: the window's first sample in its sentence)
+            for (int q = 0; q < 7; q++) tm[7 * i + q] = 0;
         }
-        ti[6 * nw] = (int)dsum;
-        if (c.gain) { int* tu = (int*)(ht + stream_tab_utt_off(nw)); for (int i = 0; i < nw; i++) tu[i] = wb[i]; }     // (the gain kernel: each window's utterance)
-        HIPCK(hipMemcpyAsync(c.d_win, ht, stream_tab_bytes(nw, c.gain), hipMemcpyHostToDevice, stream));
-        // one utterance: its window by value (no table load in the decoder's kernels); several: the tables, also while one window is live
-        int rc = B == 1 ? run_decode(c, 1, Wtot, maxW, ti[0], ti[2]) : run_decode(c, nw, Wtot, maxW, 0, -1);
-        if (rc != STS_OK) return rc;
-        // (run_decode ran the chain up to the gain plan on the windows at their absolute positions)
+        ti[6 * nw] = 0;
+        if (c.gain) { int* tu = (int*)(ht + stream_tab_utt_off(nw)); for (int i = 0; i < nw; i++) tu[i] = jt.win[i].b; }
+        const size_t joff = join_stream_tab_j_off(nw, c.gain);
+        long long* jr = (long long*)(ht + joff); long long* jm = jr + 5; long long* jw = jm + 7;
+        const long long u0 = jt.g0 * hop, ulen = (jt.g1 - jt.g0) * hop, nrs = jt.jl1 - jt.jl0, nout = jt.j1 - jt.j0;
+        jr[0] = u0; jr[1] = NJ; jr[2] = jt.jl0; jr[3] = jt.jl1; jr[4] = 0;
+        jm[0] = 0; jm[1] = srs ? jt.jl0 : u0; jm[2] = srs ? nrs : ulen; jm[3] = out_count(NJ); jm[4] = jt.j0; jm[5] = jt.j1; jm[6] = 0;
+        for (int i = 0; i < nw; i++) { const JsRow& r = jrows[i]; jw[5 * i] = r.st; jw[5 * i + 1] = r.en; jw[5 * i + 2] = r.S; jw[5 * i + 3] = r.N; jw[5 * i + 4] = r.xoff; }
+        HIPCK(hipMemcpyAsync(c.d_win, ht, join_stream_tab_bytes(nw, c.gain), hipMemcpyHostToDevice, stream));
+        if (nw > 0) {
+            const int rc = B == 1 ? run_decode(c, 1, (long)jt.Wtot, (int)jt.maxW, ti[0], ti[2]) : run_decode(c, nw, (long)jt.Wtot, (int)jt.maxW, 0, -1);
+            if (rc != STS_OK) return rc;
+        }
+        JoinWinArgs j{};
+        j.x = c.stage_out(oc.src[OS_JOIN]); j.y = bf.wave_join; j.pcm = oc.writer == OS_JOIN ? dst : nullptr;
+        j.rows = (const long long*)(bf.stab + joff) + 12;
+        j.nw = nw; j.hop = hop; j.h = join_h;
+        j.g0 = u0; j.g1 = jt.g1 * hop; j.k0 = jt.f0 * hop; j.k1 = jt.f1 * hop;
+        join_window_run(j, stream);
         if (srs) {
             ResampleArgs a{};
-            a.x = c.stage_out(oc.src[OS_RESAMPLE]); a.seg = SegView{c.d_win + nw, c.d_win + 2 * nw, hop, 0, 0, 0};
+            a.x = bf.wave_join; a.seg = SegView{nullptr, nullptr, hop, 0, 0, (int)(jt.g1 - jt.g0)};
             a.table = d_rs_table; a.P = rs.P; a.Q = rs.Q; a.K = rs.K;
             a.pcm = oc.writer == OS_RESAMPLE ? dst : bf.pcm_rs; a.wave_out = bf.wave_out;
-            a.wtab = (const long long*)(bf.stab + stream_tab_ll_off(nw));
-            resample_pcm(a, nw, max_rs, stream);
-        } else if (pack) {
-            stream_pack(bf.pcm, dst, c.d_win + 4 * nw, c.d_win + 5 * nw, nw, max_out, stream);
+            a.wtab = (const long long*)(bf.stab + joff);
+            resample_pcm(a, 1, nrs, stream);
         }
-        if (slim) {          // every window of the step in one launch; it writes the packed chunks in place of the resampler / the pack
+        if (slim) {
             LimArgs a{};
             a.x = c.stage_out(oc.src[OS_LIMIT]);
             a.H = ld.H; a.c = ld.c; a.G = ld.G;
             a.pcm = dst;
-            a.wtab = (const long long*)(bf.stab + stream_tab_lim_off(nw));
-            limiter_run(a, nw, max_out, stream);
+            a.wtab = (const long long*)(bf.stab + joff) + 5;
+            limiter_run(a, 1, nout, stream);
         }
-        // (nothing packed: the one window's kept samples, at its pack source in the decoder's own PCM)
-        const int16_t* const src = oc.chunk_in_place ? bf.pcm + ti[4 * nw] : dst;
+        wj0.assign(1, jt.j0); wn.assign(1, nout); wdst.assign(1, 0);
+        *dsum_out = nout;
+        return STS_OK;
+    };
+    const long jsteps = joined ? (long)c.js.steps() : 0;
+    for (long k = 0;; k++) {
+        const long f0 = k * Cf;
+        wb.clear();
+        if (joined) { if (k < jsteps && live[0]) wb.push_back(0); }
+        else for (int b = 0; b < B; b++) if (live[b] && f0 < lenF[b]) wb.push_back(b);
+        const int nw = (int)wb.size();
+        if (nw == 0) break;
+        long long dsum = 0;                                 // samples of the step's chunks, packed
+        const int16_t* src = dst;                           // where they are on the device
+        if (joined) {       // (here nw == 1 is the one signal J; the step's decode windows and tables are joined_step's own)
+            const int rc = joined_step(k, &dsum);
+            if (rc != STS_OK) return rc;
+        } else {
+            int* ti = (int*)ht;
+            long long* tl = (long long*)(ht + stream_tab_ll_off(nw));
+            long long* tm = (long long*)(ht + stream_tab_lim_off(nw));
+            long long rsum = 0;                             // limiter: the resampler's float outputs of the widened ranges, packed
+            wj0.assign(nw, 0); wn.assign(nw, 0); wdst.assign(nw, 0);
+            long Wtot = 0; int maxW = 0; long long max_out = 0, max_rs = 0;
+            for (int i = 0; i < nw; i++) {
+                const int b = wb[i];
+                const long F = lenF[b];
+                const Win w = window(F, f0);
+                const long wlen = w.w1 - w.w0;
+                const long long nrs = w.jl1 - w.jl0, nout = w.j1 - w.j0;
+                ti[i] = offF[b] + (int)w.w0; ti[nw + i] = (int)Wtot; ti[2 * nw + i] = (int)wlen; ti[3 * nw + i] = c.mix ? b : sidv[b];      // (a mixed run: the window's utterance, a column of bt.g)
+                ti[4 * nw + i] = (int)((Wtot + (f0 - w.w0)) * hop); ti[5 * nw + i] = (int)dsum;
+                tl[5 * i] = (long long)w.w0 * hop; tl[5 * i + 1] = (long long)F * hop; tl[5 * i + 2] = w.jl0; tl[5 * i + 3] = w.jl1; tl[5 * i + 4] = slim ? rsum : dsum;
+                tm[7 * i] = srs ? rsum : (long long)Wtot * hop; tm[7 * i + 1] = srs ? w.jl0 : (long long)w.w0 * hop;
+                tm[7 * i + 2] = srs ? nrs : (long long)wlen * hop; tm[7 * i + 3] = w.Nout;
+                tm[7 * i + 4] = w.j0; tm[7 * i + 5] = w.j1; tm[7 * i + 6] = dsum;
+                rsum += nrs; max_rs = std::max(max_rs, nrs);
+                wj0[i] = w.j0; wn[i] = nout; wdst[i] = dsum;
+                dsum += nout; max_out = std::max(max_out, nout);
+                Wtot += wlen; maxW = std::max<int>(maxW, (int)wlen);
+            }
+            ti[6 * nw] = (int)dsum;
+            if (c.gain) { int* tu = (int*)(ht + stream_tab_utt_off(nw)); for (int i = 0; i < nw; i++) tu[i] = wb[i]; }     // (the gain kernel: each window's utterance)
+            HIPCK(hipMemcpyAsync(c.d_win, ht, stream_tab_bytes(nw, c.gain), hipMemcpyHostToDevice, stream));
+            // one utterance: its window by value (no table load in the decoder's kernels); several: the tables, also while one window is live
+            int rc = B == 1 ? run_decode(c, 1, Wtot, maxW, ti[0], ti[2]) : run_decode(c, nw, Wtot, maxW, 0, -1);
+            if (rc != STS_OK) return rc;
+            // (run_decode ran the chain up to the gain plan on the windows at their absolute positions)
+            if (srs) {
+                ResampleArgs a{};
+                a.x = c.stage_out(oc.src[OS_RESAMPLE]); a.seg = SegView{c.d_win + nw, c.d_win + 2 * nw, hop, 0, 0, 0};
+                a.table = d_rs_table; a.P = rs.P; a.Q = rs.Q; a.K = rs.K;
+                a.pcm = oc.writer == OS_RESAMPLE ? dst : bf.pcm_rs; a.wave_out = bf.wave_out;
+                a.wtab = (const long long*)(bf.stab + stream_tab_ll_off(nw));
+                resample_pcm(a, nw, max_rs, stream);
+            } else if (pack) {
+                stream_pack(bf.pcm, dst, c.d_win + 4 * nw, c.d_win + 5 * nw, nw, max_out, stream);
+            }
+            if (slim) {          // every window of the step in one launch; it writes the packed chunks in place of the resampler / the pack
+                LimArgs a{};
+                a.x = c.stage_out(oc.src[OS_LIMIT]);
+                a.H = ld.H; a.c = ld.c; a.G = ld.G;
+                a.pcm = dst;
+                a.wtab = (const long long*)(bf.stab + stream_tab_lim_off(nw));
+                limiter_run(a, nw, max_out, stream);
+            }
+            // (nothing packed: the one window's kept samples, at its pack source in the decoder's own PCM)
+            if (oc.chunk_in_place) src = bf.pcm + ti[4 * nw];
+        }
         if (!stream_direct) HIPCK(hipMemcpyAsync(hp, src, (size_t)dsum * 2, hipMemcpyDeviceToHost, stream));
         HIPCK(hipStreamSynchronize(stream));
         if (conv_math == 3 && ((ovf_host_ && *(volatile unsigned*)ovf_host_ != 0u) || (stream_retry_step >= 0 && k == stream_retry_step))) {
@@ -1592,6 +1677,16 @@ int Engine::run_batch_stream(int B, const int32_t* const* ids, const int32_t* n,
     StreamSpec ss{chunk_frames, cb, user, got.data()};
     const int rc = run(B, ids, n, sid, ls, &ss);
     if (rc == STS_OK && n_total) for (int b = 0; b < B; b++) n_total[b] = got[b];
+    return rc;
+}
+
+int Engine::run_joined_stream(int B, const int32_t* const* ids, const int32_t* n, const int32_t* sid, const float* ls, const sts_join* join,
+                              int chunk_frames, int (*cb)(void*, int32_t, const int16_t*, int32_t, int32_t), void* user, int32_t* n_total) {
+    if (B < 1 || !ids || !n || chunk_frames <= 0 || !cb) return fail(STS_EINVAL, "a joined stream takes B >= 1 sentences, a positive chunk size and a callback");
+    int32_t got = 0;
+    StreamSpec ss{chunk_frames, cb, user, &got};
+    const int rc = run_joined(B, ids, n, sid, ls, join, &ss);
+    if (rc == STS_OK && n_total) *n_total = got;
     return rc;
 }
 

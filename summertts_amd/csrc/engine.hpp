@@ -142,7 +142,7 @@ public:
     // last_join_start: sentence starts of the last run in native samples (empty: it was not a joined run)
     bool join_on = false; std::vector<int32_t> join_sil; long long join_total_sil = 0; int join_h = 0;
     std::vector<int64_t> last_join_start;
-    int run_joined(int B, const int32_t* const* ids, const int32_t* n, const int32_t* sid, const float* ls, const sts_join* join);
+    int run_joined(int B, const int32_t* const* ids, const int32_t* n, const int32_t* sid, const float* ls, const sts_join* join, const StreamSpec* ss = nullptr);
     int join_offsets(int64_t* start, int64_t capacity);
     // phoneme start offsets of the last run in output samples, packed like durations_h (sts_get_phoneme_offsets); last_n: its phoneme counts
     std::vector<int32_t> last_n;
@@ -252,6 +252,11 @@ public:
     // tables are built and uploaded by the first run after a change of the bands or the output rate (eq_prepare), not per call
     int eq_n = 0; sts_eq_band eq_bands[STS_EQ_MAX_BANDS] = {};
     int set_eq(int n_bands, const sts_eq_band* bands);
+    // a joined stream (sts_infer_ids_joined_stream): run_joined with a StreamSpec -- front and flow once as the packed batch, then
+    // run_stream_steps walks the JOINED time axis (join_stream.hpp): the callback's utterance is always 0, a non-zero return ends the call.
+    // n_total (optional): samples delivered
+    int run_joined_stream(int B, const int32_t* const* ids, const int32_t* n, const int32_t* sid, const float* ls, const sts_join* join,
+                          int chunk_frames, int (*cb)(void*, int32_t, const int16_t*, int32_t, int32_t), void* user, int32_t* n_total);
 };
 
 }  // namespace sts

@@ -502,6 +502,17 @@ struct JoinArgs {
 };
 // one launch: ceil(NJ / span) workgroups, each owning a contiguous span of J (silence included: no memset)
 void join_run(const JoinArgs& a, hipStream_t st);
+// The windowed join (a joined stream's step, sts_join_apply_range): the samples [g0, g1) of J from a step's decoded windows
+struct JoinWinArgs {
+    const float* x;                      // the step's decoded windows, packed compactly (16-byte aligned)
+    float* y;                            // J[g0, g1) at y[i - g0], optional (16-byte aligned)
+    int16_t* pcm;                        // the cast of the kept samples [k0, k1) at pcm[i - k0], optional (8-byte aligned)
+    const long long* rows;               // [nw][5] = {st, en, S, N, xoff} (join_stream.hpp JsRow), ascending, device memory
+    int nw, hop, h;                      // rows (0: only silence), samples per frame, fade length in samples
+    long long g0, g1, k0, k1;            // samples of J; multiples of hop, g0 <= k0 <= k1 <= g1
+};
+// one launch: ceil((g1 - g0) / span) workgroups, each owning a contiguous span (silence included: no memset)
+void join_window_run(const JoinWinArgs& a, hipStream_t st);
 
 // Parametric equaliser (eq.hip; the definition is there and in include/summertts_hip.h sts_set_eq)
 constexpr int kEqMinRate = 8000, kEqMaxRate = 48000, kEqMaxBands = STS_EQ_MAX_BANDS, kEqDim = 2 * kEqMaxBands, kEqPow = 9;

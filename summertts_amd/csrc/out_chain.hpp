@@ -3,7 +3,8 @@
 // The stages, in their fixed order: tail, gain, join, resample, pack, eq, loud, limit.  A running stage reads the float output of the
 // nearest running stage in front of it that has one, and the last running stage that can cast to int16 writes the PCM the caller
 // gets; every other int16 result goes to scratch.  A streaming run decodes tail and gain per step and runs resample / pack / limit on
-// each step's windows; eq and loud never run in one (the engine refuses those calls).
+// each step's windows; eq and loud never run in one (the engine refuses those calls).  A joined stream (sts_infer_ids_joined_stream) joins
+// each step's windows into a window of the ONE signal J: pack never runs, and the join is the writer when nothing runs behind it.
 #pragma once
 
 namespace sts {
@@ -31,7 +32,7 @@ inline OutChain plan_out_chain(const OutFacts& f) {
     OutChain p{};
     const bool whole = !f.stream;
     p.run[OS_TAIL] = true; p.run[OS_GAIN] = f.gain; p.run[OS_JOIN] = f.join; p.run[OS_RESAMPLE] = f.resample;
-    p.run[OS_PACK] = f.stream && !f.resample && !f.limit && (f.B > 1 || f.stream_direct);
+    p.run[OS_PACK] = f.stream && !f.join && !f.resample && !f.limit && (f.B > 1 || f.stream_direct);
     p.run[OS_EQ] = f.eq && whole; p.run[OS_LOUD] = f.loud_mode != 0 && whole; p.run[OS_LIMIT] = f.limit;
     const bool normalise = p.run[OS_LOUD] && f.loud_mode == 2;
     int cur = -1;           // the current float signal
@@ -49,7 +50,7 @@ inline OutChain plan_out_chain(const OutFacts& f) {
     p.pcm_nat = p.writer != OS_TAIL; p.pcm_rs = p.run[OS_RESAMPLE] && p.writer != OS_RESAMPLE;
     p.loud_cast = p.writer == OS_LOUD; p.loud_no_clamp = p.run[OS_LIMIT]; p.lim_gloud = normalise;
     p.lws = p.run[OS_LOUD]; p.limws = p.run[OS_LIMIT] && whole; p.spack = p.run[OS_PACK] && f.B > 1; p.stab = f.stream;
-    p.chunk_in_place = f.stream && !p.run[OS_RESAMPLE] && !p.run[OS_LIMIT] && !p.run[OS_PACK];
+    p.chunk_in_place = f.stream && !f.join && !p.run[OS_RESAMPLE] && !p.run[OS_LIMIT] && !p.run[OS_PACK];
     return p;
 }
 

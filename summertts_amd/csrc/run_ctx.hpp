@@ -3,6 +3,7 @@
 #pragma once
 #include "engine.hpp"
 #include "out_chain.hpp"
+#include "join_stream.hpp"
 
 namespace sts {
 
@@ -53,6 +54,10 @@ static inline size_t stream_tab_lim_off(int nw) { return stream_tab_ll_off(nw) +
 // a run with a gain plan: behind those, each window's utterance as ints [nw] (GainArgs::utt)
 static inline size_t stream_tab_utt_off(int nw) { return stream_tab_lim_off(nw) + (size_t)nw * 7 * 8; }
 static inline size_t stream_tab_bytes(int nw, bool gain = false) { return stream_tab_utt_off(nw) + (gain ? (size_t)nw * 4 : 0); }
+// a joined stream: the same tables for the step's nw decode windows, and from the next 8-byte boundary the ONE window of J for the
+// resampler (long long [5]) and the limiter (long long [7]), then the windowed join's rows, long long [nw][5] (join_stream.hpp JsRow)
+static inline size_t join_stream_tab_j_off(int nw, bool gain) { return (stream_tab_bytes(nw, gain) + 7) & ~(size_t)7; }
+static inline size_t join_stream_tab_bytes(int nw, bool gain) { return join_stream_tab_j_off(nw, gain) + (size_t)(12 + 5 * (size_t)nw) * 8; }
 
 // Everything a run's stages share: batch geometry, workspace pointers, host / device tables.  Engine::run() fills it stage by
 // stage; the stage functions below see its fields under the names the pipeline has always used (RUN_ALIASES).
@@ -91,6 +96,8 @@ struct Engine::RunCtx {
         const float* const o[OS_COUNT] = {bf.wave, bf.wave_gain, bf.wave_join, bf.wave_out, nullptr, bf.wave_eq, nullptr, bf.wave_lim};
         return s < 0 ? nullptr : o[s];
     }
+    // (behind everything else) a joined stream: its step geometry, made when the frame counts arrive
+    JsPlan js;
 };
 #define RUN_ALIASES(c)                                                                                                              \
     [[maybe_unused]] Model& M = model;                                                                                              \

@@ -295,6 +295,10 @@ def load_library() -> C.CDLL:
     lib.sts_join_check.argtypes = [C.c_int32, C.c_void_p]
     lib.sts_join_layout.argtypes = [C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int32)]
     lib.sts_join_apply.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.sts_join_apply_range.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p,
+                                         C.c_void_p]
+    lib.sts_infer_ids_joined_stream.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
+                                                CHUNK_CB, C.c_void_p, C.c_void_p]
     lib.sts_infer_ids_joined.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                          C.POINTER(C.POINTER(C.c_int16)), C.POINTER(C.c_int32)]
     lib.sts_get_join_offsets.argtypes = [C.c_void_p, C.c_void_p, C.c_int64]
@@ -346,6 +350,7 @@ EXPORTED_SYMBOLS = [
     "sts_multi_set_gain_plan",
     "sts_debug_spline_step", "sts_debug_attention", "sts_debug_layer_norm",
     "sts_join_check", "sts_join_layout", "sts_join_apply", "sts_infer_ids_joined", "sts_get_join_offsets", "sts_pool_submit_joined",
+    "sts_infer_ids_joined_stream", "sts_join_apply_range",
     "sts_set_eq", "sts_get_eq", "sts_eq_check", "sts_eq_design", "sts_eq_apply", "sts_pool_set_eq", "sts_multi_set_eq",
 ]
 
@@ -468,6 +473,27 @@ def join_apply(signals, frames: Sequence[int], samples_per_frame: int, join=None
     _check(lib, lib.sts_join_apply(int(device), x.ctypes.data, f.ctypes.data, f.size, int(samples_per_frame), jp, y.ctypes.data,
                                    pcm.ctypes.data))
     return y[:total], pcm[:total]
+
+
+def join_apply_range(signals, frames: Sequence[int], samples_per_frame: int, first_frame: int, n_frames: int, join=None, device: int = 0):
+    """The windowed join kernel of a joined stream on caller signals (sts_join_apply_range): the frames ``[first_frame, first_frame +
+    n_frames)`` of the joined signal -> (J part, pcm part).  ``signals`` / ``frames`` / ``join`` as ``join_apply`` takes them."""
+    lib = load_library()
+    f = np.ascontiguousarray(frames, dtype=np.int32).ravel()
+    sig = [np.ascontiguousarray(x, dtype=np.float32).ravel() for x in signals]
+    if len(sig) != f.size:
+        raise ValueError("one signal per sentence")
+    for b, x in enumerate(sig):
+        if x.size != int(f[b]) * int(samples_per_frame):
+            raise ValueError(f"signal {b} needs frames * samples_per_frame = {int(f[b]) * int(samples_per_frame)} samples")
+    jp, keep = _join(f.size, join)
+    x = np.concatenate(sig) if sig else np.zeros(1, np.float32)
+    count = max(int(n_frames), 0) * int(samples_per_frame)
+    y = np.zeros(max(count, 1), np.float32)
+    pcm = np.zeros(max(count, 1), np.int16)
+    _check(lib, lib.sts_join_apply_range(int(device), x.ctypes.data, f.ctypes.data, f.size, int(samples_per_frame), jp, int(first_frame),
+                                         int(n_frames), y.ctypes.data, pcm.ctypes.data))
+    return y[:count], pcm[:count]
 
 
 def debug_spline_step(h, filter_sqrt: float, r0=None, r1=None, device: int = 0, o0=None, o1=None):
@@ -862,6 +888,28 @@ class Synthesizer:
         pcm = np.ctypeslib.as_array(out, shape=(n.value,)).copy() if n.value else np.zeros(0, np.int16)
         self.lib.sts_free(out)
         return pcm
+
+    def infer_joined_stream(self, ids, chunk_frames: int, sid=None, length_scale=None, join=None, on_chunk=None):
+        """A paragraph, streamed (include/summertts_hip.h sts_infer_ids_joined_stream): the joined signal of ``infer_joined`` in chunks of
+        ``chunk_frames`` frames of the JOINED time axis, in order.  ``on_chunk(pcm: np.int16[], sample_offset, t_seconds)`` is called per
+        chunk (return True to end the call).  Returns the list of ``(sample_offset, pcm)``; ``self.stream_total`` holds the library's count
+        of delivered samples."""
+        import time
+        p = ids if isinstance(ids, PreparedBatch) else PreparedBatch(ids, sid, length_scale)
+        jp, keep = _join(p.B, join)
+        out = []
+        t0 = time.perf_counter()
+
+        def _cb(user, pcm, ns, off):
+            arr = np.ctypeslib.as_array(pcm, shape=(ns,)).copy() if ns else np.zeros(0, np.int16)
+            out.append((int(off), arr))
+            return 1 if (on_chunk and on_chunk(arr, int(off), time.perf_counter() - t0)) else 0
+        cb = CHUNK_CB(_cb)
+        total = C.c_int32()
+        _check(self.lib, self.lib.sts_infer_ids_joined_stream(self.h, p.B, p.ptrs, p.n_p, p.sid_p, p.ls_p, jp, int(chunk_frames), cb, None,
+                                                              C.byref(total)))
+        self.stream_total = int(total.value)
+        return out
 
     def join_offsets(self, B: int) -> np.ndarray:
         """Start of every sentence of the last ``infer_joined`` in output samples at the current output rate (sts_get_join_offsets)."""

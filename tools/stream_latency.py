@@ -11,6 +11,13 @@ the utterances (min / p50 / max), time to the last chunk, and seconds of audio d
 timed repeats after one warm-up of every shape.  The launch-ahead memo is off, so (c) waits for its frame counts as (a) and (b) do.
 --rate R: PCM at R Hz (sts_set_output_rate).  --direct 1: the batched stream's step output goes to mapped pinned memory (sts_debug_set STS_DBG_STREAM_DIRECT) instead of one
 download.  Prints one JSON line per row.
+
+--joined: a paragraph instead -- --sentences sentences (default 32) of 64 to 256 phonemes joined with gaps of 8 frames and
+a 5 ms fade, three ways:
+  (a) joined_stream   one sts_infer_ids_joined_stream (chunks of the ONE joined signal, in order)
+  (b) serial_streams  the sentences as sts_infer_ids_stream calls one after another (no batch for the front and the flow, no join)
+  (c) whole_joined    one sts_infer_ids_joined (the reader hears the paragraph when all of it is done)
+Per (model, chunk, form): time to the first and to the last chunk, seconds of audio per wall second.
 """
 from __future__ import annotations
 
@@ -54,6 +61,29 @@ def _batch(syn, ids, chunk):
     return [t] * len(ids), t, sum(p.size for p in pcm), t
 
 
+JOIN = {"lead_frames": 0, "trail_frames": 0, "fade_ms": 5.0}
+
+
+def _paragraph(cfg, n):
+    lens = [64 + (97 * u * u + 31 * u) % 193 for u in range(n)]               # 64 .. 256 phonemes
+    return [sb.synthetic_ids(t, cfg.vocab, salt=u) for u, t in enumerate(lens)]
+
+
+def _joined_stream(syn, ids, chunk):
+    got = []
+    t0 = time.perf_counter()
+    chunks = syn.infer_joined_stream(ids, chunk, join=dict(JOIN, gap_frames=[8] * (len(ids) - 1)),
+                                     on_chunk=lambda pcm, off, t: got.append(time.perf_counter() - t0) and False)
+    return [got[0]], got[-1], sum(p.size for _, p in chunks), time.perf_counter() - t0
+
+
+def _whole_joined(syn, ids, chunk):
+    t0 = time.perf_counter()
+    pcm = syn.infer_joined(ids, join=dict(JOIN, gap_frames=[8] * (len(ids) - 1)))
+    t = time.perf_counter() - t0
+    return [t], t, pcm.size, t
+
+
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--models", default="hifigan_sdp,mbb_fix")
@@ -63,8 +93,13 @@ def main() -> None:
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--direct", type=int, default=0)
     ap.add_argument("--rate", type=int, default=0, help="output sample rate (0: the native 16 kHz)")
+    ap.add_argument("--joined", action="store_true", help="a paragraph: joined stream against the whole joined call and single streams in turn")
+    ap.add_argument("--sentences", type=int, default=32)
     a = ap.parse_args()
     forms = {"batched_stream": _batched, "serial_streams": _serial, "one_batch": _batch}
+    if a.joined:
+        forms = {"joined_stream": _joined_stream, "serial_streams": _serial, "whole_joined": _whole_joined}
+        a.batches = str(a.sentences)
     for kind in a.models.split(","):
         cfg = sb.full_cfg(kind)
         syn = engine.Synthesizer(sb.make_blob(cfg, 1234))
@@ -73,15 +108,15 @@ def main() -> None:
         syn.set_output_rate(a.rate)
         rate = syn.output_rate()
         for B in [int(v) for v in a.batches.split(",")]:
-            ids = [sb.synthetic_ids(a.phonemes, cfg.vocab, salt=u) for u in range(B)]
+            ids = _paragraph(cfg, B) if a.joined else [sb.synthetic_ids(a.phonemes, cfg.vocab, salt=u) for u in range(B)]
             for chunk in [int(v) for v in a.chunks.split(",")]:
                 for name, fn in forms.items():
-                    if name == "one_batch" and chunk != int(a.chunks.split(",")[0]):
+                    if name in ("one_batch", "whole_joined") and chunk != int(a.chunks.split(",")[0]):
                         continue                                  # (does not depend on the chunk size)
                     fn(syn, ids, chunk)                           # warm-up of this shape
                     runs = [fn(syn, ids, chunk) for _ in range(a.reps)]
                     med = lambda v: float(np.median(v))            # noqa: E731
-                    row = {"model": kind, "B": B, "chunk_frames": chunk if name != "one_batch" else None, "form": name,
+                    row = {"model": kind, "B": B, "chunk_frames": chunk if name not in ("one_batch", "whole_joined") else None, "form": name,
                            "first_ms_min": med([min(r[0]) * 1e3 for r in runs]),
                            "first_ms_p50": med([np.median(r[0]) * 1e3 for r in runs]),
                            "first_ms_max": med([max(r[0]) * 1e3 for r in runs]),
