@@ -489,8 +489,9 @@ int sts_join_apply_range(int device, const float* x, const int32_t* frames, int3
  * rate; after sts_infer_ids_joined it sees the ONE joined signal.  With nothing downstream (loudness mode 0 or 1, limiter off) the EQ
  * kernel writes the PCM itself; loudness and the limiter read the EQ's float output.  Tap "wave_eq": that output ("wave", "wave_gain",
  * "wave_join", "wave_out" stay the signals in front of it).
- * Streaming (sts_infer_ids_stream, sts_infer_ids_batch_stream, sts_pool_submit_stream) answers STS_EINVAL while an EQ is set: an IIR has
- * no finite halo, and a state carried from chunk to chunk would make the PCM depend on the chunking. */
+ * Streaming (sts_infer_ids_stream, sts_infer_ids_batch_stream, sts_infer_ids_joined_stream, sts_pool_submit_stream) answers STS_EINVAL
+ * while an EQ is set: an IIR has no finite halo, and the sequential state carried from chunk to chunk would make the PCM depend on the
+ * chunking -- unless sts_set_eq_streaming (below) is on. */
 #define STS_EQ_MAX_BANDS 4
 #define STS_EQ_PEAK 1
 #define STS_EQ_LOWSHELF 2
@@ -509,6 +510,32 @@ int sts_eq_design(int32_t rate, int32_t n_bands, const sts_eq_band* bands, doubl
  * NULL.  (On the device both start out as NaN / 0x7FFF, so a sample the kernels left out shows.) */
 int sts_eq_apply(int device, const float* x, const int64_t* lengths, int32_t B, int32_t rate, int32_t n_bands,
                  const sts_eq_band* bands, float* y, int16_t* pcm);
+/* ---- the equaliser in a stream (ABI number unchanged).  sts_set_eq_streaming(e, 1) lets every streaming call run while bands are set;
+ * 0 (default) keeps the refusal above.  The switch persists until changed; it has no effect without bands or in a whole-utterance call
+ * (with it off, or without bands, a stream allocates, uploads and launches exactly what it always did).  sts_get_eq_streaming returns
+ * it (0 for a null engine).  Streaming under loudness mode 1 or 2 stays refused, and sts_stream_halo_frames does not change: an IIR needs
+ * no look-ahead, and the carried state replaces the look-back.
+ *   Definition: in a streaming call the signal of utterance b (of a joined stream: the one signal J) is y of step 2 above, the float64
+ *   DF-I cascade from zero state over the ENTIRE utterance at the output rate, evaluated in eq.hip's fixed order -- chunks of 32
+ *   samples, tiles of 8192, both anchored at the utterance's first sample.  Each callback delivers its range of that y: cast, or limited
+ *   and then cast.  The carry-in of a chunk depends only on its tile's carry and on the chunks in front of it in that tile, so the
+ *   engine keeps, per utterance, the open tile's carry and input (and the last y the limiter's window reaches back into) and continues
+ *   from there: the concatenated chunks are the PCM of the corresponding whole call (sts_infer_ids, sts_infer_ids_batch per utterance,
+ *   sts_infer_ids_joined) for EVERY chunk_frames -- bit for bit with the conv mode pinned, as for a stream without an EQ.  A step the
+ *   engine decodes twice (the split-bf16 repeat) starts both times from the same state. */
+int sts_set_eq_streaming(sts_engine* e, int enable);
+int sts_get_eq_streaming(const sts_engine* e);
+/* The stream-mode kernels on caller signals: signals, rate and bands as sts_eq_apply.  bounds[0 .. n_steps): ascending step boundaries,
+ * bounds[0] = 0, common to all utterances; step k covers [bounds[k], bounds[k+1]) (the last one: to the end), clipped to each length, and
+ * an utterance with lengths[b] <= bounds[k] takes no part in it.  back in [0, 2048]: step k presents the window
+ * [max(0, bounds[k] - back), min(lengths[b], bounds[k+1] + back)) -- what the limiter's widened range does in the engine; the input behind
+ * the previous window's end is consumed, the part in front of it is answered from the carried state.  y / pcm (each may be NULL): every
+ * step's [bounds[k], bounds[k+1]), packed like x.  win_y (may be NULL; win_capacity floats): every step's WHOLE window output, step by
+ * step and utterance by utterance, and win_off[k B + b] (may be NULL; n_steps x B entries) its offset there, -1 where the utterance takes
+ * no part.  (On the device outputs, state and workspace start out as NaN / 0x7FFF.) */
+int sts_eq_apply_chunked(int device, const float* x, const int64_t* lengths, int32_t B, int32_t rate, int32_t n_bands,
+                         const sts_eq_band* bands, const int64_t* bounds, int32_t n_steps, int32_t back, float* y, int16_t* pcm,
+                         float* win_y, int64_t win_capacity, int64_t* win_off);
 /*   record intermediate tensors of the next run: "x_enc","m","logs","logw","z_p","z","wave","wave_out" ("logs": the second half of the
  *   encoder projection, computed only by runs that record taps or sample the prior; "wave_out": the resampled float wave, only at a
  *   non-native output rate, one-pass calls; "dur_w": the planned duration weights, only a run with a duration plan; "wave_gain": the
@@ -729,8 +756,10 @@ int sts_pool_set_loudness(sts_pool* p, int mode, float target_lufs, float peak_d
  *   sts_pool_set_output_rate.  Streaming requests are limited chunk by chunk. */
 int sts_pool_set_limiter(sts_pool* p, int mode, float gain_db, float ceiling_dbfs, float lookahead_ms);
 /*   sts_pool_set_eq: sts_set_eq on every engine of the pool (one setting for every request; no per-request EQ).  STS_ESTATE while any
- *   request is outstanding.  While bands are set, sts_pool_submit_stream answers STS_EINVAL. */
+ *   request is outstanding.  While bands are set, sts_pool_submit_stream answers STS_EINVAL unless sts_pool_set_eq_streaming is on. */
 int sts_pool_set_eq(sts_pool* p, int32_t n_bands, const sts_eq_band* bands);
+/*   sts_pool_set_eq_streaming: sts_set_eq_streaming on every engine of the pool.  STS_ESTATE while any request is outstanding. */
+int sts_pool_set_eq_streaming(sts_pool* p, int enable);
 /*   sts_pool_submit_plan (ABI 14): sts_pool_submit_ex with this request's own duration plan (sts_set_duration_plan: rate and fixed hold n
  *   entries each or are NULL, target_frames 0 = none; an invalid plan answers STS_EINVAL).  Whole-utterance requests only.  Requests with and
  *   without a plan share one packed batch: the plan is per utterance. */

@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "engine.hpp"
+#include "eq_stream.hpp"
 #include "join_stream.hpp"
 
 using namespace sts;
@@ -875,6 +876,12 @@ int sts_get_eq(const sts_engine* e, int32_t* n_bands, sts_eq_band* bands, int32_
     for (int i = 0; bands && i < e->eng.eq_n && i < capacity; i++) bands[i] = e->eng.eq_bands[i];
     return STS_OK;
 }
+int sts_set_eq_streaming(sts_engine* e, int enable) {
+    if (!e) return set_err(STS_EINVAL, "null engine");
+    e->eng.eq_streaming = enable != 0;
+    return STS_OK;
+}
+int sts_get_eq_streaming(const sts_engine* e) { return e && e->eng.eq_streaming ? 1 : 0; }
 int sts_eq_check(int32_t rate, int32_t n_bands, const sts_eq_band* bands) {
     const char* why = nullptr;
     return eq_valid(rate, n_bands, bands, &why) ? STS_OK : set_err(STS_EINVAL, why);
@@ -930,6 +937,95 @@ int sts_eq_apply(int device, const float* x, const int64_t* lengths, int32_t B, 
              (!y || total == 0 || hipMemcpyAsync(y, dy, (size_t)total * 4, hipMemcpyDeviceToHost, st) == hipSuccess) &&
              (!pcm || total == 0 || hipMemcpyAsync(pcm, dp, (size_t)total * 2, hipMemcpyDeviceToHost, st) == hipSuccess) &&
              hipStreamSynchronize(st) == hipSuccess;
+    }
+    if (st) (void)hipStreamDestroy(st);
+    (void)hipFree(d);
+    return ok ? STS_OK : set_err(STS_EDEVICE, "the equaliser failed on the device");
+}
+int sts_eq_apply_chunked(int device, const float* x, const int64_t* lengths, int32_t B, int32_t rate, int32_t n_bands, const sts_eq_band* bands,
+                         const int64_t* bounds, int32_t n_steps, int32_t back, float* y, int16_t* pcm, float* win_y, int64_t win_capacity,
+                         int64_t* win_off) {
+    if (B < 1 || !lengths) return set_err(STS_EINVAL, "B >= 1 and lengths are required");
+    const char* why = nullptr;
+    if (!eq_valid(rate, n_bands, bands, &why)) return set_err(STS_EINVAL, why);
+    if (n_bands < 1) return set_err(STS_EINVAL, "eq: at least one band to apply");
+    if (n_steps < 1 || !bounds || bounds[0] != 0) return set_err(STS_EINVAL, "eq stream: at least one step boundary, the first one 0");
+    for (int k = 1; k < n_steps; k++)
+        if (bounds[k] <= bounds[k - 1]) return set_err(STS_EINVAL, "eq stream: the step boundaries must ascend");
+    if (back < 0 || 2 * (int64_t)back > kEqsHist) return set_err(STS_EINVAL, "eq stream: the overlap must be in [0, 2048]");
+    std::vector<int64_t> off(B + 1, 0);
+    int64_t maxl = 0;
+    for (int b = 0; b < B; b++) {
+        if (lengths[b] < 0 || lengths[b] > (int64_t)1 << 30) return set_err(STS_EINVAL, "lengths must be in [0, 2^30]");
+        off[b + 1] = off[b] + lengths[b]; maxl = std::max<int64_t>(maxl, lengths[b]);
+    }
+    const int64_t total = off[B];
+    if (total > (int64_t)1 << 30) return set_err(STS_EINVAL, "the signals must hold at most 2^30 samples in all");
+    if (total > 0 && !x) return set_err(STS_EINVAL, "null signal");
+    // every step's rows: the window [max(0, c_k - back), min(N_b, c_k+1 + back)) of every utterance with N_b > c_k, kept [c_k, min(N_b, c_k+1))
+    EqsTrack track; track.begin(B);
+    std::vector<EqsRow> rows; std::vector<int> row0(n_steps + 1, 0); std::vector<long long> tiles(n_steps, 1);
+    int64_t wtotal = 0; size_t ws = 0;
+    for (int k = 0; k < n_steps; k++) {
+        const int64_t c0 = bounds[k], c1 = k + 1 < n_steps ? bounds[k + 1] : INT64_MAX;
+        for (int b = 0; b < B; b++) {
+            if (win_off) win_off[(size_t)k * B + b] = -1;
+            const int64_t N = lengths[b];
+            if (N <= c0) continue;
+            const int64_t o0 = std::max<int64_t>(0, c0 - back), o1 = c1 > N - back ? N : c1 + back, j1 = std::min<int64_t>(N, c1);
+            const EqsRow r = track.row(b, off[b] + o0, o0, o1 - o0, o0, o1, wtotal, c0, j1, off[b] + c0);
+            if (const char* bad = eqs_row_check(r, N)) return set_err(STS_EINVAL, bad);
+            tiles[k] = std::max(tiles[k], eqs_tiles(r.e, r.o1));
+            if (win_off) win_off[(size_t)k * B + b] = wtotal;
+            wtotal += o1 - o0;
+            rows.push_back(r);
+        }
+        track.commit();
+        row0[k + 1] = (int)rows.size();
+        ws = std::max(ws, eqs_ws_bytes(row0[k + 1] - row0[k], tiles[k]));
+    }
+    if (win_y && wtotal > win_capacity) return set_err(STS_EINVAL, "eq stream: win_y is too small for the steps' windows");
+    double coef[5 * STS_EQ_MAX_BANDS];
+    eq_design(rate, n_bands, bands, coef);
+    EqTable tab;
+    eq_table(n_bands, coef, &tab);
+    if (hipSetDevice(device) != hipSuccess) return set_err(STS_EDEVICE, "no such device");
+    auto pad = [](size_t bytes) { return (bytes + 255) & ~(size_t)255; };
+    const size_t xb = pad((size_t)total * 4), tb = pad(sizeof(EqTable)), pb = pad((size_t)total * 2), yb = pad((size_t)wtotal * 4);
+    const size_t rb = pad(rows.size() * sizeof(EqsRow)), sb = pad(eqs_state_bytes(B)), wb = pad(ws);
+    char* d = nullptr;          // [x | tables | rows | window y | pcm | state | workspace]
+    if (hipMalloc((void**)&d, xb + tb + rb + yb + pb + sb + wb + 256) != hipSuccess) return set_err(STS_EDEVICE, "out of device memory");
+    hipStream_t st = nullptr;
+    bool ok = hipStreamCreate(&st) == hipSuccess;
+    char* dt = d + xb; char* dr = dt + tb; char* dy = dr + rb; char* dp = dy + yb; char* ds = dp + pb; char* dw = ds + sb;
+    // (outputs, state and workspace start out as NaN / 0x7FFF: a sample the kernels leave out, or a stale word they read, shows)
+    ok = ok && (total == 0 || hipMemcpyAsync(d, x, (size_t)total * 4, hipMemcpyHostToDevice, st) == hipSuccess) &&
+         hipMemcpyAsync(dt, &tab, sizeof(EqTable), hipMemcpyHostToDevice, st) == hipSuccess &&
+         (rows.empty() || hipMemcpyAsync(dr, rows.data(), rows.size() * sizeof(EqsRow), hipMemcpyHostToDevice, st) == hipSuccess) &&
+         (yb == 0 || hipMemsetAsync(dy, 0xFF, yb, st) == hipSuccess) &&
+         (pb == 0 || hipMemsetD16Async((hipDeviceptr_t)dp, 0x7FFF, pb / 2, st) == hipSuccess) &&
+         hipMemsetAsync(ds, 0xFF, sb + wb, st) == hipSuccess;
+    if (ok) {
+        EqArgs a{};
+        a.x = (const float*)d; a.S = n_bands; a.tab = (const EqTable*)dt;
+        a.y = (float*)dy; a.pcm = (int16_t*)dp; a.E = (double*)dw; a.state = ds;
+        int slot = 0;
+        for (int k = 0; k < n_steps; k++) {
+            const int nw = row0[k + 1] - row0[k];
+            if (nw == 0) continue;
+            a.wtab = (const long long*)(dr + (size_t)row0[k] * sizeof(EqsRow)); a.slot = slot;
+            eq_stream_run(a, nw, tiles[k], st);
+            slot ^= 1;
+        }
+        std::vector<float> hw((size_t)wtotal);
+        float* wdst = win_y ? win_y : hw.data();
+        ok = hipGetLastError() == hipSuccess &&
+             (wtotal == 0 || hipMemcpyAsync(wdst, dy, (size_t)wtotal * 4, hipMemcpyDeviceToHost, st) == hipSuccess) &&
+             (!pcm || total == 0 || hipMemcpyAsync(pcm, dp, (size_t)total * 2, hipMemcpyDeviceToHost, st) == hipSuccess) &&
+             hipStreamSynchronize(st) == hipSuccess;
+        if (ok && y)            // each step's kept range out of its window
+            for (const EqsRow& r : rows)
+                if (r.j1 > r.j0) memcpy(y + r.pdst, wdst + r.ybase + (r.j0 - r.o0), (size_t)(r.j1 - r.j0) * 4);
     }
     if (st) (void)hipStreamDestroy(st);
     (void)hipFree(d);

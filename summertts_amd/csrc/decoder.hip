@@ -509,7 +509,7 @@ int Engine::decode_end(RunCtx& c, const float* wave, const WinGeom& win, long Wt
         resample_pcm(a, nw, max_out, stream);
         cur = a.wave_out;
     }
-    if (oc.run[OS_EQ]) {
+    if (oc.run[OS_EQ] && whole) {       // (a stream: run_stream_steps runs its stream mode on each step's windows)
         // the equaliser on every utterance of the float signal at the output rate (two launches)
         EqArgs a{};
         signal(a);

@@ -986,7 +986,7 @@ int Engine::wait_frame_counts(RunCtx& c) {
 
 // the one place that decides the output chain of a run (out_chain.hpp), with the limiter's design and the resampler's ratio for it
 int Engine::plan_output(RunCtx& c) {
-    c.oc = plan_out_chain(OutFacts{c.ss != nullptr, c.B, resampling(), c.gain, c.join, eq_n > 0, loud_mode, lim_mode != 0, record_taps, stream_direct != 0});
+    c.oc = plan_out_chain(OutFacts{c.ss != nullptr, c.B, resampling(), c.gain, c.join, eq_n > 0, loud_mode, lim_mode != 0, record_taps, stream_direct != 0, eq_streaming});
     if (c.oc.run[OS_RESAMPLE]) { c.rsP = rs.P; c.rsQ = rs.Q; }
     c.eqS = eq_n;
     if (c.oc.run[OS_LIMIT] && !limiter_design(out_rate, lim_gain_db, lim_ceiling, lim_ms, &c.limd)) return fail(STS_EINVAL, "limiter: output rate outside [8000, 48000]");
@@ -1124,12 +1124,19 @@ int Engine::run_frame_workspace(RunCtx& c) {
         bf.limws = oc.limws ? A.get<char>((size_t)B * 16) : nullptr;
         bf.wave_lim = oc.wave[OS_LIMIT] ? A.get<float>((size_t)c.Ocap) : nullptr;
         bf.wave_eq = oc.wave[OS_EQ] ? A.get<float>((size_t)c.Ocap) : nullptr;
-        bf.eqws = oc.wave[OS_EQ] ? A.get<char>(eq_ws_bytes(B, c.Ocap)) : nullptr;
+        bf.eqws = oc.eqws ? A.get<char>(eq_ws_bytes(B, c.Ocap)) : nullptr;
         bf.stab = nullptr; bf.spack = nullptr; bf.gwin = bf.cond_win = nullptr;
         if (ss) {
-            bf.stab = A.get<char>(c.join ? join_stream_tab_bytes(B, c.gain) : stream_tab_bytes(B, c.gain));
+            bf.stab = A.get<char>(c.join ? join_stream_tab_bytes(B, c.gain, oc.eqst) : stream_tab_bytes(B, c.gain, oc.eqst));
             if (oc.spack) bf.spack = A.get<int16_t>((size_t)c.Ocap);
             if (M.dec_type == 0 && c.ms && c.bstream) { bf.gwin = A.get<float>((size_t)M.gin * B); bf.cond_win = A.get<float>((size_t)M.up_init * B); }
+        }
+        // (a stream that runs the EQ: behind everything else, so that every other buffer lies where it lies without it)
+        bf.eqst = nullptr; bf.eqsE = nullptr;
+        if (oc.eqst) {
+            const int nu = c.join ? 1 : B;
+            bf.eqst = A.get<char>(eqs_state_bytes(nu));
+            bf.eqsE = (double*)A.get<char>(eqs_ws_bytes(nu, eqs_max_tiles(c.Ocap)));
         }
     };
     arenaF_.measuring = true; layoutF(arenaF_);
@@ -1343,9 +1350,10 @@ int Engine::run_once(int B, const int32_t* const* ids, const int32_t* n, const i
     if (ss && loud_mode != 0)
         return fail(STS_EINVAL, "streaming is not available while loudness measurement or normalization is on (sts_set_loudness mode 0 first): "
                                 "normalizing needs the whole utterance before its first sample leaves");
-    if (ss && eq_n > 0)
+    if (ss && eq_n > 0 && !eq_streaming)
         return fail(STS_EINVAL, "streaming is not available while an equaliser is set (sts_set_eq with 0 bands first): an IIR has no finite "
-                                "halo, and a state carried from chunk to chunk would make the PCM depend on the chunking");
+                                "halo, and a state carried from chunk to chunk would make the PCM depend on the chunking -- unless the "
+                                "carried-state stream mode is switched on (sts_set_eq_streaming)");
     if (eq_n > 0) { const int rce = eq_prepare(); if (rce != STS_OK) return rce; }
     host_t0_ = now_us(); host_t_sync_ = 0;
     RunCtx c;
@@ -1484,7 +1492,8 @@ int Engine::run_stream_steps(RunCtx& c) {
     const std::vector<int> offF(p_offF, p_offF + B), lenF(p_lenF, p_lenF + B), sidv(c.p_sid, c.p_sid + B);
     const size_t hp_off = (up_bytes + ((size_t)Ttot + B) * 4 + 255) & ~(size_t)255;
     const bool joined = c.join;       // a joined stream: the steps walk J, one chunk of the ONE signal per step (join_stream.hpp)
-    const size_t tab_room = ((joined ? join_stream_tab_bytes(B, c.gain) : stream_tab_bytes(B, c.gain)) + 255) & ~(size_t)255;
+    const bool seq = c.oc.eqst;      // the EQ runs on every step's windows from its carried state (eq_stream.hpp)
+    const size_t tab_room = ((joined ? join_stream_tab_bytes(B, c.gain, seq) : stream_tab_bytes(B, c.gain, seq)) + 255) & ~(size_t)255;
     const size_t pcm_bytes = (size_t)c.Ocap * 2 + 256;
     if (!ensure_pinned(hp_off + tab_room + pcm_bytes)) return fail(STS_EDEVICE, "pinned host allocation failed");
     c.pm = (int*)pinned_;
@@ -1513,6 +1522,16 @@ int Engine::run_stream_steps(RunCtx& c) {
     if (ss->delivered) for (int b = 0; b < (joined ? 1 : B); b++) ss->delivered[b] = 0;
     d_pcm = nullptr; total_samples = 0;
     std::vector<int> wb; std::vector<long long> wj0, wn, wdst;
+    // the streamed EQ: how far each utterance (a joined stream: J) is consumed and which state slot a step reads; a step's rows join its
+    // table upload, its two launches follow the resampler, and the slots flip only behind a step that does not run again
+    EqsTrack eqt; eqt.begin(joined ? 1 : B);
+    auto eq_step = [&](const long long* rows_dev, int nw, long long tiles) {
+        EqArgs a{};
+        a.x = c.stage_out(oc.src[OS_EQ]); a.S = c.eqS; a.tab = d_eq_;
+        a.y = bf.wave_eq; a.pcm = oc.writer == OS_EQ ? dst : nullptr;
+        a.E = bf.eqsE; a.state = bf.eqst; a.slot = eqt.slot; a.wtab = rows_dev;
+        eq_stream_run(a, nw, tiles, stream);
+    };
     // The window of chunk frames [f0, f1) of an utterance of F frames: frames [w0, w1).  Its native samples [f0 hop, f1 hop) are, at the output
     // rate, the outputs j with ceil(f0 hop P / Q) <= j < ceil(f1 hop P / Q) = [j0, j1) of Nout (the halo covers the filter's K samples beyond the
     // chunk's edges too: stream_halo).  The limiter produces them from the float signal over [jl0, jl1) = [j0 - 2H, j1 + 2H) clipped to the
@@ -1553,9 +1572,17 @@ int Engine::run_stream_steps(RunCtx& c) {
         long long* jr = (long long*)(ht + joff); long long* jm = jr + 5; long long* jw = jm + 7;
         const long long u0 = jt.g0 * hop, ulen = (jt.g1 - jt.g0) * hop, nrs = jt.jl1 - jt.jl0, nout = jt.j1 - jt.j0;
         jr[0] = u0; jr[1] = NJ; jr[2] = jt.jl0; jr[3] = jt.jl1; jr[4] = 0;
-        jm[0] = 0; jm[1] = srs ? jt.jl0 : u0; jm[2] = srs ? nrs : ulen; jm[3] = out_count(NJ); jm[4] = jt.j0; jm[5] = jt.j1; jm[6] = 0;
+        jm[0] = 0; jm[1] = srs || seq ? jt.jl0 : u0; jm[2] = srs || seq ? nrs : ulen; jm[3] = out_count(NJ); jm[4] = jt.j0; jm[5] = jt.j1; jm[6] = 0;
         for (int i = 0; i < nw; i++) { const JsRow& r = jrows[i]; jw[5 * i] = r.st; jw[5 * i + 1] = r.en; jw[5 * i + 2] = r.S; jw[5 * i + 3] = r.N; jw[5 * i + 4] = r.xoff; }
-        HIPCK(hipMemcpyAsync(c.d_win, ht, join_stream_tab_bytes(nw, c.gain), hipMemcpyHostToDevice, stream));
+        const size_t eoff = join_stream_tab_eq_off(nw, c.gain);
+        long long etiles = 1;
+        if (seq) {           // (a silence-only step too: the EQ advances over the join's zeros)
+            const EqsRow r = eqt.row(0, 0, srs ? jt.jl0 : u0, srs ? nrs : ulen, jt.jl0, jt.jl1, 0, jt.j0, jt.j1, 0);
+            if (const char* bad = eqs_row_check(r, out_count(NJ))) return fail(STS_EDEVICE, bad);
+            memcpy(ht + eoff, &r, sizeof(r));
+            etiles = eqs_tiles(r.e, r.o1);
+        }
+        HIPCK(hipMemcpyAsync(c.d_win, ht, join_stream_tab_bytes(nw, c.gain, seq), hipMemcpyHostToDevice, stream));
         if (nw > 0) {
             const int rc = B == 1 ? run_decode(c, 1, (long)jt.Wtot, (int)jt.maxW, ti[0], ti[2]) : run_decode(c, nw, (long)jt.Wtot, (int)jt.maxW, 0, -1);
             if (rc != STS_OK) return rc;
@@ -1574,6 +1601,7 @@ int Engine::run_stream_steps(RunCtx& c) {
             a.wtab = (const long long*)(bf.stab + joff);
             resample_pcm(a, 1, nrs, stream);
         }
+        if (seq) eq_step((const long long*)(bf.stab + eoff), 1, etiles);
         if (slim) {
             LimArgs a{};
             a.x = c.stage_out(oc.src[OS_LIMIT]);
@@ -1605,7 +1633,7 @@ int Engine::run_stream_steps(RunCtx& c) {
             long long* tm = (long long*)(ht + stream_tab_lim_off(nw));
             long long rsum = 0;                             // limiter: the resampler's float outputs of the widened ranges, packed
             wj0.assign(nw, 0); wn.assign(nw, 0); wdst.assign(nw, 0);
-            long Wtot = 0; int maxW = 0; long long max_out = 0, max_rs = 0;
+            long Wtot = 0; int maxW = 0; long long max_out = 0, max_rs = 0, etiles = 1;
             for (int i = 0; i < nw; i++) {
                 const int b = wb[i];
                 const long F = lenF[b];
@@ -1615,8 +1643,15 @@ int Engine::run_stream_steps(RunCtx& c) {
                 ti[i] = offF[b] + (int)w.w0; ti[nw + i] = (int)Wtot; ti[2 * nw + i] = (int)wlen; ti[3 * nw + i] = c.mix ? b : sidv[b];      // (a mixed run: the window's utterance, a column of bt.g)
                 ti[4 * nw + i] = (int)((Wtot + (f0 - w.w0)) * hop); ti[5 * nw + i] = (int)dsum;
                 tl[5 * i] = (long long)w.w0 * hop; tl[5 * i + 1] = (long long)F * hop; tl[5 * i + 2] = w.jl0; tl[5 * i + 3] = w.jl1; tl[5 * i + 4] = slim ? rsum : dsum;
-                tm[7 * i] = srs ? rsum : (long long)Wtot * hop; tm[7 * i + 1] = srs ? w.jl0 : (long long)w.w0 * hop;
-                tm[7 * i + 2] = srs ? nrs : (long long)wlen * hop; tm[7 * i + 3] = w.Nout;
+                tm[7 * i] = srs || seq ? rsum : (long long)Wtot * hop; tm[7 * i + 1] = srs || seq ? w.jl0 : (long long)w.w0 * hop;
+                tm[7 * i + 2] = srs || seq ? nrs : (long long)wlen * hop; tm[7 * i + 3] = w.Nout;
+                if (seq) {       // the EQ reads the resampler's widened outputs (native rate: the decode window) and writes what the limiter reads
+                    const EqsRow r = srs ? eqt.row(b, rsum, w.jl0, nrs, w.jl0, w.jl1, rsum, w.j0, w.j1, dsum)
+                                         : eqt.row(b, (long long)Wtot * hop, (long long)w.w0 * hop, (long long)wlen * hop, w.jl0, w.jl1, rsum, w.j0, w.j1, dsum);
+                    if (const char* bad = eqs_row_check(r, w.Nout)) return fail(STS_EDEVICE, bad);
+                    memcpy(ht + stream_tab_eq_off(nw, c.gain) + (size_t)i * sizeof(EqsRow), &r, sizeof(r));
+                    etiles = std::max(etiles, eqs_tiles(r.e, r.o1));
+                }
                 tm[7 * i + 4] = w.j0; tm[7 * i + 5] = w.j1; tm[7 * i + 6] = dsum;
                 rsum += nrs; max_rs = std::max(max_rs, nrs);
                 wj0[i] = w.j0; wn[i] = nout; wdst[i] = dsum;
@@ -1625,7 +1660,7 @@ int Engine::run_stream_steps(RunCtx& c) {
             }
             ti[6 * nw] = (int)dsum;
             if (c.gain) { int* tu = (int*)(ht + stream_tab_utt_off(nw)); for (int i = 0; i < nw; i++) tu[i] = wb[i]; }     // (the gain kernel: each window's utterance)
-            HIPCK(hipMemcpyAsync(c.d_win, ht, stream_tab_bytes(nw, c.gain), hipMemcpyHostToDevice, stream));
+            HIPCK(hipMemcpyAsync(c.d_win, ht, stream_tab_bytes(nw, c.gain, seq), hipMemcpyHostToDevice, stream));
             // one utterance: its window by value (no table load in the decoder's kernels); several: the tables, also while one window is live
             int rc = B == 1 ? run_decode(c, 1, Wtot, maxW, ti[0], ti[2]) : run_decode(c, nw, Wtot, maxW, 0, -1);
             if (rc != STS_OK) return rc;
@@ -1640,6 +1675,7 @@ int Engine::run_stream_steps(RunCtx& c) {
             } else if (pack) {
                 stream_pack(bf.pcm, dst, c.d_win + 4 * nw, c.d_win + 5 * nw, nw, max_out, stream);
             }
+            if (seq) eq_step((const long long*)(bf.stab + stream_tab_eq_off(nw, c.gain)), nw, etiles);
             if (slim) {          // every window of the step in one launch; it writes the packed chunks in place of the resampler / the pack
                 LimArgs a{};
                 a.x = c.stage_out(oc.src[OS_LIMIT]);
@@ -1658,8 +1694,10 @@ int Engine::run_stream_steps(RunCtx& c) {
             h2_fallbacks++;
             conv_math = 0;                                 // (run() restores the setting)
             k--;                                           // this step again, every window of it
+            eqt.drop();                                    // (from the state the first attempt started from)
             continue;
         }
+        eqt.commit();
         for (int i = 0; i < nw; i++) {                     // ascending utterance order
             const int b = wb[i];
             total_samples += wn[i];

@@ -19,6 +19,7 @@
 #include <string.h>
 
 #include "devmath.hpp"
+#include "eq_stream.hpp"
 #include "kernels.hpp"
 
 namespace sts {
@@ -26,6 +27,7 @@ namespace sts {
 constexpr int EQ_THREADS = 256, EQ_R = 32, EQ_TILE = EQ_THREADS * EQ_R;       // 8192 samples per workgroup
 constexpr int EQ_LDS = EQ_TILE + EQ_TILE / EQ_R;                                // one pad float per chunk: conflict-free strided access
 constexpr int EQ_LD = kEqDim;                                                   // row stride of the tables
+static_assert(EQ_TILE == kEqsTile && kEqDim == kEqsDim, "eq_stream.hpp restates the tile and the state's dimension");
 
 bool eq_valid(int rate, int n_bands, const sts_eq_band* bands, const char** why) {
     const char* w = nullptr;
@@ -205,32 +207,15 @@ __device__ __forceinline__ EqGeom eq_geom(const EqArgs& a, int b, unsigned long 
 // [0, nt) moves as one vector where the other side's address is aligned too; the utterance's edge groups go sample by sample.
 __device__ __forceinline__ int eq_phase(const float* p) { return (int)(((uintptr_t)p >> 2) & 3); }
 
-// Stages tile t of the utterance into LDS (sample p at p + p / EQ_R) and scans its chunk maps: returns this lane's carry-in relative to a
-// zero tile start (Z) and, in et (every lane), the tile's zero-start end state.  Chunk k = samples [t EQ_TILE + k EQ_R, + r), r <= EQ_R.
+// Scans the chunk maps of a tile staged in LDS (sample p at p + p / EQ_R; this lane's chunk k = tid holds r <= EQ_R samples and the input
+// history (xm1, xm2)): returns this lane's carry-in relative to a zero tile start (Z) and, in et (every lane), the tile's zero-start end
+// state.  A lane reads lower lanes and earlier waves only: Z of chunk k is a function of the chunks j < k, whatever lies behind them.
 template <int S>
-__device__ __forceinline__ void eq_tile_scan(const EqArgs& a, const double (&c)[S][5], const float* xu, long long N, long long t, float* xs,
-                             double (*wt)[kEqDim], double (&Z)[2 * S], double (&et)[2 * S], int& r, float& xm1, float& xm2) {
+__device__ __forceinline__ void eq_scan_staged(const EqArgs& a, const double (&c)[S][5], float* xs, double (*wt)[kEqDim], double (&Z)[2 * S],
+                                               double (&et)[2 * S], int r, float xm1, float xm2) {
     constexpr int D = 2 * S;
     const EqTable* __restrict__ k = a.tab;
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    const long long t0 = t * EQ_TILE;
-    const int nt = (int)(N - t0 < EQ_TILE ? N - t0 : EQ_TILE);
-    const float* xt = xu + t0;
-    const int h = eq_phase(xt);
-    for (int g = tid; g < EQ_TILE / 4 + 1; g += EQ_THREADS) {
-        const int p0 = 4 * g - h;
-        if (p0 >= 0 && p0 + 4 <= nt) {
-            const float4 v = *(const float4*)(xt + p0);
-            xs[p0 + p0 / EQ_R] = v.x; xs[p0 + 1 + (p0 + 1) / EQ_R] = v.y; xs[p0 + 2 + (p0 + 2) / EQ_R] = v.z; xs[p0 + 3 + (p0 + 3) / EQ_R] = v.w;
-        } else {
-            const int lo = p0 > 0 ? p0 : 0, hi = p0 + 4 < nt ? p0 + 4 : nt;
-            for (int p = lo; p < hi; p++) xs[p + p / EQ_R] = xt[p];
-        }
-    }
-    const long long n0 = t0 + (long long)tid * EQ_R;
-    r = N - n0 <= 0 ? 0 : (N - n0 < EQ_R ? (int)(N - n0) : EQ_R);
-    xm1 = r > 0 && n0 >= 1 ? xu[n0 - 1] : 0.f; xm2 = r > 0 && n0 >= 2 ? xu[n0 - 2] : 0.f;
-    __syncthreads();
     double P[D];
 #pragma unroll
     for (int i = 0; i < D; i++) P[i] = 0.0;
@@ -276,6 +261,33 @@ __device__ __forceinline__ void eq_tile_scan(const EqArgs& a, const double (&c)[
     eq_mpow<S, 6>(k, lane, Z);
 #pragma unroll
     for (int i = 0; i < D; i++) Z[i] += Pex[i];
+}
+
+// Stages tile t of the utterance into LDS (sample p at p + p / EQ_R) and scans its chunk maps (eq_scan_staged).
+// Chunk k = samples [t EQ_TILE + k EQ_R, + r), r <= EQ_R.
+template <int S>
+__device__ __forceinline__ void eq_tile_scan(const EqArgs& a, const double (&c)[S][5], const float* xu, long long N, long long t, float* xs,
+                             double (*wt)[kEqDim], double (&Z)[2 * S], double (&et)[2 * S], int& r, float& xm1, float& xm2) {
+    const int tid = threadIdx.x;
+    const long long t0 = t * EQ_TILE;
+    const int nt = (int)(N - t0 < EQ_TILE ? N - t0 : EQ_TILE);
+    const float* xt = xu + t0;
+    const int h = eq_phase(xt);
+    for (int g = tid; g < EQ_TILE / 4 + 1; g += EQ_THREADS) {
+        const int p0 = 4 * g - h;
+        if (p0 >= 0 && p0 + 4 <= nt) {
+            const float4 v = *(const float4*)(xt + p0);
+            xs[p0 + p0 / EQ_R] = v.x; xs[p0 + 1 + (p0 + 1) / EQ_R] = v.y; xs[p0 + 2 + (p0 + 2) / EQ_R] = v.z; xs[p0 + 3 + (p0 + 3) / EQ_R] = v.w;
+        } else {
+            const int lo = p0 > 0 ? p0 : 0, hi = p0 + 4 < nt ? p0 + 4 : nt;
+            for (int p = lo; p < hi; p++) xs[p + p / EQ_R] = xt[p];
+        }
+    }
+    const long long n0 = t0 + (long long)tid * EQ_R;
+    r = N - n0 <= 0 ? 0 : (N - n0 < EQ_R ? (int)(N - n0) : EQ_R);
+    xm1 = r > 0 && n0 >= 1 ? xu[n0 - 1] : 0.f; xm2 = r > 0 && n0 >= 2 ? xu[n0 - 2] : 0.f;
+    __syncthreads();
+    eq_scan_staged<S>(a, c, xs, wt, Z, et, r, xm1, xm2);
 }
 
 template <int S>
@@ -380,6 +392,201 @@ void eq_run(const EqArgs& a, int B, long long max_len, hipStream_t st) {
     case 2: eq_launch<2>(a, grid, tiles > 0, st); break;
     case 3: eq_launch<3>(a, grid, tiles > 0, st); break;
     default: eq_launch<4>(a, grid, tiles > 0, st); break;
+    }
+}
+
+// ---- stream mode (EqArgs::wtab; eq_stream.hpp, DESIGN.md 9j "streamed") ---------------------------------------------------------------
+// A step continues utterance b from its carried state: input consumed up to e, the open tile te = e / EQ_TILE with its carry S_te, its
+// input so far and the two samples in front of it, and a ring of the last y.  Workgroup (i, w) owns tile te + i of window w, up to the tile
+// that holds o1.  It stages the tile's samples [t0, min(o1, t0 + EQ_TILE)) -- those below e from the state, the others from the window --
+// and runs eq_scan_staged / eq_chunk on them as the whole call does on the complete tile: a chunk's carry-in reads the chunks in front of
+// it only, so every y it produces is the whole call's.  Launch 1 leaves the zero-start end state of every touched tile (used only of
+// tiles the step completes) and the new open tile's input; launch 2 composes S_t = M^256 S_{t-1} + E_{t-1} upwards from S_te in the whole
+// call's order, writes y, the cast and the new state.  The state is read from one slot and written to the other: a step that runs twice
+// starts twice from the same state.
+struct EqsView {
+    long long xbase, u0, o0, o1, ybase, j0, j1, pdst, e, t0e;
+    const double* sS; const float *sprev, *sx, *sy;
+    double* dS; float *dprev, *dx, *dy;
+};
+__device__ __forceinline__ EqsView eqs_view(const EqArgs& a, int w) {
+    const long long* r = a.wtab + (size_t)kEqsRow * w;
+    EqsView v;
+    const long long b = r[0];
+    v.xbase = r[1]; v.u0 = r[2]; v.o0 = r[4]; v.o1 = r[5]; v.ybase = r[6]; v.j0 = r[7]; v.j1 = r[8]; v.pdst = r[9]; v.e = r[10];
+    v.t0e = v.e / EQ_TILE * EQ_TILE;
+    char* rd = a.state + ((size_t)b * 2 + (size_t)a.slot) * kEqsSlotBytes;
+    char* wr = a.state + ((size_t)b * 2 + (size_t)(1 - a.slot)) * kEqsSlotBytes;
+    v.sS = (const double*)rd; v.sprev = (const float*)(rd + kEqsOffPrev); v.sx = (const float*)(rd + kEqsOffX); v.sy = (const float*)(rd + kEqsOffY);
+    v.dS = (double*)wr; v.dprev = (float*)(wr + kEqsOffPrev); v.dx = (float*)(wr + kEqsOffX); v.dy = (float*)(wr + kEqsOffY);
+    return v;
+}
+// input sample n < o1 of the utterance: the window from e on, the state below it (the open tile, then the two samples in front of it)
+__device__ __forceinline__ float eqs_x(const EqArgs& a, const EqsView& v, long long n) {
+    if (n < 0) return 0.f;
+    if (n >= v.e) return a.x[v.xbase + (n - v.u0)];
+    if (n >= v.t0e) return v.sx[n - v.t0e];
+    return v.sprev[v.t0e - 1 - n];
+}
+// Stages tile t0 / EQ_TILE's samples [0, nt) into LDS and sets this lane's chunk: 16-byte groups on either source where a group of four
+// is whole there, sample by sample at the seam and the edges.  Ends with the barrier.
+__device__ __forceinline__ void eqs_stage(const EqArgs& a, const EqsView& v, long long t0, int nt, float* xs, int& r, float& xm1, float& xm2) {
+    const int tid = threadIdx.x;
+    const int pe = (int)(v.e - t0 < 0 ? 0 : (v.e - t0 < nt ? v.e - t0 : nt));      // [0, pe): consumed before this step (the open tile only)
+    for (int g = tid; 4 * g < pe; g += EQ_THREADS) {
+        const int p0 = 4 * g;
+        if (p0 + 4 <= pe) {
+            const float4 q = *(const float4*)(v.sx + p0);
+            xs[p0 + p0 / EQ_R] = q.x; xs[p0 + 1 + (p0 + 1) / EQ_R] = q.y; xs[p0 + 2 + (p0 + 2) / EQ_R] = q.z; xs[p0 + 3 + (p0 + 3) / EQ_R] = q.w;
+        } else {
+            for (int p = p0; p < pe; p++) xs[p + p / EQ_R] = v.sx[p];
+        }
+    }
+    const long long off = v.xbase + (t0 - v.u0);                                    // tile sample p is a.x[off + p], for p >= pe
+    const int h = (int)(((long long)((uintptr_t)a.x >> 2) + off) & 3);
+    for (int g = tid; g < EQ_TILE / 4 + 1; g += EQ_THREADS) {
+        const int p0 = 4 * g - h;
+        const int lo = p0 > pe ? p0 : pe, hi = p0 + 4 < nt ? p0 + 4 : nt;
+        if (lo >= hi) continue;
+        if (lo == p0 && hi == p0 + 4) {
+            const float4 q = *(const float4*)(a.x + (off + p0));
+            xs[p0 + p0 / EQ_R] = q.x; xs[p0 + 1 + (p0 + 1) / EQ_R] = q.y; xs[p0 + 2 + (p0 + 2) / EQ_R] = q.z; xs[p0 + 3 + (p0 + 3) / EQ_R] = q.w;
+        } else {
+            for (int p = lo; p < hi; p++) xs[p + p / EQ_R] = a.x[off + p];
+        }
+    }
+    const int c0 = tid * EQ_R;
+    r = nt - c0 <= 0 ? 0 : (nt - c0 < EQ_R ? nt - c0 : EQ_R);
+    xm1 = r > 0 ? eqs_x(a, v, t0 + c0 - 1) : 0.f; xm2 = r > 0 ? eqs_x(a, v, t0 + c0 - 2) : 0.f;
+    __syncthreads();
+}
+// tile samples [lo, hi) out of LDS to dst[off + p]: 16-byte groups where four are whole and aligned at the destination
+__device__ __forceinline__ void eqs_store_f(const float* xs, float* dst, long long off, int lo, int hi) {
+    const int h = (int)(((long long)((uintptr_t)dst >> 2) + off) & 3);
+    for (int g = threadIdx.x; g < EQ_TILE / 4 + 1; g += EQ_THREADS) {
+        const int p0 = 4 * g - h;
+        const int l = p0 > lo ? p0 : lo, u = p0 + 4 < hi ? p0 + 4 : hi;
+        if (l >= u) continue;
+        if (l == p0 && u == p0 + 4)
+            *(float4*)(dst + (off + p0)) = make_float4(xs[p0 + p0 / EQ_R], xs[p0 + 1 + (p0 + 1) / EQ_R], xs[p0 + 2 + (p0 + 2) / EQ_R], xs[p0 + 3 + (p0 + 3) / EQ_R]);
+        else for (int p = l; p < u; p++) dst[off + p] = xs[p + p / EQ_R];
+    }
+}
+__device__ __forceinline__ void eqs_store_pcm(const float* xs, int16_t* dst, long long off, int lo, int hi) {
+    const int h = (int)(((long long)((uintptr_t)dst >> 1) + off) & 3);
+    for (int g = threadIdx.x; g < EQ_TILE / 4 + 1; g += EQ_THREADS) {
+        const int p0 = 4 * g - h;
+        const int l = p0 > lo ? p0 : lo, u = p0 + 4 < hi ? p0 + 4 : hi;
+        if (l >= u) continue;
+        if (l == p0 && u == p0 + 4) {
+            const float f0 = xs[p0 + p0 / EQ_R], f1 = xs[p0 + 1 + (p0 + 1) / EQ_R], f2 = xs[p0 + 2 + (p0 + 2) / EQ_R], f3 = xs[p0 + 3 + (p0 + 3) / EQ_R];
+            *(uint2*)(dst + (off + p0)) = make_uint2((uint32_t)(uint16_t)pcm_cast(f0) | ((uint32_t)(uint16_t)pcm_cast(f1) << 16),
+                                                     (uint32_t)(uint16_t)pcm_cast(f2) | ((uint32_t)(uint16_t)pcm_cast(f3) << 16));
+        } else for (int p = l; p < u; p++) dst[off + p] = pcm_cast(xs[p + p / EQ_R]);
+    }
+}
+
+// stream launch 1: the zero-start end state of every tile the step touches; the tile that holds o1 leaves its input as the new open tile's
+template <int S>
+__global__ __launch_bounds__(EQ_THREADS) void eq_stream_scan_kernel(EqArgs a) {
+    __shared__ float xs[EQ_LDS];
+    __shared__ double wt[EQ_THREADS / 64][kEqDim];
+    const int w = blockIdx.y, tid = threadIdx.x;
+    const EqsView v = eqs_view(a, w);
+    const long long t0 = v.t0e + (long long)blockIdx.x * EQ_TILE;
+    if (t0 > v.o1) return;
+    const int nt = (int)(v.o1 - t0 < EQ_TILE ? v.o1 - t0 : EQ_TILE);
+    double c[S][5];
+    eq_load_coef<S>(a, c);
+    int r; float xm1, xm2;
+    eqs_stage(a, v, t0, nt, xs, r, xm1, xm2);
+    if (nt < EQ_TILE) {         // (o1 lies in this tile: it is the open tile of the next step)
+        eqs_store_f(xs, v.dx, 0, 0, nt);
+        if (tid < 2) v.dprev[tid] = eqs_x(a, v, t0 - 1 - tid);
+    }
+    double Z[2 * S], et[2 * S];
+    eq_scan_staged<S>(a, c, xs, wt, Z, et, r, xm1, xm2);
+    double* E = a.E + ((size_t)w * gridDim.x + blockIdx.x) * kEqDim;
+#pragma unroll
+    for (int i = 0; i < 2 * S; i++)
+        if (tid == i) E[i] = et[i];
+}
+
+// stream launch 2: the tile's carry from the open tile's, the true run of every chunk, then y, the cast and the new state
+template <int S>
+__global__ __launch_bounds__(EQ_THREADS) void eq_stream_apply_kernel(EqArgs a) {
+    constexpr int D = 2 * S;
+    __shared__ float xs[EQ_LDS];
+    __shared__ double wt[EQ_THREADS / 64][kEqDim];
+    const int w = blockIdx.y, tid = threadIdx.x;
+    const EqsView v = eqs_view(a, w);
+    const long long t0 = v.t0e + (long long)blockIdx.x * EQ_TILE;
+    if (t0 > v.o1) return;
+    const int nt = (int)(v.o1 - t0 < EQ_TILE ? v.o1 - t0 : EQ_TILE);
+    const long long hist0 = v.o1 - kEqsHist;            // the new ring holds y [max(0, hist0), o1)
+    if (blockIdx.x == 0) {
+        // y in front of the open tile comes out of the carried ring: the re-presented part of the range, and the part of the new ring
+        const long long end = v.t0e < v.o1 ? v.t0e : v.o1;
+        for (long long n = v.o0 + tid; n < end; n += EQ_THREADS) {
+            const float f = v.sy[n & (kEqsHist - 1)];
+            if (a.y) a.y[v.ybase + (n - v.o0)] = f;
+            if (a.pcm && n >= v.j0 && n < v.j1) a.pcm[v.pdst + (n - v.j0)] = pcm_cast(f);
+        }
+        for (long long n = (hist0 > 0 ? hist0 : 0) + tid; n < end; n += EQ_THREADS) v.dy[n & (kEqsHist - 1)] = v.sy[n & (kEqsHist - 1)];
+    }
+    const EqTable* __restrict__ k = a.tab;
+    double c[S][5];
+    eq_load_coef<S>(a, c);
+    int r; float xm1, xm2;
+    eqs_stage(a, v, t0, nt, xs, r, xm1, xm2);
+    double Z[D], et[D];
+    eq_scan_staged<S>(a, c, xs, wt, Z, et, r, xm1, xm2);
+    // S_t upwards from the open tile's carry (zero at the utterance's start), the whole call's loop from there on
+    double St[D];
+#pragma unroll
+    for (int i = 0; i < D; i++) St[i] = v.e > 0 ? v.sS[i] : 0.0;
+    const double* E = a.E + (size_t)w * gridDim.x * kEqDim;
+    for (int q = 0; q < (int)blockIdx.x; q++) {
+        double m[D];
+        eq_mv<S>(k->Mp[8], St, m);
+        const double* Eq = E + (size_t)q * kEqDim;
+#pragma unroll
+        for (int i = 0; i < D; i++) St[i] = m[i] + Eq[i];
+    }
+    if (nt < EQ_TILE) {
+#pragma unroll
+        for (int i = 0; i < D; i++)
+            if (tid == i) v.dS[i] = St[i];
+    }
+    eq_mpow<S, 8>(k, tid, St);
+#pragma unroll
+    for (int i = 0; i < D; i++) St[i] += Z[i];
+    eq_chunk<S, true>(c, xs + tid * (EQ_R + 1), r, xm1, xm2, St);
+    __syncthreads();
+    const int ylo = (int)(v.o0 - t0 < 0 ? 0 : (v.o0 - t0 < nt ? v.o0 - t0 : nt));
+    if (a.y) eqs_store_f(xs, a.y, v.ybase + (t0 - v.o0), ylo, nt);
+    if (a.pcm) {
+        const int lo = (int)(v.j0 - t0 < 0 ? 0 : (v.j0 - t0 < nt ? v.j0 - t0 : nt)), hi = (int)(v.j1 - t0 < 0 ? 0 : (v.j1 - t0 < nt ? v.j1 - t0 : nt));
+        eqs_store_pcm(xs, a.pcm, v.pdst + (t0 - v.j0), lo, hi);
+    }
+    const int hlo = (int)(hist0 - t0 < 0 ? 0 : (hist0 - t0 < nt ? hist0 - t0 : nt));
+    for (int p = hlo + tid; p < nt; p += EQ_THREADS) v.dy[(t0 + p) & (kEqsHist - 1)] = xs[p + p / EQ_R];
+}
+
+template <int S>
+static void eq_stream_launch(const EqArgs& a, dim3 grid, hipStream_t st) {
+    hipLaunchKernelGGL(eq_stream_scan_kernel<S>, grid, dim3(EQ_THREADS), 0, st, a);
+    hipLaunchKernelGGL(eq_stream_apply_kernel<S>, grid, dim3(EQ_THREADS), 0, st, a);
+}
+
+void eq_stream_run(const EqArgs& a, int nwin, long long max_tiles, hipStream_t st) {
+    if (nwin <= 0 || max_tiles <= 0 || a.S < 1 || a.S > kEqMaxBands || !a.wtab || !a.state || !a.E) return;
+    const dim3 grid((unsigned)max_tiles, nwin);
+    switch (a.S) {
+    case 1: eq_stream_launch<1>(a, grid, st); break;
+    case 2: eq_stream_launch<2>(a, grid, st); break;
+    case 3: eq_stream_launch<3>(a, grid, st); break;
+    default: eq_stream_launch<4>(a, grid, st); break;
     }
 }
 

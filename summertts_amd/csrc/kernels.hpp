@@ -530,11 +530,17 @@ struct EqArgs {
     int S; const EqTable* tab;           // sections (1 .. 4) and their tables (device memory)
     float* y; int16_t* pcm;              // outputs packed like x, each optional (not x)
     long long* utab; double* E;          // workspace (eq_ws_carve)
+    // streaming (wtab != null; eq_stream.hpp has the row and the state's layout): window w reads its row from wtab[12 w ..] -- the
+    // utterance whose carried state it continues, its input window, the range of y to produce into y[ybase ..), the kept range whose
+    // int16 samples go to pcm[pdst ..).  state: [B][2] slots, read slot `slot`, written slot 1 - slot.  E: [nwin][tiles] end states
+    const long long* wtab; char* state; int slot;
 };
 // workspace of B utterances of total_samples samples in all (the frame-level arena's dry run sizes it)
 size_t eq_ws_bytes(int B, long long total_samples);
 void eq_ws_carve(EqArgs& a, void* ws, int B, long long total_samples);
 // 2 launches; max_len = the longest utterance's sample count or more
 void eq_run(const EqArgs& a, int B, long long max_len, hipStream_t st);
+// streaming: 2 launches over nwin windows x max_tiles tiles (eqs_tiles of the step's longest row, or more)
+void eq_stream_run(const EqArgs& a, int nwin, long long max_tiles, hipStream_t st);
 
 }  // namespace sts

@@ -3,7 +3,9 @@
 // The stages, in their fixed order: tail, gain, join, resample, pack, eq, loud, limit.  A running stage reads the float output of the
 // nearest running stage in front of it that has one, and the last running stage that can cast to int16 writes the PCM the caller
 // gets; every other int16 result goes to scratch.  A streaming run decodes tail and gain per step and runs resample / pack / limit on
-// each step's windows; eq and loud never run in one (the engine refuses those calls).  A joined stream (sts_infer_ids_joined_stream) joins
+// each step's windows; loud never runs in one (the engine refuses those calls), and eq only with the fact eq_stream (sts_set_eq_streaming):
+// it then runs on each step's windows behind the resampler from a state carried per utterance, pack never runs, and the EQ is the writer
+// when the limiter is off.  A joined stream (sts_infer_ids_joined_stream) joins
 // each step's windows into a window of the ONE signal J: pack never runs, and the join is the writer when nothing runs behind it.
 #pragma once
 
@@ -15,6 +17,7 @@ struct OutFacts {
     bool stream; int B;
     bool resample, gain, join, eq; int loud_mode; bool limit;
     bool taps, stream_direct;
+    bool eq_stream = false;     // (behind the others, which older callers initialise in order) a stream runs the EQ: sts_set_eq_streaming
 };
 
 struct OutChain {
@@ -26,14 +29,15 @@ struct OutChain {
     bool loud_cast, loud_no_clamp, lim_gloud;   // loudness casts with its gain; leaves the peak to the limiter; the limiter takes its gain
     bool lws, limws, spack, stab;   // workspaces: loudness, the limiter's result words, the packed chunk buffer, the step tables
     bool chunk_in_place;    // streaming: nothing packs the step's one chunk, it is downloaded from its offset in the PCM
+    bool eqws, eqst;        // the EQ's workspaces: the whole call's tile table; a stream's carried state, step workspace and table rows
 };
 
 inline OutChain plan_out_chain(const OutFacts& f) {
     OutChain p{};
-    const bool whole = !f.stream;
+    const bool whole = !f.stream, eqs = f.stream && f.eq && f.eq_stream;
     p.run[OS_TAIL] = true; p.run[OS_GAIN] = f.gain; p.run[OS_JOIN] = f.join; p.run[OS_RESAMPLE] = f.resample;
-    p.run[OS_PACK] = f.stream && !f.join && !f.resample && !f.limit && (f.B > 1 || f.stream_direct);
-    p.run[OS_EQ] = f.eq && whole; p.run[OS_LOUD] = f.loud_mode != 0 && whole; p.run[OS_LIMIT] = f.limit;
+    p.run[OS_PACK] = f.stream && !f.join && !f.resample && !f.limit && !eqs && (f.B > 1 || f.stream_direct);
+    p.run[OS_EQ] = f.eq && (whole || eqs); p.run[OS_LOUD] = f.loud_mode != 0 && whole; p.run[OS_LIMIT] = f.limit;
     const bool normalise = p.run[OS_LOUD] && f.loud_mode == 2;
     int cur = -1;           // the current float signal
     for (int s = 0; s < OS_COUNT; s++) {
@@ -50,7 +54,8 @@ inline OutChain plan_out_chain(const OutFacts& f) {
     p.pcm_nat = p.writer != OS_TAIL; p.pcm_rs = p.run[OS_RESAMPLE] && p.writer != OS_RESAMPLE;
     p.loud_cast = p.writer == OS_LOUD; p.loud_no_clamp = p.run[OS_LIMIT]; p.lim_gloud = normalise;
     p.lws = p.run[OS_LOUD]; p.limws = p.run[OS_LIMIT] && whole; p.spack = p.run[OS_PACK] && f.B > 1; p.stab = f.stream;
-    p.chunk_in_place = f.stream && !f.join && !p.run[OS_RESAMPLE] && !p.run[OS_LIMIT] && !p.run[OS_PACK];
+    p.chunk_in_place = f.stream && !f.join && !p.run[OS_RESAMPLE] && !p.run[OS_LIMIT] && !p.run[OS_PACK] && !eqs;
+    p.eqws = p.run[OS_EQ] && whole; p.eqst = eqs;
     return p;
 }
 

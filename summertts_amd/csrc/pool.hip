@@ -56,6 +56,7 @@ struct sts_pool {
     int max_batch = 8;
     int loud_mode = 0;                 // sts_pool_set_loudness (streaming requests are refused while it is 2)
     int eq_bands = 0;                  // sts_pool_set_eq (streaming requests are refused while it is not 0)
+    bool eq_streaming = false;         // sts_pool_set_eq_streaming (... unless this is on)
     bool stop = false;
     int64_t batches = 0, requests = 0;
 
@@ -385,7 +386,9 @@ int64_t sts_pool_submit_stream(sts_pool* p, const int32_t* ids, int32_t n, int32
         std::lock_guard<std::mutex> lk(p->mu);
         if (p->stop) return pool_err(STS_ESTATE, "pool is shutting down");
         if (p->loud_mode != 0) return pool_err(STS_EINVAL, "streaming requests are refused while the pool normalizes loudness (sts_pool_set_loudness mode 0 first)");
-        if (p->eq_bands != 0) return pool_err(STS_EINVAL, "streaming requests are refused while the pool has an equaliser set (sts_pool_set_eq with 0 bands first): an IIR has no finite halo");
+        if (p->eq_bands != 0 && !p->eq_streaming)
+            return pool_err(STS_EINVAL, "streaming requests are refused while the pool has an equaliser set (sts_pool_set_eq with 0 bands first): an IIR has no finite halo"
+                                        " -- or switch the carried-state stream mode on (sts_pool_set_eq_streaming)");
         r->ticket = p->next_ticket++;
         p->queue.push_back(r);
         p->pending[r->ticket] = r;
@@ -465,6 +468,15 @@ int sts_pool_set_eq(sts_pool* p, int32_t n_bands, const sts_eq_band* bands) {
         if (rc != STS_OK) return pool_err(rc, e->error());
     }
     p->eq_bands = n_bands;
+    return STS_OK;
+}
+
+int sts_pool_set_eq_streaming(sts_pool* p, int enable) {
+    if (!p) return pool_err(STS_EINVAL, "null pool");
+    std::lock_guard<std::mutex> lk(p->mu);
+    if (!p->pending.empty()) return pool_err(STS_ESTATE, "requests are outstanding: wait for them before changing the equaliser's stream mode");
+    for (auto& e : p->engines) e->eq_streaming = enable != 0;
+    p->eq_streaming = enable != 0;
     return STS_OK;
 }
 

@@ -2,6 +2,7 @@
 // of one run share.
 #pragma once
 #include "engine.hpp"
+#include "eq_stream.hpp"
 #include "out_chain.hpp"
 #include "join_stream.hpp"
 
@@ -45,6 +46,8 @@ struct BufF {
     float* wave_join;
     char* stab; int16_t* spack; float *gwin, *cond_win;
     float* wave_eq; char* eqws;
+    // a stream that runs the EQ only (null otherwise): the carried state [B][2] slots (eq_stream.hpp) and the step's tile end states
+    char* eqst; double* eqsE;
 };
 // Streaming, the tables of one step with nw windows (one upload, c.d_win points at them): ints [zoff nw | coff nw | wlen nw | sid nw |
 // pack source nw | packed destination nw + 1], then from an 8-byte boundary the resampler's long long [nw][5] = {u0, L_utt, j0, j1, obase}
@@ -53,11 +56,17 @@ static inline size_t stream_tab_ll_off(int nw) { return ((size_t)(6 * nw + 1) * 
 static inline size_t stream_tab_lim_off(int nw) { return stream_tab_ll_off(nw) + (size_t)nw * 5 * 8; }
 // a run with a gain plan: behind those, each window's utterance as ints [nw] (GainArgs::utt)
 static inline size_t stream_tab_utt_off(int nw) { return stream_tab_lim_off(nw) + (size_t)nw * 7 * 8; }
-static inline size_t stream_tab_bytes(int nw, bool gain = false) { return stream_tab_utt_off(nw) + (gain ? (size_t)nw * 4 : 0); }
+// a stream that runs the EQ: from the next 8-byte boundary its rows, long long [nw][12] (eq_stream.hpp EqsRow)
+static inline size_t stream_tab_eq_off(int nw, bool gain) { return (stream_tab_utt_off(nw) + (gain ? (size_t)nw * 4 : 0) + 7) & ~(size_t)7; }
+static inline size_t stream_tab_bytes(int nw, bool gain = false, bool eq = false) {
+    return eq ? stream_tab_eq_off(nw, gain) + (size_t)nw * kEqsRow * 8 : stream_tab_utt_off(nw) + (gain ? (size_t)nw * 4 : 0);
+}
 // a joined stream: the same tables for the step's nw decode windows, and from the next 8-byte boundary the ONE window of J for the
 // resampler (long long [5]) and the limiter (long long [7]), then the windowed join's rows, long long [nw][5] (join_stream.hpp JsRow)
 static inline size_t join_stream_tab_j_off(int nw, bool gain) { return (stream_tab_bytes(nw, gain) + 7) & ~(size_t)7; }
-static inline size_t join_stream_tab_bytes(int nw, bool gain) { return join_stream_tab_j_off(nw, gain) + (size_t)(12 + 5 * (size_t)nw) * 8; }
+// (a joined stream that runs the EQ: behind the rows the one EqsRow of J)
+static inline size_t join_stream_tab_eq_off(int nw, bool gain) { return join_stream_tab_j_off(nw, gain) + (size_t)(12 + 5 * (size_t)nw) * 8; }
+static inline size_t join_stream_tab_bytes(int nw, bool gain, bool eq = false) { return join_stream_tab_eq_off(nw, gain) + (eq ? (size_t)kEqsRow * 8 : 0); }
 
 // Everything a run's stages share: batch geometry, workspace pointers, host / device tables.  Engine::run() fills it stage by
 // stage; the stage functions below see its fields under the names the pipeline has always used (RUN_ALIASES).

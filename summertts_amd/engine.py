@@ -311,6 +311,11 @@ def load_library() -> C.CDLL:
     lib.sts_eq_design.argtypes = [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
     lib.sts_eq_apply.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.sts_pool_set_eq.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
+    lib.sts_set_eq_streaming.argtypes = [C.c_void_p, C.c_int]
+    lib.sts_get_eq_streaming.argtypes = [C.c_void_p]
+    lib.sts_pool_set_eq_streaming.argtypes = [C.c_void_p, C.c_int]
+    lib.sts_eq_apply_chunked.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32,
+                                         C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
     lib.sts_multi_set_eq.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
     lib.sts_infer_ids_batch_stream.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
                                                BATCH_CHUNK_CB, C.c_void_p, C.c_void_p]
@@ -352,6 +357,7 @@ EXPORTED_SYMBOLS = [
     "sts_join_check", "sts_join_layout", "sts_join_apply", "sts_infer_ids_joined", "sts_get_join_offsets", "sts_pool_submit_joined",
     "sts_infer_ids_joined_stream", "sts_join_apply_range",
     "sts_set_eq", "sts_get_eq", "sts_eq_check", "sts_eq_design", "sts_eq_apply", "sts_pool_set_eq", "sts_multi_set_eq",
+    "sts_set_eq_streaming", "sts_get_eq_streaming", "sts_pool_set_eq_streaming", "sts_eq_apply_chunked",
 ]
 
 
@@ -720,6 +726,46 @@ def eq_apply(signals, rate: int, bands, device: int = 0, want_y: bool = True, wa
     return [y[off[b]:off[b + 1]].copy() for b in range(len(sig))], [pcm[off[b]:off[b + 1]].copy() for b in range(len(sig))]
 
 
+def eq_apply_chunked(signals, rate: int, bands, bounds, back: int = 0, device: int = 0):
+    """The equaliser's STREAM-mode kernels on each float signal in ``signals`` (sts_eq_apply_chunked): step k covers
+    [bounds[k], bounds[k + 1]) of every signal that reaches it (the last step: to the end) and presents the window widened by ``back``
+    samples on either side -> (y, pcm, windows): the float32 outputs and int16 casts assembled from the steps, and ``windows[k][b]`` =
+    (start, float32 output of step k's whole window of signal b), or None where signal b takes no part in step k.  Every output buffer
+    starts as NaN / 0x7FFF."""
+    lib = load_library()
+    n, arr = _eq_bands(bands)
+    sig = [np.ascontiguousarray(s, dtype=np.float32).ravel() for s in signals]
+    lens = np.asarray([s.size for s in sig], np.int64)
+    total = int(lens.sum())
+    bnd = np.ascontiguousarray(bounds, dtype=np.int64).ravel()
+    K, B = int(bnd.size), len(sig)
+    wins = []                    # (k, b, start, stop) in the library's order
+    for k in range(K):
+        c0 = int(bnd[k]); c1 = int(bnd[k + 1]) if k + 1 < K else None
+        for b in range(B):
+            N = int(lens[b])
+            if N > c0:
+                wins.append((k, b, max(0, c0 - int(back)), N if c1 is None else min(N, c1 + int(back))))
+    wtotal = sum(w[3] - w[2] for w in wins)
+    x = np.concatenate(sig) if sig and total > 0 else np.zeros(1, np.float32)
+    y = np.full(max(total, 1), np.nan, np.float32)
+    pcm = np.full(max(total, 1), 0x7FFF, np.int16)
+    wy = np.full(wtotal + 1, np.nan, np.float32)
+    woff = np.full(max(K * B, 1), -2, np.int64)
+    _check(lib, lib.sts_eq_apply_chunked(int(device), x.ctypes.data, lens.ctypes.data, B, int(rate), n, arr, bnd.ctypes.data, K, int(back),
+                                         y.ctypes.data, pcm.ctypes.data, wy.ctypes.data, wtotal, woff.ctypes.data))
+    off = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
+    windows = [[None] * B for _ in range(K)]
+    for k, b, a0, a1 in wins:
+        o = int(woff[k * B + b])
+        if o < 0:
+            raise StsError(f"sts_eq_apply_chunked: no window for step {k}, signal {b}")
+        windows[k][b] = (a0, wy[o:o + a1 - a0].copy())
+    if not np.isnan(wy[wtotal]):
+        raise StsError("sts_eq_apply_chunked wrote behind its windows")
+    return ([y[off[b]:off[b + 1]].copy() for b in range(B)], [pcm[off[b]:off[b + 1]].copy() for b in range(B)], windows)
+
+
 def resample_table(in_rate: int, out_rate: int):
     """The output-rate filter of the library (include/summertts_hip.h sts_resample_table; host only, no GPU): -> (P, Q, table), table the
     float32 [P][taps] coefficients the resampling kernel uses."""
@@ -1027,9 +1073,18 @@ class Synthesizer:
         """Parametric equaliser of every later whole-utterance call (include/summertts_hip.h sts_set_eq): up to 4 bands
         ``(type, freq_hz, gain_db, q)`` (EQ_PEAK, EQ_LOWSHELF, EQ_HIGHSHELF, EQ_HIGHPASS, EQ_LOWPASS) in front of loudness and the
         limiter; None or an empty list switches it off.  Invalid bands raise and change nothing; streaming calls are refused while
-        bands are set."""
+        bands are set, unless ``set_eq_streaming(True)``."""
         n, arr = _eq_bands(bands)
         _check(self.lib, self.lib.sts_set_eq(self.h, n, arr))
+
+    def set_eq_streaming(self, enable: bool = True):
+        """Let streaming calls run while an equaliser is set (sts_set_eq_streaming): each step continues the filter from a state carried per
+        utterance, and the concatenated chunks are the whole call's PCM for every chunk size.  Off by default; persists until changed."""
+        _check(self.lib, self.lib.sts_set_eq_streaming(self.h, 1 if enable else 0))
+
+    def get_eq_streaming(self) -> bool:
+        """The switch set by ``set_eq_streaming``."""
+        return bool(self.lib.sts_get_eq_streaming(self.h))
 
     def get_eq(self):
         """The bands set by ``set_eq``: a list of ``(type, freq_hz, gain_db, q)``."""
@@ -1349,11 +1404,18 @@ class Pool:
 
     def set_eq(self, bands=None):
         """``Synthesizer.set_eq`` for every engine of the pool (one setting for every request); raises while any request is outstanding
-        (STS_ESTATE).  Streamed requests are refused while bands are set."""
+        (STS_ESTATE).  Streamed requests are refused while bands are set, unless ``set_eq_streaming``."""
         n, arr = _eq_bands(bands)
         rc = self.lib.sts_pool_set_eq(self.h, n, arr)
         if rc != 0:
             raise StsError(f"sts_pool_set_eq: {rc}: {self.lib.sts_pool_last_error().decode()}")
+
+    def set_eq_streaming(self, enable: bool = True):
+        """``Synthesizer.set_eq_streaming`` for every engine of the pool: streamed requests run while bands are set.  Raises while any
+        request is outstanding (STS_ESTATE)."""
+        rc = self.lib.sts_pool_set_eq_streaming(self.h, 1 if enable else 0)
+        if rc != 0:
+            raise StsError(f"sts_pool_set_eq_streaming: {rc}: {self.lib.sts_pool_last_error().decode()}")
 
     def stats(self):
         b, r = C.c_int64(), C.c_int64()

@@ -10,7 +10,8 @@ distinct utterance per client), B in {1, 8, 32}, chunks of 32 and 64 frames.  Pe
 the utterances (min / p50 / max), time to the last chunk, and seconds of audio delivered per wall second; the median of --reps
 timed repeats after one warm-up of every shape.  The launch-ahead memo is off, so (c) waits for its frame counts as (a) and (b) do.
 --rate R: PCM at R Hz (sts_set_output_rate).  --direct 1: the batched stream's step output goes to mapped pinned memory (sts_debug_set STS_DBG_STREAM_DIRECT) instead of one
-download.  Prints one JSON line per row.
+download.  --eq 1: the 4-band equaliser of DESIGN.md 9j's cost table on every call, streamed from its carried state
+(sts_set_eq_streaming); --eq 0 (default) sets neither bands nor the switch.  Prints one JSON line per row.
 
 --joined: a paragraph instead -- --sentences sentences (default 32) of 64 to 256 phonemes joined with gaps of 8 frames and
 a 5 ms fade, three ways:
@@ -61,6 +62,9 @@ def _batch(syn, ids, chunk):
     return [t] * len(ids), t, sum(p.size for p in pcm), t
 
 
+# DESIGN.md 9j's cost table: HP 100 Hz; peak 1 kHz +6 dB q 2; low shelf 300 Hz -6 dB; peak 3 kHz -9 dB q 4 (valid from 8 kHz up)
+EQ_BANDS = [(engine.EQ_HIGHPASS, 100.0, 0.0, 0.707), (engine.EQ_PEAK, 1000.0, 6.0, 2.0), (engine.EQ_LOWSHELF, 300.0, -6.0, 0.7),
+            (engine.EQ_PEAK, 3000.0, -9.0, 4.0)]
 JOIN = {"lead_frames": 0, "trail_frames": 0, "fade_ms": 5.0}
 
 
@@ -93,6 +97,7 @@ def main() -> None:
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--direct", type=int, default=0)
     ap.add_argument("--rate", type=int, default=0, help="output sample rate (0: the native 16 kHz)")
+    ap.add_argument("--eq", type=int, default=0, help="1: the 4-band EQ of DESIGN.md 9j on every call, streamed (sts_set_eq_streaming)")
     ap.add_argument("--joined", action="store_true", help="a paragraph: joined stream against the whole joined call and single streams in turn")
     ap.add_argument("--sentences", type=int, default=32)
     a = ap.parse_args()
@@ -107,6 +112,9 @@ def main() -> None:
         syn.debug_set("stream_direct", a.direct)
         syn.set_output_rate(a.rate)
         rate = syn.output_rate()
+        if a.eq:
+            syn.set_eq(EQ_BANDS)
+            syn.set_eq_streaming(True)
         for B in [int(v) for v in a.batches.split(",")]:
             ids = _paragraph(cfg, B) if a.joined else [sb.synthetic_ids(a.phonemes, cfg.vocab, salt=u) for u in range(B)]
             for chunk in [int(v) for v in a.chunks.split(",")]:
@@ -122,7 +130,7 @@ def main() -> None:
                            "first_ms_max": med([max(r[0]) * 1e3 for r in runs]),
                            "last_ms": med([r[1] * 1e3 for r in runs]),
                            "audio_s_per_wall_s": med([r[2] / rate / r[3] for r in runs]),
-                           "rate": rate, "direct": a.direct, "reps": a.reps}
+                           "rate": rate, "direct": a.direct, "eq": a.eq, "reps": a.reps}
                     print(json.dumps(row), flush=True)
         syn.close()
 
