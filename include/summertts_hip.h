@@ -182,8 +182,9 @@ int sts_resample_table(int32_t in_rate, int32_t out_rate, int32_t* P, int32_t* Q
  *     reports it too), blocks (size of the final set).
  * An utterance's results are a function of its own x only, bit for bit (not of its batch companions, its position, or repetition).
  * Streaming needs the whole utterance before normalizing: while the mode is not 0, sts_infer_ids_stream and sts_infer_ids_batch_stream
- * answer STS_EINVAL (the engine stays usable).  Bad arguments (unknown mode, NaN or out-of-range target / ceiling): STS_EINVAL, nothing
- * changes.  sts_get_loudness returns the count of the last call's results (0 after a call in mode 0, a streaming call or a failure) and
+ * answer STS_EINVAL (the engine stays usable) -- unless, for mode 1, sts_set_loudness_streaming (below) is on.  Bad arguments (unknown mode, NaN or out-of-range target / ceiling): STS_EINVAL, nothing
+ * changes.  sts_get_loudness returns the count of the last call's results (0 after a call in mode 0, a failure, or a
+ * streaming call that did not measure) and
  * copies them to out; out == NULL asks for the count alone, a capacity below it answers STS_EINVAL. */
 #define STS_LOUD_OFF 0
 #define STS_LOUD_MEASURE 1
@@ -199,6 +200,39 @@ int sts_kweight_coeffs(int32_t rate, double coeffs[10]);
  * allowed); out[b] receives the results defined above for the given target / ceiling. */
 int sts_loudness_measure(int device, const float* x, const int64_t* lengths, int32_t B, int32_t rate,
                          float target_lufs, float peak_dbfs, sts_loudness* out);
+/* ---- loudness in a stream (ABI number unchanged).  sts_set_loudness_streaming(e, 1) lets every streaming call (sts_infer_ids_stream,
+ * sts_infer_ids_batch_stream, sts_infer_ids_joined_stream, the engine side of a streamed pool request) run under STS_LOUD_MEASURE; 0
+ * (default) keeps the refusal above for modes 1 and 2, word for word, and sts_get_loudness then reports count 0 after a stream.  The
+ * switch persists until changed; it has no effect in a whole-utterance call or under mode 0 (with it off, or under mode 0, a stream
+ * allocates, uploads and launches exactly what it always did).  sts_get_loudness_streaming returns it (0 for a null engine).  Under
+ * STS_LOUD_NORMALIZE a stream stays refused with the switch on as well: the gain needs the integrated loudness of the whole utterance
+ * before its first sample leaves.  The remedy is a loop across calls: measure in a stream, then set the limiter's make-up gain
+ * (sts_set_limiter) for the next calls of that voice.  sts_stream_halo_frames does not change.
+ *   Definition: every chunk is the chunk of the same stream under mode 0, bit for bit (measuring never writes PCM).  Step k of utterance
+ *   b consumes exactly the samples it delivers -- [j0, j1) at the output rate -- of the float signal loudness reads in a whole call: the
+ *   nearest running float stage in front of it (tail, gain plan, join, resampler, or the streamed EQ's y when sts_set_eq_streaming is on).
+ *   Samples a step re-presents below j0 or looks ahead to beyond j1 (the limiter's widened range) are not consumed.  After the call,
+ *   sts_get_loudness returns B entries (a joined stream: 1, for the signal J); utterance b's entry is steps 1 to 5 and 7 above applied to
+ *   x[0 .. e_b), e_b = the samples delivered.  For an utterance that ran to its end that is the whole call's entry (sts_infer_ids,
+ *   sts_infer_ids_batch per utterance, sts_infer_ids_joined), bit for bit with the conv mode pinned and for EVERY chunk_frames: the kernels
+ *   K-weight in chunks of 32 samples and tiles of 8192, both anchored at the utterance's first sample, the carry-in of a chunk depends
+ *   only on its tile's carry and the chunks in front of it in that tile, and the engine keeps the open tile's carry and input per
+ *   utterance and every tile's sums per call.  For an utterance whose callback stopped it, it is the measurement of what was delivered.
+ *   gain is reported as in mode 1 of a whole call (under the limiter: g_L).  A step the engine decodes twice (the split-bf16 repeat)
+ *   starts both times from the same state. */
+int sts_set_loudness_streaming(sts_engine* e, int enable);
+int sts_get_loudness_streaming(const sts_engine* e);
+/* The stream-mode kernels on caller signals: signals, rate, target and ceiling as sts_loudness_measure.  bounds, n_steps and back follow
+ * sts_eq_apply_chunked: bounds[0 .. n_steps) ascending step boundaries, bounds[0] = 0, common to all utterances; step k consumes
+ * [bounds[k], bounds[k+1]) (the last one: to the end), clipped to each length, and an utterance with lengths[b] <= bounds[k] takes no
+ * part in it.  back in [0, 2048]: step k presents the window [max(0, bounds[k] - back), min(lengths[b], bounds[k+1] + back)); only the
+ * part behind the previous step's end and below bounds[k+1] is consumed.  out[B]: the final results.  partial (may be NULL; n_steps x B
+ * entries): partial[k B + b] = the result as if the call had stopped behind step k, i.e. of x_b[0 .. min(lengths[b], bounds[k+1])) -- the
+ * only place where the gate runs per step.  Malformed step lists: STS_EINVAL.  (On the device results, state, workspace and the tile
+ * tables start out as NaN.) */
+int sts_loudness_measure_chunked(int device, const float* x, const int64_t* lengths, int32_t B, int32_t rate, float target_lufs,
+                                 float peak_dbfs, const int64_t* bounds, int32_t n_steps, int32_t back, sts_loudness* out,
+                                 sts_loudness* partial);
 /* ---- look-ahead peak limiter (ABI 13; no reference counterpart).  sts_set_limiter(e, mode, gain_db, ceiling_dbfs, lookahead_ms): mode
  * STS_LIMITER_OFF (0, default: nothing extra runs, PCM bit-identical to an engine that never set it) or STS_LIMITER_ON (1).  Valid:
  * gain_db in [-40, 40], ceiling_dbfs in [-30, 0], lookahead_ms in [0.25, 10]; NaN, anything outside, or an unknown mode: STS_EINVAL,
@@ -513,7 +547,8 @@ int sts_eq_apply(int device, const float* x, const int64_t* lengths, int32_t B, 
 /* ---- the equaliser in a stream (ABI number unchanged).  sts_set_eq_streaming(e, 1) lets every streaming call run while bands are set;
  * 0 (default) keeps the refusal above.  The switch persists until changed; it has no effect without bands or in a whole-utterance call
  * (with it off, or without bands, a stream allocates, uploads and launches exactly what it always did).  sts_get_eq_streaming returns
- * it (0 for a null engine).  Streaming under loudness mode 1 or 2 stays refused, and sts_stream_halo_frames does not change: an IIR needs
+ * it (0 for a null engine).  Streaming under loudness mode 1 or 2 stays refused (mode 1 runs with sts_set_loudness_streaming: loudness
+ * then measures the streamed EQ's y), and sts_stream_halo_frames does not change: an IIR needs
  * no look-ahead, and the carried state replaces the look-back.
  *   Definition: in a streaming call the signal of utterance b (of a joined stream: the one signal J) is y of step 2 above, the float64
  *   DF-I cascade from zero state over the ENTIRE utterance at the output rate, evaluated in eq.hip's fixed order -- chunks of 32

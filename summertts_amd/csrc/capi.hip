@@ -10,6 +10,7 @@
 #include "engine.hpp"
 #include "eq_stream.hpp"
 #include "join_stream.hpp"
+#include "loud_stream.hpp"
 
 using namespace sts;
 
@@ -785,6 +786,100 @@ int sts_loudness_measure(int device, const float* x, const int64_t* lengths, int
     if (ok) {
         loudness_run(a, B, maxl, nullptr, st);
         ok = hipGetLastError() == hipSuccess && hipMemcpyAsync(out, a.out, ob, hipMemcpyDeviceToHost, st) == hipSuccess &&
+             hipStreamSynchronize(st) == hipSuccess;
+    }
+    if (st) (void)hipStreamDestroy(st);
+    (void)hipFree(d);
+    return ok ? STS_OK : set_err(STS_EDEVICE, "loudness measurement failed on the device");
+}
+int sts_set_loudness_streaming(sts_engine* e, int enable) {
+    if (!e) return set_err(STS_EINVAL, "null engine");
+    e->eng.loud_streaming = enable != 0;
+    return STS_OK;
+}
+int sts_get_loudness_streaming(const sts_engine* e) { return e && e->eng.loud_streaming ? 1 : 0; }
+int sts_loudness_measure_chunked(int device, const float* x, const int64_t* lengths, int32_t B, int32_t rate, float target_lufs, float peak_dbfs,
+                                 const int64_t* bounds, int32_t n_steps, int32_t back, sts_loudness* out, sts_loudness* partial) {
+    if (B < 1 || !lengths || !out) return set_err(STS_EINVAL, "B >= 1, lengths and out are required");
+    if (!loudness_args_valid(2, target_lufs, peak_dbfs)) return set_err(STS_EINVAL, "target in [-70, 0] LUFS, ceiling in [-30, 0] dBFS");
+    LoudStreamArgs a{};
+    if (!loud_coef(rate, &a.k)) return set_err(STS_EINVAL, "rate must be an integer in [8000, 48000]");
+    if (n_steps < 1 || !bounds || bounds[0] != 0) return set_err(STS_EINVAL, "loudness stream: at least one step boundary, the first one 0");
+    for (int k = 1; k < n_steps; k++)
+        if (bounds[k] <= bounds[k - 1]) return set_err(STS_EINVAL, "loudness stream: the step boundaries must ascend");
+    if (back < 0 || back > 2048) return set_err(STS_EINVAL, "loudness stream: the overlap must be in [0, 2048]");
+    std::vector<int64_t> off(B + 1, 0);
+    std::vector<long long> lenv(B);
+    for (int b = 0; b < B; b++) {
+        if (lengths[b] < 0 || lengths[b] > (int64_t)1 << 30) return set_err(STS_EINVAL, "lengths must be in [0, 2^30]");
+        off[b + 1] = off[b] + lengths[b]; lenv[b] = lengths[b];
+    }
+    const int64_t total = off[B];
+    if (total > (int64_t)1 << 30) return set_err(STS_EINVAL, "the signals must hold at most 2^30 samples in all");
+    if (total > 0 && !x) return set_err(STS_EINVAL, "null signal");
+    // every step's rows: the window [max(0, c_k - back), min(N_b, c_k+1 + back)) of every utterance with N_b > c_k, consumed [c_k, min(N_b, c_k+1));
+    // and the gate's table behind every step (partial) and behind the last one (out): {0, samples consumed, first tile} per utterance
+    LdsTrack track; track.begin(B);
+    const long long tiles_all = track.layout(lenv.data());
+    std::vector<LdsRow> rows; std::vector<int> row0(n_steps + 1, 0); std::vector<long long> tiles(n_steps, 1);
+    std::vector<long long> utab((size_t)(n_steps + 1) * B * 3, 0);
+    size_t ws = 0;
+    for (int k = 0; k < n_steps; k++) {
+        const int64_t c0 = bounds[k], c1 = k + 1 < n_steps ? bounds[k + 1] : INT64_MAX;
+        for (int b = 0; b < B; b++) {
+            const int64_t N = lengths[b];
+            if (N <= c0) continue;
+            const int64_t o0 = std::max<int64_t>(0, c0 - back), o1 = c1 > N - back ? N : c1 + back, j1 = std::min<int64_t>(N, c1);
+            const LdsRow r = track.row(b, off[b] + o0, o0, o1 - o0, j1);
+            if (const char* bad = lds_row_check(r, N)) return set_err(STS_EINVAL, bad);
+            if (r.e != c0) return set_err(STS_EINVAL, "loudness stream: a step does not continue where the last one ended");
+            tiles[k] = std::max(tiles[k], lds_tiles(r.e, r.j1));
+            rows.push_back(r);
+        }
+        track.commit();
+        row0[k + 1] = (int)rows.size();
+        ws = std::max(ws, lds_ws_bytes(row0[k + 1] - row0[k], tiles[k]));
+        for (int b = 0; b < B; b++) { utab[((size_t)k * B + b) * 3 + 1] = track.e[b]; utab[((size_t)k * B + b) * 3 + 2] = track.tbase[b]; }
+    }
+    for (int b = 0; b < B; b++) { utab[((size_t)n_steps * B + b) * 3 + 1] = track.e[b]; utab[((size_t)n_steps * B + b) * 3 + 2] = track.tbase[b]; }
+    if (hipSetDevice(device) != hipSuccess) return set_err(STS_EDEVICE, "no such device");
+    auto pad = [](size_t bytes) { return (bytes + 255) & ~(size_t)255; };
+    const size_t xb = pad((size_t)total * 4), rb = pad(rows.size() * sizeof(LdsRow)), ub = pad(utab.size() * 8);
+    const size_t sb = pad(lds_state_bytes(B)), wb = pad(ws), tsb = pad((size_t)tiles_all * kLdsSlots * 8), tpb = pad((size_t)tiles_all * 4);
+    const size_t ob = pad((size_t)(n_steps + 1) * B * sizeof(sts_loudness)), gb = pad((size_t)B * 4);
+    char* d = nullptr;          // [x | rows | gate tables | results | gains | state | workspace | tile sums | tile peaks]
+    if (hipMalloc((void**)&d, xb + rb + ub + ob + gb + sb + wb + tsb + tpb + 256) != hipSuccess) return set_err(STS_EDEVICE, "out of device memory");
+    hipStream_t st = nullptr;
+    bool ok = hipStreamCreate(&st) == hipSuccess;
+    char* dr = d + xb; char* du = dr + rb; char* dout = du + ub; char* dg = dout + ob; char* ds = dg + gb; char* dw = ds + sb;
+    char* dts = dw + wb; char* dtp = dts + tsb;
+    // (results, state, workspace and tables start out as NaN: a word the kernels leave out, or a stale one they read, shows)
+    ok = ok && (total == 0 || hipMemcpyAsync(d, x, (size_t)total * 4, hipMemcpyHostToDevice, st) == hipSuccess) &&
+         (rows.empty() || hipMemcpyAsync(dr, rows.data(), rows.size() * sizeof(LdsRow), hipMemcpyHostToDevice, st) == hipSuccess) &&
+         hipMemcpyAsync(du, utab.data(), utab.size() * 8, hipMemcpyHostToDevice, st) == hipSuccess &&
+         hipMemsetAsync(dout, 0xFF, ob + gb + sb + wb + tsb + tpb, st) == hipSuccess;
+    if (ok) {
+        a.x = (const float*)d; a.state = ds; a.E = (double*)dw; a.tsum = (double*)dts; a.tpeak = (float*)dtp;
+        LoudArgs g{};
+        g.k = a.k; g.target = target_lufs; g.ceiling = peak_dbfs; g.tsum = a.tsum; g.tpeak = a.tpeak; g.gain = (float*)dg;
+        int slot = 0;
+        for (int k = 0; k < n_steps; k++) {
+            const int nw = row0[k + 1] - row0[k];
+            if (nw > 0) {
+                a.wtab = (const long long*)(dr + (size_t)row0[k] * sizeof(LdsRow)); a.slot = slot;
+                loud_stream_run(a, nw, tiles[k], st);
+                slot ^= 1;
+            }
+            if (partial) {      // the result as if the call had stopped behind this step
+                g.utab = (long long*)du + (size_t)k * B * 3; g.out = (float*)dout + (size_t)k * B * 4;
+                loud_gate_run(g, B, st);
+            }
+        }
+        g.utab = (long long*)du + (size_t)n_steps * B * 3; g.out = (float*)dout + (size_t)n_steps * B * 4;
+        loud_gate_run(g, B, st);
+        ok = hipGetLastError() == hipSuccess &&
+             hipMemcpyAsync(out, g.out, (size_t)B * sizeof(sts_loudness), hipMemcpyDeviceToHost, st) == hipSuccess &&
+             (!partial || hipMemcpyAsync(partial, dout, (size_t)n_steps * B * sizeof(sts_loudness), hipMemcpyDeviceToHost, st) == hipSuccess) &&
              hipStreamSynchronize(st) == hipSuccess;
     }
     if (st) (void)hipStreamDestroy(st);

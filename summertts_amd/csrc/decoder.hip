@@ -520,7 +520,7 @@ int Engine::decode_end(RunCtx& c, const float* wave, const WinGeom& win, long Wt
         cur = a.y;
     }
     const float* gloud = nullptr;
-    if (oc.run[OS_LOUD]) {
+    if (oc.run[OS_LOUD] && whole) {     // (a stream that measures: run_stream_steps runs the stream mode on what each step delivers)
         // loudness of every window (= utterance) of the current signal; normalising, the gain cast writes the PCM unless the limiter does
         if (loud_k_rate_ != out_rate) {
             if (!loud_coef(out_rate, &loud_k_)) return fail(STS_EINVAL, "loudness: output rate outside [8000, 48000]");

@@ -986,7 +986,7 @@ int Engine::wait_frame_counts(RunCtx& c) {
 
 // the one place that decides the output chain of a run (out_chain.hpp), with the limiter's design and the resampler's ratio for it
 int Engine::plan_output(RunCtx& c) {
-    c.oc = plan_out_chain(OutFacts{c.ss != nullptr, c.B, resampling(), c.gain, c.join, eq_n > 0, loud_mode, lim_mode != 0, record_taps, stream_direct != 0, eq_streaming});
+    c.oc = plan_out_chain(OutFacts{c.ss != nullptr, c.B, resampling(), c.gain, c.join, eq_n > 0, loud_mode, lim_mode != 0, record_taps, stream_direct != 0, eq_streaming, loud_streaming});
     if (c.oc.run[OS_RESAMPLE]) { c.rsP = rs.P; c.rsQ = rs.Q; }
     c.eqS = eq_n;
     if (c.oc.run[OS_LIMIT] && !limiter_design(out_rate, lim_gain_db, lim_ceiling, lim_ms, &c.limd)) return fail(STS_EINVAL, "limiter: output rate outside [8000, 48000]");
@@ -1127,7 +1127,7 @@ int Engine::run_frame_workspace(RunCtx& c) {
         bf.eqws = oc.eqws ? A.get<char>(eq_ws_bytes(B, c.Ocap)) : nullptr;
         bf.stab = nullptr; bf.spack = nullptr; bf.gwin = bf.cond_win = nullptr;
         if (ss) {
-            bf.stab = A.get<char>(c.join ? join_stream_tab_bytes(B, c.gain, oc.eqst) : stream_tab_bytes(B, c.gain, oc.eqst));
+            bf.stab = A.get<char>(c.join ? join_stream_tab_bytes(B, c.gain, oc.eqst, oc.lst) : stream_tab_bytes(B, c.gain, oc.eqst, oc.lst));
             if (oc.spack) bf.spack = A.get<int16_t>((size_t)c.Ocap);
             if (M.dec_type == 0 && c.ms && c.bstream) { bf.gwin = A.get<float>((size_t)M.gin * B); bf.cond_win = A.get<float>((size_t)M.up_init * B); }
         }
@@ -1138,12 +1138,23 @@ int Engine::run_frame_workspace(RunCtx& c) {
             bf.eqst = A.get<char>(eqs_state_bytes(nu));
             bf.eqsE = (double*)A.get<char>(eqs_ws_bytes(nu, eqs_max_tiles(c.Ocap)));
         }
+        // (and a stream that measures loudness behind that: the result tables hold every tile of every utterance's whole length)
+        bf.ldst = nullptr; bf.ldsE = nullptr; bf.ldres = nullptr;
+        if (oc.lst) {
+            const int nu = c.join ? 1 : B;
+            long long tiles = 0;
+            if (c.join) tiles = lds_utt_tiles(out_count(c.FJ * hop));
+            else for (int b = 0; b < B; b++) tiles += lds_utt_tiles(out_count((long long)p_lenF[b] * hop));
+            bf.ldst = A.get<char>(lds_state_bytes(nu));
+            bf.ldsE = (double*)A.get<char>(lds_ws_bytes(nu, lds_max_tiles(c.Ocap)));
+            bf.ldres = A.get<char>(lds_res_bytes(nu, tiles));
+        }
     };
     arenaF_.measuring = true; layoutF(arenaF_);
     if (!ensure(arenaF_, arenaF_.used + 4096)) return fail(STS_EDEVICE, "out of device memory (frame-level workspace)");
     arenaF_.measuring = false; layoutF(arenaF_);
     poison_arena(arenaF_);
-    if (oc.lws && loud_cap_ < B) {      // host-mapped room for the results: the gating kernel writes them there, the run's last synchronisation covers them
+    if ((oc.lws || oc.lst) && loud_cap_ < B) {      // host-mapped room for the results: the gating kernel writes them there, the run's last synchronisation covers them
         if (loud_host_) (void)hipHostFree(loud_host_);
         loud_host_ = nullptr; loud_dev_ = nullptr; loud_cap_ = 0;
         if (hipHostMalloc((void**)&loud_host_, (size_t)B * sizeof(sts_loudness), hipHostMallocMapped) != hipSuccess) { loud_host_ = nullptr; return fail(STS_EDEVICE, "pinned host allocation failed"); }
@@ -1158,7 +1169,7 @@ int Engine::run_frame_workspace(RunCtx& c) {
     }
     if (poison) {           // the host-visible outputs of this call, before the first kernel that writes them is enqueued
         if (host_pcm && !ss && pinned_pcm_) poison_host16(pinned_pcm_, std::min<size_t>((size_t)c.Ocap, pinned_pcm_cap_ / 2));
-        if (oc.lws && loud_host_) poison_host32(loud_host_, (size_t)B * sizeof(sts_loudness) / 4);
+        if ((oc.lws || oc.lst) && loud_host_) poison_host32(loud_host_, (size_t)B * sizeof(sts_loudness) / 4);
         if (oc.limws && lim_host_) poison_host32(lim_host_, (size_t)B * 4);
     }
 
@@ -1347,9 +1358,13 @@ int Engine::run_once(int B, const int32_t* const* ids, const int32_t* n, const i
     mfma_flops_ = 0; mfma_exec_ = 0; bf16_exec_ = 0; mfma_launches_ = 0; in_mfma_region_ = false;
 
     loud_res.clear(); lim_res.clear(); last_join_start.clear();
-    if (ss && loud_mode != 0)
+    if (ss && loud_mode != 0 && !loud_streaming)
         return fail(STS_EINVAL, "streaming is not available while loudness measurement or normalization is on (sts_set_loudness mode 0 first): "
                                 "normalizing needs the whole utterance before its first sample leaves");
+    if (ss && loud_mode == 2)
+        return fail(STS_EINVAL, "streaming is not available while loudness is normalized (sts_set_loudness mode 2), also with "
+                                "sts_set_loudness_streaming on: the gain needs the integrated loudness of the whole utterance before its first "
+                                "sample leaves -- measure in a stream (mode 1), then set the limiter's gain (sts_set_limiter) for the next calls");
     if (ss && eq_n > 0 && !eq_streaming)
         return fail(STS_EINVAL, "streaming is not available while an equaliser is set (sts_set_eq with 0 bands first): an IIR has no finite "
                                 "halo, and a state carried from chunk to chunk would make the PCM depend on the chunking -- unless the "
@@ -1493,7 +1508,8 @@ int Engine::run_stream_steps(RunCtx& c) {
     const size_t hp_off = (up_bytes + ((size_t)Ttot + B) * 4 + 255) & ~(size_t)255;
     const bool joined = c.join;       // a joined stream: the steps walk J, one chunk of the ONE signal per step (join_stream.hpp)
     const bool seq = c.oc.eqst;      // the EQ runs on every step's windows from its carried state (eq_stream.hpp)
-    const size_t tab_room = ((joined ? join_stream_tab_bytes(B, c.gain, seq) : stream_tab_bytes(B, c.gain, seq)) + 255) & ~(size_t)255;
+    const bool sld = c.oc.lst;       // loudness measures every step's windows from its carried state (loud_stream.hpp)
+    const size_t tab_room = ((joined ? join_stream_tab_bytes(B, c.gain, seq, sld) : stream_tab_bytes(B, c.gain, seq, sld)) + 255) & ~(size_t)255;
     const size_t pcm_bytes = (size_t)c.Ocap * 2 + 256;
     if (!ensure_pinned(hp_off + tab_room + pcm_bytes)) return fail(STS_EDEVICE, "pinned host allocation failed");
     c.pm = (int*)pinned_;
@@ -1531,6 +1547,34 @@ int Engine::run_stream_steps(RunCtx& c) {
         a.y = bf.wave_eq; a.pcm = oc.writer == OS_EQ ? dst : nullptr;
         a.E = bf.eqsE; a.state = bf.eqst; a.slot = eqt.slot; a.wtab = rows_dev;
         eq_stream_run(a, nw, tiles, stream);
+    };
+    // streamed loudness: the same bookkeeping for the signal loudness reads (the nearest running float stage in front of it); a step's
+    // rows join its table upload behind the EQ's, its two launches follow that stage, and the gate runs once behind the last step
+    LdsTrack ldt;
+    const int lsrc = oc.src[OS_LOUD];
+    double* ld_tsum = nullptr; float* ld_tpeak = nullptr; float* ld_gain = nullptr;
+    if (sld) {
+        if (loud_k_rate_ != out_rate) {
+            if (!loud_coef(out_rate, &loud_k_)) return fail(STS_EINVAL, "loudness: output rate outside [8000, 48000]");
+            loud_k_rate_ = out_rate;
+        }
+        const int nu = joined ? 1 : B;
+        std::vector<long long> Nu(nu);
+        if (joined) Nu[0] = out_count(c.FJ * hop);
+        else for (int b = 0; b < B; b++) Nu[b] = out_count((long long)lenF[b] * hop);
+        ldt.begin(nu);
+        const long long tiles = ldt.layout(Nu.data());
+        char* p = bf.ldres + (size_t)nu * 3 * 8;            // (in front: the gate's table {0, samples consumed, first tile} per utterance)
+        ld_tsum = (double*)p; p += (size_t)tiles * kLdsSlots * 8;
+        ld_tpeak = (float*)p; p += (size_t)tiles * 4;
+        ld_gain = (float*)p;
+    }
+    auto loud_step = [&](const long long* rows_dev, int nw, long long tiles) {
+        LoudStreamArgs a{};
+        a.x = c.stage_out(lsrc); a.k = loud_k_;
+        a.wtab = rows_dev; a.state = bf.ldst; a.slot = ldt.slot;
+        a.E = bf.ldsE; a.tsum = ld_tsum; a.tpeak = ld_tpeak;
+        loud_stream_run(a, nw, tiles, stream);
     };
     // The window of chunk frames [f0, f1) of an utterance of F frames: frames [w0, w1).  Its native samples [f0 hop, f1 hop) are, at the output
     // rate, the outputs j with ceil(f0 hop P / Q) <= j < ceil(f1 hop P / Q) = [j0, j1) of Nout (the halo covers the filter's K samples beyond the
@@ -1582,7 +1626,16 @@ int Engine::run_stream_steps(RunCtx& c) {
             memcpy(ht + eoff, &r, sizeof(r));
             etiles = eqs_tiles(r.e, r.o1);
         }
-        HIPCK(hipMemcpyAsync(c.d_win, ht, join_stream_tab_bytes(nw, c.gain, seq), hipMemcpyHostToDevice, stream));
+        const size_t loff = join_stream_tab_loud_off(nw, c.gain, seq);
+        long long ltiles = 1;
+        if (sld) {           // (a silence-only step too: the measurement advances over the join's zeros)
+            const bool at_out = lsrc == OS_EQ || lsrc == OS_RESAMPLE;       // (the window of J at the output rate, else the join's native one)
+            const LdsRow r = ldt.row(0, 0, at_out ? jt.jl0 : u0, at_out ? nrs : ulen, jt.j1);
+            if (const char* bad = lds_row_check(r, out_count(NJ))) return fail(STS_EDEVICE, bad);
+            memcpy(ht + loff, &r, sizeof(r));
+            ltiles = lds_tiles(r.e, r.j1);
+        }
+        HIPCK(hipMemcpyAsync(c.d_win, ht, join_stream_tab_bytes(nw, c.gain, seq, sld), hipMemcpyHostToDevice, stream));
         if (nw > 0) {
             const int rc = B == 1 ? run_decode(c, 1, (long)jt.Wtot, (int)jt.maxW, ti[0], ti[2]) : run_decode(c, nw, (long)jt.Wtot, (int)jt.maxW, 0, -1);
             if (rc != STS_OK) return rc;
@@ -1602,6 +1655,7 @@ int Engine::run_stream_steps(RunCtx& c) {
             resample_pcm(a, 1, nrs, stream);
         }
         if (seq) eq_step((const long long*)(bf.stab + eoff), 1, etiles);
+        if (sld) loud_step((const long long*)(bf.stab + loff), 1, ltiles);
         if (slim) {
             LimArgs a{};
             a.x = c.stage_out(oc.src[OS_LIMIT]);
@@ -1633,7 +1687,7 @@ int Engine::run_stream_steps(RunCtx& c) {
             long long* tm = (long long*)(ht + stream_tab_lim_off(nw));
             long long rsum = 0;                             // limiter: the resampler's float outputs of the widened ranges, packed
             wj0.assign(nw, 0); wn.assign(nw, 0); wdst.assign(nw, 0);
-            long Wtot = 0; int maxW = 0; long long max_out = 0, max_rs = 0, etiles = 1;
+            long Wtot = 0; int maxW = 0; long long max_out = 0, max_rs = 0, etiles = 1, ltiles = 1;
             for (int i = 0; i < nw; i++) {
                 const int b = wb[i];
                 const long F = lenF[b];
@@ -1652,6 +1706,14 @@ int Engine::run_stream_steps(RunCtx& c) {
                     memcpy(ht + stream_tab_eq_off(nw, c.gain) + (size_t)i * sizeof(EqsRow), &r, sizeof(r));
                     etiles = std::max(etiles, eqs_tiles(r.e, r.o1));
                 }
+                if (sld) {       // loudness reads the EQ's or the resampler's widened outputs, else the decode window at the native rate
+                    const LdsRow r = lsrc == OS_EQ ? ldt.row(b, rsum, w.jl0, nrs, w.j1)
+                                     : lsrc == OS_RESAMPLE ? ldt.row(b, slim ? rsum : dsum, w.jl0, nrs, w.j1)
+                                                           : ldt.row(b, (long long)Wtot * hop, (long long)w.w0 * hop, (long long)wlen * hop, w.j1);
+                    if (const char* bad = lds_row_check(r, w.Nout)) return fail(STS_EDEVICE, bad);
+                    memcpy(ht + stream_tab_loud_off(nw, c.gain, seq) + (size_t)i * sizeof(LdsRow), &r, sizeof(r));
+                    ltiles = std::max(ltiles, lds_tiles(r.e, r.j1));
+                }
                 tm[7 * i + 4] = w.j0; tm[7 * i + 5] = w.j1; tm[7 * i + 6] = dsum;
                 rsum += nrs; max_rs = std::max(max_rs, nrs);
                 wj0[i] = w.j0; wn[i] = nout; wdst[i] = dsum;
@@ -1660,7 +1722,7 @@ int Engine::run_stream_steps(RunCtx& c) {
             }
             ti[6 * nw] = (int)dsum;
             if (c.gain) { int* tu = (int*)(ht + stream_tab_utt_off(nw)); for (int i = 0; i < nw; i++) tu[i] = wb[i]; }     // (the gain kernel: each window's utterance)
-            HIPCK(hipMemcpyAsync(c.d_win, ht, stream_tab_bytes(nw, c.gain, seq), hipMemcpyHostToDevice, stream));
+            HIPCK(hipMemcpyAsync(c.d_win, ht, stream_tab_bytes(nw, c.gain, seq, sld), hipMemcpyHostToDevice, stream));
             // one utterance: its window by value (no table load in the decoder's kernels); several: the tables, also while one window is live
             int rc = B == 1 ? run_decode(c, 1, Wtot, maxW, ti[0], ti[2]) : run_decode(c, nw, Wtot, maxW, 0, -1);
             if (rc != STS_OK) return rc;
@@ -1676,6 +1738,7 @@ int Engine::run_stream_steps(RunCtx& c) {
                 stream_pack(bf.pcm, dst, c.d_win + 4 * nw, c.d_win + 5 * nw, nw, max_out, stream);
             }
             if (seq) eq_step((const long long*)(bf.stab + stream_tab_eq_off(nw, c.gain)), nw, etiles);
+            if (sld) loud_step((const long long*)(bf.stab + stream_tab_loud_off(nw, c.gain, seq)), nw, ltiles);
             if (slim) {          // every window of the step in one launch; it writes the packed chunks in place of the resampler / the pack
                 LimArgs a{};
                 a.x = c.stage_out(oc.src[OS_LIMIT]);
@@ -1695,15 +1758,30 @@ int Engine::run_stream_steps(RunCtx& c) {
             conv_math = 0;                                 // (run() restores the setting)
             k--;                                           // this step again, every window of it
             eqt.drop();                                    // (from the state the first attempt started from)
+            if (sld) ldt.drop();
             continue;
         }
         eqt.commit();
+        if (sld) ldt.commit();
         for (int i = 0; i < nw; i++) {                     // ascending utterance order
             const int b = wb[i];
             total_samples += wn[i];
             if (ss->delivered) ss->delivered[b] += (int32_t)wn[i];
             if (ss->cb(ss->user, b, hp + wdst[i], (int32_t)wn[i], (int32_t)wj0[i]) != 0) live[b] = 0;
         }
+    }
+    if (sld) {
+        // the gate, once, on what every utterance delivered: its results go to the host-mapped block, this synchronisation covers them
+        const int nu = joined ? 1 : B;
+        long long* hu = (long long*)ht;                     // (the step tables' pinned room: every upload from it has completed)
+        for (int b = 0; b < nu; b++) { hu[3 * b] = 0; hu[3 * b + 1] = ldt.e[b]; hu[3 * b + 2] = ldt.tbase[b]; }
+        HIPCK(hipMemcpyAsync(bf.ldres, hu, (size_t)nu * 3 * 8, hipMemcpyHostToDevice, stream));
+        LoudArgs g{};
+        g.k = loud_k_; g.target = loud_target; g.ceiling = loud_peak; g.no_clamp = oc.loud_no_clamp;
+        g.utab = (long long*)bf.ldres; g.tsum = ld_tsum; g.tpeak = ld_tpeak; g.gain = ld_gain; g.out = loud_dev_;
+        loud_gate_run(g, nu, stream);
+        HIPCK(hipStreamSynchronize(stream));
+        loud_res.assign((const sts_loudness*)loud_host_, (const sts_loudness*)loud_host_ + nu);
     }
     return STS_OK;
 }

@@ -257,6 +257,9 @@ public:
     // n_total (optional): samples delivered
     int run_joined_stream(int B, const int32_t* const* ids, const int32_t* n, const int32_t* sid, const float* ls, const sts_join* join,
                           int chunk_frames, int (*cb)(void*, int32_t, const int16_t*, int32_t, int32_t), void* user, int32_t* n_total);
+    // loudness in a stream (sts_set_loudness_streaming; loudness.hip's stream mode, loud_stream.hpp): off, a stream under mode 1 or 2 is
+    // refused; on, mode 1 measures what each step delivers from a state carried per utterance in the frame arena (mode 2 stays refused)
+    bool loud_streaming = false;
     // the equaliser in a stream (sts_set_eq_streaming; eq.hip's stream mode, eq_stream.hpp): off, a stream with bands set is refused; on,
     // every step runs the EQ behind the resampler on its windows from a state carried per utterance in the frame arena
     bool eq_streaming = false;

@@ -438,6 +438,20 @@ size_t loud_ws_bytes(int B, long long total_samples);
 void loud_ws_carve(LoudArgs& a, void* ws, int B, long long total_samples);
 // 3 launches (4 with pcm: the gain cast pcm = pcm_cast(x g) into pcm, packed like x); max_len = the longest utterance's sample count or more
 void loudness_run(const LoudArgs& a, int B, long long max_len, int16_t* pcm, hipStream_t st);
+// streaming (loud_stream.hpp has the row, the state's layout and the result tables): window w reads its row from wtab[8 w ..] -- the
+// utterance whose carried state it continues, its input window and the range it consumes.  state: [B][2] slots, read slot `slot`, written
+// slot 1 - slot.  E: [nwin][tiles] end states of the step.  tsum / tpeak: the call's tables, every touched tile's entries are written.
+struct LoudStreamArgs {
+    const float* x;
+    LoudCoef k;
+    const long long* wtab; char* state; int slot;
+    double* E; double* tsum; float* tpeak;
+};
+// one step: 2 launches over (max_tiles, nwin) workgroups; max_tiles = the most tiles one of its windows touches (lds_tiles)
+void loud_stream_run(const LoudStreamArgs& a, int nwin, long long max_tiles, hipStream_t st);
+// the gate alone (loud_gate_kernel, one launch) on result tables a stream filled: a.utab[3 b + 1] = the samples consumed,
+// a.utab[3 b + 2] = the utterance's first tile, a.tsum / a.tpeak / a.gain / a.out / a.k / a.target / a.ceiling / a.no_clamp as in a whole call
+void loud_gate_run(const LoudArgs& a, int B, hipStream_t st);
 
 // Look-ahead peak limiter (limiter.hip; the definition is there and in include/summertts_hip.h sts_set_limiter)
 constexpr int kLimMinRate = 8000, kLimMaxRate = 48000, kLimMaxH = 480;

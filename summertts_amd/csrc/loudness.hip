@@ -17,12 +17,14 @@
 
 #include "devmath.hpp"
 #include "kernels.hpp"
+#include "loud_stream.hpp"
 
 namespace sts {
 
 constexpr int LD_THREADS = 256, LD_R = 32, LD_TILE = LD_THREADS * LD_R;     // 8192 samples per workgroup
 constexpr int LD_SLOTS = 16;          // 100 ms sub-blocks one tile touches at most (S >= 800: 8192 / 800 + 2 <= 12)
 constexpr int LD_LDS = LD_TILE + LD_TILE / LD_R;                              // one pad float per chunk: conflict-free strided reads
+static_assert(LD_TILE == kLdsTile && LD_SLOTS == kLdsSlots, "loud_stream.hpp restates the tile and the slots per tile");
 
 bool kweight_coeffs(int rate, double c[10]) {
     if (rate < kLoudMinRate || rate > kLoudMaxRate) return false;
@@ -139,20 +141,15 @@ __device__ LdGeom ld_geom(const LoudArgs& a, int b, unsigned long long* s_red) {
     return g;
 }
 
-// Stages tile t of the utterance into LDS (sample p at p + p / LD_R) and scans its chunk maps: returns this lane's carry-in relative to a
-// zero tile start (Z) and, in et (every lane), the tile's zero-start end state.  Chunk k = samples [t LD_TILE + k LD_R, + r), r <= LD_R.
-__device__ void ld_tile_scan(const LoudArgs& a, const float* xu, long long N, long long t, float* xs, double (*wt)[4], double Z[4],
-                             double et[4], int& r, float& xm1, float& xm2) {
+// Scans the chunk maps of a tile staged in LDS (sample p at p + p / LD_R, zeros behind the tile's last sample; this lane's chunk k = tid
+// holds r <= LD_R samples and the input history (xm1, xm2)): returns this lane's carry-in relative to a zero tile start (Z) and, in et
+// (every lane), the tile's zero-start end state.  A lane reads lower lanes and earlier waves only: Z of chunk k is a function of the
+// chunks j < k, whatever lies behind them.
+__device__ __forceinline__ void ld_scan_staged(const LoudCoef& k, const float* xs, double (*wt)[4], double Z[4], double et[4], int r,
+                                               float xm1, float xm2) {
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    const long long t0 = t * LD_TILE;
-    const long long nt = N - t0 < LD_TILE ? N - t0 : LD_TILE;
-    for (int p = tid; p < LD_TILE; p += LD_THREADS) xs[p + p / LD_R] = p < nt ? xu[t0 + p] : 0.f;
-    const long long n0 = t0 + (long long)tid * LD_R;
-    r = N - n0 <= 0 ? 0 : (N - n0 < LD_R ? (int)(N - n0) : LD_R);
-    xm1 = r > 0 ? ld_hist(xu, n0 - 1) : 0.f; xm2 = r > 0 ? ld_hist(xu, n0 - 2) : 0.f;
-    __syncthreads();
     double e[4] = {0.0, 0.0, 0.0, 0.0}, d0 = 0.0, d1 = 0.0;
-    ld_chunk<false>(a.k, xs + tid * (LD_R + 1), r, xm1, xm2, e, 0, d0, d1);
+    ld_chunk<false>(k, xs + tid * (LD_R + 1), r, xm1, xm2, e, 0, d0, d1);
     // inclusive scan within the wave: P_l = sum_{j <= l} M^(l - j) e_j
     double P[4] = {e[0], e[1], e[2], e[3]};
 #pragma unroll
@@ -161,7 +158,7 @@ __device__ void ld_tile_scan(const LoudArgs& a, const float* xu, long long N, lo
         double q[4];
 #pragma unroll
         for (int i = 0; i < 4; i++) q[i] = __shfl_up(P[i], o, 64);
-        if (lane >= o) { double m[4]; mv4(a.k.Mp[d], q, m); for (int i = 0; i < 4; i++) P[i] += m[i]; }
+        if (lane >= o) { double m[4]; mv4(k.Mp[d], q, m); for (int i = 0; i < 4; i++) P[i] += m[i]; }
     }
     double Pex[4];
 #pragma unroll
@@ -173,12 +170,27 @@ __device__ void ld_tile_scan(const LoudArgs& a, const float* xu, long long N, lo
 #pragma unroll
     for (int q = 0; q < LD_THREADS / 64; q++) {
         if (q == w) for (int i = 0; i < 4; i++) Z[i] = W[i];
-        double m[4]; mv4(a.k.Mp[6], W, m);
+        double m[4]; mv4(k.Mp[6], W, m);
         for (int i = 0; i < 4; i++) W[i] = m[i] + wt[q][i];
     }
     for (int i = 0; i < 4; i++) et[i] = W[i];
-    mpow_apply(a.k, lane, Z);
+    mpow_apply(k, lane, Z);
     for (int i = 0; i < 4; i++) Z[i] += Pex[i];
+}
+
+// Stages tile t of the utterance into LDS (sample p at p + p / LD_R) and scans its chunk maps (ld_scan_staged).
+// Chunk k = samples [t LD_TILE + k LD_R, + r), r <= LD_R.
+__device__ __forceinline__ void ld_tile_scan(const LoudArgs& a, const float* xu, long long N, long long t, float* xs, double (*wt)[4],
+                                             double Z[4], double et[4], int& r, float& xm1, float& xm2) {
+    const int tid = threadIdx.x;
+    const long long t0 = t * LD_TILE;
+    const long long nt = N - t0 < LD_TILE ? N - t0 : LD_TILE;
+    for (int p = tid; p < LD_TILE; p += LD_THREADS) xs[p + p / LD_R] = p < nt ? xu[t0 + p] : 0.f;
+    const long long n0 = t0 + (long long)tid * LD_R;
+    r = N - n0 <= 0 ? 0 : (N - n0 < LD_R ? (int)(N - n0) : LD_R);
+    xm1 = r > 0 ? ld_hist(xu, n0 - 1) : 0.f; xm2 = r > 0 ? ld_hist(xu, n0 - 2) : 0.f;
+    __syncthreads();
+    ld_scan_staged(a.k, xs, wt, Z, et, r, xm1, xm2);
 }
 
 // launch 1: every tile's zero-start end state E_t; block (0, b) also records utterance b's geometry
@@ -202,13 +214,46 @@ __device__ __forceinline__ double wave_sum(double v) {
     return v;
 }
 
+// The true run of every chunk of a staged and scanned tile t whose last sample is utterance sample tend: S = the tile's carry S_t, Z this
+// lane's carry-in relative to a zero tile start.  Sums y^2 per 100 ms sub-block (slot s = sub-block sb0 + s; a fixed reduction tree per
+// slot) into ts[LD_SLOTS], max |x| of the tile into *tp.
+__device__ __forceinline__ void ld_tile_sums(const LoudCoef& k, const float* xs, double (*red)[LD_SLOTS], float* pk, long long t, long long tend,
+                                             int r, float xm1, float xm2, double S[4], const double Z[4], double* ts, float* tp) {
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    mpow_apply(k, tid, S);
+    for (int i = 0; i < 4; i++) S[i] += Z[i];
+    const int Ssb = k.S;
+    const long long n0 = t * LD_TILE + (long long)tid * LD_R;
+    const long long sb0 = (t * LD_TILE) / Ssb;
+    const long long bin0 = n0 / Ssb;
+    const int split = (int)((bin0 + 1) * Ssb - n0);
+    double acc0 = 0.0, acc1 = 0.0;
+    const float* xl = xs + tid * (LD_R + 1);
+    ld_chunk<true>(k, xl, r, xm1, xm2, S, split, acc0, acc1);
+    float p = 0.f;
+    for (int i = 0; i < r; i++) p = fmaxf(p, fabsf(xl[i]));
+    const int nslots = (int)(tend / Ssb - sb0 + 1);
+    const int s0 = (int)(bin0 - sb0);
+    for (int s = 0; s < nslots && s < LD_SLOTS; s++) {
+        double v = r > 0 ? (s == s0 ? acc0 : (s == s0 + 1 ? acc1 : 0.0)) : 0.0;
+        v = wave_sum(v);
+        if (lane == 0) red[w][s] = v;
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) p = fmaxf(p, __shfl_xor(p, o, 64));
+    if (lane == 0) pk[w] = p;
+    __syncthreads();
+    if (tid < LD_SLOTS) ts[tid] = tid < nslots ? ((red[0][tid] + red[1][tid]) + red[2][tid]) + red[3][tid] : 0.0;
+    if (tid == 0) *tp = fmaxf(fmaxf(pk[0], pk[1]), fmaxf(pk[2], pk[3]));
+}
+
 // launch 2: the tile's carry S_t, the true run of every chunk, y^2 per 100 ms sub-block and max |x| of the tile
 __global__ __launch_bounds__(LD_THREADS) void loud_measure_kernel(LoudArgs a) {
     __shared__ float xs[LD_LDS];
     __shared__ double wt[LD_THREADS / 64][4];
     __shared__ double red[LD_THREADS / 64][LD_SLOTS];
     __shared__ float pk[LD_THREADS / 64];
-    const int b = blockIdx.y, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int b = blockIdx.y;
     const long long off = a.utab[3 * b], N = a.utab[3 * b + 1], tbase = a.utab[3 * b + 2];
     const long long t = blockIdx.x;
     if (t * LD_TILE >= N) return;
@@ -222,34 +267,8 @@ __global__ __launch_bounds__(LD_THREADS) void loud_measure_kernel(LoudArgs a) {
         const double* Eq = a.E + (tbase + q) * 4;
         for (int i = 0; i < 4; i++) S[i] = m[i] + Eq[i];
     }
-    mpow_apply(a.k, tid, S);
-    for (int i = 0; i < 4; i++) S[i] += Z[i];
-    const int Ssb = a.k.S;
-    const long long n0 = t * LD_TILE + (long long)tid * LD_R;
-    const long long sb0 = (t * LD_TILE) / Ssb;
-    const long long bin0 = n0 / Ssb;
-    const int split = (int)((bin0 + 1) * Ssb - n0);
-    double acc0 = 0.0, acc1 = 0.0;
-    const float* xl = xs + tid * (LD_R + 1);
-    ld_chunk<true>(a.k, xl, r, xm1, xm2, S, split, acc0, acc1);
-    float p = 0.f;
-    for (int i = 0; i < r; i++) p = fmaxf(p, fabsf(xl[i]));
-    // sub-block sums of the tile: slot s = sub-block sb0 + s; a fixed reduction tree per slot
     const long long tend = (N - t * LD_TILE < LD_TILE ? N : (t + 1) * LD_TILE) - 1;
-    const int nslots = (int)(tend / Ssb - sb0 + 1);
-    const int s0 = (int)(bin0 - sb0);
-    for (int s = 0; s < nslots && s < LD_SLOTS; s++) {
-        double v = r > 0 ? (s == s0 ? acc0 : (s == s0 + 1 ? acc1 : 0.0)) : 0.0;
-        v = wave_sum(v);
-        if (lane == 0) red[w][s] = v;
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) p = fmaxf(p, __shfl_xor(p, o, 64));
-    if (lane == 0) pk[w] = p;
-    __syncthreads();
-    double* ts = a.tsum + (tbase + t) * LD_SLOTS;
-    if (tid < LD_SLOTS) ts[tid] = tid < nslots ? ((red[0][tid] + red[1][tid]) + red[2][tid]) + red[3][tid] : 0.0;
-    if (tid == 0) a.tpeak[tbase + t] = fmaxf(fmaxf(pk[0], pk[1]), fmaxf(pk[2], pk[3]));
+    ld_tile_sums(a.k, xs, red, pk, t, tend, r, xm1, xm2, S, Z, a.tsum + (tbase + t) * LD_SLOTS, a.tpeak + (tbase + t));
 }
 
 __device__ __forceinline__ double ld_subblock(const LoudArgs& a, long long tbase, long long j, int Ssb) {
@@ -353,6 +372,115 @@ void loudness_run(const LoudArgs& a, int B, long long max_len, int16_t* pcm, hip
     hipLaunchKernelGGL(loud_gate_kernel, dim3(B), dim3(LD_THREADS), 0, st, a);
     if (pcm && max_len > 0)
         hipLaunchKernelGGL(loud_gain_cast_kernel, dim3((unsigned)((max_len / LC_GROUP + 2 + LC_THREADS - 1) / LC_THREADS), B), dim3(LC_THREADS), 0, st, a, pcm);
+}
+
+// ---- stream mode (LoudStreamArgs; loud_stream.hpp, DESIGN.md 9d "streamed") -----------------------------------------------------------
+// A step continues utterance b from its carried state: input consumed up to e, the open tile te = e / LD_TILE with its carry S_te, its
+// input so far and the two samples in front of it.  Workgroup (i, w) owns tile te + i of window w, up to the tile that holds j1.  It
+// stages the tile's samples [t0, min(j1, t0 + LD_TILE)) -- those below e from the state, the others from the window, zeros beyond -- and
+// runs ld_scan_staged / ld_tile_sums on them as the whole call does on a tile of an utterance that ends at j1: a chunk's carry-in reads
+// the chunks in front of it only, so the sums of a tile the step completes are the whole call's, and those of the open tile are the
+// whole call's of x[0 .. j1).  Launch 1 leaves the zero-start end state of every touched tile (used only of tiles the step completes) and
+// the new open tile's input; launch 2 composes S_t = M^256 S_{t-1} + E_{t-1} upwards from S_te in the whole call's order and writes the
+// sums, the peak and the new carry.  The state is read from one slot and written to the other: a step that runs twice starts twice from
+// the same state, and writes the same sums.
+struct LdsView {
+    long long xbase, u0, j1, e, t0e, tbase;
+    const double* sS; const float *sprev, *sx;
+    double* dS; float *dprev, *dx;
+};
+__device__ __forceinline__ LdsView lds_view(const LoudStreamArgs& a, int w) {
+    const long long* r = a.wtab + (size_t)kLdsRow * w;
+    LdsView v;
+    const long long b = r[0];
+    v.xbase = r[1]; v.u0 = r[2]; v.j1 = r[4]; v.e = r[5]; v.tbase = r[6];
+    v.t0e = v.e / LD_TILE * LD_TILE;
+    char* rd = a.state + ((size_t)b * 2 + (size_t)a.slot) * kLdsSlotBytes;
+    char* wr = a.state + ((size_t)b * 2 + (size_t)(1 - a.slot)) * kLdsSlotBytes;
+    v.sS = (const double*)rd; v.sprev = (const float*)(rd + kLdsOffPrev); v.sx = (const float*)(rd + kLdsOffX);
+    v.dS = (double*)wr; v.dprev = (float*)(wr + kLdsOffPrev); v.dx = (float*)(wr + kLdsOffX);
+    return v;
+}
+// input sample n < j1 of the utterance: the window from e on, the state below it (the open tile, then the two samples in front of it)
+__device__ __forceinline__ float lds_x(const LoudStreamArgs& a, const LdsView& v, long long n) {
+    if (n < 0) return 0.f;
+    if (n >= v.e) return a.x[v.xbase + (n - v.u0)];
+    if (n >= v.t0e) return v.sx[n - v.t0e];
+    return v.sprev[v.t0e - 1 - n];
+}
+// Stages the tile at t0's samples [0, nt) into LDS, zeros behind them, and sets this lane's chunk.  Ends with the barrier.
+__device__ __forceinline__ void lds_stage(const LoudStreamArgs& a, const LdsView& v, long long t0, int nt, float* xs, int& r, float& xm1,
+                                          float& xm2) {
+    const int tid = threadIdx.x;
+    const int pe = (int)(v.e - t0 < 0 ? 0 : (v.e - t0 < nt ? v.e - t0 : nt));      // [0, pe): consumed before this step (the open tile only)
+    const float* xw = a.x + (v.xbase + (t0 - v.u0));                                // tile sample p >= pe is xw[p]
+    for (int p = tid; p < LD_TILE; p += LD_THREADS) xs[p + p / LD_R] = p < pe ? v.sx[p] : (p < nt ? xw[p] : 0.f);
+    const int c0 = tid * LD_R;
+    r = nt - c0 <= 0 ? 0 : (nt - c0 < LD_R ? nt - c0 : LD_R);
+    xm1 = r > 0 ? lds_x(a, v, t0 + c0 - 1) : 0.f; xm2 = r > 0 ? lds_x(a, v, t0 + c0 - 2) : 0.f;
+    __syncthreads();
+}
+
+// stream launch 1: the zero-start end state of every tile the step touches; the tile that holds j1 leaves its input as the new open tile's
+__global__ __launch_bounds__(LD_THREADS) void loud_stream_scan_kernel(LoudStreamArgs a) {
+    __shared__ float xs[LD_LDS];
+    __shared__ double wt[LD_THREADS / 64][4];
+    const int w = blockIdx.y, tid = threadIdx.x;
+    const LdsView v = lds_view(a, w);
+    const long long t0 = v.t0e + (long long)blockIdx.x * LD_TILE;
+    if (t0 > v.j1) return;
+    const int nt = (int)(v.j1 - t0 < LD_TILE ? v.j1 - t0 : LD_TILE);
+    int r; float xm1, xm2;
+    lds_stage(a, v, t0, nt, xs, r, xm1, xm2);
+    if (nt < LD_TILE) {         // (j1 lies in this tile: it is the open tile of the next step)
+        for (int p = tid; p < nt; p += LD_THREADS) v.dx[p] = xs[p + p / LD_R];
+        if (tid < 2) v.dprev[tid] = lds_x(a, v, t0 - 1 - tid);
+    }
+    double Z[4], et[4];
+    ld_scan_staged(a.k, xs, wt, Z, et, r, xm1, xm2);
+    if (tid < 4) a.E[((size_t)w * gridDim.x + blockIdx.x) * 4 + tid] = et[tid];
+}
+
+// stream launch 2: the tile's carry from the open tile's, the true run of every chunk, the tile's sums and peak, the new carry
+__global__ __launch_bounds__(LD_THREADS) void loud_stream_measure_kernel(LoudStreamArgs a) {
+    __shared__ float xs[LD_LDS];
+    __shared__ double wt[LD_THREADS / 64][4];
+    __shared__ double red[LD_THREADS / 64][LD_SLOTS];
+    __shared__ float pk[LD_THREADS / 64];
+    const int w = blockIdx.y, tid = threadIdx.x;
+    const LdsView v = lds_view(a, w);
+    const long long t0 = v.t0e + (long long)blockIdx.x * LD_TILE;
+    if (t0 > v.j1) return;
+    const int nt = (int)(v.j1 - t0 < LD_TILE ? v.j1 - t0 : LD_TILE);
+    int r; float xm1, xm2;
+    lds_stage(a, v, t0, nt, xs, r, xm1, xm2);
+    double Z[4], et[4];
+    ld_scan_staged(a.k, xs, wt, Z, et, r, xm1, xm2);
+    // S_t upwards from the open tile's carry (zero at the utterance's start), the whole call's loop from there on
+    double S[4];
+    for (int i = 0; i < 4; i++) S[i] = v.e > 0 ? v.sS[i] : 0.0;
+    const double* E = a.E + (size_t)w * gridDim.x * 4;
+    for (int q = 0; q < (int)blockIdx.x; q++) {
+        double m[4]; mv4(a.k.Mp[8], S, m);
+        const double* Eq = E + (size_t)q * 4;
+        for (int i = 0; i < 4; i++) S[i] = m[i] + Eq[i];
+    }
+    if (nt < LD_TILE && tid < 4) v.dS[tid] = S[tid];
+    if (nt == 0) return;        // (j1 on a tile's edge: the new open tile is still empty -- its carry above is all there is to it)
+    const long long t = t0 / LD_TILE;
+    ld_tile_sums(a.k, xs, red, pk, t, t0 + nt - 1, r, xm1, xm2, S, Z, a.tsum + (v.tbase + t) * LD_SLOTS, a.tpeak + (v.tbase + t));
+}
+
+void loud_stream_run(const LoudStreamArgs& a, int nwin, long long max_tiles, hipStream_t st) {
+    if (nwin <= 0 || max_tiles <= 0 || !a.wtab || !a.state || !a.E || !a.tsum || !a.tpeak) return;
+    const dim3 grid((unsigned)max_tiles, nwin);
+    hipLaunchKernelGGL(loud_stream_scan_kernel, grid, dim3(LD_THREADS), 0, st, a);
+    hipLaunchKernelGGL(loud_stream_measure_kernel, grid, dim3(LD_THREADS), 0, st, a);
+}
+
+void loud_gate_run(const LoudArgs& a, int B, hipStream_t st) {
+    if (B <= 0) return;
+    hipLaunchKernelGGL(loud_gate_kernel, dim3(B), dim3(LD_THREADS), 0, st, a);
 }
 
 }  // namespace sts

@@ -3,6 +3,7 @@
 #pragma once
 #include "engine.hpp"
 #include "eq_stream.hpp"
+#include "loud_stream.hpp"
 #include "out_chain.hpp"
 #include "join_stream.hpp"
 
@@ -48,6 +49,9 @@ struct BufF {
     float* wave_eq; char* eqws;
     // a stream that runs the EQ only (null otherwise): the carried state [B][2] slots (eq_stream.hpp) and the step's tile end states
     char* eqst; double* eqsE;
+    // a stream that measures loudness only (null otherwise): the carried state [B][2] slots (loud_stream.hpp), the step's tile end states,
+    // the call's result tables (lds_res_bytes)
+    char* ldst; double* ldsE; char* ldres;
 };
 // Streaming, the tables of one step with nw windows (one upload, c.d_win points at them): ints [zoff nw | coff nw | wlen nw | sid nw |
 // pack source nw | packed destination nw + 1], then from an 8-byte boundary the resampler's long long [nw][5] = {u0, L_utt, j0, j1, obase}
@@ -61,12 +65,22 @@ static inline size_t stream_tab_eq_off(int nw, bool gain) { return (stream_tab_u
 static inline size_t stream_tab_bytes(int nw, bool gain = false, bool eq = false) {
     return eq ? stream_tab_eq_off(nw, gain) + (size_t)nw * kEqsRow * 8 : stream_tab_utt_off(nw) + (gain ? (size_t)nw * 4 : 0);
 }
+// a stream that measures loudness: behind all of that, from the next 8-byte boundary, its rows, long long [nw][8] (loud_stream.hpp LdsRow)
+static inline size_t stream_tab_loud_off(int nw, bool gain, bool eq) { return (stream_tab_bytes(nw, gain, eq) + 7) & ~(size_t)7; }
+static inline size_t stream_tab_bytes(int nw, bool gain, bool eq, bool loud) {
+    return loud ? stream_tab_loud_off(nw, gain, eq) + (size_t)nw * kLdsRow * 8 : stream_tab_bytes(nw, gain, eq);
+}
 // a joined stream: the same tables for the step's nw decode windows, and from the next 8-byte boundary the ONE window of J for the
 // resampler (long long [5]) and the limiter (long long [7]), then the windowed join's rows, long long [nw][5] (join_stream.hpp JsRow)
 static inline size_t join_stream_tab_j_off(int nw, bool gain) { return (stream_tab_bytes(nw, gain) + 7) & ~(size_t)7; }
 // (a joined stream that runs the EQ: behind the rows the one EqsRow of J)
 static inline size_t join_stream_tab_eq_off(int nw, bool gain) { return join_stream_tab_j_off(nw, gain) + (size_t)(12 + 5 * (size_t)nw) * 8; }
 static inline size_t join_stream_tab_bytes(int nw, bool gain, bool eq = false) { return join_stream_tab_eq_off(nw, gain) + (eq ? (size_t)kEqsRow * 8 : 0); }
+// (a joined stream that measures loudness: behind that the one LdsRow of J)
+static inline size_t join_stream_tab_loud_off(int nw, bool gain, bool eq) { return join_stream_tab_bytes(nw, gain, eq); }
+static inline size_t join_stream_tab_bytes(int nw, bool gain, bool eq, bool loud) {
+    return join_stream_tab_bytes(nw, gain, eq) + (loud ? (size_t)kLdsRow * 8 : 0);
+}
 
 // Everything a run's stages share: batch geometry, workspace pointers, host / device tables.  Engine::run() fills it stage by
 // stage; the stage functions below see its fields under the names the pipeline has always used (RUN_ALIASES).

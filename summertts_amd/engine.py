@@ -254,6 +254,10 @@ def load_library() -> C.CDLL:
     lib.sts_multi_set_loudness.argtypes = [C.c_void_p, C.c_int, C.c_float, C.c_float]
     lib.sts_kweight_coeffs.argtypes = [C.c_int32, C.c_void_p]
     lib.sts_loudness_measure.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_void_p]
+    lib.sts_set_loudness_streaming.argtypes = [C.c_void_p, C.c_int]
+    lib.sts_get_loudness_streaming.argtypes = [C.c_void_p]
+    lib.sts_loudness_measure_chunked.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_void_p,
+                                                 C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
     lib.sts_set_limiter.argtypes = [C.c_void_p, C.c_int, C.c_float, C.c_float, C.c_float]
     lib.sts_get_limiter_mode.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float)]
     lib.sts_get_limiter.argtypes = [C.c_void_p, C.c_void_p, C.c_int64]
@@ -358,6 +362,7 @@ EXPORTED_SYMBOLS = [
     "sts_infer_ids_joined_stream", "sts_join_apply_range",
     "sts_set_eq", "sts_get_eq", "sts_eq_check", "sts_eq_design", "sts_eq_apply", "sts_pool_set_eq", "sts_multi_set_eq",
     "sts_set_eq_streaming", "sts_get_eq_streaming", "sts_pool_set_eq_streaming", "sts_eq_apply_chunked",
+    "sts_set_loudness_streaming", "sts_get_loudness_streaming", "sts_loudness_measure_chunked",
 ]
 
 
@@ -656,6 +661,31 @@ def loudness_measure(signals, rate: int, target_lufs: float = -16.0, peak_dbfs: 
     _check(lib, lib.sts_loudness_measure(int(device), x.ctypes.data, lens.ctypes.data, len(sig), int(rate), float(target_lufs),
                                          float(peak_dbfs), out.ctypes.data))
     return out
+
+
+def loudness_measure_chunked(signals, rate: int, bounds, back: int = 0, target_lufs: float = -16.0, peak_dbfs: float = -1.0,
+                             device: int = 0, want_partial: bool = True):
+    """Loudness's STREAM-mode kernels on each float signal in ``signals`` (sts_loudness_measure_chunked): step k consumes
+    [bounds[k], bounds[k + 1]) of every signal that reaches it (the last step: to the end) and presents the window widened by ``back``
+    samples on either side -> (out, partial): structured arrays of LOUDNESS_DTYPE, ``out[b]`` the final result and ``partial[k][b]`` the
+    result as if the call had stopped behind step k (None unless ``want_partial``).  Both buffers carry a sentinel entry behind their
+    end, which the library must leave alone."""
+    lib = load_library()
+    sig = [np.ascontiguousarray(s, dtype=np.float32).ravel() for s in signals]
+    lens = np.asarray([s.size for s in sig], np.int64)
+    bnd = np.ascontiguousarray(bounds, dtype=np.int64).ravel()
+    K, B = int(bnd.size), len(sig)
+    x = np.concatenate(sig) if sig and lens.sum() > 0 else np.zeros(1, np.float32)
+    sentinel = np.array([(-1234.5, -7.0, -9.0, -77)], LOUDNESS_DTYPE)
+    out = np.repeat(sentinel, B + 1)
+    part = np.repeat(sentinel, K * B + 1)
+    _check(lib, lib.sts_loudness_measure_chunked(int(device), x.ctypes.data, lens.ctypes.data, B, int(rate), float(target_lufs), float(peak_dbfs),
+                                                 bnd.ctypes.data, K, int(back), out.ctypes.data, part.ctypes.data if want_partial else None))
+    if out[B:].tobytes() != sentinel.tobytes() or part[K * B:].tobytes() != sentinel.tobytes():
+        raise StsError("sts_loudness_measure_chunked wrote behind its results")
+    if not want_partial and part.tobytes() != np.repeat(sentinel, K * B + 1).tobytes():
+        raise StsError("sts_loudness_measure_chunked wrote partial results nobody asked for")
+    return out[:B].copy(), (part[:K * B].reshape(K, B).copy() if want_partial else None)
 
 
 LIMITER_OFF, LIMITER_ON = 0, 1
@@ -1052,7 +1082,8 @@ class Synthesizer:
         return m.value, t.value, p.value
 
     def loudness(self) -> np.ndarray:
-        """Results of the last whole-utterance call, one per utterance in call order (LOUDNESS_DTYPE; empty in mode LOUD_OFF)."""
+        """Results of the last whole-utterance call, or of the last stream that measured (``set_loudness_streaming``), one per utterance
+        in call order (LOUDNESS_DTYPE; empty in mode LOUD_OFF)."""
         n = self.lib.sts_get_loudness(self.h, None, 0)
         if n < 0:
             _check(self.lib, n)
@@ -1062,6 +1093,17 @@ class Synthesizer:
             if rc < 0:
                 _check(self.lib, rc)
         return out
+
+    def set_loudness_streaming(self, enable: bool = True):
+        """Let streaming calls run under LOUD_MEASURE (sts_set_loudness_streaming): each step measures the samples it delivers from a state
+        carried per utterance, the chunks are those of a stream without loudness, and ``loudness()`` afterwards returns the whole call's
+        entries for every chunk size (of a stopped utterance: the measurement of what was delivered).  LOUD_NORMALIZE stays refused in a
+        stream.  Off by default; persists."""
+        _check(self.lib, self.lib.sts_set_loudness_streaming(self.h, 1 if enable else 0))
+
+    def loudness_streaming(self) -> bool:
+        """The switch set by ``set_loudness_streaming``."""
+        return bool(self.lib.sts_get_loudness_streaming(self.h))
 
     def set_limiter(self, mode: int, gain_db: float = 0.0, ceiling_dbfs: float = -1.0, lookahead_ms: float = 5.0):
         """Look-ahead peak limiter of every later whole-utterance call (include/summertts_hip.h sts_set_limiter): LIMITER_OFF or

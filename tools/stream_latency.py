@@ -11,7 +11,9 @@ the utterances (min / p50 / max), time to the last chunk, and seconds of audio d
 timed repeats after one warm-up of every shape.  The launch-ahead memo is off, so (c) waits for its frame counts as (a) and (b) do.
 --rate R: PCM at R Hz (sts_set_output_rate).  --direct 1: the batched stream's step output goes to mapped pinned memory (sts_debug_set STS_DBG_STREAM_DIRECT) instead of one
 download.  --eq 1: the 4-band equaliser of DESIGN.md 9j's cost table on every call, streamed from its carried state
-(sts_set_eq_streaming); --eq 0 (default) sets neither bands nor the switch.  Prints one JSON line per row.
+(sts_set_eq_streaming); --eq 0 (default) sets neither bands nor the switch.  --loud 1: every call measures its loudness (sts_set_loudness
+mode 1), the streams from their carried state (sts_set_loudness_streaming; DESIGN.md 9d "streamed"); --loud 0 (default) sets neither the
+mode nor the switch.  Prints one JSON line per row.
 
 --joined: a paragraph instead -- --sentences sentences (default 32) of 64 to 256 phonemes joined with gaps of 8 frames and
 a 5 ms fade, three ways:
@@ -98,6 +100,7 @@ def main() -> None:
     ap.add_argument("--direct", type=int, default=0)
     ap.add_argument("--rate", type=int, default=0, help="output sample rate (0: the native 16 kHz)")
     ap.add_argument("--eq", type=int, default=0, help="1: the 4-band EQ of DESIGN.md 9j on every call, streamed (sts_set_eq_streaming)")
+    ap.add_argument("--loud", type=int, default=0, help="1: loudness mode 1 on every call, measured in the streams (sts_set_loudness_streaming)")
     ap.add_argument("--joined", action="store_true", help="a paragraph: joined stream against the whole joined call and single streams in turn")
     ap.add_argument("--sentences", type=int, default=32)
     a = ap.parse_args()
@@ -115,6 +118,9 @@ def main() -> None:
         if a.eq:
             syn.set_eq(EQ_BANDS)
             syn.set_eq_streaming(True)
+        if a.loud:
+            syn.set_loudness(engine.LOUD_MEASURE)
+            syn.set_loudness_streaming(True)
         for B in [int(v) for v in a.batches.split(",")]:
             ids = _paragraph(cfg, B) if a.joined else [sb.synthetic_ids(a.phonemes, cfg.vocab, salt=u) for u in range(B)]
             for chunk in [int(v) for v in a.chunks.split(",")]:
@@ -130,7 +136,7 @@ def main() -> None:
                            "first_ms_max": med([max(r[0]) * 1e3 for r in runs]),
                            "last_ms": med([r[1] * 1e3 for r in runs]),
                            "audio_s_per_wall_s": med([r[2] / rate / r[3] for r in runs]),
-                           "rate": rate, "direct": a.direct, "eq": a.eq, "reps": a.reps}
+                           "rate": rate, "direct": a.direct, "eq": a.eq, "loud": a.loud, "reps": a.reps}
                     print(json.dumps(row), flush=True)
         syn.close()
 
