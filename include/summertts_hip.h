@@ -617,7 +617,7 @@ enum { STS_DBG_ATTN_BLOCK_MIN_WGS = 1,
        STS_DBG_DDS_TAIL = 8 /* stochastic duration predictor: 1 (default) a ConvFlow's projection + spline step ride in its last DDSConv layer's launch, 0 three launches */,
        STS_DBG_ATTN_REG = 7 /* one-query attention: 1 (default) operands in registers (attention_reg_kernel), 0 the round-1 kernel */,
        STS_DBG_LAUNCH_AHEAD = 6 /* one-utterance calls and packed batches: 1 (default) a request the engine has served before (same ids, speaker, length scale: the frame count is a pure function of them) enqueues flow + decoder before the count reaches the host, 0 the host always waits for it, 2 (tests) the memo is keyed by the phoneme count alone -- provokes the repeat that answers a hash collision */,
-       STS_DBG_FLOW_FUSED = 5 /* reverse flow: 1 (default) one launch per WaveNet layer (wn_flow.hip, under the two-term fp16 arithmetic), 0 one launch per conv */ };
+       STS_DBG_FLOW_FUSED = 5 /* reverse flow: 1 (default) one launch per WaveNet layer (wn_flow.hip, under the two-term fp16 arithmetic) where the grid is one round of workgroups, with 16 output frames per workgroup where 32 would leave half the compute units without one; 0 one launch per conv; 2 / 3 (tests, A/B) one launch per layer at any size with 32 / 16 frames per workgroup -- 1, 2 and 3 return the same bits */ };
 /* ABI 10, sts_infer_ids_batch_stream: STS_DBG_STREAM_RETRY_STEP (tests) -- under conv math 3 the overflow word counts as raised after step k
  * (value k; -1 = off), which takes the split-bf16 repeat of that step (k > 0) or of the whole call (k = 0); STS_DBG_STREAM_DIRECT -- 1 the
  * last kernel of a step writes the step's chunks into mapped pinned host memory itself, 0 (default) one download per step */

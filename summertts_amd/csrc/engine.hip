@@ -62,6 +62,7 @@ int Engine::init(const float* blob, int64_t bytes, int dev) {
     if (dev < 0 || dev >= count) return fail(STS_EINVAL, "device index out of range");
     device = dev;
     HIPCK(hipSetDevice(dev));
+    HIPCK(hipDeviceGetAttribute(&n_cus, hipDeviceAttributeMultiprocessorCount, dev));
     HIPCK(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
     for (auto& e : ev_) HIPCK(hipEventCreate(&e));
     HIPCK(hipEventCreateWithFlags(&ev_fork_, hipEventDisableTiming));
@@ -1079,7 +1080,12 @@ int Engine::run_frame_workspace(RunCtx& c) {
         long tiles = 0;
         if (B == 1) tiles = (Ftot + 31) / 32;
         else for (int b = 0; b < B; b++) tiles += (p_lenF[b] + 31) / 32;
-        use_ff = tiles * M.cp[0].ff.G <= 256;
+        if (flow_fused < 2) use_ff = tiles * M.cp[0].ff.G <= 256;       // (2 / 3, tests and A/B: at any size)
+        // 16 frames per workgroup where the 32-frame grid would leave at least half the CUs without one (one utterance of 668 frames: 126
+        // workgroups on 256 CUs).  The two widths return the same bits, so this one choice may look at the frame count itself (a call
+        // launched ahead: the count it expects) and not at the capacity, without the two kinds of call ever differing in a sample
+        const long live = B == 1 ? ((c.ahead && !c.predF.empty() ? c.predF[0] : c.Ftot) + 31) / 32 : tiles;
+        c.ffNT = flow_fused == 3 || (flow_fused == 1 && live * M.cp[0].ff.G <= n_cus / 2) ? 16 : 32;
     }
     c.use_ff = use_ff; c.ffG = use_ff ? M.cp[0].ff.G : 0;
     BufF& bf = c.bf;
@@ -1248,7 +1254,7 @@ int Engine::run_flow(RunCtx& c) {
                 A.w_c = ff.wc[l]; A.s_c = ff.sc[l]; A.rows_c = ff.rows_c[l]; A.rows_res = ff.rows_res[l];
                 A.b_res = ff.b_res[l]; A.b_m = ff.b_m;
                 A.ovf = ovf_;
-                flow_layer(A, stream);
+                flow_layer(A, stream, c.ffNT);
                 if (l == 0 && pend_set >= 0) { cur[x0h] = A.x0_out; pend_set = -1; }
             }
             ConvOpt os; os.epi = EPI_SUB;

@@ -178,8 +178,10 @@ public:
     int chain_streams_dbg = -1;        // lab: stage mask -- the chains of the masked decoder stages as per-chain launches on three prioritised streams instead of grouped launches
     int h2p = 1;                       // 1: the wide ResBlock stages (C % 128 == 0) on pre-split channel-minor activations (conv_h2p.hip; two-term fp16 arithmetic only), 0: the staged kernels
     int h2p_tile = -1;                 // lab: tile code of conv_h2p_group (-1: automatic)
-    int flow_fused = 1;                // 1: the reverse flow as one launch per WaveNet layer where eligible (wn_flow.hip; two-term fp16 arithmetic only);
-                                       // 0: one launch per conv (sts_debug_set STS_DBG_FLOW_FUSED)
+    int flow_fused = 1;                // 1: the reverse flow as one launch per WaveNet layer where eligible (wn_flow.hip; two-term fp16 arithmetic only),
+                                       // 16-frame tiles where 32-frame tiles would leave half the CUs without a workgroup; 0: one launch per conv;
+                                       // 2 / 3: one launch per layer at any size, 32- / 16-frame tiles (sts_debug_set STS_DBG_FLOW_FUSED)
+    int n_cus = 0;                     // compute units of the device (init)
     int stream_retry_step = -1;        // tests (STS_DBG_STREAM_RETRY_STEP): a stream (of one utterance or several) under conv_math 3 treats the overflow word as raised after step k
     int stream_direct = 0;             // streaming, any B: 1 the pack / resample / limiter kernel writes each step's chunks into mapped pinned host memory, 0 one download (STS_DBG_STREAM_DIRECT)
     unsigned poison = 0;               // tests (STS_DBG_POISON): 32-bit pattern every call fills its workspace arenas and host outputs with; 0 = off

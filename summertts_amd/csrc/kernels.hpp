@@ -192,7 +192,7 @@ struct FlowFinishArgs {
 };
 bool flow_layer_shape_ok(int H, int half, int k, int dil, int n_layers);
 int flow_layer_groups(int H);
-void flow_layer(const FlowLayerArgs& a, hipStream_t st);
+void flow_layer(const FlowLayerArgs& a, hipStream_t st, int nt = 32);       // nt: output frames per workgroup, 32 or 16 (same bits)
 void flow_finish(const FlowFinishArgs& a, hipStream_t st);
 
 // ---- launchers (all asynchronous on `st`) ------------------------------------------------------

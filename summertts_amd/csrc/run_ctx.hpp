@@ -111,7 +111,7 @@ struct Engine::RunCtx {
     int halo = 0; long Wcap = 0; int upS = 1; long Lsb = 0; int sbC = 0;
     long long Ocap = 0;             // PCM capacity in output samples (== Wcap * hop at the native rate)
     bool bstream = false;           // a stream of several utterances: window i of a step is not utterance i (run_decode gathers the conditioning per window)
-    bool use_ff = false; int ffG = 0;
+    bool use_ff = false; int ffG = 0, ffNT = 32;     // the one-launch-per-layer flow: taken, its channel groups, output frames per workgroup (32 / 16)
     // the output chain of this run (Engine::plan_output), and next to it the limiter's design, the resampler's ratio (1 / 1: native rate)
     // and the EQ's band count
     OutChain oc{}; LimiterDesign limd; int rsP = 1, rsQ = 1, eqS = 0;

@@ -23,6 +23,15 @@
 //     accumulation), operands through 16-byte loads: the intermediate tensors (h, partials, macc) are CHANNEL-MINOR [frame][channel],
 //     which makes a lane's 4 accumulator rows one 16-byte store and the staged window a run of contiguous 768-byte rows.
 //   Launches per coupling: n_layers (4) instead of 2 n_layers + 2 (10); per step 17 instead of 40.
+//
+// Tile width.  The kernel exists for NT = 32 and NT = 16 output frames per workgroup (flow_layer's `nt`; the engine takes 16 where 32-frame
+// tiles would leave at least half the CUs without a workgroup: one utterance of 668 frames is 21 x 6 = 126 workgroups of one per CU).  A
+// 16-frame tile stages 16 + 2 halo positions (one round of loads instead of two at H = 192), runs `pre` on one column tile and finishes
+// one (tanh, sigmoid) pair per lane; the gate conv and the 1x1 conv keep their 32-column MFMA tile, whose upper 16 columns are dead.  Every
+// live column's sums keep their order (same K order, partials in slice order), so the two widths return the same bits.  Measured on one
+// MI355X (profiles/flow16_ab_log.md): later layers 16.65 -> 14.84 us per launch, first layers 22.37 -> 19.61 us, the 17 launches of a step
+// 294 -> 266 us; the step 2.511 -> 2.484 ms.  The block -> (group, tile) order of the 16-frame grid (flow_block_map) keeps a group's weights
+// in one L2 where it can; plain round-robin order measured the same within the spread (269 us, 2.490 ms).
 #include "conv_bf3_dev.hpp"
 
 namespace sts {
@@ -31,8 +40,13 @@ namespace sts {
 int tile_trace_bind_flow(long long* buf, unsigned capacity_records) { return tile_trace_bind(buf, capacity_records); }
 #endif
 
-constexpr int FL_WIN = 64;            // staged window: 32 output frames + 2 * halo <= 64 positions
-constexpr int FL_NT = 32;             // output frames per workgroup
+// Output frames per workgroup: NT = 32 or 16 (a template parameter of flow_layer_kernel).  The gate conv and the 1x1 conv always compute one
+// 32-column MFMA tile; with NT = 16 its upper 16 columns are dead: never parked, stored or counted into amax.
+constexpr int FL_COLS = 32;           // columns of the MFMA tile
+// window positions a chunk plane holds in LDS.  Staged: NT + 2 * halo; read by the gate conv: FL_COLS + 2 * halo (the dead columns' taps
+// lie past the staged window: whatever LDS holds there only reaches accumulator columns nobody uses) -- both inside the plane for
+// 2 * halo <= NT (flow_layer_shape_ok: k - 1 <= 14)
+constexpr int fl_win(int NT) { return NT + 32; }
 constexpr int FL_UR = 2;              // staging: (quad of channels, position) units per thread and round (each with up to 9 16-byte loads in flight)
 constexpr int FL_MAXG = 8;            // channel groups (partial-sum slices) at most
 
@@ -72,14 +86,65 @@ __device__ __forceinline__ void split4h(const float (&x)[4], unsigned (&hi)[2], 
 // itself reads LDS only.
 constexpr int FL_WAVES = 8;
 constexpr int FL_GSTEPS = 16;         // gate-conv steps (16 channels x 1 tap) a wave may own: H k / (16 KS) <= 16
-template <bool L0>        // L0: first layer of a coupling (x0 staging + `pre` inside the launch) -- separate kernels, separate register budgets
+
+// 16-frame tiles: block -> (channel group g, tile index `rest` over the batch's T tiles), every (g, rest) exactly once; false: no work.
+// A 16-frame grid wants every CU, so it cannot leave the classes G .. 7 of blockIdx % 8 empty as the 32-frame grid does.  Blocks b and
+// b + 8 were observed to share an XCD (and its L2); nothing but speed rests on that.
+//   STS_FLOW_MAP 0 (default): class g < G is group g's home, so its weight slice stays in one L2 as far as possible.  Per period of G
+//     slots (slot = blockIdx / 8) a group has 8 tiles: G run on its home class, 8 - G on the spill classes G .. 7, which take the groups
+//     in order (G = 6: groups 0-2 on class 6, 3-5 on class 7).  Tiles rise with the slot, so the tiles past the utterance's real length
+//     (the grid is sized by the frame capacity: 704 frames = 44 tiles for 668 frames = 42) end every class's list: at G = 6 the home
+//     classes run 32 live workgroups each and the spill classes 30, one round on 32 CUs per XCD.  (Group-major spill lists would put
+//     33 live workgroups on each home class.)
+//   STS_FLOW_MAP 1: plain (tile, g) round-robin, every L2 pulls every group's weights.
+#ifndef STS_FLOW_MAP
+#define STS_FLOW_MAP 0
+#endif
+__host__ __device__ __forceinline__ int flow_grid16(int G, int T) { return STS_FLOW_MAP == 1 ? T * G : 8 * G * ((T + 7) >> 3); }
+// f(integral_constant<int, n>) for a uniform slice count n in 0 .. FL_MAXG: the staging loops are compiled once per count, each with
+// exactly its loads in flight and no test inside
+template <class F>
+__device__ __forceinline__ void fl_slices(int n, F&& f) {
+    switch (n) {
+        case 0: f(std::integral_constant<int, 0>{}); break;
+        case 1: f(std::integral_constant<int, 1>{}); break;
+        case 2: f(std::integral_constant<int, 2>{}); break;
+        case 3: f(std::integral_constant<int, 3>{}); break;
+        case 4: f(std::integral_constant<int, 4>{}); break;
+        case 5: f(std::integral_constant<int, 5>{}); break;
+        case 6: f(std::integral_constant<int, 6>{}); break;
+        case 7: f(std::integral_constant<int, 7>{}); break;
+        default: f(std::integral_constant<int, 8>{}); break;
+    }
+}
+__device__ __forceinline__ bool flow_block_map(int bid, int G, int T, int& g, int& rest) {
+#if STS_FLOW_MAP == 1
+    rest = bid / G; g = bid - rest * G;
+#else
+    const int c = bid & 7, s = bid >> 3;
+    const int q = s / G, i = s - q * G;
+    if (c < G) { g = c; rest = 8 * q + i; }
+    else {
+        const int m = (c - G) * G + i, sp = 8 - G;        // the period's G (8 - G) spill tiles over (8 - G) classes x G slots
+        g = m / sp; rest = 8 * q + G + (m - g * sp);
+    }
+#endif
+    return rest < T;
+}
+template <bool L0, int NT>        // L0: first layer of a coupling (x0 staging + `pre` inside the launch) -- separate kernels, separate register budgets
 __global__ __launch_bounds__(64 * FL_WAVES) __attribute__((amdgpu_waves_per_eu(2, 2))) void flow_layer_kernel(FlowLayerArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char fsm[];
-    const int Gp = (a.G + 7) & ~7;
-    const int g = (int)(blockIdx.x % (unsigned)Gp);
-    if (g >= a.G) return;
-    const int rest = (int)(blockIdx.x / (unsigned)Gp);
+    constexpr int FL_NT = NT, FL_WIN = fl_win(NT);
     const int ntile = (a.max_len + FL_NT - 1) / FL_NT;
+    int g, rest;
+    if constexpr (NT == 32) {
+        const int Gp = (a.G + 7) & ~7;
+        g = (int)(blockIdx.x % (unsigned)Gp);
+        if (g >= a.G) return;
+        rest = (int)(blockIdx.x / (unsigned)Gp);
+    } else {
+        if (!flow_block_map((int)blockIdx.x, a.G, ntile * a.B, g, rest)) return;
+    }
     const int b = rest / ntile, tile = rest - b * ntile;
     const int len = uni(seg_len(a.seg, b));
     const int n0 = tile * FL_NT;
@@ -94,7 +159,7 @@ __global__ __launch_bounds__(64 * FL_WAVES) __attribute__((amdgpu_waves_per_eu(2
     unsigned char* const R_h = fsm;                                         // h planes: NCH chunks
     unsigned char* const R_x = fsm + (size_t)NCH * 2 * PLANE;              // layer 0: x0 planes (hc / 16 chunks); later: K-split exchange
     unsigned char* const R_a = R_x + (size_t)FL_WAVES * 4096;              // gated planes: (Cg / 16) chunks x 2 planes x 32 positions x 32 B
-    const int APL = FL_NT * 32;
+    constexpr int APL = FL_COLS * 32;
     float amax = 0.f;
     constexpr int RG = 2, KS = FL_WAVES / RG;             // Cg = 32: two gate row tiles per group, four K slices (waves) per row tile
     const int rt_l = wave % RG, kq = wave / RG;
@@ -150,7 +215,7 @@ __global__ __launch_bounds__(64 * FL_WAVES) __attribute__((amdgpu_waves_per_eu(2
 #pragma unroll
             for (int q = 0; q < 4; q++) {
                 const int c = t * 32 + 8 * q + 4 * half - a.rows_res;
-                const bool okm = t < ntc && c >= 0 && c + 3 < hc && n0 + l31 < len;
+                const bool okm = t < ntc && c >= 0 && c + 3 < hc && l31 < FL_NT && n0 + l31 < len;
                 const unsigned off = okm ? (unsigned)(((base + (size_t)(n0 + l31)) * hc + c) * 4u) : kOOB;
                 mold[ti][q] = __builtin_bit_cast(f32x4u, __builtin_amdgcn_raw_buffer_load_b128(rm, (int)off, 0, 0));
             }
@@ -163,13 +228,17 @@ __global__ __launch_bounds__(64 * FL_WAVES) __attribute__((amdgpu_waves_per_eu(2
         // path to L2, so what matters is that the path never idles --, the other half + the 1x1 conv's right behind)
         gate_prefetch(I0{}, IH{});
         // h = h_in + part_0 + part_1 + ... (the previous layer's partial res sums, fixed order); units of 4 channels x 1 position.  Branch-free:
-        // every source through a buffer descriptor, positions outside the utterance (and sources past part_n) read as zero
+        // every source through a buffer descriptor, positions outside the utterance read as zero.  Only the part_n live slices are
+        // requested: the loop exists once per slice count (fl_slices).  The slices past part_n used to be read as zeros and added: x + (+0)
+        // is x except for x = -0, so ONE +0 is still added behind the live slices wherever fewer than FL_MAXG are live -- same bits
         const int qpp = H >> 2;                           // quads per position
         const int nunit = W * qpp;
         const unsigned span = (unsigned)(((size_t)a.tot * H) * 4u);
         const rsrc_t rh = make_rsrc(a.h_in, span);
+        fl_slices(a.part_n, [&](auto ns_c) {
+        constexpr int NS = decltype(ns_c)::value;
         for (int u0 = 0; u0 < nunit; u0 += 64 * FL_WAVES * FL_UR) {
-            f32x4u v[FL_UR], p[FL_UR][FL_MAXG];
+            f32x4u v[FL_UR], p[FL_UR][NS > 0 ? NS : 1];
             int pw[FL_UR], q4[FL_UR]; bool ok[FL_UR];
 #pragma unroll
             for (int r = 0; r < FL_UR; r++) {
@@ -180,8 +249,8 @@ __global__ __launch_bounds__(64 * FL_WAVES) __attribute__((amdgpu_waves_per_eu(2
                 const unsigned off = ok[r] ? (unsigned)(((base + (size_t)pos) * H + (size_t)q4[r] * 4) * 4u) : kOOB;
                 v[r] = __builtin_bit_cast(f32x4u, __builtin_amdgcn_raw_buffer_load_b128(rh, (int)off, 0, 0));
 #pragma unroll
-                for (int s = 0; s < FL_MAXG; s++) {
-                    const rsrc_t rp = make_rsrc(a.part_in + (size_t)s * a.part_stride, s < a.part_n ? span : 0u);
+                for (int s = 0; s < NS; s++) {
+                    const rsrc_t rp = make_rsrc(a.part_in + (size_t)s * a.part_stride, span);
                     p[r][s] = __builtin_bit_cast(f32x4u, __builtin_amdgcn_raw_buffer_load_b128(rp, (int)off, 0, 0));
                 }
             }
@@ -191,7 +260,8 @@ __global__ __launch_bounds__(64 * FL_WAVES) __attribute__((amdgpu_waves_per_eu(2
                 if (u >= nunit) continue;
                 f32x4u s4 = v[r];
 #pragma unroll
-                for (int s = 0; s < FL_MAXG; s++) s4 += p[r][s];
+                for (int s = 0; s < NS; s++) s4 += p[r][s];
+                if constexpr (NS < FL_MAXG) s4 += f32x4u{0.f, 0.f, 0.f, 0.f};
                 // this group's channel slice of its own columns is the materialised h of this layer (next layer's base)
                 const int ch = q4[r] * 4;
                 if (ok[r] && pw[r] >= halo && pw[r] < halo + FL_NT && ch >= g * Cg && ch < (g + 1) * Cg)
@@ -205,6 +275,7 @@ __global__ __launch_bounds__(64 * FL_WAVES) __attribute__((amdgpu_waves_per_eu(2
                 *(uint2*)(d + PLANE) = uint2{lo[0], lo[1]};
             }
         }
+        });
         TT_STAMP(1);
         gate_prefetch(IH{}, IE{});
         c_prefetch();
@@ -228,8 +299,10 @@ __global__ __launch_bounds__(64 * FL_WAVES) __attribute__((amdgpu_waves_per_eu(2
         const int qpp = hc >> 2;
         const int nunit = W * qpp;
         const unsigned pspan = (unsigned)(((size_t)a.tot * hc) * 4u);
+        fl_slices(a.pend_n, [&](auto ns_c) {          // (live slices only, as above for the partial sums)
+        constexpr int NS = decltype(ns_c)::value;
         for (int u0 = 0; u0 < nunit; u0 += 64 * FL_WAVES * FL_UR) {
-            float zv[FL_UR][4]; f32x4u p[FL_UR][FL_MAXG];
+            float zv[FL_UR][4]; f32x4u p[FL_UR][NS > 0 ? NS : 1];
             int pw[FL_UR], q4[FL_UR]; bool ok[FL_UR];
 #pragma unroll
             for (int r = 0; r < FL_UR; r++) {
@@ -242,8 +315,8 @@ __global__ __launch_bounds__(64 * FL_WAVES) __attribute__((amdgpu_waves_per_eu(2
                 for (int e = 0; e < 4; e++) zv[r][e] = ok[r] ? a.x0[zo + (size_t)e * a.x0_ld] : 0.f;
                 const unsigned off = ok[r] ? (unsigned)(((base + (size_t)pos) * hc + (size_t)q4[r] * 4) * 4u) : kOOB;
 #pragma unroll
-                for (int s = 0; s < FL_MAXG; s++) {
-                    const rsrc_t rp = make_rsrc(a.pend + (size_t)s * a.pend_stride, s < a.pend_n ? pspan : 0u);
+                for (int s = 0; s < NS; s++) {
+                    const rsrc_t rp = make_rsrc(a.pend + (size_t)s * a.pend_stride, pspan);
                     p[r][s] = __builtin_bit_cast(f32x4u, __builtin_amdgcn_raw_buffer_load_b128(rp, (int)off, 0, 0));
                 }
             }
@@ -253,7 +326,8 @@ __global__ __launch_bounds__(64 * FL_WAVES) __attribute__((amdgpu_waves_per_eu(2
                 if (u >= nunit) continue;
                 f32x4u s4 = {zv[r][0], zv[r][1], zv[r][2], zv[r][3]};
 #pragma unroll
-                for (int s = 0; s < FL_MAXG; s++) s4 += p[r][s];
+                for (int s = 0; s < NS; s++) s4 += p[r][s];
+                if constexpr (NS < FL_MAXG) s4 += f32x4u{0.f, 0.f, 0.f, 0.f};
                 const int ch = q4[r] * 4;
                 // the updated half is written out (to x0_out, NOT over x0: neighbouring workgroups still read x0's halo columns and
                 // would add the pending slices twice): this group's share of the rows, own columns only
@@ -271,32 +345,35 @@ __global__ __launch_bounds__(64 * FL_WAVES) __attribute__((amdgpu_waves_per_eu(2
                 *(uint2*)(d + PLANE) = uint2{lo[0], lo[1]};
             }
         }
+        });
         __syncthreads();
         TT_STAMP(1);
         gate_prefetch(IH{}, IE{});     // (lands under the pre conv and the park)
-        // h = pre(x0') + b on the whole window
-        if (wave < nrt) {
+        // h = pre(x0') + b on the whole window: two 32-position column tiles, or one for a 16-frame tile (W <= 32 always).  A 32-frame
+        // tile keeps two even for a 1-tap gate conv (W == 32), where the second parks zeros nobody reads: that kernel stays the code it was
+        auto pre_park = [&](auto nct_c) {
+            constexpr int NCT = decltype(nct_c)::value;
             const int rt = wave;
-            f32x16 acc[1][2];
+            f32x16 acc[1][NCT];
 #pragma unroll
-            for (int ct = 0; ct < 2; ct++)
+            for (int ct = 0; ct < NCT; ct++)
 #pragma unroll
                 for (int r = 0; r < 16; r++) acc[0][ct][r] = 0.f;
 #pragma unroll
             for (int cs = 0; cs < 8; cs++)
                 if (cs < nk) {
-                    u32x4 fb[2][2];
+                    u32x4 fb[NCT][2];
 #pragma unroll
-                    for (int ct = 0; ct < 2; ct++)
+                    for (int ct = 0; ct < NCT; ct++)
 #pragma unroll
                         for (int pl = 0; pl < 2; pl++) fb[ct][pl] = *(const u32x4*)(R_x + fl_b_off(cs, ct * 32 + l31, half, pl, PLANE));
-                    step_mfmas<1, 1, 2, 2, 2>(acc, fp[cs], fb);
+                    step_mfmas<1, 1, NCT, 2, 2>(acc, fp[cs], fb);
                 }
             // park: + bias, ZERO outside [0, len) (the gate conv's zero padding is padding of h, not of x0), split, in the k order the
             // accumulator layout gives (a lane's rows 4 h + {0..3} and 8 + 4 h + {0..3} of a 16-row block = one 16-byte unit per plane);
             // the first layer's gate weights are packed to match (perm_k)
 #pragma unroll
-            for (int ct = 0; ct < 2; ct++) {
+            for (int ct = 0; ct < NCT; ct++) {
                 const int pw_ = ct * 32 + l31;
                 const int pos = n0 - halo + pw_;
                 const bool inside = pos >= 0 && pos < len && pw_ < W;
@@ -325,6 +402,9 @@ __global__ __launch_bounds__(64 * FL_WAVES) __attribute__((amdgpu_waves_per_eu(2
                     }
                 }
             }
+        };
+        if (wave < nrt) {
+            pre_park(std::integral_constant<int, FL_NT < 32 ? 1 : 2>{});
         }
         c_prefetch();
         m_prefetch();
@@ -369,37 +449,53 @@ __global__ __launch_bounds__(64 * FL_WAVES) __attribute__((amdgpu_waves_per_eu(2
     __syncthreads();
     {
         const int rowb = (g * RG + rt_l) * 32;
-        float gv[2];
-#pragma unroll
-        for (int i = 0; i < 2; i++) {
-            const int r = 2 * kq + i;                   // pair index 0..7 (register r and r + 8)
+        auto gated = [&](int r, int src) {          // pair r (registers r and r + 8) of the accumulator lane `src` (same half as this lane)
             float t = 0.f, sg = 0.f;
             for (int q = 0; q < KS; q++) {
-                t += red[((size_t)(q * RG + rt_l) * 16 + r) * 64 + lane];
-                sg += red[((size_t)(q * RG + rt_l) * 16 + r + 8) * 64 + lane];
+                t += red[((size_t)(q * RG + rt_l) * 16 + r) * 64 + src];
+                sg += red[((size_t)(q * RG + rt_l) * 16 + r + 8) * 64 + src];
             }
             const int rowp = rowb + (r & 3) + 8 * (r >> 2) + 4 * half;
             t = t * a.s_gate + (a.b_gate ? a.b_gate[rowp] : 0.f);
             sg = sg * a.s_gate + (a.b_gate ? a.b_gate[rowp + 16] : 0.f);
             if (a.ubias) { t += a.ubias[(size_t)rowp * a.ubias_ld + b]; sg += a.ubias[(size_t)(rowp + 16) * a.ubias_ld + b]; }
-            gv[i] = tanh_ref(t) * sigmoid_ref(sg);
+            return tanh_ref(t) * sigmoid_ref(sg);
+        };
+        if constexpr (FL_NT == FL_COLS) {
+            float gv[2];
+#pragma unroll
+            for (int i = 0; i < 2; i++) gv[i] = gated(2 * kq + i, lane);       // pair index 0..7
+            // two-term split of the pair (as split8h does per dword) -> dword kq of the lane's 16-byte unit in each plane
+            const f32x2 v = {gv[0], gv[1]};
+            const f16x2 hh = __builtin_convertvector(v, f16x2);
+            const f32x2 rr = (v - __builtin_convertvector(hh, f32x2)) * 2048.f;
+            const f16x2 ll = __builtin_convertvector(rr, f16x2);
+            amax = __builtin_fmaxf(amax, __builtin_fmaxf(__builtin_fabsf(v[0]), __builtin_fabsf(v[1])));
+            unsigned char* d = R_a + (size_t)rt_l * 2 * APL + l31 * 32 + ((half ^ ((l31 >> 3) & 1)) << 4) + kq * 4;
+            *(unsigned*)d = __builtin_bit_cast(unsigned, hh);
+            *(unsigned*)(d + APL) = __builtin_bit_cast(unsigned, ll);
+        } else {
+            // 16-frame tile: the lanes of the 16 dead columns take the second pair of the live columns, so every lane finishes ONE pair
+            // (half the tanh / sigmoid instructions of the wave); the dead columns are neither counted nor parked.  Same sums, same
+            // roundings: each value's two fp16 terms are stored as the 16-bit half of the dword the pair shares
+            const int i = l31 >> 4, col = l31 & 15;
+            float v = gated(2 * kq + i, (lane & 32) | col);
+            asm("" : "+v"(v));          // the fp32 product, rounded: left to itself the compiler folds tanh * sigmoid into the two conversions
+                                        // below (v_fma_mix*: one rounding instead of two) and the 16-frame tiles lose the 32-frame tiles' bits
+            const _Float16 hh = (_Float16)v;
+            const _Float16 ll = (_Float16)((v - (float)hh) * 2048.f);
+            amax = __builtin_fmaxf(amax, __builtin_fabsf(v));
+            unsigned char* d = R_a + (size_t)rt_l * 2 * APL + col * 32 + ((half ^ ((col >> 3) & 1)) << 4) + kq * 4 + i * 2;
+            *(_Float16*)d = hh;
+            *(_Float16*)(d + APL) = ll;
         }
-        // two-term split of the pair (as split8h does per dword) -> dword kq of the lane's 16-byte unit in each plane
-        const f32x2 v = {gv[0], gv[1]};
-        const f16x2 hh = __builtin_convertvector(v, f16x2);
-        const f32x2 rr = (v - __builtin_convertvector(hh, f32x2)) * 2048.f;
-        const f16x2 ll = __builtin_convertvector(rr, f16x2);
-        amax = __builtin_fmaxf(amax, __builtin_fmaxf(__builtin_fabsf(v[0]), __builtin_fabsf(v[1])));
-        unsigned char* d = R_a + (size_t)rt_l * 2 * APL + l31 * 32 + ((half ^ ((l31 >> 3) & 1)) << 4) + kq * 4;
-        *(unsigned*)d = __builtin_bit_cast(unsigned, hh);
-        *(unsigned*)(d + APL) = __builtin_bit_cast(unsigned, ll);
     }
     __syncthreads();
     TT_STAMP(4);
 
     // ================= 1x1 conv on the gated channels: partial sums of the res rows and of the -m rows =================
     const int pos_o = n0 + l31;
-    const bool col_ok = pos_o < len;
+    const bool col_ok = l31 < FL_NT && pos_o < len;
 #pragma unroll
     for (int ti = 0; ti < 2; ti++) {
         const int t = wave + FL_WAVES * ti;
@@ -468,7 +564,8 @@ __global__ __launch_bounds__(256) void flow_finish_kernel(FlowFinishArgs a) {
 // ------------------------------------------------------------------------------------------------
 bool flow_layer_shape_ok(int H, int half, int k, int dil, int n_layers) {
     if (H < 32 || H % 32 != 0 || H > 256 || half < 16 || half % 16 != 0 || half % 4 != 0 || half > 128) return false;
-    if (!(k & 1) || k < 1 || dil != 1 || (k - 1) > FL_WIN - FL_NT || n_layers < 1) return false;
+    // (2 * halo = k - 1 <= 16: what a 16-frame tile's plane holds, fl_win; the register bound below already keeps k <= 15)
+    if (!(k & 1) || k < 1 || dil != 1 || (k - 1) > 16 || n_layers < 1) return false;
     const int Cg = 32, G = H / Cg;
     if (G > FL_MAXG) return false;
     const int RG = 2, KS = FL_WAVES / RG, NCH = H / 16;
@@ -479,22 +576,29 @@ bool flow_layer_shape_ok(int H, int half, int k, int dil, int n_layers) {
 }
 int flow_layer_groups(int H) { return H / 32; }
 
-static size_t flow_lds_bytes(int H) {
-    const size_t h = (size_t)(H / 16) * 2 * FL_WIN * 32;
-    return h + (size_t)FL_WAVES * 4096 + (size_t)4 * 2 * FL_NT * 32 + 256;      // + x0 planes / K-split exchange (32 KB) + gated planes
+static size_t flow_lds_bytes(int H, int nt) {
+    const size_t h = (size_t)(H / 16) * 2 * fl_win(nt) * 32;
+    return h + (size_t)FL_WAVES * 4096 + (size_t)4 * 2 * FL_COLS * 32 + 256;      // + x0 planes / K-split exchange (32 KB) + gated planes
 }
 
-void flow_layer(const FlowLayerArgs& a, hipStream_t st) {
+template <bool L0, int NT>
+static void flow_layer_launch(const FlowLayerArgs& a, unsigned grid, hipStream_t st) {
+    const size_t lds = flow_lds_bytes(a.H, NT);
+    (void)hipFuncSetAttribute((const void*)flow_layer_kernel<L0, NT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);     // (per device; > 64 KB of dynamic LDS)
+    hipLaunchKernelGGL((flow_layer_kernel<L0, NT>), dim3(grid), dim3(64 * FL_WAVES), lds, st, a);
+}
+
+void flow_layer(const FlowLayerArgs& a, hipStream_t st, int nt) {
     if (a.max_len <= 0 || a.B <= 0) return;
-    const int Gp = (a.G + 7) & ~7;
-    const int ntile = (a.max_len + FL_NT - 1) / FL_NT;
-    const size_t lds = flow_lds_bytes(a.H);
-    if (a.layer == 0) {
-        (void)hipFuncSetAttribute((const void*)flow_layer_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);     // (per device; > 64 KB of dynamic LDS)
-        hipLaunchKernelGGL(flow_layer_kernel<true>, dim3((unsigned)((size_t)ntile * a.B * Gp)), dim3(64 * FL_WAVES), lds, st, a);
+    if (nt == 16) {
+        const unsigned grid = (unsigned)flow_grid16(a.G, (a.max_len + 15) / 16 * a.B);
+        if (a.layer == 0) flow_layer_launch<true, 16>(a, grid, st);
+        else flow_layer_launch<false, 16>(a, grid, st);
     } else {
-        (void)hipFuncSetAttribute((const void*)flow_layer_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        hipLaunchKernelGGL(flow_layer_kernel<false>, dim3((unsigned)((size_t)ntile * a.B * Gp)), dim3(64 * FL_WAVES), lds, st, a);
+        const int Gp = (a.G + 7) & ~7;
+        const unsigned grid = (unsigned)((size_t)((a.max_len + 31) / 32) * a.B * Gp);
+        if (a.layer == 0) flow_layer_launch<true, 32>(a, grid, st);
+        else flow_layer_launch<false, 32>(a, grid, st);
     }
 }
 
