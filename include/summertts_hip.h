@@ -97,6 +97,50 @@ int sts_infer_ids_batch_stream(sts_engine* e, int32_t B, const int32_t* const* i
                                const float* length_scale, int32_t chunk_frames, sts_batch_chunk_cb cb, void* user,
                                int32_t* n_total);
 
+/* Open streams: a batched stream that admits new utterances between its steps.  One per engine; nothing here is on by default.
+ *   sts_stream_open fixes the chunk size C = chunk_frames, the output rate, the limiter setting, the conv mode and the conv math, and
+ *   allocates a latent pool of capacity_frames frames for at most max_live utterances at a time (1 <= max_live <= 1024;
+ *   capacity_frames * inter_channels and capacity_frames * samples_per_frame at most 2 10^9).  STS_EINVAL while EQ bands are set, the
+ *   loudness mode is not 0, record taps are on, or a duration plan, speaker mix, gain plan or forced durations are pending (those forms
+ *   carry per-call tables or per-utterance filter state: opening them to admission is later work); STS_ESTATE when a stream is open.
+ *   sts_stream_admit runs text encoder, duration predictor and flow of B newcomers as the packed batch a sts_infer_ids_batch_stream call
+ *   of those B would, and moves their latents into the pool.  All or nothing: *admitted = B, or 0 when slots or frames do not suffice now
+ *   (nothing has changed; retry after a retirement).  slot_out[b] = the slot of utterance b, the `utt` its chunks arrive with (-1: it has
+ *   no frames and receives nothing); n_samples_out[b] = its total output samples at the current rate, so that the caller can tell a slot's
+ *   last chunk.  Both may be NULL; sid and length_scale may be NULL (0 and 1.0).  noise: NULL = the engine's setting with seed + b for
+ *   utterance b of the admission, as utterance b of a batch call; otherwise [B] settings used as given.  B > max_live: STS_EINVAL.
+ *   sts_stream_step is ONE step: every live slot, in ascending slot order, decodes its next chunk -- frames [f_s, min(f_s + C, F_s)) of
+ *   slot s from its own position f_s -- all windows in one decode pass, and the chunks reach `cb` (utt = slot) before the call returns.  A
+ *   slot retires, and its index and its frames become free, behind its last chunk or when its callback returns non-zero.  *live_after (may
+ *   be NULL) = slots still live.  With no live slot it does nothing.
+ *   sts_stream_info: any output may be NULL; *steps = sts_stream_step calls since open that decoded.  sts_stream_close drops the live
+ *   slots without delivering and frees the pool; sts_destroy closes an open stream.  No entry of an open stream may be called from a
+ *   chunk callback.
+ *   While a stream is open every other run entry of the engine and every setter of what open fixed (output rate, limiter, EQ, loudness,
+ *   conv mode, conv math, plans, mixes, forced durations, record taps, the debug switches other than STS_DBG_STREAM_RETRY_STEP and
+ *   STS_DBG_POISON) returns STS_ESTATE; sts_set_noise stays allowed.
+ *   Equality: whatever the admission schedule, the list of chunks of every utterance and their sample offsets equal its
+ *   sts_infer_ids_stream chunks with the same chunk_frames bit for bit when the kernel variant is pinned (sts_set_conv_mode), and its PCM
+ *   is within 1 LSB of that under the automatic choice.
+ *   conv math 3: an activation beyond fp16's range during an admission repeats that admission alone in form 0 (nothing of it has been
+ *   delivered); raised in a step, that step is decoded again in form 0 and the stream stays in form 0 until it is closed.  No chunk is
+ *   delivered twice; sts_profile.conv_math_fallbacks counts the steps of one open stream once.  STS_DBG_STREAM_RETRY_STEP = k applies to
+ *   the k-th sts_stream_step since open. */
+typedef struct sts_stream_noise { float noise_scale, noise_scale_w; uint64_t seed; } sts_stream_noise;
+int sts_stream_open(sts_engine* e, int32_t chunk_frames, int32_t max_live, int64_t capacity_frames);
+int sts_stream_admit(sts_engine* e, int32_t B, const int32_t* const* ids, const int32_t* n, const int32_t* sid,
+                     const float* length_scale, const sts_stream_noise* noise, int32_t* slot_out, int32_t* n_samples_out,
+                     int32_t* admitted);
+int sts_stream_step(sts_engine* e, sts_batch_chunk_cb cb, void* user, int32_t* live_after);
+int sts_stream_info(const sts_engine* e, int32_t* open, int32_t* live, int32_t* free_slots, int64_t* free_frames, int64_t* steps);
+int sts_stream_close(sts_engine* e);
+/* The kernel that moves an admission's latents into the pool, on caller data (host pointers in and out): B column segments of the
+ * channel-major src [C][ld_src] into dst [C][ld_dst]; segment b is len[b] columns from src_off[b] to dst_off[b].  dst comes back with
+ * every element outside the destination ranges unchanged.  Ranges outside either matrix, overlapping destination ranges, B outside
+ * [1, 65535] or C < 1: STS_EINVAL. */
+int sts_debug_adopt_z(int device, const float* src, int32_t C, int64_t ld_src, float* dst, int64_t ld_dst, const int64_t* src_off,
+                      const int64_t* dst_off, const int32_t* len, int32_t B);
+
 /* Batched form (new capability; the reference processes exactly one utterance per call).  The B
  * utterances are packed along time on the device and run through every kernel together.
  * pcm_out[b] is malloc()'d per utterance. */
@@ -795,6 +839,18 @@ int sts_pool_set_limiter(sts_pool* p, int mode, float gain_db, float ceiling_dbf
 int sts_pool_set_eq(sts_pool* p, int32_t n_bands, const sts_eq_band* bands);
 /*   sts_pool_set_eq_streaming: sts_set_eq_streaming on every engine of the pool.  STS_ESTATE while any request is outstanding. */
 int sts_pool_set_eq_streaming(sts_pool* p, int enable);
+/*   sts_pool_set_stream_admission (default off): on, a worker runs a group of streaming requests as an OPEN stream (sts_stream_open: the
+ *   group's chunk size, max_live = max_batch, capacity = max_batch * 1024 frames) and looks at the FIFO between steps: while its head is a
+ *   streaming request of the same chunk size and slots are free, it takes up to the free count and admits them into the running stream, so
+ *   a client that arrives late hears its first chunk after one admission and one step, not after the group has drained.  A head of any
+ *   other kind is left for another worker or for after the drain; FIFO order is kept.  An admission that fails with more than one request
+ *   is retried one by one (a bad request fails alone); one that finds no room goes back to the head of the FIFO.  Tickets complete as
+ *   without it.  With the pool's EQ or loudness set, and for a group that does not fit the empty pool, streamed groups run the closed way.
+ *   STS_ESTATE while any request is outstanding.  sts_pool_stream_stats: groups = streamed groups run as open streams, admitted_midstream =
+ *   requests admitted into a running one (either may be NULL). */
+int sts_pool_set_stream_admission(sts_pool* p, int enable);
+int sts_pool_get_stream_admission(const sts_pool* p);
+int sts_pool_stream_stats(sts_pool* p, int64_t* groups, int64_t* admitted_midstream);
 /*   sts_pool_submit_plan (ABI 14): sts_pool_submit_ex with this request's own duration plan (sts_set_duration_plan: rate and fixed hold n
  *   entries each or are NULL, target_frames 0 = none; an invalid plan answers STS_EINVAL).  Whole-utterance requests only.  Requests with and
  *   without a plan share one packed batch: the plan is per utterance. */

@@ -5,6 +5,7 @@
 #include <algorithm>
 #include <new>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "engine.hpp"
@@ -18,6 +19,9 @@ struct sts_engine { Engine eng; };
 
 static thread_local std::string g_err;
 static int set_err(int code, const std::string& s) { g_err = s; return code; }
+// the setters that write an engine member themselves: what an open stream fixed stays fixed until sts_stream_close (engine.hpp stream_open)
+#define STS_CAPI_NOT_WHILE_OPEN(e) \
+    do { if ((e)->eng.stream_is_open()) return set_err(STS_ESTATE, "a stream is open on this engine (sts_stream_close first)"); } while (0)
 
 extern "C" {
 
@@ -149,6 +153,39 @@ int sts_infer_ids_batch_stream(sts_engine* e, int32_t B, const int32_t* const* i
     return STS_OK;
 }
 
+int sts_stream_open(sts_engine* e, int32_t chunk_frames, int32_t max_live, int64_t capacity_frames) {
+    if (!e) return set_err(STS_EINVAL, "null engine");
+    const int rc = e->eng.stream_open(chunk_frames, max_live, capacity_frames);
+    return rc == STS_OK ? STS_OK : set_err(rc, e->eng.error());
+}
+int sts_stream_admit(sts_engine* e, int32_t B, const int32_t* const* ids, const int32_t* n, const int32_t* sid,
+                     const float* length_scale, const sts_stream_noise* noise, int32_t* slot_out, int32_t* n_samples_out,
+                     int32_t* admitted) {
+    if (!e) return set_err(STS_EINVAL, "null engine");
+    const int rc = e->eng.stream_admit(B, ids, n, sid, length_scale, noise, slot_out, n_samples_out, admitted);
+    return rc == STS_OK ? STS_OK : set_err(rc, e->eng.error());
+}
+int sts_stream_step(sts_engine* e, sts_batch_chunk_cb cb, void* user, int32_t* live_after) {
+    if (!e) return set_err(STS_EINVAL, "null engine");
+    const int rc = e->eng.stream_step(cb, user, live_after);
+    return rc == STS_OK ? STS_OK : set_err(rc, e->eng.error());
+}
+int sts_stream_info(const sts_engine* e, int32_t* open, int32_t* live, int32_t* free_slots, int64_t* free_frames, int64_t* steps) {
+    if (!e) return set_err(STS_EINVAL, "null engine");
+    const LiveStream* L = e->eng.live_;
+    if (open) *open = L ? 1 : 0;
+    if (live) *live = L ? L->live_count() : 0;
+    if (free_slots) *free_slots = L ? L->free_slots() : 0;
+    if (free_frames) *free_frames = L ? L->free_frames() : 0;
+    if (steps) *steps = L ? L->steps : 0;
+    return STS_OK;
+}
+int sts_stream_close(sts_engine* e) {
+    if (!e) return set_err(STS_EINVAL, "null engine");
+    const int rc = e->eng.stream_close();
+    return rc == STS_OK ? STS_OK : set_err(rc, e->eng.error());
+}
+
 int sts_stream_halo_frames(const sts_engine* e) {
     if (!e) return set_err(STS_EINVAL, "null engine");
     return e->eng.stream_halo();
@@ -156,6 +193,7 @@ int sts_stream_halo_frames(const sts_engine* e) {
 
 int sts_set_forced_durations(sts_engine* e, const int32_t* dur, int64_t count) {
     if (!e) return set_err(STS_EINVAL, "null engine");
+    STS_CAPI_NOT_WHILE_OPEN(e);
     if (!dur || count <= 0) { e->eng.have_forced = false; return STS_OK; }
     e->eng.forced_dur.assign(dur, dur + count);
     e->eng.have_forced = true;
@@ -664,6 +702,36 @@ int sts_debug_layer_norm(int device, const float* a, const float* b, int32_t nb,
     return d.ok ? STS_OK : set_err(STS_EDEVICE, "the LayerNorm launch failed on the device");
 }
 
+int sts_debug_adopt_z(int device, const float* src, int32_t C, int64_t ld_src, float* dst, int64_t ld_dst, const int64_t* src_off,
+                      const int64_t* dst_off, const int32_t* len, int32_t B) {
+    if (!src || !dst || !src_off || !dst_off || !len || B < 1 || B > 65535 || C < 1 || ld_src < 1 || ld_dst < 1 ||
+        (double)C * (double)ld_src > (double)(1 << 28) || (double)C * (double)ld_dst > (double)(1 << 28))
+        return set_err(STS_EINVAL, "src [C][ld_src], dst [C][ld_dst] (at most 2^28 floats each), the three tables and 1 <= B <= 65535 are required");
+    std::vector<std::pair<int64_t, int64_t>> ranges;
+    int max_len = 0;
+    for (int b = 0; b < B; b++) {
+        if (len[b] < 0 || src_off[b] < 0 || dst_off[b] < 0 || src_off[b] + len[b] > ld_src || dst_off[b] + len[b] > ld_dst)
+            return set_err(STS_EINVAL, "a segment leaves its matrix");
+        if (len[b] > 0) ranges.emplace_back(dst_off[b], dst_off[b] + len[b]);
+        max_len = std::max(max_len, (int)len[b]);
+    }
+    std::sort(ranges.begin(), ranges.end());
+    for (size_t i = 1; i < ranges.size(); i++) if (ranges[i].first < ranges[i - 1].second) return set_err(STS_EINVAL, "destination ranges overlap");
+    if (hipSetDevice(device) != hipSuccess) return set_err(STS_EDEVICE, "no such device");
+    std::vector<long long> tab(((size_t)B * 20 + 7) / 8);       // long long src_off[B] | long long dst_off[B] | int len[B] (kernels.hpp adopt_z)
+    for (int b = 0; b < B; b++) { tab[(size_t)b] = src_off[b]; tab[(size_t)B + b] = dst_off[b]; ((int*)(tab.data() + 2 * (size_t)B))[b] = len[b]; }
+    DebugBufs d;
+    const float* ds = d.up(src, (size_t)C * ld_src);
+    float* dd = (float*)d.up4(dst, (size_t)C * ld_dst);
+    const long long* dt = (const long long*)d.up4(tab.data(), tab.size() * 2);
+    if (d.ok) {
+        adopt_z(ds, ld_src, dd, ld_dst, C, dt, B, max_len, d.st);
+        d.ok = hipGetLastError() == hipSuccess && hipMemcpyAsync(dst, dd, (size_t)C * ld_dst * 4, hipMemcpyDeviceToHost, d.st) == hipSuccess &&
+               hipStreamSynchronize(d.st) == hipSuccess;
+    }
+    return d.ok ? STS_OK : set_err(STS_EDEVICE, "the adoption launch failed on the device");
+}
+
 int sts_set_noise(sts_engine* e, float noise_scale, float noise_scale_w, uint64_t seed) {
     if (!e) return set_err(STS_EINVAL, "null engine");
     if (!noise_scale_valid(noise_scale) || !noise_scale_valid(noise_scale_w)) return set_err(STS_EINVAL, "noise scales must be finite and >= 0");
@@ -677,17 +745,19 @@ int sts_get_noise(const sts_engine* e, float* noise_scale, float* noise_scale_w,
     if (seed) *seed = e->eng.noise.seed;
     return STS_OK;
 }
-int sts_set_record_taps(sts_engine* e, int enable) { if (!e) return set_err(STS_EINVAL, "null engine"); e->eng.record_taps = enable != 0; return STS_OK; }
+int sts_set_record_taps(sts_engine* e, int enable) { if (!e) return set_err(STS_EINVAL, "null engine"); STS_CAPI_NOT_WHILE_OPEN(e); e->eng.record_taps = enable != 0; return STS_OK; }
 int sts_set_conv_math(sts_engine* e, int mode) {
     if (!e) return set_err(STS_EINVAL, "null engine");
     if (mode < 0 || mode > 3) return set_err(STS_EINVAL, "conv math: 0 = split-bf16 (default), 1 = exact fp32, 2 = split-bf16 wherever eligible, 3 = two-term fp16");
+    STS_CAPI_NOT_WHILE_OPEN(e);
     e->eng.conv_math = mode;
     e->eng.h2_consecutive = 0; e->eng.h2_disabled = false;
     return STS_OK;
 }
-int sts_set_conv_mode(sts_engine* e, int mode) { if (!e) return set_err(STS_EINVAL, "null engine"); e->eng.conv_mode = mode; return STS_OK; }
+int sts_set_conv_mode(sts_engine* e, int mode) { if (!e) return set_err(STS_EINVAL, "null engine"); STS_CAPI_NOT_WHILE_OPEN(e); e->eng.conv_mode = mode; return STS_OK; }
 int sts_debug_set(sts_engine* e, int key, int value) {
     if (!e) return set_err(STS_EINVAL, "null engine");
+    if (key != STS_DBG_STREAM_RETRY_STEP && key != STS_DBG_POISON) STS_CAPI_NOT_WHILE_OPEN(e);     // (the two test hooks of a step stay settable)
     switch (key) {
         case STS_DBG_ATTN_BLOCK_MIN_WGS: if (value < 1) return set_err(STS_EINVAL, "threshold must be >= 1"); e->eng.attn_block_min_wgs = value; return STS_OK;
         case STS_DBG_FLOW_FUSED: e->eng.flow_fused = value == 2 || value == 3 ? value : value != 0; return STS_OK;
@@ -794,6 +864,7 @@ int sts_loudness_measure(int device, const float* x, const int64_t* lengths, int
 }
 int sts_set_loudness_streaming(sts_engine* e, int enable) {
     if (!e) return set_err(STS_EINVAL, "null engine");
+    STS_CAPI_NOT_WHILE_OPEN(e);
     e->eng.loud_streaming = enable != 0;
     return STS_OK;
 }
@@ -973,6 +1044,7 @@ int sts_get_eq(const sts_engine* e, int32_t* n_bands, sts_eq_band* bands, int32_
 }
 int sts_set_eq_streaming(sts_engine* e, int enable) {
     if (!e) return set_err(STS_EINVAL, "null engine");
+    STS_CAPI_NOT_WHILE_OPEN(e);
     e->eng.eq_streaming = enable != 0;
     return STS_OK;
 }

@@ -12,13 +12,19 @@
 #include <algorithm>
 #include <chrono>
 #include <math.h>
+#include <new>
 #include <stdlib.h>
 #include <string.h>
 #include <thread>
 
 namespace sts {
 
+// what an open stream fixed stays fixed, and the engine runs nothing else, until sts_stream_close (engine.hpp stream_open)
+#define STS_NOT_WHILE_OPEN(what) \
+    do { if (live_) return fail(STS_ESTATE, "a stream is open on this engine (sts_stream_close first): it refuses " what); } while (0)
+
 Engine::~Engine() {
+    if (live_) (void)stream_close();
     if (stream) (void)hipStreamSynchronize(stream);
     free_model(model);
     if (arenaT_.base) (void)hipFree(arenaT_.base);
@@ -343,6 +349,7 @@ void Engine::tap(const char* name, const float* d, int channels, long ld, long l
 
 // sts_set_output_rate: the filter's table is built on the host and uploaded once here, not per call.  An invalid rate changes nothing.
 int Engine::set_output_rate(int rate) {
+    STS_NOT_WHILE_OPEN("the output rate");
     if (rate == 0) rate = kNativeRate;
     ResampleDesign d;
     if (rate != kNativeRate && !resample_design(kNativeRate, rate, &d)) return fail(STS_EINVAL, "output rate must be 0 or an integer in [8000, 48000] with P = rate / gcd(16000, rate) <= 1024");
@@ -361,6 +368,7 @@ int Engine::set_output_rate(int rate) {
 }
 // sts_set_loudness: persists; an invalid argument changes nothing
 int Engine::set_loudness(int mode, float target, float peak) {
+    STS_NOT_WHILE_OPEN("the loudness setting");
     if (!loudness_args_valid(mode, target, peak))
         return fail(STS_EINVAL, "loudness: mode 0 (off), 1 (measure) or 2 (normalize), target in [-70, 0] LUFS, ceiling in [-30, 0] dBFS");
     loud_mode = mode; loud_target = target; loud_peak = peak;
@@ -368,6 +376,7 @@ int Engine::set_loudness(int mode, float target, float peak) {
 }
 // sts_set_limiter: persists; an invalid argument changes nothing
 int Engine::set_limiter(int mode, float gain_db, float ceiling_dbfs, float lookahead_ms) {
+    STS_NOT_WHILE_OPEN("the limiter setting");
     if (!limiter_args_valid(mode, gain_db, ceiling_dbfs, lookahead_ms))
         return fail(STS_EINVAL, "limiter: mode 0 (off) or 1 (on), gain in [-40, 40] dB, ceiling in [-30, 0] dBFS, look-ahead in [0.25, 10] ms");
     lim_mode = mode; lim_gain_db = gain_db; lim_ceiling = ceiling_dbfs; lim_ms = lookahead_ms;
@@ -375,6 +384,7 @@ int Engine::set_limiter(int mode, float gain_db, float ceiling_dbfs, float looka
 }
 // sts_set_eq: persists; checked against the current output rate; an invalid argument changes nothing
 int Engine::set_eq(int n_bands, const sts_eq_band* bands) {
+    STS_NOT_WHILE_OPEN("the equaliser");
     const char* why = nullptr;
     if (!eq_valid(out_rate, n_bands, bands, &why)) return fail(STS_EINVAL, why);
     eq_n = n_bands;
@@ -399,6 +409,7 @@ int Engine::eq_prepare() {
 }
 // sts_set_duration_plan: copied and validated here; an invalid plan changes nothing.  B == 0 or plans == null drops a pending plan.
 int Engine::set_duration_plan(int B, const int32_t* n, const sts_dur_plan* plans) {
+    STS_NOT_WHILE_OPEN("a duration plan");
     if (B == 0 || !plans) { have_plan = false; return STS_OK; }
     if (B < 0 || !n) return fail(STS_EINVAL, "duration plan: B >= 0 and n are required");
     long total = 0;
@@ -422,6 +433,7 @@ int Engine::set_duration_plan(int B, const int32_t* n, const sts_dur_plan* plans
 }
 // sts_set_speaker_mix: validated and flattened here; an invalid mix changes nothing.  B == 0 or mixes == null drops a pending mix.
 int Engine::set_speaker_mix(int B, const sts_speaker_mix* mixes) {
+    STS_NOT_WHILE_OPEN("a speaker mix");
     if (B == 0 || !mixes) { have_mix = false; return STS_OK; }
     if (B < 0 || B > (1 << 20)) return fail(STS_EINVAL, "speaker mix: B >= 0 is required");
     for (int b = 0; b < B; b++) {
@@ -436,6 +448,7 @@ int Engine::set_speaker_mix(int B, const sts_speaker_mix* mixes) {
 // sts_set_gain_plan: validated and designed here (q per phoneme, h per utterance); an invalid plan changes nothing.  B == 0 or plans == null
 // drops a pending plan.
 int Engine::set_gain_plan(int B, const int32_t* n, const sts_gain_plan* plans) {
+    STS_NOT_WHILE_OPEN("a gain plan");
     if (B == 0 || !plans) { have_gain = false; return STS_OK; }
     if (B < 0 || !n) return fail(STS_EINVAL, "gain plan: B >= 0 and n are required");
     long total = 0;
@@ -490,6 +503,7 @@ int Engine::join_offsets(int64_t* start, int64_t capacity) {
 // nothing.  The run itself is run()'s, with join_on set: run_setup uploads the table, decode_end launches the join kernel (a stream:
 // run_stream_steps launches the windowed one per step)
 int Engine::run_joined(int B, const int32_t* const* ids, const int32_t* n, const int32_t* sid, const float* ls, const sts_join* join, const StreamSpec* ss) {
+    STS_NOT_WHILE_OPEN("a joined run");
     const char* why = nullptr;
     if (!join_valid(B, join, &why)) return fail(STS_EINVAL, why);
     if (!ids || !n) return fail(STS_EINVAL, "empty batch");
@@ -1304,11 +1318,24 @@ static constexpr int kRetrySplitBf16 = 1;     // run_once: nothing was handed ou
 // An engine that had to repeat two calls in a row stays in the split-bf16 form (a model whose activations do not fit fp16 would
 // otherwise pay for both forms on every call) until sts_set_conv_math is called again.
 int Engine::run(int B, const int32_t* const* ids, const int32_t* n, const int32_t* sid, const float* ls, const StreamSpec* ss) {
+    STS_NOT_WHILE_OPEN("a run");
     const int rc = run_any_math(B, ids, n, sid, ls, ss);
     have_plan = false;          // a duration plan is for one call, whatever its outcome; the repeat inside the call above applied it again
     have_mix = false;           // and so is a speaker mix
     have_gain = false;          // and a gain plan
     return rc;
+}
+// the overflow word of conv math 3 (host-mapped) and its device address, allocated by the first call that needs it
+int Engine::ensure_overflow_word() {
+    HIPCK(hipSetDevice(device));
+    if (!ovf_host_) {
+        if (hipHostMalloc((void**)&ovf_host_, 64, hipHostMallocMapped) != hipSuccess || hipHostGetDevicePointer((void**)&ovf_, ovf_host_, 0) != hipSuccess) {
+            if (ovf_host_) (void)hipHostFree(ovf_host_);
+            ovf_host_ = nullptr; ovf_ = nullptr;
+            return fail(STS_EDEVICE, "host-mapped allocation failed");
+        }
+    }
+    return STS_OK;
 }
 int Engine::run_any_math(int B, const int32_t* const* ids, const int32_t* n, const int32_t* sid, const float* ls, const StreamSpec* ss) {
     poison_bytes_ = 0;         // (a split-bf16 repeat lays the arenas out again and fills them again: both fills count)
@@ -1319,14 +1346,7 @@ int Engine::run_any_math(int B, const int32_t* const* ids, const int32_t* n, con
         conv_math = 3;
         return rc0;
     }
-    HIPCK(hipSetDevice(device));
-    if (!ovf_host_) {
-        if (hipHostMalloc((void**)&ovf_host_, 64, hipHostMallocMapped) != hipSuccess || hipHostGetDevicePointer((void**)&ovf_, ovf_host_, 0) != hipSuccess) {
-            if (ovf_host_) (void)hipHostFree(ovf_host_);
-            ovf_host_ = nullptr; ovf_ = nullptr;
-            return fail(STS_EDEVICE, "host-mapped allocation failed");
-        }
-    }
+    { const int rco = ensure_overflow_word(); if (rco != STS_OK) return rco; }
     *(volatile unsigned*)ovf_host_ = 0u;
     const bool forced = have_forced;          // (a run consumes the forced durations: the repeat needs them again)
     const long before = h2_fallbacks;
@@ -1509,8 +1529,13 @@ int Engine::run_output(RunCtx& c) {
 int Engine::run_stream_steps(RunCtx& c) {
     RUN_ALIASES(c)
     const long Cf = ss->chunk_frames;
+    // one step of an open stream (stream_step): utterance b is the live slot c.live_slots[b] -- its z at its offset in the pool, its chunk
+    // at its own next frame -- and the loop below runs once.  Everything else of a step is the closed call's
+    LiveStream* const open = c.live;
     // (ensure_pinned below may move the pinned block the geometry tables live in)
-    const std::vector<int> offF(p_offF, p_offF + B), lenF(p_lenF, p_lenF + B), sidv(c.p_sid, c.p_sid + B);
+    std::vector<int> offF, lenF, sidv;
+    if (open) for (const int s : c.live_slots) { const LiveSlot& sl = open->slots[(size_t)s]; offF.push_back((int)sl.off); lenF.push_back((int)sl.F); sidv.push_back(sl.sid); }
+    else { offF.assign(p_offF, p_offF + B); lenF.assign(p_lenF, p_lenF + B); sidv.assign(c.p_sid, c.p_sid + B); }
     const size_t hp_off = (up_bytes + ((size_t)Ttot + B) * 4 + 255) & ~(size_t)255;
     const bool joined = c.join;       // a joined stream: the steps walk J, one chunk of the ONE signal per step (join_stream.hpp)
     const bool seq = c.oc.eqst;      // the EQ runs on every step's windows from its carried state (eq_stream.hpp)
@@ -1585,15 +1610,8 @@ int Engine::run_stream_steps(RunCtx& c) {
     // The window of chunk frames [f0, f1) of an utterance of F frames: frames [w0, w1).  Its native samples [f0 hop, f1 hop) are, at the output
     // rate, the outputs j with ceil(f0 hop P / Q) <= j < ceil(f1 hop P / Q) = [j0, j1) of Nout (the halo covers the filter's K samples beyond the
     // chunk's edges too: stream_halo).  The limiter produces them from the float signal over [jl0, jl1) = [j0 - 2H, j1 + 2H) clipped to the
-    // utterance (stream_halo covers that as well); without it [jl0, jl1) = [j0, j1).
-    struct Win { long w0, w1; long long j0, j1, jl0, jl1, Nout; };
-    auto window = [&](long F, long f0) {
-        const long f1 = std::min<long>(F, f0 + Cf);
-        Win w{std::max<long>(0, f0 - halo), std::min<long>(F, f1 + halo), out_count((long long)f0 * hop), out_count((long long)f1 * hop), 0, 0,
-              out_count((long long)F * hop)};
-        w.jl0 = slim ? std::max<long long>(0, w.j0 - 2 * ld.H) : w.j0; w.jl1 = slim ? std::min<long long>(w.Nout, w.j1 + 2 * ld.H) : w.j1;
-        return w;
-    };
+    // utterance (stream_halo covers that as well); without it [jl0, jl1) = [j0, j1).  (live_stream.hpp stream_window: the one definition)
+    auto window = [&](long F, long f0) { return stream_window(F, f0, Cf, halo, hop, srs ? rs.P : 1, srs ? rs.Q : 1, slim ? ld.H : 0); };
     // a joined stream's step: the tables of its decode windows (the layout every stream uses: run_decode and the gain kernel read them), the
     // one window of J for the resampler and the limiter, the join's rows; one upload, one decode over the windows (none: no decoder kernel),
     // the windowed join, then resampler and limiter on the one utterance J.  Everything around it -- download, synchronisation, the
@@ -1676,10 +1694,10 @@ int Engine::run_stream_steps(RunCtx& c) {
     };
     const long jsteps = joined ? (long)c.js.steps() : 0;
     for (long k = 0;; k++) {
-        const long f0 = k * Cf;
         wb.clear();
         if (joined) { if (k < jsteps && live[0]) wb.push_back(0); }
-        else for (int b = 0; b < B; b++) if (live[b] && f0 < lenF[b]) wb.push_back(b);
+        else if (open) { if (k == 0) for (int b = 0; b < B; b++) wb.push_back(b); }      // (the one step: every live slot)
+        else for (int b = 0; b < B; b++) if (live[b] && k * Cf < lenF[b]) wb.push_back(b);
         const int nw = (int)wb.size();
         if (nw == 0) break;
         long long dsum = 0;                                 // samples of the step's chunks, packed
@@ -1697,7 +1715,8 @@ int Engine::run_stream_steps(RunCtx& c) {
             for (int i = 0; i < nw; i++) {
                 const int b = wb[i];
                 const long F = lenF[b];
-                const Win w = window(F, f0);
+                const long f0 = open ? open->slots[(size_t)c.live_slots[b]].f : k * Cf;      // (an open stream: the slot's own next frame)
+                const StreamWin w = window(F, f0);
                 const long wlen = w.w1 - w.w0;
                 const long long nrs = w.jl1 - w.jl0, nout = w.j1 - w.j0;
                 ti[i] = offF[b] + (int)w.w0; ti[nw + i] = (int)Wtot; ti[2 * nw + i] = (int)wlen; ti[3 * nw + i] = c.mix ? b : sidv[b];      // (a mixed run: the window's utterance, a column of bt.g)
@@ -1730,7 +1749,8 @@ int Engine::run_stream_steps(RunCtx& c) {
             if (c.gain) { int* tu = (int*)(ht + stream_tab_utt_off(nw)); for (int i = 0; i < nw; i++) tu[i] = wb[i]; }     // (the gain kernel: each window's utterance)
             HIPCK(hipMemcpyAsync(c.d_win, ht, stream_tab_bytes(nw, c.gain, seq, sld), hipMemcpyHostToDevice, stream));
             // one utterance: its window by value (no table load in the decoder's kernels); several: the tables, also while one window is live
-            int rc = B == 1 ? run_decode(c, 1, Wtot, maxW, ti[0], ti[2]) : run_decode(c, nw, Wtot, maxW, 0, -1);
+            // (an open stream reads the tables also while one slot is live: one form whatever the live count)
+            int rc = B == 1 && !open ? run_decode(c, 1, Wtot, maxW, ti[0], ti[2]) : run_decode(c, nw, Wtot, maxW, 0, -1);
             if (rc != STS_OK) return rc;
             // (run_decode ran the chain up to the gain plan on the windows at their absolute positions)
             if (srs) {
@@ -1758,8 +1778,11 @@ int Engine::run_stream_steps(RunCtx& c) {
         }
         if (!stream_direct) HIPCK(hipMemcpyAsync(hp, src, (size_t)dsum * 2, hipMemcpyDeviceToHost, stream));
         HIPCK(hipStreamSynchronize(stream));
-        if (conv_math == 3 && ((ovf_host_ && *(volatile unsigned*)ovf_host_ != 0u) || (stream_retry_step >= 0 && k == stream_retry_step))) {
-            if (k == 0) return kRetrySplitBf16;           // nothing has left yet (run() repeats the call)
+        // (an open stream: the hook counts its steps since open; an overflow repeats this step alone -- the earlier steps' chunks have left,
+        // the stream stays in form 0 until it is closed, and stream_step restores the setting)
+        if (conv_math == 3 && ((ovf_host_ && *(volatile unsigned*)ovf_host_ != 0u) || (stream_retry_step >= 0 && (open ? open->steps : (long long)k) == stream_retry_step))) {
+            if (k == 0 && !open) return kRetrySplitBf16;  // nothing has left yet (run() repeats the call)
+            if (open) open->form0 = true;
             h2_fallbacks++;
             conv_math = 0;                                 // (run() restores the setting)
             k--;                                           // this step again, every window of it
@@ -1773,7 +1796,10 @@ int Engine::run_stream_steps(RunCtx& c) {
             const int b = wb[i];
             total_samples += wn[i];
             if (ss->delivered) ss->delivered[b] += (int32_t)wn[i];
-            if (ss->cb(ss->user, b, hp + wdst[i], (int32_t)wn[i], (int32_t)wj0[i]) != 0) live[b] = 0;
+            if (open) {       // (utt = the slot; it moves on by a chunk, and retires behind its last one or at its stop)
+                const int s = c.live_slots[b];
+                open->delivered(s, ss->cb(ss->user, s, hp + wdst[i], (int32_t)wn[i], (int32_t)wj0[i]) != 0);
+            } else if (ss->cb(ss->user, b, hp + wdst[i], (int32_t)wn[i], (int32_t)wj0[i]) != 0) live[b] = 0;
         }
     }
     if (sld) {
@@ -1809,6 +1835,174 @@ int Engine::run_joined_stream(int B, const int32_t* const* ids, const int32_t* n
     StreamSpec ss{chunk_frames, cb, user, &got};
     const int rc = run_joined(B, ids, n, sid, ls, join, &ss);
     if (rc == STS_OK && n_total) *n_total = got;
+    return rc;
+}
+
+// ---- open streams (engine.hpp stream_open; live_stream.hpp; DESIGN.md 9c "Open streams").  Between two steps the engine keeps: z of every
+// live utterance in the pool, the slot table {pool offset, F, sid, next frame}, the free column ranges, the step count and the form-0
+// flag.  Nothing in the arenas survives a step: every step and every admission lays its workspace out again.
+int Engine::stream_open(int chunk_frames, int max_live, long long capacity_frames) {
+    if (live_) return fail(STS_ESTATE, "a stream is already open on this engine (sts_stream_close first)");
+    const Model& M = model;
+    if (chunk_frames <= 0 || max_live < 1 || max_live > 1024 || capacity_frames < 1)
+        return fail(STS_EINVAL, "an open stream takes a positive chunk size, 1 <= max_live <= 1024 and a positive capacity");
+    if ((double)capacity_frames * M.inter > 2.0e9 || (double)capacity_frames * M.hop_total > 2.0e9)
+        return fail(STS_EINVAL, "an open stream's capacity_frames * inter_channels and capacity_frames * samples_per_frame may not exceed 2 10^9");
+    if (eq_n > 0) return fail(STS_EINVAL, "an open stream is not available while an equaliser is set: its state is carried per utterance in the frame arena");
+    if (loud_mode != 0) return fail(STS_EINVAL, "an open stream is not available while loudness measurement or normalization is on: its state is carried per utterance in the frame arena");
+    if (record_taps) return fail(STS_EINVAL, "an open stream is not available while taps are recorded");
+    if (have_plan || have_mix || have_gain || have_forced)
+        return fail(STS_EINVAL, "an open stream is not available while a duration plan, a speaker mix, a gain plan or forced durations are pending: their tables are per call");
+    HIPCK(hipSetDevice(device));
+    LimiterDesign d{};
+    if (lim_mode != 0 && !limiter_design(out_rate, lim_gain_db, lim_ceiling, lim_ms, &d)) return fail(STS_EINVAL, "limiter: output rate outside [8000, 48000]");
+    if (conv_math == 3) { const int rc = ensure_overflow_word(); if (rc != STS_OK) return rc; }
+    LiveStream* L = new (std::nothrow) LiveStream();
+    if (!L) return fail(STS_EDEVICE, "out of host memory");
+    L->open(chunk_frames, max_live, capacity_frames);
+    L->halo = stream_halo(); L->hop = M.hop_total;
+    L->P = resampling() ? rs.P : 1; L->Q = resampling() ? rs.Q : 1; L->H = lim_mode != 0 ? d.H : 0;
+    L->form0 = conv_math == 3 && h2_disabled;
+    // (a KB of slack behind the last row: a kernel that stages z in whole vectors may read past a row's last column, as in the arena)
+    const size_t pool_bytes = ((size_t)M.inter * (size_t)capacity_frames + 256) * sizeof(float);
+    if (hipMalloc((void**)&L->zpool, pool_bytes) != hipSuccess || hipMalloc(&L->tab_dev, adopt_tab_bytes(max_live)) != hipSuccess ||
+        hipHostMalloc(&L->tab_host, adopt_tab_bytes(max_live), hipHostMallocDefault) != hipSuccess) {
+        (void)hipGetLastError();
+        if (L->zpool) (void)hipFree(L->zpool);
+        if (L->tab_dev) (void)hipFree(L->tab_dev);
+        delete L;
+        return fail(STS_EDEVICE, "out of device memory (the open stream's latent pool)");
+    }
+    if (poison && hipMemsetD32Async((hipDeviceptr_t)L->zpool, (int)poison, pool_bytes / 4, stream) != hipSuccess) (void)hipGetLastError();
+    live_ = L;
+    return STS_OK;
+}
+
+int Engine::stream_close() {
+    if (!live_) return fail(STS_ESTATE, "no stream is open on this engine");
+    (void)hipSetDevice(device);
+    if (stream) (void)hipStreamSynchronize(stream);
+    if (live_->zpool) (void)hipFree(live_->zpool);
+    if (live_->tab_dev) (void)hipFree(live_->tab_dev);
+    if (live_->tab_host) (void)hipHostFree(live_->tab_host);
+    delete live_;
+    live_ = nullptr;
+    return STS_OK;
+}
+
+// front and flow of the B newcomers in the arithmetic conv_math names, their slots and columns, their z into the pool.  kRetrySplitBf16:
+// the overflow word was raised (conv math 3) -- nothing of the admission is kept, the caller repeats it in form 0
+int Engine::stream_admit_once(int B, const int32_t* const* ids, const int32_t* n, const int32_t* sid, const float* ls, int32_t* slot_out,
+                              int32_t* n_samples_out, int32_t* admitted) {
+    LiveStream& L = *live_;
+    const bool guarded = conv_math == 3;
+    if (guarded) *(volatile unsigned*)ovf_host_ = 0u;
+    poison_bytes_ = 0;
+    host_t0_ = now_us(); host_t_sync_ = 0;
+    StreamSpec ss{L.chunk, [](void*, int32_t, const int16_t*, int32_t, int32_t) { return 0; }, nullptr};
+    RunCtx c;
+    c.B = B; c.ids = ids; c.n = n; c.sid = sid; c.ls = ls; c.ss = &ss; c.bstream = B > 1;
+    int rc;
+    if ((rc = run_setup(c)) != STS_OK) return rc;
+    mark(0);
+    if ((rc = run_text_encoder(c)) != STS_OK) return rc;
+    if ((rc = run_durations(c)) != STS_OK) return rc;          // (a stream never launches ahead: the frame counts are on the host)
+    std::vector<long> F((size_t)B); std::vector<int> sidv((size_t)B), slots((size_t)B, -1);
+    for (int b = 0; b < B; b++) { F[(size_t)b] = c.p_lenF[b]; sidv[(size_t)b] = c.p_sid[b]; }
+    if (!L.admit(B, F.data(), sidv.data(), slots.data())) {    // no room now: the front work is lost, nothing has changed
+        HIPCK(hipStreamSynchronize(stream));
+        *admitted = 0;
+        return STS_OK;
+    }
+    auto undo = [&](int code) { for (const int s : slots) if (s >= 0) { L.retire(s); L.admitted--; L.retired--; } return code; };
+    if ((rc = run_frame_workspace(c)) != STS_OK) return undo(rc);
+    if ((rc = run_flow(c)) != STS_OK) return undo(rc);
+    // z of the newcomers leaves the arena: one table upload, one launch
+    long long* const tab = (long long*)L.tab_host;
+    int* const tlen = (int*)(tab + 2 * (size_t)B);
+    for (int b = 0; b < B; b++) {
+        tab[b] = c.p_offF[b]; tab[B + b] = slots[(size_t)b] >= 0 ? L.slots[(size_t)slots[(size_t)b]].off : 0;
+        tlen[b] = slots[(size_t)b] >= 0 ? (int)F[(size_t)b] : 0;
+    }
+    if (hipMemcpyAsync(L.tab_dev, tab, adopt_tab_bytes(B), hipMemcpyHostToDevice, stream) != hipSuccess) return undo(fail(STS_EDEVICE, "the adoption table's upload failed"));
+    adopt_z(c.bf.z, c.Fld, L.zpool, L.capacity, c.C, (const long long*)L.tab_dev, B, c.maxF, stream);
+    if (hipStreamSynchronize(stream) != hipSuccess || hipGetLastError() != hipSuccess) return undo(fail(STS_EDEVICE, "the admission failed on the device"));
+    if (guarded && *(volatile unsigned*)ovf_host_ != 0u) return undo(kRetrySplitBf16);
+    n_samples.resize((size_t)B);
+    for (int b = 0; b < B; b++) {
+        n_samples[(size_t)b] = (int32_t)out_count((long long)F[(size_t)b] * c.hop);
+        if (slot_out) slot_out[b] = slots[(size_t)b];
+        if (n_samples_out) n_samples_out[b] = n_samples[(size_t)b];
+    }
+    *admitted = B;
+    return STS_OK;
+}
+
+int Engine::stream_admit(int B, const int32_t* const* ids, const int32_t* n, const int32_t* sid, const float* ls, const sts_stream_noise* nz,
+                         int32_t* slot_out, int32_t* n_samples_out, int32_t* admitted) {
+    if (!live_) return fail(STS_ESTATE, "no stream is open on this engine (sts_stream_open first)");
+    if (!admitted) return fail(STS_EINVAL, "an admission needs the `admitted` output");
+    *admitted = 0;
+    LiveStream& L = *live_;
+    if (B < 1 || !ids || !n) return fail(STS_EINVAL, "an admission takes B >= 1 utterances with ids and n");
+    if (B > L.max_live) return fail(STS_EINVAL, "an admission of more utterances than the stream's max_live can never fit");
+    for (int b = 0; nz && b < B; b++)
+        if (!noise_scale_valid(nz[b].noise_scale) || !noise_scale_valid(nz[b].noise_scale_w)) return fail(STS_EINVAL, "noise scales must be finite and >= 0");
+    if (L.free_slots() < B) return STS_OK;                     // (no room now, known before any front work)
+    HIPCK(hipSetDevice(device));
+    std::vector<Noise> keep; keep.swap(noise_utt);             // (NULL: run_setup takes the engine's setting with seed + b)
+    if (nz) for (int b = 0; b < B; b++) noise_utt.push_back(Noise{nz[b].noise_scale, nz[b].noise_scale_w, nz[b].seed});
+    const int math = conv_math;
+    if (math == 3 && L.form0) conv_math = 0;
+    int rc = stream_admit_once(B, ids, n, sid, ls, slot_out, n_samples_out, admitted);
+    if (rc == kRetrySplitBf16) {                               // this admission alone: nothing of the newcomers has been delivered
+        h2_fallbacks++;
+        conv_math = 0;
+        rc = stream_admit_once(B, ids, n, sid, ls, slot_out, n_samples_out, admitted);
+    }
+    conv_math = math;
+    noise_utt.swap(keep);
+    prof.conv_math_fallbacks = h2_fallbacks;
+    return rc;
+}
+
+int Engine::stream_step(int (*cb)(void*, int32_t, const int16_t*, int32_t, int32_t), void* user, int32_t* live_after) {
+    if (!live_) return fail(STS_ESTATE, "no stream is open on this engine (sts_stream_open first)");
+    if (!cb) return fail(STS_EINVAL, "a step takes a callback");
+    LiveStream& L = *live_;
+    Model& M = model;
+    if (live_after) *live_after = L.live_count();
+    if (L.live_count() == 0) return STS_OK;
+    HIPCK(hipSetDevice(device));
+    StreamSpec ss{L.chunk, cb, user};
+    RunCtx c;
+    L.step_slots(c.live_slots);
+    c.live = &L;
+    const int B = c.B = (int)c.live_slots.size();
+    c.ss = &ss; c.bstream = true;                              // (a window's index is never its utterance's: the conditioning is gathered per window)
+    c.bt = BufT{}; c.bf = BufF{};
+    c.ms = M.is_ms == 1; c.H = M.hidden; c.C = M.inter; c.hop = M.hop_total;
+    c.wnH = M.n_flows ? M.cp[0].wn.H : 0; c.wnL = M.n_flows ? M.cp[0].wn.n : 0;
+    // the decode workspace of this step's windows (transient: laid out per step; ensure() synchronises before it moves the arena).  The
+    // flow's buffers are those of one frame -- no flow runs here -- and z is the pool
+    std::vector<int> lenF((size_t)B), offF((size_t)B, 0);
+    for (int b = 0; b < B; b++) lenF[(size_t)b] = (int)L.slots[(size_t)c.live_slots[(size_t)b]].F;
+    c.p_lenF = lenF.data(); c.p_offF = offF.data();
+    c.Ftot = c.Fld = 1; c.maxF = c.maxFld = 1;
+    poison_bytes_ = 0;
+    int rc;
+    if ((rc = plan_output(c)) != STS_OK) return rc;
+    if ((rc = run_frame_workspace(c)) != STS_OK) return rc;
+    c.bf.z = L.zpool; c.Fld = L.capacity;
+    const int math = conv_math;
+    if (math == 3 && L.form0) conv_math = 0;
+    if (conv_math == 3) *(volatile unsigned*)ovf_host_ = 0u;
+    rc = run_stream_steps(c);
+    conv_math = math;
+    L.steps++;
+    prof.conv_math_fallbacks = h2_fallbacks;
+    if (rc == STS_OK && hipGetLastError() != hipSuccess) rc = fail(STS_EDEVICE, "the step failed on the device");
+    if (live_after) *live_after = L.live_count();
     return rc;
 }
 

@@ -11,6 +11,7 @@
 
 #include "../../include/summertts_hip.h"
 #include "kernels.hpp"
+#include "live_stream.hpp"
 #include "model.hpp"
 
 namespace sts {
@@ -218,6 +219,9 @@ private:
     int frame_geometry(RunCtx& c);
     int run_output(RunCtx& c);
     int run_stream_steps(RunCtx& c);
+    int stream_admit_once(int B, const int32_t* const* ids, const int32_t* n, const int32_t* sid, const float* ls, int32_t* slot_out,
+                          int32_t* n_samples_out, int32_t* admitted);
+    int ensure_overflow_word();
     void tap(const char* name, const float* d, int channels, long ld, long length);
     void stage_begin(int s);
     void mark(int i);
@@ -259,6 +263,22 @@ public:
     // n_total (optional): samples delivered
     int run_joined_stream(int B, const int32_t* const* ids, const int32_t* n, const int32_t* sid, const float* ls, const sts_join* join,
                           int chunk_frames, int (*cb)(void*, int32_t, const int16_t*, int32_t, int32_t), void* user, int32_t* n_total);
+    // an open stream (sts_stream_open .. sts_stream_close; live_stream.hpp, DESIGN.md 9c "Open streams"): one per engine.  stream_open fixes
+    // the chunk size, the output rate, the limiter setting, the conv mode and the conv math, and allocates the latent pool
+    // [inter_channels][capacity_frames] by its own hipMalloc (never in arenaF_: every later run lays that out again and may reallocate it).
+    // stream_admit runs front and flow of B newcomers as the packed batch a sts_infer_ids_batch_stream call of them would, and moves their z
+    // into the pool (adopt_z); all or nothing (*admitted = B, or 0: no room now).  stream_step is ONE step of run_stream_steps over every
+    // live slot in ascending slot order, each at its own next frame; a slot retires behind its last chunk or when its callback returns
+    // non-zero.  While a stream is open every other run and every setter of what open fixed returns STS_ESTATE.  Not admitted, and refused
+    // by stream_open (later work): EQ bands, loudness, record taps, a pending duration plan / speaker mix / gain plan / forced durations --
+    // they carry per-call tables or per-utterance filter state in the frame arena.  Not to be called from a chunk callback.
+    int stream_open(int chunk_frames, int max_live, long long capacity_frames);
+    int stream_admit(int B, const int32_t* const* ids, const int32_t* n, const int32_t* sid, const float* ls, const sts_stream_noise* noise,
+                     int32_t* slot_out, int32_t* n_samples_out, int32_t* admitted);
+    int stream_step(int (*cb)(void*, int32_t, const int16_t*, int32_t, int32_t), void* user, int32_t* live_after);
+    int stream_close();
+    bool stream_is_open() const { return live_ != nullptr; }
+    LiveStream* live_ = nullptr;       // null: no stream is open
     // loudness in a stream (sts_set_loudness_streaming; loudness.hip's stream mode, loud_stream.hpp): off, a stream under mode 1 or 2 is
     // refused; on, mode 1 measures what each step delivers from a state carried per utterance in the frame arena (mode 2 stays refused)
     bool loud_streaming = false;

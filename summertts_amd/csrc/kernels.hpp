@@ -416,6 +416,12 @@ void resample_pcm(const ResampleArgs& a, int nwin, long long max_out, hipStream_
 // streaming at the native rate: window w's kept samples src[src_off[w] ..) -> dst[dst_off[w] .. dst_off[w + 1]) (one packed chunk
 // buffer per step); max_n = the most samples one window keeps
 void stream_pack(const int16_t* src, int16_t* dst, const int* src_off, const int* dst_off, int nwin, long long max_n, hipStream_t st);
+// an open stream adopts the latents of an admission (live_stream.hip): B column segments of the channel-major src [C][ld_src] into
+// dst [C][ld_dst], one launch.  tab (device): long long src_off[B] | long long dst_off[B] | int len[B]; segment b is columns
+// [src_off[b], src_off[b] + len[b]) of every row of src, to [dst_off[b], ..) of dst.  max_len = the longest segment.  Nothing outside
+// the destination ranges is written.
+static inline size_t adopt_tab_bytes(int B) { return (size_t)B * 20; }
+void adopt_z(const float* src, long long ld_src, float* dst, long long ld_dst, int C, const long long* tab, int B, int max_len, hipStream_t st);
 
 // Loudness measurement and normalisation (loudness.hip; the definition is there and in include/summertts_hip.h sts_set_loudness)
 constexpr int kLoudMinRate = 8000, kLoudMaxRate = 48000, kLoudPow = 9;

@@ -1,0 +1,140 @@
+// live_stream.hpp -- the host side of an OPEN stream (Engine::stream_open / stream_admit / stream_step / stream_close, DESIGN.md 9c
+// "Open streams"): the geometry of one chunk's window, the slot table of the live utterances, and the first-fit allocator over column
+// ranges of the persistent latent pool.  Plain C++: no HIP, no engine type (tests/live_stream_check.cpp compiles it alone).
+//
+// A closed stream (sts_infer_ids_batch_stream) keeps z of its B utterances in the frame arena for the length of the one call and walks
+// all of them with one step counter.  An open stream keeps z of every live utterance in a pool [inter_channels][capacity] of its own,
+// one column range per utterance, and a frame position PER utterance: utterances are admitted between steps, each starts at frame 0
+// whenever it arrives, and a retired one gives its slot and its columns back.  What a slot's chunks are does not depend on who else is
+// live: the window of a chunk is a function of (F, f0, C, halo, hop, P, Q, H) alone (stream_window below, the one every stream uses).
+//
+// Not admitted (the open stream refuses them when it is opened; later work): the EQ and loudness in a stream (state carried per
+// utterance in the frame arena, which every admission lays out again), and the per-call tables of a duration plan, a speaker mix, a gain
+// plan, forced durations and record taps (they are indexed by "utterance b of this call", which an open stream does not have).
+#pragma once
+#include <stdint.h>
+
+#include <algorithm>
+#include <vector>
+
+namespace sts {
+
+// The window of chunk frames [f0, f1) = [f0, min(F, f0 + C)) of an utterance of F frames: frames [w0, w1) = the chunk and `halo` frames
+// on either side, clipped to the utterance.  Its native samples [f0 hop, f1 hop) are, at the output rate P / Q, the outputs j with
+// ceil(f0 hop P / Q) <= j < ceil(f1 hop P / Q) = [j0, j1) of Nout.  With the limiter (H > 0: its look-ahead in output samples) they are
+// produced from the float signal over [jl0, jl1) = [j0 - 2H, j1 + 2H) clipped to the utterance; without it [jl0, jl1) = [j0, j1).
+struct StreamWin { long f0, f1, w0, w1; long long j0, j1, jl0, jl1, Nout; };
+static inline long long stream_out_count(long long native, long long P, long long Q) { return P == Q ? native : (native * P + Q - 1) / Q; }
+static inline StreamWin stream_window(long F, long f0, long C, long halo, long hop, long long P, long long Q, long long H) {
+    StreamWin w{};
+    w.f0 = f0; w.f1 = std::min<long>(F, f0 + C);
+    w.w0 = std::max<long>(0, f0 - halo); w.w1 = std::min<long>(F, w.f1 + halo);
+    w.j0 = stream_out_count((long long)f0 * hop, P, Q); w.j1 = stream_out_count((long long)w.f1 * hop, P, Q);
+    w.Nout = stream_out_count((long long)F * hop, P, Q);
+    w.jl0 = H > 0 ? std::max<long long>(0, w.j0 - 2 * H) : w.j0; w.jl1 = H > 0 ? std::min<long long>(w.Nout, w.j1 + 2 * H) : w.j1;
+    return w;
+}
+
+// one live utterance: its columns [off, off + F) of the pool, its speaker, the first frame of its next chunk
+struct LiveSlot { bool live = false; long long off = 0; long F = 0; int sid = 0; long f = 0; };
+struct LiveRange { long long off, len; };
+
+// The capacity a group of `max_live` utterances needs when none is longer than `longest` frames: every slot can hold the longest one.
+// (sts_pool sizes its streams with it: longest = kLivePoolFrames, 16.4 s of speech at 256 samples per frame and 16 kHz -- 0.8 MB of
+// pool per slot at 192 channels.  Requests that do not fit an EMPTY pool run as a closed stream, as without admission.)
+constexpr long long kLivePoolFrames = 1024;
+static inline long long live_capacity_rule(int max_live, long long longest) { return (long long)max_live * longest; }
+
+struct LiveStream {
+    // fixed when the stream is opened
+    int chunk = 0, max_live = 0; long long capacity = 0;
+    int halo = 0, hop = 0; long long P = 1, Q = 1, H = 0;       // the window geometry's facts: stream_halo, samples per frame, rate, limiter
+    // the pool and the adoption table (engine-owned device / pinned memory; plain pointers: this header knows no HIP)
+    float* zpool = nullptr; void* tab_dev = nullptr; void* tab_host = nullptr;
+    // state between steps
+    std::vector<LiveSlot> slots; std::vector<LiveRange> free_ranges;      // free_ranges: ascending, never adjacent (coalesced)
+    long long steps = 0;            // stream_step calls since open (STS_DBG_STREAM_RETRY_STEP counts them)
+    bool form0 = false;             // conv math 3: an overflow was raised in a step -- split-bf16 until the stream is closed
+    long long admitted = 0, retired = 0;
+
+    void open(int chunk_frames, int max_live_, long long capacity_frames) {
+        chunk = chunk_frames; max_live = max_live_; capacity = capacity_frames;
+        slots.assign((size_t)max_live, LiveSlot());
+        free_ranges.assign(1, LiveRange{0, capacity});
+        steps = 0; form0 = false; admitted = retired = 0;
+    }
+    int live_count() const { int n = 0; for (const LiveSlot& s : slots) n += s.live; return n; }
+    int free_slots() const { return max_live - live_count(); }
+    long long free_frames() const { long long n = 0; for (const LiveRange& r : free_ranges) n += r.len; return n; }
+
+    // first fit: the lowest free range that holds `len` columns gives its first `len`; -1: none does
+    static long long take(std::vector<LiveRange>& fr, long long len) {
+        for (size_t i = 0; i < fr.size(); i++)
+            if (fr[i].len >= len) {
+                const long long off = fr[i].off;
+                fr[i].off += len; fr[i].len -= len;
+                if (fr[i].len == 0) fr.erase(fr.begin() + (long)i);
+                return off;
+            }
+        return -1;
+    }
+    // columns [off, off + len) become free again; neighbours coalesce
+    static void give(std::vector<LiveRange>& fr, long long off, long long len) {
+        if (len <= 0) return;
+        size_t i = 0;
+        while (i < fr.size() && fr[i].off < off) i++;
+        fr.insert(fr.begin() + (long)i, LiveRange{off, len});
+        if (i + 1 < fr.size() && fr[i].off + fr[i].len == fr[i + 1].off) { fr[i].len += fr[i + 1].len; fr.erase(fr.begin() + (long)i + 1); }
+        if (i > 0 && fr[i - 1].off + fr[i - 1].len == fr[i].off) { fr[i - 1].len += fr[i].len; fr.erase(fr.begin() + (long)i); }
+    }
+
+    // All or nothing: utterance b of the admission (F[b] frames, speaker sid[b]) takes the lowest free slot and the first fit of F[b]
+    // columns, in the order b = 0 .. B - 1; slot_out[b] = its slot (-1: an utterance without frames takes none and is never stepped).
+    // False: slots or columns do not suffice, and nothing has changed.
+    bool admit(int B, const long* F, const int* sid, int* slot_out) {
+        std::vector<LiveRange> fr = free_ranges;
+        std::vector<long long> off((size_t)B, 0);
+        int need = 0;
+        for (int b = 0; b < B; b++) {
+            if (F[b] < 0) return false;
+            if (F[b] == 0) continue;
+            need++;
+            if ((off[(size_t)b] = take(fr, F[b])) < 0) return false;
+        }
+        if (need > free_slots()) return false;
+        size_t s = 0;
+        for (int b = 0; b < B; b++) {
+            if (F[b] == 0) { slot_out[b] = -1; continue; }
+            while (slots[s].live) s++;
+            slots[s] = LiveSlot{true, off[(size_t)b], F[b], sid ? sid[b] : 0, 0};
+            slot_out[b] = (int)s;
+            admitted++;
+        }
+        free_ranges.swap(fr);
+        return true;
+    }
+    void retire(int s) {
+        LiveSlot& sl = slots[(size_t)s];
+        if (!sl.live) return;
+        give(free_ranges, sl.off, sl.F);
+        sl = LiveSlot();
+        retired++;
+    }
+    // the live slots of the next step, ascending
+    void step_slots(std::vector<int>& out) const {
+        out.clear();
+        for (size_t s = 0; s < slots.size(); s++) if (slots[s].live) out.push_back((int)s);
+    }
+    StreamWin window(int s) const { const LiveSlot& sl = slots[(size_t)s]; return stream_window(sl.F, sl.f, chunk, halo, hop, P, Q, H); }
+    // slot s has delivered the chunk of window(s): it moves on, and retires behind its last chunk or when its callback stopped it.
+    // True: it retired.
+    bool delivered(int s, bool stop) {
+        LiveSlot& sl = slots[(size_t)s];
+        sl.f = std::min<long>(sl.F, sl.f + chunk);
+        if (stop || sl.f >= sl.F) { retire(s); return true; }
+        return false;
+    }
+    void drop_all() { for (size_t s = 0; s < slots.size(); s++) retire((int)s); }
+};
+
+}  // namespace sts

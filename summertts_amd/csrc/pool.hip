@@ -59,6 +59,8 @@ struct sts_pool {
     bool eq_streaming = false;         // sts_pool_set_eq_streaming (... unless this is on)
     bool stop = false;
     int64_t batches = 0, requests = 0;
+    bool stream_admission = false;     // sts_pool_set_stream_admission: streamed groups run as open streams (run_open_group)
+    int64_t stream_groups = 0, admitted_midstream = 0;      // sts_pool_stream_stats
 
     void worker(int k) {
         Engine& eng = *engines[k];
@@ -78,7 +80,12 @@ struct sts_pool {
                 }
             }
             if (take.front()->joined) { run_joined_request(eng, *take.front()); cv_done.notify_all(); continue; }
-            if (take.front()->stream) { run_stream_group(eng, take); cv_done.notify_all(); continue; }
+            if (take.front()->stream) {
+                // (the three settings only change while no request is outstanding)
+                if (stream_admission && loud_mode == 0 && eq_bands == 0) run_open_group(eng, take); else run_stream_group(eng, take);
+                cv_done.notify_all();
+                continue;
+            }
             // run `grp` as one packed batch; on failure of a multi-request batch, re-run its members one by one so
             // that a bad request (e.g. an id outside the vocabulary) only fails itself
             auto run_group = [&](const std::vector<std::shared_ptr<Request>>& grp, auto&& self) -> void {
@@ -218,6 +225,98 @@ struct sts_pool {
             r->done = true;
         }
         batches++; requests += B;
+    }
+
+    // sts_pool_set_stream_admission: the group as an OPEN stream on this engine (Engine::stream_open; chunk size of the group, max_live =
+    // max_batch, capacity by live_capacity_rule: every slot can hold kLivePoolFrames frames).  Between two steps the worker looks at the
+    // FIFO: while its head is a streaming request of the group's chunk size and slots are free it takes up to the free count and admits
+    // them.  A head of any other kind stays where it is.  Tickets complete as in run_stream_group: at a member's last chunk or its stop.
+    void run_open_group(Engine& eng, const std::vector<std::shared_ptr<Request>>& first) {
+        const int32_t chunk = first.front()->chunk;
+        if (eng.stream_open(chunk, max_batch, live_capacity_rule(max_batch, kLivePoolFrames)) != STS_OK) { run_stream_group(eng, first); return; }
+        struct Ctx { sts_pool* p; std::vector<std::shared_ptr<Request>> slot; std::vector<int32_t> total; };
+        Ctx cx{this, std::vector<std::shared_ptr<Request>>((size_t)max_batch), std::vector<int32_t>((size_t)max_batch, 0)};
+        auto finish = [this](Request& r, int rc, const std::string& err) {
+            { std::lock_guard<std::mutex> lk(mu); r.rc = rc; if (rc != STS_OK) r.err = err; r.done = true; }
+            cv_done.notify_all();
+        };
+        auto cb = [](void* u, int32_t slot, const int16_t* pcm, int32_t ns, int32_t off) -> int {
+            Ctx& c = *(Ctx*)u;
+            std::shared_ptr<Request> r = c.slot[(size_t)slot];
+            r->n += ns;
+            const int stop = r->cb(r->user, pcm, ns, off);
+            if (stop != 0 || r->n >= c.total[(size_t)slot]) {        // (the engine retires the slot by the same rule: it may be taken again at once)
+                c.slot[(size_t)slot].reset();
+                { std::lock_guard<std::mutex> lk(c.p->mu); r->rc = STS_OK; r->done = true; }
+                c.p->cv_done.notify_all();
+            }
+            return stop;
+        };
+        std::vector<std::shared_ptr<Request>> closed;       // members that do not fit the EMPTY pool: as a closed stream behind the drain
+        // one admission of `grp` as a packed batch; failing with several members it is retried one by one, so that a bad request fails
+        // alone.  No room now: `back` receives the members to return to the head of the FIFO (`closed`: the pool was empty)
+        auto admit = [&](const std::vector<std::shared_ptr<Request>>& grp, std::vector<std::shared_ptr<Request>>& back, auto&& self) -> void {
+            const int B = (int)grp.size();
+            std::vector<const int32_t*> idp((size_t)B); std::vector<int32_t> n((size_t)B), sid((size_t)B), slots((size_t)B, -1), tot((size_t)B, 0);
+            std::vector<float> ls((size_t)B); std::vector<sts_stream_noise> nz((size_t)B);
+            for (int b = 0; b < B; b++) {
+                const Request& r = *grp[(size_t)b];
+                idp[(size_t)b] = r.ids.data(); n[(size_t)b] = (int32_t)r.ids.size(); sid[(size_t)b] = r.sid; ls[(size_t)b] = r.ls;
+                nz[(size_t)b] = sts_stream_noise{r.noise.ns, r.noise.nsw, r.noise.seed};
+            }
+            const bool midstream = eng.live_->steps > 0 && eng.live_->live_count() > 0;
+            int32_t admitted = 0;
+            const int rc = eng.stream_admit(B, idp.data(), n.data(), sid.data(), ls.data(), nz.data(), slots.data(), tot.data(), &admitted);
+            if (rc != STS_OK || admitted == 0) {
+                if (B > 1) { for (auto& r : grp) self(std::vector<std::shared_ptr<Request>>{r}, back, self); return; }
+                if (rc != STS_OK) { finish(*grp.front(), rc, eng.error()); std::lock_guard<std::mutex> lk(mu); batches++; requests++; return; }
+                if (eng.live_->live_count() == 0) closed.push_back(grp.front()); else back.push_back(grp.front());
+                return;
+            }
+            for (int b = 0; b < B; b++) {
+                Request& r = *grp[(size_t)b];
+                r.n = 0;
+                if (slots[(size_t)b] < 0) { finish(r, STS_OK, ""); continue; }      // (no frames: nothing to deliver)
+                cx.slot[(size_t)slots[(size_t)b]] = grp[(size_t)b]; cx.total[(size_t)slots[(size_t)b]] = tot[(size_t)b];
+            }
+            std::lock_guard<std::mutex> lk(mu);
+            batches++; requests += B; if (midstream) admitted_midstream += B;
+        };
+        { std::lock_guard<std::mutex> lk(mu); stream_groups++; }
+        std::vector<std::shared_ptr<Request>> more = first, back;
+        bool blocked = false;           // an admission found no room: none is tried again before a slot retires (each costs its front work)
+        for (;;) {
+            if (!more.empty()) {
+                back.clear();
+                admit(more, back, admit);
+                more.clear();
+                if (!back.empty()) {
+                    blocked = true;
+                    { std::lock_guard<std::mutex> lk(mu); for (auto it = back.rbegin(); it != back.rend(); ++it) queue.push_front(*it); }
+                    cv_work.notify_all();            // (back at the head of the FIFO: another worker may be free)
+                }
+            }
+            const int live = eng.live_->live_count();
+            if (live > 0) {
+                int32_t after = 0;
+                const int rc = eng.stream_step(cb, &cx, &after);
+                if (rc != STS_OK) {      // the unfinished members end with the error
+                    for (auto& r : cx.slot) if (r) { finish(*r, rc, eng.error()); r.reset(); }
+                    break;
+                }
+                if (after < live) blocked = false;
+            }
+            if (!blocked) {
+                std::lock_guard<std::mutex> lk(mu);
+                const size_t room = (size_t)eng.live_->free_slots();
+                while (!queue.empty() && more.size() < room && queue.front()->stream && !queue.front()->joined && queue.front()->chunk == chunk) {
+                    more.push_back(queue.front()); queue.pop_front();
+                }
+            }
+            if (more.empty() && eng.live_->live_count() == 0) break;
+        }
+        (void)eng.stream_close();
+        for (auto& r : closed) run_stream_group(eng, std::vector<std::shared_ptr<Request>>{r});
     }
 };
 
@@ -477,6 +576,22 @@ int sts_pool_set_eq_streaming(sts_pool* p, int enable) {
     if (!p->pending.empty()) return pool_err(STS_ESTATE, "requests are outstanding: wait for them before changing the equaliser's stream mode");
     for (auto& e : p->engines) e->eq_streaming = enable != 0;
     p->eq_streaming = enable != 0;
+    return STS_OK;
+}
+
+int sts_pool_set_stream_admission(sts_pool* p, int enable) {
+    if (!p) return pool_err(STS_EINVAL, "null pool");
+    std::lock_guard<std::mutex> lk(p->mu);
+    if (!p->pending.empty()) return pool_err(STS_ESTATE, "requests are outstanding: wait for them before changing how streamed groups run");
+    p->stream_admission = enable != 0;
+    return STS_OK;
+}
+int sts_pool_get_stream_admission(const sts_pool* p) { return p && p->stream_admission ? 1 : 0; }
+int sts_pool_stream_stats(sts_pool* p, int64_t* groups, int64_t* admitted_midstream) {
+    if (!p) return pool_err(STS_EINVAL, "null pool");
+    std::lock_guard<std::mutex> lk(p->mu);
+    if (groups) *groups = p->stream_groups;
+    if (admitted_midstream) *admitted_midstream = p->admitted_midstream;
     return STS_OK;
 }
 

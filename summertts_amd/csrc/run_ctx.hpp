@@ -121,6 +121,10 @@ struct Engine::RunCtx {
     }
     // (behind everything else) a joined stream: its step geometry, made when the frame counts arrive
     JsPlan js;
+    // (and behind that) one step of an open stream (Engine::stream_step, live_stream.hpp): "utterance" b of this context is the live slot
+    // live_slots[b], its z lies at its own offset in the stream's pool (bf.z, leading dimension Fld = the pool's capacity), and its chunk
+    // starts at its own next frame.  Null: a closed call
+    LiveStream* live = nullptr; std::vector<int> live_slots;
 };
 #define RUN_ALIASES(c)                                                                                                              \
     [[maybe_unused]] Model& M = model;                                                                                              \

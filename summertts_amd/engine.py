@@ -326,6 +326,17 @@ def load_library() -> C.CDLL:
     lib.sts_pool_submit_stream.restype = C.c_int64
     lib.sts_pool_submit_stream.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_float, C.c_uint64,
                                            C.c_int32, CHUNK_CB, C.c_void_p]
+    lib.sts_stream_open.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int64]
+    lib.sts_stream_admit.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                     C.c_void_p]
+    lib.sts_stream_step.argtypes = [C.c_void_p, BATCH_CHUNK_CB, C.c_void_p, C.c_void_p]
+    lib.sts_stream_info.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.sts_stream_close.argtypes = [C.c_void_p]
+    lib.sts_debug_adopt_z.argtypes = [C.c_int, C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                      C.c_int32]
+    lib.sts_pool_set_stream_admission.argtypes = [C.c_void_p, C.c_int]
+    lib.sts_pool_get_stream_admission.argtypes = [C.c_void_p]
+    lib.sts_pool_stream_stats.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
     lib.sts_free.argtypes = [C.c_void_p]
     lib.sts_debug_conv1d.argtypes = [C.c_int, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32,
                                      C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_int32,
@@ -363,7 +374,33 @@ EXPORTED_SYMBOLS = [
     "sts_set_eq", "sts_get_eq", "sts_eq_check", "sts_eq_design", "sts_eq_apply", "sts_pool_set_eq", "sts_multi_set_eq",
     "sts_set_eq_streaming", "sts_get_eq_streaming", "sts_pool_set_eq_streaming", "sts_eq_apply_chunked",
     "sts_set_loudness_streaming", "sts_get_loudness_streaming", "sts_loudness_measure_chunked",
+    "sts_stream_open", "sts_stream_admit", "sts_stream_step", "sts_stream_info", "sts_stream_close", "sts_debug_adopt_z",
+    "sts_pool_set_stream_admission", "sts_pool_get_stream_admission", "sts_pool_stream_stats",
 ]
+
+
+class StreamNoise(C.Structure):
+    """``sts_stream_noise``: the sampling noise of one utterance of an admission (Synthesizer.stream_admit)"""
+    _fields_ = [("noise_scale", C.c_float), ("noise_scale_w", C.c_float), ("seed", C.c_uint64)]
+
+
+def debug_adopt_z(src, dst, src_off, dst_off, lengths, device: int = 0) -> np.ndarray:
+    """The kernel that moves an admission's latents into an open stream's pool (sts_debug_adopt_z), on caller data: columns
+    ``[src_off[b], src_off[b] + lengths[b])`` of every row of ``src`` [C][ld_src] go to ``[dst_off[b], ...)`` of a copy of ``dst``
+    [C][ld_dst], which is returned; everything outside the destination ranges is what ``dst`` held."""
+    lib = load_library()
+    a = np.ascontiguousarray(src, dtype=np.float32)
+    out = np.array(dst, dtype=np.float32, order="C", copy=True)
+    if a.ndim != 2 or out.ndim != 2 or a.shape[0] != out.shape[0]:
+        raise ValueError("src [C][ld_src] and dst [C][ld_dst] with the same C are required")
+    so = np.ascontiguousarray(src_off, dtype=np.int64)
+    do = np.ascontiguousarray(dst_off, dtype=np.int64)
+    ln = np.ascontiguousarray(lengths, dtype=np.int32)
+    if not (so.size == do.size == ln.size):
+        raise ValueError("one source offset, destination offset and length per segment")
+    _check(lib, lib.sts_debug_adopt_z(device, a.ctypes.data, a.shape[0], a.shape[1], out.ctypes.data, out.shape[1], so.ctypes.data,
+                                      do.ctypes.data, ln.ctypes.data, ln.size))
+    return out
 
 
 def speaker_mix_check(speaker_num: int, gin: int, mixes) -> None:
@@ -904,6 +941,53 @@ class Synthesizer:
 
     def stream_halo_frames(self) -> int:
         return int(self.lib.sts_stream_halo_frames(self.h))
+
+    # -- open streams (sts_stream_open .. sts_stream_close) -----------------------------------
+    def stream_open(self, chunk_frames: int, max_live: int, capacity_frames: int):
+        """Opens the engine's stream: utterances are admitted between its steps (``stream_admit``), every ``stream_step`` decodes the next
+        chunk of each live one.  Fixes chunk size, output rate, limiter, conv mode and conv math until ``stream_close``."""
+        _check(self.lib, self.lib.sts_stream_open(self.h, int(chunk_frames), int(max_live), int(capacity_frames)))
+
+    def stream_admit(self, ids, sid: Optional[Sequence[int]] = None, length_scale: Optional[Sequence[float]] = None, noise=None):
+        """Admits the utterances ``ids`` as one packed batch.  ``noise``: None (the engine's setting, utterance b with seed + b) or one
+        ``(noise_scale, noise_scale_w, seed)`` per utterance.  Returns ``(slots, n_samples)`` -- per utterance its slot (the ``utt`` of its
+        chunks) and its total output samples -- or None when slots or frames do not suffice now (nothing has changed)."""
+        p = PreparedBatch(ids, sid, length_scale)
+        B = len(p)
+        nz = None
+        if noise is not None:
+            nz = (StreamNoise * B)(*[StreamNoise(float(a), float(b), int(c) & 0xFFFFFFFFFFFFFFFF) for a, b, c in noise])
+        slots = np.full(B, -1, np.int32)
+        tot = np.zeros(B, np.int32)
+        adm = C.c_int32()
+        _check(self.lib, self.lib.sts_stream_admit(self.h, B, p.ptrs, p.n_p, p.sid_p, p.ls_p, None if nz is None else C.cast(nz, C.c_void_p),
+                                                   slots.ctypes.data, tot.ctypes.data, C.addressof(adm)))
+        if adm.value == 0:
+            return None
+        return [int(v) for v in slots], [int(v) for v in tot]
+
+    def stream_step(self, on_chunk=None):
+        """One step: ``on_chunk(slot, pcm: np.int16[], sample_offset)`` per live slot in ascending slot order (return True to stop that
+        slot).  Returns (list of ``(slot, pcm, sample_offset)`` of this step, slots still live)."""
+        got = []
+
+        def _cb(user, utt, pcm, ns, off):
+            arr = np.ctypeslib.as_array(pcm, shape=(ns,)).copy() if ns else np.zeros(0, np.int16)
+            got.append((int(utt), arr, int(off)))
+            return 1 if (on_chunk and on_chunk(int(utt), arr, int(off))) else 0
+        cb = BATCH_CHUNK_CB(_cb)
+        live = C.c_int32()
+        _check(self.lib, self.lib.sts_stream_step(self.h, cb, None, C.addressof(live)))
+        return got, int(live.value)
+
+    def stream_info(self) -> dict:
+        o, l, fs, ff, st = C.c_int32(), C.c_int32(), C.c_int32(), C.c_int64(), C.c_int64()
+        _check(self.lib, self.lib.sts_stream_info(self.h, C.addressof(o), C.addressof(l), C.addressof(fs), C.addressof(ff), C.addressof(st)))
+        return {"open": bool(o.value), "live": int(l.value), "free_slots": int(fs.value), "free_frames": int(ff.value), "steps": int(st.value)}
+
+    def stream_close(self):
+        """Drops the live slots without delivering and frees the pool."""
+        _check(self.lib, self.lib.sts_stream_close(self.h))
 
     # -- batched -----------------------------------------------------------------------------
     def prepare(self, ids: Sequence[Sequence[int]], sid: Optional[Sequence[int]] = None,
@@ -1458,6 +1542,22 @@ class Pool:
         rc = self.lib.sts_pool_set_eq_streaming(self.h, 1 if enable else 0)
         if rc != 0:
             raise StsError(f"sts_pool_set_eq_streaming: {rc}: {self.lib.sts_pool_last_error().decode()}")
+
+    def set_stream_admission(self, enable: bool = True):
+        """Streamed groups run as open streams: a worker admits queued streaming requests of its group's chunk size between the steps of
+        the running stream (sts_pool_set_stream_admission).  Raises while any request is outstanding (STS_ESTATE)."""
+        rc = self.lib.sts_pool_set_stream_admission(self.h, 1 if enable else 0)
+        if rc != 0:
+            raise StsError(f"sts_pool_set_stream_admission: {rc}: {self.lib.sts_pool_last_error().decode()}")
+
+    def stream_admission(self) -> bool:
+        return bool(self.lib.sts_pool_get_stream_admission(self.h))
+
+    def stream_stats(self):
+        """(streamed groups run as open streams, requests admitted into a running one)"""
+        g, a = C.c_int64(), C.c_int64()
+        self.lib.sts_pool_stream_stats(self.h, C.addressof(g), C.addressof(a))
+        return int(g.value), int(a.value)
 
     def stats(self):
         b, r = C.c_int64(), C.c_int64()

@@ -21,6 +21,13 @@ a 5 ms fade, three ways:
   (b) serial_streams  the sentences as sts_infer_ids_stream calls one after another (no batch for the front and the flow, no join)
   (c) whole_joined    one sts_infer_ids_joined (the reader hears the paragraph when all of it is done)
 Per (model, chunk, form): time to the first and to the last chunk, seconds of audio per wall second.
+
+--late: a late arrival at a pool of one engine (DESIGN.md 9c "Open streams") -- --clients clients (default 32) whose streaming requests
+are queued together and run as one group, and one more client that submits its request when the group's second step has delivered.  Two
+legs: admission off (the group is a closed stream: the late client waits until it has drained) and on (sts_pool_set_stream_admission: the
+late client is admitted between two steps).  Per leg: the late client's time from submit to its first chunk, the group's first-chunk
+times, and the group's last-chunk time with and without the late client.  A library without the switch (an older build) runs the off leg
+only.
 """
 from __future__ import annotations
 
@@ -90,6 +97,86 @@ def _whole_joined(syn, ids, chunk):
     return [t], t, pcm.size, t
 
 
+def _late_run(pool, ids, late_ids, chunk, with_late):
+    """one group of len(ids) streaming requests queued together behind a gate request, the late one submitted from client 0's second chunk"""
+    import threading
+    gate_in, gate_go = threading.Event(), threading.Event()
+    t0 = [0.0]
+    first = [None] * len(ids)
+    last = [0.0] * len(ids)
+    late = {"submit": None, "first": None, "last": None, "ticket": None}
+    seen0 = [0]
+
+    def on_gate(pcm, off):          # holds the one worker until every client is queued, then stops: the group is what is queued
+        gate_in.set()
+        gate_go.wait(60.0)
+        return True
+
+    def on_late(pcm, off):
+        t = time.perf_counter()
+        if late["first"] is None:
+            late["first"] = t
+        late["last"] = t
+        return False
+
+    def client(i):
+        def cb(pcm, off):
+            t = time.perf_counter()
+            if first[i] is None:
+                first[i] = t
+            last[i] = t
+            if i == 0 and with_late:
+                seen0[0] += 1
+                if seen0[0] == 2:          # the group's second step has delivered
+                    late["submit"] = time.perf_counter()
+                    late["ticket"] = pool.submit_stream(late_ids, chunk, on_late)
+            return False
+        return cb
+    tg = pool.submit_stream(ids[0][:8], chunk + 1, on_gate)
+    gate_in.wait(60.0)
+    tickets = [pool.submit_stream(x, chunk, client(i)) for i, x in enumerate(ids)]
+    t0[0] = time.perf_counter()
+    gate_go.set()
+    pool.wait(tg)
+    for t in tickets:
+        pool.wait(t)
+    out = {"group_first_ms_min": (min(first) - t0[0]) * 1e3, "group_first_ms_max": (max(first) - t0[0]) * 1e3,
+           "group_last_ms": (max(last) - t0[0]) * 1e3}
+    if with_late:
+        pool.wait(late["ticket"])
+        out["late_first_ms"] = (late["first"] - late["submit"]) * 1e3
+        out["late_last_ms"] = (late["last"] - late["submit"]) * 1e3
+        out["late_first_before_group_last"] = bool(late["first"] < max(last))
+    return out
+
+
+def _late(a) -> None:
+    kind = a.models.split(",")[0]
+    cfg = sb.full_cfg(kind)
+    blob = sb.make_blob(cfg, 1234)
+    chunk = int(a.chunks.split(",")[0])
+    ids = [sb.synthetic_ids(a.phonemes, cfg.vocab, salt=u) for u in range(a.clients)]
+    late_ids = sb.synthetic_ids(a.phonemes, cfg.vocab, salt=a.clients)
+    for admission in (False, True):
+        pool = engine.Pool(blob, device=0, n_engines=1, max_batch=2 * a.clients)
+        if admission:
+            if not hasattr(pool, "set_stream_admission"):
+                pool.close()
+                break
+            pool.set_stream_admission(True)
+        for with_late in (False, True):
+            _late_run(pool, ids, late_ids, chunk, with_late)          # warm-up of this shape
+            runs = [_late_run(pool, ids, late_ids, chunk, with_late) for _ in range(a.reps)]
+            row = {"model": kind, "scenario": "late_arrival", "admission": admission, "late_client": with_late, "clients": a.clients,
+                   "chunk_frames": chunk, "phonemes": a.phonemes, "reps": a.reps}
+            for k in runs[0]:
+                row[k] = float(np.median([r[k] for r in runs])) if not isinstance(runs[0][k], bool) else all(r[k] for r in runs)
+            if hasattr(pool, "stream_stats"):
+                row["stream_groups"], row["admitted_midstream"] = pool.stream_stats()
+            print(json.dumps(row), flush=True)
+        pool.close()
+
+
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--models", default="hifigan_sdp,mbb_fix")
@@ -103,7 +190,12 @@ def main() -> None:
     ap.add_argument("--loud", type=int, default=0, help="1: loudness mode 1 on every call, measured in the streams (sts_set_loudness_streaming)")
     ap.add_argument("--joined", action="store_true", help="a paragraph: joined stream against the whole joined call and single streams in turn")
     ap.add_argument("--sentences", type=int, default=32)
+    ap.add_argument("--late", action="store_true", help="a late arrival at a pool of one engine, stream admission off and on (first model, first chunk size)")
+    ap.add_argument("--clients", type=int, default=32)
     a = ap.parse_args()
+    if a.late:
+        _late(a)
+        return
     forms = {"batched_stream": _batched, "serial_streams": _serial, "one_batch": _batch}
     if a.joined:
         forms = {"joined_stream": _joined_stream, "serial_streams": _serial, "whole_joined": _whole_joined}
