@@ -36,13 +36,14 @@ int decoder_halo_frames(const Model& M) {
 
 // The windows of one decode pass.  Window w covers frames [zoff[w], zoff[w] + wlen[w]) of the packed z and owns the compact range
 // starting at coff[w] in every decoder buffer.  inl: a single window by value (wlen0 its real length, zoff0 its offset inside z);
-// otherwise the geometry is read from the device tables d_win = ints {zoff[nw], coff[nw], wlen[nw]}  (wlen0 < 0, or no_inline_seg).
+// otherwise the geometry is read from the device tables d_win = the int block of the step's table (stream_step.hpp StepTab: zoff, coff,
+// wlen) -- a call that does not stream uploads the same three columns  (wlen0 < 0, or no_inline_seg).
 struct WinGeom {
     bool inl; int nw, zoff0, wlen0; const int* d_win;
     // in the decoder's buffers at `scale` positions per frame (+ extra per window); in z
-    SegView seg(int scale, int extra) const { return inl ? SegView{nullptr, nullptr, scale, extra, 0, wlen0} : SegView{d_win + nw, d_win + 2 * nw, scale, extra, 0, 0}; }
-    SegView zseg() const { return inl ? SegView{nullptr, nullptr, 1, 0, zoff0, wlen0} : SegView{d_win, d_win + 2 * nw, 1, 0, 0, 0}; }
-    const int* len() const { return inl ? nullptr : d_win + 2 * nw; }     // (null: one window of ilen() frames)
+    SegView seg(int scale, int extra) const { return inl ? SegView{nullptr, nullptr, scale, extra, 0, wlen0} : SegView{d_win + StepTab::coff(nw), d_win + StepTab::wlen(nw), scale, extra, 0, 0}; }
+    SegView zseg() const { return inl ? SegView{nullptr, nullptr, 1, 0, zoff0, wlen0} : SegView{d_win + StepTab::zoff(nw), d_win + StepTab::wlen(nw), 1, 0, 0, 0}; }
+    const int* len() const { return inl ? nullptr : d_win + StepTab::wlen(nw); }     // (null: one window of ilen() frames)
     int ilen() const { return inl ? wlen0 : 0; }
 };
 
@@ -380,8 +381,8 @@ int Engine::run_decode(RunCtx& c, int nw, long Wtot, int maxW, int zoff0, int wl
             Lvl lw; lw.seg = SegView{nullptr, nullptr, 1, 0, 0, nw}; lw.nb = 1; lw.max_len = nw; lw.total = nw; lw.ld = nw;
             // (a run with a speaker mix: the step's table holds each window's UTTERANCE there, and the windows take that column of the blended
             // bt.g [gin][B] -- the same gather with bt.g as the table; a window's index is not its utterance's once a short one has finished)
-            if (c.mix) gather_speaker(bt.g, B, M.gin, d_win + 3 * nw, nw, bf.gwin, stream);
-            else gather_speaker(M.emb_g, M.spk_num, M.gin, d_win + 3 * nw, nw, bf.gwin, stream);
+            if (c.mix) gather_speaker(bt.g, B, M.gin, d_win + StepTab::sid(nw), nw, bf.gwin, stream);
+            else gather_speaker(M.emb_g, M.spk_num, M.gin, d_win + StepTab::sid(nw), nw, bf.gwin, stream);
             conv(M.dec_cond, bf.gwin, lw, bf.cond_win, lw, ConvOpt()); op.ubias = bf.cond_win;
         } else if (M.dec_type == 0 && ms) { conv(M.dec_cond, bt.g, lvB, bt.cond_dec, lvB, ConvOpt()); op.ubias = bt.cond_dec; }
         conv(M.conv_pre, bf.z, lz, bf.x0, lw1, op);
@@ -476,7 +477,7 @@ int Engine::decode_end(RunCtx& c, const float* wave, const WinGeom& win, long Wt
         GainArgs g{};
         g.x = cur; g.y = c.bf.wave_gain; g.pcm = pcm_of(OS_GAIN);
         g.wseg = win.seg(hop, 0); g.hop = hop;
-        if (c.ss) { g.utt = (const int*)(c.bf.stab + stream_tab_utt_off(nw)); g.wtab = (const long long*)(c.bf.stab + stream_tab_ll_off(nw)); }
+        if (c.ss) { const StepTab t(nw, true, false, false, false); g.utt = (const int*)(c.bf.stab + t.utt); g.wtab = (const long long*)(c.bf.stab + t.rs); }
         g.tseg = c.lvT.seg; g.cum = c.bt.cum; g.q = c.bt.gain_q; g.h = c.bt.gain_h;
         gain_plan_run(g, nw, (long long)maxW * hop, stream);
         cur = g.y;

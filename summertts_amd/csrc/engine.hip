@@ -1027,7 +1027,7 @@ int Engine::frame_geometry(RunCtx& c) {
     }
     if (!c.ahead) {   // frame geometry + (normal call) the decode windows = the utterances, in the same copy
         int* pw = pm + 5 * B + 2;
-        for (int b = 0; b < B; b++) { pw[b] = p_offF[b]; pw[B + b] = p_offF[b]; pw[2 * B + b] = p_lenF[b]; }
+        for (int b = 0; b < B; b++) { pw[StepTab::zoff(B) + b] = p_offF[b]; pw[StepTab::coff(B) + b] = p_offF[b]; pw[StepTab::wlen(B) + b] = p_lenF[b]; }
         // (a single utterance carries its geometry in the kernel arguments: nothing on the device reads these tables)
         if (!c.inl || ss) HIPCK(hipMemcpyAsync(c.d_offF, p_offF, (size_t)(5 * B + 2) * 4, hipMemcpyHostToDevice, stream));
     }
@@ -1147,7 +1147,7 @@ int Engine::run_frame_workspace(RunCtx& c) {
         bf.eqws = oc.eqws ? A.get<char>(eq_ws_bytes(B, c.Ocap)) : nullptr;
         bf.stab = nullptr; bf.spack = nullptr; bf.gwin = bf.cond_win = nullptr;
         if (ss) {
-            bf.stab = A.get<char>(c.join ? join_stream_tab_bytes(B, c.gain, oc.eqst, oc.lst) : stream_tab_bytes(B, c.gain, oc.eqst, oc.lst));
+            bf.stab = A.get<char>(StepTab(B, c.gain, oc.eqst, oc.lst, c.join).bytes);
             if (oc.spack) bf.spack = A.get<int16_t>((size_t)c.Ocap);
             if (M.dec_type == 0 && c.ms && c.bstream) { bf.gwin = A.get<float>((size_t)M.gin * B); bf.cond_win = A.get<float>((size_t)M.up_init * B); }
         }
@@ -1526,65 +1526,55 @@ int Engine::run_output(RunCtx& c) {
 // writes into mapped pinned memory: stream_direct), one host synchronisation, and the step's chunks go to the caller in ascending utterance
 // order before the next step is enqueued.  One utterance is the B == 1 case: its one window goes to run_decode by value, and at the native
 // rate without a limiter nothing is packed -- the chunk is downloaded from where the decoder wrote it.
+// (The tables of a step, their layout and the window geometry: stream_step.hpp, the one definition.)
+
+// what the steps of one streaming call share
+struct StreamRun {
+    char* ht = nullptr;             // the step tables' pinned room
+    int16_t* hp = nullptr;          // the step's packed chunks on the host
+    // and on the device: written by the chain's writer when that is the resampler, the EQ or the limiter, else by stream_pack -- which
+    // one utterance does without unless the chunks are to be stored into host memory
+    int16_t* dst = nullptr;
+    // the streamed EQ and streamed loudness: how far each utterance (a joined stream: J) is consumed and which state slot a step reads; the
+    // slots flip only behind a step that does not run again.  Loudness: the call's result tables, which the gate reads behind the last step
+    EqsTrack eqt; LdsTrack ldt;
+    double* ld_tsum = nullptr; float* ld_tpeak = nullptr; float* ld_gain = nullptr;
+};
+// the windows the output side of a step sees: a plain step's nw decode windows, a joined step's one window of J
+struct StreamTail {
+    int n;
+    const float* x; SegView seg;                    // what the resampler reads: the signal and the windows' places in it
+    const int *pack_src, *pack_dst;                 // stream_pack's columns of the int block (a joined step: it never runs)
+    size_t rs, lim, eq, loud;                       // their rows in the step's table (StepTab)
+    long long max_rs, max_out, etiles, ltiles;      // launch dimensions (StepOut)
+};
+
 int Engine::run_stream_steps(RunCtx& c) {
     RUN_ALIASES(c)
     const long Cf = ss->chunk_frames;
     // one step of an open stream (stream_step): utterance b is the live slot c.live_slots[b] -- its z at its offset in the pool, its chunk
     // at its own next frame -- and the loop below runs once.  Everything else of a step is the closed call's
     LiveStream* const open = c.live;
-    // (ensure_pinned below may move the pinned block the geometry tables live in)
+    // (stream_host_buffers may move the pinned block the geometry tables live in)
     std::vector<int> offF, lenF, sidv;
     if (open) for (const int s : c.live_slots) { const LiveSlot& sl = open->slots[(size_t)s]; offF.push_back((int)sl.off); lenF.push_back((int)sl.F); sidv.push_back(sl.sid); }
     else { offF.assign(p_offF, p_offF + B); lenF.assign(p_lenF, p_lenF + B); sidv.assign(c.p_sid, c.p_sid + B); }
-    const size_t hp_off = (up_bytes + ((size_t)Ttot + B) * 4 + 255) & ~(size_t)255;
     const bool joined = c.join;       // a joined stream: the steps walk J, one chunk of the ONE signal per step (join_stream.hpp)
-    const bool seq = c.oc.eqst;      // the EQ runs on every step's windows from its carried state (eq_stream.hpp)
-    const bool sld = c.oc.lst;       // loudness measures every step's windows from its carried state (loud_stream.hpp)
-    const size_t tab_room = ((joined ? join_stream_tab_bytes(B, c.gain, seq, sld) : stream_tab_bytes(B, c.gain, seq, sld)) + 255) & ~(size_t)255;
-    const size_t pcm_bytes = (size_t)c.Ocap * 2 + 256;
-    if (!ensure_pinned(hp_off + tab_room + pcm_bytes)) return fail(STS_EDEVICE, "pinned host allocation failed");
-    c.pm = (int*)pinned_;
-    char* const ht = pinned_ + hp_off;
-    int16_t* hp = (int16_t*)(pinned_ + hp_off + tab_room);
     const OutChain& oc = c.oc;
-    const bool srs = oc.run[OS_RESAMPLE], slim = oc.run[OS_LIMIT], pack = oc.run[OS_PACK];
-    const LimiterDesign& ld = c.limd;
-    // the step's packed chunks on the device: written by the chain's writer when that is the resampler or the limiter, else by stream_pack
-    // -- which one utterance does without unless the chunks are to be stored into host memory
-    int16_t* dst = pack ? bf.spack : bf.pcm;
-    if (stream_direct) {       // posted writes: the last kernel of a step stores the chunks into the mapped pinned buffer itself
-        if (pcm_bytes > pinned_pcm_cap_ || !pinned_pcm_dev_) {
-            (void)hipStreamSynchronize(stream);
-            if (pinned_pcm_) (void)hipHostFree(pinned_pcm_);
-            pinned_pcm_ = nullptr; pinned_pcm_cap_ = 0; pinned_pcm_dev_ = nullptr;
-            if (hipHostMalloc((void**)&pinned_pcm_, pcm_bytes, hipHostMallocMapped) != hipSuccess) return fail(STS_EDEVICE, "pinned host allocation failed");
-            pinned_pcm_cap_ = pcm_bytes;
-            if (hipHostGetDevicePointer((void**)&pinned_pcm_dev_, pinned_pcm_, 0) != hipSuccess) { pinned_pcm_dev_ = nullptr; return fail(STS_EDEVICE, "mapped pinned buffer has no device address"); }
-        }
-        dst = pinned_pcm_dev_; hp = (int16_t*)pinned_pcm_;
-    }
-    poison_host16(hp, (size_t)c.Ocap);
+    StreamRun s;
+    if (const int rc = stream_host_buffers(c, s)) return rc;
     c.d_win = (int*)bf.stab;
+    StepCall call;
+    call.C = Cf; call.halo = halo; call.hop = hop;
+    call.srs = oc.run[OS_RESAMPLE]; call.slim = oc.run[OS_LIMIT]; call.seq = oc.eqst; call.sld = oc.lst; call.gain = c.gain; call.mix = c.mix;
+    if (call.srs) { call.P = rs.P; call.Q = rs.Q; }
+    if (call.slim) call.H = c.limd.H;
+    call.lsrc = oc.src[OS_LOUD];
     std::vector<char> live(B, 1);
     if (ss->delivered) for (int b = 0; b < (joined ? 1 : B); b++) ss->delivered[b] = 0;
     d_pcm = nullptr; total_samples = 0;
-    std::vector<int> wb; std::vector<long long> wj0, wn, wdst;
-    // the streamed EQ: how far each utterance (a joined stream: J) is consumed and which state slot a step reads; a step's rows join its
-    // table upload, its two launches follow the resampler, and the slots flip only behind a step that does not run again
-    EqsTrack eqt; eqt.begin(joined ? 1 : B);
-    auto eq_step = [&](const long long* rows_dev, int nw, long long tiles) {
-        EqArgs a{};
-        a.x = c.stage_out(oc.src[OS_EQ]); a.S = c.eqS; a.tab = d_eq_;
-        a.y = bf.wave_eq; a.pcm = oc.writer == OS_EQ ? dst : nullptr;
-        a.E = bf.eqsE; a.state = bf.eqst; a.slot = eqt.slot; a.wtab = rows_dev;
-        eq_stream_run(a, nw, tiles, stream);
-    };
-    // streamed loudness: the same bookkeeping for the signal loudness reads (the nearest running float stage in front of it); a step's
-    // rows join its table upload behind the EQ's, its two launches follow that stage, and the gate runs once behind the last step
-    LdsTrack ldt;
-    const int lsrc = oc.src[OS_LOUD];
-    double* ld_tsum = nullptr; float* ld_tpeak = nullptr; float* ld_gain = nullptr;
-    if (sld) {
+    s.eqt.begin(joined ? 1 : B);
+    if (call.sld) {     // the call's result tables, every utterance's tiles at its place
         if (loud_k_rate_ != out_rate) {
             if (!loud_coef(out_rate, &loud_k_)) return fail(STS_EINVAL, "loudness: output rate outside [8000, 48000]");
             loud_k_rate_ = out_rate;
@@ -1593,190 +1583,60 @@ int Engine::run_stream_steps(RunCtx& c) {
         std::vector<long long> Nu(nu);
         if (joined) Nu[0] = out_count(c.FJ * hop);
         else for (int b = 0; b < B; b++) Nu[b] = out_count((long long)lenF[b] * hop);
-        ldt.begin(nu);
-        const long long tiles = ldt.layout(Nu.data());
+        s.ldt.begin(nu);
+        const long long tiles = s.ldt.layout(Nu.data());
         char* p = bf.ldres + (size_t)nu * 3 * 8;            // (in front: the gate's table {0, samples consumed, first tile} per utterance)
-        ld_tsum = (double*)p; p += (size_t)tiles * kLdsSlots * 8;
-        ld_tpeak = (float*)p; p += (size_t)tiles * 4;
-        ld_gain = (float*)p;
+        s.ld_tsum = (double*)p; p += (size_t)tiles * kLdsSlots * 8;
+        s.ld_tpeak = (float*)p; p += (size_t)tiles * 4;
+        s.ld_gain = (float*)p;
     }
-    auto loud_step = [&](const long long* rows_dev, int nw, long long tiles) {
-        LoudStreamArgs a{};
-        a.x = c.stage_out(lsrc); a.k = loud_k_;
-        a.wtab = rows_dev; a.state = bf.ldst; a.slot = ldt.slot;
-        a.E = bf.ldsE; a.tsum = ld_tsum; a.tpeak = ld_tpeak;
-        loud_stream_run(a, nw, tiles, stream);
-    };
-    // The window of chunk frames [f0, f1) of an utterance of F frames: frames [w0, w1).  Its native samples [f0 hop, f1 hop) are, at the output
-    // rate, the outputs j with ceil(f0 hop P / Q) <= j < ceil(f1 hop P / Q) = [j0, j1) of Nout (the halo covers the filter's K samples beyond the
-    // chunk's edges too: stream_halo).  The limiter produces them from the float signal over [jl0, jl1) = [j0 - 2H, j1 + 2H) clipped to the
-    // utterance (stream_halo covers that as well); without it [jl0, jl1) = [j0, j1).  (live_stream.hpp stream_window: the one definition)
-    auto window = [&](long F, long f0) { return stream_window(F, f0, Cf, halo, hop, srs ? rs.P : 1, srs ? rs.Q : 1, slim ? ld.H : 0); };
-    // a joined stream's step: the tables of its decode windows (the layout every stream uses: run_decode and the gain kernel read them), the
-    // one window of J for the resampler and the limiter, the join's rows; one upload, one decode over the windows (none: no decoder kernel),
-    // the windowed join, then resampler and limiter on the one utterance J.  Everything around it -- download, synchronisation, the
-    // conv-math-3 repeat, the callback -- is the loop's below
-    JsStep jt; std::vector<JsRow> jrows;
-    const long long NJ = c.FJ * hop;
-    auto joined_step = [&](long k, long long* dsum_out) -> int {
-        const JsPlan& js = c.js;
-        js.step(k, jt);
-        const int nw = (int)jt.win.size();
-        js.rows(jt.g0, jt.g1, jt.win, jrows);
-        int* ti = (int*)ht;
-        long long* tl = (long long*)(ht + stream_tab_ll_off(nw));
-        long long* tm = (long long*)(ht + stream_tab_lim_off(nw));
-        for (int i = 0; i < nw; i++) {
-            const JsWin& w = jt.win[i];
-            ti[i] = offF[w.b] + (int)w.w0; ti[nw + i] = (int)w.coff; ti[2 * nw + i] = (int)(w.w1 - w.w0); ti[3 * nw + i] = c.mix ? w.b : sidv[w.b];
-            ti[4 * nw + i] = 0; ti[5 * nw + i] = 0;
-            for (int q = 0; q < 5; q++) tl[5 * i + q] = 0;
-            tl[5 * i] = w.w0 * hop; tl[5 * i + 1] = (long long)lenF[w.b] * hop;        // (the gain kernel: the window's first sample in its sentence)
-            for (int q = 0; q < 7; q++) tm[7 * i + q] = 0;
-        }
-        ti[6 * nw] = 0;
-        if (c.gain) { int* tu = (int*)(ht + stream_tab_utt_off(nw)); for (int i = 0; i < nw; i++) tu[i] = jt.win[i].b; }
-        const size_t joff = join_stream_tab_j_off(nw, c.gain);
-        long long* jr = (long long*)(ht + joff); long long* jm = jr + 5; long long* jw = jm + 7;
-        const long long u0 = jt.g0 * hop, ulen = (jt.g1 - jt.g0) * hop, nrs = jt.jl1 - jt.jl0, nout = jt.j1 - jt.j0;
-        jr[0] = u0; jr[1] = NJ; jr[2] = jt.jl0; jr[3] = jt.jl1; jr[4] = 0;
-        jm[0] = 0; jm[1] = srs || seq ? jt.jl0 : u0; jm[2] = srs || seq ? nrs : ulen; jm[3] = out_count(NJ); jm[4] = jt.j0; jm[5] = jt.j1; jm[6] = 0;
-        for (int i = 0; i < nw; i++) { const JsRow& r = jrows[i]; jw[5 * i] = r.st; jw[5 * i + 1] = r.en; jw[5 * i + 2] = r.S; jw[5 * i + 3] = r.N; jw[5 * i + 4] = r.xoff; }
-        const size_t eoff = join_stream_tab_eq_off(nw, c.gain);
-        long long etiles = 1;
-        if (seq) {           // (a silence-only step too: the EQ advances over the join's zeros)
-            const EqsRow r = eqt.row(0, 0, srs ? jt.jl0 : u0, srs ? nrs : ulen, jt.jl0, jt.jl1, 0, jt.j0, jt.j1, 0);
-            if (const char* bad = eqs_row_check(r, out_count(NJ))) return fail(STS_EDEVICE, bad);
-            memcpy(ht + eoff, &r, sizeof(r));
-            etiles = eqs_tiles(r.e, r.o1);
-        }
-        const size_t loff = join_stream_tab_loud_off(nw, c.gain, seq);
-        long long ltiles = 1;
-        if (sld) {           // (a silence-only step too: the measurement advances over the join's zeros)
-            const bool at_out = lsrc == OS_EQ || lsrc == OS_RESAMPLE;       // (the window of J at the output rate, else the join's native one)
-            const LdsRow r = ldt.row(0, 0, at_out ? jt.jl0 : u0, at_out ? nrs : ulen, jt.j1);
-            if (const char* bad = lds_row_check(r, out_count(NJ))) return fail(STS_EDEVICE, bad);
-            memcpy(ht + loff, &r, sizeof(r));
-            ltiles = lds_tiles(r.e, r.j1);
-        }
-        HIPCK(hipMemcpyAsync(c.d_win, ht, join_stream_tab_bytes(nw, c.gain, seq, sld), hipMemcpyHostToDevice, stream));
-        if (nw > 0) {
-            const int rc = B == 1 ? run_decode(c, 1, (long)jt.Wtot, (int)jt.maxW, ti[0], ti[2]) : run_decode(c, nw, (long)jt.Wtot, (int)jt.maxW, 0, -1);
-            if (rc != STS_OK) return rc;
-        }
-        JoinWinArgs j{};
-        j.x = c.stage_out(oc.src[OS_JOIN]); j.y = bf.wave_join; j.pcm = oc.writer == OS_JOIN ? dst : nullptr;
-        j.rows = (const long long*)(bf.stab + joff) + 12;
-        j.nw = nw; j.hop = hop; j.h = join_h;
-        j.g0 = u0; j.g1 = jt.g1 * hop; j.k0 = jt.f0 * hop; j.k1 = jt.f1 * hop;
-        join_window_run(j, stream);
-        if (srs) {
-            ResampleArgs a{};
-            a.x = bf.wave_join; a.seg = SegView{nullptr, nullptr, hop, 0, 0, (int)(jt.g1 - jt.g0)};
-            a.table = d_rs_table; a.P = rs.P; a.Q = rs.Q; a.K = rs.K;
-            a.pcm = oc.writer == OS_RESAMPLE ? dst : bf.pcm_rs; a.wave_out = bf.wave_out;
-            a.wtab = (const long long*)(bf.stab + joff);
-            resample_pcm(a, 1, nrs, stream);
-        }
-        if (seq) eq_step((const long long*)(bf.stab + eoff), 1, etiles);
-        if (sld) loud_step((const long long*)(bf.stab + loff), 1, ltiles);
-        if (slim) {
-            LimArgs a{};
-            a.x = c.stage_out(oc.src[OS_LIMIT]);
-            a.H = ld.H; a.c = ld.c; a.G = ld.G;
-            a.pcm = dst;
-            a.wtab = (const long long*)(bf.stab + joff) + 5;
-            limiter_run(a, 1, nout, stream);
-        }
-        wj0.assign(1, jt.j0); wn.assign(1, nout); wdst.assign(1, 0);
-        *dsum_out = nout;
-        return STS_OK;
-    };
+    std::vector<int> wb; std::vector<StepWin> win; StepOut st;
     const long jsteps = joined ? (long)c.js.steps() : 0;
     for (long k = 0;; k++) {
+        // the utterances that get a chunk in this step (a joined stream: the one signal J)
         wb.clear();
         if (joined) { if (k < jsteps && live[0]) wb.push_back(0); }
         else if (open) { if (k == 0) for (int b = 0; b < B; b++) wb.push_back(b); }      // (the one step: every live slot)
         else for (int b = 0; b < B; b++) if (live[b] && k * Cf < lenF[b]) wb.push_back(b);
-        const int nw = (int)wb.size();
-        if (nw == 0) break;
-        long long dsum = 0;                                 // samples of the step's chunks, packed
-        const int16_t* src = dst;                           // where they are on the device
-        if (joined) {       // (here nw == 1 is the one signal J; the step's decode windows and tables are joined_step's own)
-            const int rc = joined_step(k, &dsum);
-            if (rc != STS_OK) return rc;
-        } else {
-            int* ti = (int*)ht;
-            long long* tl = (long long*)(ht + stream_tab_ll_off(nw));
-            long long* tm = (long long*)(ht + stream_tab_lim_off(nw));
-            long long rsum = 0;                             // limiter: the resampler's float outputs of the widened ranges, packed
-            wj0.assign(nw, 0); wn.assign(nw, 0); wdst.assign(nw, 0);
-            long Wtot = 0; int maxW = 0; long long max_out = 0, max_rs = 0, etiles = 1, ltiles = 1;
-            for (int i = 0; i < nw; i++) {
-                const int b = wb[i];
-                const long F = lenF[b];
-                const long f0 = open ? open->slots[(size_t)c.live_slots[b]].f : k * Cf;      // (an open stream: the slot's own next frame)
-                const StreamWin w = window(F, f0);
-                const long wlen = w.w1 - w.w0;
-                const long long nrs = w.jl1 - w.jl0, nout = w.j1 - w.j0;
-                ti[i] = offF[b] + (int)w.w0; ti[nw + i] = (int)Wtot; ti[2 * nw + i] = (int)wlen; ti[3 * nw + i] = c.mix ? b : sidv[b];      // (a mixed run: the window's utterance, a column of bt.g)
-                ti[4 * nw + i] = (int)((Wtot + (f0 - w.w0)) * hop); ti[5 * nw + i] = (int)dsum;
-                tl[5 * i] = (long long)w.w0 * hop; tl[5 * i + 1] = (long long)F * hop; tl[5 * i + 2] = w.jl0; tl[5 * i + 3] = w.jl1; tl[5 * i + 4] = slim ? rsum : dsum;
-                tm[7 * i] = srs || seq ? rsum : (long long)Wtot * hop; tm[7 * i + 1] = srs || seq ? w.jl0 : (long long)w.w0 * hop;
-                tm[7 * i + 2] = srs || seq ? nrs : (long long)wlen * hop; tm[7 * i + 3] = w.Nout;
-                if (seq) {       // the EQ reads the resampler's widened outputs (native rate: the decode window) and writes what the limiter reads
-                    const EqsRow r = srs ? eqt.row(b, rsum, w.jl0, nrs, w.jl0, w.jl1, rsum, w.j0, w.j1, dsum)
-                                         : eqt.row(b, (long long)Wtot * hop, (long long)w.w0 * hop, (long long)wlen * hop, w.jl0, w.jl1, rsum, w.j0, w.j1, dsum);
-                    if (const char* bad = eqs_row_check(r, w.Nout)) return fail(STS_EDEVICE, bad);
-                    memcpy(ht + stream_tab_eq_off(nw, c.gain) + (size_t)i * sizeof(EqsRow), &r, sizeof(r));
-                    etiles = std::max(etiles, eqs_tiles(r.e, r.o1));
-                }
-                if (sld) {       // loudness reads the EQ's or the resampler's widened outputs, else the decode window at the native rate
-                    const LdsRow r = lsrc == OS_EQ ? ldt.row(b, rsum, w.jl0, nrs, w.j1)
-                                     : lsrc == OS_RESAMPLE ? ldt.row(b, slim ? rsum : dsum, w.jl0, nrs, w.j1)
-                                                           : ldt.row(b, (long long)Wtot * hop, (long long)w.w0 * hop, (long long)wlen * hop, w.j1);
-                    if (const char* bad = lds_row_check(r, w.Nout)) return fail(STS_EDEVICE, bad);
-                    memcpy(ht + stream_tab_loud_off(nw, c.gain, seq) + (size_t)i * sizeof(LdsRow), &r, sizeof(r));
-                    ltiles = std::max(ltiles, lds_tiles(r.e, r.j1));
-                }
-                tm[7 * i + 4] = w.j0; tm[7 * i + 5] = w.j1; tm[7 * i + 6] = dsum;
-                rsum += nrs; max_rs = std::max(max_rs, nrs);
-                wj0[i] = w.j0; wn[i] = nout; wdst[i] = dsum;
-                dsum += nout; max_out = std::max(max_out, nout);
-                Wtot += wlen; maxW = std::max<int>(maxW, (int)wlen);
-            }
-            ti[6 * nw] = (int)dsum;
-            if (c.gain) { int* tu = (int*)(ht + stream_tab_utt_off(nw)); for (int i = 0; i < nw; i++) tu[i] = wb[i]; }     // (the gain kernel: each window's utterance)
-            HIPCK(hipMemcpyAsync(c.d_win, ht, stream_tab_bytes(nw, c.gain, seq, sld), hipMemcpyHostToDevice, stream));
-            // one utterance: its window by value (no table load in the decoder's kernels); several: the tables, also while one window is live
-            // (an open stream reads the tables also while one slot is live: one form whatever the live count)
-            int rc = B == 1 && !open ? run_decode(c, 1, Wtot, maxW, ti[0], ti[2]) : run_decode(c, nw, Wtot, maxW, 0, -1);
-            if (rc != STS_OK) return rc;
-            // (run_decode ran the chain up to the gain plan on the windows at their absolute positions)
-            if (srs) {
-                ResampleArgs a{};
-                a.x = c.stage_out(oc.src[OS_RESAMPLE]); a.seg = SegView{c.d_win + nw, c.d_win + 2 * nw, hop, 0, 0, 0};
-                a.table = d_rs_table; a.P = rs.P; a.Q = rs.Q; a.K = rs.K;
-                a.pcm = oc.writer == OS_RESAMPLE ? dst : bf.pcm_rs; a.wave_out = bf.wave_out;
-                a.wtab = (const long long*)(bf.stab + stream_tab_ll_off(nw));
-                resample_pcm(a, nw, max_rs, stream);
-            } else if (pack) {
-                stream_pack(bf.pcm, dst, c.d_win + 4 * nw, c.d_win + 5 * nw, nw, max_out, stream);
-            }
-            if (seq) eq_step((const long long*)(bf.stab + stream_tab_eq_off(nw, c.gain)), nw, etiles);
-            if (sld) loud_step((const long long*)(bf.stab + stream_tab_loud_off(nw, c.gain, seq)), nw, ltiles);
-            if (slim) {          // every window of the step in one launch; it writes the packed chunks in place of the resampler / the pack
-                LimArgs a{};
-                a.x = c.stage_out(oc.src[OS_LIMIT]);
-                a.H = ld.H; a.c = ld.c; a.G = ld.G;
-                a.pcm = dst;
-                a.wtab = (const long long*)(bf.stab + stream_tab_lim_off(nw));
-                limiter_run(a, nw, max_out, stream);
-            }
-            // (nothing packed: the one window's kept samples, at its pack source in the decoder's own PCM)
-            if (oc.chunk_in_place) src = bf.pcm + ti[4 * nw];
+        const int nu = (int)wb.size();
+        if (nu == 0) break;
+        // the step's tables (a joined step: of its own decode windows, none in a silence-only step, and of the one window of J)
+        const char* bad;
+        if (joined) bad = step_build_joined(call, c.js, k, offF.data(), sidv.data(), s.eqt, s.ldt, s.ht, st);
+        else {
+            win.clear();        // (an open stream: the slot's own next frame)
+            for (const int b : wb) win.push_back(StepWin{b, lenF[b], open ? open->slots[(size_t)c.live_slots[b]].f : k * Cf, offF[b], sidv[b]});
+            bad = step_build(call, win.data(), nu, s.eqt, s.ldt, s.ht, st);
         }
-        if (!stream_direct) HIPCK(hipMemcpyAsync(hp, src, (size_t)dsum * 2, hipMemcpyDeviceToHost, stream));
+        if (bad) return fail(STS_EDEVICE, bad);
+        const StepTab& t = st.tab;
+        const int nw = st.nw;
+        HIPCK(hipMemcpyAsync(c.d_win, s.ht, t.bytes, hipMemcpyHostToDevice, stream));
+        // one decode over the windows (none: no decoder kernel).  One utterance: its window by value (no table load in the decoder's
+        // kernels); several: the tables, also while one window is live (an open stream too: one form whatever the live count).
+        // run_decode runs the chain up to the gain plan on the windows at their absolute positions
+        if (nw > 0) {
+            const int rc = B == 1 && !open ? run_decode(c, 1, st.Wtot, st.maxW, st.zoff0, st.wlen0) : run_decode(c, nw, st.Wtot, st.maxW, 0, -1);
+            if (rc != STS_OK) return rc;
+        }
+        StreamTail tl{nw, c.stage_out(oc.src[OS_RESAMPLE]), SegView{c.d_win + StepTab::coff(nw), c.d_win + StepTab::wlen(nw), hop, 0, 0, 0},
+                      c.d_win + StepTab::pack_src(nw), c.d_win + StepTab::pack_dst(nw), t.rs, t.lim, t.eq_rows, t.loud_rows,
+                      st.max_rs, st.max_out, st.etiles, st.ltiles};
+        if (joined) {       // the windowed join, then the output side on the one utterance J
+            const JsStep& jt = st.jt;
+            JoinWinArgs j{};
+            j.x = c.stage_out(oc.src[OS_JOIN]); j.y = bf.wave_join; j.pcm = oc.writer == OS_JOIN ? s.dst : nullptr;
+            j.rows = (const long long*)(bf.stab + t.j_rows);
+            j.nw = nw; j.hop = hop; j.h = join_h;
+            j.g0 = jt.g0 * hop; j.g1 = jt.g1 * hop; j.k0 = jt.f0 * hop; j.k1 = jt.f1 * hop;
+            join_window_run(j, stream);
+            tl.n = 1; tl.x = bf.wave_join; tl.seg = SegView{nullptr, nullptr, hop, 0, 0, (int)(jt.g1 - jt.g0)};
+            tl.pack_src = tl.pack_dst = nullptr; tl.rs = t.j_rs; tl.lim = t.j_lim;
+        }
+        stream_tail(c, s, tl);
+        // where the step's chunks are on the device (nothing packed: the one window's kept samples, at its pack source in the decoder's own PCM)
+        const int16_t* src = oc.chunk_in_place ? bf.pcm + st.src0 : s.dst;
+        if (!stream_direct) HIPCK(hipMemcpyAsync(s.hp, src, (size_t)st.dsum * 2, hipMemcpyDeviceToHost, stream));
         HIPCK(hipStreamSynchronize(stream));
         // (an open stream: the hook counts its steps since open; an overflow repeats this step alone -- the earlier steps' chunks have left,
         // the stream stays in form 0 until it is closed, and stream_step restores the setting)
@@ -1786,35 +1646,105 @@ int Engine::run_stream_steps(RunCtx& c) {
             h2_fallbacks++;
             conv_math = 0;                                 // (run() restores the setting)
             k--;                                           // this step again, every window of it
-            eqt.drop();                                    // (from the state the first attempt started from)
-            if (sld) ldt.drop();
+            s.eqt.drop();                                  // (from the state the first attempt started from)
+            if (call.sld) s.ldt.drop();
             continue;
         }
-        eqt.commit();
-        if (sld) ldt.commit();
-        for (int i = 0; i < nw; i++) {                     // ascending utterance order
+        s.eqt.commit();
+        if (call.sld) s.ldt.commit();
+        for (int i = 0; i < nu; i++) {                     // ascending utterance order
             const int b = wb[i];
-            total_samples += wn[i];
-            if (ss->delivered) ss->delivered[b] += (int32_t)wn[i];
+            const int16_t* pcm = s.hp + st.dst[i];
+            const int32_t n = (int32_t)st.n[i], j0 = (int32_t)st.j0[i];
+            total_samples += st.n[i];
+            if (ss->delivered) ss->delivered[b] += n;
             if (open) {       // (utt = the slot; it moves on by a chunk, and retires behind its last one or at its stop)
-                const int s = c.live_slots[b];
-                open->delivered(s, ss->cb(ss->user, s, hp + wdst[i], (int32_t)wn[i], (int32_t)wj0[i]) != 0);
-            } else if (ss->cb(ss->user, b, hp + wdst[i], (int32_t)wn[i], (int32_t)wj0[i]) != 0) live[b] = 0;
+                const int sl = c.live_slots[b];
+                open->delivered(sl, ss->cb(ss->user, sl, pcm, n, j0) != 0);
+            } else if (ss->cb(ss->user, b, pcm, n, j0) != 0) live[b] = 0;
         }
     }
-    if (sld) {
-        // the gate, once, on what every utterance delivered: its results go to the host-mapped block, this synchronisation covers them
-        const int nu = joined ? 1 : B;
-        long long* hu = (long long*)ht;                     // (the step tables' pinned room: every upload from it has completed)
-        for (int b = 0; b < nu; b++) { hu[3 * b] = 0; hu[3 * b + 1] = ldt.e[b]; hu[3 * b + 2] = ldt.tbase[b]; }
-        HIPCK(hipMemcpyAsync(bf.ldres, hu, (size_t)nu * 3 * 8, hipMemcpyHostToDevice, stream));
-        LoudArgs g{};
-        g.k = loud_k_; g.target = loud_target; g.ceiling = loud_peak; g.no_clamp = oc.loud_no_clamp;
-        g.utab = (long long*)bf.ldres; g.tsum = ld_tsum; g.tpeak = ld_tpeak; g.gain = ld_gain; g.out = loud_dev_;
-        loud_gate_run(g, nu, stream);
-        HIPCK(hipStreamSynchronize(stream));
-        loud_res.assign((const sts_loudness*)loud_host_, (const sts_loudness*)loud_host_ + nu);
+    return call.sld ? stream_loud_gate(c, s) : STS_OK;
+}
+
+// the host side of a stream's steps: room for the step tables behind the geometry tables in the pinned block, and the chunks' buffer
+// behind that -- or, with posted writes, in mapped pinned memory of its own, which the last kernel of a step stores the chunks into itself
+int Engine::stream_host_buffers(RunCtx& c, StreamRun& s) {
+    RUN_ALIASES(c)
+    const size_t hp_off = (up_bytes + ((size_t)Ttot + B) * 4 + 255) & ~(size_t)255;
+    const size_t tab_room = (StepTab(B, c.gain, c.oc.eqst, c.oc.lst, c.join).bytes + 255) & ~(size_t)255;
+    const size_t pcm_bytes = (size_t)c.Ocap * 2 + 256;
+    if (!ensure_pinned(hp_off + tab_room + pcm_bytes)) return fail(STS_EDEVICE, "pinned host allocation failed");
+    c.pm = (int*)pinned_;
+    s.ht = pinned_ + hp_off;
+    s.hp = (int16_t*)(pinned_ + hp_off + tab_room);
+    s.dst = c.oc.run[OS_PACK] ? bf.spack : bf.pcm;
+    if (stream_direct) {
+        if (pcm_bytes > pinned_pcm_cap_ || !pinned_pcm_dev_) {
+            (void)hipStreamSynchronize(stream);
+            if (pinned_pcm_) (void)hipHostFree(pinned_pcm_);
+            pinned_pcm_ = nullptr; pinned_pcm_cap_ = 0; pinned_pcm_dev_ = nullptr;
+            if (hipHostMalloc((void**)&pinned_pcm_, pcm_bytes, hipHostMallocMapped) != hipSuccess) return fail(STS_EDEVICE, "pinned host allocation failed");
+            pinned_pcm_cap_ = pcm_bytes;
+            if (hipHostGetDevicePointer((void**)&pinned_pcm_dev_, pinned_pcm_, 0) != hipSuccess) { pinned_pcm_dev_ = nullptr; return fail(STS_EDEVICE, "mapped pinned buffer has no device address"); }
+        }
+        s.dst = pinned_pcm_dev_; s.hp = (int16_t*)pinned_pcm_;
     }
+    poison_host16(s.hp, (size_t)c.Ocap);
+    return STS_OK;
+}
+
+// a step's launches behind the decoder (a joined step: behind the windowed join): resample or pack, the EQ and loudness from their carried
+// states, the limiter -- every window in one launch each, the chain's writer storing the packed chunks
+void Engine::stream_tail(RunCtx& c, const StreamRun& s, const StreamTail& t) {
+    const OutChain& oc = c.oc;
+    const BufF& bf = c.bf;
+    if (oc.run[OS_RESAMPLE]) {
+        ResampleArgs a{};
+        a.x = t.x; a.seg = t.seg;
+        a.table = d_rs_table; a.P = rs.P; a.Q = rs.Q; a.K = rs.K;
+        a.pcm = oc.writer == OS_RESAMPLE ? s.dst : bf.pcm_rs; a.wave_out = bf.wave_out;
+        a.wtab = (const long long*)(bf.stab + t.rs);
+        resample_pcm(a, t.n, t.max_rs, stream);
+    } else if (oc.run[OS_PACK]) {
+        stream_pack(bf.pcm, s.dst, t.pack_src, t.pack_dst, t.n, t.max_out, stream);
+    }
+    if (oc.eqst) {          // its two launches follow the resampler
+        EqArgs a{};
+        a.x = c.stage_out(oc.src[OS_EQ]); a.S = c.eqS; a.tab = d_eq_;
+        a.y = bf.wave_eq; a.pcm = oc.writer == OS_EQ ? s.dst : nullptr;
+        a.E = bf.eqsE; a.state = bf.eqst; a.slot = s.eqt.slot; a.wtab = (const long long*)(bf.stab + t.eq);
+        eq_stream_run(a, t.n, t.etiles, stream);
+    }
+    if (oc.lst) {           // its two launches follow the stage it reads: the nearest running float stage in front of it
+        LoudStreamArgs a{};
+        a.x = c.stage_out(oc.src[OS_LOUD]); a.k = loud_k_;
+        a.wtab = (const long long*)(bf.stab + t.loud); a.state = bf.ldst; a.slot = s.ldt.slot;
+        a.E = bf.ldsE; a.tsum = s.ld_tsum; a.tpeak = s.ld_tpeak;
+        loud_stream_run(a, t.n, t.ltiles, stream);
+    }
+    if (oc.run[OS_LIMIT]) { // it writes the packed chunks in place of the resampler / the pack
+        LimArgs a{};
+        a.x = c.stage_out(oc.src[OS_LIMIT]);
+        a.H = c.limd.H; a.c = c.limd.c; a.G = c.limd.G;
+        a.pcm = s.dst;
+        a.wtab = (const long long*)(bf.stab + t.lim);
+        limiter_run(a, t.n, t.max_out, stream);
+    }
+}
+
+// the gate, once, on what every utterance delivered: its results go to the host-mapped block, this synchronisation covers them
+int Engine::stream_loud_gate(RunCtx& c, StreamRun& s) {
+    const int nu = c.join ? 1 : c.B;
+    long long* hu = (long long*)s.ht;                       // (the step tables' pinned room: every upload from it has completed)
+    for (int b = 0; b < nu; b++) { hu[3 * b] = 0; hu[3 * b + 1] = s.ldt.e[b]; hu[3 * b + 2] = s.ldt.tbase[b]; }
+    HIPCK(hipMemcpyAsync(c.bf.ldres, hu, (size_t)nu * 3 * 8, hipMemcpyHostToDevice, stream));
+    LoudArgs g{};
+    g.k = loud_k_; g.target = loud_target; g.ceiling = loud_peak; g.no_clamp = c.oc.loud_no_clamp;
+    g.utab = (long long*)c.bf.ldres; g.tsum = s.ld_tsum; g.tpeak = s.ld_tpeak; g.gain = s.ld_gain; g.out = loud_dev_;
+    loud_gate_run(g, nu, stream);
+    HIPCK(hipStreamSynchronize(stream));
+    loud_res.assign((const sts_loudness*)loud_host_, (const sts_loudness*)loud_host_ + nu);
     return STS_OK;
 }
 

@@ -55,6 +55,8 @@ struct StreamSpec {
 };
 int decoder_halo_frames(const Model& M);   // decoder.hip
 struct WinGeom;                             // the windows of one decode pass (decoder.hip)
+struct StreamRun;                           // what the steps of one streaming call share (engine.hip)
+struct StreamTail;                          // the windows the output side of a step sees (engine.hip)
 inline bool noise_scale_valid(float s) { return s >= 0.f && s <= 3.0e38f; }   // (false for NaN and +inf)
 // sts_set_loudness: mode 0, 1 or 2, target in [-70, 0] LUFS, ceiling in [-30, 0] dBFS (false for NaN)
 inline bool loudness_args_valid(int mode, float target, float peak) {
@@ -219,6 +221,9 @@ private:
     int frame_geometry(RunCtx& c);
     int run_output(RunCtx& c);
     int run_stream_steps(RunCtx& c);
+    int stream_host_buffers(RunCtx& c, StreamRun& s);                        // the pinned table room and the chunks' host buffer
+    void stream_tail(RunCtx& c, const StreamRun& s, const StreamTail& t);    // a step's launches behind the decoder (the join)
+    int stream_loud_gate(RunCtx& c, StreamRun& s);                           // a measuring stream's gate, once behind the last step
     int stream_admit_once(int B, const int32_t* const* ids, const int32_t* n, const int32_t* sid, const float* ls, int32_t* slot_out,
                           int32_t* n_samples_out, int32_t* admitted);
     int ensure_overflow_word();

@@ -407,8 +407,7 @@ struct ResampleArgs {
     const float* x; SegView seg;         // native float wave, windows in frames (scale = samples per frame)
     const float* table; int P, Q, K;
     int16_t* pcm; float* wave_out;       // outputs, packed utterance after utterance; wave_out optional (taps)
-    // streaming (wtab != null): window w reads {u0, L_utt, j0, j1, obase} from wtab[5 w ..]: it holds utterance samples [u0, u0 + len) of
-    // L_utt, and its outputs [j0, j1) go to pcm[obase ..) -- the windows' chunks packed back to back
+    // streaming (wtab != null): window w reads its row of the step's table (stream_step.hpp RsRow) -- the windows' chunks packed back to back
     const long long* wtab;
 };
 // grid: nwin windows x ceil(max_out / 1024) tiles; max_out = the most outputs one window emits
@@ -473,8 +472,7 @@ struct LimArgs {
     const float* gloud;                  // [B] loudness gain of each utterance (loud_gate_kernel's word), or null: 1
     float* y; int16_t* pcm;              // outputs packed like x, each optional (16-byte aligned)
     unsigned* stat;                      // [B][4] raw words {bits of g0, bits of 1.0f - bits of min s, bits of max |y|, limited} or null
-    // streaming: segment w reads {xbase, u0, xlen, N, j0, j1, dst} from wtab[7 w ..]: x[xbase .. xbase + xlen) holds samples [u0, u0 + xlen)
-    // of an utterance of N, and outputs [j0, j1) go to y / pcm[dst ..)
+    // streaming: segment w reads its row of the step's table (stream_step.hpp LimRow)
     const long long* wtab;
 };
 // one memset (stat) + one launch; max_out = the most outputs one utterance (segment) emits, or more
@@ -492,7 +490,7 @@ struct GainArgs {
     SegView wseg;                        // member i's place in x, in frames (off == null: one member {ioff, ilen}); its scale is not read: hop is
     int hop;                             // samples per frame
     // streaming (null otherwise: member i is the whole utterance i): member i belongs to utterance utt[i] and its first sample is sample
-    // wtab[5 i] of that utterance (the resampler's table of the step)
+    // u0 of row i of the resampler's table of the step (stream_step.hpp RsRow)
     const int* utt; const long long* wtab;
     SegView tseg;                        // utterance b's phonemes in cum / q
     const int* cum;                      // inclusive cumulative frame counts inside each utterance (the durations kernel's)

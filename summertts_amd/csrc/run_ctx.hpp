@@ -6,6 +6,7 @@
 #include "loud_stream.hpp"
 #include "out_chain.hpp"
 #include "join_stream.hpp"
+#include "stream_step.hpp"
 
 namespace sts {
 
@@ -36,7 +37,7 @@ struct BufF {
     float *ff_h[2], *ff_part[2], *ff_macc[2], *ff_alt;        // one-launch-per-layer flow (wn_flow.hip): channel-minor h / partial sums / -m slices, alternate home of a z half
     // the output chain (out_chain.hpp): a buffer exists iff a stage of this run reads or writes it, and is null otherwise.  pcm: the returned
     // PCM; pcm_nat / pcm_rs: the tail's / the resampler's int16 samples (pcm when that stage is the writer, else scratch); wave_*: the
-    // stages' float outputs (wave above: the tail's); lws / limws / eqws: stage workspaces; streaming: the step tables (stream_tab_bytes),
+    // stages' float outputs (wave above: the tail's); lws / limws / eqws: stage workspaces; streaming: the step tables (stream_step.hpp StepTab),
     // stream_pack's packed chunk buffer, the per-window speaker vectors and conditioning of a multi-speaker HiFi-GAN decoder
     // (members in the order they were added: the layout every earlier build measured with)
     int16_t* pcm;
@@ -53,35 +54,6 @@ struct BufF {
     // the call's result tables (lds_res_bytes)
     char* ldst; double* ldsE; char* ldres;
 };
-// Streaming, the tables of one step with nw windows (one upload, c.d_win points at them): ints [zoff nw | coff nw | wlen nw | sid nw |
-// pack source nw | packed destination nw + 1], then from an 8-byte boundary the resampler's long long [nw][5] = {u0, L_utt, j0, j1, obase}
-static inline size_t stream_tab_ll_off(int nw) { return ((size_t)(6 * nw + 1) * 4 + 7) & ~(size_t)7; }
-// and behind them the limiter's segments, long long [nw][7] = {xbase, u0, xlen, N, j0, j1, dst} (LimArgs::wtab)
-static inline size_t stream_tab_lim_off(int nw) { return stream_tab_ll_off(nw) + (size_t)nw * 5 * 8; }
-// a run with a gain plan: behind those, each window's utterance as ints [nw] (GainArgs::utt)
-static inline size_t stream_tab_utt_off(int nw) { return stream_tab_lim_off(nw) + (size_t)nw * 7 * 8; }
-// a stream that runs the EQ: from the next 8-byte boundary its rows, long long [nw][12] (eq_stream.hpp EqsRow)
-static inline size_t stream_tab_eq_off(int nw, bool gain) { return (stream_tab_utt_off(nw) + (gain ? (size_t)nw * 4 : 0) + 7) & ~(size_t)7; }
-static inline size_t stream_tab_bytes(int nw, bool gain = false, bool eq = false) {
-    return eq ? stream_tab_eq_off(nw, gain) + (size_t)nw * kEqsRow * 8 : stream_tab_utt_off(nw) + (gain ? (size_t)nw * 4 : 0);
-}
-// a stream that measures loudness: behind all of that, from the next 8-byte boundary, its rows, long long [nw][8] (loud_stream.hpp LdsRow)
-static inline size_t stream_tab_loud_off(int nw, bool gain, bool eq) { return (stream_tab_bytes(nw, gain, eq) + 7) & ~(size_t)7; }
-static inline size_t stream_tab_bytes(int nw, bool gain, bool eq, bool loud) {
-    return loud ? stream_tab_loud_off(nw, gain, eq) + (size_t)nw * kLdsRow * 8 : stream_tab_bytes(nw, gain, eq);
-}
-// a joined stream: the same tables for the step's nw decode windows, and from the next 8-byte boundary the ONE window of J for the
-// resampler (long long [5]) and the limiter (long long [7]), then the windowed join's rows, long long [nw][5] (join_stream.hpp JsRow)
-static inline size_t join_stream_tab_j_off(int nw, bool gain) { return (stream_tab_bytes(nw, gain) + 7) & ~(size_t)7; }
-// (a joined stream that runs the EQ: behind the rows the one EqsRow of J)
-static inline size_t join_stream_tab_eq_off(int nw, bool gain) { return join_stream_tab_j_off(nw, gain) + (size_t)(12 + 5 * (size_t)nw) * 8; }
-static inline size_t join_stream_tab_bytes(int nw, bool gain, bool eq = false) { return join_stream_tab_eq_off(nw, gain) + (eq ? (size_t)kEqsRow * 8 : 0); }
-// (a joined stream that measures loudness: behind that the one LdsRow of J)
-static inline size_t join_stream_tab_loud_off(int nw, bool gain, bool eq) { return join_stream_tab_bytes(nw, gain, eq); }
-static inline size_t join_stream_tab_bytes(int nw, bool gain, bool eq, bool loud) {
-    return join_stream_tab_bytes(nw, gain, eq) + (loud ? (size_t)kLdsRow * 8 : 0);
-}
-
 // Everything a run's stages share: batch geometry, workspace pointers, host / device tables.  Engine::run() fills it stage by
 // stage; the stage functions below see its fields under the names the pipeline has always used (RUN_ALIASES).
 struct Engine::RunCtx {

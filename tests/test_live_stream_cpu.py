@@ -101,7 +101,14 @@ def test_the_engine_keeps_its_pinned_layout():
     opened = eng[eng.index("int Engine::stream_open("):eng.index("int Engine::stream_close(")]
     assert "hipMalloc((void**)&L->zpool" in opened and "arenaF_" not in opened
     step = eng[eng.index("int Engine::stream_step("):]
-    assert "run_stream_steps(c)" in step and eng.count("stream_window(") == 1 and "stream_window(" in eng[eng.index("int Engine::run_stream_steps("):]
+    assert "run_stream_steps(c)" in step
+    # (the one call of the window definition: the plain builder of stream_step.hpp, which run_stream_steps calls for both)
+    dec, tab = (open(os.path.join(CSRC, f)).read() for f in ("decoder.hip", "stream_step.hpp"))
+    assert (eng + dec + tab).count("stream_window(") == 1
+    plain = tab[tab.index("static inline const char* step_build("):tab.index("static inline const char* step_build_joined(")]
+    assert "stream_window(" in plain
+    loop = eng[eng.index("int Engine::run_stream_steps("):]
+    assert "step_build(call," in loop and "step_build_joined(call," in loop
 
 
 def test_slot_table_allocator_and_windows_under_the_sanitizers(tmp_path):
