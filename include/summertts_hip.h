@@ -673,6 +673,13 @@ enum { STS_DBG_STREAM_RETRY_STEP = 16, STS_DBG_STREAM_DIRECT = 17 };
  * writes them is enqueued.  No result may depend on what the arenas held before: a poisoned call returns what an unpoisoned engine returns, bit for bit.
  * sts_profile.poison_bytes reports the bytes the last call filled. */
 enum { STS_DBG_POISON = 18 };
+/* STS_DBG_COL_PROJ (tests, A/B; no ABI change) -- the text encoder's q/k/v projection and the producer of its input (the embedding, or the
+ * previous layer's second LayerNorm): 1 (default) one launch, with all three passes in one workgroup per 16 phonemes from 24 such column
+ * blocks on and one workgroup per (column block, pass) below; 0 the producer and the conv as two launches at any size; 2 / 3 one launch at
+ * any size with the passes in one workgroup / one workgroup per pass -- 1, 2 and 3 return the same bits.
+ * STS_DBG_SDP_PRE_RIDE (tests, A/B) -- the stochastic duration predictor's `pre` conv (1x1, hidden -> hidden) of a single-speaker model:
+ * 1 (default) one more workgroup per column block in the launch of the encoder's output projection, 0 a conv launch of its own. */
+enum { STS_DBG_COL_PROJ = 19, STS_DBG_SDP_PRE_RIDE = 20 };
 int sts_debug_set(sts_engine* e, int key, int value);
 
 /* Per-stage device timing of the last run, measured with HIP events on the engine's own stream. */

@@ -774,6 +774,8 @@ int sts_debug_set(sts_engine* e, int key, int value) {
         case STS_DBG_STREAM_RETRY_STEP: e->eng.stream_retry_step = value < 0 ? -1 : value; return STS_OK;
         case STS_DBG_STREAM_DIRECT: e->eng.stream_direct = value != 0; return STS_OK;
         case STS_DBG_POISON: e->eng.poison = (unsigned)value; return STS_OK;
+        case STS_DBG_COL_PROJ: if (value < 0 || value > 3) return set_err(STS_EINVAL, "col_proj must be 0, 1, 2 or 3"); e->eng.col_proj_mode = value; return STS_OK;
+        case STS_DBG_SDP_PRE_RIDE: e->eng.sdp_pre_ride = value != 0; return STS_OK;
         default: return set_err(STS_EINVAL, "unknown debug key");
     }
 }

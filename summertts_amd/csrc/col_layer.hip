@@ -221,10 +221,14 @@ __global__ __launch_bounds__(64 * NSUB) void col_layer_kernel(ColLayerArgs a) {
 // The producer of a text-encoder layer's input and the first conv that consumes it in one launch: the input stage forms
 // x (written out: it is the residual of the layer's post-LayerNorm) and stages it in LDS; the conv then runs NPASS passes
 // of C rows each over the same staged block, the next pass's A strip in flight under the current pass's MFMA chain.
+// SPLIT (ColProjArgs::split): grid z = npass (+ 1 with a rider); every (column block, pass) pair is a workgroup of its own, which repeats
+// the input stage and runs ONE pass -- one A strip in registers, no second strip.  With a handful of column blocks (one utterance) this
+// spreads the three strips of a q/k/v projection over three times as many CUs; per pass the arithmetic is the one below, unchanged, so the
+// two forms return the same bits.  Workgroup z = 0 alone writes x_out; a rider (wc2) is one more single-pass conv over the same x.
 //   /root/reference/src/modules/attention_encoder.cpp:84-93 (x = LN(x1 + FFN(x1)) -> next layer's q/k/v convs),
 //   /root/reference/src/models/TextEncoder.cpp:54-66 (embedding * sqrt(H)) and :68-70 (proj)
 // ------------------------------------------------------------------------------------------------
-template <int NSUB>
+template <int NSUB, bool SPLIT = false>
 __global__ __launch_bounds__(64 * NSUB) void col_proj_kernel(ColProjArgs a) {
     constexpr int C = 16 * NSUB, KQ = C / 4, CG = 4 * NSUB;
     __shared__ float ys[C * 16];
@@ -239,8 +243,14 @@ __global__ __launch_bounds__(64 * NSUB) void col_proj_kernel(ColProjArgs a) {
     const int pos = n0 + col;
     const bool live = pos < len;
     const int cg = tid >> 4;
+    // the conv this workgroup runs: every pass of (wc, bias, y), or (SPLIT) pass blockIdx.z of it / the rider behind the last pass
+    const float* wsel = a.wc; const float* bsel = a.bias; float* ysel = a.y; long yld = a.y_ld; int cout = a.Cout, pass0 = 0;
+    if constexpr (SPLIT) {
+        pass0 = blockIdx.z;
+        if (pass0 >= a.npass) { wsel = a.wc2; bsel = a.bias2; ysel = a.y2; yld = a.y2_ld; cout = a.Cout2; pass0 = 0; }
+    }
 
-    // ---- input-stage operands first, then pass 0's A strip
+    // ---- input-stage operands first, then the first pass's A strip
     float v[4], g[4], be[4];
     if (a.ids) {                                 // embedding lookup (TextEncoder.cpp:54-63; emb_(v, e) = ptr[e * vocab + v])
         int id = live ? a.ids[base + pos] : 0;
@@ -262,13 +272,13 @@ __global__ __launch_bounds__(64 * NSUB) void col_proj_kernel(ColProjArgs a) {
             v[i] = x0 + bs;
         }
     }
-    f32x4 afa[KQ / 4], afb[KQ / 4];
+    f32x4 afa[KQ / 4];
     auto load_strip = [&](int pass, f32x4 (&dst)[KQ / 4]) {
-        const f32x4* wp = reinterpret_cast<const f32x4*>(a.wc) + ((size_t)pass * NSUB + wave) * (KQ / 4) * 64 + lane;
+        const f32x4* wp = reinterpret_cast<const f32x4*>(wsel) + ((size_t)pass * NSUB + wave) * (KQ / 4) * 64 + lane;
 #pragma unroll
         for (int i = 0; i < KQ / 4; i++) dst[i] = wp[(size_t)i * 64];
     };
-    load_strip(0, afa);
+    load_strip(pass0, afa);
 
     // ---- input stage
     if (!a.ids) {
@@ -292,7 +302,7 @@ __global__ __launch_bounds__(64 * NSUB) void col_proj_kernel(ColProjArgs a) {
     for (int i = 0; i < 4; i++) {
         const int c = cg + i * CG;
         ys[c * 16 + col] = live ? v[i] : 0.f;
-        if (live) a.x_out[(size_t)c * a.x_ld + base + pos] = v[i];
+        if (live && (!SPLIT || blockIdx.z == 0)) a.x_out[(size_t)c * a.x_ld + base + pos] = v[i];
     }
     __syncthreads();
 
@@ -312,16 +322,21 @@ __global__ __launch_bounds__(64 * NSUB) void col_proj_kernel(ColProjArgs a) {
 #pragma unroll
             for (int r = 0; r < 4; r++) {
                 const int row = pass * C + rloc + r;
-                if (row < a.Cout) a.y[(size_t)row * a.y_ld + base + pos] = (acc0[r] + acc1[r]) + (a.bias ? a.bias[row] : 0.f);
+                if (row < cout) ysel[(size_t)row * yld + base + pos] = (acc0[r] + acc1[r]) + (bsel ? bsel[row] : 0.f);
             }
         }
     };
-    for (int pass = 0; pass < a.npass; pass += 2) {          // two strips ping-pong: the next pass's weights are in flight
-        if (pass + 1 < a.npass) load_strip(pass + 1, afb);
-        run_pass(pass, afa);
-        if (pass + 1 < a.npass) {
-            if (pass + 2 < a.npass) load_strip(pass + 2, afa);
-            run_pass(pass + 1, afb);
+    if constexpr (SPLIT) {
+        run_pass(pass0, afa);
+    } else {
+        f32x4 afb[KQ / 4];
+        for (int pass = 0; pass < a.npass; pass += 2) {      // two strips ping-pong: the next pass's weights are in flight
+            if (pass + 1 < a.npass) load_strip(pass + 1, afb);
+            run_pass(pass, afa);
+            if (pass + 1 < a.npass) {
+                if (pass + 2 < a.npass) load_strip(pass + 2, afa);
+                run_pass(pass + 1, afb);
+            }
         }
     }
 }
@@ -331,10 +346,20 @@ bool col_proj_eligible(const ColProjArgs& a) {
     if (!a.wc || !a.y || !a.x_out || a.npass < 1 || a.npass > 4 || a.Cout > a.npass * a.C || a.Cout <= (a.npass - 1) * a.C) return false;
     if (a.ids) { if (!a.emb || a.vocab <= 0) return false; }
     else if (!a.a || !a.gamma || !a.beta || a.nb < 0 || a.nb > 8 || (a.nb > 0 && !a.bp)) return false;
+    if (a.wc2 && (!a.split || !a.y2 || a.Cout2 < 1 || a.Cout2 > a.C)) return false;     // a rider is a workgroup of the split form
     return a.max_len > 0 && a.B > 0;
 }
 
 void col_proj(const ColProjArgs& a, hipStream_t st) {
+    if (a.split) {
+        const dim3 grid((a.max_len + 15) / 16, a.B, a.npass + (a.wc2 ? 1 : 0));
+        switch (a.C) {
+            case 32: hipLaunchKernelGGL((col_proj_kernel<2, true>), grid, dim3(128), 0, st, a); break;
+            case 64: hipLaunchKernelGGL((col_proj_kernel<4, true>), grid, dim3(256), 0, st, a); break;
+            default: hipLaunchKernelGGL((col_proj_kernel<12, true>), grid, dim3(768), 0, st, a); break;
+        }
+        return;
+    }
     const dim3 grid((a.max_len + 15) / 16, a.B);
     switch (a.C) {
         case 32: hipLaunchKernelGGL((col_proj_kernel<2>), grid, dim3(128), 0, st, a); break;

@@ -686,9 +686,12 @@ int Engine::run_text_encoder(RunCtx& c) {
     // Measured (profiles/r02 notes in docs/HISTORY.md 5b): with a handful of column blocks (one 128-phoneme utterance = 8) a
     // three-pass q/k/v projection makes each of the few workgroups pull 3 x 147 KB of weights through one CU and loses to
     // the separate LayerNorm + chip-wide conv (23 vs 18 us); from a few dozen blocks on it wins (batch 8: -12 us per layer).
-    // A single-pass conv (the encoder's output projection) wins at every size.
+    // A single-pass conv (the encoder's output projection) wins at every size -- so below 24 blocks every pass gets a workgroup of
+    // its own (ColProjArgs::split): 10.3 us against 8.9 + 7.6 us for the LayerNorm and the conv (profiles/colp_split_ab_log.md).
     const long colp_blocks = (long)((Ttot + 15) / 16);
     const bool colp_grid = (long)((maxT + 15) / 16) * B <= 512;
+    bool& dh_in_enc = c.dh_in_enc;
+    dh_in_enc = false;
     auto produce_x_and_conv = [&](int l, const DConv& c, float* y) {
         // l = index of the layer whose input is produced (l == n_layers: the encoder's output projection)
         ColProjArgs pj;
@@ -698,11 +701,27 @@ int Engine::run_text_encoder(RunCtx& c) {
         if (l == 0) { pj.ids = bt.ids; pj.emb = M.emb; pj.vocab = M.vocab; pj.emb_scale = sqrtf((float)M.hidden); }
         else { pj.a = bt.x1; pj.a_ld = Ttot; pj.bp = bt.y; pj.b_ld = Ttot; pj.nb = ffn2_slices; pj.b_stride = (long)H * Ttot;
                pj.gamma = M.ln2[l - 1].g; pj.beta = M.ln2[l - 1].b; }
-        const bool ok = !no_colp && conv_mode != 1 && colp_grid && (pj.npass == 1 || colp_blocks >= 24) && c.k == 1 && c.Cin == H && M.emb_size == H && c.wc &&
+        // several passes: all in one workgroup from 24 column blocks on (the measured win at batch); below, one workgroup per (column
+        // block, pass) -- 24 workgroups of one pass each at 128 phonemes, the shape of the output projection's launch (STS_DBG_COL_PROJ)
+        const bool one_launch = pj.npass == 1 || col_proj_mode != 0;
+        pj.split = pj.npass > 1 && (col_proj_mode == 3 || (col_proj_mode == 1 && colp_blocks < 24));
+        // the stochastic duration predictor's `pre` conv reads the encoder's output x: it rides in the output projection's launch as one
+        // more workgroup per column block (single speaker: no per-utterance bias; hidden -> hidden: the staged block is its whole input)
+        const DConv& sp = M.sdp_pre;
+        const bool ride = l == M.n_layers && sdp_pre_ride && M.dur_type == 0 && !ms && sp.k == 1 && sp.Cin == H && sp.Cout == H && sp.wc;
+        if (ride) { pj.split = 1; pj.wc2 = sp.wc; pj.bias2 = sp.bias_rows; pj.y2 = bt.dh; pj.y2_ld = Ttot; pj.Cout2 = sp.Cout; }
+        const bool ok = !no_colp && conv_mode != 1 && colp_grid && one_launch && c.k == 1 && c.Cin == H && M.emb_size == H && c.wc &&
                         (l == 0 || M.ln2[l - 1].C == H) && col_proj_eligible(pj);
         if (ok) {
+            const int zs = pj.split ? pj.npass + (ride ? 1 : 0) : 1;      // workgroups per column block: each reads the input stage's operands
             flops_[0] += 2.0 * c.macs_per_out * (double)Ttot;
-            bytes_[0] += 4.0 * ((double)H * Ttot * (l == 0 ? 1.0 : 2.0 + ffn2_slices) + (double)c.Cout * Ttot + (double)H * c.Cout);
+            bytes_[0] += 4.0 * ((double)H * Ttot * (1.0 + zs * (l == 0 ? 0.0 : 1.0 + ffn2_slices)) + (double)c.Cout * Ttot + (double)H * c.Cout);
+            if (ride) {       // (booked to the duration stage, as the separate conv is)
+                flops_[1] += 2.0 * sp.macs_per_out * (double)Ttot;
+                bytes_[1] += 4.0 * ((double)sp.Cin * Ttot + (double)sp.Cout * Ttot);
+                bytes_w_[1] += 4.0 * (double)sp.Cin * sp.Cout;
+                dh_in_enc = true;
+            }
             col_proj(pj, stream);
             return;
         }
@@ -775,7 +794,7 @@ int Engine::run_durations(RunCtx& c) {
     if (M.dur_type == 0) {   // /root/reference/src/models/StochasticDurationPredictor.cpp:117-149
         ConvOpt op;
         if (ms) { conv(M.sdp_cond, bt.g, lvB, bt.cond_dp, lvB, ConvOpt()); op.ubias = bt.cond_dp; }
-        conv(M.sdp_pre, bt.x, lvT, bt.dh, lvT, op);
+        if (!c.dh_in_enc) conv(M.sdp_pre, bt.x, lvT, bt.dh, lvT, op);      // (else: written by the launch of the encoder's output projection)
         const float* dh = dds(M.sdp_dds, bt.dh, bt.dt1, bt.dt2, lvT);
         conv(M.sdp_proj, dh, lvT, bt.dc, lvT, ConvOpt());
         // the latent z (StochasticDurationPredictor.cpp:129-131): rand_gen(2, T) * noise_scale_w, flipped.  Without noise it is all

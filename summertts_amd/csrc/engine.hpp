@@ -184,6 +184,11 @@ public:
     int flow_fused = 1;                // 1: the reverse flow as one launch per WaveNet layer where eligible (wn_flow.hip; two-term fp16 arithmetic only),
                                        // 16-frame tiles where 32-frame tiles would leave half the CUs without a workgroup; 0: one launch per conv;
                                        // 2 / 3: one launch per layer at any size, 32- / 16-frame tiles (sts_debug_set STS_DBG_FLOW_FUSED)
+    int col_proj_mode = 1;                  // text encoder, the q/k/v projection and the producer of its input (col_layer.hip col_proj_kernel): 1 one launch -- all
+                                       // passes in one workgroup from 24 column blocks on, one workgroup per (column block, pass) below; 0: the producer and
+                                       // the conv as two launches; 2 / 3: one launch at any size, passes in one workgroup / split (sts_debug_set STS_DBG_COL_PROJ)
+    int sdp_pre_ride = 1;              // 1: the stochastic duration predictor's `pre` conv as one more workgroup per column block of the encoder's output
+                                       // projection launch where eligible, 0: a conv launch of its own (sts_debug_set STS_DBG_SDP_PRE_RIDE)
     int n_cus = 0;                     // compute units of the device (init)
     int stream_retry_step = -1;        // tests (STS_DBG_STREAM_RETRY_STEP): a stream (of one utterance or several) under conv_math 3 treats the overflow word as raised after step k
     int stream_direct = 0;             // streaming, any B: 1 the pack / resample / limiter kernel writes each step's chunks into mapped pinned host memory, 0 one download (STS_DBG_STREAM_DIRECT)

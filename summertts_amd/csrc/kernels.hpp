@@ -149,6 +149,12 @@ struct ColProjArgs {
     float* y; long y_ld;
     int C;
     SegView seg; int B, max_len;
+    // split != 0: grid z = npass (+ 1 with a rider); workgroup z forms x for its 16 columns itself and runs pass z ONLY (one A strip, one
+    // MFMA chain); z = 0 alone writes x_out.  The same sums in the same order as split == 0, where one workgroup runs every pass.
+    int split;
+    // optional rider of the split form (wc2 != null): one more single-pass 1x1 conv over the same staged x, with its own weights
+    // (col_proj_pack order), bias and output, Cout2 <= C rows; it is workgroup z = npass
+    const float* wc2; const float* bias2; float* y2; long y2_ld; int Cout2;
 };
 bool col_proj_eligible(const ColProjArgs& a);
 void col_proj(const ColProjArgs& a, hipStream_t st);

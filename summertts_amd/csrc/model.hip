@@ -635,7 +635,7 @@ bool load_model(const float* blob, int64_t nfloats, Model& m) {
         for (int i = 0; i < m.sdp_flows; i++) if (!parse_pack_convflow(r, st, m.cf[i])) FAIL("sdp ConvFlow");
         parse_conv(r); parse_conv(r); skip_dds(r); r.take(4);   // posterior side: loaded by the reference, never run
         for (int i = 0; i < 4; i++) skip_convflow(r);
-        { HConv h = parse_conv(r); if (!r.ok || h.k != 1 || !pack_conv(st, h, PackOpts(), m.sdp_pre)) FAIL("sdp pre"); }
+        { HConv h = parse_conv(r); if (!r.ok || h.k != 1 || !pack_conv(st, h, PackOpts(), m.sdp_pre) || !pack_col(st, h, m.sdp_pre)) FAIL("sdp pre"); }   // (col copy: the conv can ride in the encoder's last launch)
         { HConv h = parse_conv(r); if (!r.ok || h.k != 1 || !pack_conv(st, h, PackOpts(), m.sdp_proj)) FAIL("sdp proj"); }
         if (!parse_pack_dds(r, st, m.sdp_dds)) FAIL("sdp dds");
         if (m.is_ms == 1) { HConv h = parse_conv(r); if (!r.ok || !pack_conv(st, h, PackOpts(), m.sdp_cond)) FAIL("sdp cond"); }

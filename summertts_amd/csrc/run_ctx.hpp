@@ -67,6 +67,7 @@ struct Engine::RunCtx {
     int *pm = nullptr, *p_offT = nullptr, *p_lenT = nullptr, *p_sid = nullptr, *p_offF = nullptr, *p_lenF = nullptr, *p_one = nullptr;
     int *d_offT = nullptr, *d_lenT = nullptr, *d_sid = nullptr, *d_offF = nullptr, *d_lenF = nullptr, *d_one = nullptr, *d_win = nullptr;
     bool inl = false, no_inline_seg = false, ms = false;
+    bool dh_in_enc = false;         // the stochastic duration predictor's `pre` conv ran inside the text encoder's last launch (bt.dh is written)
     long Ftot = 0; int maxF = 0, hop = 0;
     // One utterance (the reference's own call shape): buffers, leading dimensions and every dispatch decision use the frame CAPACITY
     // Fld = the count rounded up to a bucket of 64 frames, so that a call which launches the flow and the decoder AHEAD of the frame count
