@@ -536,6 +536,52 @@ int sts_infer_ids_joined_stream(sts_engine* e, int32_t B, const int32_t* const* 
  * table the engine's step builds.  On the device both outputs start out as a NaN / 0x7FFF pattern, as in sts_join_apply. */
 int sts_join_apply_range(int device, const float* x, const int32_t* frames, int32_t B, int32_t samples_per_frame, const sts_join* join,
                          int64_t first_frame, int64_t n_frames, float* y, int16_t* pcm);
+/* Open paragraphs: a joined stream whose sentences are appended while it plays (a service that voices a language model's output gets its
+ * text sentence by sentence).  One per engine; nothing here is on by default.  Every delivered chunk is a chunk of the ONE joined signal
+ * J that sts_infer_ids_joined_stream would deliver for the finished paragraph: the same chunk grid, the same faded edges, one limiter,
+ * resampler taps that reach across the joins, offsets on one time axis.
+ *   sts_para_open fixes C = chunk_frames, the output rate, the limiter setting, the conv mode and the conv math, and the join's
+ *   lead_frames and fade_ms (sts_join_check's rules), and allocates a latent pool of capacity_frames frames for at most max_resident
+ *   sentences at a time, under sts_stream_open's bounds.  STS_ESTATE while an open stream or an open paragraph exists (and while a
+ *   paragraph is open sts_stream_open answers STS_ESTATE too); STS_EINVAL under the conditions that make sts_stream_open refuse.
+ *   sts_para_append runs text encoder, duration predictor and flow of the B new sentences as the packed batch a joined call of those B
+ *   would, and moves their latents into the pool.  gap_frames[b] (NULL = zeros, each in [0, 100000]) is the silence between the sentence
+ *   before and sentence b; for the paragraph's first sentence it must be 0 (the lead was given at open).  The layout is sts_join_layout's,
+ *   continued: the sentence with global index i starts at start_i = start_{i-1} + N_{i-1} + gap hop and has F_i = max(1, sum d) frames.
+ *   frames_out[b] = its frames, start_out[b] = its start in output samples, ceil(start P / Q) (sts_get_join_offsets' rule); both may be
+ *   NULL, as may sid and length_scale (0 and 1.0).  Sampling noise: global sentence i uses seed + i, the setting read at every append.
+ *   All or nothing: *appended = B, or 0 when slots or frames do not suffice now (nothing has changed; retry after steps have retired
+ *   sentences) or the paragraph was stopped.  STS_EINVAL: an append that would carry N_J past 2 10^9 native samples or L_out past
+ *   2^31 - 1, B > max_resident, bad arguments, an append after finish.
+ *   sts_para_finish: no more sentences will come; F_J = the end of the last sentence + trail_frames.  STS_EINVAL with no sentence
+ *   appended, twice, or with trail_frames outside [0, 100000].
+ *   sts_para_step is ONE step: the next chunk of J, if it is deliverable, decoded as the closed joined stream's step decodes it and handed
+ *   to `cb` before the call returns.  With Ho = the resampler's and limiter's reach in frames (sts_stream_halo_frames minus the decoder's
+ *   own halo) and E = the end of the last sentence appended so far, chunk k = frames [k C, (k + 1) C) is deliverable before finish iff
+ *   (k + 1) C + Ho <= E; after finish every remaining chunk is, the short last one included.  So a stalled writer costs at most C + Ho
+ *   frames of withheld audio behind the last sentence.  *ready_after (may be NULL) = chunks deliverable now without a further append.
+ *   With nothing deliverable it launches nothing and delivers nothing.  A silent chunk (lead, a known gap) leaves without a decode.  A
+ *   non-zero callback return stops the paragraph: later steps and appends do nothing, only sts_para_info and sts_para_close remain useful.
+ *   A sentence's slot and frames become free once no later step reads it: when the next undelivered chunk k has
+ *   k C - halo >= start frame + F_i (halo = sts_stream_halo_frames).
+ *   sts_para_info: any output may be NULL; *steps = chunks delivered.  sts_para_close frees the pool and drops what was not delivered;
+ *   sts_destroy closes an open paragraph.  No entry of an open paragraph may be called from a chunk callback.
+ *   While a paragraph is open every other run entry of the engine and every setter of what open fixed returns STS_ESTATE, as while a
+ *   stream is open; sts_set_noise stays allowed.
+ *   Equality: whatever the schedule of appends and steps, the list of chunks (count, sample offsets, sizes, samples) equals
+ *   sts_infer_ids_joined_stream's for the same sentences, gaps, lead, trail and fade bit for bit when the kernel variant is pinned
+ *   (sts_set_conv_mode), and the PCM is within 1 LSB of sts_infer_ids_joined's under the automatic choice.
+ *   Conv math 3: an activation beyond fp16's range during an append repeats that append alone in form 0; raised in a step, that step is
+ *   decoded again in form 0 and the paragraph stays there until it is closed.  No chunk leaves twice.  STS_DBG_STREAM_RETRY_STEP = k names
+ *   the step that delivers chunk k. */
+int sts_para_open(sts_engine* e, int32_t chunk_frames, int32_t max_resident, int64_t capacity_frames, int32_t lead_frames, float fade_ms);
+int sts_para_append(sts_engine* e, int32_t B, const int32_t* const* ids, const int32_t* n, const int32_t* sid, const float* length_scale,
+                    const int32_t* gap_frames, int32_t* frames_out, int64_t* start_out, int32_t* appended);
+int sts_para_finish(sts_engine* e, int32_t trail_frames);
+int sts_para_step(sts_engine* e, sts_chunk_cb cb, void* user, int32_t* ready_after);
+int sts_para_info(const sts_engine* e, int32_t* open, int32_t* finished, int64_t* sentences, int32_t* resident, int32_t* free_slots,
+                  int64_t* free_frames, int64_t* frames_known, int64_t* frames_delivered, int64_t* steps);
+int sts_para_close(sts_engine* e);
 /* ---- parametric equaliser (no reference counterpart; ABI number unchanged).  sts_set_eq(e, n_bands, bands) puts a tone stage of 0 to
  * STS_EQ_MAX_BANDS biquad sections in front of loudness and the limiter: an "audio profile" (telephone band, rumble and DC removal, a
  * presence lift) that loudness mode 2 and the limiter then measure and limit as played.  n_bands = 0 (default) switches the stage off:

@@ -12,6 +12,7 @@
 #include "eq_stream.hpp"
 #include "join_stream.hpp"
 #include "loud_stream.hpp"
+#include "para_stream.hpp"
 
 using namespace sts;
 
@@ -21,7 +22,7 @@ static thread_local std::string g_err;
 static int set_err(int code, const std::string& s) { g_err = s; return code; }
 // the setters that write an engine member themselves: what an open stream fixed stays fixed until sts_stream_close (engine.hpp stream_open)
 #define STS_CAPI_NOT_WHILE_OPEN(e) \
-    do { if ((e)->eng.stream_is_open()) return set_err(STS_ESTATE, "a stream is open on this engine (sts_stream_close first)"); } while (0)
+    do { if ((e)->eng.stream_is_open()) return set_err(STS_ESTATE, "a stream or a paragraph is open on this engine (sts_stream_close / sts_para_close first)"); } while (0)
 
 extern "C" {
 
@@ -183,6 +184,53 @@ int sts_stream_info(const sts_engine* e, int32_t* open, int32_t* live, int32_t* 
 int sts_stream_close(sts_engine* e) {
     if (!e) return set_err(STS_EINVAL, "null engine");
     const int rc = e->eng.stream_close();
+    return rc == STS_OK ? STS_OK : set_err(rc, e->eng.error());
+}
+
+// ---- open paragraphs (engine.hpp para_open; para_stream.hpp)
+int sts_para_open(sts_engine* e, int32_t chunk_frames, int32_t max_resident, int64_t capacity_frames, int32_t lead_frames, float fade_ms) {
+    if (!e) return set_err(STS_EINVAL, "null engine");
+    const int rc = e->eng.para_open(chunk_frames, max_resident, capacity_frames, lead_frames, fade_ms);
+    return rc == STS_OK ? STS_OK : set_err(rc, e->eng.error());
+}
+int sts_para_append(sts_engine* e, int32_t B, const int32_t* const* ids, const int32_t* n, const int32_t* sid, const float* length_scale,
+                    const int32_t* gap_frames, int32_t* frames_out, int64_t* start_out, int32_t* appended) {
+    if (!e) return set_err(STS_EINVAL, "null engine");
+    const int rc = e->eng.para_append(B, ids, n, sid, length_scale, gap_frames, frames_out, start_out, appended);
+    return rc == STS_OK ? STS_OK : set_err(rc, e->eng.error());
+}
+int sts_para_finish(sts_engine* e, int32_t trail_frames) {
+    if (!e) return set_err(STS_EINVAL, "null engine");
+    const int rc = e->eng.para_finish(trail_frames);
+    return rc == STS_OK ? STS_OK : set_err(rc, e->eng.error());
+}
+int sts_para_step(sts_engine* e, sts_chunk_cb cb, void* user, int32_t* ready_after) {
+    if (!e) return set_err(STS_EINVAL, "null engine");
+    if (!cb) return set_err(STS_EINVAL, "a step takes a callback");
+    struct { sts_chunk_cb cb; void* user; } one{cb, user};      // the engine's callback names the utterance; a paragraph is a single one
+    using One = decltype(one);
+    const int rc = e->eng.para_step([](void* u, int32_t, const int16_t* pcm, int32_t ns, int32_t off) { return ((One*)u)->cb(((One*)u)->user, pcm, ns, off); },
+                                    &one, ready_after);
+    return rc == STS_OK ? STS_OK : set_err(rc, e->eng.error());
+}
+int sts_para_info(const sts_engine* e, int32_t* open, int32_t* finished, int64_t* sentences, int32_t* resident, int32_t* free_slots,
+                  int64_t* free_frames, int64_t* frames_known, int64_t* frames_delivered, int64_t* steps) {
+    if (!e) return set_err(STS_EINVAL, "null engine");
+    const ParaStream* P = e->eng.para_;
+    if (open) *open = P ? 1 : 0;
+    if (finished) *finished = P && P->finished ? 1 : 0;
+    if (sentences) *sentences = P ? P->sentences() : 0;
+    if (resident) *resident = P ? P->resident() : 0;
+    if (free_slots) *free_slots = P ? P->pool.free_slots() : 0;
+    if (free_frames) *free_frames = P ? P->pool.free_frames() : 0;
+    if (frames_known) *frames_known = P ? P->frames_known() : 0;
+    if (frames_delivered) *frames_delivered = P ? P->frames_delivered() : 0;
+    if (steps) *steps = P ? P->pool.steps : 0;
+    return STS_OK;
+}
+int sts_para_close(sts_engine* e) {
+    if (!e) return set_err(STS_EINVAL, "null engine");
+    const int rc = e->eng.para_close();
     return rc == STS_OK ? STS_OK : set_err(rc, e->eng.error());
 }
 

@@ -5,6 +5,7 @@
 // Everything runs on the engine's own HIP stream; the only host synchronisation inside a run is the
 // data-dependent frame count F (SynthesizerTrn.cpp:376-381).  The decoder stage (run_decode) lives in decoder.hip.
 #include "run_ctx.hpp"
+#include "para_stream.hpp"
 #include <time.h>
 #include "knobs.hpp"
 #include "../../include/tts_logger.h"
@@ -19,12 +20,17 @@
 
 namespace sts {
 
-// what an open stream fixed stays fixed, and the engine runs nothing else, until sts_stream_close (engine.hpp stream_open)
+// what an open stream fixed stays fixed, and the engine runs nothing else, until sts_stream_close (engine.hpp stream_open); an open
+// paragraph likewise, until sts_para_close (engine.hpp para_open)
 #define STS_NOT_WHILE_OPEN(what) \
-    do { if (live_) return fail(STS_ESTATE, "a stream is open on this engine (sts_stream_close first): it refuses " what); } while (0)
+    do { \
+        if (live_) return fail(STS_ESTATE, "a stream is open on this engine (sts_stream_close first): it refuses " what); \
+        if (para_) return fail(STS_ESTATE, "a paragraph is open on this engine (sts_para_close first): it refuses " what); \
+    } while (0)
 
 Engine::~Engine() {
     if (live_) (void)stream_close();
+    if (para_) (void)para_close();
     if (stream) (void)hipStreamSynchronize(stream);
     free_model(model);
     if (arenaT_.base) (void)hipFree(arenaT_.base);
@@ -1081,7 +1087,12 @@ int Engine::run_frame_workspace(RunCtx& c) {
         Wcap = 0;
         for (int b = 0; b < B; b++) Wcap += std::min<long>(p_lenF[b], (long)ss->chunk_frames + 2 * halo);
     }
-    if (ss && c.join) {
+    if (ss && c.join && c.para_k >= 0) {
+        // one step of an open paragraph: c.js is the paragraph's plan (para_step), the workspace is what this one step decodes
+        JsStep t;
+        c.js.step(c.para_k, t);
+        Wcap = std::max<long>(1, (long)t.Wtot);
+    } else if (ss && c.join) {
         // a joined stream: the steps walk J (join_stream.hpp).  The workspace is the most frames one step decodes -- the maximum over the
         // steps of the summed window lengths, never the sum of the sentences
         JsPlan& js = c.js;
@@ -1574,9 +1585,13 @@ int Engine::run_stream_steps(RunCtx& c) {
     // one step of an open stream (stream_step): utterance b is the live slot c.live_slots[b] -- its z at its offset in the pool, its chunk
     // at its own next frame -- and the loop below runs once.  Everything else of a step is the closed call's
     LiveStream* const open = c.live;
+    // one step of an open paragraph (para_step): joined AND open -- the plan's step c.para_k alone, every sentence's z at its place in the
+    // pool; the step counter, the form-0 flag and the repeat of a step are the open stream's, the tables and launches the joined stream's
+    const bool para = c.para_k >= 0;
     // (stream_host_buffers may move the pinned block the geometry tables live in)
     std::vector<int> offF, lenF, sidv;
-    if (open) for (const int s : c.live_slots) { const LiveSlot& sl = open->slots[(size_t)s]; offF.push_back((int)sl.off); lenF.push_back((int)sl.F); sidv.push_back(sl.sid); }
+    if (para) { offF.assign(c.para_zoff, c.para_zoff + c.js.s.size()); sidv.assign(c.para_sid, c.para_sid + c.js.s.size()); }
+    else if (open) for (const int s : c.live_slots) { const LiveSlot& sl = open->slots[(size_t)s]; offF.push_back((int)sl.off); lenF.push_back((int)sl.F); sidv.push_back(sl.sid); }
     else { offF.assign(p_offF, p_offF + B); lenF.assign(p_lenF, p_lenF + B); sidv.assign(c.p_sid, c.p_sid + B); }
     const bool joined = c.join;       // a joined stream: the steps walk J, one chunk of the ONE signal per step (join_stream.hpp)
     const OutChain& oc = c.oc;
@@ -1611,10 +1626,11 @@ int Engine::run_stream_steps(RunCtx& c) {
     }
     std::vector<int> wb; std::vector<StepWin> win; StepOut st;
     const long jsteps = joined ? (long)c.js.steps() : 0;
-    for (long k = 0;; k++) {
-        // the utterances that get a chunk in this step (a joined stream: the one signal J)
+    const long k_first = para ? (long)c.para_k : 0;
+    for (long k = k_first;; k++) {
+        // the utterances that get a chunk in this step (a joined stream: the one signal J; an open paragraph: its one step)
         wb.clear();
-        if (joined) { if (k < jsteps && live[0]) wb.push_back(0); }
+        if (joined) { if (para ? k == k_first : (k < jsteps && live[0])) wb.push_back(0); }
         else if (open) { if (k == 0) for (int b = 0; b < B; b++) wb.push_back(b); }      // (the one step: every live slot)
         else for (int b = 0; b < B; b++) if (live[b] && k * Cf < lenF[b]) wb.push_back(b);
         const int nu = (int)wb.size();
@@ -1677,9 +1693,11 @@ int Engine::run_stream_steps(RunCtx& c) {
             const int32_t n = (int32_t)st.n[i], j0 = (int32_t)st.j0[i];
             total_samples += st.n[i];
             if (ss->delivered) ss->delivered[b] += n;
-            if (open) {       // (utt = the slot; it moves on by a chunk, and retires behind its last one or at its stop)
+            if (open && !para) {       // (utt = the slot; it moves on by a chunk, and retires behind its last one or at its stop)
                 const int sl = c.live_slots[b];
                 open->delivered(sl, ss->cb(ss->user, sl, pcm, n, j0) != 0);
+            } else if (para) {       // (the one signal; para_step moves the paragraph on)
+                c.para_stop = ss->cb(ss->user, 0, pcm, n, j0) != 0;
             } else if (ss->cb(ss->user, b, pcm, n, j0) != 0) live[b] = 0;
         }
     }
@@ -1792,6 +1810,7 @@ int Engine::run_joined_stream(int B, const int32_t* const* ids, const int32_t* n
 // flag.  Nothing in the arenas survives a step: every step and every admission lays its workspace out again.
 int Engine::stream_open(int chunk_frames, int max_live, long long capacity_frames) {
     if (live_) return fail(STS_ESTATE, "a stream is already open on this engine (sts_stream_close first)");
+    if (para_) return fail(STS_ESTATE, "a paragraph is open on this engine (sts_para_close first)");
     const Model& M = model;
     if (chunk_frames <= 0 || max_live < 1 || max_live > 1024 || capacity_frames < 1)
         return fail(STS_EINVAL, "an open stream takes a positive chunk size, 1 <= max_live <= 1024 and a positive capacity");
@@ -1953,6 +1972,214 @@ int Engine::stream_step(int (*cb)(void*, int32_t, const int16_t*, int32_t, int32
     if (rc == STS_OK && hipGetLastError() != hipSuccess) rc = fail(STS_EDEVICE, "the step failed on the device");
     if (live_after) *live_after = L.live_count();
     return rc;
+}
+
+// ---- open paragraphs (engine.hpp para_open; para_stream.hpp; DESIGN.md 9i "Open paragraphs").  Between two calls the engine keeps: z of
+// every resident sentence in the pool, the plan's s / F of every sentence so far, the next chunk, the free column ranges, the step count
+// and the form-0 flag.  Nothing in the arenas survives a call: every step and every append lays its workspace out again.
+int Engine::para_open(int chunk_frames, int max_resident, long long capacity_frames, int lead_frames, float fade_ms) {
+    if (live_) return fail(STS_ESTATE, "a stream is open on this engine (sts_stream_close first)");
+    if (para_) return fail(STS_ESTATE, "a paragraph is already open on this engine (sts_para_close first)");
+    const Model& M = model;
+    // (stream_open's bounds and refusals, for the reasons given there)
+    if (chunk_frames <= 0 || max_resident < 1 || max_resident > 1024 || capacity_frames < 1)
+        return fail(STS_EINVAL, "an open paragraph takes a positive chunk size, 1 <= max_resident <= 1024 and a positive capacity");
+    if ((double)capacity_frames * M.inter > 2.0e9 || (double)capacity_frames * M.hop_total > 2.0e9)
+        return fail(STS_EINVAL, "an open paragraph's capacity_frames * inter_channels and capacity_frames * samples_per_frame may not exceed 2 10^9");
+    if (eq_n > 0) return fail(STS_EINVAL, "an open paragraph is not available while an equaliser is set: its state is carried in the frame arena");
+    if (loud_mode != 0) return fail(STS_EINVAL, "an open paragraph is not available while loudness measurement or normalization is on: its state is carried in the frame arena");
+    if (record_taps) return fail(STS_EINVAL, "an open paragraph is not available while taps are recorded");
+    if (have_plan || have_mix || have_gain || have_forced)
+        return fail(STS_EINVAL, "an open paragraph is not available while a duration plan, a speaker mix, a gain plan or forced durations are pending: their tables are per call");
+    const sts_join j{nullptr, lead_frames, 0, fade_ms};
+    const char* why = nullptr;
+    if (!join_valid(1, &j, &why)) return fail(STS_EINVAL, why);
+    HIPCK(hipSetDevice(device));
+    LimiterDesign d{};
+    if (lim_mode != 0 && !limiter_design(out_rate, lim_gain_db, lim_ceiling, lim_ms, &d)) return fail(STS_EINVAL, "limiter: output rate outside [8000, 48000]");
+    if (conv_math == 3) { const int rc = ensure_overflow_word(); if (rc != STS_OK) return rc; }
+    ParaStream* P = new (std::nothrow) ParaStream();
+    if (!P) return fail(STS_EDEVICE, "out of host memory");
+    const int Hd = decoder_halo_frames(M);
+    P->open(chunk_frames, max_resident, capacity_frames, lead_frames, M.hop_total, Hd, stream_halo() - Hd, resampling() ? rs.P : 1, resampling() ? rs.Q : 1,
+            lim_mode != 0 ? d.H : 0);
+    P->fade_h = join_design(fade_ms);
+    if (!P->fits(lead_frames)) { delete P; return fail(STS_EINVAL, "the joined signal is too long for one call (N_J <= 2 10^9 native samples)"); }
+    LiveStream& L = P->pool;
+    L.form0 = conv_math == 3 && h2_disabled;
+    // the pool, as an open stream's: its own allocation (never in arenaF_), a KB of slack behind the last row
+    const size_t pool_bytes = ((size_t)M.inter * (size_t)capacity_frames + 256) * sizeof(float);
+    if (hipMalloc((void**)&L.zpool, pool_bytes) != hipSuccess || hipMalloc(&L.tab_dev, adopt_tab_bytes(max_resident)) != hipSuccess ||
+        hipHostMalloc(&L.tab_host, adopt_tab_bytes(max_resident), hipHostMallocDefault) != hipSuccess) {
+        (void)hipGetLastError();
+        if (L.zpool) (void)hipFree(L.zpool);
+        if (L.tab_dev) (void)hipFree(L.tab_dev);
+        delete P;
+        return fail(STS_EDEVICE, "out of device memory (the open paragraph's latent pool)");
+    }
+    if (poison && hipMemsetD32Async((hipDeviceptr_t)L.zpool, (int)poison, pool_bytes / 4, stream) != hipSuccess) (void)hipGetLastError();
+    mfma_launches_ = 0;                                        // (sts_profile.decoder_mfma_launches: summed over the paragraph's steps)
+    para_ = P;
+    return STS_OK;
+}
+
+int Engine::para_close() {
+    if (!para_) return fail(STS_ESTATE, "no paragraph is open on this engine");
+    (void)hipSetDevice(device);
+    if (stream) (void)hipStreamSynchronize(stream);
+    if (para_->pool.zpool) (void)hipFree(para_->pool.zpool);
+    if (para_->pool.tab_dev) (void)hipFree(para_->pool.tab_dev);
+    if (para_->pool.tab_host) (void)hipHostFree(para_->pool.tab_host);
+    delete para_;
+    para_ = nullptr;
+    return STS_OK;
+}
+
+int Engine::para_finish(int trail_frames) {
+    if (!para_) return fail(STS_ESTATE, "no paragraph is open on this engine (sts_para_open first)");
+    ParaStream& P = *para_;
+    if (P.finished) return fail(STS_EINVAL, "the paragraph is finished already");
+    if (P.sentences() == 0) return fail(STS_EINVAL, "a paragraph cannot finish without a sentence");
+    if (trail_frames < 0 || trail_frames > kJoinMaxFrames) return fail(STS_EINVAL, "join: lead_frames and trail_frames must be in [0, 100000]");
+    if (!P.finish(trail_frames)) return fail(STS_EINVAL, "the joined signal is too long for one call (N_J <= 2 10^9 native and L_out <= 2^31 - 1 output samples)");
+    return STS_OK;
+}
+
+// stream_admit_once's shape: front and flow of the B new sentences in the arithmetic conv_math names, their place in J, their slots and
+// columns, their z into the pool.  kRetrySplitBf16: the overflow word was raised (conv math 3) -- nothing of the append is kept, the
+// caller repeats it in form 0
+int Engine::para_append_once(int B, const int32_t* const* ids, const int32_t* n, const int32_t* sid, const float* ls, const long long* gap,
+                             int32_t* frames_out, int64_t* start_out, int32_t* appended) {
+    ParaStream& P = *para_;
+    LiveStream& L = P.pool;
+    const bool guarded = conv_math == 3;
+    if (guarded) *(volatile unsigned*)ovf_host_ = 0u;
+    poison_bytes_ = 0;
+    host_t0_ = now_us(); host_t_sync_ = 0;
+    StreamSpec ss{L.chunk, [](void*, int32_t, const int16_t*, int32_t, int32_t) { return 0; }, nullptr};
+    RunCtx c;
+    c.B = B; c.ids = ids; c.n = n; c.sid = sid; c.ls = ls; c.ss = &ss; c.bstream = B > 1;
+    int rc;
+    if ((rc = run_setup(c)) != STS_OK) return rc;
+    mark(0);
+    if ((rc = run_text_encoder(c)) != STS_OK) return rc;
+    if ((rc = run_durations(c)) != STS_OK) return rc;          // (a stream never launches ahead: the frame counts are on the host)
+    std::vector<long> F((size_t)B); std::vector<int> sidv((size_t)B); std::vector<long long> start((size_t)B);
+    for (int b = 0; b < B; b++) { F[(size_t)b] = c.p_lenF[b]; sidv[(size_t)b] = c.p_sid[b]; }
+    const int first = P.sentences();
+    const int fit = P.append(B, F.data(), sidv.data(), gap, start.data());
+    if (fit <= 0) {                                            // the front work is lost, nothing has changed
+        HIPCK(hipStreamSynchronize(stream));
+        if (fit < 0) return fail(STS_EINVAL, "the joined signal would be too long for one paragraph (N_J <= 2 10^9 native and L_out <= 2^31 - 1 output samples)");
+        *appended = 0;
+        return STS_OK;
+    }
+    auto undo = [&](int code) { P.undo(B); return code; };
+    if ((rc = run_frame_workspace(c)) != STS_OK) return undo(rc);
+    if ((rc = run_flow(c)) != STS_OK) return undo(rc);
+    // z of the new sentences leaves the arena: one table upload, one launch
+    long long* const tab = (long long*)L.tab_host;
+    int* const tlen = (int*)(tab + 2 * (size_t)B);
+    for (int b = 0; b < B; b++) { tab[b] = c.p_offF[b]; tab[B + b] = P.zoff[(size_t)(first + b)]; tlen[b] = (int)F[(size_t)b]; }
+    if (hipMemcpyAsync(L.tab_dev, tab, adopt_tab_bytes(B), hipMemcpyHostToDevice, stream) != hipSuccess) return undo(fail(STS_EDEVICE, "the adoption table's upload failed"));
+    adopt_z(c.bf.z, c.Fld, L.zpool, L.capacity, c.C, (const long long*)L.tab_dev, B, c.maxF, stream);
+    if (hipStreamSynchronize(stream) != hipSuccess || hipGetLastError() != hipSuccess) return undo(fail(STS_EDEVICE, "the append failed on the device"));
+    if (guarded && *(volatile unsigned*)ovf_host_ != 0u) return undo(kRetrySplitBf16);
+    for (int b = 0; b < B; b++) {
+        if (frames_out) frames_out[b] = (int32_t)F[(size_t)b];
+        if (start_out) start_out[b] = out_count(start[(size_t)b] * c.hop);
+    }
+    *appended = B;
+    return STS_OK;
+}
+
+int Engine::para_append(int B, const int32_t* const* ids, const int32_t* n, const int32_t* sid, const float* ls, const int32_t* gap_frames,
+                        int32_t* frames_out, int64_t* start_out, int32_t* appended) {
+    if (!para_) return fail(STS_ESTATE, "no paragraph is open on this engine (sts_para_open first)");
+    if (!appended) return fail(STS_EINVAL, "an append needs the `appended` output");
+    *appended = 0;
+    ParaStream& P = *para_;
+    if (P.finished) return fail(STS_EINVAL, "the paragraph is finished: it takes no more sentences");
+    if (B < 1 || !ids || !n) return fail(STS_EINVAL, "an append takes B >= 1 sentences with ids and n");
+    if (B > P.pool.max_live) return fail(STS_EINVAL, "an append of more sentences than the paragraph's max_resident can never fit");
+    std::vector<long long> gap((size_t)B, 0);
+    for (int b = 0; gap_frames && b < B; b++) {
+        if (gap_frames[b] < 0 || gap_frames[b] > kJoinMaxFrames) return fail(STS_EINVAL, "join: every gap must be in [0, 100000] frames");
+        gap[(size_t)b] = gap_frames[b];
+    }
+    if (P.sentences() == 0 && gap[0] != 0) return fail(STS_EINVAL, "the gap in front of a paragraph's first sentence must be 0: its lead was given to sts_para_open");
+    if (P.stopped || P.pool.free_slots() < B) return STS_OK;  // (no room now, known before any front work; a stopped paragraph takes nothing)
+    HIPCK(hipSetDevice(device));
+    // global sentence i samples with seed + i, the scales as they are set now
+    std::vector<Noise> keep; keep.swap(noise_utt);
+    for (int b = 0; b < B; b++) noise_utt.push_back(Noise{noise.ns, noise.nsw, noise.seed + (uint64_t)(P.sentences() + b)});
+    const int math = conv_math;
+    if (math == 3 && P.pool.form0) conv_math = 0;
+    int rc = para_append_once(B, ids, n, sid, ls, gap.data(), frames_out, start_out, appended);
+    if (rc == kRetrySplitBf16) {                               // this append alone: nothing of the new sentences has been delivered
+        h2_fallbacks++;
+        conv_math = 0;
+        rc = para_append_once(B, ids, n, sid, ls, gap.data(), frames_out, start_out, appended);
+    }
+    conv_math = math;
+    noise_utt.swap(keep);
+    prof.conv_math_fallbacks = h2_fallbacks;
+    return rc;
+}
+
+// stream_step's shape with the join and the pool both set: ONE step of run_stream_steps, chunk P.k of J, if the frontier lets it leave
+int Engine::para_step(int (*cb)(void*, int32_t, const int16_t*, int32_t, int32_t), void* user, int32_t* ready_after) {
+    if (!para_) return fail(STS_ESTATE, "no paragraph is open on this engine (sts_para_open first)");
+    if (!cb) return fail(STS_EINVAL, "a step takes a callback");
+    ParaStream& P = *para_;
+    LiveStream& L = P.pool;
+    Model& M = model;
+    auto ready = [&] { return (int32_t)std::min<long long>(P.ready(), 2147483647LL); };
+    if (ready_after) *ready_after = ready();
+    if (P.ready() == 0) return STS_OK;
+    HIPCK(hipSetDevice(device));
+    StreamSpec ss{L.chunk, cb, user};
+    RunCtx c;
+    c.live = &L; c.join = true;
+    // (the sentences that have not retired alone: a step's host work does not grow with the paragraph's age.  Until finish F_J = the end
+    // of the last sentence, which no clip of this step reaches)
+    c.js = P.resident_plan(); c.FJ = P.js.FJ;
+    c.para_k = P.k; c.para_zoff = P.zoff.data() + P.first_live; c.para_sid = P.sid.data() + P.first_live;
+    JsStep t;
+    c.js.step(P.k, t);
+    // "utterances" of this context: the step's decode windows (at least one: the tables and the conditioning are sized by it)
+    const int B = c.B = std::max<int>(1, (int)t.win.size());
+    c.ss = &ss; c.bstream = true;                              // (a window's index is never its sentence's: the conditioning is gathered per window)
+    c.bt = BufT{}; c.bf = BufF{};
+    c.ms = M.is_ms == 1; c.H = M.hidden; c.C = M.inter; c.hop = M.hop_total;
+    c.wnH = M.n_flows ? M.cp[0].wn.H : 0; c.wnL = M.n_flows ? M.cp[0].wn.n : 0;
+    // the decode workspace of this step's windows (transient: laid out per step).  The flow's buffers are those of one frame -- no flow
+    // runs here -- and z is the pool
+    std::vector<int> lenF((size_t)B, 1), offF((size_t)B, 0);
+    for (size_t i = 0; i < t.win.size(); i++) lenF[i] = (int)(t.win[i].w1 - t.win[i].w0);
+    c.p_lenF = lenF.data(); c.p_offF = offF.data();
+    c.Ftot = c.Fld = 1; c.maxF = c.maxFld = 1;
+    poison_bytes_ = 0;
+    const int keep_h = join_h;
+    join_h = P.fade_h;
+    auto leave = [&](int code) { join_h = keep_h; return code; };
+    int rc;
+    if ((rc = plan_output(c)) != STS_OK) return leave(rc);
+    if ((rc = run_frame_workspace(c)) != STS_OK) return leave(rc);
+    c.bf.z = L.zpool; c.Fld = L.capacity;
+    const int math = conv_math;
+    if (math == 3 && L.form0) conv_math = 0;
+    if (conv_math == 3) *(volatile unsigned*)ovf_host_ = 0u;
+    rc = run_stream_steps(c);
+    conv_math = math;
+    prof.decoder_mfma_launches = mfma_launches_;
+    prof.conv_math_fallbacks = h2_fallbacks;
+    if (rc == STS_OK && hipGetLastError() != hipSuccess) rc = fail(STS_EDEVICE, "the step failed on the device");
+    // (a step that failed delivered nothing and counts nothing: L.steps stays the next chunk's index, so STS_DBG_STREAM_RETRY_STEP = k
+    // names chunk k, as in a closed joined stream)
+    if (rc == STS_OK) { L.steps++; P.delivered(c.para_stop); }
+    if (ready_after) *ready_after = ready();
+    return leave(rc);
 }
 
 }  // namespace sts

@@ -57,6 +57,7 @@ int decoder_halo_frames(const Model& M);   // decoder.hip
 struct WinGeom;                             // the windows of one decode pass (decoder.hip)
 struct StreamRun;                           // what the steps of one streaming call share (engine.hip)
 struct StreamTail;                          // the windows the output side of a step sees (engine.hip)
+struct ParaStream;                          // the host side of an open paragraph (para_stream.hpp)
 inline bool noise_scale_valid(float s) { return s >= 0.f && s <= 3.0e38f; }   // (false for NaN and +inf)
 // sts_set_loudness: mode 0, 1 or 2, target in [-70, 0] LUFS, ceiling in [-30, 0] dBFS (false for NaN)
 inline bool loudness_args_valid(int mode, float target, float peak) {
@@ -231,6 +232,8 @@ private:
     int stream_loud_gate(RunCtx& c, StreamRun& s);                           // a measuring stream's gate, once behind the last step
     int stream_admit_once(int B, const int32_t* const* ids, const int32_t* n, const int32_t* sid, const float* ls, int32_t* slot_out,
                           int32_t* n_samples_out, int32_t* admitted);
+    int para_append_once(int B, const int32_t* const* ids, const int32_t* n, const int32_t* sid, const float* ls, const long long* gap,
+                         int32_t* frames_out, int64_t* start_out, int32_t* appended);
     int ensure_overflow_word();
     void tap(const char* name, const float* d, int channels, long ld, long length);
     void stage_begin(int s);
@@ -287,8 +290,21 @@ public:
                      int32_t* slot_out, int32_t* n_samples_out, int32_t* admitted);
     int stream_step(int (*cb)(void*, int32_t, const int16_t*, int32_t, int32_t), void* user, int32_t* live_after);
     int stream_close();
-    bool stream_is_open() const { return live_ != nullptr; }
+    bool stream_is_open() const { return live_ != nullptr || para_ != nullptr; }      // "open": an open stream or an open paragraph
     LiveStream* live_ = nullptr;       // null: no stream is open
+    // an open paragraph (sts_para_open .. sts_para_close; para_stream.hpp, DESIGN.md 9i "Open paragraphs"): ONE joined stream per engine
+    // whose sentences are appended between its steps.  para_open fixes what stream_open fixes and the join's lead and fade, and allocates
+    // the latent pool; para_append runs front and flow of B new sentences as the packed batch a joined call of those B would (global
+    // sentence i samples with seed + i) and moves their z into the pool; para_step is ONE step of run_stream_steps with the join and the
+    // pool both set -- the next chunk of J if the frontier rule lets it leave, its callback's utterance always 0.  While a paragraph is open
+    // the engine refuses what it refuses while a stream is open, and sts_stream_open too.  Not to be called from a chunk callback.
+    int para_open(int chunk_frames, int max_resident, long long capacity_frames, int lead_frames, float fade_ms);
+    int para_append(int B, const int32_t* const* ids, const int32_t* n, const int32_t* sid, const float* ls, const int32_t* gap_frames,
+                    int32_t* frames_out, int64_t* start_out, int32_t* appended);
+    int para_finish(int trail_frames);
+    int para_step(int (*cb)(void*, int32_t, const int16_t*, int32_t, int32_t), void* user, int32_t* ready_after);
+    int para_close();
+    ParaStream* para_ = nullptr;       // null: no paragraph is open
     // loudness in a stream (sts_set_loudness_streaming; loudness.hip's stream mode, loud_stream.hpp): off, a stream under mode 1 or 2 is
     // refused; on, mode 1 measures what each step delivers from a state carried per utterance in the frame arena (mode 2 stays refused)
     bool loud_streaming = false;

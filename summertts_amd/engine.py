@@ -334,6 +334,13 @@ def load_library() -> C.CDLL:
     lib.sts_stream_close.argtypes = [C.c_void_p]
     lib.sts_debug_adopt_z.argtypes = [C.c_int, C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
                                       C.c_int32]
+    lib.sts_para_open.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_float]
+    lib.sts_para_append.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                    C.c_void_p]
+    lib.sts_para_finish.argtypes = [C.c_void_p, C.c_int32]
+    lib.sts_para_step.argtypes = [C.c_void_p, CHUNK_CB, C.c_void_p, C.c_void_p]
+    lib.sts_para_info.argtypes = [C.c_void_p] + [C.c_void_p] * 9
+    lib.sts_para_close.argtypes = [C.c_void_p]
     lib.sts_pool_set_stream_admission.argtypes = [C.c_void_p, C.c_int]
     lib.sts_pool_get_stream_admission.argtypes = [C.c_void_p]
     lib.sts_pool_stream_stats.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
@@ -376,6 +383,7 @@ EXPORTED_SYMBOLS = [
     "sts_set_loudness_streaming", "sts_get_loudness_streaming", "sts_loudness_measure_chunked",
     "sts_stream_open", "sts_stream_admit", "sts_stream_step", "sts_stream_info", "sts_stream_close", "sts_debug_adopt_z",
     "sts_pool_set_stream_admission", "sts_pool_get_stream_admission", "sts_pool_stream_stats",
+    "sts_para_open", "sts_para_append", "sts_para_finish", "sts_para_step", "sts_para_info", "sts_para_close",
 ]
 
 
@@ -988,6 +996,106 @@ class Synthesizer:
     def stream_close(self):
         """Drops the live slots without delivering and frees the pool."""
         _check(self.lib, self.lib.sts_stream_close(self.h))
+
+    # -- open paragraphs (sts_para_open .. sts_para_close) ------------------------------------
+    def para_open(self, chunk_frames: int, max_resident: int, capacity_frames: int, lead_frames: int = 0, fade_ms: float = 0.0):
+        """Opens the engine's paragraph: ONE joined stream whose sentences are appended between its steps (``para_append``); every
+        ``para_step`` delivers the next chunk of the joined signal once it can no longer change.  Fixes chunk size, output rate, limiter,
+        conv mode, conv math and the join's lead and fade until ``para_close``."""
+        _check(self.lib, self.lib.sts_para_open(self.h, int(chunk_frames), int(max_resident), int(capacity_frames), int(lead_frames), float(fade_ms)))
+
+    def para_append(self, ids, sid: Optional[Sequence[int]] = None, length_scale: Optional[Sequence[float]] = None,
+                    gap_frames: Optional[Sequence[int]] = None):
+        """Appends the sentences ``ids`` as one packed batch; ``gap_frames[b]`` is the silence in front of sentence b (the paragraph's first:
+        0).  Returns ``(frames, starts)`` -- per sentence its frame count and its start in output samples -- or None when slots or frames
+        do not suffice now (nothing has changed; step, then retry)."""
+        p = PreparedBatch(ids, sid, length_scale)
+        B = len(p)
+        gap = None if gap_frames is None else np.ascontiguousarray(gap_frames, np.int32)
+        if gap is not None and gap.shape != (B,):
+            raise ValueError("gap_frames takes one entry per appended sentence")
+        frames = np.zeros(B, np.int32)
+        start = np.zeros(B, np.int64)
+        app = C.c_int32()
+        _check(self.lib, self.lib.sts_para_append(self.h, B, p.ptrs, p.n_p, p.sid_p, p.ls_p, None if gap is None else gap.ctypes.data,
+                                                  frames.ctypes.data, start.ctypes.data, C.addressof(app)))
+        if app.value == 0:
+            return None
+        return [int(v) for v in frames], [int(v) for v in start]
+
+    def para_finish(self, trail_frames: int = 0):
+        """No more sentences will come: the joined signal ends ``trail_frames`` behind the last one, and every remaining chunk may leave."""
+        _check(self.lib, self.lib.sts_para_finish(self.h, int(trail_frames)))
+
+    def para_step(self, on_chunk=None):
+        """One step: the next chunk of the joined signal, if it is deliverable.  ``on_chunk(pcm: np.int16[], sample_offset)`` may return True
+        to stop the paragraph.  Returns (``(sample_offset, pcm)`` or None when nothing was deliverable, chunks deliverable after it)."""
+        got = []
+
+        def _cb(user, pcm, ns, off):
+            arr = np.ctypeslib.as_array(pcm, shape=(ns,)).copy() if ns else np.zeros(0, np.int16)
+            got.append((int(off), arr))
+            return 1 if (on_chunk and on_chunk(arr, int(off))) else 0
+        cb = CHUNK_CB(_cb)
+        ready = C.c_int32()
+        _check(self.lib, self.lib.sts_para_step(self.h, cb, None, C.addressof(ready)))
+        return (got[0] if got else None), int(ready.value)
+
+    def para_info(self) -> dict:
+        o, f, r, fs = C.c_int32(), C.c_int32(), C.c_int32(), C.c_int32()
+        n, ff, fk, fd, st = C.c_int64(), C.c_int64(), C.c_int64(), C.c_int64(), C.c_int64()
+        _check(self.lib, self.lib.sts_para_info(self.h, C.addressof(o), C.addressof(f), C.addressof(n), C.addressof(r), C.addressof(fs),
+                                                C.addressof(ff), C.addressof(fk), C.addressof(fd), C.addressof(st)))
+        return {"open": bool(o.value), "finished": bool(f.value), "sentences": int(n.value), "resident": int(r.value),
+                "free_slots": int(fs.value), "free_frames": int(ff.value), "frames_known": int(fk.value),
+                "frames_delivered": int(fd.value), "steps": int(st.value)}
+
+    def para_close(self):
+        """Frees the pool and drops what was not delivered."""
+        _check(self.lib, self.lib.sts_para_close(self.h))
+
+    def stream_paragraph(self, sentences_iter, chunk_frames: int, max_resident: int = 8, capacity_frames: int = 8192, sid_iter=None,
+                         gap_frames: int = 0, lead_frames: int = 0, trail_frames: int = 0, fade_ms: float = 0.0, length_scale: float = 1.0):
+        """A generator over the chunks ``(sample_offset, pcm)`` of the paragraph whose sentences (id sequences) ``sentences_iter`` yields one
+        by one -- a language model's output, say: each sentence is appended as it arrives, ``gap_frames`` behind the one before, and
+        whatever has become deliverable is drained before the next one is asked for.  ``sid_iter``: an iterable of speaker ids, one per
+        sentence (None: 0); one that ends before the sentences do raises ValueError.  An append that finds no room is tried again after
+        a step; a lack of slots is seen before any work, but a lack of frames only once the sentence's length is known, so every such
+        attempt runs its text encoder and duration predictor again (never the flow): a pool with room for the sentences in flight spares
+        that work.  The paragraph is closed when the generator ends or is closed."""
+        self.para_open(chunk_frames, max_resident, capacity_frames, lead_frames, fade_ms)
+        try:
+            sids = iter(sid_iter) if sid_iter is not None else None
+            first = True
+            for ids in sentences_iter:
+                sid = None
+                if sids is not None:
+                    try:
+                        sid = [int(next(sids))]
+                    except StopIteration:
+                        raise ValueError("stream_paragraph: sid_iter ran out of speaker ids before sentences_iter ran out of sentences") from None
+                while self.para_append([ids], sid, [length_scale], [0 if first else gap_frames]) is None:
+                    chunk, _ = self.para_step()      # no room now: deliver, which retires sentences
+                    if chunk is None:
+                        raise StsError("stream_paragraph: a sentence does not fit the pool (capacity_frames) and nothing is left to deliver")
+                    yield chunk
+                first = False
+                while True:
+                    chunk, ready = self.para_step()
+                    if chunk is None:
+                        break
+                    yield chunk
+                    if ready == 0:
+                        break
+            if not first:
+                self.para_finish(trail_frames)
+                while True:
+                    chunk, ready = self.para_step()
+                    if chunk is None:
+                        break
+                    yield chunk
+        finally:
+            self.para_close()
 
     # -- batched -----------------------------------------------------------------------------
     def prepare(self, ids: Sequence[Sequence[int]], sid: Optional[Sequence[int]] = None,
