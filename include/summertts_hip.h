@@ -760,7 +760,7 @@ int sts_set_profiling(sts_engine* e, int enable);
  * sizeof(sts_profile)) bytes, so a client compiled against an older header passes ITS sizeof and is never overrun;
  * sts_get_profile(e, p) == sts_get_profile_ex(e, p, sizeof(sts_profile)) of the header this library was built from -- use it only
  * when client and library are built together. */
-#define STS_ABI_VERSION 16
+#define STS_ABI_VERSION 17
 int sts_abi_version(void);
 /* bit 0: lab build (-DSTS_EXPERIMENTS: environment knobs of knobs.hpp, every conv tile code);
  * 0 for the shipped library */
@@ -843,6 +843,24 @@ int sts_debug_attention(int device, const float* q, const float* k, const float*
 int sts_debug_layer_norm(int device, const float* a, const float* b, int32_t nb, int64_t b_stride, const float* res, const float* gamma,
                          const float* beta, int32_t C, int32_t pre_relu, int32_t post_gelu, const float* dw_w, const float* dw_b, int32_t dw_k,
                          int32_t dw_dil, int32_t dw_pad, const int32_t* lengths, int32_t B, float* y, int32_t y_rows);
+
+/* sts_debug_resblock_layer (ABI 17): ONE fused ResBlock layer launch of the decoder's narrow stages on caller data,
+ *   y_j = x + conv2_j(lrelu(conv1_j(lrelu(x)))),   conv1_j: k1[j] taps of dilation dil1[j], conv2_j: k2[j] taps of dilation 1, "same" padding,
+ * for the n members (ResBlock chains) j of one grid; the intermediate is zero outside every utterance, whatever b1 is.
+ * x: [C][ld]; B utterances of lengths[b] >= 1 packed back to back from column 0 (L = sum(lengths) <= ld), as the engine packs them.  Every
+ * member reads the same x and writes its own y.  w1[j] [C][k1[j]][C], w2[j] [C][k2[j]][C] in the blob's [out][k][in] order; b1 / b2: null, or
+ * n pointers to [C] each of which may be null.  The weights go through the loader's own packers and the group is filled as the decoder fills it.
+ * kind: 1 = resblock_layer (exact fp32, direct form), 2 = resblock_wino (exact fp32, Winograd domain), 3 = resblock_bf3 on three bf16 terms,
+ * 4 = resblock_bf3 on two fp16 terms.  variant (kinds 3 / 4): -1 = the shipped tile shape, 0 / 1 = resblock_bf3's two shapes per width.
+ * The kind's own eligibility function judges the filled group; what it refuses is STS_EINVAL and nothing is launched.  The kernels admit
+ * C = 32 / 64 / 128, 1 <= n <= 4, odd k1 and k2, dil1 (k1 - 1) <= 64, k2 <= 33; kind 2 moreover dil1 in {1, 2, 3, 5, 6}, k1 >= 2, 2 <= k2 <= 15.
+ * y: n x [y_rows][ld] floats, y_rows >= C.  The device buffers have exactly these sizes; every y starts out as the word 0xFFFFFFFF and is
+ * copied back whole, so an element no workgroup wrote -- and a row past C or a column past L that one did -- shows.
+ * *ovf (optional): the overflow word of the two-term fp16 form after the launch (0 for kinds 1 to 3). */
+int sts_debug_resblock_layer(int device, const float* x, int32_t C, const int32_t* lengths, int32_t B, int64_t ld, int32_t n,
+                             const float* const* w1, const float* const* b1, const int32_t* k1, const int32_t* dil1,
+                             const float* const* w2, const float* const* b2, const int32_t* k2, float slope, int kind, int variant,
+                             float* y, int32_t y_rows, uint32_t* ovf);
 
 void sts_free(void* p);
 const char* sts_last_error(void);

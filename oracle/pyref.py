@@ -160,6 +160,9 @@ def _port():
         lib.port_attention.argtypes = [C.c_void_p] * 5 + [C.c_int32] * 4 + [C.c_void_p]
         lib.port_layer_norm.restype = None
         lib.port_layer_norm.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32]
+        lib.port_resblock_layer.restype = None
+        lib.port_resblock_layer.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
+                                            C.c_int32, C.c_float]
         _port_lib = lib
     return _port_lib
 
@@ -200,6 +203,31 @@ def port_layer_norm(x, gamma, beta, post_gelu: bool = False) -> np.ndarray:
     assert y.ndim == 2 and g.shape == (y.shape[0],) and b.shape == g.shape
     lib.port_layer_norm(y.ctypes.data, y.shape[0], y.shape[1], g.ctypes.data, b.ctypes.data, 1 if post_gelu else 0)
     return y
+
+
+def port_resblock_layer(x, lengths, w1, b1, dil1: int, w2, b2, slope: float) -> np.ndarray:
+    """The oracle's ResBlock layer x + conv2(lrelu(conv1_dil(lrelu(x)))) (vits_oracle.c resblock_layer, what resblock_forward loops over) on a
+    packed batch: x float32 [C][sum(lengths)], w1 [C][k1][C], w2 [C][k2][C], b1 / b2 [C] or None -> float32, every utterance on its own."""
+    lib = _port()
+    x = np.ascontiguousarray(x, dtype=np.float32)
+    w1 = np.ascontiguousarray(w1, dtype=np.float32)
+    w2 = np.ascontiguousarray(w2, dtype=np.float32)
+    b1 = None if b1 is None else np.ascontiguousarray(b1, dtype=np.float32)
+    b2 = None if b2 is None else np.ascontiguousarray(b2, dtype=np.float32)
+    Cc = x.shape[0]
+    assert x.ndim == 2 and int(np.sum(lengths)) == x.shape[1] and w1.ndim == 3 and w2.ndim == 3
+    assert w1.shape[0] == Cc and w1.shape[2] == Cc and w2.shape[0] == Cc and w2.shape[2] == Cc and w1.shape[1] % 2 == 1 and w2.shape[1] % 2 == 1
+    assert (b1 is None or b1.shape == (Cc,)) and (b2 is None or b2.shape == (Cc,))
+    out = np.zeros(x.shape, np.float32)
+    off = 0
+    for n in lengths:
+        n = int(n)
+        part = np.array(x[:, off:off + n], dtype=np.float32, order="C", copy=True)
+        lib.port_resblock_layer(part.ctypes.data, Cc, n, w1.ctypes.data, None if b1 is None else b1.ctypes.data, w1.shape[1], int(dil1),
+                                w2.ctypes.data, None if b2 is None else b2.ctypes.data, w2.shape[1], float(slope))
+        out[:, off:off + n] = part
+        off += n
+    return out
 
 
 class RefModel(_Model):

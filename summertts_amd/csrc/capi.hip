@@ -750,6 +750,67 @@ int sts_debug_layer_norm(int device, const float* a, const float* b, int32_t nb,
     return d.ok ? STS_OK : set_err(STS_EDEVICE, "the LayerNorm launch failed on the device");
 }
 
+int sts_debug_resblock_layer(int device, const float* x, int32_t C, const int32_t* lengths, int32_t B, int64_t ld, int32_t n,
+                             const float* const* w1, const float* const* b1, const int32_t* k1, const int32_t* dil1,
+                             const float* const* w2, const float* const* b2, const int32_t* k2, float slope, int kind, int variant,
+                             float* y, int32_t y_rows, uint32_t* ovf) {
+    if (ovf) *ovf = 0;
+    if (!x || !w1 || !k1 || !dil1 || !w2 || !k2 || !y) return set_err(STS_EINVAL, "x, y and the members' w1, k1, dil1, w2, k2 tables are required");
+    if (kind < 1 || kind > 4) return set_err(STS_EINVAL, "kind: 1 = resblock_layer, 2 = resblock_wino, 3 = resblock_bf3 (bf16x3), 4 = resblock_bf3 (f16x2)");
+    if (variant < -1 || variant > 1) return set_err(STS_EINVAL, "variant: -1 = automatic, 0 or 1");
+    if (n < 1 || n > kMaxGroup) return set_err(STS_EINVAL, "1 <= n <= 4 members");
+    if (C < 1 || C > 1024 || y_rows < C) return set_err(STS_EINVAL, "1 <= C <= 1024 and every y holds at least C rows");
+    std::vector<int> tab; int max_len = 0;
+    const long L = debug_segments(lengths, B, tab, &max_len);
+    if (L < 0 || ld < L || (double)y_rows * (double)ld * n > (double)(1u << 30)) return set_err(STS_EINVAL, "lengths: B >= 1 entries, each >= 1, sum <= ld, n * y_rows * ld <= 2^30");
+    for (int j = 0; j < n; j++)
+        if (!w1[j] || !w2[j] || k1[j] < 1 || k1[j] > 255 || k2[j] < 1 || k2[j] > 255 || dil1[j] < 1 || dil1[j] > 4096)
+            return set_err(STS_EINVAL, "every member: w1, w2, 1 <= k1, k2 <= 255, 1 <= dil1 <= 4096");
+    int count = 0;
+    if (hipGetDeviceCount(&count) != hipSuccess || count <= 0) return set_err(STS_EDEVICE, "no HIP device visible (no CPU fallback)");
+    if (hipSetDevice(device) != hipSuccess) return set_err(STS_EDEVICE, "no such device");
+    // the weights as the blob carries a ResBlock layer's convs, through the loader's packers
+    HConv c1[kMaxGroup], c2[kMaxGroup];
+    for (int j = 0; j < n; j++) {
+        c1[j].out_ch = c1[j].in_ch = C; c1[j].k = k1[j]; c1[j].dil = dil1[j]; c1[j].pad = dil1[j] * (k1[j] - 1) / 2;
+        c1[j].w = w1[j]; c1[j].b = b1 ? b1[j] : nullptr; c1[j].has_bias = c1[j].b ? 1 : 0;
+        c2[j].out_ch = c2[j].in_ch = C; c2[j].k = k2[j]; c2[j].dil = 1; c2[j].pad = (k2[j] - 1) / 2;
+        c2[j].w = w2[j]; c2[j].b = b2 ? b2[j] : nullptr; c2[j].has_bias = c2[j].b ? 1 : 0;
+    }
+    Model m;
+    struct Freed { Model& m; ~Freed() { (void)hipDeviceSynchronize(); free_model(m); } } freed{m};     // (runs after the buffers' and the stream's release)
+    if (!load_resblock_layer(c1, c2, n, m)) return set_err(STS_EDEVICE, "packing the layer's weights failed: " + m.error);
+    DebugBufs d;
+    const size_t yn = (size_t)y_rows * (size_t)ld;
+    const float* dx = d.up(x, (size_t)C * (size_t)ld);
+    const int* dt = d.up(tab.data(), tab.size());
+    unsigned* dovf = (unsigned*)d.raw(4);
+    d.ok = d.ok && hipMemsetAsync(dovf, 0, 4, d.st) == hipSuccess;
+    float* dy[kMaxGroup] = {};
+    for (int j = 0; j < n; j++) dy[j] = d.out(yn);
+    if (!d.ok) return set_err(STS_EDEVICE, "device buffers of the layer");
+    // the group as Engine::ResStage::fill_fused fills it: every member reads the same x and writes its own y
+    ResLayerGroup R;
+    memset(&R, 0, sizeof(R));
+    R.n = n; R.C = C; R.ld = (long)ld; R.slope = slope; R.seg = SegView{dt, dt + B, 1, 0, 0, 0}; R.B = B; R.max_n = max_len;
+    for (int j = 0; j < n; j++) {
+        if (fill_res_member(m.rb[j].c1[0], m.rb[j].c2[0], dx, dy[j], kind == 4, R.g[j])) { R.math = 1; R.ovf = dovf; }
+        else if (kind == 4) return set_err(STS_EINVAL, "shape has no two-term fp16 copy of its weights");
+    }
+    const bool eligible = kind == 1 ? resblock_layer_eligible(R) : kind == 2 ? resblock_wino_eligible(R) : resblock_bf3_eligible(R);
+    if (!eligible) return set_err(STS_EINVAL, kind == 1 ? "shape not eligible for resblock_layer" : kind == 2 ? "shape not eligible for resblock_wino" : "shape not eligible for resblock_bf3");
+    if (kind == 1) resblock_layer(R, d.st);
+    else if (kind == 2) resblock_wino(R, d.st);
+    else resblock_bf3(R, d.st, variant);
+    d.ok = hipGetLastError() == hipSuccess;
+    for (int j = 0; j < n && d.ok; j++) d.ok = hipMemcpyAsync(y + (size_t)j * yn, dy[j], yn * 4, hipMemcpyDeviceToHost, d.st) == hipSuccess;
+    uint32_t word = 0;
+    d.ok = d.ok && hipMemcpyAsync(&word, dovf, 4, hipMemcpyDeviceToHost, d.st) == hipSuccess && hipStreamSynchronize(d.st) == hipSuccess;
+    if (!d.ok) return set_err(STS_EDEVICE, "the ResBlock layer launch failed on the device");
+    if (ovf) *ovf = word;
+    return STS_OK;
+}
+
 int sts_debug_adopt_z(int device, const float* src, int32_t C, int64_t ld_src, float* dst, int64_t ld_dst, const int64_t* src_off,
                       const int64_t* dst_off, const int32_t* len, int32_t B) {
     if (!src || !dst || !src_off || !dst_off || !len || B < 1 || B > 65535 || C < 1 || ld_src < 1 || ld_dst < 1 ||

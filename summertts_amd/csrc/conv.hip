@@ -1189,8 +1189,8 @@ bool resblock_layer_eligible(const ResLayerGroup& G) {
     if (G.n < 1 || G.n > kMaxGroup || (G.C != 32 && G.C != 64 && G.C != 128) || G.max_n <= 0 || G.B <= 0) return false;
     for (int i = 0; i < G.n; i++) {
         const ResLayerArgs& a = G.g[i];
-        if (!(a.k1 & 1) || !(a.k2 & 1) || a.k1 < 1 || a.k2 < 1) return false;
-        if (a.dil1 * (a.k1 - 1) > RL_XW - RL_W1 || a.k2 - 1 > 32) return false;
+        if (!a.w1 || !a.w2 || !(a.k1 & 1) || !(a.k2 & 1) || a.k1 < 1 || a.k2 < 1) return false;
+        if (a.dil1 < 1 || a.dil1 * (a.k1 - 1) > RL_XW - RL_W1 || a.k2 - 1 > 32) return false;
         if (a.x == a.y) return false;
     }
     return true;

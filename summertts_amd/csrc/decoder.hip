@@ -218,11 +218,7 @@ void Engine::ResStage::fill_fused(int d, ResLayerGroup& R) const {
     R.n = nk; R.C = up.Cout; R.ld = l2.ld; R.slope = 0.1f; R.seg = l2.seg; R.B = l2.nb; R.max_n = l2.max_len;
     for (int j = 0; j < nk; j++) {
         const DConv &c1 = rb(j).c1[d], &c2 = rb(j).c2[d];
-        ResLayerArgs& g = R.g[j];
-        g.x = cur[j]; g.y = b.next(j, cur[j]); g.w1 = c1.w; g.b1 = c1.bias; g.w2 = c2.w; g.b2 = c2.bias;
-        g.k1 = c1.k; g.dil1 = c1.dil; g.k2 = c2.k; g.wu1 = c1.wu; g.wu2 = c2.wu;
-        g.wb1 = c1.wb3; g.wb2 = c2.wb3p;
-        if (e.conv_math == 3 && c1.wh2 && c2.wh2p) { g.wb1 = c1.wh2; g.wb2 = c2.wh2p; g.ws1 = c1.h2_scale; g.ws2 = c2.h2_scale; R.math = 1; R.ovf = e.ovf_; }
+        if (fill_res_member(c1, c2, cur[j], b.next(j, cur[j]), e.conv_math == 3, R.g[j])) { R.math = 1; R.ovf = e.ovf_; }
     }
 }
 

@@ -27,6 +27,18 @@ struct Arena {
     template <typename T> T* get(size_t count) { return (T*)alloc(count * sizeof(T)); }
 };
 
+// One member of a fused ResBlock layer's kernarg block from the layer's two packed convs: the one place that knows which copy of the weights
+// each fused kernel reads (Engine::ResStage::fill_fused; sts_debug_resblock_layer).  h2: the two-term fp16 copies where both exist -- returns
+// whether it took them (the caller then sets ResLayerGroup::math = 1 and its overflow word).
+inline bool fill_res_member(const DConv& c1, const DConv& c2, const float* x, float* y, bool h2, ResLayerArgs& g) {
+    g.x = x; g.y = y; g.w1 = c1.w; g.b1 = c1.bias; g.w2 = c2.w; g.b2 = c2.bias;
+    g.k1 = c1.k; g.dil1 = c1.dil; g.k2 = c2.k; g.wu1 = c1.wu; g.wu2 = c2.wu;
+    g.wb1 = c1.wb3; g.wb2 = c2.wb3p;
+    if (!(h2 && c1.wh2 && c2.wh2p)) return false;
+    g.wb1 = c1.wh2; g.wb2 = c2.wh2p; g.ws1 = c1.h2_scale; g.ws2 = c2.h2_scale;
+    return true;
+}
+
 // one packed level of the pipeline: which segments, how long, how many positions in total
 struct Lvl {
     SegView seg; int nb = 0; int max_len = 0; long total = 0; long ld = 0;

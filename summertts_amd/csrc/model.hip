@@ -271,6 +271,12 @@ bool pack_h2p(Store& st, DConv& d) {
     return true;
 }
 
+// every copy of a ResBlock conv the decoder's layer kernels read; second: the layer's conv2, which the fused split-operand kernel reads in the k
+// order of its parked intermediate
+bool pack_resblock_conv(Store& st, const HConv& h, bool second, DConv& d) {
+    return pack_conv(st, h, PackOpts(), d) && pack_wino(st, h, d) && pack_bf3(st, d) && (!second || pack_bf3(st, d, true)) && pack_h2p(st, d);
+}
+
 // Operands of wn_flow.hip for one coupling (see DFlowFused).  post is linear, so m = post(sum_l skip_l) = sum_l (W_post W_skip_l) acts_l + const:
 // the composite matrices are formed in double here, negated (the kernel accumulates -m and ADDS it to x1), and appended to each layer's
 // res rows.  All sources are the already packed fp32 copies, so the coupling's channel reversal (folded into pre / post) is in.
@@ -554,8 +560,8 @@ bool load_model(const float* blob, int64_t nfloats, Model& m) {
         const int n = r.geti();
         if (!r.ok || n <= 0 || n > 32) FAIL("resblock");
         rb.c1.resize(n); rb.c2.resize(n);
-        for (int i = 0; i < n; i++) { HConv h = parse_conv(r); if (!r.ok || !pack_conv(st, h, PackOpts(), rb.c1[i]) || !pack_wino(st, h, rb.c1[i]) || !pack_bf3(st, rb.c1[i]) || !pack_h2p(st, rb.c1[i])) FAIL("resblock convs1"); }
-        for (int i = 0; i < n; i++) { HConv h = parse_conv(r); if (!r.ok || !pack_conv(st, h, PackOpts(), rb.c2[i]) || !pack_wino(st, h, rb.c2[i]) || !pack_bf3(st, rb.c2[i]) || !pack_bf3(st, rb.c2[i], true) || !pack_h2p(st, rb.c2[i])) FAIL("resblock convs2"); }
+        for (int i = 0; i < n; i++) { HConv h = parse_conv(r); if (!r.ok || !pack_resblock_conv(st, h, false, rb.c1[i])) FAIL("resblock convs1"); }
+        for (int i = 0; i < n; i++) { HConv h = parse_conv(r); if (!r.ok || !pack_resblock_conv(st, h, true, rb.c2[i])) FAIL("resblock convs2"); }
     }
     { HConv h = parse_conv(r); if (!r.ok || !pack_conv(st, h, PackOpts(), m.conv_post)) FAIL("conv_post");
       // the MB-iSTFT / iSTFT heads (128 -> 72 / 18 channels, 7 taps) run on the split-operand kernels at batch (round 6); HiFi-GAN's one-channel output conv has its own FIR kernel
@@ -655,6 +661,28 @@ bool load_model(const float* blob, int64_t nfloats, Model& m) {
     }
     if (!r.ok) FAIL("blob truncated");
     m.consumed = r.o;
+    { const float* slack; if (!st.alloc(1024, &slack)) FAIL("weight store overflow"); }   // kernels may read one row tile past a tensor
+    m.dev_floats = st.used;
+    if (!st.commit()) FAIL("mapping device memory behind the weight store failed");
+    m.dev_mapped = st.mapped; m.dev_handle = st.vmm ? (void*)st.handle : nullptr;
+    if (hipMemcpy(st.dev, st.host.data(), st.used * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) FAIL("weight upload failed");
+    return true;
+}
+
+bool load_resblock_layer(const HConv* c1, const HConv* c2, int n, Model& m) {
+    if (!c1 || !c2 || n < 1) FAIL("no convs");
+    size_t floats = 0;
+    for (int j = 0; j < n; j++) floats += (size_t)c1[j].out_ch * c1[j].k * c1[j].in_ch + (size_t)c2[j].out_ch * c2[j].k * c2[j].in_ch + (size_t)c1[j].out_ch + (size_t)c2[j].out_ch;
+    Store st;
+    if (!st.init(floats)) FAIL("allocation of the weight store failed");
+    m.dev_weights = st.dev; m.dev_vmm = st.vmm; m.dev_reserved = st.reserved;
+    m.n_up = 1; m.n_resk = n;
+    m.rb.assign((size_t)n, DResBlock());
+    for (int j = 0; j < n; j++) {
+        m.rb[j].c1.resize(1); m.rb[j].c2.resize(1);
+        if (!pack_resblock_conv(st, c1[j], false, m.rb[j].c1[0])) FAIL("resblock convs1");
+        if (!pack_resblock_conv(st, c2[j], true, m.rb[j].c2[0])) FAIL("resblock convs2");
+    }
     { const float* slack; if (!st.alloc(1024, &slack)) FAIL("weight store overflow"); }   // kernels may read one row tile past a tensor
     m.dev_floats = st.used;
     if (!st.commit()) FAIL("mapping device memory behind the weight store failed");

@@ -100,6 +100,9 @@ struct Model {
 
 // Parses `blob`, repacks and uploads to the current HIP device.  Returns false and sets m.error on failure.
 bool load_model(const float* blob, int64_t nfloats, Model& m);
+// The convs of ONE ResBlock1 layer of n chains (c1[j], c2[j]: conv1 and conv2 of chain j) through the packers, in the order, load_model packs a
+// ResBlock's convs with, into a store of their own: m.rb[j].c1[0] / c2[0].  For the kernel-level entry sts_debug_resblock_layer; freed by free_model.
+bool load_resblock_layer(const HConv* c1, const HConv* c2, int n, Model& m);
 void free_model(Model& m);
 
 }  // namespace sts

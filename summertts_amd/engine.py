@@ -294,6 +294,9 @@ def load_library() -> C.CDLL:
     lib.sts_debug_layer_norm.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
                                          C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32,
                                          C.c_void_p, C.c_int32]
+    lib.sts_debug_resblock_layer.argtypes = [C.c_int, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p,
+                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_int, C.c_int, C.c_void_p,
+                                             C.c_int32, C.POINTER(C.c_uint32)]
     lib.sts_pool_submit_gain.restype = C.c_int64
     lib.sts_pool_submit_gain.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_float, C.c_uint64, C.c_void_p]
     lib.sts_join_check.argtypes = [C.c_int32, C.c_void_p]
@@ -375,7 +378,7 @@ EXPORTED_SYMBOLS = [
     "sts_multi_set_speaker_mix",
     "sts_set_gain_plan", "sts_gain_plan_check", "sts_gain_design", "sts_gain_plan_apply", "sts_pool_submit_gain",
     "sts_multi_set_gain_plan",
-    "sts_debug_spline_step", "sts_debug_attention", "sts_debug_layer_norm",
+    "sts_debug_spline_step", "sts_debug_attention", "sts_debug_layer_norm", "sts_debug_resblock_layer",
     "sts_join_check", "sts_join_layout", "sts_join_apply", "sts_infer_ids_joined", "sts_get_join_offsets", "sts_pool_submit_joined",
     "sts_infer_ids_joined_stream", "sts_join_apply_range",
     "sts_set_eq", "sts_get_eq", "sts_eq_check", "sts_eq_design", "sts_eq_apply", "sts_pool_set_eq", "sts_multi_set_eq",
@@ -644,6 +647,45 @@ def debug_layer_norm(a, gamma, beta, lengths, b=None, res=None, pre_relu: bool =
                                          int(bool(pre_relu)), int(bool(post_gelu)), ptr(dw_w), ptr(dw_b), kk, int(dw_dil), int(dw_pad),
                                          lens.ctypes.data, lens.size, y.ctypes.data, y.shape[0]))
     return y
+
+
+RESBLOCK_KINDS = {1: "resblock_layer", 2: "resblock_wino", 3: "resblock_bf3 bf16x3", 4: "resblock_bf3 f16x2"}
+
+
+def debug_resblock_layer(x, lengths, members, slope: float, kind: int, variant: int = -1, device: int = 0, extra_rows: int = 0):
+    """One fused ResBlock layer launch on caller data (sts_debug_resblock_layer): ``x`` float32 [C][ld], the utterances of ``lengths``
+    packed back to back from column 0 (sum(lengths) <= ld); ``members``: 1 to 4 tuples (w1 [C][k1][C], b1 [C] or None, dil1, w2 [C][k2][C],
+    b2 [C] or None), every member reads ``x``.  ``kind``: 1 = resblock_layer, 2 = resblock_wino, 3 = resblock_bf3 on three bf16 terms, 4 =
+    on two fp16 terms; ``variant`` -1 / 0 / 1 goes to resblock_bf3.  A shape the kind's eligibility function refuses raises StsError
+    (STS_EINVAL).  -> (y [n][C + extra_rows][ld] whole, from device buffers that started out as the word 0xFFFFFFFF; the overflow word)."""
+    lib = load_library()
+    x = np.ascontiguousarray(x, dtype=np.float32)
+    lens = np.ascontiguousarray(lengths, dtype=np.int32).ravel()
+    if x.ndim != 2 or lens.size < 1 or int(lens.sum()) > x.shape[1]:
+        raise ValueError("x is [C][ld] with sum(lengths) <= ld")
+    Cc, ld = x.shape
+    n = len(members)
+    if n < 1:
+        raise ValueError("at least one member")
+    keep, w1p, b1p, w2p, b2p = [], (C.c_void_p * n)(), (C.c_void_p * n)(), (C.c_void_p * n)(), (C.c_void_p * n)()
+    k1, k2, dil = np.zeros(n, np.int32), np.zeros(n, np.int32), np.zeros(n, np.int32)
+    for j, (w1, b1, d1, w2, b2) in enumerate(members):
+        w1, w2 = np.ascontiguousarray(w1, dtype=np.float32), np.ascontiguousarray(w2, dtype=np.float32)
+        if w1.ndim != 3 or w2.ndim != 3 or (w1.shape[0], w1.shape[2]) != (Cc, Cc) or (w2.shape[0], w2.shape[2]) != (Cc, Cc):
+            raise ValueError("w1 is [C][k1][C] and w2 is [C][k2][C]")
+        b1 = None if b1 is None else _f32(b1, (Cc,), "b1")
+        b2 = None if b2 is None else _f32(b2, (Cc,), "b2")
+        keep += [w1, w2, b1, b2]
+        w1p[j], w2p[j] = w1.ctypes.data, w2.ctypes.data
+        b1p[j], b2p[j] = (None if b1 is None else b1.ctypes.data), (None if b2 is None else b2.ctypes.data)
+        k1[j], k2[j], dil[j] = w1.shape[1], w2.shape[1], int(d1)
+    y = np.zeros((n, Cc + int(extra_rows), ld), np.float32)
+    ovf = C.c_uint32()
+    _check(lib, lib.sts_debug_resblock_layer(int(device), x.ctypes.data, Cc, lens.ctypes.data, lens.size, ld, n, w1p, b1p, k1.ctypes.data,
+                                             dil.ctypes.data, w2p, b2p, k2.ctypes.data, float(slope), int(kind), int(variant), y.ctypes.data,
+                                             y.shape[1], C.byref(ovf)))
+    del keep
+    return y, ovf.value
 
 
 def duration_fit(w, fixed=None, target_frames: int = 0) -> np.ndarray:

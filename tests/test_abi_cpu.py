@@ -22,7 +22,7 @@ def lib():
 def test_exports_every_symbol_declared_in_the_header(lib):
     hdr = open(os.path.join(ROOT, "include", "summertts_hip.h")).read()
     declared = sorted(set(re.findall(r"\b(sts_[a-z0-9_]+)\s*\(", hdr)))
-    assert len(declared) >= 100 and {"sts_debug_spline_step", "sts_debug_attention", "sts_debug_layer_norm"} <= set(declared)
+    assert len(declared) >= 101 and {"sts_debug_spline_step", "sts_debug_attention", "sts_debug_layer_norm", "sts_debug_resblock_layer"} <= set(declared)
     for name in declared:
         assert hasattr(lib, name), f"{name} declared in summertts_hip.h but not exported"
     assert set(engine.EXPORTED_SYMBOLS) == set(declared)
