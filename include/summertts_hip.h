@@ -760,7 +760,7 @@ int sts_set_profiling(sts_engine* e, int enable);
  * sizeof(sts_profile)) bytes, so a client compiled against an older header passes ITS sizeof and is never overrun;
  * sts_get_profile(e, p) == sts_get_profile_ex(e, p, sizeof(sts_profile)) of the header this library was built from -- use it only
  * when client and library are built together. */
-#define STS_ABI_VERSION 17
+#define STS_ABI_VERSION 18
 int sts_abi_version(void);
 /* bit 0: lab build (-DSTS_EXPERIMENTS: environment knobs of knobs.hpp, every conv tile code);
  * 0 for the shipped library */
@@ -861,6 +861,30 @@ int sts_debug_resblock_layer(int device, const float* x, int32_t C, const int32_
                              const float* const* w1, const float* const* b1, const int32_t* k1, const int32_t* dil1,
                              const float* const* w2, const float* const* b2, const int32_t* k2, float slope, int kind, int variant,
                              float* y, int32_t y_rows, uint32_t* ovf);
+
+/* sts_debug_col_layer (ABI 18): ONE launch of the fused column-block layer (col_layer.hip) on caller data, in each of its forms:
+ *   h = x, or (xs_w given) h[c][t] = (xs_w[c] xr[t] + xs_b[c]) + x[c][t], each step rounded to float (the ConvFlow's folded 1 -> C input conv)
+ *   u = gelu(LN_C(dw_b + dwconv(h)) g1 + b1) with dw_w given (tap j reads position pos + j dw_dil - dw_pad of the SAME utterance of h, zero
+ *       outside it), else u = h
+ *   v = add + (conv1x1(u) + bias) ;  y = LN_C(v) g2 + b2 ;  gelu(y) if post_gelu ;  y = h + y if use_res
+ *   with tp_w: p = tp_w y + tp_b (29 rows), o0[t] = inverse spline of r1[t] under p[:, t] (tp_fs = sqrt(filter channels)), o1 = r0; y is
+ *       then not written.
+ * x, add (optional): [C][ld]; B utterances of lengths[b] >= 1 packed back to back from column 0 (sum(lengths) <= ld).  xs_w [C], xs_b [C]
+ * (optional), xr [ld] (optional: the all-zero latent); dw_w [dw_k][C], dw_b [C] (optional); g1, b1, g2, b2, bias (optional) [C]; w [C][C]
+ * and tp_w [29][C] in the blob's [out][1][in] order, tp_b [29]; tp_r0 / tp_r1 [ld] (optional: zeros).  The convs go through the loader's own
+ * packers (load_col_layer) and the kernel arguments are filled by the functions the engine fills them with.
+ * col_layer_eligible judges the filled arguments; what it refuses is STS_EINVAL and nothing is launched.  The kernel admits C = 32 / 64 /
+ * 192 / 256 (a tail: not 256), 1 <= dw_k <= 3, g1 and b1 with dw_w, xs_w only with dw_w and use_res, tp_b with tp_w.
+ * alias (the refusals of overlapping buffers): 0 = none, 1 = y is x, 2 = o0 is r0, 3 = o0 is r1, 4 = o1 is r1 -- all refused -- and 5 = o1
+ * is r0, which is admitted (o1 then comes back as that buffer: r0's own values in the columns past sum(lengths)).
+ * y: [y_rows][ld], y_rows >= C; o0, o1: [ld], required with tp_w.  The device buffers have exactly these sizes; y, o0 and o1 start out as
+ * the word 0xFFFFFFFF and are copied back whole, so an element no workgroup wrote -- and a row past C or a column past sum(lengths) that
+ * one did -- shows. */
+int sts_debug_col_layer(int device, const float* x, int32_t C, const int32_t* lengths, int32_t B, int64_t ld, const float* xs_w,
+                        const float* xs_b, const float* xr, const float* dw_w, const float* dw_b, int32_t dw_k, int32_t dw_dil, int32_t dw_pad,
+                        const float* g1, const float* b1, const float* w, const float* bias, const float* add, const float* g2,
+                        const float* b2, int32_t post_gelu, int32_t use_res, const float* tp_w, const float* tp_b, float tp_fs,
+                        const float* tp_r0, const float* tp_r1, int32_t alias, float* y, int32_t y_rows, float* o0, float* o1);
 
 void sts_free(void* p);
 const char* sts_last_error(void);

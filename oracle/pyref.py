@@ -163,6 +163,13 @@ def _port():
         lib.port_resblock_layer.restype = None
         lib.port_resblock_layer.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
                                             C.c_int32, C.c_float]
+        lib.port_dds_layer.restype = None
+        lib.port_dds_layer.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32] + [C.c_void_p] * 6
+        lib.port_convflow_step.restype = None
+        lib.port_convflow_step.argtypes = ([C.c_void_p, C.c_int32, C.c_int32] + [C.c_void_p] * 6 + [C.c_int32] * 3 + [C.c_void_p] * 8 +
+                                           [C.c_float] + [C.c_void_p] * 4)
+        lib.port_oproj_ln.restype = None
+        lib.port_oproj_ln.argtypes = [C.c_void_p, C.c_int32, C.c_int32] + [C.c_void_p] * 6
         _port_lib = lib
     return _port_lib
 
@@ -228,6 +235,102 @@ def port_resblock_layer(x, lengths, w1, b1, dil1: int, w2, b2, slope: float) -> 
         out[:, off:off + n] = part
         off += n
     return out
+
+
+def _opt(a, shape=None):
+    if a is None:
+        return None
+    a = np.ascontiguousarray(a, dtype=np.float32)
+    assert shape is None or a.shape == tuple(shape), (a.shape, shape)
+    return a
+
+
+def _ptr(a):
+    return None if a is None else a.ctypes.data
+
+
+def _dw_blob(dw_w, Cc):
+    """[k][C] (the kernel entry's order) -> the blob's [C][k][1]."""
+    dw_w = np.ascontiguousarray(dw_w, dtype=np.float32)
+    assert dw_w.ndim == 2 and dw_w.shape[1] == Cc
+    return np.ascontiguousarray(dw_w.T), dw_w.shape[0]
+
+
+def port_dds_layer(x, lengths, dw_w, dw_b, dil: int, pad: int, g1, b1, w, bias, g2, b2) -> np.ndarray:
+    """The oracle's DDSConv layer x + gelu(LN2(conv1x1(gelu(LN1(dwconv(x)))))) (vits_oracle.c dds_layer, what dds_forward loops over) on a
+    packed batch: x float32 [C][sum(lengths)], dw_w [k][C] with ``pad`` zeros on the left and dil (k - 1) - pad on the right, w [C][C] in
+    [out][in] order; dw_b / bias [C] or None -> float32, every utterance on its own."""
+    lib = _port()
+    x = np.ascontiguousarray(x, dtype=np.float32)
+    Cc = x.shape[0]
+    assert x.ndim == 2 and int(np.sum(lengths)) == x.shape[1]
+    dw, k = _dw_blob(dw_w, Cc)
+    assert 0 <= pad <= dil * (k - 1)
+    dw_b, bias = _opt(dw_b, (Cc,)), _opt(bias, (Cc,))
+    g1, b1, g2, b2 = (_opt(v, (Cc,)) for v in (g1, b1, g2, b2))
+    w = _opt(w, (Cc, Cc))
+    out = np.zeros(x.shape, np.float32)
+    off = 0
+    for n in lengths:
+        n = int(n)
+        part = np.array(x[:, off:off + n], dtype=np.float32, order="C", copy=True)
+        lib.port_dds_layer(part.ctypes.data, Cc, n, dw.ctypes.data, _ptr(dw_b), k, int(dil), int(pad), g1.ctypes.data, b1.ctypes.data,
+                           w.ctypes.data, _ptr(bias), g2.ctypes.data, b2.ctypes.data)
+        out[:, off:off + n] = part
+        off += n
+    return out
+
+
+def port_convflow_step(g, lengths, pre_w, pre_b, x0, x1, dw_w, dw_b, dil: int, pad: int, g1, b1, w, bias, g2, b2, proj_w=None, proj_b=None,
+                       filter_sqrt: float = 1.0, with_input: bool = False):
+    """The body of the oracle's convflow_inverse around one DDSConv layer, with sdp_forward's channel flip (vits_oracle.c
+    port_convflow_step): h = conv1d(pre)(x0) + g, the layer, then (``proj_w`` [29][C] given) the projection and the inverse spline of x1
+    per column.  g float32 [C][sum(lengths)], pre_w [C], pre_b [C] or None, x0 / x1 [sum(lengths)] or None (zeros).
+    -> (y [C][L] the layer's output, o0 [L] or None, o1 [L] or None), every utterance on its own; ``with_input``: h [C][L] in front."""
+    lib = _port()
+    g = np.ascontiguousarray(g, dtype=np.float32)
+    Cc, L = g.shape
+    assert int(np.sum(lengths)) == L
+    dw, k = _dw_blob(dw_w, Cc)
+    assert 0 <= pad <= dil * (k - 1)
+    pre_w, pre_b, dw_b, bias = _opt(pre_w, (Cc,)), _opt(pre_b, (Cc,)), _opt(dw_b, (Cc,)), _opt(bias, (Cc,))
+    g1, b1, g2, b2 = (_opt(v, (Cc,)) for v in (g1, b1, g2, b2))
+    w = _opt(w, (Cc, Cc))
+    x0, x1 = _opt(x0, (L,)), _opt(x1, (L,))
+    proj_w, proj_b = _opt(proj_w, (29, Cc)), _opt(proj_b, (29,))
+    y, h = np.zeros((Cc, L), np.float32), np.zeros((Cc, L), np.float32)
+    o0 = o1 = None
+    if proj_w is not None:
+        o0, o1 = np.zeros(L, np.float32), np.zeros(L, np.float32)
+    off = 0
+    for n in lengths:
+        n = int(n)
+        gp = np.ascontiguousarray(g[:, off:off + n])
+        yp, hp, a0, a1 = np.zeros((Cc, n), np.float32), np.zeros((Cc, n), np.float32), np.zeros(n, np.float32), np.zeros(n, np.float32)
+        p0 = None if x0 is None else np.ascontiguousarray(x0[off:off + n])
+        p1 = None if x1 is None else np.ascontiguousarray(x1[off:off + n])
+        lib.port_convflow_step(gp.ctypes.data, Cc, n, pre_w.ctypes.data, _ptr(pre_b), _ptr(p0), _ptr(p1), dw.ctypes.data, _ptr(dw_b), k,
+                               int(dil), int(pad), g1.ctypes.data, b1.ctypes.data, w.ctypes.data, _ptr(bias), g2.ctypes.data,
+                               b2.ctypes.data, _ptr(proj_w), _ptr(proj_b), float(filter_sqrt), hp.ctypes.data, yp.ctypes.data, a0.ctypes.data,
+                               a1.ctypes.data)
+        y[:, off:off + n], h[:, off:off + n] = yp, hp
+        if proj_w is not None:
+            o0[off:off + n], o1[off:off + n] = a0, a1
+        off += n
+    return (h, y, o0, o1) if with_input else (y, o0, o1)
+
+
+def port_oproj_ln(att, w, bias, x, gamma, beta) -> np.ndarray:
+    """The oracle's LN(x + conv1x1(att)) (vits_oracle.c text_encoder: the attention output projection, its residual and LayerNorm) of att
+    float32 [C][T], w [C][C] in [out][in] order; bias [C] / x [C][T] or None -> float32 [C][T].  (Per column: no utterance boundaries.)"""
+    lib = _port()
+    att = np.ascontiguousarray(att, dtype=np.float32)
+    Cc, T = att.shape
+    w, bias, x = _opt(w, (Cc, Cc)), _opt(bias, (Cc,)), _opt(x, (Cc, T))
+    gamma, beta = _opt(gamma, (Cc,)), _opt(beta, (Cc,))
+    y = np.zeros((Cc, T), np.float32)
+    lib.port_oproj_ln(att.ctypes.data, Cc, T, w.ctypes.data, _ptr(bias), _ptr(x), gamma.ctypes.data, beta.ctypes.data, y.ctypes.data)
+    return y
 
 
 class RefModel(_Model):

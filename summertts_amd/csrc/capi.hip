@@ -811,6 +811,77 @@ int sts_debug_resblock_layer(int device, const float* x, int32_t C, const int32_
     return STS_OK;
 }
 
+int sts_debug_col_layer(int device, const float* x, int32_t C, const int32_t* lengths, int32_t B, int64_t ld, const float* xs_w,
+                        const float* xs_b, const float* xr, const float* dw_w, const float* dw_b, int32_t dw_k, int32_t dw_dil, int32_t dw_pad,
+                        const float* g1, const float* b1, const float* w, const float* bias, const float* add, const float* g2,
+                        const float* b2, int32_t post_gelu, int32_t use_res, const float* tp_w, const float* tp_b, float tp_fs,
+                        const float* tp_r0, const float* tp_r1, int32_t alias, float* y, int32_t y_rows, float* o0, float* o1) {
+    if (!x || !w || !g2 || !b2 || !y) return set_err(STS_EINVAL, "x, w, g2, b2 and y are required");
+    if (C < 1 || C > 4096 || y_rows < C) return set_err(STS_EINVAL, "1 <= C <= 4096 and y holds at least C rows");
+    std::vector<int> tab; int max_len = 0;
+    const long L = debug_segments(lengths, B, tab, &max_len);
+    if (L < 0 || ld < L || (double)y_rows * (double)ld > (double)(1u << 30)) return set_err(STS_EINVAL, "lengths: B >= 1 entries, each >= 1, sum <= ld, y_rows * ld <= 2^30");
+    if (dw_w && (dw_k < 1 || dw_k > 64 || dw_dil < 1 || dw_dil > 4096 || dw_pad < 0 || dw_pad > (1 << 20))) return set_err(STS_EINVAL, "depthwise conv: 1 <= k <= 64, 1 <= dil <= 4096, 0 <= pad <= 2^20");
+    if (!dw_w && dw_b) return set_err(STS_EINVAL, "dw_b goes with dw_w");
+    if (!xs_w && (xs_b || xr)) return set_err(STS_EINVAL, "xs_b and xr go with xs_w");
+    if (tp_w ? (!o0 || !o1 || !(tp_fs > 0.f)) : (tp_b != nullptr)) return set_err(STS_EINVAL, "a tail needs o0, o1 and tp_fs > 0; tp_b goes with tp_w");
+    if (alias < 0 || alias > 5 || (alias >= 2 && !tp_w) || ((alias == 2 || alias == 5) && !tp_r0) || ((alias == 3 || alias == 4) && !tp_r1))
+        return set_err(STS_EINVAL, "alias: 0 none, 1 y = x, 2 o0 = r0, 3 o0 = r1, 4 o1 = r1, 5 o1 = r0 (2 - 5: a tail with that latent half)");
+    int count = 0;
+    if (hipGetDeviceCount(&count) != hipSuccess || count <= 0) return set_err(STS_EDEVICE, "no HIP device visible (no CPU fallback)");
+    if (hipSetDevice(device) != hipSuccess) return set_err(STS_EDEVICE, "no such device");
+    // the weights as the blob carries a ConvFlow's convs ([out][k][in]), through the loader's packers
+    std::vector<float> dwt;
+    HConv pre, sep, pw, proj; HLn n1, n2;
+    pre.out_ch = C; pre.in_ch = 1; pre.k = 1; pre.w = xs_w; pre.b = xs_b; pre.has_bias = xs_b ? 1 : 0;
+    if (dw_w) {
+        dwt.resize((size_t)C * dw_k);
+        for (int c = 0; c < C; c++) for (int j = 0; j < dw_k; j++) dwt[(size_t)c * dw_k + j] = dw_w[(size_t)j * C + c];
+        sep.out_ch = C; sep.in_ch = 1; sep.k = dw_k; sep.dil = dw_dil; sep.pad = dw_pad; sep.w = dwt.data(); sep.b = dw_b; sep.has_bias = dw_b ? 1 : 0;
+    }
+    pw.out_ch = pw.in_ch = C; pw.k = 1; pw.w = w; pw.b = bias; pw.has_bias = bias ? 1 : 0;
+    proj.out_ch = 29; proj.in_ch = C; proj.k = 1; proj.w = tp_w; proj.b = tp_b; proj.has_bias = tp_b ? 1 : 0;
+    n1.size = C; n1.g = g1; n1.b = b1;
+    n2.size = C; n2.g = g2; n2.b = b2;
+    Model m;
+    struct Freed { Model& m; ~Freed() { (void)hipDeviceSynchronize(); free_model(m); } } freed{m};     // (runs after the buffers' and the stream's release)
+    if (!load_col_layer(xs_w ? &pre : nullptr, dw_w ? &sep : nullptr, (g1 && b1) ? &n1 : nullptr, pw, n2, tp_w ? &proj : nullptr, m))
+        return set_err(STS_EDEVICE, "packing the layer's weights failed: " + m.error);
+    const DConvFlow& cf = m.cf[0];
+    DebugBufs d;
+    const size_t xn = (size_t)C * (size_t)ld, yn = (size_t)y_rows * (size_t)ld;
+    const float* dx = d.up(x, xn);
+    const float* dadd = d.up(add, xn);
+    const float* dxr = d.up(xr, (size_t)ld);
+    const float* dr0 = d.up(tp_r0, (size_t)ld);
+    const float* dr1 = d.up(tp_r1, (size_t)ld);
+    const int* dt = d.up(tab.data(), tab.size());
+    float* dy = d.out(yn);
+    float* do0 = tp_w ? d.out((size_t)ld) : nullptr;
+    float* do1 = tp_w ? d.out((size_t)ld) : nullptr;
+    if (!d.ok) return set_err(STS_EDEVICE, "device buffers of the layer");
+    Lvl lv;
+    lv.seg = SegView{dt, dt + B, 1, 0, 0, 0}; lv.nb = B; lv.max_len = max_len; lv.total = L; lv.ld = (long)ld;
+    // the kernarg block as the engine fills it; what the engine fixes per form and the entry leaves to the caller follows
+    ColLayerArgs g;
+    float* ydst = alias == 1 ? const_cast<float*>(dx) : dy;
+    if (dw_w) fill_col_dds(cf.dds.sep[0], cf.dds.n1[0], cf.dds.pw[0], cf.dds.n2[0], dx, ydst, lv, g);
+    else fill_col_oproj(cf.dds.pw[0], cf.dds.n2[0], dx, dadd, ydst, lv, g);
+    g.C = C; g.add = dadd; g.add_ld = (long)ld; g.post_gelu = post_gelu != 0;
+    g.res = use_res ? dx : nullptr; g.res_ld = (long)ld;
+    if (xs_w) { fill_col_pre(cf.pre, dxr, dx, g); if (!use_res) g.res = nullptr; }
+    if (tp_w)
+        fill_col_tail(cf.proj, tp_fs, dr0, dr1, alias == 2 ? const_cast<float*>(dr0) : alias == 3 ? const_cast<float*>(dr1) : do0,
+                      alias == 4 ? const_cast<float*>(dr1) : alias == 5 ? const_cast<float*>(dr0) : do1, g);
+    if (!col_layer_eligible(g)) return set_err(STS_EINVAL, "shape not eligible for col_layer");
+    col_layer(g, d.st);
+    d.ok = hipGetLastError() == hipSuccess && hipMemcpyAsync(y, dy, yn * 4, hipMemcpyDeviceToHost, d.st) == hipSuccess &&
+           (!tp_w || (hipMemcpyAsync(o0, g.tp_o0, (size_t)ld * 4, hipMemcpyDeviceToHost, d.st) == hipSuccess &&
+                      hipMemcpyAsync(o1, g.tp_o1, (size_t)ld * 4, hipMemcpyDeviceToHost, d.st) == hipSuccess)) &&
+           hipStreamSynchronize(d.st) == hipSuccess;
+    return d.ok ? STS_OK : set_err(STS_EDEVICE, "the column-block layer launch failed on the device");
+}
+
 int sts_debug_adopt_z(int device, const float* src, int32_t C, int64_t ld_src, float* dst, int64_t ld_dst, const int64_t* src_off,
                       const int64_t* dst_off, const int32_t* len, int32_t B) {
     if (!src || !dst || !src_off || !dst_off || !len || B < 1 || B > 65535 || C < 1 || ld_src < 1 || ld_dst < 1 ||

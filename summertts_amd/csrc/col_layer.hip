@@ -30,6 +30,15 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ int cl_seg_start(const SegView& s, int b) { return (s.off ? s.off[b] : s.ioff) * s.scale + b * s.extra; }
 __device__ __forceinline__ int cl_seg_len(const SegView& s, int b) { return (s.off ? s.len[b] : s.ilen) * s.scale + s.extra; }
 
+// The folded input h = (w r + b) + g with every step rounded to float, as the separate 1 -> C conv and its residual add round them (and
+// as the reference does).  __fmul_rn / __fadd_rn are plain operators to hipcc, which contracts them into fma(w, r, b) -- one rounding
+// less, an ulp off the unfused path; contraction is off in here.
+__device__ __forceinline__ float cl_fold(float w, float r, float b, float g) {
+#pragma clang fp contract(off)
+    const float p = w * r;
+    return (p + b) + g;
+}
+
 template <int NSUB, bool TAIL = false>   // TAIL: the ConvFlow projection + spline step behind the layer (ColLayerArgs::tp_*)
 __global__ __launch_bounds__(64 * NSUB) void col_layer_kernel(ColLayerArgs a) {
     constexpr int C = 16 * NSUB, KQ = C / 4, CG = 4 * NSUB;     // k-steps of 4 channels; channel groups of the input stage
@@ -72,7 +81,7 @@ __global__ __launch_bounds__(64 * NSUB) void col_layer_kernel(ColLayerArgs a) {
                 const bool ok = live && j < a.dw_k && q >= 0 && q < len && !(STS_EXP & 8);
                 dww[i][j] = j < a.dw_k ? a.dw_w[(size_t)j * a.dw_ld + c] : 0.f;
                 float xv = ok ? row[q] : 0.f;
-                if (a.xs_w && ok) xv = __fadd_rn(__fadd_rn(__fmul_rn(sw, xrq[j]), sb), xv);   // (w x + b) + g, rounded as the separate conv did
+                if (a.xs_w && ok) xv = cl_fold(sw, xrq[j], sb, xv);   // (w x + b) + g, rounded as the separate conv did
                 xin[i][j] = xv;
             }
         }
@@ -98,7 +107,7 @@ __global__ __launch_bounds__(64 * NSUB) void col_layer_kernel(ColLayerArgs a) {
         e_res[r] = (a.res && live) ? a.res[(size_t)(row0 + r) * a.res_ld + base + pos] : 0.f;
         if (a.xs_w && a.res && live) {           // the residual is the same folded input h
             const float xr0 = a.xr ? a.xr[base + pos] : 0.f;
-            e_res[r] = __fadd_rn(__fadd_rn(__fmul_rn(a.xs_w[row0 + r], xr0), a.xs_b ? a.xs_b[row0 + r] : 0.f), e_res[r]);
+            e_res[r] = cl_fold(a.xs_w[row0 + r], xr0, a.xs_b ? a.xs_b[row0 + r] : 0.f, e_res[r]);
         }
     }
 

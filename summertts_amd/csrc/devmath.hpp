@@ -41,7 +41,11 @@ __device__ __forceinline__ float rq_spline_param(int j, float h, float filter_sq
     const float e = expf(h);
     return (isinf(e) ? h : logf(e + 1.0f)) + (float)1e-3;
 }
+// Every product and sum below is rounded on its own, as the reference's are (hipcc would otherwise contract the knot sums, the three
+// quadratic coefficients and the discriminant into FMAs): where the discriminant is small against bq^2 the two roundings of
+// bq * bq - 4 aa cc and the one of its FMA form send the root different ways, and parity is defined by the reference's.
 __device__ __forceinline__ float rq_spline_inverse_t(float x, const float* t) {
+#pragma clang fp contract(off)
     constexpr int NB = 10;
     const float tail = 5.0f;
     if (!(x < tail && x > -tail)) return x;

@@ -284,18 +284,11 @@ float* Engine::dds(const DDds& d, float* h, float* t1, float* t2, const Lvl& lv,
             // the whole layer as ONE launch (col_layer.hip); output goes to the other buffer: neighbouring workgroups still
             // read `cur` through the dilated depthwise taps
             ColLayerArgs g;
-            memset(&g, 0, sizeof(g));
             float* nxt = cur == h ? t1 : h;
-            g.x = cur; g.x_ld = lv.ld;
-            g.dw_w = c.w; g.dw_b = c.bias; g.dw_k = c.k; g.dw_dil = c.dil; g.dw_pad = c.pad; g.dw_ld = c.Cout_pad;
-            g.g1 = d.n1[i].g; g.b1 = d.n1[i].b;
-            g.wc = pw.wc; g.bias = pw.bias;
-            g.g2 = d.n2[i].g; g.b2 = d.n2[i].b; g.post_gelu = 1;
-            g.res = cur; g.res_ld = lv.ld; g.y = nxt; g.y_ld = lv.ld; g.C = pw.Cin;
-            g.seg = lv.seg; g.B = lv.nb; g.max_len = lv.max_len;
+            fill_col_dds(c, d.n1[i], pw, d.n2[i], cur, nxt, lv, g);
             if (pre_pending && i == 0 && pre->Cin == 1 && pre->k == 1 && pre->Cout == pw.Cin && !pre->depthwise && pre_res) {
                 // fold h = (w r + b) + g into the layer: x = res = g, rank-1 term from the conv's single input row
-                g.x = pre_res; g.res = pre_res; g.xs_w = pre->w; g.xs_b = pre->bias; g.xr = pre_in;
+                fill_col_pre(*pre, pre_in, pre_res, g);
                 if (col_layer_eligible(g)) {
                     pre_pending = false;
                     flops_[cur_stage_] += 2.0 * pre->macs_per_out * (double)lv.total;
@@ -306,8 +299,7 @@ float* Engine::dds(const DDds& d, float* h, float* t1, float* t2, const Lvl& lv,
                 tail->proj->Cout_pad == 32 && tail->proj->Cin == pw.Cin && tail->proj->Cin_pad == pw.Cin && tail->proj->w && tail->proj->bias) {
                 // the layer's output feeds only the projection: both and the spline step in this launch
                 ColLayerArgs gt = g;
-                gt.tp_w = tail->proj->w; gt.tp_b = tail->proj->bias; gt.tp_fs = tail->filter_sqrt;
-                gt.tp_r0 = tail->r0; gt.tp_r1 = tail->r1; gt.tp_o0 = tail->o0; gt.tp_o1 = tail->o1;
+                fill_col_tail(*tail->proj, tail->filter_sqrt, tail->r0, tail->r1, tail->o0, tail->o1, gt);
                 if (col_layer_eligible(gt)) {
                     flops_[cur_stage_] += 2.0 * (c.macs_per_out + pw.macs_per_out + tail->proj->macs_per_out) * (double)lv.total;
                     bytes_[cur_stage_] += 4.0 * ((double)pw.Cin * lv.total + (double)pw.Cin * pw.Cout + (double)pw.Cin * 32 + 4.0 * lv.total);
@@ -749,10 +741,7 @@ int Engine::run_text_encoder(RunCtx& c) {
         {   // output projection + residual + LayerNorm: one launch (col_layer.hip) where the width is instantiated
             static const bool no_col = exp_flag("STS_NO_COL_LAYER");   // experiment knob
             ColLayerArgs g;
-            memset(&g, 0, sizeof(g));
-            g.x = bt.att; g.x_ld = Ttot; g.wc = a.o.wc; g.bias = a.o.bias;
-            g.add = bt.x; g.add_ld = Ttot; g.g2 = M.ln1[l].g; g.b2 = M.ln1[l].b; g.y = bt.x1; g.y_ld = Ttot; g.C = H;
-            g.seg = lvT.seg; g.B = B; g.max_len = maxT;
+            fill_col_oproj(a.o, M.ln1[l], bt.att, bt.x, bt.x1, lvT, g);
             if (!no_col && conv_mode != 1 && a.o.Cin == H && a.o.Cout == H && a.o.Cin_pad == H && M.ln1[l].C == H && col_layer_eligible(g)) {
                 flops_[0] += 2.0 * a.o.macs_per_out * (double)Ttot;
                 bytes_[0] += 4.0 * ((double)H * Ttot * 3.0 + (double)H * H);

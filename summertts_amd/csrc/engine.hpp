@@ -3,6 +3,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <string.h>
+
 #include <deque>
 #include <map>
 #include <unordered_map>
@@ -43,6 +45,37 @@ inline bool fill_res_member(const DConv& c1, const DConv& c2, const float* x, fl
 struct Lvl {
     SegView seg; int nb = 0; int max_len = 0; long total = 0; long ld = 0;
 };
+
+// The kernarg block of a column-block layer launch (col_layer.hip) in each of its forms: the one place that knows which copy of a packed
+// conv the kernel reads (Engine::dds, the text encoder's output projection; sts_debug_col_layer).
+// A DDSConv layer x -> y = x + gelu(LN2(conv1x1(gelu(LN1(dwconv(x))))))
+inline void fill_col_dds(const DConv& sep, const DLn& n1, const DConv& pw, const DLn& n2, const float* x, float* y, const Lvl& lv, ColLayerArgs& g) {
+    memset(&g, 0, sizeof(g));
+    g.x = x; g.x_ld = lv.ld;
+    g.dw_w = sep.w; g.dw_b = sep.bias; g.dw_k = sep.k; g.dw_dil = sep.dil; g.dw_pad = sep.pad; g.dw_ld = sep.Cout_pad;
+    g.g1 = n1.g; g.b1 = n1.b;
+    g.wc = pw.wc; g.bias = pw.bias;
+    g.g2 = n2.g; g.b2 = n2.b; g.post_gelu = 1;
+    g.res = x; g.res_ld = lv.ld; g.y = y; g.y_ld = lv.ld; g.C = pw.Cin;
+    g.seg = lv.seg; g.B = lv.nb; g.max_len = lv.max_len;
+}
+// ... with the ConvFlow's 1 -> C input conv folded in: h = (w r + b) + g is the layer's input and residual; x = res = g, the rank-1 term
+// from the conv's single input row (pre_in == null: the all-zero latent)
+inline void fill_col_pre(const DConv& pre, const float* pre_in, const float* pre_res, ColLayerArgs& g) {
+    g.x = pre_res; g.res = pre_res; g.xs_w = pre.w; g.xs_b = pre.bias; g.xr = pre_in;
+}
+// ... with the 29-row projection and the reverse spline step behind the layer
+inline void fill_col_tail(const DConv& proj, float filter_sqrt, const float* r0, const float* r1, float* o0, float* o1, ColLayerArgs& g) {
+    g.tp_w = proj.w; g.tp_b = proj.bias; g.tp_fs = filter_sqrt;
+    g.tp_r0 = r0; g.tp_r1 = r1; g.tp_o0 = o0; g.tp_o1 = o1;
+}
+// The attention output projection with its residual and LayerNorm: y = LN(add + conv1x1(x))
+inline void fill_col_oproj(const DConv& o, const DLn& n, const float* x, const float* add, float* y, const Lvl& lv, ColLayerArgs& g) {
+    memset(&g, 0, sizeof(g));
+    g.x = x; g.x_ld = lv.ld; g.wc = o.wc; g.bias = o.bias;
+    g.add = add; g.add_ld = lv.ld; g.g2 = n.g; g.b2 = n.b; g.y = y; g.y_ld = lv.ld; g.C = o.Cin;
+    g.seg = lv.seg; g.B = lv.nb; g.max_len = lv.max_len;
+}
 
 struct ConvOpt {
     int in_act = 0; float slope = 0.f; int reflect = 0;

@@ -398,6 +398,13 @@ bool copy_raw(Store& st, const float* src, size_t n, const float** dptr) {
     return true;
 }
 
+// The copies of a column-block layer's convs (col_layer.hip) as the loader makes them -- parse_pack_dds, parse_pack_convflow and
+// load_col_layer (the kernel-level entry sts_debug_col_layer) all pack through these.  sep: a DDSConv layer's depthwise conv, [k][C];
+// pw: its 1x1 conv, plain and in the A-strip order; the ConvFlow's 1 -> C input conv and its C -> 29 projection are plain convs ([C][32])
+bool pack_dds_sep(Store& st, const HConv& h, DConv& d) { PackOpts o; o.depthwise = true; return pack_conv(st, h, o, d); }
+bool pack_dds_pw(Store& st, const HConv& h, DConv& d) { return pack_conv(st, h, PackOpts(), d) && pack_col(st, h, d); }
+bool pack_flow_conv(Store& st, const HConv& h, DConv& d) { return pack_conv(st, h, PackOpts(), d); }
+
 // /root/reference/src/modules/DDSConv.cpp:29-59 (header pad/dil of the depthwise convs are overridden)
 bool parse_pack_dds(Reader& r, Store& st, DDds& d) {
     d.n = r.geti(); const int k = r.geti();
@@ -407,11 +414,10 @@ bool parse_pack_dds(Reader& r, Store& st, DDds& d) {
     for (int i = 0; i < d.n; i++) {
         HConv h = parse_conv(r); if (!r.ok) return false;
         h.pad = (int)floor((float)(k * dil - dil) / 2.0); h.dil = dil;
-        PackOpts o; o.depthwise = true;
-        if (!pack_conv(st, h, o, d.sep[i])) return false;
+        if (!pack_dds_sep(st, h, d.sep[i])) return false;
         dil *= k;
     }
-    for (int i = 0; i < d.n; i++) { HConv h = parse_conv(r); if (!r.ok || !pack_conv(st, h, PackOpts(), d.pw[i]) || !pack_col(st, h, d.pw[i])) return false; }
+    for (int i = 0; i < d.n; i++) { HConv h = parse_conv(r); if (!r.ok || !pack_dds_pw(st, h, d.pw[i])) return false; }
     for (int i = 0; i < d.n; i++) { HLn h = parse_ln(r); if (!r.ok || !pack_ln(st, h, d.n1[i])) return false; }
     for (int i = 0; i < d.n; i++) { HLn h = parse_ln(r); if (!r.ok || !pack_ln(st, h, d.n2[i])) return false; }
     return true;
@@ -424,9 +430,9 @@ void skip_dds(Reader& r) {
 
 // /root/reference/src/modules/ConvFlow.cpp:37-41
 bool parse_pack_convflow(Reader& r, Store& st, DConvFlow& c) {
-    HConv pre = parse_conv(r); if (!r.ok || !pack_conv(st, pre, PackOpts(), c.pre)) return false;
+    HConv pre = parse_conv(r); if (!r.ok || !pack_flow_conv(st, pre, c.pre)) return false;
     if (!parse_pack_dds(r, st, c.dds)) return false;
-    HConv proj = parse_conv(r); if (!r.ok || !pack_conv(st, proj, PackOpts(), c.proj)) return false;
+    HConv proj = parse_conv(r); if (!r.ok || !pack_flow_conv(st, proj, c.proj)) return false;
     c.filter = pre.out_ch;
     return proj.out_ch == 29;
 }
@@ -683,6 +689,31 @@ bool load_resblock_layer(const HConv* c1, const HConv* c2, int n, Model& m) {
         if (!pack_resblock_conv(st, c1[j], false, m.rb[j].c1[0])) FAIL("resblock convs1");
         if (!pack_resblock_conv(st, c2[j], true, m.rb[j].c2[0])) FAIL("resblock convs2");
     }
+    { const float* slack; if (!st.alloc(1024, &slack)) FAIL("weight store overflow"); }   // kernels may read one row tile past a tensor
+    m.dev_floats = st.used;
+    if (!st.commit()) FAIL("mapping device memory behind the weight store failed");
+    m.dev_mapped = st.mapped; m.dev_handle = st.vmm ? (void*)st.handle : nullptr;
+    if (hipMemcpy(st.dev, st.host.data(), st.used * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) FAIL("weight upload failed");
+    return true;
+}
+
+bool load_col_layer(const HConv* pre, const HConv* sep, const HLn* n1, const HConv& pw, const HLn& n2, const HConv* proj, Model& m) {
+    size_t floats = (size_t)pw.out_ch * pw.in_ch + 8 * (size_t)pw.out_ch + 64 * 8;
+    if (sep) floats += (size_t)sep->out_ch * sep->k;
+    if (proj) floats += (size_t)proj->out_ch * proj->in_ch;
+    Store st;
+    if (!st.init(floats)) FAIL("allocation of the weight store failed");
+    m.dev_weights = st.dev; m.dev_vmm = st.vmm; m.dev_reserved = st.reserved;
+    m.cf.assign(1, DConvFlow());
+    DConvFlow& c = m.cf[0];
+    c.dds.n = 1; c.dds.sep.resize(1); c.dds.pw.resize(1); c.dds.n1.resize(1); c.dds.n2.resize(1);
+    if (pre && !pack_flow_conv(st, *pre, c.pre)) FAIL("pre conv");
+    if (sep && !pack_dds_sep(st, *sep, c.dds.sep[0])) FAIL("depthwise conv");
+    if (!pack_dds_pw(st, pw, c.dds.pw[0])) FAIL("1x1 conv");
+    if (n1 && !pack_ln(st, *n1, c.dds.n1[0])) FAIL("first LayerNorm");
+    if (!pack_ln(st, n2, c.dds.n2[0])) FAIL("second LayerNorm");
+    if (proj && !pack_flow_conv(st, *proj, c.proj)) FAIL("projection");
+    c.filter = pw.in_ch;
     { const float* slack; if (!st.alloc(1024, &slack)) FAIL("weight store overflow"); }   // kernels may read one row tile past a tensor
     m.dev_floats = st.used;
     if (!st.commit()) FAIL("mapping device memory behind the weight store failed");

@@ -103,6 +103,11 @@ bool load_model(const float* blob, int64_t nfloats, Model& m);
 // The convs of ONE ResBlock1 layer of n chains (c1[j], c2[j]: conv1 and conv2 of chain j) through the packers, in the order, load_model packs a
 // ResBlock's convs with, into a store of their own: m.rb[j].c1[0] / c2[0].  For the kernel-level entry sts_debug_resblock_layer; freed by free_model.
 bool load_resblock_layer(const HConv* c1, const HConv* c2, int n, Model& m);
+// ONE column-block layer (col_layer.hip) through the packers parse_pack_dds / parse_pack_convflow pack a ConvFlow's convs with, into a
+// store of their own: m.cf[0].pre (the 1 -> C input conv, optional), .dds.sep[0] (depthwise conv, optional), .dds.n1[0] (optional),
+// .dds.pw[0] (the 1x1 conv and its A-strip copy), .dds.n2[0], .proj (C -> 29, optional).  For the kernel-level entry sts_debug_col_layer;
+// freed by free_model.
+bool load_col_layer(const HConv* pre, const HConv* sep, const HLn* n1, const HConv& pw, const HLn& n2, const HConv* proj, Model& m);
 void free_model(Model& m);
 
 }  // namespace sts

@@ -297,6 +297,9 @@ def load_library() -> C.CDLL:
     lib.sts_debug_resblock_layer.argtypes = [C.c_int, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p,
                                              C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_int, C.c_int, C.c_void_p,
                                              C.c_int32, C.POINTER(C.c_uint32)]
+    lib.sts_debug_col_layer.argtypes = ([C.c_int, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int64] + [C.c_void_p] * 5 + [C.c_int32] * 3 +
+                                        [C.c_void_p] * 7 + [C.c_int32] * 2 + [C.c_void_p] * 2 + [C.c_float] + [C.c_void_p] * 2 + [C.c_int32] +
+                                        [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p])
     lib.sts_pool_submit_gain.restype = C.c_int64
     lib.sts_pool_submit_gain.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_float, C.c_uint64, C.c_void_p]
     lib.sts_join_check.argtypes = [C.c_int32, C.c_void_p]
@@ -378,7 +381,7 @@ EXPORTED_SYMBOLS = [
     "sts_multi_set_speaker_mix",
     "sts_set_gain_plan", "sts_gain_plan_check", "sts_gain_design", "sts_gain_plan_apply", "sts_pool_submit_gain",
     "sts_multi_set_gain_plan",
-    "sts_debug_spline_step", "sts_debug_attention", "sts_debug_layer_norm", "sts_debug_resblock_layer",
+    "sts_debug_spline_step", "sts_debug_attention", "sts_debug_layer_norm", "sts_debug_resblock_layer", "sts_debug_col_layer",
     "sts_join_check", "sts_join_layout", "sts_join_apply", "sts_infer_ids_joined", "sts_get_join_offsets", "sts_pool_submit_joined",
     "sts_infer_ids_joined_stream", "sts_join_apply_range",
     "sts_set_eq", "sts_get_eq", "sts_eq_check", "sts_eq_design", "sts_eq_apply", "sts_pool_set_eq", "sts_multi_set_eq",
@@ -686,6 +689,56 @@ def debug_resblock_layer(x, lengths, members, slope: float, kind: int, variant: 
                                              y.shape[1], C.byref(ovf)))
     del keep
     return y, ovf.value
+
+
+COL_LAYER_ALIASES = {0: "none", 1: "y = x", 2: "o0 = r0", 3: "o0 = r1", 4: "o1 = r1", 5: "o1 = r0"}
+
+
+def debug_col_layer(x, lengths, w, g2, b2, bias=None, add=None, post_gelu: bool = False, use_res: bool = False, xs_w=None, xs_b=None, xr=None,
+                    dw_w=None, dw_b=None, dw_dil: int = 1, dw_pad: int = 0, dw_k=None, g1=None, b1=None, tp_w=None, tp_b=None,
+                    tp_fs: float = 1.0, tp_r0=None, tp_r1=None, alias: int = 0, device: int = 0, extra_rows: int = 0, out=None):
+    """One launch of the fused column-block layer on caller data (sts_debug_col_layer; include/summertts_hip.h states the forms): ``x``
+    float32 [C][ld], the utterances of ``lengths`` packed back to back from column 0 (sum(lengths) <= ld); ``w`` [C][C] in [out][in] order;
+    ``add`` None or [C][ld]; ``xs_w`` / ``xs_b`` [C] and ``xr`` [ld] the folded rank-1 input; ``dw_w`` [k][C] (``dw_k`` overrides the tap
+    count handed to the entry: the refusal tests); ``tp_w`` [29][C], ``tp_b`` [29], ``tp_r0`` / ``tp_r1`` [ld] the tail.  What
+    col_layer_eligible refuses raises StsError (STS_EINVAL).  ``out``: None, or (y, o0, o1) float32 arrays [C + extra_rows][ld], [ld], [ld]
+    to write into (a refused call leaves them as they were).
+    -> (y [C + extra_rows][ld], o0 [ld] or None, o1 [ld] or None), whole, from device buffers that started out as the word 0xFFFFFFFF."""
+    lib = load_library()
+    x = np.ascontiguousarray(x, dtype=np.float32)
+    lens = np.ascontiguousarray(lengths, dtype=np.int32).ravel()
+    if x.ndim != 2 or lens.size < 1 or int(lens.sum()) > x.shape[1]:
+        raise ValueError("x is [C][ld] with sum(lengths) <= ld")
+    Cc, ld = x.shape
+    opt = lambda v, shape, what: None if v is None else _f32(v, shape, what)
+    w = _f32(w, (Cc, Cc), "w")
+    g1, b1, g2, b2 = opt(g1, (Cc,), "g1"), opt(b1, (Cc,), "b1"), opt(g2, (Cc,), "g2"), opt(b2, (Cc,), "b2")
+    bias, add = opt(bias, (Cc,), "bias"), opt(add, (Cc, ld), "add")
+    xs_w, xs_b, xr = opt(xs_w, (Cc,), "xs_w"), opt(xs_b, (Cc,), "xs_b"), opt(xr, (ld,), "xr")
+    kk = 0
+    if dw_w is not None:
+        dw_w = np.ascontiguousarray(dw_w, dtype=np.float32)
+        if dw_w.ndim != 2 or dw_w.shape[1] != Cc:
+            raise ValueError("dw_w is [k][C]")
+        kk = dw_w.shape[0] if dw_k is None else int(dw_k)
+        if kk > dw_w.shape[0]:
+            raise ValueError("dw_k counts rows of dw_w")
+    dw_b = opt(dw_b, (Cc,), "dw_b")
+    tp_w, tp_b = opt(tp_w, (29, Cc), "tp_w"), opt(tp_b, (29,), "tp_b")
+    tp_r0, tp_r1 = opt(tp_r0, (ld,), "tp_r0"), opt(tp_r1, (ld,), "tp_r1")
+    if out is None:
+        y, o0, o1 = np.zeros((Cc + int(extra_rows), ld), np.float32), np.zeros(ld, np.float32), np.zeros(ld, np.float32)
+    else:
+        y, o0, o1 = out
+        if (y.dtype, o0.dtype, o1.dtype) != (np.float32,) * 3 or not (y.flags.c_contiguous and o0.flags.c_contiguous and o1.flags.c_contiguous) \
+                or y.shape != (Cc + int(extra_rows), ld) or o0.shape != (ld,) or o1.shape != (ld,):
+            raise ValueError("out is (y [C + extra_rows][ld], o0 [ld], o1 [ld]), contiguous float32")
+    ptr = lambda v: None if v is None else v.ctypes.data
+    _check(lib, lib.sts_debug_col_layer(int(device), x.ctypes.data, Cc, lens.ctypes.data, lens.size, ld, ptr(xs_w), ptr(xs_b), ptr(xr), ptr(dw_w),
+                                        ptr(dw_b), kk, int(dw_dil), int(dw_pad), ptr(g1), ptr(b1), w.ctypes.data, ptr(bias), ptr(add), ptr(g2),
+                                        ptr(b2), int(bool(post_gelu)), int(bool(use_res)), ptr(tp_w), ptr(tp_b), float(tp_fs), ptr(tp_r0),
+                                        ptr(tp_r1), int(alias), y.ctypes.data, y.shape[0], o0.ctypes.data, o1.ctypes.data))
+    return (y, o0, o1) if tp_w is not None else (y, None, None)
 
 
 def duration_fit(w, fixed=None, target_frames: int = 0) -> np.ndarray:

@@ -32,8 +32,8 @@ def test_new_symbols_are_exported_declared_and_listed(lib):
         assert hasattr(lib, s), s
         assert s in engine.EXPORTED_SYMBOLS, s
         assert s in declared, s
-    assert lib.sts_abi_version() == 17
-    assert int(re.search(r"#define STS_ABI_VERSION (\d+)", hdr).group(1)) == 17
+    assert lib.sts_abi_version() == 18
+    assert int(re.search(r"#define STS_ABI_VERSION (\d+)", hdr).group(1)) == 18
     for name, val in (("MAX_BANDS", 4), ("PEAK", 1), ("LOWSHELF", 2), ("HIGHSHELF", 3), ("HIGHPASS", 4), ("LOWPASS", 5)):
         assert int(re.search(r"#define STS_EQ_%s (\d+)" % name, hdr).group(1)) == val == getattr(engine, "EQ_" + name) == getattr(eq_ref, name)
 

@@ -40,7 +40,7 @@ def test_new_symbols_are_exported_declared_and_listed(lib):
         assert hasattr(lib, s), s
         assert s in engine.EXPORTED_SYMBOLS, s
         assert s in declared, s
-    assert lib.sts_abi_version() == 17 == int(re.search(r"#define STS_ABI_VERSION (\d+)", hdr).group(1))
+    assert lib.sts_abi_version() == 18 == int(re.search(r"#define STS_ABI_VERSION (\d+)", hdr).group(1))
 
 
 def test_python_argtypes_match_the_header(lib):

@@ -24,7 +24,7 @@ def test_symbols_are_in_the_library_the_list_and_the_header():
         assert s in engine.EXPORTED_SYMBOLS, s
         assert re.search(r"\b" + s + r"\s*\(", header), s
     assert "typedef struct sts_gain_plan" in header
-    assert lib.sts_abi_version() == 17 and "#define STS_ABI_VERSION 17" in header
+    assert lib.sts_abi_version() == 18 and "#define STS_ABI_VERSION 18" in header
     assert C.sizeof(engine.Profile) == 200                      # sts_profile did not grow
 
 

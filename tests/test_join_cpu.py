@@ -37,7 +37,7 @@ def test_symbols_are_in_the_library_the_list_and_the_header():
 
 def test_the_abi_version_is_still_15():
     lib = engine.load_library()
-    assert lib.sts_abi_version() == 17 and "#define STS_ABI_VERSION 17" in _header()
+    assert lib.sts_abi_version() == 18 and "#define STS_ABI_VERSION 18" in _header()
     assert C.sizeof(engine.Profile) == 200                      # sts_profile did not grow
 
 

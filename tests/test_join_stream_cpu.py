@@ -29,7 +29,7 @@ def test_both_symbols_are_exported_and_declared():
     hdr = open(os.path.join(ROOT, "include", "summertts_hip.h")).read()
     for s in ("sts_infer_ids_joined_stream", "sts_join_apply_range"):
         assert hasattr(lib, s) and s in engine.EXPORTED_SYMBOLS and ("int %s(" % s) in hdr, s
-    assert lib.sts_abi_version() == 17 and "#define STS_ABI_VERSION 17\n" in hdr
+    assert lib.sts_abi_version() == 18 and "#define STS_ABI_VERSION 18\n" in hdr
     assert "Out of scope: a streaming form" not in hdr
     assert hasattr(engine.Synthesizer, "infer_joined_stream") and hasattr(engine, "join_apply_range")
 

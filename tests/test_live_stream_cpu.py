@@ -36,7 +36,7 @@ def test_new_symbols_are_exported_declared_and_listed(lib):
         assert hasattr(lib, s), s
         assert s in engine.EXPORTED_SYMBOLS, s
         assert s in declared, s
-    assert lib.sts_abi_version() == 17 == int(re.search(r"#define STS_ABI_VERSION (\d+)", hdr).group(1))
+    assert lib.sts_abi_version() == 18 == int(re.search(r"#define STS_ABI_VERSION (\d+)", hdr).group(1))
     assert re.search(r"typedef struct sts_stream_noise \{ float noise_scale, noise_scale_w; uint64_t seed; \} sts_stream_noise;", hdr)
     assert C.sizeof(engine.StreamNoise) == 16 and [n for n, _ in engine.StreamNoise._fields_] == ["noise_scale", "noise_scale_w", "seed"]
     # no error code was added

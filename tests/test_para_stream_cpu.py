@@ -37,7 +37,7 @@ def test_the_entries_are_exported_declared_and_mirrored():
     hdr = open(os.path.join(ROOT, "include", "summertts_hip.h")).read()
     for s in SYMBOLS:
         assert hasattr(lib, s) and s in engine.EXPORTED_SYMBOLS and ("int %s(" % s) in hdr, s
-    assert lib.sts_abi_version() == 17 and "#define STS_ABI_VERSION 17\n" in hdr
+    assert lib.sts_abi_version() == 18 and "#define STS_ABI_VERSION 18\n" in hdr
     for m in ("para_open", "para_append", "para_finish", "para_step", "para_info", "para_close", "stream_paragraph"):
         assert hasattr(engine.Synthesizer, m), m
     assert [len(getattr(lib, s).argtypes) for s in SYMBOLS] == [6, 10, 2, 4, 10, 1]

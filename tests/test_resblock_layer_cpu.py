@@ -107,7 +107,7 @@ def test_entry_is_exported_declared_and_bound():
     assert re.search(r"\bint sts_debug_resblock_layer\(int device, const float\* x, int32_t C, const int32_t\* lengths, int32_t B, int64_t ld, int32_t n,", hdr)
     assert hasattr(lib, "sts_debug_resblock_layer") and "sts_debug_resblock_layer" in engine.EXPORTED_SYMBOLS
     assert len(lib.sts_debug_resblock_layer.argtypes) == 20
-    assert lib.sts_abi_version() == 17 and "#define STS_ABI_VERSION 17\n" in hdr
+    assert lib.sts_abi_version() == 18 and "#define STS_ABI_VERSION 18\n" in hdr
 
 
 def test_entry_argument_checks_need_no_gpu():

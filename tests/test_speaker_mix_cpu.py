@@ -34,7 +34,7 @@ def _arg_count(name, src):
 
 def test_surface_and_an_abi_that_did_not_grow(lib, tmp_path):
     src = open(HEADER).read()
-    assert re.search(r"#define STS_ABI_VERSION (\d+)", src).group(1) == "17" and lib.sts_abi_version() == 17
+    assert re.search(r"#define STS_ABI_VERSION (\d+)", src).group(1) == "18" and lib.sts_abi_version() == 18
     code = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
     for name, nargs in NEW:
         assert hasattr(lib, name) and name in engine.EXPORTED_SYMBOLS, name

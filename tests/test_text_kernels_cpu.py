@@ -139,7 +139,7 @@ def test_debug_entries_are_declared_bound_and_check_their_arguments():
     for name, nargs in (("sts_debug_attention", 16), ("sts_debug_layer_norm", 20)):
         assert hasattr(lib, name) and name in engine.EXPORTED_SYMBOLS and len(getattr(lib, name).argtypes) == nargs
         assert "`%s`" % name in open(os.path.join(ROOT, "INTEGRATION.md")).read()
-    assert lib.sts_abi_version() == 17 and "#define STS_ABI_VERSION 17\n" in hdr
+    assert lib.sts_abi_version() == 18 and "#define STS_ABI_VERSION 18\n" in hdr
     z = np.zeros((10, 8), np.float32)
     with pytest.raises(ValueError):
         engine.debug_attention(z, z, z, None, None, 3, 0, [8])                 # 10 rows, 3 heads
