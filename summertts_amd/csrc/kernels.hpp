@@ -250,6 +250,9 @@ void conv_bf3_group(const ConvGroup& G, hipStream_t st, int tile = -1);
 // math 1: the two-term fp16 form of the same layout (three planes P0 / P1 / P2, conv_bf3.hip MATH 1); *wscale receives the inverse
 // of the power of two the weights were scaled by
 size_t bf3_pack(const float* wp, int nphase, int ntap, int Cin_pad, int Cout_pad, void* dst, bool perm_k = false, int math = 0, float* wscale = nullptr);
+// slack behind a packed weight tensor, zero-filled: the kernels' unconditional prefetches run one step past the end.  Floats behind an fp32
+// copy and behind the split copies the loader makes of it, bytes behind a pre-split (conv_h2p.hip / conv_h2w.hip) copy and behind a lone wb3
+constexpr size_t kWeightSlackFloats = 1024, kPresplitSlackBytes = 8192, kBf3SlackBytes = 4096;
 // one ResBlock1 layer on the bf16 matrix cores: x + conv2(lrelu(conv1_dilated(lrelu(x)))), whole input window staged once
 bool resblock_bf3_eligible(const ResLayerGroup& G);
 void resblock_bf3(const ResLayerGroup& G, hipStream_t st, int variant = -1);

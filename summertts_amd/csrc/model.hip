@@ -9,6 +9,66 @@
 
 namespace sts {
 
+// ---- the layouts of the fp32 copies, host to host (model.hpp): what the packers below fill their store with
+// packed row -> source row for the gate pairing: every 32-row MFMA tile holds 16 tanh rows followed by the 16 sigmoid
+// rows of the SAME channels, so that one accumulator tile carries complete (t, s) pairs in each lane (rows r and r + 16
+// of a 32x32 tile live in the same lane) and a 32-row tile is a legal unit of work for the gated conv
+static int gate_perm_row(int pr, int H) {
+    int g = pr / 32, r = pr % 32;
+    return r < 16 ? g * 16 + r : H + g * 16 + (r - 16);
+}
+
+void conv_layout(const HConv& h, const PackOpts& o, int Cin_pad, int Cout_pad, float* w, float* b) {
+    const int rows = o.out_rows > 0 ? o.out_rows : h.out_ch, Cin = o.depthwise ? 1 : h.in_ch;
+    const bool perm = o.gate && (o.gate_H % 16 == 0);
+    auto src_row = [&](int pr) -> int {
+        if (pr >= rows) return -1;
+        if (o.reverse_out) return rows - 1 - pr;
+        if (perm) return gate_perm_row(pr, o.gate_H);
+        if (o.gate_blocks && o.gate_H % 16 == 0) {
+            int blk = pr / (2 * o.gate_H), within = pr % (2 * o.gate_H);
+            return blk * 2 * o.gate_H + gate_perm_row(within, o.gate_H);
+        }
+        return pr;
+    };
+    for (int pr = 0; pr < Cout_pad; pr++) {
+        const int sr = src_row(pr);
+        if (sr < 0) continue;
+        if (b) b[pr] = h.b[sr];
+        for (int t = 0; t < h.k; t++) {
+            if (o.depthwise) { w[(size_t)t * Cout_pad + pr] = h.w[(size_t)sr * h.k + t]; continue; }
+            for (int ci = 0; ci < Cin; ci++) {
+                const int cs = o.reverse_in ? Cin - 1 - ci : ci;
+                w[((size_t)t * Cin_pad + ci) * Cout_pad + pr] = h.w[((size_t)sr * h.k + t) * h.in_ch + cs];
+            }
+        }
+    }
+}
+
+void convT_layout(const HConv& h, int stride, int Cin_pad, int Cout_pad, float* w) {
+    const int J = (h.k + stride - 1) / stride;
+    for (int ph = 0; ph < stride; ph++)
+        for (int j = 0; j < J; j++) {
+            const int kk = ph + j * stride;
+            if (kk >= h.k) continue;
+            for (int ci = 0; ci < h.in_ch; ci++)
+                for (int co = 0; co < h.out_ch; co++)
+                    w[(((size_t)ph * J + j) * Cin_pad + ci) * Cout_pad + co] = h.w[((size_t)co * h.k + kk) * h.in_ch + ci];
+        }
+}
+
+void rowph_layout(const float* wh, const float* bh, int stride, int J, int Cin_pad, int Cout_pad, float* wr, float* br) {
+    const int rows = Cout_pad * stride;
+    for (int ph = 0; ph < stride; ph++)
+        for (int j = 0; j < J; j++)
+            for (int ci = 0; ci < Cin_pad; ci++) {
+                const float* src = wh + (((size_t)ph * J + j) * Cin_pad + ci) * Cout_pad;
+                float* dst = wr + ((size_t)j * Cin_pad + ci) * rows + ph;
+                for (int co = 0; co < Cout_pad; co++) dst[(size_t)co * stride] = src[co];
+            }
+    if (bh) for (int r = 0; r < rows; r++) br[r] = bh[r / stride];
+}
+
 namespace {
 
 struct Reader {
@@ -134,14 +194,6 @@ struct Store {
     }
 };
 
-// packed row -> source row for the gate pairing: every 32-row MFMA tile holds 16 tanh rows followed by the 16 sigmoid
-// rows of the SAME channels, so that one accumulator tile carries complete (t, s) pairs in each lane (rows r and r + 16
-// of a 32x32 tile live in the same lane) and a 32-row tile is a legal unit of work for the gated conv
-int gate_perm_row(int pr, int H) {
-    int g = pr / 32, r = pr % 32;
-    return r < 16 ? g * 16 + r : H + g * 16 + (r - 16);
-}
-
 bool pack_conv(Store& st, const HConv& h, const PackOpts& o, DConv& d) {
     const int rows = o.out_rows > 0 ? o.out_rows : h.out_ch;
     d = DConv();
@@ -155,35 +207,12 @@ bool pack_conv(Store& st, const HConv& h, const PackOpts& o, DConv& d) {
     d.H = o.gate_H;
     d.Cout_pad = round_up(rows, 32);
     d.macs_per_out = o.depthwise ? (double)rows * h.k : (double)d.Cin * rows * h.k;
-    auto src_row = [&](int pr) -> int {
-        if (pr >= rows) return -1;
-        if (o.reverse_out) return rows - 1 - pr;
-        if (perm) return gate_perm_row(pr, o.gate_H);
-        if (o.gate_blocks && o.gate_H % 16 == 0) {
-            int blk = pr / (2 * o.gate_H), within = pr % (2 * o.gate_H);
-            return blk * 2 * o.gate_H + gate_perm_row(within, o.gate_H);
-        }
-        return pr;
-    };
     const size_t wn = o.depthwise ? (size_t)h.k * d.Cout_pad : (size_t)h.k * d.Cin_pad * d.Cout_pad;
     float* w = st.alloc(wn, &d.w);
     if (!w) return false;
-    for (int pr = 0; pr < d.Cout_pad; pr++) {
-        const int sr = src_row(pr);
-        if (sr < 0) continue;
-        for (int t = 0; t < h.k; t++) {
-            if (o.depthwise) { w[(size_t)t * d.Cout_pad + pr] = h.w[(size_t)sr * h.k + t]; continue; }
-            for (int ci = 0; ci < d.Cin; ci++) {
-                const int cs = o.reverse_in ? d.Cin - 1 - ci : ci;
-                w[((size_t)t * d.Cin_pad + ci) * d.Cout_pad + pr] = h.w[((size_t)sr * h.k + t) * h.in_ch + cs];
-            }
-        }
-    }
-    if (h.has_bias == 1 && h.b) {
-        float* b = st.alloc(d.Cout_pad, &d.bias);
-        if (!b) return false;
-        for (int pr = 0; pr < d.Cout_pad; pr++) { const int sr = src_row(pr); if (sr >= 0) b[pr] = h.b[sr]; }
-    }
+    float* b = nullptr;
+    if (h.has_bias == 1 && h.b && !(b = st.alloc(d.Cout_pad, &d.bias))) return false;
+    conv_layout(h, o, d.Cin_pad, d.Cout_pad, w, b);
     return true;
 }
 
@@ -208,7 +237,7 @@ bool pack_bf3(Store& st, DConv& d, bool perm_k = false) {
     const int nphase = d.transposed ? d.stride : 1, ntap = d.transposed ? d.J : d.k;
     const size_t bytes = bf3_pack(nullptr, nphase, ntap, d.Cin_pad, d.Cout_pad, nullptr);
     const float* dptr = nullptr;
-    float* p = st.alloc((bytes + 3) / 4 + 1024, &dptr);     // + slack: unconditional prefetches run one step past the end
+    float* p = st.alloc((bytes + 3) / 4 + kWeightSlackFloats, &dptr);
     if (!p) return false;
     const float* wh = st.host.data() + (d.w - st.dev);
     bf3_pack(wh, nphase, ntap, d.Cin_pad, d.Cout_pad, p, perm_k);
@@ -216,7 +245,7 @@ bool pack_bf3(Store& st, DConv& d, bool perm_k = false) {
     // the two-term fp16 form of the same copy (conv math "f16x2"; same layout and size)
     const float* hptr = nullptr;
     const size_t hbytes = bf3_pack(nullptr, nphase, ntap, d.Cin_pad, d.Cout_pad, nullptr, false, 1);
-    float* q = st.alloc((hbytes + 3) / 4 + 1024, &hptr);
+    float* q = st.alloc((hbytes + 3) / 4 + kWeightSlackFloats, &hptr);
     if (!q) return false;
     bf3_pack(wh, nphase, ntap, d.Cin_pad, d.Cout_pad, q, perm_k, 1, &d.h2_scale);
     if (perm_k) d.wh2p = hptr; else d.wh2 = hptr;
@@ -228,22 +257,16 @@ bool pack_bf3_rowph(Store& st, DConv& d) {
     if (!d.transposed || !d.w || !d.wb3 || d.Cin != d.Cin_pad || d.Cout != d.Cout_pad || (d.stride != 2 && d.stride != 4 && d.stride != 8)) return true;
     const int s = d.stride, rows = d.Cout_pad * s;
     const float* wh = st.host.data() + (d.w - st.dev);        // [phase][J][Cin_pad][Cout_pad]
-    std::vector<float> wr((size_t)d.J * d.Cin_pad * rows);
-    for (int ph = 0; ph < s; ph++)
-        for (int j = 0; j < d.J; j++)
-            for (int ci = 0; ci < d.Cin_pad; ci++) {
-                const float* src = wh + (((size_t)ph * d.J + j) * d.Cin_pad + ci) * d.Cout_pad;
-                float* dst = wr.data() + ((size_t)j * d.Cin_pad + ci) * rows + ph;
-                for (int co = 0; co < d.Cout_pad; co++) dst[(size_t)co * s] = src[co];
-            }
+    std::vector<float> wr((size_t)d.J * d.Cin_pad * rows), br((size_t)rows, 0.f);
+    rowph_layout(wh, d.bias ? st.host.data() + (d.bias - st.dev) : nullptr, s, d.J, d.Cin_pad, d.Cout_pad, wr.data(), br.data());
     const size_t bytes = bf3_pack(nullptr, 1, d.J, d.Cin_pad, rows, nullptr);
     const float* dptr = nullptr;
-    float* p = st.alloc((bytes + 3) / 4 + 1024, &dptr);
+    float* p = st.alloc((bytes + 3) / 4 + kWeightSlackFloats, &dptr);
     if (!p) return false;
     bf3_pack(wr.data(), 1, d.J, d.Cin_pad, rows, p, false);
     const size_t hbytes = bf3_pack(nullptr, 1, d.J, d.Cin_pad, rows, nullptr, false, 1);
     const float* hptr = nullptr;
-    float* q = st.alloc((hbytes + 3) / 4 + 1024, &hptr);
+    float* q = st.alloc((hbytes + 3) / 4 + kWeightSlackFloats, &hptr);
     if (!q) return false;
     float sc = 1.0f;
     bf3_pack(wr.data(), 1, d.J, d.Cin_pad, rows, q, false, 1, &sc);
@@ -251,7 +274,7 @@ bool pack_bf3_rowph(Store& st, DConv& d) {
     const float* bptr = nullptr;
     float* b = st.alloc((size_t)rows, &bptr);
     if (!b) return false;
-    if (d.bias) { const float* bh = st.host.data() + (d.bias - st.dev); for (int r = 0; r < rows; r++) b[r] = bh[r / s]; }
+    memcpy(b, br.data(), sizeof(float) * rows);
     d.wb3r = dptr; d.wh2r = hptr; d.bias_r = bptr;
     return true;
 }
@@ -262,7 +285,7 @@ bool pack_h2p(Store& st, DConv& d) {
     if (d.wh2p || d.depthwise || d.transposed || !d.w || d.Cin != d.Cin_pad || d.Cout != d.Cout_pad || d.Cin != d.Cout || d.Cin % 128 != 0) return true;
     const float* hptr = nullptr;
     const size_t hbytes = bf3_pack(nullptr, 1, d.k, d.Cin_pad, d.Cout_pad, nullptr, true, 1);
-    float* q = st.alloc((hbytes + 3) / 4 + 2048, &hptr);
+    float* q = st.alloc((hbytes + 3) / 4 + kPresplitSlackBytes / 4, &hptr);
     if (!q) return false;
     const float* wh = st.host.data() + (d.w - st.dev);
     float sc = 1.0f;
@@ -297,7 +320,7 @@ bool pack_flow_fused(Store& st, DCoupling& c) {
         const DConv& gi = w.in[0];
         const size_t bytes = bf3_pack(nullptr, 1, gi.k, gi.Cin_pad, gi.Cout_pad, nullptr, true, 1);
         const float* dptr = nullptr;
-        float* p = st.alloc((bytes + 3) / 4 + 1024, &dptr);
+        float* p = st.alloc((bytes + 3) / 4 + kWeightSlackFloats, &dptr);
         if (!p) return false;
         bf3_pack(host(gi.w), 1, gi.k, gi.Cin_pad, gi.Cout_pad, p, true, 1, &f.gate0_scale);
         f.gate0 = dptr;
@@ -325,7 +348,7 @@ bool pack_flow_fused(Store& st, DCoupling& c) {
         if (brs) for (int cch = 0; cch < half; cch++) { double acc = 0.0; for (int j = 0; j < H; j++) acc += (double)wpost[(size_t)j * pcp + cch] * (double)brs[skip0 + j]; mb[cch] += acc; }
         const size_t bytes = bf3_pack(nullptr, 1, 1, H, rows_c, nullptr, true, 1);
         const float* dptr = nullptr;
-        float* p = st.alloc((bytes + 3) / 4 + 1024, &dptr);
+        float* p = st.alloc((bytes + 3) / 4 + kWeightSlackFloats, &dptr);
         if (!p) return false;
         bf3_pack(m.data(), 1, 1, H, rows_c, p, true, 1, &f.sc[l]);
         f.wc[l] = dptr; f.rows_c[l] = rows_c; f.rows_res[l] = rows_res;
@@ -367,14 +390,7 @@ bool pack_convT(Store& st, const HConv& h, int stride, int pad, DConv& d) {
     d.macs_per_out = (double)d.Cin * d.Cout * h.k;   // per INPUT position
     float* w = st.alloc((size_t)stride * d.J * d.Cin_pad * d.Cout_pad, &d.w);
     if (!w) return false;
-    for (int ph = 0; ph < stride; ph++)
-        for (int j = 0; j < d.J; j++) {
-            const int kk = ph + j * stride;
-            if (kk >= h.k) continue;
-            for (int ci = 0; ci < d.Cin; ci++)
-                for (int co = 0; co < d.Cout; co++)
-                    w[(((size_t)ph * d.J + j) * d.Cin_pad + ci) * d.Cout_pad + co] = h.w[((size_t)co * h.k + kk) * h.in_ch + ci];
-        }
+    convT_layout(h, stride, d.Cin_pad, d.Cout_pad, w);
     if (h.has_bias == 1 && h.b) {
         float* b = st.alloc(d.Cout_pad, &d.bias);
         if (!b) return false;

@@ -98,6 +98,16 @@ struct Model {
     std::string error;
 };
 
+// The layouts of the fp32 copies, host to host (the packers of model.hip allocate and call them; so do the kernel-level conv entries of
+// capi_debug.hip).  Destinations are zero-filled by the caller; b null: no bias.
+// [out][k][in] -> [k][Cin_pad][Cout_pad] (depthwise: [k][Cout_pad]) with o's row and channel mapping, bias in the same row order
+void conv_layout(const HConv& h, const PackOpts& o, int Cin_pad, int Cout_pad, float* w, float* b);
+// transposed conv, polyphase: phase p holds taps k = p + j stride -> [stride][J][Cin_pad][Cout_pad], J = ceil(k / stride)
+void convT_layout(const HConv& h, int stride, int Cin_pad, int Cout_pad, float* w);
+// polyphase copy wh (and its bias bh, or null) -> row-interleaved phases [J][Cin_pad][Cout_pad * stride], merged row = cout * stride + phase,
+// and the bias per merged row
+void rowph_layout(const float* wh, const float* bh, int stride, int J, int Cin_pad, int Cout_pad, float* wr, float* br);
+
 // Parses `blob`, repacks and uploads to the current HIP device.  Returns false and sets m.error on failure.
 bool load_model(const float* blob, int64_t nfloats, Model& m);
 // The convs of ONE ResBlock1 layer of n chains (c1[j], c2[j]: conv1 and conv2 of chain j) through the packers, in the order, load_model packs a

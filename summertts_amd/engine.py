@@ -470,29 +470,42 @@ def gain_design(gain_db, n: int, ramp_ms: float = 0.0):
     return q[:int(n)], h.value
 
 
+def _pack_signals(signals):
+    """Float signals as the stage entries take them -> (sig, x, lens, total): each signal as a flat float32 array, their concatenation (one
+    zero where there is no sample at all), their lengths (int64) and the lengths' sum."""
+    sig = [np.ascontiguousarray(s, dtype=np.float32).ravel() for s in signals]
+    lens = np.asarray([s.size for s in sig], np.int64)
+    total = int(lens.sum())
+    return sig, (np.concatenate(sig) if sig and total > 0 else np.zeros(1, np.float32)), lens, total
+
+
+def _split(packed, lens):
+    """A packed output buffer cut back into one copy per signal."""
+    off = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
+    return [packed[off[b]:off[b + 1]].copy() for b in range(len(lens))]
+
+
 def gain_plan_apply(signals, durations, plans, samples_per_frame: int, device: int = 0):
     """The gain-plan kernel on caller signals (sts_gain_plan_apply): ``durations`` a list of int arrays (frames per phoneme), one per
     utterance; ``signals[b]`` its float signal of ``max(1, sum d) * samples_per_frame`` samples; ``plans`` as
     ``Synthesizer.set_gain_plan`` takes them -> (y, pcm): lists of the gained float32 signals and their int16 casts."""
     lib = load_library()
     ds = [np.ascontiguousarray(d, dtype=np.int32).ravel() for d in durations]
-    sig = [np.ascontiguousarray(x, dtype=np.float32).ravel() for x in signals]
+    sig, x, _, _ = _pack_signals(signals)
     if len(sig) != len(ds):
         raise ValueError("one signal per utterance")
     lens = np.asarray([max(1, int(d.sum())) * int(samples_per_frame) for d in ds], np.int64)
-    for b, x in enumerate(sig):
-        if x.size != lens[b]:
+    for b, v in enumerate(sig):
+        if v.size != lens[b]:
             raise ValueError(f"signal {b} needs max(1, sum d) * samples_per_frame = {lens[b]} samples")
     nn, arr, keep = _gain_plans([d.size for d in ds], plans)
     total = int(lens.sum())
-    x = np.concatenate(sig) if sig else np.zeros(1, np.float32)
     d = np.concatenate(ds) if ds and sum(v.size for v in ds) else np.zeros(1, np.int32)
     y = np.zeros(max(total, 1), np.float32)
     pcm = np.zeros(max(total, 1), np.int16)
     _check(lib, lib.sts_gain_plan_apply(int(device), x.ctypes.data, d.ctypes.data, nn.ctypes.data, len(ds), int(samples_per_frame),
                                         C.cast(arr, C.c_void_p), y.ctypes.data, pcm.ctypes.data))
-    off = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
-    return [y[off[b]:off[b + 1]].copy() for b in range(len(ds))], [pcm[off[b]:off[b + 1]].copy() for b in range(len(ds))]
+    return _split(y, lens), _split(pcm, lens)
 
 
 def join_check(B: int, join) -> None:
@@ -521,15 +534,14 @@ def join_apply(signals, frames: Sequence[int], samples_per_frame: int, join=None
     (J, pcm): the joined float32 signal and its int16 cast."""
     lib = load_library()
     f = np.ascontiguousarray(frames, dtype=np.int32).ravel()
-    sig = [np.ascontiguousarray(x, dtype=np.float32).ravel() for x in signals]
+    sig, x, _, _ = _pack_signals(signals)
     if len(sig) != f.size:
         raise ValueError("one signal per sentence")
-    for b, x in enumerate(sig):
-        if x.size != int(f[b]) * int(samples_per_frame):
+    for b, v in enumerate(sig):
+        if v.size != int(f[b]) * int(samples_per_frame):
             raise ValueError(f"signal {b} needs frames * samples_per_frame = {int(f[b]) * int(samples_per_frame)} samples")
     _, total, _ = join_layout(f, samples_per_frame, join)
     jp, keep = _join(f.size, join)
-    x = np.concatenate(sig) if sig else np.zeros(1, np.float32)
     y = np.zeros(max(total, 1), np.float32)
     pcm = np.zeros(max(total, 1), np.int16)
     _check(lib, lib.sts_join_apply(int(device), x.ctypes.data, f.ctypes.data, f.size, int(samples_per_frame), jp, y.ctypes.data,
@@ -542,14 +554,13 @@ def join_apply_range(signals, frames: Sequence[int], samples_per_frame: int, fir
     n_frames)`` of the joined signal -> (J part, pcm part).  ``signals`` / ``frames`` / ``join`` as ``join_apply`` takes them."""
     lib = load_library()
     f = np.ascontiguousarray(frames, dtype=np.int32).ravel()
-    sig = [np.ascontiguousarray(x, dtype=np.float32).ravel() for x in signals]
+    sig, x, _, _ = _pack_signals(signals)
     if len(sig) != f.size:
         raise ValueError("one signal per sentence")
-    for b, x in enumerate(sig):
-        if x.size != int(f[b]) * int(samples_per_frame):
+    for b, v in enumerate(sig):
+        if v.size != int(f[b]) * int(samples_per_frame):
             raise ValueError(f"signal {b} needs frames * samples_per_frame = {int(f[b]) * int(samples_per_frame)} samples")
     jp, keep = _join(f.size, join)
-    x = np.concatenate(sig) if sig else np.zeros(1, np.float32)
     count = max(int(n_frames), 0) * int(samples_per_frame)
     y = np.zeros(max(count, 1), np.float32)
     pcm = np.zeros(max(count, 1), np.int16)
@@ -794,9 +805,7 @@ def loudness_measure(signals, rate: int, target_lufs: float = -16.0, peak_dbfs: 
     """Integrated loudness, sample peak and normalising gain of each float signal in ``signals`` at ``rate`` on the GPU (the engine's
     kernels, sts_loudness_measure) -> structured array of LOUDNESS_DTYPE, one entry per signal."""
     lib = load_library()
-    sig = [np.ascontiguousarray(s, dtype=np.float32).ravel() for s in signals]
-    lens = np.asarray([s.size for s in sig], np.int64)
-    x = np.concatenate(sig) if sig and lens.sum() > 0 else np.zeros(1, np.float32)
+    sig, x, lens, _ = _pack_signals(signals)
     out = np.zeros(len(sig), LOUDNESS_DTYPE)
     _check(lib, lib.sts_loudness_measure(int(device), x.ctypes.data, lens.ctypes.data, len(sig), int(rate), float(target_lufs),
                                          float(peak_dbfs), out.ctypes.data))
@@ -811,11 +820,9 @@ def loudness_measure_chunked(signals, rate: int, bounds, back: int = 0, target_l
     result as if the call had stopped behind step k (None unless ``want_partial``).  Both buffers carry a sentinel entry behind their
     end, which the library must leave alone."""
     lib = load_library()
-    sig = [np.ascontiguousarray(s, dtype=np.float32).ravel() for s in signals]
-    lens = np.asarray([s.size for s in sig], np.int64)
+    sig, x, lens, _ = _pack_signals(signals)
     bnd = np.ascontiguousarray(bounds, dtype=np.int64).ravel()
     K, B = int(bnd.size), len(sig)
-    x = np.concatenate(sig) if sig and lens.sum() > 0 else np.zeros(1, np.float32)
     sentinel = np.array([(-1234.5, -7.0, -9.0, -77)], LOUDNESS_DTYPE)
     out = np.repeat(sentinel, B + 1)
     part = np.repeat(sentinel, K * B + 1)
@@ -847,17 +854,13 @@ def limiter_apply(signals, rate: int, gain_db: float = 0.0, ceiling_dbfs: float 
     """The look-ahead limiter on each float signal in ``signals`` at ``rate`` on the GPU (the engine's kernel, sts_limiter_apply) ->
     (y, pcm, stats): lists of the limited float32 signals and their int16 casts, and a structured array of LIMITER_DTYPE."""
     lib = load_library()
-    sig = [np.ascontiguousarray(s, dtype=np.float32).ravel() for s in signals]
-    lens = np.asarray([s.size for s in sig], np.int64)
-    total = int(lens.sum())
-    x = np.concatenate(sig) if sig and total > 0 else np.zeros(1, np.float32)
+    sig, x, lens, total = _pack_signals(signals)
     y = np.zeros(max(total, 1), np.float32)
     pcm = np.zeros(max(total, 1), np.int16)
     stats = np.zeros(len(sig), LIMITER_DTYPE)
     _check(lib, lib.sts_limiter_apply(int(device), x.ctypes.data, lens.ctypes.data, len(sig), int(rate), float(gain_db), float(ceiling_dbfs),
                                       float(lookahead_ms), y.ctypes.data, pcm.ctypes.data, stats.ctypes.data))
-    off = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
-    return ([y[off[b]:off[b + 1]].copy() for b in range(len(sig))], [pcm[off[b]:off[b + 1]].copy() for b in range(len(sig))], stats)
+    return _split(y, lens), _split(pcm, lens), stats
 
 
 def eq_check(rate: int, bands) -> None:
@@ -884,16 +887,12 @@ def eq_apply(signals, rate: int, bands, device: int = 0, want_y: bool = True, wa
     caller's buffer started with (NaN / 0x7FFF)."""
     lib = load_library()
     n, arr = _eq_bands(bands)
-    sig = [np.ascontiguousarray(s, dtype=np.float32).ravel() for s in signals]
-    lens = np.asarray([s.size for s in sig], np.int64)
-    total = int(lens.sum())
-    x = np.concatenate(sig) if sig and total > 0 else np.zeros(1, np.float32)
+    sig, x, lens, total = _pack_signals(signals)
     y = np.full(max(total, 1), np.nan, np.float32)
     pcm = np.full(max(total, 1), 0x7FFF, np.int16)
     _check(lib, lib.sts_eq_apply(int(device), x.ctypes.data, lens.ctypes.data, len(sig), int(rate), n, arr,
                                  y.ctypes.data if want_y else None, pcm.ctypes.data if want_pcm else None))
-    off = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
-    return [y[off[b]:off[b + 1]].copy() for b in range(len(sig))], [pcm[off[b]:off[b + 1]].copy() for b in range(len(sig))]
+    return _split(y, lens), _split(pcm, lens)
 
 
 def eq_apply_chunked(signals, rate: int, bands, bounds, back: int = 0, device: int = 0):
@@ -904,9 +903,7 @@ def eq_apply_chunked(signals, rate: int, bands, bounds, back: int = 0, device: i
     starts as NaN / 0x7FFF."""
     lib = load_library()
     n, arr = _eq_bands(bands)
-    sig = [np.ascontiguousarray(s, dtype=np.float32).ravel() for s in signals]
-    lens = np.asarray([s.size for s in sig], np.int64)
-    total = int(lens.sum())
+    sig, x, lens, total = _pack_signals(signals)
     bnd = np.ascontiguousarray(bounds, dtype=np.int64).ravel()
     K, B = int(bnd.size), len(sig)
     wins = []                    # (k, b, start, stop) in the library's order
@@ -917,14 +914,12 @@ def eq_apply_chunked(signals, rate: int, bands, bounds, back: int = 0, device: i
             if N > c0:
                 wins.append((k, b, max(0, c0 - int(back)), N if c1 is None else min(N, c1 + int(back))))
     wtotal = sum(w[3] - w[2] for w in wins)
-    x = np.concatenate(sig) if sig and total > 0 else np.zeros(1, np.float32)
     y = np.full(max(total, 1), np.nan, np.float32)
     pcm = np.full(max(total, 1), 0x7FFF, np.int16)
     wy = np.full(wtotal + 1, np.nan, np.float32)
     woff = np.full(max(K * B, 1), -2, np.int64)
     _check(lib, lib.sts_eq_apply_chunked(int(device), x.ctypes.data, lens.ctypes.data, B, int(rate), n, arr, bnd.ctypes.data, K, int(back),
                                          y.ctypes.data, pcm.ctypes.data, wy.ctypes.data, wtotal, woff.ctypes.data))
-    off = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
     windows = [[None] * B for _ in range(K)]
     for k, b, a0, a1 in wins:
         o = int(woff[k * B + b])
@@ -933,7 +928,7 @@ def eq_apply_chunked(signals, rate: int, bands, bounds, back: int = 0, device: i
         windows[k][b] = (a0, wy[o:o + a1 - a0].copy())
     if not np.isnan(wy[wtotal]):
         raise StsError("sts_eq_apply_chunked wrote behind its windows")
-    return ([y[off[b]:off[b + 1]].copy() for b in range(B)], [pcm[off[b]:off[b + 1]].copy() for b in range(B)], windows)
+    return _split(y, lens), _split(pcm, lens), windows
 
 
 def resample_table(in_rate: int, out_rate: int):

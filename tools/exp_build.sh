@@ -17,7 +17,7 @@ O=summertts_amd/lib/obj
 OTHER=""; for f in conv conv_bf3 col_layer; do [ "$f" = "$X" ] || OTHER="$OTHER $O/$f.o"; done
 P=$([ "$X" = conv ] && echo exp || echo $X)
 for m in "$@"; do
-  /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o summertts_amd/lib/exp/lib$P$m.so summertts_amd/lib/exp/$X$m.o $OTHER $O/misc_kernels.o $O/model.o $O/engine.o $O/capi.o $O/pool.o $O/multi.o $O/synthesizer_trn.o -pthread
+  /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o summertts_amd/lib/exp/lib$P$m.so summertts_amd/lib/exp/$X$m.o $OTHER $O/misc_kernels.o $O/model.o $O/engine.o $O/capi.o $O/capi_apply.o $O/capi_debug.o $O/pool.o $O/multi.o $O/synthesizer_trn.o -pthread
   rm summertts_amd/lib/exp/$X$m.o
 done
 ls -la summertts_amd/lib/exp
