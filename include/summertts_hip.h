@@ -101,8 +101,9 @@ int sts_infer_ids_batch_stream(sts_engine* e, int32_t B, const int32_t* const* i
  *   sts_stream_open fixes the chunk size C = chunk_frames, the output rate, the limiter setting, the conv mode and the conv math, and
  *   allocates a latent pool of capacity_frames frames for at most max_live utterances at a time (1 <= max_live <= 1024;
  *   capacity_frames * inter_channels and capacity_frames * samples_per_frame at most 2 10^9).  STS_EINVAL while EQ bands are set, the
- *   loudness mode is not 0, record taps are on, or a duration plan, speaker mix, gain plan or forced durations are pending (those forms
- *   carry per-call tables or per-utterance filter state: opening them to admission is later work); STS_ESTATE when a stream is open.
+ *   loudness mode is not 0 or record taps are on (they need per-slot filter state: later work), or while a duration plan, speaker mix,
+ *   gain plan or forced durations are pending (a pending table belongs to a next run, and open is not a run); STS_ESTATE when a stream is
+ *   open.  sts_stream_open is the capacity_phonemes == 0 case of sts_stream_open_ex (below), which admits utterances WITH those tables.
  *   sts_stream_admit runs text encoder, duration predictor and flow of B newcomers as the packed batch a sts_infer_ids_batch_stream call
  *   of those B would, and moves their latents into the pool.  All or nothing: *admitted = B, or 0 when slots or frames do not suffice now
  *   (nothing has changed; retry after a retirement).  slot_out[b] = the slot of utterance b, the `utt` its chunks arrive with (-1: it has
@@ -118,7 +119,7 @@ int sts_infer_ids_batch_stream(sts_engine* e, int32_t B, const int32_t* const* i
  *   chunk callback.
  *   While a stream is open every other run entry of the engine and every setter of what open fixed (output rate, limiter, EQ, loudness,
  *   conv mode, conv math, plans, mixes, forced durations, record taps, the debug switches other than STS_DBG_STREAM_RETRY_STEP and
- *   STS_DBG_POISON) returns STS_ESTATE; sts_set_noise stays allowed.
+ *   STS_DBG_POISON) returns STS_ESTATE; sts_set_noise stays allowed.  (A planned stream, below, lets the four table setters through.)
  *   Equality: whatever the admission schedule, the list of chunks of every utterance and their sample offsets equal its
  *   sts_infer_ids_stream chunks with the same chunk_frames bit for bit when the kernel variant is pinned (sts_set_conv_mode), and its PCM
  *   is within 1 LSB of that under the automatic choice.
@@ -134,12 +135,45 @@ int sts_stream_admit(sts_engine* e, int32_t B, const int32_t* const* ids, const 
 int sts_stream_step(sts_engine* e, sts_batch_chunk_cb cb, void* user, int32_t* live_after);
 int sts_stream_info(const sts_engine* e, int32_t* open, int32_t* live, int32_t* free_slots, int64_t* free_frames, int64_t* steps);
 int sts_stream_close(sts_engine* e);
+/* Planned open streams: sts_stream_open_ex with capacity_phonemes in [1, 2^24] opens a stream whose admissions take the per-call tables of
+ * a closed stream.  capacity_phonemes == 0 is sts_stream_open exactly (same refusals, same setters refused while open, same bits);
+ * negative or larger: STS_EINVAL.  A planned stream refuses at open what sts_stream_open refuses (EQ bands, a loudness mode other than 0,
+ * record taps, and a plan, mix, gain plan or forced durations pending AT open).
+ *   While a planned stream is open sts_set_duration_plan, sts_set_speaker_mix, sts_set_gain_plan and sts_set_forced_durations return
+ *   STS_OK, and what they set applies to the NEXT sts_stream_admit only, whatever its outcome (one that finds no room, *admitted = 0, and
+ *   one that fails included).  That admission must have the B and n[b] the tables were set for: otherwise STS_EINVAL, nothing is admitted
+ *   and the tables are dropped.  A duration plan together with forced durations: STS_EINVAL, both dropped, as in a run.  The conv-math-3
+ *   repeat of an admission applies the same tables again.  Every other setter stays STS_ESTATE.
+ *   An admitted utterance carries: its planned durations (n_samples_out[b] and its chunks follow from them); its blended speaker vector,
+ *   through its last chunk; its gain plan -- an utterance whose sts_gain_plan entry has gain_db != NULL takes n[b] columns of a phoneme pool
+ *   of capacity_phonemes columns (first fit, returned when it retires), one without takes none.  Admission is all or nothing over slots,
+ *   frames AND phonemes.  A step runs the gain stage only when a live slot carries a gain plan; in such a step a slot without one keeps its
+ *   samples bit for bit.  Equality: every utterance's chunks equal those of sts_infer_ids_stream with the same tables set just before
+ *   it, under the terms of an unplanned stream.  After an admission sts_get_durations and sts_get_phoneme_offsets report the admitted
+ *   utterances, packed as after sts_infer_ids_batch_stream (so for a plain stream too).
+ *   Still refused or unsupported, as before: the EQ and loudness in an open stream (per-slot filter state, the next step), record taps,
+ *   plans in open paragraphs (sts_para_*) and sts_multi_*.
+ *   sts_stream_tables_info: any output may be NULL; *planned = 1 for an open planned stream, the pool's capacity and its free columns
+ *   (zeros otherwise).
+ *   These entries were added without a new STS_ABI_VERSION: detect them by symbol. */
+int sts_stream_open_ex(sts_engine* e, int32_t chunk_frames, int32_t max_live, int64_t capacity_frames, int64_t capacity_phonemes);
+int sts_stream_tables_info(const sts_engine* e, int32_t* planned, int64_t* capacity_phonemes, int64_t* free_phonemes);
 /* The kernel that moves an admission's latents into the pool, on caller data (host pointers in and out): B column segments of the
  * channel-major src [C][ld_src] into dst [C][ld_dst]; segment b is len[b] columns from src_off[b] to dst_off[b].  dst comes back with
  * every element outside the destination ranges unchanged.  Ranges outside either matrix, overlapping destination ranges, B outside
  * [1, 65535] or C < 1: STS_EINVAL. */
 int sts_debug_adopt_z(int device, const float* src, int32_t C, int64_t ld_src, float* dst, int64_t ld_dst, const int64_t* src_off,
                       const int64_t* dst_off, const int32_t* len, int32_t B);
+/* The kernel that moves an admission's tables into a planned stream's pools, on caller data (host pointers in and out).  For newcomer
+ * b < B with slot[b] >= 0: column b of g [gin][B] -> column slot[b] of gpool [gin][max_live] (gin 0: g and gpool NULL, nothing moves);
+ * n[b] > 0: cum[src_off[b] .. + n[b]) and q[..] (arrays of n_src entries) -> rows 0 and 1 of pool [2][capacity_phonemes + 1] at column
+ * dst_off[b], and the words of its slot in slot_words [3][max_live] (rows off | n | h) = {dst_off[b], n[b], h[b]}; n[b] == 0 (it carries
+ * no phonemes): its words = {capacity_phonemes, 1, 0}, the pool's shared neutral column.  slot[b] == -1: nothing.  gpool, pool and
+ * slot_words come back with everything else unchanged.  Ranges outside either array, overlapping destination ranges, a slot named
+ * twice or outside [-1, max_live), B outside [1, 65535]: STS_EINVAL. */
+int sts_debug_adopt_tables(int device, const float* g, int32_t gin, int32_t B, float* gpool, int32_t max_live, const int32_t* cum,
+                           const int32_t* q, int64_t n_src, int32_t* pool, int64_t capacity_phonemes, int32_t* slot_words,
+                           const int32_t* slot, const int32_t* src_off, const int32_t* n, const int32_t* dst_off, const int32_t* h);
 
 /* Batched form (new capability; the reference processes exactly one utterance per call).  The B
  * utterances are packed along time on the device and run through every kernel together.
@@ -709,7 +743,8 @@ enum { STS_DBG_ATTN_BLOCK_MIN_WGS = 1,
        STS_DBG_LAUNCH_AHEAD = 6 /* one-utterance calls and packed batches: 1 (default) a request the engine has served before (same ids, speaker, length scale: the frame count is a pure function of them) enqueues flow + decoder before the count reaches the host, 0 the host always waits for it, 2 (tests) the memo is keyed by the phoneme count alone -- provokes the repeat that answers a hash collision */,
        STS_DBG_FLOW_FUSED = 5 /* reverse flow: 1 (default) one launch per WaveNet layer (wn_flow.hip, under the two-term fp16 arithmetic) where the grid is one round of workgroups, with 16 output frames per workgroup where 32 would leave half the compute units without one; 0 one launch per conv; 2 / 3 (tests, A/B) one launch per layer at any size with 32 / 16 frames per workgroup -- 1, 2 and 3 return the same bits */ };
 /* ABI 10, sts_infer_ids_batch_stream: STS_DBG_STREAM_RETRY_STEP (tests) -- under conv math 3 the overflow word counts as raised after step k
- * (value k; -1 = off), which takes the split-bf16 repeat of that step (k > 0) or of the whole call (k = 0); STS_DBG_STREAM_DIRECT -- 1 the
+ * (value k; -1 = off), which takes the split-bf16 repeat of that step (k > 0) or of the whole call (k = 0); -2: it counts as raised in
+ * every sts_stream_admit instead, which takes the repeat of that admission; STS_DBG_STREAM_DIRECT -- 1 the
  * last kernel of a step writes the step's chunks into mapped pinned host memory itself, 0 (default) one download per step */
 enum { STS_DBG_STREAM_RETRY_STEP = 16, STS_DBG_STREAM_DIRECT = 17 };
 /* ABI 12, STS_DBG_POISON (tests): value = a 32-bit fill pattern, 0 = off (default).  While it is on, every call fills each workspace arena
@@ -760,6 +795,8 @@ int sts_set_profiling(sts_engine* e, int enable);
  * sizeof(sts_profile)) bytes, so a client compiled against an older header passes ITS sizeof and is never overrun;
  * sts_get_profile(e, p) == sts_get_profile_ex(e, p, sizeof(sts_profile)) of the header this library was built from -- use it only
  * when client and library are built together. */
+/* (Stays 18 with the planned open streams: sts_stream_open_ex, sts_stream_tables_info, sts_pool_submit_stream_ex and
+ * sts_debug_adopt_tables are additive and are detected by symbol, not by version.) */
 #define STS_ABI_VERSION 18
 int sts_abi_version(void);
 /* bit 0: lab build (-DSTS_EXPERIMENTS: environment knobs of knobs.hpp, every conv tile code);
@@ -960,6 +997,14 @@ int64_t sts_pool_submit_mix(sts_pool* p, const int32_t* ids, int32_t n, int32_t 
  *   with and without a plan share one packed batch: the plan is per utterance, and a member without one keeps its samples bit for bit. */
 int64_t sts_pool_submit_gain(sts_pool* p, const int32_t* ids, int32_t n, int32_t sid, float length_scale, float noise_scale,
                              float noise_scale_w, uint64_t seed, const sts_gain_plan* plan);
+/*   sts_pool_submit_stream_ex: sts_pool_submit_stream with this request's own duration plan, speaker mix and gain plan, each optional
+ *   (copied; validated at submit as sts_pool_submit_plan / _mix / _gain validate theirs: STS_EINVAL).  All three NULL is
+ *   sts_pool_submit_stream.  Planned and plain streaming requests of one chunk size share a group; with admission on
+ *   (sts_pool_set_stream_admission) the group is a planned open stream (sts_stream_open_ex) and a planned request is admitted into it
+ *   midstream like a plain one. */
+int64_t sts_pool_submit_stream_ex(sts_pool* p, const int32_t* ids, int32_t n, int32_t sid, float length_scale, float noise_scale,
+                                  float noise_scale_w, uint64_t seed, int32_t chunk_frames, sts_chunk_cb cb, void* user,
+                                  const sts_dur_plan* plan, const sts_speaker_mix* mix, const sts_gain_plan* gain);
 
 /*   sts_pool_submit_joined: a paragraph (sts_infer_ids_joined) as ONE request: one ticket, one PCM.  Sentence b samples with seed + b.  It
  *   runs as its own packed batch of B, whatever max_batch is, and is never folded with other requests; the pool's output rate, loudness

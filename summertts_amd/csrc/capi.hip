@@ -160,6 +160,20 @@ int sts_stream_open(sts_engine* e, int32_t chunk_frames, int32_t max_live, int64
     const int rc = e->eng.stream_open(chunk_frames, max_live, capacity_frames);
     return rc == STS_OK ? STS_OK : set_err(rc, e->eng.error());
 }
+int sts_stream_open_ex(sts_engine* e, int32_t chunk_frames, int32_t max_live, int64_t capacity_frames, int64_t capacity_phonemes) {
+    if (!e) return set_err(STS_EINVAL, "null engine");
+    if (capacity_phonemes < 0 || capacity_phonemes > (1 << 24)) return set_err(STS_EINVAL, "capacity_phonemes is 0 (sts_stream_open) or in [1, 2^24]");
+    const int rc = e->eng.stream_open(chunk_frames, max_live, capacity_frames, capacity_phonemes);
+    return rc == STS_OK ? STS_OK : set_err(rc, e->eng.error());
+}
+int sts_stream_tables_info(const sts_engine* e, int32_t* planned, int64_t* capacity_phonemes, int64_t* free_phonemes) {
+    if (!e) return set_err(STS_EINVAL, "null engine");
+    const LiveStream* L = e->eng.live_;
+    if (planned) *planned = L && L->planned() ? 1 : 0;
+    if (capacity_phonemes) *capacity_phonemes = L ? L->capacity_phonemes : 0;
+    if (free_phonemes) *free_phonemes = L ? L->free_phoneme_count() : 0;
+    return STS_OK;
+}
 int sts_stream_admit(sts_engine* e, int32_t B, const int32_t* const* ids, const int32_t* n, const int32_t* sid,
                      const float* length_scale, const sts_stream_noise* noise, int32_t* slot_out, int32_t* n_samples_out,
                      int32_t* admitted) {
@@ -242,7 +256,7 @@ int sts_stream_halo_frames(const sts_engine* e) {
 
 int sts_set_forced_durations(sts_engine* e, const int32_t* dur, int64_t count) {
     if (!e) return set_err(STS_EINVAL, "null engine");
-    STS_CAPI_NOT_WHILE_OPEN(e);
+    if (!(e->eng.live_ && e->eng.live_->planned())) STS_CAPI_NOT_WHILE_OPEN(e);     // (a planned open stream: for its next admission)
     if (!dur || count <= 0) { e->eng.have_forced = false; return STS_OK; }
     e->eng.forced_dur.assign(dur, dur + count);
     e->eng.have_forced = true;
@@ -406,7 +420,7 @@ int sts_debug_set(sts_engine* e, int key, int value) {
         case STS_DBG_ATTN_REG: e->eng.attn_reg = value != 0; return STS_OK;
         case STS_DBG_DDS_TAIL: e->eng.dds_tail = value != 0; return STS_OK;
         case STS_DBG_PCM_DIRECT: e->eng.pcm_direct = value != 0; return STS_OK;
-        case STS_DBG_STREAM_RETRY_STEP: e->eng.stream_retry_step = value < 0 ? -1 : value; return STS_OK;
+        case STS_DBG_STREAM_RETRY_STEP: e->eng.stream_retry_step = value == -2 ? -2 : (value < 0 ? -1 : value); return STS_OK;      // (-2: admissions, engine.hpp)
         case STS_DBG_STREAM_DIRECT: e->eng.stream_direct = value != 0; return STS_OK;
         case STS_DBG_POISON: e->eng.poison = (unsigned)value; return STS_OK;
         case STS_DBG_COL_PROJ: if (value < 0 || value > 3) return set_err(STS_EINVAL, "col_proj must be 0, 1, 2 or 3"); e->eng.col_proj_mode = value; return STS_OK;

@@ -301,6 +301,46 @@ int sts_debug_adopt_z(int device, const float* src, int32_t C, int64_t ld_src, f
     return d.finish() ? STS_OK : set_err(STS_EDEVICE, "the adoption launch failed on the device");
 }
 
+int sts_debug_adopt_tables(int device, const float* g, int32_t gin, int32_t B, float* gpool, int32_t max_live, const int32_t* cum,
+                           const int32_t* q, int64_t n_src, int32_t* pool, int64_t capacity_phonemes, int32_t* slot_words, const int32_t* slot,
+                           const int32_t* src_off, const int32_t* n, const int32_t* dst_off, const int32_t* h) {
+    if (!slot_words || !pool || !slot || !src_off || !n || !dst_off || !h || B < 1 || B > 65535 || max_live < 1 || max_live > (1 << 20) ||
+        gin < 0 || gin > (1 << 16) || (gin > 0) != (g != nullptr) || (gin > 0) != (gpool != nullptr) || n_src < 0 || n_src > (1 << 24) ||
+        capacity_phonemes < 1 || capacity_phonemes > (1 << 24))
+        return set_err(STS_EINVAL, "g [gin][B] and gpool [gin][max_live] (both null with gin 0), pool [2][capacity_phonemes + 1], slot_words [3][max_live], the five tables and 1 <= B <= 65535 are required");
+    std::vector<std::pair<int64_t, int64_t>> ranges;
+    std::vector<char> taken((size_t)max_live, 0);
+    int max_n = 0;
+    for (int b = 0; b < B; b++) {
+        if (slot[b] < -1 || slot[b] >= max_live) return set_err(STS_EINVAL, "a slot outside [-1, max_live)");
+        if (slot[b] < 0) continue;
+        if (taken[(size_t)slot[b]]) return set_err(STS_EINVAL, "two newcomers name one slot");
+        taken[(size_t)slot[b]] = 1;
+        if (n[b] < 0 || (n[b] > 0 && (!cum || !q || src_off[b] < 0 || dst_off[b] < 0 || (int64_t)src_off[b] + n[b] > n_src || (int64_t)dst_off[b] + n[b] > capacity_phonemes)))
+            return set_err(STS_EINVAL, "a phoneme range leaves its array");
+        if (n[b] > 0) ranges.emplace_back(dst_off[b], (int64_t)dst_off[b] + n[b]);
+        max_n = std::max(max_n, (int)n[b]);
+    }
+    std::sort(ranges.begin(), ranges.end());
+    for (size_t i = 1; i < ranges.size(); i++) if (ranges[i].first < ranges[i - 1].second) return set_err(STS_EINVAL, "destination ranges overlap");
+    if (hipSetDevice(device) != hipSuccess) return set_err(STS_EDEVICE, "no such device");
+    std::vector<int> tab(5 * (size_t)B);
+    for (int b = 0; b < B; b++) { int* t = tab.data() + 5 * (size_t)b; t[0] = slot[b]; t[1] = src_off[b]; t[2] = slot[b] >= 0 ? n[b] : 0; t[3] = dst_off[b]; t[4] = h[b]; }
+    const size_t pw = 2 * ((size_t)capacity_phonemes + 1);
+    DevScratch d;
+    AdoptTablesArgs a{};
+    a.g = d.up(g, (size_t)gin * B); a.gpool = (float*)d.up(gpool, (size_t)gin * max_live); a.gin = gin; a.B = B; a.max_live = max_live;
+    a.cum = d.up(cum, (size_t)n_src); a.q = d.up(q, (size_t)n_src);
+    a.pool = (int*)d.up(pool, pw); a.ld_pool = capacity_phonemes + 1; a.swords = (int*)d.up(slot_words, 3 * (size_t)max_live);
+    a.neutral = (int)capacity_phonemes;
+    a.tab = d.up(tab.data(), tab.size());
+    if (d.ok) adopt_tables(a, max_n, d.st);
+    d.down(gpool, a.gpool, (size_t)gin * max_live * 4);
+    d.down(pool, a.pool, pw * 4);
+    d.down(slot_words, a.swords, 3 * (size_t)max_live * 4);
+    return d.finish() ? STS_OK : set_err(STS_EDEVICE, "the table adoption launch failed on the device");
+}
+
 // ------------------------------------------------------------------------------------------------
 // op-level entries for the parity tests: one conv on host arrays through the same kernels
 static int debug_conv1d_impl(int device, const float* x, int32_t Cin, int32_t L, const float* w, const float* bias, int32_t Cout,

@@ -377,7 +377,8 @@ int Engine::run_decode(RunCtx& c, int nw, long Wtot, int maxW, int zoff0, int wl
             Lvl lw; lw.seg = SegView{nullptr, nullptr, 1, 0, 0, nw}; lw.nb = 1; lw.max_len = nw; lw.total = nw; lw.ld = nw;
             // (a run with a speaker mix: the step's table holds each window's UTTERANCE there, and the windows take that column of the blended
             // bt.g [gin][B] -- the same gather with bt.g as the table; a window's index is not its utterance's once a short one has finished)
-            if (c.mix) gather_speaker(bt.g, B, M.gin, d_win + StepTab::sid(nw), nw, bf.gwin, stream);
+            // (a planned open stream's step: the table is the stream's gpool [gin][max_live] and the column the window's slot)
+            if (c.mix) gather_speaker(bt.g, c.live && c.live->gpool ? c.live->max_live : B, M.gin, d_win + StepTab::sid(nw), nw, bf.gwin, stream);
             else gather_speaker(M.emb_g, M.spk_num, M.gin, d_win + StepTab::sid(nw), nw, bf.gwin, stream);
             conv(M.dec_cond, bf.gwin, lw, bf.cond_win, lw, ConvOpt()); op.ubias = bf.cond_win;
         } else if (M.dec_type == 0 && ms) { conv(M.dec_cond, bt.g, lvB, bt.cond_dec, lvB, ConvOpt()); op.ubias = bt.cond_dec; }

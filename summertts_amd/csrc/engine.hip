@@ -27,6 +27,13 @@ namespace sts {
         if (live_) return fail(STS_ESTATE, "a stream is open on this engine (sts_stream_close first): it refuses " what); \
         if (para_) return fail(STS_ESTATE, "a paragraph is open on this engine (sts_para_close first): it refuses " what); \
     } while (0)
+// ... the form of the four table setters (duration plan, speaker mix, gain plan, forced durations): a PLANNED open stream lets them
+// through -- what they set applies to its next admission
+#define STS_NOT_WHILE_OPEN_UNPLANNED(what) \
+    do { \
+        if (live_ && !live_->planned()) return fail(STS_ESTATE, "an unplanned stream is open on this engine (sts_stream_open_ex with capacity_phonemes > 0 admits tables): it refuses " what); \
+        if (para_) return fail(STS_ESTATE, "a paragraph is open on this engine (sts_para_close first): it refuses " what); \
+    } while (0)
 
 Engine::~Engine() {
     if (live_) (void)stream_close();
@@ -407,7 +414,7 @@ int Engine::eq_prepare() {
 }
 // sts_set_duration_plan: copied and validated here; an invalid plan changes nothing.  B == 0 or plans == null drops a pending plan.
 int Engine::set_duration_plan(int B, const int32_t* n, const sts_dur_plan* plans) {
-    STS_NOT_WHILE_OPEN("a duration plan");
+    STS_NOT_WHILE_OPEN_UNPLANNED("a duration plan");
     if (B == 0 || !plans) { have_plan = false; return STS_OK; }
     if (B < 0 || !n) return fail(STS_EINVAL, "duration plan: B >= 0 and n are required");
     long total = 0;
@@ -431,7 +438,7 @@ int Engine::set_duration_plan(int B, const int32_t* n, const sts_dur_plan* plans
 }
 // sts_set_speaker_mix: validated and flattened here; an invalid mix changes nothing.  B == 0 or mixes == null drops a pending mix.
 int Engine::set_speaker_mix(int B, const sts_speaker_mix* mixes) {
-    STS_NOT_WHILE_OPEN("a speaker mix");
+    STS_NOT_WHILE_OPEN_UNPLANNED("a speaker mix");
     if (B == 0 || !mixes) { have_mix = false; return STS_OK; }
     if (B < 0 || B > (1 << 20)) return fail(STS_EINVAL, "speaker mix: B >= 0 is required");
     for (int b = 0; b < B; b++) {
@@ -446,7 +453,7 @@ int Engine::set_speaker_mix(int B, const sts_speaker_mix* mixes) {
 // sts_set_gain_plan: validated and designed here (q per phoneme, h per utterance); an invalid plan changes nothing.  B == 0 or plans == null
 // drops a pending plan.
 int Engine::set_gain_plan(int B, const int32_t* n, const sts_gain_plan* plans) {
-    STS_NOT_WHILE_OPEN("a gain plan");
+    STS_NOT_WHILE_OPEN_UNPLANNED("a gain plan");
     if (B == 0 || !plans) { have_gain = false; return STS_OK; }
     if (B < 0 || !n) return fail(STS_EINVAL, "gain plan: B >= 0 and n are required");
     long total = 0;
@@ -458,8 +465,10 @@ int Engine::set_gain_plan(int B, const int32_t* n, const sts_gain_plan* plans) {
     }
     gain_n.assign(n, n + B);
     gain_words.assign((size_t)total + (size_t)B, 0);
+    gain_has.assign((size_t)B, 0);
     size_t off = 0;
     for (int b = 0; b < B; b++) {
+        gain_has[(size_t)b] = plans[b].gain_db != nullptr;
         gain_design(plans[b].gain_db, n[b], plans[b].ramp_ms, gain_words.data() + off, gain_words.data() + total + b);
         off += (size_t)n[b];
     }
@@ -1629,7 +1638,8 @@ int Engine::run_stream_steps(RunCtx& c) {
         if (joined) bad = step_build_joined(call, c.js, k, offF.data(), sidv.data(), s.eqt, s.ldt, s.ht, st);
         else {
             win.clear();        // (an open stream: the slot's own next frame)
-            for (const int b : wb) win.push_back(StepWin{b, lenF[b], open ? open->slots[(size_t)c.live_slots[b]].f : k * Cf, offF[b], sidv[b]});
+            for (const int b : wb) win.push_back(StepWin{b, lenF[b], open ? open->slots[(size_t)c.live_slots[b]].f : k * Cf, offF[b], sidv[b],
+                                                         open && open->planned() ? c.live_slots[b] : -1});
             bad = step_build(call, win.data(), nu, s.eqt, s.ldt, s.ht, st);
         }
         if (bad) return fail(STS_EDEVICE, bad);
@@ -1796,13 +1806,15 @@ int Engine::run_joined_stream(int B, const int32_t* const* ids, const int32_t* n
 
 // ---- open streams (engine.hpp stream_open; live_stream.hpp; DESIGN.md 9c "Open streams").  Between two steps the engine keeps: z of every
 // live utterance in the pool, the slot table {pool offset, F, sid, next frame}, the free column ranges, the step count and the form-0
-// flag.  Nothing in the arenas survives a step: every step and every admission lays its workspace out again.
-int Engine::stream_open(int chunk_frames, int max_live, long long capacity_frames) {
+// flag -- and, in a planned stream, each slot's conditioning vector, a gain-planned slot's phoneme columns and slot words, and the free
+// phoneme ranges.  Nothing in the arenas survives a step: every step and every admission lays its workspace out again.
+int Engine::stream_open(int chunk_frames, int max_live, long long capacity_frames, long long capacity_phonemes) {
     if (live_) return fail(STS_ESTATE, "a stream is already open on this engine (sts_stream_close first)");
     if (para_) return fail(STS_ESTATE, "a paragraph is open on this engine (sts_para_close first)");
     const Model& M = model;
     if (chunk_frames <= 0 || max_live < 1 || max_live > 1024 || capacity_frames < 1)
         return fail(STS_EINVAL, "an open stream takes a positive chunk size, 1 <= max_live <= 1024 and a positive capacity");
+    if (capacity_phonemes < 0 || capacity_phonemes > (1 << 24)) return fail(STS_EINVAL, "an open stream's capacity_phonemes is 0 (no tables) or in [1, 2^24]");
     if ((double)capacity_frames * M.inter > 2.0e9 || (double)capacity_frames * M.hop_total > 2.0e9)
         return fail(STS_EINVAL, "an open stream's capacity_frames * inter_channels and capacity_frames * samples_per_frame may not exceed 2 10^9");
     if (eq_n > 0) return fail(STS_EINVAL, "an open stream is not available while an equaliser is set: its state is carried per utterance in the frame arena");
@@ -1816,14 +1828,17 @@ int Engine::stream_open(int chunk_frames, int max_live, long long capacity_frame
     if (conv_math == 3) { const int rc = ensure_overflow_word(); if (rc != STS_OK) return rc; }
     LiveStream* L = new (std::nothrow) LiveStream();
     if (!L) return fail(STS_EDEVICE, "out of host memory");
-    L->open(chunk_frames, max_live, capacity_frames);
+    L->open(chunk_frames, max_live, capacity_frames, capacity_phonemes);
     L->halo = stream_halo(); L->hop = M.hop_total;
     L->P = resampling() ? rs.P : 1; L->Q = resampling() ? rs.Q : 1; L->H = lim_mode != 0 ? d.H : 0;
     L->form0 = conv_math == 3 && h2_disabled;
     // (a KB of slack behind the last row: a kernel that stages z in whole vectors may read past a row's last column, as in the arena)
     const size_t pool_bytes = ((size_t)M.inter * (size_t)capacity_frames + 256) * sizeof(float);
-    if (hipMalloc((void**)&L->zpool, pool_bytes) != hipSuccess || hipMalloc(&L->tab_dev, adopt_tab_bytes(max_live)) != hipSuccess ||
-        hipHostMalloc(&L->tab_host, adopt_tab_bytes(max_live), hipHostMallocDefault) != hipSuccess) {
+    // (a planned stream: the adoption table of its pools rides behind adopt_z's in the same block)
+    const bool planned = capacity_phonemes > 0;
+    const size_t tab_bytes = planned ? adopt_tables_tab_off(max_live) + adopt_tables_tab_bytes(max_live) : adopt_tab_bytes(max_live);
+    if (hipMalloc((void**)&L->zpool, pool_bytes) != hipSuccess || hipMalloc(&L->tab_dev, tab_bytes) != hipSuccess ||
+        hipHostMalloc(&L->tab_host, tab_bytes, hipHostMallocDefault) != hipSuccess) {
         (void)hipGetLastError();
         if (L->zpool) (void)hipFree(L->zpool);
         if (L->tab_dev) (void)hipFree(L->tab_dev);
@@ -1832,6 +1847,27 @@ int Engine::stream_open(int chunk_frames, int max_live, long long capacity_frame
     }
     if (poison && hipMemsetD32Async((hipDeviceptr_t)L->zpool, (int)poison, pool_bytes / 4, stream) != hipSuccess) (void)hipGetLastError();
     live_ = L;
+    if (!planned) return STS_OK;
+    // the planned stream's pools: each slot's conditioning vector [gin][max_live] (a multi-speaker model with a conditioned decoder only),
+    // the phoneme pool [cum | q][capacity_phonemes + 1] (the last column: the shared neutral row), the slot words [off | n | h][max_live]
+    const bool has_g = M.is_ms == 1 && M.dec_type == 0 && M.gin > 0;
+    const size_t g_words = has_g ? (size_t)M.gin * (size_t)max_live : 0;
+    const size_t p_words = 2 * ((size_t)capacity_phonemes + 1), s_words = 3 * (size_t)max_live;
+    bool ok = hipMalloc(&L->tables_dev, (g_words + p_words + s_words) * 4) == hipSuccess;       // (one allocation: an open costs the pool's group)
+    if (ok) {
+        if (has_g) L->gpool = (float*)L->tables_dev;
+        L->ppool = (int*)L->tables_dev + g_words; L->swords = L->ppool + p_words;
+    }
+    if (ok && poison) ok = hipMemsetD32Async((hipDeviceptr_t)L->tables_dev, (int)poison, g_words + p_words + s_words, stream) == hipSuccess;
+    if (ok) {    // the neutral row, behind the fill: cum 0 (no phoneme owns a frame: Q == 2^20 everywhere), q 2^20
+        static const int neutral[2] = {0, kGainOne};
+        ok = hipMemcpy2DAsync(L->ppool + capacity_phonemes, ((size_t)capacity_phonemes + 1) * 4, neutral, 4, 4, 2, hipMemcpyHostToDevice, stream) == hipSuccess;
+    }
+    if (!ok) {
+        (void)hipGetLastError();
+        (void)stream_close();        // (frees whatever was allocated)
+        return fail(STS_EDEVICE, "out of device memory (the planned stream's pools)");
+    }
     return STS_OK;
 }
 
@@ -1840,6 +1876,7 @@ int Engine::stream_close() {
     (void)hipSetDevice(device);
     if (stream) (void)hipStreamSynchronize(stream);
     if (live_->zpool) (void)hipFree(live_->zpool);
+    if (live_->tables_dev) (void)hipFree(live_->tables_dev);
     if (live_->tab_dev) (void)hipFree(live_->tab_dev);
     if (live_->tab_host) (void)hipHostFree(live_->tab_host);
     delete live_;
@@ -1852,6 +1889,7 @@ int Engine::stream_close() {
 int Engine::stream_admit_once(int B, const int32_t* const* ids, const int32_t* n, const int32_t* sid, const float* ls, int32_t* slot_out,
                               int32_t* n_samples_out, int32_t* admitted) {
     LiveStream& L = *live_;
+    Model& M = model;
     const bool guarded = conv_math == 3;
     if (guarded) *(volatile unsigned*)ovf_host_ = 0u;
     poison_bytes_ = 0;
@@ -1864,9 +1902,11 @@ int Engine::stream_admit_once(int B, const int32_t* const* ids, const int32_t* n
     mark(0);
     if ((rc = run_text_encoder(c)) != STS_OK) return rc;
     if ((rc = run_durations(c)) != STS_OK) return rc;          // (a stream never launches ahead: the frame counts are on the host)
-    std::vector<long> F((size_t)B); std::vector<int> sidv((size_t)B), slots((size_t)B, -1);
+    std::vector<long> F((size_t)B); std::vector<int> sidv((size_t)B), slots((size_t)B, -1), nph((size_t)B, 0);
     for (int b = 0; b < B; b++) { F[(size_t)b] = c.p_lenF[b]; sidv[(size_t)b] = c.p_sid[b]; }
-    if (!L.admit(B, F.data(), sidv.data(), slots.data())) {    // no room now: the front work is lost, nothing has changed
+    // (a planned stream: an utterance whose gain plan came with gain_db takes n[b] columns of the phoneme pool; room is decided over all three)
+    if (c.gain) for (int b = 0; b < B; b++) nph[(size_t)b] = gain_has[(size_t)b] ? n[b] : 0;
+    if (!L.admit(B, F.data(), sidv.data(), nph.data(), slots.data())) {    // no room now: the front work is lost, nothing has changed
         HIPCK(hipStreamSynchronize(stream));
         *admitted = 0;
         return STS_OK;
@@ -1881,10 +1921,33 @@ int Engine::stream_admit_once(int B, const int32_t* const* ids, const int32_t* n
         tab[b] = c.p_offF[b]; tab[B + b] = slots[(size_t)b] >= 0 ? L.slots[(size_t)slots[(size_t)b]].off : 0;
         tlen[b] = slots[(size_t)b] >= 0 ? (int)F[(size_t)b] : 0;
     }
-    if (hipMemcpyAsync(L.tab_dev, tab, adopt_tab_bytes(B), hipMemcpyHostToDevice, stream) != hipSuccess) return undo(fail(STS_EDEVICE, "the adoption table's upload failed"));
+    size_t tab_bytes = adopt_tab_bytes(B);
+    int max_n = 0;
+    if (L.planned()) {      // the pools' table behind it, in the same upload: {slot, toff, n, poff, h} per newcomer
+        int* const t5 = (int*)((char*)L.tab_host + adopt_tables_tab_off(B));
+        for (int b = 0; b < B; b++) {
+            const int s = slots[(size_t)b];
+            const LiveSlot* sl = s >= 0 ? &L.slots[(size_t)s] : nullptr;
+            const bool g = sl && sl->has_gain;
+            t5[5 * b] = s; t5[5 * b + 1] = c.offT[(size_t)b]; t5[5 * b + 2] = g ? sl->pn : 0; t5[5 * b + 3] = g ? (int)sl->poff : 0;
+            t5[5 * b + 4] = g ? gain_words[(size_t)c.Ttot + (size_t)b] : 0;
+            if (g) max_n = std::max(max_n, sl->pn);
+        }
+        tab_bytes = adopt_tables_tab_off(B) + adopt_tables_tab_bytes(B);
+    }
+    if (hipMemcpyAsync(L.tab_dev, tab, tab_bytes, hipMemcpyHostToDevice, stream) != hipSuccess) return undo(fail(STS_EDEVICE, "the adoption table's upload failed"));
     adopt_z(c.bf.z, c.Fld, L.zpool, L.capacity, c.C, (const long long*)L.tab_dev, B, c.maxF, stream);
+    if (L.planned()) {      // every newcomer's column of gpool (mixed or plain: bt.g is the blend or the gather), a gain-planned one's cum / q / words
+        AdoptTablesArgs a{};
+        a.g = c.bt.g; a.gpool = L.gpool; a.gin = M.gin; a.B = B; a.max_live = L.max_live;
+        a.cum = c.bt.cum; a.q = c.bt.gain_q;
+        a.pool = L.ppool; a.ld_pool = L.capacity_phonemes + 1; a.swords = L.swords; a.neutral = (int)L.capacity_phonemes;
+        a.tab = (const int*)((const char*)L.tab_dev + adopt_tables_tab_off(B));
+        adopt_tables(a, max_n, stream);
+    }
     if (hipStreamSynchronize(stream) != hipSuccess || hipGetLastError() != hipSuccess) return undo(fail(STS_EDEVICE, "the admission failed on the device"));
-    if (guarded && *(volatile unsigned*)ovf_host_ != 0u) return undo(kRetrySplitBf16);
+    if (guarded && (*(volatile unsigned*)ovf_host_ != 0u || stream_retry_step == -2)) return undo(kRetrySplitBf16);      // (-2, tests: every admission counts as raised)
+    last_join_start.clear();    // (sts_get_durations / sts_get_phoneme_offsets report this admission's utterances, packed, as after a batch stream)
     n_samples.resize((size_t)B);
     for (int b = 0; b < B; b++) {
         n_samples[(size_t)b] = (int32_t)out_count((long long)F[(size_t)b] * c.hop);
@@ -1898,6 +1961,9 @@ int Engine::stream_admit_once(int B, const int32_t* const* ids, const int32_t* n
 int Engine::stream_admit(int B, const int32_t* const* ids, const int32_t* n, const int32_t* sid, const float* ls, const sts_stream_noise* nz,
                          int32_t* slot_out, int32_t* n_samples_out, int32_t* admitted) {
     if (!live_) return fail(STS_ESTATE, "no stream is open on this engine (sts_stream_open first)");
+    // (a planned stream: the pending tables are for this admission only, whatever its outcome -- no room and a failure included; dropped
+    // here, behind the last attempt, so that the form-0 repeat below applies them again)
+    struct Drop { Engine& e; ~Drop() { e.drop_tables(); } } drop{*this};
     if (!admitted) return fail(STS_EINVAL, "an admission needs the `admitted` output");
     *admitted = 0;
     LiveStream& L = *live_;
@@ -1911,10 +1977,12 @@ int Engine::stream_admit(int B, const int32_t* const* ids, const int32_t* n, con
     if (nz) for (int b = 0; b < B; b++) noise_utt.push_back(Noise{nz[b].noise_scale, nz[b].noise_scale_w, nz[b].seed});
     const int math = conv_math;
     if (math == 3 && L.form0) conv_math = 0;
+    const bool forced = have_forced;                           // (the duration stage consumes forced durations: the repeat needs them again)
     int rc = stream_admit_once(B, ids, n, sid, ls, slot_out, n_samples_out, admitted);
     if (rc == kRetrySplitBf16) {                               // this admission alone: nothing of the newcomers has been delivered
         h2_fallbacks++;
         conv_math = 0;
+        have_forced = forced;
         rc = stream_admit_once(B, ids, n, sid, ls, slot_out, n_samples_out, admitted);
     }
     conv_math = math;
@@ -1946,6 +2014,17 @@ int Engine::stream_step(int (*cb)(void*, int32_t, const int16_t*, int32_t, int32
     for (int b = 0; b < B; b++) lenF[(size_t)b] = (int)L.slots[(size_t)c.live_slots[(size_t)b]].F;
     c.p_lenF = lenF.data(); c.p_offF = offF.data();
     c.Ftot = c.Fld = 1; c.maxF = c.maxFld = 1;
+    if (L.planned()) {
+        // the gain stage runs in a step in which a live slot carries a gain plan, and only then (the chain is planned per step); the kernel
+        // reads the stream's pools by slot -- utt[m] = the window's slot, the slot words as its segment table.  The windows of slots
+        // without a plan read the shared neutral row (their words name it: n = 1, cum 0, q 2^20, h 0 -- env == 1.0f at every sample)
+        c.gain = L.any_gain();
+        c.lvT.seg = SegView{L.swords, L.swords + L.max_live, 1, 0, 0, 0};
+        c.bt.cum = L.ppool; c.bt.gain_q = L.ppool + (L.capacity_phonemes + 1); c.bt.gain_h = L.swords + 2 * (size_t)L.max_live;
+        // each window's conditioning: column `slot` of gpool (run_decode's gather with gpool as the table, as a closed stream's with bt.g)
+        c.mix = L.gpool != nullptr;
+        c.bt.g = L.gpool;
+    }
     poison_bytes_ = 0;
     int rc;
     if ((rc = plan_output(c)) != STS_OK) return rc;

@@ -236,7 +236,7 @@ public:
     int sdp_pre_ride = 1;              // 1: the stochastic duration predictor's `pre` conv as one more workgroup per column block of the encoder's output
                                        // projection launch where eligible, 0: a conv launch of its own (sts_debug_set STS_DBG_SDP_PRE_RIDE)
     int n_cus = 0;                     // compute units of the device (init)
-    int stream_retry_step = -1;        // tests (STS_DBG_STREAM_RETRY_STEP): a stream (of one utterance or several) under conv_math 3 treats the overflow word as raised after step k
+    int stream_retry_step = -1;        // tests (STS_DBG_STREAM_RETRY_STEP): a stream (of one utterance or several) under conv_math 3 treats the overflow word as raised after step k; -2: every admission into an open stream does (it is repeated in form 0)
     int stream_direct = 0;             // streaming, any B: 1 the pack / resample / limiter kernel writes each step's chunks into mapped pinned host memory, 0 one download (STS_DBG_STREAM_DIRECT)
     unsigned poison = 0;               // tests (STS_DBG_POISON): 32-bit pattern every call fills its workspace arenas and host outputs with; 0 = off
     int64_t poison_bytes_ = 0;         // bytes the current call has filled so far (sts_profile.poison_bytes)
@@ -327,16 +327,24 @@ public:
     // stream_admit runs front and flow of B newcomers as the packed batch a sts_infer_ids_batch_stream call of them would, and moves their z
     // into the pool (adopt_z); all or nothing (*admitted = B, or 0: no room now).  stream_step is ONE step of run_stream_steps over every
     // live slot in ascending slot order, each at its own next frame; a slot retires behind its last chunk or when its callback returns
-    // non-zero.  While a stream is open every other run and every setter of what open fixed returns STS_ESTATE.  Not admitted, and refused
-    // by stream_open (later work): EQ bands, loudness, record taps, a pending duration plan / speaker mix / gain plan / forced durations --
-    // they carry per-call tables or per-utterance filter state in the frame arena.  Not to be called from a chunk callback.
-    int stream_open(int chunk_frames, int max_live, long long capacity_frames);
+    // non-zero.  While a stream is open every other run and every setter of what open fixed returns STS_ESTATE.  Refused by stream_open
+    // (later work): EQ bands, loudness and record taps -- they need per-slot filter state -- and a duration plan / speaker mix / gain plan /
+    // forced durations pending AT OPEN (a pending table belongs to a next run, and open is not one).  Not to be called from a chunk callback.
+    // capacity_phonemes > 0: a PLANNED stream (sts_stream_open_ex; live_stream.hpp, DESIGN.md 9c "Planned open streams").  Its four table
+    // setters work while it is open and apply to the next stream_admit only, whatever its outcome; what a step needs of them (each slot's
+    // conditioning vector, a gain-planned slot's cum / q columns and {off, n, h}) moves into pools of the stream's own at admission
+    // (adopt_tables, one launch next to adopt_z), and a step reads them by slot.  0: exactly the stream above.
+    int stream_open(int chunk_frames, int max_live, long long capacity_frames, long long capacity_phonemes = 0);
+    void drop_tables() { have_plan = have_mix = have_gain = have_forced = false; }
     int stream_admit(int B, const int32_t* const* ids, const int32_t* n, const int32_t* sid, const float* ls, const sts_stream_noise* noise,
                      int32_t* slot_out, int32_t* n_samples_out, int32_t* admitted);
     int stream_step(int (*cb)(void*, int32_t, const int16_t*, int32_t, int32_t), void* user, int32_t* live_after);
     int stream_close();
     bool stream_is_open() const { return live_ != nullptr || para_ != nullptr; }      // "open": an open stream or an open paragraph
     LiveStream* live_ = nullptr;       // null: no stream is open
+    // (next to the stream, so that the members in front keep their places) gain_has[b]: entry b of the pending gain plan came with gain_db
+    // -- a planned open stream gives only those utterances columns of its phoneme pool
+    std::vector<char> gain_has;
     // an open paragraph (sts_para_open .. sts_para_close; para_stream.hpp, DESIGN.md 9i "Open paragraphs"): ONE joined stream per engine
     // whose sentences are appended between its steps.  para_open fixes what stream_open fixes and the join's lead and fade, and allocates
     // the latent pool; para_append runs front and flow of B new sentences as the packed batch a joined call of those B would (global

@@ -431,6 +431,23 @@ void stream_pack(const int16_t* src, int16_t* dst, const int* src_off, const int
 // the destination ranges is written.
 static inline size_t adopt_tab_bytes(int B) { return (size_t)B * 20; }
 void adopt_z(const float* src, long long ld_src, float* dst, long long ld_dst, int C, const long long* tab, int B, int max_len, hipStream_t st);
+// ... and the tables of an admission into a PLANNED open stream (live_stream.hip adopt_tables_kernel), one launch next to adopt_z: for
+// newcomer b with the table row {slot, toff, n, poff, h} -- column b of g [gin][B] -> column slot of gpool [gin][max_live] (gpool null:
+// the model has no conditioned decoder, nothing moves); n > 0: cum[toff .. + n) and q[toff .. + n) -> rows 0 and 1 of pool [2][ld_pool]
+// at column poff, and the slot words [off | n | h][max_live] of `slot` = {poff, n, h}; n == 0 (it carries no gain plan): the words =
+// {neutral, 1, 0}, the pool's shared neutral column.  slot < 0: nothing.  The table rides behind adopt_z's in the same upload, from the
+// next 8-byte boundary (adopt_tables_tab_off).
+struct AdoptTablesArgs {
+    const float* g; float* gpool; int gin, B, max_live;
+    const int* cum; const int* q;        // the admission's packed phoneme tables (q null when no newcomer carries a gain plan)
+    int* pool; long long ld_pool;        // [2][ld_pool]: row 0 cum, row 1 q
+    int* swords; int neutral;            // [3][max_live]; the column of the pool a plain slot's words name
+    const int* tab;                      // device: int [B][5]
+};
+static inline size_t adopt_tables_tab_off(int B) { return (adopt_tab_bytes(B) + 7) & ~(size_t)7; }
+static inline size_t adopt_tables_tab_bytes(int B) { return (size_t)B * 20; }
+// max_n = the most phonemes one newcomer carries
+void adopt_tables(const AdoptTablesArgs& a, int max_n, hipStream_t st);
 
 // Loudness measurement and normalisation (loudness.hip; the definition is there and in include/summertts_hip.h sts_set_loudness)
 constexpr int kLoudMinRate = 8000, kLoudMaxRate = 48000, kLoudPow = 9;

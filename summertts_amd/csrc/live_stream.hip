@@ -1,5 +1,6 @@
-// live_stream.hip -- the one kernel of an open stream (engine.hip stream_admit, live_stream.hpp): the latents of an admission leave the
-// frame arena, which the next run lays out again, for the stream's persistent pool.
+// live_stream.hip -- the two kernels of an open stream (engine.hip stream_admit, live_stream.hpp): the latents of an admission leave the
+// frame arena, which the next run lays out again, for the stream's persistent pool (adopt_z); and, in a planned stream, so do the tables a
+// newcomer carries until it retires -- its conditioning vector, its gain plan's phoneme table and slot words (adopt_tables).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -49,6 +50,48 @@ void adopt_z(const float* src, long long ld_src, float* dst, long long ld_dst, i
     if (B <= 0 || C <= 0 || max_len <= 0) return;
     hipLaunchKernelGGL(adopt_z_kernel, dim3((unsigned)((max_len + AZ_COLS - 1) / AZ_COLS), (unsigned)((C + AZ_ROWS - 1) / AZ_ROWS), (unsigned)B),
                        dim3(AZ_THREADS), 0, st, src, ld_src, dst, ld_dst, C, tab, B);
+}
+
+// The tables of an admission into a planned stream (live_stream.hpp), one launch for everything a newcomer carries besides z.  One
+// workgroup per (tile of AT_THREADS units, newcomer); the units of newcomer b are flattened --
+//   [0, gin)              channel c of its conditioning vector: g[c][b] -> gpool[c][slot]
+//   [gin, gin + n)        its inclusive cumulative frame counts: cum[toff + i] -> pool row 0, column poff + i
+//   [gin + n, gin + 2n)   its fixed-point gains: q[toff + i] -> pool row 1, column poff + i
+//   [gin + 2n, + 3)       its slot words {off, n, h}[slot]: {poff, n, h}, or the shared neutral row {cap, 1, 0} when it carries no plan
+// -- so a 1-phoneme utterance (gin + 5 units) and a 700-phoneme one (gin + 1403) both fill their waves but for the last one.  Consecutive
+// lanes of a phoneme section read and write consecutive words; source and destination offsets are arbitrary, so the words move one per
+// lane (whole 64-lane rows of 256 bytes either way) and not in quads.  The vector's column is strided on both sides by its nature: gin
+// words in all.  Every store is a plain vector store of a loaded value; nothing outside column `slot` of gpool and the words, and columns
+// [poff, poff + n) of the pool, is written.  A row of the table with slot < 0 (an utterance without frames) moves nothing.
+constexpr int AT_THREADS = 256;
+__global__ __launch_bounds__(AT_THREADS) void adopt_tables_kernel(AdoptTablesArgs a) {
+    const int b = blockIdx.y;
+    const int* const row = a.tab + 5 * (size_t)b;
+    const int slot = row[0], toff = row[1], n = row[2], poff = row[3], h = row[4];
+    if (slot < 0) return;
+    const int gin = a.gpool ? a.gin : 0;
+    const int units = gin + 2 * n + 3;
+    const int u = blockIdx.x * AT_THREADS + threadIdx.x;
+    if (u >= units) return;
+    if (u < gin) {
+        a.gpool[(size_t)u * a.max_live + slot] = a.g[(size_t)u * a.B + b];
+    } else if (u < gin + n) {
+        const int i = u - gin;
+        a.pool[(size_t)poff + i] = a.cum[(size_t)toff + i];
+    } else if (u < gin + 2 * n) {
+        const int i = u - gin - n;
+        a.pool[(size_t)a.ld_pool + poff + i] = a.q[(size_t)toff + i];
+    } else {
+        const int w = u - gin - 2 * n;      // 0: off, 1: n, 2: h
+        const int v = n > 0 ? (w == 0 ? poff : w == 1 ? n : h) : (w == 0 ? a.neutral : w == 1 ? 1 : 0);
+        a.swords[(size_t)w * a.max_live + slot] = v;
+    }
+}
+
+void adopt_tables(const AdoptTablesArgs& a, int max_n, hipStream_t st) {
+    if (a.B <= 0) return;
+    const int units = (a.gpool ? a.gin : 0) + 2 * max_n + 3;
+    hipLaunchKernelGGL(adopt_tables_kernel, dim3((unsigned)((units + AT_THREADS - 1) / AT_THREADS), (unsigned)a.B), dim3(AT_THREADS), 0, st, a);
 }
 
 }  // namespace sts

@@ -8,9 +8,17 @@
 // whenever it arrives, and a retired one gives its slot and its columns back.  What a slot's chunks are does not depend on who else is
 // live: the window of a chunk is a function of (F, f0, C, halo, hop, P, Q, H) alone (stream_window below, the one every stream uses).
 //
+// A PLANNED open stream (sts_stream_open_ex with capacity_phonemes > 0; DESIGN.md 9c "Planned open streams") also admits utterances with
+// the per-call tables of a closed stream: a duration plan or forced durations (used by the admission's duration stage and nothing else), a
+// speaker mix and a gain plan.  What a step reads of them survives the admission's arenas in pools of the stream's own, indexed by SLOT:
+// the conditioning vector of every slot (gpool [gin][max_live]), the phoneme pool [cum | q][capacity_phonemes + 1] with one column range
+// per gain-planned utterance -- first fit over a second free list, the same take / give as the frame ranges -- and the slot words
+// [off | n | h][max_live] the gain kernel indexes by slot.  The pool's last column is the shared neutral row (cum 0, q 2^20): a slot
+// without a gain plan points its words at it {capacity_phonemes, 1, 0}, for which the gain kernel's envelope is 1.0f at every sample.
+//
 // Not admitted (the open stream refuses them when it is opened; later work): the EQ and loudness in a stream (state carried per
-// utterance in the frame arena, which every admission lays out again), and the per-call tables of a duration plan, a speaker mix, a gain
-// plan, forced durations and record taps (they are indexed by "utterance b of this call", which an open stream does not have).
+// utterance in the frame arena, which every admission lays out again: they need per-slot filter state) and record taps.  An unplanned
+// stream (capacity_phonemes == 0) refuses the per-call tables too, as it always has.
 #pragma once
 #include <stdint.h>
 
@@ -36,7 +44,8 @@ static inline StreamWin stream_window(long F, long f0, long C, long halo, long h
 }
 
 // one live utterance: its columns [off, off + F) of the pool, its speaker, the first frame of its next chunk
-struct LiveSlot { bool live = false; long long off = 0; long F = 0; int sid = 0; long f = 0; };
+// (a planned stream: its columns [poff, poff + pn) of the phoneme pool when it carries a gain plan, has_gain)
+struct LiveSlot { bool live = false; long long off = 0; long F = 0; int sid = 0; long f = 0; long long poff = 0; int pn = 0; bool has_gain = false; };
 struct LiveRange { long long off, len; };
 
 // The capacity a group of `max_live` utterances needs when none is longer than `longest` frames: every slot can hold the longest one.
@@ -44,28 +53,43 @@ struct LiveRange { long long off, len; };
 // pool per slot at 192 channels.  Requests that do not fit an EMPTY pool run as a closed stream, as without admission.)
 constexpr long long kLivePoolFrames = 1024;
 static inline long long live_capacity_rule(int max_live, long long longest) { return (long long)max_live * longest; }
+// The phoneme capacity by the same rule: every slot can hold the gain plan of the longest utterance.  Nothing ties phonemes to frames (a
+// phoneme may own no frame), so the longest is a constant of its own: kLivePoolPhonemes = 1024 phonemes, 8 KB of pool per slot.  (A
+// gain-planned request with more phonemes than the EMPTY pool holds runs as a closed stream, as for frames.)
+constexpr long long kLivePoolPhonemes = 1024;
+static inline long long live_phoneme_rule(int max_live, long long longest) { return (long long)max_live * longest; }
 
 struct LiveStream {
     // fixed when the stream is opened
     int chunk = 0, max_live = 0; long long capacity = 0;
+    long long capacity_phonemes = 0;                            // > 0: a planned stream
     int halo = 0, hop = 0; long long P = 1, Q = 1, H = 0;       // the window geometry's facts: stream_halo, samples per frame, rate, limiter
     // the pool and the adoption table (engine-owned device / pinned memory; plain pointers: this header knows no HIP)
     float* zpool = nullptr; void* tab_dev = nullptr; void* tab_host = nullptr;
+    // a planned stream's pools, one allocation [gpool | ppool | swords] (null otherwise; gpool: a multi-speaker model with a conditioned
+    // decoder only)
+    void* tables_dev = nullptr; float* gpool = nullptr; int* ppool = nullptr; int* swords = nullptr;
     // state between steps
     std::vector<LiveSlot> slots; std::vector<LiveRange> free_ranges;      // free_ranges: ascending, never adjacent (coalesced)
+    std::vector<LiveRange> free_phonemes;                                  // the phoneme pool's free columns, kept the same way
     long long steps = 0;            // stream_step calls since open (STS_DBG_STREAM_RETRY_STEP counts them)
     bool form0 = false;             // conv math 3: an overflow was raised in a step -- split-bf16 until the stream is closed
     long long admitted = 0, retired = 0;
 
-    void open(int chunk_frames, int max_live_, long long capacity_frames) {
-        chunk = chunk_frames; max_live = max_live_; capacity = capacity_frames;
+    void open(int chunk_frames, int max_live_, long long capacity_frames, long long capacity_phonemes_ = 0) {
+        chunk = chunk_frames; max_live = max_live_; capacity = capacity_frames; capacity_phonemes = capacity_phonemes_;
         slots.assign((size_t)max_live, LiveSlot());
         free_ranges.assign(1, LiveRange{0, capacity});
+        free_phonemes.clear();
+        if (capacity_phonemes > 0) free_phonemes.push_back(LiveRange{0, capacity_phonemes});
         steps = 0; form0 = false; admitted = retired = 0;
     }
     int live_count() const { int n = 0; for (const LiveSlot& s : slots) n += s.live; return n; }
     int free_slots() const { return max_live - live_count(); }
     long long free_frames() const { long long n = 0; for (const LiveRange& r : free_ranges) n += r.len; return n; }
+    bool planned() const { return capacity_phonemes > 0; }
+    long long free_phoneme_count() const { long long n = 0; for (const LiveRange& r : free_phonemes) n += r.len; return n; }
+    bool any_gain() const { for (const LiveSlot& s : slots) if (s.live && s.has_gain) return true; return false; }
 
     // first fit: the lowest free range that holds `len` columns gives its first `len`; -1: none does
     static long long take(std::vector<LiveRange>& fr, long long len) {
@@ -91,32 +115,39 @@ struct LiveStream {
     // All or nothing: utterance b of the admission (F[b] frames, speaker sid[b]) takes the lowest free slot and the first fit of F[b]
     // columns, in the order b = 0 .. B - 1; slot_out[b] = its slot (-1: an utterance without frames takes none and is never stepped).
     // False: slots or columns do not suffice, and nothing has changed.
-    bool admit(int B, const long* F, const int* sid, int* slot_out) {
-        std::vector<LiveRange> fr = free_ranges;
-        std::vector<long long> off((size_t)B, 0);
+    bool admit(int B, const long* F, const int* sid, int* slot_out) { return admit(B, F, sid, nullptr, slot_out); }
+    // ... and over phonemes too: utterance b with n_phonemes[b] > 0 carries a gain plan and takes the first fit of that many columns of
+    // the phoneme pool (0, or n_phonemes == null: it takes none; an utterance without frames takes none either).  False: slots, frame
+    // columns or phoneme columns do not suffice, and nothing has changed.
+    bool admit(int B, const long* F, const int* sid, const int* n_phonemes, int* slot_out) {
+        std::vector<LiveRange> fr = free_ranges, fp = free_phonemes;
+        std::vector<long long> off((size_t)B, 0), poff((size_t)B, 0);
         int need = 0;
         for (int b = 0; b < B; b++) {
-            if (F[b] < 0) return false;
+            if (F[b] < 0 || (n_phonemes && n_phonemes[b] < 0)) return false;
             if (F[b] == 0) continue;
             need++;
             if ((off[(size_t)b] = take(fr, F[b])) < 0) return false;
+            if (n_phonemes && n_phonemes[b] > 0 && (poff[(size_t)b] = take(fp, n_phonemes[b])) < 0) return false;
         }
         if (need > free_slots()) return false;
         size_t s = 0;
         for (int b = 0; b < B; b++) {
             if (F[b] == 0) { slot_out[b] = -1; continue; }
             while (slots[s].live) s++;
-            slots[s] = LiveSlot{true, off[(size_t)b], F[b], sid ? sid[b] : 0, 0};
+            const int pn = n_phonemes ? n_phonemes[b] : 0;
+            slots[s] = LiveSlot{true, off[(size_t)b], F[b], sid ? sid[b] : 0, 0, poff[(size_t)b], pn, pn > 0};
             slot_out[b] = (int)s;
             admitted++;
         }
-        free_ranges.swap(fr);
+        free_ranges.swap(fr); free_phonemes.swap(fp);
         return true;
     }
     void retire(int s) {
         LiveSlot& sl = slots[(size_t)s];
         if (!sl.live) return;
         give(free_ranges, sl.off, sl.F);
+        give(free_phonemes, sl.poff, sl.pn);
         sl = LiveSlot();
         retired++;
     }

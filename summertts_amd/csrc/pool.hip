@@ -96,32 +96,8 @@ struct sts_pool {
                     idp[b] = grp[b]->ids.data(); n[b] = (int32_t)grp[b]->ids.size(); sid[b] = grp[b]->sid; ls[b] = grp[b]->ls;
                     eng.noise_utt[b] = grp[b]->noise;
                 }
-                bool any_plan = false;
-                for (int b = 0; b < B; b++) any_plan = any_plan || grp[b]->planned;
-                int rc = STS_OK;
-                if (any_plan) {      // per utterance: the members without a plan get an empty one (synthesised as without, bit for bit)
-                    std::vector<sts_dur_plan> pl(B, sts_dur_plan{nullptr, nullptr, 0});
-                    for (int b = 0; b < B; b++)
-                        if (grp[b]->planned) pl[b] = sts_dur_plan{grp[b]->rate.empty() ? nullptr : grp[b]->rate.data(),
-                                                                  grp[b]->fixed.empty() ? nullptr : grp[b]->fixed.data(), grp[b]->target};
-                    rc = eng.set_duration_plan(B, n.data(), pl.data());
-                }
-                bool any_mix = false;
-                for (int b = 0; b < B; b++) any_mix = any_mix || grp[b]->mixed;
-                if (rc == STS_OK && any_mix) {      // per utterance likewise: the plain members get an empty entry (their sid, bit for bit)
-                    std::vector<sts_speaker_mix> mx(B, sts_speaker_mix{0, nullptr, nullptr, nullptr, 0.f});
-                    for (int b = 0; b < B; b++) if (grp[b]->mixed) mx[b] = grp[b]->mix.view();
-                    rc = eng.set_speaker_mix(B, mx.data());
-                }
-                bool any_gain = false;
-                for (int b = 0; b < B; b++) any_gain = any_gain || grp[b]->gained;
-                if (rc == STS_OK && any_gain) {     // and the gain plans: the members without one get an entry without gains (their samples, bit for bit)
-                    std::vector<sts_gain_plan> gp(B, sts_gain_plan{nullptr, 0.f});
-                    for (int b = 0; b < B; b++) if (grp[b]->gained) gp[b] = sts_gain_plan{grp[b]->gain_db.data(), grp[b]->ramp_ms};
-                    rc = eng.set_gain_plan(B, n.data(), gp.data());
-                }
+                int rc = set_group_tables(eng, grp, n.data());
                 if (rc == STS_OK) rc = eng.run(B, idp.data(), n.data(), sid.data(), ls.data());
-                else { eng.set_duration_plan(0, nullptr, nullptr); eng.set_speaker_mix(0, nullptr); eng.set_gain_plan(0, nullptr, nullptr); }     // (nothing ran: nothing stays pending for another group)
                 eng.noise_utt.clear();
                 std::vector<int16_t> all;
                 if (rc == STS_OK) {
@@ -155,6 +131,35 @@ struct sts_pool {
             run_group(take, run_group);
             cv_done.notify_all();
         }
+    }
+
+    // The tables of a group's members on `eng`, for its next run (or its next admission into a planned open stream): a kind of table is
+    // set when a member carries one, and the members without get an empty entry of it (synthesised as without, bit for bit).  On a
+    // failure nothing stays pending for another group.
+    int set_group_tables(Engine& eng, const std::vector<std::shared_ptr<Request>>& grp, const int32_t* n) {
+        const int B = (int)grp.size();
+        bool any_plan = false, any_mix = false, any_gain = false;
+        for (int b = 0; b < B; b++) { any_plan = any_plan || grp[b]->planned; any_mix = any_mix || grp[b]->mixed; any_gain = any_gain || grp[b]->gained; }
+        int rc = STS_OK;
+        if (any_plan) {
+            std::vector<sts_dur_plan> pl(B, sts_dur_plan{nullptr, nullptr, 0});
+            for (int b = 0; b < B; b++)
+                if (grp[b]->planned) pl[b] = sts_dur_plan{grp[b]->rate.empty() ? nullptr : grp[b]->rate.data(),
+                                                          grp[b]->fixed.empty() ? nullptr : grp[b]->fixed.data(), grp[b]->target};
+            rc = eng.set_duration_plan(B, n, pl.data());
+        }
+        if (rc == STS_OK && any_mix) {      // (the plain members: their sid)
+            std::vector<sts_speaker_mix> mx(B, sts_speaker_mix{0, nullptr, nullptr, nullptr, 0.f});
+            for (int b = 0; b < B; b++) if (grp[b]->mixed) mx[b] = grp[b]->mix.view();
+            rc = eng.set_speaker_mix(B, mx.data());
+        }
+        if (rc == STS_OK && any_gain) {     // (the members without one: an entry without gains)
+            std::vector<sts_gain_plan> gp(B, sts_gain_plan{nullptr, 0.f});
+            for (int b = 0; b < B; b++) if (grp[b]->gained) gp[b] = sts_gain_plan{grp[b]->gain_db.data(), grp[b]->ramp_ms};
+            rc = eng.set_gain_plan(B, n, gp.data());
+        }
+        if (rc != STS_OK) eng.drop_tables();
+        return rc;
     }
 
     // a paragraph (Engine::run_joined): its sentences as one packed batch of their own, one PCM
@@ -211,7 +216,8 @@ struct sts_pool {
             return stop;
         };
         for (auto& r : grp) r->n = 0;
-        const int rc = eng.run_batch_stream(B, idp.data(), n.data(), sid.data(), ls.data(), grp.front()->chunk, cb, &cx, nullptr);
+        int rc = set_group_tables(eng, grp, n.data());        // (sts_pool_submit_stream_ex: the members' own tables)
+        if (rc == STS_OK) rc = eng.run_batch_stream(B, idp.data(), n.data(), sid.data(), ls.data(), grp.front()->chunk, cb, &cx, nullptr);
         eng.noise_utt.clear();
         if (rc != STS_OK && B > 1 && !cx.any_left) {
             for (auto& r : grp) run_stream_group(eng, std::vector<std::shared_ptr<Request>>{r});
@@ -228,12 +234,16 @@ struct sts_pool {
     }
 
     // sts_pool_set_stream_admission: the group as an OPEN stream on this engine (Engine::stream_open; chunk size of the group, max_live =
-    // max_batch, capacity by live_capacity_rule: every slot can hold kLivePoolFrames frames).  Between two steps the worker looks at the
+    // max_batch, capacity by live_capacity_rule: every slot can hold kLivePoolFrames frames).  The stream is a PLANNED one
+    // (sts_stream_open_ex), its phoneme capacity by live_phoneme_rule: every slot can hold a gain plan of kLivePoolPhonemes phonemes --
+    // so that planned requests (sts_pool_submit_stream_ex) and plain ones share a group, and a planned one is admitted midstream like
+    // any other.  The tables of an admission are set right before it, every time: an admission consumes them whatever its outcome, so
+    // the one-by-one retry and a request that came back from the FIFO set theirs again.  Between two steps the worker looks at the
     // FIFO: while its head is a streaming request of the group's chunk size and slots are free it takes up to the free count and admits
     // them.  A head of any other kind stays where it is.  Tickets complete as in run_stream_group: at a member's last chunk or its stop.
     void run_open_group(Engine& eng, const std::vector<std::shared_ptr<Request>>& first) {
         const int32_t chunk = first.front()->chunk;
-        if (eng.stream_open(chunk, max_batch, live_capacity_rule(max_batch, kLivePoolFrames)) != STS_OK) { run_stream_group(eng, first); return; }
+        if (eng.stream_open(chunk, max_batch, live_capacity_rule(max_batch, kLivePoolFrames), live_phoneme_rule(max_batch, kLivePoolPhonemes)) != STS_OK) { run_stream_group(eng, first); return; }
         struct Ctx { sts_pool* p; std::vector<std::shared_ptr<Request>> slot; std::vector<int32_t> total; };
         Ctx cx{this, std::vector<std::shared_ptr<Request>>((size_t)max_batch), std::vector<int32_t>((size_t)max_batch, 0)};
         auto finish = [this](Request& r, int rc, const std::string& err) {
@@ -266,7 +276,8 @@ struct sts_pool {
             }
             const bool midstream = eng.live_->steps > 0 && eng.live_->live_count() > 0;
             int32_t admitted = 0;
-            const int rc = eng.stream_admit(B, idp.data(), n.data(), sid.data(), ls.data(), nz.data(), slots.data(), tot.data(), &admitted);
+            int rc = set_group_tables(eng, grp, n.data());
+            if (rc == STS_OK) rc = eng.stream_admit(B, idp.data(), n.data(), sid.data(), ls.data(), nz.data(), slots.data(), tot.data(), &admitted);
             if (rc != STS_OK || admitted == 0) {
                 if (B > 1) { for (auto& r : grp) self(std::vector<std::shared_ptr<Request>>{r}, back, self); return; }
                 if (rc != STS_OK) { finish(*grp.front(), rc, eng.error()); std::lock_guard<std::mutex> lk(mu); batches++; requests++; return; }
@@ -476,11 +487,33 @@ int64_t sts_pool_submit_joined(sts_pool* p, int32_t B, const int32_t* const* ids
 
 int64_t sts_pool_submit_stream(sts_pool* p, const int32_t* ids, int32_t n, int32_t sid, float length_scale, float noise_scale,
                                float noise_scale_w, uint64_t seed, int32_t chunk_frames, sts_chunk_cb cb, void* user) {
-    if (!p || !ids || n <= 0 || chunk_frames <= 0 || !cb) return pool_err(STS_EINVAL, "bad request");
+    return sts_pool_submit_stream_ex(p, ids, n, sid, length_scale, noise_scale, noise_scale_w, seed, chunk_frames, cb, user, nullptr, nullptr, nullptr);
+}
+
+int64_t sts_pool_submit_stream_ex(sts_pool* p, const int32_t* ids, int32_t n, int32_t sid, float length_scale, float noise_scale,
+                                  float noise_scale_w, uint64_t seed, int32_t chunk_frames, sts_chunk_cb cb, void* user,
+                                  const sts_dur_plan* plan, const sts_speaker_mix* mix, const sts_gain_plan* gain) {
+    if (!ids || n <= 0 || chunk_frames <= 0 || !cb) return pool_err(STS_EINVAL, "bad request");
     if (!noise_scale_valid(noise_scale) || !noise_scale_valid(noise_scale_w)) return pool_err(STS_EINVAL, "noise scales must be finite and >= 0");
+    const char* why = nullptr;      // (the three checks of sts_pool_submit_plan / _mix / _gain; the two that need no model come first)
+    if (plan && !dur_plan_valid(n, plan->rate, plan->fixed, plan->target_frames, &why)) return pool_err(STS_EINVAL, why);
+    if (gain && !gain_plan_valid(n, gain->gain_db, gain->ramp_ms, &why)) return pool_err(STS_EINVAL, why);
+    if (!p) return pool_err(STS_EINVAL, "bad request");
+    const Model& M = p->engines[0]->model;
+    if (mix && !speaker_mix_valid(M.is_ms == 1 ? M.spk_num : 0, M.gin, *mix, &why)) return pool_err(STS_EINVAL, why);
     auto r = std::make_shared<Request>();
     r->ids.assign(ids, ids + n); r->sid = sid; r->ls = length_scale; r->noise = Engine::Noise{noise_scale, noise_scale_w, seed};
     r->stream = true; r->chunk = chunk_frames; r->cb = cb; r->user = user;
+    r->planned = plan && (plan->rate || plan->fixed || plan->target_frames != 0);
+    if (r->planned) {
+        if (plan->rate) r->rate.assign(plan->rate, plan->rate + n);
+        if (plan->fixed) r->fixed.assign(plan->fixed, plan->fixed + n);
+        r->target = plan->target_frames;
+    }
+    r->mixed = mix && !speaker_mix_empty(*mix);
+    if (r->mixed) r->mix.assign(*mix, M.gin);
+    r->gained = gain && gain->gain_db;
+    if (r->gained) { r->gain_db.assign(gain->gain_db, gain->gain_db + n); r->ramp_ms = gain->ramp_ms; }
     {
         std::lock_guard<std::mutex> lk(p->mu);
         if (p->stop) return pool_err(STS_ESTATE, "pool is shutting down");

@@ -5,7 +5,8 @@
 // One step decodes nw windows and uploads one table for them (RunCtx::d_win points at it).  Its sections, in order:
 //   ints  [zoff nw | coff nw | wlen nw | sid nw | pack source nw | packed destination nw + 1]   (the last word: the step's samples in all)
 //   from the next 8-byte boundary: the resampler's rows, RsRow [nw]; behind them the limiter's, LimRow [nw]
-//   a run with a gain plan: each window's utterance, ints [nw] (GainArgs::utt; the gain kernel takes u0 from the window's RsRow)
+//   a run with a gain plan: each window's utterance, ints [nw] (GainArgs::utt; the gain kernel takes u0 from the window's RsRow) -- in a
+//   planned open stream its slot, as the sid column then holds it (StepWin::tab)
 //   a plain stream, from the next 8-byte boundary each: the EQ's rows, EqsRow [nw]; loudness' rows, LdsRow [nw]
 //   a joined stream, from the next 8-byte boundary: the ONE window of J for the resampler (RsRow) and the limiter (LimRow), the windowed
 //   join's rows, JsRow [nw], the one EqsRow of J, the one LdsRow of J
@@ -78,8 +79,10 @@ struct StepCall {
     bool srs = false, slim = false, seq = false, sld = false, gain = false, mix = false;
     int lsrc = -1;
 };
-// one window of a plain step: utterance b of F frames at z offset `zoff` speaks as `sid`; its chunk starts at frame f0
-struct StepWin { int b; long F, f0; int zoff, sid; };
+// one window of a plain step: utterance b of F frames at z offset `zoff` speaks as `sid`; its chunk starts at frame f0.  tab: the row of
+// the run's per-utterance tables it reads (the gain kernel's utt[m]; with `mix` the column of the conditioning table in the sid column)
+// -- < 0: b itself, utterance b of a closed call; a planned open stream: its SLOT (live_stream.hpp: the pools are indexed by slot)
+struct StepWin { int b; long F, f0; int zoff, sid; int tab = -1; };
 
 // what the step loop needs of a built step.  (Its vectors keep their storage from step to step.)
 struct StepOut {
@@ -124,10 +127,11 @@ static inline const char* step_build(const StepCall& c, const StepWin* w, int nw
     for (int i = 0; i < nw; i++) {
         const StepWin& u = w[i];
         const StreamWin g = stream_window(u.F, u.f0, c.C, c.halo, c.hop, c.P, c.Q, c.H);
+        const int row = u.tab >= 0 ? u.tab : u.b;
         const long wlen = g.w1 - g.w0;
         const long long nrs = g.jl1 - g.jl0, nout = g.j1 - g.j0;
         const long long xnat = Wtot * hop, unat = g.w0 * hop, lnat = wlen * hop;        // the decode window's samples: where, from, how many
-        step_put_window(ht, t, i, u.b, u.zoff + (int)g.w0, (int)Wtot, (int)wlen, c.mix ? u.b : u.sid, (int)((Wtot + (u.f0 - g.w0)) * hop), (int)dsum,
+        step_put_window(ht, t, i, row, u.zoff + (int)g.w0, (int)Wtot, (int)wlen, c.mix ? row : u.sid, (int)((Wtot + (u.f0 - g.w0)) * hop), (int)dsum,
                         RsRow{unat, u.F * hop, g.jl0, g.jl1, c.slim ? rsum : dsum},
                         LimRow{wide ? rsum : xnat, wide ? g.jl0 : unat, wide ? nrs : lnat, g.Nout, g.j0, g.j1, dsum});
         if (c.seq) {

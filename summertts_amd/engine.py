@@ -333,6 +333,13 @@ def load_library() -> C.CDLL:
     lib.sts_pool_submit_stream.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_float, C.c_uint64,
                                            C.c_int32, CHUNK_CB, C.c_void_p]
     lib.sts_stream_open.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int64]
+    lib.sts_stream_open_ex.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_int64]
+    lib.sts_stream_tables_info.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.sts_debug_adopt_tables.argtypes = [C.c_int, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64,
+                                           C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.sts_pool_submit_stream_ex.restype = C.c_int64
+    lib.sts_pool_submit_stream_ex.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_float, C.c_uint64,
+                                              C.c_int32, CHUNK_CB, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.sts_stream_admit.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                      C.c_void_p]
     lib.sts_stream_step.argtypes = [C.c_void_p, BATCH_CHUNK_CB, C.c_void_p, C.c_void_p]
@@ -390,6 +397,7 @@ EXPORTED_SYMBOLS = [
     "sts_stream_open", "sts_stream_admit", "sts_stream_step", "sts_stream_info", "sts_stream_close", "sts_debug_adopt_z",
     "sts_pool_set_stream_admission", "sts_pool_get_stream_admission", "sts_pool_stream_stats",
     "sts_para_open", "sts_para_append", "sts_para_finish", "sts_para_step", "sts_para_info", "sts_para_close",
+    "sts_stream_open_ex", "sts_stream_tables_info", "sts_pool_submit_stream_ex", "sts_debug_adopt_tables",
 ]
 
 
@@ -415,6 +423,40 @@ def debug_adopt_z(src, dst, src_off, dst_off, lengths, device: int = 0) -> np.nd
     _check(lib, lib.sts_debug_adopt_z(device, a.ctypes.data, a.shape[0], a.shape[1], out.ctypes.data, out.shape[1], so.ctypes.data,
                                       do.ctypes.data, ln.ctypes.data, ln.size))
     return out
+
+
+def debug_adopt_tables(g, gpool, cum, q, pool, slot_words, slot, src_off, n, dst_off, h, device: int = 0):
+    """The kernel that moves an admission's tables into a planned open stream's pools (sts_debug_adopt_tables), on caller data.  For
+    newcomer b with ``slot[b] >= 0``: column b of ``g`` [gin][B] goes to column ``slot[b]`` of ``gpool`` [gin][max_live] (both None: no
+    conditioning vectors); ``n[b] > 0``: ``cum`` / ``q`` ``[src_off[b], + n[b])`` go to rows 0 / 1 of ``pool`` [2][capacity + 1] at column
+    ``dst_off[b]`` and its column of ``slot_words`` [3][max_live] becomes ``(dst_off[b], n[b], h[b])``; ``n[b] == 0``: ``(capacity, 1, 0)``.
+    Returns copies ``(gpool, pool, slot_words)``; everything outside the destinations is what the arguments held."""
+    lib = load_library()
+    sl = np.ascontiguousarray(slot, dtype=np.int32)
+    so, nn, do, hh = (np.ascontiguousarray(v, dtype=np.int32) for v in (src_off, n, dst_off, h))
+    if not (sl.size == so.size == nn.size == do.size == hh.size):
+        raise ValueError("one slot, source offset, count, destination offset and h per newcomer")
+    po = np.array(pool, dtype=np.int32, order="C", copy=True)
+    sw = np.array(slot_words, dtype=np.int32, order="C", copy=True)
+    if po.ndim != 2 or po.shape[0] != 2 or po.shape[1] < 2 or sw.ndim != 2 or sw.shape[0] != 3:
+        raise ValueError("pool [2][capacity + 1] and slot_words [3][max_live] are required")
+    cu = None if cum is None else np.ascontiguousarray(cum, dtype=np.int32).ravel()
+    qq = None if q is None else np.ascontiguousarray(q, dtype=np.int32).ravel()
+    if (cu is None) != (qq is None) or (cu is not None and cu.size != qq.size):
+        raise ValueError("cum and q come together, equally long")
+    ga = gp = None
+    gin = 0
+    if g is not None:
+        ga = np.ascontiguousarray(g, dtype=np.float32)
+        gp = np.array(gpool, dtype=np.float32, order="C", copy=True)
+        if ga.ndim != 2 or gp.ndim != 2 or ga.shape[0] != gp.shape[0] or ga.shape[1] != sl.size or gp.shape[1] != sw.shape[1]:
+            raise ValueError("g [gin][B] and gpool [gin][max_live] are required")
+        gin = ga.shape[0]
+    _check(lib, lib.sts_debug_adopt_tables(device, None if ga is None else ga.ctypes.data, gin, sl.size, None if gp is None else gp.ctypes.data,
+                                           sw.shape[1], None if cu is None else cu.ctypes.data, None if qq is None else qq.ctypes.data,
+                                           0 if cu is None else cu.size, po.ctypes.data, po.shape[1] - 1, sw.ctypes.data, sl.ctypes.data,
+                                           so.ctypes.data, nn.ctypes.data, do.ctypes.data, hh.ctypes.data))
+    return gp, po, sw
 
 
 def speaker_mix_check(speaker_num: int, gin: int, mixes) -> None:
@@ -1041,10 +1083,21 @@ class Synthesizer:
         return int(self.lib.sts_stream_halo_frames(self.h))
 
     # -- open streams (sts_stream_open .. sts_stream_close) -----------------------------------
-    def stream_open(self, chunk_frames: int, max_live: int, capacity_frames: int):
+    def stream_open(self, chunk_frames: int, max_live: int, capacity_frames: int, capacity_phonemes: int = 0):
         """Opens the engine's stream: utterances are admitted between its steps (``stream_admit``), every ``stream_step`` decodes the next
-        chunk of each live one.  Fixes chunk size, output rate, limiter, conv mode and conv math until ``stream_close``."""
-        _check(self.lib, self.lib.sts_stream_open(self.h, int(chunk_frames), int(max_live), int(capacity_frames)))
+        chunk of each live one.  Fixes chunk size, output rate, limiter, conv mode and conv math until ``stream_close``.
+        ``capacity_phonemes`` > 0 opens a planned stream (sts_stream_open_ex): ``set_duration_plan``, ``set_speaker_mix``,
+        ``set_gain_plan`` and ``set_forced_durations`` then apply to the next ``stream_admit``; 0 is sts_stream_open."""
+        if capacity_phonemes:
+            _check(self.lib, self.lib.sts_stream_open_ex(self.h, int(chunk_frames), int(max_live), int(capacity_frames), int(capacity_phonemes)))
+        else:
+            _check(self.lib, self.lib.sts_stream_open(self.h, int(chunk_frames), int(max_live), int(capacity_frames)))
+
+    def stream_tables_info(self) -> dict:
+        """The phoneme pool of a planned open stream (sts_stream_tables_info); zeros when none is open."""
+        pl, cap, fr = C.c_int32(), C.c_int64(), C.c_int64()
+        _check(self.lib, self.lib.sts_stream_tables_info(self.h, C.addressof(pl), C.addressof(cap), C.addressof(fr)))
+        return {"planned": bool(pl.value), "capacity_phonemes": int(cap.value), "free_phonemes": int(fr.value)}
 
     def stream_admit(self, ids, sid: Optional[Sequence[int]] = None, length_scale: Optional[Sequence[float]] = None, noise=None):
         """Admits the utterances ``ids`` as one packed batch.  ``noise``: None (the engine's setting, utterance b with seed + b) or one
@@ -1629,18 +1682,30 @@ class Pool:
             raise StsError(f"sts_pool_create: {rc}: {self.lib.sts_pool_last_error().decode()}")
 
     def submit_stream(self, ids: Sequence[int], chunk_frames: int, on_chunk, sid: int = 0, length_scale: float = 1.0,
-                      noise_scale: float = 0.0, noise_scale_w: float = 0.0, seed: int = 0) -> int:
+                      noise_scale: float = 0.0, noise_scale_w: float = 0.0, seed: int = 0, plan=None, mix=None, gain=None) -> int:
         """Queue one streaming request (sts_pool_submit_stream).  ``on_chunk(pcm: np.int16[], sample_offset)`` runs on the pool's worker
         thread (return True to stop this request); it must not wait on a ticket of this pool.  ``wait(ticket)`` then returns the number of
-        samples delivered."""
+        samples delivered.  ``plan``, ``mix``, ``gain``: this request's own duration plan, speaker mix and gain plan, each None or a mapping
+        as the ``Synthesizer.set_*`` of its kind takes per utterance (sts_pool_submit_stream_ex; any combination)."""
         a = np.ascontiguousarray(ids, dtype=np.int32)
 
         def _cb(user, pcm, ns, off):
             arr = np.ctypeslib.as_array(pcm, shape=(ns,)).copy() if ns else np.zeros(0, np.int16)
             return 1 if on_chunk(arr, off) else 0
         cb = CHUNK_CB(_cb)
-        t = int(self.lib.sts_pool_submit_stream(self.h, a.ctypes.data, a.size, sid, length_scale, float(noise_scale), float(noise_scale_w),
-                                                int(seed) & 0xFFFFFFFFFFFFFFFF, int(chunk_frames), cb, None))
+        if plan is None and mix is None and gain is None:
+            t = int(self.lib.sts_pool_submit_stream(self.h, a.ctypes.data, a.size, sid, length_scale, float(noise_scale), float(noise_scale_w),
+                                                    int(seed) & 0xFFFFFFFFFFFFFFFF, int(chunk_frames), cb, None))
+        else:
+            keep, ptr = [], [None, None, None]
+            if plan is not None:
+                _, arr, k = _dur_plans([a.size], [plan]); keep += [arr, k]; ptr[0] = C.cast(arr, C.c_void_p)
+            if mix is not None:
+                arr, k = _speaker_mixes([mix]); keep += [arr, k]; ptr[1] = C.cast(arr, C.c_void_p)
+            if gain is not None:
+                _, arr, k = _gain_plans([a.size], [gain]); keep += [arr, k]; ptr[2] = C.cast(arr, C.c_void_p)
+            t = int(self.lib.sts_pool_submit_stream_ex(self.h, a.ctypes.data, a.size, sid, length_scale, float(noise_scale), float(noise_scale_w),
+                                                       int(seed) & 0xFFFFFFFFFFFFFFFF, int(chunk_frames), cb, None, ptr[0], ptr[1], ptr[2]))
         if t <= 0:
             raise StsError(f"sts_pool_submit_stream: {t}: {self.lib.sts_pool_last_error().decode()}")
         self._streams[t] = cb

@@ -27,7 +27,8 @@ are queued together and run as one group, and one more client that submits its r
 legs: admission off (the group is a closed stream: the late client waits until it has drained) and on (sts_pool_set_stream_admission: the
 late client is admitted between two steps).  Per leg: the late client's time from submit to its first chunk, the group's first-chunk
 times, and the group's last-chunk time with and without the late client.  A library without the switch (an older build) runs the off leg
-only.
+only.  --plans: the late client and every second member of the group carry a duration plan, a gain plan and (a multi-speaker model) a
+speaker mix (sts_pool_submit_stream_ex): the planned late client.
 """
 from __future__ import annotations
 
@@ -97,8 +98,22 @@ def _whole_joined(syn, ids, chunk):
     return [t], t, pcm.size, t
 
 
-def _late_run(pool, ids, late_ids, chunk, with_late):
-    """one group of len(ids) streaming requests queued together behind a gate request, the late one submitted from client 0's second chunk"""
+def _tables(cfg, n):
+    """--plans: one request's tables of all three kinds -- a rate span, a -6 dB span with 5 ms ramps, and (a multi-speaker model) a blend
+    of two table rows -- as Pool.submit_stream takes them"""
+    rate = np.ones(n, np.float32)
+    rate[n // 4:n // 2] = 1.1
+    db = np.zeros(n, np.float32)
+    db[n // 2:3 * n // 4] = -6.0
+    t = {"plan": {"rate": rate}, "gain": {"gain_db": db, "ramp_ms": 5.0}}
+    if cfg.is_ms:
+        t["mix"] = {"sid": [0, int(cfg.spk_num) - 1], "weight": [0.7, 0.3]}
+    return t
+
+
+def _late_run(pool, ids, late_ids, chunk, with_late, tables=None):
+    """one group of len(ids) streaming requests queued together behind a gate request, the late one submitted from client 0's second chunk.
+    tables: the late client and every second member of the group carry them (sts_pool_submit_stream_ex)"""
     import threading
     gate_in, gate_go = threading.Event(), threading.Event()
     t0 = [0.0]
@@ -129,12 +144,12 @@ def _late_run(pool, ids, late_ids, chunk, with_late):
                 seen0[0] += 1
                 if seen0[0] == 2:          # the group's second step has delivered
                     late["submit"] = time.perf_counter()
-                    late["ticket"] = pool.submit_stream(late_ids, chunk, on_late)
+                    late["ticket"] = pool.submit_stream(late_ids, chunk, on_late, **(tables or {}))
             return False
         return cb
     tg = pool.submit_stream(ids[0][:8], chunk + 1, on_gate)
     gate_in.wait(60.0)
-    tickets = [pool.submit_stream(x, chunk, client(i)) for i, x in enumerate(ids)]
+    tickets = [pool.submit_stream(x, chunk, client(i), **((tables or {}) if i % 2 else {})) for i, x in enumerate(ids)]
     t0[0] = time.perf_counter()
     gate_go.set()
     pool.wait(tg)
@@ -157,6 +172,7 @@ def _late(a) -> None:
     chunk = int(a.chunks.split(",")[0])
     ids = [sb.synthetic_ids(a.phonemes, cfg.vocab, salt=u) for u in range(a.clients)]
     late_ids = sb.synthetic_ids(a.phonemes, cfg.vocab, salt=a.clients)
+    tables = _tables(cfg, a.phonemes) if a.plans else None
     for admission in (False, True):
         pool = engine.Pool(blob, device=0, n_engines=1, max_batch=2 * a.clients)
         if admission:
@@ -165,12 +181,14 @@ def _late(a) -> None:
                 break
             pool.set_stream_admission(True)
         for with_late in (False, True):
-            _late_run(pool, ids, late_ids, chunk, with_late)          # warm-up of this shape
-            runs = [_late_run(pool, ids, late_ids, chunk, with_late) for _ in range(a.reps)]
-            row = {"model": kind, "scenario": "late_arrival", "admission": admission, "late_client": with_late, "clients": a.clients,
+            _late_run(pool, ids, late_ids, chunk, with_late, tables)          # warm-up of this shape
+            runs = [_late_run(pool, ids, late_ids, chunk, with_late, tables) for _ in range(a.reps)]
+            row = {"model": kind, "scenario": "late_arrival", "admission": admission, "late_client": with_late, "plans": bool(a.plans), "clients": a.clients,
                    "chunk_frames": chunk, "phonemes": a.phonemes, "reps": a.reps}
             for k in runs[0]:
                 row[k] = float(np.median([r[k] for r in runs])) if not isinstance(runs[0][k], bool) else all(r[k] for r in runs)
+            if with_late:
+                row["late_first_ms_runs"] = [round(r["late_first_ms"], 3) for r in runs]
             if hasattr(pool, "stream_stats"):
                 row["stream_groups"], row["admitted_midstream"] = pool.stream_stats()
             print(json.dumps(row), flush=True)
@@ -192,6 +210,7 @@ def main() -> None:
     ap.add_argument("--sentences", type=int, default=32)
     ap.add_argument("--late", action="store_true", help="a late arrival at a pool of one engine, stream admission off and on (first model, first chunk size)")
     ap.add_argument("--clients", type=int, default=32)
+    ap.add_argument("--plans", action="store_true", help="--late: the late client and half of the group carry a duration plan, a gain plan and (multi-speaker) a mix")
     a = ap.parse_args()
     if a.late:
         _late(a)
