@@ -100,8 +100,9 @@ int sts_infer_ids_batch_stream(sts_engine* e, int32_t B, const int32_t* const* i
 /* Open streams: a batched stream that admits new utterances between its steps.  One per engine; nothing here is on by default.
  *   sts_stream_open fixes the chunk size C = chunk_frames, the output rate, the limiter setting, the conv mode and the conv math, and
  *   allocates a latent pool of capacity_frames frames for at most max_live utterances at a time (1 <= max_live <= 1024;
- *   capacity_frames * inter_channels and capacity_frames * samples_per_frame at most 2 10^9).  STS_EINVAL while EQ bands are set, the
- *   loudness mode is not 0 or record taps are on (they need per-slot filter state: later work), or while a duration plan, speaker mix,
+ *   capacity_frames * inter_channels and capacity_frames * samples_per_frame at most 2 10^9).  STS_EINVAL while EQ bands are set without
+ *   sts_set_eq_streaming, the loudness mode is 1 without sts_set_loudness_streaming or is 2, or record taps are on (with the stream
+ *   modes on the EQ and the measurement run from per-slot state: "Per-slot filter state" below), or while a duration plan, speaker mix,
  *   gain plan or forced durations are pending (a pending table belongs to a next run, and open is not a run); STS_ESTATE when a stream is
  *   open.  sts_stream_open is the capacity_phonemes == 0 case of sts_stream_open_ex (below), which admits utterances WITH those tables.
  *   sts_stream_admit runs text encoder, duration predictor and flow of B newcomers as the packed batch a sts_infer_ids_batch_stream call
@@ -137,8 +138,8 @@ int sts_stream_info(const sts_engine* e, int32_t* open, int32_t* live, int32_t* 
 int sts_stream_close(sts_engine* e);
 /* Planned open streams: sts_stream_open_ex with capacity_phonemes in [1, 2^24] opens a stream whose admissions take the per-call tables of
  * a closed stream.  capacity_phonemes == 0 is sts_stream_open exactly (same refusals, same setters refused while open, same bits);
- * negative or larger: STS_EINVAL.  A planned stream refuses at open what sts_stream_open refuses (EQ bands, a loudness mode other than 0,
- * record taps, and a plan, mix, gain plan or forced durations pending AT open).
+ * negative or larger: STS_EINVAL.  A planned stream refuses at open what sts_stream_open refuses (EQ bands or loudness mode 1 without
+ * their stream modes, loudness mode 2, record taps, and a plan, mix, gain plan or forced durations pending AT open).
  *   While a planned stream is open sts_set_duration_plan, sts_set_speaker_mix, sts_set_gain_plan and sts_set_forced_durations return
  *   STS_OK, and what they set applies to the NEXT sts_stream_admit only, whatever its outcome (one that finds no room, *admitted = 0, and
  *   one that fails included).  That admission must have the B and n[b] the tables were set for: otherwise STS_EINVAL, nothing is admitted
@@ -151,13 +152,14 @@ int sts_stream_close(sts_engine* e);
  *   samples bit for bit.  Equality: every utterance's chunks equal those of sts_infer_ids_stream with the same tables set just before
  *   it, under the terms of an unplanned stream.  After an admission sts_get_durations and sts_get_phoneme_offsets report the admitted
  *   utterances, packed as after sts_infer_ids_batch_stream (so for a plain stream too).
- *   Still refused or unsupported, as before: the EQ and loudness in an open stream (per-slot filter state, the next step), record taps,
- *   plans in open paragraphs (sts_para_*) and sts_multi_*.
+ *   Still refused or unsupported: loudness mode 2 and record taps in an open stream, the EQ, loudness and plans in open paragraphs
+ *   (sts_para_*), and sts_multi_*.
  *   sts_stream_tables_info: any output may be NULL; *planned = 1 for an open planned stream, the pool's capacity and its free columns
  *   (zeros otherwise).
  *   These entries were added without a new STS_ABI_VERSION: detect them by symbol. */
 int sts_stream_open_ex(sts_engine* e, int32_t chunk_frames, int32_t max_live, int64_t capacity_frames, int64_t capacity_phonemes);
 int sts_stream_tables_info(const sts_engine* e, int32_t* planned, int64_t* capacity_phonemes, int64_t* free_phonemes);
+/* (The EQ and loudness in an open stream -- per-slot filter state -- and sts_stream_get_loudness: below, behind sts_get_loudness.) */
 /* The kernel that moves an admission's latents into the pool, on caller data (host pointers in and out): B column segments of the
  * channel-major src [C][ld_src] into dst [C][ld_dst]; segment b is len[b] columns from src_off[b] to dst_off[b].  dst comes back with
  * every element outside the destination ranges unchanged.  Ranges outside either matrix, overlapping destination ranges, B outside
@@ -271,6 +273,20 @@ typedef struct sts_loudness { float lufs; float peak; float gain; int32_t blocks
 int sts_set_loudness(sts_engine* e, int mode, float target_lufs, float peak_dbfs);
 int sts_get_loudness_mode(const sts_engine* e, int* mode, float* target_lufs, float* peak_dbfs);
 int sts_get_loudness(sts_engine* e, sts_loudness* out, int64_t capacity);
+/* Per-slot filter state: an open stream (planned or not) opened with EQ bands set and sts_set_eq_streaming on runs the streamed EQ on every
+ * slot, and one opened under loudness mode 1 with sts_set_loudness_streaming on measures every slot -- each slot from a carried state of
+ * its own, kept in pools the stream allocates at open for the stages that are on (per stream slot: 98.8 KB of EQ state, 66 KB of
+ * loudness state; and 132 bytes per tile of 8192 output samples for capacity_frames' samples / 8192 + max_live tiles).  An utterance of N
+ * output samples owns N / 8192 + 1 tiles from its admission to its retirement: admission is all or nothing over slots, frames, phonemes
+ * AND tiles (any one utterance that fits the empty frame pool fits the empty tile pool; a fragmented one may answer *admitted = 0).  Equality: every
+ * slot's chunks equal its sts_infer_ids_stream chunks under the same settings, under the terms above.  The four setters (sts_set_eq,
+ * sts_set_eq_streaming, sts_set_loudness, sts_set_loudness_streaming) return STS_ESTATE while the stream is open.
+ *   sts_stream_get_loudness: the slots retired by the most recent sts_stream_step of a measuring stream, in ascending slot order: their
+ *   count is returned, and min(count, capacity) entries are copied to slot_out / out (either may be NULL).  Each entry is what
+ *   sts_get_loudness reports after a closed stream of that utterance -- one its callback stopped: over what was delivered.  0 after a step
+ *   that retired nothing; STS_ESTATE with no stream open.  sts_get_loudness returns the same entries without the slots.
+ *   Added without a new STS_ABI_VERSION: detect it by symbol. */
+int sts_stream_get_loudness(sts_engine* e, int32_t* slot_out, sts_loudness* out, int64_t capacity);
 /* Host only (no device), like sts_resample_table: the K-weighting above for rate in [8000, 48000] as float64 {b0, b1, b2, a1, a2} of the
  * shelf, then of the high-pass. */
 int sts_kweight_coeffs(int32_t rate, double coeffs[10]);

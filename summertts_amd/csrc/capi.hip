@@ -174,6 +174,15 @@ int sts_stream_tables_info(const sts_engine* e, int32_t* planned, int64_t* capac
     if (free_phonemes) *free_phonemes = L ? L->free_phoneme_count() : 0;
     return STS_OK;
 }
+int sts_stream_get_loudness(sts_engine* e, int32_t* slot_out, sts_loudness* out, int64_t capacity) {
+    if (!e) return set_err(STS_EINVAL, "null engine");
+    if (!e->eng.live_) return set_err(STS_ESTATE, "no stream is open on this engine (sts_stream_open first)");
+    // (the two lists are filled and cleared together; the shorter one bounds the copy whatever happens)
+    const int64_t n = (int64_t)std::min(e->eng.loud_slots.size(), e->eng.loud_res.size()), m = std::min<int64_t>(n, std::max<int64_t>(capacity, 0));
+    if (slot_out && m > 0) memcpy(slot_out, e->eng.loud_slots.data(), (size_t)m * sizeof(int32_t));
+    if (out && m > 0) memcpy(out, e->eng.loud_res.data(), (size_t)m * sizeof(sts_loudness));
+    return (int)n;
+}
 int sts_stream_admit(sts_engine* e, int32_t B, const int32_t* const* ids, const int32_t* n, const int32_t* sid,
                      const float* length_scale, const sts_stream_noise* noise, int32_t* slot_out, int32_t* n_samples_out,
                      int32_t* admitted) {

@@ -1181,19 +1181,22 @@ int Engine::run_frame_workspace(RunCtx& c) {
         }
         // (a stream that runs the EQ: behind everything else, so that every other buffer lies where it lies without it)
         bf.eqst = nullptr; bf.eqsE = nullptr;
-        if (oc.eqst) {
+        // (an open stream keeps the carried states and the result tables in pools of its own, by slot: stream_step names them.  Only the
+        // step's tile end states and the gate's table and gains are of the step)
+        const bool slot_state = c.live && !c.join;
+        if (oc.eqst && !c.admission) {
             const int nu = c.join ? 1 : B;
-            bf.eqst = A.get<char>(eqs_state_bytes(nu));
+            if (!slot_state) bf.eqst = A.get<char>(eqs_state_bytes(nu));
             bf.eqsE = (double*)A.get<char>(eqs_ws_bytes(nu, eqs_max_tiles(c.Ocap)));
         }
         // (and a stream that measures loudness behind that: the result tables hold every tile of every utterance's whole length)
         bf.ldst = nullptr; bf.ldsE = nullptr; bf.ldres = nullptr;
-        if (oc.lst) {
+        if (oc.lst && !c.admission) {
             const int nu = c.join ? 1 : B;
             long long tiles = 0;
             if (c.join) tiles = lds_utt_tiles(out_count(c.FJ * hop));
-            else for (int b = 0; b < B; b++) tiles += lds_utt_tiles(out_count((long long)p_lenF[b] * hop));
-            bf.ldst = A.get<char>(lds_state_bytes(nu));
+            else if (!slot_state) for (int b = 0; b < B; b++) tiles += lds_utt_tiles(out_count((long long)p_lenF[b] * hop));
+            if (!slot_state) bf.ldst = A.get<char>(lds_state_bytes(nu));
             bf.ldsE = (double*)A.get<char>(lds_ws_bytes(nu, lds_max_tiles(c.Ocap)));
             bf.ldres = A.get<char>(lds_res_bytes(nu, tiles));
         }
@@ -1411,7 +1414,7 @@ int Engine::run_once(int B, const int32_t* const* ids, const int32_t* n, const i
     for (double& f : bytes_w_) f = 0;
     mfma_flops_ = 0; mfma_exec_ = 0; bf16_exec_ = 0; mfma_launches_ = 0; in_mfma_region_ = false;
 
-    loud_res.clear(); lim_res.clear(); last_join_start.clear();
+    loud_res.clear(); loud_slots.clear(); lim_res.clear(); last_join_start.clear();
     if (ss && loud_mode != 0 && !loud_streaming)
         return fail(STS_EINVAL, "streaming is not available while loudness measurement or normalization is on (sts_set_loudness mode 0 first): "
                                 "normalizing needs the whole utterance before its first sample leaves");
@@ -1565,8 +1568,12 @@ struct StreamRun {
     int16_t* dst = nullptr;
     // the streamed EQ and streamed loudness: how far each utterance (a joined stream: J) is consumed and which state slot a step reads; the
     // slots flip only behind a step that does not run again.  Loudness: the call's result tables, which the gate reads behind the last step
-    EqsTrack eqt; LdsTrack ldt;
+    // (an open stream: its own tracks, by slot, which persist from step to step -- eqt / ldt name them; its result tables are its tile
+    // pool's, and hu is pinned room behind the step tables for the gate's table of the step's retiring slots)
+    EqsTrack eqt_call; LdsTrack ldt_call;
+    EqsTrack* eqt = &eqt_call; LdsTrack* ldt = &ldt_call;
     double* ld_tsum = nullptr; float* ld_tpeak = nullptr; float* ld_gain = nullptr;
+    long long* hu = nullptr;
 };
 // the windows the output side of a step sees: a plain step's nw decode windows, a joined step's one window of J
 struct StreamTail {
@@ -1605,24 +1612,32 @@ int Engine::run_stream_steps(RunCtx& c) {
     std::vector<char> live(B, 1);
     if (ss->delivered) for (int b = 0; b < (joined ? 1 : B); b++) ss->delivered[b] = 0;
     d_pcm = nullptr; total_samples = 0;
-    s.eqt.begin(joined ? 1 : B);
-    if (call.sld) {     // the call's result tables, every utterance's tiles at its place
-        if (loud_k_rate_ != out_rate) {
-            if (!loud_coef(out_rate, &loud_k_)) return fail(STS_EINVAL, "loudness: output rate outside [8000, 48000]");
-            loud_k_rate_ = out_rate;
-        }
+    // an open stream with per-slot filter state (live_stream.hpp): positions and parity are the stream's, the rows name slots.  The one
+    // parity is enough because every live slot has a window in this and every step
+    const bool slot_eq = open && !para && open->eq_on && call.seq, slot_ld = open && !para && open->loud_on && call.sld;
+    if (slot_eq) { s.eqt = &open->eqt; s.eqt->drop(); } else s.eqt->begin(joined ? 1 : B);
+    if (call.sld && loud_k_rate_ != out_rate) {
+        if (!loud_coef(out_rate, &loud_k_)) return fail(STS_EINVAL, "loudness: output rate outside [8000, 48000]");
+        loud_k_rate_ = out_rate;
+    }
+    if (slot_ld) {      // the stream's result tables; of the step: the gate's table and gains
+        s.ldt = &open->ldt; s.ldt->drop();
+        s.ld_tsum = open->tsum; s.ld_tpeak = open->tpeak; s.ld_gain = (float*)(bf.ldres + (size_t)B * 3 * 8);
+    } else if (call.sld) {     // the call's result tables, every utterance's tiles at its place
         const int nu = joined ? 1 : B;
         std::vector<long long> Nu(nu);
         if (joined) Nu[0] = out_count(c.FJ * hop);
         else for (int b = 0; b < B; b++) Nu[b] = out_count((long long)lenF[b] * hop);
-        s.ldt.begin(nu);
-        const long long tiles = s.ldt.layout(Nu.data());
+        s.ldt->begin(nu);
+        const long long tiles = s.ldt->layout(Nu.data());
         char* p = bf.ldres + (size_t)nu * 3 * 8;            // (in front: the gate's table {0, samples consumed, first tile} per utterance)
         s.ld_tsum = (double*)p; p += (size_t)tiles * kLdsSlots * 8;
         s.ld_tpeak = (float*)p; p += (size_t)tiles * 4;
         s.ld_gain = (float*)p;
     }
     std::vector<int> wb; std::vector<StepWin> win; StepOut st;
+    std::vector<int> gated, stopped;                   // a measuring open stream: the slots this step's gate covers, those their callback stopped
+    std::vector<std::pair<int, sts_loudness>> lres;
     const long jsteps = joined ? (long)c.js.steps() : 0;
     const long k_first = para ? (long)c.para_k : 0;
     for (long k = k_first;; k++) {
@@ -1635,12 +1650,12 @@ int Engine::run_stream_steps(RunCtx& c) {
         if (nu == 0) break;
         // the step's tables (a joined step: of its own decode windows, none in a silence-only step, and of the one window of J)
         const char* bad;
-        if (joined) bad = step_build_joined(call, c.js, k, offF.data(), sidv.data(), s.eqt, s.ldt, s.ht, st);
+        if (joined) bad = step_build_joined(call, c.js, k, offF.data(), sidv.data(), *s.eqt, *s.ldt, s.ht, st);
         else {
             win.clear();        // (an open stream: the slot's own next frame)
             for (const int b : wb) win.push_back(StepWin{b, lenF[b], open ? open->slots[(size_t)c.live_slots[b]].f : k * Cf, offF[b], sidv[b],
-                                                         open && open->planned() ? c.live_slots[b] : -1});
-            bad = step_build(call, win.data(), nu, s.eqt, s.ldt, s.ht, st);
+                                                         open && open->planned() ? c.live_slots[b] : -1, open ? c.live_slots[b] : -1});
+            bad = step_build(call, win.data(), nu, *s.eqt, *s.ldt, s.ht, st);
         }
         if (bad) return fail(STS_EDEVICE, bad);
         const StepTab& t = st.tab;
@@ -1668,6 +1683,12 @@ int Engine::run_stream_steps(RunCtx& c) {
             tl.pack_src = tl.pack_dst = nullptr; tl.rs = t.j_rs; tl.lim = t.j_lim;
         }
         stream_tail(c, s, tl);
+        if (slot_ld) {      // the gate over the slots this step retires behind their last chunk (known now), behind the loudness launches
+            gated.clear();
+            for (const int b : wb) { const LiveSlot& sl = open->slots[(size_t)c.live_slots[b]]; if (sl.f + Cf >= sl.F) gated.push_back(c.live_slots[b]); }
+            for (size_t i = 0; i < gated.size(); i++) { s.hu[3 * i] = 0; s.hu[3 * i + 1] = s.ldt->pend[(size_t)gated[i]]; s.hu[3 * i + 2] = s.ldt->tbase[(size_t)gated[i]]; }
+            if (const int rc = live_loud_gate(c, s, (int)gated.size())) return rc;
+        }
         // where the step's chunks are on the device (nothing packed: the one window's kept samples, at its pack source in the decoder's own PCM)
         const int16_t* src = oc.chunk_in_place ? bf.pcm + st.src0 : s.dst;
         if (!stream_direct) HIPCK(hipMemcpyAsync(s.hp, src, (size_t)st.dsum * 2, hipMemcpyDeviceToHost, stream));
@@ -1680,12 +1701,13 @@ int Engine::run_stream_steps(RunCtx& c) {
             h2_fallbacks++;
             conv_math = 0;                                 // (run() restores the setting)
             k--;                                           // this step again, every window of it
-            s.eqt.drop();                                  // (from the state the first attempt started from)
-            if (call.sld) s.ldt.drop();
+            s.eqt->drop();                                 // (from the state the first attempt started from)
+            if (call.sld) s.ldt->drop();
             continue;
         }
-        s.eqt.commit();
-        if (call.sld) s.ldt.commit();
+        s.eqt->commit();
+        if (call.sld) s.ldt->commit();
+        if (slot_ld) { lres.clear(); stopped.clear(); for (size_t i = 0; i < gated.size(); i++) lres.emplace_back(gated[i], ((const sts_loudness*)loud_host_)[i]); }
         for (int i = 0; i < nu; i++) {                     // ascending utterance order
             const int b = wb[i];
             const int16_t* pcm = s.hp + st.dst[i];
@@ -1694,11 +1716,26 @@ int Engine::run_stream_steps(RunCtx& c) {
             if (ss->delivered) ss->delivered[b] += n;
             if (open && !para) {       // (utt = the slot; it moves on by a chunk, and retires behind its last one or at its stop)
                 const int sl = c.live_slots[b];
-                open->delivered(sl, ss->cb(ss->user, sl, pcm, n, j0) != 0);
+                const bool stop = ss->cb(ss->user, sl, pcm, n, j0) != 0;
+                if (slot_ld && stop && std::find(gated.begin(), gated.end(), sl) == gated.end()) stopped.push_back(sl);
+                open->delivered(sl, stop);
             } else if (para) {       // (the one signal; para_step moves the paragraph on)
                 c.para_stop = ss->cb(ss->user, 0, pcm, n, j0) != 0;
             } else if (ss->cb(ss->user, b, pcm, n, j0) != 0) live[b] = 0;
         }
+    }
+    if (slot_ld) {
+        // a slot its callback stopped is gated over what it delivered, as a closed stream's utterance is -- known only behind the step's
+        // synchronisation, so these (rare) slots cost a launch and a synchronisation of their own
+        if (!stopped.empty()) {
+            for (size_t i = 0; i < stopped.size(); i++) { s.hu[3 * i] = 0; s.hu[3 * i + 1] = s.ldt->e[(size_t)stopped[i]]; s.hu[3 * i + 2] = s.ldt->tbase[(size_t)stopped[i]]; }
+            if (const int rc = live_loud_gate(c, s, (int)stopped.size())) return rc;
+            HIPCK(hipStreamSynchronize(stream));
+            for (size_t i = 0; i < stopped.size(); i++) lres.emplace_back(stopped[i], ((const sts_loudness*)loud_host_)[i]);
+            std::sort(lres.begin(), lres.end(), [](const auto& x, const auto& y) { return x.first < y.first; });
+        }
+        for (const auto& r : lres) { loud_slots.push_back(r.first); loud_res.push_back(r.second); }
+        return STS_OK;
     }
     return call.sld ? stream_loud_gate(c, s) : STS_OK;
 }
@@ -1708,11 +1745,13 @@ int Engine::run_stream_steps(RunCtx& c) {
 int Engine::stream_host_buffers(RunCtx& c, StreamRun& s) {
     RUN_ALIASES(c)
     const size_t hp_off = (up_bytes + ((size_t)Ttot + B) * 4 + 255) & ~(size_t)255;
-    const size_t tab_room = (StepTab(B, c.gain, c.oc.eqst, c.oc.lst, c.join).bytes + 255) & ~(size_t)255;
+    const size_t tab_only = (StepTab(B, c.gain, c.oc.eqst, c.oc.lst, c.join).bytes + 255) & ~(size_t)255;
+    const size_t tab_room = tab_only + (c.live && c.oc.lst ? ((size_t)B * 3 * 8 + 255) & ~(size_t)255 : 0);     // (an open stream: the gate's table)
     const size_t pcm_bytes = (size_t)c.Ocap * 2 + 256;
     if (!ensure_pinned(hp_off + tab_room + pcm_bytes)) return fail(STS_EDEVICE, "pinned host allocation failed");
     c.pm = (int*)pinned_;
     s.ht = pinned_ + hp_off;
+    s.hu = (long long*)(s.ht + tab_only);
     s.hp = (int16_t*)(pinned_ + hp_off + tab_room);
     s.dst = c.oc.run[OS_PACK] ? bf.spack : bf.pcm;
     if (stream_direct) {
@@ -1749,13 +1788,13 @@ void Engine::stream_tail(RunCtx& c, const StreamRun& s, const StreamTail& t) {
         EqArgs a{};
         a.x = c.stage_out(oc.src[OS_EQ]); a.S = c.eqS; a.tab = d_eq_;
         a.y = bf.wave_eq; a.pcm = oc.writer == OS_EQ ? s.dst : nullptr;
-        a.E = bf.eqsE; a.state = bf.eqst; a.slot = s.eqt.slot; a.wtab = (const long long*)(bf.stab + t.eq);
+        a.E = bf.eqsE; a.state = bf.eqst; a.slot = s.eqt->slot; a.wtab = (const long long*)(bf.stab + t.eq);
         eq_stream_run(a, t.n, t.etiles, stream);
     }
     if (oc.lst) {           // its two launches follow the stage it reads: the nearest running float stage in front of it
         LoudStreamArgs a{};
         a.x = c.stage_out(oc.src[OS_LOUD]); a.k = loud_k_;
-        a.wtab = (const long long*)(bf.stab + t.loud); a.state = bf.ldst; a.slot = s.ldt.slot;
+        a.wtab = (const long long*)(bf.stab + t.loud); a.state = bf.ldst; a.slot = s.ldt->slot;
         a.E = bf.ldsE; a.tsum = s.ld_tsum; a.tpeak = s.ld_tpeak;
         loud_stream_run(a, t.n, t.ltiles, stream);
     }
@@ -1773,7 +1812,7 @@ void Engine::stream_tail(RunCtx& c, const StreamRun& s, const StreamTail& t) {
 int Engine::stream_loud_gate(RunCtx& c, StreamRun& s) {
     const int nu = c.join ? 1 : c.B;
     long long* hu = (long long*)s.ht;                       // (the step tables' pinned room: every upload from it has completed)
-    for (int b = 0; b < nu; b++) { hu[3 * b] = 0; hu[3 * b + 1] = s.ldt.e[b]; hu[3 * b + 2] = s.ldt.tbase[b]; }
+    for (int b = 0; b < nu; b++) { hu[3 * b] = 0; hu[3 * b + 1] = s.ldt->e[b]; hu[3 * b + 2] = s.ldt->tbase[b]; }
     HIPCK(hipMemcpyAsync(c.bf.ldres, hu, (size_t)nu * 3 * 8, hipMemcpyHostToDevice, stream));
     LoudArgs g{};
     g.k = loud_k_; g.target = loud_target; g.ceiling = loud_peak; g.no_clamp = c.oc.loud_no_clamp;
@@ -1781,6 +1820,18 @@ int Engine::stream_loud_gate(RunCtx& c, StreamRun& s) {
     loud_gate_run(g, nu, stream);
     HIPCK(hipStreamSynchronize(stream));
     loud_res.assign((const sts_loudness*)loud_host_, (const sts_loudness*)loud_host_ + nu);
+    return STS_OK;
+}
+
+// a measuring open stream's gate over n slots of a step (their rows {0, samples consumed, first tile} at s.hu): results to the host-mapped
+// block in that order, covered by the next synchronisation
+int Engine::live_loud_gate(RunCtx& c, StreamRun& s, int n) {
+    if (n <= 0) return STS_OK;
+    HIPCK(hipMemcpyAsync(c.bf.ldres, s.hu, (size_t)n * 3 * 8, hipMemcpyHostToDevice, stream));
+    LoudArgs g{};
+    g.k = loud_k_; g.target = loud_target; g.ceiling = loud_peak; g.no_clamp = c.oc.loud_no_clamp;
+    g.utab = (long long*)c.bf.ldres; g.tsum = s.ld_tsum; g.tpeak = s.ld_tpeak; g.gain = s.ld_gain; g.out = loud_dev_;
+    loud_gate_run(g, n, stream);
     return STS_OK;
 }
 
@@ -1817,8 +1868,9 @@ int Engine::stream_open(int chunk_frames, int max_live, long long capacity_frame
     if (capacity_phonemes < 0 || capacity_phonemes > (1 << 24)) return fail(STS_EINVAL, "an open stream's capacity_phonemes is 0 (no tables) or in [1, 2^24]");
     if ((double)capacity_frames * M.inter > 2.0e9 || (double)capacity_frames * M.hop_total > 2.0e9)
         return fail(STS_EINVAL, "an open stream's capacity_frames * inter_channels and capacity_frames * samples_per_frame may not exceed 2 10^9");
-    if (eq_n > 0) return fail(STS_EINVAL, "an open stream is not available while an equaliser is set: its state is carried per utterance in the frame arena");
-    if (loud_mode != 0) return fail(STS_EINVAL, "an open stream is not available while loudness measurement or normalization is on: its state is carried per utterance in the frame arena");
+    // (with their stream modes on, the EQ and loudness mode 1 run from per-slot state: the pools below.  Mode 2 needs the whole utterance)
+    if (eq_n > 0 && !eq_streaming) return fail(STS_EINVAL, "an open stream is not available while an equaliser is set: its state is carried per utterance in the frame arena");
+    if (loud_mode == 2 || (loud_mode != 0 && !loud_streaming)) return fail(STS_EINVAL, "an open stream is not available while loudness measurement or normalization is on: its state is carried per utterance in the frame arena");
     if (record_taps) return fail(STS_EINVAL, "an open stream is not available while taps are recorded");
     if (have_plan || have_mix || have_gain || have_forced)
         return fail(STS_EINVAL, "an open stream is not available while a duration plan, a speaker mix, a gain plan or forced durations are pending: their tables are per call");
@@ -1826,6 +1878,7 @@ int Engine::stream_open(int chunk_frames, int max_live, long long capacity_frame
     LimiterDesign d{};
     if (lim_mode != 0 && !limiter_design(out_rate, lim_gain_db, lim_ceiling, lim_ms, &d)) return fail(STS_EINVAL, "limiter: output rate outside [8000, 48000]");
     if (conv_math == 3) { const int rc = ensure_overflow_word(); if (rc != STS_OK) return rc; }
+    if (eq_n > 0) { const int rc = eq_prepare(); if (rc != STS_OK) return rc; }     // (the rate and the bands are fixed from here to close)
     LiveStream* L = new (std::nothrow) LiveStream();
     if (!L) return fail(STS_EDEVICE, "out of host memory");
     L->open(chunk_frames, max_live, capacity_frames, capacity_phonemes);
@@ -1847,6 +1900,28 @@ int Engine::stream_open(int chunk_frames, int max_live, long long capacity_frame
     }
     if (poison && hipMemsetD32Async((hipDeviceptr_t)L->zpool, (int)poison, pool_bytes / 4, stream) != hipSuccess) (void)hipGetLastError();
     live_ = L;
+    loud_res.clear(); loud_slots.clear();       // (sts_stream_get_loudness: nothing has retired in this stream)
+    // per-slot filter state (live_stream.hpp), for the stages that are on only: the EQ's and loudness' carried states, two state slots per
+    // stream slot, and loudness' result tables over the tile pool -- [eqst | ldst | tsum | tpeak] in one allocation (an open costs the
+    // pool's group its first chunk).  Nothing is cleared, here or at an admission: a slot's first step reads no state (e == 0)
+    const bool feq = eq_n > 0, fld = loud_mode == 1;
+    if (feq || fld) {
+        L->open_filters(feq, fld);
+        const size_t eb = feq ? eqs_state_bytes(max_live) : 0, lb = fld ? lds_state_bytes(max_live) : 0;
+        const size_t sb = (size_t)L->capacity_tiles * kLdsSlots * 8, pb = ((size_t)L->capacity_tiles * 4 + 255) & ~(size_t)255;
+        bool ok = hipMalloc(&L->filters_dev, eb + lb + sb + pb) == hipSuccess;
+        if (ok) {
+            char* p = (char*)L->filters_dev;
+            if (feq) L->eqst = p;
+            if (fld) { L->ldst = p + eb; L->tsum = (double*)(p + eb + lb); L->tpeak = (float*)(p + eb + lb + sb); }
+        }
+        if (ok && poison) ok = hipMemsetD32Async((hipDeviceptr_t)L->filters_dev, (int)poison, (eb + lb + sb + pb) / 4, stream) == hipSuccess;
+        if (!ok) {
+            (void)hipGetLastError();
+            (void)stream_close();        // (frees whatever was allocated)
+            return fail(STS_EDEVICE, "out of device memory (the open stream's filter state)");
+        }
+    }
     if (!planned) return STS_OK;
     // the planned stream's pools: each slot's conditioning vector [gin][max_live] (a multi-speaker model with a conditioned decoder only),
     // the phoneme pool [cum | q][capacity_phonemes + 1] (the last column: the shared neutral row), the slot words [off | n | h][max_live]
@@ -1877,10 +1952,12 @@ int Engine::stream_close() {
     if (stream) (void)hipStreamSynchronize(stream);
     if (live_->zpool) (void)hipFree(live_->zpool);
     if (live_->tables_dev) (void)hipFree(live_->tables_dev);
+    if (live_->filters_dev) (void)hipFree(live_->filters_dev);
     if (live_->tab_dev) (void)hipFree(live_->tab_dev);
     if (live_->tab_host) (void)hipHostFree(live_->tab_host);
     delete live_;
     live_ = nullptr;
+    loud_res.clear(); loud_slots.clear();       // (a stream's results end with it)
     return STS_OK;
 }
 
@@ -1897,6 +1974,7 @@ int Engine::stream_admit_once(int B, const int32_t* const* ids, const int32_t* n
     StreamSpec ss{L.chunk, [](void*, int32_t, const int16_t*, int32_t, int32_t) { return 0; }, nullptr};
     RunCtx c;
     c.B = B; c.ids = ids; c.n = n; c.sid = sid; c.ls = ls; c.ss = &ss; c.bstream = B > 1;
+    c.admission = true;                                        // (no output stage runs: the frame workspace holds nothing of the filters)
     int rc;
     if ((rc = run_setup(c)) != STS_OK) return rc;
     mark(0);
@@ -2030,6 +2108,9 @@ int Engine::stream_step(int (*cb)(void*, int32_t, const int16_t*, int32_t, int32
     if ((rc = plan_output(c)) != STS_OK) return rc;
     if ((rc = run_frame_workspace(c)) != STS_OK) return rc;
     c.bf.z = L.zpool; c.Fld = L.capacity;
+    // (and the carried filter states are the pools: run_frame_workspace carves none for an open stream)
+    if (c.oc.eqst) c.bf.eqst = L.eqst;
+    if (c.oc.lst) { c.bf.ldst = L.ldst; loud_res.clear(); loud_slots.clear(); }      // (the results of this step's retiring slots alone)
     const int math = conv_math;
     if (math == 3 && L.form0) conv_math = 0;
     if (conv_math == 3) *(volatile unsigned*)ovf_host_ = 0u;

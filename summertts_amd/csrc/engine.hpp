@@ -275,6 +275,7 @@ private:
     int stream_host_buffers(RunCtx& c, StreamRun& s);                        // the pinned table room and the chunks' host buffer
     void stream_tail(RunCtx& c, const StreamRun& s, const StreamTail& t);    // a step's launches behind the decoder (the join)
     int stream_loud_gate(RunCtx& c, StreamRun& s);                           // a measuring stream's gate, once behind the last step
+    int live_loud_gate(RunCtx& c, StreamRun& s, int n);                      // a measuring open stream's gate over n retiring slots of a step
     int stream_admit_once(int B, const int32_t* const* ids, const int32_t* n, const int32_t* sid, const float* ls, int32_t* slot_out,
                           int32_t* n_samples_out, int32_t* admitted);
     int para_append_once(int B, const int32_t* const* ids, const int32_t* n, const int32_t* sid, const float* ls, const long long* gap,
@@ -327,8 +328,10 @@ public:
     // stream_admit runs front and flow of B newcomers as the packed batch a sts_infer_ids_batch_stream call of them would, and moves their z
     // into the pool (adopt_z); all or nothing (*admitted = B, or 0: no room now).  stream_step is ONE step of run_stream_steps over every
     // live slot in ascending slot order, each at its own next frame; a slot retires behind its last chunk or when its callback returns
-    // non-zero.  While a stream is open every other run and every setter of what open fixed returns STS_ESTATE.  Refused by stream_open
-    // (later work): EQ bands, loudness and record taps -- they need per-slot filter state -- and a duration plan / speaker mix / gain plan /
+    // non-zero.  While a stream is open every other run and every setter of what open fixed returns STS_ESTATE.  With eq_streaming the
+    // EQ, and with loud_streaming loudness mode 1, run from per-slot state in pools allocated at open (live_stream.hpp "per-slot filter
+    // state"); the slots a step retires are gated inside it, their results in loud_res with their slots in loud_slots.  Refused by
+    // stream_open: EQ bands and mode 1 without their stream modes, mode 2, record taps, and a duration plan / speaker mix / gain plan /
     // forced durations pending AT OPEN (a pending table belongs to a next run, and open is not one).  Not to be called from a chunk callback.
     // capacity_phonemes > 0: a PLANNED stream (sts_stream_open_ex; live_stream.hpp, DESIGN.md 9c "Planned open streams").  Its four table
     // setters work while it is open and apply to the next stream_admit only, whatever its outcome; what a step needs of them (each slot's
@@ -358,6 +361,9 @@ public:
     int para_step(int (*cb)(void*, int32_t, const int16_t*, int32_t, int32_t), void* user, int32_t* ready_after);
     int para_close();
     ParaStream* para_ = nullptr;       // null: no paragraph is open
+    // a measuring open stream: the slots retired by the most recent step that measured, ascending -- loud_res holds their results in
+    // this order (sts_stream_get_loudness)
+    std::vector<int32_t> loud_slots;
     // loudness in a stream (sts_set_loudness_streaming; loudness.hip's stream mode, loud_stream.hpp): off, a stream under mode 1 or 2 is
     // refused; on, mode 1 measures what each step delivers from a state carried per utterance in the frame arena (mode 2 stays refused)
     bool loud_streaming = false;

@@ -16,14 +16,26 @@
 // [off | n | h][max_live] the gain kernel indexes by slot.  The pool's last column is the shared neutral row (cum 0, q 2^20): a slot
 // without a gain plan points its words at it {capacity_phonemes, 1, 0}, for which the gain kernel's envelope is 1.0f at every sample.
 //
-// Not admitted (the open stream refuses them when it is opened; later work): the EQ and loudness in a stream (state carried per
-// utterance in the frame arena, which every admission lays out again: they need per-slot filter state) and record taps.  An unplanned
-// stream (capacity_phonemes == 0) refuses the per-call tables too, as it always has.
+// PER-SLOT FILTER STATE (open_filters; DESIGN.md 9c "Per-slot filter state"): an open stream runs the streamed EQ (sts_set_eq_streaming)
+// and measures loudness (mode 1 with sts_set_loudness_streaming) from states that survive the arenas in pools of the stream's own,
+// indexed by SLOT as the kernels index them by the row's utterance: the EQ's and loudness' two state slots per stream slot, and the
+// loudness result tables tsum / tpeak over a TILE pool -- a slot of N output samples owns lds_utt_tiles(N) tiles, first fit over a third
+// free list.  The consumed positions (EqsTrack / LdsTrack, sized max_live) persist between steps; an admission sets its slot's to 0, and
+// the kernels read no state at e == 0, so a retired slot's stale state is never read and nothing is cleared.  The tracks' ONE parity
+// suffices: every live slot has a window in every step, so every live slot's state was written by the last committed step, into the
+// slot the global flip then names (a newcomer reads none and writes where the others write).
+//
+// Not admitted (the open stream refuses them when it is opened): loudness normalization (mode 2: the gain needs the whole utterance),
+// record taps, and the EQ or loudness without their stream modes.  An unplanned stream (capacity_phonemes == 0) refuses the per-call
+// tables too, as it always has.
 #pragma once
 #include <stdint.h>
 
 #include <algorithm>
 #include <vector>
+
+#include "eq_stream.hpp"
+#include "loud_stream.hpp"
 
 namespace sts {
 
@@ -45,7 +57,8 @@ static inline StreamWin stream_window(long F, long f0, long C, long halo, long h
 
 // one live utterance: its columns [off, off + F) of the pool, its speaker, the first frame of its next chunk
 // (a planned stream: its columns [poff, poff + pn) of the phoneme pool when it carries a gain plan, has_gain)
-struct LiveSlot { bool live = false; long long off = 0; long F = 0; int sid = 0; long f = 0; long long poff = 0; int pn = 0; bool has_gain = false; };
+// (a measuring stream: its tiles [toff, toff + tn) of the result tables)
+struct LiveSlot { bool live = false; long long off = 0; long F = 0; int sid = 0; long f = 0; long long poff = 0; int pn = 0; bool has_gain = false; long long toff = 0, tn = 0; };
 struct LiveRange { long long off, len; };
 
 // The capacity a group of `max_live` utterances needs when none is longer than `longest` frames: every slot can hold the longest one.
@@ -58,6 +71,12 @@ static inline long long live_capacity_rule(int max_live, long long longest) { re
 // gain-planned request with more phonemes than the EMPTY pool holds runs as a closed stream, as for frames.)
 constexpr long long kLivePoolPhonemes = 1024;
 static inline long long live_phoneme_rule(int max_live, long long longest) { return (long long)max_live * longest; }
+// The tile capacity of a measuring stream: an utterance of F <= capacity_frames frames owns out(F hop) / 8192 + 1 tiles, so any ONE
+// utterance that fits the EMPTY frame pool fits the empty tile pool.  (Several that fill the frame pool together usually fit too, but the
+// output count rounds up per utterance: their tiles may exceed the pool's by one -- the outcome is "no room now".)
+static inline long long live_tile_rule(long long capacity_frames, long hop, long long P, long long Q, int max_live) {
+    return stream_out_count(capacity_frames * hop, P, Q) / kLdsTile + max_live;
+}
 
 struct LiveStream {
     // fixed when the stream is opened
@@ -69,7 +88,13 @@ struct LiveStream {
     // a planned stream's pools, one allocation [gpool | ppool | swords] (null otherwise; gpool: a multi-speaker model with a conditioned
     // decoder only)
     void* tables_dev = nullptr; float* gpool = nullptr; int* ppool = nullptr; int* swords = nullptr;
+    // per-slot filter state (open_filters): which stages carry one, the tile pool's size, and the pools -- one allocation
+    // [eqst | ldst | tsum | tpeak], each only if its stage is on (null otherwise)
+    bool eq_on = false, loud_on = false; long long capacity_tiles = 0;
+    void* filters_dev = nullptr; char* eqst = nullptr; char* ldst = nullptr; double* tsum = nullptr; float* tpeak = nullptr;
     // state between steps
+    EqsTrack eqt; LdsTrack ldt;     // consumed positions by slot and the one parity (begun by open_filters, kept from step to step)
+    std::vector<LiveRange> free_tiles;                                     // the tile pool's free tiles, kept as the two lists below
     std::vector<LiveSlot> slots; std::vector<LiveRange> free_ranges;      // free_ranges: ascending, never adjacent (coalesced)
     std::vector<LiveRange> free_phonemes;                                  // the phoneme pool's free columns, kept the same way
     long long steps = 0;            // stream_step calls since open (STS_DBG_STREAM_RETRY_STEP counts them)
@@ -83,7 +108,20 @@ struct LiveStream {
         free_phonemes.clear();
         if (capacity_phonemes > 0) free_phonemes.push_back(LiveRange{0, capacity_phonemes});
         steps = 0; form0 = false; admitted = retired = 0;
+        eq_on = loud_on = false; capacity_tiles = 0; free_tiles.clear();
     }
+    // behind open() and the window geometry's facts (hop, P, Q): the stream carries EQ state (eq) and measures loudness (loud) per slot
+    void open_filters(bool eq, bool loud) {
+        eq_on = eq; loud_on = loud;
+        if (eq) eqt.begin(max_live);
+        if (loud) {
+            ldt.begin(max_live);
+            capacity_tiles = live_tile_rule(capacity, hop, P, Q, max_live);
+            free_tiles.assign(1, LiveRange{0, capacity_tiles});
+        }
+    }
+    long long tiles_of(long F) const { return loud_on ? lds_utt_tiles(stream_out_count((long long)F * hop, P, Q)) : 0; }
+    long long free_tile_count() const { long long n = 0; for (const LiveRange& r : free_tiles) n += r.len; return n; }
     int live_count() const { int n = 0; for (const LiveSlot& s : slots) n += s.live; return n; }
     int free_slots() const { return max_live - live_count(); }
     long long free_frames() const { long long n = 0; for (const LiveRange& r : free_ranges) n += r.len; return n; }
@@ -119,9 +157,11 @@ struct LiveStream {
     // ... and over phonemes too: utterance b with n_phonemes[b] > 0 carries a gain plan and takes the first fit of that many columns of
     // the phoneme pool (0, or n_phonemes == null: it takes none; an utterance without frames takes none either).  False: slots, frame
     // columns or phoneme columns do not suffice, and nothing has changed.
+    // ... and, in a measuring stream, over tiles: every utterance with frames takes the first fit of tiles_of(F[b]) tiles.  Its slot's
+    // consumed positions start at 0 (no state is read at e == 0: whatever the slot's last tenant left is never seen).
     bool admit(int B, const long* F, const int* sid, const int* n_phonemes, int* slot_out) {
-        std::vector<LiveRange> fr = free_ranges, fp = free_phonemes;
-        std::vector<long long> off((size_t)B, 0), poff((size_t)B, 0);
+        std::vector<LiveRange> fr = free_ranges, fp = free_phonemes, ft = free_tiles;
+        std::vector<long long> off((size_t)B, 0), poff((size_t)B, 0), toff((size_t)B, 0);
         int need = 0;
         for (int b = 0; b < B; b++) {
             if (F[b] < 0 || (n_phonemes && n_phonemes[b] < 0)) return false;
@@ -129,6 +169,7 @@ struct LiveStream {
             need++;
             if ((off[(size_t)b] = take(fr, F[b])) < 0) return false;
             if (n_phonemes && n_phonemes[b] > 0 && (poff[(size_t)b] = take(fp, n_phonemes[b])) < 0) return false;
+            if (loud_on && (toff[(size_t)b] = take(ft, tiles_of(F[b]))) < 0) return false;
         }
         if (need > free_slots()) return false;
         size_t s = 0;
@@ -136,11 +177,13 @@ struct LiveStream {
             if (F[b] == 0) { slot_out[b] = -1; continue; }
             while (slots[s].live) s++;
             const int pn = n_phonemes ? n_phonemes[b] : 0;
-            slots[s] = LiveSlot{true, off[(size_t)b], F[b], sid ? sid[b] : 0, 0, poff[(size_t)b], pn, pn > 0};
+            slots[s] = LiveSlot{true, off[(size_t)b], F[b], sid ? sid[b] : 0, 0, poff[(size_t)b], pn, pn > 0, toff[(size_t)b], tiles_of(F[b])};
+            if (eq_on) { eqt.e[s] = 0; eqt.pend[s] = -1; }
+            if (loud_on) { ldt.e[s] = 0; ldt.pend[s] = -1; ldt.tbase[s] = toff[(size_t)b]; }
             slot_out[b] = (int)s;
             admitted++;
         }
-        free_ranges.swap(fr); free_phonemes.swap(fp);
+        free_ranges.swap(fr); free_phonemes.swap(fp); free_tiles.swap(ft);
         return true;
     }
     void retire(int s) {
@@ -148,6 +191,7 @@ struct LiveStream {
         if (!sl.live) return;
         give(free_ranges, sl.off, sl.F);
         give(free_phonemes, sl.poff, sl.pn);
+        give(free_tiles, sl.toff, sl.tn);
         sl = LiveSlot();
         retired++;
     }

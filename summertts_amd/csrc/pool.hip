@@ -81,8 +81,9 @@ struct sts_pool {
             }
             if (take.front()->joined) { run_joined_request(eng, *take.front()); cv_done.notify_all(); continue; }
             if (take.front()->stream) {
-                // (the three settings only change while no request is outstanding)
-                if (stream_admission && loud_mode == 0 && eq_bands == 0) run_open_group(eng, take); else run_stream_group(eng, take);
+                // (the settings only change while no request is outstanding.  With bands set a streamed request is here only with
+                // eq_streaming on -- submit refuses it otherwise -- and the open stream then runs the EQ from per-slot state)
+                if (stream_admission && loud_mode == 0 && (eq_bands == 0 || eq_streaming)) run_open_group(eng, take); else run_stream_group(eng, take);
                 cv_done.notify_all();
                 continue;
             }

@@ -98,6 +98,9 @@ struct Engine::RunCtx {
     // live_slots[b], its z lies at its own offset in the stream's pool (bf.z, leading dimension Fld = the pool's capacity), and its chunk
     // starts at its own next frame.  Null: a closed call
     LiveStream* live = nullptr; std::vector<int> live_slots;
+    // an admission into an open stream (Engine::stream_admit_once): front and flow alone -- no output stage runs, so the frame workspace
+    // holds no carried EQ / loudness state, step workspace or result tables
+    bool admission = false;
     // (and behind that) one step of an open paragraph (Engine::para_step, para_stream.hpp): `join` and `live` are both set.  js is the
     // paragraph's plan as far as it is known, the step is chunk para_k of it alone, sentence b's z lies at para_zoff[b] of the pool and
     // speaks as para_sid[b] (b: the plan's index); para_stop: the chunk's callback ended the paragraph.  para_k < 0: no paragraph

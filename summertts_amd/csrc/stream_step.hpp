@@ -81,8 +81,9 @@ struct StepCall {
 };
 // one window of a plain step: utterance b of F frames at z offset `zoff` speaks as `sid`; its chunk starts at frame f0.  tab: the row of
 // the run's per-utterance tables it reads (the gain kernel's utt[m]; with `mix` the column of the conditioning table in the sid column)
-// -- < 0: b itself, utterance b of a closed call; a planned open stream: its SLOT (live_stream.hpp: the pools are indexed by slot)
-struct StepWin { int b; long F, f0; int zoff, sid; int tab = -1; };
+// -- < 0: b itself, utterance b of a closed call; a planned open stream: its SLOT (live_stream.hpp: the pools are indexed by slot).
+// st: whose carried EQ / loudness state and consumed position its rows name -- < 0: b itself; an open stream: its SLOT (the state pools)
+struct StepWin { int b; long F, f0; int zoff, sid; int tab = -1; int st = -1; };
 
 // what the step loop needs of a built step.  (Its vectors keep their storage from step to step.)
 struct StepOut {
@@ -127,7 +128,7 @@ static inline const char* step_build(const StepCall& c, const StepWin* w, int nw
     for (int i = 0; i < nw; i++) {
         const StepWin& u = w[i];
         const StreamWin g = stream_window(u.F, u.f0, c.C, c.halo, c.hop, c.P, c.Q, c.H);
-        const int row = u.tab >= 0 ? u.tab : u.b;
+        const int row = u.tab >= 0 ? u.tab : u.b, sb = u.st >= 0 ? u.st : u.b;
         const long wlen = g.w1 - g.w0;
         const long long nrs = g.jl1 - g.jl0, nout = g.j1 - g.j0;
         const long long xnat = Wtot * hop, unat = g.w0 * hop, lnat = wlen * hop;        // the decode window's samples: where, from, how many
@@ -135,16 +136,16 @@ static inline const char* step_build(const StepCall& c, const StepWin* w, int nw
                         RsRow{unat, u.F * hop, g.jl0, g.jl1, c.slim ? rsum : dsum},
                         LimRow{wide ? rsum : xnat, wide ? g.jl0 : unat, wide ? nrs : lnat, g.Nout, g.j0, g.j1, dsum});
         if (c.seq) {
-            const EqsRow r = c.srs ? eqt.row(u.b, rsum, g.jl0, nrs, g.jl0, g.jl1, rsum, g.j0, g.j1, dsum)
-                                   : eqt.row(u.b, xnat, unat, lnat, g.jl0, g.jl1, rsum, g.j0, g.j1, dsum);
+            const EqsRow r = c.srs ? eqt.row(sb, rsum, g.jl0, nrs, g.jl0, g.jl1, rsum, g.j0, g.j1, dsum)
+                                   : eqt.row(sb, xnat, unat, lnat, g.jl0, g.jl1, rsum, g.j0, g.j1, dsum);
             if (const char* bad = eqs_row_check(r, g.Nout)) return bad;
             step_put(ht, t.eq_rows, i, r);
             o.etiles = std::max(o.etiles, eqs_tiles(r.e, r.o1));
         }
         if (c.sld) {
-            const LdsRow r = c.lsrc == OS_EQ ? ldt.row(u.b, rsum, g.jl0, nrs, g.j1)
-                             : c.lsrc == OS_RESAMPLE ? ldt.row(u.b, c.slim ? rsum : dsum, g.jl0, nrs, g.j1)
-                                                     : ldt.row(u.b, xnat, unat, lnat, g.j1);
+            const LdsRow r = c.lsrc == OS_EQ ? ldt.row(sb, rsum, g.jl0, nrs, g.j1)
+                             : c.lsrc == OS_RESAMPLE ? ldt.row(sb, c.slim ? rsum : dsum, g.jl0, nrs, g.j1)
+                                                     : ldt.row(sb, xnat, unat, lnat, g.j1);
             if (const char* bad = lds_row_check(r, g.Nout)) return bad;
             step_put(ht, t.loud_rows, i, r);
             o.ltiles = std::max(o.ltiles, lds_tiles(r.e, r.j1));

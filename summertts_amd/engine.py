@@ -335,6 +335,8 @@ def load_library() -> C.CDLL:
     lib.sts_stream_open.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int64]
     lib.sts_stream_open_ex.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_int64]
     lib.sts_stream_tables_info.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    if hasattr(lib, "sts_stream_get_loudness"):       # (added without a new ABI revision: an older library of revision 18 lacks it)
+        lib.sts_stream_get_loudness.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]
     lib.sts_debug_adopt_tables.argtypes = [C.c_int, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64,
                                            C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.sts_pool_submit_stream_ex.restype = C.c_int64
@@ -398,6 +400,7 @@ EXPORTED_SYMBOLS = [
     "sts_pool_set_stream_admission", "sts_pool_get_stream_admission", "sts_pool_stream_stats",
     "sts_para_open", "sts_para_append", "sts_para_finish", "sts_para_step", "sts_para_info", "sts_para_close",
     "sts_stream_open_ex", "sts_stream_tables_info", "sts_pool_submit_stream_ex", "sts_debug_adopt_tables",
+    "sts_stream_get_loudness",
 ]
 
 
@@ -1135,6 +1138,22 @@ class Synthesizer:
         o, l, fs, ff, st = C.c_int32(), C.c_int32(), C.c_int32(), C.c_int64(), C.c_int64()
         _check(self.lib, self.lib.sts_stream_info(self.h, C.addressof(o), C.addressof(l), C.addressof(fs), C.addressof(ff), C.addressof(st)))
         return {"open": bool(o.value), "live": int(l.value), "free_slots": int(fs.value), "free_frames": int(ff.value), "steps": int(st.value)}
+
+    def stream_loudness(self):
+        """A measuring open stream (LOUD_MEASURE with ``set_loudness_streaming``): the slots the most recent ``stream_step`` retired, ascending,
+        and their results -- ``(slots int32 [n], results LOUDNESS_DTYPE [n])``, each result what ``loudness()`` reports after a closed
+        stream of that utterance.  Empty after a step that retired nothing (sts_stream_get_loudness)."""
+        if not hasattr(self.lib, "sts_stream_get_loudness"):
+            raise StsError("sts_stream_get_loudness: this library lacks the entry (it was added without a new ABI revision)")
+        n = self.lib.sts_stream_get_loudness(self.h, None, None, 0)
+        if n < 0:
+            _check(self.lib, n)
+        slots, out = np.zeros(n, np.int32), np.zeros(n, LOUDNESS_DTYPE)
+        if n:
+            rc = self.lib.sts_stream_get_loudness(self.h, slots.ctypes.data, out.ctypes.data, n)
+            if rc < 0:
+                _check(self.lib, rc)
+        return slots, out
 
     def stream_close(self):
         """Drops the live slots without delivering and frees the pool."""

@@ -28,7 +28,8 @@ legs: admission off (the group is a closed stream: the late client waits until i
 late client is admitted between two steps).  Per leg: the late client's time from submit to its first chunk, the group's first-chunk
 times, and the group's last-chunk time with and without the late client.  A library without the switch (an older build) runs the off leg
 only.  --plans: the late client and every second member of the group carry a duration plan, a gain plan and (a multi-speaker model) a
-speaker mix (sts_pool_submit_stream_ex): the planned late client.
+speaker mix (sts_pool_submit_stream_ex): the planned late client.  --eq: the pool of every leg runs the 4-band EQ, streamed -- with
+admission on the group is an open stream with per-slot EQ state.
 """
 from __future__ import annotations
 
@@ -175,6 +176,9 @@ def _late(a) -> None:
     tables = _tables(cfg, a.phonemes) if a.plans else None
     for admission in (False, True):
         pool = engine.Pool(blob, device=0, n_engines=1, max_batch=2 * a.clients)
+        if a.eq:        # the audio profile on every leg, streamed: with admission on the group runs as an open stream with per-slot EQ state
+            pool.set_eq(EQ_BANDS)
+            pool.set_eq_streaming(True)
         if admission:
             if not hasattr(pool, "set_stream_admission"):
                 pool.close()
@@ -183,7 +187,7 @@ def _late(a) -> None:
         for with_late in (False, True):
             _late_run(pool, ids, late_ids, chunk, with_late, tables)          # warm-up of this shape
             runs = [_late_run(pool, ids, late_ids, chunk, with_late, tables) for _ in range(a.reps)]
-            row = {"model": kind, "scenario": "late_arrival", "admission": admission, "late_client": with_late, "plans": bool(a.plans), "clients": a.clients,
+            row = {"model": kind, "scenario": "late_arrival", "admission": admission, "late_client": with_late, "plans": bool(a.plans), "eq": bool(a.eq), "clients": a.clients,
                    "chunk_frames": chunk, "phonemes": a.phonemes, "reps": a.reps}
             for k in runs[0]:
                 row[k] = float(np.median([r[k] for r in runs])) if not isinstance(runs[0][k], bool) else all(r[k] for r in runs)
@@ -204,7 +208,9 @@ def main() -> None:
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--direct", type=int, default=0)
     ap.add_argument("--rate", type=int, default=0, help="output sample rate (0: the native 16 kHz)")
-    ap.add_argument("--eq", type=int, default=0, help="1: the 4-band EQ of DESIGN.md 9j on every call, streamed (sts_set_eq_streaming)")
+    ap.add_argument("--eq", type=int, nargs="?", const=1, default=0,
+                    help="--eq or --eq 1: the 4-band EQ of DESIGN.md 9j on every call, streamed (sts_set_eq_streaming); --late: on every leg's pool "
+                         "(sts_pool_set_eq, sts_pool_set_eq_streaming)")
     ap.add_argument("--loud", type=int, default=0, help="1: loudness mode 1 on every call, measured in the streams (sts_set_loudness_streaming)")
     ap.add_argument("--joined", action="store_true", help="a paragraph: joined stream against the whole joined call and single streams in turn")
     ap.add_argument("--sentences", type=int, default=32)
