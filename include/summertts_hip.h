@@ -500,6 +500,77 @@ int sts_gain_design(const float* gain_db, int32_t n, float ramp_ms, int32_t* q, 
  * be NULL. */
 int sts_gain_plan_apply(int device, const float* x, const int32_t* dur_frames, const int32_t* lengths, int32_t B, int32_t samples_per_frame,
                         const sts_gain_plan* plans, float* y, int16_t* pcm);
+/* ---- pitch plans (no reference counterpart: VITS has no F0 input).  sts_set_pitch_plan(e, B, n, plans) gives utterance b of the NEXT call
+ * (n[b] phonemes) a pitch shift per phoneme in cents -- SSML <prosody pitch> over a span -- by a time warp: a phoneme shifted by the ratio
+ * r = 2^(cents / 1200) is synthesised r times as long and read back r times as fast through a band-limited interpolator.  Its duration
+ * stays, its pitch is multiplied by r.  THE FORMANTS MOVE WITH THE PITCH (the spectral envelope is scaled by r like everything else: a
+ * large upward shift sounds smaller / younger, a downward one larger); that is why the range ends at +-600 cents.  A formant-preserving
+ * shift is not offered.
+ * Valid (checked at the set call; otherwise STS_EINVAL and nothing changes): every cents[i] in [-600, 600].
+ * For one utterance, with the run's final durations d_i, hop = samples_per_frame, F = max(1, sum d_i) frames, N = F hop < 2^30 native
+ * samples, x[0 .. N) the float wave the warp reads (the gain plan's output if one ran, otherwise the decoder's):
+ *   1 Design (host, float64; exactly what sts_pitch_design returns): ratio_i = (float) 2^(cents_i / 1200); step_i = floor(2^(cents_i /
+ *     1200) 2^32 + 0.5) as int64, the input samples per output sample in Q32.  step(0) = 2^32.
+ *   2 Duration compensation: the run behaves as a run with a duration plan whose rate_i is the pending duration plan's rate_i (1.0f
+ *     without one) times ratio_i, one fp32 multiply on the host; all cents 0 multiply by 1.0f, so the durations are those of a call
+ *     without a pitch plan.  A phoneme with fixed_i >= 0 must have cents_i == 0 (breaks are silent), and a duration plan with
+ *     target_frames > 0 admits no non-zero cents: otherwise the run answers STS_EINVAL.  FORCED DURATIONS (sts_set_forced_durations) ARE
+ *     USED AS GIVEN AND NOT COMPENSATED: the caller who forces d_i states the length of the span that is then read r_i times as fast.
+ *   3 Layout (exact, 64-bit integers; sts_pitch_layout): o_0 = 0, e_0 = 0, L_i = (d_i hop) << 32; n_i = L_i > e_i ?
+ *     ceil((L_i - e_i) / step_i) : 0; e_i+1 = e_i + n_i step_i - L_i; o_i+1 = o_i + n_i.  Output j in [o_i, o_i+1) sits at the Q32 position
+ *     pos = (a_i << 32) + e_i + (j - o_i) step_i, a_i = hop sum_{k < i} d_k.  The warped length is N' = o_n.  A phoneme shorter than the
+ *     step that reaches it emits nothing (n_i = 0) and e carries on.  An utterance whose durations are all 0: the one frame nobody owns
+ *     takes step 2^32, so N' = hop.
+ *   4 Filter, one prototype for every ratio (Smith's band-limited interpolation; exactly what sts_pitch_table returns):
+ *     h0[k] = float32(sinc(k / 512) I0(10 sqrt(1 - (k / 16384)^2)) / I0(10)), k = 0 .. 16383; h0[16384] = h0[16385] = 0 (float64, rounded
+ *     once).  For output j: n0 = pos >> 32, f = (pos & 0xffffffff) / 2^32, rho = step_i / 2^32, c = 0.9 min(1, 1 / rho), K = ceil(32 / c)
+ *     <= 51.  Tap m in [0, 2K) reads x[n0 - K + 1 + m] -- 0 outside [0, N), never a batch neighbour -- with dd = f + K - 1 - m,
+ *     t = 512 c |dd|, k = floor(t), g_m = h0[k] + (t - k) (h0[k + 1] - h0[k]) (0 when k >= 16384).
+ *     y_j = float32(sum g_m x_m / sum g_m): coefficients, both sums (m ascending) and the division in float64.
+ *   5 An utterance whose entry has cents == NULL in a run that has a plan is copied bit for bit (y = x, N' = N); one with cents is
+ *     filtered everywhere, also where cents are 0.
+ * An output's value depends on its utterance alone: not on batch companions, the position in the packed buffer or the tile.
+ * PCM is the reference's cast (int16)(int32)(y * 32737) of y_j.
+ * The warp runs at the native rate directly behind the gain kernel: decoder wave -> gain envelope -> warp -> resampler -> EQ -> loudness
+ * -> limiter -> cast.  Everything behind it sees utterance b as N'_b native samples: the returned counts are ceil(N'_b P / Q), and
+ * sts_get_phoneme_offsets answers ceil(o_i P / Q).  Taps: "wave" and "wave_gain" stay the unwarped signals, "wave_pitch" is the warped one
+ * (all utterances back to back), "wave_out" / "wave_eq" / "wave_lim" are computed from it.
+ * The plan is copied and applies to the next run only, whatever that run's outcome (the lifetime of a gain plan): sts_infer_ids,
+ * sts_infer_ids_batch, sts_run_batch, sts_pool_submit_pitch, sts_multi_set_pitch_plan.  That run must have the same B and n[b]: otherwise
+ * it answers STS_EINVAL, nothing runs and the plan is dropped.  B == 0 or plans == NULL drops a pending plan.  A run with a pitch plan is
+ * never launched ahead and neither reads nor feeds the launch-ahead memo; its layout is made on the host when the durations arrive (they
+ * come with the frame counts) and uploaded without a further wait; the split-bf16 repeat of a call applies the same plan again.  A call
+ * with no plan pending launches, allocates and uploads nothing new.
+ * NOT AVAILABLE with a plan pending -- each answers STS_EINVAL, runs nothing and drops the plan: sts_infer_ids_stream,
+ * sts_infer_ids_batch_stream, sts_stream_open / sts_stream_open_ex, sts_stream_admit, sts_infer_ids_joined, sts_infer_ids_joined_stream,
+ * sts_para_open, sts_para_append (while a paragraph or an unplanned stream is open the setter itself answers STS_ESTATE).
+ * Added without a new STS_ABI_VERSION: detect the entries by symbol. */
+typedef struct sts_pitch_plan {
+    const int32_t* cents;   /* [n] or NULL: per-phoneme shift in cents, each in [-600, 600] */
+} sts_pitch_plan;
+int sts_set_pitch_plan(sts_engine* e, int32_t B, const int32_t* n, const sts_pitch_plan* plans);
+/* Host only (no device): the validity rules above for B plans of n[b] >= 1 phonemes each. */
+int sts_pitch_plan_check(int32_t B, const int32_t* n, const sts_pitch_plan* plans);
+/* Host only: step 1 for one utterance of n >= 1 phonemes (cents == NULL: ratio 1.0f, step 2^32); each of ratio ([n]) and step ([n]) is set
+ * when non-null.  STS_EINVAL for an invalid plan. */
+int sts_pitch_design(const int32_t* cents, int32_t n, float* ratio, int64_t* step);
+/* Host only: step 3 for one utterance: out_start[0 .. n] = o_i and resid[0 .. n] = e_i, each set when non-null (the all-zero utterance
+ * answers o_n = 0 here: the hop samples of step 4's rule belong to no phoneme).  STS_EINVAL: n < 1, a duration outside [0, 100000], a
+ * step outside [step(-600), step(600)], samples_per_frame outside [1, 2^20], or max(1, sum d) samples_per_frame >= 2^30. */
+int sts_pitch_layout(const int32_t* dur_frames, const int64_t* step, int32_t n, int32_t samples_per_frame, int64_t* out_start, int64_t* resid);
+/* Host only: the prototype h0 of step 4, 16386 floats (a smaller capacity answers STS_EINVAL). */
+int sts_pitch_table(float* table, int64_t capacity_floats);
+/* The warp kernel on caller signals, like sts_gain_plan_apply: B float signals packed back to back in x (host memory); utterance b has
+ * lengths[b] >= 1 phonemes with the durations dur_frames (packed for the whole batch) and its signal is max(1, sum d) samples_per_frame
+ * samples long (B <= 65535).  out_len[b] (optional) receives N'_b; y (float) and pcm (int16) receive the warped signals packed back to back
+ * by N'_b, each may be NULL (both NULL: only out_len is computed, on the host).  capacity: the samples y and pcm have room for; a smaller
+ * one than sum N'_b answers STS_EINVAL with out_len set. */
+int sts_pitch_apply(int device, const float* x, const int32_t* dur_frames, const int32_t* lengths, int32_t B, int32_t samples_per_frame,
+                    const sts_pitch_plan* plans, int64_t* out_len, float* y, int16_t* pcm, int64_t capacity);
+/* Lab (tools/pitch_cost.py): sts_pitch_apply's float output with the prototype read from global memory (table_in_lds 0) or staged in
+ * LDS (1), then iters >= 1 more launches between two events: *ms_out = their mean time in milliseconds. */
+int sts_debug_pitch_bench(int device, const float* x, const int32_t* dur_frames, const int32_t* lengths, int32_t B, int32_t samples_per_frame,
+                          const sts_pitch_plan* plans, float* y, int64_t capacity, int32_t table_in_lds, int32_t iters, float* ms_out);
 /* ---- paragraph synthesis (no reference counterpart: SynthesizerTrn::infer runs a whole line as ONE utterance, at quadratic attention cost and
  * without batching).  sts_infer_ids_joined runs B sentences as exactly the packed batch sts_infer_ids_batch would run and joins their float
  * waves on the device into ONE signal -- in front of the resampler, loudness, the limiter and the cast, which then see the paragraph as the
@@ -1013,6 +1084,11 @@ int64_t sts_pool_submit_mix(sts_pool* p, const int32_t* ids, int32_t n, int32_t 
  *   with and without a plan share one packed batch: the plan is per utterance, and a member without one keeps its samples bit for bit. */
 int64_t sts_pool_submit_gain(sts_pool* p, const int32_t* ids, int32_t n, int32_t sid, float length_scale, float noise_scale,
                              float noise_scale_w, uint64_t seed, const sts_gain_plan* plan);
+/*   sts_pool_submit_pitch: sts_pool_submit_ex with this request's own pitch plan (sts_set_pitch_plan; copied; plan == NULL or cents == NULL:
+ *   a plain request; an invalid plan answers STS_EINVAL).  Whole-utterance requests only.  Requests with and without a plan share one
+ *   packed batch: a member without one keeps its samples bit for bit. */
+int64_t sts_pool_submit_pitch(sts_pool* p, const int32_t* ids, int32_t n, int32_t sid, float length_scale, float noise_scale,
+                              float noise_scale_w, uint64_t seed, const sts_pitch_plan* plan);
 /*   sts_pool_submit_stream_ex: sts_pool_submit_stream with this request's own duration plan, speaker mix and gain plan, each optional
  *   (copied; validated at submit as sts_pool_submit_plan / _mix / _gain validate theirs: STS_EINVAL).  All three NULL is
  *   sts_pool_submit_stream.  Planned and plain streaming requests of one chunk size share a group; with admission on
@@ -1078,6 +1154,8 @@ int sts_multi_set_speaker_mix(sts_multi* m, int32_t B, const sts_speaker_mix* mi
  *   (otherwise STS_EINVAL, nothing runs and the plan is dropped).  plans[b] belongs to utterance b of the caller's batch and follows it into
  *   its device's shard: the PCM does not depend on the number of devices. */
 int sts_multi_set_gain_plan(sts_multi* m, int32_t B, const int32_t* n, const sts_gain_plan* plans);
+/*   sts_multi_set_pitch_plan: sts_set_pitch_plan for the NEXT sts_multi_infer_ids_batch of the handle, sharded like the gain plan. */
+int sts_multi_set_pitch_plan(sts_multi* m, int32_t B, const int32_t* n, const sts_pitch_plan* plans);
 /*   test hook: the shared library that provides the nccl* entry points (NULL / "" = librccl.so.1) and whether STS_MULTI_RCCL may list
  *   one device several times (tests/fake_rccl: N emulated ranks on one GPU; real RCCL refuses duplicates).  Only before the first
  *   STS_MULTI_RCCL handle of the process is created.  TEST-ONLY: refused with STS_ESTATE unless the process environment carries

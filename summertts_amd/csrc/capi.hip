@@ -333,6 +333,39 @@ int sts_gain_design(const float* gain_db, int32_t n, float ramp_ms, int32_t* q, 
     return STS_OK;
 }
 
+int sts_set_pitch_plan(sts_engine* e, int32_t B, const int32_t* n, const sts_pitch_plan* plans) {
+    if (!e) return set_err(STS_EINVAL, "null engine");
+    const int rc = e->eng.set_pitch_plan(B, n, plans);
+    return rc == STS_OK ? STS_OK : set_err(rc, e->eng.error());
+}
+int sts_pitch_plan_check(int32_t B, const int32_t* n, const sts_pitch_plan* plans) {
+    if (B < 0 || (B > 0 && (!n || !plans))) return set_err(STS_EINVAL, "pitch plan: B >= 0 plans and their phoneme counts are required");
+    for (int b = 0; b < B; b++) {
+        const char* why = nullptr;
+        if (!pitch_plan_valid(n[b], plans[b].cents, &why)) return set_err(STS_EINVAL, why);
+    }
+    return STS_OK;
+}
+int sts_pitch_design(const int32_t* cents, int32_t n, float* ratio, int64_t* step) {
+    const char* why = nullptr;
+    if (!pitch_plan_valid(n, cents, &why)) return set_err(STS_EINVAL, why);
+    for (int i = 0; i < n; i++) {
+        if (ratio) ratio[i] = cents ? pitch_ratio(cents[i]) : 1.f;
+        if (step) step[i] = cents ? pitch_step(cents[i]) : kPitchOne;
+    }
+    return STS_OK;
+}
+int sts_pitch_layout(const int32_t* dur_frames, const int64_t* step, int32_t n, int32_t samples_per_frame, int64_t* out_start, int64_t* resid) {
+    if (!pitch_layout(dur_frames, step, n, samples_per_frame, out_start, resid))
+        return set_err(STS_EINVAL, "pitch layout: n >= 1 durations in [0, 100000], steps in [step(-600), step(600)], samples_per_frame in [1, 2^20] and fewer than 2^30 samples are required");
+    return STS_OK;
+}
+int sts_pitch_table(float* table, int64_t capacity_floats) {
+    if (!table || capacity_floats < kPitchTableFloats) return set_err(STS_EINVAL, "pitch table: room for 16386 floats is required");
+    pitch_table(table);
+    return STS_OK;
+}
+
 int sts_join_check(int32_t B, const sts_join* join) {
     const char* why = nullptr;
     if (!join_valid(B, join, &why)) return set_err(STS_EINVAL, why);

@@ -141,6 +141,78 @@ int sts_gain_plan_apply(int device, const float* x, const int32_t* dur_frames, c
     return d.finish() ? STS_OK : set_err(STS_EDEVICE, "the gain plan failed on the device");
 }
 
+// table_mode: -1 the shipped placement of the prototype, 0 global memory, 1 LDS; iters > 0: that many more launches between two events,
+// their mean in *ms (sts_debug_pitch_bench)
+static int pitch_apply_impl(int device, const float* x, const int32_t* dur_frames, const int32_t* lengths, int32_t B, int32_t samples_per_frame,
+                            const sts_pitch_plan* plans, int64_t* out_len, float* y, int16_t* pcm, int64_t capacity, int table_mode, int iters,
+                            float* ms) {
+    if (B < 1 || B > 65535 || !x || !dur_frames || !lengths || !plans || samples_per_frame < 1 || samples_per_frame > kPitchMaxHop || capacity < 0)      // (one grid row per signal)
+        return set_err(STS_EINVAL, "1 <= B <= 65535 signals, their durations, phoneme counts and plans, and samples_per_frame in [1, 2^20] are required");
+    const int hop = samples_per_frame;
+    int64_t T = 0;
+    for (int b = 0; b < B; b++) {
+        const char* why = nullptr;
+        if (lengths[b] < 1 || !pitch_plan_valid(lengths[b], plans[b].cents, &why)) return set_err(STS_EINVAL, why ? why : "every utterance needs lengths[b] >= 1 phonemes");
+        T += lengths[b];
+        if (T > (1 << 24)) return set_err(STS_EINVAL, "batch too large");
+    }
+    // the steps of the planned members, and every member's place in x: the geometry the engine derives from its durations
+    std::vector<int64_t> steps((size_t)T);
+    std::vector<const int32_t*> dur((size_t)B);
+    std::vector<const int64_t*> step((size_t)B);
+    std::vector<long long> xoff((size_t)B);
+    int64_t t = 0, total = 0;
+    for (int b = 0; b < B; b++) {
+        int64_t f = 0;
+        for (int i = 0; i < lengths[b]; i++) {
+            const int32_t dd = dur_frames[t + i];
+            if (dd < 0 || dd > kDurMax) return set_err(STS_EINVAL, "durations must be in [0, 100000]");
+            f += dd;
+            if (plans[b].cents) steps[t + i] = pitch_step(plans[b].cents[i]);
+        }
+        dur[b] = dur_frames + t; step[b] = plans[b].cents ? steps.data() + t : nullptr; xoff[b] = total;
+        t += lengths[b]; total += std::max<int64_t>(f, 1) * hop;
+        if (total > ((int64_t)1 << 30)) return set_err(STS_EINVAL, "the signals must hold at most 2^30 samples in all");
+    }
+    PitchTables tab;
+    if (const char* bad = pitch_tables(B, lengths, dur.data(), step.data(), xoff.data(), hop, &tab)) return set_err(STS_EINVAL, bad);
+    if (out_len) for (int b = 0; b < B; b++) out_len[b] = tab.nout[b];
+    if ((y || pcm) && tab.total_out > capacity) return set_err(STS_EINVAL, "pitch plan: the outputs are too small for the warped signals (out_len has their lengths)");
+    if (!y && !pcm) return STS_OK;
+    std::vector<float> proto(kPitchTableFloats);
+    pitch_table(proto.data());
+    if (hipSetDevice(device) != hipSuccess) return set_err(STS_EDEVICE, "no such device");
+    DevScratch d;
+    PitchArgs a{};
+    pitch_args_carve(a, d.up(tab.words.data(), tab.words.size()), B, tab.TT);
+    a.table = d.up(proto.data(), proto.size());
+    // (the outputs start out as NaN / 0x7FFF: a sample the kernel leaves out shows)
+    a.x = d.up(x, (size_t)total); a.y = y ? d.out((size_t)tab.total_out) : nullptr; a.pcm = pcm ? d.out16((size_t)tab.total_out) : nullptr;
+    const bool lds = table_mode < 0 ? pitch_table_in_lds() : table_mode != 0;
+    if (d.ok) pitch_plan_run(a, B, tab.max_out, lds, d.st);
+    if (d.ok && iters > 0 && ms) {
+        hipEvent_t e0 = nullptr, e1 = nullptr;
+        d.ok = hipEventCreate(&e0) == hipSuccess && hipEventCreate(&e1) == hipSuccess && hipEventRecord(e0, d.st) == hipSuccess;
+        for (int i = 0; i < iters && d.ok; i++) pitch_plan_run(a, B, tab.max_out, lds, d.st);
+        d.ok = d.ok && hipEventRecord(e1, d.st) == hipSuccess && hipEventSynchronize(e1) == hipSuccess && hipEventElapsedTime(ms, e0, e1) == hipSuccess;
+        if (d.ok) *ms /= (float)iters;
+        if (e0) (void)hipEventDestroy(e0);
+        if (e1) (void)hipEventDestroy(e1);
+    }
+    d.down(y, a.y, (size_t)tab.total_out * 4);
+    d.down(pcm, a.pcm, (size_t)tab.total_out * 2);
+    return d.finish() ? STS_OK : set_err(STS_EDEVICE, "the pitch plan failed on the device");
+}
+int sts_pitch_apply(int device, const float* x, const int32_t* dur_frames, const int32_t* lengths, int32_t B, int32_t samples_per_frame,
+                    const sts_pitch_plan* plans, int64_t* out_len, float* y, int16_t* pcm, int64_t capacity) {
+    return pitch_apply_impl(device, x, dur_frames, lengths, B, samples_per_frame, plans, out_len, y, pcm, capacity, -1, 0, nullptr);
+}
+int sts_debug_pitch_bench(int device, const float* x, const int32_t* dur_frames, const int32_t* lengths, int32_t B, int32_t samples_per_frame,
+                          const sts_pitch_plan* plans, float* y, int64_t capacity, int32_t table_in_lds, int32_t iters, float* ms_out) {
+    if (!y || !ms_out || iters < 1 || table_in_lds < 0 || table_in_lds > 1) return set_err(STS_EINVAL, "pitch bench: y, ms_out, iters >= 1 and table_in_lds 0 or 1 are required");
+    return pitch_apply_impl(device, x, dur_frames, lengths, B, samples_per_frame, plans, nullptr, y, nullptr, capacity, table_in_lds, iters, ms_out);
+}
+
 int sts_join_apply(int device, const float* x, const int32_t* frames, int32_t B, int32_t samples_per_frame, const sts_join* join, float* y,
                    int16_t* pcm) {
     const char* why = nullptr;

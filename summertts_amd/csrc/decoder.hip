@@ -469,15 +469,27 @@ int Engine::decode_end(RunCtx& c, const float* wave, const WinGeom& win, long Wt
     const float* const raw = wave;          // (the "wave" tap stays the un-gained signal)
     const float* cur = wave;
     auto pcm_of = [&](int stage) { return oc.writer == stage ? c.bf.pcm : nullptr; };
-    if (oc.run[OS_GAIN]) {
+    if (oc.run[OS_GAIN] && c.gain) {    // (the native-rate plan stage: the gain kernel, then the warp of a pitch plan, each if its plan is there)
         // the gain plan on every window's native samples at their absolute positions (a streaming window: halo included), one launch
         GainArgs g{};
-        g.x = cur; g.y = c.bf.wave_gain; g.pcm = pcm_of(OS_GAIN);
+        g.x = cur; g.y = c.bf.wave_gain; g.pcm = c.pitch ? nullptr : pcm_of(OS_GAIN);
         g.wseg = win.seg(hop, 0); g.hop = hop;
         if (c.ss) { const StepTab t(nw, true, false, false, false); g.utt = (const int*)(c.bf.stab + t.utt); g.wtab = (const long long*)(c.bf.stab + t.rs); }
         g.tseg = c.lvT.seg; g.cum = c.bt.cum; g.q = c.bt.gain_q; g.h = c.bt.gain_h;
         gain_plan_run(g, nw, (long long)maxW * hop, stream);
         cur = g.y;
+    }
+    int sig_scale = hop;                    // native samples per unit of dw's lengths
+    if (oc.run[OS_GAIN] && c.pitch) {
+        // the pitch plan's warp of every utterance (gained or not), one launch.  From here on utterance b is N'_b samples long: dw carries
+        // the warped counts at scale 1 for the resampler's segments and for signal()
+        PitchArgs p{};
+        pitch_args_carve(p, c.bt.pitch_words, nw, c.pitch_rows);
+        p.x = cur; p.y = c.bf.wave_pitch; p.pcm = pcm_of(OS_GAIN); p.table = d_pitch_table_;
+        pitch_plan_run(p, nw, c.pitch_max, pitch_table_in_lds(), stream);
+        cur = p.y;
+        dw = WinGeom{win.inl, nw, 0, (int)c.pitch_nout[0], c.bt.pitch_win};
+        sig_scale = 1; max_out = out_count(c.pitch_max);
     }
     if (oc.run[OS_JOIN] && whole) {     // (a joined stream: run_stream_steps joins each step's windows into a window of J)
         // the B sentences (gained or not) into the one joined signal, silence included, one launch.  From here on there is ONE utterance of
@@ -495,13 +507,13 @@ int Engine::decode_end(RunCtx& c, const float* wave, const WinGeom& win, long Wt
     // EqArgs / LoudArgs / LimArgs: the float signal at the output rate and its utterances' lengths
     auto signal = [&](auto& a) {
         a.x = cur;
-        a.len = dw.len(); a.ilen = dw.ilen(); a.scale = hop;
+        a.len = dw.len(); a.ilen = dw.ilen(); a.scale = sig_scale;
         a.P = c.rsP; a.Q = c.rsQ;
     };
     if (oc.run[OS_RESAMPLE] && whole) {
         ResampleArgs a{};
         a.x = cur;
-        a.seg = dw.seg(hop, 0);
+        a.seg = dw.seg(sig_scale, 0);
         a.table = d_rs_table; a.P = rs.P; a.Q = rs.Q; a.K = rs.K;
         a.pcm = c.bf.pcm_rs; a.wave_out = c.bf.wave_out;
         resample_pcm(a, nw, max_out, stream);
@@ -546,10 +558,12 @@ int Engine::decode_end(RunCtx& c, const float* wave, const WinGeom& win, long Wt
     if (raw && record_taps) {
         tap("wave", raw, 1, Wtot * hop, (wlen0 >= 0 ? (long)wlen0 : Wtot) * hop);
         if (c.gain && !c.ss) tap("wave_gain", c.bf.wave_gain, 1, Wtot * hop, (wlen0 >= 0 ? (long)wlen0 : Wtot) * hop);
+        if (c.pitch) tap("wave_pitch", c.bf.wave_pitch, 1, (long)c.pitch_total, (long)c.pitch_total);
         if (c.join && !c.ss) tap("wave_join", c.bf.wave_join, 1, (long)(c.FJ * hop), (long)(c.FJ * hop));
         if ((c.bf.wave_out || c.bf.wave_lim || c.bf.wave_eq) && !c.ss) {    // (a stream has moved the pinned block p_lenF points into: not read then)
             long long n = 0;        // samples at the output rate: what both taps hold
             if (c.join) n = out_count(c.FJ * hop);
+            else if (c.pitch) for (int b = 0; b < c.B; b++) n += out_count(c.pitch_nout[(size_t)b]);
             else if (wlen0 >= 0) n = out_count((long long)wlen0 * hop);
             else for (int b = 0; b < c.B; b++) n += out_count((long long)c.p_lenF[b] * hop);
             if (c.bf.wave_out) tap("wave_out", c.bf.wave_out, 1, (long)c.Ocap, (long)n);

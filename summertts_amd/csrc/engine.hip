@@ -48,6 +48,7 @@ Engine::~Engine() {
     if (loud_host_) (void)hipHostFree(loud_host_);
     if (lim_host_) (void)hipHostFree(lim_host_);
     if (d_eq_) (void)hipFree(d_eq_);
+    if (d_pitch_table_) (void)hipFree(d_pitch_table_);
     if (ovf_host_) (void)hipHostFree(ovf_host_);
     if (hmap_) (void)hipHostFree(hmap_);
     if (arrive_) (void)hipFree(arrive_);
@@ -475,6 +476,31 @@ int Engine::set_gain_plan(int B, const int32_t* n, const sts_gain_plan* plans) {
     have_gain = true;
     return STS_OK;
 }
+// sts_set_pitch_plan: validated and copied here; an invalid plan changes nothing.  B == 0 or plans == null drops a pending plan.
+int Engine::set_pitch_plan(int B, const int32_t* n, const sts_pitch_plan* plans) {
+    STS_NOT_WHILE_OPEN_UNPLANNED("a pitch plan");      // (a planned open stream lets the setter through; its admission then refuses the plan)
+    if (B == 0 || !plans) { have_pitch = false; return STS_OK; }
+    if (B < 0 || !n) return fail(STS_EINVAL, "pitch plan: B >= 0 and n are required");
+    if (B > 65535) return fail(STS_EINVAL, "pitch plan: at most 65535 utterances");     // (one grid row per utterance)
+    long total = 0;
+    for (int b = 0; b < B; b++) {
+        const char* why = nullptr;
+        if (!pitch_plan_valid(n[b], plans[b].cents, &why)) return fail(STS_EINVAL, why);
+        total += n[b];
+        if (total > (1 << 24)) return fail(STS_EINVAL, "batch too large");
+    }
+    pitch_n.assign(n, n + B);
+    pitch_cents.assign((size_t)total, 0);
+    pitch_has.assign((size_t)B, 0);
+    size_t off = 0;
+    for (int b = 0; b < B; b++) {
+        pitch_has[(size_t)b] = plans[b].cents != nullptr;
+        if (plans[b].cents) std::copy(plans[b].cents, plans[b].cents + n[b], pitch_cents.begin() + (long)off);
+        off += (size_t)n[b];
+    }
+    have_pitch = true;
+    return STS_OK;
+}
 // sts_get_speaker_embedding: row sid of the device-resident table (one strided copy of gin floats)
 int Engine::speaker_embedding(int sid, float* out, int64_t capacity) const {
     if (!out) return STS_EINVAL;
@@ -489,6 +515,10 @@ int Engine::speaker_embedding(int sid, float* out, int64_t capacity) const {
 int Engine::phoneme_offsets(int64_t* start, int64_t capacity) {
     if (!start) return fail(STS_EINVAL, "null argument");
     if ((int64_t)durations_h.size() > capacity) return fail(STS_ESTATE, "destination too small");
+    if (last_pitch_start.size() == durations_h.size() && !durations_h.empty()) {      // (a run with a pitch plan: positions in the warped signal)
+        for (size_t k = 0; k < durations_h.size(); k++) start[k] = out_count(last_pitch_start[k]);
+        return STS_OK;
+    }
     size_t i = 0;
     const bool joined = last_join_start.size() == last_n.size() && !last_n.empty();      // (a joined run: positions in the joined output)
     for (size_t b = 0; b < last_n.size(); b++) {
@@ -511,6 +541,7 @@ int Engine::join_offsets(int64_t* start, int64_t capacity) {
 // run_stream_steps launches the windowed one per step)
 int Engine::run_joined(int B, const int32_t* const* ids, const int32_t* n, const int32_t* sid, const float* ls, const sts_join* join, const StreamSpec* ss) {
     STS_NOT_WHILE_OPEN("a joined run");
+    if (refuse_pitch("a joined run")) { drop_tables(); return STS_EINVAL; }
     const char* why = nullptr;
     if (!join_valid(B, join, &why)) return fail(STS_EINVAL, why);
     if (!ids || !n) return fail(STS_EINVAL, "empty batch");
@@ -570,7 +601,34 @@ int Engine::run_setup(RunCtx& c) {
         for (int b = 0; b < B && same; b++) same = gain_n[b] == n[b];
         if (!same) return fail(STS_EINVAL, "the gain plan was set for another batch (B and every n[b] must match)");      // (run() drops it)
     }
-    const bool plan = c.plan = have_plan;
+    std::vector<float> eff_rate; std::vector<int32_t> eff_fixed, eff_target;
+    const float* src_rate = plan_rate.data(); const int32_t* src_fixed = plan_fixed.data(); const int32_t* src_target = plan_target.data();
+    // a pitch plan: whole-utterance calls only; the run's duration plan is the pending one (or the neutral one) with every rate multiplied
+    // by the phoneme's ratio -- one fp32 multiply here; the plan kernel is the one of any planned run.  Forced durations are used as given
+    if (have_pitch) {
+        bool same = (int)pitch_n.size() == B;
+        for (int b = 0; b < B && same; b++) same = pitch_n[b] == n[b];
+        if (!same) return fail(STS_EINVAL, "the pitch plan was set for another batch (B and every n[b] must match)");      // (run() drops it)
+        if (c.ss || join_on) return fail(STS_EINVAL, "a pitch plan applies to whole-utterance calls only: streaming and joined runs refuse it");
+        if (!have_forced) {     // (copies: the split-bf16 repeat of this call sets up again from the same pending plan)
+            if (have_plan) { eff_rate = plan_rate; eff_fixed = plan_fixed; eff_target = plan_target; }
+            else { eff_rate.assign((size_t)Ttot, 1.0f); eff_fixed.assign((size_t)Ttot, -1); eff_target.assign((size_t)B, 0); }
+            for (int b = 0; b < B; b++)
+                for (int i = 0; i < n[b]; i++) {
+                    const size_t k = (size_t)offT[b] + i;
+                    if (pitch_cents[k] == 0) continue;
+                    if (eff_fixed[k] >= 0) return fail(STS_EINVAL, "pitch plan: a phoneme with a fixed length must have 0 cents (a break is silent)");
+                    if (eff_target[b] > 0) return fail(STS_EINVAL, "pitch plan: an utterance that is fitted to target_frames admits no non-zero cents");
+                    eff_rate[k] *= pitch_ratio(pitch_cents[k]);
+                    if (!(eff_rate[k] >= 1.0f / 64.0f && eff_rate[k] <= 64.0f)) return fail(STS_EINVAL, "pitch plan: rate times ratio must stay in [1/64, 64]");
+                }
+            src_rate = eff_rate.data(); src_fixed = eff_fixed.data(); src_target = eff_target.data();
+        }
+    }
+    const bool pitch = c.pitch = have_pitch;
+    c.pitch_rows = 0;
+    if (pitch) for (int b = 0; b < B; b++) c.pitch_rows += pitch_has[(size_t)b] ? n[b] : 0;
+    const bool plan = c.plan = have_plan || (pitch && !have_forced);
     const bool gain = c.gain = have_gain;
     const size_t gain_ints = gain ? gain_words.size() : 0;                 // [q Ttot | h B], between the mix and the plan
     const bool join = c.join = join_on;
@@ -632,6 +690,8 @@ int Engine::run_setup(RunCtx& c) {
         bt.cond_wn = A.get<float>((size_t)(2 * wnH * wnL + 4) * B * (M.n_flows > 0 ? M.n_flows : 1));   // one block per coupling
         bt.plan_rem = plan ? A.get<long long>(Ttot) : nullptr;
         bt.dur_w = plan && record_taps ? A.get<float>(Ttot) : nullptr;
+        bt.pitch_words = pitch ? A.get<long long>((size_t)6 * B + 5 * (size_t)c.pitch_rows) : nullptr;
+        bt.pitch_win = pitch ? A.get<int>((size_t)3 * B) : nullptr;
     };
     arenaT_.measuring = true; layoutT(arenaT_);
     if (!ensure(arenaT_, arenaT_.used + 4096)) return fail(STS_EDEVICE, "out of device memory (phoneme-level workspace)");
@@ -641,7 +701,8 @@ int Engine::run_setup(RunCtx& c) {
     // ---------------- one H2D: geometry + ids (+ forced durations)
     const size_t meta_ints = c.meta_ints = (size_t)9 * B + 8;
     const size_t up_bytes = c.up_bytes = (meta_ints + 5 * (size_t)B + 2 * (size_t)Ttot + mix_ints + gain_ints + join_ints + plan_ints) * 4 + 1024;
-    if (!ensure_pinned(up_bytes + ((size_t)Ttot + B) * 4)) return fail(STS_EDEVICE, "pinned host allocation failed");
+    const size_t pitch_stage = pitch ? ((size_t)6 * B + 5 * (size_t)c.pitch_rows) * 8 + (size_t)3 * B * 4 + 16 : 0;     // (pitch_geometry)
+    if (!ensure_pinned(up_bytes + ((size_t)Ttot + B) * 4 + pitch_stage)) return fail(STS_EDEVICE, "pinned host allocation failed");
     int* pm = c.pm = (int*)pinned_;
     int* p_offT = c.p_offT = pm, *p_lenT = c.p_lenT = pm + B, *p_sid = c.p_sid = pm + 2 * B, *p_one = c.p_one = pm + 5 * B;
     c.p_offF = pm + 3 * B; c.p_lenF = pm + 4 * B;
@@ -662,9 +723,9 @@ int Engine::run_setup(RunCtx& c) {
     int* p_forced = p_ids + Ttot + mix_ints + gain_ints + join_ints;
     if (have_forced) memcpy(p_forced, forced_dur.data(), sizeof(int) * Ttot);
     if (plan) {          // (never together with forced durations: the plan's arrays take their place in the copy)
-        memcpy(p_ids + Ttot + mix_ints + gain_ints + join_ints, plan_rate.data(), sizeof(float) * Ttot);
-        memcpy(p_ids + 2 * Ttot + mix_ints + gain_ints + join_ints, plan_fixed.data(), sizeof(int) * Ttot);
-        memcpy(p_ids + 3 * Ttot + mix_ints + gain_ints + join_ints, plan_target.data(), sizeof(int) * B);
+        memcpy(p_ids + Ttot + mix_ints + gain_ints + join_ints, src_rate, sizeof(float) * Ttot);
+        memcpy(p_ids + 2 * Ttot + mix_ints + gain_ints + join_ints, src_fixed, sizeof(int) * Ttot);
+        memcpy(p_ids + 3 * Ttot + mix_ints + gain_ints + join_ints, src_target, sizeof(int) * B);
     }
     HIPCK(hipMemcpyAsync(bt.meta_i, pm, (meta_ints + 5 * (size_t)B + (size_t)Ttot * (have_forced ? 2 : 1) + mix_ints + gain_ints + join_ints + plan_ints) * 4, hipMemcpyHostToDevice, stream));
     if (B > 1) HIPCK(hipEventRecord(ev_setup_, stream));     // (run_durations, batches launched from the memo: the host rewrites part of this block)
@@ -886,7 +947,7 @@ int Engine::run_durations(RunCtx& c) {
         c.req_keys[b] = h | 1ull;
     }
     c.predF.clear();
-    if (launch_ahead && !ss && !have_forced && !c.plan && !c.mix && !c.gain && !c.join && !record_taps && mapped) {     // (a planned or mixed run's frame count is not a function of the memo's key; a run with a gain plan and a joined run stay off the memo by contract)
+    if (launch_ahead && !ss && !have_forced && !c.plan && !c.mix && !c.gain && !c.pitch && !c.join && !record_taps && mapped) {     // (a planned or mixed run's frame count is not a function of the memo's key; a run with a gain plan and a joined run stay off the memo by contract)
         c.predF.resize(B);
         for (int b = 0; b < B; b++) {
             const auto it = seen_tf_.find(c.req_keys[b]);
@@ -909,7 +970,7 @@ int Engine::run_durations(RunCtx& c) {
     durations(r_final, M.dur_type == 0 ? 1 : 0, M.ea_m, M.ea_logs, bt.ls, (have_forced || c.plan) ? bt.forced : nullptr, bt.dlogw,
               bt.dur, bt.cum, bt.frames, lvT.seg, B, stream, mapped ? hmap_dev_ : nullptr, Ttot, seq_, arrive_,
               c.ahead ? c.d_lenF : nullptr, c.ahead ? c.d_win + 2 : nullptr, (int)cap);
-    c.forced = have_forced || c.plan || c.mix || c.gain || c.join;      // (none of these runs feeds the memo: its key hashes sid, not the mix)
+    c.forced = have_forced || c.plan || c.mix || c.gain || c.pitch || c.join;      // (none of these runs feeds the memo: its key hashes sid, not the mix)
     have_forced = false;
     mark(2);
     sync_wait_ms_ = 0;
@@ -1024,10 +1085,68 @@ int Engine::wait_frame_counts(RunCtx& c) {
 
 // the one place that decides the output chain of a run (out_chain.hpp), with the limiter's design and the resampler's ratio for it
 int Engine::plan_output(RunCtx& c) {
-    c.oc = plan_out_chain(OutFacts{c.ss != nullptr, c.B, resampling(), c.gain, c.join, eq_n > 0, loud_mode, lim_mode != 0, record_taps, stream_direct != 0, eq_streaming, loud_streaming});
+    c.oc = plan_out_chain(OutFacts{c.ss != nullptr, c.B, resampling(), c.gain || c.pitch, c.join, eq_n > 0, loud_mode, lim_mode != 0, record_taps, stream_direct != 0, eq_streaming, loud_streaming});
     if (c.oc.run[OS_RESAMPLE]) { c.rsP = rs.P; c.rsQ = rs.Q; }
     c.eqS = eq_n;
     if (c.oc.run[OS_LIMIT] && !limiter_design(out_rate, lim_gain_db, lim_ceiling, lim_ms, &c.limd)) return fail(STS_EINVAL, "limiter: output rate outside [8000, 48000]");
+    return STS_OK;
+}
+
+// A run with a pitch plan, when the durations are on the host (they come with the frame counts): the warp's layout in 64-bit integers
+// (kernels.hpp pitch_tables), the window table of the warped signals for everything behind the warp, both uploaded from the pinned block
+// behind the durations' place in it -- no host wait beyond the one for the frame counts -- and the phoneme starts for
+// sts_get_phoneme_offsets.  The prototype goes to the device once per engine.
+int Engine::pitch_geometry(RunCtx& c) {
+    const int B = c.B, hop = c.hop;
+    if (!d_pitch_table_) {
+        std::vector<float> proto(kPitchTableFloats);
+        pitch_table(proto.data());
+        HIPCK(hipMalloc((void**)&d_pitch_table_, proto.size() * 4));
+        HIPCK(hipMemcpy(d_pitch_table_, proto.data(), proto.size() * 4, hipMemcpyHostToDevice));
+    }
+    std::vector<int64_t> steps((size_t)c.Ttot);
+    std::vector<const int32_t*> dur((size_t)B);
+    std::vector<const int64_t*> step((size_t)B);
+    std::vector<long long> xoff((size_t)B);
+    for (int b = 0; b < B; b++) {
+        const size_t t = (size_t)c.offT[b];
+        dur[b] = durations_h.data() + t;
+        step[b] = pitch_has[(size_t)b] ? steps.data() + t : nullptr;
+        if (step[b]) for (int i = 0; i < c.lenT[b]; i++) steps[t + i] = pitch_step(pitch_cents[t + i]);
+        xoff[b] = (long long)c.p_offF[b] * hop;
+    }
+    PitchTables tab;
+    if (const char* bad = pitch_tables(B, c.lenT.data(), dur.data(), step.data(), xoff.data(), hop, &tab)) return fail(STS_EINVAL, bad);
+    if (tab.TT != c.pitch_rows) return fail(STS_EDEVICE, "pitch plan: the tables do not have the size the setup reserved");
+    if (tab.total_out > 2000000000LL || out_count(tab.total_out) + B > 2147483647LL) return fail(STS_EINVAL, "batch produces too many samples for one call");
+    c.pitch_nout = tab.nout; c.pitch_total = tab.total_out; c.pitch_max = tab.max_out;
+    // phoneme starts in the warped signal: o_i of a planned utterance (the words' o_i+1 column), frames * hop of a copied one
+    last_pitch_start.assign((size_t)c.Ttot, 0);
+    {
+        const long long* mem = tab.words.data();
+        const long long* oend = mem + 6 * (size_t)B;
+        for (int b = 0; b < B; b++) {
+            const size_t t = (size_t)c.offT[b];
+            const long long toff = mem[6 * (size_t)b + 4], rows = mem[6 * (size_t)b + 5];
+            long long f = 0;
+            for (int i = 0; i < c.lenT[b]; i++) {
+                if (!step[b]) last_pitch_start[t + i] = f * hop;
+                else last_pitch_start[t + i] = (i == 0 || rows < c.lenT[b]) ? 0 : oend[toff + i - 1];     // (rows < n: all durations 0, every start 0)
+                f += durations_h[t + i];
+            }
+        }
+    }
+    // staging behind the durations' download: [words | win: off B, off B, N' B]
+    char* stage = pinned_ + c.up_bytes + (((size_t)c.Ttot + B) * 4 + 7) / 8 * 8;
+    memcpy(stage, tab.words.data(), tab.words.size() * 8);
+    int* win = (int*)(stage + tab.words.size() * 8);
+    long long off = 0;
+    for (int b = 0; b < B; b++) {
+        win[StepTab::zoff(B) + b] = (int)off; win[StepTab::coff(B) + b] = (int)off; win[StepTab::wlen(B) + b] = (int)tab.nout[b];
+        off += tab.nout[b];
+    }
+    HIPCK(hipMemcpyAsync(c.bt.pitch_words, stage, tab.words.size() * 8, hipMemcpyHostToDevice, stream));
+    HIPCK(hipMemcpyAsync(c.bt.pitch_win, win, (size_t)3 * B * 4, hipMemcpyHostToDevice, stream));
     return STS_OK;
 }
 
@@ -1041,6 +1160,7 @@ int Engine::frame_geometry(RunCtx& c) {
     c.Fld = (B == 1 && !ss) ? (c.Ftot + 63) / 64 * 64 : c.Ftot;
     c.maxFld = (B == 1 && !ss) ? (int)c.Fld : c.maxF;
     if ((double)c.Fld * hop > 2.0e9 || (double)c.Fld * hop * 8 > 6.0e10) return fail(STS_EINVAL, "batch produces too many samples for one call");
+    if (c.pitch) { const int rc = pitch_geometry(c); if (rc != STS_OK) return rc; }
     if (c.join) {     // the joined signal's layout (64-bit host arithmetic): F_J frames, sentence b at last_join_start[b]
         c.FJ = (long long)c.Ftot + join_total_sil;
         const long long NJ = c.FJ * hop;
@@ -1056,7 +1176,7 @@ int Engine::frame_geometry(RunCtx& c) {
     }
     h_pcm = nullptr; pcm_in_host_ = false;
     if (host_pcm && !ss) {   // room for the PCM download that rides at the end of this run
-        const long long native = c.join ? c.FJ * hop : (long long)c.Fld * hop;       // (a joined run returns the joined signal)
+        const long long native = c.join ? c.FJ * hop : c.pitch ? c.pitch_total : (long long)c.Fld * hop;       // (a joined run returns the joined signal, a run with a pitch plan the warped ones)
         const size_t need = (size_t)(out_count(native) + (c.oc.run[OS_RESAMPLE] ? B : 0)) * 2 + 256;
         if (need > pinned_pcm_cap_) {
             if (pinned_pcm_) (void)hipHostFree(pinned_pcm_);
@@ -1134,6 +1254,7 @@ int Engine::run_frame_workspace(RunCtx& c) {
     const OutChain& oc = c.oc;
     c.Ocap = oc.run[OS_RESAMPLE] ? out_count((long long)Wcap * hop) + B : (long long)Wcap * hop;
     if (c.join) c.Ocap = oc.run[OS_RESAMPLE] ? out_count(c.FJ * hop) + 1 : c.FJ * hop;
+    if (c.pitch) c.Ocap = oc.run[OS_RESAMPLE] ? out_count(c.pitch_total) + B : c.pitch_total;      // (everything behind the warp sees the warped signals)
     const long long jwin = ss && c.join ? c.js.window_frames() * hop : c.FJ * hop;      // floats of the join's output: a step's window of J, or J
     if (ss && c.join) c.Ocap = oc.run[OS_RESAMPLE] ? out_count(jwin) + 4 : jwin;         // (the widened range of a step lies inside its window's outputs)
     if (ss && oc.run[OS_LIMIT] && oc.run[OS_RESAMPLE]) c.Ocap += B;       // (a window's widened output range is rounded per window)
@@ -1201,9 +1322,14 @@ int Engine::run_frame_workspace(RunCtx& c) {
             bf.ldres = A.get<char>(lds_res_bytes(nu, tiles));
         }
     };
-    arenaF_.measuring = true; layoutF(arenaF_);
+    auto layoutF_all = [&](Arena& A) {
+        layoutF(A);
+        // (a run with a pitch plan: behind everything else, so that every other buffer lies where it lies without it)
+        bf.wave_pitch = c.pitch ? A.get<float>((size_t)c.pitch_total) : nullptr;
+    };
+    arenaF_.measuring = true; layoutF_all(arenaF_);
     if (!ensure(arenaF_, arenaF_.used + 4096)) return fail(STS_EDEVICE, "out of device memory (frame-level workspace)");
-    arenaF_.measuring = false; layoutF(arenaF_);
+    arenaF_.measuring = false; layoutF_all(arenaF_);
     poison_arena(arenaF_);
     if ((oc.lws || oc.lst) && loud_cap_ < B) {      // host-mapped room for the results: the gating kernel writes them there, the run's last synchronisation covers them
         if (loud_host_) (void)hipHostFree(loud_host_);
@@ -1354,6 +1480,7 @@ int Engine::run(int B, const int32_t* const* ids, const int32_t* n, const int32_
     have_plan = false;          // a duration plan is for one call, whatever its outcome; the repeat inside the call above applied it again
     have_mix = false;           // and so is a speaker mix
     have_gain = false;          // and a gain plan
+    have_pitch = false;         // and a pitch plan
     return rc;
 }
 // the overflow word of conv math 3 (host-mapped) and its device address, allocated by the first call that needs it
@@ -1414,7 +1541,7 @@ int Engine::run_once(int B, const int32_t* const* ids, const int32_t* n, const i
     for (double& f : bytes_w_) f = 0;
     mfma_flops_ = 0; mfma_exec_ = 0; bf16_exec_ = 0; mfma_launches_ = 0; in_mfma_region_ = false;
 
-    loud_res.clear(); loud_slots.clear(); lim_res.clear(); last_join_start.clear();
+    loud_res.clear(); loud_slots.clear(); lim_res.clear(); last_join_start.clear(); last_pitch_start.clear();
     if (ss && loud_mode != 0 && !loud_streaming)
         return fail(STS_EINVAL, "streaming is not available while loudness measurement or normalization is on (sts_set_loudness mode 0 first): "
                                 "normalizing needs the whole utterance before its first sample leaves");
@@ -1473,7 +1600,7 @@ int Engine::run_output(RunCtx& c) {
         }
     }
     const long Fcount = c.Ftot;                // (from here on: the real count)
-    for (int b = 0; b < B; b++) n_samples[b] = (int32_t)out_count((long long)p_lenF[b] * hop);     // (at the output rate)
+    for (int b = 0; b < B; b++) n_samples[b] = (int32_t)out_count(c.pitch ? c.pitch_nout[(size_t)b] : (long long)p_lenF[b] * hop);     // (at the output rate)
     const int nres = c.join ? 1 : B;           // utterances the output side saw: a joined run's one signal
     if (c.join) n_samples.assign(1, (int32_t)out_count(c.FJ * hop));
     if (!ss) {
@@ -1872,6 +1999,7 @@ int Engine::stream_open(int chunk_frames, int max_live, long long capacity_frame
     if (eq_n > 0 && !eq_streaming) return fail(STS_EINVAL, "an open stream is not available while an equaliser is set: its state is carried per utterance in the frame arena");
     if (loud_mode == 2 || (loud_mode != 0 && !loud_streaming)) return fail(STS_EINVAL, "an open stream is not available while loudness measurement or normalization is on: its state is carried per utterance in the frame arena");
     if (record_taps) return fail(STS_EINVAL, "an open stream is not available while taps are recorded");
+    if (refuse_pitch("an open stream")) return STS_EINVAL;
     if (have_plan || have_mix || have_gain || have_forced)
         return fail(STS_EINVAL, "an open stream is not available while a duration plan, a speaker mix, a gain plan or forced durations are pending: their tables are per call");
     HIPCK(hipSetDevice(device));
@@ -2039,6 +2167,7 @@ int Engine::stream_admit_once(int B, const int32_t* const* ids, const int32_t* n
 int Engine::stream_admit(int B, const int32_t* const* ids, const int32_t* n, const int32_t* sid, const float* ls, const sts_stream_noise* nz,
                          int32_t* slot_out, int32_t* n_samples_out, int32_t* admitted) {
     if (!live_) return fail(STS_ESTATE, "no stream is open on this engine (sts_stream_open first)");
+    if (refuse_pitch("an admission into an open stream")) { drop_tables(); if (admitted) *admitted = 0; return STS_EINVAL; }
     // (a planned stream: the pending tables are for this admission only, whatever its outcome -- no room and a failure included; dropped
     // here, behind the last attempt, so that the form-0 repeat below applies them again)
     struct Drop { Engine& e; ~Drop() { e.drop_tables(); } } drop{*this};
@@ -2138,6 +2267,7 @@ int Engine::para_open(int chunk_frames, int max_resident, long long capacity_fra
     if (eq_n > 0) return fail(STS_EINVAL, "an open paragraph is not available while an equaliser is set: its state is carried in the frame arena");
     if (loud_mode != 0) return fail(STS_EINVAL, "an open paragraph is not available while loudness measurement or normalization is on: its state is carried in the frame arena");
     if (record_taps) return fail(STS_EINVAL, "an open paragraph is not available while taps are recorded");
+    if (refuse_pitch("an open paragraph")) return STS_EINVAL;
     if (have_plan || have_mix || have_gain || have_forced)
         return fail(STS_EINVAL, "an open paragraph is not available while a duration plan, a speaker mix, a gain plan or forced durations are pending: their tables are per call");
     const sts_join j{nullptr, lead_frames, 0, fade_ms};
@@ -2247,6 +2377,7 @@ int Engine::para_append(int B, const int32_t* const* ids, const int32_t* n, cons
     if (!para_) return fail(STS_ESTATE, "no paragraph is open on this engine (sts_para_open first)");
     if (!appended) return fail(STS_EINVAL, "an append needs the `appended` output");
     *appended = 0;
+    if (refuse_pitch("an open paragraph")) return STS_EINVAL;
     ParaStream& P = *para_;
     if (P.finished) return fail(STS_EINVAL, "the paragraph is finished: it takes no more sentences");
     if (B < 1 || !ids || !n) return fail(STS_EINVAL, "an append takes B >= 1 sentences with ids and n");

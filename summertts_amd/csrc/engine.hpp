@@ -311,6 +311,8 @@ private:
     // (the members of the equaliser sit behind everything else: the layout of the members above stays what it was)
     EqTable* d_eq_ = nullptr; int eq_tab_rate_ = 0; bool eq_dirty_ = true;        // the EQ's tables on the device, the rate they were built for
     int eq_prepare();                                                             // a run with an EQ: the bands against the current rate, the tables
+    float* d_pitch_table_ = nullptr;   // the prototype on the device, uploaded by the first run with a pitch plan
+    int pitch_geometry(RunCtx& c);     // a run with a pitch plan, when its durations are on the host: the layout, its upload, the counts
 public:
     // parametric equaliser (sts_set_eq, eq.hip): eq_n bands, 0 = off (nothing extra runs).  Every whole-utterance call filters the float
     // wave at the output rate in front of loudness and the limiter; with neither downstream the EQ kernel writes the PCM.  The device
@@ -338,7 +340,7 @@ public:
     // conditioning vector, a gain-planned slot's cum / q columns and {off, n, h}) moves into pools of the stream's own at admission
     // (adopt_tables, one launch next to adopt_z), and a step reads them by slot.  0: exactly the stream above.
     int stream_open(int chunk_frames, int max_live, long long capacity_frames, long long capacity_phonemes = 0);
-    void drop_tables() { have_plan = have_mix = have_gain = have_forced = false; }
+    void drop_tables() { have_plan = have_mix = have_gain = have_forced = have_pitch = false; }
     int stream_admit(int B, const int32_t* const* ids, const int32_t* n, const int32_t* sid, const float* ls, const sts_stream_noise* noise,
                      int32_t* slot_out, int32_t* n_samples_out, int32_t* admitted);
     int stream_step(int (*cb)(void*, int32_t, const int16_t*, int32_t, int32_t), void* user, int32_t* live_after);
@@ -364,6 +366,21 @@ public:
     // a measuring open stream: the slots retired by the most recent step that measured, ascending -- loud_res holds their results in
     // this order (sts_stream_get_loudness)
     std::vector<int32_t> loud_slots;
+    // pitch plan (sts_set_pitch_plan, pitch_plan.hip): for the NEXT call only, whatever its outcome, like the gain plan.  pitch_cents: the
+    // cents of the whole batch (0 for an utterance without a plan), pitch_has[b]: entry b came with cents, pitch_n: the phoneme counts the
+    // next call must have.  The run multiplies its duration plan's rates by the ratios (run_setup), lays the warp out on the host when the
+    // durations arrive (pitch_geometry) and launches the warp kernel behind the gain kernel (decode_end).  Whole-utterance calls only.
+    std::vector<int32_t> pitch_n, pitch_cents; std::vector<char> pitch_has; bool have_pitch = false;
+    int set_pitch_plan(int B, const int32_t* n, const sts_pitch_plan* plans);
+    // first output of every phoneme of the last run in native samples of the WARPED signal, packed like durations_h (empty: the last run
+    // had no pitch plan): what sts_get_phoneme_offsets converts instead of frames * hop
+    std::vector<int64_t> last_pitch_start;
+    // a pending pitch plan and a call form that cannot apply one: the plan is dropped and the call refused
+    bool refuse_pitch(const char* what) {
+        if (!have_pitch) return false;
+        have_pitch = false; err_ = std::string("a pitch plan is pending: ") + what + " cannot apply one (the plan is dropped)";
+        return true;
+    }
     // loudness in a stream (sts_set_loudness_streaming; loudness.hip's stream mode, loud_stream.hpp): off, a stream under mode 1 or 2 is
     // refused; on, mode 1 measures what each step delivers from a state carried per utterance in the frame arena (mode 2 stays refused)
     bool loud_streaming = false;

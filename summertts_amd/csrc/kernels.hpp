@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "../../include/summertts_hip.h"
+#include "pitch_layout.hpp"
 
 namespace sts {
 
@@ -526,6 +527,33 @@ struct GainArgs {
 };
 // one launch: nmem members x ceil(max_len / 4096) tiles; max_len = the longest member's sample count or more
 void gain_plan_run(const GainArgs& a, int nmem, long long max_len, hipStream_t st);
+
+// Pitch plans (pitch_plan.hip; the definition is there and in include/summertts_hip.h sts_set_pitch_plan; the host arithmetic in
+// pitch_layout.hpp)
+double bessel_i0(double x);              // (resample.hip) modified Bessel function of the first kind, order 0, for x <= 10
+// one utterance's plan: cents (or null) each in [-600, 600]
+bool pitch_plan_valid(int n, const int32_t* cents, const char** why);
+// the prototype h0: kPitchTableFloats floats (sts_pitch_table)
+void pitch_table(float* table);
+// The tables of one launch, built on the host from the final durations: words = [member B x {xoff, N, yoff, N', toff, rows} | o_i+1 |
+// (a_i << 32) + e_i | step_i | c_i (double) | K_i], the five per-phoneme arrays TT long each and packed over the planned members only.
+struct PitchTables { std::vector<long long> words; long long TT = 0, total_out = 0, max_out = 0; std::vector<long long> nout; };
+// member b: n[b] phonemes with the durations dur[b] and the steps step[b] (null: no plan, the member is copied), its samples from xoff[b]
+// on in x; the outputs are packed back to back in member order.  Null, or why the layout is refused
+const char* pitch_tables(int B, const int32_t* n, const int32_t* const* dur, const int64_t* const* step, const long long* xoff, int hop,
+                         PitchTables* t);
+struct PitchArgs {
+    const float* x;                      // the native float wave
+    float* y; int16_t* pcm;              // the warped signals, packed back to back by the members' N', each optional
+    const long long* mem;                // [members][6] (PitchTables::words on the device; pitch_args_carve sets these six)
+    const long long *oend, *pos0, *step; const double* c; const long long* K;
+    const float* table;                  // the prototype (device memory)
+};
+void pitch_args_carve(PitchArgs& a, const long long* dev_words, int B, long long TT);
+// one launch: nmem members x ceil(max_out / 256) tiles; max_out = the longest member's N' or more.  table_in_lds: every workgroup stages
+// the prototype (64 KiB) in LDS instead of reading it from global memory
+bool pitch_table_in_lds();              // the shipped choice (sts_debug_pitch_bench times both)
+void pitch_plan_run(const PitchArgs& a, int nmem, long long max_out, bool table_in_lds, hipStream_t st);
 
 // Paragraph join (join.hip; the definition is there and in include/summertts_hip.h sts_infer_ids_joined)
 constexpr int kJoinMaxFrames = 100000, kJoinMaxH = 800;

@@ -105,6 +105,8 @@ struct sts_multi {
     // sts_multi_set_gain_plan: the next batch's gain plans, per utterance of the caller's batch (gain_db: n entries or empty = absent)
     struct UttGain { std::vector<float> gain_db; float ramp_ms = 0.f; };
     std::vector<UttGain> gain; std::vector<int32_t> gain_n; bool have_gain = false;
+    // sts_multi_set_pitch_plan: the next batch's pitch plans, per utterance of the caller's batch (cents: n entries or empty = absent)
+    std::vector<std::vector<int32_t>> pitch; std::vector<int32_t> pitch_n; bool have_pitch = false;
     std::vector<Shard> shards;
     // RCCL gather state (gather_mode == 1)
     int gather_mode = 0;
@@ -316,8 +318,13 @@ struct sts_multi {
                     }
                     sh.rc = eng.set_gain_plan(nb, nn.data(), gp.data());
                 }
+                if (sh.rc == STS_OK && have_pitch) {    // and the pitch plans
+                    std::vector<sts_pitch_plan> pp(nb);
+                    for (int i = 0; i < nb; i++) pp[i] = sts_pitch_plan{pitch[sh.utt[i]].empty() ? nullptr : pitch[sh.utt[i]].data()};
+                    sh.rc = eng.set_pitch_plan(nb, nn.data(), pp.data());
+                }
                 if (sh.rc == STS_OK) sh.rc = eng.run(nb, idp.data(), nn.data(), sd.data(), l.data());
-                else { sh.err = eng.error(); eng.set_duration_plan(0, nullptr, nullptr); eng.set_speaker_mix(0, nullptr); eng.set_gain_plan(0, nullptr, nullptr); }     // (nothing ran: nothing stays pending)
+                else { sh.err = eng.error(); eng.set_duration_plan(0, nullptr, nullptr); eng.set_speaker_mix(0, nullptr); eng.set_gain_plan(0, nullptr, nullptr); eng.set_pitch_plan(0, nullptr, nullptr); }     // (nothing ran: nothing stays pending)
                 eng.noise_utt.clear();
                 if (sh.rc == STS_OK && gather_mode == 1) {
                     sh.n_samples = eng.n_samples;           // the PCM stays on the device: rccl_gather() below
@@ -483,6 +490,21 @@ int sts_multi_set_gain_plan(sts_multi* m, int32_t B, const int32_t* n, const sts
     m->have_gain = true;
     return STS_OK;
 }
+int sts_multi_set_pitch_plan(sts_multi* m, int32_t B, const int32_t* n, const sts_pitch_plan* plans) {
+    if (!m) return multi_err(STS_EINVAL, "null handle");
+    if (B == 0 || !plans) { m->have_pitch = false; return STS_OK; }
+    if (B < 0 || !n) return multi_err(STS_EINVAL, "pitch plan: B >= 0 and n are required");
+    for (int b = 0; b < B; b++) {
+        const char* why = nullptr;
+        if (!pitch_plan_valid(n[b], plans[b].cents, &why)) return multi_err(STS_EINVAL, why);
+    }
+    m->pitch.assign((size_t)B, std::vector<int32_t>());
+    m->pitch_n.assign(n, n + B);
+    for (int b = 0; b < B; b++)
+        if (plans[b].cents) m->pitch[b].assign(plans[b].cents, plans[b].cents + n[b]);
+    m->have_pitch = true;
+    return STS_OK;
+}
 int sts_multi_set_speaker_mix(sts_multi* m, int32_t B, const sts_speaker_mix* mixes) {
     if (!m) return multi_err(STS_EINVAL, "null handle");
     if (B == 0 || !mixes) { m->have_mix = false; return STS_OK; }
@@ -605,7 +627,7 @@ int sts_multi_shard_of(const sts_multi* m, int32_t B, const int32_t* n, int32_t*
 int sts_multi_infer_ids_batch(sts_multi* m, int32_t B, const int32_t* const* ids, const int32_t* n, const int32_t* sid,
                               const float* length_scale, int16_t** pcm_out, int32_t* n_out) {
     if (!m) return multi_err(STS_EINVAL, "bad arguments");
-    struct DropPlan { sts_multi* m; ~DropPlan() { m->have_plan = false; m->have_mix = false; m->have_gain = false; } } drop_plan{m};      // a duration plan, a speaker mix and a gain plan are for this call only, whatever its outcome
+    struct DropPlan { sts_multi* m; ~DropPlan() { m->have_plan = false; m->have_mix = false; m->have_gain = false; m->have_pitch = false; } } drop_plan{m};      // a duration plan, a speaker mix and a gain plan are for this call only, whatever its outcome
     if (!ids || !n || !pcm_out || !n_out || B <= 0) return multi_err(STS_EINVAL, "bad arguments");
     for (int b = 0; b < B; b++) { pcm_out[b] = nullptr; n_out[b] = 0; }      // every output is defined before the first early return
     for (int b = 0; b < B; b++) if (n[b] <= 0 || !ids[b]) return multi_err(STS_EINVAL, "utterance with no phonemes");
@@ -619,6 +641,11 @@ int sts_multi_infer_ids_batch(sts_multi* m, int32_t B, const int32_t* const* ids
         bool same = (int)m->gain_n.size() == B;
         for (int b = 0; b < B && same; b++) same = m->gain_n[b] == n[b];
         if (!same) return multi_err(STS_EINVAL, "the gain plan was set for another batch (B and every n[b] must match)");
+    }
+    if (m->have_pitch) {
+        bool same = (int)m->pitch_n.size() == B;
+        for (int b = 0; b < B && same; b++) same = m->pitch_n[b] == n[b];
+        if (!same) return multi_err(STS_EINVAL, "the pitch plan was set for another batch (B and every n[b] must match)");
     }
     const int ndev = (int)m->engines.size();
     const bool was_gather = m->gather_mode == 1;

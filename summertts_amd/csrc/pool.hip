@@ -33,6 +33,8 @@ struct Request {
     bool mixed = false; SpeakerMixCopy mix;
     // sts_pool_submit_gain: this request's gain plan (gained: an entry with gains; gain_db: n entries)
     bool gained = false; std::vector<float> gain_db; float ramp_ms = 0.f;
+    // sts_pool_submit_pitch: this request's pitch plan (pitched: an entry with cents; cents: n entries)
+    bool pitched = false; std::vector<int32_t> cents;
     // sts_pool_submit_joined: a paragraph -- its sentences (ids / sid / ls above stay empty), the join (gaps copied: join.gap_frames points
     // into them, or is null) -- run as its own packed batch; sentence b samples with noise.seed + b
     bool joined = false; std::vector<std::vector<int32_t>> sent_ids; std::vector<int32_t> sent_sid; std::vector<float> sent_ls;
@@ -139,8 +141,8 @@ struct sts_pool {
     // failure nothing stays pending for another group.
     int set_group_tables(Engine& eng, const std::vector<std::shared_ptr<Request>>& grp, const int32_t* n) {
         const int B = (int)grp.size();
-        bool any_plan = false, any_mix = false, any_gain = false;
-        for (int b = 0; b < B; b++) { any_plan = any_plan || grp[b]->planned; any_mix = any_mix || grp[b]->mixed; any_gain = any_gain || grp[b]->gained; }
+        bool any_plan = false, any_mix = false, any_gain = false, any_pitch = false;
+        for (int b = 0; b < B; b++) { any_plan = any_plan || grp[b]->planned; any_mix = any_mix || grp[b]->mixed; any_gain = any_gain || grp[b]->gained; any_pitch = any_pitch || grp[b]->pitched; }
         int rc = STS_OK;
         if (any_plan) {
             std::vector<sts_dur_plan> pl(B, sts_dur_plan{nullptr, nullptr, 0});
@@ -158,6 +160,11 @@ struct sts_pool {
             std::vector<sts_gain_plan> gp(B, sts_gain_plan{nullptr, 0.f});
             for (int b = 0; b < B; b++) if (grp[b]->gained) gp[b] = sts_gain_plan{grp[b]->gain_db.data(), grp[b]->ramp_ms};
             rc = eng.set_gain_plan(B, n, gp.data());
+        }
+        if (rc == STS_OK && any_pitch) {    // (the members without one: an entry without cents, copied bit for bit)
+            std::vector<sts_pitch_plan> pp(B, sts_pitch_plan{nullptr});
+            for (int b = 0; b < B; b++) if (grp[b]->pitched) pp[b] = sts_pitch_plan{grp[b]->cents.data()};
+            rc = eng.set_pitch_plan(B, n, pp.data());
         }
         if (rc != STS_OK) eng.drop_tables();
         return rc;
@@ -489,6 +496,27 @@ int64_t sts_pool_submit_joined(sts_pool* p, int32_t B, const int32_t* const* ids
 int64_t sts_pool_submit_stream(sts_pool* p, const int32_t* ids, int32_t n, int32_t sid, float length_scale, float noise_scale,
                                float noise_scale_w, uint64_t seed, int32_t chunk_frames, sts_chunk_cb cb, void* user) {
     return sts_pool_submit_stream_ex(p, ids, n, sid, length_scale, noise_scale, noise_scale_w, seed, chunk_frames, cb, user, nullptr, nullptr, nullptr);
+}
+
+int64_t sts_pool_submit_pitch(sts_pool* p, const int32_t* ids, int32_t n, int32_t sid, float length_scale, float noise_scale,
+                              float noise_scale_w, uint64_t seed, const sts_pitch_plan* plan) {
+    if (!p || !ids || n <= 0) return pool_err(STS_EINVAL, "bad request");
+    if (!noise_scale_valid(noise_scale) || !noise_scale_valid(noise_scale_w)) return pool_err(STS_EINVAL, "noise scales must be finite and >= 0");
+    const char* why = nullptr;
+    if (plan && !pitch_plan_valid(n, plan->cents, &why)) return pool_err(STS_EINVAL, why);
+    auto r = std::make_shared<Request>();
+    r->ids.assign(ids, ids + n); r->sid = sid; r->ls = length_scale; r->noise = Engine::Noise{noise_scale, noise_scale_w, seed};
+    r->pitched = plan && plan->cents;
+    if (r->pitched) r->cents.assign(plan->cents, plan->cents + n);
+    {
+        std::lock_guard<std::mutex> lk(p->mu);
+        if (p->stop) return pool_err(STS_ESTATE, "pool is shutting down");
+        r->ticket = p->next_ticket++;
+        p->queue.push_back(r);
+        p->pending[r->ticket] = r;
+    }
+    p->cv_work.notify_one();
+    return r->ticket;
 }
 
 int64_t sts_pool_submit_stream_ex(sts_pool* p, const int32_t* ids, int32_t n, int32_t sid, float length_scale, float noise_scale,

@@ -22,7 +22,7 @@ namespace sts {
 static long long gcd_ll(long long a, long long b) { while (b) { const long long t = a % b; a = b; b = t; } return a; }
 
 // modified Bessel function of the first kind, order 0 (power series; converges for the arguments used here, x <= 10)
-static double bessel_i0(double x) {
+double bessel_i0(double x) {
     double s = 1.0, t = 1.0;
     const double q = x * x / 4.0;
     for (int k = 1; k < 200; k++) {

@@ -31,6 +31,9 @@ struct BufT {
     int *gain_q, *gain_h;
     // a joined run only (null otherwise): the uploaded silence table [B] behind the gain plan's (JoinArgs::sil)
     int* join_sil;
+    // a run with a pitch plan only (null otherwise): the warp's tables (kernels.hpp PitchTables::words, sized at setup for the planned
+    // members' phonemes) and, behind them, the window table of the warped signals [off B | off B | N' B] (decoder.hip WinGeom)
+    long long* pitch_words; int* pitch_win;
 };
 struct BufF {
     float *z, *h, *acts, *out, *x0, *regA, *regB, *tailA, *tailB, *tailC, *wave, *fliptmp;
@@ -48,6 +51,7 @@ struct BufF {
     float* wave_join;
     char* stab; int16_t* spack; float *gwin, *cond_win;
     float* wave_eq; char* eqws;
+    float* wave_pitch;         // a run with a pitch plan only (null otherwise): the warped signals, packed back to back
     // a stream that runs the EQ only (null otherwise): the carried state [B][2] slots (eq_stream.hpp) and the step's tile end states
     char* eqst; double* eqsE;
     // a stream that measures loudness only (null otherwise): the carried state [B][2] slots (loud_stream.hpp), the step's tile end states,
@@ -78,6 +82,10 @@ struct Engine::RunCtx {
     bool gain = false;              // this run applies a gain plan (sts_set_gain_plan): the gain kernel runs behind the decoder's tail; never launched ahead, never in the memo
     bool join = false;              // this run joins its sentences into one signal (sts_infer_ids_joined): the join kernel runs behind the decoder's tail (and the gain kernel); never launched ahead, never in the memo
     long long FJ = 0;               // a joined run: frames of the joined signal (sum of the sentences' + lead + gaps + trail)
+    // this run applies a pitch plan (sts_set_pitch_plan): the warp kernel runs behind the gain kernel; never launched ahead, never in the
+    // memo.  Made by pitch_geometry when the durations are on the host: pitch_rows (the tables' per-phoneme length), every utterance's
+    // warped sample count, their sum and maximum
+    bool pitch = false; long long pitch_rows = 0, pitch_total = 0, pitch_max = 0; std::vector<long long> pitch_nout;
     bool mix = false;               // this run blends speakers (sts_set_speaker_mix): bt.g comes from speaker_blend; never launched ahead, never in the memo
     std::vector<Engine::Noise> nz; bool any_ns = false, any_nsw = false;   // per-utterance sampling noise (engine.hpp Noise), which of the two is used
     std::vector<unsigned long long> req_keys; std::vector<long> predF;      // launch-ahead memo: per-utterance request hashes, remembered frame counts (empty: not all known)

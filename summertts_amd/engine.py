@@ -133,6 +133,32 @@ def _gain_plans(n: Sequence[int], plans):
     return n, arr, keep
 
 
+class PitchPlan(C.Structure):
+    """``sts_pitch_plan``: one utterance's pitch plan (include/summertts_hip.h sts_set_pitch_plan)."""
+    _fields_ = [("cents", C.c_void_p)]
+
+
+def _pitch_plans(n: Sequence[int], plans):
+    """-> (n as int32 array, ctypes array of PitchPlan, the numpy arrays it points into).  ``plans[b]``: None (no plan) or a mapping with
+    ``cents`` (int per phoneme), or the sequence of cents itself."""
+    n = np.ascontiguousarray(n, dtype=np.int32)
+    if len(plans) != n.size:
+        raise ValueError("one plan (or None) per utterance")
+    arr, keep = (PitchPlan * max(n.size, 1))(), []
+    for b, p in enumerate(plans):
+        v = p.get("cents") if isinstance(p, dict) else p
+        if v is not None:
+            v = np.asarray(v)
+            if v.dtype.kind not in "iu":
+                raise ValueError(f"plan {b}: cents are integers")
+            v = np.ascontiguousarray(v, dtype=np.int32).ravel()
+            if v.size != n[b]:
+                raise ValueError(f"plan {b}: cents needs one entry per phoneme")
+            keep.append(v)
+            arr[b].cents = v.ctypes.data
+    return n, arr, keep
+
+
 class Join(C.Structure):
     """``sts_join``: how the sentences of a paragraph are joined (include/summertts_hip.h sts_infer_ids_joined)."""
     _fields_ = [("gap_frames", C.c_void_p), ("lead_frames", C.c_int32), ("trail_frames", C.c_int32), ("fade_ms", C.c_float)]
@@ -300,6 +326,18 @@ def load_library() -> C.CDLL:
     lib.sts_debug_col_layer.argtypes = ([C.c_int, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int64] + [C.c_void_p] * 5 + [C.c_int32] * 3 +
                                         [C.c_void_p] * 7 + [C.c_int32] * 2 + [C.c_void_p] * 2 + [C.c_float] + [C.c_void_p] * 2 + [C.c_int32] +
                                         [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p])
+    lib.sts_set_pitch_plan.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
+    lib.sts_multi_set_pitch_plan.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
+    lib.sts_pool_submit_pitch.restype = C.c_int64
+    lib.sts_pool_submit_pitch.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_float, C.c_uint64, C.c_void_p]
+    lib.sts_pitch_plan_check.argtypes = [C.c_int32, C.c_void_p, C.c_void_p]
+    lib.sts_pitch_design.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
+    lib.sts_pitch_layout.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
+    lib.sts_pitch_table.argtypes = [C.c_void_p, C.c_int64]
+    lib.sts_pitch_apply.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                    C.c_void_p, C.c_int64]
+    lib.sts_debug_pitch_bench.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64,
+                                          C.c_int32, C.c_int32, C.POINTER(C.c_float)]
     lib.sts_pool_submit_gain.restype = C.c_int64
     lib.sts_pool_submit_gain.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_float, C.c_uint64, C.c_void_p]
     lib.sts_join_check.argtypes = [C.c_int32, C.c_void_p]
@@ -390,6 +428,8 @@ EXPORTED_SYMBOLS = [
     "sts_multi_set_speaker_mix",
     "sts_set_gain_plan", "sts_gain_plan_check", "sts_gain_design", "sts_gain_plan_apply", "sts_pool_submit_gain",
     "sts_multi_set_gain_plan",
+    "sts_set_pitch_plan", "sts_pool_submit_pitch", "sts_multi_set_pitch_plan",
+    "sts_debug_pitch_bench", "sts_pitch_plan_check", "sts_pitch_design", "sts_pitch_layout", "sts_pitch_table", "sts_pitch_apply",
     "sts_debug_spline_step", "sts_debug_attention", "sts_debug_layer_norm", "sts_debug_resblock_layer", "sts_debug_col_layer",
     "sts_join_check", "sts_join_layout", "sts_join_apply", "sts_infer_ids_joined", "sts_get_join_offsets", "sts_pool_submit_joined",
     "sts_infer_ids_joined_stream", "sts_join_apply_range",
@@ -551,6 +591,89 @@ def gain_plan_apply(signals, durations, plans, samples_per_frame: int, device: i
     _check(lib, lib.sts_gain_plan_apply(int(device), x.ctypes.data, d.ctypes.data, nn.ctypes.data, len(ds), int(samples_per_frame),
                                         C.cast(arr, C.c_void_p), y.ctypes.data, pcm.ctypes.data))
     return _split(y, lens), _split(pcm, lens)
+
+
+PITCH_TABLE_FLOATS = 16386
+
+
+def pitch_plan_check(n: Sequence[int], plans) -> None:
+    """The validity rules of a pitch plan (include/summertts_hip.h sts_pitch_plan_check; host only, no GPU) for ``plans`` (as
+    ``Synthesizer.set_pitch_plan`` takes them) of ``n[b]`` phonemes each.  Raises StsError for an invalid plan."""
+    lib = load_library()
+    nn, arr, keep = _pitch_plans(n, plans)
+    _check(lib, lib.sts_pitch_plan_check(nn.size, nn.ctypes.data, C.cast(arr, C.c_void_p)))
+
+
+def pitch_design(cents, n: int):
+    """Step 1 of the pitch-plan definition (sts_pitch_design; host only): ``cents`` None or ``n`` ints -> (ratio float32 [n], step int64
+    [n]): the duration ratios and the Q32 input samples per output sample."""
+    lib = load_library()
+    _, arr, keep = _pitch_plans([n], [cents])
+    ratio, step = np.zeros(max(int(n), 1), np.float32), np.zeros(max(int(n), 1), np.int64)
+    _check(lib, lib.sts_pitch_design(arr[0].cents, int(n), ratio.ctypes.data, step.ctypes.data))
+    return ratio[:int(n)], step[:int(n)]
+
+
+def pitch_layout(durations, step, samples_per_frame: int):
+    """Step 3 of the pitch-plan definition (sts_pitch_layout; host only): frames and Q32 steps per phoneme -> (o, e), int64 [n + 1] each:
+    the first output of every phoneme (o[n]: the warped length) and the Q32 offset of that output behind the phoneme's first sample."""
+    lib = load_library()
+    d = np.ascontiguousarray(durations, dtype=np.int32).ravel()
+    s = np.ascontiguousarray(step, dtype=np.int64).ravel()
+    if s.size != d.size:
+        raise ValueError("one step per phoneme")
+    o, e = np.zeros(d.size + 1, np.int64), np.zeros(d.size + 1, np.int64)
+    _check(lib, lib.sts_pitch_layout(d.ctypes.data, s.ctypes.data, d.size, int(samples_per_frame), o.ctypes.data, e.ctypes.data))
+    return o, e
+
+
+def pitch_table() -> np.ndarray:
+    """The interpolator's prototype h0 (sts_pitch_table; host only): 16386 float32."""
+    lib = load_library()
+    t = np.zeros(PITCH_TABLE_FLOATS, np.float32)
+    _check(lib, lib.sts_pitch_table(t.ctypes.data, t.size))
+    return t
+
+
+def pitch_apply(signals, durations, plans, samples_per_frame: int, device: int = 0):
+    """The pitch-plan kernel on caller signals (sts_pitch_apply): ``durations`` a list of int arrays (frames per phoneme), one per
+    utterance; ``signals[b]`` its float signal of ``max(1, sum d) * samples_per_frame`` samples; ``plans`` as
+    ``Synthesizer.set_pitch_plan`` takes them -> (y, pcm): lists of the warped float32 signals and their int16 casts, ``len(y[b])`` the
+    warped length."""
+    lib = load_library()
+    ds = [np.ascontiguousarray(d, dtype=np.int32).ravel() for d in durations]
+    sig, x, _, _ = _pack_signals(signals)
+    if len(sig) != len(ds):
+        raise ValueError("one signal per utterance")
+    for b, v in enumerate(sig):
+        if v.size != max(1, int(ds[b].sum())) * int(samples_per_frame):
+            raise ValueError(f"signal {b} needs max(1, sum d) * samples_per_frame samples")
+    nn, arr, keep = _pitch_plans([d.size for d in ds], plans)
+    d = np.concatenate(ds) if ds and sum(v.size for v in ds) else np.zeros(1, np.int32)
+    lens = np.zeros(max(len(ds), 1), np.int64)
+    args = (int(device), x.ctypes.data, d.ctypes.data, nn.ctypes.data, len(ds), int(samples_per_frame), C.cast(arr, C.c_void_p))
+    _check(lib, lib.sts_pitch_apply(*args, lens.ctypes.data, None, None, 0))
+    lens = lens[:len(ds)]
+    total = int(lens.sum())
+    y = np.zeros(max(total, 1), np.float32)
+    pcm = np.zeros(max(total, 1), np.int16)
+    _check(lib, lib.sts_pitch_apply(*args, lens.ctypes.data, y.ctypes.data, pcm.ctypes.data, total))
+    return _split(y, lens), _split(pcm, lens)
+
+
+def pitch_bench(signal, durations, cents, samples_per_frame: int, table_in_lds: bool, iters: int = 50, device: int = 0):
+    """Lab (sts_debug_pitch_bench): the warp of one utterance with the prototype in LDS or in global memory -> (y, mean milliseconds of
+    ``iters`` launches)."""
+    lib = load_library()
+    d = np.ascontiguousarray(durations, dtype=np.int32).ravel()
+    x = np.ascontiguousarray(signal, dtype=np.float32).ravel()
+    nn, arr, keep = _pitch_plans([d.size], [cents])
+    cap = 2 * x.size + 64
+    y = np.zeros(cap, np.float32)
+    ms = C.c_float()
+    _check(lib, lib.sts_debug_pitch_bench(int(device), x.ctypes.data, d.ctypes.data, nn.ctypes.data, 1, int(samples_per_frame),
+                                          C.cast(arr, C.c_void_p), y.ctypes.data, cap, int(bool(table_in_lds)), int(iters), C.byref(ms)))
+    return y, float(ms.value)
 
 
 def join_check(B: int, join) -> None:
@@ -1388,6 +1511,16 @@ class Synthesizer:
         nn, arr, keep = _gain_plans(n, plans)
         _check(self.lib, self.lib.sts_set_gain_plan(self.h, nn.size, nn.ctypes.data, C.cast(arr, C.c_void_p)))
 
+    def set_pitch_plan(self, n: Optional[Sequence[int]], plans=None):
+        """Pitch plan of the NEXT call only (include/summertts_hip.h sts_set_pitch_plan).  ``n``: phoneme count of every utterance of that
+        call; ``plans``: per utterance None, a sequence of cents per phoneme (integers in [-600, 600]) or a mapping with ``cents``.  The
+        formants move with the pitch.  ``n`` or ``plans`` None drops a pending plan.  An invalid plan raises and changes nothing."""
+        if n is None or plans is None:
+            _check(self.lib, self.lib.sts_set_pitch_plan(self.h, 0, None, None))
+            return
+        nn, arr, keep = _pitch_plans(n, plans)
+        _check(self.lib, self.lib.sts_set_pitch_plan(self.h, nn.size, nn.ctypes.data, C.cast(arr, C.c_void_p)))
+
     def speaker_embedding(self, sid: int) -> np.ndarray:
         """Row ``sid`` of the model's speaker table: float32 [gin_channels] (sts_get_speaker_embedding)."""
         out = np.zeros(max(int(self.info.gin_channels), 1), np.float32)
@@ -1731,13 +1864,23 @@ class Pool:
         return t
 
     def submit(self, ids: Sequence[int], sid: int = 0, length_scale: float = 1.0, noise_scale: float = 0.0,
-               noise_scale_w: float = 0.0, seed: int = 0, plan=None, mix=None, gain=None) -> int:
+               noise_scale_w: float = 0.0, seed: int = 0, plan=None, mix=None, gain=None, pitch=None) -> int:
         """Queue one request; the noise arguments are this request's own (``Synthesizer.set_noise``; ``seed`` is used as given), and so
         is ``plan``: None or a mapping as ``Synthesizer.set_duration_plan`` takes per utterance (sts_pool_submit_plan), or ``mix``: None
         or a mapping as ``Synthesizer.set_speaker_mix`` takes per utterance (sts_pool_submit_mix).  One request carries a plan or a mix,
         not both.  ``gain``: None or a mapping as ``Synthesizer.set_gain_plan`` takes per utterance (sts_pool_submit_gain); a request with
-        a gain plan carries neither of the other two."""
+        a gain plan carries neither of the other two.  ``pitch``: None or the cents per phoneme as ``Synthesizer.set_pitch_plan`` takes
+        them per utterance (sts_pool_submit_pitch); a request with a pitch plan carries none of the other three."""
         a = np.ascontiguousarray(ids, dtype=np.int32)
+        if pitch is not None:
+            if plan is not None or mix is not None or gain is not None:
+                raise ValueError("a request with a pitch plan carries no duration plan, no mix and no gain plan")
+            _, arr, keep = _pitch_plans([a.size], [pitch])
+            t = int(self.lib.sts_pool_submit_pitch(self.h, a.ctypes.data, a.size, sid, length_scale, float(noise_scale), float(noise_scale_w),
+                                                   int(seed) & 0xFFFFFFFFFFFFFFFF, C.cast(arr, C.c_void_p)))
+            if t <= 0:
+                raise StsError(f"sts_pool_submit: {t}: {self.lib.sts_pool_last_error().decode()}")
+            return t
         if plan is not None and mix is not None:
             raise ValueError("a request carries a plan or a mix, not both")
         if gain is not None and (plan is not None or mix is not None):
@@ -1971,6 +2114,17 @@ class MultiDevice:
             rc = self.lib.sts_multi_set_gain_plan(self.h, nn.size, nn.ctypes.data, C.cast(arr, C.c_void_p))
         if rc != 0:
             raise StsError(f"sts_multi_set_gain_plan: {rc}: {self.lib.sts_multi_last_error().decode()}")
+
+    def set_pitch_plan(self, n: Optional[Sequence[int]], plans=None):
+        """``Synthesizer.set_pitch_plan`` for the next ``infer_batch``: ``plans[b]`` belongs to utterance b of that batch, whatever its
+        device."""
+        if n is None or plans is None:
+            rc = self.lib.sts_multi_set_pitch_plan(self.h, 0, None, None)
+        else:
+            nn, arr, keep = _pitch_plans(n, plans)
+            rc = self.lib.sts_multi_set_pitch_plan(self.h, nn.size, nn.ctypes.data, C.cast(arr, C.c_void_p))
+        if rc != 0:
+            raise StsError(f"sts_multi_set_pitch_plan: {rc}: {self.lib.sts_multi_last_error().decode()}")
 
     def set_conv_math(self, mode):
         m = {"bf16x3": 0, "f32": 1, "bf16x3_all": 2, "f16x2": 3}.get(mode, mode)
