@@ -917,6 +917,41 @@ int sts_debug_conv1d_packed(int device, const float* x, int32_t Cin, int32_t L, 
                             int32_t depthwise, float in_slope, int32_t in_act, int mode, float** y, int32_t* Lout,
                             const int32_t* lengths, int32_t B, uint32_t* ovf);
 
+/* sts_debug_conv1d_epi (detected by symbol, ABI 18): sts_debug_conv1d_packed with the epilogues and operand forms the engine gives its
+ * convs (kernels.hpp ConvArgs).  opts null: sts_debug_conv1d_packed, bit for bit (gap must then be 0).
+ *   epi        0 STORE  y = v | 1 RESADD  y = v + res | 3 SUB  y = y_init - v | 4 GATE  y[c] = tanh(v[c]) sigmoid(v[c + H]), Cout = 2 H |
+ *              5 RESSKIP  Cout = 2 H: y = y_init + v[:H], aux = (epi_flag & 1 ? 0 : aux_init) + v[H:]; Cout = H: every row goes to aux |
+ *              6 TANH_PCM  aux (the wave, optional) = tanh(v), pcm = trunc(wave * 32737), Cout = 1;   v = conv + bias + ubias[:, b]
+ *   gate_perm  1 (GATE, H % 16 == 0): the weights, the bias and ubias are packed with the loader's (tanh16, sigmoid16) row order
+ *   in_reflect 1: the logical input of segment b is its reflect-pad-left-1 view (len + 1 positions: p reads x[p - 1], p = 0 reads x[1]);
+ *              output segment b is len + 1 long and starts at off[b] + b
+ *   nsum       0, or 2 / 3: the logical input is ((x + xs1) [+ xs2]) / nsum, formed by the kernel while it stages its input
+ *   kslices    1, or 2 / 4 / 8 (STORE on the split-K modes 8 / 9): y holds kslices partial planes [kslices][Cout][Lout], bias on plane 0
+ *   ubias      [Cout][B] in source row order, or null;  res / y_init / aux_init: the shape of the tensor they belong to;  xs1, xs2: as x
+ * gap: segment b starts at off[b] = sum_{i < b} (lengths[i] + gap), so L = sum(lengths) + B gap (gap 0: the engine's packing); output
+ * segment b starts at off[b] * stride (+ b with in_reflect) and Lout = L * stride (+ B).  y has Cout rows (GATE and RESSKIP: H), aux H
+ * rows (TANH_PCM: 1), pcm one.  Every column of y / aux / pcm outside the output segments holds the sentinel 0xFFFFFFFF (pcm: 0x7FFF)
+ * before the launch, and so does a whole tensor without an initial value; a tensor WITH an initial value (the target of a
+ * read-modify-write epilogue) holds the finite sentinel 0x2F5A5A5A (1.99e-10) there instead, whatever y_init / aux_init hold in those
+ * columns, so that an update running into them changes their bits; all columns come back.
+ * Everything a kernel family does not take is STS_EINVAL (nothing falls back to another kernel), decided before any device call. */
+typedef struct sts_conv_epi_opts {
+    int32_t size_bytes;         /* sizeof(sts_conv_epi_opts) */
+    int32_t epi, epi_flag, H, gate_perm, in_reflect, nsum, kslices;
+    const float* ubias;
+    const float* res;
+    const float* y_init;
+    const float* aux_init;
+    const float* xs1;
+    const float* xs2;
+    float* aux_out;             /* caller-allocated [H or 1][Lout] */
+    int16_t* pcm_out;           /* caller-allocated [Lout] */
+} sts_conv_epi_opts;
+int sts_debug_conv1d_epi(int device, const float* x, int32_t Cin, int32_t L, const float* w, const float* bias,
+                         int32_t Cout, int32_t k, int32_t pad, int32_t dil, int32_t stride_transposed,
+                         int32_t depthwise, float in_slope, int32_t in_act, int mode, float** y, int32_t* Lout,
+                         const int32_t* lengths, int32_t B, uint32_t* ovf, const sts_conv_epi_opts* opts, int32_t gap);
+
 /* One "same"-padded conv (odd k, pad = dil (k - 1) / 2) through the pre-split path of the wide decoder stages (conv_h2p.hip): x fp32
  * [Cin][L] -> split_planes(in_slope) -> conv_h2p_group with `members` identical members -> member 0's three output forms, each decoded to
  * fp32 [Cout][L] (null: not wanted): y = the channel-major fp32 output, y16 = the channel-minor fp32 copy, yp = the two fp16 planes of

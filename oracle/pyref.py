@@ -163,6 +163,9 @@ def _port():
         lib.port_resblock_layer.restype = None
         lib.port_resblock_layer.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
                                             C.c_int32, C.c_float]
+        lib.port_wn_layer.restype = None
+        lib.port_wn_layer.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
+                                      C.c_void_p, C.c_int32]
         lib.port_dds_layer.restype = None
         lib.port_dds_layer.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32] + [C.c_void_p] * 6
         lib.port_convflow_step.restype = None
@@ -235,6 +238,31 @@ def port_resblock_layer(x, lengths, w1, b1, dil1: int, w2, b2, slope: float) -> 
         out[:, off:off + n] = part
         off += n
     return out
+
+
+def port_wn_layer(x, out, lengths, in_w, in_b, dil: int, rs_w, rs_b, g2=None):
+    """The oracle's WaveNet layer (vits_oracle.c wn_layer, what wn_forward loops over) on a packed batch: gate = tanh . sigmoid of the in conv
+    (+ g2 [2 H, B], the utterances' conditioning), then the 1x1 res / skip conv: rs_w [2 H][1][H] -> (x + rs[:H], out + rs[H:]); rs_w [H][1][H]
+    (the last layer) -> (x, out + rs).  x, out float32 [H][sum(lengths)] -> the updated pair, every utterance on its own."""
+    lib = _port()
+    f = lambda a: None if a is None else np.ascontiguousarray(a, dtype=np.float32)
+    x, out, in_w, in_b, rs_w, rs_b, g2 = f(x), f(out), f(in_w), f(in_b), f(rs_w), f(rs_b), f(g2)
+    H = x.shape[0]
+    assert out.shape == x.shape and int(np.sum(lengths)) == x.shape[1] and in_w.shape[0] == 2 * H and in_w.shape[2] == H and in_w.shape[1] % 2 == 1
+    assert rs_w.shape in ((H, 1, H), (2 * H, 1, H)) and (g2 is None or g2.shape == (2 * H, len(lengths)))
+    xo, oo = np.zeros_like(x), np.zeros_like(out)
+    off = 0
+    for b, n in enumerate(lengths):
+        n = int(n)
+        px = np.array(x[:, off:off + n], dtype=np.float32, order="C", copy=True)
+        po = np.array(out[:, off:off + n], dtype=np.float32, order="C", copy=True)
+        gb = None if g2 is None else np.ascontiguousarray(g2[:, b])
+        lib.port_wn_layer(px.ctypes.data, po.ctypes.data, H, n, in_w.ctypes.data, None if in_b is None else in_b.ctypes.data, in_w.shape[1], int(dil),
+                          rs_w.ctypes.data, None if rs_b is None else rs_b.ctypes.data, None if gb is None else gb.ctypes.data,
+                          1 if rs_w.shape[0] == H else 0)
+        xo[:, off:off + n], oo[:, off:off + n] = px, po
+        off += n
+    return xo, oo
 
 
 def _opt(a, shape=None):

@@ -346,7 +346,7 @@ int sts_debug_adopt_tables(int device, const float* g, int32_t gin, int32_t B, f
 static int debug_conv1d_impl(int device, const float* x, int32_t Cin, int32_t L, const float* w, const float* bias, int32_t Cout,
                              int32_t k, int32_t pad, int32_t dil, int32_t stride_t, int32_t depthwise, float in_slope,
                              int32_t in_act, int mode, float** y_out, int32_t* Lout_out, int32_t iters, float* ms_out,
-                             const int32_t* lengths, int32_t B, uint32_t* ovf_out);
+                             const int32_t* lengths, int32_t B, uint32_t* ovf_out, const sts_conv_epi_opts* eo = nullptr, int32_t gap = 0);
 
 int sts_debug_conv1d(int device, const float* x, int32_t Cin, int32_t L, const float* w, const float* bias, int32_t Cout,
                      int32_t k, int32_t pad, int32_t dil, int32_t stride_t, int32_t depthwise, float in_slope, int32_t in_act,
@@ -370,31 +370,66 @@ int sts_debug_conv1d_packed(int device, const float* x, int32_t Cin, int32_t L, 
                              0, nullptr, lengths, B, ovf_out);
 }
 
-// lengths == null: one segment of L positions (the stand-alone entries); else B segments packed back to back, as the engine packs a batch
+int sts_debug_conv1d_epi(int device, const float* x, int32_t Cin, int32_t L, const float* w, const float* bias, int32_t Cout,
+                         int32_t k, int32_t pad, int32_t dil, int32_t stride_t, int32_t depthwise, float in_slope,
+                         int32_t in_act, int mode, float** y_out, int32_t* Lout_out, const int32_t* lengths, int32_t B, uint32_t* ovf_out,
+                         const sts_conv_epi_opts* opts, int32_t gap) {
+    if (!lengths) return set_err(STS_EINVAL, "packed conv: null segment lengths");
+    if (!opts && gap != 0) return set_err(STS_EINVAL, "conv epilogues: a gap between the segments needs the options struct");
+    return debug_conv1d_impl(device, x, Cin, L, w, bias, Cout, k, pad, dil, stride_t, depthwise, in_slope, in_act, mode, y_out, Lout_out,
+                             0, nullptr, lengths, B, ovf_out, opts, gap);
+}
+
+// The argument checks of sts_debug_conv1d_epi's options (include/summertts_hip.h), none of which needs a device
+static int check_epi_opts(const sts_conv_epi_opts& o, int Cout, bool tr, bool depthwise, int gap) {
+    if (o.size_bytes < (int32_t)sizeof(sts_conv_epi_opts)) return set_err(STS_EINVAL, "conv epilogues: size_bytes is smaller than sts_conv_epi_opts");
+    if (gap < 0 || gap > 4096) return set_err(STS_EINVAL, "conv epilogues: 0 <= gap <= 4096");
+    if (depthwise) return set_err(STS_EINVAL, "conv epilogues: dense convs only");
+    const int e = o.epi;
+    if (e != EPI_STORE && e != EPI_RESADD && e != EPI_SUB && e != EPI_GATE && e != EPI_RESSKIP && e != EPI_TANH_PCM) return set_err(STS_EINVAL, "conv epilogues: unknown epi");
+    if (e == EPI_GATE && (o.H <= 0 || Cout != 2 * o.H)) return set_err(STS_EINVAL, "conv epilogues: GATE needs H > 0 and Cout == 2 H");
+    if (o.gate_perm && (e != EPI_GATE || o.H % 16 != 0)) return set_err(STS_EINVAL, "conv epilogues: gate_perm is the packing of a GATE conv with H % 16 == 0");
+    if (e == EPI_RESSKIP && (o.H <= 0 || (Cout != o.H && Cout != 2 * o.H))) return set_err(STS_EINVAL, "conv epilogues: RESSKIP needs H > 0 and Cout == H or 2 H");
+    if (e == EPI_RESSKIP && (!o.aux_out || (!(o.epi_flag & 1) && !o.aux_init) || (Cout != o.H && !o.y_init)))
+        return set_err(STS_EINVAL, "conv epilogues: RESSKIP needs aux_out, aux_init (unless epi_flag & 1) and, with Cout == 2 H, y_init");
+    if (e == EPI_TANH_PCM && (Cout != 1 || !o.pcm_out)) return set_err(STS_EINVAL, "conv epilogues: TANH_PCM needs Cout == 1 and pcm_out");
+    if (e == EPI_RESADD && !o.res) return set_err(STS_EINVAL, "conv epilogues: RESADD needs res");
+    if (e == EPI_SUB && !o.y_init) return set_err(STS_EINVAL, "conv epilogues: SUB needs y_init");
+    if (o.nsum != 0 && o.nsum != 2 && o.nsum != 3) return set_err(STS_EINVAL, "conv epilogues: nsum is 0, 2 or 3");
+    if ((o.nsum >= 2 && !o.xs1) || (o.nsum == 3 && !o.xs2)) return set_err(STS_EINVAL, "conv epilogues: nsum needs xs1 (and xs2 for 3)");
+    if (o.kslices != 1 && o.kslices != 2 && o.kslices != 4 && o.kslices != 8) return set_err(STS_EINVAL, "conv epilogues: kslices is 1, 2, 4 or 8");
+    if (o.kslices > 1 && e != EPI_STORE) return set_err(STS_EINVAL, "conv epilogues: K slices are partial sums of the STORE epilogue");
+    if (o.in_reflect && tr) return set_err(STS_EINVAL, "conv epilogues: no reflect view on a transposed conv");
+    return STS_OK;
+}
+
+// lengths == null: one segment of L positions (the stand-alone entries); else B segments packed back to back, as the engine packs a batch.
+// eo != null (sts_debug_conv1d_epi): the epilogue and operand forms of ConvArgs, and `gap` unused columns behind every segment
 static int debug_conv1d_impl(int device, const float* x, int32_t Cin, int32_t L, const float* w, const float* bias, int32_t Cout,
                              int32_t k, int32_t pad, int32_t dil, int32_t stride_t, int32_t depthwise, float in_slope,
                              int32_t in_act, int mode, float** y_out, int32_t* Lout_out, int32_t iters, float* ms_out,
-                             const int32_t* lengths, int32_t B, uint32_t* ovf_out) {
+                             const int32_t* lengths, int32_t B, uint32_t* ovf_out, const sts_conv_epi_opts* eo, int32_t gap) {
     if (!x || !w || !y_out || !Lout_out || Cin <= 0 || Cout <= 0 || L <= 0 || k <= 0) return set_err(STS_EINVAL, "bad conv arguments");
     const bool tr = stride_t > 0;
     const bool packed = lengths != nullptr;
+    if (eo) { if (const int rc = check_epi_opts(*eo, Cout, tr, depthwise != 0, gap)) return rc; }
+    const int epi = eo ? eo->epi : EPI_STORE, nsl = eo ? eo->kslices : 1, reflect = eo && eo->in_reflect ? 1 : 0;
     int maxlen = L;
     std::vector<int> seg(8, 0);       // {off = 0, len = 1} | .. | overflow word [4] | .. | the packed table [8 ..)
     seg[1] = 1;
     if (packed) {
         if (B <= 0 || dil < 1) return set_err(STS_EINVAL, "packed conv: B >= 1 segments and dil >= 1");
         std::vector<int> tab;
-        if (const int rc = conv_segments(lengths, B, L, tab, &maxlen)) return rc;
+        if (eo && (int64_t)B * gap >= L) return set_err(STS_EINVAL, "packed conv: L must equal the sum of the segment lengths and their gaps");
+        if (const int rc = conv_segments(lengths, B, L - (eo ? B * gap : 0), tab, &maxlen)) return rc;
+        if (eo) for (int b = 0; b < B; b++) tab[b] += b * gap;          // off[b] = sum_{i < b} (len_i + gap)
         seg.insert(seg.end(), tab.begin(), tab.end());
         if ((int64_t)L * (tr ? stride_t : 1) > (int64_t)1 << 26) return set_err(STS_EINVAL, "packed conv: at most 2^26 output positions");
         // the geometries the engine launches on packed buffers: output segment = input segment (x stride)
         if (tr ? (k < stride_t || ((k - stride_t) & 1) || pad != (k - stride_t) / 2 || dil != 1) : (!(k & 1) || pad != dil * (k - 1) / 2))
             return set_err(STS_EINVAL, "packed conv: 'same' padding (odd k, pad = dil (k - 1) / 2) or a transposed conv with pad = (k - stride) / 2");
     }
-    int count = 0;
-    if (hipGetDeviceCount(&count) != hipSuccess || count <= 0) return set_err(STS_EDEVICE, "no HIP device visible (no CPU fallback)");
-    if (hipSetDevice(device) != hipSuccess) return set_err(STS_EDEVICE, "hipSetDevice failed");
-    const int Lout = tr ? (L - 1) * stride_t - 2 * pad + (k - 1) + 1 : L + 2 * pad - dil * (k - 1);
+    const int Lout = (tr ? (L - 1) * stride_t - 2 * pad + (k - 1) + 1 : L + 2 * pad - dil * (k - 1)) + (reflect ? B : 0);     // (reflect view: one more position per segment)
     if (Lout <= 0) return set_err(STS_EINVAL, "empty output");
     auto r_up = [](int v, int m) { return (v + m - 1) / m * m; };
     const int cin_eff = depthwise ? 1 : Cin;
@@ -404,6 +439,7 @@ static int debug_conv1d_impl(int device, const float* x, int32_t Cin, int32_t L,
     // the fp32 copy the loader makes: plain / depthwise (pack_conv) or polyphase (pack_convT)
     const HConv hc = host_conv(w, bias, Cout, cin_eff, k);
     PackOpts po; po.depthwise = depthwise != 0;
+    if (eo && eo->gate_perm) { po.gate = true; po.gate_H = eo->H; }        // the WN in_layer's packing (model.hip parse_pack_wn)
     std::vector<float> wp(wn, 0.f), bp(Cout_pad, 0.f);
     if (tr && !depthwise) { convT_layout(hc, stride_t, Cin_pad, Cout_pad, wp.data()); if (bias) memcpy(bp.data(), bias, sizeof(float) * Cout); }
     else conv_layout(hc, po, Cin_pad, Cout_pad, wp.data(), bias ? bp.data() : nullptr);
@@ -439,33 +475,95 @@ static int debug_conv1d_impl(int device, const float* x, int32_t Cin, int32_t L,
         wb3.resize(bf3_pack(wp.data(), tr ? stride_t : 1, tr ? J : k, Cin_pad, Cout_pad, nullptr, false, h2 ? 1 : 0));
         bf3_pack(wp.data(), tr ? stride_t : 1, tr ? J : k, Cin_pad, Cout_pad, wb3.data(), false, h2 ? 1 : 0, &h2_scale);
     }
-    DevScratch d;
-    const size_t yn = (size_t)Cout * Lout;
+    // everything of the launch that is no device pointer
     ConvArgs a;
     memset(&a, 0, sizeof(a));
-    a.x = d.up(x, (size_t)Cin * L); a.x_ld = L; a.y_ld = Lout;
-    a.w = (const float*)d.zeros((wn + kWeightSlackFloats) * 4, wp.data(), wn * 4);
-    const float* db = d.up(bp.data(), bp.size());
-    a.bias = bias ? db : nullptr;
-    // packed: a NaN pattern instead of zeros, so that a position no workgroup writes cannot pass
-    a.y = packed ? d.out(yn) : (float*)d.zeros(yn * 4);
-    const int* dseg = d.up(seg.data(), seg.size());
-    if (!wu.empty()) { a.wu = (const float*)d.zeros((wu.size() + kWeightSlackFloats) * 4, wu.data(), wu.size() * 4); a.wino_n3 = wn3; a.wino_n2 = wn2; }
-    if (bf3) a.wb3 = d.zeros(wb3.size() + kBf3SlackBytes, wb3.data(), wb3.size());
-    if (!d.ok) return set_err(STS_EDEVICE, DevScratch::kNoBuffers);
+    a.x_ld = L; a.y_ld = Lout;
     a.Cin = cin_eff; a.Cout = Cout; a.Cin_pad = Cin_pad; a.Cout_pad = Cout_pad;
     a.depthwise = depthwise ? 1 : 0;
     if (tr) { a.ntap = J; a.tap_step = -1; a.tap_off = 0; a.out_stride = stride_t; a.out_off = -pad; a.transposed = 1; a.n_extra = J - 1; a.max_n = L + J - 1; }
     else { a.ntap = k; a.tap_step = dil; a.tap_off = -pad; a.out_stride = 1; a.out_off = 0; a.max_n = Lout; }
-    a.in_act = in_act; a.in_slope = in_slope; a.epi = EPI_STORE;
-    // segment lengths in base units: in = L, out = Lout -> two views over the same {off=0,len=1} table
-    a.in_seg = SegView{dseg, dseg + 1, L, 0}; a.out_seg = SegView{dseg, dseg + 1, Lout, 0}; a.B = 1;
-    if (packed) {     // real offset / length tables of B entries (behind the overflow word), output scale = stride
-        a.in_seg = SegView{dseg + 8, dseg + 8 + B, 1, 0}; a.out_seg = SegView{dseg + 8, dseg + 8 + B, tr ? stride_t : 1, 0}; a.B = B;
-        a.max_n = tr ? maxlen + J - 1 : maxlen;
-    }
-    if (h2) { a.math = 1; a.wscale = h2_scale; a.ovf = (unsigned*)dseg + 4; }     // (overflow word: behind the segment table)
+    a.in_act = in_act; a.in_slope = in_slope; a.epi = epi;
+    a.B = 1;
+    if (packed) { a.B = B; a.max_n = tr ? maxlen + J - 1 : maxlen + reflect; }
+    if (h2) { a.math = 1; a.wscale = h2_scale; }
     if (rowph) { a.rowph = stride_t; a.Cout = a.Cout_pad = Cout_pad * stride_t; }
+    if (!wu.empty()) { a.wino_n3 = wn3; a.wino_n2 = wn2; }
+    // rows of y and aux, and the K-slice planes of y
+    const int y_rows = eo && (epi == EPI_GATE || epi == EPI_RESSKIP) ? eo->H : Cout;
+    const int aux_rows = epi == EPI_RESSKIP ? eo->H : (epi == EPI_TANH_PCM && eo->aux_out ? 1 : 0);
+    const size_t yn = (size_t)y_rows * Lout * nsl;
+    if (eo) {
+        a.epi_flag = eo->epi_flag; a.H = eo->H; a.gate_perm = eo->gate_perm ? 1 : 0; a.in_reflect = reflect; a.nsum = eo->nsum >= 2 ? eo->nsum : 0;
+        a.ubias_ld = B; a.res_ld = Lout; a.aux_ld = Lout;
+        if (nsl > 1) { a.kslices = nsl; a.kslice_stride = (long)y_rows * Lout; }
+        // what the named kernel family takes, by the engine's own eligibility functions (which look at no operand but whether the weight
+        // copies exist): nothing falls back to another kernel
+        static const float here = 0.f;
+        ConvArgs p = a;
+        if (bf3) p.wb3 = &here;
+        if (!wu.empty()) p.wu = &here;
+        if (eo->nsum >= 2) { p.xs1 = &here; p.xs2 = eo->nsum == 3 ? &here : nullptr; }
+        if (rowph && (epi != EPI_STORE || eo->ubias)) return set_err(STS_EINVAL, "row-interleaved phases: the plain epilogue only");
+        if (a.gate_perm && tr) return set_err(STS_EINVAL, "conv epilogues: no gate packing of a transposed conv");
+        const bool mfma = !bf3 && mode != 12 && mode != 1 && conv_mfma_eligible(p);
+        if (bf3 && !conv_bf3_eligible(p)) return set_err(STS_EINVAL, "shape or epilogue not eligible for the split-bf16 kernel");
+        if (mode == 12 && !conv_wino_eligible(p)) return set_err(STS_EINVAL, "shape or epilogue not eligible for the Winograd kernel");
+        if (!bf3 && mode >= 2 && mode != 12 && !mfma) return set_err(STS_EINVAL, "shape or epilogue not eligible for the matrix-core kernel");
+        if (nsl > 1 && !(mfma && (mode == 8 || mode == 9))) return set_err(STS_EINVAL, "K slices: the split-K modes 8 / 9 only");
+        if (a.nsum) {
+            // (modes 42 / 43 = tiles 22 / 23: the tiles conv_bf3.hip's switch instantiates with SUM -- keep in step with it and with
+            // conv_bf3_takes_sum, which cannot judge here because it asks for the AUTOMATIC tile of the shape)
+            const bool folds = bf3 ? (tr && !reflect && (mode == 42 || mode == 43)) : (!mfma && mode != 12 && conv_cout1_takes(p));
+            if (!folds) return set_err(STS_EINVAL, "nsum: the phase-merged split-operand tiles of a transposed conv (modes 42 / 43 / 82 / 83) and the single-output-channel kernel only");
+        }
+    }
+    int count = 0;
+    if (hipGetDeviceCount(&count) != hipSuccess || count <= 0) return set_err(STS_EDEVICE, "no HIP device visible (no CPU fallback)");
+    if (hipSetDevice(device) != hipSuccess) return set_err(STS_EDEVICE, "hipSetDevice failed");
+    DevScratch d;
+    a.x = d.up(x, (size_t)Cin * L);
+    a.w = (const float*)d.zeros((wn + kWeightSlackFloats) * 4, wp.data(), wn * 4);
+    const float* db = d.up(bp.data(), bp.size());
+    a.bias = bias ? db : nullptr;
+    // packed: a NaN pattern instead of zeros, so that a position no workgroup writes cannot pass
+    if (!eo) a.y = packed ? d.out(yn) : (float*)d.zeros(yn * 4);
+    const int* dseg = d.up(seg.data(), seg.size());
+    if (!wu.empty()) a.wu = (const float*)d.zeros((wu.size() + kWeightSlackFloats) * 4, wu.data(), wu.size() * 4);
+    if (bf3) a.wb3 = d.zeros(wb3.size() + kBf3SlackBytes, wb3.data(), wb3.size());
+    const int oscale = tr ? stride_t : 1;
+    if (eo) {
+        // y / aux: the sentinel everywhere, then the caller's initial values inside the output segments alone.  A tensor with initial
+        // values is the target of a read-modify-write epilogue: its sentinel is finite and tiny (0x2F5A5A5A = 1.99e-10), so that an update
+        // that runs into an unused column changes its bits (NaN + v would keep the NaN's)
+        auto initial = [&](const float* init, int rows, int planes) {
+            std::vector<float> h((size_t)rows * Lout * planes);
+            memset(h.data(), 0xFF, h.size() * 4);
+            if (init) { const uint32_t s = 0x2F5A5A5Au; for (float& f : h) memcpy(&f, &s, 4); }
+            if (init) for (int r = 0; r < rows; r++) for (int b = 0; b < B; b++) {
+                const size_t o = (size_t)r * Lout + (size_t)seg[8 + b] * oscale + (size_t)b * reflect;
+                memcpy(h.data() + o, init + o, ((size_t)lengths[b] * oscale + reflect) * 4);
+            }
+            return (float*)d.up(h.data(), h.size());
+        };
+        a.y = initial(eo->y_init, y_rows, nsl);
+        if (aux_rows) a.aux = initial(eo->aux_init, aux_rows, 1);
+        if (epi == EPI_TANH_PCM) a.pcm = d.out16((size_t)Lout);
+        a.res = d.up(eo->res, (size_t)Cout * Lout);
+        if (a.nsum) { a.xs1 = d.up(eo->xs1, (size_t)Cin * L); a.xs2 = d.up(eo->xs2, (size_t)Cin * L); }
+        if (eo->ubias) {      // rows in the packed order of the weights: the same layout code, on ubias as a [Cout][1][B] filter
+            std::vector<float> up((size_t)B * Cout_pad, 0.f), ub((size_t)Cout_pad * B, 0.f);
+            conv_layout(host_conv(eo->ubias, nullptr, Cout, B, 1), po, B, Cout_pad, up.data(), nullptr);
+            for (int r = 0; r < Cout_pad; r++) for (int b = 0; b < B; b++) ub[(size_t)r * B + b] = up[(size_t)b * Cout_pad + r];
+            a.ubias = d.up(ub.data(), ub.size());
+        }
+    }
+    if (!d.ok) return set_err(STS_EDEVICE, DevScratch::kNoBuffers);
+    // segment lengths in base units: in = L, out = Lout -> two views over the same {off=0,len=1} table
+    a.in_seg = SegView{dseg, dseg + 1, L, 0}; a.out_seg = SegView{dseg, dseg + 1, Lout, 0};
+    // packed: real offset / length tables of B entries (behind the overflow word), output scale = stride
+    if (packed) { a.in_seg = SegView{dseg + 8, dseg + 8 + B, 1, 0}; a.out_seg = SegView{dseg + 8, dseg + 8 + B, oscale, reflect}; }
+    if (h2) a.ovf = (unsigned*)dseg + 4;     // (overflow word: behind the segment table)
     auto launch = [&]() {
         if (bf3) conv_bf3(a, d.st, mode == 13 ? -1 : mode - 20);
         else if (mode == 12) conv_wino(a, d.st);
@@ -483,6 +581,7 @@ static int debug_conv1d_impl(int device, const float* x, int32_t Cin, int32_t L,
     float* y = (float*)malloc(yn * 4);
     if (!y) return set_err(STS_EDEVICE, "out of host memory");
     d.down(y, a.y, yn * 4);
+    if (eo) { d.down(eo->aux_out, a.aux, (size_t)aux_rows * Lout * 4); d.down(eo->pcm_out, a.pcm, (size_t)Lout * 2); }
     uint32_t word = 0;
     if (h2) d.down(&word, dseg + 4, 4);
     if (!d.finish()) { free(y); return set_err(STS_EDEVICE, "conv kernel failed"); }

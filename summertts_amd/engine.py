@@ -410,7 +410,7 @@ EXPORTED_SYMBOLS = [
     "sts_create", "sts_destroy", "sts_speaker_num", "sts_get_info", "sts_infer_ids", "sts_infer_ids_batch",
     "sts_run_batch", "sts_copy_pcm_device", "sts_copy_pcm_host", "sts_pcm_host_view", "sts_set_forced_durations",
     "sts_set_record_taps", "sts_get_tap", "sts_get_durations", "sts_set_conv_mode", "sts_set_conv_math", "sts_set_profiling",
-    "sts_get_profile", "sts_set_host_pcm", "sts_debug_conv1d", "sts_debug_conv1d_bench", "sts_debug_conv1d_packed", "sts_debug_conv_h2p", "sts_debug_conv_h2p_packed", "sts_debug_conv_h2w", "sts_free", "sts_last_error",
+    "sts_get_profile", "sts_set_host_pcm", "sts_debug_conv1d", "sts_debug_conv1d_bench", "sts_debug_conv1d_packed", "sts_debug_conv1d_epi", "sts_debug_conv_h2p", "sts_debug_conv_h2p_packed", "sts_debug_conv_h2w", "sts_free", "sts_last_error",
     "sts_infer_ids_stream", "sts_stream_halo_frames", "sts_debug_wino_pack", "sts_debug_set", "sts_multi_create_ex", "sts_multi_gather_mode", "sts_multi_gather_layout",
     "sts_pool_create", "sts_pool_destroy", "sts_pool_submit", "sts_pool_wait", "sts_pool_stats", "sts_pool_last_error",
     "sts_multi_create", "sts_multi_destroy", "sts_multi_device_count", "sts_multi_speaker_num", "sts_multi_infer_ids_batch",
@@ -1755,6 +1755,61 @@ def debug_conv1d_packed(x: np.ndarray, lengths, w: np.ndarray, bias: Optional[np
     out = np.ctypeslib.as_array(y, shape=(cout, lout.value)).copy()
     lib.sts_free(y)
     return (out, int(ovf.value)) if return_ovf else out
+
+
+class ConvEpiOpts(C.Structure):
+    """sts_conv_epi_opts (include/summertts_hip.h)."""
+    _fields_ = [("size_bytes", C.c_int32), ("epi", C.c_int32), ("epi_flag", C.c_int32), ("H", C.c_int32), ("gate_perm", C.c_int32),
+                ("in_reflect", C.c_int32), ("nsum", C.c_int32), ("kslices", C.c_int32),
+                ("ubias", C.c_void_p), ("res", C.c_void_p), ("y_init", C.c_void_p), ("aux_init", C.c_void_p), ("xs1", C.c_void_p),
+                ("xs2", C.c_void_p), ("aux_out", C.c_void_p), ("pcm_out", C.c_void_p)]
+
+
+EPI_STORE, EPI_RESADD, EPI_SUB, EPI_GATE, EPI_RESSKIP, EPI_TANH_PCM = 0, 1, 3, 4, 5, 6      # kernels.hpp Epilogue
+CONV_EPI_SENTINEL = 0xFFFFFFFF          # what the columns outside the output segments hold (pcm: 0x7FFF) ...
+CONV_EPI_SENTINEL_RMW = 0x2F5A5A5A      # ... and in a tensor that was given initial values: finite, so that old + v changes its bits
+
+
+def debug_conv1d_epi(x: np.ndarray, lengths, w: np.ndarray, bias: Optional[np.ndarray], dil: int = 1, stride_transposed: int = 0,
+                     in_slope: float = 0.0, in_act: int = 0, mode: int = 0, gap: int = 0, epi: int = EPI_STORE, epi_flag: int = 0, H: int = 0,
+                     gate_perm: int = 0, in_reflect: int = 0, nsum: int = 0, kslices: int = 1, ubias=None, res=None, y_init=None,
+                     aux_init=None, xs1=None, xs2=None, device: int = 0, size_bytes: Optional[int] = None, want_aux: Optional[bool] = None,
+                     want_pcm: Optional[bool] = None):
+    """One packed conv with an engine epilogue and operand form (sts_debug_conv1d_epi).  x: [Cin, sum(lengths) + B gap], every segment followed
+    by `gap` unused columns; the other operands have the shape of the tensor they belong to, ubias is [Cout, B] in source row order.  Returns a
+    dict: y [rows, Lout] (kslices > 1: [kslices, Cout, Lout]), ovf, and aux [H or 1, Lout] / pcm [Lout] for RESSKIP / TANH_PCM."""
+    lib = load_library()
+    f32 = lambda v: None if v is None else np.ascontiguousarray(v, np.float32)
+    ptr = lambda v: None if v is None else v.ctypes.data
+    x, w, b = f32(x), f32(w), f32(bias)
+    ln = np.ascontiguousarray(lengths, np.int32)
+    cout, k = w.shape[0], w.shape[1]
+    scale = max(stride_transposed, 1)
+    lout_want = x.shape[1] * scale + (ln.size if in_reflect else 0)
+    pad = (k - stride_transposed) // 2 if stride_transposed else dil * (k - 1) // 2
+    keep = [f32(v) for v in (ubias, res, y_init, aux_init, xs1, xs2)]
+    if want_aux is None:
+        want_aux = epi in (EPI_RESSKIP, EPI_TANH_PCM)
+    if want_pcm is None:
+        want_pcm = epi == EPI_TANH_PCM
+    aux = np.zeros((H if epi == EPI_RESSKIP else 1, lout_want), np.float32) if want_aux else None
+    pcm = np.zeros(lout_want, np.int16) if want_pcm else None
+    o = ConvEpiOpts(C.sizeof(ConvEpiOpts) if size_bytes is None else size_bytes, epi, epi_flag, H, gate_perm, in_reflect, nsum, kslices,
+                    *[ptr(v) for v in keep], ptr(aux), ptr(pcm))
+    y = C.POINTER(C.c_float)()
+    lout = C.c_int32()
+    ovf = C.c_uint32(0)
+    lib.sts_debug_conv1d_epi.argtypes = lib.sts_debug_conv1d.argtypes + [C.c_void_p, C.c_int32, C.POINTER(C.c_uint32), C.POINTER(ConvEpiOpts), C.c_int32]
+    _check(lib, lib.sts_debug_conv1d_epi(device, x.ctypes.data, x.shape[0], x.shape[1], w.ctypes.data, ptr(b), cout, k, pad, dil, stride_transposed,
+                                         0, in_slope, in_act, mode, C.byref(y), C.byref(lout), ln.ctypes.data, ln.size, C.byref(ovf),
+                                         C.byref(o), gap))
+    assert lout.value == lout_want, (lout.value, lout_want)
+    rows = H if epi in (EPI_GATE, EPI_RESSKIP) else cout
+    out = np.ctypeslib.as_array(y, shape=(kslices * rows, lout.value)).copy()
+    lib.sts_free(y)
+    if kslices > 1:
+        out = out.reshape(kslices, rows, lout.value)
+    return {"y": out, "ovf": int(ovf.value), "aux": aux, "pcm": pcm}
 
 
 def debug_conv_h2p_packed(x: np.ndarray, lengths, w: np.ndarray, bias: Optional[np.ndarray], dil: int = 1, res: Optional[np.ndarray] = None,

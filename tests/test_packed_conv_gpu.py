@@ -1,4 +1,5 @@
-"""GPU suite (MI355X): the conv kernels on PACKED batches, at the kernel.  sts_debug_conv1d_packed / sts_debug_conv_h2p_packed hand every kernel
+"""GPU suite (MI355X): the conv kernels' plain epilogue (y = conv + bias; every other epilogue and operand form: tests/test_conv_epi_gpu.py)
+on PACKED batches, at the kernel.  sts_debug_conv1d_packed / sts_debug_conv_h2p_packed hand every kernel
 family a real B-entry segment table whose boundaries sit on the tile widths (32 / 64 / 128 columns), one position either side of them, and
 around segments shorter than the conv's halo; the result is compared with a float64 convolution of every segment on its own
 (tests/packed_conv_ref.py).  Every second segment is 64 x louder than its neighbours, so one halo tap read across a boundary lands orders of
