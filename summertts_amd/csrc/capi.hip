@@ -266,9 +266,7 @@ int sts_stream_halo_frames(const sts_engine* e) {
 int sts_set_forced_durations(sts_engine* e, const int32_t* dur, int64_t count) {
     if (!e) return set_err(STS_EINVAL, "null engine");
     if (!(e->eng.live_ && e->eng.live_->planned())) STS_CAPI_NOT_WHILE_OPEN(e);     // (a planned open stream: for its next admission)
-    if (!dur || count <= 0) { e->eng.have_forced = false; return STS_OK; }
-    e->eng.forced_dur.assign(dur, dur + count);
-    e->eng.have_forced = true;
+    e->eng.set_forced_durations(dur, count);
     return STS_OK;
 }
 

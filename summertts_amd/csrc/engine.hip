@@ -12,6 +12,7 @@
 
 #include <algorithm>
 #include <chrono>
+#include <limits.h>
 #include <math.h>
 #include <new>
 #include <stdlib.h>
@@ -413,93 +414,126 @@ int Engine::eq_prepare() {
     eq_dirty_ = false; eq_tab_rate_ = out_rate;
     return STS_OK;
 }
-// sts_set_duration_plan: copied and validated here; an invalid plan changes nothing.  B == 0 or plans == null drops a pending plan.
+// sts_set_forced_durations: null or count <= 0 drops pending ones
+void Engine::set_forced_durations(const int32_t* dur, int64_t count) {
+    pend.have_forced = dur && count > 0;
+    if (pend.have_forced) pend.forced_dur.assign(dur, dur + count);
+}
+// What the four table setters share: B == 0 or no table drops the pending one (`have`), B < 0 (or no n where the kind has phoneme
+// counts, with_n) and B > max_B (message `over`, or the B >= 0 one) are refused, valid(b, &why) is asked per utterance, and a kind with
+// phoneme counts may have 2^24 in all (*total).  False: *rc is the setter's answer and nothing else has changed
+template <typename Valid>
+bool Engine::table_begin(const char* what, bool given, bool& have, int B, const int32_t* n, bool with_n, int max_B, const char* over, long* total, int* rc,
+                         Valid&& valid) {
+    *rc = STS_OK;
+    if (B == 0 || !given) { have = false; return false; }
+    const std::string required = std::string(what) + (with_n ? ": B >= 0 and n are required" : ": B >= 0 is required");
+    if (B < 0 || (with_n && !n)) { *rc = fail(STS_EINVAL, required); return false; }
+    if (B > max_B) { *rc = fail(STS_EINVAL, over ? over : required); return false; }
+    *total = 0;
+    for (int b = 0; b < B; b++) {
+        const char* why = nullptr;
+        if (!valid(b, &why)) { *rc = fail(STS_EINVAL, why); return false; }
+        if (with_n && (*total += n[b]) > (1 << 24)) { *rc = fail(STS_EINVAL, "batch too large"); return false; }
+    }
+    return true;
+}
+// sts_set_duration_plan: copied as the flattened rate / fixed / target of the whole batch
 int Engine::set_duration_plan(int B, const int32_t* n, const sts_dur_plan* plans) {
     STS_NOT_WHILE_OPEN_UNPLANNED("a duration plan");
-    if (B == 0 || !plans) { have_plan = false; return STS_OK; }
-    if (B < 0 || !n) return fail(STS_EINVAL, "duration plan: B >= 0 and n are required");
-    long total = 0;
-    for (int b = 0; b < B; b++) {
-        const char* why = nullptr;
-        if (!dur_plan_valid(n[b], plans[b].rate, plans[b].fixed, plans[b].target_frames, &why)) return fail(STS_EINVAL, why);
-        total += n[b];
-        if (total > (1 << 24)) return fail(STS_EINVAL, "batch too large");
-    }
-    plan_n.assign(n, n + B);
-    plan_rate.assign((size_t)total, 1.0f); plan_fixed.assign((size_t)total, -1); plan_target.assign((size_t)B, 0);
+    PendingTables& t = pend; long total = 0; int rc;
+    if (!table_begin("duration plan", plans, t.have_plan, B, n, true, INT_MAX, nullptr, &total, &rc, [&](int b, const char** why) {
+            return dur_plan_valid(n[b], plans[b].rate, plans[b].fixed, plans[b].target_frames, why); })) return rc;
+    t.plan_n.assign(n, n + B);
+    t.plan_rate.assign((size_t)total, 1.0f); t.plan_fixed.assign((size_t)total, -1); t.plan_target.assign((size_t)B, 0);
     size_t off = 0;
     for (int b = 0; b < B; b++) {
-        if (plans[b].rate) std::copy(plans[b].rate, plans[b].rate + n[b], plan_rate.begin() + (long)off);
-        if (plans[b].fixed) std::copy(plans[b].fixed, plans[b].fixed + n[b], plan_fixed.begin() + (long)off);
-        plan_target[b] = plans[b].target_frames;
+        if (plans[b].rate) std::copy(plans[b].rate, plans[b].rate + n[b], t.plan_rate.begin() + (long)off);
+        if (plans[b].fixed) std::copy(plans[b].fixed, plans[b].fixed + n[b], t.plan_fixed.begin() + (long)off);
+        t.plan_target[b] = plans[b].target_frames;
         off += (size_t)n[b];
     }
-    have_plan = true;
+    t.have_plan = true;
     return STS_OK;
 }
-// sts_set_speaker_mix: validated and flattened here; an invalid mix changes nothing.  B == 0 or mixes == null drops a pending mix.
+// sts_set_speaker_mix: flattened into the term table the run uploads
 int Engine::set_speaker_mix(int B, const sts_speaker_mix* mixes) {
     STS_NOT_WHILE_OPEN_UNPLANNED("a speaker mix");
-    if (B == 0 || !mixes) { have_mix = false; return STS_OK; }
-    if (B < 0 || B > (1 << 20)) return fail(STS_EINVAL, "speaker mix: B >= 0 is required");
-    for (int b = 0; b < B; b++) {
-        const char* why = nullptr;
-        if (!speaker_mix_valid(model.is_ms == 1 ? model.spk_num : 0, model.gin, mixes[b], &why)) return fail(STS_EINVAL, why);
-    }
-    speaker_mix_flatten(mixes, B, model.gin, mix_words, &mix_K);
-    mix_B = B;
-    have_mix = true;
+    PendingTables& t = pend; long total = 0; int rc;
+    if (!table_begin("speaker mix", mixes, t.have_mix, B, nullptr, false, 1 << 20, nullptr, &total, &rc, [&](int b, const char** why) {
+            return speaker_mix_valid(model.is_ms == 1 ? model.spk_num : 0, model.gin, mixes[b], why); })) return rc;
+    speaker_mix_flatten(mixes, B, model.gin, t.mix_words, &t.mix_K);
+    t.mix_B = B;
+    t.have_mix = true;
     return STS_OK;
 }
-// sts_set_gain_plan: validated and designed here (q per phoneme, h per utterance); an invalid plan changes nothing.  B == 0 or plans == null
-// drops a pending plan.
+// sts_set_gain_plan: designed here (q per phoneme, h per utterance)
 int Engine::set_gain_plan(int B, const int32_t* n, const sts_gain_plan* plans) {
     STS_NOT_WHILE_OPEN_UNPLANNED("a gain plan");
-    if (B == 0 || !plans) { have_gain = false; return STS_OK; }
-    if (B < 0 || !n) return fail(STS_EINVAL, "gain plan: B >= 0 and n are required");
-    long total = 0;
-    for (int b = 0; b < B; b++) {
-        const char* why = nullptr;
-        if (!gain_plan_valid(n[b], plans[b].gain_db, plans[b].ramp_ms, &why)) return fail(STS_EINVAL, why);
-        total += n[b];
-        if (total > (1 << 24)) return fail(STS_EINVAL, "batch too large");
-    }
-    gain_n.assign(n, n + B);
-    gain_words.assign((size_t)total + (size_t)B, 0);
-    gain_has.assign((size_t)B, 0);
+    PendingTables& t = pend; long total = 0; int rc;
+    if (!table_begin("gain plan", plans, t.have_gain, B, n, true, INT_MAX, nullptr, &total, &rc, [&](int b, const char** why) {
+            return gain_plan_valid(n[b], plans[b].gain_db, plans[b].ramp_ms, why); })) return rc;
+    t.gain_n.assign(n, n + B);
+    t.gain_words.assign((size_t)total + (size_t)B, 0);
+    t.gain_has.assign((size_t)B, 0);
     size_t off = 0;
     for (int b = 0; b < B; b++) {
-        gain_has[(size_t)b] = plans[b].gain_db != nullptr;
-        gain_design(plans[b].gain_db, n[b], plans[b].ramp_ms, gain_words.data() + off, gain_words.data() + total + b);
+        t.gain_has[(size_t)b] = plans[b].gain_db != nullptr;
+        gain_design(plans[b].gain_db, n[b], plans[b].ramp_ms, t.gain_words.data() + off, t.gain_words.data() + total + b);
         off += (size_t)n[b];
     }
-    have_gain = true;
+    t.have_gain = true;
     return STS_OK;
 }
-// sts_set_pitch_plan: validated and copied here; an invalid plan changes nothing.  B == 0 or plans == null drops a pending plan.
+// sts_set_pitch_plan: the cents of the whole batch, copied (one grid row per utterance: at most 65535)
 int Engine::set_pitch_plan(int B, const int32_t* n, const sts_pitch_plan* plans) {
     STS_NOT_WHILE_OPEN_UNPLANNED("a pitch plan");      // (a planned open stream lets the setter through; its admission then refuses the plan)
-    if (B == 0 || !plans) { have_pitch = false; return STS_OK; }
-    if (B < 0 || !n) return fail(STS_EINVAL, "pitch plan: B >= 0 and n are required");
-    if (B > 65535) return fail(STS_EINVAL, "pitch plan: at most 65535 utterances");     // (one grid row per utterance)
-    long total = 0;
-    for (int b = 0; b < B; b++) {
-        const char* why = nullptr;
-        if (!pitch_plan_valid(n[b], plans[b].cents, &why)) return fail(STS_EINVAL, why);
-        total += n[b];
-        if (total > (1 << 24)) return fail(STS_EINVAL, "batch too large");
-    }
-    pitch_n.assign(n, n + B);
-    pitch_cents.assign((size_t)total, 0);
-    pitch_has.assign((size_t)B, 0);
+    PendingTables& t = pend; long total = 0; int rc;
+    if (!table_begin("pitch plan", plans, t.have_pitch, B, n, true, 65535, "pitch plan: at most 65535 utterances", &total, &rc, [&](int b, const char** why) {
+            return pitch_plan_valid(n[b], plans[b].cents, why); })) return rc;
+    t.pitch_n.assign(n, n + B);
+    t.pitch_cents.assign((size_t)total, 0);
+    t.pitch_has.assign((size_t)B, 0);
     size_t off = 0;
     for (int b = 0; b < B; b++) {
-        pitch_has[(size_t)b] = plans[b].cents != nullptr;
-        if (plans[b].cents) std::copy(plans[b].cents, plans[b].cents + n[b], pitch_cents.begin() + (long)off);
+        t.pitch_has[(size_t)b] = plans[b].cents != nullptr;
+        if (plans[b].cents) std::copy(plans[b].cents, plans[b].cents + n[b], t.pitch_cents.begin() + (long)off);
         off += (size_t)n[b];
     }
-    have_pitch = true;
+    t.have_pitch = true;
     return STS_OK;
+}
+// The tables of nb utterances on `eng` (engine.hpp): per kind, the members' views in one array, through the kind's setter
+int apply_utt_tables(Engine& eng, int nb, const int32_t* n, const UttTables* const* members, int kinds) {
+    if (kinds < 0) {
+        kinds = 0;
+        for (int i = 0; i < nb; i++)
+            kinds |= (members[i]->has_duration() ? kTabDuration : 0) | (members[i]->has_mix() ? kTabMix : 0) | (members[i]->has_gain() ? kTabGain : 0) |
+                     (members[i]->has_pitch() ? kTabPitch : 0);
+    }
+    int rc = STS_OK;
+    if (kinds & kTabDuration) {
+        std::vector<sts_dur_plan> v((size_t)nb);
+        for (int i = 0; i < nb; i++) v[(size_t)i] = members[i]->view_duration();
+        rc = eng.set_duration_plan(nb, n, v.data());
+    }
+    if (rc == STS_OK && (kinds & kTabMix)) {
+        std::vector<sts_speaker_mix> v((size_t)nb);
+        for (int i = 0; i < nb; i++) v[(size_t)i] = members[i]->view_mix();
+        rc = eng.set_speaker_mix(nb, v.data());
+    }
+    if (rc == STS_OK && (kinds & kTabGain)) {
+        std::vector<sts_gain_plan> v((size_t)nb);
+        for (int i = 0; i < nb; i++) v[(size_t)i] = members[i]->view_gain();
+        rc = eng.set_gain_plan(nb, n, v.data());
+    }
+    if (rc == STS_OK && (kinds & kTabPitch)) {
+        std::vector<sts_pitch_plan> v((size_t)nb);
+        for (int i = 0; i < nb; i++) v[(size_t)i] = members[i]->view_pitch();
+        rc = eng.set_pitch_plan(nb, n, v.data());
+    }
+    if (rc != STS_OK) eng.drop_tables();
+    return rc;
 }
 // sts_get_speaker_embedding: row sid of the device-resident table (one strided copy of gin floats)
 int Engine::speaker_embedding(int sid, float* out, int64_t capacity) const {
@@ -588,54 +622,43 @@ int Engine::run_setup(RunCtx& c) {
     }
     if (Ttot > (1 << 24)) return fail(STS_EINVAL, "batch too large");
     if ((size_t)(M.hidden / 2 + 8 + 5 * (size_t)maxT) * 4 > 150 * 1024) return fail(STS_EINVAL, "utterance too long for the attention kernel");
-    if (have_plan && have_forced) { have_forced = false; have_plan = false; return fail(STS_EINVAL, "a duration plan and forced durations are both pending: both are dropped"); }
-    if (have_forced && (long)forced_dur.size() != Ttot) { have_forced = false; return fail(STS_EINVAL, "forced durations do not match the batch"); }
-    if (have_plan) {
-        bool same = (int)plan_n.size() == B;
-        for (int b = 0; b < B && same; b++) same = plan_n[b] == n[b];
-        if (!same) return fail(STS_EINVAL, "the duration plan was set for another batch (B and every n[b] must match)");
-    }
-    if (have_mix && mix_B != B) return fail(STS_EINVAL, "the speaker mix was set for another batch (B must match)");      // (run() drops it)
-    if (have_gain) {
-        bool same = (int)gain_n.size() == B;
-        for (int b = 0; b < B && same; b++) same = gain_n[b] == n[b];
-        if (!same) return fail(STS_EINVAL, "the gain plan was set for another batch (B and every n[b] must match)");      // (run() drops it)
-    }
+    if (pend.have_plan && pend.have_forced) { pend.have_forced = false; pend.have_plan = false; return fail(STS_EINVAL, "a duration plan and forced durations are both pending: both are dropped"); }
+    if (pend.have_forced && (long)pend.forced_dur.size() != Ttot) { pend.have_forced = false; return fail(STS_EINVAL, "forced durations do not match the batch"); }
+    // (a table these checks refuse: run() drops it)
+    if (pend.have_plan && !table_matches(pend.plan_n, B, n)) return fail(STS_EINVAL, other_batch_message("duration plan"));
+    if (pend.have_mix && pend.mix_B != B) return fail(STS_EINVAL, other_batch_message("speaker mix", false));
+    if (pend.have_gain && !table_matches(pend.gain_n, B, n)) return fail(STS_EINVAL, other_batch_message("gain plan"));
     std::vector<float> eff_rate; std::vector<int32_t> eff_fixed, eff_target;
-    const float* src_rate = plan_rate.data(); const int32_t* src_fixed = plan_fixed.data(); const int32_t* src_target = plan_target.data();
+    const float* src_rate = pend.plan_rate.data(); const int32_t* src_fixed = pend.plan_fixed.data(); const int32_t* src_target = pend.plan_target.data();
     // a pitch plan: whole-utterance calls only; the run's duration plan is the pending one (or the neutral one) with every rate multiplied
     // by the phoneme's ratio -- one fp32 multiply here; the plan kernel is the one of any planned run.  Forced durations are used as given
-    if (have_pitch) {
-        bool same = (int)pitch_n.size() == B;
-        for (int b = 0; b < B && same; b++) same = pitch_n[b] == n[b];
-        if (!same) return fail(STS_EINVAL, "the pitch plan was set for another batch (B and every n[b] must match)");      // (run() drops it)
+    if (pend.have_pitch) {
+        if (!table_matches(pend.pitch_n, B, n)) return fail(STS_EINVAL, other_batch_message("pitch plan"));
         if (c.ss || join_on) return fail(STS_EINVAL, "a pitch plan applies to whole-utterance calls only: streaming and joined runs refuse it");
-        if (!have_forced) {     // (copies: the split-bf16 repeat of this call sets up again from the same pending plan)
-            if (have_plan) { eff_rate = plan_rate; eff_fixed = plan_fixed; eff_target = plan_target; }
+        if (!pend.have_forced) {     // (copies: the split-bf16 repeat of this call sets up again from the same pending plan)
+            if (pend.have_plan) { eff_rate = pend.plan_rate; eff_fixed = pend.plan_fixed; eff_target = pend.plan_target; }
             else { eff_rate.assign((size_t)Ttot, 1.0f); eff_fixed.assign((size_t)Ttot, -1); eff_target.assign((size_t)B, 0); }
             for (int b = 0; b < B; b++)
                 for (int i = 0; i < n[b]; i++) {
                     const size_t k = (size_t)offT[b] + i;
-                    if (pitch_cents[k] == 0) continue;
+                    if (pend.pitch_cents[k] == 0) continue;
                     if (eff_fixed[k] >= 0) return fail(STS_EINVAL, "pitch plan: a phoneme with a fixed length must have 0 cents (a break is silent)");
                     if (eff_target[b] > 0) return fail(STS_EINVAL, "pitch plan: an utterance that is fitted to target_frames admits no non-zero cents");
-                    eff_rate[k] *= pitch_ratio(pitch_cents[k]);
+                    eff_rate[k] *= pitch_ratio(pend.pitch_cents[k]);
                     if (!(eff_rate[k] >= 1.0f / 64.0f && eff_rate[k] <= 64.0f)) return fail(STS_EINVAL, "pitch plan: rate times ratio must stay in [1/64, 64]");
                 }
             src_rate = eff_rate.data(); src_fixed = eff_fixed.data(); src_target = eff_target.data();
         }
     }
-    const bool pitch = c.pitch = have_pitch;
+    const bool pitch = c.pitch = pend.have_pitch;
     c.pitch_rows = 0;
-    if (pitch) for (int b = 0; b < B; b++) c.pitch_rows += pitch_has[(size_t)b] ? n[b] : 0;
-    const bool plan = c.plan = have_plan || (pitch && !have_forced);
-    const bool gain = c.gain = have_gain;
-    const size_t gain_ints = gain ? gain_words.size() : 0;                 // [q Ttot | h B], between the mix and the plan
+    if (pitch) for (int b = 0; b < B; b++) c.pitch_rows += pend.pitch_has[(size_t)b] ? n[b] : 0;
+    const bool plan = c.plan = pend.have_plan || (pitch && !pend.have_forced);
+    const bool gain = c.gain = pend.have_gain;
     const bool join = c.join = join_on;
-    const size_t join_ints = join ? (size_t)B : 0;                         // silence frames in front of each sentence, between the gain plan and the duration plan
-    const bool mix = c.mix = have_mix && M.is_ms == 1;       // (a single-speaker model accepts empty entries only: nothing to blend)
-    const size_t mix_ints = mix ? mix_words.size() : 0;                    // the term table, between the ids and the plan
-    const size_t plan_ints = plan ? 2 * (size_t)Ttot + (size_t)B : 0;      // [rate Ttot | fixed Ttot | target B] behind the ids
+    const bool mix = c.mix = pend.have_mix && M.is_ms == 1;       // (a single-speaker model accepts empty entries only: nothing to blend)
+    // the staging block (utt_tables.hpp): where every section stands, on the device and in pinned memory alike
+    const StageLayout L((size_t)B, (size_t)Ttot, mix ? pend.mix_words.size() : 0, gain ? pend.gain_words.size() : 0, join, plan, pend.have_forced);
     // sampling noise of every utterance: the caller's per-utterance table (sts_pool, sts_multi) or the engine's setting with seed + b
     c.nz.resize(B);
     for (int b = 0; b < B; b++) {
@@ -655,23 +678,19 @@ int Engine::run_setup(RunCtx& c) {
     BufT& bt = c.bt;
     auto layoutT = [&](Arena& A) {
         A.used = 0;
-        // one device block mirroring the pinned staging block [geometry ints | length scales | noise scales, seeds | ids | forced
-        // durations]: a single host-to-device copy per run
-        // (a run with a duration plan: the plan's arrays ride in the same copy, between the ids and `forced`, which the plan kernel then writes;
-        // a run with a speaker mix: its term table too, right behind the ids; a run with a gain plan: its q / h table behind that; a joined run: its silence table behind that)
-        bt.meta_i = A.get<int>((size_t)9 * B + 8 + 5 * (size_t)B + 2 * (size_t)Ttot + mix_ints + gain_ints + join_ints + plan_ints);
-        bt.ls = (float*)(bt.meta_i + ((size_t)9 * B + 8));
-        bt.ns = bt.ls + B; bt.nsw = bt.ns + B;
-        bt.seed = (uint64_t*)(bt.nsw + B);      // (9B + 8 + 3B ints from a 256-byte boundary: 8-byte aligned)
-        bt.ids = (int*)(bt.seed + B);
-        bt.mix = mix ? bt.ids + Ttot : nullptr;
-        bt.gain_q = gain ? bt.ids + Ttot + mix_ints : nullptr;
-        bt.gain_h = gain ? bt.ids + 2 * Ttot + mix_ints : nullptr;
-        bt.join_sil = join ? bt.ids + Ttot + mix_ints + gain_ints : nullptr;
-        bt.plan_rate = plan ? (float*)(bt.ids + Ttot + mix_ints + gain_ints + join_ints) : nullptr;
-        bt.plan_fixed = plan ? bt.ids + 2 * Ttot + mix_ints + gain_ints + join_ints : nullptr;
-        bt.plan_target = plan ? bt.ids + 3 * Ttot + mix_ints + gain_ints + join_ints : nullptr;
-        bt.forced = bt.ids + Ttot + mix_ints + gain_ints + join_ints + plan_ints;
+        // one device block mirroring the pinned staging block: a single host-to-device copy per run
+        int* const d = bt.meta_i = A.get<int>(L.words);
+        bt.ls = (float*)(d + L.ls); bt.ns = (float*)(d + L.ns); bt.nsw = (float*)(d + L.nsw);
+        bt.seed = (uint64_t*)(d + L.seed);
+        bt.ids = d + L.ids;
+        bt.mix = mix ? d + L.mix : nullptr;
+        bt.gain_q = gain ? d + L.gain_q : nullptr;
+        bt.gain_h = gain ? d + L.gain_h : nullptr;
+        bt.join_sil = join ? d + L.join_sil : nullptr;
+        bt.plan_rate = plan ? (float*)(d + L.plan_rate) : nullptr;
+        bt.plan_fixed = plan ? d + L.plan_fixed : nullptr;
+        bt.plan_target = plan ? d + L.plan_target : nullptr;
+        bt.forced = d + L.forced;
         bt.x = A.get<float>((size_t)H * Ttot); bt.qkv = A.get<float>((size_t)3 * H * Ttot);
         bt.att = A.get<float>((size_t)H * Ttot); bt.y = A.get<float>((size_t)H * Ttot * ffn2_slices);
         bt.x1 = A.get<float>((size_t)H * Ttot); bt.ffh = A.get<float>((size_t)FF * Ttot);
@@ -699,8 +718,7 @@ int Engine::run_setup(RunCtx& c) {
     poison_arena(arenaT_);
 
     // ---------------- one H2D: geometry + ids (+ forced durations)
-    const size_t meta_ints = c.meta_ints = (size_t)9 * B + 8;
-    const size_t up_bytes = c.up_bytes = (meta_ints + 5 * (size_t)B + 2 * (size_t)Ttot + mix_ints + gain_ints + join_ints + plan_ints) * 4 + 1024;
+    const size_t up_bytes = c.up_bytes = L.words * 4 + 1024;
     const size_t pitch_stage = pitch ? ((size_t)6 * B + 5 * (size_t)c.pitch_rows) * 8 + (size_t)3 * B * 4 + 16 : 0;     // (pitch_geometry)
     if (!ensure_pinned(up_bytes + ((size_t)Ttot + B) * 4 + pitch_stage)) return fail(STS_EDEVICE, "pinned host allocation failed");
     int* pm = c.pm = (int*)pinned_;
@@ -711,23 +729,19 @@ int Engine::run_setup(RunCtx& c) {
     if (B == 1) { int* pw0 = pm + 5 * B + 2; c.p_offF[0] = 0; c.p_lenF[0] = 0; pw0[0] = 0; pw0[1] = 0; pw0[2] = 0; }   // (a launch-ahead run: the durations kernel fills the two lengths on the device)
     int* d_offT = c.d_offT = bt.meta_i, *d_lenT = c.d_lenT = bt.meta_i + B, *d_one = c.d_one = bt.meta_i + 5 * B;
     c.d_sid = bt.meta_i + 2 * B; c.d_offF = bt.meta_i + 3 * B; c.d_lenF = bt.meta_i + 4 * B; c.d_win = bt.meta_i + 5 * B + 2;
-    float* p_ls = (float*)(pm + meta_ints);
-    for (int b = 0; b < B; b++) p_ls[b] = ls ? ls[b] : 1.0f;
-    float* p_ns = p_ls + B; float* p_nsw = p_ns + B; uint64_t* p_seed = (uint64_t*)(p_nsw + B);
-    for (int b = 0; b < B; b++) { p_ns[b] = c.nz[b].ns; p_nsw[b] = c.nz[b].nsw; p_seed[b] = c.nz[b].seed; }
-    int* p_ids = (int*)(p_seed + B);
-    for (int b = 0; b < B; b++) memcpy(p_ids + offT[b], ids[b], sizeof(int) * n[b]);
-    if (mix) memcpy(p_ids + Ttot, mix_words.data(), sizeof(int) * mix_ints);
-    if (gain) memcpy(p_ids + Ttot + mix_ints, gain_words.data(), sizeof(int) * gain_ints);
-    if (join) memcpy(p_ids + Ttot + mix_ints + gain_ints, join_sil.data(), sizeof(int) * join_ints);
-    int* p_forced = p_ids + Ttot + mix_ints + gain_ints + join_ints;
-    if (have_forced) memcpy(p_forced, forced_dur.data(), sizeof(int) * Ttot);
-    if (plan) {          // (never together with forced durations: the plan's arrays take their place in the copy)
-        memcpy(p_ids + Ttot + mix_ints + gain_ints + join_ints, src_rate, sizeof(float) * Ttot);
-        memcpy(p_ids + 2 * Ttot + mix_ints + gain_ints + join_ints, src_fixed, sizeof(int) * Ttot);
-        memcpy(p_ids + 3 * Ttot + mix_ints + gain_ints + join_ints, src_target, sizeof(int) * B);
+    float* p_ls = (float*)(pm + L.ls); float* p_ns = (float*)(pm + L.ns); float* p_nsw = (float*)(pm + L.nsw); uint64_t* p_seed = (uint64_t*)(pm + L.seed);
+    for (int b = 0; b < B; b++) { p_ls[b] = ls ? ls[b] : 1.0f; p_ns[b] = c.nz[b].ns; p_nsw[b] = c.nz[b].nsw; p_seed[b] = c.nz[b].seed; }
+    for (int b = 0; b < B; b++) memcpy(pm + L.ids + offT[b], ids[b], sizeof(int) * n[b]);
+    if (mix) memcpy(pm + L.mix, pend.mix_words.data(), sizeof(int) * pend.mix_words.size());
+    if (gain) memcpy(pm + L.gain_q, pend.gain_words.data(), sizeof(int) * pend.gain_words.size());
+    if (join) memcpy(pm + L.join_sil, join_sil.data(), sizeof(int) * B);
+    if (pend.have_forced) memcpy(pm + L.forced, pend.forced_dur.data(), sizeof(int) * Ttot);
+    if (plan) {
+        memcpy(pm + L.plan_rate, src_rate, sizeof(float) * Ttot);
+        memcpy(pm + L.plan_fixed, src_fixed, sizeof(int) * Ttot);
+        memcpy(pm + L.plan_target, src_target, sizeof(int) * B);
     }
-    HIPCK(hipMemcpyAsync(bt.meta_i, pm, (meta_ints + 5 * (size_t)B + (size_t)Ttot * (have_forced ? 2 : 1) + mix_ints + gain_ints + join_ints + plan_ints) * 4, hipMemcpyHostToDevice, stream));
+    HIPCK(hipMemcpyAsync(bt.meta_i, pm, L.copy_words * 4, hipMemcpyHostToDevice, stream));
     if (B > 1) HIPCK(hipEventRecord(ev_setup_, stream));     // (run_durations, batches launched from the memo: the host rewrites part of this block)
 
     // single-segment views travel by value (kernels.hpp SegView): no segment-table load in the kernels of a one-utterance call
@@ -851,7 +865,7 @@ int Engine::run_durations(RunCtx& c) {
 
     // ---------------- speaker conditioning vectors (all 1x1 convs on g; SynthesizerTrn.cpp:363-372)
     stage_begin(1);
-    if (ms && c.mix) speaker_blend(M.emb_g, M.spk_num, M.gin, d_sid, B, speaker_mix_tab(bt.mix, B, mix_K), bt.g, stream);     // (in place of the gather)
+    if (ms && c.mix) speaker_blend(M.emb_g, M.spk_num, M.gin, d_sid, B, speaker_mix_tab(bt.mix, B, pend.mix_K), bt.g, stream);     // (in place of the gather)
     else if (ms) gather_speaker(M.emb_g, M.spk_num, M.gin, d_sid, B, bt.g, stream);
 
     // ---------------- duration predictor
@@ -947,7 +961,7 @@ int Engine::run_durations(RunCtx& c) {
         c.req_keys[b] = h | 1ull;
     }
     c.predF.clear();
-    if (launch_ahead && !ss && !have_forced && !c.plan && !c.mix && !c.gain && !c.pitch && !c.join && !record_taps && mapped) {     // (a planned or mixed run's frame count is not a function of the memo's key; a run with a gain plan and a joined run stay off the memo by contract)
+    if (launch_ahead && !ss && !pend.have_forced && !c.plan && !c.mix && !c.gain && !c.pitch && !c.join && !record_taps && mapped) {     // (a planned or mixed run's frame count is not a function of the memo's key; a run with a gain plan and a joined run stay off the memo by contract)
         c.predF.resize(B);
         for (int b = 0; b < B; b++) {
             const auto it = seen_tf_.find(c.req_keys[b]);
@@ -967,11 +981,11 @@ int Engine::run_durations(RunCtx& c) {
         pa.forced = bt.forced; pa.dur_w = bt.dur_w; pa.rem = bt.plan_rem; pa.seg = lvT.seg;
         duration_plan(pa, B, stream);
     }
-    durations(r_final, M.dur_type == 0 ? 1 : 0, M.ea_m, M.ea_logs, bt.ls, (have_forced || c.plan) ? bt.forced : nullptr, bt.dlogw,
+    durations(r_final, M.dur_type == 0 ? 1 : 0, M.ea_m, M.ea_logs, bt.ls, (pend.have_forced || c.plan) ? bt.forced : nullptr, bt.dlogw,
               bt.dur, bt.cum, bt.frames, lvT.seg, B, stream, mapped ? hmap_dev_ : nullptr, Ttot, seq_, arrive_,
               c.ahead ? c.d_lenF : nullptr, c.ahead ? c.d_win + 2 : nullptr, (int)cap);
-    c.forced = have_forced || c.plan || c.mix || c.gain || c.pitch || c.join;      // (none of these runs feeds the memo: its key hashes sid, not the mix)
-    have_forced = false;
+    c.forced = pend.have_forced || c.plan || c.mix || c.gain || c.pitch || c.join;      // (none of these runs feeds the memo: its key hashes sid, not the mix)
+    pend.have_forced = false;
     mark(2);
     sync_wait_ms_ = 0;
     if (c.ahead) {
@@ -1111,8 +1125,8 @@ int Engine::pitch_geometry(RunCtx& c) {
     for (int b = 0; b < B; b++) {
         const size_t t = (size_t)c.offT[b];
         dur[b] = durations_h.data() + t;
-        step[b] = pitch_has[(size_t)b] ? steps.data() + t : nullptr;
-        if (step[b]) for (int i = 0; i < c.lenT[b]; i++) steps[t + i] = pitch_step(pitch_cents[t + i]);
+        step[b] = pend.pitch_has[(size_t)b] ? steps.data() + t : nullptr;
+        if (step[b]) for (int i = 0; i < c.lenT[b]; i++) steps[t + i] = pitch_step(pend.pitch_cents[t + i]);
         xoff[b] = (long long)c.p_offF[b] * hop;
     }
     PitchTables tab;
@@ -1477,10 +1491,7 @@ static constexpr int kRetrySplitBf16 = 1;     // run_once: nothing was handed ou
 int Engine::run(int B, const int32_t* const* ids, const int32_t* n, const int32_t* sid, const float* ls, const StreamSpec* ss) {
     STS_NOT_WHILE_OPEN("a run");
     const int rc = run_any_math(B, ids, n, sid, ls, ss);
-    have_plan = false;          // a duration plan is for one call, whatever its outcome; the repeat inside the call above applied it again
-    have_mix = false;           // and so is a speaker mix
-    have_gain = false;          // and a gain plan
-    have_pitch = false;         // and a pitch plan
+    pend.drop_call_tables();         // a table is for one call, whatever its outcome; the repeat inside the call above applied it again
     return rc;
 }
 // the overflow word of conv math 3 (host-mapped) and its device address, allocated by the first call that needs it
@@ -1506,7 +1517,7 @@ int Engine::run_any_math(int B, const int32_t* const* ids, const int32_t* n, con
     }
     { const int rco = ensure_overflow_word(); if (rco != STS_OK) return rco; }
     *(volatile unsigned*)ovf_host_ = 0u;
-    const bool forced = have_forced;          // (a run consumes the forced durations: the repeat needs them again)
+    KeepForced keep_forced(pend);
     const long before = h2_fallbacks;
     int rc = run_once(B, ids, n, sid, ls, ss);
     if ((rc == STS_OK && !ss && *(volatile unsigned*)ovf_host_ != 0u) || rc == kRetrySplitBf16) {
@@ -1515,7 +1526,7 @@ int Engine::run_any_math(int B, const int32_t* const* ids, const int32_t* n, con
                                    "(same result, about twice the latency; sts_profile.conv_math_fallbacks counts these; STS_CONV_MATH=bf16x3 avoids them)\n");
         h2_fallbacks++;
         conv_math = 0;
-        have_forced = forced;
+        keep_forced.again();
         rc = run_once(B, ids, n, sid, ls, ss);
     }
     conv_math = 3;
@@ -2000,7 +2011,7 @@ int Engine::stream_open(int chunk_frames, int max_live, long long capacity_frame
     if (loud_mode == 2 || (loud_mode != 0 && !loud_streaming)) return fail(STS_EINVAL, "an open stream is not available while loudness measurement or normalization is on: its state is carried per utterance in the frame arena");
     if (record_taps) return fail(STS_EINVAL, "an open stream is not available while taps are recorded");
     if (refuse_pitch("an open stream")) return STS_EINVAL;
-    if (have_plan || have_mix || have_gain || have_forced)
+    if (pend.have_plan || pend.have_mix || pend.have_gain || pend.have_forced)
         return fail(STS_EINVAL, "an open stream is not available while a duration plan, a speaker mix, a gain plan or forced durations are pending: their tables are per call");
     HIPCK(hipSetDevice(device));
     LimiterDesign d{};
@@ -2111,7 +2122,7 @@ int Engine::stream_admit_once(int B, const int32_t* const* ids, const int32_t* n
     std::vector<long> F((size_t)B); std::vector<int> sidv((size_t)B), slots((size_t)B, -1), nph((size_t)B, 0);
     for (int b = 0; b < B; b++) { F[(size_t)b] = c.p_lenF[b]; sidv[(size_t)b] = c.p_sid[b]; }
     // (a planned stream: an utterance whose gain plan came with gain_db takes n[b] columns of the phoneme pool; room is decided over all three)
-    if (c.gain) for (int b = 0; b < B; b++) nph[(size_t)b] = gain_has[(size_t)b] ? n[b] : 0;
+    if (c.gain) for (int b = 0; b < B; b++) nph[(size_t)b] = pend.gain_has[(size_t)b] ? n[b] : 0;
     if (!L.admit(B, F.data(), sidv.data(), nph.data(), slots.data())) {    // no room now: the front work is lost, nothing has changed
         HIPCK(hipStreamSynchronize(stream));
         *admitted = 0;
@@ -2136,7 +2147,7 @@ int Engine::stream_admit_once(int B, const int32_t* const* ids, const int32_t* n
             const LiveSlot* sl = s >= 0 ? &L.slots[(size_t)s] : nullptr;
             const bool g = sl && sl->has_gain;
             t5[5 * b] = s; t5[5 * b + 1] = c.offT[(size_t)b]; t5[5 * b + 2] = g ? sl->pn : 0; t5[5 * b + 3] = g ? (int)sl->poff : 0;
-            t5[5 * b + 4] = g ? gain_words[(size_t)c.Ttot + (size_t)b] : 0;
+            t5[5 * b + 4] = g ? pend.gain_words[(size_t)c.Ttot + (size_t)b] : 0;
             if (g) max_n = std::max(max_n, sl->pn);
         }
         tab_bytes = adopt_tables_tab_off(B) + adopt_tables_tab_bytes(B);
@@ -2184,12 +2195,12 @@ int Engine::stream_admit(int B, const int32_t* const* ids, const int32_t* n, con
     if (nz) for (int b = 0; b < B; b++) noise_utt.push_back(Noise{nz[b].noise_scale, nz[b].noise_scale_w, nz[b].seed});
     const int math = conv_math;
     if (math == 3 && L.form0) conv_math = 0;
-    const bool forced = have_forced;                           // (the duration stage consumes forced durations: the repeat needs them again)
+    KeepForced keep_forced(pend);
     int rc = stream_admit_once(B, ids, n, sid, ls, slot_out, n_samples_out, admitted);
     if (rc == kRetrySplitBf16) {                               // this admission alone: nothing of the newcomers has been delivered
         h2_fallbacks++;
         conv_math = 0;
-        have_forced = forced;
+        keep_forced.again();
         rc = stream_admit_once(B, ids, n, sid, ls, slot_out, n_samples_out, admitted);
     }
     conv_math = math;
@@ -2268,7 +2279,7 @@ int Engine::para_open(int chunk_frames, int max_resident, long long capacity_fra
     if (loud_mode != 0) return fail(STS_EINVAL, "an open paragraph is not available while loudness measurement or normalization is on: its state is carried in the frame arena");
     if (record_taps) return fail(STS_EINVAL, "an open paragraph is not available while taps are recorded");
     if (refuse_pitch("an open paragraph")) return STS_EINVAL;
-    if (have_plan || have_mix || have_gain || have_forced)
+    if (pend.have_plan || pend.have_mix || pend.have_gain || pend.have_forced)
         return fail(STS_EINVAL, "an open paragraph is not available while a duration plan, a speaker mix, a gain plan or forced durations are pending: their tables are per call");
     const sts_join j{nullptr, lead_frames, 0, fade_ms};
     const char* why = nullptr;

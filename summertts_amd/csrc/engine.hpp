@@ -112,6 +112,38 @@ inline bool loudness_args_valid(int mode, float target, float peak) {
 void limiter_stats_decode(const unsigned* raw, int B, sts_limiter_stats* out);
 
 struct Tap { std::vector<float> data; int channels = 0; long length = 0; };
+// What the setters left for the NEXT call only, whatever its outcome, each kind as the run uploads it (Engine::run_setup):
+struct PendingTables {
+    // forced durations (sts_set_forced_durations): consumed by the duration stage of the run that uses them
+    std::vector<int32_t> forced_dur; bool have_forced = false;
+    // duration plan (duration_plan.hip), materialised for the whole batch: an utterance without a plan has rate 1 (w * 1.0f == w bit for
+    // bit), fixed -1, target 0.  plan_n: the phoneme counts the next call must have
+    std::vector<int32_t> plan_n, plan_fixed, plan_target; std::vector<float> plan_rate; bool have_plan = false;
+    // speaker mix (misc_kernels.hip speaker_blend): the flattened term table (kernels.hpp SpeakerMixTab) for mix_B utterances with mix_K
+    // terms in all
+    std::vector<int32_t> mix_words; int mix_B = 0, mix_K = 0; bool have_mix = false;
+    // gain plan (gain_plan.hip): q per phoneme of the whole batch (an utterance without a plan: 2^20 throughout, env == 1.0f), then h per
+    // utterance.  gain_has[b]: entry b came with gain_db -- a planned open stream gives only those utterances columns of its phoneme pool
+    std::vector<int32_t> gain_n, gain_words; std::vector<char> gain_has; bool have_gain = false;
+    // pitch plan (pitch_plan.hip): the cents of the whole batch (0 for an utterance without a plan); pitch_has[b]: entry b came with cents
+    std::vector<int32_t> pitch_n, pitch_cents; std::vector<char> pitch_has; bool have_pitch = false;
+    void drop_call_tables() { have_plan = have_mix = have_gain = have_pitch = false; }      // (forced durations stay: their run consumes them)
+    void drop_all() { drop_call_tables(); have_forced = false; }
+};
+// The split-bf16 repeat of a run sets up again from the same pending tables; the forced durations, which the first attempt's duration
+// stage consumed, are pending again behind again()
+struct KeepForced {
+    PendingTables& t; const bool had;
+    explicit KeepForced(PendingTables& tables) : t(tables), had(tables.have_forced) {}
+    void again() { t.have_forced = had; }
+};
+class Engine;
+// The tables of nb utterances (phoneme counts n, members[i] the tables of utterance i) on `eng` for its next run or admission, in the
+// order duration plan, speaker mix, gain plan, pitch plan.  kinds < 0: a kind is set when a member carries it; otherwise the kinds of
+// the mask (kTab*) are set.  A member without a kind that is set gets its empty entry.  On a failure nothing stays pending and the
+// error is eng.error()
+enum : int { kTabDuration = 1, kTabMix = 2, kTabGain = 4, kTabPitch = 8 };
+int apply_utt_tables(Engine& eng, int nb, const int32_t* n, const UttTables* const* members, int kinds = -1);
 constexpr int kNativeRate = 16000;   // every model of the reference produces 16 kHz (test/main.cpp:13,16)
 
 class Engine {
@@ -169,22 +201,25 @@ public:
     int lim_mode = 0; float lim_gain_db = 0.f, lim_ceiling = -1.f, lim_ms = 5.f;
     std::vector<sts_limiter_stats> lim_res;
     int set_limiter(int mode, float gain_db, float ceiling_dbfs, float lookahead_ms);
-    std::vector<int32_t> forced_dur; bool have_forced = false;
-    // duration plan (sts_set_duration_plan, duration_plan.hip): for the NEXT call only, whatever its outcome -- run() drops it when the call
-    // returns, so the conv-math-3 repeat of a call applies it again.  Materialised for the whole batch: an utterance without a plan has
-    // rate 1 (w * 1.0f == w bit for bit), fixed -1, target 0.  plan_n: the phoneme counts the next call must have.
-    std::vector<int32_t> plan_n, plan_fixed, plan_target; std::vector<float> plan_rate; bool have_plan = false;
+    // the tables of the NEXT call only, whatever its outcome (sts_set_forced_durations, sts_set_duration_plan, sts_set_speaker_mix,
+    // sts_set_gain_plan, sts_set_pitch_plan): run() drops them when the call returns, so the conv-math-3 repeat of a call applies them
+    // again.  A setter validates and materialises here; an invalid table changes nothing; B == 0 or null drops a pending one.  A pitch
+    // plan is for whole-utterance calls only: the run multiplies its duration plan's rates by the ratios (run_setup), lays the warp out
+    // on the host when the durations arrive (pitch_geometry) and launches the warp kernel behind the gain kernel (decode_end)
+    PendingTables pend;
+    void set_forced_durations(const int32_t* dur, int64_t count);
     int set_duration_plan(int B, const int32_t* n, const sts_dur_plan* plans);
-    // speaker mix (sts_set_speaker_mix, misc_kernels.hip speaker_blend): for the NEXT call only, whatever its outcome, like the plan.  Kept as
-    // the flattened term table the run uploads (kernels.hpp SpeakerMixTab) for mix_B utterances with mix_K terms in all
-    std::vector<int32_t> mix_words; int mix_B = 0, mix_K = 0; bool have_mix = false;
     int set_speaker_mix(int B, const sts_speaker_mix* mixes);
-    int speaker_embedding(int sid, float* out, int64_t capacity) const;
-    // gain plan (sts_set_gain_plan, gain_plan.hip): for the NEXT call only, whatever its outcome, like the duration plan.  Kept as the table
-    // the run uploads: q per phoneme of the whole batch (an utterance without a plan: 2^20 throughout, env == 1.0f), then h per utterance.
-    // gain_n: the phoneme counts the next call must have
-    std::vector<int32_t> gain_n, gain_words; bool have_gain = false;
     int set_gain_plan(int B, const int32_t* n, const sts_gain_plan* plans);
+    int set_pitch_plan(int B, const int32_t* n, const sts_pitch_plan* plans);
+    void drop_tables() { pend.drop_all(); }
+    // a pending pitch plan and a call form that cannot apply one: the plan is dropped and the call refused
+    bool refuse_pitch(const char* what) {
+        if (!pend.have_pitch) return false;
+        pend.have_pitch = false; err_ = std::string("a pitch plan is pending: ") + what + " cannot apply one (the plan is dropped)";
+        return true;
+    }
+    int speaker_embedding(int sid, float* out, int64_t capacity) const;
     // paragraph join (sts_infer_ids_joined, join.hip): run_joined() runs the B sentences as run() would and joins their native float waves
     // into one signal in front of the resampler, loudness, the limiter and the cast.  join_on: the run in progress joins; join_sil: silence
     // frames in front of each sentence (kernels.hpp join_silence), join_total_sil: lead + every gap + trail; join_h: the fade in samples.
@@ -281,6 +316,9 @@ private:
     int para_append_once(int B, const int32_t* const* ids, const int32_t* n, const int32_t* sid, const float* ls, const long long* gap,
                          int32_t* frames_out, int64_t* start_out, int32_t* appended);
     int ensure_overflow_word();
+    template <typename Valid>       // what the four table setters share (engine.hip)
+    bool table_begin(const char* what, bool given, bool& have, int B, const int32_t* n, bool with_n, int max_B, const char* over, long* total, int* rc,
+                     Valid&& valid);
     void tap(const char* name, const float* d, int channels, long ld, long length);
     void stage_begin(int s);
     void mark(int i);
@@ -308,7 +346,6 @@ private:
     double bytes_[4] = {0, 0, 0, 0};
     double bytes_w_[4] = {0, 0, 0, 0};       // the weight share of bytes_ (does not scale with the positions)
     double mfma_flops_ = 0, mfma_exec_ = 0, bf16_exec_ = 0, sync_wait_ms_ = 0; int mfma_launches_ = 0; bool in_mfma_region_ = false;
-    // (the members of the equaliser sit behind everything else: the layout of the members above stays what it was)
     EqTable* d_eq_ = nullptr; int eq_tab_rate_ = 0; bool eq_dirty_ = true;        // the EQ's tables on the device, the rate they were built for
     int eq_prepare();                                                             // a run with an EQ: the bands against the current rate, the tables
     float* d_pitch_table_ = nullptr;   // the prototype on the device, uploaded by the first run with a pitch plan
@@ -340,16 +377,12 @@ public:
     // conditioning vector, a gain-planned slot's cum / q columns and {off, n, h}) moves into pools of the stream's own at admission
     // (adopt_tables, one launch next to adopt_z), and a step reads them by slot.  0: exactly the stream above.
     int stream_open(int chunk_frames, int max_live, long long capacity_frames, long long capacity_phonemes = 0);
-    void drop_tables() { have_plan = have_mix = have_gain = have_forced = have_pitch = false; }
     int stream_admit(int B, const int32_t* const* ids, const int32_t* n, const int32_t* sid, const float* ls, const sts_stream_noise* noise,
                      int32_t* slot_out, int32_t* n_samples_out, int32_t* admitted);
     int stream_step(int (*cb)(void*, int32_t, const int16_t*, int32_t, int32_t), void* user, int32_t* live_after);
     int stream_close();
     bool stream_is_open() const { return live_ != nullptr || para_ != nullptr; }      // "open": an open stream or an open paragraph
     LiveStream* live_ = nullptr;       // null: no stream is open
-    // (next to the stream, so that the members in front keep their places) gain_has[b]: entry b of the pending gain plan came with gain_db
-    // -- a planned open stream gives only those utterances columns of its phoneme pool
-    std::vector<char> gain_has;
     // an open paragraph (sts_para_open .. sts_para_close; para_stream.hpp, DESIGN.md 9i "Open paragraphs"): ONE joined stream per engine
     // whose sentences are appended between its steps.  para_open fixes what stream_open fixes and the join's lead and fade, and allocates
     // the latent pool; para_append runs front and flow of B new sentences as the packed batch a joined call of those B would (global
@@ -366,21 +399,9 @@ public:
     // a measuring open stream: the slots retired by the most recent step that measured, ascending -- loud_res holds their results in
     // this order (sts_stream_get_loudness)
     std::vector<int32_t> loud_slots;
-    // pitch plan (sts_set_pitch_plan, pitch_plan.hip): for the NEXT call only, whatever its outcome, like the gain plan.  pitch_cents: the
-    // cents of the whole batch (0 for an utterance without a plan), pitch_has[b]: entry b came with cents, pitch_n: the phoneme counts the
-    // next call must have.  The run multiplies its duration plan's rates by the ratios (run_setup), lays the warp out on the host when the
-    // durations arrive (pitch_geometry) and launches the warp kernel behind the gain kernel (decode_end).  Whole-utterance calls only.
-    std::vector<int32_t> pitch_n, pitch_cents; std::vector<char> pitch_has; bool have_pitch = false;
-    int set_pitch_plan(int B, const int32_t* n, const sts_pitch_plan* plans);
     // first output of every phoneme of the last run in native samples of the WARPED signal, packed like durations_h (empty: the last run
     // had no pitch plan): what sts_get_phoneme_offsets converts instead of frames * hop
     std::vector<int64_t> last_pitch_start;
-    // a pending pitch plan and a call form that cannot apply one: the plan is dropped and the call refused
-    bool refuse_pitch(const char* what) {
-        if (!have_pitch) return false;
-        have_pitch = false; err_ = std::string("a pitch plan is pending: ") + what + " cannot apply one (the plan is dropped)";
-        return true;
-    }
     // loudness in a stream (sts_set_loudness_streaming; loudness.hip's stream mode, loud_stream.hpp): off, a stream under mode 1 or 2 is
     // refused; on, mode 1 measures what each step delivers from a state carried per utterance in the frame arena (mode 2 stays refused)
     bool loud_streaming = false;

@@ -12,6 +12,7 @@
 
 #include "../../include/summertts_hip.h"
 #include "pitch_layout.hpp"
+#include "utt_tables.hpp"
 
 namespace sts {
 
@@ -319,22 +320,8 @@ void gather_speaker(const float* emb_g, int spk_num, int gin, const int* sid, in
 // Speaker blending (the definition is in include/summertts_hip.h, sts_set_speaker_mix)
 constexpr int kMixMaxTerms = 16;
 constexpr float kMixMaxWeight = 16.f;
-inline bool speaker_mix_empty(const sts_speaker_mix& m) { return m.k == 0 && !m.vector; }
 // one entry against a table of spk_num rows of gin floats (spk_num 0: a single-speaker model, which takes empty entries only)
 bool speaker_mix_valid(int spk_num, int gin, const sts_speaker_mix& m, const char** why);
-// host copy of one entry (requests of a pool, utterances of a multi-device batch)
-struct SpeakerMixCopy {
-    std::vector<int32_t> sid; std::vector<float> weight, vector; float vector_weight = 0.f; bool has_vector = false;
-    void assign(const sts_speaker_mix& m, int gin) {
-        sid.assign(m.sid, m.sid + (m.k > 0 ? m.k : 0)); weight.assign(m.weight, m.weight + (m.k > 0 ? m.k : 0));
-        has_vector = m.vector != nullptr; vector_weight = has_vector ? m.vector_weight : 0.f;
-        if (has_vector) vector.assign(m.vector, m.vector + gin); else vector.clear();
-    }
-    sts_speaker_mix view() const {
-        return sts_speaker_mix{(int32_t)sid.size(), sid.empty() ? nullptr : sid.data(), weight.empty() ? nullptr : weight.data(),
-                               has_vector ? vector.data() : nullptr, vector_weight};
-    }
-};
 // The flattened term table of B entries, 32-bit words: [off B + 1 | vidx B | vw B | tsid K | tw K | vec V * gin]: entry b owns the terms
 // off[b] .. off[b + 1) and, when vidx[b] >= 0, row vidx[b] of vec with the weight vw[b] (K terms and V vectors in all)
 struct SpeakerMixTab { const int* off; const int* vidx; const float* vw; const int* tsid; const float* tw; const float* vec; };

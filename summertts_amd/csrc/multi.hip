@@ -97,16 +97,12 @@ struct sts_multi {
     int64_t epoch = 0; int pending = 0; bool stop = false;
     int32_t B = 0; const int32_t* const* ids = nullptr; const int32_t* n = nullptr; const int32_t* sid = nullptr; const float* ls = nullptr;
     Engine::Noise noise;                    // sts_multi_set_noise: utterance b of a batch samples with noise.seed + b (its index in the caller's batch)
-    // sts_multi_set_duration_plan: the next batch's plans, per utterance of the caller's batch (rate / fixed: n entries or empty = absent)
-    struct UttPlan { std::vector<float> rate; std::vector<int32_t> fixed; int32_t target = 0; };
-    std::vector<UttPlan> plan; std::vector<int32_t> plan_n; bool have_plan = false;
-    // sts_multi_set_speaker_mix: the next batch's mixes, per utterance of the caller's batch
-    std::vector<SpeakerMixCopy> mix; bool have_mix = false;
-    // sts_multi_set_gain_plan: the next batch's gain plans, per utterance of the caller's batch (gain_db: n entries or empty = absent)
-    struct UttGain { std::vector<float> gain_db; float ramp_ms = 0.f; };
-    std::vector<UttGain> gain; std::vector<int32_t> gain_n; bool have_gain = false;
-    // sts_multi_set_pitch_plan: the next batch's pitch plans, per utterance of the caller's batch (cents: n entries or empty = absent)
-    std::vector<std::vector<int32_t>> pitch; std::vector<int32_t> pitch_n; bool have_pitch = false;
+    // sts_multi_set_duration_plan / _speaker_mix / _gain_plan / _pitch_plan: the next batch's tables.  kinds: which kinds are pending
+    // (kTab*); utt[b]: utterance b of the caller's batch, its entry of a pending kind; plan_n / gain_n / pitch_n and mix_B: the batch
+    // each kind was set for
+    std::vector<UttTables> utt; int kinds = 0;
+    std::vector<int32_t> plan_n, gain_n, pitch_n; int mix_B = 0;
+    void drop_tables() { kinds = 0; }
     std::vector<Shard> shards;
     // RCCL gather state (gather_mode == 1)
     int gather_mode = 0;
@@ -297,34 +293,12 @@ struct sts_multi {
                     eng.noise_utt[i] = Engine::Noise{noise.ns, noise.nsw, noise.seed + (uint64_t)u};
                 }
                 sh.rc = STS_OK;
-                if (have_plan) {      // the plans follow their utterances into the shard
-                    std::vector<sts_dur_plan> pl(nb);
-                    for (int i = 0; i < nb; i++) {
-                        const UttPlan& up = plan[sh.utt[i]];
-                        pl[i] = sts_dur_plan{up.rate.empty() ? nullptr : up.rate.data(), up.fixed.empty() ? nullptr : up.fixed.data(), up.target};
-                    }
-                    sh.rc = eng.set_duration_plan(nb, nn.data(), pl.data());
-                }
-                if (sh.rc == STS_OK && have_mix) {      // and so do the mixes
-                    std::vector<sts_speaker_mix> mx(nb);
-                    for (int i = 0; i < nb; i++) mx[i] = mix[sh.utt[i]].view();
-                    sh.rc = eng.set_speaker_mix(nb, mx.data());
-                }
-                if (sh.rc == STS_OK && have_gain) {     // and the gain plans
-                    std::vector<sts_gain_plan> gp(nb);
-                    for (int i = 0; i < nb; i++) {
-                        const UttGain& ug = gain[sh.utt[i]];
-                        gp[i] = sts_gain_plan{ug.gain_db.empty() ? nullptr : ug.gain_db.data(), ug.ramp_ms};
-                    }
-                    sh.rc = eng.set_gain_plan(nb, nn.data(), gp.data());
-                }
-                if (sh.rc == STS_OK && have_pitch) {    // and the pitch plans
-                    std::vector<sts_pitch_plan> pp(nb);
-                    for (int i = 0; i < nb; i++) pp[i] = sts_pitch_plan{pitch[sh.utt[i]].empty() ? nullptr : pitch[sh.utt[i]].data()};
-                    sh.rc = eng.set_pitch_plan(nb, nn.data(), pp.data());
-                }
+                // the tables follow their utterances into the shard: a kind that was set goes to every utterance of it
+                std::vector<const UttTables*> tabs(nb, nullptr);
+                for (int i = 0; kinds && i < nb; i++) tabs[i] = &utt[sh.utt[i]];
+                sh.rc = apply_utt_tables(eng, nb, nn.data(), tabs.data(), kinds);
                 if (sh.rc == STS_OK) sh.rc = eng.run(nb, idp.data(), nn.data(), sd.data(), l.data());
-                else { sh.err = eng.error(); eng.set_duration_plan(0, nullptr, nullptr); eng.set_speaker_mix(0, nullptr); eng.set_gain_plan(0, nullptr, nullptr); eng.set_pitch_plan(0, nullptr, nullptr); }     // (nothing ran: nothing stays pending)
+                else sh.err = eng.error();      // (nothing ran: nothing stays pending)
                 eng.noise_utt.clear();
                 if (sh.rc == STS_OK && gather_mode == 1) {
                     sh.n_samples = eng.n_samples;           // the PCM stays on the device: rccl_gather() below
@@ -377,6 +351,24 @@ static void shard_by_phonemes(int B, const int32_t* n, int ndev, std::vector<Sha
         load[best] += n[u];
     }
     for (auto& s : out) std::sort(s.utt.begin(), s.utt.end());
+}
+
+// What the four table setters share: B == 0 or no table drops the pending one of `kind`; every entry is validated before anything
+// changes; set_n (the kinds with phoneme counts) remembers the batch
+template <typename Valid, typename Assign>
+static int multi_set_table(sts_multi* m, int kind, const char* what, int32_t B, const int32_t* n, bool given, std::vector<int32_t>* set_n, Valid&& valid, Assign&& assign) {
+    if (!m) return multi_err(STS_EINVAL, "null handle");
+    if (B == 0 || !given) { m->kinds &= ~kind; return STS_OK; }
+    if (B < 0 || (set_n && !n)) return multi_err(STS_EINVAL, std::string(what) + (set_n ? ": B >= 0 and n are required" : ": B >= 0 is required"));
+    for (int b = 0; b < B; b++) {
+        const char* why = nullptr;
+        if (!valid(b, &why)) return multi_err(STS_EINVAL, why);
+    }
+    if (m->utt.size() < (size_t)B) m->utt.resize((size_t)B);
+    for (int b = 0; b < B; b++) assign(m->utt[(size_t)b], b);
+    if (set_n) set_n->assign(n, n + B);
+    m->kinds |= kind;
+    return STS_OK;
 }
 
 extern "C" {
@@ -456,68 +448,26 @@ int sts_multi_set_eq(sts_multi* m, int32_t n_bands, const sts_eq_band* bands) {
     return STS_OK;
 }
 int sts_multi_set_duration_plan(sts_multi* m, int32_t B, const int32_t* n, const sts_dur_plan* plans) {
-    if (!m) return multi_err(STS_EINVAL, "null handle");
-    if (B == 0 || !plans) { m->have_plan = false; return STS_OK; }
-    if (B < 0 || !n) return multi_err(STS_EINVAL, "duration plan: B >= 0 and n are required");
-    for (int b = 0; b < B; b++) {
-        const char* why = nullptr;
-        if (!dur_plan_valid(n[b], plans[b].rate, plans[b].fixed, plans[b].target_frames, &why)) return multi_err(STS_EINVAL, why);
-    }
-    m->plan.assign((size_t)B, sts_multi::UttPlan());
-    m->plan_n.assign(n, n + B);
-    for (int b = 0; b < B; b++) {
-        if (plans[b].rate) m->plan[b].rate.assign(plans[b].rate, plans[b].rate + n[b]);
-        if (plans[b].fixed) m->plan[b].fixed.assign(plans[b].fixed, plans[b].fixed + n[b]);
-        m->plan[b].target = plans[b].target_frames;
-    }
-    m->have_plan = true;
-    return STS_OK;
+    return multi_set_table(m, kTabDuration, "duration plan", B, n, plans, m ? &m->plan_n : nullptr,
+                           [&](int b, const char** why) { return dur_plan_valid(n[b], plans[b].rate, plans[b].fixed, plans[b].target_frames, why); },
+                           [&](UttTables& u, int b) { u.assign_duration(plans[b], n[b]); });
 }
 int sts_multi_set_gain_plan(sts_multi* m, int32_t B, const int32_t* n, const sts_gain_plan* plans) {
-    if (!m) return multi_err(STS_EINVAL, "null handle");
-    if (B == 0 || !plans) { m->have_gain = false; return STS_OK; }
-    if (B < 0 || !n) return multi_err(STS_EINVAL, "gain plan: B >= 0 and n are required");
-    for (int b = 0; b < B; b++) {
-        const char* why = nullptr;
-        if (!gain_plan_valid(n[b], plans[b].gain_db, plans[b].ramp_ms, &why)) return multi_err(STS_EINVAL, why);
-    }
-    m->gain.assign((size_t)B, sts_multi::UttGain());
-    m->gain_n.assign(n, n + B);
-    for (int b = 0; b < B; b++) {
-        if (plans[b].gain_db) m->gain[b].gain_db.assign(plans[b].gain_db, plans[b].gain_db + n[b]);
-        m->gain[b].ramp_ms = plans[b].ramp_ms;
-    }
-    m->have_gain = true;
-    return STS_OK;
+    return multi_set_table(m, kTabGain, "gain plan", B, n, plans, m ? &m->gain_n : nullptr,
+                           [&](int b, const char** why) { return gain_plan_valid(n[b], plans[b].gain_db, plans[b].ramp_ms, why); },
+                           [&](UttTables& u, int b) { u.assign_gain(plans[b], n[b]); });
 }
 int sts_multi_set_pitch_plan(sts_multi* m, int32_t B, const int32_t* n, const sts_pitch_plan* plans) {
-    if (!m) return multi_err(STS_EINVAL, "null handle");
-    if (B == 0 || !plans) { m->have_pitch = false; return STS_OK; }
-    if (B < 0 || !n) return multi_err(STS_EINVAL, "pitch plan: B >= 0 and n are required");
-    for (int b = 0; b < B; b++) {
-        const char* why = nullptr;
-        if (!pitch_plan_valid(n[b], plans[b].cents, &why)) return multi_err(STS_EINVAL, why);
-    }
-    m->pitch.assign((size_t)B, std::vector<int32_t>());
-    m->pitch_n.assign(n, n + B);
-    for (int b = 0; b < B; b++)
-        if (plans[b].cents) m->pitch[b].assign(plans[b].cents, plans[b].cents + n[b]);
-    m->have_pitch = true;
-    return STS_OK;
+    return multi_set_table(m, kTabPitch, "pitch plan", B, n, plans, m ? &m->pitch_n : nullptr,
+                           [&](int b, const char** why) { return pitch_plan_valid(n[b], plans[b].cents, why); },
+                           [&](UttTables& u, int b) { u.assign_pitch(plans[b], n[b]); });
 }
 int sts_multi_set_speaker_mix(sts_multi* m, int32_t B, const sts_speaker_mix* mixes) {
-    if (!m) return multi_err(STS_EINVAL, "null handle");
-    if (B == 0 || !mixes) { m->have_mix = false; return STS_OK; }
-    if (B < 0) return multi_err(STS_EINVAL, "speaker mix: B >= 0 is required");
-    const Model& M = m->engines[0]->model;
-    for (int b = 0; b < B; b++) {
-        const char* why = nullptr;
-        if (!speaker_mix_valid(M.is_ms == 1 ? M.spk_num : 0, M.gin, mixes[b], &why)) return multi_err(STS_EINVAL, why);
-    }
-    m->mix.assign((size_t)B, SpeakerMixCopy());
-    for (int b = 0; b < B; b++) m->mix[b].assign(mixes[b], M.gin);
-    m->have_mix = true;
-    return STS_OK;
+    const int rc = multi_set_table(m, kTabMix, "speaker mix", B, nullptr, mixes, nullptr,
+                                   [&](int b, const char** why) { const Model& M = m->engines[0]->model; return speaker_mix_valid(M.is_ms == 1 ? M.spk_num : 0, M.gin, mixes[b], why); },
+                                   [&](UttTables& u, int b) { u.assign_mix(mixes[b], m->engines[0]->model.gin); });
+    if (rc == STS_OK && m && (m->kinds & kTabMix)) m->mix_B = B;
+    return rc;
 }
 int sts_multi_set_conv_math(sts_multi* m, int mode) {
     if (!m) return multi_err(STS_EINVAL, "null handle");
@@ -627,26 +577,14 @@ int sts_multi_shard_of(const sts_multi* m, int32_t B, const int32_t* n, int32_t*
 int sts_multi_infer_ids_batch(sts_multi* m, int32_t B, const int32_t* const* ids, const int32_t* n, const int32_t* sid,
                               const float* length_scale, int16_t** pcm_out, int32_t* n_out) {
     if (!m) return multi_err(STS_EINVAL, "bad arguments");
-    struct DropPlan { sts_multi* m; ~DropPlan() { m->have_plan = false; m->have_mix = false; m->have_gain = false; m->have_pitch = false; } } drop_plan{m};      // a duration plan, a speaker mix and a gain plan are for this call only, whatever its outcome
+    struct DropTables { sts_multi* m; ~DropTables() { m->drop_tables(); } } drop_tables{m};      // the tables are for this call only, whatever its outcome
     if (!ids || !n || !pcm_out || !n_out || B <= 0) return multi_err(STS_EINVAL, "bad arguments");
     for (int b = 0; b < B; b++) { pcm_out[b] = nullptr; n_out[b] = 0; }      // every output is defined before the first early return
     for (int b = 0; b < B; b++) if (n[b] <= 0 || !ids[b]) return multi_err(STS_EINVAL, "utterance with no phonemes");
-    if (m->have_plan) {
-        bool same = (int)m->plan_n.size() == B;
-        for (int b = 0; b < B && same; b++) same = m->plan_n[b] == n[b];
-        if (!same) return multi_err(STS_EINVAL, "the duration plan was set for another batch (B and every n[b] must match)");
-    }
-    if (m->have_mix && (int)m->mix.size() != B) return multi_err(STS_EINVAL, "the speaker mix was set for another batch (B must match)");
-    if (m->have_gain) {
-        bool same = (int)m->gain_n.size() == B;
-        for (int b = 0; b < B && same; b++) same = m->gain_n[b] == n[b];
-        if (!same) return multi_err(STS_EINVAL, "the gain plan was set for another batch (B and every n[b] must match)");
-    }
-    if (m->have_pitch) {
-        bool same = (int)m->pitch_n.size() == B;
-        for (int b = 0; b < B && same; b++) same = m->pitch_n[b] == n[b];
-        if (!same) return multi_err(STS_EINVAL, "the pitch plan was set for another batch (B and every n[b] must match)");
-    }
+    if ((m->kinds & kTabDuration) && !table_matches(m->plan_n, B, n)) return multi_err(STS_EINVAL, other_batch_message("duration plan"));
+    if ((m->kinds & kTabMix) && m->mix_B != B) return multi_err(STS_EINVAL, other_batch_message("speaker mix", false));
+    if ((m->kinds & kTabGain) && !table_matches(m->gain_n, B, n)) return multi_err(STS_EINVAL, other_batch_message("gain plan"));
+    if ((m->kinds & kTabPitch) && !table_matches(m->pitch_n, B, n)) return multi_err(STS_EINVAL, other_batch_message("pitch plan"));
     const int ndev = (int)m->engines.size();
     const bool was_gather = m->gather_mode == 1;
     {

@@ -27,14 +27,7 @@ struct Request {
     int64_t ticket = 0;
     std::vector<int32_t> ids; int32_t sid = 0; float ls = 1.f;
     Engine::Noise noise;               // sts_pool_submit_ex: this request's sampling noise
-    // sts_pool_submit_plan: this request's duration plan (rate / fixed: n entries or empty = absent; target 0 = none)
-    bool planned = false; std::vector<float> rate; std::vector<int32_t> fixed; int32_t target = 0;
-    // sts_pool_submit_mix: this request's speaker mix (mixed: a non-empty entry)
-    bool mixed = false; SpeakerMixCopy mix;
-    // sts_pool_submit_gain: this request's gain plan (gained: an entry with gains; gain_db: n entries)
-    bool gained = false; std::vector<float> gain_db; float ramp_ms = 0.f;
-    // sts_pool_submit_pitch: this request's pitch plan (pitched: an entry with cents; cents: n entries)
-    bool pitched = false; std::vector<int32_t> cents;
+    UttTables tab;                     // sts_pool_submit_plan / _mix / _gain / _pitch / _stream_ex: this request's own tables
     // sts_pool_submit_joined: a paragraph -- its sentences (ids / sid / ls above stay empty), the join (gaps copied: join.gap_frames points
     // into them, or is null) -- run as its own packed batch; sentence b samples with noise.seed + b
     bool joined = false; std::vector<std::vector<int32_t>> sent_ids; std::vector<int32_t> sent_sid; std::vector<float> sent_ls;
@@ -140,34 +133,9 @@ struct sts_pool {
     // set when a member carries one, and the members without get an empty entry of it (synthesised as without, bit for bit).  On a
     // failure nothing stays pending for another group.
     int set_group_tables(Engine& eng, const std::vector<std::shared_ptr<Request>>& grp, const int32_t* n) {
-        const int B = (int)grp.size();
-        bool any_plan = false, any_mix = false, any_gain = false, any_pitch = false;
-        for (int b = 0; b < B; b++) { any_plan = any_plan || grp[b]->planned; any_mix = any_mix || grp[b]->mixed; any_gain = any_gain || grp[b]->gained; any_pitch = any_pitch || grp[b]->pitched; }
-        int rc = STS_OK;
-        if (any_plan) {
-            std::vector<sts_dur_plan> pl(B, sts_dur_plan{nullptr, nullptr, 0});
-            for (int b = 0; b < B; b++)
-                if (grp[b]->planned) pl[b] = sts_dur_plan{grp[b]->rate.empty() ? nullptr : grp[b]->rate.data(),
-                                                          grp[b]->fixed.empty() ? nullptr : grp[b]->fixed.data(), grp[b]->target};
-            rc = eng.set_duration_plan(B, n, pl.data());
-        }
-        if (rc == STS_OK && any_mix) {      // (the plain members: their sid)
-            std::vector<sts_speaker_mix> mx(B, sts_speaker_mix{0, nullptr, nullptr, nullptr, 0.f});
-            for (int b = 0; b < B; b++) if (grp[b]->mixed) mx[b] = grp[b]->mix.view();
-            rc = eng.set_speaker_mix(B, mx.data());
-        }
-        if (rc == STS_OK && any_gain) {     // (the members without one: an entry without gains)
-            std::vector<sts_gain_plan> gp(B, sts_gain_plan{nullptr, 0.f});
-            for (int b = 0; b < B; b++) if (grp[b]->gained) gp[b] = sts_gain_plan{grp[b]->gain_db.data(), grp[b]->ramp_ms};
-            rc = eng.set_gain_plan(B, n, gp.data());
-        }
-        if (rc == STS_OK && any_pitch) {    // (the members without one: an entry without cents, copied bit for bit)
-            std::vector<sts_pitch_plan> pp(B, sts_pitch_plan{nullptr});
-            for (int b = 0; b < B; b++) if (grp[b]->pitched) pp[b] = sts_pitch_plan{grp[b]->cents.data()};
-            rc = eng.set_pitch_plan(B, n, pp.data());
-        }
-        if (rc != STS_OK) eng.drop_tables();
-        return rc;
+        std::vector<const UttTables*> members;
+        for (auto& r : grp) members.push_back(&r->tab);
+        return apply_utt_tables(eng, (int)grp.size(), n, members.data());
     }
 
     // a paragraph (Engine::run_joined): its sentences as one packed batch of their own, one PCM
@@ -378,12 +346,8 @@ int64_t sts_pool_submit(sts_pool* p, const int32_t* ids, int32_t n, int32_t sid,
     return sts_pool_submit_ex(p, ids, n, sid, length_scale, 0.f, 0.f, 0);
 }
 
-int64_t sts_pool_submit_ex(sts_pool* p, const int32_t* ids, int32_t n, int32_t sid, float length_scale, float noise_scale,
-                           float noise_scale_w, uint64_t seed) {
-    if (!p || !ids || n <= 0) return pool_err(STS_EINVAL, "bad request");
-    if (!noise_scale_valid(noise_scale) || !noise_scale_valid(noise_scale_w)) return pool_err(STS_EINVAL, "noise scales must be finite and >= 0");
-    auto r = std::make_shared<Request>();
-    r->ids.assign(ids, ids + n); r->sid = sid; r->ls = length_scale; r->noise = Engine::Noise{noise_scale, noise_scale_w, seed};
+// a request that is not a streaming one into the FIFO: its ticket
+static int64_t enqueue(sts_pool* p, const std::shared_ptr<Request>& r) {
     {
         std::lock_guard<std::mutex> lk(p->mu);
         if (p->stop) return pool_err(STS_ESTATE, "pool is shutting down");
@@ -395,6 +359,15 @@ int64_t sts_pool_submit_ex(sts_pool* p, const int32_t* ids, int32_t n, int32_t s
     return r->ticket;
 }
 
+int64_t sts_pool_submit_ex(sts_pool* p, const int32_t* ids, int32_t n, int32_t sid, float length_scale, float noise_scale,
+                           float noise_scale_w, uint64_t seed) {
+    if (!p || !ids || n <= 0) return pool_err(STS_EINVAL, "bad request");
+    if (!noise_scale_valid(noise_scale) || !noise_scale_valid(noise_scale_w)) return pool_err(STS_EINVAL, "noise scales must be finite and >= 0");
+    auto r = std::make_shared<Request>();
+    r->ids.assign(ids, ids + n); r->sid = sid; r->ls = length_scale; r->noise = Engine::Noise{noise_scale, noise_scale_w, seed};
+    return enqueue(p, r);
+}
+
 int64_t sts_pool_submit_plan(sts_pool* p, const int32_t* ids, int32_t n, int32_t sid, float length_scale, float noise_scale,
                              float noise_scale_w, uint64_t seed, const float* rate, const int32_t* fixed, int32_t target_frames) {
     if (!p || !ids || n <= 0) return pool_err(STS_EINVAL, "bad request");
@@ -403,19 +376,8 @@ int64_t sts_pool_submit_plan(sts_pool* p, const int32_t* ids, int32_t n, int32_t
     if (!dur_plan_valid(n, rate, fixed, target_frames, &why)) return pool_err(STS_EINVAL, why);
     auto r = std::make_shared<Request>();
     r->ids.assign(ids, ids + n); r->sid = sid; r->ls = length_scale; r->noise = Engine::Noise{noise_scale, noise_scale_w, seed};
-    r->planned = rate || fixed || target_frames != 0;
-    if (rate) r->rate.assign(rate, rate + n);
-    if (fixed) r->fixed.assign(fixed, fixed + n);
-    r->target = target_frames;
-    {
-        std::lock_guard<std::mutex> lk(p->mu);
-        if (p->stop) return pool_err(STS_ESTATE, "pool is shutting down");
-        r->ticket = p->next_ticket++;
-        p->queue.push_back(r);
-        p->pending[r->ticket] = r;
-    }
-    p->cv_work.notify_one();
-    return r->ticket;
+    r->tab.assign_duration(sts_dur_plan{rate, fixed, target_frames}, n);
+    return enqueue(p, r);
 }
 
 int64_t sts_pool_submit_mix(sts_pool* p, const int32_t* ids, int32_t n, int32_t sid, float length_scale, float noise_scale,
@@ -427,17 +389,8 @@ int64_t sts_pool_submit_mix(sts_pool* p, const int32_t* ids, int32_t n, int32_t 
     if (mix && !speaker_mix_valid(M.is_ms == 1 ? M.spk_num : 0, M.gin, *mix, &why)) return pool_err(STS_EINVAL, why);
     auto r = std::make_shared<Request>();
     r->ids.assign(ids, ids + n); r->sid = sid; r->ls = length_scale; r->noise = Engine::Noise{noise_scale, noise_scale_w, seed};
-    r->mixed = mix && !speaker_mix_empty(*mix);
-    if (r->mixed) r->mix.assign(*mix, M.gin);
-    {
-        std::lock_guard<std::mutex> lk(p->mu);
-        if (p->stop) return pool_err(STS_ESTATE, "pool is shutting down");
-        r->ticket = p->next_ticket++;
-        p->queue.push_back(r);
-        p->pending[r->ticket] = r;
-    }
-    p->cv_work.notify_one();
-    return r->ticket;
+    if (mix) r->tab.assign_mix(*mix, M.gin);
+    return enqueue(p, r);
 }
 
 int64_t sts_pool_submit_gain(sts_pool* p, const int32_t* ids, int32_t n, int32_t sid, float length_scale, float noise_scale,
@@ -448,17 +401,8 @@ int64_t sts_pool_submit_gain(sts_pool* p, const int32_t* ids, int32_t n, int32_t
     if (plan && !gain_plan_valid(n, plan->gain_db, plan->ramp_ms, &why)) return pool_err(STS_EINVAL, why);
     auto r = std::make_shared<Request>();
     r->ids.assign(ids, ids + n); r->sid = sid; r->ls = length_scale; r->noise = Engine::Noise{noise_scale, noise_scale_w, seed};
-    r->gained = plan && plan->gain_db;
-    if (r->gained) { r->gain_db.assign(plan->gain_db, plan->gain_db + n); r->ramp_ms = plan->ramp_ms; }
-    {
-        std::lock_guard<std::mutex> lk(p->mu);
-        if (p->stop) return pool_err(STS_ESTATE, "pool is shutting down");
-        r->ticket = p->next_ticket++;
-        p->queue.push_back(r);
-        p->pending[r->ticket] = r;
-    }
-    p->cv_work.notify_one();
-    return r->ticket;
+    if (plan && plan->gain_db) r->tab.assign_gain(*plan, n);      // (a plan without gains is no plan: its ramp is not kept)
+    return enqueue(p, r);
 }
 
 int64_t sts_pool_submit_joined(sts_pool* p, int32_t B, const int32_t* const* ids, const int32_t* n, const int32_t* sid,
@@ -482,15 +426,7 @@ int64_t sts_pool_submit_joined(sts_pool* p, int32_t B, const int32_t* const* ids
         if (join->gap_frames && B > 1) { r->gaps.assign(join->gap_frames, join->gap_frames + (B - 1)); r->join.gap_frames = r->gaps.data(); }
         else r->join.gap_frames = nullptr;
     }
-    {
-        std::lock_guard<std::mutex> lk(p->mu);
-        if (p->stop) return pool_err(STS_ESTATE, "pool is shutting down");
-        r->ticket = p->next_ticket++;
-        p->queue.push_back(r);
-        p->pending[r->ticket] = r;
-    }
-    p->cv_work.notify_one();
-    return r->ticket;
+    return enqueue(p, r);
 }
 
 int64_t sts_pool_submit_stream(sts_pool* p, const int32_t* ids, int32_t n, int32_t sid, float length_scale, float noise_scale,
@@ -506,17 +442,8 @@ int64_t sts_pool_submit_pitch(sts_pool* p, const int32_t* ids, int32_t n, int32_
     if (plan && !pitch_plan_valid(n, plan->cents, &why)) return pool_err(STS_EINVAL, why);
     auto r = std::make_shared<Request>();
     r->ids.assign(ids, ids + n); r->sid = sid; r->ls = length_scale; r->noise = Engine::Noise{noise_scale, noise_scale_w, seed};
-    r->pitched = plan && plan->cents;
-    if (r->pitched) r->cents.assign(plan->cents, plan->cents + n);
-    {
-        std::lock_guard<std::mutex> lk(p->mu);
-        if (p->stop) return pool_err(STS_ESTATE, "pool is shutting down");
-        r->ticket = p->next_ticket++;
-        p->queue.push_back(r);
-        p->pending[r->ticket] = r;
-    }
-    p->cv_work.notify_one();
-    return r->ticket;
+    if (plan) r->tab.assign_pitch(*plan, n);
+    return enqueue(p, r);
 }
 
 int64_t sts_pool_submit_stream_ex(sts_pool* p, const int32_t* ids, int32_t n, int32_t sid, float length_scale, float noise_scale,
@@ -533,16 +460,9 @@ int64_t sts_pool_submit_stream_ex(sts_pool* p, const int32_t* ids, int32_t n, in
     auto r = std::make_shared<Request>();
     r->ids.assign(ids, ids + n); r->sid = sid; r->ls = length_scale; r->noise = Engine::Noise{noise_scale, noise_scale_w, seed};
     r->stream = true; r->chunk = chunk_frames; r->cb = cb; r->user = user;
-    r->planned = plan && (plan->rate || plan->fixed || plan->target_frames != 0);
-    if (r->planned) {
-        if (plan->rate) r->rate.assign(plan->rate, plan->rate + n);
-        if (plan->fixed) r->fixed.assign(plan->fixed, plan->fixed + n);
-        r->target = plan->target_frames;
-    }
-    r->mixed = mix && !speaker_mix_empty(*mix);
-    if (r->mixed) r->mix.assign(*mix, M.gin);
-    r->gained = gain && gain->gain_db;
-    if (r->gained) { r->gain_db.assign(gain->gain_db, gain->gain_db + n); r->ramp_ms = gain->ramp_ms; }
+    if (plan) r->tab.assign_duration(*plan, n);
+    if (mix) r->tab.assign_mix(*mix, M.gin);
+    if (gain && gain->gain_db) r->tab.assign_gain(*gain, n);      // (as sts_pool_submit_gain)
     {
         std::lock_guard<std::mutex> lk(p->mu);
         if (p->stop) return pool_err(STS_ESTATE, "pool is shutting down");

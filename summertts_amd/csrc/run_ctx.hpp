@@ -67,7 +67,7 @@ struct Engine::RunCtx {
     int H = 0, C = 0, FF = 0, fdp = 0, wnH = 0, wnL = 0, ffn2_slices = 1;
     Lvl lvT, lvB, lv1;
     BufT bt; BufF bf;
-    size_t meta_ints = 0, up_bytes = 0;
+    size_t up_bytes = 0;
     int *pm = nullptr, *p_offT = nullptr, *p_lenT = nullptr, *p_sid = nullptr, *p_offF = nullptr, *p_lenF = nullptr, *p_one = nullptr;
     int *d_offT = nullptr, *d_lenT = nullptr, *d_sid = nullptr, *d_offF = nullptr, *d_lenF = nullptr, *d_one = nullptr, *d_win = nullptr;
     bool inl = false, no_inline_seg = false, ms = false;

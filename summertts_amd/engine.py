@@ -1124,7 +1124,32 @@ def _check(lib, rc: int):
         raise StsError(f"sts error {rc}: {lib.sts_last_error().decode(errors='replace')}")
 
 
-class Synthesizer:
+class _TableSetters:
+    """The table setters of ``Synthesizer`` and ``MultiDevice`` (``set_duration_plan``, ``set_speaker_mix``, ``set_gain_plan``,
+    ``set_pitch_plan``) in one place.  A class names its C entries (``_TABLE_ENTRY % kind``), the gin a mix's vector is checked
+    against here (``_mix_gin``, None: the library checks it) and how a failed entry raises (``_table_failed``)."""
+
+    _TABLE_BUILDERS = {"duration_plan": _dur_plans, "gain_plan": _gain_plans, "pitch_plan": _pitch_plans}
+
+    def _set_table(self, kind: str, n, tables):
+        name = self._TABLE_ENTRY % kind
+        fn = getattr(self.lib, name)
+        if kind == "speaker_mix":
+            if tables is None:
+                rc = fn(self.h, 0, None)
+            else:
+                arr, keep = _speaker_mixes(tables, self._mix_gin())
+                rc = fn(self.h, len(tables), C.cast(arr, C.c_void_p))
+        elif n is None or tables is None:
+            rc = fn(self.h, 0, None, None)
+        else:
+            nn, arr, keep = self._TABLE_BUILDERS[kind](n, tables)
+            rc = fn(self.h, nn.size, nn.ctypes.data, C.cast(arr, C.c_void_p))
+        if rc != 0:
+            self._table_failed(name, rc)
+
+
+class Synthesizer(_TableSetters):
     """Python mirror of the reference's ``SynthesizerTrn`` (include/SynthesizerTrn.h) at the phoneme-id
     boundary: construct from a model blob, ``infer_ids`` -> int16 PCM.  Adds the batched entry."""
 
@@ -1478,48 +1503,40 @@ class Synthesizer:
         d = np.ascontiguousarray(dur, dtype=np.int32)
         _check(self.lib, self.lib.sts_set_forced_durations(self.h, d.ctypes.data, d.size))
 
+    _TABLE_ENTRY = "sts_set_%s"
+
+    def _mix_gin(self):
+        return int(self.info.gin_channels)
+
+    def _table_failed(self, name, rc):
+        _check(self.lib, rc)
+
     def set_duration_plan(self, n: Optional[Sequence[int]], plans=None):
         """Duration plan of the NEXT call only (include/summertts_hip.h sts_set_duration_plan).  ``n``: phoneme count of every utterance
         of that call; ``plans``: per utterance None or a mapping with any of ``rate`` (float per phoneme, multiplies the length scale),
         ``fixed`` (frames per phoneme, -1 = predicted), ``target_frames`` (the utterance's exact length; 0 = none).  ``n`` or ``plans``
         None drops a pending plan.  An invalid plan raises and changes nothing."""
-        if n is None or plans is None:
-            _check(self.lib, self.lib.sts_set_duration_plan(self.h, 0, None, None))
-            return
-        nn, arr, keep = _dur_plans(n, plans)
-        _check(self.lib, self.lib.sts_set_duration_plan(self.h, nn.size, nn.ctypes.data, C.cast(arr, C.c_void_p)))
+        self._set_table("duration_plan", n, plans)
 
     def set_speaker_mix(self, mixes=None):
         """Speaker mix of the NEXT call only (include/summertts_hip.h sts_set_speaker_mix).  ``mixes``: per utterance of that call None
         (its plain sid) or a mapping with any of ``sid`` + ``weight`` (rows of the model's table and their weights), ``vector`` (a caller's
         embedding, gin_channels floats) and ``vector_weight`` (default 1).  None drops a pending mix.  An invalid mix raises and changes
         nothing."""
-        if mixes is None:
-            _check(self.lib, self.lib.sts_set_speaker_mix(self.h, 0, None))
-            return
-        arr, keep = _speaker_mixes(mixes, int(self.info.gin_channels))
-        _check(self.lib, self.lib.sts_set_speaker_mix(self.h, len(mixes), C.cast(arr, C.c_void_p)))
+        self._set_table("speaker_mix", None, mixes)
 
     def set_gain_plan(self, n: Optional[Sequence[int]], plans=None):
         """Gain plan of the NEXT call only (include/summertts_hip.h sts_set_gain_plan).  ``n``: phoneme count of every utterance of that
         call; ``plans``: per utterance None or a mapping with ``gain_db`` (dB per phoneme, ``-inf`` = mute) and ``ramp_ms`` (width of the
         transition across a phoneme boundary, default 0).  ``n`` or ``plans`` None drops a pending plan.  An invalid plan raises and
         changes nothing."""
-        if n is None or plans is None:
-            _check(self.lib, self.lib.sts_set_gain_plan(self.h, 0, None, None))
-            return
-        nn, arr, keep = _gain_plans(n, plans)
-        _check(self.lib, self.lib.sts_set_gain_plan(self.h, nn.size, nn.ctypes.data, C.cast(arr, C.c_void_p)))
+        self._set_table("gain_plan", n, plans)
 
     def set_pitch_plan(self, n: Optional[Sequence[int]], plans=None):
         """Pitch plan of the NEXT call only (include/summertts_hip.h sts_set_pitch_plan).  ``n``: phoneme count of every utterance of that
         call; ``plans``: per utterance None, a sequence of cents per phoneme (integers in [-600, 600]) or a mapping with ``cents``.  The
         formants move with the pitch.  ``n`` or ``plans`` None drops a pending plan.  An invalid plan raises and changes nothing."""
-        if n is None or plans is None:
-            _check(self.lib, self.lib.sts_set_pitch_plan(self.h, 0, None, None))
-            return
-        nn, arr, keep = _pitch_plans(n, plans)
-        _check(self.lib, self.lib.sts_set_pitch_plan(self.h, nn.size, nn.ctypes.data, C.cast(arr, C.c_void_p)))
+        self._set_table("pitch_plan", n, plans)
 
     def speaker_embedding(self, sid: int) -> np.ndarray:
         """Row ``sid`` of the model's speaker table: float32 [gin_channels] (sts_get_speaker_embedding)."""
@@ -2067,7 +2084,7 @@ def multi_gather_layout(counts: Sequence[int]):
     return off, total
 
 
-class MultiDevice:
+class MultiDevice(_TableSetters):
     """``sts_multi``: one process, one engine per listed HIP device; batches are sharded by utterance."""
 
     MODES = {"auto": 0, "rccl": 1, "download": 2}
@@ -2137,49 +2154,33 @@ class MultiDevice:
         if rc != 0:
             raise StsError(f"sts_multi_set_eq: {rc}: {self.lib.sts_multi_last_error().decode()}")
 
+    _TABLE_ENTRY = "sts_multi_set_%s"
+
+    def _mix_gin(self):
+        return None
+
+    def _table_failed(self, name, rc):
+        raise StsError(f"{name}: {rc}: {self.lib.sts_multi_last_error().decode()}")
+
     def set_duration_plan(self, n: Optional[Sequence[int]], plans=None):
         """``Synthesizer.set_duration_plan`` for the next ``infer_batch``: ``plans[b]`` belongs to utterance b of that batch, whatever its
         device."""
-        if n is None or plans is None:
-            rc = self.lib.sts_multi_set_duration_plan(self.h, 0, None, None)
-        else:
-            nn, arr, keep = _dur_plans(n, plans)
-            rc = self.lib.sts_multi_set_duration_plan(self.h, nn.size, nn.ctypes.data, C.cast(arr, C.c_void_p))
-        if rc != 0:
-            raise StsError(f"sts_multi_set_duration_plan: {rc}: {self.lib.sts_multi_last_error().decode()}")
+        self._set_table("duration_plan", n, plans)
 
     def set_speaker_mix(self, mixes=None):
         """``Synthesizer.set_speaker_mix`` for the next ``infer_batch``: ``mixes[b]`` belongs to utterance b of that batch, whatever its
         device."""
-        if mixes is None:
-            rc = self.lib.sts_multi_set_speaker_mix(self.h, 0, None)
-        else:
-            arr, keep = _speaker_mixes(mixes)
-            rc = self.lib.sts_multi_set_speaker_mix(self.h, len(mixes), C.cast(arr, C.c_void_p))
-        if rc != 0:
-            raise StsError(f"sts_multi_set_speaker_mix: {rc}: {self.lib.sts_multi_last_error().decode()}")
+        self._set_table("speaker_mix", None, mixes)
 
     def set_gain_plan(self, n: Optional[Sequence[int]], plans=None):
         """``Synthesizer.set_gain_plan`` for the next ``infer_batch``: ``plans[b]`` belongs to utterance b of that batch, whatever its
         device."""
-        if n is None or plans is None:
-            rc = self.lib.sts_multi_set_gain_plan(self.h, 0, None, None)
-        else:
-            nn, arr, keep = _gain_plans(n, plans)
-            rc = self.lib.sts_multi_set_gain_plan(self.h, nn.size, nn.ctypes.data, C.cast(arr, C.c_void_p))
-        if rc != 0:
-            raise StsError(f"sts_multi_set_gain_plan: {rc}: {self.lib.sts_multi_last_error().decode()}")
+        self._set_table("gain_plan", n, plans)
 
     def set_pitch_plan(self, n: Optional[Sequence[int]], plans=None):
         """``Synthesizer.set_pitch_plan`` for the next ``infer_batch``: ``plans[b]`` belongs to utterance b of that batch, whatever its
         device."""
-        if n is None or plans is None:
-            rc = self.lib.sts_multi_set_pitch_plan(self.h, 0, None, None)
-        else:
-            nn, arr, keep = _pitch_plans(n, plans)
-            rc = self.lib.sts_multi_set_pitch_plan(self.h, nn.size, nn.ctypes.data, C.cast(arr, C.c_void_p))
-        if rc != 0:
-            raise StsError(f"sts_multi_set_pitch_plan: {rc}: {self.lib.sts_multi_last_error().decode()}")
+        self._set_table("pitch_plan", n, plans)
 
     def set_conv_math(self, mode):
         m = {"bf16x3": 0, "f32": 1, "bf16x3_all": 2, "f16x2": 3}.get(mode, mode)
