@@ -541,8 +541,8 @@ int sts_gain_plan_apply(int device, const float* x, const int32_t* dur_frames, c
  * never launched ahead and neither reads nor feeds the launch-ahead memo; its layout is made on the host when the durations arrive (they
  * come with the frame counts) and uploaded without a further wait; the split-bf16 repeat of a call applies the same plan again.  A call
  * with no plan pending launches, allocates and uploads nothing new.
- * NOT AVAILABLE with a plan pending -- each answers STS_EINVAL, runs nothing and drops the plan: sts_infer_ids_stream,
- * sts_infer_ids_batch_stream, sts_stream_open / sts_stream_open_ex, sts_stream_admit, sts_infer_ids_joined, sts_infer_ids_joined_stream,
+ * NOT AVAILABLE with a plan pending -- each answers STS_EINVAL, runs nothing and drops the plan: sts_infer_ids_stream and
+ * sts_infer_ids_batch_stream (unless sts_set_pitch_streaming is on, below), sts_stream_open / sts_stream_open_ex, sts_stream_admit, sts_infer_ids_joined, sts_infer_ids_joined_stream,
  * sts_para_open, sts_para_append (while a paragraph or an unplanned stream is open the setter itself answers STS_ESTATE).
  * Added without a new STS_ABI_VERSION: detect the entries by symbol. */
 typedef struct sts_pitch_plan {
@@ -571,6 +571,48 @@ int sts_pitch_apply(int device, const float* x, const int32_t* dur_frames, const
  * LDS (1), then iters >= 1 more launches between two events: *ms_out = their mean time in milliseconds. */
 int sts_debug_pitch_bench(int device, const float* x, const int32_t* dur_frames, const int32_t* lengths, int32_t B, int32_t samples_per_frame,
                           const sts_pitch_plan* plans, float* y, int64_t capacity, int32_t table_in_lds, int32_t iters, float* ms_out);
+/* ---- a pitch plan in a stream (ABI number unchanged: detect the entries by symbol).  The warp's layout is exact integer arithmetic on
+ * durations that are known before a stream's first step, and output j depends on nothing but j and its taps: so a chunk of decoder frames
+ * maps to a range of warped outputs.  sts_set_pitch_streaming(e, 1) lets sts_infer_ids_stream and sts_infer_ids_batch_stream run with a
+ * plan pending: the steps and the chunk grid are those of a duration-planned stream with the compensated rates, every step warps its
+ * decode windows with the range form of the warp kernel, and the concatenated chunks of utterance b are the PCM of sts_infer_ids /
+ * sts_infer_ids_batch with the same plan bit for bit (under a pinned conv mode, as for every stream), for every chunk size, at every
+ * output rate, with the limiter, a gain plan, a duration plan, a speaker mix and sampling noise.  The callback's n and first-output index,
+ * delivered[b] and sts_get_phoneme_offsets carry the warped counts at the output rate; a chunk that owns no output (possible when a chunk
+ * is a single sample) is not delivered.  sts_stream_halo_frames reports the larger halo of such a stream while a plan is pending:
+ * dec_halo + ceil((ceil(extra step(+600) / 2^32) + 52) / hop), extra = the resampler's K plus the limiter's reach in native samples.
+ * Off by default and persistent; STS_ESTATE while a stream or a paragraph is open.  With the switch off every call does what it did.  With
+ * it on and a plan pending, a stream still answers STS_EINVAL, runs nothing and drops the plan while the streamed EQ has bands set
+ * (sts_set_eq_streaming), streamed loudness measures (sts_set_loudness_streaming under mode 1) or record taps are on; and every other
+ * form of the NOT AVAILABLE list above refuses as before: open streams, joined runs and joined streams, open paragraphs, the pool's
+ * streaming requests and sts_multi_*.
+ * With pos(j) the Q32 position of step 3 (strictly increasing; a member without a plan: j << 32),
+ *   Y(f) = #{j : pos(j) < (f hop) << 32}, Y(F) = N';
+ * chunk k of an utterance of F frames, C = chunk_frames, owns the warped outputs [Y(k C), Y(min(F, (k + 1) C))) and, at the output rate
+ * P / Q, the samples [ceil(Y(k C) P / Q), ceil(Y(min(F, (k + 1) C)) P / Q)) of ceil(N' P / Q): the chunks partition the signal in order.
+ * sts_pitch_chunk_starts (host only) returns the number of chunks ceil(F / C) -- or a negative STS_E* code -- and, when out_first is
+ * non-null, out_first[k] = Y(k C) for every chunk and out_first[chunks] = N' (capacity below chunks + 1: STS_EINVAL).  step == NULL is the
+ * member without a plan (Y(f) = f hop); otherwise the steps of sts_pitch_design.  Arguments as sts_pitch_layout. */
+int sts_set_pitch_streaming(sts_engine* e, int enable);
+int sts_pitch_chunk_starts(const int32_t* dur_frames, const int64_t* step, int32_t n, int32_t samples_per_frame, int32_t chunk_frames,
+                           int64_t* out_first, int64_t capacity);
+/* The range form of the warp kernel on caller data: what a step of a stream through the warp launches.  The batch (dur_frames, lengths, B,
+ * samples_per_frame, plans) is sts_pitch_apply's and fixes every utterance's layout.  Window i computes the outputs [y0, y1) of utterance
+ * utt from the native samples [u0, u0 + xlen) of that utterance, which stand at x[xbase .. xbase + xlen) of the caller's buffer of x_len
+ * floats; the kernel reads nothing else of x and takes every other sample of the utterance as 0.  The window must therefore cover the span
+ * its outputs read, clipped to the utterance: [max(0, n0(y0) - 50), min(N, n0(y1 - 1) + 52)) with n0 of step 4 (an utterance without a
+ * plan: [y0, y1) itself) -- otherwise STS_EINVAL, as for a window outside x or outside [0, N), a range outside [0, N'], n_win outside
+ * [1, 65535] or a capacity below sum (y1 - y0).  y (float) and pcm (int16) receive the ranges packed back to back in window order, each
+ * may be NULL.  Every sample equals sts_pitch_apply's sample j of that utterance bit for bit. */
+typedef struct sts_pitch_range {
+    int32_t utt;            /* the utterance of the batch, [0, B) */
+    int64_t xbase;          /* where the window's first sample stands in x */
+    int64_t u0, xlen;       /* the window: native samples [u0, u0 + xlen) of the utterance */
+    int64_t y0, y1;         /* the warped outputs to compute */
+} sts_pitch_range;
+int sts_pitch_apply_range(int device, const float* x, int64_t x_len, const int32_t* dur_frames, const int32_t* lengths, int32_t B,
+                          int32_t samples_per_frame, const sts_pitch_plan* plans, const sts_pitch_range* win, int32_t n_win, float* y,
+                          int16_t* pcm, int64_t capacity);
 /* ---- paragraph synthesis (no reference counterpart: SynthesizerTrn::infer runs a whole line as ONE utterance, at quadratic attention cost and
  * without batching).  sts_infer_ids_joined runs B sentences as exactly the packed batch sts_infer_ids_batch would run and joins their float
  * waves on the device into ONE signal -- in front of the resampler, loudness, the limiter and the cast, which then see the paragraph as the

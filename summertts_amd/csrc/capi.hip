@@ -15,6 +15,7 @@
 #include "join_stream.hpp"
 #include "loud_stream.hpp"
 #include "para_stream.hpp"
+#include "pitch_stream.hpp"
 
 using namespace sts;
 
@@ -260,7 +261,7 @@ int sts_para_close(sts_engine* e) {
 
 int sts_stream_halo_frames(const sts_engine* e) {
     if (!e) return set_err(STS_EINVAL, "null engine");
-    return e->eng.stream_halo();
+    return e->eng.stream_halo(e->eng.pitch_streaming && e->eng.pend.have_pitch);      // (the larger halo of a stream through the pitch warp)
 }
 
 int sts_set_forced_durations(sts_engine* e, const int32_t* dur, int64_t count) {
@@ -357,6 +358,32 @@ int sts_pitch_layout(const int32_t* dur_frames, const int64_t* step, int32_t n, 
     if (!pitch_layout(dur_frames, step, n, samples_per_frame, out_start, resid))
         return set_err(STS_EINVAL, "pitch layout: n >= 1 durations in [0, 100000], steps in [step(-600), step(600)], samples_per_frame in [1, 2^20] and fewer than 2^30 samples are required");
     return STS_OK;
+}
+int sts_set_pitch_streaming(sts_engine* e, int enable) {
+    if (!e) return set_err(STS_EINVAL, "null engine");
+    STS_CAPI_NOT_WHILE_OPEN(e);
+    e->eng.pitch_streaming = enable != 0;
+    return STS_OK;
+}
+int sts_pitch_chunk_starts(const int32_t* dur_frames, const int64_t* step, int32_t n, int32_t samples_per_frame, int32_t chunk_frames,
+                           int64_t* out_first, int64_t capacity) {
+    if (n < 1 || !dur_frames || samples_per_frame < 1 || samples_per_frame > kPitchMaxHop || chunk_frames < 1 || capacity < 0 || (capacity > 0 && !out_first))
+        return set_err(STS_EINVAL, "pitch chunk starts: n >= 1 durations, samples_per_frame in [1, 2^20] and chunk_frames >= 1 are required");
+    if (step)
+        for (int i = 0; i < n; i++)
+            if (step[i] < kPitchStepMin || step[i] > kPitchStepMax) return set_err(STS_EINVAL, "pitch chunk starts: steps must be in [step(-600), step(600)]");
+    PitchTables tab;
+    const long long xoff = 0;
+    if (const char* bad = pitch_tables(1, &n, &dur_frames, &step, &xoff, samples_per_frame, &tab)) return set_err(STS_EINVAL, bad);
+    const PsUtt u = ps_utt(tab.words.data(), 1, tab.TT, 0);
+    const long long F = u.N / samples_per_frame, chunks = (F + chunk_frames - 1) / chunk_frames;
+    if (chunks > 0x7fffffffll) return set_err(STS_EINVAL, "pitch chunk starts: too many chunks");
+    if (out_first) {
+        if (capacity < chunks + 1) return set_err(STS_EINVAL, "pitch chunk starts: out_first needs room for one entry per chunk and one more");
+        for (long long k = 0; k < chunks; k++) out_first[k] = ps_Y(u, k * chunk_frames * samples_per_frame);
+        out_first[chunks] = u.Nw;
+    }
+    return (int)chunks;
 }
 int sts_pitch_table(float* table, int64_t capacity_floats) {
     if (!table || capacity_floats < kPitchTableFloats) return set_err(STS_EINVAL, "pitch table: room for 16386 floats is required");

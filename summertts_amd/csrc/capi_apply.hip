@@ -13,6 +13,7 @@
 #include "eq_stream.hpp"
 #include "join_stream.hpp"
 #include "loud_stream.hpp"
+#include "pitch_stream.hpp"
 
 using namespace sts;
 
@@ -141,12 +142,11 @@ int sts_gain_plan_apply(int device, const float* x, const int32_t* dur_frames, c
     return d.finish() ? STS_OK : set_err(STS_EDEVICE, "the gain plan failed on the device");
 }
 
-// table_mode: -1 the shipped placement of the prototype, 0 global memory, 1 LDS; iters > 0: that many more launches between two events,
-// their mean in *ms (sts_debug_pitch_bench)
-static int pitch_apply_impl(int device, const float* x, const int32_t* dur_frames, const int32_t* lengths, int32_t B, int32_t samples_per_frame,
-                            const sts_pitch_plan* plans, int64_t* out_len, float* y, int16_t* pcm, int64_t capacity, int table_mode, int iters,
-                            float* ms) {
-    if (B < 1 || B > 65535 || !x || !dur_frames || !lengths || !plans || samples_per_frame < 1 || samples_per_frame > kPitchMaxHop || capacity < 0)      // (one grid row per signal)
+// the host side of the pitch entries: the batch's validity and the warp's tables (utterance b's signal at its offset in the packed x:
+// the geometry the engine derives from its durations); *total = the samples of x.  STS_OK, or the error set
+static int pitch_host_tables(const int32_t* dur_frames, const int32_t* lengths, int32_t B, int32_t samples_per_frame, const sts_pitch_plan* plans,
+                             PitchTables& tab, int64_t* total_out) {
+    if (B < 1 || B > 65535 || !dur_frames || !lengths || !plans || samples_per_frame < 1 || samples_per_frame > kPitchMaxHop)      // (one grid row per signal)
         return set_err(STS_EINVAL, "1 <= B <= 65535 signals, their durations, phoneme counts and plans, and samples_per_frame in [1, 2^20] are required");
     const int hop = samples_per_frame;
     int64_t T = 0;
@@ -156,7 +156,6 @@ static int pitch_apply_impl(int device, const float* x, const int32_t* dur_frame
         T += lengths[b];
         if (T > (1 << 24)) return set_err(STS_EINVAL, "batch too large");
     }
-    // the steps of the planned members, and every member's place in x: the geometry the engine derives from its durations
     std::vector<int64_t> steps((size_t)T);
     std::vector<const int32_t*> dur((size_t)B);
     std::vector<const int64_t*> step((size_t)B);
@@ -174,8 +173,20 @@ static int pitch_apply_impl(int device, const float* x, const int32_t* dur_frame
         t += lengths[b]; total += std::max<int64_t>(f, 1) * hop;
         if (total > ((int64_t)1 << 30)) return set_err(STS_EINVAL, "the signals must hold at most 2^30 samples in all");
     }
-    PitchTables tab;
     if (const char* bad = pitch_tables(B, lengths, dur.data(), step.data(), xoff.data(), hop, &tab)) return set_err(STS_EINVAL, bad);
+    *total_out = total;
+    return STS_OK;
+}
+
+// table_mode: -1 the shipped placement of the prototype, 0 global memory, 1 LDS; iters > 0: that many more launches between two events,
+// their mean in *ms (sts_debug_pitch_bench)
+static int pitch_apply_impl(int device, const float* x, const int32_t* dur_frames, const int32_t* lengths, int32_t B, int32_t samples_per_frame,
+                            const sts_pitch_plan* plans, int64_t* out_len, float* y, int16_t* pcm, int64_t capacity, int table_mode, int iters,
+                            float* ms) {
+    if (!x || capacity < 0) return set_err(STS_EINVAL, "1 <= B <= 65535 signals, their durations, phoneme counts and plans, and samples_per_frame in [1, 2^20] are required");
+    PitchTables tab;
+    int64_t total = 0;
+    if (const int rc = pitch_host_tables(dur_frames, lengths, B, samples_per_frame, plans, tab, &total)) return rc;
     if (out_len) for (int b = 0; b < B; b++) out_len[b] = tab.nout[b];
     if ((y || pcm) && tab.total_out > capacity) return set_err(STS_EINVAL, "pitch plan: the outputs are too small for the warped signals (out_len has their lengths)");
     if (!y && !pcm) return STS_OK;
@@ -211,6 +222,48 @@ int sts_debug_pitch_bench(int device, const float* x, const int32_t* dur_frames,
                           const sts_pitch_plan* plans, float* y, int64_t capacity, int32_t table_in_lds, int32_t iters, float* ms_out) {
     if (!y || !ms_out || iters < 1 || table_in_lds < 0 || table_in_lds > 1) return set_err(STS_EINVAL, "pitch bench: y, ms_out, iters >= 1 and table_in_lds 0 or 1 are required");
     return pitch_apply_impl(device, x, dur_frames, lengths, B, samples_per_frame, plans, nullptr, y, nullptr, capacity, table_in_lds, iters, ms_out);
+}
+
+int sts_pitch_apply_range(int device, const float* x, int64_t x_len, const int32_t* dur_frames, const int32_t* lengths, int32_t B,
+                          int32_t samples_per_frame, const sts_pitch_plan* plans, const sts_pitch_range* win, int32_t n_win, float* y,
+                          int16_t* pcm, int64_t capacity) {
+    if (!x || x_len < 1 || x_len > ((int64_t)1 << 30) || !win || n_win < 1 || n_win > 65535 || capacity < 0)
+        return set_err(STS_EINVAL, "pitch range: a signal buffer of at most 2^30 samples and 1 <= n_win <= 65535 windows are required");
+    PitchTables tab;
+    int64_t total = 0;
+    if (const int rc = pitch_host_tables(dur_frames, lengths, B, samples_per_frame, plans, tab, &total)) return rc;
+    // every window: inside the caller's buffer, its range inside [0, N'], and the staged span of the range (clipped to the utterance)
+    // inside the window -- the kernel reads nothing else, so nothing else needs to be there
+    std::vector<PsRow> rows((size_t)n_win);
+    long long ysum = 0, max_out = 0;
+    for (int i = 0; i < n_win; i++) {
+        const sts_pitch_range& w = win[i];
+        if (w.utt < 0 || w.utt >= B) return set_err(STS_EINVAL, "pitch range: a window names no utterance of the batch");
+        const PsUtt u = ps_utt(tab.words.data(), B, tab.TT, w.utt);
+        if (w.xlen < 0 || w.xlen > x_len || w.xbase < 0 || w.xbase > x_len - w.xlen || w.u0 < 0 || w.u0 > u.N - w.xlen)
+            return set_err(STS_EINVAL, "pitch range: a window lies outside the signal buffer or outside its utterance");
+        if (w.y0 < 0 || w.y1 < w.y0 || w.y1 > u.Nw) return set_err(STS_EINVAL, "pitch range: outputs outside [0, N']");
+        long long c0, c1;
+        pitch_staged(u, w.y0, w.y1, &c0, &c1);
+        if (c0 < c1 && (c0 < w.u0 || c1 > w.u0 + w.xlen)) return set_err(STS_EINVAL, "pitch range: a window does not cover the input span its outputs read");
+        rows[(size_t)i] = PsRow{w.xbase, w.u0, w.xlen, w.utt, w.y0, w.y1, ysum, w.y0, w.y1, ysum};
+        ysum += w.y1 - w.y0; max_out = std::max<long long>(max_out, w.y1 - w.y0);
+    }
+    if ((y || pcm) && ysum > capacity) return set_err(STS_EINVAL, "pitch range: the outputs are too small for the ranges");
+    if ((!y && !pcm) || ysum == 0) return STS_OK;
+    std::vector<float> proto(kPitchTableFloats);
+    pitch_table(proto.data());
+    if (hipSetDevice(device) != hipSuccess) return set_err(STS_EDEVICE, "no such device");
+    DevScratch d;
+    PitchArgs a{};
+    pitch_args_carve(a, d.up(tab.words.data(), tab.words.size()), B, tab.TT);
+    a.table = d.up(proto.data(), proto.size());
+    a.rows = (const long long*)d.up(rows.data(), rows.size());
+    a.x = d.up(x, (size_t)x_len); a.y = y ? d.out((size_t)ysum) : nullptr; a.pcm = pcm ? d.out16((size_t)ysum) : nullptr;
+    if (d.ok) pitch_range_run(a, n_win, max_out, d.st);
+    d.down(y, a.y, (size_t)ysum * 4);
+    d.down(pcm, a.pcm, (size_t)ysum * 2);
+    return d.finish() ? STS_OK : set_err(STS_EDEVICE, "the pitch range warp failed on the device");
 }
 
 int sts_join_apply(int device, const float* x, const int32_t* frames, int32_t B, int32_t samples_per_frame, const sts_join* join, float* y,

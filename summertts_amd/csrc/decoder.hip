@@ -474,13 +474,17 @@ int Engine::decode_end(RunCtx& c, const float* wave, const WinGeom& win, long Wt
         GainArgs g{};
         g.x = cur; g.y = c.bf.wave_gain; g.pcm = c.pitch ? nullptr : pcm_of(OS_GAIN);
         g.wseg = win.seg(hop, 0); g.hop = hop;
-        if (c.ss) { const StepTab t(nw, true, false, false, false); g.utt = (const int*)(c.bf.stab + t.utt); g.wtab = (const long long*)(c.bf.stab + t.rs); }
+        if (c.ss) { const StepTab t(nw, true, false, false, false, c.pitch); g.utt = (const int*)(c.bf.stab + t.utt); g.wtab = (const long long*)(c.bf.stab + t.rs); }
+        if (c.ss && c.pitch) {      // (a warped step: the RsRow describes the warped window, the decode window's u0 is the PsRow's)
+            const StepTab t(nw, true, false, false, false, true);
+            g.wtab = (const long long*)(c.bf.stab + t.ps_rows); g.wstride = (int)(sizeof(PsRow) / 8); g.wcol = 1;
+        }
         g.tseg = c.lvT.seg; g.cum = c.bt.cum; g.q = c.bt.gain_q; g.h = c.bt.gain_h;
         gain_plan_run(g, nw, (long long)maxW * hop, stream);
         cur = g.y;
     }
     int sig_scale = hop;                    // native samples per unit of dw's lengths
-    if (oc.run[OS_GAIN] && c.pitch) {
+    if (oc.run[OS_GAIN] && c.pitch && whole) {      // (a stream: run_stream_steps runs the range form on each step's windows)
         // the pitch plan's warp of every utterance (gained or not), one launch.  From here on utterance b is N'_b samples long: dw carries
         // the warped counts at scale 1 for the resampler's segments and for signal()
         PitchArgs p{};

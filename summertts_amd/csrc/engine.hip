@@ -590,7 +590,7 @@ int Engine::run_joined(int B, const int32_t* const* ids, const int32_t* n, const
     join_on = false;
     return rc;
 }
-int Engine::stream_halo() const {
+int Engine::stream_halo(bool warped) const {
     const int h = decoder_halo_frames(model);
     // the limiter reads the float signal 2H output samples beyond a chunk's edges: 2H Q / P native samples (+ 1 for the rounding of the
     // chunk's first output position), on top of the resampler's K
@@ -602,6 +602,8 @@ int Engine::stream_halo() const {
             extra += (2LL * d.H * Q + P - 1) / P + 1;
         }
     }
+    // (a stream through the pitch warp: extra is in warped samples, the warp's taps reach kPitchMaxK further -- pitch_stream.hpp)
+    if (warped) return (int)pitch_stream_halo(h, extra, model.hop_total);
     return h + (int)((extra + model.hop_total - 1) / model.hop_total);
 }
 
@@ -634,7 +636,11 @@ int Engine::run_setup(RunCtx& c) {
     // by the phoneme's ratio -- one fp32 multiply here; the plan kernel is the one of any planned run.  Forced durations are used as given
     if (pend.have_pitch) {
         if (!table_matches(pend.pitch_n, B, n)) return fail(STS_EINVAL, other_batch_message("pitch plan"));
-        if (c.ss || join_on) return fail(STS_EINVAL, "a pitch plan applies to whole-utterance calls only: streaming and joined runs refuse it");
+        // (a closed stream takes the plan through the range warp when sts_set_pitch_streaming is on: DESIGN.md 9l "Streamed")
+        const bool warp_stream = pitch_streaming && c.ss && !join_on && !c.live && c.para_k < 0;
+        if ((c.ss || join_on) && !warp_stream) return fail(STS_EINVAL, "a pitch plan applies to whole-utterance calls only: streaming and joined runs refuse it");
+        if (warp_stream && ((eq_n > 0 && eq_streaming) || (loud_mode == 1 && loud_streaming) || record_taps))
+            return fail(STS_EINVAL, "a pitch plan in a stream does not run with the streamed equaliser, streamed loudness or record taps: their state is carried across the chunk grid");
         if (!pend.have_forced) {     // (copies: the split-bf16 repeat of this call sets up again from the same pending plan)
             if (pend.have_plan) { eff_rate = pend.plan_rate; eff_fixed = pend.plan_fixed; eff_target = pend.plan_target; }
             else { eff_rate.assign((size_t)Ttot, 1.0f); eff_fixed.assign((size_t)Ttot, -1); eff_target.assign((size_t)B, 0); }
@@ -1099,7 +1105,7 @@ int Engine::wait_frame_counts(RunCtx& c) {
 
 // the one place that decides the output chain of a run (out_chain.hpp), with the limiter's design and the resampler's ratio for it
 int Engine::plan_output(RunCtx& c) {
-    c.oc = plan_out_chain(OutFacts{c.ss != nullptr, c.B, resampling(), c.gain || c.pitch, c.join, eq_n > 0, loud_mode, lim_mode != 0, record_taps, stream_direct != 0, eq_streaming, loud_streaming});
+    c.oc = plan_out_chain(OutFacts{c.ss != nullptr, c.B, resampling(), c.gain || c.pitch, c.join, eq_n > 0, loud_mode, lim_mode != 0, record_taps, stream_direct != 0, eq_streaming, loud_streaming, c.pitch && c.ss != nullptr});
     if (c.oc.run[OS_RESAMPLE]) { c.rsP = rs.P; c.rsQ = rs.Q; }
     c.eqS = eq_n;
     if (c.oc.run[OS_LIMIT] && !limiter_design(out_rate, lim_gain_db, lim_ceiling, lim_ms, &c.limd)) return fail(STS_EINVAL, "limiter: output rate outside [8000, 48000]");
@@ -1134,6 +1140,7 @@ int Engine::pitch_geometry(RunCtx& c) {
     if (tab.TT != c.pitch_rows) return fail(STS_EDEVICE, "pitch plan: the tables do not have the size the setup reserved");
     if (tab.total_out > 2000000000LL || out_count(tab.total_out) + B > 2147483647LL) return fail(STS_EINVAL, "batch produces too many samples for one call");
     c.pitch_nout = tab.nout; c.pitch_total = tab.total_out; c.pitch_max = tab.max_out;
+    if (c.ss) c.pitch_words_h = tab.words;         // (a stream: every step's geometry reads them, pitch_stream.hpp)
     // phoneme starts in the warped signal: o_i of a planned utterance (the words' o_i+1 column), frames * hop of a copied one
     last_pitch_start.assign((size_t)c.Ttot, 0);
     {
@@ -1213,7 +1220,8 @@ int Engine::run_frame_workspace(RunCtx& c) {
     int* const p_lenF = c.p_lenF; int* const d_offF = c.d_offF; int* const d_lenF = c.d_lenF;
     // ---------------- frame-level workspace.  The flow works on all Ftot frames; the decoder works on
     // "windows" of z: whole utterances normally (Wcap == Ftot), one chunk plus its two halos when streaming.
-    const int halo = c.halo = stream_halo();
+    const bool warp = c.pitch && ss;        // a stream through the pitch warp: the larger halo, a step's warped windows, the warped tables
+    const int halo = c.halo = stream_halo(warp);
     long Wcap = Ftot;
     if (ss) {    // a step decodes at most one window per utterance, each at most a chunk plus two halos: sum_b min(F_b, C + 2 halo)
         Wcap = 0;
@@ -1310,7 +1318,7 @@ int Engine::run_frame_workspace(RunCtx& c) {
         bf.eqws = oc.eqws ? A.get<char>(eq_ws_bytes(B, c.Ocap)) : nullptr;
         bf.stab = nullptr; bf.spack = nullptr; bf.gwin = bf.cond_win = nullptr;
         if (ss) {
-            bf.stab = A.get<char>(StepTab(B, c.gain, oc.eqst, oc.lst, c.join).bytes);
+            bf.stab = A.get<char>(StepTab(B, c.gain, oc.eqst, oc.lst, c.join, warp).bytes);
             if (oc.spack) bf.spack = A.get<int16_t>((size_t)c.Ocap);
             if (M.dec_type == 0 && c.ms && c.bstream) { bf.gwin = A.get<float>((size_t)M.gin * B); bf.cond_win = A.get<float>((size_t)M.up_init * B); }
         }
@@ -1339,7 +1347,10 @@ int Engine::run_frame_workspace(RunCtx& c) {
     auto layoutF_all = [&](Arena& A) {
         layoutF(A);
         // (a run with a pitch plan: behind everything else, so that every other buffer lies where it lies without it)
-        bf.wave_pitch = c.pitch ? A.get<float>((size_t)c.pitch_total) : nullptr;
+        // (a stream: the warped windows of one step, each at most pitch_stream_cap samples and never more than its utterance's N')
+        long long warped = c.pitch_total;
+        if (warp) { warped = 0; for (int b = 0; b < B; b++) warped += std::min(c.pitch_nout[(size_t)b], pitch_stream_cap((long long)ss->chunk_frames + 2 * halo, hop)); }
+        bf.wave_pitch = c.pitch ? A.get<float>((size_t)warped) : nullptr;
     };
     arenaF_.measuring = true; layoutF_all(arenaF_);
     if (!ensure(arenaF_, arenaF_.used + 4096)) return fail(STS_EDEVICE, "out of device memory (frame-level workspace)");
@@ -1747,6 +1758,8 @@ int Engine::run_stream_steps(RunCtx& c) {
     if (call.srs) { call.P = rs.P; call.Q = rs.Q; }
     if (call.slim) call.H = c.limd.H;
     call.lsrc = oc.src[OS_LOUD];
+    const bool warp = c.pitch;      // a stream through the pitch warp (run_setup admits closed streams alone)
+    if (warp) { call.pitch_words = c.pitch_words_h.data(); call.pitch_B = B; call.pitch_TT = c.pitch_rows; call.dec_halo = decoder_halo_frames(M); call.K = call.srs ? rs.K : 0; }
     std::vector<char> live(B, 1);
     if (ss->delivered) for (int b = 0; b < (joined ? 1 : B); b++) ss->delivered[b] = 0;
     d_pcm = nullptr; total_samples = 0;
@@ -1803,12 +1816,22 @@ int Engine::run_stream_steps(RunCtx& c) {
         // kernels); several: the tables, also while one window is live (an open stream too: one form whatever the live count).
         // run_decode runs the chain up to the gain plan on the windows at their absolute positions
         if (nw > 0) {
-            const int rc = B == 1 && !open ? run_decode(c, 1, st.Wtot, st.maxW, st.zoff0, st.wlen0) : run_decode(c, nw, st.Wtot, st.maxW, 0, -1);
+            const int rc = B == 1 && !open && !warp ? run_decode(c, 1, st.Wtot, st.maxW, st.zoff0, st.wlen0) : run_decode(c, nw, st.Wtot, st.maxW, 0, -1);
             if (rc != STS_OK) return rc;
         }
         StreamTail tl{nw, c.stage_out(oc.src[OS_RESAMPLE]), SegView{c.d_win + StepTab::coff(nw), c.d_win + StepTab::wlen(nw), hop, 0, 0, 0},
                       c.d_win + StepTab::pack_src(nw), c.d_win + StepTab::pack_dst(nw), t.rs, t.lim, t.eq_rows, t.loud_rows,
                       st.max_rs, st.max_out, st.etiles, st.ltiles};
+        if (warp) {         // the range warp over the step's windows; everything behind it sees window i as [yl0, yl1) of N' at its place in wave_pitch
+            PitchArgs p{};
+            pitch_args_carve(p, bt.pitch_words, B, c.pitch_rows);
+            p.x = c.gain ? bf.wave_gain : bf.wave; p.y = bf.wave_pitch; p.pcm = oc.writer == OS_GAIN ? s.dst : nullptr; p.table = d_pitch_table_;
+            p.rows = (const long long*)(bf.stab + t.ps_rows);
+            pitch_range_run(p, nw, st.max_yl, stream);
+            const int* seg = (const int*)(bf.stab + t.ps_seg);
+            tl.x = bf.wave_pitch; tl.seg = SegView{seg, seg + nw, 1, 0, 0, 0};
+            tl.pack_src = tl.pack_dst = nullptr;
+        }
         if (joined) {       // the windowed join, then the output side on the one utterance J
             const JsStep& jt = st.jt;
             JoinWinArgs j{};
@@ -1850,6 +1873,7 @@ int Engine::run_stream_steps(RunCtx& c) {
             const int b = wb[i];
             const int16_t* pcm = s.hp + st.dst[i];
             const int32_t n = (int32_t)st.n[i], j0 = (int32_t)st.j0[i];
+            if (warp && n == 0) continue;                  // (a chunk of one sample may own no warped output: not delivered)
             total_samples += st.n[i];
             if (ss->delivered) ss->delivered[b] += n;
             if (open && !para) {       // (utt = the slot; it moves on by a chunk, and retires behind its last one or at its stop)
@@ -1883,7 +1907,7 @@ int Engine::run_stream_steps(RunCtx& c) {
 int Engine::stream_host_buffers(RunCtx& c, StreamRun& s) {
     RUN_ALIASES(c)
     const size_t hp_off = (up_bytes + ((size_t)Ttot + B) * 4 + 255) & ~(size_t)255;
-    const size_t tab_only = (StepTab(B, c.gain, c.oc.eqst, c.oc.lst, c.join).bytes + 255) & ~(size_t)255;
+    const size_t tab_only = (StepTab(B, c.gain, c.oc.eqst, c.oc.lst, c.join, c.pitch).bytes + 255) & ~(size_t)255;
     const size_t tab_room = tab_only + (c.live && c.oc.lst ? ((size_t)B * 3 * 8 + 255) & ~(size_t)255 : 0);     // (an open stream: the gate's table)
     const size_t pcm_bytes = (size_t)c.Ocap * 2 + 256;
     if (!ensure_pinned(hp_off + tab_room + pcm_bytes)) return fail(STS_EDEVICE, "pinned host allocation failed");
@@ -1938,7 +1962,7 @@ void Engine::stream_tail(RunCtx& c, const StreamRun& s, const StreamTail& t) {
     }
     if (oc.run[OS_LIMIT]) { // it writes the packed chunks in place of the resampler / the pack
         LimArgs a{};
-        a.x = c.stage_out(oc.src[OS_LIMIT]);
+        a.x = c.pitch && oc.src[OS_LIMIT] == OS_GAIN ? bf.wave_pitch : c.stage_out(oc.src[OS_LIMIT]);     // (a warped step: the plan stage's output is the warp's)
         a.H = c.limd.H; a.c = c.limd.c; a.G = c.limd.G;
         a.pcm = s.dst;
         a.wtab = (const long long*)(bf.stab + t.lim);

@@ -188,7 +188,7 @@ public:
     bool resampling() const { return out_rate != kNativeRate; }
     long long out_count(long long native) const { return resampling() ? (native * rs.P + rs.Q - 1) / rs.Q : native; }   // L_out = ceil(L_in P / Q)
     int set_output_rate(int rate);
-    int stream_halo() const;           // decoder halo frames of a streaming chunk at the current rate (+ the resampler's K samples)
+    int stream_halo(bool warped = false) const;           // decoder halo frames of a streaming chunk at the current rate (+ the resampler's K samples)
     // loudness (sts_set_loudness, loudness.hip): 0 off (nothing extra runs), 1 measure every utterance of a whole-utterance call, 2 measure
     // and cast each utterance with its own gain.  Measured on the float wave at the output rate; loud_res: the last call's results, one per
     // utterance (empty after a call in mode 0, a streaming call or a failure)
@@ -402,6 +402,9 @@ public:
     // first output of every phoneme of the last run in native samples of the WARPED signal, packed like durations_h (empty: the last run
     // had no pitch plan): what sts_get_phoneme_offsets converts instead of frames * hop
     std::vector<int64_t> last_pitch_start;
+    // a pitch plan in a closed stream (sts_set_pitch_streaming; pitch_plan.hip's range form, pitch_stream.hpp): off, a stream with a plan
+    // pending is refused; on, sts_infer_ids_stream and sts_infer_ids_batch_stream run it through the range warp
+    bool pitch_streaming = false;
     // loudness in a stream (sts_set_loudness_streaming; loudness.hip's stream mode, loud_stream.hpp): off, a stream under mode 1 or 2 is
     // refused; on, mode 1 measures what each step delivers from a state carried per utterance in the frame arena (mode 2 stays refused)
     bool loud_streaming = false;

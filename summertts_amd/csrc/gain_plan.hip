@@ -61,7 +61,7 @@ __global__ __launch_bounds__(GP_THREADS) void gain_plan_kernel(GainArgs a) {
     const long long s0 = (long long)blockIdx.x * GP_TILE;
     if (s0 >= xlen) return;
     const int nt = xlen - s0 < GP_TILE ? (int)(xlen - s0) : GP_TILE;
-    const long long u0 = a.wtab ? a.wtab[5 * (long long)m] : 0;
+    const long long u0 = a.wtab ? a.wtab[(a.wstride ? a.wstride : 5) * (long long)m + a.wcol] : 0;
     const int b = a.utt ? a.utt[m] : m;
     const int toff = a.tseg.off ? a.tseg.off[b] : a.tseg.ioff, n = a.tseg.len ? a.tseg.len[b] : a.tseg.ilen;
     const int* cum = a.cum + toff;

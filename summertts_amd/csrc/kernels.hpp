@@ -505,8 +505,9 @@ struct GainArgs {
     SegView wseg;                        // member i's place in x, in frames (off == null: one member {ioff, ilen}); its scale is not read: hop is
     int hop;                             // samples per frame
     // streaming (null otherwise: member i is the whole utterance i): member i belongs to utterance utt[i] and its first sample is sample
-    // u0 of row i of the resampler's table of the step (stream_step.hpp RsRow)
-    const int* utt; const long long* wtab;
+    // u0 of row i of the resampler's table of the step (stream_step.hpp RsRow) -- word wcol of the wstride-word row i of wtab; wstride
+    // 0 means the RsRow {5, 0}.  (A step through the pitch warp names its PsRow: there the RsRow describes the warped window.)
+    const int* utt; const long long* wtab; int wstride, wcol;
     SegView tseg;                        // utterance b's phonemes in cum / q
     const int* cum;                      // inclusive cumulative frame counts inside each utterance (the durations kernel's)
     const int* q;                        // fixed-point gain per phoneme, packed like cum
@@ -535,12 +536,18 @@ struct PitchArgs {
     const long long* mem;                // [members][6] (PitchTables::words on the device; pitch_args_carve sets these six)
     const long long *oend, *pos0, *step; const double* c; const long long* K;
     const float* table;                  // the prototype (device memory)
+    // the range form only (pitch_range_run; null otherwise): one PsRow per window (pitch_stream.hpp), 10 words each.  x is then the
+    // step's float wave and y / pcm the step's buffers; of mem only N, toff and rows are read
+    const long long* rows;
 };
 void pitch_args_carve(PitchArgs& a, const long long* dev_words, int B, long long TT);
 // one launch: nmem members x ceil(max_out / 256) tiles; max_out = the longest member's N' or more.  table_in_lds: every workgroup stages
 // the prototype (64 KiB) in LDS instead of reading it from global memory
 bool pitch_table_in_lds();              // the shipped choice (sts_debug_pitch_bench times both)
 void pitch_plan_run(const PitchArgs& a, int nmem, long long max_out, bool table_in_lds, hipStream_t st);
+// the range form, one launch: nwin windows x ceil(max_out / 256) tiles; max_out = the most outputs [yl0, yl1) one window emits or more.
+// The prototype is read from global memory.  A sample is bit for bit the whole-utterance kernel's (one device function makes both)
+void pitch_range_run(const PitchArgs& a, int nwin, long long max_out, hipStream_t st);
 
 // Paragraph join (join.hip; the definition is there and in include/summertts_hip.h sts_infer_ids_joined)
 constexpr int kJoinMaxFrames = 100000, kJoinMaxH = 800;

@@ -9,6 +9,8 @@
 // it then runs on each step's windows behind the resampler from a state carried per utterance, pack never runs, and the EQ is the writer
 // when the limiter is off.  A joined stream (sts_infer_ids_joined_stream) joins
 // each step's windows into a window of the ONE signal J: pack never runs, and the join is the writer when nothing runs behind it.
+// A stream through the pitch warp (the fact pitch_stream, sts_set_pitch_streaming) runs the range warp in the gain stage on each step's
+// windows: pack never runs and nothing is downloaded in place -- the warp is the writer when nothing runs behind it.
 #pragma once
 
 namespace sts {
@@ -21,6 +23,7 @@ struct OutFacts {
     bool taps, stream_direct;
     bool eq_stream = false;     // (behind the others, which older callers initialise in order) a stream runs the EQ: sts_set_eq_streaming
     bool loud_stream = false;   // (behind that one) a stream under loudness mode 1 measures: sts_set_loudness_streaming
+    bool pitch_stream = false;  // (behind that one) a stream through the pitch warp (sts_set_pitch_streaming): the range warp packs its chunks
 };
 
 struct OutChain {
@@ -40,7 +43,7 @@ inline OutChain plan_out_chain(const OutFacts& f) {
     OutChain p{};
     const bool whole = !f.stream, eqs = f.stream && f.eq && f.eq_stream, lds = f.stream && f.loud_stream && f.loud_mode == 1;
     p.run[OS_TAIL] = true; p.run[OS_GAIN] = f.gain; p.run[OS_JOIN] = f.join; p.run[OS_RESAMPLE] = f.resample;
-    p.run[OS_PACK] = f.stream && !f.join && !f.resample && !f.limit && !eqs && (f.B > 1 || f.stream_direct);
+    p.run[OS_PACK] = f.stream && !f.join && !f.resample && !f.limit && !eqs && !f.pitch_stream && (f.B > 1 || f.stream_direct);
     p.run[OS_EQ] = f.eq && (whole || eqs); p.run[OS_LOUD] = (f.loud_mode != 0 && whole) || lds; p.run[OS_LIMIT] = f.limit;
     const bool normalise = p.run[OS_LOUD] && f.loud_mode == 2;
     int cur = -1;           // the current float signal
@@ -58,7 +61,7 @@ inline OutChain plan_out_chain(const OutFacts& f) {
     p.pcm_nat = p.writer != OS_TAIL; p.pcm_rs = p.run[OS_RESAMPLE] && p.writer != OS_RESAMPLE;
     p.loud_cast = p.writer == OS_LOUD; p.loud_no_clamp = p.run[OS_LIMIT]; p.lim_gloud = normalise;
     p.lws = p.run[OS_LOUD] && whole; p.limws = p.run[OS_LIMIT] && whole; p.spack = p.run[OS_PACK] && f.B > 1; p.stab = f.stream;
-    p.chunk_in_place = f.stream && !f.join && !p.run[OS_RESAMPLE] && !p.run[OS_LIMIT] && !p.run[OS_PACK] && !eqs;
+    p.chunk_in_place = f.stream && !f.join && !p.run[OS_RESAMPLE] && !p.run[OS_LIMIT] && !p.run[OS_PACK] && !eqs && !f.pitch_stream;
     p.eqws = p.run[OS_EQ] && whole; p.eqst = eqs; p.lst = lds;
     return p;
 }

@@ -11,8 +11,8 @@
 // counts o_i+1 (a phoneme that emits nothing can never be the answer).  The tile's input span [n0_first - 51 + 1, n0_last + 51] (the
 // widest K: a later output of the tile may reach further back than the first) -- consecutive outputs are at most step(+600) < 1.4143
 // samples apart, whichever phonemes they belong to, so at most PP_TILE 1.4143 + 2 * 52 + 2 floats -- is staged in LDS with zeros outside
-// the utterance.  A lane runs PP_PER outputs, PP_THREADS apart (coalesced stores), their tap loops interleaved; steps change inside a
-// tile, so each output's loop ends at its own 2K.  The prototype is read from global memory (64 KiB, L2-resident) or staged in LDS.
+// the utterance.  A lane runs one output (coalesced stores); steps change inside a tile, so each output's loop ends at its own 2K.
+// The prototype is read from global memory (64 KiB, L2-resident) or staged in LDS.
 // Measured (one utterance of 185 k samples, microseconds per launch, LDS / global): tiles of 1024 outputs 48.8 / 62.6, of 512
 // 29.3 / 34.5, of 256 30.2 / 22.6 -- the work is latency-bound, so what counts is workgroups in flight, and a workgroup that keeps 2 KiB of
 // LDS instead of 66 runs eight to a CU: 256 outputs per workgroup, one per lane, the prototype from L2.  A member without a plan is copied.
@@ -28,7 +28,7 @@
 
 namespace sts {
 
-constexpr int PP_THREADS = 256, PP_PER = 1, PP_TILE = PP_THREADS * PP_PER;
+constexpr int PP_THREADS = 256, PP_TILE = PP_THREADS;    // one output per lane
 constexpr bool kPitchTableLds = false; // where the prototype is read from (the measurement above)
 constexpr int PP_LDS = 480;         // >= (PP_TILE - 1) step(+600) / 2^32 + 2 kPitchMaxK + 2 = 464.7
 
@@ -114,6 +114,29 @@ __device__ __forceinline__ PpOut pp_locate(const PitchArgs& a, long long toff, i
 }
 }  // namespace
 
+// output j of a member whose staged input span starts at sample s0 in xs: the tap loop of the definition, m ascending, float64.  The
+// whole-utterance kernel and the range kernel both run this one function, so a sample does not depend on which of them made it.
+__device__ __forceinline__ float pp_output(const PitchArgs& a, long long toff, int n, long long j, const float* xs, long long s0, const float* h0) {
+    const PpOut p = pp_locate(a, toff, n, j);
+    const float* const xv = xs + (p.n0 - p.K + 1 - s0);               // taps [0, 2K) lie inside the span: n0 ascends with j and K <= kPitchMaxK
+    const double f = p.f, c = p.c;
+    const int T = 2 * p.K, K1 = p.K - 1;
+    double num = 0.0, den = 0.0;
+    for (int m = 0; m < T; m++) {
+        const double dd = f + (double)(K1 - m);
+        const double t = 512.0 * (c * fabs(dd));
+        const int k = (int)t;                                         // t >= 0: floor
+        double g = 0.0;
+        if (k < kPitchProto) {
+            const double ha = (double)h0[k], hb = (double)h0[k + 1];
+            g = ha + (t - (double)k) * (hb - ha);
+        }
+        num += g * (double)xv[m];
+        den += g;
+    }
+    return (float)(num / den);
+}
+
 template <bool TAB_LDS>
 __global__ __launch_bounds__(PP_THREADS) void pitch_plan_kernel(PitchArgs a) {
     __shared__ float xs[PP_LDS];
@@ -125,15 +148,12 @@ __global__ __launch_bounds__(PP_THREADS) void pitch_plan_kernel(PitchArgs a) {
     const long long t0 = (long long)blockIdx.x * PP_TILE;
     if (t0 >= nout) return;
     const long long t1 = t0 + PP_TILE < nout ? t0 + PP_TILE : nout;
+    const long long j = t0 + tid;
     if (n == 0) {                   // no plan: y = x, bit for bit (nout == N)
-#pragma unroll
-        for (int r = 0; r < PP_PER; r++) {
-            const long long j = t0 + r * PP_THREADS + tid;
-            if (j < t1) {
-                const float v = a.x[xoff + j];
-                if (a.y) a.y[yoff + j] = v;
-                if (a.pcm) a.pcm[yoff + j] = pcm_cast(v);
-            }
+        if (j < t1) {
+            const float v = a.x[xoff + j];
+            if (a.y) a.y[yoff + j] = v;
+            if (a.pcm) a.pcm[yoff + j] = pcm_cast(v);
         }
         return;
     }
@@ -149,44 +169,47 @@ __global__ __launch_bounds__(PP_THREADS) void pitch_plan_kernel(PitchArgs a) {
     if (TAB_LDS)
         for (int i = tid; i < kPitchTableFloats; i += PP_THREADS) hs[i] = a.table[i];
     __syncthreads();
-    const float* const h0 = TAB_LDS ? hs : a.table;
-    const float* xv[PP_PER]; double f[PP_PER], c[PP_PER], num[PP_PER], den[PP_PER]; int T[PP_PER], K1[PP_PER];
-    int Tmax = 0;
-#pragma unroll
-    for (int r = 0; r < PP_PER; r++) {
-        long long j = t0 + r * PP_THREADS + tid;
-        if (j >= t1) j = t0;                                          // (past the tile: computes output t0 again, stores nothing)
-        const PpOut p = pp_locate(a, toff, n, j);
-        xv[r] = xs + (p.n0 - p.K + 1 - s0);                           // taps [0, 2K) lie inside [0, span): n0 ascends with j and K <= kPitchMaxK
-        f[r] = p.f; c[r] = p.c; T[r] = 2 * p.K; K1[r] = p.K - 1;
-        num[r] = 0.0; den[r] = 0.0;
-        Tmax = T[r] > Tmax ? T[r] : Tmax;
+    const float y = pp_output(a, toff, n, j < t1 ? j : t0, xs, s0, TAB_LDS ? hs : a.table);      // (past the tile: output t0 again, stored nowhere)
+    if (j < t1) {
+        if (a.y) a.y[yoff + j] = y;
+        if (a.pcm) a.pcm[yoff + j] = pcm_cast(y);
     }
-    for (int m = 0; m < Tmax; m++) {
-#pragma unroll
-        for (int r = 0; r < PP_PER; r++) {
-            if (m < T[r]) {
-                const double dd = f[r] + (double)(K1[r] - m);
-                const double t = 512.0 * (c[r] * fabs(dd));
-                const int k = (int)t;                                 // t >= 0: floor
-                double g = 0.0;
-                if (k < kPitchProto) {
-                    const double ha = (double)h0[k], hb = (double)h0[k + 1];
-                    g = ha + (t - (double)k) * (hb - ha);
-                }
-                num[r] += g * (double)xv[r][m];
-                den[r] += g;
-            }
+}
+
+// The range form (a stream through the warp, sts_pitch_apply_range): one workgroup per (tile of PP_TILE outputs, window), the tiles
+// anchored at the window's yl0.  Window w reads its PsRow (pitch_stream.hpp): x[xbase ..) holds the samples [u0, u0 + xlen) of member
+// `mem`; a staged position outside the utterance OR outside the window is 0 and is never read (the geometry keeps every tap that counts
+// inside the window).  The float outputs [yl0, yl1) go to y[ybase ..); of them [y0, y1) go as int16 to pcm[pbase ..) when a.pcm is set.
+__global__ __launch_bounds__(PP_THREADS) void pitch_range_kernel(PitchArgs a) {
+    __shared__ float xs[PP_LDS];
+    const int tid = threadIdx.x;
+    const long long* row = a.rows + 10 * (long long)blockIdx.y;
+    const long long xbase = row[0], u0 = row[1], u1 = row[1] + row[2], yl0 = row[4], yl1 = row[5], ybase = row[6], y0 = row[7], y1 = row[8], pbase = row[9];
+    const long long* mem = a.mem + 6 * row[3];
+    const long long N = mem[1], toff = mem[4];
+    const int n = (int)mem[5];
+    const long long t0 = yl0 + (long long)blockIdx.x * PP_TILE;
+    if (t0 >= yl1) return;
+    const long long t1 = t0 + PP_TILE < yl1 ? t0 + PP_TILE : yl1;
+    const long long j = t0 + tid;
+    float y;
+    if (n == 0) {                   // no plan: y = x, bit for bit
+        y = (j < t1 && j >= u0 && j < u1 && j < N) ? a.x[xbase + (j - u0)] : 0.f;
+    } else {
+        const PpOut first = pp_locate(a, toff, n, t0), last = pp_locate(a, toff, n, t1 - 1);
+        const long long s0 = first.n0 - kPitchMaxK + 1, s1 = last.n0 + kPitchMaxK;
+        const int span = (int)(s1 - s0 + 1);
+        if (span > PP_LDS) return;  // (never, as above)
+        for (int i = tid; i < span; i += PP_THREADS) {
+            const long long p = s0 + i;
+            xs[i] = (p >= 0 && p < N && p >= u0 && p < u1) ? a.x[xbase + (p - u0)] : 0.f;
         }
+        __syncthreads();
+        y = pp_output(a, toff, n, j < t1 ? j : t0, xs, s0, a.table);
     }
-#pragma unroll
-    for (int r = 0; r < PP_PER; r++) {
-        const long long j = t0 + r * PP_THREADS + tid;
-        if (j < t1) {
-            const float y = (float)(num[r] / den[r]);
-            if (a.y) a.y[yoff + j] = y;
-            if (a.pcm) a.pcm[yoff + j] = pcm_cast(y);
-        }
+    if (j < t1) {
+        if (a.y) a.y[ybase + (j - yl0)] = y;
+        if (a.pcm && j >= y0 && j < y1) a.pcm[pbase + (j - y0)] = pcm_cast(y);
     }
 }
 
@@ -197,6 +220,11 @@ void pitch_plan_run(const PitchArgs& a, int nmem, long long max_out, bool table_
     const dim3 grid((unsigned)((max_out + PP_TILE - 1) / PP_TILE), nmem);
     if (table_in_lds) hipLaunchKernelGGL(pitch_plan_kernel<true>, grid, dim3(PP_THREADS), 0, st, a);
     else hipLaunchKernelGGL(pitch_plan_kernel<false>, grid, dim3(PP_THREADS), 0, st, a);
+}
+
+void pitch_range_run(const PitchArgs& a, int nwin, long long max_out, hipStream_t st) {
+    if (nwin <= 0 || max_out <= 0) return;
+    hipLaunchKernelGGL(pitch_range_kernel, dim3((unsigned)((max_out + PP_TILE - 1) / PP_TILE), nwin), dim3(PP_THREADS), 0, st, a);
 }
 
 }  // namespace sts

@@ -86,6 +86,7 @@ struct Engine::RunCtx {
     // memo.  Made by pitch_geometry when the durations are on the host: pitch_rows (the tables' per-phoneme length), every utterance's
     // warped sample count, their sum and maximum
     bool pitch = false; long long pitch_rows = 0, pitch_total = 0, pitch_max = 0; std::vector<long long> pitch_nout;
+    std::vector<long long> pitch_words_h;     // a stream through the warp: the tables on the host, for every step's geometry (pitch_stream.hpp)
     bool mix = false;               // this run blends speakers (sts_set_speaker_mix): bt.g comes from speaker_blend; never launched ahead, never in the memo
     std::vector<Engine::Noise> nz; bool any_ns = false, any_nsw = false;   // per-utterance sampling noise (engine.hpp Noise), which of the two is used
     std::vector<unsigned long long> req_keys; std::vector<long> predF;      // launch-ahead memo: per-utterance request hashes, remembered frame counts (empty: not all known)

@@ -10,7 +10,9 @@
 //   a plain stream, from the next 8-byte boundary each: the EQ's rows, EqsRow [nw]; loudness' rows, LdsRow [nw]
 //   a joined stream, from the next 8-byte boundary: the ONE window of J for the resampler (RsRow) and the limiter (LimRow), the windowed
 //   join's rows, JsRow [nw], the one EqsRow of J, the one LdsRow of J
-// A section exists only in a run that reads it (gain, eq, loud); the sections in front of it lie where they lie without it.
+//   a stream through the pitch warp (pitch_stream.hpp), from the next 8-byte boundary: the range warp's rows, PsRow [nw]; behind them the
+//   windows' places in the step's warped float buffer, ints [offset nw | length nw] (the SegView at scale 1 of everything behind the warp)
+// A section exists only in a run that reads it (gain, eq, loud, pitch); the sections in front of it lie where they lie without it.
 #pragma once
 #include <stddef.h>
 #include <string.h>
@@ -20,6 +22,7 @@
 #include "live_stream.hpp"
 #include "loud_stream.hpp"
 #include "out_chain.hpp"
+#include "pitch_stream.hpp"
 
 namespace sts {
 
@@ -40,6 +43,8 @@ struct StepTab {
     size_t rs, lim, utt;            // every stream
     size_t j_rs, j_lim, j_rows;     // a joined stream only (0 otherwise)
     size_t eq_rows, loud_rows;      // nw rows each; a joined stream: one row each
+    size_t ps_rows = 0, ps_seg = 0; // a warped stream only (0 otherwise): PsRow [nw], then ints [offset nw | length nw]
+    bool pitch = false;
     size_t bytes;
     static size_t up8(size_t v) { return (v + 7) & ~(size_t)7; }
     // the int block's columns, in ints from the table's start
@@ -51,7 +56,7 @@ struct StepTab {
     static int pack_dst(int nw) { return 5 * nw; }
     static int ints(int nw) { return 6 * nw + 1; }
 
-    StepTab(int nw_, bool gain_, bool eq_, bool loud_, bool joined_) : nw(nw_), gain(gain_), eq(eq_), loud(loud_), joined(joined_) {
+    StepTab(int nw_, bool gain_, bool eq_, bool loud_, bool joined_, bool pitch_ = false) : nw(nw_), gain(gain_), eq(eq_), loud(loud_), joined(joined_), pitch(pitch_) {
         const size_t n = (size_t)nw;
         rs = up8((size_t)ints(nw) * 4);
         lim = rs + n * sizeof(RsRow);
@@ -69,6 +74,7 @@ struct StepTab {
             loud_rows = up8(end);
             bytes = loud ? loud_rows + n * sizeof(LdsRow) : end;
         }
+        if (pitch) { ps_rows = up8(bytes); ps_seg = ps_rows + n * sizeof(PsRow); bytes = ps_seg + 2 * n * 4; }
     }
 };
 
@@ -78,6 +84,9 @@ struct StepCall {
     long C = 1, halo = 0; int hop = 1; long long P = 1, Q = 1, H = 0;
     bool srs = false, slim = false, seq = false, sld = false, gain = false, mix = false;
     int lsrc = -1;
+    // a stream through the pitch warp (null otherwise): the host copy of the warp's tables over the call's B utterances, the decoder's own
+    // halo in frames (`halo` is pitch_stream_halo's) and the resampler's reach K (0: off)
+    const long long* pitch_words = nullptr; int pitch_B = 0; long long pitch_TT = 0; long dec_halo = 0; long long K = 0;
 };
 // one window of a plain step: utterance b of F frames at z offset `zoff` speaks as `sid`; its chunk starts at frame f0.  tab: the row of
 // the run's per-utterance tables it reads (the gain kernel's utt[m]; with `mix` the column of the conditioning table in the sid column)
@@ -92,11 +101,12 @@ struct StepOut {
     int zoff0 = 0, wlen0 = 0, src0 = 0;                 // window 0 by value: its place in z, its frames, its pack source
     long long max_rs = 0, max_out = 0, etiles = 1, ltiles = 1;      // launch dimensions of the output side
     long long dsum = 0;                                 // samples of the step's chunks, packed
+    long long ysum = 0, max_yl = 0;                     // a warped step: the warped samples of its windows in all, the most of one
     std::vector<long long> j0, n, dst;                  // each delivered chunk: first output, count, offset in the packed buffer
     JsStep jt; std::vector<JsRow> jrows;                // a joined step: its geometry and the join's rows
     void begin(const StepTab& t, int chunks) {
         tab = t; nw = t.nw; Wtot = 0; maxW = 0; zoff0 = wlen0 = src0 = 0;
-        max_rs = max_out = 0; etiles = ltiles = 1; dsum = 0;
+        max_rs = max_out = 0; etiles = ltiles = 1; dsum = 0; ysum = max_yl = 0;
         j0.assign((size_t)chunks, 0); n.assign((size_t)chunks, 0); dst.assign((size_t)chunks, 0);
     }
 };
@@ -118,7 +128,9 @@ static inline void step_put_window(char* ht, const StepTab& t, int i, int b, int
 // windows packed in the order given.  The resampler writes each window's widened outputs [jl0, jl1) back to back (rsum) when the
 // limiter follows, else its kept ones [j0, j1) (dsum); the EQ reads the resampler's outputs (native rate: the decode window) and writes
 // what the limiter reads; loudness reads the stage the chain names.  Null, or why a row cannot run.
+static inline const char* step_build_warped(const StepCall& c, const StepWin* w, int nw, char* ht, StepOut& o);
 static inline const char* step_build(const StepCall& c, const StepWin* w, int nw, EqsTrack& eqt, LdsTrack& ldt, char* ht, StepOut& o) {
+    if (c.pitch_words) return step_build_warped(c, w, nw, ht, o);
     const StepTab t(nw, c.gain, c.seq, c.sld, false);
     o.begin(t, nw);
     const long long hop = c.hop;
@@ -158,6 +170,46 @@ static inline const char* step_build(const StepCall& c, const StepWin* w, int nw
     }
     ((int*)ht)[StepTab::pack_dst(nw) + nw] = (int)dsum;
     o.Wtot = Wtot; o.dsum = dsum;
+    return nullptr;
+}
+
+// A step of a closed stream through the pitch warp: window i decodes the frames pitch_window gives (the larger halo), the range warp turns
+// it into the warped samples [yl0, yl1) of utterance b at ysum in the step's warped buffer, and the resampler's and the limiter's rows
+// describe THAT window of an utterance of N' samples.  At the native rate without the limiter the warp writes the kept [y0, y1) itself.
+// The EQ's and loudness' stream modes do not run (the engine refuses them with a plan).  A chunk may own no output (C hop = 1): n = 0.
+static inline const char* step_build_warped(const StepCall& c, const StepWin* w, int nw, char* ht, StepOut& o) {
+    if (c.seq || c.sld) return "pitch stream: the streamed EQ and streamed loudness do not run behind the warp";
+    const StepTab t(nw, c.gain, false, false, false, true);
+    o.begin(t, nw);
+    const long long hop = c.hop;
+    long long rsum = 0, dsum = 0, ysum = 0;
+    long Wtot = 0;
+    int* const seg = (int*)(ht + t.ps_seg);
+    for (int i = 0; i < nw; i++) {
+        const StepWin& u = w[i];
+        if (u.b < 0 || u.b >= c.pitch_B) return "pitch stream: a window of an utterance the warp's tables do not hold";
+        const PsUtt pu = ps_utt(c.pitch_words, c.pitch_B, c.pitch_TT, u.b);
+        if (pu.N != (long long)u.F * hop) return "pitch stream: the warp's tables were laid out for another frame count";
+        const PsWin g = pitch_window(pu, u.F, u.f0, c.C, c.halo, c.hop, c.P, c.Q, c.H, c.srs ? c.K : 0);
+        if (const char* bad = pitch_window_check(pu, g, u.F, c.hop, c.dec_halo)) return bad;
+        const int row = u.tab >= 0 ? u.tab : u.b;
+        const long wlen = g.w1 - g.w0;
+        const long long nrs = g.jl1 - g.jl0, nout = g.j1 - g.j0, nyl = g.yl1 - g.yl0;
+        if (ysum + nyl > 0x7fffffffll) return "pitch stream: a step's warped samples exceed 2^31";
+        step_put_window(ht, t, i, row, u.zoff + (int)g.w0, (int)Wtot, (int)wlen, c.mix ? row : u.sid, 0, (int)dsum,
+                        RsRow{g.yl0, g.Nw, g.jl0, g.jl1, c.slim ? rsum : dsum},
+                        LimRow{c.srs ? rsum : ysum, c.srs ? g.jl0 : g.yl0, c.srs ? nrs : nyl, g.Nout, g.j0, g.j1, dsum});
+        step_put(ht, t.ps_rows, i, PsRow{Wtot * hop, g.w0 * hop, wlen * hop, u.b, g.yl0, g.yl1, ysum, g.y0, g.y1, dsum});
+        seg[i] = (int)ysum; seg[nw + i] = (int)nyl;
+        if (i == 0) { o.zoff0 = u.zoff + (int)g.w0; o.wlen0 = (int)wlen; o.src0 = 0; }
+        o.j0[(size_t)i] = g.j0; o.n[(size_t)i] = nout; o.dst[(size_t)i] = dsum;
+        rsum += nrs; o.max_rs = std::max(o.max_rs, nrs);
+        dsum += nout; o.max_out = std::max(o.max_out, nout);
+        ysum += nyl; o.max_yl = std::max(o.max_yl, nyl);
+        Wtot += wlen; o.maxW = std::max(o.maxW, (int)wlen);
+    }
+    ((int*)ht)[StepTab::pack_dst(nw) + nw] = (int)dsum;
+    o.Wtot = Wtot; o.dsum = dsum; o.ysum = ysum;
     return nullptr;
 }
 

@@ -336,6 +336,10 @@ def load_library() -> C.CDLL:
     lib.sts_pitch_table.argtypes = [C.c_void_p, C.c_int64]
     lib.sts_pitch_apply.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
                                     C.c_void_p, C.c_int64]
+    lib.sts_set_pitch_streaming.argtypes = [C.c_void_p, C.c_int]
+    lib.sts_pitch_chunk_starts.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int64]
+    lib.sts_pitch_apply_range.argtypes = [C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
+                                          C.c_int32, C.c_void_p, C.c_void_p, C.c_int64]
     lib.sts_debug_pitch_bench.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64,
                                           C.c_int32, C.c_int32, C.POINTER(C.c_float)]
     lib.sts_pool_submit_gain.restype = C.c_int64
@@ -430,6 +434,7 @@ EXPORTED_SYMBOLS = [
     "sts_multi_set_gain_plan",
     "sts_set_pitch_plan", "sts_pool_submit_pitch", "sts_multi_set_pitch_plan",
     "sts_debug_pitch_bench", "sts_pitch_plan_check", "sts_pitch_design", "sts_pitch_layout", "sts_pitch_table", "sts_pitch_apply",
+    "sts_set_pitch_streaming", "sts_pitch_chunk_starts", "sts_pitch_apply_range",
     "sts_debug_spline_step", "sts_debug_attention", "sts_debug_layer_norm", "sts_debug_resblock_layer", "sts_debug_col_layer",
     "sts_join_check", "sts_join_layout", "sts_join_apply", "sts_infer_ids_joined", "sts_get_join_offsets", "sts_pool_submit_joined",
     "sts_infer_ids_joined_stream", "sts_join_apply_range",
@@ -658,6 +663,50 @@ def pitch_apply(signals, durations, plans, samples_per_frame: int, device: int =
     y = np.zeros(max(total, 1), np.float32)
     pcm = np.zeros(max(total, 1), np.int16)
     _check(lib, lib.sts_pitch_apply(*args, lens.ctypes.data, y.ctypes.data, pcm.ctypes.data, total))
+    return _split(y, lens), _split(pcm, lens)
+
+
+class PitchRange(C.Structure):
+    """``sts_pitch_range``: one window of ``sts_pitch_apply_range``."""
+    _fields_ = [("utt", C.c_int32), ("xbase", C.c_int64), ("u0", C.c_int64), ("xlen", C.c_int64), ("y0", C.c_int64), ("y1", C.c_int64)]
+
+
+def pitch_chunk_starts(durations, step, samples_per_frame: int, chunk_frames: int) -> np.ndarray:
+    """Which warped outputs every chunk of a stream through the pitch warp starts at (sts_pitch_chunk_starts; host only): frames per
+    phoneme, the Q32 steps of ``pitch_design`` (None: an utterance without a plan) -> int64 [chunks + 1]: Y(k C) for every chunk of
+    ``chunk_frames`` frames, then the warped length N'."""
+    lib = load_library()
+    d = np.ascontiguousarray(durations, dtype=np.int32).ravel()
+    s = None if step is None else np.ascontiguousarray(step, dtype=np.int64).ravel()
+    if s is not None and s.size != d.size:
+        raise ValueError("one step per phoneme")
+    args = (d.ctypes.data, None if s is None else s.ctypes.data, d.size, int(samples_per_frame), int(chunk_frames))
+    n = int(lib.sts_pitch_chunk_starts(*args, None, 0))
+    _check(lib, min(n, 0))
+    out = np.zeros(n + 1, np.int64)
+    _check(lib, min(int(lib.sts_pitch_chunk_starts(*args, out.ctypes.data, out.size)), 0))
+    return out
+
+
+def pitch_apply_range(x, durations, plans, samples_per_frame: int, windows, device: int = 0):
+    """The range form of the pitch-plan kernel on caller data (sts_pitch_apply_range): ``x`` one float buffer; ``durations`` and
+    ``plans`` the batch as ``pitch_apply`` takes it; ``windows`` a list of ``(utt, xbase, u0, xlen, y0, y1)`` -- the native samples
+    ``[u0, u0 + xlen)`` of utterance ``utt`` stand at ``x[xbase:xbase + xlen]``, and the warped outputs ``[y0, y1)`` are asked for ->
+    (y, pcm): lists with one float32 / int16 array per window.  Raises StsError when a window does not cover what its outputs read."""
+    lib = load_library()
+    ds = [np.ascontiguousarray(d, dtype=np.int32).ravel() for d in durations]
+    xx = np.ascontiguousarray(x, dtype=np.float32).ravel()
+    nn, arr, keep = _pitch_plans([d.size for d in ds], plans)
+    d = np.concatenate(ds) if ds and sum(v.size for v in ds) else np.zeros(1, np.int32)
+    win = (PitchRange * max(len(windows), 1))()
+    for i, w in enumerate(windows):
+        win[i] = PitchRange(*[int(v) for v in w])
+    lens = np.asarray([max(0, int(w[5]) - int(w[4])) for w in windows], np.int64)
+    total = int(lens.sum())
+    y = np.zeros(max(total, 1), np.float32)
+    pcm = np.zeros(max(total, 1), np.int16)
+    _check(lib, lib.sts_pitch_apply_range(int(device), xx.ctypes.data, xx.size, d.ctypes.data, nn.ctypes.data, len(ds), int(samples_per_frame),
+                                          C.cast(arr, C.c_void_p), C.cast(win, C.c_void_p), len(windows), y.ctypes.data, pcm.ctypes.data, total))
     return _split(y, lens), _split(pcm, lens)
 
 
@@ -1627,6 +1676,12 @@ class Synthesizer(_TableSetters):
         """Let streaming calls run while an equaliser is set (sts_set_eq_streaming): each step continues the filter from a state carried per
         utterance, and the concatenated chunks are the whole call's PCM for every chunk size.  Off by default; persists until changed."""
         _check(self.lib, self.lib.sts_set_eq_streaming(self.h, 1 if enable else 0))
+
+    def set_pitch_streaming(self, enable: bool = True):
+        """Let ``infer_ids_stream`` and ``infer_batch_stream`` run with a pitch plan pending (sts_set_pitch_streaming): every step warps its
+        decode windows, and the concatenated chunks are the whole call's PCM with the same plan for every chunk size.  Off by default;
+        persists until changed.  Open streams, joined runs, paragraphs and the pool's streams still refuse a plan."""
+        _check(self.lib, self.lib.sts_set_pitch_streaming(self.h, 1 if enable else 0))
 
     def get_eq_streaming(self) -> bool:
         """The switch set by ``set_eq_streaming``."""
